@@ -12,8 +12,13 @@ sharded over ranks (u -> rank u mod N), weights are broadcast once from rank 0 o
 RCCL, there is no data-path collective: scaling is weak.
 
 Rank 0 prints ONE JSON line with the contract keys plus "roofline" (the affine-GEMM
-kernel, timed live with HIP events on the stream it runs on) and "cpu_baseline"
-(the oracle port timed on this box's host cores, bounded sample, N = 1 only).
+kernel, timed live with HIP events on the stream it runs on).  A plain run does nothing
+else: set-up, warm-up, the K timed steps, the line.  --full adds the supplementary legs
+(other precision and softmax modes, host end-points, BASELINE configs[1] / configs[4],
+"cpu_baseline": the oracle port timed on this box's host cores, bounded sample, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's log-likelihoods, a
+fixed sample of rows when the whole batch would exceed the cap) as DIR/*.npy.
 """
 import argparse
 import ctypes
@@ -362,6 +367,34 @@ def cpu_identity():
             "affinity_cores": len(os.sched_getaffinity(0))}
 
 
+DUMP_ROW_BYTES = 48 << 20      # log-likelihood rows of --dump-outputs; with the row index well under 64 MB
+
+
+def dump_rows(frames_per_utt, num_pdfs, budget=DUMP_ROW_BYTES, seed=0):
+    """The (utterance, frame) pairs --dump-outputs writes, in batch order: every frame of the batch when its
+    float32 rows fit in `budget` bytes, else a sample without replacement drawn with a fixed seed."""
+    offs = np.concatenate([[0], np.cumsum(frames_per_utt, dtype=np.int64)])
+    total = int(offs[-1])
+    n = min(total, budget // (4 * num_pdfs))
+    pick = np.arange(total) if n == total else np.sort(np.random.default_rng(seed).choice(total, n, replace=False))
+    utt = np.searchsorted(offs, pick, side="right") - 1
+    return utt, pick - offs[utt]
+
+
+def dump_outputs(out_dir, scorer, num_pdfs):
+    """What a caller of the timed path receives from its last step -- every utterance's log-likelihoods
+    (pk_decodable_t.log_prob, [frames][num_pdfs]) -- as DIR/log_likelihoods.npy (float32 rows) and
+    DIR/log_likelihoods_rows.npy (float64 [rows][2]: utterance, frame of each row)."""
+    utt, frame = dump_rows([scorer.num_frames(u) for u in range(scorer.num_utts())], num_pdfs)
+    rows = np.empty((len(utt), num_pdfs), dtype=np.float32)
+    for u in np.unique(utt):
+        sel = np.nonzero(utt == u)[0]
+        rows[sel] = scorer.fetch(int(u)).log_prob()[frame[sel]]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "log_likelihoods.npy"), rows)
+    np.save(os.path.join(out_dir, "log_likelihoods_rows.npy"), np.stack([utt, frame], axis=1).astype(np.float64))
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -400,7 +433,7 @@ def self_launch(gpus, argv):
     return child.wait()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -416,6 +449,14 @@ def main():
                          "operations one by one -- with f32 the whole path is then bit-identical to the oracle restatement of the CPU path")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo = rehearsal of the multi-rank flow, e.g. two ranks on ONE GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the supplementary legs as well: the other precision mode and the "
+                         "reference softmax, the host end-points, BASELINE configs[1] / configs[4], the CPU baselines "
+                         "(each can be left out again with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the log-likelihoods of the last timed step (rank 0; a seeded sample of rows past %d MB) "
+                         "to DIR/log_likelihoods.npy, their (utterance, frame) to DIR/log_likelihoods_rows.npy"
+                         % (DUMP_ROW_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-precision", action="store_true",
                     help="skip the supplementary run in the other precision mode")
@@ -428,7 +469,14 @@ def main():
     ap.add_argument("--ragged", action="store_true",
                     help="utterance lengths U[2 s, 20 s] (seeded) instead of equal lengths; ranks take the shards "
                          "pkdist.partition_by_frames gives them (longest-first greedy on the frame count)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -585,10 +633,12 @@ def main():
     # every rank's own rate over ITS barrier-to-barrier time (stragglers show as a low minimum)
     rank_lo, rank_hi = pkdist.min_max_over_ranks(frames_per_step * args.steps / timed_steps.own_elapsed, cdev)
     total_frames = pkdist.sum_over_ranks(frames_per_step, cdev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bs, am.num_pdfs())
 
     # ---- supplementary: the same workload in the other precision mode (same K, W)
     other = None
-    if not args.no_other_precision:
+    if args.full and not args.no_other_precision:
         other_prec = "f16x3" if args.precision == "f32" else "f32"
         bs.close()
         am2 = pk.AcousticModel(layers, prior, L, R, precision=other_prec).set_softmax(args.softmax)
@@ -609,7 +659,7 @@ def main():
 
     # ---- supplementary: the same workload with the reference's softmax arithmetic (bit-identical path)
     ref_softmax = None
-    if not args.no_other_precision and args.softmax == "stable" and args.precision == "f32":
+    if args.full and not args.no_other_precision and args.softmax == "stable" and args.precision == "f32":
         am.set_softmax("reference")
         bs3 = pk.BatchScorer(am, synth.global_cmvn_stats(), nutts, int(sum(ns)))
         bs3.set_waves_device(pcm.data_ptr(), ns, keep_alive=pcm)
@@ -702,7 +752,7 @@ def main():
                                                    "(written sc1, read back by the row tile's owner) and writes the log-likelihoods: "
                                                    "~9.6 GB of the step's traffic is the fused tail, not operand re-reads")
             out["roofline"]["algorithmic_bytes_per_launch"] = alg / gemm_launches
-        if world == 1 and not args.no_host_endpoints and args.precision == "f32":
+        if args.full and world == 1 and not args.no_host_endpoints and args.precision == "f32":
             bs.close()
             out["endpoints"] = {"device_complete": {"value": value, "unit": "frames/s",
                                                     "start": "float PCM resident in HBM", "end": "log-likelihoods complete in HBM",
@@ -713,12 +763,12 @@ def main():
             out["value_from_pinned_host"] = out["endpoints"]["from_pinned_host"]["value"]
             out["value_from_pinned_host_note"] = ("same workload and unit as `value`, timed from int16 PCM in page-locked host "
                                                   "memory (upload included, two batches in flight) to log-likelihoods complete in HBM")
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             bs.close()
             out["other_configs"], wide_sample = other_configs(pk, synth, torch, max(2, min(args.steps, 3)))
         else:
             wide_sample = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.model, args.seconds, args.cpu_seconds)
             if wide_sample is not None:      # the fp16 modes' error against the oracle
                 errs = oracle_errors_wide(wide_sample)

@@ -13,7 +13,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_has_the_contract_keys():
     out = subprocess.check_output(
         [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
-         "--seconds", "2", "--cpu-seconds", "1", "--no-other-configs"], text=True, cwd=REPO)
+         "--seconds", "2", "--cpu-seconds", "1", "--no-other-configs", "--full"], text=True, cwd=REPO)
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1, "exactly one line on stdout"
     d = json.loads(lines[0])
@@ -52,6 +52,69 @@ def test_bench_line_has_the_contract_keys():
     assert "page-locked" in d["value_from_pinned_host_note"]
 
 
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps and the line: no supplementary leg.  --dump-outputs
+    writes the last timed step's log-likelihoods, which are the oracle's within the contract (1e-4 * max(|ref|, 1))."""
+    import numpy as np
+    from oracle import oracle as O
+    from pocketkaldi_amd import synth
+    out_dir = tmp_path / "dump"
+    out = subprocess.check_output(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "3",
+         "--seconds", "1", "--dump-outputs", str(out_dir)], text=True, cwd=REPO)
+    lines = [l for l in out.splitlines() if l.strip()]
+    assert len(lines) == 1, "exactly one line on stdout"
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["frames_per_gpu_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("other_precision", "reference_softmax", "endpoints", "other_configs", "cpu_baseline", "cpu_baseline_all_cores"):
+        assert k not in d, k
+    assert d["roofline"]["kernel_ms_per_step"] > 0
+    ll = np.load(out_dir / "log_likelihoods.npy")
+    idx = np.load(out_dir / "log_likelihoods_rows.npy")
+    assert ll.dtype == np.float32 and idx.dtype == np.float64
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 << 20
+    layers, prior, L, R = synth.model("S")
+    nn, g = O.Nnet(layers), synth.global_cmvn_stats()
+    assert ll.shape == (d["config"]["frames_per_gpu_per_step"], 3000) and idx.shape == (ll.shape[0], 2)
+    for u in range(3):
+        ref = nn.am_compute(O.cmvn(g, O.Fbank().compute(synth.utterance(u, 1.0))), prior, L, R, 0.1)
+        sel = idx[:, 0] == u
+        assert np.array_equal(idx[sel, 1], np.arange(ref.shape[0]))
+        err = np.abs(ll[sel].astype(np.float64) - ref)
+        assert np.all(err <= 1e-4 * np.maximum(np.abs(ref), 1.0)), err.max()
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: the whole batch when it fits, else a seeded sample of rows that is the same on every run."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import bench
+    utt, frame = bench.dump_rows([3, 0, 2], 10)
+    assert utt.tolist() == [0, 0, 0, 2, 2] and frame.tolist() == [0, 1, 2, 0, 1]
+    frames = [998] * 256
+    utt, frame = bench.dump_rows(frames, 3000)
+    n = bench.DUMP_ROW_BYTES // (4 * 3000)
+    assert len(utt) == n and n * 3000 * 4 <= bench.DUMP_ROW_BYTES
+    g = utt * 998 + frame
+    assert np.all(np.diff(g) > 0) and np.all((frame >= 0) & (frame < 998)) and utt.min() >= 0 and utt.max() < 256
+    u2, f2 = bench.dump_rows(frames, 3000)
+    assert np.array_equal(utt, u2) and np.array_equal(frame, f2)
+    assert bench.DUMP_ROW_BYTES + 16 * n < 64 << 20       # rows + the float64 (utterance, frame) index
+
+
+def test_plain_run_is_lean_unless_full_is_asked_for():
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def _one_json_line(stdout):
     lines = [l for l in stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, stdout
@@ -81,7 +144,7 @@ def test_driver_launch_shape_two_ranks_on_one_gpu():
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
-         "--batch", "8", "--seconds", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+         "--batch", "8", "--seconds", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
         capture_output=True, text=True, cwd=REPO, env=env, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     d = _one_json_line(r.stdout)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=gpurun_out/sweep.txt
 : > $OUT
-LEAN="--no-cpu-baseline --no-other-configs --no-host-endpoints --steps 3 --warmup 1"
+LEAN="--full --no-cpu-baseline --no-other-configs --no-host-endpoints --steps 3 --warmup 1"
 run() {
   echo "## $*" >> $OUT
   timeout -k 10 400 python3 bench.py $LEAN "$@" 2>> gpurun_out/sweep.err | python3 -c "

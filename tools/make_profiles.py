@@ -8,7 +8,7 @@ Per section found (S = headline workload, W = BASELINE configs[4] wide model, B1
   rNN_<sec>_pmc_traffic.json               FETCH_SIZE / WRITE_SIZE passes -> HBM bytes per launch
   rNN_<sec>_pmc_mfma.json                  MFMA-busy passes (+ effective clock from GRBM_GUI_ACTIVE)
   rNN_B1_kernel_stats.csv, rNN_B1_probe.txt
-  rNN_bench.json                           the plain benchmark line
+  rNN_bench.json                           the full benchmark line (bench.py --full)
 """
 import collections
 import csv

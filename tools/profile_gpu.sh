@@ -6,7 +6,7 @@
 #         domain other than kernel-trace): FETCH_SIZE, WRITE_SIZE, MFMA busy
 #   W     BASELINE configs[4], the wide model 440 -> 6 x 2048 -> 8000: the same passes
 #   B1    BASELINE configs[1], one utterance: kernel-trace + stats of tools/b1_probe.py
-#   bench the plain benchmark line
+#   bench the full benchmark line (bench.py --full)
 # Raw output -> gpurun_out/prof/; tools/make_profiles.py turns it into the small committed summaries.
 set -e
 export TMPDIR=/tmp
@@ -41,7 +41,7 @@ for s in $SECTIONS; do
     B1) rm -rf $OUT/B1
         rocprofv3 --kernel-trace --stats -d $OUT/B1 -o p --output-format csv -- python3 tools/b1_probe.py > $OUT/B1_probe.log 2> $OUT/B1.err
         echo "B1 trace done" ;;
-    bench) python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench done" ;;
+    bench) python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench done" ;;
   esac
 done
 # keep what travels back small: the per-dispatch traces are not needed, the stats are
