@@ -84,10 +84,13 @@ enum {
   PK_MI355_E_DEVICE = -2,    /* HIP runtime failure or no gfx950 device  */
   PK_MI355_E_IO = -3,        /* file missing or corrupted                */
   PK_MI355_E_STATE = -4,     /* call order (e.g. model not finalized)    */
-  PK_MI355_E_RANGE = -5      /* f16x3 / f16: an operand left the fp16 split's range (results withheld) */
+  PK_MI355_E_RANGE = -5,     /* f16x3 / f16: an operand left the fp16 split's range (results withheld) */
+  PK_MI355_E_CAPACITY = -6   /* decoder: backtrace storage exhausted     */
 };
 
 const char *pk_mi355_last_error(void);
+/* The code of the failure pk_mi355_last_error() describes (for entries that return a pointer, NULL on failure). */
+int pk_mi355_last_error_code(void);
 
 /* Select the HIP device used by objects this THREAD creates afterwards (default 0; like
  * hipSetDevice the setting is per host thread).  One process drives one GPU (one rank per GPU
@@ -381,6 +384,67 @@ int pk_mi355_16kpcm_read(const char *filename, pk_vector_t *pcm_data);
 int pk_mi355_process_acoustic(pk_mi355_am_t *am, const pk_vector_t *cmvn_global_stats,
                               const pk_vector_t *raw_wave, float prob_scale, pk_decodable_t *out,
                               int verbose);
+
+/* ------------------------------------------------------------------------- */
+/* Graph and decoder -- Fst (fst.h) + Decoder::Decode / BestPath (decoder.cc:39-339) */
+/* on the GPU, batched: one workgroup per utterance, log-likelihoods read in HBM.     */
+/* Semantics and the three deliberate differences from the reference: DESIGN.md.     */
+/* ------------------------------------------------------------------------- */
+
+/* Fst::Read (fst.cc:29-92): section name "pk::fst_0", i32 size, i32 states, arcs, start,
+ * float final[states], i32 first[states], arcs {i32 next, ilabel, olabel; float weight}.
+ * Host only, needs no GPU.  NULL on failure: PK_MI355_E_IO for a malformed file (name, size,
+ * truncation), PK_MI355_E_INVALID for a graph that does not make sense (next state, start state
+ * or arc range out of range, negative label); pk_mi355_last_error() says which.            */
+typedef struct pk_mi355_fst pk_mi355_fst_t;
+pk_mi355_fst_t *pk_mi355_fst_read(const char *path);
+void pk_mi355_fst_destroy(pk_mi355_fst_t *fst);
+int pk_mi355_fst_num_states(const pk_mi355_fst_t *fst);
+int pk_mi355_fst_num_arcs(const pk_mi355_fst_t *fst);
+int pk_mi355_fst_start(const pk_mi355_fst_t *fst);
+/* Fst::CountArcs (fst.cc:94-110), its quirk included: a state's arcs end at the `first` of the
+ * next state whose first is > 0 (not >= 0).  *count = 0 for a state with first < 0.           */
+int pk_mi355_fst_arc_range(const pk_mi355_fst_t *fst, int state, int *first, int *count);
+
+/* A device copy of the graph, checked against am: every non-zero ilabel must map through the
+ * model's tid2pdf (identity without one) to a pdf < num_pdfs, otherwise PK_MI355_E_INVALID.
+ * max_utts: utterances per call.  trace_capacity: tokens of backtrace storage (8 bytes each)
+ * shared by the utterances of one call; 0 = 2^27.  Device memory: 68 bytes x states x max_utts
+ * + 12 x trace_capacity + the graph (DESIGN.md "Decoder").  The decoder is bound to am: it
+ * decodes batches scored with that model only.  A decoder belongs to one host thread at a
+ * time, like a batch.  Arc weights must be finite and final weights not NaN (the reader
+ * rejects others with PK_MI355_E_INVALID).                                                    */
+typedef struct pk_mi355_decoder pk_mi355_decoder_t;
+pk_mi355_decoder_t *pk_mi355_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am,
+                                            int max_utts, int64_t trace_capacity);
+void pk_mi355_decoder_destroy(pk_mi355_decoder_t *d);
+/* Decoder::beam_ (default 16.0) and kBeamSize (max-active, default 30000).                    */
+int pk_mi355_decoder_set_beam(pk_mi355_decoder_t *d, float beam, int max_active);
+/* All utterances of a scored batch, on the batch's stream, ordered after its scoring; nothing
+ * leaves HBM.  If the score call ended in PK_MI355_E_RANGE the results are withheld (with
+ * sync == 0 pk_mi355_decoder_synchronize returns the code).  The batch must be neither scored
+ * again nor destroyed before the decoder has been synchronised.                               */
+int pk_mi355_decoder_decode_batch(pk_mi355_decoder_t *d, pk_mi355_batch_t *b, int sync);
+/* Host decodables ({ncol = T, nrow = num_pdfs}; fetch_all views accepted): uploaded, then
+ * decoded.  With sync == 0 the decodables' memory must stay valid until synchronize.          */
+int pk_mi355_decoder_decode(pk_mi355_decoder_t *d, const pk_decodable_t *utts, int num_utts, int sync);
+/* Waits for the last call.  PK_MI355_E_CAPACITY (trace storage exhausted) and
+ * PK_MI355_E_INVALID (a negative epsilon cycle kept the closure from settling) name the first
+ * utterance concerned in pk_mi355_last_error(); no result of that call is readable then.        */
+int pk_mi355_decoder_synchronize(pk_mi355_decoder_t *d);
+/* Results of the last call, readable after synchronize (or sync != 0).  Words in spoken order
+ * (as pk_process prints them after its std::reverse, pocketkaldi.cc:226-227; at most max_words
+ * written), weight = Hypothesis::weight() (the final weight counted twice, as the reference
+ * does), ok = Decode()'s return (0 also where the beam emptied mid-utterance: no words, weight
+ * 0).  Returns the word count.                                                                 */
+int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, int max_words,
+                            float *weight, int *ok);
+/* Test hooks: the original arc ids of the best path (epsilon arcs included, start to end; at
+ * most max_arcs written, the length returned), and the largest per-frame count of states the
+ * decoder touched in utt (states <= R0 after the emitting step plus those the closure added):
+ * an upper bound on the reference's token count, so <= max-active shows it did not bind.      */
+int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs);
+int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt);
 
 /* Library / device facts */
 int pk_mi355_device_count(void);

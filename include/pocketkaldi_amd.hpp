@@ -9,6 +9,8 @@
 //   pocketkaldi::AcousticModel::Read / num_pdfs / TransitionIdToPdfId    src/am.h:23-52
 //   pocketkaldi::AcousticModel::Compute(frames, loglikelihood)           src/am.h:35
 //   pk_decodable_init/_destroy/_loglikelihood/_islastframe               src/decodable.h:20-41
+//   pocketkaldi::Fst::Read / CountArcs                                   src/fst.h
+//   pocketkaldi::Decoder(fst, am).Decode(pk_decodable_t*) / BestPath()   src/decoder.h (on the GPU)
 //
 // Error behaviour: the reference reports load errors through Status and treats misuse as
 // assert(); here load / device errors surface as pocketkaldi::Status (ok() / what()), and the
@@ -146,6 +148,88 @@ class AcousticModel {
 
  private:
   pk_mi355_am_t *am_;
+};
+
+// src/fst.h: the decoding graph, read on the host (Fst::Read, src/fst.cc:29-92)
+class Fst {
+ public:
+  Fst() : fst_(nullptr) {}
+  ~Fst() { pk_mi355_fst_destroy(fst_); }
+  Fst(const Fst &) = delete;
+  Fst &operator=(const Fst &) = delete;
+
+  Status Read(const std::string &path) {
+    pk_mi355_fst_destroy(fst_);
+    fst_ = pk_mi355_fst_read(path.c_str());
+    return fst_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  int start_state() const { return pk_mi355_fst_start(fst_); }
+  int num_states() const { return pk_mi355_fst_num_states(fst_); }
+  int num_arcs() const { return pk_mi355_fst_num_arcs(fst_); }
+  // Fst::CountArcs (src/fst.cc:94-110)
+  int CountArcs(int state) const {
+    int first = 0, count = 0;
+    return pk_mi355_fst_arc_range(fst_, state, &first, &count) == 0 ? count : 0;
+  }
+  const pk_mi355_fst_t *handle() const { return fst_; }
+
+ private:
+  pk_mi355_fst_t *fst_;
+};
+
+// src/decoder.h: Decoder::Decode + BestPath on the GPU (one utterance per call; pk_mi355_decoder_decode_batch
+// decodes a whole scored batch).  The graph's device copy is made for `am` (its tid2pdf maps the ilabels).
+class Decoder {
+ public:
+  // src/decoder.h:34-40
+  class Hypothesis {
+   public:
+    Hypothesis(const std::vector<int> &words, float weight) : words_(words), weight_(weight) {}
+    // The reference's order: last word first (pk_process reverses it, src/pocketkaldi.cc:226-227)
+    const std::vector<int> &words() const { return words_; }
+    float weight() const { return weight_; }
+
+   private:
+    std::vector<int> words_;
+    float weight_;
+  };
+
+  Decoder(const Fst *fst, pk_mi355_am_t *am) : d_(pk_mi355_decoder_create(fst->handle(), am, 1, 0)) {
+    if (!d_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  ~Decoder() { pk_mi355_decoder_destroy(d_); }
+  Decoder(const Decoder &) = delete;
+  Decoder &operator=(const Decoder &) = delete;
+
+  Status SetBeam(float beam, int max_active) { return Status::FromLast(pk_mi355_decoder_set_beam(d_, beam, max_active)); }
+
+  // Decoder::Decode (src/decoder.cc:39-77): true when tokens survive the last frame.  A device or capacity
+  // failure returns false and sets last_status().
+  bool Decode(pk_decodable_t *decodable) {
+    if (!d_) return false;
+    status_ = Status::FromLast(pk_mi355_decoder_decode(d_, decodable, 1, 1));
+    if (!status_.ok()) return false;
+    int ok = 0;
+    pk_mi355_decoder_result(d_, 0, nullptr, 0, nullptr, &ok);
+    return ok != 0;
+  }
+
+  // Decoder::BestPath (src/decoder.cc:304-339) of the last Decode
+  Hypothesis BestPath() const {
+    float weight = 0.0f;
+    const int n = d_ && status_.ok() ? pk_mi355_decoder_result(d_, 0, nullptr, 0, &weight, nullptr) : 0;
+    if (n <= 0) return Hypothesis(std::vector<int>(), 0.0f);
+    std::vector<int> words(n);
+    pk_mi355_decoder_result(d_, 0, words.data(), n, &weight, nullptr);
+    std::reverse(words.begin(), words.end());
+    return Hypothesis(words, weight);
+  }
+
+  const Status &last_status() const { return status_; }
+
+ private:
+  pk_mi355_decoder_t *d_;
+  Status status_;
 };
 
 // Utterance sharding for N GPUs (one process per GPU, a full weight replica each, no data-path collective): which rank

@@ -11,6 +11,8 @@ benchmark; it mirrors the reference's class names and argument meaning:
     AcousticModel.propagate(x)               nnet.h:96       Nnet::Propagate
     Decodable(am, prob_scale, feats)         decodable.h:22-41
     BatchScorer(am, global_stats, ...)       pocketkaldi.cc:176-218 stages, batched
+    Fst(path)                                fst.h           Fst::Read, CountArcs
+    Decoder(fst, am, max_utts)               decoder.h       Decoder::Decode + BestPath, batched on the GPU
 
 There is no CPU fallback: if the library is missing or no gfx950 device is usable,
 every compute call raises ``PkError``.
@@ -23,7 +25,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "Fst", "Decoder", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -69,6 +71,10 @@ EXPORTS = [
     "pk_mi355_am_flops_per_frame", "pk_mi355_16kpcm_read", "pk_mi355_process_acoustic",
     "pk_mi355_device_count", "pk_mi355_version",
     "pk_mi355_am_get_exponents", "pk_mi355_am_set_input_exponents", "pk_mi355_am_calibrate", "pk_mi355_batch_calibrate",
+    "pk_mi355_fst_read", "pk_mi355_fst_destroy", "pk_mi355_fst_num_states", "pk_mi355_fst_num_arcs", "pk_mi355_fst_start",
+    "pk_mi355_fst_arc_range", "pk_mi355_decoder_create", "pk_mi355_decoder_destroy", "pk_mi355_decoder_set_beam",
+    "pk_mi355_decoder_decode_batch", "pk_mi355_decoder_decode", "pk_mi355_decoder_synchronize", "pk_mi355_decoder_result",
+    "pk_mi355_decoder_best_path_arcs", "pk_mi355_decoder_active_bound", "pk_mi355_last_error_code",
 ]
 
 
@@ -179,6 +185,25 @@ def lib():
     L.pk_mi355_am_set_input_exponents.argtypes = [C.c_void_p, i32p, C.c_int]
     L.pk_mi355_am_calibrate.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t)]
     L.pk_mi355_batch_calibrate.argtypes = [C.c_void_p]
+    L.pk_mi355_last_error_code.argtypes = []
+    L.pk_mi355_fst_read.restype = C.c_void_p
+    L.pk_mi355_fst_read.argtypes = [C.c_char_p]
+    L.pk_mi355_fst_destroy.restype = None
+    L.pk_mi355_fst_destroy.argtypes = [C.c_void_p]
+    for f in ("num_states", "num_arcs", "start"):
+        getattr(L, "pk_mi355_fst_" + f).argtypes = [C.c_void_p]
+    L.pk_mi355_fst_arc_range.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_decoder_create.restype = C.c_void_p
+    L.pk_mi355_decoder_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]
+    L.pk_mi355_decoder_destroy.restype = None
+    L.pk_mi355_decoder_destroy.argtypes = [C.c_void_p]
+    L.pk_mi355_decoder_set_beam.argtypes = [C.c_void_p, C.c_float, C.c_int]
+    L.pk_mi355_decoder_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.pk_mi355_decoder_decode.argtypes = [C.c_void_p, C.POINTER(pk_decodable_t), C.c_int, C.c_int]
+    L.pk_mi355_decoder_synchronize.argtypes = [C.c_void_p]
+    L.pk_mi355_decoder_result.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.POINTER(C.c_int)]
+    L.pk_mi355_decoder_best_path_arcs.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
+    L.pk_mi355_decoder_active_bound.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 
@@ -600,3 +625,127 @@ class BatchScorer:
         n = (C.c_int * 5)()
         _check(lib().pk_mi355_batch_get_timing(self._h, ms, n))
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KINDS)}
+
+
+class PkCodeError(PkError):
+    """A PkError that carries the library's negative status code."""
+
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
+
+
+def _check_code(rc):
+    if rc < 0:
+        raise PkCodeError(rc, lib().pk_mi355_last_error().decode() or "pk_mi355 error %d" % rc)
+    return rc
+
+
+class Fst:
+    """fst.h: the reference's pk::fst_0 graph, read on the host (pk_mi355_fst_read)."""
+
+    def __init__(self, path):
+        self._h = lib().pk_mi355_fst_read(os.fspath(path).encode())
+        if not self._h:
+            msg = lib().pk_mi355_last_error().decode()
+            raise PkCodeError(lib().pk_mi355_last_error_code(), msg)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def num_states(self):
+        return lib().pk_mi355_fst_num_states(self._h)
+
+    def num_arcs(self):
+        return lib().pk_mi355_fst_num_arcs(self._h)
+
+    def start(self):
+        return lib().pk_mi355_fst_start(self._h)
+
+    def arc_range(self, state):
+        """Fst::CountArcs (fst.cc:94-110): (first arc, count) of a state."""
+        first, count = C.c_int(), C.c_int()
+        _check_code(lib().pk_mi355_fst_arc_range(self._h, int(state), C.byref(first), C.byref(count)))
+        return first.value, count.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_fst_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Decoder:
+    """decoder.h: Decoder::Decode + BestPath on the GPU, one workgroup per utterance."""
+
+    def __init__(self, fst, am, max_utts, trace_capacity=0):
+        self._fst, self._am = fst, am
+        self._h = lib().pk_mi355_decoder_create(fst.handle, am.handle, int(max_utts), int(trace_capacity))
+        if not self._h:
+            msg = lib().pk_mi355_last_error().decode()
+            raise PkCodeError(lib().pk_mi355_last_error_code(), msg)
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_beam(self, beam=16.0, max_active=30000):
+        _check_code(lib().pk_mi355_decoder_set_beam(self._h, float(beam), int(max_active)))
+
+    def decode_batch(self, batch, sync=True):
+        """Every utterance of a scored BatchScorer, read where it lies in HBM."""
+        self._keep = batch
+        _check_code(lib().pk_mi355_decoder_decode_batch(self._h, batch._h, 1 if sync else 0))
+
+    def decode(self, logliks, sync=True):
+        """Host log-likelihood arrays, each float32 [T][num_pdfs] (or Decodable objects)."""
+        arrs, arr = [], (pk_decodable_t * max(len(logliks), 1))()
+        for i, x in enumerate(logliks):
+            if isinstance(x, Decodable):
+                arr[i] = x._d
+                arrs.append(x)
+                continue
+            a = _f32(x)
+            if a.ndim != 2:
+                raise PkError("log-likelihoods must be [T][num_pdfs]")
+            arrs.append(a)
+            arr[i].log_prob.ncol, arr[i].log_prob.nrow = a.shape
+            arr[i].log_prob.data = _fp(a) if a.size else None
+            arr[i].am = self._am.handle
+        self._keep = (arrs, arr)
+        _check_code(lib().pk_mi355_decoder_decode(self._h, arr, len(logliks), 1 if sync else 0))
+
+    def synchronize(self):
+        _check_code(lib().pk_mi355_decoder_synchronize(self._h))
+
+    def result(self, utt):
+        """(words in spoken order, weight, ok) -- pk_process's hyp and Hypothesis::weight()."""
+        weight, ok = C.c_float(), C.c_int()
+        n = _check_code(lib().pk_mi355_decoder_result(self._h, int(utt), None, 0, C.byref(weight), C.byref(ok)))
+        words = np.zeros(max(n, 1), np.int32)
+        _check_code(lib().pk_mi355_decoder_result(self._h, int(utt), words.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                                  C.byref(weight), C.byref(ok)))
+        return [int(w) for w in words[:n]], weight.value, ok.value
+
+    def best_path_arcs(self, utt):
+        n = _check_code(lib().pk_mi355_decoder_best_path_arcs(self._h, int(utt), None, 0))
+        arcs = np.zeros(max(n, 1), np.int32)
+        lib().pk_mi355_decoder_best_path_arcs(self._h, int(utt), arcs.ctypes.data_as(C.POINTER(C.c_int32)), n)
+        return [int(a) for a in arcs[:n]]
+
+    def active_bound(self, utt):
+        return _check_code(lib().pk_mi355_decoder_active_bound(self._h, int(utt)))

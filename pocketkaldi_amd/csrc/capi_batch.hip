@@ -296,6 +296,11 @@ int64_t TotalSamples(const int *num_samples, int n) {
 
 }  // namespace
 
+namespace pkhost {
+bool BatchScored(const pk_mi355_batch *b) { return b->scored; }
+const pk_mi355_am *BatchModel(const pk_mi355_batch *b) { return b->am; }
+}  // namespace pkhost
+
 extern "C" {
 
 int pk_mi355_num_frames(int num_samples) {      // fbank.cc:35-42

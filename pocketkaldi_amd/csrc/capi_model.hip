@@ -22,6 +22,7 @@ using namespace pkhost;
 
 namespace {
 thread_local char g_err[512] = "";
+thread_local int g_err_code = 0;
 thread_local int g_device = 0;
 }  // namespace
 
@@ -32,6 +33,7 @@ int Fail(int code, const char *fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+  g_err_code = code;
   return code;
 }
 const char *LastError() { return g_err; }
@@ -73,6 +75,7 @@ int UploadExps(pk_mi355_am *am) {
 extern "C" {
 
 const char *pk_mi355_last_error(void) { return g_err; }
+int pk_mi355_last_error_code(void) { return g_err_code; }
 const char *pk_mi355_version(void) { return "pk_mi355 0.1 (gfx950)"; }
 
 int pk_mi355_device_count(void) {

@@ -1,0 +1,847 @@
+// decode.hip -- the search half of pk_process (Decoder::Decode + BestPath, decoder.cc:39-339) on the GPU,
+// batched: one workgroup per utterance decodes the whole utterance in ONE launch, frame after frame,
+// synchronising only with __syncthreads() (no workgroup waits on another).  Plus the host-only reader of
+// the reference's graph format (Fst::Read / CountArcs, fst.cc:29-110).
+//
+// Semantics (DESIGN.md "Decoder"): the reference's float / double arithmetic operation for operation;
+// order-independent where the reference depends on iteration order:
+//   * emitting candidates are kept when <= R0 (the bound from the best token's arcs, decoder.cc:244-262),
+//     and only tokens <= F (the exact non-emitting cutoff) form the next frame's list;
+//   * ties on a state go to the lowest candidate id (64-bit atomicMin of (ordered cost bits << 32) | id);
+//   * when max-active binds, the cutoff is the EXACT max_active-th smallest cost (radix select), not the
+//     reference's 200-cost sample (decoder.cc:137-168).
+// Compiled with -ffp-contract=off and no fast-math (build.py), like every other translation unit.
+#include <math.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+#include "pk_host.h"
+
+using namespace pkhost;
+
+namespace {
+
+constexpr int kDecThreads = 512;
+constexpr int kDecWaves = kDecThreads / 64;
+constexpr int kMaxDecPdfs = 16384;                 // one frame's log-likelihood row in LDS: 64 KiB at most
+constexpr uint32_t kEpsBit = 0x80000000u;          // candidate id of an epsilon arc (loses ties to an emitting one)
+constexpr uint32_t kStartId = 0x7FFFFFFFu;         // the start token's id (never resolved: it has no arc)
+constexpr uint64_t kEmpty = ~0ull;
+constexpr int64_t kDefaultTrace = int64_t(1) << 27;   // tokens of backtrace storage per call when the caller says 0
+
+struct Tok {        // one token: its state, cost and trace record (-1: the start token)
+  int state;
+  float cost;
+  int trace;
+  int pad;
+};
+
+struct UttResult {
+  int status;       // 0, PK_MI355_E_CAPACITY, PK_MI355_E_INVALID
+  int ok;           // Decode()'s return (decoder.cc:77)
+  float weight;     // Hypothesis::weight()
+  int path_off;     // arc ids of the best path in the path arena, start to end
+  int path_len;
+  int active_bound; // largest per-frame count of touched states
+  int pad[2];
+};
+
+struct DecArgs {
+  // graph, split into emitting and epsilon CSR lists (arc order kept).  Arcs: x = next state, y = pdf
+  // (ilabel mapped through the model's tid2pdf at create), z = weight bits, w = original arc id.
+  const int *e_off; const int4 *e_arc; const int *e_src;
+  const int *n_off; const int4 *n_arc; const int *n_src;
+  const float *final_w;
+  int num_states, start, num_pdfs;
+  // log-likelihoods: utterance u's frame t is ll + ll_off[u] + t * num_pdfs
+  const float *ll; const int64_t *ll_off; const int *T;
+  int num_utts;
+  // per-utterance work areas (stride num_states entries)
+  uint64_t *key; int *tr; int *mark; int *touched; int *nxt; Tok *la; Tok *lb; Tok *fa; Tok *fb;
+  // backtrace arena (shared by the call) and best-path arena
+  int2 *rec; int64_t rec_cap; unsigned long long *rec_top;
+  int *path; int path_cap; int *path_top;
+  float beam; int max_active; int max_rounds;
+  UttResult *res;
+};
+
+__device__ __forceinline__ uint32_t OrdBits(float c) {
+  const uint32_t u = __float_as_uint(c);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float OrdFloat(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+__device__ __forceinline__ uint64_t Pack(float c, uint32_t id) { return (uint64_t(OrdBits(c)) << 32) | id; }
+// keys are changed by atomics (performed at L2): read them past the L1
+__device__ __forceinline__ uint64_t LoadKey(const uint64_t *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct Shared {
+  int scan[kDecWaves];
+  int cnt_touched, cnt_nxt, fail;
+  unsigned long long base;
+  double dred[kDecWaves];
+  uint64_t ured[kDecWaves];
+  int hist[256];
+  int sel;
+  // one chunk of source tokens of a load-balanced expansion
+  int excl[kDecThreads];
+  int first[kDecThreads];
+};
+
+// exclusive scan of one int per thread; *total = the sum (all threads)
+__device__ int BlockScan(Shared &sh, int v, int *total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) sh.scan[w] = x;
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int i = 0; i < kDecWaves; ++i) {
+    const int s = sh.scan[i];
+    if (i < w) before += s;
+    all += s;
+  }
+  __syncthreads();
+  *total = all;
+  return before + x - v;
+}
+
+__device__ double BlockMinD(Shared &sh, double v) {
+  for (int d = 32; d >= 1; d >>= 1) v = fmin(v, __shfl_xor(v, d, 64));
+  if ((threadIdx.x & 63) == 0) sh.dred[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = sh.dred[0];
+  for (int i = 1; i < kDecWaves; ++i) r = fmin(r, sh.dred[i]);
+  __syncthreads();
+  return r;
+}
+
+__device__ uint64_t BlockMinU(Shared &sh, uint64_t v) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint64_t o = __shfl_xor(v, d, 64);
+    v = o < v ? o : v;
+  }
+  if ((threadIdx.x & 63) == 0) sh.ured[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint64_t r = sh.ured[0];
+  for (int i = 1; i < kDecWaves; ++i) r = sh.ured[i] < r ? sh.ured[i] : r;
+  __syncthreads();
+  return r;
+}
+
+// The k-th smallest (1-based) ordered cost of list[0..n): four 8-bit radix passes over an LDS histogram.
+__device__ uint32_t SelectKth(Shared &sh, const Tok *list, int n, int k) {
+  uint32_t prefix = 0, mask = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = threadIdx.x; i < 256; i += kDecThreads) sh.hist[i] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += kDecThreads) {
+      const uint32_t o = OrdBits(list[i].cost);
+      if ((o & mask) == prefix) atomicAdd(&sh.hist[(o >> shift) & 255], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int acc = 0, b = 0;
+      for (; b < 255; ++b) {
+        if (acc + sh.hist[b] >= k) break;
+        acc += sh.hist[b];
+      }
+      sh.sel = b;
+      sh.cnt_nxt = k - acc;      // rank inside the chosen bin (scratch; cnt_nxt is reset before use)
+    }
+    __syncthreads();
+    prefix |= uint32_t(sh.sel) << shift;
+    mask |= 255u << shift;
+    k = sh.cnt_nxt;
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// Load-balanced walk over the arcs of src[0..n) (CSR off/arcs), skipping tokens whose cost > cut.
+// fn(token index j, csr arc index a) for every arc; lanes walk the flattened arc range chunk by chunk.
+template <typename Fn>
+__device__ void ForArcs(Shared &sh, const Tok *src, int n, float cut, const int *off, Fn fn) {
+  for (int c0 = 0; c0 < n; c0 += kDecThreads) {
+    const int j = c0 + threadIdx.x;
+    int cnt = 0, first = 0;
+    if (j < n) {
+      const Tok t = src[j];
+      if (!(t.cost > cut)) {
+        first = off[t.state];
+        cnt = off[t.state + 1] - first;
+      }
+    }
+    int total;
+    const int ex = BlockScan(sh, cnt, &total);
+    sh.excl[threadIdx.x] = ex;
+    sh.first[threadIdx.x] = first;
+    __syncthreads();
+    const int m = min(kDecThreads, n - c0);
+    for (int e = threadIdx.x; e < total; e += kDecThreads) {
+      int lo = 0, hi = m - 1;                        // the last token whose exclusive offset is <= e
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sh.excl[mid] <= e) lo = mid; else hi = mid - 1;
+      }
+      fn(c0 + lo, sh.first[lo] + (e - sh.excl[lo]));
+    }
+    __syncthreads();
+  }
+}
+
+// Give each winner of touched-or-improved states a trace record and write it as a token into out[].
+// states[0..n): the states; arcs/srcs: the CSR the winners' ids index (emitting or epsilon);
+// only winners <= F are kept.  Returns the number written (all threads), or -1 when the arena is full.
+__device__ int Resolve(Shared &sh, const DecArgs &A, const int *states, int n, float F, bool eps, uint64_t *key,
+                       int *tr, int *mark, Tok *out) {
+  int written = 0;
+  for (int c0 = 0; c0 < n; c0 += kDecThreads) {
+    const int i = c0 + threadIdx.x;
+    int need = 0, s = 0, prev = -1, arc = -1;
+    float c = 0.f;
+    if (i < n) {
+      s = states[i];
+      if (eps) mark[s] = 0;
+      const uint64_t k = LoadKey(&key[s]);
+      c = OrdFloat(uint32_t(k >> 32));
+      const uint32_t id = uint32_t(k);
+      if (!(c > F) && id != kStartId) {
+        need = 1;
+        if (eps) {
+          const int a = int(id & ~kEpsBit);
+          prev = tr[A.n_src[a]];
+          arc = A.n_arc[a].w;
+        } else {
+          prev = tr[A.e_src[id]];
+          arc = A.e_arc[id].w;
+        }
+      }
+    }
+    int total;
+    const int ex = BlockScan(sh, need, &total);
+    if (threadIdx.x == 0) sh.base = total ? atomicAdd(A.rec_top, (unsigned long long)total) : 0ull;
+    __syncthreads();
+    const unsigned long long base = sh.base;
+    __syncthreads();
+    if (base + (unsigned long long)total > (unsigned long long)A.rec_cap) return -1;
+    if (need) {
+      const int r = int(base) + ex;
+      A.rec[r] = make_int2(prev, arc);
+      Tok t;
+      t.state = s; t.cost = c; t.trace = r; t.pad = 0;
+      out[written + ex] = t;
+    }
+    written += total;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < written; i += kDecThreads) tr[out[i].state] = out[i].trace;
+  __syncthreads();
+  return written;
+}
+
+__global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
+  extern __shared__ float s_ll[];
+  __shared__ Shared sh;
+  const int u = blockIdx.x;
+  if (u >= A.num_utts) return;
+  const size_t S = (size_t)A.num_states;
+  uint64_t *key = A.key + S * u;
+  int *tr = A.tr + S * u, *mark = A.mark + S * u, *touched = A.touched + S * u, *nxt = A.nxt + S * u;
+  Tok *L = A.la + S * u, *Lnext = A.lb + S * u, *fa = A.fa + S * u, *fb = A.fb + S * u;
+  const int T = A.T[u];
+  const float *ll = A.ll + A.ll_off[u];
+  UttResult *res = A.res + u;
+
+  int status = 0, ok = 1, active = 0;
+  int nL = 0, nT = 0, nF = 0;
+  float F = INFINITY;
+
+  // InitDecoding (decoder.cc:79-97): the start token, cost 0, then the epsilon closure with an infinite cutoff
+  if (threadIdx.x == 0) {
+    key[A.start] = Pack(0.0f, kStartId);
+    touched[0] = A.start;
+    tr[A.start] = -1;
+    Tok t;
+    t.state = A.start; t.cost = 0.0f; t.trace = -1; t.pad = 0;
+    fa[0] = t;
+    sh.fail = 0;
+  }
+  nT = 1;
+  nF = 1;
+  __syncthreads();
+
+  for (int t = -1; t < T; ++t) {
+    if (t >= 0) {
+      // ---- ProcessEmitting (decoder.cc:226-301)
+      for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads) s_ll[p] = ll[(size_t)t * A.num_pdfs + p];
+      if (nL == 0) { ok = 0; break; }                 // the beam emptied: the reference dereferences a null best_tok
+      // GetCutoff (:132-182): best token (lowest state on equal cost), exact max-active cutoff
+      uint64_t bk = kEmpty;
+      for (int i = threadIdx.x; i < nL; i += kDecThreads) {
+        const uint64_t k = (uint64_t(OrdBits(L[i].cost)) << 32) | uint32_t(L[i].state);
+        bk = k < bk ? k : bk;
+      }
+      bk = BlockMinU(sh, bk);
+      const float best = OrdFloat(uint32_t(bk >> 32));
+      const int best_state = int(uint32_t(bk));
+      const double beam_cutoff = (double)best + (double)A.beam;
+      float adaptive_beam = A.beam, weight_cutoff = (float)beam_cutoff;
+      if (nL > A.max_active) {
+        const double kth = (double)OrdFloat(SelectKth(sh, L, nL, A.max_active));
+        if (kth < beam_cutoff) {
+          adaptive_beam = (float)(kth - (double)best + (double)0.5f);
+          weight_cutoff = (float)kth;
+        }
+      }
+      // R0: the bound from the best token's arcs (:244-262)
+      double r0 = INFINITY;
+      for (int a = A.e_off[best_state] + threadIdx.x; a < A.e_off[best_state + 1]; a += kDecThreads) {
+        const int4 arc = A.e_arc[a];
+        const float c = (best + __int_as_float(arc.z)) + (-s_ll[arc.y]);
+        r0 = fmin(r0, (double)c + (double)adaptive_beam);
+      }
+      __syncthreads();                                 // (s_ll complete before the block reductions' barriers matter)
+      r0 = BlockMinD(sh, r0);
+      if (threadIdx.x == 0) sh.cnt_touched = 0;
+      __syncthreads();
+      // every candidate <= R0 into the state table
+      double cmin = INFINITY;
+      ForArcs(sh, L, nL, weight_cutoff, A.e_off, [&](int j, int a) {
+        const int4 arc = A.e_arc[a];
+        const float c = (L[j].cost + __int_as_float(arc.z)) + (-s_ll[arc.y]);
+        cmin = fmin(cmin, (double)c);
+        if ((double)c > r0) return;
+        const uint64_t k = Pack(c, uint32_t(a));
+        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
+        if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
+      });
+      cmin = BlockMinD(sh, cmin);
+      nT = sh.cnt_touched;
+      F = (float)(cmin + (double)adaptive_beam);       // the non-emitting cutoff ProcessEmitting returns
+      nF = Resolve(sh, A, touched, nT, F, false, key, tr, mark, fa);
+      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
+    }
+    // ---- ProcessNonemitting (decoder.cc:186-222): frontier by frontier to the fixed point, bounded
+    int rounds = 0;
+    while (nF > 0) {
+      if (rounds >= A.max_rounds) { status = PK_MI355_E_INVALID; break; }
+      if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.cnt_touched = nT; }
+      __syncthreads();
+      ForArcs(sh, fa, nF, INFINITY, A.n_off, [&](int j, int a) {
+        const int4 arc = A.n_arc[a];
+        const float c = fa[j].cost + __int_as_float(arc.z);
+        if (c > F) return;
+        const uint64_t k = Pack(c, uint32_t(a) | kEpsBit);
+        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
+        if (k < old) {
+          if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
+          if (atomicExch(&mark[arc.x], 1) == 0) nxt[atomicAdd(&sh.cnt_nxt, 1)] = arc.x;
+        }
+      });
+      const int nN = sh.cnt_nxt;
+      nT = sh.cnt_touched;
+      __syncthreads();
+      nF = Resolve(sh, A, nxt, nN, F, true, key, tr, mark, fb);
+      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
+      Tok *x = fa; fa = fb; fb = x;
+      ++rounds;
+    }
+    if (status) break;
+    active = max(active, nT);
+    // the next frame's tokens: the touched states <= F; every touched entry of the table is reset
+    int written = 0;
+    for (int c0 = 0; c0 < nT; c0 += kDecThreads) {
+      const int i = c0 + threadIdx.x;
+      int keep = 0, s = 0;
+      float c = 0.f;
+      if (i < nT) {
+        s = touched[i];
+        c = OrdFloat(uint32_t(LoadKey(&key[s]) >> 32));
+        keep = !(c > F);
+      }
+      int total;
+      const int ex = BlockScan(sh, keep, &total);
+      if (keep) {
+        Tok tk;
+        tk.state = s; tk.cost = c; tk.trace = tr[s]; tk.pad = 0;
+        Lnext[written + ex] = tk;
+      }
+      written += total;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nT; i += kDecThreads) key[touched[i]] = kEmpty;
+    nT = 0;
+    nL = written;
+    { Tok *x = L; L = Lnext; Lnext = x; }
+    __syncthreads();
+  }
+  if (status) {                                        // leave the work areas clean for the next call
+    for (int i = threadIdx.x; i < nT; i += kDecThreads) {
+      key[touched[i]] = kEmpty;
+      mark[touched[i]] = 0;
+    }
+  }
+
+  // ---- BestPath (decoder.cc:304-339): min (double)cost + final over the final tokens, != INFINITY
+  double bc = INFINITY;
+  int bi = -1;
+  if (!status && ok) {
+    for (int i = threadIdx.x; i < nL; i += kDecThreads) {
+      const double c = (double)L[i].cost + (double)A.final_w[L[i].state];
+      if (c != INFINITY && (c < bc || (c == bc && bi >= 0 && L[i].state < L[bi].state))) { bc = c; bi = i; }
+    }
+    const double m = BlockMinD(sh, bc);
+    uint64_t cand = (bi >= 0 && bc == m) ? ((uint64_t(uint32_t(L[bi].state)) << 32) | uint32_t(bi)) : kEmpty;
+    cand = BlockMinU(sh, cand);
+    bc = m;
+    bi = cand == kEmpty ? -1 : int(uint32_t(cand));
+  }
+  if (threadIdx.x == 0) {
+    UttResult r;
+    r.status = status; r.ok = (status || nL == 0) ? 0 : ok; r.weight = 0.f;
+    r.path_off = 0; r.path_len = 0; r.active_bound = active; r.pad[0] = r.pad[1] = 0;
+    if (!status && r.ok && bi >= 0) {
+      float w = (float)bc;
+      w += A.final_w[L[bi].state];                     // final() counted twice, as the reference does (:338-339)
+      r.weight = w;
+      int len = 0;
+      for (int x = L[bi].trace; x >= 0 && len <= A.rec_cap; x = A.rec[x].x) ++len;
+      const int off = atomicAdd(A.path_top, len);
+      if (off + len > A.path_cap) {                   // (cannot happen: see CreateDecoder)
+        r.status = PK_MI355_E_CAPACITY;
+        r.ok = 0;
+      } else {
+        r.path_off = off; r.path_len = len;
+        int p = off + len;
+        for (int x = L[bi].trace; x >= 0 && p > off; x = A.rec[x].x) A.path[--p] = A.rec[x].y;
+      }
+    }
+    *res = r;
+  }
+}
+
+}  // namespace
+
+// ================================================================== host objects
+
+struct pk_mi355_fst {
+  int num_states = 0, num_arcs = 0, start = 0;
+  std::vector<float> final_w;
+  std::vector<int32_t> first;
+  std::vector<int32_t> arc_first, arc_count;    // Fst::CountArcs per state
+  struct Arc { int32_t next, ilabel, olabel; float weight; };
+  std::vector<Arc> arcs;
+};
+
+struct pk_mi355_decoder {
+  int device = 0;
+  const pk_mi355_am *am = nullptr;              // the model the graph's ilabels were checked against
+  int max_utts = 0, num_states = 0, start = 0, num_pdfs = 0;
+  float beam = 16.0f;
+  int max_active = 30000;
+  int64_t trace_cap = 0;
+  std::vector<int32_t> olabel;                  // by original arc id
+  // device graph
+  int *e_off = nullptr, *e_src = nullptr, *n_off = nullptr, *n_src = nullptr;
+  int4 *e_arc = nullptr, *n_arc = nullptr;
+  float *final_w = nullptr;
+  // work areas
+  uint64_t *key = nullptr;
+  int *tr = nullptr, *mark = nullptr, *touched = nullptr, *nxt = nullptr;
+  Tok *lists = nullptr;
+  int2 *rec = nullptr;
+  unsigned long long *counters = nullptr;       // [0] records used; [1] (as int) path entries used
+  int *path = nullptr;
+  int path_cap = 0;
+  UttResult *d_res = nullptr;
+  float *d_ll = nullptr;                        // host decodables uploaded here
+  size_t d_ll_floats = 0;
+  int64_t *d_off = nullptr;
+  int *d_T = nullptr;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;                 // where the last call was queued
+  hipEvent_t done = nullptr;
+  pk_mi355_batch_t *batch = nullptr;            // decode_batch: the scored batch (its range verdict)
+  // results of the last call
+  bool pending = false, have = false;
+  int num_utts = 0;
+  std::vector<UttResult> res;
+  std::vector<int32_t> h_path;
+  std::vector<int> h_T;
+  std::vector<int64_t> h_off;
+};
+
+namespace {
+
+int ReadFst(const char *path, pk_mi355_fst *f) {
+  FileBuf fb;
+  int rc = fb.Open(path);
+  if (rc) return rc;
+  const std::vector<unsigned char> &d = fb.d;
+  if (d.size() < 48) return Fail(PK_MI355_E_IO, "%s: malformed graph: truncated header", path);
+  char name[32];
+  memcpy(name, d.data(), 32);
+  name[31] = '\0';
+  if (strcmp(name, "pk::fst_0") != 0) return Fail(PK_MI355_E_IO, "%s: malformed graph: section name 'pk::fst_0' expected", path);
+  int32_t size, ns, na, start;
+  memcpy(&size, &d[32], 4); memcpy(&ns, &d[36], 4); memcpy(&na, &d[40], 4); memcpy(&start, &d[44], 4);
+  if (ns < 0 || na < 0) return Fail(PK_MI355_E_IO, "%s: malformed graph: negative state or arc count", path);
+  const int64_t expect = 12 + (int64_t)ns * 8 + (int64_t)na * 16;
+  if (expect != size) return Fail(PK_MI355_E_IO, "%s: malformed graph: section size %d, %lld expected", path, size, (long long)expect);
+  if ((int64_t)d.size() < 36 + expect) return Fail(PK_MI355_E_IO, "%s: malformed graph: truncated (%zu bytes, %lld expected)", path,
+                                                   d.size(), (long long)(36 + expect));
+  if (start < 0 || start >= ns) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: start state %d out of range", path, start);
+  f->num_states = ns; f->num_arcs = na; f->start = start;
+  f->final_w.resize(ns); f->first.resize(ns); f->arcs.resize(na);
+  if (ns) {
+    memcpy(f->final_w.data(), &d[48], (size_t)ns * 4);
+    memcpy(f->first.data(), &d[48 + (size_t)ns * 4], (size_t)ns * 4);
+  }
+  if (na) memcpy(f->arcs.data(), &d[48 + (size_t)ns * 8], (size_t)na * 16);
+  // Fst::CountArcs (fst.cc:94-110): a state's arcs end at the `first` of the next state whose first is > 0
+  f->arc_first.assign(ns, 0); f->arc_count.assign(ns, 0);
+  int32_t next_idx = na;
+  for (int s = ns - 1; s >= 0; --s) {
+    const int32_t fs = f->first[s];
+    if (fs >= 0) {
+      if (fs > na || next_idx < fs)
+        return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc range [%d, %d) of state %d outside the arc array", path, fs, next_idx, s);
+      f->arc_first[s] = fs;
+      f->arc_count[s] = next_idx - fs;
+    }
+    if (fs > 0) next_idx = fs;
+  }
+  for (int s = 0; s < ns; ++s)
+    if (std::isnan(f->final_w[s]))
+      return Fail(PK_MI355_E_INVALID, "%s: invalid graph: final weight of state %d is NaN", path, s);
+  for (int a = 0; a < na; ++a) {
+    const auto &arc = f->arcs[a];
+    if (!std::isfinite(arc.weight)) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: weight is not finite", path, a);
+    if (arc.next < 0 || arc.next >= ns) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: next state %d out of range", path, a, arc.next);
+    if (arc.ilabel < 0 || arc.olabel < 0) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: negative label", path, a);
+  }
+  return 0;
+}
+
+void FreeDecoderDevice(pk_mi355_decoder *d) {
+  void *ptrs[] = {d->e_off, d->e_src, d->n_off, d->n_src, d->e_arc, d->n_arc, d->final_w, d->key, d->tr, d->mark,
+                  d->touched, d->nxt, d->lists, d->rec, d->counters, d->path, d->d_res, d->d_ll, d->d_off, d->d_T};
+  for (void *p : ptrs) if (p) hipFree(p);
+  if (d->done) hipEventDestroy(d->done);
+  if (d->own_stream) hipStreamDestroy(d->own_stream);
+}
+
+template <typename T>
+int Upload(T **dst, const std::vector<T> &src, size_t min_count = 1) {
+  const size_t n = std::max(src.size(), min_count);
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(dst), sizeof(T) * n));
+  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int CreateDecoder(pk_mi355_decoder *d, const pk_mi355_fst *f, const pk_mi355_am *am, int max_utts, int64_t trace_capacity) {
+  const int S = f->num_states;
+  const int N = am->num_pdfs;
+  if (N <= 0 || N > kMaxDecPdfs) return Fail(PK_MI355_E_INVALID, "decoder: num_pdfs %d outside [1, %d]", N, kMaxDecPdfs);
+  // split the graph; ilabels are mapped to pdfs here (tid2pdf, or identity without one) and checked
+  std::vector<int> e_off(S + 1, 0), n_off(S + 1, 0), e_src, n_src;
+  std::vector<int4> e_arc, n_arc;
+  for (int s = 0; s < S; ++s) {
+    for (int i = 0; i < f->arc_count[s]; ++i) {
+      const int a = f->arc_first[s] + i;
+      const auto &arc = f->arcs[a];
+      int4 v;
+      v.x = arc.next; v.z = 0; v.w = a;
+      memcpy(&v.z, &arc.weight, 4);
+      if (arc.ilabel == 0) {
+        v.y = 0;
+        n_arc.push_back(v); n_src.push_back(s);
+      } else {
+        int pdf;
+        if (am->tid2pdf.empty()) {
+          pdf = arc.ilabel;
+        } else {
+          if (arc.ilabel >= (int)am->tid2pdf.size())
+            return Fail(PK_MI355_E_INVALID, "decoder: arc %d: transition id %d outside the model's tid2pdf (%zu entries)",
+                        a, arc.ilabel, am->tid2pdf.size());
+          pdf = am->tid2pdf[arc.ilabel];
+        }
+        if (pdf < 0 || pdf >= N)
+          return Fail(PK_MI355_E_INVALID, "decoder: arc %d: transition id %d maps to pdf %d, the model has %d", a, arc.ilabel, pdf, N);
+        v.y = pdf;
+        e_arc.push_back(v); e_src.push_back(s);
+      }
+      if (e_arc.size() >= (size_t)kEpsBit - 1 || n_arc.size() >= (size_t)kEpsBit - 1)
+        return Fail(PK_MI355_E_INVALID, "decoder: too many arcs");
+    }
+    e_off[s + 1] = (int)e_arc.size();
+    n_off[s + 1] = (int)n_arc.size();
+  }
+  d->max_utts = max_utts; d->num_states = S; d->start = f->start; d->num_pdfs = N;
+  d->trace_cap = trace_capacity > 0 ? trace_capacity : kDefaultTrace;
+  if (d->trace_cap > (int64_t)INT32_MAX) return Fail(PK_MI355_E_INVALID, "decoder: trace_capacity above 2^31 - 1");
+  d->olabel.resize(f->num_arcs);
+  for (int a = 0; a < f->num_arcs; ++a) d->olabel[a] = f->arcs[a].olabel;
+  int rc;
+  if ((rc = Upload(&d->e_off, e_off)) || (rc = Upload(&d->n_off, n_off)) || (rc = Upload(&d->e_src, e_src)) ||
+      (rc = Upload(&d->n_src, n_src)) || (rc = Upload(&d->e_arc, e_arc)) || (rc = Upload(&d->n_arc, n_arc)) ||
+      (rc = Upload(&d->final_w, f->final_w)))
+    return rc;
+  const size_t per = (size_t)S * max_utts;
+  HIP_TRY(hipMalloc(&d->key, sizeof(uint64_t) * per));
+  HIP_TRY(hipMemset(d->key, 0xFF, sizeof(uint64_t) * per));
+  HIP_TRY(hipMalloc(&d->tr, sizeof(int) * per));
+  HIP_TRY(hipMalloc(&d->mark, sizeof(int) * per));
+  HIP_TRY(hipMemset(d->mark, 0, sizeof(int) * per));
+  HIP_TRY(hipMalloc(&d->touched, sizeof(int) * per));
+  HIP_TRY(hipMalloc(&d->nxt, sizeof(int) * per));
+  HIP_TRY(hipMalloc(&d->lists, sizeof(Tok) * per * 4));
+  HIP_TRY(hipMalloc(&d->rec, sizeof(int2) * (size_t)d->trace_cap));
+  // The best paths of one call are disjoint chains of that call's trace records, so an arena of trace_capacity
+  // entries always holds them all.
+  HIP_TRY(hipMalloc(&d->path, sizeof(int) * (size_t)d->trace_cap));
+  d->path_cap = (int)d->trace_cap;
+  HIP_TRY(hipMalloc(&d->counters, sizeof(unsigned long long) * 2));
+  HIP_TRY(hipMalloc(&d->d_res, sizeof(UttResult) * max_utts));
+  HIP_TRY(hipMalloc(&d->d_off, sizeof(int64_t) * max_utts));
+  HIP_TRY(hipMalloc(&d->d_T, sizeof(int) * max_utts));
+  HIP_TRY(hipStreamCreateWithFlags(&d->own_stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&d->done, hipEventDisableTiming));
+  return 0;
+}
+
+// Queue one decode of num_utts utterances whose log-likelihoods lie at ll + off[u] (T[u] frames each) on `stream`.
+int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off, const std::vector<int> &T,
+           hipStream_t stream) {
+  const int n = (int)T.size();
+  if (d->pending) HIP_TRY(hipEventSynchronize(d->done));   // the previous call's work areas are about to be reused
+  d->pending = false; d->have = false; d->num_utts = n;
+  d->h_T = T;
+  d->h_off = off;
+  d->stream = stream;
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d->d_off, d->h_off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d->d_T, d->h_T.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * 2, stream));
+    DecArgs A;
+    A.e_off = d->e_off; A.e_arc = d->e_arc; A.e_src = d->e_src;
+    A.n_off = d->n_off; A.n_arc = d->n_arc; A.n_src = d->n_src;
+    A.final_w = d->final_w;
+    A.num_states = d->num_states; A.start = d->start; A.num_pdfs = d->num_pdfs;
+    A.ll = ll; A.ll_off = d->d_off; A.T = d->d_T; A.num_utts = n;
+    const size_t per = (size_t)d->num_states * d->max_utts;
+    A.key = d->key; A.tr = d->tr; A.mark = d->mark; A.touched = d->touched; A.nxt = d->nxt;
+    A.la = d->lists; A.lb = d->lists + per; A.fa = d->lists + 2 * per; A.fb = d->lists + 3 * per;
+    A.rec = d->rec; A.rec_cap = d->trace_cap; A.rec_top = d->counters;
+    A.path = d->path; A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
+    A.beam = d->beam; A.max_active = d->max_active;
+    A.max_rounds = d->num_states + 2;    // Bellman-Ford bound: more rounds only under a negative epsilon cycle
+    A.res = d->d_res;
+    hipLaunchKernelGGL(DecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
+  }
+  HIP_TRY(hipEventRecord(d->done, stream));
+  d->pending = true;
+  return 0;
+}
+
+int Collect(pk_mi355_decoder *d) {
+  if (!d->pending) return d->have ? 0 : Fail(PK_MI355_E_STATE, "decoder: nothing decoded");
+  int rc = UseDevice(d->device);
+  if (rc) return rc;
+  d->pending = false;
+  HIP_TRY(hipEventSynchronize(d->done));
+  if (d->batch) {                                    // the score call's range verdict: its results are withheld
+    pk_mi355_batch_t *b = d->batch;
+    d->batch = nullptr;
+    if ((rc = pk_mi355_batch_synchronize(b))) return rc;
+  }
+  const int n = d->num_utts;
+  d->res.resize(n);
+  if (n) HIP_TRY(hipMemcpy(d->res.data(), d->d_res, sizeof(UttResult) * n, hipMemcpyDeviceToHost));
+  int used = 0;
+  for (const auto &r : d->res) used = std::max(used, r.path_off + r.path_len);
+  d->h_path.resize(used);
+  if (used) HIP_TRY(hipMemcpy(d->h_path.data(), d->path, sizeof(int) * used, hipMemcpyDeviceToHost));
+  for (int u = 0; u < n; ++u) {
+    const UttResult &r = d->res[u];
+    if (r.status == PK_MI355_E_CAPACITY)
+      return Fail(PK_MI355_E_CAPACITY, "decoder: utterance %d: backtrace storage exhausted (trace_capacity %lld: raise it, "
+                  "or decode fewer utterances per call)", u, (long long)d->trace_cap);
+    if (r.status == PK_MI355_E_INVALID)
+      return Fail(PK_MI355_E_INVALID, "decoder: utterance %d: negative epsilon cycle (the closure did not settle)", u);
+    if (r.path_off < 0 || r.path_len < 0 || r.path_off + r.path_len > used)
+      return Fail(PK_MI355_E_DEVICE, "decoder: utterance %d: corrupt result", u);
+  }
+  d->have = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+pk_mi355_fst_t *pk_mi355_fst_read(const char *path) {
+  if (!path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
+  pk_mi355_fst *f = new pk_mi355_fst();
+  if (ReadFst(path, f)) { delete f; return nullptr; }
+  return f;
+}
+
+void pk_mi355_fst_destroy(pk_mi355_fst_t *fst) { delete fst; }
+int pk_mi355_fst_num_states(const pk_mi355_fst_t *fst) { return fst ? fst->num_states : Fail(PK_MI355_E_INVALID, "null graph"); }
+int pk_mi355_fst_num_arcs(const pk_mi355_fst_t *fst) { return fst ? fst->num_arcs : Fail(PK_MI355_E_INVALID, "null graph"); }
+int pk_mi355_fst_start(const pk_mi355_fst_t *fst) { return fst ? fst->start : Fail(PK_MI355_E_INVALID, "null graph"); }
+
+int pk_mi355_fst_arc_range(const pk_mi355_fst_t *fst, int state, int *first, int *count) {
+  if (!fst || state < 0 || state >= fst->num_states) return Fail(PK_MI355_E_INVALID, "bad graph state");
+  if (first) *first = fst->arc_first[state];
+  if (count) *count = fst->arc_count[state];
+  return 0;
+}
+
+pk_mi355_decoder_t *pk_mi355_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am, int max_utts,
+                                            int64_t trace_capacity) {
+  if (!fst || !am) { Fail(PK_MI355_E_INVALID, "null graph or model"); return nullptr; }
+  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (max_utts <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad decoder capacity"); return nullptr; }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_decoder *d = new pk_mi355_decoder();
+  d->device = am->device;
+  d->am = am;
+  if (CreateDecoder(d, fst, am, max_utts, trace_capacity)) {
+    FreeDecoderDevice(d);
+    delete d;
+    return nullptr;
+  }
+  return d;
+}
+
+void pk_mi355_decoder_destroy(pk_mi355_decoder_t *d) {
+  if (!d) return;
+  if (!UseDevice(d->device)) {
+    if (d->pending) hipEventSynchronize(d->done);
+    FreeDecoderDevice(d);
+  }
+  delete d;
+}
+
+int pk_mi355_decoder_set_beam(pk_mi355_decoder_t *d, float beam, int max_active) {
+  if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
+  if (!(beam >= 0.0f) || max_active <= 0) return Fail(PK_MI355_E_INVALID, "beam must be >= 0 and max_active > 0");
+  d->beam = beam;
+  d->max_active = max_active;
+  return 0;
+}
+
+int pk_mi355_decoder_decode_batch(pk_mi355_decoder_t *d, pk_mi355_batch_t *b, int sync) {
+  if (!d || !b) return Fail(PK_MI355_E_INVALID, "null decoder or batch");
+  if (!BatchScored(b)) return Fail(PK_MI355_E_STATE, "batch not scored");
+  if (BatchModel(b) != d->am)        // the pdf map the graph was checked and mapped with is that model's
+    return Fail(PK_MI355_E_INVALID, "decoder: the batch was scored with another model than the decoder was created for");
+  const int n = pk_mi355_batch_num_utts(b);
+  if (n > d->max_utts) return Fail(PK_MI355_E_INVALID, "decoder: %d utterances, capacity %d", n, d->max_utts);
+  int rc = UseDevice(d->device);
+  if (rc) return rc;
+  std::vector<int64_t> off(n);
+  std::vector<int> T(n);
+  const float *base = n ? pk_mi355_batch_loglik_device(b, 0) : nullptr;
+  for (int u = 0; u < n; ++u) {
+    T[u] = pk_mi355_batch_num_frames(b, u);
+    off[u] = pk_mi355_batch_loglik_device(b, u) - base;
+  }
+  d->batch = nullptr;
+  if ((rc = Launch(d, base, off, T, (hipStream_t)pk_mi355_batch_stream(b)))) return rc;
+  d->batch = b;
+  return sync ? Collect(d) : 0;
+}
+
+int pk_mi355_decoder_decode(pk_mi355_decoder_t *d, const pk_decodable_t *utts, int num_utts, int sync) {
+  if (!d || (num_utts > 0 && !utts) || num_utts < 0) return Fail(PK_MI355_E_INVALID, "bad decode arguments");
+  if (num_utts > d->max_utts) return Fail(PK_MI355_E_INVALID, "decoder: %d utterances, capacity %d", num_utts, d->max_utts);
+  int rc = UseDevice(d->device);
+  if (rc) return rc;
+  if (d->pending) HIP_TRY(hipEventSynchronize(d->done));   // d_ll may still be read by the previous call
+  std::vector<int64_t> off(num_utts);
+  std::vector<int> T(num_utts);
+  int64_t total = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    const pk_matrix_t &m = utts[u].log_prob;
+    if (m.ncol < 0 || (m.ncol > 0 && (m.nrow != d->num_pdfs || !m.data)))
+      return Fail(PK_MI355_E_INVALID, "decoder: utterance %d: log_prob is {ncol %d, nrow %d}, nrow %d expected", u, m.ncol,
+                  m.nrow, d->num_pdfs);
+    off[u] = total;
+    T[u] = m.ncol;
+    total += (int64_t)m.ncol * d->num_pdfs;
+  }
+  if ((size_t)total > d->d_ll_floats) {
+    if (d->d_ll) hipFree(d->d_ll);
+    d->d_ll = nullptr;
+    d->d_ll_floats = 0;
+    HIP_TRY(hipMalloc(&d->d_ll, sizeof(float) * (size_t)total));
+    d->d_ll_floats = (size_t)total;
+  }
+  for (int u = 0; u < num_utts; ++u)
+    if (T[u] > 0)
+      HIP_TRY(hipMemcpyAsync(d->d_ll + off[u], utts[u].log_prob.data, sizeof(float) * (size_t)T[u] * d->num_pdfs,
+                             hipMemcpyHostToDevice, d->own_stream));
+  d->batch = nullptr;
+  if ((rc = Launch(d, d->d_ll, off, T, d->own_stream))) return rc;
+  return sync ? Collect(d) : 0;
+}
+
+int pk_mi355_decoder_synchronize(pk_mi355_decoder_t *d) {
+  if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
+  return Collect(d);
+}
+
+static int CheckResult(const pk_mi355_decoder_t *d, int utt) {
+  if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
+  if (!d->have) return Fail(PK_MI355_E_STATE, "decoder: no results (synchronize first)");
+  if (utt < 0 || utt >= d->num_utts) return Fail(PK_MI355_E_INVALID, "bad utterance index");
+  return 0;
+}
+
+int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, int max_words, float *weight, int *ok) {
+  int rc = CheckResult(d, utt);
+  if (rc) return rc;
+  const UttResult &r = d->res[utt];
+  int n = 0;
+  for (int i = 0; i < r.path_len; ++i) {
+    const int arc = d->h_path[r.path_off + i];
+    const int w = (arc >= 0 && arc < (int)d->olabel.size()) ? d->olabel[arc] : 0;
+    if (w != 0) {
+      if (words && n < max_words) words[n] = w;
+      ++n;
+    }
+  }
+  if (weight) *weight = r.weight;
+  if (ok) *ok = r.ok;
+  return n;
+}
+
+int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs) {
+  int rc = CheckResult(d, utt);
+  if (rc) return rc;
+  const UttResult &r = d->res[utt];
+  for (int i = 0; i < r.path_len && i < max_arcs; ++i) arcs[i] = d->h_path[r.path_off + i];
+  return r.path_len;
+}
+
+int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt) {
+  int rc = CheckResult(d, utt);
+  if (rc) return rc;
+  return d->res[utt].active_bound;
+}
+
+}  // extern "C"

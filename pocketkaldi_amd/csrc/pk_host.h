@@ -287,6 +287,10 @@ inline ViewGen *GenOf(const pk_mi355_am_t *am) { return reinterpret_cast<ViewGen
 inline pk_mi355_am_t *Untag(pk_mi355_am_t *am) { return IsView(am) ? GenOf(am)->am : am; }
 void ReleaseArenaView(pk_mi355_am_t *handle);
 
+// what the decoder (decode.hip) needs to know of a batch beyond the ABI
+bool BatchScored(const pk_mi355_batch *b);
+const pk_mi355_am *BatchModel(const pk_mi355_batch *b);
+
 }  // namespace pkhost
 
 #endif  // PK_HOST_H_

@@ -1,0 +1,142 @@
+"""GPU decoder benchmark: 256 x 10 s utterances, model S, a synthetic word-loop graph of about 200 k
+states (pocketkaldi_amd/synth_graph.py).  Prints ONE JSON line and writes it to profiles/r06_decode.json:
+
+  score_ms / decode_ms      hipEvents on the batch's stream (score; decode_batch ordered after it)
+  gpu_frames_per_s          frames / (score + GPU decode)
+  max_active / max_active_bound   the max-active of the 256-utterance leg (model S's synthetic outputs are near-flat:
+                            at 30000 the backtrace of 256 x 1000 frames would not fit) and the largest active_bound
+  same_work                 the first `cpu_utts` utterances decoded by BOTH decoders at max-active 30000 (the
+                            reference's kBeamSize): GPU and CPU (reference decoder, oracle/_ref/libpkref_decoder.so,
+                            16 host threads) times, the reference's per-call graph load, and how many results agree
+
+    python tools/decode_bench.py [--utts 256] [--seconds 10] [--states 200000] [--cpu-utts 16] [--steps 3]
+                                 [--max-active 2000] [--trace-capacity 2^30]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402  (one HIP runtime in the process: the one torch loads, as bench.py)
+import numpy as np  # noqa: E402
+
+import pocketkaldi_amd as pk  # noqa: E402
+from pocketkaldi_amd import synth, synth_graph as SG  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--utts", type=int, default=256)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--states", type=int, default=200000)
+    ap.add_argument("--cpu-utts", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=3)
+    # model S's synthetic outputs are near-flat: without a tighter max-active every utterance keeps tens of
+    # thousands of tokens per frame, and the backtrace (no GC) of 256 x 1000 frames would not fit in HBM
+    ap.add_argument("--max-active", type=int, default=2000)
+    ap.add_argument("--trace-capacity", type=int, default=1 << 30)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r06_decode.json"))
+    a = ap.parse_args()
+
+    pk.set_device(0)
+    layers, prior, L, R = synth.model("S")
+    am = pk.AcousticModel(layers, prior, L, R)
+    waves = [synth.utterance(u, a.seconds) for u in range(a.utts)]
+    bs = pk.BatchScorer(am, synth.global_cmvn_stats(), a.utts, sum(len(w) for w in waves))
+    bs.set_waves(waves)
+    g = SG.size_for_states(a.states, seed=1)
+    tmp = tempfile.mkdtemp()
+    fst_path = os.path.join(tmp, "g.fst")
+    SG.write_fst(fst_path, g["start"], g["final"], g["arcs"])
+    fst = pk.Fst(fst_path)
+    dec = pk.Decoder(fst, am, a.utts, trace_capacity=a.trace_capacity)
+    dec.set_beam(16.0, a.max_active)
+    stream = torch.cuda.ExternalStream(bs.stream())
+    frames = bs.total_frames()
+    score_ms, decode_ms = [], []
+    for step in range(a.steps + 1):
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record(stream)
+        bs.score(0.1, sync=False)
+        e1.record(stream)
+        dec.decode_batch(bs, sync=False)
+        e2.record(stream)
+        dec.synchronize()
+        if step:                                     # the first pass warms up
+            score_ms.append(e0.elapsed_time(e1))
+            decode_ms.append(e1.elapsed_time(e2))
+    bound = max(dec.active_bound(u) for u in range(a.utts))
+    s_ms, d_ms = float(np.median(score_ms)), float(np.median(decode_ms))
+    res = dict(kind="decode", utts=a.utts, seconds=a.seconds, frames=int(frames), graph_states=fst.num_states(),
+               graph_arcs=fst.num_arcs(), beam=16.0, max_active=a.max_active, score_ms=round(s_ms, 3), decode_ms=round(d_ms, 3),
+               gpu_frames_per_s=round(frames / ((s_ms + d_ms) / 1e3)), max_active_bound=int(bound),
+               words_utt0=len(dec.result(0)[0]))
+    # Same work on both sides: the first cpu_utts utterances at the reference's own max-active (kBeamSize = 30000;
+    # pkref_decode cannot take another), decoded by the GPU decoder from the same fetch_all views and by the
+    # reference's decoder on 16 host threads.  pkref_decode reads the graph file on every call: that load is timed
+    # on its own (a T = 0 decodable) and reported beside the raw figure.
+    declib = os.path.join(REPO, "oracle", "_ref", "libpkref_decoder.so")
+    if os.path.exists(declib) and a.cpu_utts > 0:
+        L = C.CDLL(declib)
+        L.pkref_decode.argtypes = [C.c_char_p, C.POINTER(pk.pk_decodable_t), C.POINTER(C.c_int), C.c_int,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        n = min(a.cpu_utts, a.utts)
+        t0 = time.perf_counter()
+        views = bs.fetch_all()
+        t1 = time.perf_counter()
+        same = pk.Decoder(fst, am, n, trace_capacity=a.trace_capacity)
+        same.set_beam(16.0, 30000)
+        same.decode(views[:n])                               # warm-up (upload path, allocations)
+        g0 = time.perf_counter()
+        same.decode(views[:n])
+        g1 = time.perf_counter()
+
+        def run(u):
+            words = (C.c_int * 8192)()
+            w, ok = C.c_float(), C.c_int()
+            d = views[u]._d
+            k = L.pkref_decode(fst_path.encode(), C.byref(d), words, 8192, C.byref(w), C.byref(ok))
+            return list(words[:max(k, 0)]), w.value, ok.value
+
+        empty = pk.pk_decodable_t()
+        empty.am = am.handle
+        l0 = time.perf_counter()
+        for _ in range(3):
+            L.pkref_decode(fst_path.encode(), C.byref(empty), (C.c_int * 1)(), 1, C.byref(C.c_float()), C.byref(C.c_int()))
+        load_ms = (time.perf_counter() - l0) / 3 * 1e3
+        c0 = time.perf_counter()
+        with ThreadPoolExecutor(16) as ex:
+            ref = list(ex.map(run, range(n)))
+        c1 = time.perf_counter()
+        agree = sum(1 for u in range(n) if (same.result(u)[0], np.float32(same.result(u)[1]).tobytes(), same.result(u)[2])
+                    == (ref[u][0], np.float32(ref[u][1]).tobytes(), ref[u][2]))
+        fr = sum(bs.num_frames(u) for u in range(n))
+        cpu_ms = (c1 - c0) * 1e3
+        cpu_ms_noload = max(cpu_ms - -(-n // 16) * load_ms, 1e-3)
+        res["same_work"] = dict(
+            utts=n, frames=int(fr), max_active=30000, note="both decoders at max-active 30000 on the same fetch_all views; "
+            "gpu: pk_mi355_decoder_decode wall time (upload included, the n utterances use n CUs); cpu: the reference's "
+            "decoder on 16 host threads, whose pkref_decode re-reads the graph file on every call",
+            gpu_decode_ms=round((g1 - g0) * 1e3, 3), gpu_frames_per_s=round(fr / (g1 - g0)),
+            gpu_max_active_bound=max(same.active_bound(u) for u in range(n)),
+            cpu_decode_ms=round(cpu_ms, 3), cpu_frames_per_s=round(fr / (cpu_ms / 1e3)),
+            cpu_graph_load_ms_per_call=round(load_ms, 3),
+            cpu_decode_ms_without_graph_loads=round(cpu_ms_noload, 3),
+            cpu_frames_per_s_without_graph_loads=round(fr / (cpu_ms_noload / 1e3)),
+            identical_results=agree, fetch_all_ms=round((t1 - t0) * 1e3, 3))
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
