@@ -9,7 +9,9 @@
 //     and only tokens <= F (the exact non-emitting cutoff) form the next frame's list;
 //   * ties on a state go to the lowest candidate id (64-bit atomicMin of (ordered cost bits << 32) | id);
 //   * when max-active binds, the cutoff is the EXACT max_active-th smallest cost (radix select), not the
-//     reference's 200-cost sample (decoder.cc:137-168).
+//     reference's 200-cost sample (decoder.cc:137-168);
+//   * N1: a NaN log-likelihood decodes as -inf; N2: a frame that starts without a token of finite cost ends the
+//     utterance with ok = 0 (where the reference dereferences a null best_tok).
 // Compiled with -ffp-contract=off and no fast-math (build.py), like every other translation unit.
 #include <math.h>
 
@@ -282,8 +284,9 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
   for (int t = -1; t < T; ++t) {
     if (t >= 0) {
       // ---- ProcessEmitting (decoder.cc:226-301)
-      for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads) s_ll[p] = ll[(size_t)t * A.num_pdfs + p];
-      if (nL == 0) { ok = 0; break; }                 // the beam emptied: the reference dereferences a null best_tok
+      // N1: a NaN log-likelihood decodes as -inf (fmaxf returns the operand that is not NaN), its candidates as +inf
+      for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads)
+        s_ll[p] = fmaxf(ll[(size_t)t * A.num_pdfs + p], -INFINITY);
       // GetCutoff (:132-182): best token (lowest state on equal cost), exact max-active cutoff
       uint64_t bk = kEmpty;
       for (int i = threadIdx.x; i < nL; i += kDecThreads) {
@@ -293,6 +296,8 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
       bk = BlockMinU(sh, bk);
       const float best = OrdFloat(uint32_t(bk >> 32));
       const int best_state = int(uint32_t(bk));
+      // N2: no token of finite cost (or none at all: the beam emptied) -- the reference's best_tok stays null
+      if (!(best < INFINITY)) { ok = 0; break; }
       const double beam_cutoff = (double)best + (double)A.beam;
       float adaptive_beam = A.beam, weight_cutoff = (float)beam_cutoff;
       if (nL > A.max_active) {

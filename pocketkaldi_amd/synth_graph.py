@@ -12,6 +12,9 @@ The graph is a word loop:
   * optionally a silence word (id V + 1, one phone) on the same loop;
   * weights are random floats (no ties); final weights span less than the beam.
 Transition ids are 1 + 2 * (3 * phone + hmm_state) + (0 forward | 1 self-loop), all < num_pdfs.
+
+general() makes small graphs of no particular shape for the decoder's edge tests (tests/test_gpu_decode_edges.py),
+with dyadic weights and log-likelihoods (dyadic()) so that every float sum of a decode is exact.
 """
 import struct
 
@@ -110,3 +113,47 @@ def flat(num_frames, num_pdfs, seed, spread=0.05):
     """Nearly flat log-likelihoods: everything stays inside the beam (max-active binds)."""
     rng = np.random.default_rng(seed)
     return (-1.0 - spread * rng.random((num_frames, num_pdfs))).astype(np.float32)
+
+
+def general(num_states, seed, k=2, eps_k=12, num_pdfs=12, max_arcs=4, eps_frac=0.3, hubs=1, hub_arcs=40,
+            final_frac=0.3, empty_frac=0.08, neg_eps=True):
+    """A seeded graph of no particular shape -> dict(start=0, final, arcs (by state), num_pdfs).  Ilabels are pdfs
+    1 .. num_pdfs - 1 (identity map).  It has several final states (the rest +inf), states without arcs, parallel
+    arcs, emitting and epsilon self-loops, epsilon arcs of zero or negative weight and `hubs` states of `hub_arcs`
+    arcs.  Emitting weights are multiples of 2^-k in [-0.5, 3], epsilon weights multiples of 2^-eps_k: with the
+    log-likelihoods of dyadic(), every float32 sum of a decode of a few hundred frames is exact.  An epsilon arc
+    s -> t weighs phi(t) - phi(s) + r with a potential phi in [0, 2] (0 without neg_eps) and r >= 0 (0 in 10 %):
+    every epsilon cycle weighs the sum of its r >= 0, so there is no negative cycle, and zero-weight ones occur."""
+    rng = np.random.default_rng(seed)
+    q, qe = 2.0 ** -k, 2.0 ** -eps_k
+
+    def grid(lo, hi, step):
+        return float(rng.integers(round(lo / step), round(hi / step) + 1)) * step
+
+    phi = [grid(0.0, 2.0, qe) if neg_eps else 0.0 for _ in range(num_states)]
+    hub_set = set(int(x) for x in rng.choice(num_states, min(hubs, num_states), replace=False)) if hubs else set()
+    arcs = [[] for _ in range(num_states)]
+    for s in range(num_states):
+        if s != 0 and s not in hub_set and rng.random() < empty_frac:
+            continue
+        for i in range(hub_arcs if s in hub_set else int(rng.integers(1, max_arcs + 1))):
+            nxt = s if rng.random() < 0.1 else int(rng.integers(num_states))
+            ol = int(rng.integers(1, 50)) if rng.random() < 0.3 else 0
+            if i and rng.random() < eps_frac:                        # the first arc of a state emits
+                r = 0.0 if rng.random() < 0.1 else grid(0.0, 1.0, qe)
+                arcs[s].append((nxt, 0, ol, phi[nxt] - phi[s] + r))
+            else:
+                arcs[s].append((nxt, int(rng.integers(1, num_pdfs)), ol, grid(-0.5, 3.0, q)))
+            if arcs[s][-1][1] and rng.random() < 0.1:                # a parallel emitting arc: same ends, maybe a twin
+                a = arcs[s][-1]
+                arcs[s].append(a if rng.random() < 0.5 else (a[0], a[1], int(rng.integers(0, 50)), a[3]))
+    final = np.array([grid(0.0, 3.0, q) if rng.random() < final_frac else np.inf for _ in range(num_states)], np.float32)
+    final[int(rng.integers(num_states))] = grid(0.0, 3.0, q)
+    return dict(start=0, final=final, arcs=arcs, num_pdfs=num_pdfs)
+
+
+def dyadic(num_frames, num_pdfs, seed, k=2, lo=-4.0, hi=2.0):
+    """Log-likelihoods [T][num_pdfs], multiples of 2^-k in [lo, hi] (float32, exact)."""
+    rng = np.random.default_rng(seed)
+    q = 2.0 ** -k
+    return (rng.integers(round(lo / q), round(hi / q) + 1, (num_frames, num_pdfs)) * q).astype(np.float32)

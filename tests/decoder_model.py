@@ -1,7 +1,9 @@
 """A small host model of the GPU decoder's semantics (DESIGN.md "Decoder"), float32 arithmetic where the
 reference computes in float and float64 where it computes in double (decoder.cc:132-339).  Slow; for
 small graphs only.  Order-independent by construction: candidates keyed (cost, candidate id), the
-epsilon closure run to its fixed point, the exact max_active-th cost as the max-active cutoff."""
+epsilon closure run to its fixed point, the exact max_active-th cost as the max-active cutoff.  Non-finite
+log-likelihoods: N1, a NaN decodes as -inf; N2, a frame that starts without a token of finite cost ends the
+utterance with ok = 0."""
 import numpy as np
 
 f32, f64 = np.float32, np.float64
@@ -28,10 +30,18 @@ def split(arcs_by_state):
 
 def decode(fst, ll, pdf_of, beam=16.0, max_active=30000, arc_ids=None):
     """fst = (start, final, arcs_by_state) with arcs (next, ilabel, olabel, weight[, arc id]).
-    -> dict(words, weight, ok, active_bound, path)."""
+    -> dict(words, weight, ok, active_bound, path, determined).
+
+    `determined` is False when the best path (words, arcs) may legitimately depend on the order of the epsilon
+    closure: at some closure's fixed point a state won by an epsilon arc has a second epsilon candidate of its
+    final cost.  A source that improves at equal cost (a lower candidate id only) does not re-resolve the
+    successors it already reached, so the GPU's frontier order and this model's stack order can then keep
+    different, equally cheap paths.  Weight, ok and active_bound never depend on the order."""
     start, final, arcs = fst
     emit, eps, ids_e, ids_n = split(arcs)
     beam = f32(beam)
+    ll = np.where(np.isnan(ll), f32(-np.inf), ll).astype(f32)          # N1
+    determined = True
 
     def closure(tok, F):
         work = [s for s, v in tok.items() if not v[0] > F]
@@ -46,6 +56,20 @@ def decode(fst, ll, pdf_of, beam=16.0, max_active=30000, arc_ids=None):
                 if a[0] not in tok or k < tok[a[0]][:2]:
                     tok[a[0]] = (cc, k[1], path + [a])
                     work.append(a[0])
+        nonlocal determined
+        ties = {}
+        for s, (c, _, _) in tok.items():
+            if c > F:
+                continue
+            for a in eps[s]:
+                cc = f32(c + f32(a[3]))
+                if cc > F:
+                    continue
+                v = tok[a[0]]
+                if v[1] >= EPS_ID and cc == v[0]:
+                    ties[a[0]] = ties.get(a[0], 0) + 1
+        if any(n > 1 for n in ties.values()):
+            determined = False
         return tok
 
     tok = closure({start: (f32(0.0), -1, [])}, f32(np.inf))
@@ -54,7 +78,7 @@ def decode(fst, ll, pdf_of, beam=16.0, max_active=30000, arc_ids=None):
     ok = 1
     for t in range(ll.shape[0]):
         L = sorted((v[0], s, v[2]) for s, v in tok.items() if not v[0] > F)
-        if not L:
+        if not L or not L[0][0] < np.inf:                             # N2 (and the empty beam)
             ok = 0
             break
         best, best_state = L[0][0], L[0][1]
@@ -86,18 +110,18 @@ def decode(fst, ll, pdf_of, beam=16.0, max_active=30000, arc_ids=None):
         active = max(active, len(tok))
     L = [(v[0], s, v[2]) for s, v in tok.items() if not v[0] > F] if ok else []
     if not L:
-        return dict(words=[], weight=0.0, ok=0, active_bound=active, path=[])
+        return dict(words=[], weight=0.0, ok=0, active_bound=active, path=[], determined=determined)
     bc, bs, bp = np.inf, -1, None
     for c, s, path in sorted(L, key=lambda x: x[1]):
         v = f64(c) + f64(final[s])
         if v != np.inf and v < bc:
             bc, bs, bp = v, s, path
     if bs < 0:
-        return dict(words=[], weight=0.0, ok=1, active_bound=active, path=[])
+        return dict(words=[], weight=0.0, ok=1, active_bound=active, path=[], determined=determined)
     w = f32(bc)
     w = f32(w + f32(final[bs]))
     return dict(words=[a[2] for a in bp if a[2] != 0], weight=float(w), ok=1, active_bound=active,
-                path=[a[4] for a in bp] if bp and len(bp[0]) > 4 else None)
+                path=[a[4] for a in bp] if bp and len(bp[0]) > 4 else None, determined=determined)
 
 
 
