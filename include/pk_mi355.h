@@ -446,6 +446,100 @@ int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, in
 int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs);
 int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt);
 
+/* ------------------------------------------------------------------------- */
+/* Online scorer -- live PCM in chunks, pk_process's acoustic stages (pocketkaldi.cc: */
+/* 176-218) frame by frame as frames become final; DESIGN.md section 10.             */
+/* ------------------------------------------------------------------------- */
+
+/* The reference pipeline is causal: fbank frame t reads samples [160 t, 160 t + 400) (fbank.cc:35-42),
+ * CMVN is online (cmvn.cc:35-71: a running window sum rounded to float every frame), and the splice needs R
+ * frames of look-ahead and clamps only at the first and last frame (am.cc:65-88).  So every frame's
+ * log-likelihoods equal those of pk_mi355_batch_score on the whole wave bit for bit, whatever the chunk sizes.
+ *
+ * A stream object has max_streams slots.  A slot is opened, fed PCM any number of times, and closed; each
+ * pk_mi355_stream_step scores, for every slot, the frames that became final since the last step: frames
+ * [a, n - R) while the slot is open (n: frames whose 400 samples have arrived, R: the model's right context),
+ * frames [a, n) in the step after pk_mi355_stream_close (the right edge replicated, am.cc:73-75).  That step
+ * frees the slot; it may then be opened again.  A slot closed with fewer than 400 samples yields no frames.
+ *
+ * F32 models only (PK_MI355_PRECISION_F32, both softmax modes); an F16X3 or F16 model is refused with
+ * PK_MI355_E_INVALID (their calibration and range verdict are per batch).  Capacity: max_step_samples PCM
+ * samples pushed, over all slots, between two steps.  global_stats41: as pk_mi355_batch_create.  Like a
+ * batch, a stream object belongs to one host thread at a time.  Device memory per slot: 96 000 bytes of
+ * CMVN window + 3 360 bytes + 160 x (L + R) bytes; per object: step buffers sized by max_step_samples
+ * (DESIGN.md section 10).                                                                              */
+typedef struct pk_mi355_stream pk_mi355_stream_t;
+pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams,
+                                          int64_t max_step_samples);
+void pk_mi355_stream_destroy(pk_mi355_stream_t *s);
+/* PK_MI355_E_STATE if the slot is open, or closed and not yet flushed by a step.                   */
+int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot);
+/* Append host PCM (float sample values as pk_16kpcm_read produces them, pcm_reader.cc:189-211) to an
+ * open slot; copied, the caller's buffer is free on return.  num_samples may be 0.  A push that would take
+ * the samples pending for the next step beyond max_step_samples fails with PK_MI355_E_INVALID and
+ * consumes nothing; a push to a slot that is not open fails with PK_MI355_E_STATE.                    */
+int pk_mi355_stream_push(pk_mi355_stream_t *s, int slot, const float *samples, int num_samples);
+/* Same, int16 samples (the WAV payload itself; exact in float).                                      */
+int pk_mi355_stream_push_i16(pk_mi355_stream_t *s, int slot, const int16_t *samples, int num_samples);
+/* No more samples: the next step flushes the frames held back for look-ahead.                        */
+int pk_mi355_stream_close(pk_mi355_stream_t *s, int slot);
+/* One step for every open or closed-but-unflushed slot (PK_MI355_E_STATE if there is none): fbank, CMVN
+ * carried over from the slot's last step, layer stack and log-likelihood tail, all on the stream object's
+ * HIP stream.  Asynchronous unless sync != 0.  The results of the previous step are void from here on.  */
+int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync);
+int pk_mi355_stream_synchronize(pk_mi355_stream_t *s);
+/* The rows the last step scored for slot: device pointer to [count][num_pdfs] log-likelihoods of frames
+ * first_frame .. first_frame + count - 1 (NULL and count 0 if it scored none).  Valid until the next step;
+ * read on the stream object's stream or after pk_mi355_stream_synchronize.                            */
+const float *pk_mi355_stream_loglik_device(const pk_mi355_stream_t *s, int slot, int *first_frame, int *count);
+/* The same rows copied into a host decodable ({ncol = count, nrow = num_pdfs}, malloc'd like
+ * pk_mi355_batch_fetch; release with pk_decodable_destroy); *first_frame (may be NULL) receives the
+ * global index of its frame 0.  Synchronous.                                                          */
+int pk_mi355_stream_fetch(pk_mi355_stream_t *s, int slot, pk_decodable_t *out, int *first_frame);
+
+/* ------------------------------------------------------------------------- */
+/* Online decoder -- Decoder::Decode (decoder.cc:49-70) frame-synchronous across calls: */
+/* partial hypotheses while a stream is live, BestPath (decoder.cc:304-339) at its end. */
+/* ------------------------------------------------------------------------- */
+
+/* Semantics are the batch decoder's (N1, N2, exact max-active, the three documented
+ * differences): a slot fed its frames in chunks of any size ends with the words, weight bits, ok, best-path arcs
+ * and active_bound of pk_mi355_decoder_decode on the whole utterance.  Each slot has a backtrace arena of
+ * trace_capacity records (8 bytes each; 0 = 2^20); when one is more than half full between two frames its
+ * reachable records are compacted, and a slot still full ends with PK_MI355_E_CAPACITY
+ * while the other slots go on.  Device memory: the batch decoder's with max_utts = max_streams and
+ * max_streams x trace_capacity records, plus 4 bytes per record.  One host thread at a time.             */
+typedef struct pk_mi355_online_decoder pk_mi355_online_decoder_t;
+pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am, int max_streams,
+                                                          int64_t trace_capacity);
+void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *d);
+/* Decoder::beam_ and kBeamSize, as pk_mi355_decoder_set_beam (takes effect at the next advance).             */
+int pk_mi355_online_decoder_set_beam(pk_mi355_online_decoder_t *d, float beam, int max_active);
+/* Start an utterance in slot (InitDecoding runs with its first frames).  PK_MI355_E_STATE if it is open.    */
+int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *d, int slot);
+/* The rows the online scorer's last pk_mi355_stream_step scored, slot for slot (decoder slot i takes scorer slot
+ * i; the scorer needs no more slots than the decoder), read in HBM and queued on the scorer's stream after its
+ * step.  A slot the step flushed (it was closed) is finished: BestPath runs.  Only open decoder slots take part.
+ * Call it after every step and before the next one.                                                         */
+int pk_mi355_online_decoder_advance(pk_mi355_online_decoder_t *d, pk_mi355_stream_t *s, int sync);
+/* Host chunks: chunks[i] ({ncol = frames, nrow = num_pdfs}, ncol may be 0) continues open slot slots[i];
+ * final_[i] != 0 (final_ may be NULL) finishes the slot after them.  Copied before the call returns.         */
+int pk_mi355_online_decoder_advance_host(pk_mi355_online_decoder_t *d, const int *slots, const pk_decodable_t *chunks,
+                                         const int *final_, int n, int sync);
+/* Waits for the last advance.  PK_MI355_E_CAPACITY / PK_MI355_E_INVALID name the first slot of that call that
+ * ended so (the others' results stay readable).                                                              */
+int pk_mi355_online_decoder_synchronize(pk_mi355_online_decoder_t *d);
+/* The partial hypothesis after the slot's last advance: the path of the best token (lowest cost, lowest state on
+ * a tie, no final weight), its words in spoken order (at most max_words written) and its cost; the word count is
+ * returned.  After the slot's final advance this is the final result.                                        */
+int pk_mi355_online_decoder_partial(const pk_mi355_online_decoder_t *d, int slot, int *words, int max_words, float *cost);
+/* A finished slot: as pk_mi355_decoder_result.  PK_MI355_E_STATE before the slot's final advance.             */
+int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *d, int slot, int *words, int max_words, float *weight,
+                                   int *ok);
+/* Test hooks, as pk_mi355_decoder_best_path_arcs / _active_bound (the arcs of the partial path while live).  */
+int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *d, int slot, int32_t *arcs, int max_arcs);
+int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *d, int slot);
+
 /* Library / device facts */
 int pk_mi355_device_count(void);
 const char *pk_mi355_version(void);

@@ -11,6 +11,8 @@
 //   pk_decodable_init/_destroy/_loglikelihood/_islastframe               src/decodable.h:20-41
 //   pocketkaldi::Fst::Read / CountArcs                                   src/fst.h
 //   pocketkaldi::Decoder(fst, am).Decode(pk_decodable_t*) / BestPath()   src/decoder.h (on the GPU)
+//   pocketkaldi::OnlineScorer(am, stats, ...).Push / Step / Fetch        live PCM, frames scored as they become final
+//   pocketkaldi::OnlineDecoder(fst, am, ...).Advance / Partial / Result  the search over them, partial text while live
 //
 // Error behaviour: the reference reports load errors through Status and treats misuse as
 // assert(); here load / device errors surface as pocketkaldi::Status (ok() / what()), and the
@@ -229,6 +231,76 @@ class Decoder {
 
  private:
   pk_mi355_decoder_t *d_;
+  Status status_;
+};
+
+// Online scoring of live streams (pk_mi355_stream_*): PCM pushed per slot in chunks; every
+// Step() scores the frames that became final since the last one, bit for bit what the whole wave gives.
+class OnlineScorer {
+ public:
+  OnlineScorer(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples)
+      : s_(pk_mi355_stream_create(am, global_stats41, max_streams, max_step_samples)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  ~OnlineScorer() { pk_mi355_stream_destroy(s_); }
+  OnlineScorer(const OnlineScorer &) = delete;
+  OnlineScorer &operator=(const OnlineScorer &) = delete;
+
+  Status Open(int slot) { return Status::FromLast(pk_mi355_stream_open(s_, slot)); }
+  Status Push(int slot, const float *samples, int num_samples) {
+    return Status::FromLast(pk_mi355_stream_push(s_, slot, samples, num_samples));
+  }
+  Status PushI16(int slot, const int16_t *samples, int num_samples) {
+    return Status::FromLast(pk_mi355_stream_push_i16(s_, slot, samples, num_samples));
+  }
+  Status Close(int slot) { return Status::FromLast(pk_mi355_stream_close(s_, slot)); }
+  // Synchronous: the rows are ready on return.
+  Status Step(float prob_scale) { return Status::FromLast(pk_mi355_stream_step(s_, prob_scale, 1)); }
+  // The rows the last Step() scored for slot, as a host decodable ({ncol = count, nrow = num_pdfs}; release with
+  // pk_decodable_destroy) and the global index of its first frame.
+  Status Fetch(int slot, pk_decodable_t *out, int *first_frame) {
+    return Status::FromLast(pk_mi355_stream_fetch(s_, slot, out, first_frame));
+  }
+
+  const Status &last_status() const { return status_; }
+  pk_mi355_stream_t *handle() const { return s_; }
+
+ private:
+  pk_mi355_stream_t *s_;
+  Status status_;
+};
+
+// The search of pk_process frame by frame across calls (pk_mi355_online_decoder_*): Advance() after every
+// OnlineScorer::Step(), Partial() while the stream is live, Result() once its slot is finished.
+class OnlineDecoder {
+ public:
+  OnlineDecoder(const Fst *fst, pk_mi355_am_t *am, int max_streams)
+      : d_(pk_mi355_online_decoder_create(fst->handle(), am, max_streams, 0)) {
+    if (!d_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  ~OnlineDecoder() { pk_mi355_online_decoder_destroy(d_); }
+  OnlineDecoder(const OnlineDecoder &) = delete;
+  OnlineDecoder &operator=(const OnlineDecoder &) = delete;
+
+  Status Open(int slot) { return Status::FromLast(pk_mi355_online_decoder_open(d_, slot)); }
+  Status Advance(OnlineScorer *scorer) { return Status::FromLast(pk_mi355_online_decoder_advance(d_, scorer->handle(), 1)); }
+  // words in spoken order
+  std::vector<int> Partial(int slot, float *cost) const {
+    const int n = pk_mi355_online_decoder_partial(d_, slot, nullptr, 0, cost);
+    std::vector<int> w(n > 0 ? n : 0);
+    if (n > 0) pk_mi355_online_decoder_partial(d_, slot, w.data(), n, cost);
+    return w;
+  }
+  std::vector<int> Result(int slot, float *weight, int *ok) const {
+    const int n = pk_mi355_online_decoder_result(d_, slot, nullptr, 0, weight, ok);
+    std::vector<int> w(n > 0 ? n : 0);
+    if (n > 0) pk_mi355_online_decoder_result(d_, slot, w.data(), n, weight, ok);
+    return w;
+  }
+  const Status &last_status() const { return status_; }
+
+ private:
+  pk_mi355_online_decoder_t *d_;
   Status status_;
 };
 

@@ -11,8 +11,10 @@ benchmark; it mirrors the reference's class names and argument meaning:
     AcousticModel.propagate(x)               nnet.h:96       Nnet::Propagate
     Decodable(am, prob_scale, feats)         decodable.h:22-41
     BatchScorer(am, global_stats, ...)       pocketkaldi.cc:176-218 stages, batched
+    OnlineScorer(am, global_stats, ...)      the same stages on live PCM chunks, frame by frame as frames become final
     Fst(path)                                fst.h           Fst::Read, CountArcs
     Decoder(fst, am, max_utts)               decoder.h       Decoder::Decode + BestPath, batched on the GPU
+    OnlineDecoder(fst, am, max_streams)      the same search frame by frame across calls, partial hypotheses
 
 There is no CPU fallback: if the library is missing or no gfx950 device is usable,
 every compute call raises ``PkError``.
@@ -25,7 +27,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "Fst", "Decoder", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -75,6 +77,13 @@ EXPORTS = [
     "pk_mi355_fst_arc_range", "pk_mi355_decoder_create", "pk_mi355_decoder_destroy", "pk_mi355_decoder_set_beam",
     "pk_mi355_decoder_decode_batch", "pk_mi355_decoder_decode", "pk_mi355_decoder_synchronize", "pk_mi355_decoder_result",
     "pk_mi355_decoder_best_path_arcs", "pk_mi355_decoder_active_bound", "pk_mi355_last_error_code",
+    "pk_mi355_stream_create", "pk_mi355_stream_destroy", "pk_mi355_stream_open", "pk_mi355_stream_push",
+    "pk_mi355_stream_push_i16", "pk_mi355_stream_close", "pk_mi355_stream_step", "pk_mi355_stream_synchronize",
+    "pk_mi355_stream_loglik_device", "pk_mi355_stream_fetch",
+    "pk_mi355_online_decoder_create", "pk_mi355_online_decoder_destroy", "pk_mi355_online_decoder_set_beam",
+    "pk_mi355_online_decoder_open", "pk_mi355_online_decoder_advance", "pk_mi355_online_decoder_advance_host",
+    "pk_mi355_online_decoder_synchronize", "pk_mi355_online_decoder_partial", "pk_mi355_online_decoder_result",
+    "pk_mi355_online_decoder_best_path_arcs", "pk_mi355_online_decoder_active_bound",
 ]
 
 
@@ -204,6 +213,33 @@ def lib():
     L.pk_mi355_decoder_result.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.POINTER(C.c_int)]
     L.pk_mi355_decoder_best_path_arcs.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
     L.pk_mi355_decoder_active_bound.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_stream_create.restype = C.c_void_p
+    L.pk_mi355_stream_create.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int64]
+    L.pk_mi355_stream_destroy.restype = None
+    L.pk_mi355_stream_destroy.argtypes = [C.c_void_p]
+    L.pk_mi355_stream_open.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_stream_push.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int]
+    L.pk_mi355_stream_push_i16.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int16), C.c_int]
+    L.pk_mi355_stream_close.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_stream_step.argtypes = [C.c_void_p, C.c_float, C.c_int]
+    L.pk_mi355_stream_synchronize.argtypes = [C.c_void_p]
+    L.pk_mi355_stream_loglik_device.restype = C.c_void_p
+    L.pk_mi355_stream_loglik_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_stream_fetch.argtypes = [C.c_void_p, C.c_int, C.POINTER(pk_decodable_t), C.POINTER(C.c_int)]
+    L.pk_mi355_online_decoder_create.restype = C.c_void_p
+    L.pk_mi355_online_decoder_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]
+    L.pk_mi355_online_decoder_destroy.restype = None
+    L.pk_mi355_online_decoder_destroy.argtypes = [C.c_void_p]
+    L.pk_mi355_online_decoder_set_beam.argtypes = [C.c_void_p, C.c_float, C.c_int]
+    L.pk_mi355_online_decoder_open.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_advance.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_advance_host.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(pk_decodable_t),
+                                                       C.POINTER(C.c_int), C.c_int, C.c_int]
+    L.pk_mi355_online_decoder_synchronize.argtypes = [C.c_void_p]
+    L.pk_mi355_online_decoder_partial.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p]
+    L.pk_mi355_online_decoder_result.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.POINTER(C.c_int)]
+    L.pk_mi355_online_decoder_best_path_arcs.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
+    L.pk_mi355_online_decoder_active_bound.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 
@@ -627,6 +663,69 @@ class BatchScorer:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KINDS)}
 
 
+class OnlineScorer:
+    """Live PCM in chunks per slot: every step() scores the frames that became final since the last one (frames
+    [a, n - R) of an open slot, the rest after close()), bit for bit what BatchScorer gives on the whole wave."""
+
+    def __init__(self, am, global_stats, max_streams, max_step_samples):
+        g = _f32(global_stats)
+        if g.shape != (41,):
+            raise PkError("global_stats must have 41 entries")
+        self._am = am
+        self._h = lib().pk_mi355_stream_create(am.handle, _fp(g), int(max_streams), int(max_step_samples))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def open(self, slot):
+        _check_code(lib().pk_mi355_stream_open(self._h, int(slot)))
+
+    def push(self, slot, samples):
+        """float sample values (as read_wav gives them); an int16 array goes through push_i16."""
+        if isinstance(samples, np.ndarray) and samples.dtype == np.int16:
+            return self.push_i16(slot, samples)
+        x = _f32(samples)
+        _check_code(lib().pk_mi355_stream_push(self._h, int(slot), _fp(x) if x.size else None, x.shape[0]))
+
+    def push_i16(self, slot, samples):
+        x = np.ascontiguousarray(samples, dtype=np.int16)
+        _check_code(lib().pk_mi355_stream_push_i16(self._h, int(slot),
+                                                   x.ctypes.data_as(C.POINTER(C.c_int16)) if x.size else None, x.shape[0]))
+
+    def close(self, slot):
+        _check_code(lib().pk_mi355_stream_close(self._h, int(slot)))
+
+    def step(self, prob_scale=0.1, sync=True):
+        _check_code(lib().pk_mi355_stream_step(self._h, float(prob_scale), 1 if sync else 0))
+
+    def synchronize(self):
+        _check_code(lib().pk_mi355_stream_synchronize(self._h))
+
+    def loglik_device(self, slot):
+        """(device pointer or None, first frame, count) of the rows the last step scored for slot."""
+        first, count = C.c_int(), C.c_int()
+        p = lib().pk_mi355_stream_loglik_device(self._h, int(slot), C.byref(first), C.byref(count))
+        return p, first.value, count.value
+
+    def fetch(self, slot):
+        """(first frame, float32 [count][num_pdfs]) of the rows the last step scored for slot."""
+        d, first = pk_decodable_t(), C.c_int()
+        _check_code(lib().pk_mi355_stream_fetch(self._h, int(slot), C.byref(d), C.byref(first)))
+        if d.log_prob.ncol == 0:
+            return first.value, np.zeros((0, self._am.num_pdfs()), dtype=np.float32)
+        return first.value, _take_matrix(d.log_prob)
+
+
 class PkCodeError(PkError):
     """A PkError that carries the library's negative status code."""
 
@@ -749,3 +848,81 @@ class Decoder:
 
     def active_bound(self, utt):
         return _check_code(lib().pk_mi355_decoder_active_bound(self._h, int(utt)))
+
+
+class OnlineDecoder:
+    """Decoder::Decode frame-synchronous across calls: open(slot), advance(scorer) after every OnlineScorer.step (or
+    advance_host with log-likelihood chunks), partial(slot) after every call, result(slot) once the slot is finished."""
+
+    def __init__(self, fst, am, max_streams, trace_capacity=0):
+        self._fst, self._am = fst, am
+        self._h = lib().pk_mi355_online_decoder_create(fst.handle, am.handle, int(max_streams), int(trace_capacity))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self._keep = None
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_online_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def set_beam(self, beam=16.0, max_active=30000):
+        _check_code(lib().pk_mi355_online_decoder_set_beam(self._h, float(beam), int(max_active)))
+
+    def open(self, slot):
+        _check_code(lib().pk_mi355_online_decoder_open(self._h, int(slot)))
+
+    def advance(self, scorer, sync=True):
+        """The rows of the OnlineScorer's last step, slot for slot, read in HBM."""
+        self._keep = scorer
+        _check_code(lib().pk_mi355_online_decoder_advance(self._h, scorer._h, 1 if sync else 0))
+
+    def advance_host(self, chunks, sync=True):
+        """chunks: {slot: (loglik [frames][num_pdfs], final)}."""
+        items = sorted(chunks.items())
+        n = len(items)
+        slots = (C.c_int * max(n, 1))(*[s for s, _ in items])
+        fin = (C.c_int * max(n, 1))(*[1 if f else 0 for _, (_, f) in items])
+        arr, keep = (pk_decodable_t * max(n, 1))(), []
+        for i, (_, (x, _)) in enumerate(items):
+            a = _f32(x).reshape(-1, self._am.num_pdfs())
+            keep.append(a)
+            arr[i].log_prob.ncol, arr[i].log_prob.nrow = a.shape
+            arr[i].log_prob.data = _fp(a) if a.size else None
+            arr[i].am = self._am.handle
+        _check_code(lib().pk_mi355_online_decoder_advance_host(self._h, slots, arr, fin, n, 1 if sync else 0))
+
+    def synchronize(self):
+        _check_code(lib().pk_mi355_online_decoder_synchronize(self._h))
+
+    def partial(self, slot):
+        """(words in spoken order, cost) of the best token's path after the slot's last call."""
+        cost = C.c_float()
+        n = _check_code(lib().pk_mi355_online_decoder_partial(self._h, int(slot), None, 0, C.byref(cost)))
+        words = np.zeros(max(n, 1), np.int32)
+        lib().pk_mi355_online_decoder_partial(self._h, int(slot), words.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(cost))
+        return [int(w) for w in words[:n]], cost.value
+
+    def result(self, slot):
+        """(words in spoken order, weight, ok) of a finished slot, as Decoder.result."""
+        weight, ok = C.c_float(), C.c_int()
+        n = _check_code(lib().pk_mi355_online_decoder_result(self._h, int(slot), None, 0, C.byref(weight), C.byref(ok)))
+        words = np.zeros(max(n, 1), np.int32)
+        lib().pk_mi355_online_decoder_result(self._h, int(slot), words.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                             C.byref(weight), C.byref(ok))
+        return [int(w) for w in words[:n]], weight.value, ok.value
+
+    def best_path_arcs(self, slot):
+        n = _check_code(lib().pk_mi355_online_decoder_best_path_arcs(self._h, int(slot), None, 0))
+        arcs = np.zeros(max(n, 1), np.int32)
+        lib().pk_mi355_online_decoder_best_path_arcs(self._h, int(slot), arcs.ctypes.data_as(C.POINTER(C.c_int32)), n)
+        return [int(a) for a in arcs[:n]]
+
+    def active_bound(self, slot):
+        return _check_code(lib().pk_mi355_online_decoder_active_bound(self._h, int(slot)))

@@ -434,6 +434,263 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
   }
 }
 
+
+// ================================================================== online decoding (pk_mi355_online_decoder_*)
+// The same frame step as DecodeKernel, resumable: a slot's token list, its count and buffer, ok / status, the
+// largest touched count, the frames decoded and its trace-arena top live in HBM between launches.  One workgroup per
+// slot with new frames; InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot
+// has an arena of its own; when it is more than half full between two frames the reachable records are compacted
+// (CompactTrace).  DecodeKernel itself is not touched: the whole-utterance path compiles to the same code as before.
+
+struct OnlineState {
+  int nL, par;            // tokens of the current list and which of the slot's two list buffers holds them
+  int ok, status;         // N2 / capacity / closure verdicts: a slot that ended stays ended
+  int active, frames;     // largest touched count; frames decoded
+  int started, pad;
+  unsigned long long top; // records used in the slot's arena
+};
+
+struct OnlineResult {
+  int status, ok, final_, path_len;
+  float weight;           // final: Hypothesis::weight(); partial: the best token's cost
+  int active_bound, frames, has_path;
+};
+
+struct OnlineCall {       // one slot of a launch
+  int slot, T, final_, fresh;
+  int64_t ll_off;
+};
+
+// Mark the records reachable from the list's tokens, renumber them in creation order with an exclusive scan (a
+// record's predecessor is always older, so one forward pass remaps every `prev`), move them down, and rewrite the
+// tokens' trace (and the state table's, which the next emitting step reads).  Changes where records live, never a
+// result.
+__device__ void CompactTrace(Shared &sh, int2 *rec, int *remap, unsigned long long *top, Tok *L, int nL, int *tr) {
+  const int n = (int)*top;
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += kDecThreads) remap[i] = 0;
+  __syncthreads();
+  for (int j = threadIdx.x; j < nL; j += kDecThreads)
+    for (int x = L[j].trace; x >= 0 && atomicExch(&remap[x], 1) == 0;) x = rec[x].x;
+  __syncthreads();
+  int base = 0;
+  for (int c0 = 0; c0 < n; c0 += kDecThreads) {
+    const int i = c0 + threadIdx.x;
+    const int alive = i < n ? __hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;   // set by atomics
+    int2 r = make_int2(-1, -1);
+    if (alive) r = rec[i];
+    int total;
+    const int ex = BlockScan(sh, alive, &total);    // (its barriers: every read of this chunk is done)
+    if (i < n) remap[i] = alive ? base + ex : -1;
+    __syncthreads();
+    if (alive) {
+      r.x = r.x >= 0 ? remap[r.x] : -1;            // older: remapped in this chunk or an earlier one
+      rec[base + ex] = r;
+    }
+    base += total;
+    __syncthreads();
+  }
+  for (int j = threadIdx.x; j < nL; j += kDecThreads) {
+    const int x = L[j].trace;
+    if (x >= 0) {
+      L[j].trace = remap[x];
+      tr[L[j].state] = remap[x];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *top = (unsigned long long)base;
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, const OnlineCall *calls, OnlineState *states,
+                                                                    OnlineResult *results, int *remap_all, int64_t cap) {
+  extern __shared__ float s_ll[];
+  __shared__ Shared sh;
+  const OnlineCall call = calls[blockIdx.x];
+  const int u = call.slot;
+  const size_t S = (size_t)A.num_states;
+  uint64_t *key = A.key + S * u;
+  int *tr = A.tr + S * u, *mark = A.mark + S * u, *touched = A.touched + S * u, *nxt = A.nxt + S * u;
+  Tok *fa = A.fa + S * u, *fb = A.fb + S * u;
+  Tok *bufs[2] = {A.la + S * u, A.lb + S * u};
+  OnlineState st = states[u];
+  if (call.fresh) {
+    st.nL = 0; st.par = 0; st.ok = 1; st.status = 0; st.active = 0; st.frames = 0; st.started = 0; st.pad = 0; st.top = 0;
+  }
+  __shared__ unsigned long long s_top;
+  if (threadIdx.x == 0) s_top = st.top;
+  __syncthreads();
+  DecArgs B = A;                                        // the slot's own arena
+  B.rec = A.rec + (int64_t)u * cap; B.rec_cap = cap; B.rec_top = &s_top;
+  int *remap = remap_all + (int64_t)u * cap;
+  Tok *L = bufs[st.par], *Lnext = bufs[st.par ^ 1];
+  const float *ll = A.ll + call.ll_off;
+  int status = st.status, ok = st.ok, active = st.active, nL = st.nL;
+  int nT = 0, nF = 0;
+  float F = INFINITY;
+  const bool live = !status && ok;
+  int t = st.started ? 0 : -1;
+  if (live && !st.started) {                            // InitDecoding (decoder.cc:79-97)
+    if (threadIdx.x == 0) {
+      key[A.start] = Pack(0.0f, kStartId);
+      touched[0] = A.start;
+      tr[A.start] = -1;
+      Tok tk;
+      tk.state = A.start; tk.cost = 0.0f; tk.trace = -1; tk.pad = 0;
+      fa[0] = tk;
+    }
+    nT = 1;
+    nF = 1;
+    __syncthreads();
+  }
+  for (; live && t < call.T; ++t) {
+    if (t >= 0) {
+      if (s_top > (unsigned long long)(cap / 2)) CompactTrace(sh, B.rec, remap, &s_top, L, nL, tr);
+      for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads)
+        s_ll[p] = fmaxf(ll[(size_t)t * A.num_pdfs + p], -INFINITY);
+      uint64_t bk = kEmpty;
+      for (int i = threadIdx.x; i < nL; i += kDecThreads) {
+        const uint64_t k = (uint64_t(OrdBits(L[i].cost)) << 32) | uint32_t(L[i].state);
+        bk = k < bk ? k : bk;
+      }
+      bk = BlockMinU(sh, bk);
+      const float best = OrdFloat(uint32_t(bk >> 32));
+      const int best_state = int(uint32_t(bk));
+      if (!(best < INFINITY)) { ok = 0; break; }
+      const double beam_cutoff = (double)best + (double)A.beam;
+      float adaptive_beam = A.beam, weight_cutoff = (float)beam_cutoff;
+      if (nL > A.max_active) {
+        const double kth = (double)OrdFloat(SelectKth(sh, L, nL, A.max_active));
+        if (kth < beam_cutoff) {
+          adaptive_beam = (float)(kth - (double)best + (double)0.5f);
+          weight_cutoff = (float)kth;
+        }
+      }
+      double r0 = INFINITY;
+      for (int a = A.e_off[best_state] + threadIdx.x; a < A.e_off[best_state + 1]; a += kDecThreads) {
+        const int4 arc = A.e_arc[a];
+        const float c = (best + __int_as_float(arc.z)) + (-s_ll[arc.y]);
+        r0 = fmin(r0, (double)c + (double)adaptive_beam);
+      }
+      __syncthreads();
+      r0 = BlockMinD(sh, r0);
+      if (threadIdx.x == 0) sh.cnt_touched = 0;
+      __syncthreads();
+      double cmin = INFINITY;
+      ForArcs(sh, L, nL, weight_cutoff, A.e_off, [&](int j, int a) {
+        const int4 arc = A.e_arc[a];
+        const float c = (L[j].cost + __int_as_float(arc.z)) + (-s_ll[arc.y]);
+        cmin = fmin(cmin, (double)c);
+        if ((double)c > r0) return;
+        const uint64_t k = Pack(c, uint32_t(a));
+        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
+        if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
+      });
+      cmin = BlockMinD(sh, cmin);
+      nT = sh.cnt_touched;
+      F = (float)(cmin + (double)adaptive_beam);
+      nF = Resolve(sh, B, touched, nT, F, false, key, tr, mark, fa);
+      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
+    }
+    int rounds = 0;
+    while (nF > 0) {
+      if (rounds >= A.max_rounds) { status = PK_MI355_E_INVALID; break; }
+      if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.cnt_touched = nT; }
+      __syncthreads();
+      ForArcs(sh, fa, nF, INFINITY, A.n_off, [&](int j, int a) {
+        const int4 arc = A.n_arc[a];
+        const float c = fa[j].cost + __int_as_float(arc.z);
+        if (c > F) return;
+        const uint64_t k = Pack(c, uint32_t(a) | kEpsBit);
+        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
+        if (k < old) {
+          if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
+          if (atomicExch(&mark[arc.x], 1) == 0) nxt[atomicAdd(&sh.cnt_nxt, 1)] = arc.x;
+        }
+      });
+      const int nN = sh.cnt_nxt;
+      nT = sh.cnt_touched;
+      __syncthreads();
+      nF = Resolve(sh, B, nxt, nN, F, true, key, tr, mark, fb);
+      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
+      Tok *x = fa; fa = fb; fb = x;
+      ++rounds;
+    }
+    if (status) break;
+    active = max(active, nT);
+    int written = 0;
+    for (int c0 = 0; c0 < nT; c0 += kDecThreads) {
+      const int i = c0 + threadIdx.x;
+      int keep = 0, s = 0;
+      float c = 0.f;
+      if (i < nT) {
+        s = touched[i];
+        c = OrdFloat(uint32_t(LoadKey(&key[s]) >> 32));
+        keep = !(c > F);
+      }
+      int total;
+      const int ex = BlockScan(sh, keep, &total);
+      if (keep) {
+        Tok tk;
+        tk.state = s; tk.cost = c; tk.trace = tr[s]; tk.pad = 0;
+        Lnext[written + ex] = tk;
+      }
+      written += total;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nT; i += kDecThreads) key[touched[i]] = kEmpty;
+    nT = 0;
+    nL = written;
+    { Tok *x = L; L = Lnext; Lnext = x; }
+    st.par ^= 1;
+    if (t >= 0) ++st.frames;
+    __syncthreads();
+  }
+  if (status) {
+    for (int i = threadIdx.x; i < nT; i += kDecThreads) {
+      key[touched[i]] = kEmpty;
+      mark[touched[i]] = 0;
+    }
+  }
+  // the path of the best token: BestPath's rule (min cost + final, lowest state on a tie) once closed; the partial
+  // hypothesis (min cost, lowest state on a tie, no final weight) otherwise
+  double bc = INFINITY;
+  int bi = -1;
+  const bool fin = call.final_ != 0;
+  if (!status && ok) {
+    for (int i = threadIdx.x; i < nL; i += kDecThreads) {
+      const double c = (double)L[i].cost + (fin ? (double)A.final_w[L[i].state] : 0.0);
+      if (c != INFINITY && (c < bc || (c == bc && bi >= 0 && L[i].state < L[bi].state))) { bc = c; bi = i; }
+    }
+    const double m = BlockMinD(sh, bc);
+    uint64_t cand = (bi >= 0 && bc == m) ? ((uint64_t(uint32_t(L[bi].state)) << 32) | uint32_t(bi)) : kEmpty;
+    cand = BlockMinU(sh, cand);
+    bc = m;
+    bi = cand == kEmpty ? -1 : int(uint32_t(cand));
+  }
+  if (threadIdx.x == 0) {
+    OnlineResult r;
+    r.status = status; r.final_ = fin ? 1 : 0;
+    r.ok = (status || nL == 0) ? 0 : ok;
+    r.weight = 0.f; r.path_len = 0; r.has_path = 0;
+    r.active_bound = active; r.frames = st.frames;
+    if (!status && r.ok && bi >= 0) {
+      float w = (float)bc;
+      if (fin) w += A.final_w[L[bi].state];            // final() counted twice, as the reference does (:338-339)
+      r.weight = w;
+      int len = 0;
+      for (int x = L[bi].trace; x >= 0 && len <= cap; x = B.rec[x].x) ++len;
+      int *path = A.path + (int64_t)u * cap;
+      int p = len;
+      for (int x = L[bi].trace; x >= 0 && p > 0; x = B.rec[x].x) path[--p] = B.rec[x].y;
+      r.path_len = len;
+      r.has_path = 1;
+    }
+    results[u] = r;
+    st.nL = nL; st.ok = ok; st.status = status; st.active = active; st.started = 1; st.top = s_top;
+    states[u] = st;
+  }
+}
 }  // namespace
 
 // ================================================================== host objects
@@ -847,6 +1104,267 @@ int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt) {
   int rc = CheckResult(d, utt);
   if (rc) return rc;
   return d->res[utt].active_bound;
+}
+
+}  // extern "C"
+
+// ================================================================== online decoder (host)
+
+struct pk_mi355_online_decoder {
+  pk_mi355_decoder dec;                         // graph, work areas (one per slot), arenas (cap records per slot)
+  int max_streams = 0;
+  int64_t cap = 0;
+  OnlineState *d_state = nullptr;
+  OnlineResult *d_results = nullptr;
+  int *d_remap = nullptr;
+  OnlineCall *d_calls = nullptr;
+  std::vector<int> open_, fresh, finished;      // per slot
+  std::vector<OnlineResult> res;                // per slot, after synchronize
+  std::vector<std::vector<int32_t>> paths;      // per slot: the arcs of res[slot]'s path
+  std::vector<int> last_slots;                  // slots of the last call
+  bool pending = false;
+};
+
+namespace {
+
+int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<OnlineCall> &calls, hipStream_t stream) {
+  pk_mi355_decoder *d = &o->dec;
+  if (o->pending) HIP_TRY(hipEventSynchronize(d->done));
+  o->pending = false;
+  o->last_slots.clear();
+  for (const auto &c : calls) o->last_slots.push_back(c.slot);
+  const int n = (int)calls.size();
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
+    DecArgs A;
+    A.e_off = d->e_off; A.e_arc = d->e_arc; A.e_src = d->e_src;
+    A.n_off = d->n_off; A.n_arc = d->n_arc; A.n_src = d->n_src;
+    A.final_w = d->final_w;
+    A.num_states = d->num_states; A.start = d->start; A.num_pdfs = d->num_pdfs;
+    A.ll = ll; A.ll_off = nullptr; A.T = nullptr; A.num_utts = n;
+    const size_t per = (size_t)d->num_states * d->max_utts;
+    A.key = d->key; A.tr = d->tr; A.mark = d->mark; A.touched = d->touched; A.nxt = d->nxt;
+    A.la = d->lists; A.lb = d->lists + per; A.fa = d->lists + 2 * per; A.fb = d->lists + 3 * per;
+    A.rec = d->rec; A.rec_cap = o->cap; A.rec_top = nullptr;
+    A.path = d->path; A.path_cap = (int)o->cap; A.path_top = nullptr;
+    A.beam = d->beam; A.max_active = d->max_active;
+    A.max_rounds = d->num_states + 2;
+    A.res = nullptr;
+    hipLaunchKernelGGL(OnlineDecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A, o->d_calls,
+                       o->d_state, o->d_results, o->d_remap, o->cap);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
+  }
+  for (const auto &c : calls) {
+    o->fresh[c.slot] = 0;
+    if (c.final_) { o->finished[c.slot] = 1; o->open_[c.slot] = 0; }
+  }
+  HIP_TRY(hipEventRecord(d->done, stream));
+  o->pending = true;
+  return 0;
+}
+
+int OnlineCollect(pk_mi355_online_decoder *o) {
+  if (!o->pending) return 0;
+  int rc = UseDevice(o->dec.device);
+  if (rc) return rc;
+  o->pending = false;
+  HIP_TRY(hipEventSynchronize(o->dec.done));
+  if (o->last_slots.empty()) return 0;
+  HIP_TRY(hipMemcpy(o->res.data(), o->d_results, sizeof(OnlineResult) * o->max_streams, hipMemcpyDeviceToHost));
+  int first_bad = -1;
+  for (int slot : o->last_slots) {
+    const OnlineResult &r = o->res[slot];
+    if (r.path_len < 0 || r.path_len > o->cap) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
+    o->paths[slot].resize(r.path_len);
+    if (r.path_len)
+      HIP_TRY(hipMemcpy(o->paths[slot].data(), o->dec.path + (int64_t)slot * o->cap, sizeof(int32_t) * r.path_len,
+                        hipMemcpyDeviceToHost));
+    if (r.status && first_bad < 0) first_bad = slot;
+  }
+  if (first_bad >= 0) {
+    const OnlineResult &r = o->res[first_bad];
+    if (r.status == PK_MI355_E_CAPACITY)
+      return Fail(PK_MI355_E_CAPACITY, "online decoder: slot %d: backtrace storage exhausted after compaction (%lld records "
+                  "per slot)", first_bad, (long long)o->cap);
+    return Fail(PK_MI355_E_INVALID, "online decoder: slot %d: negative epsilon cycle (the closure did not settle)", first_bad);
+  }
+  return 0;
+}
+
+int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
+  int n = 0;
+  for (int arc : o->paths[slot]) {
+    const int w = (arc >= 0 && arc < (int)o->dec.olabel.size()) ? o->dec.olabel[arc] : 0;
+    if (w != 0) {
+      if (words && n < max_words) words[n] = w;
+      ++n;
+    }
+  }
+  return n;
+}
+
+int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  if (slot < 0 || slot >= o->max_streams) return Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, o->max_streams);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am, int max_streams,
+                                                          int64_t trace_capacity) {
+  if (!fst || !am) { Fail(PK_MI355_E_INVALID, "null graph or model"); return nullptr; }
+  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (max_streams <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online decoder capacity"); return nullptr; }
+  const int64_t cap = trace_capacity > 0 ? trace_capacity : (int64_t)1 << 20;
+  if (cap * max_streams > (int64_t)INT32_MAX) { Fail(PK_MI355_E_INVALID, "online decoder: max_streams x trace_capacity above 2^31 - 1"); return nullptr; }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_online_decoder *o = new pk_mi355_online_decoder();
+  o->dec.device = am->device;
+  o->dec.am = am;
+  o->max_streams = max_streams;
+  o->cap = cap;
+  bool ok = CreateDecoder(&o->dec, fst, am, max_streams, cap * max_streams) == 0;
+  auto chk = [&](hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "online_decoder_create: %s", hipGetErrorString(e)); } };
+  if (ok) chk(hipMalloc(&o->d_state, sizeof(OnlineState) * max_streams));
+  if (ok) chk(hipMemset(o->d_state, 0, sizeof(OnlineState) * max_streams));
+  if (ok) chk(hipMalloc(&o->d_results, sizeof(OnlineResult) * max_streams));
+  if (ok) chk(hipMemset(o->d_results, 0, sizeof(OnlineResult) * max_streams));
+  if (ok) chk(hipMalloc(&o->d_remap, sizeof(int) * cap * max_streams));
+  if (ok) chk(hipMalloc(&o->d_calls, sizeof(OnlineCall) * max_streams));
+  if (!ok) { pk_mi355_online_decoder_destroy(o); return nullptr; }
+  o->open_.assign(max_streams, 0); o->fresh.assign(max_streams, 1); o->finished.assign(max_streams, 0);
+  o->res.assign(max_streams, OnlineResult{});
+  o->paths.assign(max_streams, {});
+  return o;
+}
+
+void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *o) {
+  if (!o) return;
+  if (!UseDevice(o->dec.device)) {
+    if (o->pending) hipEventSynchronize(o->dec.done);
+    FreeDecoderDevice(&o->dec);
+    hipFree(o->d_state); hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
+  }
+  delete o;
+}
+
+int pk_mi355_online_decoder_set_beam(pk_mi355_online_decoder_t *o, float beam, int max_active) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  return pk_mi355_decoder_set_beam(&o->dec, beam, max_active);
+}
+
+int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open", slot);
+  if ((rc = OnlineCollect(o))) return rc;       // a result of the slot's last utterance is replaced
+  o->open_[slot] = 1; o->fresh[slot] = 1; o->finished[slot] = 0;
+  o->res[slot] = OnlineResult{};
+  o->paths[slot].clear();
+  return 0;
+}
+
+int pk_mi355_online_decoder_advance_host(pk_mi355_online_decoder_t *o, const int *slots, const pk_decodable_t *chunks,
+                                         const int *final_, int n, int sync) {
+  if (!o || n < 0 || (n > 0 && (!slots || !chunks))) return Fail(PK_MI355_E_INVALID, "bad advance arguments");
+  pk_mi355_decoder *d = &o->dec;
+  int rc = UseDevice(d->device);
+  if (rc) return rc;
+  std::vector<char> seen(o->max_streams, 0);
+  int64_t total = 0;
+  std::vector<OnlineCall> calls(n);
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i];
+    if ((rc = OnlineSlot(o, slot))) return rc;
+    if (!o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not open", slot);
+    if (seen[slot]) return Fail(PK_MI355_E_INVALID, "online decoder: slot %d twice in one call", slot);
+    seen[slot] = 1;
+    const pk_matrix_t &m = chunks[i].log_prob;
+    if (m.ncol < 0 || (m.ncol > 0 && (m.nrow != d->num_pdfs || !m.data)))
+      return Fail(PK_MI355_E_INVALID, "online decoder: chunk %d: log_prob is {ncol %d, nrow %d}, nrow %d expected", i, m.ncol,
+                  m.nrow, d->num_pdfs);
+    calls[i] = OnlineCall{slot, m.ncol, final_ && final_[i] ? 1 : 0, o->fresh[slot], total};
+    total += (int64_t)m.ncol * d->num_pdfs;
+  }
+  if (o->pending) HIP_TRY(hipEventSynchronize(d->done));     // d_ll may still be read by the previous call
+  if ((size_t)total > d->d_ll_floats) {
+    if (d->d_ll) hipFree(d->d_ll);
+    d->d_ll = nullptr;
+    d->d_ll_floats = 0;
+    HIP_TRY(hipMalloc(&d->d_ll, sizeof(float) * (size_t)total));
+    d->d_ll_floats = (size_t)total;
+  }
+  for (int i = 0; i < n; ++i)
+    if (calls[i].T > 0)
+      HIP_TRY(hipMemcpyAsync(d->d_ll + calls[i].ll_off, chunks[i].log_prob.data, sizeof(float) * (size_t)calls[i].T * d->num_pdfs,
+                             hipMemcpyHostToDevice, d->own_stream));
+  if ((rc = OnlineLaunch(o, d->d_ll, calls, d->own_stream))) return rc;
+  return sync ? OnlineCollect(o) : 0;
+}
+
+int pk_mi355_online_decoder_advance(pk_mi355_online_decoder_t *o, pk_mi355_stream_t *s, int sync) {
+  if (!o || !s) return Fail(PK_MI355_E_INVALID, "null online decoder or stream");
+  if (StreamModel(s) != o->dec.am)
+    return Fail(PK_MI355_E_INVALID, "online decoder: the stream scores with another model than the decoder was created for");
+  if (StreamSlots(s) > o->max_streams) return Fail(PK_MI355_E_INVALID, "online decoder: the stream has more slots than the decoder");
+  int rc = UseDevice(o->dec.device);
+  if (rc) return rc;
+  std::vector<OnlineCall> calls;
+  const float *base = StreamLoglikBase(s);
+  for (int slot = 0; slot < StreamSlots(s); ++slot) {
+    if (!o->open_[slot]) continue;
+    int first = 0, count = 0;
+    const float *p = pk_mi355_stream_loglik_device(s, slot, &first, &count);
+    const bool fin = StreamSlotFlushed(s, slot);
+    if (count == 0 && !fin) continue;
+    calls.push_back(OnlineCall{slot, count, fin ? 1 : 0, o->fresh[slot], count ? (int64_t)(p - base) : 0});
+  }
+  if ((rc = OnlineLaunch(o, base, calls, StreamHipStream(s)))) return rc;
+  return sync ? OnlineCollect(o) : 0;
+}
+
+int pk_mi355_online_decoder_synchronize(pk_mi355_online_decoder_t *o) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  return OnlineCollect(o);
+}
+
+int pk_mi355_online_decoder_partial(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, float *cost) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  if (cost) *cost = o->res[slot].weight;
+  return OnlineWords(o, slot, words, max_words);
+}
+
+int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, float *weight,
+                                   int *ok) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  if (!o->finished[slot] || !o->res[slot].final_) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not finished", slot);
+  if (weight) *weight = o->res[slot].weight;
+  if (ok) *ok = o->res[slot].ok;
+  return OnlineWords(o, slot, words, max_words);
+}
+
+int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, int slot, int32_t *arcs, int max_arcs) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  const auto &p = o->paths[slot];
+  for (int i = 0; i < (int)p.size() && i < max_arcs; ++i) arcs[i] = p[i];
+  return (int)p.size();
+}
+
+int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *o, int slot) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  return o->res[slot].active_bound;
 }
 
 }  // extern "C"

@@ -291,6 +291,13 @@ void ReleaseArenaView(pk_mi355_am_t *handle);
 bool BatchScored(const pk_mi355_batch *b);
 const pk_mi355_am *BatchModel(const pk_mi355_batch *b);
 
+// what the online decoder (decode.hip) needs to know of an online scorer (stream.hip) beyond the ABI
+const pk_mi355_am *StreamModel(const pk_mi355_stream *s);
+int StreamSlots(const pk_mi355_stream *s);
+hipStream_t StreamHipStream(const pk_mi355_stream *s);
+const float *StreamLoglikBase(const pk_mi355_stream *s);
+bool StreamSlotFlushed(const pk_mi355_stream *s, int slot);   // the last step flushed the slot (it was closed)
+
 }  // namespace pkhost
 
 #endif  // PK_HOST_H_
