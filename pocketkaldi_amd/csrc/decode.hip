@@ -62,7 +62,8 @@ struct DecArgs {
   int num_utts;
   // per-utterance work areas (stride num_states entries)
   uint64_t *key; int *tr; int *mark; int *touched; int *nxt; Tok *la; Tok *lb; Tok *fa; Tok *fb;
-  // backtrace arena (shared by the call) and best-path arena
+  // backtrace arena and best-path arena.  DecodeKernel: shared by the call, with their capacities and bump counters;
+  // OnlineDecodeKernel: rec and path only, a slice per slot (its capacity is a kernel argument, its top the slot's state)
   int2 *rec; int64_t rec_cap; unsigned long long *rec_top;
   int *path; int path_cap; int *path_top;
   float beam; int max_active; int max_rounds;
@@ -200,11 +201,39 @@ __device__ void ForArcs(Shared &sh, const Tok *src, int n, float cut, const int 
   }
 }
 
+// The backtrace arena that trace records go to: the call's shared one (DecodeKernel) or a slot's own (OnlineDecodeKernel).
+struct Arena {
+  int2 *rec;                    // (previous record, original arc id)
+  int64_t cap;
+  unsigned long long *top;      // records used
+};
+
+// One utterance's (slot's) decoding state for the duration of a launch.
+struct Work {
+  uint64_t *key; int *tr, *mark, *touched, *nxt;    // state table, trace index, frontier mark, touched / improved states
+  Tok *L, *Lnext, *fa, *fb;                         // this frame's tokens, the next frame's, the closure's two frontiers
+  Arena arena;
+  int nL;                                           // tokens in L
+  int status, ok, active;                           // failure code; N2's verdict; largest per-frame count of touched states
+  int frames, par;                                  // online only: frames decoded; which list buffer L is
+};
+
+__device__ __forceinline__ Work WorkOf(const DecArgs &A, int u, const Arena &arena) {
+  const size_t at = (size_t)A.num_states * u;
+  Work w;
+  w.key = A.key + at;
+  w.tr = A.tr + at; w.mark = A.mark + at; w.touched = A.touched + at; w.nxt = A.nxt + at;
+  w.L = A.la + at; w.Lnext = A.lb + at; w.fa = A.fa + at; w.fb = A.fb + at;
+  w.arena = arena;
+  w.nL = 0; w.status = 0; w.ok = 1; w.active = 0; w.frames = 0; w.par = 0;
+  return w;
+}
+
 // Give each winner of touched-or-improved states a trace record and write it as a token into out[].
 // states[0..n): the states; arcs/srcs: the CSR the winners' ids index (emitting or epsilon);
 // only winners <= F are kept.  Returns the number written (all threads), or -1 when the arena is full.
-__device__ int Resolve(Shared &sh, const DecArgs &A, const int *states, int n, float F, bool eps, uint64_t *key,
-                       int *tr, int *mark, Tok *out) {
+__device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *states, int n, float F, bool eps,
+                       uint64_t *key, int *tr, int *mark, Tok *out) {
   int written = 0;
   for (int c0 = 0; c0 < n; c0 += kDecThreads) {
     const int i = c0 + threadIdx.x;
@@ -230,14 +259,14 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const int *states, int n, f
     }
     int total;
     const int ex = BlockScan(sh, need, &total);
-    if (threadIdx.x == 0) sh.base = total ? atomicAdd(A.rec_top, (unsigned long long)total) : 0ull;
+    if (threadIdx.x == 0) sh.base = total ? atomicAdd(R.top, (unsigned long long)total) : 0ull;
     __syncthreads();
     const unsigned long long base = sh.base;
     __syncthreads();
-    if (base + (unsigned long long)total > (unsigned long long)A.rec_cap) return -1;
+    if (base + (unsigned long long)total > (unsigned long long)R.cap) return -1;
     if (need) {
       const int r = int(base) + ex;
-      A.rec[r] = make_int2(prev, arc);
+      R.rec[r] = make_int2(prev, arc);
       Tok t;
       t.state = s; t.cost = c; t.trace = r; t.pad = 0;
       out[written + ex] = t;
@@ -250,39 +279,37 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const int *states, int n, f
   return written;
 }
 
-__global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
-  extern __shared__ float s_ll[];
-  __shared__ Shared sh;
-  const int u = blockIdx.x;
-  if (u >= A.num_utts) return;
-  const size_t S = (size_t)A.num_states;
-  uint64_t *key = A.key + S * u;
-  int *tr = A.tr + S * u, *mark = A.mark + S * u, *touched = A.touched + S * u, *nxt = A.nxt + S * u;
-  Tok *L = A.la + S * u, *Lnext = A.lb + S * u, *fa = A.fa + S * u, *fb = A.fb + S * u;
-  const int T = A.T[u];
-  const float *ll = A.ll + A.ll_off[u];
-  UttResult *res = A.res + u;
-
-  int status = 0, ok = 1, active = 0;
-  int nL = 0, nT = 0, nF = 0;
+// The frame step, shared by the whole-utterance and the online kernel: InitDecoding when the first frame index t is
+// -1, then frames t .. T - 1 of ll (ProcessEmitting, ProcessNonemitting, the next token list).  before(L, nL) runs
+// ahead of every emitting frame: nothing for DecodeKernel, the trace compaction for OnlineDecodeKernel.
+template <typename Before>
+__device__ __forceinline__ void DecodeFrames(Shared &sh, float *s_ll, const DecArgs &A, Work &w, const float *ll, int t,
+                                             int T, Before before) {
+  uint64_t *key = w.key;
+  int *tr = w.tr, *mark = w.mark, *touched = w.touched, *nxt = w.nxt;
+  Tok *L = w.L, *Lnext = w.Lnext, *fa = w.fa, *fb = w.fb;
+  int status = w.status, ok = w.ok, active = w.active;
+  int nL = w.nL, nT = 0, nF = 0;
   float F = INFINITY;
 
   // InitDecoding (decoder.cc:79-97): the start token, cost 0, then the epsilon closure with an infinite cutoff
-  if (threadIdx.x == 0) {
-    key[A.start] = Pack(0.0f, kStartId);
-    touched[0] = A.start;
-    tr[A.start] = -1;
-    Tok t;
-    t.state = A.start; t.cost = 0.0f; t.trace = -1; t.pad = 0;
-    fa[0] = t;
-    sh.fail = 0;
+  if (t < 0) {
+    if (threadIdx.x == 0) {
+      key[A.start] = Pack(0.0f, kStartId);
+      touched[0] = A.start;
+      tr[A.start] = -1;
+      Tok tk;
+      tk.state = A.start; tk.cost = 0.0f; tk.trace = -1; tk.pad = 0;
+      fa[0] = tk;
+    }
+    nT = 1;
+    nF = 1;
+    __syncthreads();
   }
-  nT = 1;
-  nF = 1;
-  __syncthreads();
 
-  for (int t = -1; t < T; ++t) {
+  for (; t < T; ++t) {
     if (t >= 0) {
+      before(L, nL);
       // ---- ProcessEmitting (decoder.cc:226-301)
       // N1: a NaN log-likelihood decodes as -inf (fmaxf returns the operand that is not NaN), its candidates as +inf
       for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads)
@@ -332,7 +359,7 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
       cmin = BlockMinD(sh, cmin);
       nT = sh.cnt_touched;
       F = (float)(cmin + (double)adaptive_beam);       // the non-emitting cutoff ProcessEmitting returns
-      nF = Resolve(sh, A, touched, nT, F, false, key, tr, mark, fa);
+      nF = Resolve(sh, A, w.arena, touched, nT, F, false, key, tr, mark, fa);
       if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
     }
     // ---- ProcessNonemitting (decoder.cc:186-222): frontier by frontier to the fixed point, bounded
@@ -355,7 +382,7 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
       const int nN = sh.cnt_nxt;
       nT = sh.cnt_touched;
       __syncthreads();
-      nF = Resolve(sh, A, nxt, nN, F, true, key, tr, mark, fb);
+      nF = Resolve(sh, A, w.arena, nxt, nN, F, true, key, tr, mark, fb);
       if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
       Tok *x = fa; fa = fb; fb = x;
       ++rounds;
@@ -387,6 +414,8 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
     nT = 0;
     nL = written;
     { Tok *x = L; L = Lnext; Lnext = x; }
+    w.par ^= 1;
+    if (t >= 0) ++w.frames;
     __syncthreads();
   }
   if (status) {                                        // leave the work areas clean for the next call
@@ -395,52 +424,78 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
       mark[touched[i]] = 0;
     }
   }
+  w.L = L; w.Lnext = Lnext; w.nL = nL; w.status = status; w.ok = ok; w.active = active;
+}
 
-  // ---- BestPath (decoder.cc:304-339): min (double)cost + final over the final tokens, != INFINITY
+// The token whose path is the result (its index in w.L to every thread, or -1) and the hypothesis' weight.
+// fin: BestPath (decoder.cc:304-339), min (double)cost + final over the final tokens, != INFINITY; otherwise the
+// partial hypothesis, the bare cost.  Lowest state on a tie in both.
+__device__ __forceinline__ int BestToken(Shared &sh, const DecArgs &A, const Work &w, bool fin, float *weight) {
+  const Tok *L = w.L;
   double bc = INFINITY;
   int bi = -1;
-  if (!status && ok) {
-    for (int i = threadIdx.x; i < nL; i += kDecThreads) {
-      const double c = (double)L[i].cost + (double)A.final_w[L[i].state];
-      if (c != INFINITY && (c < bc || (c == bc && bi >= 0 && L[i].state < L[bi].state))) { bc = c; bi = i; }
-    }
-    const double m = BlockMinD(sh, bc);
-    uint64_t cand = (bi >= 0 && bc == m) ? ((uint64_t(uint32_t(L[bi].state)) << 32) | uint32_t(bi)) : kEmpty;
-    cand = BlockMinU(sh, cand);
-    bc = m;
-    bi = cand == kEmpty ? -1 : int(uint32_t(cand));
+  for (int i = threadIdx.x; i < w.nL; i += kDecThreads) {
+    const double c = (double)L[i].cost + (fin ? (double)A.final_w[L[i].state] : 0.0);
+    if (c != INFINITY && (c < bc || (c == bc && bi >= 0 && L[i].state < L[bi].state))) { bc = c; bi = i; }
   }
+  const double m = BlockMinD(sh, bc);
+  uint64_t cand = (bi >= 0 && bc == m) ? ((uint64_t(uint32_t(L[bi].state)) << 32) | uint32_t(bi)) : kEmpty;
+  cand = BlockMinU(sh, cand);
+  bi = cand == kEmpty ? -1 : int(uint32_t(cand));
+  float wt = (float)m;
+  if (fin && bi >= 0) wt += A.final_w[L[bi].state];    // final() counted twice, as the reference does (:338-339)
+  *weight = wt;
+  return bi;
+}
+
+// The path walk of one lane: count the records from `trace` back to the start, then fill path[0..len) back to front.
+__device__ __forceinline__ int PathLen(const Arena &R, int trace) {
+  int len = 0;
+  for (int x = trace; x >= 0 && len <= R.cap; x = R.rec[x].x) ++len;
+  return len;
+}
+__device__ __forceinline__ void FillPath(const Arena &R, int trace, int *path, int len) {
+  for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) path[--len] = R.rec[x].y;
+}
+
+__global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
+  extern __shared__ float s_ll[];
+  __shared__ Shared sh;
+  const int u = blockIdx.x;
+  if (u >= A.num_utts) return;
+  Work w = WorkOf(A, u, Arena{A.rec, A.rec_cap, A.rec_top});
+  DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [](Tok *, int) {});
+  float weight = 0.f;
+  int bi = -1;
+  if (!w.status && w.ok) bi = BestToken(sh, A, w, true, &weight);
   if (threadIdx.x == 0) {
     UttResult r;
-    r.status = status; r.ok = (status || nL == 0) ? 0 : ok; r.weight = 0.f;
-    r.path_off = 0; r.path_len = 0; r.active_bound = active; r.pad[0] = r.pad[1] = 0;
-    if (!status && r.ok && bi >= 0) {
-      float w = (float)bc;
-      w += A.final_w[L[bi].state];                     // final() counted twice, as the reference does (:338-339)
-      r.weight = w;
-      int len = 0;
-      for (int x = L[bi].trace; x >= 0 && len <= A.rec_cap; x = A.rec[x].x) ++len;
-      const int off = atomicAdd(A.path_top, len);
+    r.status = w.status; r.ok = (w.status || w.nL == 0) ? 0 : w.ok; r.weight = 0.f;
+    r.path_off = 0; r.path_len = 0; r.active_bound = w.active; r.pad[0] = r.pad[1] = 0;
+    if (!w.status && r.ok && bi >= 0) {
+      r.weight = weight;
+      const int len = PathLen(w.arena, w.L[bi].trace);
+      const int off = atomicAdd(A.path_top, len);      // the call's shared path arena
       if (off + len > A.path_cap) {                   // (cannot happen: see CreateDecoder)
         r.status = PK_MI355_E_CAPACITY;
         r.ok = 0;
       } else {
         r.path_off = off; r.path_len = len;
-        int p = off + len;
-        for (int x = L[bi].trace; x >= 0 && p > off; x = A.rec[x].x) A.path[--p] = A.rec[x].y;
+        FillPath(w.arena, w.L[bi].trace, A.path + off, len);
       }
     }
-    *res = r;
+    A.res[u] = r;
   }
 }
 
 
 // ================================================================== online decoding (pk_mi355_online_decoder_*)
-// The same frame step as DecodeKernel, resumable: a slot's token list, its count and buffer, ok / status, the
-// largest touched count, the frames decoded and its trace-arena top live in HBM between launches.  One workgroup per
-// slot with new frames; InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot
-// has an arena of its own; when it is more than half full between two frames the reachable records are compacted
-// (CompactTrace).  DecodeKernel itself is not touched: the whole-utterance path compiles to the same code as before.
+// DecodeFrames, resumable: a slot's token list, its count and buffer, ok / status, the largest touched count, the
+// frames decoded and its trace-arena top live in HBM between launches.  One workgroup per slot with new frames;
+// InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot has an arena of its own
+// (A.rec and A.path hold `cap` entries per slot); when it is more than half full before an emitting frame the
+// reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity are all
+// this kernel adds to the frame step: DecodeKernel instantiates it with an empty `before` and never reads them.
 
 struct OnlineState {
   int nL, par;            // tokens of the current list and which of the slot's two list buffers holds them
@@ -508,11 +563,6 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
   __shared__ Shared sh;
   const OnlineCall call = calls[blockIdx.x];
   const int u = call.slot;
-  const size_t S = (size_t)A.num_states;
-  uint64_t *key = A.key + S * u;
-  int *tr = A.tr + S * u, *mark = A.mark + S * u, *touched = A.touched + S * u, *nxt = A.nxt + S * u;
-  Tok *fa = A.fa + S * u, *fb = A.fb + S * u;
-  Tok *bufs[2] = {A.la + S * u, A.lb + S * u};
   OnlineState st = states[u];
   if (call.fresh) {
     st.nL = 0; st.par = 0; st.ok = 1; st.status = 0; st.active = 0; st.frames = 0; st.started = 0; st.pad = 0; st.top = 0;
@@ -520,174 +570,34 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
   __shared__ unsigned long long s_top;
   if (threadIdx.x == 0) s_top = st.top;
   __syncthreads();
-  DecArgs B = A;                                        // the slot's own arena
-  B.rec = A.rec + (int64_t)u * cap; B.rec_cap = cap; B.rec_top = &s_top;
+  Work w = WorkOf(A, u, Arena{A.rec + (int64_t)u * cap, cap, &s_top});   // the slot's own arena
   int *remap = remap_all + (int64_t)u * cap;
-  Tok *L = bufs[st.par], *Lnext = bufs[st.par ^ 1];
-  const float *ll = A.ll + call.ll_off;
-  int status = st.status, ok = st.ok, active = st.active, nL = st.nL;
-  int nT = 0, nF = 0;
-  float F = INFINITY;
-  const bool live = !status && ok;
-  int t = st.started ? 0 : -1;
-  if (live && !st.started) {                            // InitDecoding (decoder.cc:79-97)
-    if (threadIdx.x == 0) {
-      key[A.start] = Pack(0.0f, kStartId);
-      touched[0] = A.start;
-      tr[A.start] = -1;
-      Tok tk;
-      tk.state = A.start; tk.cost = 0.0f; tk.trace = -1; tk.pad = 0;
-      fa[0] = tk;
-    }
-    nT = 1;
-    nF = 1;
-    __syncthreads();
-  }
-  for (; live && t < call.T; ++t) {
-    if (t >= 0) {
-      if (s_top > (unsigned long long)(cap / 2)) CompactTrace(sh, B.rec, remap, &s_top, L, nL, tr);
-      for (int p = threadIdx.x; p < A.num_pdfs; p += kDecThreads)
-        s_ll[p] = fmaxf(ll[(size_t)t * A.num_pdfs + p], -INFINITY);
-      uint64_t bk = kEmpty;
-      for (int i = threadIdx.x; i < nL; i += kDecThreads) {
-        const uint64_t k = (uint64_t(OrdBits(L[i].cost)) << 32) | uint32_t(L[i].state);
-        bk = k < bk ? k : bk;
-      }
-      bk = BlockMinU(sh, bk);
-      const float best = OrdFloat(uint32_t(bk >> 32));
-      const int best_state = int(uint32_t(bk));
-      if (!(best < INFINITY)) { ok = 0; break; }
-      const double beam_cutoff = (double)best + (double)A.beam;
-      float adaptive_beam = A.beam, weight_cutoff = (float)beam_cutoff;
-      if (nL > A.max_active) {
-        const double kth = (double)OrdFloat(SelectKth(sh, L, nL, A.max_active));
-        if (kth < beam_cutoff) {
-          adaptive_beam = (float)(kth - (double)best + (double)0.5f);
-          weight_cutoff = (float)kth;
-        }
-      }
-      double r0 = INFINITY;
-      for (int a = A.e_off[best_state] + threadIdx.x; a < A.e_off[best_state + 1]; a += kDecThreads) {
-        const int4 arc = A.e_arc[a];
-        const float c = (best + __int_as_float(arc.z)) + (-s_ll[arc.y]);
-        r0 = fmin(r0, (double)c + (double)adaptive_beam);
-      }
-      __syncthreads();
-      r0 = BlockMinD(sh, r0);
-      if (threadIdx.x == 0) sh.cnt_touched = 0;
-      __syncthreads();
-      double cmin = INFINITY;
-      ForArcs(sh, L, nL, weight_cutoff, A.e_off, [&](int j, int a) {
-        const int4 arc = A.e_arc[a];
-        const float c = (L[j].cost + __int_as_float(arc.z)) + (-s_ll[arc.y]);
-        cmin = fmin(cmin, (double)c);
-        if ((double)c > r0) return;
-        const uint64_t k = Pack(c, uint32_t(a));
-        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
-        if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
-      });
-      cmin = BlockMinD(sh, cmin);
-      nT = sh.cnt_touched;
-      F = (float)(cmin + (double)adaptive_beam);
-      nF = Resolve(sh, B, touched, nT, F, false, key, tr, mark, fa);
-      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
-    }
-    int rounds = 0;
-    while (nF > 0) {
-      if (rounds >= A.max_rounds) { status = PK_MI355_E_INVALID; break; }
-      if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.cnt_touched = nT; }
-      __syncthreads();
-      ForArcs(sh, fa, nF, INFINITY, A.n_off, [&](int j, int a) {
-        const int4 arc = A.n_arc[a];
-        const float c = fa[j].cost + __int_as_float(arc.z);
-        if (c > F) return;
-        const uint64_t k = Pack(c, uint32_t(a) | kEpsBit);
-        const uint64_t old = atomicMin((unsigned long long *)&key[arc.x], (unsigned long long)k);
-        if (k < old) {
-          if (old == kEmpty) touched[atomicAdd(&sh.cnt_touched, 1)] = arc.x;
-          if (atomicExch(&mark[arc.x], 1) == 0) nxt[atomicAdd(&sh.cnt_nxt, 1)] = arc.x;
-        }
-      });
-      const int nN = sh.cnt_nxt;
-      nT = sh.cnt_touched;
-      __syncthreads();
-      nF = Resolve(sh, B, nxt, nN, F, true, key, tr, mark, fb);
-      if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
-      Tok *x = fa; fa = fb; fb = x;
-      ++rounds;
-    }
-    if (status) break;
-    active = max(active, nT);
-    int written = 0;
-    for (int c0 = 0; c0 < nT; c0 += kDecThreads) {
-      const int i = c0 + threadIdx.x;
-      int keep = 0, s = 0;
-      float c = 0.f;
-      if (i < nT) {
-        s = touched[i];
-        c = OrdFloat(uint32_t(LoadKey(&key[s]) >> 32));
-        keep = !(c > F);
-      }
-      int total;
-      const int ex = BlockScan(sh, keep, &total);
-      if (keep) {
-        Tok tk;
-        tk.state = s; tk.cost = c; tk.trace = tr[s]; tk.pad = 0;
-        Lnext[written + ex] = tk;
-      }
-      written += total;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nT; i += kDecThreads) key[touched[i]] = kEmpty;
-    nT = 0;
-    nL = written;
-    { Tok *x = L; L = Lnext; Lnext = x; }
-    st.par ^= 1;
-    if (t >= 0) ++st.frames;
-    __syncthreads();
-  }
-  if (status) {
-    for (int i = threadIdx.x; i < nT; i += kDecThreads) {
-      key[touched[i]] = kEmpty;
-      mark[touched[i]] = 0;
-    }
-  }
-  // the path of the best token: BestPath's rule (min cost + final, lowest state on a tie) once closed; the partial
-  // hypothesis (min cost, lowest state on a tie, no final weight) otherwise
-  double bc = INFINITY;
-  int bi = -1;
+  if (st.par) { Tok *x = w.L; w.L = w.Lnext; w.Lnext = x; }
+  w.nL = st.nL; w.status = st.status; w.ok = st.ok; w.active = st.active; w.frames = st.frames; w.par = st.par;
+  if (!w.status && w.ok)
+    DecodeFrames(sh, s_ll, A, w, A.ll + call.ll_off, st.started ? 0 : -1, call.T, [&](Tok *L, int nL) {
+      if (s_top > (unsigned long long)(cap / 2)) CompactTrace(sh, w.arena.rec, remap, &s_top, L, nL, w.tr);
+    });
+  // the path of the best token: BestPath's once the slot is closed, the partial hypothesis' otherwise
   const bool fin = call.final_ != 0;
-  if (!status && ok) {
-    for (int i = threadIdx.x; i < nL; i += kDecThreads) {
-      const double c = (double)L[i].cost + (fin ? (double)A.final_w[L[i].state] : 0.0);
-      if (c != INFINITY && (c < bc || (c == bc && bi >= 0 && L[i].state < L[bi].state))) { bc = c; bi = i; }
-    }
-    const double m = BlockMinD(sh, bc);
-    uint64_t cand = (bi >= 0 && bc == m) ? ((uint64_t(uint32_t(L[bi].state)) << 32) | uint32_t(bi)) : kEmpty;
-    cand = BlockMinU(sh, cand);
-    bc = m;
-    bi = cand == kEmpty ? -1 : int(uint32_t(cand));
-  }
+  float weight = 0.f;
+  int bi = -1;
+  if (!w.status && w.ok) bi = BestToken(sh, A, w, fin, &weight);
   if (threadIdx.x == 0) {
     OnlineResult r;
-    r.status = status; r.final_ = fin ? 1 : 0;
-    r.ok = (status || nL == 0) ? 0 : ok;
+    r.status = w.status; r.final_ = fin ? 1 : 0;
+    r.ok = (w.status || w.nL == 0) ? 0 : w.ok;
     r.weight = 0.f; r.path_len = 0; r.has_path = 0;
-    r.active_bound = active; r.frames = st.frames;
-    if (!status && r.ok && bi >= 0) {
-      float w = (float)bc;
-      if (fin) w += A.final_w[L[bi].state];            // final() counted twice, as the reference does (:338-339)
-      r.weight = w;
-      int len = 0;
-      for (int x = L[bi].trace; x >= 0 && len <= cap; x = B.rec[x].x) ++len;
-      int *path = A.path + (int64_t)u * cap;
-      int p = len;
-      for (int x = L[bi].trace; x >= 0 && p > 0; x = B.rec[x].x) path[--p] = B.rec[x].y;
-      r.path_len = len;
+    r.active_bound = w.active; r.frames = w.frames;
+    if (!w.status && r.ok && bi >= 0) {
+      r.weight = weight;
+      r.path_len = PathLen(w.arena, w.L[bi].trace);
+      FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, r.path_len);
       r.has_path = 1;
     }
     results[u] = r;
-    st.nL = nL; st.ok = ok; st.status = status; st.active = active; st.started = 1; st.top = s_top;
+    st.nL = w.nL; st.par = w.par; st.ok = w.ok; st.status = w.status; st.active = w.active; st.frames = w.frames;
+    st.started = 1; st.top = s_top;
     states[u] = st;
   }
 }
@@ -881,6 +791,69 @@ int CreateDecoder(pk_mi355_decoder *d, const pk_mi355_fst *f, const pk_mi355_am 
   return 0;
 }
 
+// What every launch over d's graph and work areas shares (n utterances or slots, log-likelihoods at ll); the caller
+// adds where its frames, backtrace arena, paths and results are.
+DecArgs ArgsOf(const pk_mi355_decoder *d, const float *ll, int n) {
+  DecArgs A = {};
+  A.e_off = d->e_off; A.e_arc = d->e_arc; A.e_src = d->e_src;
+  A.n_off = d->n_off; A.n_arc = d->n_arc; A.n_src = d->n_src;
+  A.final_w = d->final_w;
+  A.num_states = d->num_states; A.start = d->start; A.num_pdfs = d->num_pdfs;
+  A.ll = ll; A.num_utts = n;
+  const size_t per = (size_t)d->num_states * d->max_utts;
+  A.key = d->key; A.tr = d->tr; A.mark = d->mark; A.touched = d->touched; A.nxt = d->nxt;
+  A.la = d->lists; A.lb = d->lists + per; A.fa = d->lists + 2 * per; A.fb = d->lists + 3 * per;
+  A.rec = d->rec; A.path = d->path;
+  A.beam = d->beam; A.max_active = d->max_active;
+  A.max_rounds = d->num_states + 2;    // Bellman-Ford bound: more rounds only under a negative epsilon cycle
+  return A;
+}
+
+// One host log-likelihood matrix against the model (`what`: the caller's name for item i).
+int CheckLoglik(const pk_mi355_decoder *d, const pk_matrix_t &m, const char *what, int i) {
+  if (m.ncol < 0 || (m.ncol > 0 && (m.nrow != d->num_pdfs || !m.data)))
+    return Fail(PK_MI355_E_INVALID, "%s %d: log_prob is {ncol %d, nrow %d}, nrow %d expected", what, i, m.ncol, m.nrow,
+                d->num_pdfs);
+  return 0;
+}
+
+// Checked host log-likelihoods into d_ll, one after the other (item i at the sum of the sizes before it), queued on
+// own_stream.  The caller has waited for the last call that read d_ll.
+int UploadLoglik(pk_mi355_decoder *d, const pk_decodable_t *src, int n) {
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) total += (int64_t)src[i].log_prob.ncol * d->num_pdfs;
+  if ((size_t)total > d->d_ll_floats) {
+    if (d->d_ll) hipFree(d->d_ll);
+    d->d_ll = nullptr;
+    d->d_ll_floats = 0;
+    HIP_TRY(hipMalloc(&d->d_ll, sizeof(float) * (size_t)total));
+    d->d_ll_floats = (size_t)total;
+  }
+  int64_t at = 0;
+  for (int i = 0; i < n; ++i) {
+    const pk_matrix_t &m = src[i].log_prob;
+    const int64_t count = (int64_t)m.ncol * d->num_pdfs;
+    if (count > 0)
+      HIP_TRY(hipMemcpyAsync(d->d_ll + at, m.data, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, d->own_stream));
+    at += count;
+  }
+  return 0;
+}
+
+// The words of a path: its arcs' non-zero olabels, in path order.  Returns their number; writes at most max_words.
+int PathWords(const pk_mi355_decoder *d, const int32_t *arcs, int num_arcs, int *words, int max_words) {
+  int n = 0;
+  for (int i = 0; i < num_arcs; ++i) {
+    const int arc = arcs[i];
+    const int w = (arc >= 0 && arc < (int)d->olabel.size()) ? d->olabel[arc] : 0;
+    if (w != 0) {
+      if (words && n < max_words) words[n] = w;
+      ++n;
+    }
+  }
+  return n;
+}
+
 // Queue one decode of num_utts utterances whose log-likelihoods lie at ll + off[u] (T[u] frames each) on `stream`.
 int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off, const std::vector<int> &T,
            hipStream_t stream) {
@@ -894,19 +867,10 @@ int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off
     HIP_TRY(hipMemcpyAsync(d->d_off, d->h_off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d->d_T, d->h_T.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * 2, stream));
-    DecArgs A;
-    A.e_off = d->e_off; A.e_arc = d->e_arc; A.e_src = d->e_src;
-    A.n_off = d->n_off; A.n_arc = d->n_arc; A.n_src = d->n_src;
-    A.final_w = d->final_w;
-    A.num_states = d->num_states; A.start = d->start; A.num_pdfs = d->num_pdfs;
-    A.ll = ll; A.ll_off = d->d_off; A.T = d->d_T; A.num_utts = n;
-    const size_t per = (size_t)d->num_states * d->max_utts;
-    A.key = d->key; A.tr = d->tr; A.mark = d->mark; A.touched = d->touched; A.nxt = d->nxt;
-    A.la = d->lists; A.lb = d->lists + per; A.fa = d->lists + 2 * per; A.fb = d->lists + 3 * per;
-    A.rec = d->rec; A.rec_cap = d->trace_cap; A.rec_top = d->counters;
-    A.path = d->path; A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
-    A.beam = d->beam; A.max_active = d->max_active;
-    A.max_rounds = d->num_states + 2;    // Bellman-Ford bound: more rounds only under a negative epsilon cycle
+    DecArgs A = ArgsOf(d, ll, n);
+    A.ll_off = d->d_off; A.T = d->d_T;
+    A.rec_cap = d->trace_cap; A.rec_top = d->counters;       // one arena and one path arena shared by the call
+    A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
     A.res = d->d_res;
     hipLaunchKernelGGL(DecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
     hipError_t e = hipGetLastError();
@@ -1039,24 +1003,12 @@ int pk_mi355_decoder_decode(pk_mi355_decoder_t *d, const pk_decodable_t *utts, i
   int64_t total = 0;
   for (int u = 0; u < num_utts; ++u) {
     const pk_matrix_t &m = utts[u].log_prob;
-    if (m.ncol < 0 || (m.ncol > 0 && (m.nrow != d->num_pdfs || !m.data)))
-      return Fail(PK_MI355_E_INVALID, "decoder: utterance %d: log_prob is {ncol %d, nrow %d}, nrow %d expected", u, m.ncol,
-                  m.nrow, d->num_pdfs);
+    if ((rc = CheckLoglik(d, m, "decoder: utterance", u))) return rc;
     off[u] = total;
     T[u] = m.ncol;
     total += (int64_t)m.ncol * d->num_pdfs;
   }
-  if ((size_t)total > d->d_ll_floats) {
-    if (d->d_ll) hipFree(d->d_ll);
-    d->d_ll = nullptr;
-    d->d_ll_floats = 0;
-    HIP_TRY(hipMalloc(&d->d_ll, sizeof(float) * (size_t)total));
-    d->d_ll_floats = (size_t)total;
-  }
-  for (int u = 0; u < num_utts; ++u)
-    if (T[u] > 0)
-      HIP_TRY(hipMemcpyAsync(d->d_ll + off[u], utts[u].log_prob.data, sizeof(float) * (size_t)T[u] * d->num_pdfs,
-                             hipMemcpyHostToDevice, d->own_stream));
+  if ((rc = UploadLoglik(d, utts, num_utts))) return rc;
   d->batch = nullptr;
   if ((rc = Launch(d, d->d_ll, off, T, d->own_stream))) return rc;
   return sync ? Collect(d) : 0;
@@ -1078,18 +1030,9 @@ int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, in
   int rc = CheckResult(d, utt);
   if (rc) return rc;
   const UttResult &r = d->res[utt];
-  int n = 0;
-  for (int i = 0; i < r.path_len; ++i) {
-    const int arc = d->h_path[r.path_off + i];
-    const int w = (arc >= 0 && arc < (int)d->olabel.size()) ? d->olabel[arc] : 0;
-    if (w != 0) {
-      if (words && n < max_words) words[n] = w;
-      ++n;
-    }
-  }
   if (weight) *weight = r.weight;
   if (ok) *ok = r.ok;
-  return n;
+  return PathWords(d, d->h_path.data() + r.path_off, r.path_len, words, max_words);
 }
 
 int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs) {
@@ -1136,22 +1079,9 @@ int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<
   const int n = (int)calls.size();
   if (n > 0) {
     HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
-    DecArgs A;
-    A.e_off = d->e_off; A.e_arc = d->e_arc; A.e_src = d->e_src;
-    A.n_off = d->n_off; A.n_arc = d->n_arc; A.n_src = d->n_src;
-    A.final_w = d->final_w;
-    A.num_states = d->num_states; A.start = d->start; A.num_pdfs = d->num_pdfs;
-    A.ll = ll; A.ll_off = nullptr; A.T = nullptr; A.num_utts = n;
-    const size_t per = (size_t)d->num_states * d->max_utts;
-    A.key = d->key; A.tr = d->tr; A.mark = d->mark; A.touched = d->touched; A.nxt = d->nxt;
-    A.la = d->lists; A.lb = d->lists + per; A.fa = d->lists + 2 * per; A.fb = d->lists + 3 * per;
-    A.rec = d->rec; A.rec_cap = o->cap; A.rec_top = nullptr;
-    A.path = d->path; A.path_cap = (int)o->cap; A.path_top = nullptr;
-    A.beam = d->beam; A.max_active = d->max_active;
-    A.max_rounds = d->num_states + 2;
-    A.res = nullptr;
-    hipLaunchKernelGGL(OnlineDecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A, o->d_calls,
-                       o->d_state, o->d_results, o->d_remap, o->cap);
+    // (frames, arenas and results are per slot: the calls, and o->cap entries of rec and path each)
+    hipLaunchKernelGGL(OnlineDecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, ArgsOf(d, ll, n),
+                       o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
   }
@@ -1193,15 +1123,7 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
 }
 
 int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
-  int n = 0;
-  for (int arc : o->paths[slot]) {
-    const int w = (arc >= 0 && arc < (int)o->dec.olabel.size()) ? o->dec.olabel[arc] : 0;
-    if (w != 0) {
-      if (words && n < max_words) words[n] = w;
-      ++n;
-    }
-  }
-  return n;
+  return PathWords(&o->dec, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
 }
 
 int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {
@@ -1284,24 +1206,12 @@ int pk_mi355_online_decoder_advance_host(pk_mi355_online_decoder_t *o, const int
     if (seen[slot]) return Fail(PK_MI355_E_INVALID, "online decoder: slot %d twice in one call", slot);
     seen[slot] = 1;
     const pk_matrix_t &m = chunks[i].log_prob;
-    if (m.ncol < 0 || (m.ncol > 0 && (m.nrow != d->num_pdfs || !m.data)))
-      return Fail(PK_MI355_E_INVALID, "online decoder: chunk %d: log_prob is {ncol %d, nrow %d}, nrow %d expected", i, m.ncol,
-                  m.nrow, d->num_pdfs);
+    if ((rc = CheckLoglik(d, m, "online decoder: chunk", i))) return rc;
     calls[i] = OnlineCall{slot, m.ncol, final_ && final_[i] ? 1 : 0, o->fresh[slot], total};
     total += (int64_t)m.ncol * d->num_pdfs;
   }
   if (o->pending) HIP_TRY(hipEventSynchronize(d->done));     // d_ll may still be read by the previous call
-  if ((size_t)total > d->d_ll_floats) {
-    if (d->d_ll) hipFree(d->d_ll);
-    d->d_ll = nullptr;
-    d->d_ll_floats = 0;
-    HIP_TRY(hipMalloc(&d->d_ll, sizeof(float) * (size_t)total));
-    d->d_ll_floats = (size_t)total;
-  }
-  for (int i = 0; i < n; ++i)
-    if (calls[i].T > 0)
-      HIP_TRY(hipMemcpyAsync(d->d_ll + calls[i].ll_off, chunks[i].log_prob.data, sizeof(float) * (size_t)calls[i].T * d->num_pdfs,
-                             hipMemcpyHostToDevice, d->own_stream));
+  if ((rc = UploadLoglik(d, chunks, n))) return rc;
   if ((rc = OnlineLaunch(o, d->d_ll, calls, d->own_stream))) return rc;
   return sync ? OnlineCollect(o) : 0;
 }
