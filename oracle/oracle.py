@@ -1,5 +1,6 @@
-"""ctypes front for the CPU oracle (oracle/liboracle.so) and the partial
-real-reference build (oracle/_ref/libpkref.so).
+"""ctypes front for the CPU oracle (oracle/liboracle.so) and the real-reference builds:
+oracle/_ref/libpkref.so (FFT + SGEMM) and oracle/_ref/libpkref_am[_ndebug].so (the whole
+acoustic path: WAV reader, fbank, CMVN, nnet, am tail, decodable).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  The product package never imports this.
@@ -13,6 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "liboracle.so")
 _REF = os.path.join(_HERE, "_ref", "libpkref.so")
+_REF_AM = os.path.join(_HERE, "_ref", "libpkref_am.so")                  # assertions on, as the reference builds
+_REF_AM_NDEBUG = os.path.join(_HERE, "_ref", "libpkref_am_ndebug.so")    # -DNDEBUG: the non-finite softmax case only
 
 NUM_BINS = 40
 FRAME_LENGTH = 400
@@ -27,7 +30,8 @@ _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 def build(force=False):
     """Compile liboracle.so (and _ref when /root/reference is mounted)."""
     if force or not os.path.exists(_LIB) or (
-            os.path.isdir("/root/reference/src") and not os.path.exists(_REF)):
+            os.path.isdir("/root/reference/src")
+            and not all(os.path.exists(p) for p in (_REF, _REF_AM, _REF_AM_NDEBUG))):
         subprocess.check_call(["make", "-s", "-C", _HERE])
 
 
@@ -97,6 +101,138 @@ def ref():
 
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
+
+
+# --------------------------------------------------------------------------- the reference's acoustic path
+
+def have_ref_am():
+    build()
+    return os.path.exists(_REF_AM) and os.path.exists(_REF_AM_NDEBUG)
+
+
+_ref_am = {}
+
+
+def ref_am(ndebug=False):
+    """The REAL reference acoustic path (oracle/ref_am_shim.cc).  ndebug=False: assertions on, as the
+    reference's Makefile.am builds it -- a NaN reaching ApplyLog ABORTS the process (vector.cc:336), so only
+    finite cases go there; ndebug=True: the same sources with -DNDEBUG."""
+    if ndebug not in _ref_am:
+        build()
+        R = C.CDLL(_REF_AM_NDEBUG if ndebug else _REF_AM)
+        pp = C.POINTER(C.POINTER(C.c_float))
+        R.pkref_wav_read.argtypes = [C.c_char_p, pp, C.c_char_p]
+        R.pkref_free.argtypes = [C.c_void_p]
+        R.pkref_fbank.argtypes = [_f32p, C.c_int, _f32p, C.c_int]
+        R.pkref_cmvn.argtypes = [_f32p, _f32p, C.c_int, _f32p]
+        R.pkref_nnet_load.restype = C.c_void_p
+        R.pkref_nnet_load.argtypes = [C.c_char_p, C.c_char_p]
+        R.pkref_nnet_propagate.argtypes = [C.c_void_p, _f32p, C.c_int, C.c_int, pp]
+        R.pkref_nnet_free.argtypes = [C.c_void_p]
+        R.pkref_am_load.restype = C.c_void_p
+        R.pkref_am_load.argtypes = [C.c_char_p, C.c_char_p]
+        R.pkref_am_free.argtypes = [C.c_void_p]
+        R.pkref_am_num_pdfs.argtypes = [C.c_void_p]
+        R.pkref_am_tid2pdf.argtypes = [C.c_void_p, C.c_int]
+        R.pkref_decodable.argtypes = [C.c_void_p, C.c_float, _f32p, C.c_int, C.c_int, _f32p, C.c_int]
+        _ref_am[ndebug] = R
+    return _ref_am[ndebug]
+
+
+def _take(R, p, shape):
+    n = int(np.prod(shape))
+    arr = np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].copy().reshape(shape)
+    R.pkref_free(p)
+    return arr
+
+
+def ref_wav_read(path, ndebug=False):
+    """pk_16kpcm_read."""
+    R = ref_am(ndebug)
+    p, msg = C.POINTER(C.c_float)(), C.create_string_buffer(256)
+    n = R.pkref_wav_read(path.encode(), C.byref(p), msg)
+    if n < 0:
+        raise IOError(msg.value.decode())
+    return _take(R, p, (n,))
+
+
+def ref_fbank(wave, ndebug=False):
+    """Fbank::Compute -> [T][40].  An empty wave is not handed in (pk_process returns before the
+    front-end, pocketkaldi.cc:180-184); the reference's 0 x 0 for fewer than 400 samples comes back as 0 x 40."""
+    wave = np.ascontiguousarray(wave, dtype=np.float32)
+    cap = wave.shape[0] // FRAME_SHIFT + 2
+    out = np.zeros((cap, NUM_BINS), dtype=np.float32)
+    T = ref_am(ndebug).pkref_fbank(wave, wave.shape[0], out, cap) if wave.shape[0] else 0
+    assert 0 <= T <= cap, T
+    return out[:T].copy()
+
+
+def ref_cmvn(global_stats, raw, ndebug=False):
+    """CMVN + GetFrame frame by frame, as pk_process does."""
+    g = np.ascontiguousarray(global_stats, dtype=np.float32)
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    assert g.shape == (NUM_BINS + 1,) and g[NUM_BINS] > 0 and raw.shape[1] == NUM_BINS
+    out = np.zeros_like(raw)
+    if raw.shape[0]:
+        ref_am(ndebug).pkref_cmvn(g, raw, raw.shape[0], out)
+    return out
+
+
+class RefNnet:
+    """Nnet::Read on an NNT0 file + Nnet::Propagate."""
+
+    def __init__(self, path, ndebug=False):
+        self._R = ref_am(ndebug)
+        msg = C.create_string_buffer(256)
+        self._h = self._R.pkref_nnet_load(path.encode(), msg)
+        if not self._h:
+            raise IOError(msg.value.decode())
+
+    def propagate(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        T, D = x.shape
+        assert T >= 1 and D >= 1
+        p = C.POINTER(C.c_float)()
+        dim = self._R.pkref_nnet_propagate(self._h, x, T, D, C.byref(p))
+        assert dim >= 1, dim
+        return _take(self._R, p, (T, dim))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._R.pkref_nnet_free(self._h)
+            self._h = None
+
+
+class RefAm:
+    """Configuration::Read + AcousticModel::Read on a model .conf; decodable() = pk_decodable_init."""
+
+    def __init__(self, conf_path, ndebug=False):
+        self._R = ref_am(ndebug)
+        msg = C.create_string_buffer(256)
+        self._h = self._R.pkref_am_load(conf_path.encode(), msg)
+        if not self._h:
+            raise IOError(msg.value.decode())
+
+    def num_pdfs(self):
+        return self._R.pkref_am_num_pdfs(self._h)
+
+    def tid2pdf(self, tid):
+        return self._R.pkref_am_tid2pdf(self._h, int(tid))
+
+    def decodable(self, feats, prob_scale):
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        T, D = feats.shape
+        N = self.num_pdfs()
+        out = np.zeros((T, N), dtype=np.float32)
+        if T:
+            dim = self._R.pkref_decodable(self._h, float(prob_scale), feats, T, D, out, N)
+            assert dim == N, (dim, N)
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._R.pkref_am_free(self._h)
+            self._h = None
 
 
 # --------------------------------------------------------------------------- FFT

@@ -17,12 +17,15 @@
  *     known-answer vector of test/srfft_test.cc.
  *   - sgemm: bit-identical to the reference's GEMM<float>::Gemm (gemm.cc +
  *     gemm_haswell.cc compiled into oracle/_ref).
- *   - fbank / cmvn: pinned by the reference's Kaldi dumps
- *     (test/data/fbank*_en-us-hello.wav.txt) at the precision those dumps have.
- *   - layers: pinned by the known answers of test/nnet_test.cc.
- *   The reference's vector.cc / matrix.cc cannot be compiled in this image
- *   (they include <cblas.h>, which the image lacks), so fbank.cc, cmvn.cc,
- *   nnet.cc, am.cc and decodable.cc cannot be linked into oracle/_ref.
+ *   - WAV reader, fbank, cmvn, every layer kind, splice, the am tail and the
+ *     decodable scale: bit-identical to the reference's own pcm_reader.cc,
+ *     fbank.cc, cmvn.cc, nnet.cc, am.cc, decodable.cc compiled into
+ *     oracle/_ref/libpkref_am*.so (oracle/Makefile: ref_am; an EMPTY <cblas.h>
+ *     satisfies the two includes of vector.cc / matrix.cc, which use no cblas_
+ *     symbol) -- tests/test_oracle_ref_am.py, and against committed outputs of
+ *     that build (tests/golden/ref_am_path.npz) where the reference is absent.
+ *   - also: the reference's Kaldi dumps (test/data/fbank*_en-us-hello.wav.txt)
+ *     at the precision they have, and the known answers of test/nnet_test.cc.
  */
 #ifndef PK_ORACLE_H_
 #define PK_ORACLE_H_

@@ -6,9 +6,8 @@
 // TEST INFRASTRUCTURE ONLY.  The reference sources are compiled where they lie;
 // nothing of them is copied into this repository.  Output: oracle/_ref/libpkref.so.
 //
-// The reference's vector.cc / matrix.cc include <cblas.h>, which this image does
-// not have, so fbank.cc, cmvn.cc, nnet.cc, am.cc and decodable.cc cannot be
-// linked here; those stages are pinned by the reference's fixtures instead.
+// The rest of the acoustic path (fbank.cc, cmvn.cc, nnet.cc, am.cc, decodable.cc, pcm_reader.cc) is built
+// by the same Makefile into oracle/_ref/libpkref_am*.so: see ref_am_shim.cc.
 #include "gemm.h"
 #include "srfft.h"
 

@@ -260,7 +260,9 @@ int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
       for (const int64_t end = (b->h_out_base[u] + RoundUp(b->h_T[u], 4)) / 4; g < end; ++g) b->h_shift4[g] = shift;
     }
     for (; g < groups; ++g) b->h_shift4[g] = shift;
-    if (shift + kTile > b->zero_span) return Fail(PK_MI355_E_INVALID, "internal: column shift %d exceeds the zero span", shift);
+    // (a negative shift would wrap in the kernels' unsigned lane offsets; batch_create keeps L + R < 3 out of this layout)
+    if (*std::min_element(b->h_shift4.begin(), b->h_shift4.end()) < 0 || shift + kTile > b->zero_span)
+      return Fail(PK_MI355_E_INVALID, "internal: column shift outside [0, %lld]", (long long)(b->zero_span - kTile));
     HIP_TRY(hipMemcpyAsync(b->d_shift4, b->h_shift4.data(), sizeof(int32_t) * groups, hipMemcpyHostToDevice, b->stream));
   }
   HIP_TRY(hipMemcpyAsync(b->d_wave_off, b->h_wave_off.data(), sizeof(int64_t) * num_utts, hipMemcpyHostToDevice, b->stream));
@@ -327,8 +329,14 @@ pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_s
   b->max_frames = max_total_samples / kFrameShift + max_utts;
   b->max_cols = RoundUp(b->max_frames + (int64_t)max_utts * pad, kTileF16);
   b->chunk = std::min<int64_t>(b->chunk, b->max_cols);
-  b->compact = true;
-  if (const char *c = getenv("PK_MI355_COMPACT_ROWS")) b->compact = atoi(c) != 0;    // (A/B switch: 0 = row = column of Yt)
+  // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
+  // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
+  // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
+  // the shift to UNSIGNED 32-bit lane offsets of scalar-base LDS-DMA (gemm.hip issue_splice, gemm_f16.hip xoff), where a
+  // negative value addresses 4 GiB further on.  With fewer than three context frames there are next to no pad rows to
+  // save anyway: such models keep row = column of Yt.
+  b->compact = pad >= 3;
+  if (const char *c = getenv("PK_MI355_COMPACT_ROWS")) b->compact = b->compact && atoi(c) != 0;    // (A/B switch: 0 = row = column of Yt)
   // (the padding rows of the spliced operand read zeros from the end of feature row 0, at their column shift: at most
   // `pad` columns per utterance in front of them)
   b->zero_span = RoundUp((int64_t)max_utts * pad + 2 * kTile, 256);

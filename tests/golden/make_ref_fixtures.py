@@ -9,6 +9,13 @@ And outputs of the REAL reference code that builds here (oracle/_ref: srfft.cc,
 gemm.cc, gemm_haswell.cc) on our own seeded inputs:
   * ref_srfft512.npz  -- 8 frames in, packed spectra out
   * ref_sgemm.npz     -- small A, B and the reference GEMM<float>::Gemm product
+And outputs of the reference's whole acoustic path (oracle/_ref/libpkref_am*.so: pcm_reader.cc, fbank.cc, cmvn.cc,
+nnet.cc, am.cc, decodable.cc compiled from their own files) -- `make_ref_fixtures.py am` writes this one alone:
+  * ref_am_path.npz   -- fbank and CMVN (test/data/cmvn_stats.bin) of both golden WAVs and of synth.utterance(950, 7.3 s)
+                         (728 frames: the CMVN window slides); pk_decodable_init for tests/golden/refmodel on both WAVs
+                         (CMVN with refmodel_cmvn.bin); for the synthetic models "S" and "W" on the hello WAV's CMVN'd
+                         features a SHA-256 of the 47 x N matrix and rows 0, 23, 46; the overflowing softmax's 5 x 200
+                         matrix from the -DNDEBUG flavour (with assertions on that input aborts, vector.cc:336).
 """
 import json
 import os
@@ -29,7 +36,48 @@ def parse_float_array(text, name):
     return [float(tok.rstrip("f")) for tok in re.findall(r"[-+0-9.eE]+f?", m.group(1)) if tok.strip("f")]
 
 
+def make_am_fixture():
+    import tempfile
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from oracle import oracle as O
+    from pocketkaldi_amd import synth
+    from refmodel_files import overflow_model, sha256_rows, write_model
+    assert O.have_ref_am()
+    z = {}
+    stats = O.read_vec(os.path.join(HERE, "cmvn_stats.bin"))
+    rstats = O.read_vec(os.path.join(HERE, "refmodel", "refmodel_cmvn.bin"))
+    refmodel = O.RefAm(os.path.join(HERE, "refmodel", "refmodel.conf"))
+    waves = {"hello": O.ref_wav_read(os.path.join(HERE, "en-us-hello.wav")),
+             "cat": O.ref_wav_read(os.path.join(HERE, "en-us-cat.wav")),
+             "utt950": synth.utterance(950, seconds=7.3)}
+    for name, w in waves.items():
+        z["fbank_" + name] = O.ref_fbank(w)
+        z["cmvn_" + name] = O.ref_cmvn(stats, z["fbank_" + name])
+        if name != "utt950":
+            z["ll_refmodel_" + name] = refmodel.decodable(O.ref_cmvn(rstats, z["fbank_" + name]), 0.1)
+    assert z["fbank_utt950"].shape == (728, 40)
+    for name in ("S", "W"):
+        layers, prior, L, R = synth.model(name)
+        with tempfile.TemporaryDirectory() as d:
+            ll = O.RefAm(write_model(d, layers, prior, L, R)).decodable(z["cmvn_hello"], 0.1)
+        z["ll_%s_hello_sha256" % name] = sha256_rows(ll)
+        z["ll_%s_hello_rows" % name] = ll[[0, 23, 46]]
+    layers, prior = overflow_model()
+    with tempfile.TemporaryDirectory() as d:
+        conf = write_model(d, layers, prior, 0, 0)
+        z["ll_overflow"] = O.RefAm(conf, ndebug=True).decodable(np.zeros((5, 40), np.float32), 0.1)
+    # float arrays are stored as their four byte planes (uint8 [4, ...], little-endian): sign / exponent bytes compress
+    # far better apart from the mantissa bytes, which keeps the file under the size of the largest fixture so far;
+    # tests/refmodel_files.py: load_ref_am_path() puts them together again
+    z = {k: (np.moveaxis(np.ascontiguousarray(v, "<f4").view(np.uint8).reshape(v.shape + (4,)), -1, 0).copy()
+             if v.dtype == np.float32 else v) for k, v in z.items()}
+    np.savez_compressed(os.path.join(HERE, "ref_am_path.npz"), **z)
+    print("ref_am_path.npz: %d bytes" % os.path.getsize(os.path.join(HERE, "ref_am_path.npz")))
+
+
 def main():
+    if sys.argv[1:] == ["am"]:
+        return make_am_fixture()
     src = open(os.path.join(REF, "test/srfft_test.cc")).read()
     data = parse_float_array(src, "data")
     fft = parse_float_array(src, "fft_data")
@@ -77,6 +125,7 @@ def main():
         gem["B%d" % i] = B
         gem["C%d" % i] = O.ref_sgemm(A, B)
     np.savez(os.path.join(HERE, "ref_sgemm.npz"), **gem)
+    make_am_fixture()
     print("fixtures written to", HERE)
 
 

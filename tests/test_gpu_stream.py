@@ -158,8 +158,9 @@ def test_stream_int16_pushes_and_one_sample_chunks():
 
 @pytest.mark.parametrize("softmax", ["reference", "stable"])
 def test_no_context_model_against_the_oracle(softmax):
-    """L + R = 0 (the case whose compact-row column shift goes negative in the batch scorer, which is therefore not run
-    here): the oracle, bitwise with the reference softmax, within the 1e-4 contract with the stable one."""
+    """L + R = 0 through the online scorer (its column shifts are non-negative by construction; the batch scorer lays
+    models with L + R < 3 out with row = column, tests/test_gpu_reference_pin.py runs it): the oracle, bitwise with
+    the reference softmax, within the 1e-4 contract with the stable one."""
     layers, prior, L, R, _, g = model_s(left=0, right=0)
     am = pk.AcousticModel(layers, prior, L, R).set_softmax(softmax)
     waves = [pk.read_wav(os.path.join(GOLDEN, "en-us-cat.wav")), synth.utterance(970, seconds=6.5),

@@ -55,3 +55,66 @@ def test_sgemm_bitwise_vs_live_reference(shape):
     r = O.ref_sgemm(A, B)
     assert np.array_equal(_bits(O.sgemm(A, B)), _bits(r))
     assert np.array_equal(_bits(O.sgemm_naive(A, B)), _bits(r))
+
+
+# ------------------------------------------------------------------ the reference's whole acoustic path, committed
+# tests/golden/ref_am_path.npz holds outputs of the REAL reference (oracle/_ref/libpkref_am*.so, made by
+# tests/golden/make_ref_fixtures.py): a pin that holds in a checkout without the reference tree.  The live library
+# against the same fixture shows a drifting compiler or flag as such, not as an oracle or kernel bug.
+
+def _same_bits_nan(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    both = np.isnan(a) & np.isnan(b)
+    return a.shape == b.shape and np.array_equal(np.where(both, 0, a.view(np.uint32)), np.where(both, 0, b.view(np.uint32)))
+
+
+def _check_against_fixture(wav_read, fbank, cmvn, refmodel_ll, model_ll, overflow_ll):
+    """Every array / hash of the fixture recomputed by one implementation (the oracle, or the live reference)."""
+    from pocketkaldi_amd import synth
+    from refmodel_files import load_ref_am_path, overflow_model, sha256_rows
+    z = load_ref_am_path()
+    stats = O.read_vec(os.path.join(G, "cmvn_stats.bin"))
+    rstats = O.read_vec(os.path.join(G, "refmodel", "refmodel_cmvn.bin"))
+    waves = {"hello": wav_read(os.path.join(G, "en-us-hello.wav")), "cat": wav_read(os.path.join(G, "en-us-cat.wav")),
+             "utt950": synth.utterance(950, seconds=7.3)}
+    for name, w in waves.items():
+        fb = fbank(w)
+        assert _same_bits_nan(fb, z["fbank_" + name]), name
+        assert _same_bits_nan(cmvn(stats, fb), z["cmvn_" + name]), name
+        if name != "utt950":
+            assert _same_bits_nan(refmodel_ll(cmvn(rstats, fb)), z["ll_refmodel_" + name]), name
+    assert z["fbank_utt950"].shape == (728, 40)                      # the 600-frame window slides
+    for name in ("S", "W"):
+        layers, prior, L, R = synth.model(name)
+        ll = model_ll(layers, prior, L, R, z["cmvn_hello"])
+        assert np.array_equal(sha256_rows(ll), z["ll_%s_hello_sha256" % name]), name
+        assert _same_bits_nan(ll[[0, 23, 46]], z["ll_%s_hello_rows" % name]), name
+    layers, prior = overflow_model()
+    assert int(np.isnan(z["ll_overflow"]).sum()) == 30
+    assert _same_bits_nan(overflow_ll(layers, prior, np.zeros((5, 40), np.float32)), z["ll_overflow"])
+
+
+def test_oracle_matches_committed_reference_acoustic_path():
+    from refmodel_text import load_text_model
+    layers, prior, L, R, _, _ = load_text_model()
+    nn = O.Nnet(layers)
+    _check_against_fixture(O.wav_read, O.Fbank().compute, O.cmvn,
+                           lambda f: nn.am_compute(f, prior, L, R, 0.1),
+                           lambda ls, pr, l, r, f: O.Nnet(ls).am_compute(f, pr, l, r, 0.1),
+                           lambda ls, pr, f: O.Nnet(ls).am_compute(f, pr, 0, 0, 0.1))
+
+
+@pytest.mark.skipif(not O.have_ref_am(), reason="oracle/_ref/libpkref_am.so not built")
+def test_live_reference_matches_its_committed_outputs(tmp_path):
+    from refmodel_files import write_model
+    refmodel = O.RefAm(os.path.join(G, "refmodel", "refmodel.conf"))
+    n = [0]
+
+    def model_ll(layers, prior, L, R, feats, ndebug=False):
+        n[0] += 1
+        d = tmp_path / str(n[0])
+        d.mkdir()
+        return O.RefAm(write_model(d, layers, prior, L, R), ndebug=ndebug).decodable(feats, 0.1)
+
+    _check_against_fixture(O.ref_wav_read, O.ref_fbank, O.ref_cmvn, lambda f: refmodel.decodable(f, 0.1), model_ll,
+                           lambda ls, pr, f: model_ll(ls, pr, 0, 0, f, ndebug=True))   # (aborts with assertions on)
