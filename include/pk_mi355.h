@@ -420,6 +420,17 @@ pk_mi355_decoder_t *pk_mi355_decoder_create(const pk_mi355_fst_t *fst, const pk_
 void pk_mi355_decoder_destroy(pk_mi355_decoder_t *d);
 /* Decoder::beam_ (default 16.0) and kBeamSize (max-active, default 30000).                    */
 int pk_mi355_decoder_set_beam(pk_mi355_decoder_t *d, float beam, int max_active);
+/* Backtrace garbage collection, off (0) by default; takes effect at the next decode /
+ * decode_batch (a call already queued keeps the mode it was queued with, as with set_beam).
+ * On: each of the n utterances of a call owns floor(trace_capacity / n) records of the arena
+ * (n is that call's count, not max_utts) and compacts them -- keeps the records its live tokens
+ * can still reach -- whenever more than half are in use before a frame.  Results are the same,
+ * bit for bit; what is bounded is no longer the records a call writes but those one utterance
+ * keeps alive: a slice needs about twice its live records plus one frame's records
+ * (pk_mi355_decoder_trace_stats measures it).  A slice still full after compaction, or a frame
+ * that writes more than the free part, ends the call with PK_MI355_E_CAPACITY as below.  No
+ * additional device memory.                                                                    */
+int pk_mi355_decoder_set_trace_gc(pk_mi355_decoder_t *d, int enable);
 /* All utterances of a scored batch, on the batch's stream, ordered after its scoring; nothing
  * leaves HBM.  If the score call ended in PK_MI355_E_RANGE the results are withheld (with
  * sync == 0 pk_mi355_decoder_synchronize returns the code).  The batch must be neither scored
@@ -445,6 +456,13 @@ int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, in
  * an upper bound on the reference's token count, so <= max-active shows it did not bind.      */
 int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs);
 int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt);
+/* Backtrace use of the last call, for sizing trace_capacity (any pointer may be NULL).  With
+ * trace gc on: the most records utt's slice held at once (sampled before every compaction and
+ * at the end), the slice's size, and how often it was compacted.  With it off: the records the
+ * whole call wrote (the same for every utt), trace_capacity, and 0.  PK_MI355_E_STATE before
+ * any result is readable.                                                                      */
+int pk_mi355_decoder_trace_stats(const pk_mi355_decoder_t *d, int utt, int64_t *peak_records,
+                                 int64_t *slice_records, int *compactions);
 
 /* ------------------------------------------------------------------------- */
 /* Online scorer -- live PCM in chunks, pk_process's acoustic stages (pocketkaldi.cc: */

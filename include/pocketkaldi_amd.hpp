@@ -204,6 +204,12 @@ class Decoder {
   Decoder &operator=(const Decoder &) = delete;
 
   Status SetBeam(float beam, int max_active) { return Status::FromLast(pk_mi355_decoder_set_beam(d_, beam, max_active)); }
+  // From the next Decode on: the backtrace is compacted as it fills (pk_mi355_decoder_set_trace_gc); same results
+  Status SetTraceGc(bool on) { return Status::FromLast(pk_mi355_decoder_set_trace_gc(d_, on ? 1 : 0)); }
+  // Backtrace use of the last Decode (pk_mi355_decoder_trace_stats), for sizing trace_capacity
+  Status TraceStats(int64_t *peak_records, int64_t *slice_records, int *compactions) const {
+    return Status::FromLast(pk_mi355_decoder_trace_stats(d_, 0, peak_records, slice_records, compactions));
+  }
 
   // Decoder::Decode (src/decoder.cc:39-77): true when tokens survive the last frame.  A device or capacity
   // failure returns false and sets last_status().

@@ -77,6 +77,7 @@ EXPORTS = [
     "pk_mi355_fst_arc_range", "pk_mi355_decoder_create", "pk_mi355_decoder_destroy", "pk_mi355_decoder_set_beam",
     "pk_mi355_decoder_decode_batch", "pk_mi355_decoder_decode", "pk_mi355_decoder_synchronize", "pk_mi355_decoder_result",
     "pk_mi355_decoder_best_path_arcs", "pk_mi355_decoder_active_bound", "pk_mi355_last_error_code",
+    "pk_mi355_decoder_set_trace_gc", "pk_mi355_decoder_trace_stats",
     "pk_mi355_stream_create", "pk_mi355_stream_destroy", "pk_mi355_stream_open", "pk_mi355_stream_push",
     "pk_mi355_stream_push_i16", "pk_mi355_stream_close", "pk_mi355_stream_step", "pk_mi355_stream_synchronize",
     "pk_mi355_stream_loglik_device", "pk_mi355_stream_fetch",
@@ -213,6 +214,9 @@ def lib():
     L.pk_mi355_decoder_result.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.POINTER(C.c_int)]
     L.pk_mi355_decoder_best_path_arcs.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
     L.pk_mi355_decoder_active_bound.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_decoder_set_trace_gc.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_decoder_trace_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int)]
     L.pk_mi355_stream_create.restype = C.c_void_p
     L.pk_mi355_stream_create.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int64]
     L.pk_mi355_stream_destroy.restype = None
@@ -781,15 +785,18 @@ class Fst:
 
 
 class Decoder:
-    """decoder.h: Decoder::Decode + BestPath on the GPU, one workgroup per utterance."""
+    """decoder.h: Decoder::Decode + BestPath on the GPU, one workgroup per utterance.  trace_gc: every utterance of
+    a call owns trace_capacity // n backtrace records and compacts them as they fill (same results, bit for bit)."""
 
-    def __init__(self, fst, am, max_utts, trace_capacity=0):
+    def __init__(self, fst, am, max_utts, trace_capacity=0, trace_gc=False):
         self._fst, self._am = fst, am
         self._h = lib().pk_mi355_decoder_create(fst.handle, am.handle, int(max_utts), int(trace_capacity))
         if not self._h:
             msg = lib().pk_mi355_last_error().decode()
             raise PkCodeError(lib().pk_mi355_last_error_code(), msg)
         self._keep = None
+        if trace_gc:
+            self.set_trace_gc(True)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -804,6 +811,10 @@ class Decoder:
 
     def set_beam(self, beam=16.0, max_active=30000):
         _check_code(lib().pk_mi355_decoder_set_beam(self._h, float(beam), int(max_active)))
+
+    def set_trace_gc(self, on=True):
+        """From the next call on: a slice of the backtrace arena per utterance, compacted as it fills."""
+        _check_code(lib().pk_mi355_decoder_set_trace_gc(self._h, 1 if on else 0))
 
     def decode_batch(self, batch, sync=True):
         """Every utterance of a scored BatchScorer, read where it lies in HBM."""
@@ -848,6 +859,13 @@ class Decoder:
 
     def active_bound(self, utt):
         return _check_code(lib().pk_mi355_decoder_active_bound(self._h, int(utt)))
+
+    def trace_stats(self, utt):
+        """(peak records, slice records, compactions) of the last call: per utterance with trace gc on; with it off
+        the records the whole call wrote, trace_capacity and 0."""
+        peak, size, n = C.c_int64(), C.c_int64(), C.c_int()
+        _check_code(lib().pk_mi355_decoder_trace_stats(self._h, int(utt), C.byref(peak), C.byref(size), C.byref(n)))
+        return peak.value, size.value, n.value
 
 
 class OnlineDecoder:

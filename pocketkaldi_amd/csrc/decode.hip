@@ -47,7 +47,8 @@ struct UttResult {
   int path_off;     // arc ids of the best path in the path arena, start to end
   int path_len;
   int active_bound; // largest per-frame count of touched states
-  int pad[2];
+  int peak;         // trace-gc mode: the most records the utterance's slice held (taken before every compaction)
+  int compactions;  // trace-gc mode: how often the slice was compacted
 };
 
 struct DecArgs {
@@ -62,7 +63,8 @@ struct DecArgs {
   int num_utts;
   // per-utterance work areas (stride num_states entries)
   uint64_t *key; int *tr; int *mark; int *touched; int *nxt; Tok *la; Tok *lb; Tok *fa; Tok *fb;
-  // backtrace arena and best-path arena.  DecodeKernel: shared by the call, with their capacities and bump counters;
+  // backtrace arena and best-path arena.  DecodeKernel<false>: shared by the call, with their capacities and bump
+  // counters; DecodeKernel<true>: a slice of rec_cap entries of each per utterance (no counter: the top lives in LDS);
   // OnlineDecodeKernel: rec and path only, a slice per slot (its capacity is a kernel argument, its top the slot's state)
   int2 *rec; int64_t rec_cap; unsigned long long *rec_top;
   int *path; int path_cap; int *path_top;
@@ -201,7 +203,8 @@ __device__ void ForArcs(Shared &sh, const Tok *src, int n, float cut, const int 
   }
 }
 
-// The backtrace arena that trace records go to: the call's shared one (DecodeKernel) or a slot's own (OnlineDecodeKernel).
+// The backtrace arena that trace records go to: the call's shared one (DecodeKernel<false>), an utterance's slice of it
+// (DecodeKernel<true>) or a slot's own (OnlineDecodeKernel).
 struct Arena {
   int2 *rec;                    // (previous record, original arc id)
   int64_t cap;
@@ -281,7 +284,8 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *
 
 // The frame step, shared by the whole-utterance and the online kernel: InitDecoding when the first frame index t is
 // -1, then frames t .. T - 1 of ll (ProcessEmitting, ProcessNonemitting, the next token list).  before(L, nL) runs
-// ahead of every emitting frame: nothing for DecodeKernel, the trace compaction for OnlineDecodeKernel.
+// ahead of every emitting frame: nothing for DecodeKernel<false>, the trace compaction for DecodeKernel<true> and
+// OnlineDecodeKernel.
 template <typename Before>
 __device__ __forceinline__ void DecodeFrames(Shared &sh, float *s_ll, const DecArgs &A, Work &w, const float *ll, int t,
                                              int T, Before before) {
@@ -458,64 +462,6 @@ __device__ __forceinline__ void FillPath(const Arena &R, int trace, int *path, i
   for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) path[--len] = R.rec[x].y;
 }
 
-__global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
-  extern __shared__ float s_ll[];
-  __shared__ Shared sh;
-  const int u = blockIdx.x;
-  if (u >= A.num_utts) return;
-  Work w = WorkOf(A, u, Arena{A.rec, A.rec_cap, A.rec_top});
-  DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [](Tok *, int) {});
-  float weight = 0.f;
-  int bi = -1;
-  if (!w.status && w.ok) bi = BestToken(sh, A, w, true, &weight);
-  if (threadIdx.x == 0) {
-    UttResult r;
-    r.status = w.status; r.ok = (w.status || w.nL == 0) ? 0 : w.ok; r.weight = 0.f;
-    r.path_off = 0; r.path_len = 0; r.active_bound = w.active; r.pad[0] = r.pad[1] = 0;
-    if (!w.status && r.ok && bi >= 0) {
-      r.weight = weight;
-      const int len = PathLen(w.arena, w.L[bi].trace);
-      const int off = atomicAdd(A.path_top, len);      // the call's shared path arena
-      if (off + len > A.path_cap) {                   // (cannot happen: see CreateDecoder)
-        r.status = PK_MI355_E_CAPACITY;
-        r.ok = 0;
-      } else {
-        r.path_off = off; r.path_len = len;
-        FillPath(w.arena, w.L[bi].trace, A.path + off, len);
-      }
-    }
-    A.res[u] = r;
-  }
-}
-
-
-// ================================================================== online decoding (pk_mi355_online_decoder_*)
-// DecodeFrames, resumable: a slot's token list, its count and buffer, ok / status, the largest touched count, the
-// frames decoded and its trace-arena top live in HBM between launches.  One workgroup per slot with new frames;
-// InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot has an arena of its own
-// (A.rec and A.path hold `cap` entries per slot); when it is more than half full before an emitting frame the
-// reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity are all
-// this kernel adds to the frame step: DecodeKernel instantiates it with an empty `before` and never reads them.
-
-struct OnlineState {
-  int nL, par;            // tokens of the current list and which of the slot's two list buffers holds them
-  int ok, status;         // N2 / capacity / closure verdicts: a slot that ended stays ended
-  int active, frames;     // largest touched count; frames decoded
-  int started, pad;
-  unsigned long long top; // records used in the slot's arena
-};
-
-struct OnlineResult {
-  int status, ok, final_, path_len;
-  float weight;           // final: Hypothesis::weight(); partial: the best token's cost
-  int active_bound, frames, has_path;
-};
-
-struct OnlineCall {       // one slot of a launch
-  int slot, T, final_, fresh;
-  int64_t ll_off;
-};
-
 // Mark the records reachable from the list's tokens, renumber them in creation order with an exclusive scan (a
 // record's predecessor is always older, so one forward pass remaps every `prev`), move them down, and rewrite the
 // tokens' trace (and the state table's, which the next emitting step reads).  Changes where records live, never a
@@ -556,6 +502,113 @@ __device__ void CompactTrace(Shared &sh, int2 *rec, int *remap, unsigned long lo
   if (threadIdx.x == 0) *top = (unsigned long long)base;
   __syncthreads();
 }
+
+// kGc = false: the call's shared arena and path arena, their bump counters in HBM; nothing is reclaimed.
+// kGc = true (pk_mi355_decoder_set_trace_gc): utterance u owns entries [u * rec_cap, (u + 1) * rec_cap) of rec and of
+// path, its top lives in LDS, and the slice is compacted when more than half full before an emitting frame, as the
+// online kernel does.  Until the best path is written the utterance's slice of path is the compaction's remap scratch
+// (one int per record); no counter of the call is touched.
+template <bool kGc>
+__global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
+  extern __shared__ float s_ll[];
+  __shared__ Shared sh;
+  __shared__ unsigned long long s_top;                 // kGc only
+  const int u = blockIdx.x;
+  if (u >= A.num_utts) return;
+  Work w;
+  int peak = 0, compactions = 0;
+  if constexpr (kGc) {
+    if (threadIdx.x == 0) s_top = 0;
+    __syncthreads();
+    const int64_t at = (int64_t)u * A.rec_cap;
+    w = WorkOf(A, u, Arena{A.rec + at, A.rec_cap, &s_top});
+    int *remap = A.path + at;
+    DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [&](Tok *L, int nL) {
+      const unsigned long long top = s_top;
+      peak = max(peak, (int)top);
+      if (top > (unsigned long long)(A.rec_cap / 2)) {
+        CompactTrace(sh, w.arena.rec, remap, &s_top, L, nL, w.tr);
+        ++compactions;
+      }
+    });
+    peak = (int)min((unsigned long long)A.rec_cap, max((unsigned long long)peak, s_top));   // (a failed bump overshoots)
+  } else {
+    w = WorkOf(A, u, Arena{A.rec, A.rec_cap, A.rec_top});
+    DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [](Tok *, int) {});
+  }
+  float weight = 0.f;
+  int bi = -1;
+  if (!w.status && w.ok) bi = BestToken(sh, A, w, true, &weight);
+  if (threadIdx.x == 0) {
+    UttResult r;
+    r.status = w.status; r.ok = (w.status || w.nL == 0) ? 0 : w.ok; r.weight = 0.f;
+    r.path_off = 0; r.path_len = 0; r.active_bound = w.active; r.peak = peak; r.compactions = compactions;
+    if (!w.status && r.ok && bi >= 0) {
+      r.weight = weight;
+      const int len = PathLen(w.arena, w.L[bi].trace);
+      if constexpr (kGc) {                             // a chain of the slice's records: it fits the slice of path
+        if (len > A.rec_cap) {                         // (cannot happen: PathLen stops counting at cap + 1)
+          r.status = PK_MI355_E_CAPACITY;
+          r.ok = 0;
+        } else {
+          r.path_off = int((int64_t)u * A.rec_cap); r.path_len = len;
+          FillPath(w.arena, w.L[bi].trace, A.path + r.path_off, len);
+        }
+      } else {
+        const int off = atomicAdd(A.path_top, len);    // the call's shared path arena
+        if (off + len > A.path_cap) {                  // (cannot happen: see CreateDecoder)
+          r.status = PK_MI355_E_CAPACITY;
+          r.ok = 0;
+        } else {
+          r.path_off = off; r.path_len = len;
+          FillPath(w.arena, w.L[bi].trace, A.path + off, len);
+        }
+      }
+    }
+    A.res[u] = r;
+  }
+}
+
+// After DecodeKernel<true> the best paths lie one per slice of the path arena.  Moved together, in utterance order, to
+// the front of `out` (the record arena, dead once every path is written: at most trace_capacity ints of its
+// 2 x trace_capacity), so that the host fetches one prefix as it does with the mode off.  One workgroup per utterance.
+__global__ void __launch_bounds__(256) GatherPathsKernel(UttResult *res, int n, const int *path, int *out) {
+  const int u = blockIdx.x;
+  if (u >= n) return;
+  int off = 0;
+  for (int v = 0; v < u; ++v) off += res[v].path_len;
+  const int from = res[u].path_off, len = res[u].path_len;
+  for (int i = threadIdx.x; i < len; i += blockDim.x) out[off + i] = path[from + i];
+  __syncthreads();
+  if (threadIdx.x == 0) res[u].path_off = off;
+}
+
+// ================================================================== online decoding (pk_mi355_online_decoder_*)
+// DecodeFrames, resumable: a slot's token list, its count and buffer, ok / status, the largest touched count, the
+// frames decoded and its trace-arena top live in HBM between launches.  One workgroup per slot with new frames;
+// InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot has an arena of its own
+// (A.rec and A.path hold `cap` entries per slot); when it is more than half full before an emitting frame the
+// reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity are all
+// this kernel adds to the frame step: DecodeKernel<false> instantiates it with an empty `before` and never reads them.
+
+struct OnlineState {
+  int nL, par;            // tokens of the current list and which of the slot's two list buffers holds them
+  int ok, status;         // N2 / capacity / closure verdicts: a slot that ended stays ended
+  int active, frames;     // largest touched count; frames decoded
+  int started, pad;
+  unsigned long long top; // records used in the slot's arena
+};
+
+struct OnlineResult {
+  int status, ok, final_, path_len;
+  float weight;           // final: Hypothesis::weight(); partial: the best token's cost
+  int active_bound, frames, has_path;
+};
+
+struct OnlineCall {       // one slot of a launch
+  int slot, T, final_, fresh;
+  int64_t ll_off;
+};
 
 __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, const OnlineCall *calls, OnlineState *states,
                                                                     OnlineResult *results, int *remap_all, int64_t cap) {
@@ -621,6 +674,7 @@ struct pk_mi355_decoder {
   float beam = 16.0f;
   int max_active = 30000;
   int64_t trace_cap = 0;
+  bool trace_gc = false;                        // set_trace_gc: how the next call uses the arena
   std::vector<int32_t> olabel;                  // by original arc id
   // device graph
   int *e_off = nullptr, *e_src = nullptr, *n_off = nullptr, *n_src = nullptr;
@@ -646,6 +700,8 @@ struct pk_mi355_decoder {
   // results of the last call
   bool pending = false, have = false;
   int num_utts = 0;
+  bool call_gc = false;                         // the last call: trace-gc mode, its slice (records per utterance),
+  int64_t call_slice = 0, call_records = 0;     // and with the mode off the records it used in all
   std::vector<UttResult> res;
   std::vector<int32_t> h_path;
   std::vector<int> h_T;
@@ -863,16 +919,25 @@ int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off
   d->h_T = T;
   d->h_off = off;
   d->stream = stream;
+  d->call_gc = d->trace_gc;
+  d->call_slice = d->call_gc ? d->trace_cap / std::max(n, 1) : d->trace_cap;
+  d->call_records = 0;
   if (n > 0) {
     HIP_TRY(hipMemcpyAsync(d->d_off, d->h_off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d->d_T, d->h_T.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * 2, stream));
     DecArgs A = ArgsOf(d, ll, n);
     A.ll_off = d->d_off; A.T = d->d_T;
-    A.rec_cap = d->trace_cap; A.rec_top = d->counters;       // one arena and one path arena shared by the call
-    A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
     A.res = d->d_res;
-    hipLaunchKernelGGL(DecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
+    if (d->call_gc) {                                          // a slice of the arena and of the path arena per utterance
+      A.rec_cap = d->call_slice;
+      hipLaunchKernelGGL(DecodeKernel<true>, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
+      hipLaunchKernelGGL(GatherPathsKernel, dim3(n), dim3(256), 0, stream, d->d_res, n, d->path, reinterpret_cast<int *>(d->rec));
+    } else {
+      A.rec_cap = d->trace_cap; A.rec_top = d->counters;       // one arena and one path arena shared by the call
+      A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
+      hipLaunchKernelGGL(DecodeKernel<false>, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
   }
@@ -897,10 +962,22 @@ int Collect(pk_mi355_decoder *d) {
   if (n) HIP_TRY(hipMemcpy(d->res.data(), d->d_res, sizeof(UttResult) * n, hipMemcpyDeviceToHost));
   int used = 0;
   for (const auto &r : d->res) used = std::max(used, r.path_off + r.path_len);
+  if ((int64_t)used > d->trace_cap) return Fail(PK_MI355_E_DEVICE, "decoder: corrupt result");
   d->h_path.resize(used);
-  if (used) HIP_TRY(hipMemcpy(d->h_path.data(), d->path, sizeof(int) * used, hipMemcpyDeviceToHost));
+  // (with trace gc on GatherPathsKernel has moved the paths to the front of the record arena)
+  const int *paths = d->call_gc ? reinterpret_cast<const int *>(d->rec) : d->path;
+  if (used) HIP_TRY(hipMemcpy(d->h_path.data(), paths, sizeof(int) * used, hipMemcpyDeviceToHost));
+  if (!d->call_gc) {
+    unsigned long long records = 0;
+    if (n) HIP_TRY(hipMemcpy(&records, d->counters, sizeof(records), hipMemcpyDeviceToHost));
+    d->call_records = (int64_t)std::min(records, (unsigned long long)d->trace_cap);   // (a failed bump overshoots)
+  }
   for (int u = 0; u < n; ++u) {
     const UttResult &r = d->res[u];
+    if (r.status == PK_MI355_E_CAPACITY && d->call_gc)
+      return Fail(PK_MI355_E_CAPACITY, "decoder: utterance %d: backtrace storage exhausted after compaction (a slice of %lld "
+                  "records: trace_capacity %lld over the call's %d utterances; raise it, or decode fewer utterances per call)",
+                  u, (long long)d->call_slice, (long long)d->trace_cap, n);
     if (r.status == PK_MI355_E_CAPACITY)
       return Fail(PK_MI355_E_CAPACITY, "decoder: utterance %d: backtrace storage exhausted (trace_capacity %lld: raise it, "
                   "or decode fewer utterances per call)", u, (long long)d->trace_cap);
@@ -967,6 +1044,12 @@ int pk_mi355_decoder_set_beam(pk_mi355_decoder_t *d, float beam, int max_active)
   if (!(beam >= 0.0f) || max_active <= 0) return Fail(PK_MI355_E_INVALID, "beam must be >= 0 and max_active > 0");
   d->beam = beam;
   d->max_active = max_active;
+  return 0;
+}
+
+int pk_mi355_decoder_set_trace_gc(pk_mi355_decoder_t *d, int enable) {
+  if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
+  d->trace_gc = enable != 0;
   return 0;
 }
 
@@ -1047,6 +1130,17 @@ int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt) {
   int rc = CheckResult(d, utt);
   if (rc) return rc;
   return d->res[utt].active_bound;
+}
+
+int pk_mi355_decoder_trace_stats(const pk_mi355_decoder_t *d, int utt, int64_t *peak_records, int64_t *slice_records,
+                                 int *compactions) {
+  int rc = CheckResult(d, utt);
+  if (rc) return rc;
+  const UttResult &r = d->res[utt];
+  if (peak_records) *peak_records = d->call_gc ? (int64_t)r.peak : d->call_records;
+  if (slice_records) *slice_records = d->call_slice;
+  if (compactions) *compactions = d->call_gc ? r.compactions : 0;
+  return 0;
 }
 
 }  // extern "C"
