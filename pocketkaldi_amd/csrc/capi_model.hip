@@ -1,16 +1,12 @@
-// capi_model.hip -- errors and device selection, model construction (arrays -> the packed device blob),
+// capi_model.hip -- device selection, model construction (arrays -> the packed device blob),
 // accessors, and the operand exponents of the f16 modes.  Host C++ over the HIP runtime; no CPU compute path.
 #include <hip/hip_runtime.h>
-#include <ctype.h>
-#include <dlfcn.h>
 #include <math.h>
 #include <cmath>
 
 #include <algorithm>
-#include <string>
 #include <mutex>
 #include <utility>
-#include <unordered_set>
 #include <vector>
 
 #include "pk_host.h"
@@ -18,25 +14,14 @@
 using namespace pkmi;
 using namespace pkhost;
 
-// ------------------------------------------------------------------ errors
+// ------------------------------------------------------------------ device selection
 
 namespace {
-thread_local char g_err[512] = "";
-thread_local int g_err_code = 0;
 thread_local int g_device = 0;
 }  // namespace
 
 namespace pkhost {
 
-int Fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  g_err_code = code;
-  return code;
-}
-const char *LastError() { return g_err; }
 int CurrentDevice() { return g_device; }
 
 int UseDevice(int device) {
@@ -74,8 +59,6 @@ int UploadExps(pk_mi355_am *am) {
 
 extern "C" {
 
-const char *pk_mi355_last_error(void) { return g_err; }
-int pk_mi355_last_error_code(void) { return g_err_code; }
 const char *pk_mi355_version(void) { return "pk_mi355 0.1 (gfx950)"; }
 
 int pk_mi355_device_count(void) {

@@ -1,7 +1,7 @@
 // decode.hip -- the search half of pk_process (Decoder::Decode + BestPath, decoder.cc:39-339) on the GPU,
 // batched: one workgroup per utterance decodes the whole utterance in ONE launch, frame after frame,
-// synchronising only with __syncthreads() (no workgroup waits on another).  Plus the host-only reader of
-// the reference's graph format (Fst::Read / CountArcs, fst.cc:29-110).
+// synchronising only with __syncthreads() (no workgroup waits on another).  The graph's reader and its split into
+// the arc lists below are host-only: pk_files.cc.
 //
 // Semantics (DESIGN.md "Decoder"): the reference's float / double arithmetic operation for operation;
 // order-independent where the reference depends on iteration order:
@@ -658,15 +658,6 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
 
 // ================================================================== host objects
 
-struct pk_mi355_fst {
-  int num_states = 0, num_arcs = 0, start = 0;
-  std::vector<float> final_w;
-  std::vector<int32_t> first;
-  std::vector<int32_t> arc_first, arc_count;    // Fst::CountArcs per state
-  struct Arc { int32_t next, ilabel, olabel; float weight; };
-  std::vector<Arc> arcs;
-};
-
 struct pk_mi355_decoder {
   int device = 0;
   const pk_mi355_am *am = nullptr;              // the model the graph's ilabels were checked against
@@ -710,56 +701,6 @@ struct pk_mi355_decoder {
 
 namespace {
 
-int ReadFst(const char *path, pk_mi355_fst *f) {
-  FileBuf fb;
-  int rc = fb.Open(path);
-  if (rc) return rc;
-  const std::vector<unsigned char> &d = fb.d;
-  if (d.size() < 48) return Fail(PK_MI355_E_IO, "%s: malformed graph: truncated header", path);
-  char name[32];
-  memcpy(name, d.data(), 32);
-  name[31] = '\0';
-  if (strcmp(name, "pk::fst_0") != 0) return Fail(PK_MI355_E_IO, "%s: malformed graph: section name 'pk::fst_0' expected", path);
-  int32_t size, ns, na, start;
-  memcpy(&size, &d[32], 4); memcpy(&ns, &d[36], 4); memcpy(&na, &d[40], 4); memcpy(&start, &d[44], 4);
-  if (ns < 0 || na < 0) return Fail(PK_MI355_E_IO, "%s: malformed graph: negative state or arc count", path);
-  const int64_t expect = 12 + (int64_t)ns * 8 + (int64_t)na * 16;
-  if (expect != size) return Fail(PK_MI355_E_IO, "%s: malformed graph: section size %d, %lld expected", path, size, (long long)expect);
-  if ((int64_t)d.size() < 36 + expect) return Fail(PK_MI355_E_IO, "%s: malformed graph: truncated (%zu bytes, %lld expected)", path,
-                                                   d.size(), (long long)(36 + expect));
-  if (start < 0 || start >= ns) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: start state %d out of range", path, start);
-  f->num_states = ns; f->num_arcs = na; f->start = start;
-  f->final_w.resize(ns); f->first.resize(ns); f->arcs.resize(na);
-  if (ns) {
-    memcpy(f->final_w.data(), &d[48], (size_t)ns * 4);
-    memcpy(f->first.data(), &d[48 + (size_t)ns * 4], (size_t)ns * 4);
-  }
-  if (na) memcpy(f->arcs.data(), &d[48 + (size_t)ns * 8], (size_t)na * 16);
-  // Fst::CountArcs (fst.cc:94-110): a state's arcs end at the `first` of the next state whose first is > 0
-  f->arc_first.assign(ns, 0); f->arc_count.assign(ns, 0);
-  int32_t next_idx = na;
-  for (int s = ns - 1; s >= 0; --s) {
-    const int32_t fs = f->first[s];
-    if (fs >= 0) {
-      if (fs > na || next_idx < fs)
-        return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc range [%d, %d) of state %d outside the arc array", path, fs, next_idx, s);
-      f->arc_first[s] = fs;
-      f->arc_count[s] = next_idx - fs;
-    }
-    if (fs > 0) next_idx = fs;
-  }
-  for (int s = 0; s < ns; ++s)
-    if (std::isnan(f->final_w[s]))
-      return Fail(PK_MI355_E_INVALID, "%s: invalid graph: final weight of state %d is NaN", path, s);
-  for (int a = 0; a < na; ++a) {
-    const auto &arc = f->arcs[a];
-    if (!std::isfinite(arc.weight)) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: weight is not finite", path, a);
-    if (arc.next < 0 || arc.next >= ns) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: next state %d out of range", path, a, arc.next);
-    if (arc.ilabel < 0 || arc.olabel < 0) return Fail(PK_MI355_E_INVALID, "%s: invalid graph: arc %d: negative label", path, a);
-  }
-  return 0;
-}
-
 void FreeDecoderDevice(pk_mi355_decoder *d) {
   void *ptrs[] = {d->e_off, d->e_src, d->n_off, d->n_src, d->e_arc, d->n_arc, d->final_w, d->key, d->tr, d->mark,
                   d->touched, d->nxt, d->lists, d->rec, d->counters, d->path, d->d_res, d->d_ll, d->d_off, d->d_T};
@@ -780,50 +721,26 @@ int CreateDecoder(pk_mi355_decoder *d, const pk_mi355_fst *f, const pk_mi355_am 
   const int S = f->num_states;
   const int N = am->num_pdfs;
   if (N <= 0 || N > kMaxDecPdfs) return Fail(PK_MI355_E_INVALID, "decoder: num_pdfs %d outside [1, %d]", N, kMaxDecPdfs);
-  // split the graph; ilabels are mapped to pdfs here (tid2pdf, or identity without one) and checked
-  std::vector<int> e_off(S + 1, 0), n_off(S + 1, 0), e_src, n_src;
-  std::vector<int4> e_arc, n_arc;
-  for (int s = 0; s < S; ++s) {
-    for (int i = 0; i < f->arc_count[s]; ++i) {
-      const int a = f->arc_first[s] + i;
-      const auto &arc = f->arcs[a];
-      int4 v;
-      v.x = arc.next; v.z = 0; v.w = a;
-      memcpy(&v.z, &arc.weight, 4);
-      if (arc.ilabel == 0) {
-        v.y = 0;
-        n_arc.push_back(v); n_src.push_back(s);
-      } else {
-        int pdf;
-        if (am->tid2pdf.empty()) {
-          pdf = arc.ilabel;
-        } else {
-          if (arc.ilabel >= (int)am->tid2pdf.size())
-            return Fail(PK_MI355_E_INVALID, "decoder: arc %d: transition id %d outside the model's tid2pdf (%zu entries)",
-                        a, arc.ilabel, am->tid2pdf.size());
-          pdf = am->tid2pdf[arc.ilabel];
-        }
-        if (pdf < 0 || pdf >= N)
-          return Fail(PK_MI355_E_INVALID, "decoder: arc %d: transition id %d maps to pdf %d, the model has %d", a, arc.ilabel, pdf, N);
-        v.y = pdf;
-        e_arc.push_back(v); e_src.push_back(s);
-      }
-      if (e_arc.size() >= (size_t)kEpsBit - 1 || n_arc.size() >= (size_t)kEpsBit - 1)
-        return Fail(PK_MI355_E_INVALID, "decoder: too many arcs");
-    }
-    e_off[s + 1] = (int)e_arc.size();
-    n_off[s + 1] = (int)n_arc.size();
-  }
+  GraphSplit g;
+  int rc = SplitGraph(*f, am->tid2pdf, N, &g);
+  if (rc) return rc;
   d->max_utts = max_utts; d->num_states = S; d->start = f->start; d->num_pdfs = N;
   d->trace_cap = trace_capacity > 0 ? trace_capacity : kDefaultTrace;
   if (d->trace_cap > (int64_t)INT32_MAX) return Fail(PK_MI355_E_INVALID, "decoder: trace_capacity above 2^31 - 1");
-  d->olabel.resize(f->num_arcs);
-  for (int a = 0; a < f->num_arcs; ++a) d->olabel[a] = f->arcs[a].olabel;
-  int rc;
-  if ((rc = Upload(&d->e_off, e_off)) || (rc = Upload(&d->n_off, n_off)) || (rc = Upload(&d->e_src, e_src)) ||
-      (rc = Upload(&d->n_src, n_src)) || (rc = Upload(&d->e_arc, e_arc)) || (rc = Upload(&d->n_arc, n_arc)) ||
-      (rc = Upload(&d->final_w, f->final_w)))
+  // a SplitArc is uploaded as the int4 the kernels read: x = next state, y = pdf, z = weight bits, w = original arc id
+  static_assert(sizeof(SplitArc) == sizeof(int4) && offsetof(SplitArc, next) == offsetof(int4, x) &&
+                offsetof(SplitArc, pdf) == offsetof(int4, y) && offsetof(SplitArc, weight_bits) == offsetof(int4, z) &&
+                offsetof(SplitArc, arc) == offsetof(int4, w), "SplitArc is laid out as int4");
+  static_assert(kMaxSplitArcs == kEpsBit - 1, "candidate ids: an arc's index, the top bit for epsilon arcs");
+  SplitArc *e_arc = nullptr, *n_arc = nullptr;
+  rc = Upload(&e_arc, g.e_arc);
+  d->e_arc = reinterpret_cast<int4 *>(e_arc);
+  if (!rc) rc = Upload(&n_arc, g.n_arc);
+  d->n_arc = reinterpret_cast<int4 *>(n_arc);
+  if (rc || (rc = Upload(&d->e_off, g.e_off)) || (rc = Upload(&d->n_off, g.n_off)) || (rc = Upload(&d->e_src, g.e_src)) ||
+      (rc = Upload(&d->n_src, g.n_src)) || (rc = Upload(&d->final_w, f->final_w)))
     return rc;
+  d->olabel = std::move(g.olabel);
   const size_t per = (size_t)S * max_utts;
   HIP_TRY(hipMalloc(&d->key, sizeof(uint64_t) * per));
   HIP_TRY(hipMemset(d->key, 0xFF, sizeof(uint64_t) * per));
@@ -894,20 +811,6 @@ int UploadLoglik(pk_mi355_decoder *d, const pk_decodable_t *src, int n) {
     at += count;
   }
   return 0;
-}
-
-// The words of a path: its arcs' non-zero olabels, in path order.  Returns their number; writes at most max_words.
-int PathWords(const pk_mi355_decoder *d, const int32_t *arcs, int num_arcs, int *words, int max_words) {
-  int n = 0;
-  for (int i = 0; i < num_arcs; ++i) {
-    const int arc = arcs[i];
-    const int w = (arc >= 0 && arc < (int)d->olabel.size()) ? d->olabel[arc] : 0;
-    if (w != 0) {
-      if (words && n < max_words) words[n] = w;
-      ++n;
-    }
-  }
-  return n;
 }
 
 // Queue one decode of num_utts utterances whose log-likelihoods lie at ll + off[u] (T[u] frames each) on `stream`.
@@ -993,25 +896,6 @@ int Collect(pk_mi355_decoder *d) {
 }  // namespace
 
 extern "C" {
-
-pk_mi355_fst_t *pk_mi355_fst_read(const char *path) {
-  if (!path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
-  pk_mi355_fst *f = new pk_mi355_fst();
-  if (ReadFst(path, f)) { delete f; return nullptr; }
-  return f;
-}
-
-void pk_mi355_fst_destroy(pk_mi355_fst_t *fst) { delete fst; }
-int pk_mi355_fst_num_states(const pk_mi355_fst_t *fst) { return fst ? fst->num_states : Fail(PK_MI355_E_INVALID, "null graph"); }
-int pk_mi355_fst_num_arcs(const pk_mi355_fst_t *fst) { return fst ? fst->num_arcs : Fail(PK_MI355_E_INVALID, "null graph"); }
-int pk_mi355_fst_start(const pk_mi355_fst_t *fst) { return fst ? fst->start : Fail(PK_MI355_E_INVALID, "null graph"); }
-
-int pk_mi355_fst_arc_range(const pk_mi355_fst_t *fst, int state, int *first, int *count) {
-  if (!fst || state < 0 || state >= fst->num_states) return Fail(PK_MI355_E_INVALID, "bad graph state");
-  if (first) *first = fst->arc_first[state];
-  if (count) *count = fst->arc_count[state];
-  return 0;
-}
 
 pk_mi355_decoder_t *pk_mi355_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am, int max_utts,
                                             int64_t trace_capacity) {
@@ -1115,7 +999,7 @@ int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, in
   const UttResult &r = d->res[utt];
   if (weight) *weight = r.weight;
   if (ok) *ok = r.ok;
-  return PathWords(d, d->h_path.data() + r.path_off, r.path_len, words, max_words);
+  return PathWords(d->olabel, d->h_path.data() + r.path_off, r.path_len, words, max_words);
 }
 
 int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs) {
@@ -1217,7 +1101,7 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
 }
 
 int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
-  return PathWords(&o->dec, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
+  return PathWords(o->dec.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
 }
 
 int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {

@@ -1,8 +1,10 @@
 // pk_host.h -- what the host-side translation units of libpk_mi355.so share (internal):
-//   capi_model.hip       errors / device selection, model construction, operand exponents
+//   pk_files.cc          (plain C++, pk_files.h) the error state and every file reader: model / config / WAV / graph,
+//                        the graph's split into the decoder's arc lists
+//   capi_model.hip       device selection, model construction, operand exponents
 //   capi_exec.hip        the layer executor, the single-utterance workspace, pk_decodable_*
 //   capi_batch.hip       the batched device-resident scorer, result arenas and views
-//   capi_io.hip          model / config / WAV files, the single-utterance front-end entries, test hooks
+//   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
 // Nothing here is part of the ABI (include/pk_mi355.h is); the library exports the C entries only
 // (libpk_mi355.map).
@@ -10,7 +12,6 @@
 #define PK_HOST_H_
 
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pk_mi355.h"
+#include "pk_files.h"
 #include "pk_kernels.h"
 #include "pk_tables.h"
 
@@ -28,11 +29,8 @@ namespace pkhost {
 
 using namespace pkmi;
 
-// ------------------------------------------------------------------ errors, device selection (capi_model.hip)
+// ------------------------------------------------------------------ device selection (capi_model.hip; errors: pk_files.h)
 
-// formats the thread's error text (pk_mi355_last_error) and returns `code`
-int Fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-const char *LastError();
 // Like hipSetDevice, the selected device is a per-thread setting (a worker thread that never
 // called pk_mi355_set_device creates its objects on device 0).
 int CurrentDevice();
@@ -101,61 +99,7 @@ struct Scoped {
   ~Scoped() { if (t) t->End(id, s); }
 };
 
-// ------------------------------------------------------------------ section files
-// "VEC0" i32 bytes(=4n+4) i32 n, n x 4 bytes (vector.cc:393-425);
-// "MAT0" i32 8, i32 rows, i32 cols, rows x VEC0 (matrix.cc:288-319);
-// "NNT0" i32 4, i32 layers; "LAY0" i32 4, i32 type [+ MAT0 W, VEC0 b] (nnet.cc:80-147)
-
-struct FileBuf {
-  std::vector<unsigned char> d;
-  size_t pos = 0;
-  std::string path;
-  int Open(const char *p) {
-    path = p;
-    FILE *f = fopen(p, "rb");
-    if (!f) return Fail(PK_MI355_E_IO, "cannot open %s", p);
-    fseek(f, 0, SEEK_END);
-    long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    d.resize(n > 0 ? n : 0);
-    size_t got = n > 0 ? fread(d.data(), 1, n, f) : 0;
-    fclose(f);
-    if ((long)got != n) return Fail(PK_MI355_E_IO, "short read on %s", p);
-    return 0;
-  }
-  bool Tag(const char *t) {
-    if (pos + 4 > d.size() || memcmp(&d[pos], t, 4) != 0) return false;
-    pos += 4;
-    return true;
-  }
-  bool I32(int32_t *v) {
-    if (pos + 4 > d.size()) return false;
-    memcpy(v, &d[pos], 4);
-    pos += 4;
-    return true;
-  }
-  template <typename T>
-  int Vec(std::vector<T> *out) {
-    int32_t bytes, n;
-    if (!Tag("VEC0") || !I32(&bytes) || !I32(&n))
-      return Fail(PK_MI355_E_IO, "VEC0 section expected in %s", path.c_str());
-    if (n < 0 || bytes != n * 4 + 4 || pos + (size_t)n * 4 > d.size())
-      return Fail(PK_MI355_E_IO, "corrupted VEC0 section in %s", path.c_str());
-    out->resize(n);
-    if (n) memcpy(out->data(), &d[pos], (size_t)n * 4);
-    pos += (size_t)n * 4;
-    return 0;
-  }
-};
-
 // ------------------------------------------------------------------ model
-
-struct HostLayer {
-  int type = 0;
-  int in_dim = 0, out_dim = 0;
-  std::vector<float> W;   // [out][in]
-  std::vector<float> b;
-};
 
 struct DevLinear {
   int K = 0, N = 0, Kpad = 0, Npad = 0;

@@ -175,6 +175,7 @@ def test_readers_survive_mutated_files(tmp_path):
     (No GPU here: a model that parses stops at PK_MI355_E_DEVICE when it would be uploaded.)"""
     import ctypes as C
     import random
+    import struct
     L = pk.lib()
     D = os.path.join(GOLDEN, "refmodel")
     names = ["refmodel.nnet", "refmodel.prior", "refmodel_tid2pdf.bin", "refmodel_cmvn.bin"]
@@ -211,6 +212,40 @@ def test_readers_survive_mutated_files(tmp_path):
         if rc == 0:
             L.pk_mi355_am_destroy(h)
     assert codes <= {0, -1, -2, -3} and -3 in codes
+
+    # What the random mutations miss: headers that size an allocation no file could back (a 40-byte .nnet whose MAT0 states
+    # 2^30 x 2^30 or 2^20 x 2^20, or 2^30 x (2^31 - 1) either way round, whose byte count leaves 64 bits; a VEC0 of 2^30
+    # entries).  Through the real pk_mi355_load, in a child process: an abort
+    # fails this test instead of ending pytest.
+    import subprocess
+    import sys
+
+    def mat0(rows, cols):
+        return b"NNT0" + struct.pack("<ii", 4, 1) + b"LAY0" + struct.pack("<ii", 4, 0) + b"MAT0" + struct.pack("<iii", 8, rows, cols)
+
+    fixed = {"mat0_2p30": ("refmodel.nnet", mat0(1 << 30, 1 << 30)), "mat0_2p20": ("refmodel.nnet", mat0(1 << 20, 1 << 20)),
+             "mat0_rows_max": ("refmodel.nnet", mat0(2**31 - 1, 1 << 30)), "mat0_cols_max": ("refmodel.nnet", mat0(1 << 30, 2**31 - 1)),
+             "vec0_2p30": ("refmodel.prior", b"VEC0" + struct.pack("<ii", 4, 1 << 30) + bytes(64))}
+    for case, (victim, data) in fixed.items():
+        d = tmp_path / case
+        d.mkdir()
+        for n in names:
+            (d / n).write_bytes(data if n == victim else orig[n])
+        (d / "m.conf").write_text(conf)
+    child = ("import ctypes as C, sys\n"
+             "L = C.CDLL(sys.argv[1])\n"
+             "L.pk_mi355_last_error.restype = C.c_char_p\n"
+             "for conf in sys.argv[2:]:\n"
+             "    h, stats = C.c_void_p(), (C.c_float * 41)()\n"
+             "    rc = L.pk_mi355_load(conf.encode(), 0, C.byref(h), stats)\n"
+             "    print(rc, L.pk_mi355_last_error().decode())\n")
+    run = subprocess.run([sys.executable, "-c", child, pk.lib_path()] + [str(tmp_path / case / "m.conf") for case in fixed],
+                         capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = run.stdout.splitlines()
+    assert len(lines) == len(fixed)
+    for (case, (victim, _)), line in zip(fixed.items(), lines):
+        assert line.startswith("-3 ") and str(tmp_path / case / victim) in line, (case, line)
 
     wav = open(os.path.join(GOLDEN, "en-us-hello.wav"), "rb").read()
     libc = C.CDLL(None)
