@@ -3,29 +3,14 @@ float16 with subnormals, to pin down WHY the round-4 power-of-two prescale is ne
   * unscaled, the error grows as the weights shrink (the lo halves fall into fp16 subnormals, then vanish);
   * prescaled so that max |W| is in [2^13, 2^14) -- what pk_mi355_am_finalize does (capi_model.hip) -- the error is
     the same at every scale, and the scaling itself changes no bit of the exact product.
-No GPU, no product code: this is the arithmetic the GPU tests in test_gpu_f16_range.py then hold the kernels to.
+No GPU, no product code.  The arithmetic itself lives in tests/f16_model.py; test_gpu_f16_exact.py holds the kernels
+to it bit for bit on exactly representable inputs (test_f16_exact_cases.py checks those constructions on the CPU), and
+test_gpu_f16_range.py bounds the rounding error on real-valued data.
 """
 import numpy as np
 import pytest
 
-
-def split(x):
-    x = np.clip(x.astype(np.float32), -65504.0, 65504.0)
-    hi = x.astype(np.float16)
-    lo = (x - hi.astype(np.float32)).astype(np.float16)
-    return hi.astype(np.float64), lo.astype(np.float64)
-
-
-def f16x3_matmul(X, W):
-    xh, xl = split(X)
-    wh, wl = split(W)
-    return xh @ wh.T + xh @ wl.T + xl @ wh.T           # fp64 sums: isolates the operand error from the accumulation order
-
-
-def finalize_exponent(W):
-    """capi_model.hip, pk_mi355_am_finalize: 13 - ilogb(max |W|), clamped to +-60."""
-    m = np.abs(W).max()
-    return 0 if m == 0 else int(np.clip(13 - int(np.floor(np.log2(m))), -60, 60))
+from f16_model import split, f16x3_matmul, finalize_exponent  # noqa: F401
 
 
 @pytest.mark.parametrize("log2_scale", [-16, -12, -8, -4, 0, 4])
