@@ -410,7 +410,8 @@ int pk_mi355_fst_arc_range(const pk_mi355_fst_t *fst, int state, int *first, int
  * model's tid2pdf (identity without one) to a pdf < num_pdfs, otherwise PK_MI355_E_INVALID.
  * max_utts: utterances per call.  trace_capacity: tokens of backtrace storage (8 bytes each)
  * shared by the utterances of one call; 0 = 2^27.  Device memory: 68 bytes x states x max_utts
- * + 12 x trace_capacity + the graph (DESIGN.md "Decoder").  The decoder is bound to am: it
+ * + 12 x trace_capacity + the graph (DESIGN.md "Decoder"; pk_mi355_decoder_set_alignment adds 4 bytes x arcs
+ * + 8 bytes x frames of a call from its first enable on).  The decoder is bound to am: it
  * decodes batches scored with that model only.  A decoder belongs to one host thread at a
  * time, like a batch.  Arc weights must be finite and final weights not NaN (the reader
  * rejects others with PK_MI355_E_INVALID).                                                    */
@@ -557,6 +558,90 @@ int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *d, int slot,
 /* Test hooks, as pk_mi355_decoder_best_path_arcs / _active_bound (the arcs of the partial path while live).  */
 int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *d, int slot, int32_t *arcs, int max_arcs);
 int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *d, int slot);
+
+/* ------------------------------------------------------------------------- */
+/* Best-path alignment and word segments ("Alignment")       */
+/* ------------------------------------------------------------------------- */
+
+/* Off (0) by default; like set_trace_gc it takes effect at the next decode / decode_batch.  On: one more launch
+ * follows the decode on the same stream and, for every utterance with ok = 1 and a best path, writes per FRAME t
+ * the original arc id of the t-th emitting arc of the path (ilabel != 0) and its acoustic cost
+ * -N1(log_prob[t][pdf of that arc]) (N1: a NaN log-likelihood counts as -inf, so the cost is +inf), reading the
+ * log-likelihoods where they lie in HBM.  Words, weight, ok and best-path arcs are those of the mode off, bit for
+ * bit.  Device memory the mode adds: 4 bytes x arcs of the graph (allocated and uploaded at the first enable, not
+ * at create) + 8 bytes x frames of the largest call + 16 bytes x max_utts.                                        */
+int pk_mi355_decoder_set_alignment(pk_mi355_decoder_t *d, int enable);
+/* The alignment of utt in the last call: per frame the arc id, its transition-id (the arc's ilabel) and its
+ * acoustic cost (any pointer may be NULL; at most max_frames entries written).  Returns the frames aligned: the
+ * utterance's frame count, or 0 for an utterance that ended with ok = 0 or has no best path.  PK_MI355_E_STATE
+ * when the call ran with alignment off.                                                                          */
+int pk_mi355_decoder_alignment(const pk_mi355_decoder_t *d, int utt, int32_t *arc_ids, int32_t *trans_ids,
+                               float *acoustic_cost, int max_frames);
+/* One segment of the best path per word.  A segment begins at every arc whose olabel is not 0 (epsilon arcs
+ * included) and runs up to the next such arc, exclusive; the arcs before the first one form a leading segment with
+ * word = 0 (a path without any olabel is one such segment, an empty path gives none).  start_frame: emitting arcs
+ * of the path before the segment's first arc; num_frames: emitting arcs inside it (may be 0); graph_cost: (float)
+ * of the sum in double, in path order, of the segment's arc weights; acoustic_cost: the same over its frames'
+ * acoustic costs.  The final weight belongs to no segment.                                                       */
+typedef struct pk_mi355_word_t {
+  int32_t word;
+  int32_t start_frame;
+  int32_t num_frames;
+  float graph_cost;
+  float acoustic_cost;
+} pk_mi355_word_t;
+/* Segments of utt in the last call (at most max written, the count returned).  PK_MI355_E_STATE when the call ran
+ * with alignment off.                                                                                            */
+int pk_mi355_decoder_word_segments(const pk_mi355_decoder_t *d, int utt, pk_mi355_word_t *out, int max);
+/* Segments of the slot's current path: the partial hypothesis while the slot is live, the final one after its
+ * last advance.  acoustic_cost is NaN in every segment: the online scorer's rows are void after each step, so no
+ * log-likelihood of the path's frames is left to read.                                                           */
+int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *d, int slot, pk_mi355_word_t *out, int max);
+
+/* ------------------------------------------------------------------------- */
+/* Symbol table -- pk_symboltable_read / _get (symbol_table.cc:23-79)              */
+/* ------------------------------------------------------------------------- */
+
+/* "SYM0", i32 section size, i32 size, i32 buffer_size, size x i32 offsets, buffer_size bytes of NUL-terminated
+ * strings.  Host only, needs no GPU.  NULL on failure: PK_MI355_E_IO for a malformed or truncated file (tag,
+ * section size != 8 + 4 size + buffer_size, negative counts, fewer bytes than stated, a non-empty buffer that does
+ * not end in NUL), PK_MI355_E_INVALID for an offset outside [0, buffer_size).                                     */
+typedef struct pk_mi355_symtab pk_mi355_symtab_t;
+pk_mi355_symtab_t *pk_mi355_symtab_read(const char *path);
+void pk_mi355_symtab_destroy(pk_mi355_symtab_t *st);
+int pk_mi355_symtab_size(const pk_mi355_symtab_t *st);
+/* The string of symbol id; NULL (PK_MI355_E_INVALID) outside [0, size) -- the reference asserts there.  The pointer
+ * is valid until the table is destroyed.                                                                         */
+const char *pk_mi355_symtab_get(const pk_mi355_symtab_t *st, int id);
+
+/* ------------------------------------------------------------------------- */
+/* Recognizer -- pk_load + pk_process (pocketkaldi.cc:72-248): model file and waves to text */
+/* ------------------------------------------------------------------------- */
+
+/* pk_load: reads the model file's fst, cmvn_stats, AcousticModel keys (through pk_mi355_load) and symbol_table,
+ * and owns a batch scorer (max_utts, max_total_samples: as pk_mi355_batch_create) and a decoder with alignment on
+ * (trace_capacity: as pk_mi355_decoder_create).  A missing key is reported in the reference's words ("Unable to
+ * find key 'fst' in ..."); every olabel of the graph must be < the symbol table's size, else PK_MI355_E_INVALID
+ * (the reference asserts this at lookup).  The keys and the host-side files are checked before the device is
+ * touched.  NULL on failure.                                                                                     */
+typedef struct pk_mi355_recognizer pk_mi355_recognizer_t;
+pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int precision, int max_utts,
+                                                int64_t max_total_samples, int64_t trace_capacity);
+void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r);
+/* The owned objects: beam, trace gc, softmax mode, f16 calibration and every result getter (words, weight, ok,
+ * alignment, word segments) are their existing entries.                                                          */
+pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r);
+pk_mi355_batch_t *pk_mi355_recognizer_batch(pk_mi355_recognizer_t *r);
+pk_mi355_decoder_t *pk_mi355_recognizer_decoder(pk_mi355_recognizer_t *r);
+const pk_mi355_symtab_t *pk_mi355_recognizer_symtab(const pk_mi355_recognizer_t *r);
+/* pk_process for n waves at once: set_waves, score (prob_scale 0.1), decode_batch, synchronize.                   */
+int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *waves, int n);
+/* utt->hyp of the last process: the words' strings in spoken order joined by one space, no trailing space; "" for
+ * an utterance without words (also one the decoder ended with ok = 0).  Valid until the next process.  NULL on
+ * misuse.                                                                                                        */
+const char *pk_mi355_recognizer_hyp(const pk_mi355_recognizer_t *r, int utt);
+/* utt->loglikelihood_per_frame: weight / num_frames in float; 0.0f for an utterance without words (NaN on misuse). */
+float pk_mi355_recognizer_loglikelihood_per_frame(const pk_mi355_recognizer_t *r, int utt);
 
 /* Library / device facts */
 int pk_mi355_device_count(void);

@@ -11,6 +11,9 @@
 //   pk_decodable_init/_destroy/_loglikelihood/_islastframe               src/decodable.h:20-41
 //   pocketkaldi::Fst::Read / CountArcs                                   src/fst.h
 //   pocketkaldi::Decoder(fst, am).Decode(pk_decodable_t*) / BestPath()   src/decoder.h (on the GPU)
+//   pocketkaldi::Decoder::SetAlignment / Alignment / WordSegments        per-frame arcs and costs, word times
+//   pocketkaldi::SymbolTable::Read / size / Get                          src/symbol_table.h
+//   pocketkaldi::Recognizer::Load / Process                              pk_load + pk_process, src/pocketkaldi.cc:72-248
 //   pocketkaldi::OnlineScorer(am, stats, ...).Push / Step / Fetch        live PCM, frames scored as they become final
 //   pocketkaldi::OnlineDecoder(fst, am, ...).Advance / Partial / Result  the search over them, partial text while live
 //
@@ -233,11 +236,97 @@ class Decoder {
     return Hypothesis(words, weight);
   }
 
+  // From the next Decode on: the frame-by-frame alignment of the best path is kept (pk_mi355_decoder_set_alignment)
+  Status SetAlignment(bool on) { return Status::FromLast(pk_mi355_decoder_set_alignment(d_, on ? 1 : 0)); }
+  // Per frame of the last Decode: the best path's emitting arc, its transition-id and its acoustic cost (any pointer
+  // may be null).  Returns the frames aligned, or a negative code (alignment off: PK_MI355_E_STATE).
+  int Alignment(std::vector<int32_t> *arc_ids, std::vector<int32_t> *trans_ids, std::vector<float> *acoustic_cost) const {
+    const int n = pk_mi355_decoder_alignment(d_, 0, nullptr, nullptr, nullptr, 0);
+    if (n < 0) return n;
+    if (arc_ids) arc_ids->resize(n);
+    if (trans_ids) trans_ids->resize(n);
+    if (acoustic_cost) acoustic_cost->resize(n);
+    return pk_mi355_decoder_alignment(d_, 0, arc_ids ? arc_ids->data() : nullptr, trans_ids ? trans_ids->data() : nullptr,
+                                      acoustic_cost ? acoustic_cost->data() : nullptr, n);
+  }
+  // The word segments of the last Decode's best path, in spoken order (empty on failure: see the C entry)
+  std::vector<pk_mi355_word_t> WordSegments() const {
+    const int n = pk_mi355_decoder_word_segments(d_, 0, nullptr, 0);
+    std::vector<pk_mi355_word_t> out(n > 0 ? n : 0);
+    if (n > 0) pk_mi355_decoder_word_segments(d_, 0, out.data(), n);
+    return out;
+  }
+
   const Status &last_status() const { return status_; }
 
  private:
   pk_mi355_decoder_t *d_;
   Status status_;
+};
+
+// src/symbol_table.h: the word list (pk_symboltable_read / pk_symboltable_get, src/symbol_table.cc:23-79)
+class SymbolTable {
+ public:
+  SymbolTable() : st_(nullptr) {}
+  ~SymbolTable() { pk_mi355_symtab_destroy(st_); }
+  SymbolTable(const SymbolTable &) = delete;
+  SymbolTable &operator=(const SymbolTable &) = delete;
+
+  Status Read(const std::string &path) {
+    pk_mi355_symtab_destroy(st_);
+    st_ = pk_mi355_symtab_read(path.c_str());
+    return st_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  int size() const { return st_ ? pk_mi355_symtab_size(st_) : 0; }
+  // nullptr outside [0, size()), where the reference asserts
+  const char *Get(int symbol_id) const { return st_ ? pk_mi355_symtab_get(st_, symbol_id) : nullptr; }
+
+ private:
+  pk_mi355_symtab_t *st_;
+};
+
+// pk_t + pk_load + pk_process (src/pocketkaldi.h, src/pocketkaldi.cc:72-248): model file and waves to text.
+class Recognizer {
+ public:
+  // pk_utterance_t's results (src/pocketkaldi.h): hyp and loglikelihood_per_frame
+  struct Utterance {
+    std::string hyp;
+    float loglikelihood_per_frame;
+  };
+
+  Recognizer() : r_(nullptr) {}
+  ~Recognizer() { pk_mi355_recognizer_destroy(r_); }
+  Recognizer(const Recognizer &) = delete;
+  Recognizer &operator=(const Recognizer &) = delete;
+
+  Status Load(const std::string &model_file, int precision = PK_MI355_PRECISION_F32, int max_utts = 1,
+              int64_t max_total_samples = 16000 * 60, int64_t trace_capacity = 0) {
+    pk_mi355_recognizer_destroy(r_);
+    r_ = pk_mi355_recognizer_load(model_file.c_str(), precision, max_utts, max_total_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // pk_process for n waves at once; out (may be null) receives one Utterance per wave
+  Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out) {
+    const int rc = pk_mi355_recognizer_process(r_, waves, n);
+    if (rc != 0) return Status::FromLast(rc);
+    if (out) {
+      out->clear();
+      for (int u = 0; u < n; ++u) {
+        const char *hyp = pk_mi355_recognizer_hyp(r_, u);
+        out->push_back(Utterance{hyp ? hyp : "", pk_mi355_recognizer_loglikelihood_per_frame(r_, u)});
+      }
+    }
+    return Status();
+  }
+  // The owned objects: beam, trace gc, softmax mode, calibration and the result getters are their entries
+  pk_mi355_am_t *am() const { return pk_mi355_recognizer_am(r_); }
+  pk_mi355_batch_t *batch() const { return pk_mi355_recognizer_batch(r_); }
+  pk_mi355_decoder_t *decoder() const { return pk_mi355_recognizer_decoder(r_); }
+  const pk_mi355_symtab_t *symbols() const { return pk_mi355_recognizer_symtab(r_); }
+  pk_mi355_recognizer_t *handle() const { return r_; }
+
+ private:
+  pk_mi355_recognizer_t *r_;
 };
 
 // Online scoring of live streams (pk_mi355_stream_*): PCM pushed per slot in chunks; every

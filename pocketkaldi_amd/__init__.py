@@ -15,10 +15,13 @@ benchmark; it mirrors the reference's class names and argument meaning:
     Fst(path)                                fst.h           Fst::Read, CountArcs
     Decoder(fst, am, max_utts)               decoder.h       Decoder::Decode + BestPath, batched on the GPU
     OnlineDecoder(fst, am, max_streams)      the same search frame by frame across calls, partial hypotheses
+    SymbolTable(path)                        symbol_table.h  pk_symboltable_read / _get
+    Recognizer(config, ...).process(waves)   pocketkaldi.cc:72-248  pk_load + pk_process: waves to text
 
 There is no CPU fallback: if the library is missing or no gfx950 device is usable,
 every compute call raises ``PkError``.
 """
+import collections
 import ctypes as C
 import os
 
@@ -27,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "Result", "Segment", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -49,6 +52,11 @@ class pk_vector_t(C.Structure):          # vector.h:39-42
 
 class pk_decodable_t(C.Structure):       # decodable.h:15-18
     _fields_ = [("log_prob", pk_matrix_t), ("am", C.c_void_p)]
+
+
+class pk_mi355_word_t(C.Structure):      # one word segment of a best path (include/pk_mi355.h)
+    _fields_ = [("word", C.c_int32), ("start_frame", C.c_int32), ("num_frames", C.c_int32), ("graph_cost", C.c_float),
+                ("acoustic_cost", C.c_float)]
 
 
 _lib = None
@@ -85,6 +93,12 @@ EXPORTS = [
     "pk_mi355_online_decoder_open", "pk_mi355_online_decoder_advance", "pk_mi355_online_decoder_advance_host",
     "pk_mi355_online_decoder_synchronize", "pk_mi355_online_decoder_partial", "pk_mi355_online_decoder_result",
     "pk_mi355_online_decoder_best_path_arcs", "pk_mi355_online_decoder_active_bound",
+    "pk_mi355_decoder_set_alignment", "pk_mi355_decoder_alignment", "pk_mi355_decoder_word_segments",
+    "pk_mi355_online_decoder_word_segments",
+    "pk_mi355_symtab_read", "pk_mi355_symtab_destroy", "pk_mi355_symtab_size", "pk_mi355_symtab_get",
+    "pk_mi355_recognizer_load", "pk_mi355_recognizer_destroy", "pk_mi355_recognizer_am", "pk_mi355_recognizer_batch",
+    "pk_mi355_recognizer_decoder", "pk_mi355_recognizer_symtab", "pk_mi355_recognizer_process", "pk_mi355_recognizer_hyp",
+    "pk_mi355_recognizer_loglikelihood_per_frame",
 ]
 
 
@@ -244,6 +258,29 @@ def lib():
     L.pk_mi355_online_decoder_result.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.POINTER(C.c_int)]
     L.pk_mi355_online_decoder_best_path_arcs.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
     L.pk_mi355_online_decoder_active_bound.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_decoder_set_alignment.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_decoder_alignment.argtypes = [C.c_void_p, C.c_int, i32p, i32p, f32p, C.c_int]
+    L.pk_mi355_decoder_word_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(pk_mi355_word_t), C.c_int]
+    L.pk_mi355_online_decoder_word_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(pk_mi355_word_t), C.c_int]
+    L.pk_mi355_symtab_read.restype = C.c_void_p
+    L.pk_mi355_symtab_read.argtypes = [C.c_char_p]
+    L.pk_mi355_symtab_destroy.restype = None
+    L.pk_mi355_symtab_destroy.argtypes = [C.c_void_p]
+    L.pk_mi355_symtab_size.argtypes = [C.c_void_p]
+    L.pk_mi355_symtab_get.restype = C.c_char_p
+    L.pk_mi355_symtab_get.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_recognizer_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int64, C.c_int64]
+    L.pk_mi355_recognizer_destroy.restype = None
+    L.pk_mi355_recognizer_destroy.argtypes = [C.c_void_p]
+    for f in ("am", "batch", "decoder", "symtab"):
+        getattr(L, "pk_mi355_recognizer_" + f).restype = C.c_void_p
+        getattr(L, "pk_mi355_recognizer_" + f).argtypes = [C.c_void_p]
+    L.pk_mi355_recognizer_process.argtypes = [C.c_void_p, C.POINTER(pk_vector_t), C.c_int]
+    L.pk_mi355_recognizer_hyp.restype = C.c_char_p
+    L.pk_mi355_recognizer_hyp.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_recognizer_loglikelihood_per_frame.restype = C.c_float
+    L.pk_mi355_recognizer_loglikelihood_per_frame.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 
@@ -784,6 +821,17 @@ class Fst:
             pass
 
 
+Segment = collections.namedtuple("Segment", "word start_frame num_frames graph_cost acoustic_cost")
+Result = collections.namedtuple("Result", "text words weight ok loglikelihood_per_frame segments")
+
+
+def _segments(entry, handle, index):
+    n = _check_code(entry(handle, int(index), None, 0))
+    out = (pk_mi355_word_t * max(n, 1))()
+    _check_code(entry(handle, int(index), out, n))
+    return [Segment(s.word, s.start_frame, s.num_frames, s.graph_cost, s.acoustic_cost) for s in out[:n]]
+
+
 class Decoder:
     """decoder.h: Decoder::Decode + BestPath on the GPU, one workgroup per utterance.  trace_gc: every utterance of
     a call owns trace_capacity // n backtrace records and compacts them as they fill (same results, bit for bit)."""
@@ -859,6 +907,24 @@ class Decoder:
 
     def active_bound(self, utt):
         return _check_code(lib().pk_mi355_decoder_active_bound(self._h, int(utt)))
+
+    def set_alignment(self, on=True):
+        """From the next call on: one more launch writes, per frame, the best path's emitting arc and its acoustic cost."""
+        _check_code(lib().pk_mi355_decoder_set_alignment(self._h, 1 if on else 0))
+
+    def alignment(self, utt):
+        """(arc ids int32 [frames], transition-ids int32 [frames], acoustic costs float32 [frames]) of the best path;
+        empty for an utterance without one.  Raises (PK_MI355_E_STATE) when the call ran with alignment off."""
+        n = _check_code(lib().pk_mi355_decoder_alignment(self._h, int(utt), None, None, None, 0))
+        arcs, tids, ac = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if n:
+            _check_code(lib().pk_mi355_decoder_alignment(self._h, int(utt), arcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         tids.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ac), n))
+        return arcs, tids, ac
+
+    def word_segments(self, utt):
+        """[Segment(word, start_frame, num_frames, graph_cost, acoustic_cost)] of the best path (pk_mi355_word_t)."""
+        return _segments(lib().pk_mi355_decoder_word_segments, self._h, utt)
 
     def trace_stats(self, utt):
         """(peak records, slice records, compactions) of the last call: per utterance with trace gc on; with it off
@@ -944,3 +1010,117 @@ class OnlineDecoder:
 
     def active_bound(self, slot):
         return _check_code(lib().pk_mi355_online_decoder_active_bound(self._h, int(slot)))
+
+    def word_segments(self, slot):
+        """Segments of the slot's current path (partial while live, final after close); acoustic_cost is NaN."""
+        return _segments(lib().pk_mi355_online_decoder_word_segments, self._h, slot)
+
+
+class SymbolTable:
+    """symbol_table.h: the reference's SYM0 word list, read on the host (pk_mi355_symtab_read).  len(), [id] -> str."""
+
+    def __init__(self, path):
+        self._owner = None
+        self._h = lib().pk_mi355_symtab_read(os.fspath(path).encode())
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+
+    @classmethod
+    def _borrowed(cls, handle, owner):
+        self = cls.__new__(cls)
+        self._h, self._owner = handle, owner
+        return self
+
+    def __len__(self):
+        return _check_code(lib().pk_mi355_symtab_size(self._h))
+
+    def __getitem__(self, symbol_id):
+        s = lib().pk_mi355_symtab_get(self._h, int(symbol_id))
+        if s is None:
+            raise IndexError(lib().pk_mi355_last_error().decode())
+        return s.decode()
+
+    def close(self):
+        if getattr(self, "_h", None) and self._owner is None:
+            lib().pk_mi355_symtab_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Borrowed:
+    """An AcousticModel / BatchScorer / Decoder over a handle the Recognizer owns: every method, nothing to free."""
+
+    @staticmethod
+    def of(cls, handle, owner, **fields):
+        self = cls.__new__(cls)
+        self._h, self._owner, self._keep = handle, owner, None
+        for k, v in fields.items():
+            setattr(self, k, v)
+        self.close = lambda: None
+        return self
+
+
+class Recognizer:
+    """pk_load + pk_process (pocketkaldi.cc:72-248): the model file's graph, symbol table and acoustic model, a batch
+    scorer and a decoder with alignment on.  .am / .batch / .decoder / .symbols are the owned objects (beam, trace gc,
+    softmax mode and calibration are set through them); process(waves) -> [Result]."""
+
+    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0):
+        self._h = lib().pk_mi355_recognizer_load(os.fspath(config).encode(), AcousticModel.PRECISIONS[precision], int(max_utts),
+                                                 int(max_total_samples), int(trace_capacity))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self.max_utts, self.max_total_samples = int(max_utts), int(max_total_samples)
+        L = lib()
+        self.am = _Borrowed.of(AcousticModel, L.pk_mi355_recognizer_am(self._h), self)
+        self.batch = _Borrowed.of(BatchScorer, L.pk_mi355_recognizer_batch(self._h), self, _am=self.am)
+        self.decoder = _Borrowed.of(Decoder, L.pk_mi355_recognizer_decoder(self._h), self, _am=self.am, _fst=None)
+        self.symbols = SymbolTable._borrowed(L.pk_mi355_recognizer_symtab(self._h), self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_recognizer_destroy(self._h)
+            self._h = None
+            for part in (self.am, self.batch, self.decoder, self.symbols):
+                part._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _process_call(self, waves):
+        arr = (pk_vector_t * max(len(waves), 1))()
+        for i, w in enumerate(waves):
+            arr[i].dim, arr[i].data = w.shape[0], (_fp(w) if w.size else None)
+        _check_code(lib().pk_mi355_recognizer_process(self._h, arr, len(waves)))
+        out = []
+        for u in range(len(waves)):
+            words, weight, ok = self.decoder.result(u)
+            out.append(Result(lib().pk_mi355_recognizer_hyp(self._h, u).decode(), words, weight, ok,
+                              lib().pk_mi355_recognizer_loglikelihood_per_frame(self._h, u), self.decoder.word_segments(u)))
+        return out
+
+    def process(self, waves):
+        """pk_process for every wave (float sample values as read_wav gives them).  A list that does not fit max_utts /
+        max_total_samples is split into as many calls as it needs; a single wave that cannot fit is refused."""
+        waves = [_f32(w).ravel() for w in waves]
+        for i, w in enumerate(waves):
+            if w.shape[0] > self.max_total_samples:
+                raise PkCodeError(-1, "wave %d has %d samples, the recognizer holds %d" % (i, w.shape[0], self.max_total_samples))
+        out, call, samples = [], [], 0
+        for w in waves:
+            if call and (len(call) == self.max_utts or samples + w.shape[0] > self.max_total_samples):
+                out += self._process_call(call)
+                call, samples = [], 0
+            call.append(w)
+            samples += w.shape[0]
+        if call:
+            out += self._process_call(call)
+        return out

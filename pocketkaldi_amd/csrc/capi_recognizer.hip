@@ -1,0 +1,126 @@
+// capi_recognizer.hip -- pk_load + pk_process (pocketkaldi.cc:72-248) as one object: model file -> graph, symbol
+// table, acoustic model, batch scorer and decoder (alignment on); waves -> sentence and log-likelihood per frame.
+// Nothing here computes: the scorer and the decoder are the library's own entries, and every knob of theirs stays
+// theirs (pk_mi355_recognizer_am / _batch / _decoder hand them out).
+#include <string>
+#include <vector>
+
+#include "pk_host.h"
+
+using namespace pkhost;
+
+struct pk_mi355_recognizer {
+  pk_mi355_fst_t *fst = nullptr;
+  pk_mi355_symtab_t *symtab = nullptr;
+  pk_mi355_am_t *am = nullptr;
+  pk_mi355_batch_t *batch = nullptr;
+  pk_mi355_decoder_t *decoder = nullptr;
+  bool have = false;                       // results of a process call are readable
+  std::vector<std::string> hyp;            // per utterance of the last process
+  std::vector<float> per_frame;
+};
+
+extern "C" {
+
+void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
+  if (!r) return;
+  pk_mi355_decoder_destroy(r->decoder);    // (waits for its last call, which reads the batch's rows)
+  pk_mi355_batch_destroy(r->batch);
+  pk_mi355_am_destroy(r->am);
+  pk_mi355_symtab_destroy(r->symtab);
+  pk_mi355_fst_destroy(r->fst);
+  delete r;
+}
+
+pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int precision, int max_utts, int64_t max_total_samples,
+                                                int64_t trace_capacity) {
+  if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
+  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
+  pk_mi355_recognizer *r = new pk_mi355_recognizer();
+  auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
+  // pk_load's order (pocketkaldi.cc:81-131): fst, cmvn_stats, the AcousticModel keys, symbol_table.  Keys and host-side
+  // files first, so that a model file that cannot work is refused before the device is touched.
+  std::string path;
+  ModelConfig conf;
+  if (ConfigPath(config_path, "fst", &path) || !(r->fst = pk_mi355_fst_read(path.c_str()))) return failed();
+  if (ReadModelConfig(config_path, &conf)) return failed();
+  if (ConfigPath(config_path, "symbol_table", &path) || !(r->symtab = pk_mi355_symtab_read(path.c_str()))) return failed();
+  const int symbols = pk_mi355_symtab_size(r->symtab);
+  for (int a = 0; a < r->fst->num_arcs; ++a)       // pk_symboltable_get asserts this when the word is looked up
+    if (r->fst->arcs[a].olabel >= symbols) {
+      Fail(PK_MI355_E_INVALID, "%s: arc %d of the graph has output label %d, the symbol table has %d symbols", config_path, a,
+           r->fst->arcs[a].olabel, symbols);
+      return failed();
+    }
+  float stats[kCmvnStats];
+  if (pk_mi355_load(config_path, precision, &r->am, stats)) return failed();
+  if (!(r->batch = pk_mi355_batch_create(r->am, stats, max_utts, max_total_samples))) return failed();
+  if (!(r->decoder = pk_mi355_decoder_create(r->fst, r->am, max_utts, trace_capacity))) return failed();
+  if (pk_mi355_decoder_set_alignment(r->decoder, 1)) return failed();
+  return r;
+}
+
+pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return nullptr; }
+  return r->am;
+}
+pk_mi355_batch_t *pk_mi355_recognizer_batch(pk_mi355_recognizer_t *r) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return nullptr; }
+  return r->batch;
+}
+pk_mi355_decoder_t *pk_mi355_recognizer_decoder(pk_mi355_recognizer_t *r) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return nullptr; }
+  return r->decoder;
+}
+const pk_mi355_symtab_t *pk_mi355_recognizer_symtab(const pk_mi355_recognizer_t *r) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return nullptr; }
+  return r->symtab;
+}
+
+int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *waves, int n) {
+  if (!r || n < 0 || (n > 0 && !waves)) return Fail(PK_MI355_E_INVALID, "bad process arguments");
+  r->have = false;
+  pk_vector_t none = {0, nullptr};
+  int rc;
+  if ((rc = pk_mi355_batch_set_waves(r->batch, n ? waves : &none, n)) || (rc = pk_mi355_batch_score(r->batch, 0.1f, 0)) ||
+      (rc = pk_mi355_decoder_decode_batch(r->decoder, r->batch, 1)))
+    return rc;
+  r->hyp.assign(n, std::string());
+  r->per_frame.assign(n, 0.0f);
+  std::vector<int> words;
+  for (int u = 0; u < n; ++u) {
+    float weight = 0.0f;
+    int ok = 0;
+    const int count = pk_mi355_decoder_result(r->decoder, u, nullptr, 0, &weight, &ok);
+    if (count < 0) return count;
+    if (!ok || count == 0) continue;                 // pocketkaldi.cc:240-243: no words, "" and 0.0f
+    words.resize(count);
+    pk_mi355_decoder_result(r->decoder, u, words.data(), count, &weight, &ok);
+    std::string &text = r->hyp[u];
+    for (int i = 0; i < count; ++i) {
+      const char *word = pk_mi355_symtab_get(r->symtab, words[i]);
+      if (!word) return pk_mi355_last_error_code();  // (cannot happen: load has checked every olabel)
+      if (i) text += ' ';                            // (:232-238: a space after every word, the last one dropped by pk_strlcpy)
+      text += word;
+    }
+    r->per_frame[u] = weight / pk_mi355_batch_num_frames(r->batch, u);     // :239
+  }
+  r->have = true;
+  return 0;
+}
+
+const char *pk_mi355_recognizer_hyp(const pk_mi355_recognizer_t *r, int utt) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return nullptr; }
+  if (!r->have) { Fail(PK_MI355_E_STATE, "recognizer: nothing processed"); return nullptr; }
+  if (utt < 0 || utt >= (int)r->hyp.size()) { Fail(PK_MI355_E_INVALID, "bad utterance index"); return nullptr; }
+  return r->hyp[utt].c_str();
+}
+
+float pk_mi355_recognizer_loglikelihood_per_frame(const pk_mi355_recognizer_t *r, int utt) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null recognizer"); return NAN; }
+  if (!r->have) { Fail(PK_MI355_E_STATE, "recognizer: nothing processed"); return NAN; }
+  if (utt < 0 || utt >= (int)r->hyp.size()) { Fail(PK_MI355_E_INVALID, "bad utterance index"); return NAN; }
+  return r->per_frame[utt];
+}
+
+}  // extern "C"

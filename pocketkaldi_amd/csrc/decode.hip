@@ -583,6 +583,71 @@ __global__ void __launch_bounds__(256) GatherPathsKernel(UttResult *res, int n, 
   if (threadIdx.x == 0) res[u].path_off = off;
 }
 
+// ================================================================== alignment (pk_mi355_decoder_set_alignment)
+// After the decode (and, with trace gc, after GatherPathsKernel) on the same stream: the frame of every emitting arc of
+// the best path.  One workgroup per utterance walks the path's arc ids in chunks of the block size; an exclusive scan
+// over "this arc emits" with a base carried from chunk to chunk numbers the frames.  Per frame t it writes the arc id
+// and the acoustic cost -N1(ll[t][pdf]).  An utterance that failed, ended with ok = 0 or has no path writes nothing.
+
+struct AlignResult {
+  int status;       // 0, or PK_MI355_E_DEVICE: the path's emitting arcs are not the utterance's frames
+  int frames;       // frames aligned
+};
+
+struct AlignArgs {
+  const UttResult *res;
+  const int *path; int path_cap;        // the call's paths (path_off / path_len of res index it) and its entries
+  const int *arc_pdf; int num_arcs;     // by original arc id: the pdf, -1 for an epsilon arc
+  const float *ll; const int64_t *ll_off; const int *T; const int64_t *frame_off;
+  int num_pdfs, num_utts;
+  int *ali; float *ac;                  // per frame of the call: utterance u's frame t at frame_off[u] + t
+  AlignResult *out;
+};
+
+__global__ void __launch_bounds__(kDecThreads) AlignKernel(AlignArgs A) {
+  __shared__ Shared sh;
+  __shared__ int s_bad;
+  const int u = blockIdx.x;
+  if (u >= A.num_utts) return;
+  const UttResult r = A.res[u];
+  const int T = A.T[u];
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  const bool active = !r.status && r.ok && r.path_len > 0;
+  const bool inside = r.path_off >= 0 && (int64_t)r.path_off + r.path_len <= (int64_t)A.path_cap;
+  int base = 0;
+  if (active && inside) {
+    const int *path = A.path + r.path_off;
+    const float *ll = A.ll + A.ll_off[u];
+    const int64_t at = A.frame_off[u];
+    for (int c0 = 0; c0 < r.path_len; c0 += kDecThreads) {
+      const int i = c0 + threadIdx.x;
+      int arc = -1, pdf = -1;
+      if (i < r.path_len) {
+        arc = path[i];
+        if (arc >= 0 && arc < A.num_arcs) pdf = A.arc_pdf[arc];
+        else s_bad = 1;
+      }
+      const int emits = pdf >= 0 && pdf < A.num_pdfs;
+      int total;
+      const int t = base + BlockScan(sh, emits, &total);
+      if (emits && t < T) {
+        A.ali[at + t] = arc;
+        A.ac[at + t] = -fmaxf(ll[(size_t)t * A.num_pdfs + pdf], -INFINITY);   // N1: a NaN log-likelihood counts as -inf
+      }
+      base += total;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const bool good = active && inside && !s_bad && base == T;
+    AlignResult o;
+    o.status = active && !good ? PK_MI355_E_DEVICE : 0;
+    o.frames = good ? base : 0;
+    A.out[u] = o;
+  }
+}
+
 // ================================================================== online decoding (pk_mi355_online_decoder_*)
 // DecodeFrames, resumable: a slot's token list, its count and buffer, ok / status, the largest touched count, the
 // frames decoded and its trace-arena top live in HBM between launches.  One workgroup per slot with new frames;
@@ -666,7 +731,6 @@ struct pk_mi355_decoder {
   int max_active = 30000;
   int64_t trace_cap = 0;
   bool trace_gc = false;                        // set_trace_gc: how the next call uses the arena
-  std::vector<int32_t> olabel;                  // by original arc id
   // device graph
   int *e_off = nullptr, *e_src = nullptr, *n_off = nullptr, *n_src = nullptr;
   int4 *e_arc = nullptr, *n_arc = nullptr;
@@ -697,13 +761,28 @@ struct pk_mi355_decoder {
   std::vector<int32_t> h_path;
   std::vector<int> h_T;
   std::vector<int64_t> h_off;
+  ArcLabels labels;                             // the graph's labels and weights by original arc id (words, segments)
+  // alignment (set_alignment): the mode of the next call and of the last one; the device table and buffers, made at
+  // the first enable
+  bool alignment = false, call_align = false;
+  int *d_arc_pdf = nullptr;
+  int64_t *d_frame_off = nullptr;
+  AlignResult *d_align = nullptr;
+  int *d_ali = nullptr;
+  float *d_ac = nullptr;
+  size_t d_ali_frames = 0;
+  std::vector<int64_t> h_frame_off;               // the last call's prefix sum of T (num_utts + 1 entries)
+  std::vector<AlignResult> h_align;
+  std::vector<int32_t> h_ali;
+  std::vector<float> h_ac;
 };
 
 namespace {
 
 void FreeDecoderDevice(pk_mi355_decoder *d) {
   void *ptrs[] = {d->e_off, d->e_src, d->n_off, d->n_src, d->e_arc, d->n_arc, d->final_w, d->key, d->tr, d->mark,
-                  d->touched, d->nxt, d->lists, d->rec, d->counters, d->path, d->d_res, d->d_ll, d->d_off, d->d_T};
+                  d->touched, d->nxt, d->lists, d->rec, d->counters, d->path, d->d_res, d->d_ll, d->d_off, d->d_T,
+                  d->d_arc_pdf, d->d_frame_off, d->d_align, d->d_ali, d->d_ac};
   for (void *p : ptrs) if (p) hipFree(p);
   if (d->done) hipEventDestroy(d->done);
   if (d->own_stream) hipStreamDestroy(d->own_stream);
@@ -740,7 +819,7 @@ int CreateDecoder(pk_mi355_decoder *d, const pk_mi355_fst *f, const pk_mi355_am 
   if (rc || (rc = Upload(&d->e_off, g.e_off)) || (rc = Upload(&d->n_off, g.n_off)) || (rc = Upload(&d->e_src, g.e_src)) ||
       (rc = Upload(&d->n_src, g.n_src)) || (rc = Upload(&d->final_w, f->final_w)))
     return rc;
-  d->olabel = std::move(g.olabel);
+  LabelsOf(*f, &d->labels);
   const size_t per = (size_t)S * max_utts;
   HIP_TRY(hipMalloc(&d->key, sizeof(uint64_t) * per));
   HIP_TRY(hipMemset(d->key, 0xFF, sizeof(uint64_t) * per));
@@ -825,9 +904,25 @@ int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off
   d->call_gc = d->trace_gc;
   d->call_slice = d->call_gc ? d->trace_cap / std::max(n, 1) : d->trace_cap;
   d->call_records = 0;
+  d->call_align = d->alignment;
+  if (d->call_align) {                                         // the frames of the call, one utterance after the other
+    d->h_frame_off.assign(n + 1, 0);
+    for (int u = 0; u < n; ++u) d->h_frame_off[u + 1] = d->h_frame_off[u] + T[u];
+    const size_t frames = (size_t)d->h_frame_off[n];
+    if (frames > d->d_ali_frames) {
+      if (d->d_ali) hipFree(d->d_ali);
+      if (d->d_ac) hipFree(d->d_ac);
+      d->d_ali = nullptr; d->d_ac = nullptr; d->d_ali_frames = 0;
+      HIP_TRY(hipMalloc(&d->d_ali, sizeof(int) * frames));
+      HIP_TRY(hipMalloc(&d->d_ac, sizeof(float) * frames));
+      d->d_ali_frames = frames;
+    }
+  }
   if (n > 0) {
     HIP_TRY(hipMemcpyAsync(d->d_off, d->h_off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d->d_T, d->h_T.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream));
+    if (d->call_align)
+      HIP_TRY(hipMemcpyAsync(d->d_frame_off, d->h_frame_off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * 2, stream));
     DecArgs A = ArgsOf(d, ll, n);
     A.ll_off = d->d_off; A.T = d->d_T;
@@ -840,6 +935,18 @@ int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off
       A.rec_cap = d->trace_cap; A.rec_top = d->counters;       // one arena and one path arena shared by the call
       A.path_cap = d->path_cap; A.path_top = reinterpret_cast<int *>(d->counters + 1);
       hipLaunchKernelGGL(DecodeKernel<false>, dim3(n), dim3(kDecThreads), sizeof(float) * d->num_pdfs, stream, A);
+    }
+    if (d->call_align) {
+      AlignArgs G = {};
+      G.res = d->d_res;
+      // (with trace gc on GatherPathsKernel has moved the paths to the front of the record arena)
+      G.path = d->call_gc ? reinterpret_cast<const int *>(d->rec) : d->path;
+      G.path_cap = (int)d->trace_cap;
+      G.arc_pdf = d->d_arc_pdf; G.num_arcs = (int)d->labels.ilabel.size();
+      G.ll = ll; G.ll_off = d->d_off; G.T = d->d_T; G.frame_off = d->d_frame_off;
+      G.num_pdfs = d->num_pdfs; G.num_utts = n;
+      G.ali = d->d_ali; G.ac = d->d_ac; G.out = d->d_align;
+      hipLaunchKernelGGL(AlignKernel, dim3(n), dim3(kDecThreads), 0, stream, G);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
@@ -875,6 +982,15 @@ int Collect(pk_mi355_decoder *d) {
     if (n) HIP_TRY(hipMemcpy(&records, d->counters, sizeof(records), hipMemcpyDeviceToHost));
     d->call_records = (int64_t)std::min(records, (unsigned long long)d->trace_cap);   // (a failed bump overshoots)
   }
+  if (d->call_align) {
+    const size_t frames = n ? (size_t)d->h_frame_off[n] : 0;
+    d->h_align.resize(n); d->h_ali.resize(frames); d->h_ac.resize(frames);
+    if (n) HIP_TRY(hipMemcpy(d->h_align.data(), d->d_align, sizeof(AlignResult) * n, hipMemcpyDeviceToHost));
+    if (frames) {
+      HIP_TRY(hipMemcpy(d->h_ali.data(), d->d_ali, sizeof(int) * frames, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(d->h_ac.data(), d->d_ac, sizeof(float) * frames, hipMemcpyDeviceToHost));
+    }
+  }
   for (int u = 0; u < n; ++u) {
     const UttResult &r = d->res[u];
     if (r.status == PK_MI355_E_CAPACITY && d->call_gc)
@@ -888,6 +1004,9 @@ int Collect(pk_mi355_decoder *d) {
       return Fail(PK_MI355_E_INVALID, "decoder: utterance %d: negative epsilon cycle (the closure did not settle)", u);
     if (r.path_off < 0 || r.path_len < 0 || r.path_off + r.path_len > used)
       return Fail(PK_MI355_E_DEVICE, "decoder: utterance %d: corrupt result", u);
+    if (d->call_align && (d->h_align[u].status || (d->h_align[u].frames != 0 && d->h_align[u].frames != d->h_T[u])))
+      return Fail(PK_MI355_E_DEVICE, "decoder: utterance %d: corrupt result (the best path's emitting arcs are not its %d frames)",
+                  u, d->h_T[u]);
   }
   d->have = true;
   return 0;
@@ -934,6 +1053,29 @@ int pk_mi355_decoder_set_beam(pk_mi355_decoder_t *d, float beam, int max_active)
 int pk_mi355_decoder_set_trace_gc(pk_mi355_decoder_t *d, int enable) {
   if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
   d->trace_gc = enable != 0;
+  return 0;
+}
+
+int pk_mi355_decoder_set_alignment(pk_mi355_decoder_t *d, int enable) {
+  if (!d) return Fail(PK_MI355_E_INVALID, "null decoder");
+  if (enable && !d->d_arc_pdf) {                  // the first enable: the emitting flag and pdf of every arc, by arc id
+    int rc = UseDevice(d->device);
+    if (rc) return rc;
+    const std::vector<int32_t> &tid2pdf = d->am->tid2pdf;
+    std::vector<int> arc_pdf(d->labels.ilabel.size());
+    for (size_t a = 0; a < arc_pdf.size(); ++a) {
+      const int il = d->labels.ilabel[a];           // (CreateDecoder has checked every ilabel against the model)
+      arc_pdf[a] = il == 0 ? -1 : tid2pdf.empty() ? il : tid2pdf[il];
+    }
+    if (!d->d_frame_off) HIP_TRY(hipMalloc(&d->d_frame_off, sizeof(int64_t) * d->max_utts));
+    if (!d->d_align) HIP_TRY(hipMalloc(&d->d_align, sizeof(AlignResult) * d->max_utts));
+    if ((rc = Upload(&d->d_arc_pdf, arc_pdf))) {
+      if (d->d_arc_pdf) hipFree(d->d_arc_pdf);
+      d->d_arc_pdf = nullptr;
+      return rc;
+    }
+  }
+  d->alignment = enable != 0;
   return 0;
 }
 
@@ -999,7 +1141,7 @@ int pk_mi355_decoder_result(const pk_mi355_decoder_t *d, int utt, int *words, in
   const UttResult &r = d->res[utt];
   if (weight) *weight = r.weight;
   if (ok) *ok = r.ok;
-  return PathWords(d->olabel, d->h_path.data() + r.path_off, r.path_len, words, max_words);
+  return PathWords(d->labels.olabel, d->h_path.data() + r.path_off, r.path_len, words, max_words);
 }
 
 int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_t *arcs, int max_arcs) {
@@ -1008,6 +1150,37 @@ int pk_mi355_decoder_best_path_arcs(const pk_mi355_decoder_t *d, int utt, int32_
   const UttResult &r = d->res[utt];
   for (int i = 0; i < r.path_len && i < max_arcs; ++i) arcs[i] = d->h_path[r.path_off + i];
   return r.path_len;
+}
+
+static int CheckAligned(const pk_mi355_decoder_t *d, int utt) {
+  int rc = CheckResult(d, utt);
+  if (rc) return rc;
+  if (!d->call_align) return Fail(PK_MI355_E_STATE, "decoder: the call ran with alignment off (pk_mi355_decoder_set_alignment)");
+  return 0;
+}
+
+int pk_mi355_decoder_alignment(const pk_mi355_decoder_t *d, int utt, int32_t *arc_ids, int32_t *trans_ids, float *acoustic_cost,
+                               int max_frames) {
+  int rc = CheckAligned(d, utt);
+  if (rc) return rc;
+  const int frames = d->h_align[utt].frames;
+  const int64_t at = d->h_frame_off[utt];
+  for (int t = 0; t < frames && t < max_frames; ++t) {
+    const int arc = d->h_ali[at + t];
+    if (arc_ids) arc_ids[t] = arc;
+    if (trans_ids) trans_ids[t] = (arc >= 0 && arc < (int)d->labels.ilabel.size()) ? d->labels.ilabel[arc] : 0;
+    if (acoustic_cost) acoustic_cost[t] = d->h_ac[at + t];
+  }
+  return frames;
+}
+
+int pk_mi355_decoder_word_segments(const pk_mi355_decoder_t *d, int utt, pk_mi355_word_t *out, int max) {
+  int rc = CheckAligned(d, utt);
+  if (rc) return rc;
+  const UttResult &r = d->res[utt];
+  static const float none = 0.0f;                   // (a call without any frame: still "given", and never read)
+  const float *ac = d->h_ac.empty() ? &none : d->h_ac.data() + d->h_frame_off[utt];
+  return WordSegments(d->labels, d->h_path.data() + r.path_off, r.path_len, ac, d->h_align[utt].frames, out, max);
 }
 
 int pk_mi355_decoder_active_bound(const pk_mi355_decoder_t *d, int utt) {
@@ -1101,7 +1274,7 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
 }
 
 int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
-  return PathWords(o->dec.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
+  return PathWords(o->dec.labels.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
 }
 
 int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {
@@ -1246,6 +1419,14 @@ int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, i
   const auto &p = o->paths[slot];
   for (int i = 0; i < (int)p.size() && i < max_arcs; ++i) arcs[i] = p[i];
   return (int)p.size();
+}
+
+int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *o, int slot, pk_mi355_word_t *out, int max) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  const auto &p = o->paths[slot];
+  return WordSegments(o->dec.labels, p.data(), (int)p.size(), nullptr, 0, out, max);   // (the rows are gone: no acoustic cost)
 }
 
 int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *o, int slot) {

@@ -302,6 +302,83 @@ int PathWords(const std::vector<int32_t> &olabel, const int32_t *arcs, int num_a
   return n;
 }
 
+void LabelsOf(const pk_mi355_fst &f, ArcLabels *out) {
+  out->ilabel.resize(f.num_arcs); out->olabel.resize(f.num_arcs); out->weight.resize(f.num_arcs);
+  for (int a = 0; a < f.num_arcs; ++a) {
+    out->ilabel[a] = f.arcs[a].ilabel; out->olabel[a] = f.arcs[a].olabel; out->weight[a] = f.arcs[a].weight;
+  }
+}
+
+int WordSegments(const ArcLabels &g, const int32_t *arcs, int num_arcs, const float *ac, int num_ac, pk_mi355_word_t *out,
+                 int max) {
+  int n = 0, frame = 0;
+  bool open = false;
+  pk_mi355_word_t cur = {0, 0, 0, 0.0f, 0.0f};
+  double graph = 0.0, acoustic = 0.0;
+  auto close = [&]() {
+    cur.graph_cost = (float)graph;
+    cur.acoustic_cost = ac ? (float)acoustic : NAN;
+    if (out && n < max) out[n] = cur;
+    ++n;
+  };
+  for (int i = 0; i < num_arcs; ++i) {
+    const int arc = arcs[i];
+    const bool known = arc >= 0 && arc < (int)g.olabel.size();      // (an id outside the graph: an epsilon arc of weight 0)
+    const int word = known ? g.olabel[arc] : 0;
+    if (word != 0 || !open) {
+      if (open) close();
+      open = true;
+      cur.word = word; cur.start_frame = frame; cur.num_frames = 0;
+      graph = 0.0; acoustic = 0.0;
+    }
+    if (known) graph += (double)g.weight[arc];
+    if (known && g.ilabel[arc] != 0) {
+      acoustic += (ac && frame < num_ac) ? (double)ac[frame] : (double)NAN;
+      ++cur.num_frames;
+      ++frame;
+    }
+  }
+  if (open) close();
+  return n;
+}
+
+int ConfigPath(const char *config_path, const char *key, std::string *out) {
+  ConfigFile conf;
+  int rc = conf.Read(config_path);
+  return rc ? rc : conf.Path(key, out);
+}
+
+// ------------------------------------------------------------------ symbol table
+
+int ReadSymtab(const char *path, pk_mi355_symtab *st) {
+  FileBuf f;
+  int rc = f.Open(path);
+  if (rc) return rc;
+  int32_t section, size, buffer_size;
+  if (!f.Tag("SYM0") || !f.I32(&section)) return Fail(PK_MI355_E_IO, "SYM0 section expected in %s", path);
+  if (!f.I32(&size) || !f.I32(&buffer_size)) return Fail(PK_MI355_E_IO, "%s: malformed symbol table: truncated header", path);
+  if (size < 0 || buffer_size < 0)
+    return Fail(PK_MI355_E_IO, "%s: malformed symbol table: negative size %d or buffer size %d", path, size, buffer_size);
+  const int64_t expect = 8 + 4 * (int64_t)size + (int64_t)buffer_size;      // symbol_table.cc:45-54
+  if (expect != section)
+    return Fail(PK_MI355_E_IO, "pk_symboltable_read: section_size = %lld expected, but %d found (%s)", (long long)expect, section,
+                path);
+  if ((uint64_t)(expect - 8) > (uint64_t)(f.d.size() - f.pos))
+    return Fail(PK_MI355_E_IO, "%s: malformed symbol table: truncated (%zu bytes, %lld expected)", path, f.d.size(),
+                (long long)(8 + expect));
+  st->index.resize(size);
+  if (size) memcpy(st->index.data(), &f.d[f.pos], (size_t)size * 4);
+  f.pos += (size_t)size * 4;
+  st->buffer.assign(f.d.begin() + f.pos, f.d.begin() + f.pos + buffer_size);
+  if (buffer_size > 0 && st->buffer.back() != '\0')
+    return Fail(PK_MI355_E_IO, "%s: malformed symbol table: the string buffer does not end in NUL", path);
+  for (int i = 0; i < size; ++i)
+    if (st->index[i] < 0 || st->index[i] >= buffer_size)
+      return Fail(PK_MI355_E_INVALID, "%s: invalid symbol table: offset %d of symbol %d outside [0, %d)", path, st->index[i], i,
+                  buffer_size);
+  return 0;
+}
+
 }  // namespace pkhost
 
 using namespace pkhost;
@@ -342,6 +419,25 @@ int pk_mi355_fst_arc_range(const pk_mi355_fst_t *fst, int state, int *first, int
   if (first) *first = fst->arc_first[state];
   if (count) *count = fst->arc_count[state];
   return 0;
+}
+
+pk_mi355_symtab_t *pk_mi355_symtab_read(const char *path) {
+  if (!path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
+  pk_mi355_symtab *st = new pk_mi355_symtab();
+  if (ReadSymtab(path, st)) { delete st; return nullptr; }
+  return st;
+}
+
+void pk_mi355_symtab_destroy(pk_mi355_symtab_t *st) { delete st; }
+int pk_mi355_symtab_size(const pk_mi355_symtab_t *st) { return st ? (int)st->index.size() : Fail(PK_MI355_E_INVALID, "null symbol table"); }
+
+const char *pk_mi355_symtab_get(const pk_mi355_symtab_t *st, int id) {
+  if (!st) { Fail(PK_MI355_E_INVALID, "null symbol table"); return nullptr; }
+  if (id < 0 || id >= (int)st->index.size()) {
+    Fail(PK_MI355_E_INVALID, "symbol id %d outside [0, %d)", id, (int)st->index.size());
+    return nullptr;
+  }
+  return st->buffer.data() + st->index[id];
 }
 
 }  // extern "C"

@@ -139,6 +139,35 @@ int SplitGraph(const pk_mi355_fst &f, const std::vector<int32_t> &tid2pdf, int n
 // The words of a path: its arcs' non-zero olabels, in path order.  Returns their number; writes at most max_words.
 int PathWords(const std::vector<int32_t> &olabel, const int32_t *arcs, int num_arcs, int *words, int max_words);
 
+// The graph's labels and weights by original arc id, as the segment function reads them.
+struct ArcLabels {
+  std::vector<int32_t> ilabel, olabel;
+  std::vector<float> weight;
+};
+void LabelsOf(const pk_mi355_fst &f, ArcLabels *out);
+
+// The word segments of a path (pk_mi355_word_t, include/pk_mi355.h): a segment begins at every arc whose olabel is
+// not 0 and runs up to the next such arc; the arcs before the first one form a leading segment with word 0.  ac: the
+// acoustic cost of each of the path's num_ac frames, or null (acoustic_cost is then NaN).  Sums are taken in double
+// in path order and rounded to float once.  Returns the number of segments; writes at most max.
+int WordSegments(const ArcLabels &g, const int32_t *arcs, int num_arcs, const float *ac, int num_ac, pk_mi355_word_t *out,
+                 int max);
+
+// pk_load's own keys (pocketkaldi.cc:81-88, 117-124): the path a key of the model file names, resolved against the
+// file's directory; a missing key is "Unable to find key '<key>' in <file>".
+int ConfigPath(const char *config_path, const char *key, std::string *out);
+
+}  // namespace pkhost
+
+// ------------------------------------------------------------------ symbol table (pk_symboltable_read, symbol_table.cc:23-73)
+
+struct pk_mi355_symtab {
+  std::vector<int32_t> index;      // offset of symbol i's string in buffer
+  std::vector<char> buffer;        // NUL-terminated strings; ends in NUL when not empty
+};
+
+namespace pkhost {
+int ReadSymtab(const char *path, pk_mi355_symtab *st);
 }  // namespace pkhost
 
 #endif  // PK_FILES_H_

@@ -6,6 +6,7 @@
 //   capi_batch.hip       the batched device-resident scorer, result arenas and views
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
+//   capi_recognizer.hip  pk_load + pk_process as one object over the entries of the others
 // Nothing here is part of the ABI (include/pk_mi355.h is); the library exports the C entries only
 // (libpk_mi355.map).
 #ifndef PK_HOST_H_

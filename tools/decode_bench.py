@@ -17,10 +17,13 @@ a condition:
                             largest active_bound, peak records against the slice, all compactions, and how many of
                             the first `cpu_utts` results equal the reference decoder's (words, weight bits, ok)
   mode_cost                 (--mode-cost) the first leg's call with trace gc off, on, off, on in one session
+  alignment_cost            (--alignment) the first leg's call with alignment off, on, off, on on the one decoder in one
+                            session (written to profiles/r08_decode_alignment.json): each on-run has an off-run beside
+                            it as its yardstick; the frames aligned in the on-runs are counted
 
     python tools/decode_bench.py [--utts 256] [--seconds 10] [--states 200000] [--cpu-utts 16] [--steps 3]
                                  [--max-active 2000] [--trace-capacity 2^30] [--trace-gc] [--reference-settings]
-                                 [--mode-cost]
+                                 [--mode-cost] [--alignment]
 """
 import argparse
 import ctypes as C
@@ -57,12 +60,14 @@ def main():
     ap.add_argument("--reference-settings", action="store_true",
                     help="add the leg at the reference's settings: the whole batch at max-active 30000, trace gc on")
     ap.add_argument("--mode-cost", action="store_true", help="add the first leg's call with trace gc off / on / off / on")
+    ap.add_argument("--alignment", action="store_true", help="add the first leg's call with alignment off / on / off / on")
     ap.add_argument("--out", default=None, help="profiles/r06_decode.json; profiles/r07_decode_gc.json with any of "
                     "--trace-gc, --reference-settings, --mode-cost")
     a = ap.parse_args()
     if a.out is None:
         gc_run = a.trace_gc or a.reference_settings or a.mode_cost
-        a.out = os.path.join(REPO, "profiles", "r07_decode_gc.json" if gc_run else "r06_decode.json")
+        a.out = os.path.join(REPO, "profiles", "r08_decode_alignment.json" if a.alignment else
+                             "r07_decode_gc.json" if gc_run else "r06_decode.json")
 
     pk.set_device(0)
     layers, prior, L, R = synth.model("S")
@@ -116,6 +121,19 @@ def main():
         off_ms = np.mean([x["decode_ms"] for x in legs if not x["trace_gc"]])
         on_ms = np.mean([x["decode_ms"] for x in legs if x["trace_gc"]])
         res["mode_cost"] = dict(max_active=a.max_active, legs=legs, on_over_off=round(float(on_ms / off_ms), 4))
+    if a.alignment:
+        legs = []
+        for on in (False, True, False, True):
+            dec.set_alignment(on)
+            ms = round(timed(a.max_active, a.steps)[1], 3)
+            legs.append(dict(alignment=on, decode_ms=ms,
+                             frames_aligned=sum(len(dec.alignment(u)[0]) for u in range(a.utts)) if on else 0))
+        dec.set_alignment(False)
+        off = [x["decode_ms"] for x in legs if not x["alignment"]]
+        on_ms = [x["decode_ms"] for x in legs if x["alignment"]]
+        res["alignment_cost"] = dict(max_active=a.max_active, trace_gc=bool(a.trace_gc), legs=legs,
+                                     on_over_off=round(float(np.mean(on_ms) / np.mean(off)), 4),
+                                     off_spread=round(float(max(off) / min(off)), 4))
     ref = None
     # Same work on both sides: the first cpu_utts utterances at the reference's own max-active (kBeamSize = 30000;
     # pkref_decode cannot take another), decoded by the GPU decoder from the same fetch_all views and by the
