@@ -1,0 +1,239 @@
+// capi_online_decoder.hip -- the online decoder, pk_mi355_online_decoder_*: slots that are opened, advanced by chunks
+// of log-likelihoods (the host's, or an online scorer's rows on the device) and closed; a slot's tokens and backtrace
+// live on the device between calls.  Over the decoder core (pk_decode.h); the kernel is decode.hip's.
+#include <vector>
+
+#include "pk_decode.h"
+
+using namespace pkhost;
+
+// The core's work areas are one per slot, its arenas cap records per slot.
+struct pk_mi355_online_decoder : DecoderCore {
+  int max_streams = 0;
+  int64_t cap = 0;
+  OnlineState *d_state = nullptr;
+  OnlineResult *d_results = nullptr;
+  int *d_remap = nullptr;
+  OnlineCall *d_calls = nullptr;
+  std::vector<int> open_, fresh, finished;      // per slot
+  std::vector<OnlineResult> res;                // per slot, after synchronize
+  std::vector<std::vector<int32_t>> paths;      // per slot: the arcs of res[slot]'s path
+  std::vector<int> last_slots;                  // slots of the last call
+  bool pending = false;
+};
+
+namespace {
+
+int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<OnlineCall> &calls, hipStream_t stream) {
+  if (o->pending) HIP_TRY(hipEventSynchronize(o->done));
+  o->pending = false;
+  o->last_slots.clear();
+  for (const auto &c : calls) o->last_slots.push_back(c.slot);
+  const int n = (int)calls.size();
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
+    // (frames, arenas and results are per slot: the calls, and o->cap entries of rec and path each)
+    LaunchOnlineDecode(ArgsOf(o, ll, n), o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap, n, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
+  }
+  for (const auto &c : calls) {
+    o->fresh[c.slot] = 0;
+    if (c.final_) { o->finished[c.slot] = 1; o->open_[c.slot] = 0; }
+  }
+  HIP_TRY(hipEventRecord(o->done, stream));
+  o->pending = true;
+  return 0;
+}
+
+int OnlineCollect(pk_mi355_online_decoder *o) {
+  if (!o->pending) return 0;
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  o->pending = false;
+  HIP_TRY(hipEventSynchronize(o->done));
+  if (o->last_slots.empty()) return 0;
+  HIP_TRY(hipMemcpy(o->res.data(), o->d_results, sizeof(OnlineResult) * o->max_streams, hipMemcpyDeviceToHost));
+  int first_bad = -1;
+  for (int slot : o->last_slots) {
+    const OnlineResult &r = o->res[slot];
+    if (r.path_len < 0 || r.path_len > o->cap) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
+    o->paths[slot].resize(r.path_len);
+    if (r.path_len)
+      HIP_TRY(hipMemcpy(o->paths[slot].data(), o->path + (int64_t)slot * o->cap, sizeof(int32_t) * r.path_len,
+                        hipMemcpyDeviceToHost));
+    if (r.status && first_bad < 0) first_bad = slot;
+  }
+  if (first_bad >= 0) {
+    const OnlineResult &r = o->res[first_bad];
+    if (r.status == PK_MI355_E_CAPACITY)
+      return Fail(PK_MI355_E_CAPACITY, "online decoder: slot %d: backtrace storage exhausted after compaction (%lld records "
+                  "per slot)", first_bad, (long long)o->cap);
+    return Fail(PK_MI355_E_INVALID, "online decoder: slot %d: negative epsilon cycle (the closure did not settle)", first_bad);
+  }
+  return 0;
+}
+
+int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
+  return PathWords(o->labels.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
+}
+
+int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  if (slot < 0 || slot >= o->max_streams) return Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, o->max_streams);
+  return 0;
+}
+
+// A getter's slot: in range, and no call in flight.
+int OnlineReady(const pk_mi355_online_decoder *o, int slot) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->pending) return Fail(PK_MI355_E_STATE, "online decoder: synchronize first");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *fst, const pk_mi355_am_t *am, int max_streams,
+                                                          int64_t trace_capacity) {
+  if (CheckCoreInputs(fst, am)) return nullptr;
+  if (max_streams <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online decoder capacity"); return nullptr; }
+  const int64_t cap = trace_capacity > 0 ? trace_capacity : (int64_t)1 << 20;
+  if (cap * max_streams > (int64_t)INT32_MAX) { Fail(PK_MI355_E_INVALID, "online decoder: max_streams x trace_capacity above 2^31 - 1"); return nullptr; }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_online_decoder *o = new pk_mi355_online_decoder();
+  o->max_streams = max_streams;
+  o->cap = cap;
+  bool ok = CreateCore(o, fst, am, max_streams, cap * max_streams) == 0;
+  auto chk = [&](hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "online_decoder_create: %s", hipGetErrorString(e)); } };
+  if (ok) chk(hipMalloc(&o->d_state, sizeof(OnlineState) * max_streams));
+  if (ok) chk(hipMemset(o->d_state, 0, sizeof(OnlineState) * max_streams));
+  if (ok) chk(hipMalloc(&o->d_results, sizeof(OnlineResult) * max_streams));
+  if (ok) chk(hipMemset(o->d_results, 0, sizeof(OnlineResult) * max_streams));
+  if (ok) chk(hipMalloc(&o->d_remap, sizeof(int) * cap * max_streams));
+  if (ok) chk(hipMalloc(&o->d_calls, sizeof(OnlineCall) * max_streams));
+  if (!ok) { pk_mi355_online_decoder_destroy(o); return nullptr; }
+  o->open_.assign(max_streams, 0); o->fresh.assign(max_streams, 1); o->finished.assign(max_streams, 0);
+  o->res.assign(max_streams, OnlineResult{});
+  o->paths.assign(max_streams, {});
+  return o;
+}
+
+void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *o) {
+  if (!o) return;
+  if (!UseDevice(o->device)) {
+    if (o->pending) hipEventSynchronize(o->done);
+    hipFree(o->d_state); hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
+    FreeCore(o);
+  }
+  delete o;
+}
+
+int pk_mi355_online_decoder_set_beam(pk_mi355_online_decoder_t *o, float beam, int max_active) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  return SetBeam(o, beam, max_active);
+}
+
+int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
+  int rc = OnlineSlot(o, slot);
+  if (rc) return rc;
+  if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open", slot);
+  if ((rc = OnlineCollect(o))) return rc;       // a result of the slot's last utterance is replaced
+  o->open_[slot] = 1; o->fresh[slot] = 1; o->finished[slot] = 0;
+  o->res[slot] = OnlineResult{};
+  o->paths[slot].clear();
+  return 0;
+}
+
+int pk_mi355_online_decoder_advance_host(pk_mi355_online_decoder_t *o, const int *slots, const pk_decodable_t *chunks,
+                                         const int *final_, int n, int sync) {
+  if (!o || n < 0 || (n > 0 && (!slots || !chunks))) return Fail(PK_MI355_E_INVALID, "bad advance arguments");
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  std::vector<char> seen(o->max_streams, 0);
+  int64_t total = 0;
+  std::vector<OnlineCall> calls(n);
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i];
+    if ((rc = OnlineSlot(o, slot))) return rc;
+    if (!o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not open", slot);
+    if (seen[slot]) return Fail(PK_MI355_E_INVALID, "online decoder: slot %d twice in one call", slot);
+    seen[slot] = 1;
+    const pk_matrix_t &m = chunks[i].log_prob;
+    if ((rc = CheckLoglik(o, m, "online decoder: chunk", i))) return rc;
+    calls[i] = OnlineCall{slot, m.ncol, final_ && final_[i] ? 1 : 0, o->fresh[slot], total};
+    total += (int64_t)m.ncol * o->num_pdfs;
+  }
+  if (o->pending) HIP_TRY(hipEventSynchronize(o->done));     // d_ll may still be read by the previous call
+  if ((rc = UploadLoglik(o, chunks, n))) return rc;
+  if ((rc = OnlineLaunch(o, o->d_ll, calls, o->own_stream))) return rc;
+  return sync ? OnlineCollect(o) : 0;
+}
+
+int pk_mi355_online_decoder_advance(pk_mi355_online_decoder_t *o, pk_mi355_stream_t *s, int sync) {
+  if (!o || !s) return Fail(PK_MI355_E_INVALID, "null online decoder or stream");
+  if (StreamModel(s) != o->am)
+    return Fail(PK_MI355_E_INVALID, "online decoder: the stream scores with another model than the decoder was created for");
+  if (StreamSlots(s) > o->max_streams) return Fail(PK_MI355_E_INVALID, "online decoder: the stream has more slots than the decoder");
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  std::vector<OnlineCall> calls;
+  const float *base = StreamLoglikBase(s);
+  for (int slot = 0; slot < StreamSlots(s); ++slot) {
+    if (!o->open_[slot]) continue;
+    int first = 0, count = 0;
+    const float *p = pk_mi355_stream_loglik_device(s, slot, &first, &count);
+    const bool fin = StreamSlotFlushed(s, slot);
+    if (count == 0 && !fin) continue;
+    calls.push_back(OnlineCall{slot, count, fin ? 1 : 0, o->fresh[slot], count ? (int64_t)(p - base) : 0});
+  }
+  if ((rc = OnlineLaunch(o, base, calls, StreamHipStream(s)))) return rc;
+  return sync ? OnlineCollect(o) : 0;
+}
+
+int pk_mi355_online_decoder_synchronize(pk_mi355_online_decoder_t *o) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  return OnlineCollect(o);
+}
+
+int pk_mi355_online_decoder_partial(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, float *cost) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  if (cost) *cost = o->res[slot].weight;
+  return OnlineWords(o, slot, words, max_words);
+}
+
+int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, float *weight,
+                                   int *ok) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  if (!o->finished[slot] || !o->res[slot].final_) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not finished", slot);
+  if (weight) *weight = o->res[slot].weight;
+  if (ok) *ok = o->res[slot].ok;
+  return OnlineWords(o, slot, words, max_words);
+}
+
+int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, int slot, int32_t *arcs, int max_arcs) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  const auto &p = o->paths[slot];
+  for (int i = 0; i < (int)p.size() && i < max_arcs; ++i) arcs[i] = p[i];
+  return (int)p.size();
+}
+
+int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *o, int slot, pk_mi355_word_t *out, int max) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  const auto &p = o->paths[slot];
+  return WordSegments(o->labels, p.data(), (int)p.size(), nullptr, 0, out, max);   // (the rows are gone: no acoustic cost)
+}
+
+int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *o, int slot) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  return o->res[slot].active_bound;
+}
+
+}  // extern "C"

@@ -7,6 +7,10 @@
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
 //   capi_recognizer.hip  pk_load + pk_process as one object over the entries of the others
+//   capi_decoder.hip     (pk_decode.h) the decoder core -- graph, work areas, arenas -- and the batch decoder over it
+//   capi_online_decoder.hip  (pk_decode.h) the online decoder over the same core
+//   stream.hip           the online scorer: its kernels and its host object
+// (decode.hip holds the decoder's kernels and their launchers, declared in pk_decode.h.)
 // Nothing here is part of the ABI (include/pk_mi355.h is); the library exports the C entries only
 // (libpk_mi355.map).
 #ifndef PK_HOST_H_
@@ -232,11 +236,11 @@ inline ViewGen *GenOf(const pk_mi355_am_t *am) { return reinterpret_cast<ViewGen
 inline pk_mi355_am_t *Untag(pk_mi355_am_t *am) { return IsView(am) ? GenOf(am)->am : am; }
 void ReleaseArenaView(pk_mi355_am_t *handle);
 
-// what the decoder (decode.hip) needs to know of a batch beyond the ABI
+// what the batch decoder (capi_decoder.hip) needs to know of a batch beyond the ABI
 bool BatchScored(const pk_mi355_batch *b);
 const pk_mi355_am *BatchModel(const pk_mi355_batch *b);
 
-// what the online decoder (decode.hip) needs to know of an online scorer (stream.hip) beyond the ABI
+// what the online decoder (capi_online_decoder.hip) needs to know of an online scorer (stream.hip) beyond the ABI
 const pk_mi355_am *StreamModel(const pk_mi355_stream *s);
 int StreamSlots(const pk_mi355_stream *s);
 hipStream_t StreamHipStream(const pk_mi355_stream *s);

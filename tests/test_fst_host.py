@@ -1,5 +1,6 @@
 """Host-only: the graph reader (pk_mi355_fst_*, Fst::Read / CountArcs, fst.cc:29-110) and the decoder
 entries' behaviour without a device.  No GPU needed."""
+import ctypes as C
 import os
 import struct
 
@@ -135,3 +136,38 @@ def test_decoder_entries_fail_loudly_without_gpu():
     with pytest.raises(pk.PkError):          # a model cannot even be finalized without a device
         pk.Decoder(f, pk.AcousticModel([("linear", np.eye(4, dtype=np.float32), np.zeros(4, np.float32))],
                                        prior=np.full(4, 0.25, np.float32)), 1)
+
+
+def test_null_handles_are_invalid_in_every_decoder_entry():
+    """Every pk_mi355_online_decoder_* entry, and the batch decoder's mode and alignment entries, given a null handle
+    (tests/test_decode_gc_host.py has set_trace_gc and trace_stats): checked before any device is touched."""
+    L = pk.lib()
+    f = pk.Fst(os.path.join(G, "testinput.fst"))
+    word, slot0, ll = pk.pk_mi355_word_t(), C.c_int(0), pk.pk_decodable_t()
+    am = L.pk_mi355_am_create()
+    try:
+        for create in (L.pk_mi355_decoder_create, L.pk_mi355_online_decoder_create):
+            for fst_h, am_h in ((None, am), (f.handle, None)):
+                assert not create(fst_h, am_h, 1, 0)
+                assert L.pk_mi355_last_error_code() == E_INVALID and b"null graph or model" in L.pk_mi355_last_error()
+    finally:
+        L.pk_mi355_am_destroy(am)
+    L.pk_mi355_online_decoder_destroy(None)
+    calls = [
+        lambda: L.pk_mi355_online_decoder_set_beam(None, 16.0, 10),
+        lambda: L.pk_mi355_online_decoder_open(None, 0),
+        lambda: L.pk_mi355_online_decoder_advance(None, None, 1),
+        lambda: L.pk_mi355_online_decoder_advance_host(None, C.byref(slot0), C.byref(ll), None, 1, 1),
+        lambda: L.pk_mi355_online_decoder_synchronize(None),
+        lambda: L.pk_mi355_online_decoder_partial(None, 0, None, 0, None),
+        lambda: L.pk_mi355_online_decoder_result(None, 0, None, 0, None, None),
+        lambda: L.pk_mi355_online_decoder_best_path_arcs(None, 0, None, 0),
+        lambda: L.pk_mi355_online_decoder_word_segments(None, 0, C.byref(word), 1),
+        lambda: L.pk_mi355_online_decoder_active_bound(None, 0),
+        lambda: L.pk_mi355_decoder_set_trace_gc(None, 1),
+        lambda: L.pk_mi355_decoder_set_alignment(None, 1),
+        lambda: L.pk_mi355_decoder_alignment(None, 0, None, None, None, 0),
+        lambda: L.pk_mi355_decoder_word_segments(None, 0, C.byref(word), 1),
+    ]
+    for i, call in enumerate(calls):
+        assert call() == E_INVALID and L.pk_mi355_last_error_code() == E_INVALID, i

@@ -1,5 +1,5 @@
-"""The best-path alignment (AlignKernel in csrc/decode.hip, pk_mi355_decoder_set_alignment / _alignment /
-_word_segments): per frame the emitting arc of the best path, its transition-id and its acoustic cost; per word a
+"""The best-path alignment (AlignKernel in csrc/decode.hip, queued by csrc/capi_decoder.hip:
+pk_mi355_decoder_set_alignment / _alignment / _word_segments): per frame the emitting arc of the best path, its transition-id and its acoustic cost; per word a
 segment with its frames and its two costs.  Every expectation is a Python restatement over best_path_arcs, the graph's
 arcs as the test wrote them and the host log-likelihoods -- never the code under test: arc ids are the path's emitting
 arcs in order, acoustic costs the bit patterns of -N1(ll[t, pdf]), segments the rule of include/pk_mi355.h with sums

@@ -1,5 +1,5 @@
-"""The GPU decoder (csrc/decode.hip, pk_mi355_decoder_*): words and weight against the reference's own
-decoder (oracle/_ref/libpkref_decoder.so, where built), an exhaustive Viterbi and a host model of the
+"""The GPU decoder (pk_mi355_decoder_*: kernels in csrc/decode.hip, host object in csrc/capi_decoder.hip): words and
+weight against the reference's own decoder (oracle/_ref/libpkref_decoder.so, where built), an exhaustive Viterbi and a host model of the
 documented semantics (tests/decoder_model.py); every best path re-scored on the host."""
 import ctypes as C
 import os

@@ -1,4 +1,5 @@
-"""The GPU decoder (csrc/decode.hip) at its edges, against the host model of its semantics (tests/decoder_model.py):
+"""The GPU decoder (kernels in csrc/decode.hip, host object in csrc/capi_decoder.hip) at its edges, against the host
+model of its semantics (tests/decoder_model.py):
 general graphs (synth_graph.general) in exact dyadic arithmetic -- a coarse grid where ties are everywhere and a
 fine one where they are rare --, every tie rule, max-active at its boundaries, shapes that cross the 512-lane
 chunks, beam 0 and beam inf, non-finite log-likelihoods (N1 / N2), reuse of a decoder after a

@@ -1,5 +1,5 @@
-"""The batch decoder with trace gc on (pk_mi355_decoder_set_trace_gc, DecodeKernel<true> in csrc/decode.hip): every
-utterance of a call owns trace_capacity // n backtrace records and compacts them as they fill.  Where the records
+"""The batch decoder with trace gc on (pk_mi355_decoder_set_trace_gc in csrc/capi_decoder.hip, DecodeKernel<true> in
+csrc/decode.hip): every utterance of a call owns trace_capacity // n backtrace records and compacts them as they fill.  Where the records
 live must never show: words, weight bits, ok, best-path arcs and active_bound equal the mode-off decoder's, the host
 model's (tests/decoder_model.py) and, where built, the reference decoder's -- at capacities the shared arena cannot
 decode at all.  "Same" below is outcome() of test_gpu_decode_edges: all five."""

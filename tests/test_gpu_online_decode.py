@@ -1,7 +1,9 @@
-"""The online decoder (pk_mi355_online_decoder_*, csrc/decode.hip OnlineDecodeKernel): log-likelihoods fed in chunks
+"""The online decoder (pk_mi355_online_decoder_*: csrc/capi_online_decoder.hip over the decoder core, OnlineDecodeKernel
+in csrc/decode.hip): log-likelihoods fed in chunks
 must end in the words, weight bits, ok, best-path arcs and active_bound of Decoder.decode on the whole utterance;
 partial hypotheses equal the decode of the prefix on graphs whose final weights are 0; compaction of the per-slot
-backtrace arena changes no result; and OnlineScorer + OnlineDecoder equal BatchScorer + Decoder.decode_batch."""
+backtrace arena changes no result; a refused set_beam changes no result; and OnlineScorer + OnlineDecoder equal
+BatchScorer + Decoder.decode_batch."""
 import os
 
 import numpy as np
@@ -13,7 +15,7 @@ from pocketkaldi_amd import synth, synth_graph as SG
 pytestmark = pytest.mark.gpu
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-E_CAPACITY = -6
+E_INVALID, E_CAPACITY = -1, -6
 
 
 def ident_model(num_pdfs):
@@ -142,6 +144,26 @@ def test_nan_and_empty_frames_mid_stream(tmp_path):
     assert want[1][0][2] == 0
     got = online(fst, am, [a, b], [1, "random"], seed=6)
     assert same(got[0], want[0]) and same(got[1], want[1])
+
+
+def test_refused_set_beam_leaves_the_decoder_as_it_was():
+    fst = pk.Fst(os.path.join(G, "testinput.fst"))
+    am = ident_model(4)
+    ll = (np.random.default_rng(11).standard_normal((3, 4)) * 2).astype(np.float32)
+
+    def run(dec):
+        dec.open(0)
+        dec.advance_host({0: (ll, True)})
+        return dec.result(0)
+
+    want = run(pk.OnlineDecoder(fst, am, 1))               # an untouched decoder
+    dec = pk.OnlineDecoder(fst, am, 1)
+    for beam, max_active in ((-1.0, 10), (16.0, 0)):
+        with pytest.raises(pk.PkCodeError) as e:
+            dec.set_beam(beam, max_active)
+        assert e.value.code == E_INVALID
+    got = run(dec)
+    assert got[0] == want[0] and np.float32(got[1]).tobytes() == np.float32(want[1]).tobytes() and got[2] == want[2]
 
 
 # ---------------------------------------------------------------- 3. partials
