@@ -1,25 +1,21 @@
-// capi_exec.hip -- the layer executor (fp32 and split-fp16 walks over the layer stack), the range words of the
-// f16 modes, the single-utterance workspace, and the reference-compatible pk_decodable_* functions
+// capi_exec.hip -- the layer executor (fp32 and split-fp16 walks over the layer stack, and the chunk walk over
+// them), the range words of the f16 modes, the single-utterance workspace, and the reference-compatible pk_decodable_* functions
 // (decodable.h:20-41).  Host C++ over the HIP runtime; no CPU compute path.
 #include <hip/hip_runtime.h>
-#include <ctype.h>
-#include <dlfcn.h>
 #include <math.h>
-#include <cmath>
 
 #include <algorithm>
-#include <string>
 #include <mutex>
-#include <utility>
-#include <unordered_set>
 #include <vector>
 
-#include "pk_host.h"
+#include "pk_score.h"
 
 using namespace pkmi;
 using namespace pkhost;
 
 namespace pkhost {
+
+struct ExecResult { const float *data = nullptr; int64_t ld = 0; int dim = 0; };   // where RunLayers left its result: frame-major rows
 
 int AllocExec(const pk_mi355_am *am, int64_t rows_cap, ExecBufs *e) {
   e->rows_cap = rows_cap;
@@ -115,8 +111,8 @@ int EvalRange(const pk_mi355_am *am, const ExecBufs *const *bufs, int nbufs) {
 //       otherwise the log-likelihood tail is written to tail_out[row * tail_ld].
 int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t ldq,
               int splice_dim, int rows, bool want_tail, float scale, float *tail_out,
-              int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const float *splice_zero,
-              const int32_t *splice_shift) {
+              int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const float *splice_zero = nullptr,
+              const int32_t *splice_shift = nullptr) {
   const int rows_pad = (int)RoundUp(rows, kTile);
   if (splice_dim > 0 && !splice_zero) return Fail(PK_MI355_E_INVALID, "spliced input without a zero source");
   if (rows_pad > e.rows_cap) return Fail(PK_MI355_E_INVALID, "chunk larger than workspace");
@@ -291,7 +287,7 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
 // already checked the layer pattern: (Linear [ReLU])+ [Softmax].
 int RunLayersF16(const pk_mi355_am *am, const ExecBufs &e, const _Float16 *x, int64_t ldx, int rows,
                  bool want_tail, float scale, float *tail_out,
-                 int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const int32_t *row_shift4) {
+                 int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const int32_t *row_shift4 = nullptr) {
   const int rows_pad = (int)RoundUp(rows, kTileF16);
   if (rows_pad > e.rows_cap) return Fail(PK_MI355_E_INVALID, "chunk larger than workspace");
   const float *blob = am->d_blob;
@@ -356,17 +352,34 @@ int RunLayersF16(const pk_mi355_am *am, const ExecBufs &e, const _Float16 *x, in
   return 0;
 }
 
+int WalkChunks(const pk_mi355_am *am, const Operand &op, int64_t total_rows, int64_t chunk, const Lane *lanes, int nlanes,
+               bool want_tail, float scale, float *out, Timer *timer) {
+  const int D = am->feat_dim, N = am->num_pdfs;
+  const bool f16 = IsF16(am->precision);
+  for (int64_t r0 = 0; r0 < total_rows; r0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, total_rows - r0);
+    const Lane &l = lanes[r0 / chunk % nlanes];
+    const int32_t *shift4 = op.shift4 ? op.shift4 + r0 / 4 : nullptr;
+    float *dst = out + r0 * N;
+    const int rc = f16 ? RunLayersF16(am, *l.exec, op.y2 + r0 * 2 * D, 2 * D, rows, want_tail, scale, dst, N, l.stream, timer, nullptr, shift4)
+                       : RunLayers(am, *l.exec, op.yt + r0, op.ld, D, rows, want_tail, scale, dst, N, l.stream, timer, nullptr, op.zero, shift4);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 // Single-utterance workspace used by pk_decodable_init / nnet_propagate.
 struct Workspace {
   ExecBufs exec;
   float *d_feats = nullptr;  int64_t feats_cap = 0;     // frame-major host upload
-  float *d_yt = nullptr;     int64_t yt_ld = 0;          // [feat_dim][yt_ld]
+  float *d_yt = nullptr;     int64_t yt_ld = 0;          // [feat_dim][yt_ld], the last kSingleZeroSpan columns never written
   _Float16 *d_y2 = nullptr;                             // f16x3: interleaved rows [yt_ld][2 feat_dim]
   float *d_out = nullptr;    int64_t out_cap = 0;        // [rows][num_pdfs]
   hipStream_t stream = nullptr;
 };
 
 constexpr int64_t kSingleChunk = 4096;   // frames per pass of the single-utterance path
+const int64_t kSingleZeroSpan = ZeroSpan(0, 0);   // one utterance at column 0: no column shift
 
 int EnsureWorkspace(pk_mi355_am *am, int64_t frames, int width) {
   if (!am->ws) {
@@ -383,7 +396,7 @@ int EnsureWorkspace(pk_mi355_am *am, int64_t frames, int width) {
     HIP_TRY(hipMalloc(&w->d_feats, sizeof(float) * w->feats_cap));
   }
   const int64_t pad = am->left + am->right;
-  const int64_t need_ld = RoundUp(frames + pad, kSingleChunk) + 256;
+  const int64_t need_ld = RoundUp(frames + pad, kSingleChunk) + kSingleZeroSpan;
   if (am->feat_dim > 0 && need_ld > w->yt_ld) {
     hipFree(w->d_yt);
     w->yt_ld = need_ld;
@@ -457,6 +470,20 @@ int CalibrateStep(pk_mi355_am *am, const ExecBufs &e, std::vector<char> *settled
   return 0;
 }
 
+int CalibrateLoop(pk_mi355_am *am, const ExecBufs &e, const std::function<int()> &pass) {
+  const int max_passes = 6 * (int)am->lin.size() + 8;
+  std::vector<char> settled(am->lin.size(), 0);
+  for (int i = 0, rc; i < max_passes; ++i) {
+    if ((rc = pass())) return rc;
+    if (!CalibrateStep(am, e, &settled)) {
+      const ExecBufs *eb = &e;                     // settled: what this last pass wrote must be in range (an operand
+      return EvalRange(am, &eb, 1);                // pinned at the exponent limit is reported, not accepted)
+    }
+    if ((rc = UploadExps(am))) return rc;
+  }
+  return Fail(PK_MI355_E_RANGE, "calibration did not settle in %d passes", max_passes);
+}
+
 }  // namespace pkhost
 
 namespace {
@@ -466,7 +493,7 @@ namespace {
 // range words of the call are zeroed first and collected into the page-locked mirror last.
 int ScoreSingleQueue(pk_mi355_am *am, const pk_matrix_t *feats, bool want_tail, float prob_scale) {
   Workspace *w = am->ws;
-  const int T = feats->ncol, D = feats->nrow, N = am->num_pdfs;
+  const int T = feats->ncol, D = feats->nrow;
   const bool f16 = IsF16(am->precision);
   int rc;
   HIP_TRY(hipMemcpyAsync(w->d_feats, feats->data, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, w->stream));
@@ -475,14 +502,9 @@ int ScoreSingleQueue(pk_mi355_am *am, const pk_matrix_t *feats, bool want_tail, 
     if ((rc = BeginRange(w->exec, w->stream))) return rc;
     LaunchSplitF16(w->d_yt, 1, w->yt_ld, (int)w->yt_ld, D, D, w->d_y2, 2 * D, ExpX(am, 0), RangeOf(w->exec, 0), w->stream);
   }
-  for (int64_t r0 = 0; r0 < T; r0 += kSingleChunk) {
-    const int rows = (int)std::min<int64_t>(kSingleChunk, T - r0);
-    rc = f16 ? RunLayersF16(am, w->exec, w->d_y2 + r0 * 2 * D, 2 * D, rows, want_tail, prob_scale,
-                            w->d_out + r0 * N, N, w->stream, nullptr, nullptr)
-             : RunLayers(am, w->exec, w->d_yt + r0, w->yt_ld, D, rows, want_tail, prob_scale,
-                         w->d_out + r0 * N, N, w->stream, nullptr, nullptr, w->d_yt + (w->yt_ld - 256));
-    if (rc) return rc;
-  }
+  const Operand op{w->d_yt, w->d_y2, w->yt_ld, ZeroSource(w->d_yt, w->yt_ld, kSingleZeroSpan), nullptr};
+  const Lane lane{w->stream, &w->exec};
+  if ((rc = WalkChunks(am, op, T, kSingleChunk, &lane, 1, want_tail, prob_scale, w->d_out, nullptr))) return rc;
   if (f16 && (rc = CollectRange(w->exec, w->stream))) return rc;
   return 0;
 }
@@ -533,10 +555,7 @@ int pk_mi355_nnet_propagate(pk_mi355_am_t *am, const pk_matrix_t *in, pk_matrix_
 
 void pk_decodable_init(pk_decodable_t *self, pk_mi355_am_t *am, float prob_scale,
                        const pk_matrix_t *feats) {
-  self->log_prob.ncol = 0;
-  self->log_prob.nrow = 0;
-  self->log_prob.data = nullptr;
-  self->am = am;
+  ClearDecodable(self, am);
   if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return; }
   if (!feats || feats->nrow != am->feat_dim) {
     Fail(PK_MI355_E_INVALID, "features have %d rows, the model expects %d", feats ? feats->nrow : -1, am->feat_dim);
@@ -584,10 +603,7 @@ void pk_decodable_destroy(pk_decodable_t *self) {
   // the batch's page-locked arena (tagged handle) and owns nothing.
   if (IsView(self->am)) ReleaseArenaView(self->am);
   else free(self->log_prob.data);
-  self->log_prob.data = nullptr;
-  self->log_prob.nrow = 0;
-  self->log_prob.ncol = 0;
-  self->am = nullptr;
+  ClearDecodable(self, nullptr);
 }
 
 float pk_decodable_loglikelihood(pk_decodable_t *self, int frame, int trans_id) {
@@ -611,19 +627,11 @@ int pk_mi355_am_calibrate(pk_mi355_am_t *am, const pk_matrix_t *feats) {
   std::lock_guard<std::mutex> lock(am->mu);
   if ((rc = EnsureWorkspace(am, feats->ncol, feats->nrow))) return rc;
   if (am->exps_stale && (rc = RefreshExps(am))) return rc;
-  Workspace *w = am->ws;
-  const int max_passes = 6 * (int)am->lin.size() + 8;
-  std::vector<char> settled(am->lin.size(), 0);
-  for (int pass = 0; pass < max_passes; ++pass) {
-    if ((rc = ScoreSingleQueue(am, feats, false, 1.0f))) return rc;
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    if (!CalibrateStep(am, w->exec, &settled)) {
-      const ExecBufs *eb = &w->exec;               // settled: what this last pass wrote must be in range (an operand
-      return EvalRange(am, &eb, 1);                // pinned at the exponent limit is reported, not accepted)
-    }
-    if ((rc = UploadExps(am))) return rc;
-  }
-  return Fail(PK_MI355_E_RANGE, "calibration did not settle in %d passes", max_passes);
+  return CalibrateLoop(am, am->ws->exec, [&]() -> int {
+    if (int rc = ScoreSingleQueue(am, feats, false, 1.0f)) return rc;
+    HIP_TRY(hipStreamSynchronize(am->ws->stream));
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -1,0 +1,310 @@
+// capi_stream.hip -- the online scorer (pk_mi355_stream_*): live PCM pushed in chunks per slot, and every step scores,
+// for every slot, the frames that became final since the last step.  Host C++ over the HIP runtime; the kernels that
+// carry a slot's state from one step to the next are in stream.hip, and why the result is exact is told there
+// (DESIGN.md section 10 walks through one step).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "pk_score.h"
+
+using namespace pkmi;
+using namespace pkhost;
+
+namespace {
+enum SlotState { kFree = 0, kOpen = 1, kClosed = 2 };
+
+struct Slot {
+  int state = kFree;
+  int n = 0;               // CMVN frames computed
+  int a = 0;               // frames scored (the next row to score)
+  int tail_len = 0;
+  int tail_par = 0;
+  std::vector<float> pending;   // pushed since the last step
+  // the last step's rows of this slot
+  int last_first = 0, last_count = 0;
+  int64_t last_out = 0;
+  bool last_flushed = false;     // the last step was the slot's final one
+};
+
+}  // namespace
+
+struct pk_mi355_stream {
+  ScorerCore core;                    // model, stream, front-end tables, Yt, log-likelihood rows, layer buffers
+  int max_streams = 0;
+  int64_t max_step_samples = 0, pending_total = 0;
+  std::vector<Slot> slots;
+  int hist_len = 1;                   // max(L + R, 1)
+  int64_t wave_cap = 0;
+  // per-slot state in HBM
+  float *d_tails = nullptr;           // [slots][2][kTailCap]
+  float *d_sums = nullptr;            // [slots][40]
+  float *d_raw_hist = nullptr;        // [slots][600][40]
+  float *d_hist = nullptr;            // [slots][hist_len][40]
+  // per-step staging
+  float *h_upload = nullptr, *d_upload = nullptr;    // pushed samples, page-locked -> HBM
+  float *d_wave = nullptr;            // segments
+  float *d_rows = nullptr;            // raw -> CMVN'd rows of the step's new frames
+  char *h_meta = nullptr, *d_meta = nullptr;          // records, UttLayout arrays, column shifts
+  size_t meta_bytes = 0;
+  hipEvent_t ev_staged = nullptr;     // the last step's uploads have left the page-locked buffers
+  bool staged = false;
+};
+
+namespace {
+int SlotIndex(const pk_mi355_stream *s, int slot) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  if (slot < 0 || slot >= s->max_streams) return Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, s->max_streams);
+  return 0;
+}
+}  // namespace
+
+namespace pkhost {
+const pk_mi355_am *StreamModel(const pk_mi355_stream *s) { return s->core.am; }
+int StreamSlots(const pk_mi355_stream *s) { return s->max_streams; }
+hipStream_t StreamHipStream(const pk_mi355_stream *s) { return s->core.stream; }
+const float *StreamLoglikBase(const pk_mi355_stream *s) { return s->core.d_ll; }
+bool StreamSlotFlushed(const pk_mi355_stream *s, int slot) { return slot >= 0 && slot < s->max_streams && s->slots[slot].last_flushed; }
+}  // namespace pkhost
+
+extern "C" {
+
+pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples) {
+  if (!am) { Fail(PK_MI355_E_INVALID, "null model"); return nullptr; }
+  if (am->precision != PK_MI355_PRECISION_F32) {
+    Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
+    return nullptr;
+  }
+  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
+  if (!global_stats41 || max_streams <= 0 || max_step_samples <= 0 || max_step_samples > (int64_t)1 << 30) {
+    Fail(PK_MI355_E_INVALID, "bad stream capacity");
+    return nullptr;
+  }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_stream *s = new pk_mi355_stream();
+  ScorerCore &c = s->core;
+  s->max_streams = max_streams; s->max_step_samples = max_step_samples;
+  s->slots.resize(max_streams);
+  const int pad = am->left + am->right;
+  s->hist_len = std::max(pad, 1);
+  // a slot's segment holds at most 399 carried samples and its pushes; its rows are its new frames and the (at most R)
+  // frames held back for look-ahead, padded to four
+  s->wave_cap = max_step_samples + (int64_t)max_streams * kTailCap;
+  const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
+  CreateCheck chk{"stream_create"};
+  CreateScorerCore(&c, am, global_stats41, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
+                  sizeof(int32_t) * Shift4Cap(c.max_cols);
+  chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
+  chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
+  chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
+  chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * kNumBins));
+  chk(hipMalloc(&s->d_hist, sizeof(float) * max_streams * s->hist_len * kNumBins));
+  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * max_step_samples, hipHostMallocDefault));
+  chk(hipMalloc(&s->d_upload, sizeof(float) * max_step_samples));
+  chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
+  chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
+  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
+  chk(hipMalloc(&s->d_meta, s->meta_bytes));
+  if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
+  return s;
+}
+
+void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
+  if (!s) return;
+  hipSetDevice(s->core.device);
+  if (s->core.stream) hipStreamSynchronize(s->core.stream);
+  hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist);
+  hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta);
+  if (s->h_upload) hipHostFree(s->h_upload);
+  if (s->h_meta) hipHostFree(s->h_meta);
+  if (s->ev_staged) hipEventDestroy(s->ev_staged);
+  FreeScorerCore(&s->core);
+  delete s;
+}
+
+int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  Slot &z = s->slots[slot];
+  if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
+  z.state = kOpen;
+  z.n = z.a = z.tail_len = 0;
+  z.pending.clear();
+  return 0;
+}
+
+int pk_mi355_stream_push(pk_mi355_stream_t *s, int slot, const float *samples, int num_samples) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  Slot &z = s->slots[slot];
+  if (z.state != kOpen) return Fail(PK_MI355_E_STATE, "slot %d is not open", slot);
+  if (num_samples < 0 || (num_samples > 0 && !samples)) return Fail(PK_MI355_E_INVALID, "bad samples");
+  if (s->pending_total + num_samples > s->max_step_samples)
+    return Fail(PK_MI355_E_INVALID, "push of %d samples exceeds the step capacity (%lld pending of %lld)", num_samples,
+                (long long)s->pending_total, (long long)s->max_step_samples);
+  z.pending.insert(z.pending.end(), samples, samples + num_samples);
+  s->pending_total += num_samples;
+  return 0;
+}
+
+int pk_mi355_stream_push_i16(pk_mi355_stream_t *s, int slot, const int16_t *samples, int num_samples) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  if (num_samples < 0 || (num_samples > 0 && !samples)) return Fail(PK_MI355_E_INVALID, "bad samples");
+  std::vector<float> f(samples, samples + num_samples);    // exact: 16-bit integers
+  return pk_mi355_stream_push(s, slot, f.data(), num_samples);
+}
+
+int pk_mi355_stream_close(pk_mi355_stream_t *s, int slot) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  Slot &z = s->slots[slot];
+  if (z.state != kOpen) return Fail(PK_MI355_E_STATE, "slot %d is not open", slot);
+  z.state = kClosed;
+  return 0;
+}
+
+int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  ScorerCore &c = s->core;
+  int rc = UseDevice(c.device);
+  if (rc) return rc;
+  pk_mi355_am *am = c.am;
+  const int L = am->left, R = am->right, pad = L + R;
+  bool any = false;
+  for (const Slot &z : s->slots) any = any || z.state != kFree;
+  if (!any) return Fail(PK_MI355_E_STATE, "step with no open slot");
+  if (s->staged) HIP_TRY(hipEventSynchronize(s->ev_staged));   // the page-locked staging is free again
+  s->staged = false;
+  for (Slot &z : s->slots) { z.last_count = 0; z.last_flushed = false; }   // a step's rows are readable until the next step
+  // ---- the step's plan, on the host
+  StreamRec *recs = reinterpret_cast<StreamRec *>(s->h_meta);
+  char *lay_base = s->h_meta + RoundUp(sizeof(StreamRec) * s->max_streams, 256);
+  const size_t shift4_at = s->meta_bytes - sizeof(int32_t) * Shift4Cap(c.max_cols);
+  std::vector<int> who, flushed;                      // slots taking part; closed slots with nothing left
+  int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0;
+  int max_m = 0;
+  std::vector<ShiftSpan> spans;                       // (end row, column shift) per slot with rows
+  for (int slot = 0; slot < s->max_streams; ++slot) {
+    const Slot &z = s->slots[slot];
+    if (z.state == kFree) continue;
+    const bool closed = z.state == kClosed;
+    const int new_len = (int)z.pending.size();
+    const int seg = z.tail_len + new_len;
+    const int m = pk_mi355_num_frames(seg);
+    const int n = z.n + m;
+    const int b = closed ? n : std::max(z.a, n - R);    // open: R frames of look-ahead held back
+    if (new_len == 0 && m == 0 && b == z.a) {
+      if (closed) flushed.push_back(slot);
+      continue;
+    }
+    StreamRec &r = recs[who.size()];
+    r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
+    r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
+    r.woff = woff; r.new_off = upl; r.raw_base = raw;
+    r.col_base = 0; r.cols = 0;
+    if (b > z.a) {
+      // Rows slot after slot, each padded to four; the slot's columns a - L .. b + R - 1 in a region of RoundUp(b - a, 4)
+      // + L + R columns.  The column of row j is j + (the number of earlier slots with rows) x (L + R): never negative.
+      // (The batch scorer's compact rows pad the rows but not the columns: their shift goes negative when L + R < 3.)
+      const int32_t shift = (int32_t)(col - out);
+      r.col_base = col;
+      r.cols = (int)RoundUp(b - z.a, 4) + pad;
+      out += RoundUp(b - z.a, 4);
+      col += r.cols;
+      spans.push_back({out, shift});
+    }
+    woff += seg; upl += new_len; raw += m;
+    max_m = std::max(max_m, m);
+    who.push_back(slot);
+  }
+  if (woff > s->wave_cap || raw > c.max_frames || RoundUp(out, kTileF16) > c.max_cols || col > c.max_cols)
+    return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
+  // the column shift of every group of four rows (the groups past the last row keep the last shift)
+  const int64_t total_rows = out;
+  int32_t bad = 0;
+  if (total_rows > 0 && !ExpandShift4(spans, total_rows, c.zero_span, reinterpret_cast<int32_t *>(s->h_meta + shift4_at), &bad))
+    return Fail(PK_MI355_E_INVALID, "internal: column shift %d outside [0, %lld]", bad, (long long)(c.zero_span - kTile));
+  // the plan holds: consume every pushed sample, advance the slots
+  for (size_t k = 0; k < who.size(); ++k) {
+    const StreamRec &r = recs[k];
+    Slot &z = s->slots[r.slot];
+    if (r.new_len) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * r.new_len);
+    z.pending.clear();
+    z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
+    z.tail_par ^= 1;
+    z.n = r.n_old + r.m;
+    z.a = r.b;
+    z.last_first = r.a; z.last_count = r.b - r.a;
+    if (z.state == kClosed) { z.state = kFree; z.last_flushed = true; }   // flushed: the slot may be opened again
+  }
+  for (int slot : flushed) { s->slots[slot].state = kFree; s->slots[slot].last_flushed = true; }
+  s->pending_total = 0;
+  {
+    int64_t o = 0;
+    for (size_t k = 0; k < who.size(); ++k) {
+      Slot &z = s->slots[recs[k].slot];
+      z.last_out = o;
+      o += RoundUp(z.last_count, 4);
+    }
+  }
+  const int K = (int)who.size();
+  if (K == 0) return sync ? pk_mi355_stream_synchronize(s) : 0;
+  // UttLayout arrays
+  int64_t *h_woff = reinterpret_cast<int64_t *>(lay_base);
+  int64_t *h_rawb = h_woff + s->max_streams;
+  int32_t *h_T = reinterpret_cast<int32_t *>(h_rawb + s->max_streams);
+  for (int k = 0; k < K; ++k) { h_woff[k] = recs[k].woff; h_rawb[k] = recs[k].raw_base; h_T[k] = recs[k].m; }
+  // ---- uploads (one for the samples, one for the plan) and the launches, all on the stream
+  if (upl) HIP_TRY(hipMemcpyAsync(s->d_upload, s->h_upload, sizeof(float) * upl, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipMemcpyAsync(s->d_meta, s->h_meta, s->meta_bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipEventRecord(s->ev_staged, c.stream));
+  s->staged = true;
+  const StreamRec *d_recs = reinterpret_cast<const StreamRec *>(s->d_meta);
+  const char *d_lay = s->d_meta + (lay_base - s->h_meta);
+  const int64_t *d_woff = reinterpret_cast<const int64_t *>(d_lay);
+  const int64_t *d_rawb = d_woff + s->max_streams;
+  const int32_t *d_T = reinterpret_cast<const int32_t *>(d_rawb + s->max_streams);
+  LaunchStreamAssemble(d_recs, K, s->d_upload, s->d_tails, s->d_wave, c.stream);
+  UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
+  LaunchFbank(s->d_wave, nullptr, lay, K, max_m, c.d_tables, s->d_rows, c.stream);
+  LaunchStreamCmvn(d_recs, K, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
+                   c.d_yt, c.ldy, c.stream);
+  const Operand op{c.d_yt, nullptr, c.ldy, ZeroSource(c), reinterpret_cast<const int32_t *>(s->d_meta + shift4_at)};
+  const Lane lane{c.stream, &c.exec};
+  if ((rc = WalkChunks(am, op, total_rows, c.chunk, &lane, 1, true, prob_scale, c.d_ll, nullptr))) return rc;
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return Fail(PK_MI355_E_DEVICE, "stream step launch failed: %s", hipGetErrorString(le));
+  if (sync) return pk_mi355_stream_synchronize(s);
+  return 0;
+}
+
+int pk_mi355_stream_synchronize(pk_mi355_stream_t *s) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  HIP_TRY(hipStreamSynchronize(s->core.stream));
+  return 0;
+}
+
+const float *pk_mi355_stream_loglik_device(const pk_mi355_stream_t *s, int slot, int *first_frame, int *count) {
+  if (first_frame) *first_frame = 0;
+  if (count) *count = 0;
+  if (SlotIndex(s, slot)) return nullptr;
+  const Slot &z = s->slots[slot];
+  if (first_frame) *first_frame = z.last_first;
+  if (count) *count = z.last_count;
+  return z.last_count > 0 ? s->core.d_ll + z.last_out * s->core.am->num_pdfs : nullptr;
+}
+
+int pk_mi355_stream_fetch(pk_mi355_stream_t *s, int slot, pk_decodable_t *out, int *first_frame) {
+  int rc = SlotIndex(s, slot);
+  if (rc) return rc;
+  if (!out) return Fail(PK_MI355_E_INVALID, "null decodable");
+  if ((rc = UseDevice(s->core.device))) return rc;
+  int count = 0, first = 0;
+  const float *src = pk_mi355_stream_loglik_device(s, slot, &first, &count);
+  if (first_frame) *first_frame = first;
+  ClearDecodable(out, s->core.am);
+  if (count == 0) return 0;
+  return FetchRows(src, count, s->core.am->num_pdfs, s->core.stream, "stream fetch", out, [] { return 0; });
+}
+
+}  // extern "C"

@@ -2,15 +2,16 @@
 //   pk_files.cc          (plain C++, pk_files.h) the error state and every file reader: model / config / WAV / graph,
 //                        the graph's split into the decoder's arc lists
 //   capi_model.hip       device selection, model construction, operand exponents
-//   capi_exec.hip        the layer executor, the single-utterance workspace, pk_decodable_*
-//   capi_batch.hip       the batched device-resident scorer, result arenas and views
+//   capi_exec.hip        the layer executor and (pk_score.h) the chunk walk over it, the single-utterance workspace, pk_decodable_*
+//   capi_batch.hip       (pk_score.h) the scorer core, the batched device-resident scorer over it, result arenas and views
+//   capi_stream.hip      (pk_score.h) the online scorer over the same core
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
 //   capi_recognizer.hip  pk_load + pk_process as one object over the entries of the others
 //   capi_decoder.hip     (pk_decode.h) the decoder core -- graph, work areas, arenas -- and the batch decoder over it
 //   capi_online_decoder.hip  (pk_decode.h) the online decoder over the same core
-//   stream.hip           the online scorer: its kernels and its host object
-// (decode.hip holds the decoder's kernels and their launchers, declared in pk_decode.h.)
+// (decode.hip and stream.hip hold the decoder's and the online scorer's kernels and their launchers, declared in
+// pk_decode.h and pk_score.h.)
 // Nothing here is part of the ABI (include/pk_mi355.h is); the library exports the C entries only
 // (libpk_mi355.map).
 #ifndef PK_HOST_H_
@@ -179,13 +180,6 @@ struct ExecBufs {
 int AllocExec(const pk_mi355_am *am, int64_t rows_cap, ExecBufs *e);
 void FreeExec(ExecBufs *e);
 
-// Where the result of RunLayers ended up.
-struct ExecResult {
-  const float *data = nullptr;   // frame-major rows
-  int64_t ld = 0;
-  int dim = 0;
-};
-
 // ---- f16x3 / f16 operand exponents and range words
 inline const int32_t *ExpBase(const pk_mi355_am *am) { return reinterpret_cast<const int32_t *>(am->d_blob + am->exp_off); }
 inline const int32_t *ExpW(const pk_mi355_am *am, int l) { return ExpBase(am) + l; }
@@ -201,20 +195,7 @@ constexpr float kRangeTooSmall = 0.03125f;       // 2^-5: below this every lo ha
 int BeginRange(const ExecBufs &e, hipStream_t s);
 int CollectRange(const ExecBufs &e, hipStream_t s);
 void ClearHostRange(const ExecBufs &e);          // a lane that took no part in a call must not contribute stale maxima
-float RangeMax(const ExecBufs &e, int l);
 int EvalRange(const pk_mi355_am *am, const ExecBufs *const *bufs, int nbufs);
-int CalibrateStep(pk_mi355_am *am, const ExecBufs &e, std::vector<char> *settled);
-
-// splice_zero (spliced input only): zero floats in the same allocation as q0 (128 + the largest column shift of them) --
-// the tail of feature row 0 of every Yt this library allocates is never written.  splice_shift: GemmArgs::splice_shift
-int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t ldq,
-              int splice_dim, int rows, bool want_tail, float scale, float *tail_out,
-              int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const float *splice_zero = nullptr,
-              const int32_t *splice_shift = nullptr);
-int RunLayersF16(const pk_mi355_am *am, const ExecBufs &e, const _Float16 *x, int64_t ldx, int rows,
-                 bool want_tail, float scale, float *tail_out,
-                 int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const int32_t *row_shift4 = nullptr);
-
 void FreeWorkspace(Workspace *w);
 int ResizeHostMatrix(pk_matrix_t *m, int nrow, int ncol);
 
@@ -240,7 +221,7 @@ void ReleaseArenaView(pk_mi355_am_t *handle);
 bool BatchScored(const pk_mi355_batch *b);
 const pk_mi355_am *BatchModel(const pk_mi355_batch *b);
 
-// what the online decoder (capi_online_decoder.hip) needs to know of an online scorer (stream.hip) beyond the ABI
+// what the online decoder (capi_online_decoder.hip) needs to know of an online scorer (capi_stream.hip) beyond the ABI
 const pk_mi355_am *StreamModel(const pk_mi355_stream *s);
 int StreamSlots(const pk_mi355_stream *s);
 hipStream_t StreamHipStream(const pk_mi355_stream *s);

@@ -1,0 +1,113 @@
+// pk_score.h -- what crosses between the online scorer's kernels (stream.hip) and its host object (capi_stream.hip),
+// and what the scorers share: the scorer core and the one copy of the operand layout, the span expansion, the chunk
+// walk, the calibration loop and the way rows become a host decodable (internal).
+#ifndef PK_SCORE_H_
+#define PK_SCORE_H_
+
+#include <functional>
+
+#include "pk_host.h"
+
+namespace pkmi {
+
+constexpr int kTailCap = kFrameLength;     // a carried tail holds at most 399 samples (fewer than one frame's 400)
+
+// One slot's share of a step (device array, one entry per slot taking part).
+struct StreamRec {
+  int32_t slot;
+  int32_t tail_len;    // samples carried from earlier steps (global samples 160 n_old ...)
+  int32_t new_len;     // samples pushed since the last step
+  int32_t tail_par;    // the slot's tail buffer that holds the carried samples (the step writes the other one)
+  int32_t n_old;       // CMVN frames computed before this step
+  int32_t m;           // frames this step computes: n_old .. n_old + m - 1
+  int32_t a, b;        // rows scored: frames [a, b)
+  int32_t closed;      // 1: the right edge is the last frame (am.cc:73-75)
+  int32_t cols;        // columns of the slot's region of Yt: RoundUp(b - a, 4) + L + R (0: no rows)
+  int64_t woff;        // first sample of the segment in the wave staging
+  int64_t new_off;     // first pushed sample in the upload staging
+  int64_t raw_base;    // first row of the slot's new frames in the step's raw rows
+  int64_t col_base;    // first column of the slot's region of Yt
+};
+
+// launchers (stream.hip): one workgroup (StreamAssembleKernel) / one wavefront (StreamCmvnKernel) for each of n records
+void LaunchStreamAssemble(const StreamRec *recs, int n, const float *upload, float *tails, float *wave, hipStream_t stream);
+void LaunchStreamCmvn(const StreamRec *recs, int n, float *rows, const float *g, const CmvnTables *tab, float *sums,
+                      float *raw_hist, float *hist, int hist_len, int left, int right, float *yt, int64_t ldy, hipStream_t stream);
+
+}  // namespace pkmi
+
+namespace pkhost {
+
+// ------------------------------------------------------------------ scorer core (capi_batch.hip)
+// What the batch and the online scorer both are: the front-end tables on the device, the first layer's feature-major
+// operand Yt with its zero span, the log-likelihood rows and one set of layer buffers, on one stream.  A row of Yt is
+// RoundUp(max_cols, chunk) columns (whole passes), 256 of slack behind them, then zero_span columns nobody writes: the
+// padding rows of the spliced operand read zeros there, at their column shift (at most `pad` columns per unit).
+struct ScorerCore {
+  pk_mi355_am *am = nullptr; int device = 0; hipStream_t stream = nullptr;
+  FrontendTables *d_tables = nullptr; float *d_global = nullptr; CmvnTables *d_cmvn_tab = nullptr;   // front-end tables
+  int64_t max_frames = 0, max_cols = 0, chunk = 0, zero_span = 0, ldy = 0;
+  float *d_yt = nullptr, *d_ll = nullptr;   // [feat_dim][ldy], [max_cols][num_pdfs]
+  ExecBufs exec;
+};
+
+inline int64_t ZeroSpan(int64_t units, int pad) { return RoundUp(units * pad + 2 * kTile, 256); }
+inline const float *ZeroSource(const float *yt, int64_t ld, int64_t zero_span) { return yt + (ld - zero_span); }
+inline const float *ZeroSource(const ScorerCore &c) { return ZeroSource(c.d_yt, c.ldy, c.zero_span); }
+
+// The first HIP failure of a create entry becomes its fail text; the entry goes on and destroys the object at its end.
+struct CreateCheck {
+  const char *name; bool ok = true;
+  void operator()(hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "%s: %s", name, hipGetErrorString(e)); } }
+};
+// On the selected device (am's): `units` utterances or slots of at most max_frames frames and max_rows rows of the
+// layer stack together, passes of at most chunk_cap rows.  On failure (chk.ok false) the caller still calls FreeScorerCore.
+void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats41, int units, int64_t max_frames,
+                      int64_t max_rows, int64_t chunk_cap, CreateCheck &chk);
+void FreeScorerCore(ScorerCore *c);             // (the owner has waited for the stream)
+
+// ------------------------------------------------------------------ column shifts (capi_batch.hip)
+// Spans of rows (a multiple of four each) with one column shift -> one entry per group of four rows, for every row a
+// tile of the layer stack can touch (the last tile's padding rows and the rows past a span's last frame read real
+// memory and are ignored); the groups past the last span keep the last shift.  False, *bad (if given) = the shift, when one lies
+// outside [0, zero_span - kTile]: a negative one would wrap in the kernels' unsigned lane offsets.
+struct ShiftSpan { int64_t end_row; int32_t shift; };
+inline int64_t Shift4Groups(int64_t total_rows) { return RoundUp(total_rows, kTileF16) / 4 + kTileF16 / 4; }
+// entries of a scorer's host and device arrays: total_rows <= max_cols, a multiple of kTileF16, so Shift4Groups <=
+// max_cols / 4 + kTileF16 / 4 (the rest is slack)
+inline int64_t Shift4Cap(int64_t max_cols) { return max_cols / 4 + kTileF16; }
+bool ExpandShift4(const std::vector<ShiftSpan> &spans, int64_t total_rows, int64_t zero_span, int32_t *shift4, int32_t *bad);
+
+// ------------------------------------------------------------------ chunk walk (capi_exec.hip)
+// The spliced first-layer operand: Yt [feat_dim][ld] or (f16 modes) its split copy [ld][2 feat_dim].  zero: zero floats
+// in the same allocation as yt (128 + the largest column shift of them) -- the tail of feature row 0 of every Yt this
+// library allocates is never written.  shift4: GemmArgs::splice_shift, or null.
+struct Operand { const float *yt; const _Float16 *y2; int64_t ld; const float *zero; const int32_t *shift4; };
+struct Lane { hipStream_t stream; const ExecBufs *exec; };
+// RunLayers / RunLayersF16 over rows [0, total_rows), `chunk` at a time, chunk k on lane k % nlanes; row r at out + r * num_pdfs
+int WalkChunks(const pk_mi355_am *am, const Operand &op, int64_t total_rows, int64_t chunk, const Lane *lanes, int nlanes,
+               bool want_tail, float scale, float *out, Timer *timer);
+
+// ------------------------------------------------------------------ calibration (capi_exec.hip), rows to the host
+// pass(): queue one scoring pass and synchronise, so that e's range words are the pass's.
+int CalibrateLoop(pk_mi355_am *am, const ExecBufs &e, const std::function<int()> &pass);
+
+inline void ClearDecodable(pk_decodable_t *out, pk_mi355_am_t *am) { out->am = am; out->log_prob = pk_matrix_t{0, 0, nullptr}; }
+// rows x N floats at src -> a malloc'd matrix in *out (pk_decodable_destroy frees it); verdict() may still withhold
+// them once the stream has been synchronised.  `what` names the entry in the fail text.
+template <class Verdict>
+int FetchRows(const float *src, int rows, int N, hipStream_t stream, const char *what, pk_decodable_t *out, Verdict verdict) {
+  const size_t bytes = sizeof(float) * (size_t)rows * N;
+  float *host = static_cast<float *>(malloc(bytes));
+  if (!host) return Fail(PK_MI355_E_INVALID, "out of host memory");
+  hipError_t e = hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { free(host); return Fail(PK_MI355_E_DEVICE, "%s: %s", what, hipGetErrorString(e)); }
+  if (int rc = verdict()) { free(host); return rc; }
+  out->log_prob = pk_matrix_t{rows, N, host};
+  return 0;
+}
+
+}  // namespace pkhost
+
+#endif  // PK_SCORE_H_

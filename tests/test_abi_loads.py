@@ -168,6 +168,44 @@ def test_broadcast_entry_reports_misuse_without_gpu():
         L.pk_mi355_am_destroy(am)
 
 
+def test_null_batch_is_an_error_not_a_crash():
+    """Every pk_mi355_batch_* entry with a null handle: its error code (the three const getters: 0, the two pointer
+    getters: null), nothing dereferenced.  tests/test_stream_host.py holds the online scorer's counterpart."""
+    import ctypes as C
+    L = pk.lib()
+    E_INVALID, E_STATE = -1, -4
+    f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    x, n = np.zeros(16, np.float32), np.array([16], np.int32)
+    ms, launches = (C.c_float * 16)(), (C.c_int * 16)()
+    d = pk.pk_decodable_t()
+    assert not L.pk_mi355_batch_create(None, x.ctypes.data_as(f32p), 1, 16)
+    assert L.pk_mi355_last_error_code() == E_STATE
+    wave = pk.pk_vector_t(16, x.ctypes.data_as(f32p))
+    assert L.pk_mi355_batch_set_waves(None, C.byref(wave), 1) == E_INVALID
+    assert L.pk_mi355_batch_set_waves_i16(None, np.zeros(16, np.int16).ctypes.data_as(C.POINTER(C.c_int16)), n.ctypes.data_as(i32p), 1) == E_INVALID
+    assert L.pk_mi355_batch_set_waves_device(None, None, n.ctypes.data_as(i32p), 1) == E_INVALID
+    assert L.pk_mi355_batch_score(None, 0.1, 1) == E_INVALID
+    assert L.pk_mi355_batch_synchronize(None) == E_INVALID
+    assert L.pk_mi355_batch_calibrate(None) == E_INVALID
+    assert L.pk_mi355_batch_num_utts(None) == 0
+    assert L.pk_mi355_batch_num_frames(None, 0) == 0
+    assert L.pk_mi355_batch_total_frames(None) == 0
+    assert not L.pk_mi355_batch_loglik_device(None, 0)
+    assert L.pk_mi355_batch_fetch(None, 0, C.byref(d)) == E_INVALID
+    assert L.pk_mi355_batch_fetch_all(None, C.byref(d), 1, 1) == E_INVALID
+    assert L.pk_mi355_batch_fetch_fbank(None, 0, x.ctypes.data_as(f32p)) == E_INVALID
+    assert L.pk_mi355_batch_fetch_cmvn(None, 0, x.ctypes.data_as(f32p)) == E_INVALID
+    assert L.pk_mi355_batch_gather_loglik(None, 0, None, None, 0, None) == E_INVALID
+    assert not L.pk_mi355_batch_stream(None)
+    assert L.pk_mi355_batch_enable_timing(None, 1) == E_INVALID
+    assert L.pk_mi355_batch_get_timing(None, ms, launches) == E_INVALID
+    assert sorted(e for e in pk.EXPORTS if e.startswith("pk_mi355_batch_")) == sorted(
+        "pk_mi355_batch_" + e for e in ("create", "destroy", "set_waves", "set_waves_i16", "set_waves_device", "score", "synchronize",
+                                        "calibrate", "num_utts", "num_frames", "total_frames", "loglik_device", "fetch", "fetch_all",
+                                        "fetch_fbank", "fetch_cmvn", "gather_loglik", "stream", "enable_timing", "get_timing"))
+    L.pk_mi355_batch_destroy(None)
+
+
 def test_readers_survive_mutated_files(tmp_path):
     """The host-side readers parse files a caller hands them (pcm_reader.cc:45-220, nnet.cc:80-147, vector.cc:393-425):
     truncated, bit-flipped, length-field-poisoned and over-long variants of the reference-written model files and of the

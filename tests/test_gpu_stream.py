@@ -1,4 +1,4 @@
-"""The online scorer (csrc/stream.hip, pk_mi355_stream_*): PCM pushed in chunks, scored step by step as frames become
+"""The online scorer (csrc/capi_stream.hip, pk_mi355_stream_*): PCM pushed in chunks, scored step by step as frames become
 final.  Every frame's log-likelihoods must equal the batch scorer's on the whole wave bit for bit, whatever the chunk
 sizes, with many slots in one object opened and closed at different steps and reused."""
 import os
@@ -258,3 +258,74 @@ def test_f16_models_are_refused():
     with pytest.raises(pk.PkCodeError) as e:
         pk.OnlineScorer(am, g, 1, 1000)
     assert e.value.code == E_INVALID
+
+
+# ---------------------------------------------------------------- 3. both scorers exactly at their capacity
+
+FULL_LENGTHS = [0, 399, 400, 560, 720, 880, 1040, 1360, 1680]       # 0, 0, 1, 2, 3, 4, 5, 7 and 9 frames
+_alone = {}
+
+
+def scored_alone(which, softmax, am, g, n):
+    """Utterance u of the full batch (FULL_LENGTHS in turn), scored alone in a fresh one-utterance BatchScorer: made
+    once per model and softmax, shared by the cases below and left unchanged."""
+    waves, rows = _alone.setdefault((which, softmax), ([], []))
+    for u in range(len(waves), n):
+        waves.append(synth.utterance(1100 + u, seconds=0.2)[:FULL_LENGTHS[u % len(FULL_LENGTHS)]])
+        rows.append(batch_rows(am, g, [waves[u]])[0])
+    return waves[:n], rows[:n]
+
+
+@pytest.mark.parametrize("max_utts", [48, 96])
+@pytest.mark.parametrize("lanes", ["1", "2"])
+@pytest.mark.parametrize("softmax", ["stable", "reference"])
+@pytest.mark.parametrize("which", ["refmodel", "S"])
+def test_batch_exactly_full_equals_each_utterance_alone(which, softmax, lanes, max_utts, monkeypatch):
+    """A batch scorer filled to both of its capacities (max_utts utterances, max_total_samples = the exact sum of the
+    lengths) with empty, one-frame and not-a-multiple-of-four utterances, so that the column shift changes every few
+    compact rows.  PK_MI355_CHUNK=128 is rounded up to the 256-row tile of the f16 kernels, and 48 utterances make 224
+    compact rows: one pass, not full.  96 utterances make 456: two passes, the second not full, and with
+    PK_MI355_LANES=2 one on each lane."""
+    layers, prior, L, R, tid2pdf, g = refmodel() if which == "refmodel" else model_s()
+    am = pk.AcousticModel(layers, prior, L, R, tid2pdf).set_softmax(softmax)
+    waves, want = scored_alone(which, softmax, am, g, max_utts)
+    monkeypatch.setenv("PK_MI355_CHUNK", "128")
+    monkeypatch.setenv("PK_MI355_LANES", lanes)
+    frames = [pk.num_frames(len(w)) for w in waves]
+    assert sum((T + 3) // 4 * 4 for T in frames) == {48: 224, 96: 456}[max_utts]
+    bs = pk.BatchScorer(am, g, max_utts, sum(len(w) for w in waves))
+    bs.set_waves(waves)
+    bs.score(0.1)
+    for u in range(max_utts):
+        got = bs.fetch(u).log_prob()
+        assert got.shape == want[u].shape == (frames[u], am.num_pdfs() if frames[u] else 0), (u, got.shape)
+        assert bits_equal(got, want[u]), (u, len(waves[u]))
+
+
+@pytest.mark.parametrize("softmax", ["stable", "reference"])
+@pytest.mark.parametrize("which", ["refmodel", "S"])
+def test_stream_exactly_full_twice(which, softmax):
+    """Five slots, max_step_samples = what one step pushes.  Step 1 pushes it all; step 2 pushes as much again and
+    closes every slot, so every slot flushes its R held-back frames on top of its new ones: the max_frames +
+    slots x (R + 3) row bound.  Every slot's second-step row count is 1 mod 4 (three padding rows each), except the
+    slot that gets fewer than 400 samples in all and has no frames."""
+    layers, prior, L, R, tid2pdf, g = refmodel() if which == "refmodel" else model_s()
+    am = pk.AcousticModel(layers, prior, L, R, tid2pdf).set_softmax(softmax)
+
+    def second_step_rows(p):
+        return pk.num_frames(2 * p) - max(0, pk.num_frames(p) - R)
+
+    per_step = [199]
+    for base in (400, 1700, 3100, 5000):
+        per_step.append(next(p for p in range(base, base + 1000) if second_step_rows(p) % 4 == 1))
+    assert pk.num_frames(2 * per_step[0]) == 0 and all(second_step_rows(p) % 4 == 1 for p in per_step[1:])
+    waves = [synth.utterance(1200 + i, seconds=1.0)[:2 * p] for i, p in enumerate(per_step)]
+    assert [len(w) for w in waves] == [2 * p for p in per_step]
+    want = batch_rows(am, g, waves)
+    sc = pk.OnlineScorer(am, g, 5, sum(per_step))
+    got = run_jobs(sc, [{"slot": i, "wave": w, "chunks": [p, p], "start": 0, "close_with_last": True}
+                        for i, (w, p) in enumerate(zip(waves, per_step))])
+    assert got[0] is None
+    for u in range(1, 5):
+        assert got[u].shape == want[u].shape == (pk.num_frames(len(waves[u])), am.num_pdfs()), u
+        assert bits_equal(got[u], want[u]), u
