@@ -2,7 +2,15 @@
 //
 // SoftmaxLayer (nnet.cc:38-47) + the floor / log / prior step of AcousticModel::Compute (am.cc:106-112) + the
 // acoustic scale (decodable.cc:15), overflow-safe:   out = scale * (max(x - lse, log 1e-20) - log prior),
-// lse = m + log sum exp(x - m).  Lane l of the wave owns the 16-byte chunks q = l + 64 c (c < C) of the row, keeps
+// lse = m + log sum exp(x - m).
+// DOMAIN: |x| < FLT_MAX / log2 e = 2.36e38 (and -inf).  exp(x - m) is formed as exp2(fma(x, log2 e, -m log2 e)), and
+// -m log2 e is a float product: past that bound it is +-inf.  A row whose maximum lies above it comes out all +inf
+// (every argument -inf: s = 0, lse = -inf); one whose maximum lies below minus it comes out all floor (arguments +inf:
+// lse = +inf), or all NaN when the wave also holds a column selected to -inf (-inf + inf) -- any row that does not fill
+// its 256 C columns per wave, or holds a -inf logit.  TailKernel (tail.hip: expf(v - m)) has no such limit, so in that
+// band -- a factor 1.44 below FLT_MAX -- the results do depend on which tail ran.  Pinned as it is by
+// tests/test_gpu_tail_edges.py (test_documented_limit_...); up to +-2^127 the same file holds every instantiation to
+// exact bits.  Lane l of the wave owns the 16-byte chunks q = l + 64 c (c < C) of the row, keeps
 // them in registers and reduces on the vector ALU (DPP) -- no workgroup barrier, no LDS exchange for rows of up to
 // 4 096 columns; wider rows are shared by two waves.  exp is the hardware's v_exp_f32 on fma(x, log2 e, -m log2 e)
 // (1 ulp; two instructions, which keeps a row's code to a few hundred of them -- a tail phase inlined with the libm
@@ -137,10 +145,14 @@ __device__ __forceinline__ void TailWaveRows(const float *__restrict__ in, int64
     }
     if (live) {
       const float lse = m + logf(s);
-      // A row with a NaN logit (or +inf, or nothing but -inf) has lse = NaN and must come out NaN, as the reference's
-      // does (am.cc:109 `x < 1e-20` is false for NaN, log follows): v_max_f32(NaN, floor) would return the floor and
-      // turn the row into plausible numbers.  One select per ROW instead of a compare-select per element: the floor
-      // operand itself becomes NaN, and max(NaN, NaN) = NaN.  (lse is finite for every other row: s is in [1, 8192].)
+      // A row with a NaN logit (or +inf, or nothing but -inf) has lse = NaN and must come out NaN: v_max_f32(NaN, floor)
+      // would return the floor and turn the row into plausible numbers.  For a NaN logit that is what the reference does
+      // (am.cc:109 `x < 1e-20` is false for NaN, log follows).  For a +inf logit the reference makes THAT element NaN
+      // (inf / inf) and the rest of the row floor (0 / inf); the whole row NaN here is on purpose: a row with an
+      // infinite score has no log-softmax, and floor values would pass for one.  One select per ROW instead of a
+      // compare-select per element: the floor operand itself becomes NaN, and max(NaN, NaN) = NaN.  (lse is finite for
+      // every other row INSIDE THE DOMAIN stated at the top: there the maximum's own term is exp2(0) = 1, so s is in
+      // [1, 8192].  Past it s is 0 or inf and lse -inf or +inf: see there.)
       const float row_floor = (lse == lse) ? kLogFloor : lse;
       // the row as a buffer of n floats: a store past its end is dropped by the range check
       const __amdgpu_buffer_rsrc_t yrow = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)row * ld_out, 0, n * 4, 0x00020000);
