@@ -109,7 +109,12 @@ int pk_mi355_set_device(int device);
 
 /* decodable.cc:8-17.  feats: CMVN'd features, {ncol = T, nrow = feat_dim}, host,
  * borrowed.  Allocates self->log_prob {ncol = T, nrow = num_pdfs} on the host with
- * malloc(), fills it with (log softmax - log prior) * prob_scale.                */
+ * malloc(), fills it with (log softmax - log prior) * prob_scale.
+ *
+ * Isolation and reuse: every call (this one and pk_mi355_nnet_propagate) is a function of its own inputs,
+ * whatever the model's workspace held from earlier calls -- longer, NaN or out-of-range ones included; in F32
+ * a row is a function of the frames it splices (a NaN frame makes the rows within its context NaN and no
+ * others).  F16X3 / F16 exception: the range verdict covers the whole call (tests/test_gpu_isolation.py).   */
 void pk_decodable_init(pk_decodable_t *self, pk_mi355_am_t *am, float prob_scale,
                        const pk_matrix_t *feats);
 /* decodable.cc:19-22 */
@@ -266,7 +271,14 @@ int pk_mi355_cmvn_apply(const pk_vector_t *global_stats, const pk_matrix_t *raw,
 typedef struct pk_mi355_batch pk_mi355_batch_t;
 
 /* global_stats41: the cmvn_stats vector pk_load reads (pocketkaldi.cc:96-112).
- * Capacity: at most max_utts utterances and max_total_samples PCM samples.       */
+ * Capacity: at most max_utts utterances and max_total_samples PCM samples.
+ *
+ * Isolation and reuse: in an F32 call an utterance's results (fbank, CMVN, log-likelihoods) are a function of
+ * that utterance's samples alone -- a neighbour full of NaN, Inf or loud samples changes no bit of them, and a
+ * NaN or Inf sample makes NaN exactly the rows the reference makes NaN.  Every call is a function of its own
+ * inputs, whatever the object scored before (other layouts, failed calls, either ingestion path).  F16X3 / F16
+ * exception: the range verdict (PK_MI355_E_RANGE) covers the whole call -- one utterance out of range withholds
+ * every utterance's results -- but never a later call (tests/test_gpu_isolation.py).                        */
 pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_stats41,
                                         int max_utts, int64_t max_total_samples);
 void pk_mi355_batch_destroy(pk_mi355_batch_t *b);
@@ -482,6 +494,10 @@ int pk_mi355_decoder_trace_stats(const pk_mi355_decoder_t *d, int utt, int64_t *
  * [a, n - R) while the slot is open (n: frames whose 400 samples have arrived, R: the model's right context),
  * frames [a, n) in the step after pk_mi355_stream_close (the right edge replicated, am.cc:73-75).  That step
  * frees the slot; it may then be opened again.  A slot closed with fewer than 400 samples yields no frames.
+ *
+ * Isolation and reuse: a slot's rows are a function of the samples pushed to that slot since it was opened --
+ * what the other slots stream (NaN, Inf, loud samples) changes no bit of them.  Every opening of a slot is a
+ * function of its own pushes, whatever the slot or the object carried before (tests/test_gpu_isolation.py).
  *
  * F32 models only (PK_MI355_PRECISION_F32, both softmax modes); an F16X3 or F16 model is refused with
  * PK_MI355_E_INVALID (their calibration and range verdict are per batch).  Capacity: max_step_samples PCM

@@ -373,6 +373,7 @@ struct Workspace {
   ExecBufs exec;
   float *d_feats = nullptr;  int64_t feats_cap = 0;     // frame-major host upload
   float *d_yt = nullptr;     int64_t yt_ld = 0;          // [feat_dim][yt_ld], the last kSingleZeroSpan columns never written
+  int64_t dirty_cols = 0;                               // columns of d_yt that may hold an earlier call's features (ScoreSingleQueue)
   _Float16 *d_y2 = nullptr;                             // f16x3: interleaved rows [yt_ld][2 feat_dim]
   float *d_out = nullptr;    int64_t out_cap = 0;        // [rows][num_pdfs]
   hipStream_t stream = nullptr;
@@ -402,6 +403,7 @@ int EnsureWorkspace(pk_mi355_am *am, int64_t frames, int width) {
     w->yt_ld = need_ld;
     HIP_TRY(hipMalloc(&w->d_yt, sizeof(float) * w->yt_ld * am->feat_dim));
     HIP_TRY(hipMemset(w->d_yt, 0, sizeof(float) * w->yt_ld * am->feat_dim));
+    w->dirty_cols = 0;
     if (IsF16(am->precision)) {
       hipFree(w->d_y2);
       HIP_TRY(hipMalloc(&w->d_y2, sizeof(_Float16) * 2 * w->yt_ld * am->feat_dim));
@@ -498,9 +500,19 @@ int ScoreSingleQueue(pk_mi355_am *am, const pk_matrix_t *feats, bool want_tail, 
   int rc;
   HIP_TRY(hipMemcpyAsync(w->d_feats, feats->data, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, w->stream));
   LaunchPadTranspose(w->d_feats, T, D, am->left, am->right, w->d_yt, w->yt_ld, 0, w->stream);
+  // Columns behind this call's last one that an earlier, longer call filled: the padded rows of the last tile are
+  // computed from them, and in the f16 modes whatever they produce counts towards the range verdict (a loud utterance
+  // followed by a shorter healthy one must not fail on the loud one's leftovers; capi_batch.hip: SetLayout).  Zero again.
+  const int64_t cols = (int64_t)T + am->left + am->right;
+  if (cols < w->dirty_cols)
+    HIP_TRY(hipMemset2DAsync(w->d_yt + cols, sizeof(float) * w->yt_ld, 0, sizeof(float) * (size_t)(w->dirty_cols - cols), D, w->stream));
+  w->dirty_cols = cols;
   if (f16) {
     if ((rc = BeginRange(w->exec, w->stream))) return rc;
-    LaunchSplitF16(w->d_yt, 1, w->yt_ld, (int)w->yt_ld, D, D, w->d_y2, 2 * D, ExpX(am, 0), RangeOf(w->exec, 0), w->stream);
+    // only the rows the layer stack reads (the last pass's padded rows and their right context): rows further out hold
+    // zeros or an earlier call's split, and their maxima are not this call's
+    const int split_rows = (int)std::min<int64_t>(w->yt_ld, RoundUp(cols, kTileF16) + 2 * kTileF16);
+    LaunchSplitF16(w->d_yt, 1, w->yt_ld, split_rows, D, D, w->d_y2, 2 * D, ExpX(am, 0), RangeOf(w->exec, 0), w->stream);
   }
   const Operand op{w->d_yt, w->d_y2, w->yt_ld, ZeroSource(w->d_yt, w->yt_ld, kSingleZeroSpan), nullptr};
   const Lane lane{w->stream, &w->exec};
@@ -531,6 +543,11 @@ int pk_mi355_nnet_propagate(pk_mi355_am_t *am, const pk_matrix_t *in, pk_matrix_
     if (IsF16(am->precision)) {
       const int kp = (int)RoundUp(D, kBKF16);
       if ((rc = BeginRange(w->exec, w->stream))) return rc;
+      // the GEMM computes whole 256-row tiles: the rows behind this pass's last one must not be an earlier pass's
+      // (what they produce counts towards the range verdict of the operands behind the first)
+      const int64_t rows_pad = RoundUp(rows, kTileF16);
+      if (rows_pad > rows)
+        HIP_TRY(hipMemsetAsync(w->exec.xin + (size_t)rows * 2 * kp, 0, sizeof(_Float16) * 2 * kp * (size_t)(rows_pad - rows), w->stream));
       LaunchSplitF16(w->d_feats + r0 * D, D, 1, rows, D, kp, w->exec.xin, 2 * kp, ExpX(am, 0), RangeOf(w->exec, 0), w->stream);
       rc = RunLayersF16(am, w->exec, w->exec.xin, 2 * kp, rows, false, 1.0f, nullptr, 0, w->stream, nullptr, &res);
       if (!rc) rc = CollectRange(w->exec, w->stream);
