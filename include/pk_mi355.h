@@ -576,6 +576,8 @@ int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *d, int slot,
 /* Test hooks, as pk_mi355_decoder_best_path_arcs / _active_bound (the arcs of the partial path while live).  */
 int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *d, int slot, int32_t *arcs, int max_arcs);
 int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *d, int slot);
+/* The frames the slot has decoded so far (0 after open; what a slot that ended early had decoded).            */
+int pk_mi355_online_decoder_num_frames(const pk_mi355_online_decoder_t *d, int slot);
 
 /* ------------------------------------------------------------------------- */
 /* Best-path alignment and word segments ("Alignment")       */
@@ -611,9 +613,27 @@ typedef struct pk_mi355_word_t {
 /* Segments of utt in the last call (at most max written, the count returned).  PK_MI355_E_STATE when the call ran
  * with alignment off.                                                                                            */
 int pk_mi355_decoder_word_segments(const pk_mi355_decoder_t *d, int utt, pk_mi355_word_t *out, int max);
+/* Online alignment.  Off (0) by default; the mode is the object's (one launch serves every slot), so it can be
+ * changed only while no slot is open: PK_MI355_E_STATE otherwise.  On: every backtrace record also keeps the
+ * acoustic cost of its arc -- -N1(log_prob[t][pdf]) for an emitting arc, the bits the batch decoder's alignment
+ * gives, 0 for an epsilon arc -- written when the frame is decoded (the only moment its row exists), moved by the
+ * trace compaction and read out with the path.  Words, weight, ok, best-path arcs and active_bound are those of the
+ * mode off, bit for bit.  Device memory the mode adds: 8 bytes x max_streams x trace_capacity, allocated at the
+ * first enable, not at create.  A finished slot keeps the mode it was opened with.  A call still in flight is waited
+ * for first; what it says of a slot (PK_MI355_E_CAPACITY, ...) is not this entry's failure and stays readable in the
+ * slot's result.                                                                                                   */
+int pk_mi355_online_decoder_set_alignment(pk_mi355_online_decoder_t *d, int enable);
+/* The alignment of the slot's current path -- partial while the slot is live, final after its last advance -- as
+ * pk_mi355_decoder_alignment: per frame the arc id, its transition-id and its acoustic cost (any pointer may be
+ * NULL; at most max_frames entries written).  Returns the frames aligned: pk_mi355_online_decoder_num_frames, or 0
+ * for a slot without a path or one that ended with ok = 0.  PK_MI355_E_STATE with the mode off (or for a slot opened
+ * with it off); PK_MI355_E_DEVICE if the path's emitting arcs are not the slot's decoded frames.                  */
+int pk_mi355_online_decoder_alignment(const pk_mi355_online_decoder_t *d, int slot, int32_t *arc_ids, int32_t *trans_ids,
+                                      float *acoustic_cost, int max_frames);
 /* Segments of the slot's current path: the partial hypothesis while the slot is live, the final one after its
- * last advance.  acoustic_cost is NaN in every segment: the online scorer's rows are void after each step, so no
- * log-likelihood of the path's frames is left to read.                                                           */
+ * last advance.  With alignment off acoustic_cost is NaN in every segment: the online scorer's rows are void after
+ * each step, so no log-likelihood of the path's frames is left to read.  With alignment on it is the sum over the
+ * costs kept with the trace, as pk_mi355_decoder_word_segments gives it.                                         */
 int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *d, int slot, pk_mi355_word_t *out, int max);
 
 /* ------------------------------------------------------------------------- */
@@ -660,6 +680,46 @@ int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *wav
 const char *pk_mi355_recognizer_hyp(const pk_mi355_recognizer_t *r, int utt);
 /* utt->loglikelihood_per_frame: weight / num_frames in float; 0.0f for an utterance without words (NaN on misuse). */
 float pk_mi355_recognizer_loglikelihood_per_frame(const pk_mi355_recognizer_t *r, int utt);
+
+/* ------------------------------------------------------------------------- */
+/* Online recognizer -- pk_load + a live pk_process: PCM chunks to text             */
+/* ------------------------------------------------------------------------- */
+
+/* pk_load as pk_mi355_recognizer_load does it (same keys, order, messages and olabel check; host-side files before
+ * the device is touched), F32 only (the online scorer refuses f16 models).  Owns graph, symbol table, model, an
+ * online scorer (max_streams, max_step_samples: as pk_mi355_stream_create) and an online decoder with alignment on
+ * (trace_capacity: as pk_mi355_online_decoder_create).  It computes nothing itself: beam, softmax mode and every
+ * result getter (words, weight, ok, alignment, word segments) are the owned objects' entries.  NULL on failure.   */
+typedef struct pk_mi355_online_recognizer pk_mi355_online_recognizer_t;
+pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config_path, int max_streams,
+                                                              int64_t max_step_samples, int64_t trace_capacity);
+void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r);
+pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r);
+pk_mi355_stream_t *pk_mi355_online_recognizer_stream(pk_mi355_online_recognizer_t *r);
+pk_mi355_online_decoder_t *pk_mi355_online_recognizer_decoder(pk_mi355_online_recognizer_t *r);
+const pk_mi355_symtab_t *pk_mi355_online_recognizer_symtab(const pk_mi355_online_recognizer_t *r);
+/* Start an utterance in slot: opens the scorer's slot and the decoder's (neither, if either refuses).  Open, push,
+ * close and step through these entries, not through the owned objects: a slot closed behind the recognizer's back
+ * is never reported finished.                                                                                      */
+int pk_mi355_online_recognizer_open(pk_mi355_online_recognizer_t *r, int slot);
+/* As pk_mi355_stream_push / _push_i16 / _close.                                                                    */
+int pk_mi355_online_recognizer_push(pk_mi355_online_recognizer_t *r, int slot, const float *samples, int num_samples);
+int pk_mi355_online_recognizer_push_i16(pk_mi355_online_recognizer_t *r, int slot, const int16_t *samples, int num_samples);
+int pk_mi355_online_recognizer_close(pk_mi355_online_recognizer_t *r, int slot);
+/* pk_mi355_stream_step (prob_scale 0.1), pk_mi355_online_decoder_advance (synchronous), then the text of every slot
+ * is refreshed.  Returns what those return: a slot the decoder ended (PK_MI355_E_CAPACITY, ...) stays ended until
+ * it is closed, flushed by a step and opened again, while the other slots go on.                                  */
+int pk_mi355_online_recognizer_step(pk_mi355_online_recognizer_t *r);
+/* The slot's current hypothesis: the words' strings in spoken order joined by one space ("" without words).  Valid
+ * until the next step.  NULL on misuse.                                                                            */
+const char *pk_mi355_online_recognizer_partial(const pk_mi355_online_recognizer_t *r, int slot);
+/* 1 once the step after the slot's close has run (its result is final), 0 before; negative on misuse.             */
+int pk_mi355_online_recognizer_finished(const pk_mi355_online_recognizer_t *r, int slot);
+/* A finished slot's utt->hyp and utt->loglikelihood_per_frame, by pk_mi355_recognizer_hyp's rules: "" and 0.0f for a
+ * slot without words (also one the decoder ended with ok = 0), else weight / frames in float.  Before the slot is
+ * finished: NULL / NaN with PK_MI355_E_STATE.  Valid until the slot is opened again.                               */
+const char *pk_mi355_online_recognizer_hyp(const pk_mi355_online_recognizer_t *r, int slot);
+float pk_mi355_online_recognizer_loglikelihood_per_frame(const pk_mi355_online_recognizer_t *r, int slot);
 
 /* Library / device facts */
 int pk_mi355_device_count(void);

@@ -392,11 +392,82 @@ class OnlineDecoder {
     if (n > 0) pk_mi355_online_decoder_result(d_, slot, w.data(), n, weight, ok);
     return w;
   }
+  // While no slot is open: every trace record also keeps its arc's acoustic cost (pk_mi355_online_decoder_set_alignment)
+  Status SetAlignment(bool on) { return Status::FromLast(pk_mi355_online_decoder_set_alignment(d_, on ? 1 : 0)); }
+  // Per frame of the slot's current path (partial while live): the emitting arc, its transition-id and its acoustic
+  // cost (any pointer may be null).  Returns the frames aligned, or a negative code (alignment off: PK_MI355_E_STATE).
+  int Alignment(int slot, std::vector<int32_t> *arc_ids, std::vector<int32_t> *trans_ids, std::vector<float> *acoustic_cost) const {
+    const int n = pk_mi355_online_decoder_alignment(d_, slot, nullptr, nullptr, nullptr, 0);
+    if (n < 0) return n;
+    if (arc_ids) arc_ids->resize(n);
+    if (trans_ids) trans_ids->resize(n);
+    if (acoustic_cost) acoustic_cost->resize(n);
+    return pk_mi355_online_decoder_alignment(d_, slot, arc_ids ? arc_ids->data() : nullptr, trans_ids ? trans_ids->data() : nullptr,
+                                             acoustic_cost ? acoustic_cost->data() : nullptr, n);
+  }
+  // The frames the slot has decoded
+  int NumFrames(int slot) const { return pk_mi355_online_decoder_num_frames(d_, slot); }
+  // The word segments of the slot's current path (acoustic_cost is NaN with alignment off)
+  std::vector<pk_mi355_word_t> WordSegments(int slot) const {
+    const int n = pk_mi355_online_decoder_word_segments(d_, slot, nullptr, 0);
+    std::vector<pk_mi355_word_t> out(n > 0 ? n : 0);
+    if (n > 0) pk_mi355_online_decoder_word_segments(d_, slot, out.data(), n);
+    return out;
+  }
   const Status &last_status() const { return status_; }
+  pk_mi355_online_decoder_t *handle() const { return d_; }
 
  private:
   pk_mi355_online_decoder_t *d_;
   Status status_;
+};
+
+// pk_load + a live pk_process (pk_mi355_online_recognizer_*): PCM pushed per slot in chunks, Step() after every round
+// of pushes, Partial() while a slot is live; Close(), one more Step(), then Result().
+class OnlineRecognizer {
+ public:
+  OnlineRecognizer() : r_(nullptr) {}
+  ~OnlineRecognizer() { pk_mi355_online_recognizer_destroy(r_); }
+  OnlineRecognizer(const OnlineRecognizer &) = delete;
+  OnlineRecognizer &operator=(const OnlineRecognizer &) = delete;
+
+  Status Load(const std::string &model_file, int max_streams = 1, int64_t max_step_samples = 16000 * 8,
+              int64_t trace_capacity = 0) {
+    pk_mi355_online_recognizer_destroy(r_);
+    r_ = pk_mi355_online_recognizer_load(model_file.c_str(), max_streams, max_step_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  Status Open(int slot) { return Status::FromLast(pk_mi355_online_recognizer_open(r_, slot)); }
+  Status Push(int slot, const float *samples, int num_samples) {
+    return Status::FromLast(pk_mi355_online_recognizer_push(r_, slot, samples, num_samples));
+  }
+  Status PushI16(int slot, const int16_t *samples, int num_samples) {
+    return Status::FromLast(pk_mi355_online_recognizer_push_i16(r_, slot, samples, num_samples));
+  }
+  Status Close(int slot) { return Status::FromLast(pk_mi355_online_recognizer_close(r_, slot)); }
+  Status Step() { return Status::FromLast(pk_mi355_online_recognizer_step(r_)); }
+  // The slot's current hypothesis as text ("" on misuse); valid until the next Step()
+  std::string Partial(int slot) const {
+    const char *text = pk_mi355_online_recognizer_partial(r_, slot);
+    return text ? text : "";
+  }
+  bool Finished(int slot) const { return pk_mi355_online_recognizer_finished(r_, slot) == 1; }
+  // A finished slot's hyp and loglikelihood_per_frame; PK_MI355_E_STATE before that
+  Status Result(int slot, Recognizer::Utterance *out) const {
+    const char *hyp = pk_mi355_online_recognizer_hyp(r_, slot);
+    if (!hyp) return Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+    if (out) *out = Recognizer::Utterance{hyp, pk_mi355_online_recognizer_loglikelihood_per_frame(r_, slot)};
+    return Status();
+  }
+  // The owned objects: beam, softmax mode and the other result getters (words, alignment, word segments) are their entries
+  pk_mi355_am_t *am() const { return pk_mi355_online_recognizer_am(r_); }
+  pk_mi355_stream_t *stream() const { return pk_mi355_online_recognizer_stream(r_); }
+  pk_mi355_online_decoder_t *decoder() const { return pk_mi355_online_recognizer_decoder(r_); }
+  const pk_mi355_symtab_t *symbols() const { return pk_mi355_online_recognizer_symtab(r_); }
+  pk_mi355_online_recognizer_t *handle() const { return r_; }
+
+ private:
+  pk_mi355_online_recognizer_t *r_;
 };
 
 // Utterance sharding for N GPUs (one process per GPU, a full weight replica each, no data-path collective): which rank

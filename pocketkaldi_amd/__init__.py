@@ -30,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "Result", "Segment", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -99,6 +99,13 @@ EXPORTS = [
     "pk_mi355_recognizer_load", "pk_mi355_recognizer_destroy", "pk_mi355_recognizer_am", "pk_mi355_recognizer_batch",
     "pk_mi355_recognizer_decoder", "pk_mi355_recognizer_symtab", "pk_mi355_recognizer_process", "pk_mi355_recognizer_hyp",
     "pk_mi355_recognizer_loglikelihood_per_frame",
+    "pk_mi355_online_decoder_set_alignment", "pk_mi355_online_decoder_alignment", "pk_mi355_online_decoder_num_frames",
+    "pk_mi355_online_recognizer_load", "pk_mi355_online_recognizer_destroy", "pk_mi355_online_recognizer_am",
+    "pk_mi355_online_recognizer_stream", "pk_mi355_online_recognizer_decoder", "pk_mi355_online_recognizer_symtab",
+    "pk_mi355_online_recognizer_open", "pk_mi355_online_recognizer_push", "pk_mi355_online_recognizer_push_i16",
+    "pk_mi355_online_recognizer_close", "pk_mi355_online_recognizer_step", "pk_mi355_online_recognizer_partial",
+    "pk_mi355_online_recognizer_finished", "pk_mi355_online_recognizer_hyp",
+    "pk_mi355_online_recognizer_loglikelihood_per_frame",
 ]
 
 
@@ -281,6 +288,27 @@ def lib():
     L.pk_mi355_recognizer_hyp.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_recognizer_loglikelihood_per_frame.restype = C.c_float
     L.pk_mi355_recognizer_loglikelihood_per_frame.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_set_alignment.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_alignment.argtypes = [C.c_void_p, C.c_int, i32p, i32p, f32p, C.c_int]
+    L.pk_mi355_online_decoder_num_frames.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_online_recognizer_load.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64]
+    L.pk_mi355_online_recognizer_destroy.restype = None
+    L.pk_mi355_online_recognizer_destroy.argtypes = [C.c_void_p]
+    for f in ("am", "stream", "decoder", "symtab"):
+        getattr(L, "pk_mi355_online_recognizer_" + f).restype = C.c_void_p
+        getattr(L, "pk_mi355_online_recognizer_" + f).argtypes = [C.c_void_p]
+    for f in ("open", "close", "finished"):
+        getattr(L, "pk_mi355_online_recognizer_" + f).argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_push.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int]
+    L.pk_mi355_online_recognizer_push_i16.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int16), C.c_int]
+    L.pk_mi355_online_recognizer_step.argtypes = [C.c_void_p]
+    L.pk_mi355_online_recognizer_partial.restype = C.c_char_p
+    L.pk_mi355_online_recognizer_partial.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_hyp.restype = C.c_char_p
+    L.pk_mi355_online_recognizer_hyp.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_loglikelihood_per_frame.restype = C.c_float
+    L.pk_mi355_online_recognizer_loglikelihood_per_frame.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 
@@ -1012,8 +1040,28 @@ class OnlineDecoder:
         return _check_code(lib().pk_mi355_online_decoder_active_bound(self._h, int(slot)))
 
     def word_segments(self, slot):
-        """Segments of the slot's current path (partial while live, final after close); acoustic_cost is NaN."""
+        """Segments of the slot's current path (partial while live, final after close); acoustic_cost is NaN with
+        alignment off."""
         return _segments(lib().pk_mi355_online_decoder_word_segments, self._h, slot)
+
+    def set_alignment(self, on=True):
+        """While no slot is open: every trace record also keeps its arc's acoustic cost, so that alignment() and the
+        segments' acoustic_cost are the batch decoder's."""
+        _check_code(lib().pk_mi355_online_decoder_set_alignment(self._h, 1 if on else 0))
+
+    def alignment(self, slot):
+        """(arc ids int32 [frames], transition-ids int32 [frames], acoustic costs float32 [frames]) of the slot's current
+        path, as Decoder.alignment.  Raises (PK_MI355_E_STATE) with alignment off."""
+        n = _check_code(lib().pk_mi355_online_decoder_alignment(self._h, int(slot), None, None, None, 0))
+        arcs, tids, ac = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if n:
+            _check_code(lib().pk_mi355_online_decoder_alignment(self._h, int(slot), arcs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                tids.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ac), n))
+        return arcs, tids, ac
+
+    def num_frames(self, slot):
+        """The frames the slot has decoded."""
+        return _check_code(lib().pk_mi355_online_decoder_num_frames(self._h, int(slot)))
 
 
 class SymbolTable:
@@ -1056,12 +1104,13 @@ class _Borrowed:
     """An AcousticModel / BatchScorer / Decoder over a handle the Recognizer owns: every method, nothing to free."""
 
     @staticmethod
-    def of(cls, handle, owner, **fields):
+    def of(cls, handle, owner, free="close", **fields):
+        """free: the name of cls's method that frees the handle (close, or destroy where close(slot) means a slot)."""
         self = cls.__new__(cls)
         self._h, self._owner, self._keep = handle, owner, None
         for k, v in fields.items():
             setattr(self, k, v)
-        self.close = lambda: None
+        setattr(self, free, lambda: None)
         return self
 
 
@@ -1124,3 +1173,81 @@ class Recognizer:
         if call:
             out += self._process_call(call)
         return out
+
+
+class OnlineRecognizer:
+    """pk_load + a live pk_process: the model file's graph, symbol table and acoustic model, an online scorer and an
+    online decoder with alignment on.  .am / .scorer / .decoder / .symbols are the owned objects (beam and softmax mode
+    are set through them).  open(slot), push(slot, samples) ..., step() after every round of pushes, partial(slot)
+    while live; close(slot), one more step(), then result(slot) -> Result, as Recognizer.process yields.  Open, push,
+    close and step through the recognizer, not through .scorer / .decoder: a slot closed behind its back is never
+    reported finished."""
+
+    def __init__(self, config, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0):
+        self._h = lib().pk_mi355_online_recognizer_load(os.fspath(config).encode(), int(max_streams), int(max_step_samples),
+                                                        int(trace_capacity))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self.max_streams, self.max_step_samples = int(max_streams), int(max_step_samples)
+        L = lib()
+        self.am = _Borrowed.of(AcousticModel, L.pk_mi355_online_recognizer_am(self._h), self)
+        self.scorer = _Borrowed.of(OnlineScorer, L.pk_mi355_online_recognizer_stream(self._h), self, free="destroy", _am=self.am)
+        self.decoder = _Borrowed.of(OnlineDecoder, L.pk_mi355_online_recognizer_decoder(self._h), self, free="destroy",
+                                    _am=self.am, _fst=None)
+        self.symbols = SymbolTable._borrowed(L.pk_mi355_online_recognizer_symtab(self._h), self)
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_online_recognizer_destroy(self._h)
+            self._h = None
+            for part in (self.am, self.scorer, self.decoder, self.symbols):
+                part._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def open(self, slot):
+        _check_code(lib().pk_mi355_online_recognizer_open(self._h, int(slot)))
+
+    def push(self, slot, samples):
+        """float sample values (as read_wav gives them); an int16 array goes through push_i16."""
+        if isinstance(samples, np.ndarray) and samples.dtype == np.int16:
+            return self.push_i16(slot, samples)
+        x = _f32(samples).ravel()
+        _check_code(lib().pk_mi355_online_recognizer_push(self._h, int(slot), _fp(x) if x.size else None, x.shape[0]))
+
+    def push_i16(self, slot, samples):
+        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
+        _check_code(lib().pk_mi355_online_recognizer_push_i16(self._h, int(slot),
+                                                              x.ctypes.data_as(C.POINTER(C.c_int16)) if x.size else None,
+                                                              x.shape[0]))
+
+    def close(self, slot):
+        """No more samples for slot: the next step() finishes it."""
+        _check_code(lib().pk_mi355_online_recognizer_close(self._h, int(slot)))
+
+    def step(self):
+        _check_code(lib().pk_mi355_online_recognizer_step(self._h))
+
+    def partial(self, slot):
+        """The slot's current hypothesis as text (valid until the next step)."""
+        s = lib().pk_mi355_online_recognizer_partial(self._h, int(slot))
+        if s is None:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        return s.decode()
+
+    def finished(self, slot):
+        return bool(_check_code(lib().pk_mi355_online_recognizer_finished(self._h, int(slot))))
+
+    def result(self, slot):
+        """The Result of a finished slot: what Recognizer.process gives on the whole wave."""
+        text = lib().pk_mi355_online_recognizer_hyp(self._h, int(slot))
+        if text is None:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        words, weight, ok = self.decoder.result(slot)
+        return Result(text.decode(), words, weight, ok,
+                      lib().pk_mi355_online_recognizer_loglikelihood_per_frame(self._h, int(slot)),
+                      self.decoder.word_segments(slot))

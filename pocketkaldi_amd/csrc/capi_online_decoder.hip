@@ -15,8 +15,13 @@ struct pk_mi355_online_decoder : DecoderCore {
   OnlineResult *d_results = nullptr;
   int *d_remap = nullptr;
   OnlineCall *d_calls = nullptr;
+  bool align = false;                           // pk_mi355_online_decoder_set_alignment
+  float *d_rec_ac = nullptr, *d_path_ac = nullptr;   // cap floats per slot each, from the first enable
+  std::vector<std::vector<float>> path_acs;     // per slot, align only: the acoustic cost of every arc of paths[slot]
   std::vector<int> open_, fresh, finished;      // per slot
+  std::vector<char> aligned;                    // per slot: opened with the alignment mode on
   std::vector<OnlineResult> res;                // per slot, after synchronize
+  std::vector<OnlineResult> fetched;            // d_results as copied back; res takes the last call's slots from it
   std::vector<std::vector<int32_t>> paths;      // per slot: the arcs of res[slot]'s path
   std::vector<int> last_slots;                  // slots of the last call
   bool pending = false;
@@ -33,7 +38,8 @@ int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<
   if (n > 0) {
     HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
     // (frames, arenas and results are per slot: the calls, and o->cap entries of rec and path each)
-    LaunchOnlineDecode(ArgsOf(o, ll, n), o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap, n, stream);
+    LaunchOnlineDecode(ArgsOf(o, ll, n), o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap,
+                       o->align ? o->d_rec_ac : nullptr, o->align ? o->d_path_ac : nullptr, n, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
   }
@@ -53,15 +59,25 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
   o->pending = false;
   HIP_TRY(hipEventSynchronize(o->done));
   if (o->last_slots.empty()) return 0;
-  HIP_TRY(hipMemcpy(o->res.data(), o->d_results, sizeof(OnlineResult) * o->max_streams, hipMemcpyDeviceToHost));
+  // Only the call's slots take their record: a slot opened again since its last launch keeps the cleared record that
+  // open gave it, whatever the device still holds of its previous utterance.
+  o->fetched.resize(o->max_streams);
+  HIP_TRY(hipMemcpy(o->fetched.data(), o->d_results, sizeof(OnlineResult) * o->max_streams, hipMemcpyDeviceToHost));
   int first_bad = -1;
   for (int slot : o->last_slots) {
+    o->res[slot] = o->fetched[slot];
     const OnlineResult &r = o->res[slot];
     if (r.path_len < 0 || r.path_len > o->cap) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
     o->paths[slot].resize(r.path_len);
     if (r.path_len)
       HIP_TRY(hipMemcpy(o->paths[slot].data(), o->path + (int64_t)slot * o->cap, sizeof(int32_t) * r.path_len,
                         hipMemcpyDeviceToHost));
+    if (o->aligned[slot]) {
+      o->path_acs[slot].resize(r.path_len);
+      if (r.path_len)
+        HIP_TRY(hipMemcpy(o->path_acs[slot].data(), o->d_path_ac + (int64_t)slot * o->cap, sizeof(float) * r.path_len,
+                          hipMemcpyDeviceToHost));
+    }
     if (r.status && first_bad < 0) first_bad = slot;
   }
   if (first_bad >= 0) {
@@ -92,7 +108,24 @@ int OnlineReady(const pk_mi355_online_decoder *o, int slot) {
   return 0;
 }
 
+// The slot's current path as frames (PathFrames): 0 for a slot without a path.
+int OnlineFrames(const pk_mi355_online_decoder *o, int slot, int32_t *arc_ids, int32_t *trans_ids, float *ac, int max_frames) {
+  const OnlineResult &r = o->res[slot];
+  if (!r.has_path || !r.ok || r.status) return 0;
+  if (!o->aligned[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d was decoded with alignment off", slot);
+  const auto &p = o->paths[slot];
+  const auto &pa = o->path_acs[slot];
+  if (pa.size() != p.size()) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: path and costs differ in length", slot);
+  return PathFrames(o->labels, p.data(), pa.data(), (int)p.size(), r.frames, arc_ids, trans_ids, ac, max_frames);
+}
+
 }  // namespace
+
+namespace pkhost {
+bool OnlineDecoderSlotOpen(const pk_mi355_online_decoder *o, int slot) {
+  return o && slot >= 0 && slot < o->max_streams && o->open_[slot] != 0;
+}
+}  // namespace pkhost
 
 extern "C" {
 
@@ -118,6 +151,8 @@ pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *
   o->open_.assign(max_streams, 0); o->fresh.assign(max_streams, 1); o->finished.assign(max_streams, 0);
   o->res.assign(max_streams, OnlineResult{});
   o->paths.assign(max_streams, {});
+  o->path_acs.assign(max_streams, {});
+  o->aligned.assign(max_streams, 0);
   return o;
 }
 
@@ -126,6 +161,7 @@ void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *o) {
   if (!UseDevice(o->device)) {
     if (o->pending) hipEventSynchronize(o->done);
     hipFree(o->d_state); hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
+    hipFree(o->d_rec_ac); hipFree(o->d_path_ac);
     FreeCore(o);
   }
   delete o;
@@ -136,6 +172,27 @@ int pk_mi355_online_decoder_set_beam(pk_mi355_online_decoder_t *o, float beam, i
   return SetBeam(o, beam, max_active);
 }
 
+int pk_mi355_online_decoder_set_alignment(pk_mi355_online_decoder_t *o, int enable) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  for (int slot = 0; slot < o->max_streams; ++slot)     // one launch serves every slot: the mode is the object's
+    if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_alignment needs every slot closed)", slot);
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  // A call still in flight ends first.  What it says of a slot (capacity, a closure that did not settle) was that
+  // advance's to report and stays readable in the slot's result: only a device failure stops the mode change.
+  if ((rc = OnlineCollect(o)) == PK_MI355_E_DEVICE) return rc;
+  if (enable && !o->d_rec_ac) {
+    const size_t bytes = sizeof(float) * (size_t)o->cap * o->max_streams;
+    float *rec_ac = nullptr, *path_ac = nullptr;
+    hipError_t e = hipMalloc(&rec_ac, bytes);
+    if (e == hipSuccess && (e = hipMalloc(&path_ac, bytes)) != hipSuccess) hipFree(rec_ac);
+    if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online_decoder_set_alignment: %s", hipGetErrorString(e));
+    o->d_rec_ac = rec_ac; o->d_path_ac = path_ac;
+  }
+  o->align = enable != 0;                                // (a finished slot keeps its results, and the mode it was opened with)
+  return 0;
+}
+
 int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
   int rc = OnlineSlot(o, slot);
   if (rc) return rc;
@@ -144,6 +201,8 @@ int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
   o->open_[slot] = 1; o->fresh[slot] = 1; o->finished[slot] = 0;
   o->res[slot] = OnlineResult{};
   o->paths[slot].clear();
+  o->path_acs[slot].clear();
+  o->aligned[slot] = o->align ? 1 : 0;
   return 0;
 }
 
@@ -227,7 +286,26 @@ int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *o, in
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
   const auto &p = o->paths[slot];
-  return WordSegments(o->labels, p.data(), (int)p.size(), nullptr, 0, out, max);   // (the rows are gone: no acoustic cost)
+  if (!o->align || !o->aligned[slot])             // (the rows are gone, and no cost was kept: no acoustic cost)
+    return WordSegments(o->labels, p.data(), (int)p.size(), nullptr, 0, out, max);
+  std::vector<float> ac(std::max(o->res[slot].frames, 1));                    // the costs kept with the trace
+  const int frames = OnlineFrames(o, slot, nullptr, nullptr, ac.data(), (int)ac.size());
+  if (frames < 0) return frames;
+  return WordSegments(o->labels, p.data(), (int)p.size(), ac.data(), frames, out, max);
+}
+
+int pk_mi355_online_decoder_alignment(const pk_mi355_online_decoder_t *o, int slot, int32_t *arc_ids, int32_t *trans_ids,
+                                      float *acoustic_cost, int max_frames) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  if (!o->align) return Fail(PK_MI355_E_STATE, "online decoder: alignment is off (pk_mi355_online_decoder_set_alignment)");
+  return OnlineFrames(o, slot, arc_ids, trans_ids, acoustic_cost, max_frames);
+}
+
+int pk_mi355_online_decoder_num_frames(const pk_mi355_online_decoder_t *o, int slot) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  return o->res[slot].frames;
 }
 
 int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *o, int slot) {

@@ -9,9 +9,46 @@
 
 using namespace pkhost;
 
-struct pk_mi355_recognizer {
-  pk_mi355_fst_t *fst = nullptr;
-  pk_mi355_symtab_t *symtab = nullptr;
+namespace pkhost {
+
+int LoadRecognizerFiles(const char *config_path, RecognizerFiles *r) {
+  // pk_load's order (pocketkaldi.cc:81-131): fst, cmvn_stats, the AcousticModel keys, symbol_table.  Keys and host-side
+  // files first, so that a model file that cannot work is refused before the device is touched.
+  std::string path;
+  ModelConfig conf;
+  if (ConfigPath(config_path, "fst", &path) || !(r->fst = pk_mi355_fst_read(path.c_str()))) return pk_mi355_last_error_code();
+  int rc = ReadModelConfig(config_path, &conf);
+  if (rc) return rc;
+  if (ConfigPath(config_path, "symbol_table", &path) || !(r->symtab = pk_mi355_symtab_read(path.c_str())))
+    return pk_mi355_last_error_code();
+  const int symbols = pk_mi355_symtab_size(r->symtab);
+  for (int a = 0; a < r->fst->num_arcs; ++a)       // pk_symboltable_get asserts this when the word is looked up
+    if (r->fst->arcs[a].olabel >= symbols)
+      return Fail(PK_MI355_E_INVALID, "%s: arc %d of the graph has output label %d, the symbol table has %d symbols", config_path, a,
+                  r->fst->arcs[a].olabel, symbols);
+  return 0;
+}
+
+void FreeRecognizerFiles(RecognizerFiles *f) {
+  pk_mi355_symtab_destroy(f->symtab);
+  pk_mi355_fst_destroy(f->fst);
+  f->symtab = nullptr; f->fst = nullptr;
+}
+
+int JoinWords(const pk_mi355_symtab_t *symtab, const int *words, int count, std::string *text) {
+  text->clear();
+  for (int i = 0; i < count; ++i) {
+    const char *word = pk_mi355_symtab_get(symtab, words[i]);
+    if (!word) return pk_mi355_last_error_code();  // (cannot happen: load has checked every olabel)
+    if (i) *text += ' ';                           // (:232-238: a space after every word, the last one dropped by pk_strlcpy)
+    *text += word;
+  }
+  return 0;
+}
+
+}  // namespace pkhost
+
+struct pk_mi355_recognizer : RecognizerFiles {
   pk_mi355_am_t *am = nullptr;
   pk_mi355_batch_t *batch = nullptr;
   pk_mi355_decoder_t *decoder = nullptr;
@@ -27,8 +64,7 @@ void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
   pk_mi355_decoder_destroy(r->decoder);    // (waits for its last call, which reads the batch's rows)
   pk_mi355_batch_destroy(r->batch);
   pk_mi355_am_destroy(r->am);
-  pk_mi355_symtab_destroy(r->symtab);
-  pk_mi355_fst_destroy(r->fst);
+  FreeRecognizerFiles(r);
   delete r;
 }
 
@@ -38,20 +74,7 @@ pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int pre
   if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
   pk_mi355_recognizer *r = new pk_mi355_recognizer();
   auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
-  // pk_load's order (pocketkaldi.cc:81-131): fst, cmvn_stats, the AcousticModel keys, symbol_table.  Keys and host-side
-  // files first, so that a model file that cannot work is refused before the device is touched.
-  std::string path;
-  ModelConfig conf;
-  if (ConfigPath(config_path, "fst", &path) || !(r->fst = pk_mi355_fst_read(path.c_str()))) return failed();
-  if (ReadModelConfig(config_path, &conf)) return failed();
-  if (ConfigPath(config_path, "symbol_table", &path) || !(r->symtab = pk_mi355_symtab_read(path.c_str()))) return failed();
-  const int symbols = pk_mi355_symtab_size(r->symtab);
-  for (int a = 0; a < r->fst->num_arcs; ++a)       // pk_symboltable_get asserts this when the word is looked up
-    if (r->fst->arcs[a].olabel >= symbols) {
-      Fail(PK_MI355_E_INVALID, "%s: arc %d of the graph has output label %d, the symbol table has %d symbols", config_path, a,
-           r->fst->arcs[a].olabel, symbols);
-      return failed();
-    }
+  if (LoadRecognizerFiles(config_path, r)) return failed();
   float stats[kCmvnStats];
   if (pk_mi355_load(config_path, precision, &r->am, stats)) return failed();
   if (!(r->batch = pk_mi355_batch_create(r->am, stats, max_utts, max_total_samples))) return failed();
@@ -96,13 +119,7 @@ int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *wav
     if (!ok || count == 0) continue;                 // pocketkaldi.cc:240-243: no words, "" and 0.0f
     words.resize(count);
     pk_mi355_decoder_result(r->decoder, u, words.data(), count, &weight, &ok);
-    std::string &text = r->hyp[u];
-    for (int i = 0; i < count; ++i) {
-      const char *word = pk_mi355_symtab_get(r->symtab, words[i]);
-      if (!word) return pk_mi355_last_error_code();  // (cannot happen: load has checked every olabel)
-      if (i) text += ' ';                            // (:232-238: a space after every word, the last one dropped by pk_strlcpy)
-      text += word;
-    }
+    if ((rc = JoinWords(r->symtab, words.data(), count, &r->hyp[u]))) return rc;
     r->per_frame[u] = weight / pk_mi355_batch_num_frames(r->batch, u);     // :239
   }
   r->have = true;

@@ -164,6 +164,7 @@ struct Arena {
   int2 *rec;                    // (previous record, original arc id)
   int64_t cap;
   unsigned long long *top;      // records used
+  float *ac;                    // kAc only: a record's acoustic cost, parallel to rec (null otherwise, never read)
 };
 
 // One utterance's (slot's) decoding state for the duration of a launch.
@@ -190,13 +191,17 @@ __device__ __forceinline__ Work WorkOf(const DecArgs &A, int u, const Arena &are
 // Give each winner of touched-or-improved states a trace record and write it as a token into out[].
 // states[0..n): the states; arcs/srcs: the CSR the winners' ids index (emitting or epsilon);
 // only winners <= F are kept.  Returns the number written (all threads), or -1 when the arena is full.
-__device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *states, int n, float F, bool eps,
-                       uint64_t *key, int *tr, int *mark, Tok *out) {
+// kAc (pk_mi355_online_decoder_set_alignment): the record also keeps its acoustic cost, -s_ll[pdf of the winning arc]
+// (s_ll: the frame's row as staged, N1 applied -- the bits AlignKernel writes), 0 for an epsilon arc.
+template <bool kAc>
+__device__ int Resolve(Shared &sh, const float *s_ll, const DecArgs &A, const Arena &R, const int *states, int n, float F,
+                       bool eps, uint64_t *key, int *tr, int *mark, Tok *out) {
   int written = 0;
   for (int c0 = 0; c0 < n; c0 += kDecThreads) {
     const int i = c0 + threadIdx.x;
     int need = 0, s = 0, prev = -1, arc = -1;
     float c = 0.f;
+    [[maybe_unused]] float ac = 0.0f;
     if (i < n) {
       s = states[i];
       if (eps) mark[s] = 0;
@@ -212,6 +217,7 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *
         } else {
           prev = tr[A.e_src[id]];
           arc = A.e_arc[id].w;
+          if constexpr (kAc) ac = -s_ll[A.e_arc[id].y];
         }
       }
     }
@@ -225,6 +231,7 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *
     if (need) {
       const int r = int(base) + ex;
       R.rec[r] = make_int2(prev, arc);
+      if constexpr (kAc) R.ac[r] = ac;
       Tok t;
       t.state = s; t.cost = c; t.trace = r; t.pad = 0;
       out[written + ex] = t;
@@ -241,7 +248,7 @@ __device__ int Resolve(Shared &sh, const DecArgs &A, const Arena &R, const int *
 // -1, then frames t .. T - 1 of ll (ProcessEmitting, ProcessNonemitting, the next token list).  before(L, nL) runs
 // ahead of every emitting frame: nothing for DecodeKernel<false>, the trace compaction for DecodeKernel<true> and
 // OnlineDecodeKernel.
-template <typename Before>
+template <bool kAc, typename Before>
 __device__ __forceinline__ void DecodeFrames(Shared &sh, float *s_ll, const DecArgs &A, Work &w, const float *ll, int t,
                                              int T, Before before) {
   uint64_t *key = w.key;
@@ -318,7 +325,7 @@ __device__ __forceinline__ void DecodeFrames(Shared &sh, float *s_ll, const DecA
       cmin = BlockMinD(sh, cmin);
       nT = sh.cnt_touched;
       F = (float)(cmin + (double)adaptive_beam);       // the non-emitting cutoff ProcessEmitting returns
-      nF = Resolve(sh, A, w.arena, touched, nT, F, false, key, tr, mark, fa);
+      nF = Resolve<kAc>(sh, s_ll, A, w.arena, touched, nT, F, false, key, tr, mark, fa);
       if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
     }
     // ---- ProcessNonemitting (decoder.cc:186-222): frontier by frontier to the fixed point, bounded
@@ -341,7 +348,7 @@ __device__ __forceinline__ void DecodeFrames(Shared &sh, float *s_ll, const DecA
       const int nN = sh.cnt_nxt;
       nT = sh.cnt_touched;
       __syncthreads();
-      nF = Resolve(sh, A, w.arena, nxt, nN, F, true, key, tr, mark, fb);
+      nF = Resolve<kAc>(sh, s_ll, A, w.arena, nxt, nN, F, true, key, tr, mark, fb);
       if (nF < 0) { status = PK_MI355_E_CAPACITY; break; }
       Tok *x = fa; fa = fb; fb = x;
       ++rounds;
@@ -416,12 +423,21 @@ __device__ __forceinline__ int PathLen(const Arena &R, int trace) {
 __device__ __forceinline__ void FillPath(const Arena &R, int trace, int *path, int len) {
   for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) path[--len] = R.rec[x].y;
 }
+// the same walk, the records' acoustic costs beside their arcs (kAc)
+__device__ __forceinline__ void FillPathAc(const Arena &R, int trace, int *path, float *path_ac, int len) {
+  for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) {
+    path[--len] = R.rec[x].y;
+    path_ac[len] = R.ac[x];
+  }
+}
 
 // Mark the records reachable from the list's tokens, renumber them in creation order with an exclusive scan (a
 // record's predecessor is always older, so one forward pass remaps every `prev`), move them down, and rewrite the
 // tokens' trace (and the state table's, which the next emitting step reads).  Changes where records live, never a
-// result.
-__device__ void CompactTrace(Shared &sh, int2 *rec, int *remap, unsigned long long *top, Tok *L, int nL, int *tr) {
+// result.  kAc: rec_ac[i] moves wherever rec[i] does.
+template <bool kAc>
+__device__ void CompactTrace(Shared &sh, int2 *rec, float *rec_ac, int *remap, unsigned long long *top, Tok *L, int nL,
+                             int *tr) {
   const int n = (int)*top;
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += kDecThreads) remap[i] = 0;
@@ -434,7 +450,11 @@ __device__ void CompactTrace(Shared &sh, int2 *rec, int *remap, unsigned long lo
     const int i = c0 + threadIdx.x;
     const int alive = i < n ? __hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;   // set by atomics
     int2 r = make_int2(-1, -1);
-    if (alive) r = rec[i];
+    [[maybe_unused]] float ac = 0.0f;
+    if (alive) {
+      r = rec[i];
+      if constexpr (kAc) ac = rec_ac[i];
+    }
     int total;
     const int ex = BlockScan(sh, alive, &total);    // (its barriers: every read of this chunk is done)
     if (i < n) remap[i] = alive ? base + ex : -1;
@@ -442,6 +462,7 @@ __device__ void CompactTrace(Shared &sh, int2 *rec, int *remap, unsigned long lo
     if (alive) {
       r.x = r.x >= 0 ? remap[r.x] : -1;            // older: remapped in this chunk or an earlier one
       rec[base + ex] = r;
+      if constexpr (kAc) rec_ac[base + ex] = ac;
     }
     base += total;
     __syncthreads();
@@ -476,20 +497,20 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
     if (threadIdx.x == 0) s_top = 0;
     __syncthreads();
     const int64_t at = (int64_t)u * A.rec_cap;
-    w = WorkOf(A, u, Arena{A.rec + at, A.rec_cap, &s_top});
+    w = WorkOf(A, u, Arena{A.rec + at, A.rec_cap, &s_top, nullptr});
     int *remap = A.path + at;
-    DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [&](Tok *L, int nL) {
+    DecodeFrames<false>(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [&](Tok *L, int nL) {
       const unsigned long long top = s_top;
       peak = max(peak, (int)top);
       if (top > (unsigned long long)(A.rec_cap / 2)) {
-        CompactTrace(sh, w.arena.rec, remap, &s_top, L, nL, w.tr);
+        CompactTrace<false>(sh, w.arena.rec, nullptr, remap, &s_top, L, nL, w.tr);
         ++compactions;
       }
     });
     peak = (int)min((unsigned long long)A.rec_cap, max((unsigned long long)peak, s_top));   // (a failed bump overshoots)
   } else {
-    w = WorkOf(A, u, Arena{A.rec, A.rec_cap, A.rec_top});
-    DecodeFrames(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [](Tok *, int) {});
+    w = WorkOf(A, u, Arena{A.rec, A.rec_cap, A.rec_top, nullptr});
+    DecodeFrames<false>(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [](Tok *, int) {});
   }
   float weight = 0.f;
   int bi = -1;
@@ -595,9 +616,14 @@ __global__ void __launch_bounds__(kDecThreads) AlignKernel(AlignArgs A) {
 // (A.rec and A.path hold `cap` entries per slot); when it is more than half full before an emitting frame the
 // reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity are all
 // this kernel adds to the frame step: DecodeKernel<false> instantiates it with an empty `before` and never reads them.
+// kAc (pk_mi355_online_decoder_set_alignment): rec_ac and path_ac, `cap` floats per slot, run parallel to the slot's
+// records and path -- a frame's acoustic cost is kept when the frame is decoded, since its row is void afterwards.
+// With kAc = false neither pointer is read.
 
+template <bool kAc>
 __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, const OnlineCall *calls, OnlineState *states,
-                                                                    OnlineResult *results, int *remap_all, int64_t cap) {
+                                                                    OnlineResult *results, int *remap_all, int64_t cap,
+                                                                    float *rec_ac, float *path_ac) {
   extern __shared__ float s_ll[];
   __shared__ Shared sh;
   const OnlineCall call = calls[blockIdx.x];
@@ -609,13 +635,13 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
   __shared__ unsigned long long s_top;
   if (threadIdx.x == 0) s_top = st.top;
   __syncthreads();
-  Work w = WorkOf(A, u, Arena{A.rec + (int64_t)u * cap, cap, &s_top});   // the slot's own arena
+  Work w = WorkOf(A, u, Arena{A.rec + (int64_t)u * cap, cap, &s_top, kAc ? rec_ac + (int64_t)u * cap : nullptr});   // the slot's own arena
   int *remap = remap_all + (int64_t)u * cap;
   if (st.par) { Tok *x = w.L; w.L = w.Lnext; w.Lnext = x; }
   w.nL = st.nL; w.status = st.status; w.ok = st.ok; w.active = st.active; w.frames = st.frames; w.par = st.par;
   if (!w.status && w.ok)
-    DecodeFrames(sh, s_ll, A, w, A.ll + call.ll_off, st.started ? 0 : -1, call.T, [&](Tok *L, int nL) {
-      if (s_top > (unsigned long long)(cap / 2)) CompactTrace(sh, w.arena.rec, remap, &s_top, L, nL, w.tr);
+    DecodeFrames<kAc>(sh, s_ll, A, w, A.ll + call.ll_off, st.started ? 0 : -1, call.T, [&](Tok *L, int nL) {
+      if (s_top > (unsigned long long)(cap / 2)) CompactTrace<kAc>(sh, w.arena.rec, w.arena.ac, remap, &s_top, L, nL, w.tr);
     });
   // the path of the best token: BestPath's once the slot is closed, the partial hypothesis' otherwise
   const bool fin = call.final_ != 0;
@@ -631,7 +657,10 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
     if (!w.status && r.ok && bi >= 0) {
       r.weight = weight;
       r.path_len = PathLen(w.arena, w.L[bi].trace);
-      FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, r.path_len);
+      if constexpr (kAc)
+        FillPathAc(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, path_ac + (int64_t)u * cap, r.path_len);
+      else
+        FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, r.path_len);
       r.has_path = 1;
     }
     results[u] = r;
@@ -662,9 +691,13 @@ void LaunchAlign(const AlignArgs &A, hipStream_t stream) {
 }
 
 void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(OnlineDecodeKernel, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls, states,
-                     results, remap, cap);
+                        int64_t cap, float *rec_ac, float *path_ac, int n, hipStream_t stream) {
+  if (rec_ac && path_ac)
+    hipLaunchKernelGGL(OnlineDecodeKernel<true>, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls,
+                       states, results, remap, cap, rec_ac, path_ac);
+  else
+    hipLaunchKernelGGL(OnlineDecodeKernel<false>, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls,
+                       states, results, remap, cap, nullptr, nullptr);
 }
 
 }  // namespace pkmi

@@ -94,9 +94,11 @@ void LaunchDecode(const DecArgs &A, bool trace_gc, hipStream_t stream);
 void LaunchGatherPaths(UttResult *res, int n, const int *path, int *out, hipStream_t stream);
 // after the decode (and the gather) on the same stream: the frame of every emitting arc of the best paths
 void LaunchAlign(const AlignArgs &A, hipStream_t stream);
-// the new frames of n slots; states, results, remap and A.rec / A.path hold `cap` entries per slot
+// the new frames of n slots; states, results, remap and A.rec / A.path hold `cap` entries per slot.  rec_ac and path_ac
+// (`cap` floats per slot, both or neither): the alignment mode -- a record's acoustic cost kept beside it, a path's beside
+// its arcs (OnlineDecodeKernel<true>); null: OnlineDecodeKernel<false>
 void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, int n, hipStream_t stream);
+                        int64_t cap, float *rec_ac, float *path_ac, int n, hipStream_t stream);
 
 }  // namespace pkmi
 

@@ -342,6 +342,25 @@ int WordSegments(const ArcLabels &g, const int32_t *arcs, int num_arcs, const fl
   return n;
 }
 
+int PathFrames(const ArcLabels &g, const int32_t *arcs, const float *arc_ac, int num_arcs, int expect_frames,
+               int32_t *arc_ids, int32_t *trans_ids, float *ac, int max_frames) {
+  int frames = 0;
+  for (int i = 0; i < num_arcs; ++i) {
+    const int arc = arcs[i];
+    const int tid = (arc >= 0 && arc < (int)g.ilabel.size()) ? g.ilabel[arc] : 0;
+    if (tid == 0) continue;
+    if (frames < max_frames) {
+      if (arc_ids) arc_ids[frames] = arc;
+      if (trans_ids) trans_ids[frames] = tid;
+      if (ac) ac[frames] = arc_ac ? arc_ac[i] : NAN;
+    }
+    ++frames;
+  }
+  if (frames != expect_frames)
+    return Fail(PK_MI355_E_DEVICE, "alignment: the path has %d emitting arcs, %d frames were decoded", frames, expect_frames);
+  return frames;
+}
+
 int ConfigPath(const char *config_path, const char *key, std::string *out) {
   ConfigFile conf;
   int rc = conf.Read(config_path);

@@ -153,6 +153,13 @@ void LabelsOf(const pk_mi355_fst &f, ArcLabels *out);
 int WordSegments(const ArcLabels &g, const int32_t *arcs, int num_arcs, const float *ac, int num_ac, pk_mi355_word_t *out,
                  int max);
 
+// The frames of a path: its arcs whose ilabel is not 0, in path order.  arc_ac: one cost per arc of the path (an
+// epsilon arc's is ignored).  Per frame the arc id, its ilabel and its cost (any pointer may be null; at most
+// max_frames entries written).  Returns the frames, or PK_MI355_E_DEVICE when the path's emitting arcs are not
+// expect_frames -- the verdict AlignKernel gives for a path whose emitting arcs are not the utterance's frames.
+int PathFrames(const ArcLabels &g, const int32_t *arcs, const float *arc_ac, int num_arcs, int expect_frames,
+               int32_t *arc_ids, int32_t *trans_ids, float *ac, int max_frames);
+
 // pk_load's own keys (pocketkaldi.cc:81-88, 117-124): the path a key of the model file names, resolved against the
 // file's directory; a missing key is "Unable to find key '<key>' in <file>".
 int ConfigPath(const char *config_path, const char *key, std::string *out);

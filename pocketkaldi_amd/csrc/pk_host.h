@@ -8,6 +8,7 @@
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
 //   capi_recognizer.hip  pk_load + pk_process as one object over the entries of the others
+//   capi_online_recognizer.hip  pk_load + a live pk_process: the online scorer and the online decoder as one object
 //   capi_decoder.hip     (pk_decode.h) the decoder core -- graph, work areas, arenas -- and the batch decoder over it
 //   capi_online_decoder.hip  (pk_decode.h) the online decoder over the same core
 // (decode.hip and stream.hip hold the decoder's and the online scorer's kernels and their launchers, declared in
@@ -227,6 +228,21 @@ int StreamSlots(const pk_mi355_stream *s);
 hipStream_t StreamHipStream(const pk_mi355_stream *s);
 const float *StreamLoglikBase(const pk_mi355_stream *s);
 bool StreamSlotFlushed(const pk_mi355_stream *s, int slot);   // the last step flushed the slot (it was closed)
+
+// what the online recognizer (capi_online_recognizer.hip) needs to know of an online decoder beyond the ABI
+bool OnlineDecoderSlotOpen(const pk_mi355_online_decoder *o, int slot);
+
+// ------------------------------------------------------------------ pk_load's host half (capi_recognizer.hip)
+// What both recognizers read before the device is touched, in pk_load's order (pocketkaldi.cc:81-131): the graph, the
+// AcousticModel keys (checked, read again by pk_mi355_load), the symbol table, and every olabel against its size.
+struct RecognizerFiles {
+  pk_mi355_fst_t *fst = nullptr;
+  pk_mi355_symtab_t *symtab = nullptr;
+};
+int LoadRecognizerFiles(const char *config_path, RecognizerFiles *out);   // on failure the caller still frees *out
+void FreeRecognizerFiles(RecognizerFiles *f);
+// The words' strings joined by one space (pocketkaldi.cc:232-238); PK_MI355_E_INVALID for a word without a name.
+int JoinWords(const pk_mi355_symtab_t *symtab, const int *words, int count, std::string *text);
 
 }  // namespace pkhost
 

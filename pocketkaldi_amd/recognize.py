@@ -1,12 +1,18 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax]
+                                        [--online [--chunk-ms N] [--partials]]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
 that does not end in .wav is a list of wave files, one per line (main.cc:34-46); its waves are decoded together, as
 many per call as the recognizer holds.  --ctm prints the word times instead: "<file> 1 <start> <duration> <word>"
 per word segment of the best path, in seconds at the 10 ms frame shift (fbank.cc:35-42); segments without a word
 (word 0: what precedes the first word of a path) are skipped.
+
+--online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step,
+up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
+also prints every changed partial hypothesis to stderr: "<file>\t<seconds of audio fed>\t<text>".  --chunk-ms and
+--partials without --online are refused with the usage text.
 """
 import sys
 
@@ -18,19 +24,76 @@ MAX_SAMPLES = 16000 * 120
 
 
 def usage():
-    print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax]")
+    print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] "
+          "[--online [--chunk-ms N] [--partials]]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
     return 1
 
 
+def recognize_online(model_file, files, waves, chunk, reference_softmax, partials):
+    """Every wave through a slot of an OnlineRecognizer, `chunk` samples per step, MAX_UTTS waves at a time.
+    -> (the results in order, the symbol names by word id)"""
+    rec = pk.OnlineRecognizer(model_file, max_streams=min(max(len(waves), 1), MAX_UTTS),
+                              max_step_samples=chunk * min(max(len(waves), 1), MAX_UTTS))
+    try:
+        return stream_waves(rec, files, waves, chunk, reference_softmax, partials)
+    finally:
+        rec.destroy()
+
+
+def stream_waves(rec, files, waves, chunk, reference_softmax, partials):
+    if reference_softmax:
+        rec.am.set_softmax("reference")
+    results = [None] * len(waves)
+    for first in range(0, len(waves), MAX_UTTS):
+        group = list(range(first, min(first + MAX_UTTS, len(waves))))
+        pos, shown = {u: 0 for u in group}, {u: "" for u in group}
+        for u in group:
+            rec.open(u - first)
+        live = set(group)
+        while live:
+            closing = []
+            for u in sorted(live):
+                rec.push(u - first, waves[u][pos[u]:pos[u] + chunk])
+                pos[u] += chunk
+                if pos[u] >= len(waves[u]):          # the last chunk and the close in the same step
+                    rec.close(u - first)
+                    closing.append(u)
+            rec.step()
+            for u in sorted(live):
+                text = rec.partial(u - first)
+                if partials and text != shown[u]:
+                    sys.stderr.write("%s\t%.2f\t%s\n" % (files[u], min(pos[u], len(waves[u])) / 16000.0, text))
+                    shown[u] = text
+            for u in closing:
+                results[u] = rec.result(u - first)
+                live.discard(u)
+    names = {s.word: rec.symbols[s.word] for r in results for s in r.segments if s.word != 0}
+    return results, names
+
+
 def main(argv):
+    argv = list(argv)
+    chunk_ms = 100
+    if "--chunk-ms" in argv:
+        at = argv.index("--chunk-ms")
+        try:
+            chunk_ms = int(argv[at + 1])
+        except (IndexError, ValueError):
+            return usage()
+        if chunk_ms <= 0 or "--online" not in argv:
+            return usage()
+        del argv[at:at + 2]
     flags = [a for a in argv if a.startswith("--")]
     args = [a for a in argv if not a.startswith("--")]
-    if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax"}:
+    if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax", "--online", "--partials"}:
+        return usage()
+    if "--partials" in flags and "--online" not in flags:
         return usage()
     model_file, input_file = args
+    rec = None
     try:
         if input_file.endswith(".wav"):
             files = [input_file]
@@ -38,12 +101,16 @@ def main(argv):
             with open(input_file) as f:
                 files = [line.strip() for line in f if line.strip()]
         waves = [pk.read_wav(name) for name in files]
-        longest = max([len(w) for w in waves] + [1])
-        rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
-                            max_total_samples=max(longest, min(sum(len(w) for w in waves), MAX_SAMPLES)))
-        if "--reference-softmax" in flags:
-            rec.am.set_softmax("reference")
-        results = rec.process(waves)
+        if "--online" in flags:
+            results, names = recognize_online(model_file, files, waves, 16 * chunk_ms, "--reference-softmax" in flags,
+                                              "--partials" in flags)
+        else:
+            longest = max([len(w) for w in waves] + [1])
+            rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
+                                max_total_samples=max(longest, min(sum(len(w) for w in waves), MAX_SAMPLES)))
+            if "--reference-softmax" in flags:
+                rec.am.set_softmax("reference")
+            results, names = rec.process(waves), rec.symbols
     except (pk.PkError, OSError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
@@ -51,10 +118,11 @@ def main(argv):
         if "--ctm" in flags:
             for s in r.segments:
                 if s.word != 0:
-                    print("%s 1 %.2f %.2f %s" % (name, s.start_frame * FRAME_SHIFT, s.num_frames * FRAME_SHIFT, rec.symbols[s.word]))
+                    print("%s 1 %.2f %.2f %s" % (name, s.start_frame * FRAME_SHIFT, s.num_frames * FRAME_SHIFT, names[s.word]))
         else:
             sys.stdout.write("%s\t%s\t%f\n" % (name, r.text, r.loglikelihood_per_frame))
-    rec.close()
+    if rec is not None:
+        rec.close()
     return 0
 
 
