@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 
+#include "pk_f16_layout.h"
 #include "pk_host.h"
 
 using namespace pkmi;
@@ -227,8 +228,7 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
     if (L.type != PK_NNET_LINEAR_LAYER) continue;
     const DevLinear &D = am->lin[li++];
     if (f16) {
-      // W stays [out][in] (k contiguous), split into fp16 hi and lo = fp16(w - hi), the
-      // pairs interleaved in chunks of 8 k's (see gemm_f16.hip).
+      // W stays [out][in] (k contiguous), split into fp16 (hi, lo) pairs and interleaved as pk_f16_layout.h has it.
       // Range safety: the layer's weights are first multiplied by 2^w_exp -- exact in fp32 -- chosen so that
       // max |W| lands in [2^13, 2^14): every weight within 2^-16 of the largest then has a NORMAL lo half
       // (lo = fp16(w - hi) needs |w| >= 2^-3 for that), whatever the scale the model was trained at; the GEMM's
@@ -249,12 +249,10 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
       _Float16 *w2 = reinterpret_cast<_Float16 *>(blob.data() + D.wt_off);
       for (int o = 0; o < D.N; ++o)
         for (int k = 0; k < D.K; ++k) {
-          float v = L.W[(size_t)o * D.K + k] * w_scale;
-          v = std::min(std::max(v, -65504.0f), 65504.0f);
-          const _Float16 hi = static_cast<_Float16>(v);
-          _Float16 *dst = w2 + (size_t)o * 2 * D.Kpad + (k >> 3) * 16 + (k & 7);
-          dst[0] = hi;
-          dst[8] = static_cast<_Float16>(v - static_cast<float>(hi));
+          const SplitOut s = Split(L.W[(size_t)o * D.K + k] * w_scale);
+          _Float16 *dst = HiPtr(w2 + (size_t)o * 2 * D.Kpad, k);
+          dst[0] = s.hi;
+          dst[kLoHalves] = s.lo;
         }
     } else {
       float *wt = blob.data() + D.wt_off;

@@ -1,39 +1,35 @@
 // gemm_f16.hip -- the affine layers on the fp16 matrix cores at fp32-class accuracy
 // ("f16x3" precision mode; the default mode is the bit-exact fp32 kernel in gemm.hip).
 //
-// Every fp32 operand is carried as a pair of fp16 values, x = hi + lo with
-// hi = fp16(x), lo = fp16(x - hi)   (x - hi is exact in fp32), and
+// Every fp32 operand is carried as a pair of fp16 values x = hi + lo (pk_f16_layout.h: Split), and
 //
 //   D[m][n] = sum_k Xhi Whi + Xhi Wlo + Xlo Whi          (Xlo Wlo ~ 2^-22, dropped)
 //
-// three fp16 MFMAs per block into ONE fp32 accumulator (fp16 products are exact in fp32; the
-// cross terms sit 11 bits below the main term and fit the accumulator).  Two kernels share the
-// layouts, the tile and the LDS-DMA ring described here:
+// three fp16 MFMAs per block into ONE fp32 accumulator (fp16 products are exact in fp32; the cross terms sit 11 bits
+// below the main term and fit the accumulator).  Measured error vs the fp32 reference chain is ~1e-6 relative on
+// log-likelihoods -- inside the 1e-4 contract, not bit-exact.  Two kernels:
 //   GemmF16K32Kernel  v_mfma_f32_16x16x32_f16, k32 steps -- what f16x3 runs on (round 3; further down)
 //   GemmF16Kernel     v_mfma_f32_32x32x16_f16, k16 steps -- the round-2 form, kept for the plain-fp16
-//                     mode (one MFMA per product), which is bound by the operand stream, not by the clock.  Measured error vs the fp32 reference chain is ~1e-6
-// relative on log-likelihoods -- inside the 1e-4 contract, not bit-exact.  Range: fp16
-// saturates at 65504; the split clamps instead of overflowing.
+//                     mode (one MFMA per product), which is bound by the operand stream, not by the clock.
+// What they share is written once: the operand rows, the half-slab, the W row -> column maps and the swizzles in
+// pk_f16_layout.h; the tile walk (WalkTile), the exponent scaling (Exps), the range words (RangeAcc, PublishRange)
+// and the diagnostic stamps (Stamps) below; the launcher's kernel table (kGemmF16).  Each kernel keeps its own
+// DMA role, k loop and write-out: moved into shared functions, those compile to other instructions.
 //
-// Layout (everything frame-major here): X = [rows][K] (rows = frames, k contiguous),
-// W = [N][K] -- the model file's own [out][in] order -- D = [rows][N].  A row stores its
-// (hi, lo) pairs interleaved in chunks of 8 k's: [hi k0..7][lo k0..7][hi k8..15][lo ...],
-// so the 64 bytes one k16 step needs of a row are contiguous.  Layer 1 reads the CMVN
-// output [frames][40] (5 chunks per frame, row stride 80 halves) with K = 440: the
-// splice (am.cc:65-88) is again just an address function.
+// Everything is frame-major here: X = [rows][K] (rows = frames, k contiguous), W = [N][K] -- the model file's own
+// [out][in] order -- D = [rows][N].  Layer 1 reads the CMVN output [frames][40] (5 chunks per frame, row stride 80
+// halves) with K = 440: the splice (am.cc:65-88) is again just an address function.
 //
-// Tile 256 x 256 per 512-thread workgroup (8 waves as 2 x 4, 128 x 64 per wave = 4 x 2
-// MFMA tiles, 128 accumulator registers).  The k loop advances in k16 "half-slabs" of
-// 32 KiB (256 X rows + 256 W rows x 64 bytes) through a ring of FOUR LDS buffers filled
-// by LDS-DMA three half-slabs ahead (the DMA wait + barrier was where the waves sat:
-// 33 % of their lifetime with a one-slab lead).  XOR swizzle on the DMA SOURCE address
-// (linear LDS destination) and on the ds_read_b128 fragment reads (conflict-free).  The
-// two column sub-tiles of a wave take interleaved columns, so a lane holds adjacent output
-// columns; the epilogue stages each wave's rows through the (by then idle) LDS ring and
-// writes them as whole 256-byte row pieces, 16 bytes per lane.
-// (Measured alternative: 256 x 128 tiles, 4 waves, two workgroups per CU -- independent
-// barriers, one tile's epilogue under the other's MFMAs -- 5 % slower: the operand traffic
-// L2 -> LDS per MFMA is 1.5 x, and the chip is power-limited in this mode.)
+// Tile 256 x 256 per 512-thread workgroup (8 waves as 2 x 4, 128 x 64 per wave = 4 x 2 MFMA tiles, 128 accumulator
+// registers).  The k loop advances in k16 "half-slabs" of 32 KiB through a ring of FOUR LDS buffers filled by LDS-DMA
+// three half-slabs ahead (the DMA wait + barrier was where the waves sat: 33 % of their lifetime with a one-slab
+// lead).  XOR swizzle on the DMA SOURCE address (linear LDS destination) and on the ds_read_b128 fragment reads
+// (conflict-free).  The column sub-tiles of a wave take interleaved columns, so a lane holds adjacent output columns;
+// the epilogue stages each wave's rows through the (by then idle) LDS ring and writes them as whole 256-byte row
+// pieces, 16 bytes per lane.
+// (Measured alternative: 256 x 128 tiles, 4 waves, two workgroups per CU -- independent barriers, one tile's epilogue
+// under the other's MFMAs -- 5 % slower: the operand traffic L2 -> LDS per MFMA is 1.5 x, and the chip is
+// power-limited in this mode.)
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -42,6 +38,7 @@
 #include <stdlib.h>
 #include <mutex>
 
+#include "pk_f16_layout.h"
 #include "pk_kernels.h"
 
 namespace pkmi {
@@ -60,36 +57,8 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) void *GlobalPtr;
 typedef __attribute__((address_space(3))) void *LdsPtr;
 
-constexpr int kT = kTileF16;                  // 256: tile edge
-constexpr int kStepK = 16;                    // k per half-slab = one MFMA k16 step
 constexpr int kThreadsF16 = 512;
-constexpr int kOperandBytes = kT * 64;        // one operand of one half-slab: 256 rows x 64 B
-constexpr int kHalfSlabBytes = 2 * kOperandBytes;   // X rows, then W rows: 32 KiB
-constexpr int kRingF16 = 4;
 constexpr int kPiecesPerWave = 4;             // 32 x 1 KiB pieces per half-slab / 8 waves
-
-// LDS row (0..255) of the W tile -> column n of the tile.  Within each block of 64
-// columns sub-tile y of a wave owns columns 2 i' + y, stored as 32 consecutive LDS rows.
-__device__ __forceinline__ int WRowToCol(int row) {
-  return (row & ~63) + 2 * (row & 31) + ((row >> 5) & 1);
-}
-
-// byte offset of logical 16-byte position q of LDS row `row`; the four positions of a
-// 64-byte row are [k0..7 hi][k0..7 lo][k8..15 hi][k8..15 lo]
-__device__ __forceinline__ int SwzOff(int row, int q) {
-  return row * 64 + ((q ^ ((row >> 2) & 3)) << 4);
-}
-
-struct SplitOut {
-  _Float16 hi, lo;
-};
-__device__ __forceinline__ SplitOut Split(float v) {
-  v = fminf(fmaxf(v, -65504.0f), 65504.0f);
-  SplitOut s;
-  s.hi = static_cast<_Float16>(v);
-  s.lo = static_cast<_Float16>(v - static_cast<float>(s.hi));
-  return s;
-}
 
 // 2^e as a float (|e| <= 126: the host clamps the exponents it stores)
 __device__ __forceinline__ float Pow2(int e) { return __int_as_float((127 + e) << 23); }
@@ -131,7 +100,16 @@ __device__ __forceinline__ float RangeValue(short bits) {      // the fp16 whose
 
 // The three exponent words of a launch (wave-uniform, fetched before the first DMA is issued: left to the
 // compiler they became vector loads at the top of the epilogue, a full memory round trip with the matrix pipes idle).
-struct Exps { int e_in_w, e_out; };
+// Scaling: the accumulators hold sum (X 2^e_in)(W 2^e_w); what is written is
+//   v 2^e_out,  v = acc 2^-(e_in + e_w) + bias        (nnet.cc:32-35)
+// as ONE fma per value, acc * AccScale() + bias * BiasScale(): every factor is a power of two, so this is
+// the rounding of v itself, scaled exactly (ReLU commutes with a positive factor).  Costs what the plain bias
+// add cost (v_pk_fma_f32 for v_pk_add_f32).  e_out is 0 for fp32 output.
+struct Exps {
+  int e_in_w, e_out;
+  __device__ __forceinline__ float AccScale() const { return Pow2(e_out - e_in_w); }
+  __device__ __forceinline__ float BiasScale() const { return Pow2(e_out); }
+};
 __device__ __forceinline__ Exps LoadExps(const GemmF16Args &a, bool last) {
   Exps e;
   e.e_in_w = __builtin_amdgcn_readfirstlane(*a.e_in + *a.e_w);
@@ -139,25 +117,11 @@ __device__ __forceinline__ Exps LoadExps(const GemmF16Args &a, bool last) {
   return e;
 }
 
-// Diagnostic build only (tools/ubench/f16_gemm_probe.hip defines PK_F16_STAMPS): s_memtime stamps
-// around the three waits of a step, summed per wave.  In the product build PK_STAMP is nothing.
-#ifdef PK_F16_STAMPS
-#define PK_STAMP(i) do { const long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_last; st_last = t_; } while (0)
-#else
-#define PK_STAMP(i) do { } while (0)
-#endif
-
-// TERMS = 3: the split-fp16 arithmetic above.  TERMS = 1 (PK_MI355_PRECISION_F16): the hi halves only --
-// plain fp16 operands, one MFMA per product; same layouts (the lo halves travel unused), so the mode
-// is bound by the L2 -> LDS operand stream rather than by the matrix pipes.
-template <bool RELU, bool LAST, int TERMS>
-__global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the ring: 4 x 32 KiB
-#ifdef PK_F16_STAMPS
-  const long long st_kernel = __builtin_amdgcn_s_memtime();
-#endif
-
-  // XCD-aware tile walk, as in gemm.hip: contiguous ids per XCD, walk_m x walk_n (4 x 4) super-tiles
+// XCD-aware tile walk, as in gemm.hip: workgroup ids are made contiguous per XCD and walk walk_m x walk_n super-tiles
+// (4 x 4: the 32 workgroups resident on an XCD then cover 8 x 4 tiles and share 8 X and 4 W panels in that XCD's L2).
+// Ids past the last super-tile (the grid is rounded up to a multiple of 8) fall outside the tile range.
+struct Tile { int tm, tn; };
+__device__ __forceinline__ Tile WalkTile(const GemmF16Args &a) {
   const int nblk = gridDim.x;                       // multiple of 8
   const int b = blockIdx.x;
   const int wg = (b % 8) * (nblk / 8) + b / 8;
@@ -166,8 +130,48 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   const int s = wg / per, w = wg % per;
   const int tm = (s % super_m) * a.walk_m + (w % a.walk_m);
   const int tn = (s / super_m) * a.walk_n + (w / a.walk_m);
-  if (tm >= a.tiles_m || tn >= a.tiles_n) return;
-  const int m0 = tm * kT, n0 = tn * kT;
+  return Tile{tm, tn};
+}
+
+// Diagnostic build only (tools/ubench/f16_gemm_probe.hip defines PK_F16_STAMPS): s_memtime stamps
+// around the three waits of a step, summed per wave.  In the product build Stamps is empty and does nothing.
+struct Stamps {
+#ifdef PK_F16_STAMPS
+  long long kernel = __builtin_amdgcn_s_memtime(), begin, last, loop_end, acc[4] = {0, 0, 0, 0};
+  __device__ __forceinline__ void LoopBegin() { begin = last = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void Mark(int i) { const long long t = __builtin_amdgcn_s_memtime(); acc[i] += t - last; last = t; }
+  __device__ __forceinline__ void LoopEnd() { loop_end = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void Write(int lane, int wave) const {
+    if (lane == 0 && blockIdx.x < 256) {
+      long long *o = pk_f16_stamps + (blockIdx.x * 8 + wave) * 8;
+      o[0] = loop_end - begin;                             // k loop, cycles
+      o[1] = acc[0];                                       // MFMA / issue segments (barrier release -> next lgkm wait)
+      o[2] = acc[1];                                       // lgkmcnt(0) wait
+      o[3] = acc[2];                                       // vmcnt wait
+      o[4] = acc[3];                                       // barrier wait
+      o[5] = begin - kernel;                               // prologue (start -> first fragments requested)
+      o[6] = __builtin_amdgcn_s_memtime() - loop_end;      // epilogue (stores issued)
+    }
+  }
+#else
+  __device__ __forceinline__ void LoopBegin() {}
+  __device__ __forceinline__ void Mark(int) {}
+  __device__ __forceinline__ void LoopEnd() {}
+  __device__ __forceinline__ void Write(int, int) const {}
+#endif
+};
+
+// TERMS = 3: the split-fp16 arithmetic above.  TERMS = 1 (PK_MI355_PRECISION_F16): the hi halves only --
+// plain fp16 operands, one MFMA per product; same layouts (the lo halves travel unused), so the mode
+// is bound by the L2 -> LDS operand stream rather than by the matrix pipes.
+template <bool RELU, bool LAST, int TERMS>
+__global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the ring: 4 x 32 KiB
+  Stamps st;
+
+  const Tile tile = WalkTile(a);
+  if (tile.tm >= a.tiles_m || tile.tn >= a.tiles_n) return;
+  const int m0 = tile.tm * kT, n0 = tile.tn * kT;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -198,15 +202,15 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
     for (int p = 0; p < 2; ++p)
       xoff[p] += (uint32_t)((int64_t)a.row_shift4[(m0 + (wave * 2 + p) * 16 + lr) >> 2] * a.ldx * sizeof(_Float16));
   }
-  // one of this wave's four DMA pieces of k16 step h (32 halves of every row): piece = 2 op + p
-  auto issue_piece = [&](int h, int slot, int piece) {
+  // piece 0..3 of k16 step h (32 halves of every row), into ring slot h % 4: operand piece >> 1, p = piece & 1
+  auto issue_piece = [&](int h, int piece) {
     const int op = piece >> 1, p = piece & 1;
-    unsigned char *dst = smem + slot * kHalfSlabBytes + op * kOperandBytes + (wave * 2 + p) * 1024;
+    unsigned char *dst = smem + (h & (kRingF16 - 1)) * kHalfSlabBytes + op * kOperandBytes + (wave * 2 + p) * 1024;
     DmaScalarBase(reinterpret_cast<const float *>(dst), sbase[p][op] + h * 64, op == 0 ? xoff[p] : voff[1]);
   };
-  auto issue_step = [&](int h, int slot) {
+  auto issue_step = [&](int h) {
 #pragma unroll
-    for (int piece = 0; piece < kPiecesPerWave; ++piece) issue_piece(h, slot, piece);
+    for (int piece = 0; piece < kPiecesPerWave; ++piece) issue_piece(h, piece);
   };
 
   f32x16 acc[4][2];
@@ -241,10 +245,10 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   // the first MFMA after the barrier.  (Issued back to back behind the barrier, by both waves of a
   // SIMD at once, the pieces cost 4-5 %.)
   const int nsteps = a.K / kStepK;
-  issue_step(0, 0);
-  if (nsteps > 1) issue_step(1, 1);
-  if (nsteps > 2) issue_step(2, 2);
-  if (nsteps > 3) issue_step(3, 3);
+  issue_step(0);
+  if (nsteps > 1) issue_step(1);
+  if (nsteps > 2) issue_step(2);
+  if (nsteps > 3) issue_step(3);
   if (nsteps > 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * kPiecesPerWave) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -266,11 +270,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   read_b(smem, 0);
   read_a(smem, 0, ah[0], al[0]);
 
-#ifdef PK_F16_STAMPS
-  long long st_acc[4] = {0, 0, 0, 0};
-  long long st_last = __builtin_amdgcn_s_memtime();
-  const long long st_begin = st_last;
-#endif
+  st.LoopBegin();
   auto mfma3 = [&](int x, int y, int cur, int par, int which) {
     // the three products of one (x, y) tile and k16 step: hi lo, lo hi, hi hi -- in this order
     if (TERMS == 3 && which == 0) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur], bl[par][y], acc[x][y], 0, 0, 0);
@@ -282,9 +282,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   // per PAIR of steps, the next pair's DMA issued right behind it: 3.5 % slower -- the barrier wait
   // of the older wave of a SIMD is the time its partner needs the matrix pipe for, not lost time.)
   auto step = [&](int h, const int par) {             // par = h & 1, compile-time in the body
-    const int slot = h & (kRingF16 - 1);
-    const int prev_slot = (h - 1) & (kRingF16 - 1);
-    const unsigned char *base = smem + slot * kHalfSlabBytes;
+    const unsigned char *base = smem + (h & (kRingF16 - 1)) * kHalfSlabBytes;
     const unsigned char *next = smem + ((h + 1) & (kRingF16 - 1)) * kHalfSlabBytes;
     const bool dma_tail = h >= 1 && h + 3 < nsteps;   // pieces 2, 3 of step h + 3 (its pieces 0, 1 went out in step h - 1)
     const bool dma_head = h + 4 < nsteps;             // pieces 0, 1 of step h + 4
@@ -292,16 +290,16 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
     for (int x = 0; x < 4; ++x) {
       const int cur = x & 1;
       if (x == 3) {
-        PK_STAMP(0);
+        st.Mark(0);
         __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0): all of step h is in registers
-        PK_STAMP(1);
+        st.Mark(1);
         // this wave's pieces of step h+1 landed; steps h+2, h+3 may stay in flight
         if (h + 3 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kPiecesPerWave) : "memory");
         else if (h + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPiecesPerWave) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PK_STAMP(2);
+        st.Mark(2);
         __builtin_amdgcn_s_barrier();
-        PK_STAMP(3);
+        st.Mark(3);
         __builtin_amdgcn_sched_barrier(0);
         mfma3(x, 0, cur, par, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -311,12 +309,12 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
         mfma3(x, 0, cur, par, 1);
         mfma3(x, 0, cur, par, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (dma_head) issue_piece(h + 4, slot, 0);    // nobody reads step h's buffer any more
+        if (dma_head) issue_piece(h + 4, 0);          // into step h's buffer: nobody reads it any more
         __builtin_amdgcn_sched_barrier(0);
         mfma3(x, 1, cur, par, 0);
         mfma3(x, 1, cur, par, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (dma_head) issue_piece(h + 4, slot, 1);
+        if (dma_head) issue_piece(h + 4, 1);
         __builtin_amdgcn_sched_barrier(0);
         mfma3(x, 1, cur, par, 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -326,13 +324,13 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
         mfma3(x, 0, cur, par, 0);
         mfma3(x, 0, cur, par, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (x == 0 && dma_tail) issue_piece(h + 3, prev_slot, 2);
+        if (x == 0 && dma_tail) issue_piece(h + 3, 2);
         __builtin_amdgcn_sched_barrier(0);
         mfma3(x, 0, cur, par, 2);
         mfma3(x, 1, cur, par, 0);
         mfma3(x, 1, cur, par, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (x == 0 && dma_tail) issue_piece(h + 3, prev_slot, 3);
+        if (x == 0 && dma_tail) issue_piece(h + 3, 3);
         __builtin_amdgcn_sched_barrier(0);
         mfma3(x, 1, cur, par, 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -346,9 +344,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
     if (h + 1 < nsteps) step(h + 1, 1);
   }
 
-#ifdef PK_F16_STAMPS
-  const long long st_loop_end = __builtin_amdgcn_s_memtime();
-#endif
+  st.LoopEnd();
   // ---- epilogue: acc[x][y][r] = D[M0 + 32x + i'][N0 + y], N0 = n0 + wn*64 + 2 l31,
   // i' = (r & 3) + 8 (r >> 2) + 4 kg; bias (nnet.cc:32-35), ReLU (nnet.cc:56-58).
   // A lane holds two adjacent columns of 64 rows: stored from the registers that is 128 four-byte
@@ -360,13 +356,12 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   // per lane: one store instruction = four whole 256-byte row pieces.  No barrier: a wave reads
   // back only what it wrote itself.
   const int M0 = m0 + wm * 128, N0 = n0 + wn * 64 + 2 * l31;
-  // operand exponents (gemm_f16.hip header of GemmF16K32Kernel's epilogue): v = acc * 2^(e_out - e_in - e_w) + bias * 2^e_out
-  const float acc_scale = Pow2(ex.e_out - ex.e_in_w);
-  const f32x2 bias = *reinterpret_cast<const f32x2 *>(a.bias + N0) * Pow2(ex.e_out);
+  const float acc_scale = ex.AccScale();
+  const f32x2 bias = *reinterpret_cast<const f32x2 *>(a.bias + N0) * ex.BiasScale();
   s16x2 hmax = s16x2{0, 0};
   unsigned char *stage = smem + wave * (2 * 8192);
   // byte offset of this lane's pair in a staged row: fp32 pair, or the (hi, lo) halves of chunk l31 / 4
-  const int pair_byte = LAST ? l31 * 8 : (l31 >> 2) * 32 + (l31 & 3) * 4;
+  const int pair_byte = LAST ? l31 * 8 : HiByteOfGroup(l31, 2);
   // this wave's 64 columns start at byte 256 * (column block) of an output row in both formats
   unsigned char *out_rows = LAST ? reinterpret_cast<unsigned char *>(a.out_f32 + (int64_t)M0 * a.ldo + n0 + wn * 64)
                                  : reinterpret_cast<unsigned char *>(a.out + (int64_t)M0 * a.ldo + 2 * (n0 + wn * 64));
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
         const f16x2 hi = f16x2{s0.hi, s1.hi};
         hmax = RangeAcc<RELU>(hmax, hi);
         *reinterpret_cast<f16x2 *>(buf + row * 256 + pair_byte) = hi;
-        *reinterpret_cast<f16x2 *>(buf + row * 256 + pair_byte + 16) = f16x2{s0.lo, s1.lo};
+        *reinterpret_cast<f16x2 *>(buf + row * 256 + pair_byte + 2 * kLoHalves) = f16x2{s0.lo, s1.lo};
       }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);                 // this wave's LDS writes are in
@@ -403,18 +398,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
   }
   if (!LAST && a.range)
     PublishRange(a.range, blockIdx.x * 8 + wave, RangeValue(hmax[0] > hmax[1] ? hmax[0] : hmax[1]));
-#ifdef PK_F16_STAMPS
-  if (lane == 0 && blockIdx.x < 256) {
-    long long *o = pk_f16_stamps + (blockIdx.x * 8 + wave) * 8;
-    o[0] = st_loop_end - st_begin;                       // k loop, cycles
-    o[1] = st_acc[0];                                    // MFMA / issue segments (barrier release -> next lgkm wait)
-    o[2] = st_acc[1];                                    // lgkmcnt(0) wait
-    o[3] = st_acc[2];                                    // vmcnt wait
-    o[4] = st_acc[3];                                    // barrier wait
-    o[5] = st_begin - st_kernel;                         // prologue (start -> first fragments requested)
-    o[6] = __builtin_amdgcn_s_memtime() - st_loop_end;   // epilogue (stores issued)
-  }
-#endif
+  st.Write(lane, wave);
 }
 
 // ======================================================================= 16 x 16 x 32 form
@@ -435,34 +419,16 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16Kernel(GemmF16Args a) {
 //   * a wave's 128 x 64 is 8 x 4 tiles of 16 x 16; the four column tiles take interleaved columns
 //     (tile y owns columns 4 j + y of the wave's 64), so a lane holds four adjacent output columns of
 //     four rows per row tile and stages them 16 bytes (fp32) or 8 + 8 bytes (hi, lo halves) at a time.
-__device__ __forceinline__ int Gray2(int c) { return c ^ (c >> 1); }
-__device__ __forceinline__ int WRowToCol16(int row) {
-  return (row & ~63) + 4 * (row & 15) + ((row >> 4) & 3);
-}
-__device__ __forceinline__ int SwzOff16(int row, int q) {
-  return row * 64 + ((q ^ Gray2((row >> 2) & 3)) << 4);
-}
 
 template <bool RELU, bool LAST, int TERMS>
 __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the ring: 4 x 32 KiB = 2 pair slots
   constexpr int kPairBytes = 2 * kHalfSlabBytes;
-#ifdef PK_F16_STAMPS
-  const long long st_kernel = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps st;
 
-  // XCD-aware tile walk: workgroup ids are made contiguous per XCD and walk walk_m x walk_n super-tiles (4 x 4: the
-  // 32 workgroups resident on an XCD then cover 8 x 4 tiles and share 8 X and 4 W panels in that XCD's L2)
-  const int nblk = gridDim.x;                       // multiple of 8
-  const int b = blockIdx.x;
-  const int wg = (b % 8) * (nblk / 8) + b / 8;
-  const int super_m = (a.tiles_m + a.walk_m - 1) / a.walk_m;
-  const int per = a.walk_m * a.walk_n;
-  const int s = wg / per, w = wg % per;
-  const int tm = (s % super_m) * a.walk_m + (w % a.walk_m);
-  const int tn = (s / super_m) * a.walk_n + (w / a.walk_m);
-  if (tm >= a.tiles_m || tn >= a.tiles_n) return;
-  const int m0 = tm * kT, n0 = tn * kT;
+  const Tile tile = WalkTile(a);
+  if (tile.tm >= a.tiles_m || tile.tn >= a.tiles_n) return;
+  const int m0 = tile.tm * kT, n0 = tile.tn * kT;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -539,11 +505,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a
   for (int y = 0; y < 4; ++y) read_b(smem, 0, y);
   read_a(smem, 0, ah[0], al[0]);
 
-#ifdef PK_F16_STAMPS
-  long long st_acc[4] = {0, 0, 0, 0};
-  long long st_last = __builtin_amdgcn_s_memtime();
-  const long long st_begin = st_last;
-#endif
+  st.LoopBegin();
   // one term of the four column tiles of row tile x: consecutive MFMAs are independent
   auto mfma_row = [&](int x, int cur, int par, int which) {
 #pragma unroll
@@ -573,13 +535,13 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a
     for (int x = 0; x < 8; ++x) {
       const int cur = x & 1;
       if (x == 7) {
-        PK_STAMP(0);
+        st.Mark(0);
         __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0): all of step P is in registers
-        PK_STAMP(1);
+        st.Mark(1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PK_STAMP(2);
+        st.Mark(2);
         __builtin_amdgcn_s_barrier();
-        PK_STAMP(3);
+        st.Mark(3);
         __builtin_amdgcn_sched_barrier(0);
         if (TERMS == 3) {
           mfma_row(x, cur, par, 0);
@@ -628,26 +590,19 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a
     if (P + 1 < npairs) step(P + 1, 1);
   }
 
-#ifdef PK_F16_STAMPS
-  const long long st_loop_end = __builtin_amdgcn_s_memtime();
-#endif
+  st.LoopEnd();
   // ---- epilogue: acc[x][y][r] = D[M0 + 16 x + 4 g + r][N0 + 4 l15 + y]; bias (nnet.cc:32-35), ReLU
   // (nnet.cc:56-58).  Staged through this wave's own 2 x 8 KiB of the idle ring, 32 rows (two row tiles)
   // at a time, as the rows will lie in memory -- 256 bytes per row: 64 fp32 logits, or 64 x (hi, lo)
   // halves in chunks of 8 -- and written out 16 bytes per lane: one store instruction = four whole
   // 256-byte row pieces.  No barrier: a wave reads back only what it wrote itself.
   const int M0 = m0 + wm * 128, N0 = n0 + wn * 64 + 4 * l15;
-  // Operand exponents: the accumulators hold sum (X 2^e_in)(W 2^e_w); what is written is
-  //   v 2^e_out,  v = acc 2^-(e_in + e_w) + bias        (nnet.cc:32-35)
-  // as ONE fma per value, acc * 2^(e_out - e_in - e_w) + bias * 2^e_out: every factor is a power of two, so this is
-  // the rounding of v itself, scaled exactly (ReLU commutes with a positive factor).  Costs what the plain bias
-  // add cost (v_pk_fma_f32 for v_pk_add_f32).  e_out is 0 for fp32 output.
-  const float acc_scale = Pow2(ex.e_out - ex.e_in_w);
-  const f32x4v bias = *reinterpret_cast<const f32x4v *>(a.bias + N0) * Pow2(ex.e_out);
+  const float acc_scale = ex.AccScale();
+  const f32x4v bias = *reinterpret_cast<const f32x4v *>(a.bias + N0) * ex.BiasScale();
   const f32x4v acc_scale4 = f32x4v{acc_scale, acc_scale, acc_scale, acc_scale};
   unsigned char *stage = smem + wave * (2 * 8192);
   // byte offset of this lane's four columns in a staged row: fp32 quad, or the hi halves of chunk l15 / 2
-  const int quad_byte = LAST ? l15 * 16 : (l15 >> 1) * 32 + (l15 & 1) * 8;
+  const int quad_byte = LAST ? l15 * 16 : HiByteOfGroup(l15, 4);
   unsigned char *out_rows = LAST ? reinterpret_cast<unsigned char *>(a.out_f32 + (int64_t)M0 * a.ldo + n0 + wn * 64)
                                  : reinterpret_cast<unsigned char *>(a.out + (int64_t)M0 * a.ldo + 2 * (n0 + wn * 64));
   const int64_t row_bytes = a.ldo * (LAST ? (int64_t)sizeof(float) : (int64_t)sizeof(_Float16));
@@ -684,7 +639,7 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a
           const f16x4 hi = f16x4{s0.hi, s1.hi, s2.hi, s3.hi};
           hmax[r & 1] = RangeAcc<RELU>(hmax[r & 1], hi);
           *reinterpret_cast<f16x4 *>(buf + row * 256 + quad_byte) = hi;
-          *reinterpret_cast<f16x4 *>(buf + row * 256 + quad_byte + 16) = f16x4{s0.lo, s1.lo, s2.lo, s3.lo};
+          *reinterpret_cast<f16x4 *>(buf + row * 256 + quad_byte + 2 * kLoHalves) = f16x4{s0.lo, s1.lo, s2.lo, s3.lo};
         }
       }
     }
@@ -702,23 +657,11 @@ __global__ __launch_bounds__(kThreadsF16, 2) void GemmF16K32Kernel(GemmF16Args a
     const s16x2 h2 = __builtin_elementwise_max(s16x2{h4[0], h4[1]}, s16x2{h4[2], h4[3]});
     PublishRange(a.range, blockIdx.x * 8 + wave, RangeValue(h2[0] > h2[1] ? h2[0] : h2[1]));
   }
-#ifdef PK_F16_STAMPS
-  if (lane == 0 && blockIdx.x < 256) {
-    long long *o = pk_f16_stamps + (blockIdx.x * 8 + wave) * 8;
-    o[0] = st_loop_end - st_begin;                       // k loop, cycles
-    o[1] = st_acc[0];                                    // MFMA / issue segments (barrier release -> next lgkm wait)
-    o[2] = st_acc[1];                                    // lgkmcnt(0) wait
-    o[3] = st_acc[2];                                    // vmcnt wait
-    o[4] = st_acc[3];                                    // barrier wait
-    o[5] = st_begin - st_kernel;                         // prologue
-    o[6] = __builtin_amdgcn_s_memtime() - st_loop_end;   // epilogue (stores issued)
-  }
-#endif
+  st.Write(lane, wave);
 }
 
-// fp32 -> interleaved (hi, lo) fp16 rows.  in: element (r, c) at in[r * stride_r + c *
-// stride_c]; out row r starts at out + r * ld_out (halves); logical column c lives at
-// (c / 8) * 16 + c % 8 (hi) and 8 halves further (lo); columns cols..cols_pad-1 are zero.
+// fp32 -> interleaved (hi, lo) fp16 rows (pk_f16_layout.h).  in: element (r, c) at in[r * stride_r + c *
+// stride_c]; out row r starts at out + r * ld_out (halves); columns cols..cols_pad-1 are zero.
 __global__ void SplitKernel(const float *__restrict__ in, int64_t stride_r, int64_t stride_c,
                             int rows, int cols, int cols_pad, _Float16 *__restrict__ out,
                             int64_t ld_out, const int32_t *__restrict__ e_x, uint32_t *range) {
@@ -731,16 +674,13 @@ __global__ void SplitKernel(const float *__restrict__ in, int64_t stride_r, int6
     const float v = c < cols ? in[(int64_t)r * stride_r + (int64_t)c * stride_c] * sc : 0.0f;
     const SplitOut s = Split(v);
     hmax = fmaxf(hmax, fabsf(static_cast<float>(s.hi)));
-    _Float16 *o = out + (int64_t)r * ld_out + (c >> 3) * 16 + (c & 7);
+    _Float16 *o = HiPtr(out + (int64_t)r * ld_out, c);
     o[0] = s.hi;
-    o[8] = s.lo;
+    o[kLoHalves] = s.lo;
   }
   if (range) PublishRange(range, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), hmax);
 }
 
-}  // namespace
-
-namespace {
 // a zero exponent word for callers that scale nothing (probes, tests): one per device, made on first use
 const int32_t *ZeroWord() {
   static std::mutex mu;
@@ -752,6 +692,14 @@ const int32_t *ZeroWord() {
   if (!word[dev] && hipMalloc(&word[dev], sizeof(int32_t)) == hipSuccess) hipMemset(word[dev], 0, sizeof(int32_t));
   return word[dev];
 }
+
+// the 16 kernels: [16x16x32 form][TERMS == 3][LAST][RELU]
+using GemmF16Fn = void (*)(GemmF16Args);
+const GemmF16Fn kGemmF16[2][2][2][2] = {
+    {{{GemmF16Kernel<false, false, 1>, GemmF16Kernel<true, false, 1>}, {GemmF16Kernel<false, true, 1>, GemmF16Kernel<true, true, 1>}},
+     {{GemmF16Kernel<false, false, 3>, GemmF16Kernel<true, false, 3>}, {GemmF16Kernel<false, true, 3>, GemmF16Kernel<true, true, 3>}}},
+    {{{GemmF16K32Kernel<false, false, 1>, GemmF16K32Kernel<true, false, 1>}, {GemmF16K32Kernel<false, true, 1>, GemmF16K32Kernel<true, true, 1>}},
+     {{GemmF16K32Kernel<false, false, 3>, GemmF16K32Kernel<true, false, 3>}, {GemmF16K32Kernel<false, true, 3>, GemmF16K32Kernel<true, true, 3>}}}};
 }  // namespace
 
 void LaunchGemmF16(const GemmF16Args &a_in, hipStream_t stream) {
@@ -779,12 +727,8 @@ void LaunchGemmF16(const GemmF16Args &a_in, hipStream_t stream) {
     hipGetDevice(&dev);
     std::lock_guard<std::mutex> g(mu);
     if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-#define PK_SET_LDS(R, L, T) do { \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmF16Kernel<R, L, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmF16K32Kernel<R, L, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); } while (0)
-      PK_SET_LDS(true, false, 3); PK_SET_LDS(false, false, 3); PK_SET_LDS(true, true, 3); PK_SET_LDS(false, true, 3);
-      PK_SET_LDS(true, false, 1); PK_SET_LDS(false, false, 1); PK_SET_LDS(true, true, 1); PK_SET_LDS(false, true, 1);
-#undef PK_SET_LDS
+      for (const GemmF16Fn *f = &kGemmF16[0][0][0][0]; f != &kGemmF16[0][0][0][0] + 16; ++f)
+        hipFuncSetAttribute(reinterpret_cast<const void *>(*f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       attr_set[dev] = true;
     }
   }
@@ -796,16 +740,7 @@ void LaunchGemmF16(const GemmF16Args &a_in, hipStream_t stream) {
   // differ in the last bits only (the k order of the fp32 accumulation), so the choice is fixed per process.
   static const int forced = [] { const char *e = getenv("PK_MI355_F16_SHAPE"); return e ? atoi(e) : 0; }();
   const bool k32 = forced == 16 || (forced != 32 && a.terms == 3);
-#define PK_LAUNCH(R, L, T) do { if (k32) hipLaunchKernelGGL((GemmF16K32Kernel<R, L, T>), grid, block, lds, stream, a); \
-                                else hipLaunchKernelGGL((GemmF16Kernel<R, L, T>), grid, block, lds, stream, a); } while (0)
-  if (a.terms == 1) {
-    if (a.out_f32) { if (a.relu) PK_LAUNCH(true, true, 1); else PK_LAUNCH(false, true, 1); }
-    else { if (a.relu) PK_LAUNCH(true, false, 1); else PK_LAUNCH(false, false, 1); }
-  } else {
-    if (a.out_f32) { if (a.relu) PK_LAUNCH(true, true, 3); else PK_LAUNCH(false, true, 3); }
-    else { if (a.relu) PK_LAUNCH(true, false, 3); else PK_LAUNCH(false, false, 3); }
-  }
-#undef PK_LAUNCH
+  hipLaunchKernelGGL(kGemmF16[k32][a.terms != 1][a.out_f32 != nullptr][a.relu ? 1 : 0], grid, block, lds, stream, a);
 }
 
 // NormalizeLayer (nnet.cc:62-75) between two f16x3 affine layers: fp32 rows in (what the GEMM wrote with
@@ -850,8 +785,8 @@ __global__ __launch_bounds__(256) void NormalizeSplitKernel(const float *__restr
       lo[e] = sp.lo;
       hmax = fmaxf(hmax, fabsf(static_cast<float>(sp.hi)));
     }
-    *reinterpret_cast<f16x8 *>(o + 2 * c) = hi;
-    *reinterpret_cast<f16x8 *>(o + 2 * c + 8) = lo;
+    *reinterpret_cast<f16x8 *>(HiPtr(o, c)) = hi;
+    *reinterpret_cast<f16x8 *>(HiPtr(o, c) + kLoHalves) = lo;
   }
   if (range) PublishRange(range, row, hmax);
 }

@@ -189,7 +189,7 @@ inline const int32_t *ExpZero(const pk_mi355_am *am) { return ExpBase(am) + 2 * 
 inline uint32_t *RangeOf(const ExecBufs &e, int l) { return e.range ? e.range + (size_t)l * kRangeSlots : nullptr; }
 
 constexpr int kMaxXExp = 30;                     // |operand exponent| (|w_exp| <= 60: 2^(e_out - e_in - e_w) stays a normal float)
-constexpr float kRangeSaturated = 65504.0f;      // the split clamps here (gemm_f16.hip: Split)
+constexpr float kRangeSaturated = 65504.0f;      // the split clamps here (pk_f16_layout.h: Split)
 constexpr float kRangeTooSmall = 0.03125f;       // 2^-5: below this every lo half of the operand is an fp16 subnormal
                                                  // (|lo| <= 2^-12 |x|), and the mode degrades towards plain fp16
 
