@@ -637,6 +637,37 @@ int pk_mi355_online_decoder_alignment(const pk_mi355_online_decoder_t *d, int sl
 int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *d, int slot, pk_mi355_word_t *out, int max);
 
 /* ------------------------------------------------------------------------- */
+/* Online commit mode ("Commit"): streams of any length     */
+/* ------------------------------------------------------------------------- */
+
+/* Off (0) by default; like online alignment the mode is the object's and can be changed only while no slot is open
+ * (PK_MI355_E_STATE otherwise); a finished slot keeps the mode it was opened with.  On: at the end of every launch
+ * that does not finish the slot, the arcs that the backtraces of ALL the slot's tokens share -- which no later audio
+ * can change -- are handed to the host, but for the last of them, and leave the slot's arena; that last shared record
+ * stays as the arena's root.  The arena, the end-of-launch path walk and the copy to the host are then bounded by the
+ * undecided tail, not by the time since open: a stream may be longer than trace_capacity, while a single launch must
+ * still fit it.  Nothing is committed while a token still sits at the start or two first arcs are alive, and nothing
+ * for a slot that ended (status, ok = 0): such a slot reports no path, whatever it committed earlier, as does a slot
+ * that finishes without a token in a final state (BestPath's empty hypothesis).  Every getter
+ * sees committed ++ tail: words, costs, weight bits, arcs, alignment, segments and active_bound are those of the mode
+ * off, bit for bit.  No device memory is added; host memory grows by 4 bytes per committed arc, 8 with alignment,
+ * until the slot is opened again.                                                                                    */
+int pk_mi355_online_decoder_set_commit(pk_mi355_online_decoder_t *d, int enable);
+/* The committed prefix of the slot's path after its last advance: its words in spoken order (olabel != 0; at most
+ * max_words written, the count returned), the number of committed arcs and of emitting arcs among them (either
+ * pointer may be NULL).  It only ever grows while the slot is live, and every later path of the slot starts with it.
+ * 0 / 0 / 0 with the mode off, and for a slot that ended.                                                            */
+int pk_mi355_online_decoder_committed(const pk_mi355_online_decoder_t *d, int slot, int *words, int max_words, int *num_arcs,
+                                      int *num_frames);
+/* The slot's backtrace arena (any pointer may be NULL): records in it after the slot's last launch; the most it
+ * held since open; its capacity in records (trace_capacity).  With the commit mode on the peak is sampled before
+ * every compaction and commit and at the end of each launch, as pk_mi355_decoder_trace_stats does; with the mode off
+ * the kernel is the one that knows no such mode and keeps no maximum, so the peak is sampled at the end of each
+ * launch only.  PK_MI355_E_STATE before the slot's first launch.                                                     */
+int pk_mi355_online_decoder_trace_stats(const pk_mi355_online_decoder_t *d, int slot, int64_t *in_use, int64_t *peak,
+                                        int64_t *capacity);
+
+/* ------------------------------------------------------------------------- */
 /* Symbol table -- pk_symboltable_read / _get (symbol_table.cc:23-79)              */
 /* ------------------------------------------------------------------------- */
 
@@ -713,6 +744,10 @@ int pk_mi355_online_recognizer_step(pk_mi355_online_recognizer_t *r);
 /* The slot's current hypothesis: the words' strings in spoken order joined by one space ("" without words).  Valid
  * until the next step.  NULL on misuse.                                                                            */
 const char *pk_mi355_online_recognizer_partial(const pk_mi355_online_recognizer_t *r, int slot);
+/* The words of the hypothesis that are final now: the decoder's committed prefix (pk_mi355_online_decoder_committed)
+ * joined as the partial is; the partial always starts with it.  "" while the owned decoder's commit mode is off
+ * (pk_mi355_online_decoder_set_commit on pk_mi355_online_recognizer_decoder).  Valid until the next step.           */
+const char *pk_mi355_online_recognizer_stable(const pk_mi355_online_recognizer_t *r, int slot);
 /* 1 once the step after the slot's close has run (its result is final), 0 before; negative on misuse.             */
 int pk_mi355_online_recognizer_finished(const pk_mi355_online_recognizer_t *r, int slot);
 /* A finished slot's utt->hyp and utt->loglikelihood_per_frame, by pk_mi355_recognizer_hyp's rules: "" and 0.0f for a

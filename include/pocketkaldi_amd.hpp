@@ -414,6 +414,20 @@ class OnlineDecoder {
     if (n > 0) pk_mi355_online_decoder_word_segments(d_, slot, out.data(), n);
     return out;
   }
+  // While no slot is open: the arcs all of a slot's tokens share leave the device for a host list at the end of every
+  // launch, so a stream may be longer than the arena (pk_mi355_online_decoder_set_commit).  No result changes.
+  Status SetCommit(bool on) { return Status::FromLast(pk_mi355_online_decoder_set_commit(d_, on ? 1 : 0)); }
+  // The words of the committed prefix of the slot's path; its arcs and emitting arcs (either pointer may be null)
+  std::vector<int> Committed(int slot, int *num_arcs, int *num_frames) const {
+    const int n = pk_mi355_online_decoder_committed(d_, slot, nullptr, 0, num_arcs, num_frames);
+    std::vector<int> w(n > 0 ? n : 0);
+    if (n > 0) pk_mi355_online_decoder_committed(d_, slot, w.data(), n, num_arcs, num_frames);
+    return w;
+  }
+  // The slot's backtrace arena: records in use after its last launch, the most since Open(), the capacity
+  Status TraceStats(int slot, int64_t *in_use, int64_t *peak, int64_t *capacity) const {
+    return Status::FromLast(pk_mi355_online_decoder_trace_stats(d_, slot, in_use, peak, capacity));
+  }
   const Status &last_status() const { return status_; }
   pk_mi355_online_decoder_t *handle() const { return d_; }
 
@@ -449,6 +463,11 @@ class OnlineRecognizer {
   // The slot's current hypothesis as text ("" on misuse); valid until the next Step()
   std::string Partial(int slot) const {
     const char *text = pk_mi355_online_recognizer_partial(r_, slot);
+    return text ? text : "";
+  }
+  // The words of Partial(slot) that are final now ("" unless pk_mi355_online_decoder_set_commit(decoder(), 1) was called)
+  std::string Stable(int slot) const {
+    const char *text = pk_mi355_online_recognizer_stable(r_, slot);
     return text ? text : "";
   }
   bool Finished(int slot) const { return pk_mi355_online_recognizer_finished(r_, slot) == 1; }

@@ -106,6 +106,8 @@ EXPORTS = [
     "pk_mi355_online_recognizer_close", "pk_mi355_online_recognizer_step", "pk_mi355_online_recognizer_partial",
     "pk_mi355_online_recognizer_finished", "pk_mi355_online_recognizer_hyp",
     "pk_mi355_online_recognizer_loglikelihood_per_frame",
+    "pk_mi355_online_decoder_set_commit", "pk_mi355_online_decoder_committed", "pk_mi355_online_decoder_trace_stats",
+    "pk_mi355_online_recognizer_stable",
 ]
 
 
@@ -309,6 +311,12 @@ def lib():
     L.pk_mi355_online_recognizer_hyp.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_online_recognizer_loglikelihood_per_frame.restype = C.c_float
     L.pk_mi355_online_recognizer_loglikelihood_per_frame.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_set_commit.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_decoder_committed.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_online_decoder_trace_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                      C.POINTER(C.c_int64)]
+    L.pk_mi355_online_recognizer_stable.restype = C.c_char_p
+    L.pk_mi355_online_recognizer_stable.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 
@@ -1063,6 +1071,26 @@ class OnlineDecoder:
         """The frames the slot has decoded."""
         return _check_code(lib().pk_mi355_online_decoder_num_frames(self._h, int(slot)))
 
+    def set_commit(self, on=True):
+        """While no slot is open: at the end of every launch the arcs that all of a slot's tokens share leave the device
+        for a host list, so that a stream may be longer than trace_capacity.  No result changes."""
+        _check_code(lib().pk_mi355_online_decoder_set_commit(self._h, 1 if on else 0))
+
+    def committed(self, slot):
+        """(words, num_arcs, num_frames) of the committed prefix of the slot's path: final whatever audio follows.
+        ([], 0, 0) with the commit mode off."""
+        arcs, frames = C.c_int(), C.c_int()
+        n = _check_code(lib().pk_mi355_online_decoder_committed(self._h, int(slot), None, 0, C.byref(arcs), C.byref(frames)))
+        words = np.zeros(max(n, 1), np.int32)
+        lib().pk_mi355_online_decoder_committed(self._h, int(slot), words.ctypes.data_as(C.POINTER(C.c_int32)), n, None, None)
+        return [int(w) for w in words[:n]], arcs.value, frames.value
+
+    def trace_stats(self, slot):
+        """(records in use after the last launch, peak since open, capacity) of the slot's backtrace arena."""
+        in_use, peak, cap = C.c_int64(), C.c_int64(), C.c_int64()
+        _check_code(lib().pk_mi355_online_decoder_trace_stats(self._h, int(slot), C.byref(in_use), C.byref(peak), C.byref(cap)))
+        return in_use.value, peak.value, cap.value
+
 
 class SymbolTable:
     """symbol_table.h: the reference's SYM0 word list, read on the host (pk_mi355_symtab_read).  len(), [id] -> str."""
@@ -1235,6 +1263,13 @@ class OnlineRecognizer:
     def partial(self, slot):
         """The slot's current hypothesis as text (valid until the next step)."""
         s = lib().pk_mi355_online_recognizer_partial(self._h, int(slot))
+        if s is None:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        return s.decode()
+
+    def stable(self, slot):
+        """The words of partial(slot) that are final now, as text; "" unless decoder.set_commit(True) was called."""
+        s = lib().pk_mi355_online_recognizer_stable(self._h, int(slot))
         if s is None:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         return s.decode()

@@ -11,8 +11,10 @@ using namespace pkhost;
 struct pk_mi355_online_decoder : DecoderCore {
   int max_streams = 0;
   int64_t cap = 0;
-  OnlineState *d_state = nullptr;
+  // one allocation, fetched in one copy: max_streams results, then as many states, then as many commit lengths
   OnlineResult *d_results = nullptr;
+  OnlineState *d_state = nullptr;
+  int *d_commit = nullptr;
   int *d_remap = nullptr;
   OnlineCall *d_calls = nullptr;
   bool align = false;                           // pk_mi355_online_decoder_set_alignment
@@ -21,7 +23,18 @@ struct pk_mi355_online_decoder : DecoderCore {
   std::vector<int> open_, fresh, finished;      // per slot
   std::vector<char> aligned;                    // per slot: opened with the alignment mode on
   std::vector<OnlineResult> res;                // per slot, after synchronize
-  std::vector<OnlineResult> fetched;            // d_results as copied back; res takes the last call's slots from it
+  std::vector<char> fetched;                    // d_results' allocation as copied back; the last call's slots are read from it
+  // pk_mi355_online_decoder_set_commit.  A committing slot's path is committed[slot] ++ paths[slot]: the arcs that left
+  // the device for good, then the best token's tail.  Host memory grows by 4 bytes per committed arc, 8 with alignment.
+  bool commit = false;
+  std::vector<char> committing;                 // per slot: opened with the commit mode on
+  std::vector<std::vector<int32_t>> committed;  // per slot
+  std::vector<std::vector<float>> committed_ac; // per slot, align only
+  std::vector<std::vector<int>> committed_words;  // per slot: the words (olabel != 0) of committed[slot], kept as the arcs arrive
+  std::vector<int> committed_frames;            // per slot: the emitting arcs among committed[slot]
+  std::vector<int64_t> in_use, peak;            // per slot: records in the arena after the last launch; the most since open
+  std::vector<int32_t> got;                     // a slot's path slice as copied back
+  std::vector<float> got_ac;
   std::vector<std::vector<int32_t>> paths;      // per slot: the arcs of res[slot]'s path
   std::vector<int> last_slots;                  // slots of the last call
   bool pending = false;
@@ -29,7 +42,18 @@ struct pk_mi355_online_decoder : DecoderCore {
 
 namespace {
 
+size_t OnlineBlockBytes(int max_streams) { return (sizeof(OnlineResult) + sizeof(OnlineState) + sizeof(int)) * max_streams; }
+
+int OnlineCollect(pk_mi355_online_decoder *o);
+
 int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<OnlineCall> &calls, hipStream_t stream) {
+  // With the commit mode on, what the last call committed exists only in its slots' path slices and commit lengths,
+  // which this launch overwrites: a call that was never synchronized is collected first.  What it says of a slot
+  // (capacity, ...) was that advance's to report and stays readable in the slot's result; a device failure is returned.
+  if (o->pending && o->commit) {
+    const int rc = OnlineCollect(o);
+    if (rc == PK_MI355_E_DEVICE) return rc;
+  }
   if (o->pending) HIP_TRY(hipEventSynchronize(o->done));
   o->pending = false;
   o->last_slots.clear();
@@ -39,7 +63,8 @@ int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<
     HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
     // (frames, arenas and results are per slot: the calls, and o->cap entries of rec and path each)
     LaunchOnlineDecode(ArgsOf(o, ll, n), o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap,
-                       o->align ? o->d_rec_ac : nullptr, o->align ? o->d_path_ac : nullptr, n, stream);
+                       o->align ? o->d_rec_ac : nullptr, o->align ? o->d_path_ac : nullptr,
+                       o->commit ? o->d_commit : nullptr, n, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
   }
@@ -61,22 +86,46 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
   if (o->last_slots.empty()) return 0;
   // Only the call's slots take their record: a slot opened again since its last launch keeps the cleared record that
   // open gave it, whatever the device still holds of its previous utterance.
-  o->fetched.resize(o->max_streams);
-  HIP_TRY(hipMemcpy(o->fetched.data(), o->d_results, sizeof(OnlineResult) * o->max_streams, hipMemcpyDeviceToHost));
+  o->fetched.resize(OnlineBlockBytes(o->max_streams));
+  HIP_TRY(hipMemcpy(o->fetched.data(), o->d_results, o->fetched.size(), hipMemcpyDeviceToHost));
+  const OnlineResult *results = reinterpret_cast<const OnlineResult *>(o->fetched.data());
+  const OnlineState *states = reinterpret_cast<const OnlineState *>(results + o->max_streams);
+  const int *commits = reinterpret_cast<const int *>(states + o->max_streams);
   int first_bad = -1;
   for (int slot : o->last_slots) {
-    o->res[slot] = o->fetched[slot];
+    o->res[slot] = results[slot];
     const OnlineResult &r = o->res[slot];
-    if (r.path_len < 0 || r.path_len > o->cap) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
-    o->paths[slot].resize(r.path_len);
-    if (r.path_len)
-      HIP_TRY(hipMemcpy(o->paths[slot].data(), o->path + (int64_t)slot * o->cap, sizeof(int32_t) * r.path_len,
-                        hipMemcpyDeviceToHost));
+    const int nc = o->committing[slot] ? commits[slot] : 0;     // newly committed arcs, ahead of the tail in the slice
+    if (r.path_len < 0 || nc < 0 || (int64_t)nc + r.path_len > o->cap)
+      return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
+    // (the mode-off kernel keeps no maximum inside a launch: there the peak is sampled at the end of each launch only)
+    o->in_use[slot] = (int64_t)std::min<unsigned long long>(states[slot].top, (unsigned long long)o->cap);
+    o->peak[slot] = std::max(o->peak[slot], std::max(o->in_use[slot], (int64_t)(o->committing[slot] ? states[slot].peak : 0)));
+    const int len = nc + r.path_len;
+    o->got.resize(len);
+    if (len)
+      HIP_TRY(hipMemcpy(o->got.data(), o->path + (int64_t)slot * o->cap, sizeof(int32_t) * len, hipMemcpyDeviceToHost));
+    o->committed[slot].insert(o->committed[slot].end(), o->got.begin(), o->got.begin() + nc);
+    for (int i = 0; i < nc; ++i) {                       // the host's per-step work: the new arcs, not the whole prefix
+      const int32_t arc = o->got[i];
+      if (arc < 0 || arc >= (int32_t)o->labels.olabel.size()) continue;
+      if (o->labels.olabel[arc] != 0) o->committed_words[slot].push_back(o->labels.olabel[arc]);
+      o->committed_frames[slot] += o->labels.ilabel[arc] != 0;
+    }
+    o->paths[slot].assign(o->got.begin() + nc, o->got.end());
     if (o->aligned[slot]) {
-      o->path_acs[slot].resize(r.path_len);
-      if (r.path_len)
-        HIP_TRY(hipMemcpy(o->path_acs[slot].data(), o->d_path_ac + (int64_t)slot * o->cap, sizeof(float) * r.path_len,
-                          hipMemcpyDeviceToHost));
+      o->got_ac.resize(len);
+      if (len)
+        HIP_TRY(hipMemcpy(o->got_ac.data(), o->d_path_ac + (int64_t)slot * o->cap, sizeof(float) * len, hipMemcpyDeviceToHost));
+      o->committed_ac[slot].insert(o->committed_ac[slot].end(), o->got_ac.begin(), o->got_ac.begin() + nc);
+      o->path_acs[slot].assign(o->got_ac.begin() + nc, o->got_ac.end());
+    }
+    // no path at all, whatever was committed earlier: a slot that ended, or one that finished without a final token
+    if (r.status || !r.ok || !r.has_path) {
+      o->committed[slot].clear();
+      o->committed_ac[slot].clear();
+      o->committed_words[slot].clear();
+      o->committed_frames[slot] = 0;
     }
     if (r.status && first_bad < 0) first_bad = slot;
   }
@@ -85,13 +134,35 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
     if (r.status == PK_MI355_E_CAPACITY)
       return Fail(PK_MI355_E_CAPACITY, "online decoder: slot %d: backtrace storage exhausted after compaction (%lld records "
                   "per slot)", first_bad, (long long)o->cap);
+    if (r.status == PK_MI355_E_DEVICE)
+      return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: inconsistent backtrace records at the commit", first_bad);
     return Fail(PK_MI355_E_INVALID, "online decoder: slot %d: negative epsilon cycle (the closure did not settle)", first_bad);
   }
   return 0;
 }
 
+// The slot's path as every getter sees it: the tail alone, or committed ++ tail put together in `joined`.
+const std::vector<int32_t> &OnlinePath(const pk_mi355_online_decoder *o, int slot, std::vector<int32_t> *joined) {
+  if (o->committed[slot].empty()) return o->paths[slot];
+  *joined = o->committed[slot];
+  joined->insert(joined->end(), o->paths[slot].begin(), o->paths[slot].end());
+  return *joined;
+}
+const std::vector<float> &OnlinePathAc(const pk_mi355_online_decoder *o, int slot, std::vector<float> *joined) {
+  if (o->committed_ac[slot].empty()) return o->path_acs[slot];
+  *joined = o->committed_ac[slot];
+  joined->insert(joined->end(), o->path_acs[slot].begin(), o->path_acs[slot].end());
+  return *joined;
+}
+
+// The words of the slot's path: those of the committed prefix as they were kept, then the tail's.
 int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
-  return PathWords(o->labels.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), words, max_words);
+  const auto &cw = o->committed_words[slot];
+  const int c = (int)cw.size();
+  for (int i = 0; words && i < c && i < max_words; ++i) words[i] = cw[i];
+  const bool room = words && c < max_words;
+  return c + PathWords(o->labels.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), room ? words + c : nullptr,
+                       room ? max_words - c : 0);
 }
 
 int OnlineSlot(const pk_mi355_online_decoder *o, int slot) {
@@ -113,8 +184,10 @@ int OnlineFrames(const pk_mi355_online_decoder *o, int slot, int32_t *arc_ids, i
   const OnlineResult &r = o->res[slot];
   if (!r.has_path || !r.ok || r.status) return 0;
   if (!o->aligned[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d was decoded with alignment off", slot);
-  const auto &p = o->paths[slot];
-  const auto &pa = o->path_acs[slot];
+  std::vector<int32_t> joined;
+  std::vector<float> joined_ac;
+  const auto &p = OnlinePath(o, slot, &joined);
+  const auto &pa = OnlinePathAc(o, slot, &joined_ac);
   if (pa.size() != p.size()) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: path and costs differ in length", slot);
   return PathFrames(o->labels, p.data(), pa.data(), (int)p.size(), r.frames, arc_ids, trans_ids, ac, max_frames);
 }
@@ -124,6 +197,16 @@ int OnlineFrames(const pk_mi355_online_decoder *o, int slot, int32_t *arc_ids, i
 namespace pkhost {
 bool OnlineDecoderSlotOpen(const pk_mi355_online_decoder *o, int slot) {
   return o && slot >= 0 && slot < o->max_streams && o->open_[slot] != 0;
+}
+const std::vector<int> *OnlineDecoderCommittedWords(const pk_mi355_online_decoder *o, int slot) {
+  return o && slot >= 0 && slot < o->max_streams ? &o->committed_words[slot] : nullptr;
+}
+void OnlineDecoderTailWords(const pk_mi355_online_decoder *o, int slot, std::vector<int> *words) {
+  words->clear();
+  if (!o || slot < 0 || slot >= o->max_streams) return;
+  const auto &p = o->paths[slot];
+  words->resize(PathWords(o->labels.olabel, p.data(), (int)p.size(), nullptr, 0));
+  PathWords(o->labels.olabel, p.data(), (int)p.size(), words->data(), (int)words->size());
 }
 }  // namespace pkhost
 
@@ -141,10 +224,13 @@ pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *
   o->cap = cap;
   bool ok = CreateCore(o, fst, am, max_streams, cap * max_streams) == 0;
   auto chk = [&](hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "online_decoder_create: %s", hipGetErrorString(e)); } };
-  if (ok) chk(hipMalloc(&o->d_state, sizeof(OnlineState) * max_streams));
-  if (ok) chk(hipMemset(o->d_state, 0, sizeof(OnlineState) * max_streams));
-  if (ok) chk(hipMalloc(&o->d_results, sizeof(OnlineResult) * max_streams));
-  if (ok) chk(hipMemset(o->d_results, 0, sizeof(OnlineResult) * max_streams));
+  static_assert(sizeof(OnlineResult) % alignof(OnlineState) == 0, "the states follow the results in one allocation");
+  if (ok) chk(hipMalloc(&o->d_results, OnlineBlockBytes(max_streams)));
+  if (ok) chk(hipMemset(o->d_results, 0, OnlineBlockBytes(max_streams)));
+  if (ok) {
+    o->d_state = reinterpret_cast<OnlineState *>(o->d_results + max_streams);
+    o->d_commit = reinterpret_cast<int *>(o->d_state + max_streams);
+  }
   if (ok) chk(hipMalloc(&o->d_remap, sizeof(int) * cap * max_streams));
   if (ok) chk(hipMalloc(&o->d_calls, sizeof(OnlineCall) * max_streams));
   if (!ok) { pk_mi355_online_decoder_destroy(o); return nullptr; }
@@ -153,6 +239,13 @@ pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *
   o->paths.assign(max_streams, {});
   o->path_acs.assign(max_streams, {});
   o->aligned.assign(max_streams, 0);
+  o->committing.assign(max_streams, 0);
+  o->committed.assign(max_streams, {});
+  o->committed_ac.assign(max_streams, {});
+  o->committed_words.assign(max_streams, {});
+  o->committed_frames.assign(max_streams, 0);
+  o->in_use.assign(max_streams, 0);
+  o->peak.assign(max_streams, 0);
   return o;
 }
 
@@ -160,7 +253,7 @@ void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *o) {
   if (!o) return;
   if (!UseDevice(o->device)) {
     if (o->pending) hipEventSynchronize(o->done);
-    hipFree(o->d_state); hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
+    hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
     hipFree(o->d_rec_ac); hipFree(o->d_path_ac);
     FreeCore(o);
   }
@@ -193,6 +286,17 @@ int pk_mi355_online_decoder_set_alignment(pk_mi355_online_decoder_t *o, int enab
   return 0;
 }
 
+int pk_mi355_online_decoder_set_commit(pk_mi355_online_decoder_t *o, int enable) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  for (int slot = 0; slot < o->max_streams; ++slot)     // one launch serves every slot: the mode is the object's
+    if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_commit needs every slot closed)", slot);
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  if ((rc = OnlineCollect(o)) == PK_MI355_E_DEVICE) return rc;      // (as set_alignment: a call in flight ends first)
+  o->commit = enable != 0;                               // (a finished slot keeps its results, and the mode it was opened with)
+  return 0;
+}
+
 int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
   int rc = OnlineSlot(o, slot);
   if (rc) return rc;
@@ -203,6 +307,12 @@ int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
   o->paths[slot].clear();
   o->path_acs[slot].clear();
   o->aligned[slot] = o->align ? 1 : 0;
+  o->committing[slot] = o->commit ? 1 : 0;
+  o->committed[slot].clear();
+  o->committed_ac[slot].clear();
+  o->committed_words[slot].clear();
+  o->committed_frames[slot] = 0;
+  o->in_use[slot] = 0; o->peak[slot] = 0;
   return 0;
 }
 
@@ -277,7 +387,8 @@ int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *o, int slot,
 int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, int slot, int32_t *arcs, int max_arcs) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  const auto &p = o->paths[slot];
+  std::vector<int32_t> joined;
+  const auto &p = OnlinePath(o, slot, &joined);
   for (int i = 0; i < (int)p.size() && i < max_arcs; ++i) arcs[i] = p[i];
   return (int)p.size();
 }
@@ -285,7 +396,8 @@ int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, i
 int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *o, int slot, pk_mi355_word_t *out, int max) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  const auto &p = o->paths[slot];
+  std::vector<int32_t> joined;
+  const auto &p = OnlinePath(o, slot, &joined);
   if (!o->align || !o->aligned[slot])             // (the rows are gone, and no cost was kept: no acoustic cost)
     return WordSegments(o->labels, p.data(), (int)p.size(), nullptr, 0, out, max);
   std::vector<float> ac(std::max(o->res[slot].frames, 1));                    // the costs kept with the trace
@@ -300,6 +412,28 @@ int pk_mi355_online_decoder_alignment(const pk_mi355_online_decoder_t *o, int sl
   if (rc) return rc;
   if (!o->align) return Fail(PK_MI355_E_STATE, "online decoder: alignment is off (pk_mi355_online_decoder_set_alignment)");
   return OnlineFrames(o, slot, arc_ids, trans_ids, acoustic_cost, max_frames);
+}
+
+int pk_mi355_online_decoder_committed(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, int *num_arcs,
+                                      int *num_frames) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  const auto &cw = o->committed_words[slot];
+  if (num_arcs) *num_arcs = (int)o->committed[slot].size();
+  if (num_frames) *num_frames = o->committed_frames[slot];
+  for (int i = 0; words && i < (int)cw.size() && i < max_words; ++i) words[i] = cw[i];
+  return (int)cw.size();
+}
+
+int pk_mi355_online_decoder_trace_stats(const pk_mi355_online_decoder_t *o, int slot, int64_t *in_use, int64_t *peak,
+                                        int64_t *capacity) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  if (o->fresh[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d has not been advanced since it was opened", slot);
+  if (in_use) *in_use = o->in_use[slot];
+  if (peak) *peak = o->peak[slot];
+  if (capacity) *capacity = o->cap;
+  return 0;
 }
 
 int pk_mi355_online_decoder_num_frames(const pk_mi355_online_decoder_t *o, int slot) {

@@ -17,6 +17,8 @@ struct pk_mi355_online_recognizer : RecognizerFiles {
   int max_streams = 0;
   std::vector<char> live, closed, finished;  // per slot: opened here; closed, its flush still to come; its result is final
   std::vector<std::string> partial, hyp;     // per slot: the text after the last step; a finished slot's sentence
+  std::vector<std::string> stable;           // per slot: the committed words' text after the last step ("": mode off)
+  std::vector<size_t> stable_words;          // per slot: how many of the decoder's committed words stable[slot] holds
   std::vector<float> per_frame;
 };
 
@@ -29,10 +31,19 @@ int Refresh(pk_mi355_online_recognizer *r) {
     if (!r->live[slot]) continue;
     const int count = pk_mi355_online_decoder_partial(r->decoder, slot, nullptr, 0, nullptr);
     if (count < 0) return count;
-    words.resize(count);
-    if (count) pk_mi355_online_decoder_partial(r->decoder, slot, words.data(), count, nullptr);
-    int rc = JoinWords(r->symtab, words.data(), count, &r->partial[slot]);
+    // Per step: the newly committed words are appended to the stable text, and only the tail's words are joined anew.
+    const std::vector<int> *committed = OnlineDecoderCommittedWords(r->decoder, slot);
+    if (!committed) return Fail(PK_MI355_E_INVALID, "online recognizer: slot %d is not the decoder's", slot);
+    if (committed->size() < r->stable_words[slot]) { r->stable[slot].clear(); r->stable_words[slot] = 0; }   // (the slot ended)
+    std::string more;
+    int rc = JoinWords(r->symtab, committed->data() + r->stable_words[slot], (int)(committed->size() - r->stable_words[slot]), &more);
     if (rc) return rc;
+    if (!more.empty()) r->stable[slot] += (r->stable[slot].empty() ? "" : " ") + more;
+    r->stable_words[slot] = committed->size();
+    OnlineDecoderTailWords(r->decoder, slot, &words);
+    if ((int)(committed->size() + words.size()) != count) return Fail(PK_MI355_E_DEVICE, "online recognizer: slot %d: word counts differ", slot);
+    if ((rc = JoinWords(r->symtab, words.data(), (int)words.size(), &more))) return rc;
+    r->partial[slot] = r->stable[slot] + (!r->stable[slot].empty() && !more.empty() ? " " : "") + more;
     if (!r->closed[slot]) continue;
     float weight = 0.0f;
     int ok = 0;
@@ -82,6 +93,8 @@ pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config
   r->max_streams = max_streams;
   r->live.assign(max_streams, 0); r->closed.assign(max_streams, 0); r->finished.assign(max_streams, 0);
   r->partial.assign(max_streams, std::string()); r->hyp.assign(max_streams, std::string());
+  r->stable.assign(max_streams, std::string());
+  r->stable_words.assign(max_streams, 0);
   r->per_frame.assign(max_streams, 0.0f);
   return r;
 }
@@ -110,7 +123,8 @@ int pk_mi355_online_recognizer_open(pk_mi355_online_recognizer_t *r, int slot) {
   if (OnlineDecoderSlotOpen(r->decoder, slot)) return Fail(PK_MI355_E_STATE, "online recognizer: slot %d is open in the decoder", slot);
   if ((rc = pk_mi355_stream_open(r->stream, slot)) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
   r->live[slot] = 1; r->closed[slot] = 0; r->finished[slot] = 0;
-  r->partial[slot].clear(); r->hyp[slot].clear();
+  r->partial[slot].clear(); r->hyp[slot].clear(); r->stable[slot].clear();
+  r->stable_words[slot] = 0;
   r->per_frame[slot] = 0.0f;
   return 0;
 }
@@ -149,6 +163,11 @@ int pk_mi355_online_recognizer_step(pk_mi355_online_recognizer_t *r) {
 const char *pk_mi355_online_recognizer_partial(const pk_mi355_online_recognizer_t *r, int slot) {
   if (CheckSlot(r, slot)) return nullptr;
   return r->partial[slot].c_str();
+}
+
+const char *pk_mi355_online_recognizer_stable(const pk_mi355_online_recognizer_t *r, int slot) {
+  if (CheckSlot(r, slot)) return nullptr;
+  return r->stable[slot].c_str();
 }
 
 int pk_mi355_online_recognizer_finished(const pk_mi355_online_recognizer_t *r, int slot) {

@@ -479,6 +479,92 @@ __device__ void CompactTrace(Shared &sh, int2 *rec, float *rec_ac, int *remap, u
   __syncthreads();
 }
 
+// The commit mode's end-of-launch compaction (pk_mi355_online_decoder_set_commit): CompactTrace's three passes with a
+// count in place of the mark.  Every token walks from its record towards the root adding 1 to remap[x] and goes on
+// only where it was the first to arrive, so remap[x] = (reachable children of x) + (tokens at x) and every reachable
+// record is visited by one walker.  With one root and no token at the start (trace < 0), b = the lowest index that
+// either carries a count >= 2 or is a token's own record is the last record every path shares: a predecessor is always
+// older and compaction keeps creation order, so everything off the trunk -- a descendant of the first branching
+// record -- has a higher index than it, and the reachable records below b ARE the trunk, in path order.  Those go, in
+// that order, to path[0, nc) (their costs to path_ac with kAc); the rest moves down as in CompactTrace, b to index 0
+// with prev = -1.  Otherwise b = 0 and this is a plain compaction.  Every index read from memory is checked against
+// the arena's top before it is used.  Returns nc (all threads), or -1 when the records are inconsistent.
+constexpr int kCommitNone = 1, kCommitBad = 2;       // sh.fail: a token at the start; an index out of range
+
+template <bool kAc>
+__device__ int CommitTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int nL, int *tr, int *path, float *path_ac) {
+  int2 *rec = R.rec;
+  const unsigned long long top = *R.top;
+  __syncthreads();
+  if (top > (unsigned long long)R.cap) return -1;
+  const int n = (int)top;
+  for (int i = threadIdx.x; i < n; i += kDecThreads) remap[i] = 0;
+  if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.fail = 0; sh.sel = 0; }     // roots; flags; nc
+  __syncthreads();
+  uint64_t lo = kEmpty;
+  for (int j = threadIdx.x; j < nL; j += kDecThreads) {
+    int x = L[j].trace;
+    if (x < 0) { atomicOr(&sh.fail, kCommitNone); continue; }
+    if (x >= n) { atomicOr(&sh.fail, kCommitBad); continue; }
+    lo = min(lo, (uint64_t)x);
+    while (atomicAdd(&remap[x], 1) == 0) {
+      const int p = rec[x].x;
+      if (p < 0) { atomicAdd(&sh.cnt_nxt, 1); break; }
+      if (p >= x) { atomicOr(&sh.fail, kCommitBad); break; }            // (older, so in range; and the walk ends)
+      x = p;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += kDecThreads)
+    if (__hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 2) { lo = min(lo, (uint64_t)i); break; }
+  lo = BlockMinU(sh, lo);
+  const int flags = sh.fail;
+  if (flags & kCommitBad) return -1;
+  const int b = (sh.cnt_nxt == 1 && !flags && lo != kEmpty) ? (int)lo : 0;
+  int base = 0;
+  for (int c0 = 0; c0 < n; c0 += kDecThreads) {
+    const int i = c0 + threadIdx.x;
+    const int alive = i < n ? __hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0 : 0;   // set by atomics
+    int2 r = make_int2(-1, -1);
+    [[maybe_unused]] float ac = 0.0f;
+    if (alive) {
+      r = rec[i];
+      if constexpr (kAc) ac = R.ac[i];
+    }
+    int total;
+    const int g = base + BlockScan(sh, alive, &total);   // rank among the reachable: trunk first, b at nc
+    if (alive && i == b) sh.sel = g;
+    __syncthreads();
+    const int nc = i >= b ? sh.sel : 0;
+    if (i < n) remap[i] = (alive && i >= b) ? g - nc : -1;
+    __syncthreads();
+    if (alive) {
+      if (i < b) {
+        path[g] = r.y;
+        if constexpr (kAc) path_ac[g] = ac;
+      } else {
+        r.x = (i > b && r.x >= 0) ? remap[r.x] : -1;     // older: remapped in this chunk or an earlier one
+        rec[g - nc] = r;
+        if constexpr (kAc) R.ac[g - nc] = ac;
+      }
+    }
+    base += total;
+    __syncthreads();
+  }
+  const int nc = sh.sel;
+  for (int j = threadIdx.x; j < nL; j += kDecThreads) {
+    const int x = L[j].trace;
+    if (x >= 0) {
+      L[j].trace = remap[x];
+      tr[L[j].state] = remap[x];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *R.top = (unsigned long long)(base - nc);
+  __syncthreads();
+  return nc;
+}
+
 // kGc = false: the call's shared arena and path arena, their bump counters in HBM; nothing is reclaimed.
 // kGc = true (pk_mi355_decoder_set_trace_gc): utterance u owns entries [u * rec_cap, (u + 1) * rec_cap) of rec and of
 // path, its top lives in LDS, and the slice is compacted when more than half full before an emitting frame, as the
@@ -620,31 +706,46 @@ __global__ void __launch_bounds__(kDecThreads) AlignKernel(AlignArgs A) {
 // records and path -- a frame's acoustic cost is kept when the frame is decoded, since its row is void afterwards.
 // With kAc = false neither pointer is read.
 
-template <bool kAc>
+template <bool kAc, bool kCommit>
 __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, const OnlineCall *calls, OnlineState *states,
                                                                     OnlineResult *results, int *remap_all, int64_t cap,
-                                                                    float *rec_ac, float *path_ac) {
+                                                                    float *rec_ac, float *path_ac, int *commit_len) {
   extern __shared__ float s_ll[];
   __shared__ Shared sh;
   const OnlineCall call = calls[blockIdx.x];
   const int u = call.slot;
   OnlineState st = states[u];
   if (call.fresh) {
-    st.nL = 0; st.par = 0; st.ok = 1; st.status = 0; st.active = 0; st.frames = 0; st.started = 0; st.pad = 0; st.top = 0;
+    st.nL = 0; st.par = 0; st.ok = 1; st.status = 0; st.active = 0; st.frames = 0; st.started = 0; st.peak = 0; st.top = 0;
   }
   __shared__ unsigned long long s_top;
   if (threadIdx.x == 0) s_top = st.top;
   __syncthreads();
   Work w = WorkOf(A, u, Arena{A.rec + (int64_t)u * cap, cap, &s_top, kAc ? rec_ac + (int64_t)u * cap : nullptr});   // the slot's own arena
   int *remap = remap_all + (int64_t)u * cap;
+  [[maybe_unused]] unsigned long long peak = (unsigned long long)st.peak;   // kCommit: the most the arena held since open
   if (st.par) { Tok *x = w.L; w.L = w.Lnext; w.Lnext = x; }
   w.nL = st.nL; w.status = st.status; w.ok = st.ok; w.active = st.active; w.frames = st.frames; w.par = st.par;
   if (!w.status && w.ok)
     DecodeFrames<kAc>(sh, s_ll, A, w, A.ll + call.ll_off, st.started ? 0 : -1, call.T, [&](Tok *L, int nL) {
-      if (s_top > (unsigned long long)(cap / 2)) CompactTrace<kAc>(sh, w.arena.rec, w.arena.ac, remap, &s_top, L, nL, w.tr);
+      if (s_top > (unsigned long long)(cap / 2)) {
+        if constexpr (kCommit) peak = max(peak, s_top);
+        CompactTrace<kAc>(sh, w.arena.rec, w.arena.ac, remap, &s_top, L, nL, w.tr);
+      }
     });
-  // the path of the best token: BestPath's once the slot is closed, the partial hypothesis' otherwise
   const bool fin = call.final_ != 0;
+  // kCommit: the arcs every token's path shares, but the last, leave the arena for the front of the slot's path (not in
+  // the launch that finishes the slot, and not for a slot that has ended); the best token's tail follows them below
+  [[maybe_unused]] int nc = 0;
+  if constexpr (kCommit) {
+    peak = max(peak, s_top);
+    if (!w.status && w.ok && !fin && w.nL > 0) {
+      nc = CommitTrace<kAc>(sh, w.arena, remap, w.L, w.nL, w.tr, A.path + (int64_t)u * cap,
+                            kAc ? path_ac + (int64_t)u * cap : nullptr);
+      if (nc < 0) { w.status = PK_MI355_E_DEVICE; nc = 0; }
+    }
+  }
+  // the path of the best token: BestPath's once the slot is closed, the partial hypothesis' otherwise
   float weight = 0.f;
   int bi = -1;
   if (!w.status && w.ok) bi = BestToken(sh, A, w, fin, &weight);
@@ -654,7 +755,27 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
     r.ok = (w.status || w.nL == 0) ? 0 : w.ok;
     r.weight = 0.f; r.path_len = 0; r.has_path = 0;
     r.active_bound = w.active; r.frames = w.frames;
-    if (!w.status && r.ok && bi >= 0) {
+    if constexpr (kCommit) {
+      // (the committed arcs and the tail are distinct records reachable before the commit: together they fit the slice)
+      if (!w.status && r.ok && bi >= 0) {
+        r.weight = weight;
+        const int len = PathLen(w.arena, w.L[bi].trace);
+        if ((int64_t)nc + len > cap) {
+          w.status = r.status = PK_MI355_E_DEVICE;
+          r.ok = 0; r.weight = 0.f;
+          nc = 0;
+        } else {
+          r.path_len = len;
+          if constexpr (kAc)
+            FillPathAc(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap + nc, path_ac + (int64_t)u * cap + nc, len);
+          else
+            FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap + nc, len);
+          r.has_path = 1;
+        }
+      }
+      commit_len[u] = nc;
+      st.peak = (int)min((unsigned long long)cap, max(peak, s_top));        // (a failed bump overshoots)
+    } else if (!w.status && r.ok && bi >= 0) {
       r.weight = weight;
       r.path_len = PathLen(w.arena, w.L[bi].trace);
       if constexpr (kAc)
@@ -691,13 +812,17 @@ void LaunchAlign(const AlignArgs &A, hipStream_t stream) {
 }
 
 void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, float *rec_ac, float *path_ac, int n, hipStream_t stream) {
-  if (rec_ac && path_ac)
-    hipLaunchKernelGGL(OnlineDecodeKernel<true>, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls,
-                       states, results, remap, cap, rec_ac, path_ac);
-  else
-    hipLaunchKernelGGL(OnlineDecodeKernel<false>, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls,
-                       states, results, remap, cap, nullptr, nullptr);
+                        int64_t cap, float *rec_ac, float *path_ac, int *commit_len, int n, hipStream_t stream) {
+  const bool ac = rec_ac && path_ac;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls, states, results,
+                       remap, cap, ac ? rec_ac : nullptr, ac ? path_ac : nullptr, commit_len);
+  };
+  if (commit_len) {
+    if (ac) launch(OnlineDecodeKernel<true, true>); else launch(OnlineDecodeKernel<false, true>);
+  } else {
+    if (ac) launch(OnlineDecodeKernel<true, false>); else launch(OnlineDecodeKernel<false, false>);
+  }
 }
 
 }  // namespace pkmi

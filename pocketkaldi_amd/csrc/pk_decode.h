@@ -70,7 +70,7 @@ struct OnlineState {
   int nL, par;            // tokens of the current list and which of the slot's two list buffers holds them
   int ok, status;         // N2 / capacity / closure verdicts: a slot that ended stays ended
   int active, frames;     // largest touched count; frames decoded
-  int started, pad;
+  int started, peak;      // peak: the commit mode's kernel only -- the most the arena held since open
   unsigned long long top; // records used in the slot's arena
 };
 
@@ -96,9 +96,11 @@ void LaunchGatherPaths(UttResult *res, int n, const int *path, int *out, hipStre
 void LaunchAlign(const AlignArgs &A, hipStream_t stream);
 // the new frames of n slots; states, results, remap and A.rec / A.path hold `cap` entries per slot.  rec_ac and path_ac
 // (`cap` floats per slot, both or neither): the alignment mode -- a record's acoustic cost kept beside it, a path's beside
-// its arcs (OnlineDecodeKernel<true>); null: OnlineDecodeKernel<false>
+// its arcs (OnlineDecodeKernel<true, .>); null: OnlineDecodeKernel<false, .>.  commit_len (one int per slot): the commit
+// mode, OnlineDecodeKernel<., true> -- a slot's path slice then holds commit_len[slot] newly committed arcs followed by
+// the result's path_len arcs of the best token's tail; null: OnlineDecodeKernel<., false>, which never reads it
 void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, float *rec_ac, float *path_ac, int n, hipStream_t stream);
+                        int64_t cap, float *rec_ac, float *path_ac, int *commit_len, int n, hipStream_t stream);
 
 }  // namespace pkmi
 

@@ -231,6 +231,10 @@ bool StreamSlotFlushed(const pk_mi355_stream *s, int slot);   // the last step f
 
 // what the online recognizer (capi_online_recognizer.hip) needs to know of an online decoder beyond the ABI
 bool OnlineDecoderSlotOpen(const pk_mi355_online_decoder *o, int slot);
+// the words of the slot's committed prefix as the decoder keeps them (they only grow until the slot ends or is opened
+// again; null for a slot out of range), and the words of the tail that follows them
+const std::vector<int> *OnlineDecoderCommittedWords(const pk_mi355_online_decoder *o, int slot);
+void OnlineDecoderTailWords(const pk_mi355_online_decoder *o, int slot, std::vector<int> *words);
 
 // ------------------------------------------------------------------ pk_load's host half (capi_recognizer.hip)
 // What both recognizers read before the device is touched, in pk_load's order (pocketkaldi.cc:81-131): the graph, the

@@ -1,7 +1,7 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax]
-                                        [--online [--chunk-ms N] [--partials]]
+                                        [--online [--chunk-ms N] [--partials] [--commit]]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
 that does not end in .wav is a list of wave files, one per line (main.cc:34-46); its waves are decoded together, as
@@ -12,7 +12,9 @@ per word segment of the best path, in seconds at the 10 ms frame shift (fbank.cc
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step,
 up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
 also prints every changed partial hypothesis to stderr: "<file>\t<seconds of audio fed>\t<text>".  --chunk-ms and
---partials without --online are refused with the usage text.
+--partials without --online are refused with the usage text, as is --commit.  --commit turns the online decoder's commit
+mode on (streams of any length; pk_mi355_online_decoder_set_commit): stdout is unchanged, and every --partials line gains
+a fourth tab field, the stable text -- the words of the partial that no later audio can change.
 """
 import sys
 
@@ -25,31 +27,33 @@ MAX_SAMPLES = 16000 * 120
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] "
-          "[--online [--chunk-ms N] [--partials]]")
+          "[--online [--chunk-ms N] [--partials] [--commit]]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
     return 1
 
 
-def recognize_online(model_file, files, waves, chunk, reference_softmax, partials):
+def recognize_online(model_file, files, waves, chunk, reference_softmax, partials, commit=False):
     """Every wave through a slot of an OnlineRecognizer, `chunk` samples per step, MAX_UTTS waves at a time.
     -> (the results in order, the symbol names by word id)"""
     rec = pk.OnlineRecognizer(model_file, max_streams=min(max(len(waves), 1), MAX_UTTS),
                               max_step_samples=chunk * min(max(len(waves), 1), MAX_UTTS))
     try:
-        return stream_waves(rec, files, waves, chunk, reference_softmax, partials)
+        if commit:
+            rec.decoder.set_commit(True)
+        return stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit)
     finally:
         rec.destroy()
 
 
-def stream_waves(rec, files, waves, chunk, reference_softmax, partials):
+def stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit=False):
     if reference_softmax:
         rec.am.set_softmax("reference")
     results = [None] * len(waves)
     for first in range(0, len(waves), MAX_UTTS):
         group = list(range(first, min(first + MAX_UTTS, len(waves))))
-        pos, shown = {u: 0 for u in group}, {u: "" for u in group}
+        pos, shown = {u: 0 for u in group}, {u: ("", "") if commit else "" for u in group}
         for u in group:
             rec.open(u - first)
         live = set(group)
@@ -64,8 +68,11 @@ def stream_waves(rec, files, waves, chunk, reference_softmax, partials):
             rec.step()
             for u in sorted(live):
                 text = rec.partial(u - first)
+                if commit:
+                    text = (text, rec.stable(u - first))
                 if partials and text != shown[u]:
-                    sys.stderr.write("%s\t%.2f\t%s\n" % (files[u], min(pos[u], len(waves[u])) / 16000.0, text))
+                    sys.stderr.write("%s\t%.2f\t%s\n" % (files[u], min(pos[u], len(waves[u])) / 16000.0,
+                                                        "\t".join(text) if commit else text))
                     shown[u] = text
             for u in closing:
                 results[u] = rec.result(u - first)
@@ -88,9 +95,9 @@ def main(argv):
         del argv[at:at + 2]
     flags = [a for a in argv if a.startswith("--")]
     args = [a for a in argv if not a.startswith("--")]
-    if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax", "--online", "--partials"}:
+    if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax", "--online", "--partials", "--commit"}:
         return usage()
-    if "--partials" in flags and "--online" not in flags:
+    if ("--partials" in flags or "--commit" in flags) and "--online" not in flags:
         return usage()
     model_file, input_file = args
     rec = None
@@ -103,7 +110,7 @@ def main(argv):
         waves = [pk.read_wav(name) for name in files]
         if "--online" in flags:
             results, names = recognize_online(model_file, files, waves, 16 * chunk_ms, "--reference-softmax" in flags,
-                                              "--partials" in flags)
+                                              "--partials" in flags, "--commit" in flags)
         else:
             longest = max([len(w) for w in waves] + [1])
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),

@@ -11,6 +11,20 @@ step (pk_mi355_stream_*).  Prints ONE JSON line and writes it to profiles/stream
   check              the first stream's rows equal BatchScorer on its whole wave, bit for bit
 
     python tools/stream_bench.py [--streams 256] [--seconds 10] [--chunk-ms 100] [--out profiles/stream_bench.json]
+
+--decode adds the online decoder to every step (a word loop of about 20000 states, beam 16, max-active 2000): the
+step is then push + score + pk_mi355_online_decoder_advance + every live stream's partial(), and the record gains
+
+  window_ms          the median step time over the streams' first 10 s and over their last 10 s: a step whose cost
+                     grows with the time since open shows here.  `step` is the whole step, `advance` the same
+                     without the partial() calls (push + score + advance, the library alone), `partial` the
+                     partial() calls of all streams alone (the Python getter builds a list of every word)
+  trace              the largest arena peak and the records in use at the end, over the streams (trace_stats); the
+                     most and the fewest arcs a stream committed, and the longest tail (final path - committed)
+
+--commit (implies --decode) turns the decoder's commit mode on.  The long-stream leg is
+    python tools/stream_bench.py --streams 32 --seconds 120 --decode [--commit] --out <file>
+run with the mode off, on, off, on, each in a process of its own (profiles/stream_commit.json holds the four records).
 """
 import argparse
 import json
@@ -34,7 +48,11 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--chunk-ms", type=float, default=100.0)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "stream_bench.json"))
+    ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--commit", action="store_true")
+    ap.add_argument("--trace-capacity", type=int, default=0)
     a = ap.parse_args()
+    a.decode = a.decode or a.commit
 
     pk.set_device(0)
     layers, prior, L, R = synth.model("S")
@@ -44,11 +62,27 @@ def main():
     chunk = int(round(a.chunk_ms * synth.SAMPLE_RATE / 1000.0))
     nsteps = (len(waves[0]) + chunk - 1) // chunk
     sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk)
+    dec = None
+    if a.decode:
+        import tempfile
+        from pocketkaldi_amd import synth_graph
+        graph = synth_graph.size_for_states(20000, seed=1)
+        with tempfile.TemporaryDirectory() as tmp:
+            synth_graph.write_fst(os.path.join(tmp, "loop.fst"), graph["start"], graph["final"], graph["arcs"])
+            fst = pk.Fst(os.path.join(tmp, "loop.fst"))
+        dec = pk.OnlineDecoder(fst, am, a.streams, trace_capacity=a.trace_capacity)
+        dec.set_beam(16.0, 2000)
+        dec.set_commit(a.commit)
 
-    def run(record):
+    cores = []                               # --decode: a step's time up to the end of advance
+
+    def run(record, nsteps=nsteps):
         for s in range(a.streams):
             sc.open(s)
+            if dec:
+                dec.open(s)
         walls, frames, rows0 = [], 0, []
+        del cores[:]
         for k in range(nsteps + 1):
             t0 = time.perf_counter()
             for s in range(a.streams):
@@ -56,7 +90,13 @@ def main():
                     sc.push(s, waves[s][k * chunk:(k + 1) * chunk])
                 else:
                     sc.close(s)
-            sc.step(0.1, sync=True)
+            sc.step(0.1, sync=dec is None)
+            if dec:
+                dec.advance(sc)
+                cores.append(time.perf_counter() - t0)
+                if k < nsteps:
+                    for s in range(a.streams):
+                        dec.partial(s)
             wall = time.perf_counter() - t0
             n = 0
             for s in range(a.streams):
@@ -70,7 +110,7 @@ def main():
             frames += n
         return walls, frames, rows0
 
-    run(False)                               # warm-up: one whole pass
+    run(False, min(nsteps, 100))             # warm-up: a pass of at most 100 steps
     walls, frames, rows0 = run(True)
     walls_ms = np.array(walls) * 1e3
     bs = pk.BatchScorer(am, g, 1, len(waves[0]))
@@ -89,6 +129,18 @@ def main():
         "algorithmic_delay_ms": {"window_and_lookahead": 15.0 + 10.0 * R, "plus_chunk_at_most": a.chunk_ms},
         "check_stream0_equals_batch": bool(ok),
     }
+    if dec:
+        per_window = int(round(10000.0 / a.chunk_ms))
+        stats = [dec.trace_stats(s) for s in range(a.streams)]
+        rec["decoder"] = {"graph": "word loop, about 20000 states", "beam": 16.0, "max_active": 2000, "commit": bool(a.commit),
+                          "trace_capacity": int(stats[0][2])}
+        cores_ms = np.array(cores) * 1e3
+        window = lambda x: {"first_10s": float(np.median(x[:per_window])), "last_10s": float(np.median(x[-1 - per_window:-1]))}
+        rec["window_ms"] = {"step": window(walls_ms), "advance": window(cores_ms), "partial": window(walls_ms - cores_ms)}
+        rec["trace"] = {"peak_max": int(max(p for _, p, _ in stats)), "in_use_end_max": int(max(i for i, _, _ in stats)),
+                        "committed_arcs_max": int(max(dec.committed(s)[1] for s in range(a.streams))),
+                        "committed_arcs_min": int(min(dec.committed(s)[1] for s in range(a.streams))),
+                        "tail_arcs_max": int(max(len(dec.best_path_arcs(s)) - dec.committed(s)[1] for s in range(a.streams)))}
     line = json.dumps(rec)
     print(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
