@@ -192,6 +192,10 @@ void FreeDecoder(pk_mi355_decoder *d) {         // (after its last call: pk_mi35
   FreeCore(d);
 }
 
+// The device pointer where the last call's paths lie: with trace gc on GatherPathsKernel has moved them to the front of
+// the record arena.
+const int *CallPaths(const pk_mi355_decoder *d) { return d->call_gc ? reinterpret_cast<const int *>(d->rec) : d->path; }
+
 // Queue one decode of num_utts utterances whose log-likelihoods lie at ll + off[u] (T[u] frames each) on `stream`.
 int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off, const std::vector<int> &T,
            hipStream_t stream) {
@@ -238,8 +242,7 @@ int Launch(pk_mi355_decoder *d, const float *ll, const std::vector<int64_t> &off
     if (d->call_align) {
       AlignArgs G = {};
       G.res = d->d_res;
-      // (with trace gc on GatherPathsKernel has moved the paths to the front of the record arena)
-      G.path = d->call_gc ? reinterpret_cast<const int *>(d->rec) : d->path;
+      G.path = CallPaths(d);
       G.path_cap = (int)d->trace_cap;
       G.arc_pdf = d->d_arc_pdf; G.num_arcs = (int)d->labels.ilabel.size();
       G.ll = ll; G.ll_off = d->d_off; G.T = d->d_T; G.frame_off = d->d_frame_off;
@@ -273,9 +276,7 @@ int Collect(pk_mi355_decoder *d) {
   for (const auto &r : d->res) used = std::max(used, r.path_off + r.path_len);
   if ((int64_t)used > d->trace_cap) return Fail(PK_MI355_E_DEVICE, "decoder: corrupt result");
   d->h_path.resize(used);
-  // (with trace gc on GatherPathsKernel has moved the paths to the front of the record arena)
-  const int *paths = d->call_gc ? reinterpret_cast<const int *>(d->rec) : d->path;
-  if (used) HIP_TRY(hipMemcpy(d->h_path.data(), paths, sizeof(int) * used, hipMemcpyDeviceToHost));
+  if (used) HIP_TRY(hipMemcpy(d->h_path.data(), CallPaths(d), sizeof(int) * used, hipMemcpyDeviceToHost));
   if (!d->call_gc) {
     unsigned long long records = 0;
     if (n) HIP_TRY(hipMemcpy(&records, d->counters, sizeof(records), hipMemcpyDeviceToHost));

@@ -7,6 +7,23 @@
 
 using namespace pkhost;
 
+// What the host keeps of one slot.  A committing slot's path is committed ++ path: the arcs that left the device for
+// good, then the best token's tail.  Host memory grows by 4 bytes per committed arc, 8 with alignment.
+struct Slot {
+  int open = 0, fresh = 1, finished = 0;
+  char aligned = 0, committing = 0;             // opened with the alignment / the commit mode on
+  OnlineResult res = {};                        // after synchronize
+  std::vector<int32_t> path;                    // the arcs of res's path
+  std::vector<float> path_ac;                   // aligned only: the acoustic cost of every arc of path
+  std::vector<int32_t> committed;
+  std::vector<float> committed_ac;              // aligned only
+  std::vector<int> committed_words;             // the words (olabel != 0) of committed, kept as the arcs arrive
+  int committed_frames = 0;                     // the emitting arcs among committed
+  int64_t in_use = 0, peak = 0;                 // records in the arena after the last launch; the most since open
+
+  void ClearCommitted() { committed.clear(); committed_ac.clear(); committed_words.clear(); committed_frames = 0; }
+};
+
 // The core's work areas are one per slot, its arenas cap records per slot.
 struct pk_mi355_online_decoder : DecoderCore {
   int max_streams = 0;
@@ -19,23 +36,11 @@ struct pk_mi355_online_decoder : DecoderCore {
   OnlineCall *d_calls = nullptr;
   bool align = false;                           // pk_mi355_online_decoder_set_alignment
   float *d_rec_ac = nullptr, *d_path_ac = nullptr;   // cap floats per slot each, from the first enable
-  std::vector<std::vector<float>> path_acs;     // per slot, align only: the acoustic cost of every arc of paths[slot]
-  std::vector<int> open_, fresh, finished;      // per slot
-  std::vector<char> aligned;                    // per slot: opened with the alignment mode on
-  std::vector<OnlineResult> res;                // per slot, after synchronize
+  bool commit = false;                          // pk_mi355_online_decoder_set_commit
+  std::vector<Slot> slots;
   std::vector<char> fetched;                    // d_results' allocation as copied back; the last call's slots are read from it
-  // pk_mi355_online_decoder_set_commit.  A committing slot's path is committed[slot] ++ paths[slot]: the arcs that left
-  // the device for good, then the best token's tail.  Host memory grows by 4 bytes per committed arc, 8 with alignment.
-  bool commit = false;
-  std::vector<char> committing;                 // per slot: opened with the commit mode on
-  std::vector<std::vector<int32_t>> committed;  // per slot
-  std::vector<std::vector<float>> committed_ac; // per slot, align only
-  std::vector<std::vector<int>> committed_words;  // per slot: the words (olabel != 0) of committed[slot], kept as the arcs arrive
-  std::vector<int> committed_frames;            // per slot: the emitting arcs among committed[slot]
-  std::vector<int64_t> in_use, peak;            // per slot: records in the arena after the last launch; the most since open
   std::vector<int32_t> got;                     // a slot's path slice as copied back
   std::vector<float> got_ac;
-  std::vector<std::vector<int32_t>> paths;      // per slot: the arcs of res[slot]'s path
   std::vector<int> last_slots;                  // slots of the last call
   bool pending = false;
 };
@@ -62,15 +67,18 @@ int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<
   if (n > 0) {
     HIP_TRY(hipMemcpyAsync(o->d_calls, calls.data(), sizeof(OnlineCall) * n, hipMemcpyHostToDevice, stream));
     // (frames, arenas and results are per slot: the calls, and o->cap entries of rec and path each)
-    LaunchOnlineDecode(ArgsOf(o, ll, n), o->d_calls, o->d_state, o->d_results, o->d_remap, o->cap,
-                       o->align ? o->d_rec_ac : nullptr, o->align ? o->d_path_ac : nullptr,
-                       o->commit ? o->d_commit : nullptr, n, stream);
+    DecArgs A = ArgsOf(o, ll, n);
+    A.rec_cap = o->cap; A.remap = o->d_remap;
+    if (o->align) { A.rec_ac = o->d_rec_ac; A.path_ac = o->d_path_ac; }
+    if (o->commit) A.commit_len = o->d_commit;
+    LaunchOnlineDecode(A, o->d_calls, o->d_state, o->d_results, n, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
   }
   for (const auto &c : calls) {
-    o->fresh[c.slot] = 0;
-    if (c.final_) { o->finished[c.slot] = 1; o->open_[c.slot] = 0; }
+    Slot &s = o->slots[c.slot];
+    s.fresh = 0;
+    if (c.final_) { s.finished = 1; s.open = 0; }
   }
   HIP_TRY(hipEventRecord(o->done, stream));
   o->pending = true;
@@ -93,44 +101,40 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
   const int *commits = reinterpret_cast<const int *>(states + o->max_streams);
   int first_bad = -1;
   for (int slot : o->last_slots) {
-    o->res[slot] = results[slot];
-    const OnlineResult &r = o->res[slot];
-    const int nc = o->committing[slot] ? commits[slot] : 0;     // newly committed arcs, ahead of the tail in the slice
+    Slot &s = o->slots[slot];
+    s.res = results[slot];
+    const OnlineResult &r = s.res;
+    const int nc = s.committing ? commits[slot] : 0;            // newly committed arcs, ahead of the tail in the slice
     if (r.path_len < 0 || nc < 0 || (int64_t)nc + r.path_len > o->cap)
       return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: corrupt result", slot);
     // (the mode-off kernel keeps no maximum inside a launch: there the peak is sampled at the end of each launch only)
-    o->in_use[slot] = (int64_t)std::min<unsigned long long>(states[slot].top, (unsigned long long)o->cap);
-    o->peak[slot] = std::max(o->peak[slot], std::max(o->in_use[slot], (int64_t)(o->committing[slot] ? states[slot].peak : 0)));
+    s.in_use = (int64_t)std::min<unsigned long long>(states[slot].top, (unsigned long long)o->cap);
+    s.peak = std::max(s.peak, std::max(s.in_use, (int64_t)(s.committing ? states[slot].peak : 0)));
     const int len = nc + r.path_len;
     o->got.resize(len);
     if (len)
       HIP_TRY(hipMemcpy(o->got.data(), o->path + (int64_t)slot * o->cap, sizeof(int32_t) * len, hipMemcpyDeviceToHost));
-    o->committed[slot].insert(o->committed[slot].end(), o->got.begin(), o->got.begin() + nc);
+    s.committed.insert(s.committed.end(), o->got.begin(), o->got.begin() + nc);
     for (int i = 0; i < nc; ++i) {                       // the host's per-step work: the new arcs, not the whole prefix
       const int32_t arc = o->got[i];
       if (arc < 0 || arc >= (int32_t)o->labels.olabel.size()) continue;
-      if (o->labels.olabel[arc] != 0) o->committed_words[slot].push_back(o->labels.olabel[arc]);
-      o->committed_frames[slot] += o->labels.ilabel[arc] != 0;
+      if (o->labels.olabel[arc] != 0) s.committed_words.push_back(o->labels.olabel[arc]);
+      s.committed_frames += o->labels.ilabel[arc] != 0;
     }
-    o->paths[slot].assign(o->got.begin() + nc, o->got.end());
-    if (o->aligned[slot]) {
+    s.path.assign(o->got.begin() + nc, o->got.end());
+    if (s.aligned) {
       o->got_ac.resize(len);
       if (len)
         HIP_TRY(hipMemcpy(o->got_ac.data(), o->d_path_ac + (int64_t)slot * o->cap, sizeof(float) * len, hipMemcpyDeviceToHost));
-      o->committed_ac[slot].insert(o->committed_ac[slot].end(), o->got_ac.begin(), o->got_ac.begin() + nc);
-      o->path_acs[slot].assign(o->got_ac.begin() + nc, o->got_ac.end());
+      s.committed_ac.insert(s.committed_ac.end(), o->got_ac.begin(), o->got_ac.begin() + nc);
+      s.path_ac.assign(o->got_ac.begin() + nc, o->got_ac.end());
     }
     // no path at all, whatever was committed earlier: a slot that ended, or one that finished without a final token
-    if (r.status || !r.ok || !r.has_path) {
-      o->committed[slot].clear();
-      o->committed_ac[slot].clear();
-      o->committed_words[slot].clear();
-      o->committed_frames[slot] = 0;
-    }
+    if (r.status || !r.ok || !r.has_path) s.ClearCommitted();
     if (r.status && first_bad < 0) first_bad = slot;
   }
   if (first_bad >= 0) {
-    const OnlineResult &r = o->res[first_bad];
+    const OnlineResult &r = o->slots[first_bad].res;
     if (r.status == PK_MI355_E_CAPACITY)
       return Fail(PK_MI355_E_CAPACITY, "online decoder: slot %d: backtrace storage exhausted after compaction (%lld records "
                   "per slot)", first_bad, (long long)o->cap);
@@ -141,27 +145,22 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
   return 0;
 }
 
-// The slot's path as every getter sees it: the tail alone, or committed ++ tail put together in `joined`.
-const std::vector<int32_t> &OnlinePath(const pk_mi355_online_decoder *o, int slot, std::vector<int32_t> *joined) {
-  if (o->committed[slot].empty()) return o->paths[slot];
-  *joined = o->committed[slot];
-  joined->insert(joined->end(), o->paths[slot].begin(), o->paths[slot].end());
-  return *joined;
-}
-const std::vector<float> &OnlinePathAc(const pk_mi355_online_decoder *o, int slot, std::vector<float> *joined) {
-  if (o->committed_ac[slot].empty()) return o->path_acs[slot];
-  *joined = o->committed_ac[slot];
-  joined->insert(joined->end(), o->path_acs[slot].begin(), o->path_acs[slot].end());
+// A slot's path (or its costs) as every getter sees it: the tail alone, or committed ++ tail put together in `joined`.
+template <typename T>
+const std::vector<T> &Joined(const std::vector<T> &committed, const std::vector<T> &tail, std::vector<T> *joined) {
+  if (committed.empty()) return tail;
+  *joined = committed;
+  joined->insert(joined->end(), tail.begin(), tail.end());
   return *joined;
 }
 
 // The words of the slot's path: those of the committed prefix as they were kept, then the tail's.
 int OnlineWords(const pk_mi355_online_decoder *o, int slot, int *words, int max_words) {
-  const auto &cw = o->committed_words[slot];
-  const int c = (int)cw.size();
-  for (int i = 0; words && i < c && i < max_words; ++i) words[i] = cw[i];
+  const Slot &s = o->slots[slot];
+  const int c = (int)s.committed_words.size();
+  for (int i = 0; words && i < c && i < max_words; ++i) words[i] = s.committed_words[i];
   const bool room = words && c < max_words;
-  return c + PathWords(o->labels.olabel, o->paths[slot].data(), (int)o->paths[slot].size(), room ? words + c : nullptr,
+  return c + PathWords(o->labels.olabel, s.path.data(), (int)s.path.size(), room ? words + c : nullptr,
                        room ? max_words - c : 0);
 }
 
@@ -181,13 +180,14 @@ int OnlineReady(const pk_mi355_online_decoder *o, int slot) {
 
 // The slot's current path as frames (PathFrames): 0 for a slot without a path.
 int OnlineFrames(const pk_mi355_online_decoder *o, int slot, int32_t *arc_ids, int32_t *trans_ids, float *ac, int max_frames) {
-  const OnlineResult &r = o->res[slot];
+  const Slot &s = o->slots[slot];
+  const OnlineResult &r = s.res;
   if (!r.has_path || !r.ok || r.status) return 0;
-  if (!o->aligned[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d was decoded with alignment off", slot);
+  if (!s.aligned) return Fail(PK_MI355_E_STATE, "online decoder: slot %d was decoded with alignment off", slot);
   std::vector<int32_t> joined;
   std::vector<float> joined_ac;
-  const auto &p = OnlinePath(o, slot, &joined);
-  const auto &pa = OnlinePathAc(o, slot, &joined_ac);
+  const auto &p = Joined(s.committed, s.path, &joined);
+  const auto &pa = Joined(s.committed_ac, s.path_ac, &joined_ac);
   if (pa.size() != p.size()) return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: path and costs differ in length", slot);
   return PathFrames(o->labels, p.data(), pa.data(), (int)p.size(), r.frames, arc_ids, trans_ids, ac, max_frames);
 }
@@ -196,15 +196,15 @@ int OnlineFrames(const pk_mi355_online_decoder *o, int slot, int32_t *arc_ids, i
 
 namespace pkhost {
 bool OnlineDecoderSlotOpen(const pk_mi355_online_decoder *o, int slot) {
-  return o && slot >= 0 && slot < o->max_streams && o->open_[slot] != 0;
+  return o && slot >= 0 && slot < o->max_streams && o->slots[slot].open != 0;
 }
 const std::vector<int> *OnlineDecoderCommittedWords(const pk_mi355_online_decoder *o, int slot) {
-  return o && slot >= 0 && slot < o->max_streams ? &o->committed_words[slot] : nullptr;
+  return o && slot >= 0 && slot < o->max_streams ? &o->slots[slot].committed_words : nullptr;
 }
 void OnlineDecoderTailWords(const pk_mi355_online_decoder *o, int slot, std::vector<int> *words) {
   words->clear();
   if (!o || slot < 0 || slot >= o->max_streams) return;
-  const auto &p = o->paths[slot];
+  const auto &p = o->slots[slot].path;
   words->resize(PathWords(o->labels.olabel, p.data(), (int)p.size(), nullptr, 0));
   PathWords(o->labels.olabel, p.data(), (int)p.size(), words->data(), (int)words->size());
 }
@@ -234,18 +234,7 @@ pk_mi355_online_decoder_t *pk_mi355_online_decoder_create(const pk_mi355_fst_t *
   if (ok) chk(hipMalloc(&o->d_remap, sizeof(int) * cap * max_streams));
   if (ok) chk(hipMalloc(&o->d_calls, sizeof(OnlineCall) * max_streams));
   if (!ok) { pk_mi355_online_decoder_destroy(o); return nullptr; }
-  o->open_.assign(max_streams, 0); o->fresh.assign(max_streams, 1); o->finished.assign(max_streams, 0);
-  o->res.assign(max_streams, OnlineResult{});
-  o->paths.assign(max_streams, {});
-  o->path_acs.assign(max_streams, {});
-  o->aligned.assign(max_streams, 0);
-  o->committing.assign(max_streams, 0);
-  o->committed.assign(max_streams, {});
-  o->committed_ac.assign(max_streams, {});
-  o->committed_words.assign(max_streams, {});
-  o->committed_frames.assign(max_streams, 0);
-  o->in_use.assign(max_streams, 0);
-  o->peak.assign(max_streams, 0);
+  o->slots.assign(max_streams, Slot{});
   return o;
 }
 
@@ -268,7 +257,7 @@ int pk_mi355_online_decoder_set_beam(pk_mi355_online_decoder_t *o, float beam, i
 int pk_mi355_online_decoder_set_alignment(pk_mi355_online_decoder_t *o, int enable) {
   if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
   for (int slot = 0; slot < o->max_streams; ++slot)     // one launch serves every slot: the mode is the object's
-    if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_alignment needs every slot closed)", slot);
+    if (o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_alignment needs every slot closed)", slot);
   int rc = UseDevice(o->device);
   if (rc) return rc;
   // A call still in flight ends first.  What it says of a slot (capacity, a closure that did not settle) was that
@@ -289,7 +278,7 @@ int pk_mi355_online_decoder_set_alignment(pk_mi355_online_decoder_t *o, int enab
 int pk_mi355_online_decoder_set_commit(pk_mi355_online_decoder_t *o, int enable) {
   if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
   for (int slot = 0; slot < o->max_streams; ++slot)     // one launch serves every slot: the mode is the object's
-    if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_commit needs every slot closed)", slot);
+    if (o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_commit needs every slot closed)", slot);
   int rc = UseDevice(o->device);
   if (rc) return rc;
   if ((rc = OnlineCollect(o)) == PK_MI355_E_DEVICE) return rc;      // (as set_alignment: a call in flight ends first)
@@ -300,19 +289,11 @@ int pk_mi355_online_decoder_set_commit(pk_mi355_online_decoder_t *o, int enable)
 int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {
   int rc = OnlineSlot(o, slot);
   if (rc) return rc;
-  if (o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open", slot);
+  if (o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open", slot);
   if ((rc = OnlineCollect(o))) return rc;       // a result of the slot's last utterance is replaced
-  o->open_[slot] = 1; o->fresh[slot] = 1; o->finished[slot] = 0;
-  o->res[slot] = OnlineResult{};
-  o->paths[slot].clear();
-  o->path_acs[slot].clear();
-  o->aligned[slot] = o->align ? 1 : 0;
-  o->committing[slot] = o->commit ? 1 : 0;
-  o->committed[slot].clear();
-  o->committed_ac[slot].clear();
-  o->committed_words[slot].clear();
-  o->committed_frames[slot] = 0;
-  o->in_use[slot] = 0; o->peak[slot] = 0;
+  Slot fresh;
+  fresh.open = 1; fresh.aligned = o->align; fresh.committing = o->commit;
+  o->slots[slot] = fresh;
   return 0;
 }
 
@@ -327,12 +308,12 @@ int pk_mi355_online_decoder_advance_host(pk_mi355_online_decoder_t *o, const int
   for (int i = 0; i < n; ++i) {
     const int slot = slots[i];
     if ((rc = OnlineSlot(o, slot))) return rc;
-    if (!o->open_[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not open", slot);
+    if (!o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not open", slot);
     if (seen[slot]) return Fail(PK_MI355_E_INVALID, "online decoder: slot %d twice in one call", slot);
     seen[slot] = 1;
     const pk_matrix_t &m = chunks[i].log_prob;
     if ((rc = CheckLoglik(o, m, "online decoder: chunk", i))) return rc;
-    calls[i] = OnlineCall{slot, m.ncol, final_ && final_[i] ? 1 : 0, o->fresh[slot], total};
+    calls[i] = OnlineCall{slot, m.ncol, final_ && final_[i] ? 1 : 0, o->slots[slot].fresh, total};
     total += (int64_t)m.ncol * o->num_pdfs;
   }
   if (o->pending) HIP_TRY(hipEventSynchronize(o->done));     // d_ll may still be read by the previous call
@@ -351,12 +332,12 @@ int pk_mi355_online_decoder_advance(pk_mi355_online_decoder_t *o, pk_mi355_strea
   std::vector<OnlineCall> calls;
   const float *base = StreamLoglikBase(s);
   for (int slot = 0; slot < StreamSlots(s); ++slot) {
-    if (!o->open_[slot]) continue;
+    if (!o->slots[slot].open) continue;
     int first = 0, count = 0;
     const float *p = pk_mi355_stream_loglik_device(s, slot, &first, &count);
     const bool fin = StreamSlotFlushed(s, slot);
     if (count == 0 && !fin) continue;
-    calls.push_back(OnlineCall{slot, count, fin ? 1 : 0, o->fresh[slot], count ? (int64_t)(p - base) : 0});
+    calls.push_back(OnlineCall{slot, count, fin ? 1 : 0, o->slots[slot].fresh, count ? (int64_t)(p - base) : 0});
   }
   if ((rc = OnlineLaunch(o, base, calls, StreamHipStream(s)))) return rc;
   return sync ? OnlineCollect(o) : 0;
@@ -370,7 +351,7 @@ int pk_mi355_online_decoder_synchronize(pk_mi355_online_decoder_t *o) {
 int pk_mi355_online_decoder_partial(const pk_mi355_online_decoder_t *o, int slot, int *words, int max_words, float *cost) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  if (cost) *cost = o->res[slot].weight;
+  if (cost) *cost = o->slots[slot].res.weight;
   return OnlineWords(o, slot, words, max_words);
 }
 
@@ -378,9 +359,9 @@ int pk_mi355_online_decoder_result(const pk_mi355_online_decoder_t *o, int slot,
                                    int *ok) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  if (!o->finished[slot] || !o->res[slot].final_) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not finished", slot);
-  if (weight) *weight = o->res[slot].weight;
-  if (ok) *ok = o->res[slot].ok;
+  if (!o->slots[slot].finished || !o->slots[slot].res.final_) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not finished", slot);
+  if (weight) *weight = o->slots[slot].res.weight;
+  if (ok) *ok = o->slots[slot].res.ok;
   return OnlineWords(o, slot, words, max_words);
 }
 
@@ -388,7 +369,7 @@ int pk_mi355_online_decoder_best_path_arcs(const pk_mi355_online_decoder_t *o, i
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
   std::vector<int32_t> joined;
-  const auto &p = OnlinePath(o, slot, &joined);
+  const auto &p = Joined(o->slots[slot].committed, o->slots[slot].path, &joined);
   for (int i = 0; i < (int)p.size() && i < max_arcs; ++i) arcs[i] = p[i];
   return (int)p.size();
 }
@@ -397,10 +378,10 @@ int pk_mi355_online_decoder_word_segments(const pk_mi355_online_decoder_t *o, in
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
   std::vector<int32_t> joined;
-  const auto &p = OnlinePath(o, slot, &joined);
-  if (!o->align || !o->aligned[slot])             // (the rows are gone, and no cost was kept: no acoustic cost)
+  const auto &p = Joined(o->slots[slot].committed, o->slots[slot].path, &joined);
+  if (!o->align || !o->slots[slot].aligned)             // (the rows are gone, and no cost was kept: no acoustic cost)
     return WordSegments(o->labels, p.data(), (int)p.size(), nullptr, 0, out, max);
-  std::vector<float> ac(std::max(o->res[slot].frames, 1));                    // the costs kept with the trace
+  std::vector<float> ac(std::max(o->slots[slot].res.frames, 1));                    // the costs kept with the trace
   const int frames = OnlineFrames(o, slot, nullptr, nullptr, ac.data(), (int)ac.size());
   if (frames < 0) return frames;
   return WordSegments(o->labels, p.data(), (int)p.size(), ac.data(), frames, out, max);
@@ -418,9 +399,9 @@ int pk_mi355_online_decoder_committed(const pk_mi355_online_decoder_t *o, int sl
                                       int *num_frames) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  const auto &cw = o->committed_words[slot];
-  if (num_arcs) *num_arcs = (int)o->committed[slot].size();
-  if (num_frames) *num_frames = o->committed_frames[slot];
+  const auto &cw = o->slots[slot].committed_words;
+  if (num_arcs) *num_arcs = (int)o->slots[slot].committed.size();
+  if (num_frames) *num_frames = o->slots[slot].committed_frames;
   for (int i = 0; words && i < (int)cw.size() && i < max_words; ++i) words[i] = cw[i];
   return (int)cw.size();
 }
@@ -429,9 +410,9 @@ int pk_mi355_online_decoder_trace_stats(const pk_mi355_online_decoder_t *o, int 
                                         int64_t *capacity) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  if (o->fresh[slot]) return Fail(PK_MI355_E_STATE, "online decoder: slot %d has not been advanced since it was opened", slot);
-  if (in_use) *in_use = o->in_use[slot];
-  if (peak) *peak = o->peak[slot];
+  if (o->slots[slot].fresh) return Fail(PK_MI355_E_STATE, "online decoder: slot %d has not been advanced since it was opened", slot);
+  if (in_use) *in_use = o->slots[slot].in_use;
+  if (peak) *peak = o->slots[slot].peak;
   if (capacity) *capacity = o->cap;
   return 0;
 }
@@ -439,13 +420,13 @@ int pk_mi355_online_decoder_trace_stats(const pk_mi355_online_decoder_t *o, int 
 int pk_mi355_online_decoder_num_frames(const pk_mi355_online_decoder_t *o, int slot) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  return o->res[slot].frames;
+  return o->slots[slot].res.frames;
 }
 
 int pk_mi355_online_decoder_active_bound(const pk_mi355_online_decoder_t *o, int slot) {
   int rc = OnlineReady(o, slot);
   if (rc) return rc;
-  return o->res[slot].active_bound;
+  return o->slots[slot].res.active_bound;
 }
 
 }  // extern "C"

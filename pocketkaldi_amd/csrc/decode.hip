@@ -420,107 +420,75 @@ __device__ __forceinline__ int PathLen(const Arena &R, int trace) {
   for (int x = trace; x >= 0 && len <= R.cap; x = R.rec[x].x) ++len;
   return len;
 }
-__device__ __forceinline__ void FillPath(const Arena &R, int trace, int *path, int len) {
-  for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) path[--len] = R.rec[x].y;
-}
-// the same walk, the records' acoustic costs beside their arcs (kAc)
-__device__ __forceinline__ void FillPathAc(const Arena &R, int trace, int *path, float *path_ac, int len) {
+// kAc: the records' acoustic costs beside their arcs (path_ac is not read otherwise)
+template <bool kAc>
+__device__ __forceinline__ void FillPath(const Arena &R, int trace, int *path, [[maybe_unused]] float *path_ac, int len) {
   for (int x = trace; x >= 0 && len > 0; x = R.rec[x].x) {
     path[--len] = R.rec[x].y;
-    path_ac[len] = R.ac[x];
+    if constexpr (kAc) path_ac[len] = R.ac[x];
   }
 }
 
-// Mark the records reachable from the list's tokens, renumber them in creation order with an exclusive scan (a
-// record's predecessor is always older, so one forward pass remaps every `prev`), move them down, and rewrite the
-// tokens' trace (and the state table's, which the next emitting step reads).  Changes where records live, never a
-// result.  kAc: rec_ac[i] moves wherever rec[i] does.
-template <bool kAc>
-__device__ void CompactTrace(Shared &sh, int2 *rec, float *rec_ac, int *remap, unsigned long long *top, Tok *L, int nL,
-                             int *tr) {
-  const int n = (int)*top;
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += kDecThreads) remap[i] = 0;
-  __syncthreads();
-  for (int j = threadIdx.x; j < nL; j += kDecThreads)
-    for (int x = L[j].trace; x >= 0 && atomicExch(&remap[x], 1) == 0;) x = rec[x].x;
-  __syncthreads();
-  int base = 0;
-  for (int c0 = 0; c0 < n; c0 += kDecThreads) {
-    const int i = c0 + threadIdx.x;
-    const int alive = i < n ? __hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;   // set by atomics
-    int2 r = make_int2(-1, -1);
-    [[maybe_unused]] float ac = 0.0f;
-    if (alive) {
-      r = rec[i];
-      if constexpr (kAc) ac = rec_ac[i];
-    }
-    int total;
-    const int ex = BlockScan(sh, alive, &total);    // (its barriers: every read of this chunk is done)
-    if (i < n) remap[i] = alive ? base + ex : -1;
-    __syncthreads();
-    if (alive) {
-      r.x = r.x >= 0 ? remap[r.x] : -1;            // older: remapped in this chunk or an earlier one
-      rec[base + ex] = r;
-      if constexpr (kAc) rec_ac[base + ex] = ac;
-    }
-    base += total;
-    __syncthreads();
-  }
-  for (int j = threadIdx.x; j < nL; j += kDecThreads) {
-    const int x = L[j].trace;
-    if (x >= 0) {
-      L[j].trace = remap[x];
-      tr[L[j].state] = remap[x];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *top = (unsigned long long)base;
-  __syncthreads();
-}
-
-// The commit mode's end-of-launch compaction (pk_mi355_online_decoder_set_commit): CompactTrace's three passes with a
-// count in place of the mark.  Every token walks from its record towards the root adding 1 to remap[x] and goes on
-// only where it was the first to arrive, so remap[x] = (reachable children of x) + (tokens at x) and every reachable
-// record is visited by one walker.  With one root and no token at the start (trace < 0), b = the lowest index that
-// either carries a count >= 2 or is a token's own record is the last record every path shares: a predecessor is always
-// older and compaction keeps creation order, so everything off the trunk -- a descendant of the first branching
-// record -- has a higher index than it, and the reachable records below b ARE the trunk, in path order.  Those go, in
-// that order, to path[0, nc) (their costs to path_ac with kAc); the rest moves down as in CompactTrace, b to index 0
-// with prev = -1.  Otherwise b = 0 and this is a plain compaction.  Every index read from memory is checked against
-// the arena's top before it is used.  Returns nc (all threads), or -1 when the records are inconsistent.
+// The trace compaction, three passes.  Count: every token walks from its record towards the root adding 1 to remap[x]
+// and goes on only where it was the first to arrive, so remap[x] = (reachable children of x) + (tokens at x) and every
+// reachable record is visited by one walker.  Rank: the reachable records are numbered in creation order with a chunked
+// exclusive scan (a record's predecessor is always older, so one forward pass remaps every `prev`).  Move: they go
+// down to their rank, and the tokens' trace (and the state table's, which the next emitting step reads) is rewritten.
+// Changes where records live, never a result.  kAc: R.ac[i] moves wherever rec[i] does.
+// kCommit = false, the compaction inside a launch: every reachable record stays (b = 0); remap is trusted, nothing is
+// checked, path and path_ac are not read, and 0 is returned.
+// kCommit = true, the commit mode's end of a launch (pk_mi355_online_decoder_set_commit): with one root and no token at
+// the start (trace < 0), b = the lowest index that either carries a count >= 2 or is a token's own record is the last
+// record every path shares: a predecessor is always older and compaction keeps creation order, so everything off the
+// trunk -- a descendant of the first branching record -- has a higher index than it, and the reachable records below b
+// ARE the trunk, in path order.  Those go, in that order, to path[0, nc) (their costs to path_ac with kAc); the rest
+// moves down, b to index 0 with prev = -1.  Otherwise b = 0 and this is the plain compaction.  Every index read from
+// memory is checked against the arena's top before it is used.  Returns nc (all threads), or -1 when the records are
+// inconsistent.
 constexpr int kCommitNone = 1, kCommitBad = 2;       // sh.fail: a token at the start; an index out of range
 
-template <bool kAc>
-__device__ int CommitTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int nL, int *tr, int *path, float *path_ac) {
+template <bool kAc, bool kCommit>
+__device__ int CompactTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int nL, int *tr, [[maybe_unused]] int *path,
+                            [[maybe_unused]] float *path_ac) {
   int2 *rec = R.rec;
   const unsigned long long top = *R.top;
   __syncthreads();
-  if (top > (unsigned long long)R.cap) return -1;
+  if constexpr (kCommit) {
+    if (top > (unsigned long long)R.cap) return -1;
+  }
   const int n = (int)top;
   for (int i = threadIdx.x; i < n; i += kDecThreads) remap[i] = 0;
-  if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.fail = 0; sh.sel = 0; }     // roots; flags; nc
+  if constexpr (kCommit) {
+    if (threadIdx.x == 0) { sh.cnt_nxt = 0; sh.fail = 0; sh.sel = 0; }   // roots; flags; nc
+  }
   __syncthreads();
-  uint64_t lo = kEmpty;
+  [[maybe_unused]] uint64_t lo = kEmpty;
   for (int j = threadIdx.x; j < nL; j += kDecThreads) {
     int x = L[j].trace;
-    if (x < 0) { atomicOr(&sh.fail, kCommitNone); continue; }
-    if (x >= n) { atomicOr(&sh.fail, kCommitBad); continue; }
-    lo = min(lo, (uint64_t)x);
-    while (atomicAdd(&remap[x], 1) == 0) {
+    if constexpr (kCommit) {
+      if (x < 0) { atomicOr(&sh.fail, kCommitNone); continue; }
+      if (x >= n) { atomicOr(&sh.fail, kCommitBad); continue; }
+      lo = min(lo, (uint64_t)x);
+    }
+    while (x >= 0 && atomicAdd(&remap[x], 1) == 0) {
       const int p = rec[x].x;
-      if (p < 0) { atomicAdd(&sh.cnt_nxt, 1); break; }
-      if (p >= x) { atomicOr(&sh.fail, kCommitBad); break; }            // (older, so in range; and the walk ends)
+      if constexpr (kCommit) {
+        if (p < 0) atomicAdd(&sh.cnt_nxt, 1);
+        else if (p >= x) { atomicOr(&sh.fail, kCommitBad); break; }     // (older, so in range; and the walk ends)
+      }
       x = p;
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < n; i += kDecThreads)
-    if (__hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 2) { lo = min(lo, (uint64_t)i); break; }
-  lo = BlockMinU(sh, lo);
-  const int flags = sh.fail;
-  if (flags & kCommitBad) return -1;
-  const int b = (sh.cnt_nxt == 1 && !flags && lo != kEmpty) ? (int)lo : 0;
+  int b = 0;
+  if constexpr (kCommit) {
+    for (int i = threadIdx.x; i < n; i += kDecThreads)
+      if (__hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 2) { lo = min(lo, (uint64_t)i); break; }
+    lo = BlockMinU(sh, lo);
+    const int flags = sh.fail;
+    if (flags & kCommitBad) return -1;
+    if (sh.cnt_nxt == 1 && !flags && lo != kEmpty) b = (int)lo;
+  }
   int base = 0;
   for (int c0 = 0; c0 < n; c0 += kDecThreads) {
     const int i = c0 + threadIdx.x;
@@ -533,17 +501,21 @@ __device__ int CommitTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int n
     }
     int total;
     const int g = base + BlockScan(sh, alive, &total);   // rank among the reachable: trunk first, b at nc
-    if (alive && i == b) sh.sel = g;
-    __syncthreads();
-    const int nc = i >= b ? sh.sel : 0;
+                                                         // (its barriers: every read of this chunk is done)
+    int nc = 0;
+    if constexpr (kCommit) {
+      if (alive && i == b) sh.sel = g;
+      __syncthreads();
+      nc = i >= b ? sh.sel : 0;
+    }
     if (i < n) remap[i] = (alive && i >= b) ? g - nc : -1;
     __syncthreads();
     if (alive) {
-      if (i < b) {
+      if (kCommit && i < b) {
         path[g] = r.y;
         if constexpr (kAc) path_ac[g] = ac;
       } else {
-        r.x = (i > b && r.x >= 0) ? remap[r.x] : -1;     // older: remapped in this chunk or an earlier one
+        r.x = (!(kCommit && i == b) && r.x >= 0) ? remap[r.x] : -1;   // older: remapped in this chunk or an earlier one
         rec[g - nc] = r;
         if constexpr (kAc) R.ac[g - nc] = ac;
       }
@@ -551,7 +523,7 @@ __device__ int CommitTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int n
     base += total;
     __syncthreads();
   }
-  const int nc = sh.sel;
+  const int nc = kCommit ? sh.sel : 0;
   for (int j = threadIdx.x; j < nL; j += kDecThreads) {
     const int x = L[j].trace;
     if (x >= 0) {
@@ -563,6 +535,14 @@ __device__ int CommitTrace(Shared &sh, const Arena &R, int *remap, Tok *L, int n
   if (threadIdx.x == 0) *R.top = (unsigned long long)(base - nc);
   __syncthreads();
   return nc;
+}
+
+// What DecodeKernel<true> and OnlineDecodeKernel run before an emitting frame: a slice more than half full is compacted.
+template <bool kAc>
+__device__ __forceinline__ bool CompactIfHalfFull(Shared &sh, const Arena &R, int *remap, Tok *L, int nL, int *tr) {
+  if (*R.top <= (unsigned long long)(R.cap / 2)) return false;
+  CompactTrace<kAc, false>(sh, R, remap, L, nL, tr, nullptr, nullptr);
+  return true;
 }
 
 // kGc = false: the call's shared arena and path arena, their bump counters in HBM; nothing is reclaimed.
@@ -586,12 +566,8 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
     w = WorkOf(A, u, Arena{A.rec + at, A.rec_cap, &s_top, nullptr});
     int *remap = A.path + at;
     DecodeFrames<false>(sh, s_ll, A, w, A.ll + A.ll_off[u], -1, A.T[u], [&](Tok *L, int nL) {
-      const unsigned long long top = s_top;
-      peak = max(peak, (int)top);
-      if (top > (unsigned long long)(A.rec_cap / 2)) {
-        CompactTrace<false>(sh, w.arena.rec, nullptr, remap, &s_top, L, nL, w.tr);
-        ++compactions;
-      }
+      peak = max(peak, (int)s_top);
+      compactions += CompactIfHalfFull<false>(sh, w.arena, remap, L, nL, w.tr);
     });
     peak = (int)min((unsigned long long)A.rec_cap, max((unsigned long long)peak, s_top));   // (a failed bump overshoots)
   } else {
@@ -614,7 +590,7 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
           r.ok = 0;
         } else {
           r.path_off = int((int64_t)u * A.rec_cap); r.path_len = len;
-          FillPath(w.arena, w.L[bi].trace, A.path + r.path_off, len);
+          FillPath<false>(w.arena, w.L[bi].trace, A.path + r.path_off, nullptr, len);
         }
       } else {
         const int off = atomicAdd(A.path_top, len);    // the call's shared path arena
@@ -623,7 +599,7 @@ __global__ void __launch_bounds__(kDecThreads) DecodeKernel(DecArgs A) {
           r.ok = 0;
         } else {
           r.path_off = off; r.path_len = len;
-          FillPath(w.arena, w.L[bi].trace, A.path + off, len);
+          FillPath<false>(w.arena, w.L[bi].trace, A.path + off, nullptr, len);
         }
       }
     }
@@ -699,21 +675,24 @@ __global__ void __launch_bounds__(kDecThreads) AlignKernel(AlignArgs A) {
 // DecodeFrames, resumable: a slot's token list, its count and buffer, ok / status, the largest touched count, the
 // frames decoded and its trace-arena top live in HBM between launches.  One workgroup per slot with new frames;
 // InitDecoding on the slot's first launch, BestPath only once the slot is closed.  Each slot has an arena of its own
-// (A.rec and A.path hold `cap` entries per slot); when it is more than half full before an emitting frame the
-// reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity are all
-// this kernel adds to the frame step: DecodeKernel<false> instantiates it with an empty `before` and never reads them.
-// kAc (pk_mi355_online_decoder_set_alignment): rec_ac and path_ac, `cap` floats per slot, run parallel to the slot's
+// (A.rec, A.path and A.remap hold cap = A.rec_cap entries per slot); when it is more than half full before an emitting
+// frame the reachable records are compacted (CompactTrace).  The compaction, the frame count and the list-buffer parity
+// are all this kernel adds to the frame step: DecodeKernel<false> instantiates it with an empty `before` and never
+// reads them.
+// kAc (pk_mi355_online_decoder_set_alignment): A.rec_ac and A.path_ac, `cap` floats per slot, run parallel to the slot's
 // records and path -- a frame's acoustic cost is kept when the frame is decoded, since its row is void afterwards.
-// With kAc = false neither pointer is read.
+// kCommit (pk_mi355_online_decoder_set_commit): the slot's path slice ends the launch with A.commit_len[slot] newly
+// committed arcs followed by the result's path_len arcs of the best token's tail, and st.peak is kept.
+// A mode that is off reads none of its pointers and writes neither A.commit_len nor st.peak.
 
 template <bool kAc, bool kCommit>
 __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, const OnlineCall *calls, OnlineState *states,
-                                                                    OnlineResult *results, int *remap_all, int64_t cap,
-                                                                    float *rec_ac, float *path_ac, int *commit_len) {
+                                                                    OnlineResult *results) {
   extern __shared__ float s_ll[];
   __shared__ Shared sh;
   const OnlineCall call = calls[blockIdx.x];
   const int u = call.slot;
+  const int64_t cap = A.rec_cap, at = (int64_t)u * cap;      // the slot's own arena, and where its slices begin
   OnlineState st = states[u];
   if (call.fresh) {
     st.nL = 0; st.par = 0; st.ok = 1; st.status = 0; st.active = 0; st.frames = 0; st.started = 0; st.peak = 0; st.top = 0;
@@ -721,27 +700,28 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
   __shared__ unsigned long long s_top;
   if (threadIdx.x == 0) s_top = st.top;
   __syncthreads();
-  Work w = WorkOf(A, u, Arena{A.rec + (int64_t)u * cap, cap, &s_top, kAc ? rec_ac + (int64_t)u * cap : nullptr});   // the slot's own arena
-  int *remap = remap_all + (int64_t)u * cap;
+  Work w = WorkOf(A, u, Arena{A.rec + at, cap, &s_top, kAc ? A.rec_ac + at : nullptr});
+  int *remap = A.remap + at;
+  int *path = A.path + at;
+  [[maybe_unused]] float *path_ac = kAc ? A.path_ac + at : nullptr;
   [[maybe_unused]] unsigned long long peak = (unsigned long long)st.peak;   // kCommit: the most the arena held since open
   if (st.par) { Tok *x = w.L; w.L = w.Lnext; w.Lnext = x; }
   w.nL = st.nL; w.status = st.status; w.ok = st.ok; w.active = st.active; w.frames = st.frames; w.par = st.par;
   if (!w.status && w.ok)
     DecodeFrames<kAc>(sh, s_ll, A, w, A.ll + call.ll_off, st.started ? 0 : -1, call.T, [&](Tok *L, int nL) {
-      if (s_top > (unsigned long long)(cap / 2)) {
-        if constexpr (kCommit) peak = max(peak, s_top);
-        CompactTrace<kAc>(sh, w.arena.rec, w.arena.ac, remap, &s_top, L, nL, w.tr);
+      [[maybe_unused]] const unsigned long long top = s_top;
+      if (CompactIfHalfFull<kAc>(sh, w.arena, remap, L, nL, w.tr)) {
+        if constexpr (kCommit) peak = max(peak, top);
       }
     });
   const bool fin = call.final_ != 0;
   // kCommit: the arcs every token's path shares, but the last, leave the arena for the front of the slot's path (not in
   // the launch that finishes the slot, and not for a slot that has ended); the best token's tail follows them below
-  [[maybe_unused]] int nc = 0;
+  int nc = 0;
   if constexpr (kCommit) {
     peak = max(peak, s_top);
     if (!w.status && w.ok && !fin && w.nL > 0) {
-      nc = CommitTrace<kAc>(sh, w.arena, remap, w.L, w.nL, w.tr, A.path + (int64_t)u * cap,
-                            kAc ? path_ac + (int64_t)u * cap : nullptr);
+      nc = CompactTrace<kAc, true>(sh, w.arena, remap, w.L, w.nL, w.tr, path, path_ac);
       if (nc < 0) { w.status = PK_MI355_E_DEVICE; nc = 0; }
     }
   }
@@ -755,34 +735,24 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
     r.ok = (w.status || w.nL == 0) ? 0 : w.ok;
     r.weight = 0.f; r.path_len = 0; r.has_path = 0;
     r.active_bound = w.active; r.frames = w.frames;
-    if constexpr (kCommit) {
-      // (the committed arcs and the tail are distinct records reachable before the commit: together they fit the slice)
-      if (!w.status && r.ok && bi >= 0) {
-        r.weight = weight;
-        const int len = PathLen(w.arena, w.L[bi].trace);
-        if ((int64_t)nc + len > cap) {
-          w.status = r.status = PK_MI355_E_DEVICE;
-          r.ok = 0; r.weight = 0.f;
-          nc = 0;
-        } else {
-          r.path_len = len;
-          if constexpr (kAc)
-            FillPathAc(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap + nc, path_ac + (int64_t)u * cap + nc, len);
-          else
-            FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap + nc, len);
-          r.has_path = 1;
-        }
-      }
-      commit_len[u] = nc;
-      st.peak = (int)min((unsigned long long)cap, max(peak, s_top));        // (a failed bump overshoots)
-    } else if (!w.status && r.ok && bi >= 0) {
+    if (!w.status && r.ok && bi >= 0) {
       r.weight = weight;
-      r.path_len = PathLen(w.arena, w.L[bi].trace);
-      if constexpr (kAc)
-        FillPathAc(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, path_ac + (int64_t)u * cap, r.path_len);
-      else
-        FillPath(w.arena, w.L[bi].trace, A.path + (int64_t)u * cap, r.path_len);
-      r.has_path = 1;
+      const int len = PathLen(w.arena, w.L[bi].trace);
+      // kCommit: the committed arcs and the tail are distinct records reachable before the commit, so together they fit
+      // the slice; with nc = 0 the check is vacuous (a chain of the arena's records), and it is not compiled
+      if (kCommit && (int64_t)nc + len > cap) {
+        w.status = r.status = PK_MI355_E_DEVICE;
+        r.ok = 0; r.weight = 0.f;
+        nc = 0;
+      } else {
+        r.path_len = len;
+        FillPath<kAc>(w.arena, w.L[bi].trace, path + nc, kAc ? path_ac + nc : nullptr, len);
+        r.has_path = 1;
+      }
+    }
+    if constexpr (kCommit) {
+      A.commit_len[u] = nc;
+      st.peak = (int)min((unsigned long long)cap, max(peak, s_top));        // (a failed bump overshoots)
     }
     results[u] = r;
     st.nL = w.nL; st.par = w.par; st.ok = w.ok; st.status = w.status; st.active = w.active; st.frames = w.frames;
@@ -811,17 +781,15 @@ void LaunchAlign(const AlignArgs &A, hipStream_t stream) {
   hipLaunchKernelGGL(AlignKernel, dim3(A.num_utts), dim3(kDecThreads), 0, stream, A);
 }
 
-void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, float *rec_ac, float *path_ac, int *commit_len, int n, hipStream_t stream) {
-  const bool ac = rec_ac && path_ac;
+void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int n,
+                        hipStream_t stream) {
   auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls, states, results,
-                       remap, cap, ac ? rec_ac : nullptr, ac ? path_ac : nullptr, commit_len);
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(kDecThreads), sizeof(float) * A.num_pdfs, stream, A, calls, states, results);
   };
-  if (commit_len) {
-    if (ac) launch(OnlineDecodeKernel<true, true>); else launch(OnlineDecodeKernel<false, true>);
+  if (A.commit_len) {
+    if (A.rec_ac && A.path_ac) launch(OnlineDecodeKernel<true, true>); else launch(OnlineDecodeKernel<false, true>);
   } else {
-    if (ac) launch(OnlineDecodeKernel<true, false>); else launch(OnlineDecodeKernel<false, false>);
+    if (A.rec_ac && A.path_ac) launch(OnlineDecodeKernel<true, false>); else launch(OnlineDecodeKernel<false, false>);
   }
 }
 

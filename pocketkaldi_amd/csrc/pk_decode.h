@@ -42,13 +42,16 @@ struct DecArgs {
   int num_utts;
   // per-utterance work areas (stride num_states entries)
   uint64_t *key; int *tr; int *mark; int *touched; int *nxt; Tok *la; Tok *lb; Tok *fa; Tok *fb;
-  // backtrace arena and best-path arena.  DecodeKernel<false>: shared by the call, with their capacities and bump
-  // counters; DecodeKernel<true>: a slice of rec_cap entries of each per utterance (no counter: the top lives in LDS);
-  // OnlineDecodeKernel: rec and path only, a slice per slot (its capacity is a kernel argument, its top the slot's state)
+  // backtrace arena and best-path arena, rec_cap entries of each per utterance or slot.  Read by
+  //   DecodeKernel<false>: rec, path, rec_cap (one of each for the call), path_cap, the bump counters rec_top / path_top
+  //   DecodeKernel<true>:  rec, path (the remap scratch until the path is written), rec_cap; the slice's top is in LDS
+  //   OnlineDecodeKernel:  rec, path, rec_cap, remap (the slot's top is its OnlineState's); rec_ac and path_ac, both or
+  //     neither, with alignment (<true, .>); commit_len with commit (<., true>): what each holds is said at the kernel
   int2 *rec; int64_t rec_cap; unsigned long long *rec_top;
   int *path; int path_cap; int *path_top;
   float beam; int max_active; int max_rounds;
   UttResult *res;
+  int *remap; float *rec_ac; float *path_ac; int *commit_len;
 };
 
 struct AlignResult {
@@ -94,13 +97,9 @@ void LaunchDecode(const DecArgs &A, bool trace_gc, hipStream_t stream);
 void LaunchGatherPaths(UttResult *res, int n, const int *path, int *out, hipStream_t stream);
 // after the decode (and the gather) on the same stream: the frame of every emitting arc of the best paths
 void LaunchAlign(const AlignArgs &A, hipStream_t stream);
-// the new frames of n slots; states, results, remap and A.rec / A.path hold `cap` entries per slot.  rec_ac and path_ac
-// (`cap` floats per slot, both or neither): the alignment mode -- a record's acoustic cost kept beside it, a path's beside
-// its arcs (OnlineDecodeKernel<true, .>); null: OnlineDecodeKernel<false, .>.  commit_len (one int per slot): the commit
-// mode, OnlineDecodeKernel<., true> -- a slot's path slice then holds commit_len[slot] newly committed arcs followed by
-// the result's path_len arcs of the best token's tail; null: OnlineDecodeKernel<., false>, which never reads it
-void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int *remap,
-                        int64_t cap, float *rec_ac, float *path_ac, int *commit_len, int n, hipStream_t stream);
+// the new frames of n slots (calls; states and results are per slot): OnlineDecodeKernel<A.rec_ac && A.path_ac, A.commit_len>
+void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int n,
+                        hipStream_t stream);
 
 }  // namespace pkmi
 

@@ -1,8 +1,8 @@
 """The commit rule of the online decoder (pk_mi355_online_decoder_set_commit) on the CPU: the per-frame host model
 (tests/commit_model.py) ends where decoder_model.decode ends; hand-worked cases of the rule; and the ordering claim
-CommitTrace rests on -- in an arena whose indices are in creation order, the reachable records below the first
-branching index are the shared trunk, in path order -- on a model of the arena that grows, branches, prunes, compacts
-and commits."""
+the commit (CompactTrace<., true>) rests on -- in an arena whose indices are in creation order, the reachable records
+below the first branching index are the shared trunk, in path order -- on a model of the arena that grows, branches,
+prunes, compacts and commits."""
 import numpy as np
 import pytest
 
@@ -153,3 +153,35 @@ def test_reachable_records_below_the_first_branch_are_the_trunk_in_path_order(se
             committed += arcs
             grew += 1
     assert grew >= 3 and len(committed) >= 10, (seed, grew, len(committed))
+
+
+@pytest.mark.parametrize("n", CC.EDGES)
+def test_two_chains_hold_exactly_n_records_at_the_first_compaction(n):
+    """The record counts tests/test_gpu_compact_edges.py rests on, from the host model's token sets: every token of a
+    frame is one new record behind its predecessor's; before a frame the arena is compacted, order kept, when more than
+    half of cap is in use.  The first compaction finds exactly n records and keeps n - DEAD_FROM; there is no second."""
+    D = CC.DEAD_FROM
+    g, ll, cap = CC.two_chains(n)
+    r = CM.decode(CC.with_ids(g), ll, CC.PDF, beam=CC.WIDE, max_active=1 << 30)
+    assert r["ok"] == 1 and len(r["path"]) == ll.shape[0] == n - D + 4
+    assert [len(f["tokens"]) for f in r["frames"][1:]] == [2] * D + [1] * (n - D + 4 - D)
+    rec, at, seen = [], {(): -1}, []                           # records (prev, arc); a path's record; (top, survivors)
+    for t in range(ll.shape[0]):
+        if len(rec) > cap // 2:
+            alive = set()
+            for p in (p for _, p in r["frames"][t]["tokens"].values()):
+                x = at[tuple(p)]
+                while x >= 0 and x not in alive:
+                    alive.add(x)
+                    x = rec[x][0]
+            remap = {x: i for i, x in enumerate(sorted(alive))}
+            seen.append((len(rec), len(alive), t))
+            rec = [(remap.get(rec[x][0], -1), rec[x][1]) for x in sorted(alive)]
+            at = {p: remap[x] for p, x in at.items() if x in remap}
+        for _, p in sorted(r["frames"][t + 1]["tokens"].values(), key=lambda v: v[1][-1]):
+            rec.append((at[tuple(p[:-1])] if len(p) > 1 else -1, p[-1]))
+            at[tuple(p)] = len(rec) - 1
+    assert seen == [(n, n - D, n - D)]                         # top == n exactly, before frame n - D
+    assert len(rec) == n - D + 4 and max(len(rec), seen[0][0]) == n
+    # (the dead chain's records lay between the live ones: what moved down is still the best path, in order)
+    assert CC.path_of(rec, len(rec) - 1) == r["path"]

@@ -1,5 +1,5 @@
 """The online decoder's commit mode (pk_mi355_online_decoder_set_commit / _committed / _trace_stats,
-pk_mi355_online_recognizer_stable: csrc/capi_online_decoder.hip; CommitTrace and OnlineDecodeKernel<., true> in
+pk_mi355_online_recognizer_stable: csrc/capi_online_decoder.hip; CompactTrace<., true> and OnlineDecodeKernel<., true> in
 csrc/decode.hip).  The mode changes no result at any step; the committed prefix only grows, is a prefix of every later
 path and is exactly the host model's max(|P| - 1, 0) arcs (tests/commit_model.py); a stream longer than its arena
 decodes with the mode on and ends with PK_MI355_E_CAPACITY with it off; the scan's chunk edges; the edges of the rule;
