@@ -264,6 +264,30 @@ int pk_mi355_cmvn_apply(const pk_vector_t *global_stats, const pk_matrix_t *raw,
                         pk_matrix_t *out);
 
 /* ------------------------------------------------------------------------- */
+/* Sample-rate conversion to 16 kHz: 8 .. 96 kHz in, on the GPU */
+/* ------------------------------------------------------------------------- */
+
+/* The windowed-sinc rule of Kaldi's LinearResample.  Input rate fi, output rate fo = 16000, g = gcd(fi, fo),
+ * Q = fi / g input samples per unit, P = fo / g phases; cutoff fc = 0.99 * 0.5 * min(fi, fo), Z = 6 zero crossings,
+ * half-width w = Z / (2 fc) seconds.  Phase p (time offset p / fo) has the taps i with |i / fi - p / fo| < w: first[p]
+ * is the smallest, count[p] their number, weight[p][k] = 2 fc sinc(2 fc d) 0.5 (1 + cos(2 pi fc d / Z)) / fi with
+ * d = (first[p] + k) / fi - p / fo, formed in double and rounded to float once.  Output j = u P + p is
+ *     y[j] = sum over k = 0 .. count[p] - 1, ascending, of weight[p][k] * x[first[p] + u Q + k]
+ * in fp32 from +0.0f, each term a rounded product then a rounded add, x outside [0, n) read as +0.0f (its term is
+ * still evaluated).  n inputs give floor(n P / Q) outputs.  One arithmetic order per output sample: the result does not
+ * depend on batching, tiling or chunking.  Supported: 8000 <= fi <= 96000 with P * max count <= 16384; any other rate
+ * fails with PK_MI355_E_INVALID and is named in pk_mi355_last_error().  fi = 16000 is the identity and launches nothing.
+ *
+ * Host only, no device: the plan of a rate, its table (first[P], count[P], weights[P][max_taps] with every row
+ * zero-padded behind count[p]; any pointer may be NULL) and the output count (negative code on failure).            */
+int pk_mi355_resample_plan(int rate, int *Q, int *P, int *max_taps);
+int pk_mi355_resample_table(int rate, int32_t *first, int32_t *count, float *weights);
+int64_t pk_mi355_resample_num_output(int rate, int64_t num_samples);
+/* One wave (host, sample values at `rate`) -> out (host, 16 kHz; out->data is (re)allocated with realloc()), converted
+ * on the device as pk_mi355_fbank_compute computes features.                                                         */
+int pk_mi355_resample(const pk_vector_t *wave, int rate, pk_vector_t *out);
+
+/* ------------------------------------------------------------------------- */
 /* Batched scorer: many utterances in flight, PCM in -> log-likelihoods out,     */
 /* everything device-resident (the stages of pk_process, pocketkaldi.cc:176-218). */
 /* ------------------------------------------------------------------------- */
@@ -286,6 +310,13 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b);
 /* Hand over B utterances as host PCM (float sample values as pk_16kpcm_read
  * produces them, pcm_reader.cc:189-211); copied to HBM.                          */
 int pk_mi355_batch_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, int num_utts);
+/* Same, utterance u sampled at rates[u] Hz (rates == NULL: 16000 throughout).  With 16000 everywhere this IS
+ * pk_mi355_batch_set_waves.  Otherwise the utterances at 16000 are copied as set_waves copies them and the others are
+ * staged at their own rate (a page-locked and a device buffer the batch makes and grows on demand) and converted on the
+ * batch's stream straight to where set_waves would have put them: scoring reads the same layout.  Capacity
+ * (max_total_samples) counts 16 kHz samples, the sum of pk_mi355_resample_num_output over the utterances.
+ * (Named with the resampler's entries: it is pk_mi355_batch_set_waves with a conversion in front.)                  */
+int pk_mi355_resample_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, const int *rates, int num_utts);
 /* Same, from one concatenated host int16 buffer (the WAV payload itself).        */
 int pk_mi355_batch_set_waves_i16(pk_mi355_batch_t *b, const int16_t *samples,
                                  const int *num_samples, int num_utts);
@@ -390,6 +421,12 @@ double pk_mi355_am_flops_per_frame(const pk_mi355_am_t *am);
  * 16 kHz, 8/16/32-bit; samples are stored unscaled as float.  pcm_data->data is
  * (re)allocated with realloc().  Host only, needs no GPU.                          */
 int pk_mi355_16kpcm_read(const char *filename, pk_vector_t *pcm_data);
+/* The same reader for the files people have: the same header checks in the same order, but any positive sample rate
+ * and 1 .. 8 interleaved channels (byte_rate and block_align are checked against the channel count).  pcm_data
+ * receives channel `channel` (0-based), de-interleaved on the host, sample values as pk_mi355_16kpcm_read gives them;
+ * *rate and *channels (may be NULL) the header's.  A channel outside the file is PK_MI355_E_INVALID; a trailing
+ * partial sample block is dropped, as pk_16kpcm_read drops a partial sample.  Host only, needs no GPU.             */
+int pk_mi355_wave_read(const char *filename, int channel, pk_vector_t *pcm_data, int *rate, int *channels);
 
 /* Stages 1-3 of pk_process fused on the device: raw_wave -> fbank -> CMVN -> nnet ->
  * decodable (host log_prob, ready for Decoder::Decode).  An empty wave gives an empty
@@ -511,6 +548,21 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
 void pk_mi355_stream_destroy(pk_mi355_stream_t *s);
 /* PK_MI355_E_STATE if the slot is open, or closed and not yet flushed by a step.                   */
 int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot);
+/* The same for audio sampled at `rate` Hz (pk_mi355_stream_open is open_rate(16000)): pk_mi355_stream_push / _push_i16 then
+ * take samples at that rate, and every step first converts, on the device, the 16 kHz samples that became final -- output
+ * j is final once the last input its window reads has arrived; after pk_mi355_stream_close every j < floor(n P / Q) is
+ *  -- into the place pushed 16 kHz samples lie, then runs the same sequence.  Every frame's
+ * log-likelihoods equal those of the batch scorer on the whole converted wave bit for bit, whatever the chunk sizes.
+ * The rate is fixed until the slot is flushed; an unsupported rate fails with PK_MI355_E_INVALID and opens nothing.
+ * Capacity: max_step_samples keeps its meaning, 16 kHz samples between two steps; such a slot counts floor(n P / Q) minus
+ * the outputs already converted -- what a close would make final: the filter's half-width, 6 to 12 samples, more than
+ * what is final now -- so that a close never exceeds the capacity; a push that would is refused with PK_MI355_E_INVALID and consumes nothing.
+ * Memory: at the first such open the object makes a page-locked and a device buffer of 4 B x (6 max_step_samples +
+ * 8448 max_streams) for samples at their own rate; a slot keeps the at most Q + max_taps input samples the next output
+ * still reads on the host with its pushes and sends them with the next step's.                                      */
+int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate);
+/* The rate the slot was last opened at (16000 before its first opening); negative on misuse.                        */
+int pk_mi355_stream_rate(const pk_mi355_stream_t *s, int slot);
 /* Append host PCM (float sample values as pk_16kpcm_read produces them, pcm_reader.cc:189-211) to an
  * open slot; copied, the caller's buffer is free on return.  num_samples may be 0.  A push that would take
  * the samples pending for the next step beyond max_step_samples fails with PK_MI355_E_INVALID and
@@ -705,6 +757,9 @@ pk_mi355_decoder_t *pk_mi355_recognizer_decoder(pk_mi355_recognizer_t *r);
 const pk_mi355_symtab_t *pk_mi355_recognizer_symtab(const pk_mi355_recognizer_t *r);
 /* pk_process for n waves at once: set_waves, score (prob_scale 0.1), decode_batch, synchronize.                   */
 int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *waves, int n);
+/* Same, wave u sampled at rates[u] Hz (pk_mi355_resample_set_waves; rates == NULL: 16000 throughout).  Capacity and
+ * every result -- frames, word times -- are those of the converted 16 kHz audio.                                  */
+int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_t *waves, const int *rates, int n);
 /* utt->hyp of the last process: the words' strings in spoken order joined by one space, no trailing space; "" for
  * an utterance without words (also one the decoder ended with ok = 0).  Valid until the next process.  NULL on
  * misuse.                                                                                                        */
@@ -733,6 +788,8 @@ const pk_mi355_symtab_t *pk_mi355_online_recognizer_symtab(const pk_mi355_online
  * close and step through these entries, not through the owned objects: a slot closed behind the recognizer's back
  * is never reported finished.                                                                                      */
 int pk_mi355_online_recognizer_open(pk_mi355_online_recognizer_t *r, int slot);
+/* The same for audio sampled at `rate` Hz: pk_mi355_stream_open_rate for the scorer's slot.                         */
+int pk_mi355_online_recognizer_open_rate(pk_mi355_online_recognizer_t *r, int slot, int rate);
 /* As pk_mi355_stream_push / _push_i16 / _close.                                                                    */
 int pk_mi355_online_recognizer_push(pk_mi355_online_recognizer_t *r, int slot, const float *samples, int num_samples);
 int pk_mi355_online_recognizer_push_i16(pk_mi355_online_recognizer_t *r, int slot, const int16_t *samples, int num_samples);

@@ -285,6 +285,25 @@ class SymbolTable {
   pk_mi355_symtab_t *st_;
 };
 
+// Audio as people have it: a WAV file of any rate and up to 8 channels, and its conversion to
+// the 16 kHz the recognizer hears, on the GPU.
+// ReadWave: channel `channel` of the file into *samples (sample values as pk_mi355_16kpcm_read gives them) and its rate.
+inline Status ReadWave(const std::string &path, int channel, std::vector<float> *samples, int *rate) {
+  pk_vector_t v = {0, nullptr};
+  const int rc = pk_mi355_wave_read(path.c_str(), channel, &v, rate, nullptr);
+  if (rc == 0) samples->assign(v.data, v.data + v.dim);
+  free(v.data);
+  return Status::FromLast(rc);
+}
+// Resample: samples at `rate` Hz -> 16 kHz (pk_mi355_resample; 16000 is the identity)
+inline Status Resample(const std::vector<float> &wave, int rate, std::vector<float> *out) {
+  pk_vector_t in = {(int)wave.size(), const_cast<float *>(wave.data())}, v = {0, nullptr};
+  const int rc = pk_mi355_resample(&in, rate, &v);
+  if (rc == 0) out->assign(v.data, v.data + v.dim);
+  free(v.data);
+  return Status::FromLast(rc);
+}
+
 // pk_t + pk_load + pk_process (src/pocketkaldi.h, src/pocketkaldi.cc:72-248): model file and waves to text.
 class Recognizer {
  public:
@@ -305,9 +324,10 @@ class Recognizer {
     r_ = pk_mi355_recognizer_load(model_file.c_str(), precision, max_utts, max_total_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
-  // pk_process for n waves at once; out (may be null) receives one Utterance per wave
-  Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out) {
-    const int rc = pk_mi355_recognizer_process(r_, waves, n);
+  // pk_process for n waves at once; out (may be null) receives one Utterance per wave.  rates (may be null: 16000
+  // throughout): the sample rate of every wave; the others are converted on the GPU (pk_mi355_recognizer_process_rates)
+  Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out, const int *rates = nullptr) {
+    const int rc = rates ? pk_mi355_recognizer_process_rates(r_, waves, rates, n) : pk_mi355_recognizer_process(r_, waves, n);
     if (rc != 0) return Status::FromLast(rc);
     if (out) {
       out->clear();
@@ -342,6 +362,9 @@ class OnlineScorer {
   OnlineScorer &operator=(const OnlineScorer &) = delete;
 
   Status Open(int slot) { return Status::FromLast(pk_mi355_stream_open(s_, slot)); }
+  // The slot's pushes are samples at `rate` Hz (8 .. 96 kHz), converted on the GPU step by step
+  Status Open(int slot, int rate) { return Status::FromLast(pk_mi355_stream_open_rate(s_, slot, rate)); }
+  int Rate(int slot) const { return pk_mi355_stream_rate(s_, slot); }
   Status Push(int slot, const float *samples, int num_samples) {
     return Status::FromLast(pk_mi355_stream_push(s_, slot, samples, num_samples));
   }
@@ -452,6 +475,7 @@ class OnlineRecognizer {
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   Status Open(int slot) { return Status::FromLast(pk_mi355_online_recognizer_open(r_, slot)); }
+  Status Open(int slot, int rate) { return Status::FromLast(pk_mi355_online_recognizer_open_rate(r_, slot, rate)); }
   Status Push(int slot, const float *samples, int num_samples) {
     return Status::FromLast(pk_mi355_online_recognizer_push(r_, slot, samples, num_samples));
   }

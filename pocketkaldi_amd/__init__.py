@@ -29,7 +29,7 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["PkError", "lib", "lib_path", "read_wav", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
+__all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
            "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
@@ -108,6 +108,9 @@ EXPORTS = [
     "pk_mi355_online_recognizer_loglikelihood_per_frame",
     "pk_mi355_online_decoder_set_commit", "pk_mi355_online_decoder_committed", "pk_mi355_online_decoder_trace_stats",
     "pk_mi355_online_recognizer_stable",
+    "pk_mi355_resample_plan", "pk_mi355_resample_table", "pk_mi355_resample_num_output", "pk_mi355_resample",
+    "pk_mi355_resample_set_waves", "pk_mi355_wave_read", "pk_mi355_recognizer_process_rates",
+    "pk_mi355_stream_open_rate", "pk_mi355_stream_rate", "pk_mi355_online_recognizer_open_rate",
 ]
 
 
@@ -317,6 +320,17 @@ def lib():
                                                       C.POINTER(C.c_int64)]
     L.pk_mi355_online_recognizer_stable.restype = C.c_char_p
     L.pk_mi355_online_recognizer_stable.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_resample_plan.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_resample_table.argtypes = [C.c_int, i32p, i32p, f32p]
+    L.pk_mi355_resample_num_output.restype = C.c_int64
+    L.pk_mi355_resample_num_output.argtypes = [C.c_int, C.c_int64]
+    L.pk_mi355_resample.argtypes = [C.POINTER(pk_vector_t), C.c_int, C.POINTER(pk_vector_t)]
+    L.pk_mi355_resample_set_waves.argtypes = [C.c_void_p, C.POINTER(pk_vector_t), C.POINTER(C.c_int), C.c_int]
+    L.pk_mi355_wave_read.argtypes = [C.c_char_p, C.c_int, C.POINTER(pk_vector_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_recognizer_process_rates.argtypes = [C.c_void_p, C.POINTER(pk_vector_t), C.POINTER(C.c_int), C.c_int]
+    L.pk_mi355_stream_open_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pk_mi355_stream_rate.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_open_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -372,6 +386,57 @@ def read_wav(path):
     out = np.ctypeslib.as_array(v.data, shape=(max(v.dim, 1),))[:v.dim].copy()
     _libc.free(v.data)
     return out
+
+
+def _take_vector(v):
+    out = np.ctypeslib.as_array(v.data, shape=(max(v.dim, 1),))[:v.dim].copy()
+    _libc.free(v.data)
+    return out
+
+
+def read_wave(path, channel=0):
+    """pk_mi355_wave_read: any sample rate, 1 .. 8 channels -> (float32 samples of `channel`, unscaled; the rate)."""
+    v, rate = pk_vector_t(0, None), C.c_int()
+    _check_code(lib().pk_mi355_wave_read(os.fspath(path).encode(), int(channel), C.byref(v), C.byref(rate), None))
+    return _take_vector(v), rate.value
+
+
+ResampleTable = collections.namedtuple("ResampleTable", "Q P max_taps first count weights")
+
+
+def resample_table(rate):
+    """The polyphase table of `rate` -> 16000 (pk_mi355_resample_table; host only): Q input samples per unit, P phases,
+    first[P], count[P] and weights[P][max_taps] (zero-padded).  PkCodeError (-1) names an unsupported rate."""
+    q, p, taps = C.c_int(), C.c_int(), C.c_int()
+    _check_code(lib().pk_mi355_resample_plan(int(rate), C.byref(q), C.byref(p), C.byref(taps)))
+    first, count = np.zeros(p.value, np.int32), np.zeros(p.value, np.int32)
+    weights = np.zeros((p.value, taps.value), np.float32)
+    i32p = C.POINTER(C.c_int32)
+    _check_code(lib().pk_mi355_resample_table(int(rate), first.ctypes.data_as(i32p), count.ctypes.data_as(i32p), _fp(weights)))
+    return ResampleTable(q.value, p.value, taps.value, first, count, weights)
+
+
+def resample_num_output(rate, num_samples):
+    """floor(num_samples * P / Q): the 16 kHz samples `num_samples` samples at `rate` give."""
+    return _check_code(lib().pk_mi355_resample_num_output(int(rate), int(num_samples)))
+
+
+def resample(wave, rate):
+    """One wave at `rate` Hz -> float32 samples at 16 kHz, converted on the GPU (pk_mi355_resample)."""
+    w = _f32(wave).ravel()
+    v, out = pk_vector_t(w.shape[0], _fp(w) if w.size else None), pk_vector_t(0, None)
+    _check_code(lib().pk_mi355_resample(C.byref(v), int(rate), C.byref(out)))
+    return _take_vector(out)
+
+
+def _rates_array(rates, n):
+    """rates (None: 16000 throughout) -> a C int array, or None where every rate is 16000."""
+    if rates is None:
+        return None
+    rates = [int(r) for r in rates]
+    if len(rates) != n:
+        raise PkCodeError(-1, "%d rates for %d waves" % (len(rates), n))
+    return (C.c_int * max(n, 1))(*rates)
 
 
 def process_acoustic(am, global_stats, wave, prob_scale=0.1, verbose=False):
@@ -648,12 +713,16 @@ class BatchScorer:
         except Exception:
             pass
 
-    def set_waves(self, waves):
+    def set_waves(self, waves, rates=None):
+        """rates: the sample rate of every wave (None: 16000); the others are converted on the GPU on the way in."""
         waves = [_f32(w) for w in waves]
         arr = (pk_vector_t * max(len(waves), 1))()
         for i, w in enumerate(waves):
             arr[i].dim, arr[i].data = w.shape[0], _fp(w)
-        _check(lib().pk_mi355_batch_set_waves(self._h, arr, len(waves)))
+        if rates is None:
+            _check(lib().pk_mi355_batch_set_waves(self._h, arr, len(waves)))
+        else:
+            _check_code(lib().pk_mi355_resample_set_waves(self._h, arr, _rates_array(rates, len(waves)), len(waves)))
 
     def set_waves_i16(self, waves):
         waves = [np.ascontiguousarray(w, dtype=np.int16) for w in waves]
@@ -764,8 +833,15 @@ class OnlineScorer:
         except Exception:
             pass
 
-    def open(self, slot):
-        _check_code(lib().pk_mi355_stream_open(self._h, int(slot)))
+    def open(self, slot, rate=16000):
+        """rate: the sample rate of what will be pushed to the slot; converted to 16 kHz on the GPU step by step."""
+        if rate == 16000:
+            _check_code(lib().pk_mi355_stream_open(self._h, int(slot)))
+        else:
+            _check_code(lib().pk_mi355_stream_open_rate(self._h, int(slot), int(rate)))
+
+    def rate(self, slot):
+        return _check_code(lib().pk_mi355_stream_rate(self._h, int(slot)))
 
     def push(self, slot, samples):
         """float sample values (as read_wav gives them); an int16 array goes through push_i16."""
@@ -1172,11 +1248,14 @@ class Recognizer:
         except Exception:
             pass
 
-    def _process_call(self, waves):
+    def _process_call(self, waves, rates=None):
         arr = (pk_vector_t * max(len(waves), 1))()
         for i, w in enumerate(waves):
             arr[i].dim, arr[i].data = w.shape[0], (_fp(w) if w.size else None)
-        _check_code(lib().pk_mi355_recognizer_process(self._h, arr, len(waves)))
+        if rates is None:
+            _check_code(lib().pk_mi355_recognizer_process(self._h, arr, len(waves)))
+        else:
+            _check_code(lib().pk_mi355_recognizer_process_rates(self._h, arr, _rates_array(rates, len(waves)), len(waves)))
         out = []
         for u in range(len(waves)):
             words, weight, ok = self.decoder.result(u)
@@ -1184,22 +1263,32 @@ class Recognizer:
                               lib().pk_mi355_recognizer_loglikelihood_per_frame(self._h, u), self.decoder.word_segments(u)))
         return out
 
-    def process(self, waves):
-        """pk_process for every wave (float sample values as read_wav gives them).  A list that does not fit max_utts /
-        max_total_samples is split into as many calls as it needs; a single wave that cannot fit is refused."""
+    def process(self, waves, rates=None):
+        """pk_process for every wave (float sample values as read_wav gives them; rates: the sample rate of every wave,
+        None for 16000 -- the others are converted on the GPU).  A list that does not fit max_utts / max_total_samples
+        (counted at 16 kHz) is split into as many calls as it needs; a single wave that cannot fit is refused."""
         waves = [_f32(w).ravel() for w in waves]
-        for i, w in enumerate(waves):
-            if w.shape[0] > self.max_total_samples:
-                raise PkCodeError(-1, "wave %d has %d samples, the recognizer holds %d" % (i, w.shape[0], self.max_total_samples))
+        if rates is None:
+            sizes = [w.shape[0] for w in waves]
+        else:
+            _rates_array(rates, len(waves))
+            sizes = [resample_num_output(r, w.shape[0]) for w, r in zip(waves, rates)]
+        for i, n in enumerate(sizes):
+            if n > self.max_total_samples:
+                raise PkCodeError(-1, "wave %d has %d samples, the recognizer holds %d" % (i, n, self.max_total_samples))
         out, call, samples = [], [], 0
-        for w in waves:
-            if call and (len(call) == self.max_utts or samples + w.shape[0] > self.max_total_samples):
-                out += self._process_call(call)
+
+        def flush():
+            first = len(out)
+            return self._process_call(call, None if rates is None else rates[first:first + len(call)])
+        for w, n in zip(waves, sizes):
+            if call and (len(call) == self.max_utts or samples + n > self.max_total_samples):
+                out += flush()
                 call, samples = [], 0
             call.append(w)
-            samples += w.shape[0]
+            samples += n
         if call:
-            out += self._process_call(call)
+            out += flush()
         return out
 
 
@@ -1237,8 +1326,12 @@ class OnlineRecognizer:
         except Exception:
             pass
 
-    def open(self, slot):
-        _check_code(lib().pk_mi355_online_recognizer_open(self._h, int(slot)))
+    def open(self, slot, rate=16000):
+        """rate: the sample rate of what will be pushed to the slot."""
+        if rate == 16000:
+            _check_code(lib().pk_mi355_online_recognizer_open(self._h, int(slot)))
+        else:
+            _check_code(lib().pk_mi355_online_recognizer_open_rate(self._h, int(slot), int(rate)))
 
     def push(self, slot, samples):
         """float sample values (as read_wav gives them); an int16 array goes through push_i16."""

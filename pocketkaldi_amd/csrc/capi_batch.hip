@@ -8,6 +8,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "pk_resample.h"
 #include "pk_score.h"
 
 using namespace pkmi;
@@ -150,6 +151,11 @@ struct pk_mi355_batch {
   int16_t *d_wave_i16 = nullptr;    // owned int16 buffer
   const float *wave_f32 = nullptr;  // what the kernels read (owned or external)
   const int16_t *wave_i16 = nullptr;
+  // pk_mi355_resample_set_waves: the utterances that are not at 16 kHz wait here at their own rate, page-locked and
+  // on the device (both made and grown on demand), and are converted straight into d_wave
+  Resampler resampler;
+  float *h_native = nullptr, *d_native = nullptr;
+  int64_t native_cap = 0;
   // per-utterance placement
   int num_utts = 0;
   int max_T = 0;
@@ -385,6 +391,9 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2);
+  b->resampler.Free();
+  if (b->h_native) hipHostFree(b->h_native);
+  hipFree(b->d_native);
   hipFree(b->d_wave_off); hipFree(b->d_raw_base); hipFree(b->d_pad_base); hipFree(b->d_T); hipFree(b->d_shift4);
   if (b->arena) RetireArena(b->arena);   // released now, or by the last outstanding view of the last fetch_all
   FreeScorerCore(&b->core);
@@ -404,6 +413,59 @@ int pk_mi355_batch_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, int 
       HIP_TRY(hipMemcpyAsync(b->d_wave + off, waves[u].data, sizeof(float) * ns[u], hipMemcpyHostToDevice, b->core.stream));
     off += ns[u];
   }
+  b->wave_f32 = b->d_wave;
+  b->wave_i16 = nullptr;
+  return SetLayout(b, ns.data(), num_utts);
+}
+
+int pk_mi355_resample_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, const int *rates, int num_utts) {
+  if (!b || !waves) return Fail(PK_MI355_E_INVALID, "null argument");
+  bool native = false;
+  for (int u = 0; rates && u < num_utts; ++u) native = native || rates[u] != kSampleRate;
+  if (!native) return pk_mi355_batch_set_waves(b, waves, num_utts);      // 16 kHz throughout: today's call, launch for launch
+  if (num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+  if (int rc = UseDevice(b->core.device)) return rc;
+  // every utterance's length at 16 kHz and the native samples to stage, checked before anything is copied
+  std::vector<int> ns(num_utts);
+  std::vector<const DeviceResampleTable *> tab(num_utts, nullptr);
+  int64_t total_native = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    if (waves[u].dim < 0) return Fail(PK_MI355_E_INVALID, "negative sample count");
+    if (rates[u] == kSampleRate) { ns[u] = waves[u].dim; continue; }
+    if (int rc = b->resampler.Table(rates[u], &tab[u])) return rc;
+    const int64_t n_out = ResampleNumOutput(tab[u]->host, waves[u].dim);
+    if (n_out > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples");
+    ns[u] = (int)n_out;
+    total_native += waves[u].dim;
+  }
+  if (TotalSamples(ns.data(), num_utts) > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples");
+  if (!b->d_wave) HIP_TRY(hipMalloc(&b->d_wave, sizeof(float) * b->max_samples));
+  HIP_TRY(hipStreamSynchronize(b->core.stream));       // the previous call has left the staging buffers
+  if (total_native > b->native_cap) {
+    const int64_t cap = std::max<int64_t>(total_native, 2 * b->native_cap);
+    if (b->h_native) hipHostFree(b->h_native);
+    hipFree(b->d_native);
+    b->h_native = nullptr; b->d_native = nullptr; b->native_cap = 0;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_native), sizeof(float) * cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&b->d_native, sizeof(float) * cap));
+    b->native_cap = cap;
+  }
+  std::vector<ResampleItem> items;
+  int64_t off = 0, noff = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    const int n = waves[u].dim;
+    if (!tab[u]) {
+      if (n > 0) HIP_TRY(hipMemcpyAsync(b->d_wave + off, waves[u].data, sizeof(float) * n, hipMemcpyHostToDevice, b->core.stream));
+    } else {
+      if (n > 0) memcpy(b->h_native + noff, waves[u].data, sizeof(float) * n);
+      if (ns[u] > 0) items.push_back(Resampler::Item(*tab[u], b->d_native + noff, 0, n, 0, ns[u], b->d_wave + off));
+      noff += n;
+    }
+    off += ns[u];
+  }
+  if (total_native > 0)
+    HIP_TRY(hipMemcpyAsync(b->d_native, b->h_native, sizeof(float) * total_native, hipMemcpyHostToDevice, b->core.stream));
+  if (int rc = b->resampler.Run(items, b->core.stream)) return rc;
   b->wave_f32 = b->d_wave;
   b->wave_i16 = nullptr;
   return SetLayout(b, ns.data(), num_utts);

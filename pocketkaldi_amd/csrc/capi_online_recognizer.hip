@@ -117,11 +117,15 @@ const pk_mi355_symtab_t *pk_mi355_online_recognizer_symtab(const pk_mi355_online
 }
 
 int pk_mi355_online_recognizer_open(pk_mi355_online_recognizer_t *r, int slot) {
+  return pk_mi355_online_recognizer_open_rate(r, slot, pkmi::kSampleRate);
+}
+
+int pk_mi355_online_recognizer_open_rate(pk_mi355_online_recognizer_t *r, int slot, int rate) {
   int rc = CheckSlot(r, slot);
   if (rc) return rc;
   // (asked first: a scorer slot, once open, could not be taken back if the decoder then refused its own)
   if (OnlineDecoderSlotOpen(r->decoder, slot)) return Fail(PK_MI355_E_STATE, "online recognizer: slot %d is open in the decoder", slot);
-  if ((rc = pk_mi355_stream_open(r->stream, slot)) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
+  if ((rc = pk_mi355_stream_open_rate(r->stream, slot, rate)) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
   r->live[slot] = 1; r->closed[slot] = 0; r->finished[slot] = 0;
   r->partial[slot].clear(); r->hyp[slot].clear(); r->stable[slot].clear();
   r->stable_words[slot] = 0;

@@ -101,11 +101,15 @@ const pk_mi355_symtab_t *pk_mi355_recognizer_symtab(const pk_mi355_recognizer_t 
 }
 
 int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *waves, int n) {
+  return pk_mi355_recognizer_process_rates(r, waves, nullptr, n);
+}
+
+int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_t *waves, const int *rates, int n) {
   if (!r || n < 0 || (n > 0 && !waves)) return Fail(PK_MI355_E_INVALID, "bad process arguments");
   r->have = false;
   pk_vector_t none = {0, nullptr};
   int rc;
-  if ((rc = pk_mi355_batch_set_waves(r->batch, n ? waves : &none, n)) || (rc = pk_mi355_batch_score(r->batch, 0.1f, 0)) ||
+  if ((rc = pk_mi355_resample_set_waves(r->batch, n ? waves : &none, rates, n)) || (rc = pk_mi355_batch_score(r->batch, 0.1f, 0)) ||
       (rc = pk_mi355_decoder_decode_batch(r->decoder, r->batch, 1)))
     return rc;
   r->hyp.assign(n, std::string());

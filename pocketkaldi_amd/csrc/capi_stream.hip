@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "pk_resample.h"
 #include "pk_score.h"
 
 using namespace pkmi;
@@ -26,7 +27,19 @@ struct Slot {
   int last_first = 0, last_count = 0;
   int64_t last_out = 0;
   bool last_flushed = false;     // the last step was the slot's final one
+  // A slot opened at another rate than 16 kHz (tab != null): its pushes are samples at that rate and `pending` stays
+  // empty.  `native` holds the input samples from index nat_x0 on -- the carry (what the next output's window still
+  // reads, at most Q + max_taps samples) and what was pushed since the last step.  n_in inputs received, n_prod
+  // outputs handed to the front-end; `reserve` = floor(n_in P / Q) - n_prod is what the slot counts against the step
+  // capacity: the outputs a close would make final.
+  int rate = kSampleRate;
+  const DeviceResampleTable *tab = nullptr;
+  std::vector<float> native;
+  int64_t nat_x0 = 0, n_in = 0, n_prod = 0, reserve = 0;
 };
+
+// the most input samples a native-rate slot carries from one step to the next (Q + max_taps <= 8190 + 74)
+constexpr int64_t kNativeCarryCap = 8448;
 
 }  // namespace
 
@@ -49,6 +62,11 @@ struct pk_mi355_stream {
   char *h_meta = nullptr, *d_meta = nullptr;          // records, UttLayout arrays, column shifts
   size_t meta_bytes = 0;
   hipEvent_t ev_staged = nullptr;     // the last step's uploads have left the page-locked buffers
+  // native-rate slots (made at the first pk_mi355_stream_open_rate other than 16000): the tables of the rates met, and
+  // the step's native samples, page-locked -> HBM, which ResampleKernel converts into d_upload
+  Resampler resampler;
+  float *h_native = nullptr, *d_native = nullptr;
+  int64_t native_cap = 0;
   bool staged = false;
 };
 
@@ -118,6 +136,9 @@ void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
   hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist);
   hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta);
+  s->resampler.Free();
+  if (s->h_native) hipHostFree(s->h_native);
+  hipFree(s->d_native);
   if (s->h_upload) hipHostFree(s->h_upload);
   if (s->h_meta) hipHostFree(s->h_meta);
   if (s->ev_staged) hipEventDestroy(s->ev_staged);
@@ -125,14 +146,37 @@ void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   delete s;
 }
 
-int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot) {
+int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot) { return pk_mi355_stream_open_rate(s, slot, kSampleRate); }
+
+int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
   if (int rc = SlotIndex(s, slot)) return rc;
   Slot &z = s->slots[slot];
   if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
+  const DeviceResampleTable *tab = nullptr;
+  if (rate != kSampleRate) {
+    if (int rc = UseDevice(s->core.device)) return rc;
+    if (int rc = s->resampler.Table(rate, &tab)) return rc;
+    if (!s->h_native) {
+      const int64_t cap = 6 * s->max_step_samples + (int64_t)s->max_streams * kNativeCarryCap;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_native), sizeof(float) * cap, hipHostMallocDefault));
+      HIP_TRY(hipMalloc(&s->d_native, sizeof(float) * cap));
+      s->native_cap = cap;
+    }
+  }
   z.state = kOpen;
   z.n = z.a = z.tail_len = 0;
   z.pending.clear();
+  z.rate = rate; z.tab = tab;
+  z.native.clear();
+  z.nat_x0 = z.n_in = z.n_prod = 0;
+  s->pending_total -= z.reserve;      // (zero unless the slot's last opening ended without its flush)
+  z.reserve = 0;
   return 0;
+}
+
+int pk_mi355_stream_rate(const pk_mi355_stream_t *s, int slot) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  return s->slots[slot].rate;
 }
 
 int pk_mi355_stream_push(pk_mi355_stream_t *s, int slot, const float *samples, int num_samples) {
@@ -140,6 +184,17 @@ int pk_mi355_stream_push(pk_mi355_stream_t *s, int slot, const float *samples, i
   Slot &z = s->slots[slot];
   if (z.state != kOpen) return Fail(PK_MI355_E_STATE, "slot %d is not open", slot);
   if (num_samples < 0 || (num_samples > 0 && !samples)) return Fail(PK_MI355_E_INVALID, "bad samples");
+  if (z.tab) {                         // samples at the slot's rate: what counts is the 16 kHz samples they become
+    const int64_t reserve = ResampleNumOutput(z.tab->host, z.n_in + num_samples) - z.n_prod;
+    if (s->pending_total + reserve - z.reserve > s->max_step_samples)
+      return Fail(PK_MI355_E_INVALID, "push of %d samples at %d Hz exceeds the step capacity (%lld pending of %lld at 16 kHz)", num_samples,
+                  z.rate, (long long)s->pending_total, (long long)s->max_step_samples);
+    z.native.insert(z.native.end(), samples, samples + num_samples);
+    z.n_in += num_samples;
+    s->pending_total += reserve - z.reserve;
+    z.reserve = reserve;
+    return 0;
+  }
   if (s->pending_total + num_samples > s->max_step_samples)
     return Fail(PK_MI355_E_INVALID, "push of %d samples exceeds the step capacity (%lld pending of %lld)", num_samples,
                 (long long)s->pending_total, (long long)s->max_step_samples);
@@ -181,14 +236,16 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   char *lay_base = s->h_meta + RoundUp(sizeof(StreamRec) * s->max_streams, 256);
   const size_t shift4_at = s->meta_bytes - sizeof(int32_t) * Shift4Cap(c.max_cols);
   std::vector<int> who, flushed;                      // slots taking part; closed slots with nothing left
-  int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0;
+  int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
   int max_m = 0;
   std::vector<ShiftSpan> spans;                       // (end row, column shift) per slot with rows
   for (int slot = 0; slot < s->max_streams; ++slot) {
     const Slot &z = s->slots[slot];
     if (z.state == kFree) continue;
     const bool closed = z.state == kClosed;
-    const int new_len = (int)z.pending.size();
+    // a native-rate slot's new samples are the outputs that became final (all of them once it is closed)
+    const int new_len = !z.tab ? (int)z.pending.size()
+                               : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
     const int seg = z.tail_len + new_len;
     const int m = pk_mi355_num_frames(seg);
     const int n = z.n + m;
@@ -214,10 +271,12 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       spans.push_back({out, shift});
     }
     woff += seg; upl += new_len; raw += m;
+    if (z.tab && new_len) native_total += (int64_t)z.native.size();
     max_m = std::max(max_m, m);
     who.push_back(slot);
   }
-  if (woff > s->wave_cap || raw > c.max_frames || RoundUp(out, kTileF16) > c.max_cols || col > c.max_cols)
+  if (woff > s->wave_cap || upl > s->max_step_samples || native_total > s->native_cap || raw > c.max_frames ||
+      RoundUp(out, kTileF16) > c.max_cols || col > c.max_cols)
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
   // the column shift of every group of four rows (the groups past the last row keep the last shift)
   const int64_t total_rows = out;
@@ -225,10 +284,27 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   if (total_rows > 0 && !ExpandShift4(spans, total_rows, c.zero_span, reinterpret_cast<int32_t *>(s->h_meta + shift4_at), &bad))
     return Fail(PK_MI355_E_INVALID, "internal: column shift %d outside [0, %lld]", bad, (long long)(c.zero_span - kTile));
   // the plan holds: consume every pushed sample, advance the slots
+  std::vector<ResampleItem> items;
+  int64_t native_at = 0;
   for (size_t k = 0; k < who.size(); ++k) {
     const StreamRec &r = recs[k];
     Slot &z = s->slots[r.slot];
-    if (r.new_len) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * r.new_len);
+    if (z.tab && r.new_len) {
+      // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
+      const ResampleTable &t = z.tab->host;
+      memcpy(s->h_native + native_at, z.native.data(), sizeof(float) * z.native.size());
+      items.push_back(Resampler::Item(*z.tab, s->d_native + native_at, z.nat_x0, (int64_t)z.native.size(), z.n_prod, z.n_prod + r.new_len,
+                                      s->d_upload + r.new_off));
+      native_at += (int64_t)z.native.size();
+      z.n_prod += r.new_len;
+      // the carry: nothing before the first sample the next output's window can read is read again
+      const int64_t keep = std::min(z.n_in, std::max(z.nat_x0, z.n_prod / t.P * t.Q + t.min_first));
+      z.native.erase(z.native.begin(), z.native.begin() + (keep - z.nat_x0));
+      z.nat_x0 = keep;
+      z.reserve = ResampleNumOutput(t, z.n_in) - z.n_prod;
+    } else if (r.new_len) {
+      memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * r.new_len);
+    }
     z.pending.clear();
     z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
     z.tail_par ^= 1;
@@ -239,6 +315,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   }
   for (int slot : flushed) { s->slots[slot].state = kFree; s->slots[slot].last_flushed = true; }
   s->pending_total = 0;
+  for (Slot &z : s->slots) {
+    if (z.state == kFree) z.reserve = 0;
+    s->pending_total += z.reserve;     // native-rate slots: the outputs that are not final yet stay counted
+  }
   {
     int64_t o = 0;
     for (size_t k = 0; k < who.size(); ++k) {
@@ -256,6 +336,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   for (int k = 0; k < K; ++k) { h_woff[k] = recs[k].woff; h_rawb[k] = recs[k].raw_base; h_T[k] = recs[k].m; }
   // ---- uploads (one for the samples, one for the plan) and the launches, all on the stream
   if (upl) HIP_TRY(hipMemcpyAsync(s->d_upload, s->h_upload, sizeof(float) * upl, hipMemcpyHostToDevice, c.stream));
+  if (native_at) {                     // the native-rate slots' new 16 kHz samples, written over their part of d_upload
+    HIP_TRY(hipMemcpyAsync(s->d_native, s->h_native, sizeof(float) * native_at, hipMemcpyHostToDevice, c.stream));
+    if ((rc = s->resampler.Run(items, c.stream))) return rc;
+  }
   HIP_TRY(hipMemcpyAsync(s->d_meta, s->h_meta, s->meta_bytes, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipEventRecord(s->ev_staged, c.stream));
   s->staged = true;

@@ -167,7 +167,11 @@ int ReadModelConfig(const char *config_path, ModelConfig *out) {
 
 // ------------------------------------------------------------------ WAV
 
-int ReadWav16k(const char *filename, std::vector<float> *samples) {
+namespace {
+
+// One reader for both entries.  strict: pk_16kpcm_read's refusals (mono, 16 kHz) in its words; otherwise any positive
+// rate and 1 .. 8 channels, of which `channel` is returned.  Every other check is the same, in the same order.
+int ReadWaveFile(const char *filename, bool strict, int channel, std::vector<float> *samples, int *rate_out, int *channels_out) {
   FileBuf f;
   int rc = f.Open(filename);
   if (rc) return rc;
@@ -182,26 +186,45 @@ int ReadWav16k(const char *filename, std::vector<float> *samples) {
   if (memcmp(b + 12, "fmt ", 4)) return Fail(PK_MI355_E_IO, "subchunk1 == 'fmt ' expected: %s", filename);
   if (i32(16) != 16) return Fail(PK_MI355_E_IO, "subchunk1_size == 16 expected, but %d found: %s", i32(16), filename);
   if (i16(20) != 1) return Fail(PK_MI355_E_IO, "audio_format == 1 (PCM) expected, but %d found: %s", i16(20), filename);
-  if (i16(22) != 1) return Fail(PK_MI355_E_IO, "num_channels == 1 (mono) expected, but %d found: %s", i16(22), filename);
+  const int channels = i16(22);
+  if (strict && channels != 1) return Fail(PK_MI355_E_IO, "num_channels == 1 (mono) expected, but %d found: %s", channels, filename);
+  if (channels < 1 || channels > 8) return Fail(PK_MI355_E_IO, "num_channels == 1 .. 8 expected, but %d found: %s", channels, filename);
   const int rate = i32(24);
-  if (rate != 16000) return Fail(PK_MI355_E_IO, "sample_rate == 16000 expected, but %d found: %s", rate, filename);
+  if (strict && rate != 16000) return Fail(PK_MI355_E_IO, "sample_rate == 16000 expected, but %d found: %s", rate, filename);
+  if (rate <= 0) return Fail(PK_MI355_E_IO, "sample_rate > 0 expected, but %d found: %s", rate, filename);
   const int byte_rate = i32(28), align = i16(32), bits = i16(34);
   if (bits != 8 && bits != 16 && bits != 32)
     return Fail(PK_MI355_E_IO, "bits_per_sample == 8, 16 or 32 expected, but %d found: %s", bits, filename);
-  if (byte_rate != rate * bits / 8) return Fail(PK_MI355_E_IO, "bytes_rate == %d expected, but %d found: %s", rate * bits / 8, byte_rate, filename);
-  if (align != bits / 8) return Fail(PK_MI355_E_IO, "block_align == %d expected, but %d found: %s", bits / 8, align, filename);
+  const int64_t want_rate = (int64_t)rate * channels * bits / 8;
+  if (byte_rate != want_rate) return Fail(PK_MI355_E_IO, "bytes_rate == %lld expected, but %d found: %s", (long long)want_rate, byte_rate, filename);
+  if (align != channels * bits / 8) return Fail(PK_MI355_E_IO, "block_align == %d expected, but %d found: %s", channels * bits / 8, align, filename);
   if (memcmp(b + 36, "data", 4)) return Fail(PK_MI355_E_IO, "subchunk2 == 'data' expected: %s", filename);
   if (i32(40) != size - 44) return Fail(PK_MI355_E_IO, "subchunk2_size == %ld expected, but %d found: %s", size - 44, i32(40), filename);
-  const int n = (int)((size - 44) / (bits / 8));
+  if (channel < 0 || channel >= channels)
+    return Fail(PK_MI355_E_INVALID, "channel %d asked of a file with %d: %s", channel, channels, filename);
+  const int width = bits / 8;
+  const int n = (int)((size - 44) / align);              // whole sample blocks (a trailing partial block is dropped)
   samples->resize(n);
-  const unsigned char *p = b + 44;
-  for (int i = 0; i < n; ++i) {
+  const unsigned char *p = b + 44 + channel * width;     // de-interleave: one block of `align` bytes per sample time
+  for (int i = 0; i < n; ++i, p += align) {
     float &s = (*samples)[i];
-    if (bits == 8) { s = (float)(int8_t)p[0]; p += 1; }
-    else if (bits == 16) { int16_t v; memcpy(&v, p, 2); s = (float)v; p += 2; }
-    else { int32_t v; memcpy(&v, p, 4); s = (float)v; p += 4; }
+    if (bits == 8) { s = (float)(int8_t)p[0]; }
+    else if (bits == 16) { int16_t v; memcpy(&v, p, 2); s = (float)v; }
+    else { int32_t v; memcpy(&v, p, 4); s = (float)v; }
   }
+  if (rate_out) *rate_out = rate;
+  if (channels_out) *channels_out = channels;
   return 0;
+}
+
+}  // namespace
+
+int ReadWav16k(const char *filename, std::vector<float> *samples) {
+  return ReadWaveFile(filename, true, 0, samples, nullptr, nullptr);
+}
+
+int ReadWave(const char *filename, int channel, std::vector<float> *samples, int *rate, int *channels) {
+  return ReadWaveFile(filename, false, channel, samples, rate, channels);
 }
 
 // ------------------------------------------------------------------ graph
@@ -411,6 +434,20 @@ int pk_mi355_16kpcm_read(const char *filename, pk_vector_t *pcm_data) {
   if (!filename || !pcm_data) return Fail(PK_MI355_E_INVALID, "null argument");
   std::vector<float> samples;
   int rc = ReadWav16k(filename, &samples);
+  if (rc) return rc;
+  const size_t n = samples.size();
+  float *s = static_cast<float *>(realloc(pcm_data->data, sizeof(float) * (n > 0 ? n : 1)));
+  if (!s) return Fail(PK_MI355_E_INVALID, "out of host memory");
+  if (n) memcpy(s, samples.data(), sizeof(float) * n);
+  pcm_data->data = s;
+  pcm_data->dim = (int)n;
+  return 0;
+}
+
+int pk_mi355_wave_read(const char *filename, int channel, pk_vector_t *pcm_data, int *rate, int *channels) {
+  if (!filename || !pcm_data) return Fail(PK_MI355_E_INVALID, "null argument");
+  std::vector<float> samples;
+  int rc = ReadWave(filename, channel, &samples, rate, channels);
   if (rc) return rc;
   const size_t n = samples.size();
   float *s = static_cast<float *>(realloc(pcm_data->data, sizeof(float) * (n > 0 ? n : 1)));

@@ -107,6 +107,10 @@ int ReadModelConfig(const char *config_path, ModelConfig *out);
 // pcm_reader.cc:45-220: strict 44-byte-header RIFF/WAVE PCM, mono, 16 kHz, 8/16/32-bit,
 // sample values kept unscaled as float.
 int ReadWav16k(const char *filename, std::vector<float> *samples);
+// The same header checks for any positive rate and 1 .. 8 interleaved channels (byte_rate and block_align against the
+// channel count): channel `channel` of the file, de-interleaved, sample values as ReadWav16k gives them.  A channel
+// outside the file is PK_MI355_E_INVALID; rate / channels (may be null) receive the header's.
+int ReadWave(const char *filename, int channel, std::vector<float> *samples, int *rate, int *channels);
 
 }  // namespace pkhost
 

@@ -6,6 +6,8 @@
 //   capi_batch.hip       (pk_score.h) the scorer core, the batched device-resident scorer over it, result arenas and views
 //   capi_stream.hip      (pk_score.h) the online scorer over the same core
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
+//   capi_resample.hip    (pk_resample.h) a rate's polyphase table on the device, the checked plan upload and launch of
+//                        ResampleKernel (resample.hip) that the batch and the online scorer convert through, pk_mi355_resample
 //   capi_collective.hip  the one collective: weight-blob broadcast over the caller's RCCL communicator
 //   capi_recognizer.hip  pk_load + pk_process as one object over the entries of the others
 //   capi_online_recognizer.hip  pk_load + a live pk_process: the online scorer and the online decoder as one object

@@ -1,8 +1,10 @@
-// pk_tables.cc -- host construction of the front-end constant tables.
+// pk_tables.cc -- host construction of the front-end constant tables and of the resampler's polyphase table.
 // Compile: g++ -O2 -ffp-contract=off (no -march): float expressions must round
-// exactly where the reference's do.  See pk_tables.h for what each table is.
+// exactly where the reference's do.  See pk_tables.h / pk_resample.h for what each table is.
 #include "pk_tables.h"
+#include "pk_files.h"
 #include "pk_logf.h"
+#include "pk_resample.h"
 
 #include <math.h>
 #include <string.h>
@@ -199,4 +201,112 @@ void BuildCmvnTables(float global_count_f, CmvnTables *t) {
   }
 }
 
+// ------------------------------------------------------------------ resampler (pk_resample.h)
+
+int BuildResampleTable(int rate, ResampleTable *t) {
+  if (rate < kResampleMinRate || rate > kResampleMaxRate) return -1;
+  if (rate == kResampleOutRate) {                      // the identity (no filter: callers copy)
+    t->rate = rate; t->Q = t->P = t->max_taps = 1;
+    t->min_first = 0; t->max_end = 1;
+    t->first.assign(1, 0); t->count.assign(1, 1); t->weights.assign(1, 1.0f);
+    return 0;
+  }
+  const int fi = rate, fo = kResampleOutRate;
+  int a = fi, b = fo;
+  while (b) { const int r = a % b; a = b; b = r; }
+  const int Q = fi / a, P = fo / a;
+  if ((int64_t)P * 12 > kResampleMaxEntries) return -1;   // (a window of 2 w fi >= 12.1 samples holds at least 12 taps)
+  const double fc = 0.99 * 0.5 * std::min(fi, fo);
+  const double Z = 6.0;
+  const double w = Z / (2 * fc);
+  std::vector<int32_t> first(P), count(P);
+  int max_taps = 0;
+  for (int p = 0; p < P; ++p) {
+    const double tau = (double)p / fo;
+    // the taps: the integers i with |i / fi - tau| < w (strict); scanned over a range that certainly holds them
+    const int lo = (int)floor((tau - w) * fi) - 2, hi = (int)ceil((tau + w) * fi) + 2;
+    int f = 0, c = 0;
+    for (int i = lo; i <= hi; ++i)
+      if (fabs((double)i / fi - tau) < w) {
+        if (c == 0) f = i;
+        ++c;
+      }
+    first[p] = f;
+    count[p] = c;
+    max_taps = std::max(max_taps, c);
+  }
+  if ((int64_t)P * max_taps > kResampleMaxEntries) return -1;
+  t->rate = rate; t->Q = Q; t->P = P; t->max_taps = max_taps;
+  t->first.swap(first);
+  t->count.swap(count);
+  t->weights.assign((size_t)P * max_taps, 0.0f);
+  t->min_first = t->first[0];
+  t->max_end = t->first[0] + t->count[0];
+  for (int p = 0; p < P; ++p) {
+    const double tau = (double)p / fo;
+    t->min_first = std::min(t->min_first, t->first[p]);
+    t->max_end = std::max(t->max_end, t->first[p] + t->count[p]);
+    for (int k = 0; k < t->count[p]; ++k) {
+      const double d = (double)(t->first[p] + k) / fi - tau;
+      const double x = 2 * fc * d;
+      const double sinc = x == 0 ? 1.0 : sin(M_PI * x) / (M_PI * x);
+      const double window = 0.5 * (1 + cos(2 * M_PI * fc * d / Z));
+      t->weights[(size_t)p * max_taps + k] = (float)(2 * fc * sinc * window / fi);   // double throughout, one rounding
+    }
+  }
+  return 0;
+}
+
+int64_t ResampleNumFinal(const ResampleTable &t, int64_t n) {
+  if (n <= 0) return 0;
+  // every window of a unit below u0 ends below u0 Q + max_end - Q <= n: the search starts there
+  int64_t j = (n > t.max_end ? (n - t.max_end) / t.Q : 0) * t.P;
+  for (;; ++j) {
+    const int64_t u = j / t.P;
+    const int p = (int)(j - u * t.P);
+    if (t.first[p] + u * t.Q + t.count[p] - 1 >= n) break;
+  }
+  return std::min(j, ResampleNumOutput(t, n));
+}
+
 }  // namespace pkmi
+
+// ------------------------------------------------------------------ the resampler's host entries (no device)
+
+namespace {
+int BuildOrFail(int rate, pkmi::ResampleTable *t) {
+  if (pkmi::BuildResampleTable(rate, t))
+    return pkhost::Fail(PK_MI355_E_INVALID, "sample rate %d is not supported: 8000 .. 96000 Hz with a polyphase table of at most %d entries",
+                        rate, pkmi::kResampleMaxEntries);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int pk_mi355_resample_plan(int rate, int *Q, int *P, int *max_taps) {
+  pkmi::ResampleTable t;
+  if (int rc = BuildOrFail(rate, &t)) return rc;
+  if (Q) *Q = t.Q;
+  if (P) *P = t.P;
+  if (max_taps) *max_taps = t.max_taps;
+  return 0;
+}
+
+int pk_mi355_resample_table(int rate, int32_t *first, int32_t *count, float *weights) {
+  pkmi::ResampleTable t;
+  if (int rc = BuildOrFail(rate, &t)) return rc;
+  if (first) memcpy(first, t.first.data(), sizeof(int32_t) * t.P);
+  if (count) memcpy(count, t.count.data(), sizeof(int32_t) * t.P);
+  if (weights) memcpy(weights, t.weights.data(), sizeof(float) * t.weights.size());
+  return 0;
+}
+
+int64_t pk_mi355_resample_num_output(int rate, int64_t n) {
+  pkmi::ResampleTable t;
+  if (int rc = BuildOrFail(rate, &t)) return rc;
+  if (n < 0) return pkhost::Fail(PK_MI355_E_INVALID, "negative sample count");
+  return pkmi::ResampleNumOutput(t, n);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
-    python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax]
+    python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
                                         [--online [--chunk-ms N] [--partials] [--commit]]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
@@ -9,7 +9,12 @@ many per call as the recognizer holds.  --ctm prints the word times instead: "<f
 per word segment of the best path, in seconds at the 10 ms frame shift (fbank.cc:35-42); segments without a word
 (word 0: what precedes the first word of a path) are skipped.
 
---online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step,
+Every file is read with read_wave: any sample rate from 8 to 96 kHz and up to 8 channels, of which --channel N
+(default 0) is taken; audio that is not at 16 kHz is converted on the GPU on the way in, and the word times stay on
+the 10 ms frame grid of the converted audio.
+
+--online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
+(measured at the file's own rate),
 up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
 also prints every changed partial hypothesis to stderr: "<file>\t<seconds of audio fed>\t<text>".  --chunk-ms and
 --partials without --online are refused with the usage text, as is --commit.  --commit turns the online decoder's commit
@@ -23,10 +28,11 @@ import pocketkaldi_amd as pk
 FRAME_SHIFT = 0.01
 MAX_UTTS = 16
 MAX_SAMPLES = 16000 * 120
+RESERVE = 32
 
 
 def usage():
-    print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] "
+    print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
           "[--online [--chunk-ms N] [--partials] [--commit]]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
@@ -34,20 +40,24 @@ def usage():
     return 1
 
 
-def recognize_online(model_file, files, waves, chunk, reference_softmax, partials, commit=False):
-    """Every wave through a slot of an OnlineRecognizer, `chunk` samples per step, MAX_UTTS waves at a time.
+def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None):
+    """Every wave through a slot of an OnlineRecognizer, `chunk_ms` milliseconds per step, MAX_UTTS waves at a time.
     -> (the results in order, the symbol names by word id)"""
+    rates = rates or [16000] * len(waves)
+    # a step's capacity counts 16 kHz samples; a converted slot also counts the few a close would add (RESERVE)
+    reserve = RESERVE if any(r != 16000 for r in rates) else 0
     rec = pk.OnlineRecognizer(model_file, max_streams=min(max(len(waves), 1), MAX_UTTS),
-                              max_step_samples=chunk * min(max(len(waves), 1), MAX_UTTS))
+                              max_step_samples=(16 * chunk_ms + reserve) * min(max(len(waves), 1), MAX_UTTS))
     try:
         if commit:
             rec.decoder.set_commit(True)
-        return stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit)
+        return stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit, rates)
     finally:
         rec.destroy()
 
 
-def stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit=False):
+def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None):
+    rates = rates or [16000] * len(waves)
     if reference_softmax:
         rec.am.set_softmax("reference")
     results = [None] * len(waves)
@@ -55,11 +65,12 @@ def stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit=F
         group = list(range(first, min(first + MAX_UTTS, len(waves))))
         pos, shown = {u: 0 for u in group}, {u: ("", "") if commit else "" for u in group}
         for u in group:
-            rec.open(u - first)
+            rec.open(u - first, rates[u])
         live = set(group)
         while live:
             closing = []
             for u in sorted(live):
+                chunk = max(rates[u] * chunk_ms // 1000, 1)
                 rec.push(u - first, waves[u][pos[u]:pos[u] + chunk])
                 pos[u] += chunk
                 if pos[u] >= len(waves[u]):          # the last chunk and the close in the same step
@@ -71,7 +82,7 @@ def stream_waves(rec, files, waves, chunk, reference_softmax, partials, commit=F
                 if commit:
                     text = (text, rec.stable(u - first))
                 if partials and text != shown[u]:
-                    sys.stderr.write("%s\t%.2f\t%s\n" % (files[u], min(pos[u], len(waves[u])) / 16000.0,
+                    sys.stderr.write("%s\t%.2f\t%s\n" % (files[u], min(pos[u], len(waves[u])) / float(rates[u]),
                                                         "\t".join(text) if commit else text))
                     shown[u] = text
             for u in closing:
@@ -93,6 +104,16 @@ def main(argv):
         if chunk_ms <= 0 or "--online" not in argv:
             return usage()
         del argv[at:at + 2]
+    channel = 0
+    if "--channel" in argv:
+        at = argv.index("--channel")
+        try:
+            channel = int(argv[at + 1])
+        except (IndexError, ValueError):
+            return usage()
+        if channel < 0:
+            return usage()
+        del argv[at:at + 2]
     flags = [a for a in argv if a.startswith("--")]
     args = [a for a in argv if not a.startswith("--")]
     if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax", "--online", "--partials", "--commit"}:
@@ -107,17 +128,22 @@ def main(argv):
         else:
             with open(input_file) as f:
                 files = [line.strip() for line in f if line.strip()]
-        waves = [pk.read_wav(name) for name in files]
+        waves, rates = [], []
+        for name in files:
+            wave, rate = pk.read_wave(name, channel)
+            waves.append(wave)
+            rates.append(rate)
         if "--online" in flags:
-            results, names = recognize_online(model_file, files, waves, 16 * chunk_ms, "--reference-softmax" in flags,
-                                              "--partials" in flags, "--commit" in flags)
+            results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
+                                              "--partials" in flags, "--commit" in flags, rates)
         else:
-            longest = max([len(w) for w in waves] + [1])
+            sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
-                                max_total_samples=max(longest, min(sum(len(w) for w in waves), MAX_SAMPLES)))
+                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)))
             if "--reference-softmax" in flags:
                 rec.am.set_softmax("reference")
-            results, names = rec.process(waves), rec.symbols
+            native = any(r != 16000 for r in rates)
+            results, names = rec.process(waves, rates if native else None), rec.symbols
     except (pk.PkError, OSError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
