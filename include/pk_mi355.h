@@ -720,6 +720,57 @@ int pk_mi355_online_decoder_trace_stats(const pk_mi355_online_decoder_t *d, int 
                                         int64_t *capacity);
 
 /* ------------------------------------------------------------------------- */
+/* Online endpointing ("Endpointing"): when has the speaker stopped */
+/* ------------------------------------------------------------------------- */
+
+/* One rule, in frames (10 ms each).  With contains_nonsilence = frames > trailing_silence_frames it fires when
+ *   (contains_nonsilence || !must_contain_nonsilence) && trailing_silence_frames >= min_trailing_silence_frames &&
+ *   relative_cost <= max_relative_cost && frames >= min_utterance_frames,
+ * and never at frames == 0.  Every test is on integers but the one float comparison.                               */
+typedef struct pk_mi355_endpoint_rule_t {
+  int must_contain_nonsilence;
+  int min_trailing_silence_frames;
+  float max_relative_cost;           /* +inf: the final-state cost is not asked                                     */
+  int min_utterance_frames;
+} pk_mi355_endpoint_rule_t;
+/* What the rules are tried on, for one slot after its last advance.  frames: decoded since open.
+ * trailing_silence_frames: the emitting arcs of the best partial path (lowest cost, lowest state on a tie) after its
+ * last arc that emits a pdf outside the silence set -- all of them if it has none.  best_cost: the lowest token cost
+ * (the partial's cost).  final_cost: the lowest (double)cost + (double)final weight over the num_final tokens for
+ * which that is not INFINITY, as float; relative_cost: the difference of the two, taken in double, as float.  Both
+ * +inf with num_final == 0.  rule: 1 + the first rule that fires, 0 for none.  valid == 0 (and all else 0): the slot
+ * has not advanced, finished, ended (status, ok = 0) or holds no token.                                             */
+typedef struct pk_mi355_endpoint_t {
+  int valid, frames, trailing_silence_frames, num_final, rule;
+  float best_cost, final_cost, relative_cost;
+} pk_mi355_endpoint_t;
+/* The five usual rules at a 10 ms frame shift, (must_contain_nonsilence, min_trailing_silence_frames,
+ * max_relative_cost, min_utterance_frames): (0, 500, inf, 0), (1, 50, 2.0, 0), (1, 100, 8.0, 0), (1, 200, inf, 0),
+ * (0, 0, inf, 2000).  Writes at most max of them (rules may be NULL); returns 5.  Host only, needs no GPU.           */
+int pk_mi355_endpoint_default_rules(pk_mi355_endpoint_rule_t *rules, int max);
+/* 1 + the index of the first rule that fires, 0 if none does (also for num_rules <= 0).  Host only, needs no GPU.    */
+int pk_mi355_endpoint_eval(const pk_mi355_endpoint_rule_t *rules, int num_rules, int frames, int trailing_silence_frames,
+                           float relative_cost);
+/* Off by default; num_rules == 0 turns it off.  Like alignment and commit the mode is the object's: set while no
+ * slot is open (PK_MI355_E_STATE otherwise), a call in flight is waited for first.  silence_pdfs: the pdfs (after the
+ * model's transition-id map) that count as silence; may be empty.  PK_MI355_E_INVALID for a pdf outside
+ * [0, num_pdfs), a negative frame count or a NaN max_relative_cost -- checked before anything else.  On: after every
+ * launch a second kernel leaves one record per slot of the call, fetched with the results; the decode kernels and
+ * every result are those of the mode off.  Device memory: 4 bytes per arc, num_pdfs / 8 bytes and 40 bytes per slot,
+ * from the first enable.                                                                                            */
+int pk_mi355_online_decoder_set_endpointing(pk_mi355_online_decoder_t *d, const int32_t *silence_pdfs, int num_silence,
+                                            const pk_mi355_endpoint_rule_t *rules, int num_rules);
+/* The slot's record after its last advance (out may be NULL); returns its rule.  PK_MI355_E_STATE with the mode off. */
+int pk_mi355_online_decoder_endpoint(const pk_mi355_online_decoder_t *d, int slot, pk_mi355_endpoint_t *out);
+/* Ends each listed open slot now, with no new frame: the slot's closing launch (BestPath with final weights over the
+ * frames decoded so far) on the decoder's own stream, after a pending advance.  result, word_segments and alignment
+ * are then those of pk_mi355_decoder_decode on the rows the slot has seen, bit for bit, and the slot can be opened
+ * again at once.  A slot that was never advanced gives the empty utterance's result.  An utterance ended while no
+ * token is final has no words (BestPath's empty hypothesis), as in the reference.  PK_MI355_E_STATE for a slot that
+ * is not open.  Needs no endpointing mode.                                                                          */
+int pk_mi355_online_decoder_finish(pk_mi355_online_decoder_t *d, const int *slots, int n, int sync);
+
+/* ------------------------------------------------------------------------- */
 /* Symbol table -- pk_symboltable_read / _get (symbol_table.cc:23-79)              */
 /* ------------------------------------------------------------------------- */
 
@@ -812,6 +863,33 @@ int pk_mi355_online_recognizer_finished(const pk_mi355_online_recognizer_t *r, i
  * finished: NULL / NaN with PK_MI355_E_STATE.  Valid until the slot is opened again.                               */
 const char *pk_mi355_online_recognizer_hyp(const pk_mi355_online_recognizer_t *r, int slot);
 float pk_mi355_online_recognizer_loglikelihood_per_frame(const pk_mi355_online_recognizer_t *r, int slot);
+
+/* Endpointing: pk_mi355_online_decoder_set_endpointing on the owned decoder, and the stream of every slot is cut into
+ * utterances.  While no slot is open (PK_MI355_E_STATE otherwise); num_rules == 0 turns it off.  On: after a step's
+ * advance every live slot that is not closing and whose endpoint rule fired is finished with the frames decoded so far
+ * (pk_mi355_online_decoder_finish, one call for all of them), kept as an utterance, and its decoder slot is opened
+ * again.  The scorer's slot stays open -- CMVN, context and resampler state run on -- so every later row is still the
+ * batch scorer's row on the whole wave, and an utterance is pk_mi355_decoder_decode on the rows
+ * [first_frame, first_frame + num_frames).  After close and the flushing step the rest is appended as the last
+ * utterance, with rule 0; _hyp and _loglikelihood_per_frame are that last one's, _partial and _stable the current
+ * one's.  The utterances are kept until the slot is opened again.  Off: no utterance is kept, and no entry changes.   */
+int pk_mi355_online_recognizer_set_endpointing(pk_mi355_online_recognizer_t *r, const int32_t *silence_pdfs, int num_silence,
+                                               const pk_mi355_endpoint_rule_t *rules, int num_rules);
+typedef struct pk_mi355_utterance_t {
+  int first_frame, num_frames;       /* of the slot's stream: first_frame is the sum of the earlier num_frames       */
+  int rule;                          /* 1 + the rule that ended it; 0: the stream's end                               */
+  int ok, num_words, num_word_segments;
+  float weight;
+  float loglikelihood_per_frame;     /* weight / num_frames; 0.0f without words, as is the text ""                    */
+} pk_mi355_utterance_t;
+int pk_mi355_online_recognizer_num_utterances(const pk_mi355_online_recognizer_t *r, int slot);
+int pk_mi355_online_recognizer_utterance(const pk_mi355_online_recognizer_t *r, int slot, int i, pk_mi355_utterance_t *out);
+/* Valid until the slot is opened again.  NULL on misuse.                                                            */
+const char *pk_mi355_online_recognizer_utterance_hyp(const pk_mi355_online_recognizer_t *r, int slot, int i);
+/* At most max written, the count returned.  Segment frames are relative to the utterance's first_frame.            */
+int pk_mi355_online_recognizer_utterance_words(const pk_mi355_online_recognizer_t *r, int slot, int i, int *words, int max);
+int pk_mi355_online_recognizer_utterance_word_segments(const pk_mi355_online_recognizer_t *r, int slot, int i,
+                                                       pk_mi355_word_t *out, int max);
 
 /* Library / device facts */
 int pk_mi355_device_count(void);

@@ -451,6 +451,26 @@ class OnlineDecoder {
   Status TraceStats(int slot, int64_t *in_use, int64_t *peak, int64_t *capacity) const {
     return Status::FromLast(pk_mi355_online_decoder_trace_stats(d_, slot, in_use, peak, capacity));
   }
+  // While no slot is open: after every advance each slot gets an endpoint record -- the silence (frames whose pdf is in
+  // silence_pdfs) that ends its best partial path, and its best final token's cost relative to its best token's -- on
+  // which `rules` are tried (pk_mi355_online_decoder_set_endpointing).  No rules: off.
+  Status SetEndpointing(const std::vector<int32_t> &silence_pdfs, const std::vector<pk_mi355_endpoint_rule_t> &rules) {
+    return Status::FromLast(pk_mi355_online_decoder_set_endpointing(d_, silence_pdfs.data(), static_cast<int>(silence_pdfs.size()),
+                                                                    rules.data(), static_cast<int>(rules.size())));
+  }
+  static std::vector<pk_mi355_endpoint_rule_t> DefaultEndpointRules() {
+    std::vector<pk_mi355_endpoint_rule_t> rules(pk_mi355_endpoint_default_rules(nullptr, 0));
+    pk_mi355_endpoint_default_rules(rules.data(), static_cast<int>(rules.size()));
+    return rules;
+  }
+  // The slot's record after its last advance (out may be null).  Returns 1 + the first rule that fires, 0 for none, or
+  // a negative code (the mode is off: PK_MI355_E_STATE).
+  int Endpoint(int slot, pk_mi355_endpoint_t *out) const { return pk_mi355_online_decoder_endpoint(d_, slot, out); }
+  // End the open slots now, with no new frame: Result() is then BestPath over the frames decoded so far, and the slots
+  // can be opened again.
+  Status Finish(const std::vector<int> &slots) {
+    return Status::FromLast(pk_mi355_online_decoder_finish(d_, slots.data(), static_cast<int>(slots.size()), 1));
+  }
   const Status &last_status() const { return status_; }
   pk_mi355_online_decoder_t *handle() const { return d_; }
 
@@ -501,6 +521,37 @@ class OnlineRecognizer {
     if (!hyp) return Status(pk_mi355_last_error_code(), pk_mi355_last_error());
     if (out) *out = Recognizer::Utterance{hyp, pk_mi355_online_recognizer_loglikelihood_per_frame(r_, slot)};
     return Status();
+  }
+  // While no slot is open: every Step() ends the utterance of each live slot whose endpoint rule fired and starts the next
+  // one at the scorer's next row (pk_mi355_online_recognizer_set_endpointing).  No rules: off.
+  Status SetEndpointing(const std::vector<int32_t> &silence_pdfs, const std::vector<pk_mi355_endpoint_rule_t> &rules) {
+    return Status::FromLast(pk_mi355_online_recognizer_set_endpointing(r_, silence_pdfs.data(), static_cast<int>(silence_pdfs.size()),
+                                                                       rules.data(), static_cast<int>(rules.size())));
+  }
+  // One utterance of a slot's stream: frames [first_frame, first_frame + num_frames), rule = 1 + the rule that ended it
+  // (0: the stream's end); segment frames are relative to first_frame
+  struct Piece {
+    pk_mi355_utterance_t info;
+    std::string hyp;
+    std::vector<int> words;
+    std::vector<pk_mi355_word_t> segments;
+  };
+  // The utterances since Open(slot), in order; the last one (rule 0) is there once the slot is finished
+  std::vector<Piece> Utterances(int slot) const {
+    const int n = pk_mi355_online_recognizer_num_utterances(r_, slot);
+    std::vector<Piece> out(n > 0 ? n : 0);
+    for (int i = 0; i < n; ++i) {
+      Piece &p = out[i];
+      if (pk_mi355_online_recognizer_utterance(r_, slot, i, &p.info) != 0) continue;
+      const char *hyp = pk_mi355_online_recognizer_utterance_hyp(r_, slot, i);
+      p.hyp = hyp ? hyp : "";
+      p.words.resize(p.info.num_words);
+      p.segments.resize(p.info.num_word_segments);
+      if (!p.words.empty()) pk_mi355_online_recognizer_utterance_words(r_, slot, i, p.words.data(), p.info.num_words);
+      if (!p.segments.empty())
+        pk_mi355_online_recognizer_utterance_word_segments(r_, slot, i, p.segments.data(), p.info.num_word_segments);
+    }
+    return out;
   }
   // The owned objects: beam, softmax mode and the other result getters (words, alignment, word segments) are their entries
   pk_mi355_am_t *am() const { return pk_mi355_online_recognizer_am(r_); }

@@ -59,6 +59,21 @@ class pk_mi355_word_t(C.Structure):      # one word segment of a best path (incl
                 ("acoustic_cost", C.c_float)]
 
 
+class pk_mi355_endpoint_rule_t(C.Structure):     # one endpoint rule, in frames (include/pk_mi355.h)
+    _fields_ = [("must_contain_nonsilence", C.c_int), ("min_trailing_silence_frames", C.c_int),
+                ("max_relative_cost", C.c_float), ("min_utterance_frames", C.c_int)]
+
+
+class pk_mi355_utterance_t(C.Structure):         # one utterance of an endpointed stream (include/pk_mi355.h)
+    _fields_ = [("first_frame", C.c_int), ("num_frames", C.c_int), ("rule", C.c_int), ("ok", C.c_int), ("num_words", C.c_int),
+                ("num_word_segments", C.c_int), ("weight", C.c_float), ("loglikelihood_per_frame", C.c_float)]
+
+
+class pk_mi355_endpoint_t(C.Structure):          # a slot's endpoint record (include/pk_mi355.h)
+    _fields_ = [("valid", C.c_int), ("frames", C.c_int), ("trailing_silence_frames", C.c_int), ("num_final", C.c_int),
+                ("rule", C.c_int), ("best_cost", C.c_float), ("final_cost", C.c_float), ("relative_cost", C.c_float)]
+
+
 _lib = None
 
 # every symbol include/pk_mi355.h declares (tests check the library exports all of them)
@@ -111,6 +126,11 @@ EXPORTS = [
     "pk_mi355_resample_plan", "pk_mi355_resample_table", "pk_mi355_resample_num_output", "pk_mi355_resample",
     "pk_mi355_resample_set_waves", "pk_mi355_wave_read", "pk_mi355_recognizer_process_rates",
     "pk_mi355_stream_open_rate", "pk_mi355_stream_rate", "pk_mi355_online_recognizer_open_rate",
+    "pk_mi355_endpoint_default_rules", "pk_mi355_endpoint_eval", "pk_mi355_online_decoder_set_endpointing",
+    "pk_mi355_online_decoder_endpoint", "pk_mi355_online_decoder_finish",
+    "pk_mi355_online_recognizer_set_endpointing", "pk_mi355_online_recognizer_num_utterances",
+    "pk_mi355_online_recognizer_utterance", "pk_mi355_online_recognizer_utterance_hyp",
+    "pk_mi355_online_recognizer_utterance_words", "pk_mi355_online_recognizer_utterance_word_segments",
 ]
 
 
@@ -331,6 +351,20 @@ def lib():
     L.pk_mi355_stream_open_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pk_mi355_stream_rate.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_online_recognizer_open_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    rulep = C.POINTER(pk_mi355_endpoint_rule_t)
+    L.pk_mi355_endpoint_default_rules.argtypes = [rulep, C.c_int]
+    L.pk_mi355_endpoint_eval.argtypes = [rulep, C.c_int, C.c_int, C.c_int, C.c_float]
+    L.pk_mi355_online_decoder_set_endpointing.argtypes = [C.c_void_p, i32p, C.c_int, rulep, C.c_int]
+    L.pk_mi355_online_decoder_endpoint.argtypes = [C.c_void_p, C.c_int, C.POINTER(pk_mi355_endpoint_t)]
+    L.pk_mi355_online_decoder_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int]
+    L.pk_mi355_online_recognizer_set_endpointing.argtypes = [C.c_void_p, i32p, C.c_int, rulep, C.c_int]
+    L.pk_mi355_online_recognizer_num_utterances.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_utterance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(pk_mi355_utterance_t)]
+    L.pk_mi355_online_recognizer_utterance_hyp.restype = C.c_char_p
+    L.pk_mi355_online_recognizer_utterance_hyp.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pk_mi355_online_recognizer_utterance_words.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int]
+    L.pk_mi355_online_recognizer_utterance_word_segments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(pk_mi355_word_t),
+                                                                     C.c_int]
     _lib = L
     return L
 
@@ -1046,6 +1080,40 @@ class Decoder:
         return peak.value, size.value, n.value
 
 
+EndpointRule = collections.namedtuple("EndpointRule",
+                                      "must_contain_nonsilence min_trailing_silence max_relative_cost min_utterance_length")
+EndpointRule.__doc__ = """One endpoint rule, times in seconds (a frame is 10 ms: int(round(s * 100)) frames)."""
+Utterance = collections.namedtuple("Utterance", "result first_frame num_frames rule")
+Endpoint = collections.namedtuple("Endpoint",
+                                  "valid frames trailing_silence_frames num_final rule best_cost final_cost relative_cost")
+
+
+def _rules_array(rules):
+    arr = (pk_mi355_endpoint_rule_t * max(len(rules), 1))()
+    for i, r in enumerate(rules):
+        r = EndpointRule(*r)
+        arr[i].must_contain_nonsilence = 1 if r.must_contain_nonsilence else 0
+        arr[i].min_trailing_silence_frames = int(round(r.min_trailing_silence * 100))
+        arr[i].max_relative_cost = float(r.max_relative_cost)
+        arr[i].min_utterance_frames = int(round(r.min_utterance_length * 100))
+    return arr
+
+
+def endpoint_default_rules():
+    """The five usual rules (pk_mi355_endpoint_default_rules), as EndpointRule in seconds."""
+    arr = (pk_mi355_endpoint_rule_t * 5)()
+    n = lib().pk_mi355_endpoint_default_rules(arr, 5)
+    return [EndpointRule(bool(r.must_contain_nonsilence), r.min_trailing_silence_frames / 100.0, r.max_relative_cost,
+                         r.min_utterance_frames / 100.0) for r in arr[:n]]
+
+
+def endpoint_eval(rules, frames, trailing, relative_cost):
+    """1 + the index of the first of `rules` (EndpointRule) that fires for an utterance of `frames` frames that ends in
+    `trailing` frames of silence and whose best final token costs `relative_cost` more than its best token; 0 if none."""
+    rules = list(rules)
+    return lib().pk_mi355_endpoint_eval(_rules_array(rules), len(rules), int(frames), int(trailing), float(relative_cost))
+
+
 class OnlineDecoder:
     """Decoder::Decode frame-synchronous across calls: open(slot), advance(scorer) after every OnlineScorer.step (or
     advance_host with log-likelihood chunks), partial(slot) after every call, result(slot) once the slot is finished."""
@@ -1166,6 +1234,29 @@ class OnlineDecoder:
         in_use, peak, cap = C.c_int64(), C.c_int64(), C.c_int64()
         _check_code(lib().pk_mi355_online_decoder_trace_stats(self._h, int(slot), C.byref(in_use), C.byref(peak), C.byref(cap)))
         return in_use.value, peak.value, cap.value
+
+    def set_endpointing(self, silence_pdfs, rules=None):
+        """While no slot is open: after every advance a second kernel works out, per slot, the silence that ends the best
+        partial path (in frames whose pdf is in silence_pdfs) and the best final token's cost relative to the best
+        token's; endpoint(slot) tries `rules` (EndpointRule, default endpoint_default_rules()) on them.  rules=[]: off."""
+        rules = endpoint_default_rules() if rules is None else list(rules)
+        sil = np.ascontiguousarray(silence_pdfs, dtype=np.int32).ravel()
+        _check_code(lib().pk_mi355_online_decoder_set_endpointing(
+            self._h, sil.ctypes.data_as(C.POINTER(C.c_int32)) if sil.size else None, sil.shape[0], _rules_array(rules), len(rules)))
+
+    def endpoint(self, slot):
+        """The slot's Endpoint record after its last advance; .rule is 1 + the first rule that fires, 0 for none."""
+        e = pk_mi355_endpoint_t()
+        _check_code(lib().pk_mi355_online_decoder_endpoint(self._h, int(slot), C.byref(e)))
+        return Endpoint(e.valid, e.frames, e.trailing_silence_frames, e.num_final, e.rule, e.best_cost, e.final_cost,
+                        e.relative_cost)
+
+    def finish(self, slots, sync=True):
+        """End the open slots now, with no new frame: result(slot) is then Decoder.decode's on the rows the slot has seen,
+        and the slot can be opened again."""
+        slots = [int(s) for s in slots]
+        arr = (C.c_int * max(len(slots), 1))(*slots)
+        _check_code(lib().pk_mi355_online_decoder_finish(self._h, arr, len(slots), 1 if sync else 0))
 
 
 class SymbolTable:
@@ -1379,3 +1470,34 @@ class OnlineRecognizer:
         return Result(text.decode(), words, weight, ok,
                       lib().pk_mi355_online_recognizer_loglikelihood_per_frame(self._h, int(slot)),
                       self.decoder.word_segments(slot))
+
+    def set_endpointing(self, silence_pdfs, rules=None):
+        """While no slot is open: OnlineDecoder.set_endpointing on the owned decoder, and every step() ends the utterance
+        of each live slot whose rule fired and starts the next one at the scorer's next row; utterances(slot) lists them.
+        rules=[]: off."""
+        rules = endpoint_default_rules() if rules is None else list(rules)
+        sil = np.ascontiguousarray(silence_pdfs, dtype=np.int32).ravel()
+        _check_code(lib().pk_mi355_online_recognizer_set_endpointing(
+            self._h, sil.ctypes.data_as(C.POINTER(C.c_int32)) if sil.size else None, sil.shape[0], _rules_array(rules), len(rules)))
+
+    def utterances(self, slot):
+        """The utterances the slot's stream was cut into since open(slot), in order: Utterance(result, first_frame,
+        num_frames, rule).  result is what Decoder.decode gives on the scorer's rows [first_frame, first_frame +
+        num_frames), segment frames relative to first_frame; rule is 1 + the rule that ended it, 0 for the last one,
+        which is there once the slot is finished."""
+        L, slot = lib(), int(slot)
+        out = []
+        for i in range(_check_code(L.pk_mi355_online_recognizer_num_utterances(self._h, slot))):
+            u = pk_mi355_utterance_t()
+            _check_code(L.pk_mi355_online_recognizer_utterance(self._h, slot, i, C.byref(u)))
+            words = np.zeros(max(u.num_words, 1), np.int32)
+            _check_code(L.pk_mi355_online_recognizer_utterance_words(self._h, slot, i, words.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                     u.num_words))
+            segs = (pk_mi355_word_t * max(u.num_word_segments, 1))()
+            _check_code(L.pk_mi355_online_recognizer_utterance_word_segments(self._h, slot, i, segs, u.num_word_segments))
+            result = Result(L.pk_mi355_online_recognizer_utterance_hyp(self._h, slot, i).decode(),
+                            [int(w) for w in words[:u.num_words]], u.weight, u.ok, u.loglikelihood_per_frame,
+                            [Segment(s.word, s.start_frame, s.num_frames, s.graph_cost, s.acoustic_cost)
+                             for s in segs[:u.num_word_segments]])
+            out.append(Utterance(result, u.first_frame, u.num_frames, u.rule))
+        return out

@@ -20,8 +20,10 @@ struct Slot {
   std::vector<int> committed_words;             // the words (olabel != 0) of committed, kept as the arcs arrive
   int committed_frames = 0;                     // the emitting arcs among committed
   int64_t in_use = 0, peak = 0;                 // records in the arena after the last launch; the most since open
+  int committed_run = 0;                        // endpointing: the silent emitting arcs that end committed (epsilons skipped)
+  pk_mi355_endpoint_t ep = {};                  // endpointing: the record after the slot's last advance
 
-  void ClearCommitted() { committed.clear(); committed_ac.clear(); committed_words.clear(); committed_frames = 0; }
+  void ClearCommitted() { committed.clear(); committed_ac.clear(); committed_words.clear(); committed_frames = 0; committed_run = 0; }
 };
 
 // The core's work areas are one per slot, its arenas cap records per slot.
@@ -37,6 +39,15 @@ struct pk_mi355_online_decoder : DecoderCore {
   bool align = false;                           // pk_mi355_online_decoder_set_alignment
   float *d_rec_ac = nullptr, *d_path_ac = nullptr;   // cap floats per slot each, from the first enable
   bool commit = false;                          // pk_mi355_online_decoder_set_commit
+  // pk_mi355_online_decoder_set_endpointing: the rules, the arcs' kind on the host (0 epsilon, 1 emitting, 2 emitting a
+  // silence pdf) and, from the first enable, the arcs' pdfs, the silence mask and one record per slot on the device
+  bool endpoint = false;
+  std::vector<pk_mi355_endpoint_rule_t> rules;
+  std::vector<char> arc_kind;
+  int *d_arc_pdf = nullptr;
+  uint32_t *d_silence = nullptr;
+  EndpointRecord *d_endpoint = nullptr;
+  std::vector<EndpointRecord> ep_fetched;       // d_endpoint as copied back
   std::vector<Slot> slots;
   std::vector<char> fetched;                    // d_results' allocation as copied back; the last call's slots are read from it
   std::vector<int32_t> got;                     // a slot's path slice as copied back
@@ -74,6 +85,18 @@ int OnlineLaunch(pk_mi355_online_decoder *o, const float *ll, const std::vector<
     LaunchOnlineDecode(A, o->d_calls, o->d_state, o->d_results, n, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "online decode launch: %s", hipGetErrorString(e));
+    if (o->endpoint) {                                   // the endpoint records of the call's slots, from what the launch left
+      EndpointArgs E;
+      E.calls = o->d_calls; E.states = o->d_state; E.results = o->d_results; E.n = n;
+      E.la = A.la; E.lb = A.lb; E.num_states = o->num_states; E.final_w = o->final_w;
+      E.path = o->path; E.cap = o->cap; E.commit_len = o->commit ? o->d_commit : nullptr;
+      E.arc_pdf = o->d_arc_pdf; E.num_arcs = (int)o->labels.ilabel.size();
+      E.silence = o->d_silence; E.num_pdfs = o->num_pdfs;
+      E.out = o->d_endpoint;
+      LaunchEndpoint(E, stream);
+      e = hipGetLastError();
+      if (e != hipSuccess) return Fail(PK_MI355_E_DEVICE, "endpoint launch: %s", hipGetErrorString(e));
+    }
   }
   for (const auto &c : calls) {
     Slot &s = o->slots[c.slot];
@@ -99,7 +122,11 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
   const OnlineResult *results = reinterpret_cast<const OnlineResult *>(o->fetched.data());
   const OnlineState *states = reinterpret_cast<const OnlineState *>(results + o->max_streams);
   const int *commits = reinterpret_cast<const int *>(states + o->max_streams);
-  int first_bad = -1;
+  if (o->endpoint) {
+    o->ep_fetched.resize(o->max_streams);
+    HIP_TRY(hipMemcpy(o->ep_fetched.data(), o->d_endpoint, sizeof(EndpointRecord) * o->max_streams, hipMemcpyDeviceToHost));
+  }
+  int first_bad = -1, first_bad_ep = -1;
   for (int slot : o->last_slots) {
     Slot &s = o->slots[slot];
     s.res = results[slot];
@@ -120,6 +147,7 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
       if (arc < 0 || arc >= (int32_t)o->labels.olabel.size()) continue;
       if (o->labels.olabel[arc] != 0) s.committed_words.push_back(o->labels.olabel[arc]);
       s.committed_frames += o->labels.ilabel[arc] != 0;
+      if (o->endpoint && o->arc_kind[arc]) s.committed_run = o->arc_kind[arc] == 2 ? s.committed_run + 1 : 0;
     }
     s.path.assign(o->got.begin() + nc, o->got.end());
     if (s.aligned) {
@@ -132,7 +160,23 @@ int OnlineCollect(pk_mi355_online_decoder *o) {
     // no path at all, whatever was committed earlier: a slot that ended, or one that finished without a final token
     if (r.status || !r.ok || !r.has_path) s.ClearCommitted();
     if (r.status && first_bad < 0) first_bad = slot;
+    if (o->endpoint) {
+      const EndpointRecord &e = o->ep_fetched[slot];
+      s.ep = pk_mi355_endpoint_t{};
+      if (e.status && !r.status && first_bad_ep < 0) first_bad_ep = slot;
+      if (e.valid && !e.status && !r.status && r.ok) {
+        s.ep.valid = 1;
+        s.ep.frames = r.frames;
+        s.ep.trailing_silence_frames = e.tail_silence + (e.tail_open ? s.committed_run : 0);
+        s.ep.num_final = e.num_final;
+        s.ep.best_cost = e.best_cost; s.ep.final_cost = e.final_cost; s.ep.relative_cost = e.relative_cost;
+        s.ep.rule = pk_mi355_endpoint_eval(o->rules.data(), (int)o->rules.size(), s.ep.frames, s.ep.trailing_silence_frames,
+                                           s.ep.relative_cost);
+      }
+    }
   }
+  if (first_bad < 0 && first_bad_ep >= 0)
+    return Fail(PK_MI355_E_DEVICE, "online decoder: slot %d: the endpoint scan met an arc or a length out of range", first_bad_ep);
   if (first_bad >= 0) {
     const OnlineResult &r = o->slots[first_bad].res;
     if (r.status == PK_MI355_E_CAPACITY)
@@ -244,6 +288,7 @@ void pk_mi355_online_decoder_destroy(pk_mi355_online_decoder_t *o) {
     if (o->pending) hipEventSynchronize(o->done);
     hipFree(o->d_results); hipFree(o->d_remap); hipFree(o->d_calls);
     hipFree(o->d_rec_ac); hipFree(o->d_path_ac);
+    hipFree(o->d_arc_pdf); hipFree(o->d_silence); hipFree(o->d_endpoint);
     FreeCore(o);
   }
   delete o;
@@ -284,6 +329,90 @@ int pk_mi355_online_decoder_set_commit(pk_mi355_online_decoder_t *o, int enable)
   if ((rc = OnlineCollect(o)) == PK_MI355_E_DEVICE) return rc;      // (as set_alignment: a call in flight ends first)
   o->commit = enable != 0;                               // (a finished slot keeps its results, and the mode it was opened with)
   return 0;
+}
+
+int pk_mi355_online_decoder_set_endpointing(pk_mi355_online_decoder_t *o, const int32_t *silence_pdfs, int num_silence,
+                                            const pk_mi355_endpoint_rule_t *rules, int num_rules) {
+  if (!o) return Fail(PK_MI355_E_INVALID, "null online decoder");
+  if (num_silence < 0 || num_rules < 0 || (num_silence > 0 && !silence_pdfs) || (num_rules > 0 && !rules))
+    return Fail(PK_MI355_E_INVALID, "online decoder: bad endpointing arguments");
+  for (int i = 0; i < num_silence; ++i)
+    if (silence_pdfs[i] < 0 || silence_pdfs[i] >= o->num_pdfs)
+      return Fail(PK_MI355_E_INVALID, "online decoder: silence pdf %d outside [0, %d)", (int)silence_pdfs[i], o->num_pdfs);
+  for (int i = 0; i < num_rules; ++i) {
+    if (rules[i].min_trailing_silence_frames < 0 || rules[i].min_utterance_frames < 0)
+      return Fail(PK_MI355_E_INVALID, "online decoder: endpoint rule %d: negative frame count", i);
+    if (rules[i].max_relative_cost != rules[i].max_relative_cost)
+      return Fail(PK_MI355_E_INVALID, "online decoder: endpoint rule %d: max_relative_cost is NaN", i);
+  }
+  for (int slot = 0; slot < o->max_streams; ++slot)     // one launch serves every slot: the mode is the object's
+    if (o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is open (set_endpointing needs every slot closed)", slot);
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  if ((rc = OnlineCollect(o)) == PK_MI355_E_DEVICE) return rc;      // (as set_alignment: a call in flight ends first)
+  if (num_rules == 0) { o->endpoint = false; o->rules.clear(); return 0; }
+  const size_t words = ((size_t)o->num_pdfs + 31) / 32;
+  std::vector<uint32_t> mask(words, 0u);
+  for (int i = 0; i < num_silence; ++i) mask[silence_pdfs[i] >> 5] |= 1u << (silence_pdfs[i] & 31);
+  const std::vector<int32_t> &tid2pdf = o->am->tid2pdf;
+  const size_t num_arcs = o->labels.ilabel.size();
+  std::vector<int> arc_pdf(num_arcs);
+  std::vector<char> kind(num_arcs);
+  for (size_t a = 0; a < num_arcs; ++a) {
+    const int il = o->labels.ilabel[a];                  // (CreateCore has checked every ilabel against the model)
+    arc_pdf[a] = il == 0 ? -1 : tid2pdf.empty() ? il : tid2pdf[il];
+    const int p = arc_pdf[a];
+    kind[a] = p < 0 ? 0 : (p < o->num_pdfs && ((mask[p >> 5] >> (p & 31)) & 1u)) ? 2 : 1;
+  }
+  if (!o->d_endpoint) {                                  // the first enable
+    int *d_arc_pdf = nullptr;
+    uint32_t *d_silence = nullptr;
+    EndpointRecord *d_endpoint = nullptr;
+    hipError_t e = hipMalloc(&d_arc_pdf, sizeof(int) * std::max<size_t>(num_arcs, 1));
+    if (e == hipSuccess) e = hipMalloc(&d_silence, sizeof(uint32_t) * std::max<size_t>(words, 1));
+    if (e == hipSuccess) e = hipMalloc(&d_endpoint, sizeof(EndpointRecord) * o->max_streams);
+    if (e == hipSuccess) e = hipMemset(d_endpoint, 0, sizeof(EndpointRecord) * o->max_streams);
+    if (e == hipSuccess && num_arcs) e = hipMemcpy(d_arc_pdf, arc_pdf.data(), sizeof(int) * num_arcs, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      hipFree(d_arc_pdf); hipFree(d_silence); hipFree(d_endpoint);
+      return Fail(PK_MI355_E_DEVICE, "online_decoder_set_endpointing: %s", hipGetErrorString(e));
+    }
+    o->d_arc_pdf = d_arc_pdf; o->d_silence = d_silence; o->d_endpoint = d_endpoint;
+  }
+  if (words) HIP_TRY(hipMemcpy(o->d_silence, mask.data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice));
+  o->arc_kind.swap(kind);
+  o->rules.assign(rules, rules + num_rules);
+  o->endpoint = true;                                    // (a finished slot keeps its results)
+  return 0;
+}
+
+int pk_mi355_online_decoder_endpoint(const pk_mi355_online_decoder_t *o, int slot, pk_mi355_endpoint_t *out) {
+  int rc = OnlineReady(o, slot);
+  if (rc) return rc;
+  if (!o->endpoint) return Fail(PK_MI355_E_STATE, "online decoder: endpointing is off (pk_mi355_online_decoder_set_endpointing)");
+  const Slot &s = o->slots[slot];
+  const bool live = s.open && !s.fresh && !s.finished;
+  if (out) *out = live ? s.ep : pk_mi355_endpoint_t{};
+  return live ? s.ep.rule : 0;
+}
+
+int pk_mi355_online_decoder_finish(pk_mi355_online_decoder_t *o, const int *slots, int n, int sync) {
+  if (!o || n < 0 || (n > 0 && !slots)) return Fail(PK_MI355_E_INVALID, "bad finish arguments");
+  int rc = UseDevice(o->device);
+  if (rc) return rc;
+  std::vector<char> seen(o->max_streams, 0);
+  std::vector<OnlineCall> calls(n);
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i];
+    if ((rc = OnlineSlot(o, slot))) return rc;
+    if (!o->slots[slot].open) return Fail(PK_MI355_E_STATE, "online decoder: slot %d is not open", slot);
+    if (seen[slot]) return Fail(PK_MI355_E_INVALID, "online decoder: slot %d twice in one call", slot);
+    seen[slot] = 1;
+    calls[i] = OnlineCall{slot, 0, 1, o->slots[slot].fresh, 0};      // no new frame: the closing launch alone
+  }
+  // (OnlineLaunch waits for a pending advance -- and collects it with commit on -- before it queues this one)
+  if ((rc = OnlineLaunch(o, o->d_ll, calls, o->own_stream))) return rc;
+  return sync ? OnlineCollect(o) : 0;
 }
 
 int pk_mi355_online_decoder_open(pk_mi355_online_decoder_t *o, int slot) {

@@ -4,6 +4,7 @@
 // decoder are the library's own entries, wired slot for slot, and every knob of theirs stays theirs
 // (pk_mi355_online_recognizer_am / _stream / _decoder hand them out).  The file-loading half is capi_recognizer.hip's.
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pk_host.h"
@@ -20,9 +21,71 @@ struct pk_mi355_online_recognizer : RecognizerFiles {
   std::vector<std::string> stable;           // per slot: the committed words' text after the last step ("": mode off)
   std::vector<size_t> stable_words;          // per slot: how many of the decoder's committed words stable[slot] holds
   std::vector<float> per_frame;
+  // pk_mi355_online_recognizer_set_endpointing: a slot's stream is cut into utterances where a rule fires.  Per slot the
+  // pieces since it was opened, and the frames they hold (the next piece's first_frame)
+  bool endpointing = false;
+  struct Piece {
+    pk_mi355_utterance_t info;
+    std::string hyp;
+    std::vector<int> words;
+    std::vector<pk_mi355_word_t> segments;
+  };
+  std::vector<std::vector<Piece>> pieces;
+  std::vector<int> piece_first;
 };
 
 namespace {
+
+// The decoder slot's finished utterance as the slot's next piece (rule: what ended it, 0 for the stream's end).  Text
+// and per-frame figure by pk_process's rules (pocketkaldi.cc:239-243); segment frames are relative to first_frame.
+int Snapshot(pk_mi355_online_recognizer *r, int slot, int rule) {
+  pk_mi355_online_recognizer::Piece p;
+  float weight = 0.0f;
+  int ok = 0;
+  const int count = pk_mi355_online_decoder_result(r->decoder, slot, nullptr, 0, &weight, &ok);
+  if (count < 0) return count;
+  p.words.resize(count);
+  if (count) pk_mi355_online_decoder_result(r->decoder, slot, p.words.data(), count, nullptr, nullptr);
+  const int frames = pk_mi355_online_decoder_num_frames(r->decoder, slot);
+  if (frames < 0) return frames;
+  const int segs = pk_mi355_online_decoder_word_segments(r->decoder, slot, nullptr, 0);
+  if (segs < 0) return segs;
+  p.segments.resize(segs);
+  if (segs) pk_mi355_online_decoder_word_segments(r->decoder, slot, p.segments.data(), segs);
+  float per_frame = 0.0f;
+  if (ok && count > 0) {
+    const int rc = JoinWords(r->symtab, p.words.data(), count, &p.hyp);
+    if (rc) return rc;
+    per_frame = weight / frames;
+  }
+  p.info = pk_mi355_utterance_t{r->piece_first[slot], frames, rule, ok, count, segs, weight, per_frame};
+  r->piece_first[slot] += frames;
+  r->pieces[slot].push_back(std::move(p));
+  return 0;
+}
+
+// After a step's advance and refresh, with endpointing on: every live slot that is not closing and whose endpoint rule
+// fired ends its utterance now (one finish call for all of them), becomes a piece and starts the next utterance at the
+// scorer's next row.  The scorer's slot is not touched: CMVN, context and resampler run on.
+int CutAtEndpoints(pk_mi355_online_recognizer *r) {
+  std::vector<int> cut, rules;
+  for (int slot = 0; slot < r->max_streams; ++slot) {
+    if (!r->live[slot] || r->closed[slot]) continue;
+    const int rule = pk_mi355_online_decoder_endpoint(r->decoder, slot, nullptr);
+    if (rule < 0) return rule;
+    if (rule > 0) { cut.push_back(slot); rules.push_back(rule); }
+  }
+  if (cut.empty()) return 0;
+  int rc = pk_mi355_online_decoder_finish(r->decoder, cut.data(), (int)cut.size(), 1);
+  if (rc) return rc;
+  for (size_t i = 0; i < cut.size(); ++i) {
+    const int slot = cut[i];
+    if ((rc = Snapshot(r, slot, rules[i])) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
+    r->partial[slot].clear(); r->stable[slot].clear();      // the next piece's text starts empty
+    r->stable_words[slot] = 0;
+  }
+  return 0;
+}
 
 // The text of every slot this object opened, after a step; a slot whose close the step flushed becomes finished.
 int Refresh(pk_mi355_online_recognizer *r) {
@@ -57,6 +120,27 @@ int Refresh(pk_mi355_online_recognizer *r) {
     r->per_frame[slot] = weight / pk_mi355_online_decoder_num_frames(r->decoder, slot);     // :239
   }
   return 0;
+}
+
+// Refresh, and with endpointing on the stream's last piece of every slot that it found finished.
+int RefreshAndClose(pk_mi355_online_recognizer *r) {
+  if (!r->endpointing) return Refresh(r);
+  const std::vector<char> was_live = r->live;
+  int rc = Refresh(r);
+  for (int slot = 0; slot < r->max_streams && !rc; ++slot)
+    if (was_live[slot] && r->finished[slot]) rc = Snapshot(r, slot, 0);
+  return rc;
+}
+
+// A getter's piece: slot and index in range.
+const pk_mi355_online_recognizer::Piece *PieceOf(const pk_mi355_online_recognizer *r, int slot, int i) {
+  if (!r) { Fail(PK_MI355_E_INVALID, "null online recognizer"); return nullptr; }
+  if (slot < 0 || slot >= r->max_streams) { Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, r->max_streams); return nullptr; }
+  if (i < 0 || i >= (int)r->pieces[slot].size()) {
+    Fail(PK_MI355_E_INVALID, "online recognizer: slot %d has %d utterances, not %d", slot, (int)r->pieces[slot].size(), i);
+    return nullptr;
+  }
+  return &r->pieces[slot][i];
 }
 
 int CheckSlot(const pk_mi355_online_recognizer *r, int slot) {
@@ -96,6 +180,8 @@ pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config
   r->stable.assign(max_streams, std::string());
   r->stable_words.assign(max_streams, 0);
   r->per_frame.assign(max_streams, 0.0f);
+  r->pieces.assign(max_streams, std::vector<pk_mi355_online_recognizer::Piece>());
+  r->piece_first.assign(max_streams, 0);
   return r;
 }
 
@@ -130,6 +216,8 @@ int pk_mi355_online_recognizer_open_rate(pk_mi355_online_recognizer_t *r, int sl
   r->partial[slot].clear(); r->hyp[slot].clear(); r->stable[slot].clear();
   r->stable_words[slot] = 0;
   r->per_frame[slot] = 0.0f;
+  r->pieces[slot].clear();
+  r->piece_first[slot] = 0;
   return 0;
 }
 
@@ -158,10 +246,58 @@ int pk_mi355_online_recognizer_step(pk_mi355_online_recognizer_t *r) {
   // What the advance returns is returned.  A slot's verdict (capacity, a closure that did not settle) comes after
   // every slot's result was fetched, so the text is refreshed whatever it said: the other slots go on.
   rc = pk_mi355_online_decoder_advance(r->decoder, r->stream, 1);
-  if (!rc) return Refresh(r);
+  if (!rc) {
+    if ((rc = RefreshAndClose(r)) || !r->endpointing) return rc;
+    return CutAtEndpoints(r);
+  }
   const std::string said = LastError();                  // (the refresh's getters may say something of their own)
-  Refresh(r);
+  RefreshAndClose(r);
+  if (r->endpointing) CutAtEndpoints(r);                 // (the other slots go on, cuts included)
   return Fail(rc, "%s", said.c_str());
+}
+
+int pk_mi355_online_recognizer_set_endpointing(pk_mi355_online_recognizer_t *r, const int32_t *silence_pdfs, int num_silence,
+                                               const pk_mi355_endpoint_rule_t *rules, int num_rules) {
+  if (!r) return Fail(PK_MI355_E_INVALID, "null online recognizer");
+  for (int slot = 0; slot < r->max_streams; ++slot)
+    if (r->live[slot]) return Fail(PK_MI355_E_STATE, "online recognizer: slot %d is open (set_endpointing needs every slot closed)", slot);
+  const int rc = pk_mi355_online_decoder_set_endpointing(r->decoder, silence_pdfs, num_silence, rules, num_rules);
+  if (rc) return rc;
+  r->endpointing = num_rules > 0;
+  return 0;
+}
+
+int pk_mi355_online_recognizer_num_utterances(const pk_mi355_online_recognizer_t *r, int slot) {
+  const int rc = CheckSlot(r, slot);
+  if (rc) return rc;
+  return (int)r->pieces[slot].size();
+}
+
+int pk_mi355_online_recognizer_utterance(const pk_mi355_online_recognizer_t *r, int slot, int i, pk_mi355_utterance_t *out) {
+  const pk_mi355_online_recognizer::Piece *p = PieceOf(r, slot, i);
+  if (!p) return PK_MI355_E_INVALID;
+  if (out) *out = p->info;
+  return 0;
+}
+
+const char *pk_mi355_online_recognizer_utterance_hyp(const pk_mi355_online_recognizer_t *r, int slot, int i) {
+  const pk_mi355_online_recognizer::Piece *p = PieceOf(r, slot, i);
+  return p ? p->hyp.c_str() : nullptr;
+}
+
+int pk_mi355_online_recognizer_utterance_words(const pk_mi355_online_recognizer_t *r, int slot, int i, int *words, int max) {
+  const pk_mi355_online_recognizer::Piece *p = PieceOf(r, slot, i);
+  if (!p) return PK_MI355_E_INVALID;
+  for (int k = 0; words && k < (int)p->words.size() && k < max; ++k) words[k] = p->words[k];
+  return (int)p->words.size();
+}
+
+int pk_mi355_online_recognizer_utterance_word_segments(const pk_mi355_online_recognizer_t *r, int slot, int i,
+                                                       pk_mi355_word_t *out, int max) {
+  const pk_mi355_online_recognizer::Piece *p = PieceOf(r, slot, i);
+  if (!p) return PK_MI355_E_INVALID;
+  for (int k = 0; out && k < (int)p->segments.size() && k < max; ++k) out[k] = p->segments[k];
+  return (int)p->segments.size();
 }
 
 const char *pk_mi355_online_recognizer_partial(const pk_mi355_online_recognizer_t *r, int slot) {

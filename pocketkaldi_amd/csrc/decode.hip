@@ -760,6 +760,108 @@ __global__ void __launch_bounds__(kDecThreads) OnlineDecodeKernel(DecArgs A, con
     states[u] = st;
   }
 }
+
+// ================================================================== endpointing (pk_mi355_online_decoder_set_endpointing)
+// After OnlineDecodeKernel on the same stream, over the same calls, one workgroup per call entry: what the endpoint
+// rules need of a slot that is still live (its launch was not final, status == 0, ok, nL > 0); any other slot gets
+// valid = 0.  A kernel of its own, so that the decode kernels' code is the same with the mode on, off or never built.
+//   * relative cost: over the slot's token list as the decode launch left it, m_best = min (double)cost and
+//     m_fin = min (double)cost + (double)final over the tokens where that sum is not INFINITY (BestPath's test);
+//     relative_cost = (float)(m_fin - m_best), +inf without a final token.
+//   * trailing silence: over the best token's path as the decode launch wrote it (behind the newly committed arcs with
+//     commit on), in chunks of the workgroup's width: a wave ballots "emits" and "emits a non-silence pdf", its lane 0
+//     leaves (emitting arcs, has a non-silent one, emitting arcs after the last non-silent one) in LDS, and every thread
+//     folds the waves in path order into the carry (frames, silence run, still open).
+// Every arc id is checked against the table before it indexes it, and the slice's lengths against the slot's capacity.
+__global__ void __launch_bounds__(kDecThreads) EndpointKernel(EndpointArgs E) {
+  __shared__ Shared sh;
+  __shared__ int s_wave[kDecWaves][3];
+  __shared__ int s_bad;
+  if ((int)blockIdx.x >= E.n) return;
+  const OnlineCall call = E.calls[blockIdx.x];
+  const int u = call.slot;
+  const OnlineState st = E.states[u];
+  const OnlineResult r = E.results[u];
+  EndpointRecord o;
+  o.valid = 0; o.status = 0; o.num_final = 0; o.tail_silence = 0; o.tail_open = 0; o.tail_frames = 0;
+  o.best_cost = 0.f; o.final_cost = 0.f; o.relative_cost = 0.f; o.pad = 0;
+  const bool live = !call.final_ && !st.status && st.ok && st.nL > 0 && st.nL <= E.num_states;
+  if (!live) {                                          // (the same verdict in every thread)
+    if (threadIdx.x == 0) E.out[u] = o;
+    return;
+  }
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  // ---- the best token and the best final token
+  const Tok *L = (st.par ? E.lb : E.la) + (size_t)E.num_states * u;
+  double m_best = INFINITY, m_fin = INFINITY;
+  int finals = 0;
+  for (int i = threadIdx.x; i < st.nL; i += kDecThreads) {
+    const Tok tk = L[i];
+    if (tk.state < 0 || tk.state >= E.num_states) { s_bad = 1; continue; }
+    const double c = (double)tk.cost;
+    m_best = fmin(m_best, c);
+    const double f = c + (double)E.final_w[tk.state];
+    if (f != INFINITY) { m_fin = fmin(m_fin, f); ++finals; }
+  }
+  m_best = BlockMinD(sh, m_best);
+  m_fin = BlockMinD(sh, m_fin);
+  int num_final;
+  BlockScan(sh, finals, &num_final);
+  // ---- the silence at the end of the best token's path
+  const int nc = E.commit_len ? E.commit_len[u] : 0;
+  const bool inside = nc >= 0 && r.path_len >= 0 && (int64_t)nc + r.path_len <= E.cap;
+  int frames = 0, run = 0, open = 1;
+  if (inside) {
+    const int *path = E.path + (int64_t)u * E.cap + nc;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < r.path_len; c0 += kDecThreads) {
+      const int i = c0 + threadIdx.x;
+      int pdf = -1;
+      if (i < r.path_len) {
+        const int arc = path[i];
+        if (arc >= 0 && arc < E.num_arcs) pdf = E.arc_pdf[arc];
+        else s_bad = 1;
+      }
+      const int emits = pdf >= 0;
+      int silent = 0;
+      if (emits) {
+        if (pdf < E.num_pdfs) silent = (E.silence[pdf >> 5] >> (pdf & 31)) & 1u;
+        else s_bad = 1;
+      }
+      const unsigned long long em = __ballot(emits), nm = __ballot(emits && !silent);
+      if (lane == 0) {
+        // (the lanes above the last non-silent one: bits last + 1 .. 63)
+        const int last = nm ? 63 - __clzll((long long)nm) : -1;
+        const unsigned long long after = last < 0 ? em : last == 63 ? 0ull : em & (~0ull << (last + 1));
+        s_wave[wv][0] = __popcll(em);
+        s_wave[wv][1] = nm != 0;
+        s_wave[wv][2] = __popcll(after);
+      }
+      __syncthreads();
+      for (int k = 0; k < kDecWaves; ++k) {
+        frames += s_wave[k][0];
+        if (s_wave[k][1]) { run = s_wave[k][2]; open = 0; }
+        else run += s_wave[k][2];
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (!inside || s_bad) {
+      o.status = PK_MI355_E_DEVICE;
+    } else {
+      o.valid = 1;
+      o.num_final = num_final;
+      o.tail_silence = run; o.tail_open = open; o.tail_frames = frames;
+      o.best_cost = (float)m_best;
+      o.final_cost = num_final ? (float)m_fin : INFINITY;
+      o.relative_cost = num_final ? (float)(m_fin - m_best) : INFINITY;
+    }
+    E.out[u] = o;
+  }
+}
 }  // namespace
 
 // ================================================================== launchers (pk_decode.h)
@@ -791,6 +893,10 @@ void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *
   } else {
     if (A.rec_ac && A.path_ac) launch(OnlineDecodeKernel<true, false>); else launch(OnlineDecodeKernel<false, false>);
   }
+}
+
+void LaunchEndpoint(const EndpointArgs &E, hipStream_t stream) {
+  hipLaunchKernelGGL(EndpointKernel, dim3(E.n), dim3(kDecThreads), 0, stream, E);
 }
 
 }  // namespace pkmi

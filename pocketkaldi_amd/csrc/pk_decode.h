@@ -88,6 +88,28 @@ struct OnlineCall {       // one slot of a launch
   int64_t ll_off;
 };
 
+struct EndpointRecord {   // what EndpointKernel says of one slot after a launch (pk_mi355_online_decoder_set_endpointing)
+  int valid;              // 0: the slot finished, ended or holds no token -- nothing else is meaningful
+  int status;             // 0, or PK_MI355_E_DEVICE: an arc id or a length of the slot's path is out of range
+  int num_final;          // tokens whose cost + final weight is not INFINITY
+  int tail_silence;       // emitting arcs of the scanned path after its last non-silent emitting arc
+  int tail_open;          // the scanned path has no non-silent emitting arc
+  int tail_frames;        // emitting arcs of the scanned path
+  float best_cost, final_cost, relative_cost;
+  int pad;
+};
+
+struct EndpointArgs {
+  const OnlineCall *calls; const OnlineState *states; const OnlineResult *results;   // of the decode launch before it
+  int n;
+  const Tok *la, *lb; int num_states;                  // the slots' two token lists (DecArgs), stride num_states
+  const float *final_w;
+  const int *path; int64_t cap; const int *commit_len; // the slots' path slices; commit_len: null with commit off
+  const int *arc_pdf; int num_arcs;                    // by original arc id: the pdf, -1 for an epsilon arc
+  const uint32_t *silence; int num_pdfs;               // bit p of the mask: pdf p is silence
+  EndpointRecord *out;                                 // per slot
+};
+
 // ------------------------------------------------------------------ launchers (decode.hip)
 // One workgroup per utterance (slot) of A.num_utts (n); a frame's log-likelihood row is the dynamic LDS.
 
@@ -100,6 +122,8 @@ void LaunchAlign(const AlignArgs &A, hipStream_t stream);
 // the new frames of n slots (calls; states and results are per slot): OnlineDecodeKernel<A.rec_ac && A.path_ac, A.commit_len>
 void LaunchOnlineDecode(const DecArgs &A, const OnlineCall *calls, OnlineState *states, OnlineResult *results, int n,
                         hipStream_t stream);
+// after LaunchOnlineDecode on the same stream, over the same calls: EndpointKernel, one record per slot of the call
+void LaunchEndpoint(const EndpointArgs &E, hipStream_t stream);
 
 }  // namespace pkmi
 

@@ -496,4 +496,26 @@ const char *pk_mi355_symtab_get(const pk_mi355_symtab_t *st, int id) {
   return st->buffer.data() + st->index[id];
 }
 
+// ---- endpoint rules (pk_mi355_online_decoder_set_endpointing): the usual five at a 10 ms frame shift, and their test
+
+int pk_mi355_endpoint_default_rules(pk_mi355_endpoint_rule_t *rules, int max) {
+  const pk_mi355_endpoint_rule_t usual[5] = {
+      {0, 500, INFINITY, 0}, {1, 50, 2.0f, 0}, {1, 100, 8.0f, 0}, {1, 200, INFINITY, 0}, {0, 0, INFINITY, 2000}};
+  for (int i = 0; rules && i < 5 && i < max; ++i) rules[i] = usual[i];
+  return 5;
+}
+
+int pk_mi355_endpoint_eval(const pk_mi355_endpoint_rule_t *rules, int num_rules, int frames, int trailing_silence_frames,
+                           float relative_cost) {
+  if (!rules || frames <= 0) return 0;
+  const bool contains_nonsilence = frames > trailing_silence_frames;
+  for (int i = 0; i < num_rules; ++i) {
+    const pk_mi355_endpoint_rule_t &r = rules[i];
+    if ((contains_nonsilence || !r.must_contain_nonsilence) && trailing_silence_frames >= r.min_trailing_silence_frames &&
+        relative_cost <= r.max_relative_cost && frames >= r.min_utterance_frames)
+      return i + 1;
+  }
+  return 0;
+}
+
 }  // extern "C"

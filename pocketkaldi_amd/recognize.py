@@ -1,7 +1,8 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
-                                        [--online [--chunk-ms N] [--partials] [--commit]]
+                                        [--online [--chunk-ms N] [--partials] [--commit]
+                                         [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
 that does not end in .wav is a list of wave files, one per line (main.cc:34-46); its waves are decoded together, as
@@ -20,6 +21,11 @@ also prints every changed partial hypothesis to stderr: "<file>\t<seconds of aud
 --partials without --online are refused with the usage text, as is --commit.  --commit turns the online decoder's commit
 mode on (streams of any length; pk_mi355_online_decoder_set_commit): stdout is unchanged, and every --partials line gains
 a fourth tab field, the stable text -- the words of the partial that no later audio can change.
+
+--endpoint-silence P,Q,... (with --online) turns endpointing on with these pdfs as silence: a wave is cut into utterances
+where an endpoint rule fires, and stdout has one line per utterance, "<file>[<start s>-<end s>]\t<sentence>\t<llpf>";
+with --ctm the word times are offset by the utterance's start.  The rules are the usual five unless --endpoint-rule gives
+others, one "must_contain_nonsilence,min_trailing_silence_s,max_relative_cost,min_utterance_length_s" each (inf allowed).
 """
 import sys
 
@@ -33,15 +39,17 @@ RESERVE = 32
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
-          "[--online [--chunk-ms N] [--partials] [--commit]]")
+          "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
     return 1
 
 
-def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None):
+def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, endpoint=None,
+                     pieces=None):
     """Every wave through a slot of an OnlineRecognizer, `chunk_ms` milliseconds per step, MAX_UTTS waves at a time.
+    endpoint: (silence pdfs, rules or None) turns endpointing on; pieces[u] is then wave u's list of Utterance.
     -> (the results in order, the symbol names by word id)"""
     rates = rates or [16000] * len(waves)
     # a step's capacity counts 16 kHz samples; a converted slot also counts the few a close would add (RESERVE)
@@ -51,12 +59,14 @@ def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, part
     try:
         if commit:
             rec.decoder.set_commit(True)
-        return stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit, rates)
+        if endpoint:
+            rec.set_endpointing(*endpoint)
+        return stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit, rates, pieces)
     finally:
         rec.destroy()
 
 
-def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None):
+def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, pieces=None):
     rates = rates or [16000] * len(waves)
     if reference_softmax:
         rec.am.set_softmax("reference")
@@ -87,8 +97,11 @@ def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commi
                     shown[u] = text
             for u in closing:
                 results[u] = rec.result(u - first)
+                if pieces is not None:
+                    pieces[u] = rec.utterances(u - first)
                 live.discard(u)
-    names = {s.word: rec.symbols[s.word] for r in results for s in r.segments if s.word != 0}
+    every = results + [p.result for u in (pieces or {}) for p in pieces[u]]
+    names = {s.word: rec.symbols[s.word] for r in every for s in r.segments if s.word != 0}
     return results, names
 
 
@@ -114,6 +127,21 @@ def main(argv):
         if channel < 0:
             return usage()
         del argv[at:at + 2]
+    endpoint, rules = None, []
+    try:
+        while "--endpoint-rule" in argv:
+            at = argv.index("--endpoint-rule")
+            must, trail, cost, length = argv[at + 1].split(",")
+            rules.append(pk.EndpointRule(int(must) != 0, float(trail), float(cost), float(length)))
+            del argv[at:at + 2]
+        if "--endpoint-silence" in argv:
+            at = argv.index("--endpoint-silence")
+            endpoint = ([int(p) for p in argv[at + 1].split(",") if p], rules or None)
+            del argv[at:at + 2]
+    except (IndexError, ValueError):
+        return usage()
+    if (endpoint or rules) and (endpoint is None or "--online" not in argv):
+        return usage()
     flags = [a for a in argv if a.startswith("--")]
     args = [a for a in argv if not a.startswith("--")]
     if len(args) != 2 or len(args[1]) < 4 or set(flags) - {"--ctm", "--reference-softmax", "--online", "--partials", "--commit"}:
@@ -121,7 +149,7 @@ def main(argv):
     if ("--partials" in flags or "--commit" in flags) and "--online" not in flags:
         return usage()
     model_file, input_file = args
-    rec = None
+    rec, pieces = None, {}
     try:
         if input_file.endswith(".wav"):
             files = [input_file]
@@ -135,7 +163,8 @@ def main(argv):
             rates.append(rate)
         if "--online" in flags:
             results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
-                                              "--partials" in flags, "--commit" in flags, rates)
+                                              "--partials" in flags, "--commit" in flags, rates, endpoint,
+                                              pieces if endpoint else None)
         else:
             sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
@@ -147,7 +176,18 @@ def main(argv):
     except (pk.PkError, OSError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
-    for name, r in zip(files, results):
+    for u, name in enumerate(files if endpoint else []):       # one line per utterance; word times from the wave's start
+        for p in pieces[u]:
+            if "--ctm" in flags:
+                for s in p.result.segments:
+                    if s.word != 0:
+                        print("%s 1 %.2f %.2f %s" % (name, (p.first_frame + s.start_frame) * FRAME_SHIFT,
+                                                     s.num_frames * FRAME_SHIFT, names[s.word]))
+            else:
+                sys.stdout.write("%s[%.2f-%.2f]\t%s\t%f\n" % (name, p.first_frame * FRAME_SHIFT,
+                                                               (p.first_frame + p.num_frames) * FRAME_SHIFT, p.result.text,
+                                                               p.result.loglikelihood_per_frame))
+    for name, r in zip([] if endpoint else files, results):
         if "--ctm" in flags:
             for s in r.segments:
                 if s.word != 0:

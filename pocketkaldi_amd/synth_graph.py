@@ -109,6 +109,54 @@ def planted(graph, num_frames, seed, bonus=8.0, noise=3.0, num_pdfs=None):
     return ll, seq
 
 
+def silence_pdfs(graph):
+    """The pdfs of word_loop(silence=True)'s silence word (phone 0): the transition ids of its three HMM states."""
+    return sorted(tid(0, k, loop) for k in range(3) for loop in (False, True))
+
+
+def planted_pauses(graph, num_frames, seed, pause_frames, words_between=2, lead=0, bonus=8.0, noise=3.0, num_pdfs=None):
+    """planted() for endpointing, on a word_loop(silence=True) graph: `lead` frames of the silence word, then runs of
+    `words_between` planted words (never the silence word), each run followed by a stretch of the silence word of
+    pause_frames[i % len(pause_frames)] frames (>= 3: one per HMM state, the rest self-loops spread over the three),
+    until there are num_frames frames or more.  The last stretch returns to the loop state.
+    -> (loglik float32, words, pauses [(first frame, frames)])."""
+    rng = np.random.default_rng(seed)
+    n = int(num_pdfs or graph["num_tids"])
+    sil = max(graph["words"])
+    assert graph["words"][sil] == [0], "the graph has no silence word"
+    ids = [w for w in sorted(graph["words"]) if w != sil]
+    seq, frames, pauses = [], [], []
+
+    def stretch(total):
+        assert total >= 3
+        d = [1 + (total - 3) // 3 + (1 if k < (total - 3) % 3 else 0) for k in range(3)]
+        pauses.append((len(frames), total))
+        seq.append(sil)
+        for k in range(3):
+            frames.append(tid(0, k, False))
+            frames.extend([tid(0, k, True)] * (d[k] - 1))
+
+    if lead:
+        stretch(lead)
+    i = 0
+    while len(frames) < num_frames or not seq:
+        for _ in range(words_between):
+            w = int(rng.choice(ids))
+            seq.append(w)
+            for p in graph["words"][w]:
+                for k in range(3):
+                    d = int(rng.integers(1, 4))
+                    frames.append(tid(p, k, False))
+                    frames.extend([tid(p, k, True)] * (d - 1))
+        stretch(int(pause_frames[i % len(pause_frames)]))
+        i += 1
+    T = len(frames)
+    ll = (-2.0 - noise * np.abs(rng.standard_normal((T, n)))).astype(np.float32)
+    for t, pdf in enumerate(frames):
+        ll[t, pdf] += np.float32(bonus)
+    return ll, seq, pauses
+
+
 def flat(num_frames, num_pdfs, seed, spread=0.05):
     """Nearly flat log-likelihoods: everything stays inside the beam (max-active binds)."""
     rng = np.random.default_rng(seed)

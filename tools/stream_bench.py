@@ -25,6 +25,12 @@ step is then push + score + pk_mi355_online_decoder_advance + every live stream'
 --commit (implies --decode) turns the decoder's commit mode on.  The long-stream leg is
     python tools/stream_bench.py --streams 32 --seconds 120 --decode [--commit] --out <file>
 run with the mode off, on, off, on, each in a process of its own (profiles/stream_commit.json holds the four records).
+
+--endpoint (implies --decode) turns endpointing on, the word loop's silence pdfs and the usual five rules: after every
+advance every stream's endpoint() is read, and the streams whose rule fired are finished in one call and opened again.
+window_ms gains `endpoint`, the time of those reads and cuts, and the record `endpoint.cuts`.  What the mode costs is
+`advance` (the second kernel and the copy of its records are inside the synchronous advance) plus `endpoint`, against a
+run without the flag: profiles/stream_endpoint.json.
 """
 import argparse
 import json
@@ -50,9 +56,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "stream_bench.json"))
     ap.add_argument("--decode", action="store_true")
     ap.add_argument("--commit", action="store_true")
+    ap.add_argument("--endpoint", action="store_true")
     ap.add_argument("--trace-capacity", type=int, default=0)
     a = ap.parse_args()
-    a.decode = a.decode or a.commit
+    a.decode = a.decode or a.commit or a.endpoint
 
     pk.set_device(0)
     layers, prior, L, R = synth.model("S")
@@ -73,8 +80,12 @@ def main():
         dec = pk.OnlineDecoder(fst, am, a.streams, trace_capacity=a.trace_capacity)
         dec.set_beam(16.0, 2000)
         dec.set_commit(a.commit)
+        if a.endpoint:
+            dec.set_endpointing(synth_graph.silence_pdfs(graph))
 
     cores = []                               # --decode: a step's time up to the end of advance
+    ends = []                                # ... and up to the end of the endpoint reads and cuts
+    cuts = [0]
 
     def run(record, nsteps=nsteps):
         for s in range(a.streams):
@@ -83,6 +94,8 @@ def main():
                 dec.open(s)
         walls, frames, rows0 = [], 0, []
         del cores[:]
+        del ends[:]
+        cuts[0] = 0
         for k in range(nsteps + 1):
             t0 = time.perf_counter()
             for s in range(a.streams):
@@ -94,6 +107,14 @@ def main():
             if dec:
                 dec.advance(sc)
                 cores.append(time.perf_counter() - t0)
+                if a.endpoint and k < nsteps:
+                    fired = [s for s in range(a.streams) if dec.endpoint(s).rule]
+                    if fired:
+                        dec.finish(fired)
+                        for s in fired:
+                            dec.open(s)
+                        cuts[0] += len(fired)
+                ends.append(time.perf_counter() - t0)
                 if k < nsteps:
                     for s in range(a.streams):
                         dec.partial(s)
@@ -136,7 +157,11 @@ def main():
                           "trace_capacity": int(stats[0][2])}
         cores_ms = np.array(cores) * 1e3
         window = lambda x: {"first_10s": float(np.median(x[:per_window])), "last_10s": float(np.median(x[-1 - per_window:-1]))}
-        rec["window_ms"] = {"step": window(walls_ms), "advance": window(cores_ms), "partial": window(walls_ms - cores_ms)}
+        ends_ms = np.array(ends) * 1e3
+        rec["window_ms"] = {"step": window(walls_ms), "advance": window(cores_ms), "partial": window(walls_ms - ends_ms)}
+        if a.endpoint:
+            rec["window_ms"]["endpoint"] = window(ends_ms - cores_ms)
+            rec["endpoint"] = {"silence_pdfs": synth_graph.silence_pdfs(graph), "rules": "the usual five", "cuts": cuts[0]}
         rec["trace"] = {"peak_max": int(max(p for _, p, _ in stats)), "in_use_end_max": int(max(i for i, _, _ in stats)),
                         "committed_arcs_max": int(max(dec.committed(s)[1] for s in range(a.streams))),
                         "committed_arcs_min": int(min(dec.committed(s)[1] for s in range(a.streams))),
