@@ -325,6 +325,31 @@ int pk_mi355_batch_set_waves_i16(pk_mi355_batch_t *b, const int16_t *samples,
 int pk_mi355_batch_set_waves_device(pk_mi355_batch_t *b, const float *d_samples,
                                     const int *num_samples, int num_utts);
 
+/* ---- Features instead of audio.  Everything behind the set_* call -- score, synchronize,
+ * calibrate, fetch, fetch_all, gather_loglik, loglik_device, timing, pk_mi355_decoder_decode_batch -- sees a batch
+ * of num_utts utterances of T_u frames, whatever it was fed.  (Named with a prefix of their own, as
+ * pk_mi355_resample_set_waves is: they are batch entries with another source in front.)                          */
+#define PK_MI355_FEATS_NORMALIZED 0   /* ready for the splice, as pk_decodable_init takes them */
+#define PK_MI355_FEATS_RAW        1   /* raw 40-dim log-mel fbank: the sliding-window CMVN is applied first */
+
+/* A batch scorer without a front-end.  Any model (any feat_dim; F16X3 / F16: a multiple of 8, as pk_decodable_init).
+ * global_stats41 may be NULL; given (41 floats, feat_dim must be 40) it enables PK_MI355_FEATS_RAW.  Capacity in
+ * frames, not samples.  The wave entries fail with PK_MI355_E_STATE on such a batch.                             */
+pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41,
+                                                 int max_utts, int64_t max_total_frames);
+/* feats[u]: nrow = feat_dim, ncol = T_u, memory [T_u][feat_dim] (the pk_matrix_t image pk_decodable_init takes);
+ * copied to HBM.  T_u = 0 is an utterance without rows.  Also on a batch made by pk_mi355_batch_create (feat_dim 40,
+ * both kinds, capacity: the frames its sample capacity can produce, max_total_samples / 160 + max_utts); a later
+ * set_waves* switches such a batch back to audio.  PK_MI355_E_INVALID, before anything is copied or launched: a null
+ * argument, nrow != feat_dim, a negative ncol, an unknown kind, RAW without statistics or with feat_dim != 40, more
+ * utterances, frames or columns than the capacity; the batch keeps what it held.                                  */
+int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num_utts, int kind);
+/* Same, features already in HBM, utterance after utterance, [sum T][feat_dim] (4-byte aligned).  NORMALIZED: not
+ * copied, must stay valid until scored.  RAW: one device-to-device copy on the batch's stream.                   */
+int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, const int *num_frames,
+                                       int num_utts, int kind);
+int pk_mi355_features_dim(const pk_mi355_batch_t *b);
+
 /* Run fbank -> CMVN -> nnet -> log-likelihood tail for the current utterances.
  * Asynchronous on the batch's stream unless sync != 0.  Results stay in HBM.     */
 int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync);
@@ -360,8 +385,10 @@ int pk_mi355_batch_fetch(pk_mi355_batch_t *b, int utt, pk_decodable_t *out);
  * pk_mi355_batch_synchronize then returns PK_MI355_E_RANGE the results are withheld -- pk_decodable_loglikelihood
  * on those views returns NaN from then on (do not read log_prob.data of views whose synchronize failed).      */
 int pk_mi355_batch_fetch_all(pk_mi355_batch_t *b, pk_decodable_t *out, int num_out, int sync);
-/* Intermediate stages, for parity tests: raw fbank / CMVN'd features of utt,
- * copied to host as [T][40].                                                     */
+/* Intermediate stages, for parity tests: raw fbank / CMVN'd features of utt, copied to host as [T][40] /
+ * [T][feat_dim].  fetch_cmvn returns what the first layer reads: after pk_mi355_features_set(NORMALIZED) the input itself,
+ * bit for bit.  fetch_fbank after pk_mi355_features_set(RAW) returns the input; after NORMALIZED there is no fbank:
+ * PK_MI355_E_STATE.                                                                                           */
 int pk_mi355_batch_fetch_fbank(pk_mi355_batch_t *b, int utt, float *out);
 int pk_mi355_batch_fetch_cmvn(pk_mi355_batch_t *b, int utt, float *out);
 /* Parity-test hook: the front-end's logf (fbank.cc:244-245 -> vector.cc:334-339 -> libm logf,
@@ -400,7 +427,7 @@ void *pk_mi355_batch_stream(pk_mi355_batch_t *b);
  * stream (enable before scoring).  Kinds index the arrays below.                 */
 enum {
   PK_MI355_K_FBANK = 0,
-  PK_MI355_K_CMVN = 1,
+  PK_MI355_K_CMVN = 1,       /* features: FeatureLayoutKernel after NORMALIZED (and no fbank launch) */
   PK_MI355_K_GEMM = 2,       /* all affine-layer launches */
   PK_MI355_K_TAIL = 3,       /* log-softmax / prior / scale */
   PK_MI355_K_OTHER = 4,
@@ -811,6 +838,9 @@ int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *wav
 /* Same, wave u sampled at rates[u] Hz (pk_mi355_resample_set_waves; rates == NULL: 16000 throughout).  Capacity and
  * every result -- frames, word times -- are those of the converted 16 kHz audio.                                  */
 int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_t *waves, const int *rates, int n);
+/* Same from features (pk_mi355_features_set on the recognizer's batch: its failures are this entry's); the
+ * results are read as after pk_mi355_recognizer_process.                                                        */
+int pk_mi355_recognizer_process_features(pk_mi355_recognizer_t *r, const pk_matrix_t *feats, int n, int kind);
 /* utt->hyp of the last process: the words' strings in spoken order joined by one space, no trailing space; "" for
  * an utterance without words (also one the decoder ended with ok = 0).  Valid until the next process.  NULL on
  * misuse.                                                                                                        */

@@ -328,6 +328,22 @@ class Recognizer {
   // throughout): the sample rate of every wave; the others are converted on the GPU (pk_mi355_recognizer_process_rates)
   Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out, const int *rates = nullptr) {
     const int rc = rates ? pk_mi355_recognizer_process_rates(r_, waves, rates, n) : pk_mi355_recognizer_process(r_, waves, n);
+    return Collect(rc, n, out);
+  }
+  // The same from features: feats[u] is utterance u's [T][feat_dim] matrix (nrow = feat_dim, ncol = T), kind
+  // PK_MI355_FEATS_RAW (40-dim log-mel fbank, the CMVN is applied) or PK_MI355_FEATS_NORMALIZED
+  Status ProcessFeatures(const pk_matrix_t *feats, int n, int kind, std::vector<Utterance> *out) {
+    return Collect(pk_mi355_recognizer_process_features(r_, feats, n, kind), n, out);
+  }
+  // The owned objects: beam, trace gc, softmax mode, calibration and the result getters are their entries
+  pk_mi355_am_t *am() const { return pk_mi355_recognizer_am(r_); }
+  pk_mi355_batch_t *batch() const { return pk_mi355_recognizer_batch(r_); }
+  pk_mi355_decoder_t *decoder() const { return pk_mi355_recognizer_decoder(r_); }
+  const pk_mi355_symtab_t *symbols() const { return pk_mi355_recognizer_symtab(r_); }
+  pk_mi355_recognizer_t *handle() const { return r_; }
+
+ private:
+  Status Collect(int rc, int n, std::vector<Utterance> *out) {
     if (rc != 0) return Status::FromLast(rc);
     if (out) {
       out->clear();
@@ -338,14 +354,6 @@ class Recognizer {
     }
     return Status();
   }
-  // The owned objects: beam, trace gc, softmax mode, calibration and the result getters are their entries
-  pk_mi355_am_t *am() const { return pk_mi355_recognizer_am(r_); }
-  pk_mi355_batch_t *batch() const { return pk_mi355_recognizer_batch(r_); }
-  pk_mi355_decoder_t *decoder() const { return pk_mi355_recognizer_decoder(r_); }
-  const pk_mi355_symtab_t *symbols() const { return pk_mi355_recognizer_symtab(r_); }
-  pk_mi355_recognizer_t *handle() const { return r_; }
-
- private:
   pk_mi355_recognizer_t *r_;
 };
 

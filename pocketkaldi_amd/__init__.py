@@ -131,6 +131,8 @@ EXPORTS = [
     "pk_mi355_online_recognizer_set_endpointing", "pk_mi355_online_recognizer_num_utterances",
     "pk_mi355_online_recognizer_utterance", "pk_mi355_online_recognizer_utterance_hyp",
     "pk_mi355_online_recognizer_utterance_words", "pk_mi355_online_recognizer_utterance_word_segments",
+    "pk_mi355_features_batch_create", "pk_mi355_features_set", "pk_mi355_features_set_device",
+    "pk_mi355_features_dim", "pk_mi355_recognizer_process_features",
 ]
 
 
@@ -365,6 +367,12 @@ def lib():
     L.pk_mi355_online_recognizer_utterance_words.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int]
     L.pk_mi355_online_recognizer_utterance_word_segments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(pk_mi355_word_t),
                                                                      C.c_int]
+    L.pk_mi355_features_batch_create.restype = C.c_void_p
+    L.pk_mi355_features_batch_create.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int64]
+    L.pk_mi355_features_set.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t), C.c_int, C.c_int]
+    L.pk_mi355_features_set_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int]
+    L.pk_mi355_features_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_recognizer_process_features.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t), C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -680,6 +688,32 @@ class _OwnedArray(np.ndarray):
         self._owner = getattr(obj, "_owner", None)
 
 
+FEATURE_KINDS = {"normalized": 0, "raw": 1}         # PK_MI355_FEATS_*
+
+
+def _feature_kind(kind):
+    if kind not in FEATURE_KINDS:
+        raise PkCodeError(-1, "feature kind %r (one of %s)" % (kind, ", ".join(sorted(FEATURE_KINDS))))
+    return FEATURE_KINDS[kind]
+
+
+def _feature_matrices(feats, feat_dim):
+    """A list of [T][feat_dim] arrays -> (pk_matrix_t array, the float32 arrays it borrows)."""
+    keep = []
+    for i, f in enumerate(feats):
+        try:
+            f = _f32(f)
+        except (TypeError, ValueError) as e:
+            raise PkCodeError(-1, "features %d are not a float matrix: %s" % (i, e))
+        if f.ndim != 2 or f.shape[1] != feat_dim:
+            raise PkCodeError(-1, "features %d have shape %s, expected [T][%d]" % (i, f.shape, feat_dim))
+        keep.append(f)
+    arr = (pk_matrix_t * max(len(keep), 1))()
+    for i, f in enumerate(keep):
+        arr[i] = _as_matrix(f)
+    return arr, keep
+
+
 class Decodable:
     """decodable.h:15-41 over the C ABI (what decoder.cc consumes)."""
 
@@ -778,6 +812,21 @@ class BatchScorer:
         self._keep = keep_alive
         _check(lib().pk_mi355_batch_set_waves_device(self._h, C.c_void_p(device_ptr), ns, len(num_samples)))
 
+    def feat_dim(self):
+        return lib().pk_mi355_features_dim(self._h)
+
+    def set_features(self, feats, kind="normalized"):
+        """Features instead of audio: one [T][feat_dim] matrix per utterance.  kind "normalized": ready for the splice
+        (what Decodable takes); "raw": 40-dim log-mel fbank, the sliding-window CMVN is applied first."""
+        arr, keep = _feature_matrices(feats, self.feat_dim())
+        _check_code(lib().pk_mi355_features_set(self._h, arr, len(keep), _feature_kind(kind)))
+
+    def set_features_device(self, device_ptr, num_frames, kind="normalized", keep_alive=None):
+        """Features already in HBM: device_ptr -> the utterances' rows one after the other, [sum T][feat_dim] floats."""
+        ns = (C.c_int * max(len(num_frames), 1))(*[int(n) for n in num_frames])
+        self._keep = keep_alive
+        _check_code(lib().pk_mi355_features_set_device(self._h, C.c_void_p(device_ptr), ns, len(num_frames), _feature_kind(kind)))
+
     def score(self, prob_scale=0.1, sync=True):
         _check(lib().pk_mi355_batch_score(self._h, float(prob_scale), 1 if sync else 0))
 
@@ -820,12 +869,13 @@ class BatchScorer:
 
     def fetch_fbank(self, utt):
         out = np.zeros((self.num_frames(utt), 40), dtype=np.float32)
-        _check(lib().pk_mi355_batch_fetch_fbank(self._h, utt, _fp(out)))
+        _check_code(lib().pk_mi355_batch_fetch_fbank(self._h, utt, _fp(out)))
         return out
 
     def fetch_cmvn(self, utt):
-        out = np.zeros((self.num_frames(utt), 40), dtype=np.float32)
-        _check(lib().pk_mi355_batch_fetch_cmvn(self._h, utt, _fp(out)))
+        """What the first layer reads, [T][feat_dim]."""
+        out = np.zeros((self.num_frames(utt), self.feat_dim()), dtype=np.float32)
+        _check_code(lib().pk_mi355_batch_fetch_cmvn(self._h, utt, _fp(out)))
         return out
 
     def gather_loglik(self, utt, d_frames, d_trans_ids, n, d_out):
@@ -841,6 +891,23 @@ class BatchScorer:
         n = (C.c_int * 5)()
         _check(lib().pk_mi355_batch_get_timing(self._h, ms, n))
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KINDS)}
+
+
+class FeatureScorer(BatchScorer):
+    """A BatchScorer without a front-end, fed by set_features / set_features_device: any model (any feature
+    dimension), capacity in frames.  global_stats (41 floats, 40-dim models) enables kind "raw"."""
+
+    def __init__(self, am, max_utts, max_total_frames, global_stats=None):
+        g = None
+        if global_stats is not None:
+            g = _f32(global_stats)
+            if g.shape != (41,):
+                raise PkError("global_stats must have 41 entries")
+        self._am = am
+        self._h = lib().pk_mi355_features_batch_create(am.handle, None if g is None else _fp(g), int(max_utts), int(max_total_frames))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self._keep = None
 
 
 class OnlineScorer:
@@ -1347,11 +1414,36 @@ class Recognizer:
             _check_code(lib().pk_mi355_recognizer_process(self._h, arr, len(waves)))
         else:
             _check_code(lib().pk_mi355_recognizer_process_rates(self._h, arr, _rates_array(rates, len(waves)), len(waves)))
+        return self._results(len(waves))
+
+    def _results(self, n):
         out = []
-        for u in range(len(waves)):
+        for u in range(n):
             words, weight, ok = self.decoder.result(u)
             out.append(Result(lib().pk_mi355_recognizer_hyp(self._h, u).decode(), words, weight, ok,
                               lib().pk_mi355_recognizer_loglikelihood_per_frame(self._h, u), self.decoder.word_segments(u)))
+        return out
+
+    def process_features(self, feats, kind="raw"):
+        """pk_process from features: one [T][feat_dim] matrix per utterance (kind: as BatchScorer.set_features).  A list
+        that does not fit max_utts or the frames the recognizer holds is split into as many calls as it needs; a
+        single matrix that cannot fit is refused."""
+        code = _feature_kind(kind)
+        arr, keep = _feature_matrices(feats, self.batch.feat_dim())
+        cap = self.max_total_samples // 160 + self.max_utts       # the frames pk_mi355_batch_create makes room for
+        for i, f in enumerate(keep):
+            if f.shape[0] > cap:
+                raise PkCodeError(-1, "features %d have %d frames, the recognizer holds %d" % (i, f.shape[0], cap))
+        out, first, frames = [], 0, 0
+        for i in range(len(keep) + 1):
+            if i == len(keep) or i - first == self.max_utts or frames + keep[i].shape[0] > cap:
+                if i > first:
+                    sub = (pk_matrix_t * (i - first))(*[arr[j] for j in range(first, i)])
+                    _check_code(lib().pk_mi355_recognizer_process_features(self._h, sub, i - first, code))
+                    out += self._results(i - first)
+                first, frames = i, 0
+            if i < len(keep):
+                frames += keep[i].shape[0]
         return out
 
     def process(self, waves, rates=None):

@@ -1,5 +1,6 @@
 // capi_batch.hip -- the scorer core (pk_score.h) and the batched, device-resident scorer over it (PCM in HBM ->
-// fbank -> CMVN -> layer stack -> log-likelihoods in HBM), the page-locked result arenas and the decodable views handed
+// fbank -> CMVN -> layer stack -> log-likelihoods in HBM; or features in at the CMVN or at the layer stack, DESIGN.md
+// section 12), the page-locked result arenas and the decodable views handed
 // out over them, and the acoustic half of pk_process (pocketkaldi.cc:186-218).  Host C++ over the HIP runtime.
 #include <hip/hip_runtime.h>
 
@@ -151,6 +152,14 @@ struct pk_mi355_batch {
   int16_t *d_wave_i16 = nullptr;    // owned int16 buffer
   const float *wave_f32 = nullptr;  // what the kernels read (owned or external)
   const int16_t *wave_i16 = nullptr;
+  // What the last set_* call handed over, and so what score starts from: audio (fbank, CMVN, layers), raw fbank
+  // features in d_raw (CMVN, layers) or normalised features at `feats` (FeatureLayoutKernel, layers).
+  enum Source { kNone, kWaves, kRaw, kNormalized };
+  Source source = kNone;
+  bool features_only = false;       // made by pk_mi355_features_batch_create: no PCM capacity, the wave entries are refused
+  bool have_stats = false;          // the CMVN tables and d_raw exist (always, for a wave batch)
+  float *d_feats = nullptr;         // owned [max_frames][feat_dim] staging of set_features(NORMALIZED), made on first use
+  const float *feats = nullptr;     // normalised features, frame-major (d_feats or the caller's device pointer)
   // pk_mi355_resample_set_waves: the utterances that are not at 16 kHz wait here at their own rate, page-locked and
   // on the device (both made and grown on demand), and are converted straight into d_wave
   Resampler resampler;
@@ -199,8 +208,25 @@ struct pk_mi355_batch {
 
 namespace {
 
-int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
-  if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+// Frames and columns (every utterance with its context pads) against the batch's capacity.
+int FramesFit(const pk_mi355_batch *b, const int *frames, int num_utts) {
+  const int pad = b->core.am->left + b->core.am->right;
+  int64_t raw = 0, col = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    raw += frames[u];
+    col += frames[u] > 0 ? frames[u] + pad : 0;
+  }
+  if (raw > b->core.max_frames || RoundUp(col, kTile) > b->core.max_cols)
+    return Fail(PK_MI355_E_INVALID, "frame capacity exceeded (%lld frames, %lld columns; the batch holds %lld and %lld)", (long long)raw,
+                (long long)RoundUp(col, kTile), (long long)b->core.max_frames, (long long)b->core.max_cols);
+  return 0;
+}
+
+// The layout of a call, from the utterances' frame counts: placement in the raw rows and in Yt, compact rows, shift4,
+// the capacity checks and the dirty_cols rule.  num_samples: the PCM behind the frames (null for features).  The
+// counts have been checked (utterances, no negative one, PCM capacity); nothing changes when the frames do not fit.
+int SetLayoutFrames(pk_mi355_batch *b, const int *frames, const int *num_samples, int num_utts) {
+  if (int rc = FramesFit(b, frames, num_utts)) return rc;
   ScorerCore &c = b->core;
   const int pad = c.am->left + c.am->right;
   int64_t woff = 0, raw = 0, col = 0;
@@ -208,21 +234,18 @@ int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
   b->h_pad_base.resize(num_utts); b->h_T.resize(num_utts);
   b->max_T = 0;
   for (int u = 0; u < num_utts; ++u) {
-    if (num_samples[u] < 0) return Fail(PK_MI355_E_INVALID, "negative sample count");
-    const int T = pk_mi355_num_frames(num_samples[u]);
+    const int T = frames[u];
     b->h_wave_off[u] = woff; b->h_raw_base[u] = raw; b->h_pad_base[u] = col; b->h_T[u] = T;
-    woff += num_samples[u];
+    woff += num_samples ? num_samples[u] : 0;
     raw += T;
     col += T > 0 ? T + pad : 0;
     b->max_T = std::max(b->max_T, T);
   }
-  if (woff > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples (%lld > %lld)", (long long)woff, (long long)b->max_samples);
-  if (raw > c.max_frames || RoundUp(col, kTile) > c.max_cols) return Fail(PK_MI355_E_INVALID, "frame capacity exceeded");
   // Columns behind this layout's last one that an earlier, larger layout filled: the padded rows of the last tile
   // are computed from them, and in the f16 modes whatever they produce counts towards the range verdict (a loud
   // batch followed by a smaller healthy one must not fail on the loud one's leftovers).  Zero again.
   if (col < b->dirty_cols) {
-    HIP_TRY(hipMemset2DAsync(c.d_yt + col, sizeof(float) * c.ldy, 0, sizeof(float) * (size_t)(b->dirty_cols - col), kNumBins, c.stream));
+    HIP_TRY(hipMemset2DAsync(c.d_yt + col, sizeof(float) * c.ldy, 0, sizeof(float) * (size_t)(b->dirty_cols - col), c.am->feat_dim, c.stream));
     b->dirty_cols = col;
   }
   b->dirty_cols = std::max(b->dirty_cols, col);
@@ -252,6 +275,41 @@ int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
   HIP_TRY(hipMemcpyAsync(b->d_pad_base, b->h_pad_base.data(), sizeof(int64_t) * num_utts, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemcpyAsync(b->d_T, b->h_T.data(), sizeof(int32_t) * num_utts, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));   // the host vectors may be reused right away
+  return 0;
+}
+
+// The wave form: fbank's frame count for every utterance's samples (fbank.cc:35-42), then the layout of those frames.
+int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
+  if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+  std::vector<int> frames(num_utts);
+  int64_t total = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    if (num_samples[u] < 0) return Fail(PK_MI355_E_INVALID, "negative sample count");
+    frames[u] = pk_mi355_num_frames(num_samples[u]);
+    total += num_samples[u];
+  }
+  if (total > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples (%lld > %lld)", (long long)total, (long long)b->max_samples);
+  if (int rc = SetLayoutFrames(b, frames.data(), num_samples, num_utts)) return rc;
+  b->source = pk_mi355_batch::kWaves;
+  return 0;
+}
+
+// What both feature entries check before the device is touched (kind, and RAW's needs).
+int CheckFeatureKind(const pk_mi355_batch *b, int kind) {
+  if (kind != PK_MI355_FEATS_NORMALIZED && kind != PK_MI355_FEATS_RAW) return Fail(PK_MI355_E_INVALID, "unknown feature kind %d", kind);
+  if (kind == PK_MI355_FEATS_RAW && (!b->have_stats || b->core.am->feat_dim != kNumBins))
+    return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics and a %d-dim model (this batch: %s, %d-dim)", kNumBins,
+                b->have_stats ? "statistics" : "no statistics", b->core.am->feat_dim);
+  return 0;
+}
+int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts) {
+  if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+  for (int u = 0; u < num_utts; ++u)
+    if (frames[u] < 0) return Fail(PK_MI355_E_INVALID, "utterance %d has a negative frame count (%d)", u, frames[u]);
+  return FramesFit(b, frames, num_utts);
+}
+int WaveEntryAllowed(const pk_mi355_batch *b) {
+  if (b->features_only) return Fail(PK_MI355_E_STATE, "this batch was made by pk_mi355_features_batch_create: it takes features, not audio");
   return 0;
 }
 
@@ -292,20 +350,22 @@ void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats4
   c->chunk = std::min<int64_t>(chunk_cap, c->max_cols);
   c->zero_span = ZeroSpan(units, pad);
   c->ldy = RoundUp(c->max_cols, c->chunk) + 256 + c->zero_span;
-  FrontendTables host;
-  if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
-  CmvnTables ctab;
-  BuildCmvnTables(global_stats41[kNumBins], &ctab);
   auto table = [&](auto **d, const void *h, size_t bytes) {
     chk(hipMalloc(d, bytes));
     if (chk.ok) chk(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
   };
   chk(hipStreamCreate(&c->stream));
-  table(&c->d_tables, &host, sizeof(FrontendTables));
-  table(&c->d_global, global_stats41, sizeof(float) * (kNumBins + 1));
-  table(&c->d_cmvn_tab, &ctab, sizeof(CmvnTables));
-  chk(hipMalloc(&c->d_yt, sizeof(float) * c->ldy * kNumBins));
-  if (chk.ok) chk(hipMemset(c->d_yt, 0, sizeof(float) * c->ldy * kNumBins));   // the zero span at the end of feature row 0
+  if (global_stats41) {
+    FrontendTables host;
+    if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+    CmvnTables ctab;
+    BuildCmvnTables(global_stats41[kNumBins], &ctab);
+    table(&c->d_tables, &host, sizeof(FrontendTables));
+    table(&c->d_global, global_stats41, sizeof(float) * (kNumBins + 1));
+    table(&c->d_cmvn_tab, &ctab, sizeof(CmvnTables));
+  }
+  chk(hipMalloc(&c->d_yt, sizeof(float) * c->ldy * am->feat_dim));
+  if (chk.ok) chk(hipMemset(c->d_yt, 0, sizeof(float) * c->ldy * am->feat_dim));   // the zero span at the end of feature row 0
   chk(hipMalloc(&c->d_ll, sizeof(float) * c->max_cols * am->num_pdfs));
   if (chk.ok && AllocExec(am, c->chunk, &c->exec)) chk.ok = false;
 }
@@ -336,18 +396,21 @@ int pk_mi355_num_frames(int num_samples) {      // fbank.cc:35-42
   return 1 + (num_samples - kFrameLength) / kFrameShift;
 }
 
-pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
-  if (!global_stats41 || max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+}  // extern "C"
+
+namespace {
+// Both create entries, arguments checked: a batch of max_utts utterances and max_frames frames; max_total_samples PCM
+// samples (0: features only).  global_stats41 may be null for a features-only batch.
+pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples, int64_t max_frames) {
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
   b->max_utts = max_utts; b->max_samples = max_total_samples;
+  b->features_only = max_total_samples == 0;
+  b->have_stats = global_stats41 != nullptr;
   if (const char *e = getenv("PK_MI355_CHUNK")) if (atol(e) >= kTile) b->chunk_cap = RoundUp(atol(e), kTileF16);
   const int pad = am->left + am->right;
-  const int64_t max_frames = max_total_samples / kFrameShift + max_utts;
-  CreateCheck chk{"batch_create"};
+  CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
   CreateScorerCore(&c, am, global_stats41, max_utts, max_frames, max_frames, b->chunk_cap, chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
@@ -365,11 +428,13 @@ pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_s
     b->h_shift4.resize(Shift4Cap(c.max_cols));
     chk(hipMalloc(&b->d_shift4, sizeof(int32_t) * b->h_shift4.size()));
   }
-  const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
-  chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
-  if (chk.ok) chk(hipMemset(b->d_raw_alloc, 0, sizeof(float) * raw_floats));
-  if (chk.ok) b->d_raw = b->d_raw_alloc + kCmvnRawLead;
-  if (IsF16(am->precision)) chk(hipMalloc(&b->d_y2, sizeof(_Float16) * 2 * c.ldy * kNumBins));
+  if (b->have_stats) {
+    const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
+    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
+    if (chk.ok) chk(hipMemset(b->d_raw_alloc, 0, sizeof(float) * raw_floats));
+    if (chk.ok) b->d_raw = b->d_raw_alloc + kCmvnRawLead;
+  }
+  if (IsF16(am->precision)) chk(hipMalloc(&b->d_y2, sizeof(_Float16) * 2 * c.ldy * am->feat_dim));
   if (const char *e = getenv("PK_MI355_LANES")) b->lanes = atoi(e) >= 2 ? 2 : 1;
   if (c.max_cols <= c.chunk) b->lanes = 1;           // a single chunk has nothing to overlap with
   if (b->lanes == 2) {
@@ -381,6 +446,32 @@ pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_s
   if (!chk.ok) { pk_mi355_batch_destroy(b); return nullptr; }
   return b;
 }
+}  // namespace
+
+extern "C" {
+
+pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
+  if (!global_stats41 || max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  return CreateBatch(am, global_stats41, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts);
+}
+
+pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_frames) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (max_utts <= 0 || max_total_frames <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  if (global_stats41 && am->feat_dim != kNumBins) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
+    return nullptr;
+  }
+  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_decodable_init: the spliced view of the split copy needs whole 8-k chunks
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
+    return nullptr;
+  }
+  return CreateBatch(am, global_stats41, max_utts, 0, max_total_frames);
+}
+
+int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
 
 void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   if (!b) return;
@@ -390,7 +481,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   FreeExec(&b->exec2);
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
-  hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2);
+  hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
   hipFree(b->d_native);
@@ -402,6 +493,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
 
 int pk_mi355_batch_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, int num_utts) {
   if (!b || !waves) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = WaveEntryAllowed(b)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   std::vector<int> ns(num_utts);
   for (int u = 0; u < num_utts; ++u) ns[u] = waves[u].dim;
@@ -420,6 +512,7 @@ int pk_mi355_batch_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, int 
 
 int pk_mi355_resample_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, const int *rates, int num_utts) {
   if (!b || !waves) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = WaveEntryAllowed(b)) return rc;
   bool native = false;
   for (int u = 0; rates && u < num_utts; ++u) native = native || rates[u] != kSampleRate;
   if (!native) return pk_mi355_batch_set_waves(b, waves, num_utts);      // 16 kHz throughout: today's call, launch for launch
@@ -474,6 +567,7 @@ int pk_mi355_resample_set_waves(pk_mi355_batch_t *b, const pk_vector_t *waves, c
 int pk_mi355_batch_set_waves_i16(pk_mi355_batch_t *b, const int16_t *samples, const int *num_samples,
                                  int num_utts) {
   if (!b || !samples || !num_samples) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = WaveEntryAllowed(b)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   const int64_t total = TotalSamples(num_samples, num_utts);
   if (total > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples");
@@ -488,15 +582,63 @@ int pk_mi355_batch_set_waves_i16(pk_mi355_batch_t *b, const int16_t *samples, co
 int pk_mi355_batch_set_waves_device(pk_mi355_batch_t *b, const float *d_samples, const int *num_samples,
                                     int num_utts) {
   if (!b || !d_samples || !num_samples) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = WaveEntryAllowed(b)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   b->wave_f32 = d_samples;
   b->wave_i16 = nullptr;
   return SetLayout(b, num_samples, num_utts);
 }
 
+int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num_utts, int kind) {
+  if (!b || (num_utts > 0 && !feats)) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = CheckFeatureKind(b, kind)) return rc;
+  const int D = b->core.am->feat_dim;
+  std::vector<int> frames(std::max(num_utts, 0));
+  for (int u = 0; u < num_utts; ++u) {
+    if (feats[u].nrow != D) return Fail(PK_MI355_E_INVALID, "features of utterance %d have %d rows, the model expects %d", u, feats[u].nrow, D);
+    if (feats[u].ncol > 0 && !feats[u].data) return Fail(PK_MI355_E_INVALID, "features of utterance %d: null data", u);
+    frames[u] = feats[u].ncol;                          // (a negative one is named by CheckFeatureCounts)
+  }
+  if (int rc = CheckFeatureCounts(b, frames.data(), num_utts)) return rc;
+  if (int rc = UseDevice(b->core.device)) return rc;
+  // RAW: where FbankKernel would have written them; NORMALIZED: the staging FeatureLayoutKernel reads
+  float *dst = b->d_raw;
+  if (kind == PK_MI355_FEATS_NORMALIZED) {
+    if (!b->d_feats) HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * D));
+    dst = b->d_feats;
+  }
+  int64_t row = 0;
+  for (int u = 0; u < num_utts; ++u) {
+    if (frames[u] > 0)
+      HIP_TRY(hipMemcpyAsync(dst + row * D, feats[u].data, sizeof(float) * (size_t)frames[u] * D, hipMemcpyHostToDevice, b->core.stream));
+    row += frames[u];
+  }
+  if (int rc = SetLayoutFrames(b, frames.data(), nullptr, num_utts)) return rc;
+  b->feats = b->d_feats;
+  b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
+  return 0;
+}
+
+int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, const int *num_frames, int num_utts, int kind) {
+  if (!b || (num_utts > 0 && (!d_feats || !num_frames))) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = CheckFeatureKind(b, kind)) return rc;
+  if (int rc = CheckFeatureCounts(b, num_frames, num_utts)) return rc;
+  if (int rc = UseDevice(b->core.device)) return rc;
+  if (kind == PK_MI355_FEATS_RAW) {                     // CMVN reads around every utterance: into d_raw with its lead and slack
+    int64_t total = 0;
+    for (int u = 0; u < num_utts; ++u) total += num_frames[u];
+    if (total > 0)
+      HIP_TRY(hipMemcpyAsync(b->d_raw, d_feats, sizeof(float) * (size_t)total * kNumBins, hipMemcpyDeviceToDevice, b->core.stream));
+  }
+  if (int rc = SetLayoutFrames(b, num_frames, nullptr, num_utts)) return rc;
+  b->feats = d_feats;                                   // NORMALIZED: read where they lie
+  b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
+  return 0;
+}
+
 int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   if (!b) return Fail(PK_MI355_E_INVALID, "null batch");
-  if (!b->wave_f32 && !b->wave_i16) return Fail(PK_MI355_E_STATE, "no waves set");
+  if (b->source == pk_mi355_batch::kNone) return Fail(PK_MI355_E_STATE, "no waves or features set");
   ScorerCore &c = b->core;
   int rc = UseDevice(c.device);
   if (rc) return rc;
@@ -511,13 +653,17 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   b->scored = false;
   if (b->num_utts == 0 || b->total_frames == 0) { b->scored = true; return 0; }
   UttLayout lay{b->d_wave_off, b->d_T, b->d_raw_base, b->d_pad_base};
-  {
+  const int D = am->feat_dim;
+  if (b->source == pk_mi355_batch::kWaves) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
     LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_raw, c.stream);
   }
-  {
+  {                                            // raw rows (fbank's, or the caller's) or normalised features -> Yt
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);
-    LaunchCmvn(b->d_raw, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    if (b->source == pk_mi355_batch::kNormalized)
+      LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    else
+      LaunchCmvn(b->d_raw, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream);
   }
   // Rows of the layer stack: compact (row out_base[u] + t is frame t of utterance u; the first layer finds its
   // features shift4[row / 4] columns -- f16 modes: rows of the split copy -- further on).
@@ -529,7 +675,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     // out hold zeros or an earlier call's split, and their maxima are not this call's
     // (compact rows: the last tile's padding rows sit at most one tile + the context behind the last column)
     const int split_rows = (int)std::min<int64_t>(c.ldy, RoundUp(b->total_cols, kTileF16) + 2 * kTileF16);
-    LaunchSplitF16(c.d_yt, 1, c.ldy, split_rows, kNumBins, kNumBins, b->d_y2, 2 * kNumBins, ExpX(am, 0), RangeOf(c.exec, 0), c.stream);
+    LaunchSplitF16(c.d_yt, 1, c.ldy, split_rows, D, D, b->d_y2, 2 * D, ExpX(am, 0), RangeOf(c.exec, 0), c.stream);
   }
   const bool two = b->lanes == 2 && b->total_rows > c.chunk;
   if (f16 && b->lanes == 2 && !two) ClearHostRange(b->exec2);     // lane 2 takes no part in this call: no stale maxima
@@ -566,7 +712,7 @@ int pk_mi355_batch_calibrate(pk_mi355_batch_t *b) {
   if (!b) return Fail(PK_MI355_E_INVALID, "null batch");
   pk_mi355_am *am = b->core.am;
   if (!IsF16(am->precision)) return 0;
-  if (!b->wave_f32 && !b->wave_i16) return Fail(PK_MI355_E_STATE, "no waves set");
+  if (b->source == pk_mi355_batch::kNone) return Fail(PK_MI355_E_STATE, "no waves or features set");
   if (b->total_frames == 0) return Fail(PK_MI355_E_INVALID, "calibration needs at least one frame");
   int rc = UseDevice(b->core.device);
   if (rc) return rc;
@@ -658,6 +804,7 @@ int pk_mi355_batch_fetch_all(pk_mi355_batch_t *b, pk_decodable_t *out, int num_o
 int pk_mi355_batch_fetch_fbank(pk_mi355_batch_t *b, int utt, float *out) {
   if (!b || !out || utt < 0 || utt >= b->num_utts) return Fail(PK_MI355_E_INVALID, "bad utterance index");
   if (!b->scored) return Fail(PK_MI355_E_STATE, "batch not scored");
+  if (b->source == pk_mi355_batch::kNormalized) return Fail(PK_MI355_E_STATE, "the batch was fed normalised features: there is no fbank");
   const int T = b->h_T[utt];
   if (T == 0) return 0;
   HIP_TRY(hipMemcpyAsync(out, b->d_raw + b->h_raw_base[utt] * kNumBins, sizeof(float) * (size_t)T * kNumBins,
@@ -671,12 +818,13 @@ int pk_mi355_batch_fetch_cmvn(pk_mi355_batch_t *b, int utt, float *out) {
   if (!b->scored) return Fail(PK_MI355_E_STATE, "batch not scored");
   const int T = b->h_T[utt];
   if (T == 0) return 0;
-  std::vector<float> tmp((size_t)kNumBins * T);
+  const int D = b->core.am->feat_dim;
+  std::vector<float> tmp((size_t)D * T);
   HIP_TRY(hipMemcpy2DAsync(tmp.data(), sizeof(float) * T, b->core.d_yt + b->h_pad_base[utt] + b->core.am->left,
-                           sizeof(float) * b->core.ldy, sizeof(float) * T, kNumBins, hipMemcpyDeviceToHost, b->core.stream));
+                           sizeof(float) * b->core.ldy, sizeof(float) * T, D, hipMemcpyDeviceToHost, b->core.stream));
   HIP_TRY(hipStreamSynchronize(b->core.stream));
   for (int t = 0; t < T; ++t)
-    for (int d = 0; d < kNumBins; ++d) out[(size_t)t * kNumBins + d] = tmp[(size_t)d * T + t];
+    for (int d = 0; d < D; ++d) out[(size_t)t * D + d] = tmp[(size_t)d * T + t];
   return 0;
 }
 

@@ -104,13 +104,15 @@ int pk_mi355_recognizer_process(pk_mi355_recognizer_t *r, const pk_vector_t *wav
   return pk_mi355_recognizer_process_rates(r, waves, nullptr, n);
 }
 
-int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_t *waves, const int *rates, int n) {
-  if (!r || n < 0 || (n > 0 && !waves)) return Fail(PK_MI355_E_INVALID, "bad process arguments");
+}  // extern "C"
+
+namespace {
+// pk_process behind the batch's set_* call (`set`: the call that hands the n utterances over): score, decode, collect.
+template <class Set>
+int ProcessWith(pk_mi355_recognizer *r, int n, Set set) {
   r->have = false;
-  pk_vector_t none = {0, nullptr};
   int rc;
-  if ((rc = pk_mi355_resample_set_waves(r->batch, n ? waves : &none, rates, n)) || (rc = pk_mi355_batch_score(r->batch, 0.1f, 0)) ||
-      (rc = pk_mi355_decoder_decode_batch(r->decoder, r->batch, 1)))
+  if ((rc = set()) || (rc = pk_mi355_batch_score(r->batch, 0.1f, 0)) || (rc = pk_mi355_decoder_decode_batch(r->decoder, r->batch, 1)))
     return rc;
   r->hyp.assign(n, std::string());
   r->per_frame.assign(n, 0.0f);
@@ -128,6 +130,20 @@ int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_
   }
   r->have = true;
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int pk_mi355_recognizer_process_rates(pk_mi355_recognizer_t *r, const pk_vector_t *waves, const int *rates, int n) {
+  if (!r || n < 0 || (n > 0 && !waves)) return Fail(PK_MI355_E_INVALID, "bad process arguments");
+  pk_vector_t none = {0, nullptr};
+  return ProcessWith(r, n, [&] { return pk_mi355_resample_set_waves(r->batch, n ? waves : &none, rates, n); });
+}
+
+int pk_mi355_recognizer_process_features(pk_mi355_recognizer_t *r, const pk_matrix_t *feats, int n, int kind) {
+  if (!r || n < 0 || (n > 0 && !feats)) return Fail(PK_MI355_E_INVALID, "bad process arguments");
+  return ProcessWith(r, n, [&] { return pk_mi355_features_set(r->batch, feats, n, kind); });
 }
 
 const char *pk_mi355_recognizer_hyp(const pk_mi355_recognizer_t *r, int utt) {

@@ -14,7 +14,7 @@
 //   capi_decoder.hip     (pk_decode.h) the decoder core -- graph, work areas, arenas -- and the batch decoder over it
 //   capi_online_decoder.hip  (pk_decode.h) the online decoder over the same core
 // (decode.hip and stream.hip hold the decoder's and the online scorer's kernels and their launchers, declared in
-// pk_decode.h and pk_score.h.)
+// pk_decode.h and pk_score.h; features.hip the batch scorer's layout kernel for features, declared in pk_score.h.)
 // Nothing here is part of the ABI (include/pk_mi355.h is); the library exports the C entries only
 // (libpk_mi355.map).
 #ifndef PK_HOST_H_

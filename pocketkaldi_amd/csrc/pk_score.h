@@ -34,6 +34,13 @@ void LaunchStreamAssemble(const StreamRec *recs, int n, const float *upload, flo
 void LaunchStreamCmvn(const StreamRec *recs, int n, float *rows, const float *g, const CmvnTables *tab, float *sums,
                       float *raw_hist, float *hist, int hist_len, int left, int right, float *yt, int64_t ldy, hipStream_t stream);
 
+// launcher (features.hip): features frame-major [sum T][dim], utterance u's rows from raw_base[u] on -> the padded
+// feature-major Yt[dim][ldy], frame t at column pad_base[u] + left + t, the first / last frame replicated into the
+// pads (what LaunchCmvn writes, without the arithmetic: a copy, bit for bit).  One launch for all utterances;
+// max_frames: the longest utterance.  The caller has checked every base and count against the buffers.
+void LaunchFeatureLayout(const float *feats, const UttLayout &utts, int num_utts, int max_frames, int dim, int left, int right,
+                         float *yt, int64_t ldy, hipStream_t stream);
+
 }  // namespace pkmi
 
 namespace pkhost {
@@ -61,7 +68,9 @@ struct CreateCheck {
   void operator()(hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "%s: %s", name, hipGetErrorString(e)); } }
 };
 // On the selected device (am's): `units` utterances or slots of at most max_frames frames and max_rows rows of the
-// layer stack together, passes of at most chunk_cap rows.  On failure (chk.ok false) the caller still calls FreeScorerCore.
+// layer stack together, passes of at most chunk_cap rows.  Yt has am->feat_dim rows.  global_stats41 may be null (a
+// scorer that is only ever fed normalised features): the front-end tables are then not made.
+// On failure (chk.ok false) the caller still calls FreeScorerCore.
 void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats41, int units, int64_t max_frames,
                       int64_t max_rows, int64_t chunk_cap, CreateCheck &chk);
 void FreeScorerCore(ScorerCore *c);             // (the owner has waited for the stream)

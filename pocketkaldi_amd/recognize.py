@@ -3,6 +3,7 @@
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
                                         [--online [--chunk-ms N] [--partials] [--commit]
                                          [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
+    python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz> --features raw|normalized [--ctm] [--reference-softmax]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
 that does not end in .wav is a list of wave files, one per line (main.cc:34-46); its waves are decoded together, as
@@ -13,6 +14,11 @@ per word segment of the best path, in seconds at the 10 ms frame shift (fbank.cc
 Every file is read with read_wave: any sample rate from 8 to 96 kHz and up to 8 channels, of which --channel N
 (default 0) is taken; audio that is not at 16 kHz is converted on the GPU on the way in, and the word times stay on
 the 10 ms frame grid of the converted audio.
+
+--features KIND takes features instead of audio (Recognizer.process_features): a .npy file holds one [T][D] matrix and is
+printed under the file's name, a .npz file holds one utterance per array and each is printed under its array's name, in
+the file's order.  KIND raw: 40-dim log-mel fbank, the CMVN is applied; normalized: ready for the splice.  --ctm works as
+it does for audio.  Not with --online (the online scorer takes audio only).
 
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
@@ -40,9 +46,11 @@ RESERVE = 32
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
+    print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz> --features raw|normalized [--ctm] [--reference-softmax]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
+    print("    *.npy / *.npz (with --features): decode this feature matrix / every array of the file.")
     return 1
 
 
@@ -127,6 +135,13 @@ def main(argv):
         if channel < 0:
             return usage()
         del argv[at:at + 2]
+    features = None
+    if "--features" in argv:
+        at = argv.index("--features")
+        if at + 1 >= len(argv) or argv[at + 1] not in pk.FEATURE_KINDS or "--online" in argv:
+            return usage()
+        features = argv[at + 1]
+        del argv[at:at + 2]
     endpoint, rules = None, []
     try:
         while "--endpoint-rule" in argv:
@@ -151,17 +166,34 @@ def main(argv):
     model_file, input_file = args
     rec, pieces = None, {}
     try:
-        if input_file.endswith(".wav"):
+        if features:
+            import numpy as np
+            if not input_file.endswith((".npy", ".npz")):
+                return usage()
+            if input_file.endswith(".npy"):
+                files, feats = [input_file], [np.load(input_file, allow_pickle=False)]
+            else:
+                with np.load(input_file, allow_pickle=False) as z:
+                    files, feats = list(z.files), [z[k] for k in z.files]
+            frames = [int(f.shape[0]) if getattr(f, "ndim", 0) == 2 else 1 for f in feats]     # (process_features names a bad shape)
+            rec = pk.Recognizer(model_file, max_utts=min(max(len(feats), 1), MAX_UTTS),
+                                max_total_samples=160 * max(max(frames + [1]), min(sum(frames), MAX_SAMPLES // 160)))
+            if "--reference-softmax" in flags:
+                rec.am.set_softmax("reference")
+            results, names = rec.process_features(feats, features), rec.symbols
+        elif input_file.endswith(".wav"):
             files = [input_file]
         else:
             with open(input_file) as f:
                 files = [line.strip() for line in f if line.strip()]
         waves, rates = [], []
-        for name in files:
+        for name in [] if features else files:
             wave, rate = pk.read_wave(name, channel)
             waves.append(wave)
             rates.append(rate)
-        if "--online" in flags:
+        if features:
+            pass
+        elif "--online" in flags:
             results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
                                               "--partials" in flags, "--commit" in flags, rates, endpoint,
                                               pieces if endpoint else None)
@@ -173,7 +205,7 @@ def main(argv):
                 rec.am.set_softmax("reference")
             native = any(r != 16000 for r in rates)
             results, names = rec.process(waves, rates if native else None), rec.symbols
-    except (pk.PkError, OSError) as e:
+    except (pk.PkError, OSError, ValueError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
     for u, name in enumerate(files if endpoint else []):       # one line per utterance; word times from the wave's start
