@@ -143,10 +143,6 @@ struct pk_mi355_batch {
   Timer timer;
   int max_utts = 0;
   int64_t max_samples = 0;
-  int64_t chunk_cap = 262144;  // frames per pass through the layer stack at most (PK_MI355_CHUNK overrides).  Without the fused
-                               // tail the size hardly matters (256 x 10 s: 65536 -> 25.92, 131072 -> 25.79, 262144 -> 25.78 ms per
-                               // step); with it every last-layer launch ends in ~0.25 ms of tail phases on an emptying chip, so fewer,
-                               // larger passes win: 65536 -> 25.45, 131072 -> 25.0, 262144 -> 24.75 (profiles/r04_fused_tail32.txt)
   // PCM
   float *d_wave = nullptr;          // owned float buffer
   int16_t *d_wave_i16 = nullptr;    // owned int16 buffer
@@ -170,18 +166,22 @@ struct pk_mi355_batch {
   int max_T = 0;
   int64_t total_frames = 0, total_cols = 0;
   int64_t dirty_cols = 0;           // columns of d_yt that may hold an earlier layout's features (SetLayout zeroes what a smaller one leaves behind)
-  std::vector<int64_t> h_wave_off, h_raw_base, h_pad_base;
+  // What a set call uploads -- wave_off, raw_base, pad_base, T (num_utts entries each) and, when a shift is not zero,
+  // shift4 -- lies in ONE page-locked block, packed, and goes to a device block of the same shape in one copy with
+  // ev_layout recorded behind it; the next set call waits for that event before it rewrites the host block.
+  char *h_lay = nullptr, *d_lay = nullptr;
+  hipEvent_t ev_layout = nullptr;
+  int64_t *h_wave_off = nullptr, *h_raw_base = nullptr, *h_pad_base = nullptr;   // into h_lay
+  int32_t *h_T = nullptr;
+  UttLayout lay{};                  // the same arrays in d_lay
   // Rows of the layer stack and of d_ll: COMPACT -- utterance after utterance, each padded to a multiple of four rows, no
   // rows for the L + R context pads that separate two utterances in Yt (1 % of the matrix work at 10 s); the first
   // layer finds row j's features at column (f16 modes: row of the split copy) j + shift4[j / 4].
+  // The rows end at the last frame of the last utterance that has frames: the padding behind it belongs to nobody.
   std::vector<int64_t> h_out_base;  // first row of utterance u
   int64_t total_rows = 0;
   bool compact = false;
-  std::vector<int32_t> h_shift4;
-  int32_t *d_shift4 = nullptr;
-  std::vector<int32_t> h_T;
-  int64_t *d_wave_off = nullptr, *d_raw_base = nullptr, *d_pad_base = nullptr;
-  int32_t *d_T = nullptr;
+  const int32_t *d_shift4 = nullptr;   // in d_lay; null when every shift of the layout is zero (one utterance at column 0) or rows = columns
   // stages
   float *d_raw_alloc = nullptr;
   float *d_raw = nullptr;   // [max_frames][40], kCmvnRawLead floats into d_raw_alloc
@@ -208,6 +208,8 @@ struct pk_mi355_batch {
 
 namespace {
 
+constexpr size_t kLayoutEntry = 3 * sizeof(int64_t) + sizeof(int32_t);   // bytes of one utterance in the layout block (h_lay, d_lay)
+
 // Frames and columns (every utterance with its context pads) against the batch's capacity.
 int FramesFit(const pk_mi355_batch *b, const int *frames, int num_utts) {
   const int pad = b->core.am->left + b->core.am->right;
@@ -225,13 +227,20 @@ int FramesFit(const pk_mi355_batch *b, const int *frames, int num_utts) {
 // The layout of a call, from the utterances' frame counts: placement in the raw rows and in Yt, compact rows, shift4,
 // the capacity checks and the dirty_cols rule.  num_samples: the PCM behind the frames (null for features).  The
 // counts have been checked (utterances, no negative one, PCM capacity); nothing changes when the frames do not fit.
+// Queues one upload and waits for nothing but the upload before it: the callers' own copies out of pageable memory
+// (waves, features) have read their source when hipMemcpyAsync returns, as for every pageable source.
 int SetLayoutFrames(pk_mi355_batch *b, const int *frames, const int *num_samples, int num_utts) {
   if (int rc = FramesFit(b, frames, num_utts)) return rc;
   ScorerCore &c = b->core;
   const int pad = c.am->left + c.am->right;
+  HIP_TRY(hipEventSynchronize(b->ev_layout));      // the last layout's upload has left the page-locked block
+  const size_t n = (size_t)num_utts;
+  size_t bytes = kLayoutEntry * n;                 // wave_off | raw_base | pad_base | T, then shift4 at the next multiple of 256
+  b->h_wave_off = reinterpret_cast<int64_t *>(b->h_lay); b->h_raw_base = b->h_wave_off + n; b->h_pad_base = b->h_raw_base + n;
+  b->h_T = reinterpret_cast<int32_t *>(b->h_pad_base + n);
+  const int64_t *d64 = reinterpret_cast<const int64_t *>(b->d_lay);
+  b->lay = UttLayout{d64, reinterpret_cast<const int32_t *>(d64 + 3 * n), d64 + n, d64 + 2 * n};
   int64_t woff = 0, raw = 0, col = 0;
-  b->h_wave_off.resize(num_utts); b->h_raw_base.resize(num_utts);
-  b->h_pad_base.resize(num_utts); b->h_T.resize(num_utts);
   b->max_T = 0;
   for (int u = 0; u < num_utts; ++u) {
     const int T = frames[u];
@@ -244,37 +253,38 @@ int SetLayoutFrames(pk_mi355_batch *b, const int *frames, const int *num_samples
   // Columns behind this layout's last one that an earlier, larger layout filled: the padded rows of the last tile
   // are computed from them, and in the f16 modes whatever they produce counts towards the range verdict (a loud
   // batch followed by a smaller healthy one must not fail on the loud one's leftovers).  Zero again.
-  if (col < b->dirty_cols) {
+  if (col < b->dirty_cols)
     HIP_TRY(hipMemset2DAsync(c.d_yt + col, sizeof(float) * c.ldy, 0, sizeof(float) * (size_t)(b->dirty_cols - col), c.am->feat_dim, c.stream));
-    b->dirty_cols = col;
-  }
-  b->dirty_cols = std::max(b->dirty_cols, col);
+  b->dirty_cols = col;
   b->num_utts = num_utts;
   b->total_frames = raw;
   b->total_cols = col;
   b->scored = false;
   b->h_out_base.resize(num_utts);
+  b->total_rows = 0;
   int64_t row = 0;
+  std::vector<ShiftSpan> spans;
+  bool shifted = false;
   for (int u = 0; u < num_utts; ++u) {
+    const int T = b->h_T[u];
     b->h_out_base[u] = b->compact ? row : b->h_pad_base[u];
-    if (b->h_T[u] > 0) row += RoundUp(b->h_T[u], 4);
+    if (T == 0) continue;
+    b->total_rows = b->h_out_base[u] + T;
+    row += RoundUp(T, 4);
+    spans.push_back({row, (int32_t)(b->h_pad_base[u] - b->h_out_base[u])});
+    shifted = shifted || spans.back().shift != 0;
   }
-  b->total_rows = b->compact ? row : col;
+  b->d_shift4 = nullptr;
   if (num_utts == 0) return 0;
-  if (b->compact) {
-    std::vector<ShiftSpan> spans;
-    for (int u = 0; u < num_utts; ++u)
-      if (b->h_T[u] > 0) spans.push_back({b->h_out_base[u] + RoundUp(b->h_T[u], 4), (int32_t)(b->h_pad_base[u] - b->h_out_base[u])});
-    // (batch_create keeps L + R < 3, whose shifts go negative, out of this layout)
-    if (!ExpandShift4(spans, b->total_rows, c.zero_span, b->h_shift4.data(), nullptr))
+  if (shifted) {                                 // (compact rows only; batch_create keeps L + R < 3, whose shifts go negative, out of them)
+    bytes = RoundUp(bytes, 256);
+    if (!ExpandShift4(spans, b->total_rows, c.zero_span, reinterpret_cast<int32_t *>(b->h_lay + bytes), nullptr))
       return Fail(PK_MI355_E_INVALID, "internal: column shift outside [0, %lld]", (long long)(c.zero_span - kTile));
-    HIP_TRY(hipMemcpyAsync(b->d_shift4, b->h_shift4.data(), sizeof(int32_t) * Shift4Groups(b->total_rows), hipMemcpyHostToDevice, c.stream));
+    b->d_shift4 = reinterpret_cast<const int32_t *>(b->d_lay + bytes);
+    bytes += sizeof(int32_t) * Shift4Groups(b->total_rows);
   }
-  HIP_TRY(hipMemcpyAsync(b->d_wave_off, b->h_wave_off.data(), sizeof(int64_t) * num_utts, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(hipMemcpyAsync(b->d_raw_base, b->h_raw_base.data(), sizeof(int64_t) * num_utts, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(hipMemcpyAsync(b->d_pad_base, b->h_pad_base.data(), sizeof(int64_t) * num_utts, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(hipMemcpyAsync(b->d_T, b->h_T.data(), sizeof(int32_t) * num_utts, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));   // the host vectors may be reused right away
+  HIP_TRY(hipMemcpyAsync(b->d_lay, b->h_lay, bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipEventRecord(b->ev_layout, c.stream));
   return 0;
 }
 
@@ -399,19 +409,28 @@ int pk_mi355_num_frames(int num_samples) {      // fbank.cc:35-42
 }  // extern "C"
 
 namespace {
-// Both create entries, arguments checked: a batch of max_utts utterances and max_frames frames; max_total_samples PCM
-// samples (0: features only).  global_stats41 may be null for a features-only batch.
-pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples, int64_t max_frames) {
+// Frames per pass through the layer stack at most, for a batch made through the ABI (PK_MI355_CHUNK overrides).  Without
+// the fused tail the size hardly matters (256 x 10 s: 65536 -> 25.92, 131072 -> 25.79, 262144 -> 25.78 ms per step); with
+// it every last-layer launch ends in ~0.25 ms of tail phases on an emptying chip, so fewer, larger passes win:
+// 65536 -> 25.45, 131072 -> 25.0, 262144 -> 24.75 (profiles/r04_fused_tail32.txt)
+int64_t PublicChunkCap() {
+  const char *e = getenv("PK_MI355_CHUNK");
+  return e && atol(e) >= kTile ? RoundUp(atol(e), kTileF16) : 262144;
+}
+
+// Every way to a batch, arguments checked: max_utts utterances and max_frames frames; max_total_samples PCM samples
+// (0: features only); passes of at most chunk_cap frames.  global_stats41 may be null for a features-only batch.
+pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples, int64_t max_frames,
+                            int64_t chunk_cap) {
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
   b->max_utts = max_utts; b->max_samples = max_total_samples;
   b->features_only = max_total_samples == 0;
   b->have_stats = global_stats41 != nullptr;
-  if (const char *e = getenv("PK_MI355_CHUNK")) if (atol(e) >= kTile) b->chunk_cap = RoundUp(atol(e), kTileF16);
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
-  CreateScorerCore(&c, am, global_stats41, max_utts, max_frames, max_frames, b->chunk_cap, chk);
+  CreateScorerCore(&c, am, global_stats41, max_utts, max_frames, max_frames, chunk_cap, chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
   // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
@@ -420,14 +439,10 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int 
   // save anyway: such models keep row = column of Yt.
   b->compact = pad >= 3;
   if (const char *e = getenv("PK_MI355_COMPACT_ROWS")) b->compact = b->compact && atoi(e) != 0;    // (A/B switch: 0 = row = column of Yt)
-  chk(hipMalloc(&b->d_wave_off, sizeof(int64_t) * max_utts));
-  chk(hipMalloc(&b->d_raw_base, sizeof(int64_t) * max_utts));
-  chk(hipMalloc(&b->d_pad_base, sizeof(int64_t) * max_utts));
-  chk(hipMalloc(&b->d_T, sizeof(int32_t) * max_utts));
-  if (b->compact) {
-    b->h_shift4.resize(Shift4Cap(c.max_cols));
-    chk(hipMalloc(&b->d_shift4, sizeof(int32_t) * b->h_shift4.size()));
-  }
+  const size_t lay_bytes = RoundUp(kLayoutEntry * max_utts, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
+  chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
+  chk(hipMalloc(&b->d_lay, lay_bytes));
+  chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
   if (b->have_stats) {
     const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
     chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
@@ -446,7 +461,26 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int 
   if (!chk.ok) { pk_mi355_batch_destroy(b); return nullptr; }
   return b;
 }
+
+// am->mu held.  One of the model's own one-utterance scorers for a call of `need` samples or frames: kept while the call
+// fits and `keep` holds, otherwise destroyed and made again by make(capacity), the capacity at least doubled.
+template <class Make>
+pk_mi355_batch *EnsureOwned(OwnedBatch *o, int64_t need, bool keep, Make make) {
+  if (o->b && need <= o->cap && keep) return o->b;
+  if (o->b) pk_mi355_batch_destroy(o->b);
+  o->cap = std::max<int64_t>(need, 2 * o->cap);
+  o->b = make(o->cap);
+  if (!o->b) o->cap = 0;
+  return o->b;
+}
 }  // namespace
+
+namespace pkhost {
+pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames) {      // (at least one whole pass: every pass is kSingleChunk rows)
+  return EnsureOwned(&am->single, std::max(frames, kSingleChunk), true,
+                     [&](int64_t cap) { return CreateBatch(am, nullptr, 1, 0, cap, kSingleChunk); });
+}
+}  // namespace pkhost
 
 extern "C" {
 
@@ -454,7 +488,7 @@ pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_s
   if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
   if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
   if (!global_stats41 || max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  return CreateBatch(am, global_stats41, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts);
+  return CreateBatch(am, global_stats41, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts, PublicChunkCap());
 }
 
 pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_frames) {
@@ -468,7 +502,7 @@ pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float 
     Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
     return nullptr;
   }
-  return CreateBatch(am, global_stats41, max_utts, 0, max_total_frames);
+  return CreateBatch(am, global_stats41, max_utts, 0, max_total_frames, PublicChunkCap());
 }
 
 int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
@@ -479,13 +513,14 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   if (b->core.stream) hipStreamSynchronize(b->core.stream);
   if (b->stream2) hipStreamSynchronize(b->stream2);
   FreeExec(&b->exec2);
-  for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched}) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched, b->ev_layout}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
   hipFree(b->d_native);
-  hipFree(b->d_wave_off); hipFree(b->d_raw_base); hipFree(b->d_pad_base); hipFree(b->d_T); hipFree(b->d_shift4);
+  if (b->h_lay) hipHostFree(b->h_lay);
+  hipFree(b->d_lay);
   if (b->arena) RetireArena(b->arena);   // released now, or by the last outstanding view of the last fetch_all
   FreeScorerCore(&b->core);
   delete b;
@@ -607,13 +642,16 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
     if (!b->d_feats) HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * D));
     dst = b->d_feats;
   }
+  // The layout first: its upload travels while the host stages the features below (a copy out of pageable memory
+  // holds the host until it is done), and the first kernel of the score call is then queued straight behind them.
+  if (int rc = SetLayoutFrames(b, frames.data(), nullptr, num_utts)) return rc;
+  b->source = pk_mi355_batch::kNone;             // (until the features are there too)
   int64_t row = 0;
   for (int u = 0; u < num_utts; ++u) {
     if (frames[u] > 0)
       HIP_TRY(hipMemcpyAsync(dst + row * D, feats[u].data, sizeof(float) * (size_t)frames[u] * D, hipMemcpyHostToDevice, b->core.stream));
     row += frames[u];
   }
-  if (int rc = SetLayoutFrames(b, frames.data(), nullptr, num_utts)) return rc;
   b->feats = b->d_feats;
   b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
   return 0;
@@ -652,7 +690,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   b->range_msg[0] = 0;
   b->scored = false;
   if (b->num_utts == 0 || b->total_frames == 0) { b->scored = true; return 0; }
-  UttLayout lay{b->d_wave_off, b->d_T, b->d_raw_base, b->d_pad_base};
+  const UttLayout &lay = b->lay;
   const int D = am->feat_dim;
   if (b->source == pk_mi355_batch::kWaves) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
@@ -666,7 +704,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
       LaunchCmvn(b->d_raw, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream);
   }
   // Rows of the layer stack: compact (row out_base[u] + t is frame t of utterance u; the first layer finds its
-  // features shift4[row / 4] columns -- f16 modes: rows of the split copy -- further on).
+  // features shift4[row / 4] columns -- f16 modes: rows of the split copy -- further on; no shift4 when all are zero).
   const bool f16 = IsF16(am->precision);
   if (f16) {
     if ((rc = BeginRange(c.exec, c.stream))) return rc;
@@ -684,7 +722,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     HIP_TRY(hipStreamWaitEvent(b->stream2, b->ev_front, 0));
     if (f16 && (rc = BeginRange(b->exec2, b->stream2))) return rc;
   }
-  const Operand op{c.d_yt, b->d_y2, c.ldy, ZeroSource(c), b->compact ? b->d_shift4 : nullptr};
+  const Operand op{c.d_yt, b->d_y2, c.ldy, ZeroSource(c), b->d_shift4};
   const Lane lanes[2] = {{c.stream, &c.exec}, {b->stream2, &b->exec2}};
   if ((rc = WalkChunks(am, op, b->total_rows, c.chunk, lanes, two ? 2 : 1, true, prob_scale, c.d_ll, tm))) return rc;
   if (two) {                                   // everything is ordered on the batch's stream again
@@ -714,10 +752,16 @@ int pk_mi355_batch_calibrate(pk_mi355_batch_t *b) {
   if (!IsF16(am->precision)) return 0;
   if (b->source == pk_mi355_batch::kNone) return Fail(PK_MI355_E_STATE, "no waves or features set");
   if (b->total_frames == 0) return Fail(PK_MI355_E_INVALID, "calibration needs at least one frame");
-  int rc = UseDevice(b->core.device);
-  if (rc) return rc;
+  if (int rc = UseDevice(b->core.device)) return rc;
   std::lock_guard<std::mutex> lock(am->mu);
-  if (am->exps_stale && (rc = RefreshExps(am))) return rc;
+  return BatchCalibrateLocked(b);
+}
+
+}  // extern "C"
+
+int pkhost::BatchCalibrateLocked(pk_mi355_batch *b) {
+  pk_mi355_am *am = b->core.am;
+  if (am->exps_stale) if (int rc = RefreshExps(am)) return rc;
   const ExecBufs &e = b->core.exec;
   return CalibrateLoop(am, e, [&]() -> int {
     const int rc = pk_mi355_batch_score(b, 1.0f, 0);
@@ -730,6 +774,8 @@ int pk_mi355_batch_calibrate(pk_mi355_batch_t *b) {
     return 0;
   });
 }
+
+extern "C" {
 
 int pk_mi355_batch_num_utts(const pk_mi355_batch_t *b) { return b ? b->num_utts : 0; }
 int pk_mi355_batch_num_frames(const pk_mi355_batch_t *b, int utt) {
@@ -874,16 +920,11 @@ int pk_mi355_process_acoustic(pk_mi355_am_t *am, const pk_vector_t *cmvn_global_
   ClearDecodable(out, am);
   if (raw_wave->dim == 0) return 0;                           // pocketkaldi.cc:180-184
   std::lock_guard<std::mutex> lock(am->mu);
-  const int64_t need = std::max<int64_t>(raw_wave->dim, 16000);
-  if (!am->proc || need > am->proc_cap ||
-      memcmp(am->proc_stats, cmvn_global_stats->data, sizeof(am->proc_stats)) != 0) {
-    if (am->proc) pk_mi355_batch_destroy(am->proc);
-    am->proc_cap = std::max<int64_t>(need, 2 * am->proc_cap);
-    am->proc = pk_mi355_batch_create(am, cmvn_global_stats->data, 1, am->proc_cap);
-    if (!am->proc) { am->proc_cap = 0; return PK_MI355_E_DEVICE; }
-    memcpy(am->proc_stats, cmvn_global_stats->data, sizeof(am->proc_stats));
-  }
-  pk_mi355_batch *b = am->proc;
+  const float *stats = cmvn_global_stats->data;
+  pk_mi355_batch *b = EnsureOwned(&am->proc, std::max<int64_t>(raw_wave->dim, 16000), memcmp(am->proc_stats, stats, sizeof(am->proc_stats)) == 0,
+                                  [&](int64_t cap) { return pk_mi355_batch_create(am, stats, 1, cap); });
+  if (!b) return PK_MI355_E_DEVICE;
+  memcpy(am->proc_stats, stats, sizeof(am->proc_stats));
   int rc = pk_mi355_batch_set_waves(b, raw_wave, 1);
   if (rc) return rc;
   pk_mi355_batch_enable_timing(b, verbose);

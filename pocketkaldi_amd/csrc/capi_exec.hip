@@ -1,6 +1,7 @@
 // capi_exec.hip -- the layer executor (fp32 and split-fp16 walks over the layer stack, and the chunk walk over
-// them), the range words of the f16 modes, the single-utterance workspace, and the reference-compatible pk_decodable_* functions
-// (decodable.h:20-41).  Host C++ over the HIP runtime; no CPU compute path.
+// them), the range words of the f16 modes, the calibration loop, pk_mi355_nnet_propagate on its own buffers, and the
+// reference-compatible pk_decodable_* functions (decodable.h:20-41): pk_decodable_init and pk_mi355_am_calibrate are
+// calls on the model's one-utterance features batch (capi_batch.hip).  Host C++ over the HIP runtime; no CPU compute path.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -368,21 +369,14 @@ int WalkChunks(const pk_mi355_am *am, const Operand &op, int64_t total_rows, int
   return 0;
 }
 
-// Single-utterance workspace used by pk_decodable_init / nnet_propagate.
+// What pk_mi355_nnet_propagate runs on (am->mu held): its stream, one pass's layer buffers and the uploaded input.
 struct Workspace {
   ExecBufs exec;
   float *d_feats = nullptr;  int64_t feats_cap = 0;     // frame-major host upload
-  float *d_yt = nullptr;     int64_t yt_ld = 0;          // [feat_dim][yt_ld], the last kSingleZeroSpan columns never written
-  int64_t dirty_cols = 0;                               // columns of d_yt that may hold an earlier call's features (ScoreSingleQueue)
-  _Float16 *d_y2 = nullptr;                             // f16x3: interleaved rows [yt_ld][2 feat_dim]
-  float *d_out = nullptr;    int64_t out_cap = 0;        // [rows][num_pdfs]
   hipStream_t stream = nullptr;
 };
 
-constexpr int64_t kSingleChunk = 4096;   // frames per pass of the single-utterance path
-const int64_t kSingleZeroSpan = ZeroSpan(0, 0);   // one utterance at column 0: no column shift
-
-int EnsureWorkspace(pk_mi355_am *am, int64_t frames, int width) {
+int EnsureWorkspace(pk_mi355_am *am, int64_t feats_floats) {
   if (!am->ws) {
     am->ws = new Workspace();
     HIP_TRY(hipStreamCreate(&am->ws->stream));
@@ -390,30 +384,10 @@ int EnsureWorkspace(pk_mi355_am *am, int64_t frames, int width) {
     if (rc) return rc;
   }
   Workspace *w = am->ws;
-  const int64_t need_feats = frames * width;
-  if (need_feats > w->feats_cap) {
+  if (feats_floats > w->feats_cap) {
     hipFree(w->d_feats);
-    w->feats_cap = need_feats;
+    w->feats_cap = feats_floats;
     HIP_TRY(hipMalloc(&w->d_feats, sizeof(float) * w->feats_cap));
-  }
-  const int64_t pad = am->left + am->right;
-  const int64_t need_ld = RoundUp(frames + pad, kSingleChunk) + kSingleZeroSpan;
-  if (am->feat_dim > 0 && need_ld > w->yt_ld) {
-    hipFree(w->d_yt);
-    w->yt_ld = need_ld;
-    HIP_TRY(hipMalloc(&w->d_yt, sizeof(float) * w->yt_ld * am->feat_dim));
-    HIP_TRY(hipMemset(w->d_yt, 0, sizeof(float) * w->yt_ld * am->feat_dim));
-    w->dirty_cols = 0;
-    if (IsF16(am->precision)) {
-      hipFree(w->d_y2);
-      HIP_TRY(hipMalloc(&w->d_y2, sizeof(_Float16) * 2 * w->yt_ld * am->feat_dim));
-    }
-  }
-  const int64_t need_out = frames * std::max(am->output_dim, 1);
-  if (need_out > w->out_cap) {
-    hipFree(w->d_out);
-    w->out_cap = need_out;
-    HIP_TRY(hipMalloc(&w->d_out, sizeof(float) * w->out_cap));
   }
   return 0;
 }
@@ -422,9 +396,6 @@ void FreeWorkspace(Workspace *w) {
   if (!w) return;
   FreeExec(&w->exec);
   hipFree(w->d_feats);
-  hipFree(w->d_yt);
-  hipFree(w->d_y2);
-  hipFree(w->d_out);
   if (w->stream) hipStreamDestroy(w->stream);
   delete w;
 }
@@ -488,40 +459,6 @@ int CalibrateLoop(pk_mi355_am *am, const ExecBufs &e, const std::function<int()>
 
 }  // namespace pkhost
 
-namespace {
-// The device half of pk_decodable_init (decodable.cc:8-17 -> am.cc:90-115), queued on the model's
-// single-utterance stream (am->mu held, workspace sized): features up, edge-padded transpose (am.cc:73-75),
-// the layer stack chunk by chunk; with want_tail the log-likelihoods land in ws->d_out.  In the f16 modes the
-// range words of the call are zeroed first and collected into the page-locked mirror last.
-int ScoreSingleQueue(pk_mi355_am *am, const pk_matrix_t *feats, bool want_tail, float prob_scale) {
-  Workspace *w = am->ws;
-  const int T = feats->ncol, D = feats->nrow;
-  const bool f16 = IsF16(am->precision);
-  int rc;
-  HIP_TRY(hipMemcpyAsync(w->d_feats, feats->data, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, w->stream));
-  LaunchPadTranspose(w->d_feats, T, D, am->left, am->right, w->d_yt, w->yt_ld, 0, w->stream);
-  // Columns behind this call's last one that an earlier, longer call filled: the padded rows of the last tile are
-  // computed from them, and in the f16 modes whatever they produce counts towards the range verdict (a loud utterance
-  // followed by a shorter healthy one must not fail on the loud one's leftovers; capi_batch.hip: SetLayout).  Zero again.
-  const int64_t cols = (int64_t)T + am->left + am->right;
-  if (cols < w->dirty_cols)
-    HIP_TRY(hipMemset2DAsync(w->d_yt + cols, sizeof(float) * w->yt_ld, 0, sizeof(float) * (size_t)(w->dirty_cols - cols), D, w->stream));
-  w->dirty_cols = cols;
-  if (f16) {
-    if ((rc = BeginRange(w->exec, w->stream))) return rc;
-    // only the rows the layer stack reads (the last pass's padded rows and their right context): rows further out hold
-    // zeros or an earlier call's split, and their maxima are not this call's
-    const int split_rows = (int)std::min<int64_t>(w->yt_ld, RoundUp(cols, kTileF16) + 2 * kTileF16);
-    LaunchSplitF16(w->d_yt, 1, w->yt_ld, split_rows, D, D, w->d_y2, 2 * D, ExpX(am, 0), RangeOf(w->exec, 0), w->stream);
-  }
-  const Operand op{w->d_yt, w->d_y2, w->yt_ld, ZeroSource(w->d_yt, w->yt_ld, kSingleZeroSpan), nullptr};
-  const Lane lane{w->stream, &w->exec};
-  if ((rc = WalkChunks(am, op, T, kSingleChunk, &lane, 1, want_tail, prob_scale, w->d_out, nullptr))) return rc;
-  if (f16 && (rc = CollectRange(w->exec, w->stream))) return rc;
-  return 0;
-}
-}  // namespace
-
 extern "C" {
 
 int pk_mi355_nnet_propagate(pk_mi355_am_t *am, const pk_matrix_t *in, pk_matrix_t *out) {
@@ -534,7 +471,7 @@ int pk_mi355_nnet_propagate(pk_mi355_am_t *am, const pk_matrix_t *in, pk_matrix_
   const int T = in->ncol, D = in->nrow;
   if ((rc = ResizeHostMatrix(out, am->output_dim, T))) return rc;
   if (T == 0) return 0;
-  if ((rc = EnsureWorkspace(am, T, std::max(D, am->output_dim)))) return rc;
+  if ((rc = EnsureWorkspace(am, (int64_t)T * D))) return rc;
   Workspace *w = am->ws;
   HIP_TRY(hipMemcpyAsync(w->d_feats, in->data, sizeof(float) * (size_t)T * D, hipMemcpyHostToDevice, w->stream));
   for (int64_t r0 = 0; r0 < T; r0 += kSingleChunk) {
@@ -579,40 +516,24 @@ void pk_decodable_init(pk_decodable_t *self, pk_mi355_am_t *am, float prob_scale
     return;
   }
   if (UseDevice(am->device)) return;
-  const int T = feats->ncol, D = feats->nrow, N = am->num_pdfs;
+  const int T = feats->ncol, D = feats->nrow;
   if (T <= 0) return;
-  const bool f16 = IsF16(am->precision);
-  if (f16 && D % 8 != 0) {
+  if (IsF16(am->precision) && D % 8 != 0) {
     // the interleaved (hi, lo) row of a frame is made of whole 8-k chunks: the spliced view
     // (row stride 2 D halves, gemm_f16.hip) exists only for such D
     Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", D);
     return;
   }
+  // One utterance through the model's own features batch: set, score without waiting, fetch.  The fetch is one copy
+  // behind the last kernel: the 12 MB of a 10 s utterance cross the link in 0.22 ms (54 GB/s, into pageable malloc()
+  // memory as fast as into page-locked memory) -- more than the network takes (0.17 ms); sending the log-likelihoods in
+  // row blocks under the last layer's remaining blocks was built three ways and gains nothing
+  // (tools/experiments/init_pipeline, profiles/r04_decodable_init_pipeline.txt).  In the f16 modes the fetch withholds
+  // the rows of a call whose operands left the fp16 split's range.
   std::lock_guard<std::mutex> lock(am->mu);
-  if (EnsureWorkspace(am, T, D)) return;
-  Workspace *w = am->ws;
-  auto dev_fail = [&](hipError_t e) { Fail(PK_MI355_E_DEVICE, "HIP failure in pk_decodable_init: %s", hipGetErrorString(e)); };
-  // One copy behind the last kernel.  The 12 MB of a 10 s utterance cross the link in 0.22 ms (54 GB/s, into pageable
-  // malloc() memory as fast as into page-locked memory) -- more than the network takes (0.17 ms); sending the
-  // log-likelihoods in row blocks under the last layer's remaining blocks was built three ways and gains nothing
-  // (tools/experiments/init_pipeline, profiles/r04_decodable_init_pipeline.txt).
-  const size_t bytes = sizeof(float) * (size_t)T * N;
-  float *host = static_cast<float *>(malloc(bytes));                              // util.cc:58-68 pk_alloc
-  if (!host) { Fail(PK_MI355_E_INVALID, "out of host memory"); return; }
-  int rc = ScoreSingleQueue(am, feats, true, prob_scale);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(host, w->d_out, bytes, hipMemcpyDeviceToHost, w->stream);
-  const hipError_t se = hipStreamSynchronize(w->stream);      // (drained whatever happened: `host` may be freed next)
-  if (e == hipSuccess) e = se;
-  if (!rc && e != hipSuccess) { dev_fail(e); rc = PK_MI355_E_DEVICE; }
-  if (!rc && f16) {                 // an operand left the fp16 split's range: fail loudly, deliver nothing
-    const ExecBufs *eb = &w->exec;
-    rc = EvalRange(am, &eb, 1);
-  }
-  if (rc) { free(host); return; }
-  self->log_prob.ncol = T;
-  self->log_prob.nrow = N;
-  self->log_prob.data = host;
+  pk_mi355_batch *b = SingleBatch(am, T);
+  if (!b || pk_mi355_features_set(b, feats, 1, PK_MI355_FEATS_NORMALIZED) || pk_mi355_batch_score(b, prob_scale, 0)) return;
+  pk_mi355_batch_fetch(b, 0, self);
 }
 
 void pk_decodable_destroy(pk_decodable_t *self) {
@@ -642,13 +563,10 @@ int pk_mi355_am_calibrate(pk_mi355_am_t *am, const pk_matrix_t *feats) {
   int rc = UseDevice(am->device);
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(am->mu);
-  if ((rc = EnsureWorkspace(am, feats->ncol, feats->nrow))) return rc;
-  if (am->exps_stale && (rc = RefreshExps(am))) return rc;
-  return CalibrateLoop(am, am->ws->exec, [&]() -> int {
-    if (int rc = ScoreSingleQueue(am, feats, false, 1.0f)) return rc;
-    HIP_TRY(hipStreamSynchronize(am->ws->stream));
-    return 0;
-  });
+  pk_mi355_batch *b = SingleBatch(am, feats->ncol);
+  if (!b) return PK_MI355_E_DEVICE;
+  if ((rc = pk_mi355_features_set(b, feats, 1, PK_MI355_FEATS_NORMALIZED))) return rc;
+  return BatchCalibrateLocked(b);
 }
 
 }  // extern "C"

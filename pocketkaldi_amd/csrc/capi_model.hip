@@ -86,7 +86,8 @@ pk_mi355_am_t *pk_mi355_am_create(void) {
 void pk_mi355_am_destroy(pk_mi355_am_t *am) {
   if (!am) return;
   hipSetDevice(am->device);
-  if (am->proc) pk_mi355_batch_destroy(am->proc);
+  pk_mi355_batch_destroy(am->proc.b);         // (null: nothing)
+  pk_mi355_batch_destroy(am->single.b);
   FreeWorkspace(am->ws);
   hipFree(am->d_blob);
   hipFree(am->d_tid2pdf);

@@ -684,19 +684,6 @@ __global__ __launch_bounds__(kWave * kCmvnWaves) void CmvnKernel(
   }
 }
 
-__global__ void PadTransposeKernel(const float *__restrict__ feats, int T, int dim, int left,
-                                   int right, float *__restrict__ yt, int64_t ldy,
-                                   int64_t col0) {
-  const int total = T + left + right;
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < (int64_t)total * dim;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int c = idx % total, d = idx / total;
-    int t = c - left;
-    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
-    yt[(int64_t)d * ldy + col0 + c] = feats[(int64_t)t * dim + d];
-  }
-}
-
 }  // namespace
 
 // Parity-test hook: LogfRestated on arbitrary inputs.
@@ -776,16 +763,6 @@ void LaunchCmvn(const float *raw, const UttLayout &utts, int num_utts, const flo
   if (num_utts <= 0) return;
   hipLaunchKernelGGL(CmvnKernel, dim3(num_utts), dim3(kWave * kCmvnWaves), 0, stream, raw, utts,
                      d_global41, d_cmvn_tab, left, right, yt, ldy);
-}
-
-void LaunchPadTranspose(const float *feats, int T, int dim, int left, int right, float *yt,
-                        int64_t ldy, int64_t col0, hipStream_t stream) {
-  if (T <= 0) return;
-  int64_t n = (int64_t)(T + left + right) * dim;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(PadTransposeKernel, dim3(blocks), dim3(256), 0, stream, feats, T, dim, left,
-                     right, yt, ldy, col0);
 }
 
 }  // namespace pkmi

@@ -2,8 +2,9 @@
 //   pk_files.cc          (plain C++, pk_files.h) the error state and every file reader: model / config / WAV / graph,
 //                        the graph's split into the decoder's arc lists
 //   capi_model.hip       device selection, model construction, operand exponents
-//   capi_exec.hip        the layer executor and (pk_score.h) the chunk walk over it, the single-utterance workspace, pk_decodable_*
-//   capi_batch.hip       (pk_score.h) the scorer core, the batched device-resident scorer over it, result arenas and views
+//   capi_exec.hip        the layer executor and (pk_score.h) the chunk walk over it, pk_mi355_nnet_propagate, pk_decodable_*
+//   capi_batch.hip       (pk_score.h) the scorer core, the batched device-resident scorer over it (also the model's own
+//                        one-utterance scorers), result arenas and views
 //   capi_stream.hip      (pk_score.h) the online scorer over the same core
 //   capi_io.hip          model files -> device model, the single-utterance front-end entries, test hooks
 //   capi_resample.hip    (pk_resample.h) a rate's polyphase table on the device, the checked plan upload and launch of
@@ -116,7 +117,10 @@ struct DevLinear {
                                    // (hi, lo) rows [Npad][2 Kpad] halves)
 };
 
-struct Workspace;   // the single-utterance workspace (capi_exec.hip)
+struct Workspace;   // the buffers of pk_mi355_nnet_propagate (capi_exec.hip)
+
+// A one-utterance scorer the model owns and remakes, at least doubled, when a call does not fit (capi_batch.hip: EnsureOwned)
+struct OwnedBatch { pk_mi355_batch *b = nullptr; int64_t cap = 0; };
 
 }  // namespace pkhost
 
@@ -145,11 +149,11 @@ struct pk_mi355_am {
   pkhost::ModelKnobs knobs;        // the environment switches as they stood when the model was created
   // The reference's pk_decodable_init / AcousticModel::Compute allocate per call and are re-entrant
   // for a shared model (nnet.cc:149-163 is const); here the single-utterance entry points share
-  // one device workspace per model, so they serialise on this mutex instead.
+  // device buffers the model owns, so they serialise on this mutex instead.  Under mu:
   std::mutex mu;
-  pkhost::Workspace *ws = nullptr; // single-utterance workspace of pk_decodable_init (under mu)
-  struct pk_mi355_batch *proc = nullptr;   // cached 1-utterance scorer of pk_mi355_process_acoustic (under mu)
-  int64_t proc_cap = 0;
+  pkhost::Workspace *ws = nullptr; // pk_mi355_nnet_propagate's buffers (plain, unspliced input)
+  pkhost::OwnedBatch proc;         // pk_mi355_process_acoustic's scorer: audio, cap in samples, made for proc_stats
+  pkhost::OwnedBatch single;       // pk_decodable_init's and pk_mi355_am_calibrate's: features only, cap in frames
   float proc_stats[41] = {0};
 };
 

@@ -45,10 +45,6 @@ void LaunchCmvn(const float *raw, const UttLayout &utts, int num_utts, const flo
                 const CmvnTables *d_cmvn_tab, int left, int right, float *yt, int64_t ldy,
                 hipStream_t stream);
 
-// Already-normalised features [T][dim] (frame-major) -> padded feature-major Yt.
-void LaunchPadTranspose(const float *feats, int T, int dim, int left, int right, float *yt,
-                        int64_t ldy, int64_t col0, hipStream_t stream);
-
 // ---------------------------------------------------------------- affine GEMM
 
 constexpr int kTile = 128;   // block tile edge (both output dimensions)

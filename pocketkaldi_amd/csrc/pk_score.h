@@ -101,6 +101,14 @@ int WalkChunks(const pk_mi355_am *am, const Operand &op, int64_t total_rows, int
 // pass(): queue one scoring pass and synchronise, so that e's range words are the pass's.
 int CalibrateLoop(pk_mi355_am *am, const ExecBufs &e, const std::function<int()> &pass);
 
+// ------------------------------------------------------------------ the single-utterance entries' scorer (capi_batch.hip)
+constexpr int64_t kSingleChunk = 4096;   // frames per pass of pk_decodable_init, pk_mi355_am_calibrate and nnet_propagate
+// am->mu held: the model's one-utterance features batch (pk_mi355_features_batch_create's, without statistics, passes
+// of kSingleChunk rows), remade when `frames` do not fit.  Null: the create failed (its text is in pk_mi355_last_error).
+pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames);
+// pk_mi355_batch_calibrate behind its argument checks, for a caller that holds am->mu
+int BatchCalibrateLocked(pk_mi355_batch *b);
+
 inline void ClearDecodable(pk_decodable_t *out, pk_mi355_am_t *am) { out->am = am; out->log_prob = pk_matrix_t{0, 0, nullptr}; }
 // rows x N floats at src -> a malloc'd matrix in *out (pk_decodable_destroy frees it); verdict() may still withhold
 // them once the stream has been synchronised.  `what` names the entry in the fail text.

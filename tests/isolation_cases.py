@@ -183,7 +183,7 @@ def reuse_healthy_waves(index):
 
 # ------------------------------------------------------------------ single-utterance workspace
 
-SINGLE_POISON_T = 4500                          # two 4 096-row passes (capi_exec.hip: kSingleChunk)
+SINGLE_POISON_T = 4500                          # two 4 096-row passes (pk_score.h: kSingleChunk)
 SINGLE_T = (1, 127, 129, 4097)
 SINGLE_STACKS = ("normalize", "no_softmax", "softmax")
 

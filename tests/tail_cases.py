@@ -35,7 +35,7 @@ FUSED_WIDTHS = [1000, 1024, 1800, 2048, 3000, 3072, 4096, 6100, 6144, 8000, 8192
 KERNEL_WIDTHS = [1, 5, 1023, 1024, 1025, 3072, 3073, 8191, 8192, 8193, 8200]
 REFERENCE_WIDTHS = [3008, 3009, 8000]
 PLAIN_WIDTHS = [1024, 1025, 8193]
-SINGLE_PASS_ROWS = 4096            # pk_decodable_init walks an utterance in passes of 4 096 frames (capi_exec.hip)
+SINGLE_PASS_ROWS = 4096            # pk_decodable_init walks an utterance in passes of 4 096 frames (pk_score.h: kSingleChunk)
 
 PEAKS = [(0.0, -32.0), (0.0, -64.0), (2.0 ** 10, -32.0), (2.0 ** 10, -64.0), (-2.0 ** 10, -32.0), (-2.0 ** 10, -64.0),
          (2.0 ** 127, None), (-2.0 ** 127, None)]

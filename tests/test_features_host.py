@@ -73,6 +73,25 @@ def test_null_and_malformed_arguments_are_invalid_before_any_device_call():
         L.pk_mi355_am_destroy(am)
 
 
+def test_single_utterance_entries_refuse_an_unfinished_model_in_their_old_words():
+    """pk_decodable_init and pk_mi355_am_calibrate answer a null or unfinished model before anything else, with the text
+    they had before they became calls on the model's own features batch (the other texts need a finalized model:
+    test_gpu_single_utterance.py)."""
+    L = pk.lib()
+    m = matrix(np.zeros((3, 40), np.float32))
+    am = L.pk_mi355_am_create()
+    try:
+        for handle in (None, am):
+            d = pk.pk_decodable_t()
+            L.pk_decodable_init(C.byref(d), handle, 0.1, C.byref(m))
+            assert d.log_prob.ncol == 0 and not d.log_prob.data
+            assert L.pk_mi355_last_error_code() == E_STATE and L.pk_mi355_last_error() == b"model not finalized"
+            assert L.pk_mi355_am_calibrate(handle, C.byref(m)) == E_STATE
+            assert L.pk_mi355_last_error() == b"model not finalized"
+    finally:
+        L.pk_mi355_am_destroy(am)
+
+
 class _Scorer(pk.BatchScorer):
     """A BatchScorer whose handle is null: what the wrappers refuse, they refuse before they call the library."""
 

@@ -2,10 +2,10 @@
 line and writes it to profiles/features_layout.json.
 
   layout       tools/ubench/layout_probe (built here if it is missing and there is a hipcc): FeatureLayoutKernel's one
-               launch for 256 utterances x 998 frames x 40 features, L = R = 5, beside PadTransposeKernel launched once
-               per utterance on one stream (the only way there was before), hipEvents around the launches alone, the two
-               alternating in one session, medians of 20 after warm-up; the traffic floor 2 x 4 x 40 bytes per frame at
-               8 TB/s; and whether both wrote the same Yt
+               launch for 256 utterances x 998 frames x 40 features, L = R = 5, hipEvents around the launch alone, median
+               of 20 after warm-up; the traffic floor 2 x 4 x 40 bytes per frame at 8 TB/s; and whether Yt is the padded
+               transpose.  (The comparison with the per-utterance PadTransposeKernel, since removed, is history: the
+               figures recorded in the output file are carried over as layout.pad_transpose_recorded.)
   score        score() of a wave batch (256 x 10 s, model S) beside score() of the same utterances fed as RAW features
                (the wave call's fbank) and as NORMALIZED features (its CMVN) to the same scorer, hipEvents on the
                batch's stream, alternating, medians; the stage times of each (the layout launch is reported in the
@@ -39,7 +39,7 @@ def build_probe():
     csrc = os.path.join(REPO, "pocketkaldi_amd", "csrc")
     subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=" + pkbuild.ARCH, "-std=c++17", "-O3",
                            "-ffp-contract=off", "-w", "-I", csrc, "-I", os.path.join(REPO, "include"), PROBE + ".hip",
-                           os.path.join(csrc, "frontend.hip"), os.path.join(csrc, "features.hip"), "-o", PROBE])
+                           os.path.join(csrc, "features.hip"), "-o", PROBE])
 
 
 def layout_leg(utts, frames):
@@ -121,11 +121,18 @@ def main():
     if a.bench_lines:
         res["bench"] = dict(what="bench.py --gpus 1 of this tree (new) and of the parent commit's tree (old), alternating in one session",
                             **bench_leg(a.bench_lines))
+    try:                                                     # the recorded comparison with the removed kernel stays
+        with open(a.out) as f:
+            old = json.load(f)["layout"]
+        res["layout"]["pad_transpose_recorded"] = old.get("pad_transpose_recorded") or {
+            k: v for k, v in old.items() if k.startswith("pad_transpose") or k in ("launches_before", "feature_layout_us")}
+    except (OSError, ValueError, KeyError):
+        pass
     print(json.dumps(res))
     with open(a.out, "w") as f:
         f.write(json.dumps(res, indent=1) + "\n")
     lay = res["layout"]
-    ok = lay["same_yt"] and res["score"]["same_rows"] and lay["feature_layout_us"] <= lay["pad_transpose_per_utterance_us"]
+    ok = lay["same_yt"] and res["score"]["same_rows"]
     return 0 if ok else 1
 
 

@@ -1,10 +1,10 @@
-// Developer probe (tools/features_bench.py builds and runs it): FeatureLayoutKernel's one launch for a batch beside the
-// only way there was to do this work before it -- PadTransposeKernel once per utterance on one stream -- with hipEvents
-// around the launches alone, the two alternating in one session.  Linked against the library's own kernel units:
+// Developer probe (tools/features_bench.py builds and runs it): FeatureLayoutKernel's one launch for a batch, with
+// hipEvents around the launch alone.  (The kernel it replaced, one launch per utterance, is gone from the library; the
+// comparison with it is recorded in profiles/features_layout.json.)  Linked against the library's own kernel unit:
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I pocketkaldi_amd/csrc -I include tools/ubench/layout_probe.hip \
-//         pocketkaldi_amd/csrc/frontend.hip pocketkaldi_amd/csrc/features.hip -o tools/ubench/layout_probe
+//         pocketkaldi_amd/csrc/features.hip -o tools/ubench/layout_probe
 //   tools/ubench/layout_probe [utts 256] [frames 998] [dim 40] [left 5] [right 5] [reps 20]
-// Prints one JSON object: the medians in microseconds, the traffic floor, and whether both wrote the same Yt.
+// Prints one JSON object: the median in microseconds, the traffic floor, and whether Yt is the padded transpose.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,12 +35,11 @@ int main(int argc, char **argv) {
   std::vector<int64_t> raw_base(U), pad_base(U), wave_off(U, 0);
   std::vector<int32_t> frames(U, T);
   for (int u = 0; u < U; ++u) { raw_base[u] = (int64_t)u * T; pad_base[u] = (int64_t)u * (T + L + R); }
-  float *d_feats, *d_a, *d_b;
+  float *d_feats, *d_a;
   int64_t *d_raw, *d_pad, *d_woff;
   int32_t *d_T;
   CHECK(hipMalloc(&d_feats, sizeof(float) * feats.size()));
   CHECK(hipMalloc(&d_a, sizeof(float) * ldy * D));
-  CHECK(hipMalloc(&d_b, sizeof(float) * ldy * D));
   CHECK(hipMalloc(&d_raw, sizeof(int64_t) * U));
   CHECK(hipMalloc(&d_pad, sizeof(int64_t) * U));
   CHECK(hipMalloc(&d_woff, sizeof(int64_t) * U));
@@ -51,7 +50,6 @@ int main(int argc, char **argv) {
   CHECK(hipMemcpy(d_woff, wave_off.data(), sizeof(int64_t) * U, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_T, frames.data(), sizeof(int32_t) * U, hipMemcpyHostToDevice));
   CHECK(hipMemset(d_a, 0, sizeof(float) * ldy * D));
-  CHECK(hipMemset(d_b, 0, sizeof(float) * ldy * D));
   hipStream_t s;
   hipEvent_t e0, e1;
   CHECK(hipStreamCreate(&s));
@@ -59,11 +57,8 @@ int main(int argc, char **argv) {
   CHECK(hipEventCreate(&e1));
   const pkmi::UttLayout lay{d_woff, d_T, d_raw, d_pad};
   auto one = [&] { pkmi::LaunchFeatureLayout(d_feats, lay, U, T, D, L, R, d_a, ldy, s); };
-  auto many = [&] {
-    for (int u = 0; u < U; ++u) pkmi::LaunchPadTranspose(d_feats + raw_base[u] * D, T, D, L, R, d_b, ldy, pad_base[u], s);
-  };
-  std::vector<float> t_one, t_many;
-  for (int i = 0; i < 3 + reps; ++i) {                      // three warm-up rounds, then alternating
+  std::vector<float> t_one;
+  for (int i = 0; i < 3 + reps; ++i) {                      // three warm-up rounds
     float ms = 0;
     CHECK(hipEventRecord(e0, s));
     one();
@@ -71,24 +66,20 @@ int main(int argc, char **argv) {
     CHECK(hipEventSynchronize(e1));
     CHECK(hipEventElapsedTime(&ms, e0, e1));
     if (i >= 3) t_one.push_back(ms * 1000.0f);
-    CHECK(hipEventRecord(e0, s));
-    many();
-    CHECK(hipEventRecord(e1, s));
-    CHECK(hipEventSynchronize(e1));
-    CHECK(hipEventElapsedTime(&ms, e0, e1));
-    if (i >= 3) t_many.push_back(ms * 1000.0f);
   }
   CHECK(hipGetLastError());
-  std::vector<float> a((size_t)ldy * D), b((size_t)ldy * D);
+  std::vector<float> a((size_t)ldy * D), b((size_t)ldy * D, 0.0f);
   CHECK(hipMemcpy(a.data(), d_a, sizeof(float) * a.size(), hipMemcpyDeviceToHost));
-  CHECK(hipMemcpy(b.data(), d_b, sizeof(float) * b.size(), hipMemcpyDeviceToHost));
+  for (int u = 0; u < U; ++u)                               // the padded transpose on the host (am.cc:73-75)
+    for (int d = 0; d < D; ++d)
+      for (int c = 0; c < T + L + R; ++c)
+        b[(size_t)d * ldy + pad_base[u] + c] = feats[(size_t)(raw_base[u] + std::min(std::max(c - L, 0), T - 1)) * D + d];
   const bool same = memcmp(a.data(), b.data(), sizeof(float) * a.size()) == 0;
   const double bytes = 2.0 * 4.0 * D * (double)U * T, floor_us = bytes / 8e12 * 1e6;
   printf("{\"utts\": %d, \"frames\": %d, \"dim\": %d, \"left\": %d, \"right\": %d, \"reps\": %d, "
-         "\"feature_layout_us\": %.3f, \"feature_layout_min_us\": %.3f, \"pad_transpose_per_utterance_us\": %.3f, "
-         "\"pad_transpose_per_utterance_min_us\": %.3f, \"launches_before\": %d, \"traffic_bytes\": %.0f, \"floor_us_at_8TBps\": %.3f, "
+         "\"feature_layout_us\": %.3f, \"feature_layout_min_us\": %.3f, \"traffic_bytes\": %.0f, \"floor_us_at_8TBps\": %.3f, "
          "\"achieved_GBps\": %.1f, \"same_yt\": %s}\n",
-         U, T, D, L, R, reps, Median(t_one), *std::min_element(t_one.begin(), t_one.end()), Median(t_many),
-         *std::min_element(t_many.begin(), t_many.end()), U, bytes, floor_us, bytes / (Median(t_one) * 1e-6) / 1e9, same ? "true" : "false");
+         U, T, D, L, R, reps, Median(t_one), *std::min_element(t_one.begin(), t_one.end()), bytes, floor_us,
+         bytes / (Median(t_one) * 1e-6) / 1e9, same ? "true" : "false");
   return same ? 0 : 3;
 }
