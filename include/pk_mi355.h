@@ -613,6 +613,39 @@ const float *pk_mi355_stream_loglik_device(const pk_mi355_stream_t *s, int slot,
  * global index of its frame 0.  Synchronous.                                                          */
 int pk_mi355_stream_fetch(pk_mi355_stream_t *s, int slot, pk_decodable_t *out, int *first_frame);
 
+/* Live features.  A feature slot is opened with a kind (PK_MI355_FEATS_NORMALIZED: ready for the
+ * splice; PK_MI355_FEATS_RAW: 40-dim log-mel fbank, the sliding-window CMVN is applied first, carried from step to step
+ * as for audio) and fed frames, frame-major [num_frames][feat_dim], any number per push, 0 included.  With n the frames
+ * received and a the frames scored: a step scores frames [a, max(a, n - R)) while the slot is open and [a, n) after its
+ * close (frame 0 replicated to the left, the last frame to the right, am.cc:73-75) -- the audio slot's rule with "frames
+ * computed" replaced by "frames pushed".  Over a slot's life the rows equal, bit for bit and at every chunking, those of
+ * pk_mi355_features_set + pk_mi355_batch_score on the whole matrix (RAW on a wave's fbank: those of the audio slot on
+ * the wave).  NORMALIZED frames are copied: every bit pattern reaches the first layer as pushed.  Isolation and reuse
+ * hold as for audio; feature slots and audio slots may share a step.  close, step, synchronize, loglik_device and fetch
+ * serve both slot types.
+ *
+ * pk_mi355_features_stream_create: an online scorer without a front-end, for a model of any feat_dim (F32 only).
+ * Capacity: max_step_frames frames pushed, over all slots, between two steps.  global_stats41 may be NULL; given (41
+ * floats, feat_dim must be 40) it enables PK_MI355_FEATS_RAW.  It owns no PCM buffers: pk_mi355_stream_open, _open_rate,
+ * _push and _push_i16 fail on it with PK_MI355_E_STATE.  Device memory per slot: 8 x max(L + R, 1) x feat_dim bytes,
+ * and with statistics the audio object's 96 000 + 160 x (1 + max(L + R, 1)) bytes of CMVN state.                      */
+pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams,
+                                                   int64_t max_step_frames);
+/* Open slot for features of `kind`.  Also valid on an object made by pk_mi355_stream_create (40-dim, both kinds): there
+ * a pushed frame counts as 160 samples against max_step_samples.  The NORMALIZED slots' device state is made at the
+ * first such open.  PK_MI355_E_INVALID: an unknown kind, RAW on an object without statistics; PK_MI355_E_STATE: the
+ * slot is open, or closed and not yet flushed.                                                                       */
+int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind);
+/* Append num_frames x feat_dim floats to an open feature slot; copied, the caller's buffer is free on return.  A push
+ * beyond the step capacity fails with PK_MI355_E_INVALID and consumes nothing; a slot that is not open, or is open for
+ * audio, fails with PK_MI355_E_STATE (as pk_mi355_stream_push does on a feature slot).                               */
+int pk_mi355_stream_push_features(pk_mi355_stream_t *s, int slot, const float *frames, int num_frames);
+/* The model's feature dimension: the length of a pushed frame.  Negative on a null object.                          */
+int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s);
+/* What the slot was last opened as: -1 for audio (also before its first opening), else its PK_MI355_FEATS_* kind.  A
+ * null object or a slot out of range gives PK_MI355_E_INVALID, which is -1 as well, and sets pk_mi355_last_error.     */
+int pk_mi355_stream_slot_kind(const pk_mi355_stream_t *s, int slot);
+
 /* ------------------------------------------------------------------------- */
 /* Online decoder -- Decoder::Decode (decoder.cc:49-70) frame-synchronous across calls: */
 /* partial hypotheses while a stream is live, BestPath (decoder.cc:304-339) at its end. */
@@ -875,6 +908,11 @@ int pk_mi355_online_recognizer_open_rate(pk_mi355_online_recognizer_t *r, int sl
 int pk_mi355_online_recognizer_push(pk_mi355_online_recognizer_t *r, int slot, const float *samples, int num_samples);
 int pk_mi355_online_recognizer_push_i16(pk_mi355_online_recognizer_t *r, int slot, const int16_t *samples, int num_samples);
 int pk_mi355_online_recognizer_close(pk_mi355_online_recognizer_t *r, int slot);
+/* The slot fed with features instead of audio: pk_mi355_stream_open_features / _push_features for the scorer's slot (the
+ * recognizer's model is 40-dim; RAW is what a front-end of the caller's would produce).  Everything after the scorer --
+ * step, partial, stable, result, utterances, endpointing, commit -- is the same.                                     */
+int pk_mi355_online_recognizer_open_features(pk_mi355_online_recognizer_t *r, int slot, int kind);
+int pk_mi355_online_recognizer_push_features(pk_mi355_online_recognizer_t *r, int slot, const float *frames, int num_frames);
 /* pk_mi355_stream_step (prob_scale 0.1), pk_mi355_online_decoder_advance (synchronous), then the text of every slot
  * is refreshed.  Returns what those return: a slot the decoder ended (PK_MI355_E_CAPACITY, ...) stays ended until
  * it is closed, flushed by a step and opened again, while the other slots go on.                                  */

@@ -358,11 +358,20 @@ class Recognizer {
 };
 
 // Online scoring of live streams (pk_mi355_stream_*): PCM pushed per slot in chunks; every
-// Step() scores the frames that became final since the last one, bit for bit what the whole wave gives.
+// Step() scores the frames that became final since the last one, bit for bit what the whole wave gives.  A slot may
+// take features instead (OpenFeatures / PushFeatures): the rows are then the batch scorer's on
+// the whole feature matrix.
 class OnlineScorer {
  public:
+  enum FeaturesOnlyTag { kFeaturesOnly };
   OnlineScorer(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples)
       : s_(pk_mi355_stream_create(am, global_stats41, max_streams, max_step_samples)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // Without a front-end (pk_mi355_features_stream_create): a model of any feature dimension, feature slots only,
+  // capacity in frames.  global_stats41 may be null; given (40-dim models) it enables PK_MI355_FEATS_RAW.
+  OnlineScorer(FeaturesOnlyTag, pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames)
+      : s_(pk_mi355_features_stream_create(am, global_stats41, max_streams, max_step_frames)) {
     if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   ~OnlineScorer() { pk_mi355_stream_destroy(s_); }
@@ -379,6 +388,16 @@ class OnlineScorer {
   Status PushI16(int slot, const int16_t *samples, int num_samples) {
     return Status::FromLast(pk_mi355_stream_push_i16(s_, slot, samples, num_samples));
   }
+  // The slot takes features of `kind` (PK_MI355_FEATS_NORMALIZED or PK_MI355_FEATS_RAW): frames of FeatDim() floats
+  Status OpenFeatures(int slot, int kind = PK_MI355_FEATS_NORMALIZED) {
+    return Status::FromLast(pk_mi355_stream_open_features(s_, slot, kind));
+  }
+  Status PushFeatures(int slot, const float *frames, int num_frames) {
+    return Status::FromLast(pk_mi355_stream_push_features(s_, slot, frames, num_frames));
+  }
+  int FeatDim() const { return pk_mi355_stream_feat_dim(s_); }
+  // -1: audio, else the PK_MI355_FEATS_* kind the slot was last opened with
+  int SlotKind(int slot) const { return pk_mi355_stream_slot_kind(s_, slot); }
   Status Close(int slot) { return Status::FromLast(pk_mi355_stream_close(s_, slot)); }
   // Synchronous: the rows are ready on return.
   Status Step(float prob_scale) { return Status::FromLast(pk_mi355_stream_step(s_, prob_scale, 1)); }
@@ -509,6 +528,13 @@ class OnlineRecognizer {
   }
   Status PushI16(int slot, const int16_t *samples, int num_samples) {
     return Status::FromLast(pk_mi355_online_recognizer_push_i16(r_, slot, samples, num_samples));
+  }
+  // The slot takes 40-dim features instead of audio (raw log-mel fbank by default), [num_frames][40] per push
+  Status OpenFeatures(int slot, int kind = PK_MI355_FEATS_RAW) {
+    return Status::FromLast(pk_mi355_online_recognizer_open_features(r_, slot, kind));
+  }
+  Status PushFeatures(int slot, const float *frames, int num_frames) {
+    return Status::FromLast(pk_mi355_online_recognizer_push_features(r_, slot, frames, num_frames));
   }
   Status Close(int slot) { return Status::FromLast(pk_mi355_online_recognizer_close(r_, slot)); }
   Status Step() { return Status::FromLast(pk_mi355_online_recognizer_step(r_)); }

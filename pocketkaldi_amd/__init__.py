@@ -133,6 +133,9 @@ EXPORTS = [
     "pk_mi355_online_recognizer_utterance_words", "pk_mi355_online_recognizer_utterance_word_segments",
     "pk_mi355_features_batch_create", "pk_mi355_features_set", "pk_mi355_features_set_device",
     "pk_mi355_features_dim", "pk_mi355_recognizer_process_features",
+    "pk_mi355_features_stream_create", "pk_mi355_stream_open_features", "pk_mi355_stream_push_features",
+    "pk_mi355_stream_feat_dim", "pk_mi355_stream_slot_kind",
+    "pk_mi355_online_recognizer_open_features", "pk_mi355_online_recognizer_push_features",
 ]
 
 
@@ -373,6 +376,14 @@ def lib():
     L.pk_mi355_features_set_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int]
     L.pk_mi355_features_dim.argtypes = [C.c_void_p]
     L.pk_mi355_recognizer_process_features.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t), C.c_int, C.c_int]
+    L.pk_mi355_features_stream_create.restype = C.c_void_p
+    L.pk_mi355_features_stream_create.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int64]
+    L.pk_mi355_stream_open_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pk_mi355_stream_push_features.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int]
+    L.pk_mi355_stream_feat_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_stream_slot_kind.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_online_recognizer_open_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pk_mi355_online_recognizer_push_features.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int]
     _lib = L
     return L
 
@@ -714,6 +725,17 @@ def _feature_matrices(feats, feat_dim):
     return arr, keep
 
 
+def _feature_frames(frames, feat_dim):
+    """[n][feat_dim] -> a float32 array the library may read; another shape is refused here, by name."""
+    try:
+        f = _f32(frames)
+    except (TypeError, ValueError) as e:
+        raise PkCodeError(-1, "frames are not a float matrix: %s" % e)
+    if f.ndim != 2 or f.shape[1] != feat_dim:
+        raise PkCodeError(-1, "frames have shape %s, expected [n][%d]" % (f.shape, feat_dim))
+    return f
+
+
 class Decodable:
     """decodable.h:15-41 over the C ABI (what decoder.cc consumes)."""
 
@@ -912,13 +934,15 @@ class FeatureScorer(BatchScorer):
 
 class OnlineScorer:
     """Live PCM in chunks per slot: every step() scores the frames that became final since the last one (frames
-    [a, n - R) of an open slot, the rest after close()), bit for bit what BatchScorer gives on the whole wave."""
+    [a, n - R) of an open slot, the rest after close()), bit for bit what BatchScorer gives on the whole wave.  A slot
+    opened with open_features takes [n][40] frames through push_features instead (OnlineFeatureScorer: any dimension)."""
 
     def __init__(self, am, global_stats, max_streams, max_step_samples):
         g = _f32(global_stats)
         if g.shape != (41,):
             raise PkError("global_stats must have 41 entries")
         self._am = am
+        self._max_streams = int(max_streams)
         self._h = lib().pk_mi355_stream_create(am.handle, _fp(g), int(max_streams), int(max_step_samples))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
@@ -943,6 +967,26 @@ class OnlineScorer:
 
     def rate(self, slot):
         return _check_code(lib().pk_mi355_stream_rate(self._h, int(slot)))
+
+    def open_features(self, slot, kind="normalized"):
+        """The slot takes features instead of audio: kind "normalized" (ready for the splice) or "raw" (40-dim log-mel
+        fbank; the sliding-window CMVN is applied first, carried from step to step)."""
+        _check_code(lib().pk_mi355_stream_open_features(self._h, int(slot), _feature_kind(kind)))
+
+    def push_features(self, slot, frames):
+        """[n][feat_dim] frames, n >= 0."""
+        f = _feature_frames(frames, self.feat_dim())
+        _check_code(lib().pk_mi355_stream_push_features(self._h, int(slot), _fp(f) if f.size else None, f.shape[0]))
+
+    def feat_dim(self):
+        return _check_code(lib().pk_mi355_stream_feat_dim(self._h))
+
+    def slot_kind(self, slot):
+        """None for an audio slot, else "normalized" / "raw": what the slot was last opened as."""
+        if not 0 <= int(slot) < self._max_streams:     # (the entry's -1 is both "audio" and PK_MI355_E_INVALID)
+            raise PkCodeError(-1, "slot %d out of range [0, %d)" % (int(slot), self._max_streams))
+        code = lib().pk_mi355_stream_slot_kind(self._h, int(slot))
+        return None if code < 0 else {v: k for k, v in FEATURE_KINDS.items()}[code]
 
     def push(self, slot, samples):
         """float sample values (as read_wav gives them); an int16 array goes through push_i16."""
@@ -978,6 +1022,24 @@ class OnlineScorer:
         if d.log_prob.ncol == 0:
             return first.value, np.zeros((0, self._am.num_pdfs()), dtype=np.float32)
         return first.value, _take_matrix(d.log_prob)
+
+
+class OnlineFeatureScorer(OnlineScorer):
+    """An OnlineScorer without a front-end, fed by open_features / push_features: any model (any feature dimension),
+    capacity in frames pushed between two steps.  global_stats (41 floats, 40-dim models) enables kind "raw".  The
+    audio entries (open, push, push_i16) fail on it."""
+
+    def __init__(self, am, max_streams, max_step_frames, global_stats=None):
+        g = None
+        if global_stats is not None:
+            g = _f32(global_stats)
+            if g.shape != (41,):
+                raise PkError("global_stats must have 41 entries")
+        self._am = am
+        self._max_streams = int(max_streams)
+        self._h = lib().pk_mi355_features_stream_create(am.handle, None if g is None else _fp(g), int(max_streams), int(max_step_frames))
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
 
 
 class PkCodeError(PkError):
@@ -1491,7 +1553,8 @@ class OnlineRecognizer:
         self.max_streams, self.max_step_samples = int(max_streams), int(max_step_samples)
         L = lib()
         self.am = _Borrowed.of(AcousticModel, L.pk_mi355_online_recognizer_am(self._h), self)
-        self.scorer = _Borrowed.of(OnlineScorer, L.pk_mi355_online_recognizer_stream(self._h), self, free="destroy", _am=self.am)
+        self.scorer = _Borrowed.of(OnlineScorer, L.pk_mi355_online_recognizer_stream(self._h), self, free="destroy", _am=self.am,
+                                   _max_streams=int(max_streams))
         self.decoder = _Borrowed.of(OnlineDecoder, L.pk_mi355_online_recognizer_decoder(self._h), self, free="destroy",
                                     _am=self.am, _fst=None)
         self.symbols = SymbolTable._borrowed(L.pk_mi355_online_recognizer_symtab(self._h), self)
@@ -1528,6 +1591,16 @@ class OnlineRecognizer:
         _check_code(lib().pk_mi355_online_recognizer_push_i16(self._h, int(slot),
                                                               x.ctypes.data_as(C.POINTER(C.c_int16)) if x.size else None,
                                                               x.shape[0]))
+
+    def open_features(self, slot, kind="raw"):
+        """The slot takes 40-dim features instead of audio: "raw" log-mel fbank (what a front-end of the caller's makes)
+        or "normalized" (CMVN already applied)."""
+        _check_code(lib().pk_mi355_online_recognizer_open_features(self._h, int(slot), _feature_kind(kind)))
+
+    def push_features(self, slot, frames):
+        """[n][40] frames, n >= 0."""
+        f = _feature_frames(frames, self.scorer.feat_dim())
+        _check_code(lib().pk_mi355_online_recognizer_push_features(self._h, int(slot), _fp(f) if f.size else None, f.shape[0]))
 
     def close(self, slot):
         """No more samples for slot: the next step() finishes it."""

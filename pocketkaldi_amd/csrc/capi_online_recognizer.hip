@@ -149,6 +149,23 @@ int CheckSlot(const pk_mi355_online_recognizer *r, int slot) {
   return 0;
 }
 
+// open_scorer(): the scorer's own open entry for the slot, audio or features.
+template <class OpenScorer>
+int OpenSlot(pk_mi355_online_recognizer_t *r, int slot, OpenScorer open_scorer) {
+  int rc = CheckSlot(r, slot);
+  if (rc) return rc;
+  // (asked first: a scorer slot, once open, could not be taken back if the decoder then refused its own)
+  if (OnlineDecoderSlotOpen(r->decoder, slot)) return Fail(PK_MI355_E_STATE, "online recognizer: slot %d is open in the decoder", slot);
+  if ((rc = open_scorer()) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
+  r->live[slot] = 1; r->closed[slot] = 0; r->finished[slot] = 0;
+  r->partial[slot].clear(); r->hyp[slot].clear(); r->stable[slot].clear();
+  r->stable_words[slot] = 0;
+  r->per_frame[slot] = 0.0f;
+  r->pieces[slot].clear();
+  r->piece_first[slot] = 0;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -207,18 +224,16 @@ int pk_mi355_online_recognizer_open(pk_mi355_online_recognizer_t *r, int slot) {
 }
 
 int pk_mi355_online_recognizer_open_rate(pk_mi355_online_recognizer_t *r, int slot, int rate) {
-  int rc = CheckSlot(r, slot);
-  if (rc) return rc;
-  // (asked first: a scorer slot, once open, could not be taken back if the decoder then refused its own)
-  if (OnlineDecoderSlotOpen(r->decoder, slot)) return Fail(PK_MI355_E_STATE, "online recognizer: slot %d is open in the decoder", slot);
-  if ((rc = pk_mi355_stream_open_rate(r->stream, slot, rate)) || (rc = pk_mi355_online_decoder_open(r->decoder, slot))) return rc;
-  r->live[slot] = 1; r->closed[slot] = 0; r->finished[slot] = 0;
-  r->partial[slot].clear(); r->hyp[slot].clear(); r->stable[slot].clear();
-  r->stable_words[slot] = 0;
-  r->per_frame[slot] = 0.0f;
-  r->pieces[slot].clear();
-  r->piece_first[slot] = 0;
-  return 0;
+  return OpenSlot(r, slot, [&] { return pk_mi355_stream_open_rate(r->stream, slot, rate); });
+}
+
+int pk_mi355_online_recognizer_open_features(pk_mi355_online_recognizer_t *r, int slot, int kind) {
+  return OpenSlot(r, slot, [&] { return pk_mi355_stream_open_features(r->stream, slot, kind); });
+}
+
+int pk_mi355_online_recognizer_push_features(pk_mi355_online_recognizer_t *r, int slot, const float *frames, int num_frames) {
+  if (!r) return Fail(PK_MI355_E_INVALID, "null online recognizer");
+  return pk_mi355_stream_push_features(r->stream, slot, frames, num_frames);
 }
 
 int pk_mi355_online_recognizer_push(pk_mi355_online_recognizer_t *r, int slot, const float *samples, int num_samples) {

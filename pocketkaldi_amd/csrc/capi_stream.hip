@@ -1,7 +1,7 @@
-// capi_stream.hip -- the online scorer (pk_mi355_stream_*): live PCM pushed in chunks per slot, and every step scores,
-// for every slot, the frames that became final since the last step.  Host C++ over the HIP runtime; the kernels that
-// carry a slot's state from one step to the next are in stream.hip, and why the result is exact is told there
-// (DESIGN.md section 10 walks through one step).
+// capi_stream.hip -- the online scorer (pk_mi355_stream_*): live PCM, or live features, pushed in
+// chunks per slot, and every step scores, for every slot, the frames that became final since the last step.  Host C++
+// over the HIP runtime; the kernels that carry a slot's state from one step to the next are in stream.hip, and why the
+// result is exact is told there (DESIGN.md section 10 walks through one step).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +36,10 @@ struct Slot {
   const DeviceResampleTable *tab = nullptr;
   std::vector<float> native;
   int64_t nat_x0 = 0, n_in = 0, n_prod = 0, reserve = 0;
+  // A feature slot (kind PK_MI355_FEATS_*; -1: audio): its pushes are frames, `pending` holds them frame-major, n counts
+  // the frames handed to a step.  hist_par: the NORMALIZED history buffer that holds the frames below n.
+  int kind = -1;
+  int hist_par = 0;
 };
 
 // the most input samples a native-rate slot carries from one step to the next (Q + max_taps <= 8190 + 74)
@@ -46,7 +50,11 @@ constexpr int64_t kNativeCarryCap = 8448;
 struct pk_mi355_stream {
   ScorerCore core;                    // model, stream, front-end tables, Yt, log-likelihood rows, layer buffers
   int max_streams = 0;
-  int64_t max_step_samples = 0, pending_total = 0;
+  int64_t max_step_samples = 0, pending_total = 0;   // (a features-only object: frames, not samples)
+  bool features_only = false;         // pk_mi355_features_stream_create: no front-end, no PCM buffers
+  bool have_stats = false;            // RAW feature slots are possible
+  int frame_cost = kFrameShift;       // what a pushed frame counts against max_step_samples (features-only: 1)
+  int64_t upload_cap = 0;             // floats of h_upload / d_upload
   std::vector<Slot> slots;
   int hist_len = 1;                   // max(L + R, 1)
   int64_t wave_cap = 0;
@@ -55,6 +63,7 @@ struct pk_mi355_stream {
   float *d_sums = nullptr;            // [slots][40]
   float *d_raw_hist = nullptr;        // [slots][600][40]
   float *d_hist = nullptr;            // [slots][hist_len][40]
+  float *d_feat_hist = nullptr;       // [slots][2][hist_len][feat_dim]: NORMALIZED slots (made at the first such open)
   // per-step staging
   float *h_upload = nullptr, *d_upload = nullptr;    // pushed samples, page-locked -> HBM
   float *d_wave = nullptr;            // segments
@@ -76,6 +85,43 @@ int SlotIndex(const pk_mi355_stream *s, int slot) {
   if (slot < 0 || slot >= s->max_streams) return Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, s->max_streams);
   return 0;
 }
+
+// What every create entry checks of its model before the device is touched.
+bool ModelAllowed(const pk_mi355_am *am) {
+  if (!am) { Fail(PK_MI355_E_INVALID, "null model"); return false; }
+  if (am->precision != PK_MI355_PRECISION_F32) {
+    Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
+    return false;
+  }
+  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
+  return true;
+}
+
+// The per-slot CMVN state and the step's raw rows (audio and RAW slots), the upload staging and the step's plan.
+void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
+  const ScorerCore &c = s->core;
+  const int max_streams = s->max_streams;
+  s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
+                  sizeof(int32_t) * Shift4Cap(c.max_cols);
+  chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
+  if (s->have_stats) {
+    chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
+    chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * kNumBins));
+    chk(hipMalloc(&s->d_hist, sizeof(float) * max_streams * s->hist_len * kNumBins));
+    chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
+  }
+  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * s->upload_cap, hipHostMallocDefault));
+  chk(hipMalloc(&s->d_upload, sizeof(float) * s->upload_cap));
+  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
+  chk(hipMalloc(&s->d_meta, s->meta_bytes));
+}
+
+int EnsureFeatureHistory(pk_mi355_stream *s) {
+  if (s->d_feat_hist) return 0;
+  if (int rc = UseDevice(s->core.device)) return rc;
+  HIP_TRY(hipMalloc(&s->d_feat_hist, sizeof(float) * s->max_streams * 2 * s->hist_len * s->core.am->feat_dim));
+  return 0;
+}
 }  // namespace
 
 namespace pkhost {
@@ -89,12 +135,7 @@ bool StreamSlotFlushed(const pk_mi355_stream *s, int slot) { return slot >= 0 &&
 extern "C" {
 
 pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples) {
-  if (!am) { Fail(PK_MI355_E_INVALID, "null model"); return nullptr; }
-  if (am->precision != PK_MI355_PRECISION_F32) {
-    Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
-    return nullptr;
-  }
-  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (!ModelAllowed(am)) return nullptr;
   if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
   if (!global_stats41 || max_streams <= 0 || max_step_samples <= 0 || max_step_samples > (int64_t)1 << 30) {
     Fail(PK_MI355_E_INVALID, "bad stream capacity");
@@ -104,6 +145,7 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
   pk_mi355_stream *s = new pk_mi355_stream();
   ScorerCore &c = s->core;
   s->max_streams = max_streams; s->max_step_samples = max_step_samples;
+  s->have_stats = true; s->upload_cap = max_step_samples;
   s->slots.resize(max_streams);
   const int pad = am->left + am->right;
   s->hist_len = std::max(pad, 1);
@@ -113,28 +155,48 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
   const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
   CreateCheck chk{"stream_create"};
   CreateScorerCore(&c, am, global_stats41, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
-  s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
-                  sizeof(int32_t) * Shift4Cap(c.max_cols);
-  chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
+  CreateStepBuffers(s, chk);
   chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
-  chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
-  chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * kNumBins));
-  chk(hipMalloc(&s->d_hist, sizeof(float) * max_streams * s->hist_len * kNumBins));
-  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * max_step_samples, hipHostMallocDefault));
-  chk(hipMalloc(&s->d_upload, sizeof(float) * max_step_samples));
   chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
-  chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
-  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
-  chk(hipMalloc(&s->d_meta, s->meta_bytes));
   if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
   return s;
+}
+
+pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames) {
+  if (!ModelAllowed(am)) return nullptr;
+  if (global_stats41 && am->feat_dim != kNumBins) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
+    return nullptr;
+  }
+  if (max_streams <= 0 || max_step_frames <= 0 || max_step_frames > ((int64_t)1 << 30) / am->feat_dim) {
+    Fail(PK_MI355_E_INVALID, "bad stream capacity");
+    return nullptr;
+  }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_stream *s = new pk_mi355_stream();
+  s->max_streams = max_streams; s->max_step_samples = max_step_frames;
+  s->features_only = true; s->have_stats = global_stats41 != nullptr;
+  s->frame_cost = 1; s->upload_cap = max_step_frames * am->feat_dim;
+  s->slots.resize(max_streams);
+  s->hist_len = std::max(am->left + am->right, 1);
+  // a slot's rows are its new frames and the (at most R) frames held back for look-ahead, padded to four
+  CreateCheck chk{"features_stream_create"};
+  CreateScorerCore(&s->core, am, global_stats41, max_streams, max_step_frames, max_step_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  CreateStepBuffers(s, chk);
+  if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
+  return s;
+}
+
+int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  return s->core.am->feat_dim;
 }
 
 void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   if (!s) return;
   hipSetDevice(s->core.device);
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
-  hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist);
+  hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist); hipFree(s->d_feat_hist);
   hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta);
   s->resampler.Free();
   if (s->h_native) hipHostFree(s->h_native);
@@ -150,6 +212,7 @@ int pk_mi355_stream_open(pk_mi355_stream_t *s, int slot) { return pk_mi355_strea
 
 int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
   if (int rc = SlotIndex(s, slot)) return rc;
+  if (s->features_only) return Fail(PK_MI355_E_STATE, "a features-only stream object takes no audio (pk_mi355_stream_open_features)");
   Slot &z = s->slots[slot];
   if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
   const DeviceResampleTable *tab = nullptr;
@@ -167,10 +230,51 @@ int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
   z.n = z.a = z.tail_len = 0;
   z.pending.clear();
   z.rate = rate; z.tab = tab;
+  z.kind = -1;
   z.native.clear();
   z.nat_x0 = z.n_in = z.n_prod = 0;
   s->pending_total -= z.reserve;      // (zero unless the slot's last opening ended without its flush)
   z.reserve = 0;
+  return 0;
+}
+
+int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  if (kind != PK_MI355_FEATS_NORMALIZED && kind != PK_MI355_FEATS_RAW) return Fail(PK_MI355_E_INVALID, "unknown feature kind %d", kind);
+  if (kind == PK_MI355_FEATS_RAW && !s->have_stats)
+    return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics the stream object was made without");
+  Slot &z = s->slots[slot];
+  if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
+  if (kind == PK_MI355_FEATS_NORMALIZED)
+    if (int rc = EnsureFeatureHistory(s)) return rc;
+  z.state = kOpen;
+  z.n = z.a = z.tail_len = 0;
+  z.pending.clear();
+  z.rate = kSampleRate; z.tab = nullptr;
+  z.kind = kind;
+  z.native.clear();
+  z.nat_x0 = z.n_in = z.n_prod = 0;
+  s->pending_total -= z.reserve;      // (as pk_mi355_stream_open_rate)
+  z.reserve = 0;
+  return 0;
+}
+
+int pk_mi355_stream_slot_kind(const pk_mi355_stream_t *s, int slot) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  return s->slots[slot].kind;
+}
+
+int pk_mi355_stream_push_features(pk_mi355_stream_t *s, int slot, const float *frames, int num_frames) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  Slot &z = s->slots[slot];
+  if (z.state != kOpen) return Fail(PK_MI355_E_STATE, "slot %d is not open", slot);
+  if (z.kind < 0) return Fail(PK_MI355_E_STATE, "slot %d is open for audio (pk_mi355_stream_push)", slot);
+  if (num_frames < 0 || (num_frames > 0 && !frames)) return Fail(PK_MI355_E_INVALID, "bad frames");
+  if (s->pending_total + (int64_t)num_frames * s->frame_cost > s->max_step_samples)
+    return Fail(PK_MI355_E_INVALID, "push of %d frames exceeds the step capacity (%lld pending of %lld, a frame counts %d)", num_frames,
+                (long long)s->pending_total, (long long)s->max_step_samples, s->frame_cost);
+  z.pending.insert(z.pending.end(), frames, frames + (size_t)num_frames * s->core.am->feat_dim);
+  s->pending_total += (int64_t)num_frames * s->frame_cost;
   return 0;
 }
 
@@ -181,8 +285,10 @@ int pk_mi355_stream_rate(const pk_mi355_stream_t *s, int slot) {
 
 int pk_mi355_stream_push(pk_mi355_stream_t *s, int slot, const float *samples, int num_samples) {
   if (int rc = SlotIndex(s, slot)) return rc;
+  if (s->features_only) return Fail(PK_MI355_E_STATE, "a features-only stream object takes no audio (pk_mi355_stream_push_features)");
   Slot &z = s->slots[slot];
   if (z.state != kOpen) return Fail(PK_MI355_E_STATE, "slot %d is not open", slot);
+  if (z.kind >= 0) return Fail(PK_MI355_E_STATE, "slot %d is open for features (pk_mi355_stream_push_features)", slot);
   if (num_samples < 0 || (num_samples > 0 && !samples)) return Fail(PK_MI355_E_INVALID, "bad samples");
   if (z.tab) {                         // samples at the slot's rate: what counts is the 16 kHz samples they become
     const int64_t reserve = ResampleNumOutput(z.tab->host, z.n_in + num_samples) - z.n_prod;
@@ -235,29 +341,37 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   StreamRec *recs = reinterpret_cast<StreamRec *>(s->h_meta);
   char *lay_base = s->h_meta + RoundUp(sizeof(StreamRec) * s->max_streams, 256);
   const size_t shift4_at = s->meta_bytes - sizeof(int32_t) * Shift4Cap(c.max_cols);
-  std::vector<int> who, flushed;                      // slots taking part; closed slots with nothing left
+  // Records: audio and RAW slots (StreamAssembleKernel, FbankKernel, StreamCmvnKernel) from the front of the array,
+  // NORMALIZED slots (StreamFeatureLayoutKernel) from its back; rows and columns in slot order whichever the type.
+  std::vector<int> who, at, flushed;                  // slots taking part, their records; closed slots with nothing left
   int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
-  int max_m = 0;
+  int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, max_feat_cols = 0;
+  const int D = am->feat_dim;
   std::vector<ShiftSpan> spans;                       // (end row, column shift) per slot with rows
   for (int slot = 0; slot < s->max_streams; ++slot) {
     const Slot &z = s->slots[slot];
     if (z.state == kFree) continue;
     const bool closed = z.state == kClosed;
     // a native-rate slot's new samples are the outputs that became final (all of them once it is closed)
-    const int new_len = !z.tab ? (int)z.pending.size()
-                               : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
+    // (a feature slot: no samples, an empty segment; its frames are what was pushed)
+    const bool feats = z.kind >= 0, layout = z.kind == PK_MI355_FEATS_NORMALIZED;
+    const int new_len = feats    ? 0
+                        : !z.tab ? (int)z.pending.size()
+                                 : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
     const int seg = z.tail_len + new_len;
-    const int m = pk_mi355_num_frames(seg);
+    const int m = feats ? (int)(z.pending.size() / D) : pk_mi355_num_frames(seg);
     const int n = z.n + m;
     const int b = closed ? n : std::max(z.a, n - R);    // open: R frames of look-ahead held back
     if (new_len == 0 && m == 0 && b == z.a) {
       if (closed) flushed.push_back(slot);
       continue;
     }
-    StreamRec &r = recs[who.size()];
+    const int rec_at = layout ? s->max_streams - 1 - n_back++ : n_front++;
+    StreamRec &r = recs[rec_at];
+    r.kind = z.kind; r.hist_par = z.hist_par;
     r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
     r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
-    r.woff = woff; r.new_off = upl; r.raw_base = raw;
+    r.woff = woff; r.new_off = upl; r.raw_base = layout ? 0 : raw;
     r.col_base = 0; r.cols = 0;
     if (b > z.a) {
       // Rows slot after slot, each padded to four; the slot's columns a - L .. b + R - 1 in a region of RoundUp(b - a, 4)
@@ -269,13 +383,17 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       out += RoundUp(b - z.a, 4);
       col += r.cols;
       spans.push_back({out, shift});
+      if (layout) max_feat_cols = std::max(max_feat_cols, r.cols);
     }
-    woff += seg; upl += new_len; raw += m;
+    woff += seg; upl += feats ? (int64_t)m * D : new_len;
+    if (!layout) raw += m;
     if (z.tab && new_len) native_total += (int64_t)z.native.size();
-    max_m = std::max(max_m, m);
+    if (!feats) { max_m = std::max(max_m, m); ++n_audio; }
+    if (z.kind == PK_MI355_FEATS_RAW) raw_pushed += m;
     who.push_back(slot);
+    at.push_back(rec_at);
   }
-  if (woff > s->wave_cap || upl > s->max_step_samples || native_total > s->native_cap || raw > c.max_frames ||
+  if (woff > s->wave_cap || upl > s->upload_cap || (n_back > 0 && !s->d_feat_hist) || native_total > s->native_cap || raw > c.max_frames ||
       RoundUp(out, kTileF16) > c.max_cols || col > c.max_cols)
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
   // the column shift of every group of four rows (the groups past the last row keep the last shift)
@@ -287,9 +405,12 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   std::vector<ResampleItem> items;
   int64_t native_at = 0;
   for (size_t k = 0; k < who.size(); ++k) {
-    const StreamRec &r = recs[k];
+    const StreamRec &r = recs[at[k]];
     Slot &z = s->slots[r.slot];
-    if (z.tab && r.new_len) {
+    if (z.kind >= 0) {                   // pushed frames, frame-major
+      if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * D);
+      if (r.m && z.kind == PK_MI355_FEATS_NORMALIZED) z.hist_par ^= 1;    // the step writes the other history buffer
+    } else if (z.tab && r.new_len) {
       // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
       const ResampleTable &t = z.tab->host;
       memcpy(s->h_native + native_at, z.native.data(), sizeof(float) * z.native.size());
@@ -306,8 +427,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * r.new_len);
     }
     z.pending.clear();
-    z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
-    z.tail_par ^= 1;
+    if (z.kind < 0) {
+      z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
+      z.tail_par ^= 1;
+    }
     z.n = r.n_old + r.m;
     z.a = r.b;
     z.last_first = r.a; z.last_count = r.b - r.a;
@@ -322,7 +445,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   {
     int64_t o = 0;
     for (size_t k = 0; k < who.size(); ++k) {
-      Slot &z = s->slots[recs[k].slot];
+      Slot &z = s->slots[who[k]];
       z.last_out = o;
       o += RoundUp(z.last_count, 4);
     }
@@ -333,7 +456,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   int64_t *h_woff = reinterpret_cast<int64_t *>(lay_base);
   int64_t *h_rawb = h_woff + s->max_streams;
   int32_t *h_T = reinterpret_cast<int32_t *>(h_rawb + s->max_streams);
-  for (int k = 0; k < K; ++k) { h_woff[k] = recs[k].woff; h_rawb[k] = recs[k].raw_base; h_T[k] = recs[k].m; }
+  for (int k = 0; k < n_front; ++k) { h_woff[k] = recs[k].woff; h_rawb[k] = recs[k].raw_base; h_T[k] = recs[k].kind < 0 ? recs[k].m : 0; }
   // ---- uploads (one for the samples, one for the plan) and the launches, all on the stream
   if (upl) HIP_TRY(hipMemcpyAsync(s->d_upload, s->h_upload, sizeof(float) * upl, hipMemcpyHostToDevice, c.stream));
   if (native_at) {                     // the native-rate slots' new 16 kHz samples, written over their part of d_upload
@@ -348,11 +471,20 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   const int64_t *d_woff = reinterpret_cast<const int64_t *>(d_lay);
   const int64_t *d_rawb = d_woff + s->max_streams;
   const int32_t *d_T = reinterpret_cast<const int32_t *>(d_rawb + s->max_streams);
-  LaunchStreamAssemble(d_recs, K, s->d_upload, s->d_tails, s->d_wave, c.stream);
-  UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
-  LaunchFbank(s->d_wave, nullptr, lay, K, max_m, c.d_tables, s->d_rows, c.stream);
-  LaunchStreamCmvn(d_recs, K, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
-                   c.d_yt, c.ldy, c.stream);
+  // A step of audio slots alone: the three launches below, over all K records, as ever.  RAW slots ride along with an
+  // empty segment and T = 0; their pushed rows reach d_rows by one launch more per step.
+  if (n_audio > 0) {
+    LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
+    UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
+    LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
+  }
+  if (raw_pushed > 0) LaunchStreamRawRows(d_recs, n_front, s->d_upload, s->d_rows, c.stream);
+  if (n_front > 0)
+    LaunchStreamCmvn(d_recs, n_front, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
+                     c.d_yt, c.ldy, c.stream);
+  if (n_back > 0)
+    LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
+                              c.d_yt, c.ldy, c.stream);
   const Operand op{c.d_yt, nullptr, c.ldy, ZeroSource(c), reinterpret_cast<const int32_t *>(s->d_meta + shift4_at)};
   const Lane lane{c.stream, &c.exec};
   if ((rc = WalkChunks(am, op, total_rows, c.chunk, &lane, 1, true, prob_scale, c.d_ll, nullptr))) return rc;

@@ -23,6 +23,9 @@ struct StreamRec {
   int32_t a, b;        // rows scored: frames [a, b)
   int32_t closed;      // 1: the right edge is the last frame (am.cc:73-75)
   int32_t cols;        // columns of the slot's region of Yt: RoundUp(b - a, 4) + L + R (0: no rows)
+  int32_t kind;        // -1: audio; PK_MI355_FEATS_RAW / _NORMALIZED: a feature slot (tail_len = new_len = 0, an empty
+                       // segment; m = frames pushed since the last step, [m][D] floats at new_off of the upload staging)
+  int32_t hist_par;    // NORMALIZED: the slot's history buffer that holds the frames below n_old (the step writes the other one)
   int64_t woff;        // first sample of the segment in the wave staging
   int64_t new_off;     // first pushed sample in the upload staging
   int64_t raw_base;    // first row of the slot's new frames in the step's raw rows
@@ -33,6 +36,16 @@ struct StreamRec {
 void LaunchStreamAssemble(const StreamRec *recs, int n, const float *upload, float *tails, float *wave, hipStream_t stream);
 void LaunchStreamCmvn(const StreamRec *recs, int n, float *rows, const float *g, const CmvnTables *tab, float *sums,
                       float *raw_hist, float *hist, int hist_len, int left, int right, float *yt, int64_t ldy, hipStream_t stream);
+
+// launchers (stream.hip), feature slots.  LaunchStreamRawRows: one workgroup for each of n records; those of kind
+// PK_MI355_FEATS_RAW have their m pushed rows copied from the upload staging to rows + 40 raw_base, where FbankKernel
+// would have written them.  LaunchStreamFeatureLayout: (tiles of 64 columns) x (n records, all NORMALIZED): the slot's
+// region of Yt[dim][ldy] as StreamCmvnKernel defines it, frame f from the new frames (f >= n_old) or from the slot's
+// history hist[slot][hist_par][f % hist_len][dim]; the other history buffer receives frames [max(n - hist_len, 0), n).
+// max_cols: the widest region.  The caller has checked every base and count against the buffers.
+void LaunchStreamRawRows(const StreamRec *recs, int n, const float *upload, float *rows, hipStream_t stream);
+void LaunchStreamFeatureLayout(const StreamRec *recs, int n, int max_cols, const float *upload, float *hist, int hist_len, int dim,
+                               int left, int right, float *yt, int64_t ldy, hipStream_t stream);
 
 // launcher (features.hip): features frame-major [sum T][dim], utterance u's rows from raw_base[u] on -> the padded
 // feature-major Yt[dim][ldy], frame t at column pad_base[u] + left + t, the first / last frame replicated into the

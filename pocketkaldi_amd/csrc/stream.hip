@@ -6,6 +6,10 @@
 // so that float vector and the raw frames still inside the 600-frame window are its whole state; the splice
 // (am.cc:65-88) needs R frames of look-ahead and clamps at frame 0 and at the last frame only.  Every frame's
 // log-likelihoods therefore equal the whole-utterance batch scorer's, bit for bit, whatever the chunk sizes.
+//
+// Feature slots enter behind the front-end: RAW rows are copied to where FbankKernel would have
+// written them (StreamRawRowsKernel) and StreamCmvnKernel runs on them unchanged; NORMALIZED frames of any dimension
+// are laid out by StreamFeatureLayoutKernel, which carries the left context in two history buffers used in turn.
 #include <hip/hip_runtime.h>
 
 #include "pk_score.h"
@@ -97,6 +101,89 @@ __global__ __launch_bounds__(kWave) void StreamCmvnKernel(const StreamRec *__res
   }
 }
 
+// ------------------------------------------------------------------ feature slots
+
+// One workgroup per record: a RAW slot's pushed rows go from the upload staging to where FbankKernel would have written
+// them, the slot's raw rows of the step; StreamCmvnKernel then finds them there.  A copy through uint32_t.
+__global__ __launch_bounds__(256) void StreamRawRowsKernel(const StreamRec *__restrict__ recs, const uint32_t *__restrict__ upload,
+                                                           uint32_t *__restrict__ rows) {
+  const StreamRec r = recs[blockIdx.x];
+  if (r.kind != PK_MI355_FEATS_RAW) return;
+  const uint32_t *src = upload + r.new_off;
+  uint32_t *dst = rows + r.raw_base * kNumBins;
+  for (int i = threadIdx.x; i < r.m * kNumBins; i += blockDim.x) dst[i] = src[i];
+}
+
+constexpr int kSflTile = 64;            // columns per workgroup, features per block
+constexpr int kSflLd = kSflTile + 1;    // odd leading dimension of the LDS tile (features.hip tells why)
+constexpr int kSflThreads = 256;
+
+// NORMALIZED slots: what StreamCmvnKernel's column loop does, without the arithmetic and for any D, shaped after
+// FeatureLayoutKernel (features.hip).  One 256-thread workgroup per (record, tile of 64 columns of the slot's region);
+// the features are walked in blocks of 64 through an LDS tile: a column's features are read as one run contiguous in
+// memory (neighbouring columns are neighbouring frames, so for D <= 64 the runs join), and written with lane = column,
+// 256 contiguous bytes per wave and feature row.  Column c of the region holds frame a - L + c, clamped to frame 0 and
+// to frame n - 1 (an open slot's last column is frame b + R - 1 <= n - 1 already: the clamp binds once it is closed);
+// the columns from (b - a) + L + R on are zero.  Frame f comes from the step's new frames when f >= n_old, otherwise from
+// the slot's history: the ring [f % hist_len][D] of buffer hist_par, read only for f < n_old, so only when n_old > 0,
+// and f >= a - L >= n_old - R - L lies inside it.
+//
+// The history is handed on without workgroups talking to each other: every workgroup of the slot reads buffer hist_par,
+// and the slot's first workgroup writes frames [max(n - hist_len, 0), n) -- the new ones, and those of the old ring that
+// survive -- into the OTHER buffer, which nobody reads in this launch.  The host flips hist_par when m > 0; with m == 0
+// (a flush served from history alone) nothing is written and nothing flips.  A pure copy through uint32_t: NaN payloads,
+// -0.0 and subnormals arrive as they were.  Plain dword accesses, __syncthreads() only; every condition around a
+// barrier is uniform over the workgroup.
+__global__ __launch_bounds__(kSflThreads) void StreamFeatureLayoutKernel(const StreamRec *__restrict__ recs, int num_recs,
+                                                                         const uint32_t *__restrict__ upload, uint32_t *__restrict__ hist,
+                                                                         int hist_len, int D, int left, int right,
+                                                                         uint32_t *__restrict__ yt, int64_t ldy) {
+  __shared__ uint32_t tile[kSflTile * kSflLd];          // [column][feature of the block]
+  const int tid = threadIdx.x;
+  const int c0 = blockIdx.x * kSflTile;
+  for (int k = blockIdx.y; k < num_recs; k += gridDim.y) {
+    const StreamRec r = recs[k];
+    const int n = r.n_old + r.m;
+    const uint32_t *fresh = upload + r.new_off;                                            // frames n_old .. n - 1, [m][D]
+    const uint32_t *old = hist + ((int64_t)r.slot * 2 + r.hist_par) * hist_len * D;        // frames below n_old
+    if (blockIdx.x == 0 && r.m > 0) {
+      uint32_t *next = hist + ((int64_t)r.slot * 2 + (r.hist_par ^ 1)) * hist_len * D;
+      const int f0 = n - hist_len > 0 ? n - hist_len : 0;
+      for (int i = tid; i < (n - f0) * D; i += kSflThreads) {
+        const int j = i / D, d = i - j * D, f = f0 + j;
+        const uint32_t *src = f >= r.n_old ? fresh + (int64_t)(f - r.n_old) * D : old + (int64_t)(f % hist_len) * D;
+        next[(int64_t)(f % hist_len) * D + d] = src[d];
+      }
+    }
+    if (c0 >= r.cols) continue;                                                            // past the slot's region (or no rows)
+    const int nc = r.cols - c0 < kSflTile ? r.cols - c0 : kSflTile;                        // columns of this tile
+    const int real = r.b - r.a + left + right;
+    uint32_t *col0 = yt + r.col_base + c0;
+    for (int d0 = 0; d0 < D; d0 += kSflTile) {
+      const int nd = D - d0 < kSflTile ? D - d0 : kSflTile;                                // features of this block
+      const int w = D <= kSflTile ? D : kSflTile;                                          // (D <= 64: one block, nd == D)
+      for (int i = tid; i < nc * w; i += kSflThreads) {
+        const int c = i / w, d = i - c * w;
+        if (d >= nd) continue;
+        uint32_t v = 0;
+        if (c0 + c < real) {
+          int f = r.a - left + c0 + c;
+          f = f < 0 ? 0 : f;
+          f = f > n - 1 ? n - 1 : f;
+          const uint32_t *src = f >= r.n_old ? fresh + (int64_t)(f - r.n_old) * D : old + (int64_t)(f % hist_len) * D;
+          v = src[d0 + d];
+        }
+        tile[c * kSflLd + d] = v;
+      }
+      __syncthreads();
+      const int c = tid & 63;                                                              // lane = column
+      if (c < nc)
+        for (int d = tid >> 6; d < nd; d += kSflThreads / 64) col0[(int64_t)(d0 + d) * ldy + c] = tile[c * kSflLd + d];
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace
 
 // ================================================================== launchers (pk_score.h)
@@ -111,6 +198,21 @@ void LaunchStreamCmvn(const StreamRec *recs, int n, float *rows, const float *g,
                       float *raw_hist, float *hist, int hist_len, int left, int right, float *yt, int64_t ldy, hipStream_t stream) {
   hipLaunchKernelGGL(StreamCmvnKernel, dim3(n), dim3(kWave), 0, stream, recs, rows, g, tab, sums, raw_hist, hist, hist_len,
                      left, right, yt, ldy);
+}
+
+void LaunchStreamRawRows(const StreamRec *recs, int n, const float *upload, float *rows, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(StreamRawRowsKernel, dim3(n), dim3(256), 0, stream, recs, reinterpret_cast<const uint32_t *>(upload),
+                     reinterpret_cast<uint32_t *>(rows));
+}
+
+void LaunchStreamFeatureLayout(const StreamRec *recs, int n, int max_cols, const float *upload, float *hist, int hist_len, int dim,
+                               int left, int right, float *yt, int64_t ldy, hipStream_t stream) {
+  if (n <= 0 || dim <= 0) return;
+  // (a slot without rows still has its history written: one tile at least)
+  const dim3 grid(max_cols > kSflTile ? (max_cols + kSflTile - 1) / kSflTile : 1, n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(StreamFeatureLayoutKernel, grid, dim3(kSflThreads), 0, stream, recs, n, reinterpret_cast<const uint32_t *>(upload),
+                     reinterpret_cast<uint32_t *>(hist), hist_len, dim, left, right, reinterpret_cast<uint32_t *>(yt), ldy);
 }
 
 }  // namespace pkmi

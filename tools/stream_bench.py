@@ -31,6 +31,12 @@ advance every stream's endpoint() is read, and the streams whose rule fired are 
 window_ms gains `endpoint`, the time of those reads and cuts, and the record `endpoint.cuts`.  What the mode costs is
 `advance` (the second kernel and the copy of its records are inside the synchronous advance) plus `endpoint`, against a
 run without the flag: profiles/stream_endpoint.json.
+
+--features normalized|raw feeds the same streams as features instead of audio: every stream pushes
+the frames of one chunk per step (10 frames for 100 ms) into a features-only scorer (pk.OnlineFeatureScorer; with the
+statistics for raw).  The features are the batch scorer's on the same waves -- its fbank for raw, its CMVN'd features for
+normalized -- so the check against BatchScorer stays bit for bit.  profiles/stream_features_bench.json holds the audio
+leg and both feature legs of one session.
 """
 import argparse
 import json
@@ -58,6 +64,7 @@ def main():
     ap.add_argument("--commit", action="store_true")
     ap.add_argument("--endpoint", action="store_true")
     ap.add_argument("--trace-capacity", type=int, default=0)
+    ap.add_argument("--features", choices=["normalized", "raw"], default=None)
     a = ap.parse_args()
     a.decode = a.decode or a.commit or a.endpoint
 
@@ -68,7 +75,18 @@ def main():
     waves = [synth.utterance(u, a.seconds) for u in range(a.streams)]
     chunk = int(round(a.chunk_ms * synth.SAMPLE_RATE / 1000.0))
     nsteps = (len(waves[0]) + chunk - 1) // chunk
-    sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk)
+    feats = None
+    if a.features:
+        bs = pk.BatchScorer(am, g, a.streams, sum(len(w) for w in waves))
+        bs.set_waves(waves)
+        bs.score(0.1)
+        feats = [(bs.fetch_fbank if a.features == "raw" else bs.fetch_cmvn)(u) for u in range(a.streams)]
+        bs.close()
+        chunk = int(round(a.chunk_ms / 10.0))                  # frames per step
+        nsteps = (feats[0].shape[0] + chunk - 1) // chunk
+        sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None)
+    else:
+        sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk)
     dec = None
     if a.decode:
         import tempfile
@@ -89,7 +107,7 @@ def main():
 
     def run(record, nsteps=nsteps):
         for s in range(a.streams):
-            sc.open(s)
+            sc.open_features(s, a.features) if feats else sc.open(s)
             if dec:
                 dec.open(s)
         walls, frames, rows0 = [], 0, []
@@ -99,7 +117,9 @@ def main():
         for k in range(nsteps + 1):
             t0 = time.perf_counter()
             for s in range(a.streams):
-                if k < nsteps:
+                if k < nsteps and feats:
+                    sc.push_features(s, feats[s][k * chunk:(k + 1) * chunk])
+                elif k < nsteps:
                     sc.push(s, waves[s][k * chunk:(k + 1) * chunk])
                 else:
                     sc.close(s)
@@ -140,6 +160,7 @@ def main():
     ok = np.concatenate(rows0).tobytes() == bs.fetch(0).log_prob().tobytes()
     rec = {
         "streams": a.streams, "seconds": a.seconds, "chunk_ms": a.chunk_ms, "steps": len(walls),
+        "input": "features, %s, %d frames a push" % (a.features, chunk) if feats else "audio",
         "model": "S (440 -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax",
         "device": torch.cuda.get_device_name(0),
         "step_ms": {"median": float(np.median(walls_ms)), "p90": float(np.percentile(walls_ms, 90)),
