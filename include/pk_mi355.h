@@ -214,6 +214,7 @@ int pk_mi355_load(const char *config_path, int precision, pk_mi355_am_t **am_out
 
 int pk_mi355_am_num_pdfs(const pk_mi355_am_t *am);      /* am.h:38 */
 int pk_mi355_am_input_dim(const pk_mi355_am_t *am);     /* spliced width */
+int pk_mi355_am_feat_dim(const pk_mi355_am_t *am);      /* per-frame feature dimension: input_dim / (left + 1 + right); 0: null or not finalized */
 int pk_mi355_am_transition_to_pdf(const pk_mi355_am_t *am, int trans_id); /* am.h:30-32 */
 
 /* The packed device weight blob (weights, biases, log-priors), for the one RCCL
@@ -330,25 +331,59 @@ int pk_mi355_batch_set_waves_device(pk_mi355_batch_t *b, const float *d_samples,
  * of num_utts utterances of T_u frames, whatever it was fed.  (Named with a prefix of their own, as
  * pk_mi355_resample_set_waves is: they are batch entries with another source in front.)                          */
 #define PK_MI355_FEATS_NORMALIZED 0   /* ready for the splice, as pk_decodable_init takes them */
-#define PK_MI355_FEATS_RAW        1   /* raw 40-dim log-mel fbank: the sliding-window CMVN is applied first */
+#define PK_MI355_FEATS_RAW        1   /* raw features (40-dim log-mel fbank, or any dimension on an object made by a
+                                         _create_stats entry): the sliding-window CMVN is applied first */
 
 /* A batch scorer without a front-end.  Any model (any feat_dim; F16X3 / F16: a multiple of 8, as pk_decodable_init).
  * global_stats41 may be NULL; given (41 floats, feat_dim must be 40) it enables PK_MI355_FEATS_RAW.  Capacity in
  * frames, not samples.  The wave entries fail with PK_MI355_E_STATE on such a batch.                             */
 pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41,
                                                  int max_utts, int64_t max_total_frames);
+/* The same with statistics at the model's own dimension: global_stats holds feat_dim sums, then
+ * the frame count, and stats_len must be pk_mi355_am_feat_dim(am) + 1 -- otherwise PK_MI355_E_INVALID, whose text names
+ * both numbers; a null model or null statistics are refused too.  At feat_dim == 40 it is the entry above.  At any other
+ * dimension PK_MI355_FEATS_RAW runs cmvn.cc's rule (mean normalisation, elementwise in the feature index) column by
+ * column: column d of the result is, bit for bit, what the 40-dim path gives for a matrix that holds that column, with
+ * the same sum and count.                                                                                          */
+pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len,
+                                                       int max_utts, int64_t max_total_frames);
 /* feats[u]: nrow = feat_dim, ncol = T_u, memory [T_u][feat_dim] (the pk_matrix_t image pk_decodable_init takes);
  * copied to HBM.  T_u = 0 is an utterance without rows.  Also on a batch made by pk_mi355_batch_create (feat_dim 40,
  * both kinds, capacity: the frames its sample capacity can produce, max_total_samples / 160 + max_utts); a later
  * set_waves* switches such a batch back to audio.  PK_MI355_E_INVALID, before anything is copied or launched: a null
- * argument, nrow != feat_dim, a negative ncol, an unknown kind, RAW without statistics or with feat_dim != 40, more
- * utterances, frames or columns than the capacity; the batch keeps what it held.                                  */
+ * argument, nrow != feat_dim, a negative ncol, an unknown kind, RAW on a batch without statistics (with feat_dim != 40
+ * only pk_mi355_features_batch_create_stats gives it some), more utterances, frames or columns than the capacity; the
+ * batch keeps what it held.                                                                                       */
 int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num_utts, int kind);
 /* Same, features already in HBM, utterance after utterance, [sum T][feat_dim] (4-byte aligned).  NORMALIZED: not
  * copied, must stay valid until scored.  RAW: one device-to-device copy on the batch's stream.                   */
 int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, const int *num_frames,
                                        int num_utts, int kind);
 int pk_mi355_features_dim(const pk_mi355_batch_t *b);
+
+/* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
+ * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
+ * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is
+ * read entry by entry, and every size a file states is checked against the bytes that remain before anything is
+ * allocated.  PK_MI355_E_IO: a file that cannot be opened, a truncated object, a size byte other than 4, negative
+ * dimensions, a ragged text matrix, garbage where a key or token belongs.  PK_MI355_E_INVALID: well-formed input this
+ * reader does not take, named in pk_mi355_last_error (an scp line by its number): compressed matrices ("CM ", "CM2 ",
+ * "CM3 ": write them uncompressed), vectors ("FV ", "DV "), scp row or column ranges ("path[a:b]"), pipes and "-".  */
+typedef struct pk_mi355_ark pk_mi355_ark_t;
+/* spec: "ark:<path>", "scp:<path>" (options as in "ark,t:" are skipped), or a bare path: a ".scp" suffix means a script
+ * file ("<key> <path>" or "<key> <path>:<offset>" per line, paths opened as given), anything else an archive.  NULL on
+ * failure.                                                                                                          */
+pk_mi355_ark_t *pk_mi355_ark_open(const char *spec);
+/* Advance: 1 for an entry, 0 at the end, a negative code for an error (every later call repeats the code).         */
+int pk_mi355_ark_next(pk_mi355_ark_t *h);
+/* The current entry's key ("" when there is none) and matrix: view->nrow = the feature dimension, view->ncol = the
+ * frames, memory [frames][dim] -- the image pk_mi355_features_set takes.  Both are valid until the next call on h.  */
+const char *pk_mi355_ark_key(const pk_mi355_ark_t *h);
+int pk_mi355_ark_matrix(const pk_mi355_ark_t *h, pk_matrix_t *view);
+void pk_mi355_ark_close(pk_mi355_ark_t *h);
+/* One keyless object from "path" or "path:offset" (a global CMVN statistics file, say): a handle whose current entry
+ * is that object (pk_mi355_ark_matrix; pk_mi355_ark_next gives 0), to be closed as any other.  NULL on failure.     */
+pk_mi355_ark_t *pk_mi355_ark_read_object(const char *rxfilename);
 
 /* Run fbank -> CMVN -> nnet -> log-likelihood tail for the current utterances.
  * Asynchronous on the batch's stream unless sync != 0.  Results stay in HBM.     */
@@ -631,6 +666,13 @@ int pk_mi355_stream_fetch(pk_mi355_stream_t *s, int slot, pk_decodable_t *out, i
  * and with statistics the audio object's 96 000 + 160 x (1 + max(L + R, 1)) bytes of CMVN state.                      */
 pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams,
                                                    int64_t max_step_frames);
+/* The same with statistics at the model's own dimension (feat_dim sums, then the count; stats_len must be
+ * pk_mi355_am_feat_dim(am) + 1, else PK_MI355_E_INVALID naming both numbers; null statistics are refused).  At
+ * feat_dim == 40 the object is the one the entry above makes.  At any other dimension a RAW slot carries feat_dim
+ * running sums and a ring of the last 600 raw frames: 4 x feat_dim + 2400 x feat_dim bytes per slot, beside the
+ * 8 x max(L + R, 1) x feat_dim bytes of every feature slot.                                                        */
+pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len,
+                                                         int max_streams, int64_t max_step_frames);
 /* Open slot for features of `kind`.  Also valid on an object made by pk_mi355_stream_create (40-dim, both kinds): there
  * a pushed frame counts as 160 samples against max_step_samples.  The NORMALIZED slots' device state is made at the
  * first such open.  PK_MI355_E_INVALID: an unknown kind, RAW on an object without statistics; PK_MI355_E_STATE: the

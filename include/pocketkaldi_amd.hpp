@@ -139,6 +139,7 @@ class AcousticModel {
 
   int TransitionIdToPdfId(int transition_id) const { return pk_mi355_am_transition_to_pdf(am_, transition_id); }
   int num_pdfs() const { return pk_mi355_am_num_pdfs(am_); }
+  int feat_dim() const { return pk_mi355_am_feat_dim(am_); }   // 0 until the model is finalized
 
   // src/am.cc:90-115: frames {nrow = feat_dim, ncol = T} -> loglikelihood {nrow = num_pdfs,
   // ncol = T} = log(max(p, 1e-20)) - log prior  (no acoustic scale; pk_decodable_init applies it)
@@ -374,6 +375,12 @@ class OnlineScorer {
       : s_(pk_mi355_features_stream_create(am, global_stats41, max_streams, max_step_frames)) {
     if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // The same with statistics at the model's own dimension (pk_mi355_features_stream_create_stats, DESIGN.md section
+  // 15): global_stats holds feat_dim sums, then the count, stats_len = feat_dim + 1; RAW slots at any dimension.
+  OnlineScorer(FeaturesOnlyTag, pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_streams, int64_t max_step_frames)
+      : s_(pk_mi355_features_stream_create_stats(am, global_stats, stats_len, max_streams, max_step_frames)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   ~OnlineScorer() { pk_mi355_stream_destroy(s_); }
   OnlineScorer(const OnlineScorer &) = delete;
   OnlineScorer &operator=(const OnlineScorer &) = delete;
@@ -412,6 +419,51 @@ class OnlineScorer {
 
  private:
   pk_mi355_stream_t *s_;
+  Status status_;
+};
+
+// Kaldi archives and script files of float matrices (pk_mi355_ark_*), entry by entry:
+//   ArkReader r("scp:feats.scp");  while (r.Next()) use(r.Key(), r.Matrix());  if (!r.last_status().ok()) ...
+class ArkReader {
+ public:
+  // spec: "ark:<path>", "scp:<path>" or a bare path (a ".scp" suffix means a script file)
+  explicit ArkReader(const std::string &spec) : h_(pk_mi355_ark_open(spec.c_str())) {
+    if (!h_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  ~ArkReader() { pk_mi355_ark_close(h_); }
+  ArkReader(const ArkReader &) = delete;
+  ArkReader &operator=(const ArkReader &) = delete;
+
+  // True: there is a current entry.  False: the end, or an error (last_status() tells which).
+  bool Next() {
+    if (!h_) return false;
+    const int rc = pk_mi355_ark_next(h_);
+    if (rc < 0) status_ = Status::FromLast(rc);
+    return rc == 1;
+  }
+  std::string Key() const { return pk_mi355_ark_key(h_); }
+  // {nrow = the feature dimension, ncol = frames}, memory [frames][dim]; valid until the next call on this reader
+  pk_matrix_t Matrix() const {
+    pk_matrix_t m = {0, 0, nullptr};
+    if (h_) pk_mi355_ark_matrix(h_, &m);
+    return m;
+  }
+  // One keyless object ("path" or "path:offset": a global CMVN statistics file, say), row-major into *values
+  static Status ReadObject(const std::string &rxfilename, std::vector<float> *values, int *rows, int *cols) {
+    pk_mi355_ark_t *h = pk_mi355_ark_read_object(rxfilename.c_str());
+    if (!h) return Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+    pk_matrix_t m = {0, 0, nullptr};
+    pk_mi355_ark_matrix(h, &m);
+    values->assign(m.data, m.data + static_cast<size_t>(m.ncol) * m.nrow);
+    *rows = m.ncol;
+    *cols = m.nrow;
+    pk_mi355_ark_close(h);
+    return Status();
+  }
+  const Status &last_status() const { return status_; }
+
+ private:
+  pk_mi355_ark_t *h_;
   Status status_;
 };
 

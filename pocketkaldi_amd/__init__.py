@@ -81,7 +81,7 @@ EXPORTS = [
     "pk_mi355_last_error", "pk_mi355_set_device", "pk_decodable_init", "pk_decodable_destroy",
     "pk_decodable_loglikelihood", "pk_decodable_islastframe", "pk_mi355_am_create",
     "pk_mi355_am_destroy", "pk_mi355_am_add_linear", "pk_mi355_am_add_layer",
-    "pk_mi355_am_finalize", "pk_mi355_am_set_precision", "pk_mi355_am_precision", "pk_mi355_am_set_softmax", "pk_mi355_am_softmax", "pk_mi355_am_read", "pk_mi355_load", "pk_mi355_am_num_pdfs", "pk_mi355_am_input_dim",
+    "pk_mi355_am_finalize", "pk_mi355_am_set_precision", "pk_mi355_am_precision", "pk_mi355_am_set_softmax", "pk_mi355_am_softmax", "pk_mi355_am_read", "pk_mi355_load", "pk_mi355_am_num_pdfs", "pk_mi355_am_input_dim", "pk_mi355_am_feat_dim",
     "pk_mi355_am_transition_to_pdf", "pk_mi355_am_blob_device_ptr", "pk_mi355_am_blob_bytes",
     "pk_mi355_nnet_propagate", "pk_mi355_num_frames", "pk_mi355_fbank_compute",
     "pk_mi355_cmvn_apply", "pk_mi355_batch_create", "pk_mi355_batch_destroy",
@@ -131,7 +131,8 @@ EXPORTS = [
     "pk_mi355_online_recognizer_set_endpointing", "pk_mi355_online_recognizer_num_utterances",
     "pk_mi355_online_recognizer_utterance", "pk_mi355_online_recognizer_utterance_hyp",
     "pk_mi355_online_recognizer_utterance_words", "pk_mi355_online_recognizer_utterance_word_segments",
-    "pk_mi355_features_batch_create", "pk_mi355_features_set", "pk_mi355_features_set_device",
+    "pk_mi355_ark_open", "pk_mi355_ark_next", "pk_mi355_ark_key", "pk_mi355_ark_matrix", "pk_mi355_ark_close", "pk_mi355_ark_read_object",
+    "pk_mi355_features_batch_create", "pk_mi355_features_batch_create_stats", "pk_mi355_features_stream_create_stats", "pk_mi355_features_set", "pk_mi355_features_set_device",
     "pk_mi355_features_dim", "pk_mi355_recognizer_process_features",
     "pk_mi355_features_stream_create", "pk_mi355_stream_open_features", "pk_mi355_stream_push_features",
     "pk_mi355_stream_feat_dim", "pk_mi355_stream_slot_kind",
@@ -372,6 +373,21 @@ def lib():
                                                                      C.c_int]
     L.pk_mi355_features_batch_create.restype = C.c_void_p
     L.pk_mi355_features_batch_create.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int64]
+    L.pk_mi355_features_batch_create_stats.restype = C.c_void_p
+    L.pk_mi355_features_batch_create_stats.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_features_stream_create_stats.restype = C.c_void_p
+    L.pk_mi355_features_stream_create_stats.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_am_feat_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_ark_open.restype = C.c_void_p
+    L.pk_mi355_ark_open.argtypes = [C.c_char_p]
+    L.pk_mi355_ark_read_object.restype = C.c_void_p
+    L.pk_mi355_ark_read_object.argtypes = [C.c_char_p]
+    L.pk_mi355_ark_next.argtypes = [C.c_void_p]
+    L.pk_mi355_ark_key.restype = C.c_char_p
+    L.pk_mi355_ark_key.argtypes = [C.c_void_p]
+    L.pk_mi355_ark_matrix.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t)]
+    L.pk_mi355_ark_close.restype = None
+    L.pk_mi355_ark_close.argtypes = [C.c_void_p]
     L.pk_mi355_features_set.argtypes = [C.c_void_p, C.POINTER(pk_matrix_t), C.c_int, C.c_int]
     L.pk_mi355_features_set_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int]
     L.pk_mi355_features_dim.argtypes = [C.c_void_p]
@@ -603,6 +619,10 @@ class AcousticModel:
 
     def num_pdfs(self):
         return lib().pk_mi355_am_num_pdfs(self._h)
+
+    def feat_dim(self):
+        """The per-frame feature dimension; 0 until the model is finalized."""
+        return lib().pk_mi355_am_feat_dim(self._h)
 
     def input_dim(self):
         return lib().pk_mi355_am_input_dim(self._h)
@@ -839,7 +859,8 @@ class BatchScorer:
 
     def set_features(self, feats, kind="normalized"):
         """Features instead of audio: one [T][feat_dim] matrix per utterance.  kind "normalized": ready for the splice
-        (what Decodable takes); "raw": 40-dim log-mel fbank, the sliding-window CMVN is applied first."""
+        (what Decodable takes); "raw": features the sliding-window CMVN is applied to first (40-dim log-mel fbank, or
+        the model's own dimension on a FeatureScorer made with feat_dim + 1 statistics)."""
         arr, keep = _feature_matrices(feats, self.feat_dim())
         _check_code(lib().pk_mi355_features_set(self._h, arr, len(keep), _feature_kind(kind)))
 
@@ -890,7 +911,7 @@ class BatchScorer:
         return out
 
     def fetch_fbank(self, utt):
-        out = np.zeros((self.num_frames(utt), 40), dtype=np.float32)
+        out = np.zeros((self.num_frames(utt), self.feat_dim()), dtype=np.float32)     # (40 wherever there is a front-end)
         _check_code(lib().pk_mi355_batch_fetch_fbank(self._h, utt, _fp(out)))
         return out
 
@@ -915,18 +936,33 @@ class BatchScorer:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KINDS)}
 
 
+def _stats_route(am, global_stats):
+    """(statistics or None, True when they go to the _create_stats entries).  41 entries: the 40-dim entries, with every
+    refusal of theirs; feat_dim + 1: the entries that take the model's own dimension; anything else is refused here."""
+    if global_stats is None:
+        return None, False
+    g = _f32(global_stats)
+    if g.shape == (41,):
+        return g, False
+    dim = lib().pk_mi355_am_feat_dim(am.handle)
+    if dim > 0 and g.shape == (dim + 1,):
+        return g, True
+    raise PkError("global_stats must have 41 entries, or feat_dim + 1 = %d for this model (got %s)"
+                  % (dim + 1, "x".join(str(n) for n in g.shape)))
+
+
 class FeatureScorer(BatchScorer):
     """A BatchScorer without a front-end, fed by set_features / set_features_device: any model (any feature
-    dimension), capacity in frames.  global_stats (41 floats, 40-dim models) enables kind "raw"."""
+    dimension), capacity in frames.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim model)
+    enables kind "raw"."""
 
     def __init__(self, am, max_utts, max_total_frames, global_stats=None):
-        g = None
-        if global_stats is not None:
-            g = _f32(global_stats)
-            if g.shape != (41,):
-                raise PkError("global_stats must have 41 entries")
+        g, own_dim = _stats_route(am, global_stats)
         self._am = am
-        self._h = lib().pk_mi355_features_batch_create(am.handle, None if g is None else _fp(g), int(max_utts), int(max_total_frames))
+        if own_dim:
+            self._h = lib().pk_mi355_features_batch_create_stats(am.handle, _fp(g), g.shape[0], int(max_utts), int(max_total_frames))
+        else:
+            self._h = lib().pk_mi355_features_batch_create(am.handle, None if g is None else _fp(g), int(max_utts), int(max_total_frames))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self._keep = None
@@ -1026,18 +1062,17 @@ class OnlineScorer:
 
 class OnlineFeatureScorer(OnlineScorer):
     """An OnlineScorer without a front-end, fed by open_features / push_features: any model (any feature dimension),
-    capacity in frames pushed between two steps.  global_stats (41 floats, 40-dim models) enables kind "raw".  The
-    audio entries (open, push, push_i16) fail on it."""
+    capacity in frames pushed between two steps.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim
+    model) enables kind "raw".  The audio entries (open, push, push_i16) fail on it."""
 
     def __init__(self, am, max_streams, max_step_frames, global_stats=None):
-        g = None
-        if global_stats is not None:
-            g = _f32(global_stats)
-            if g.shape != (41,):
-                raise PkError("global_stats must have 41 entries")
+        g, own_dim = _stats_route(am, global_stats)
         self._am = am
         self._max_streams = int(max_streams)
-        self._h = lib().pk_mi355_features_stream_create(am.handle, None if g is None else _fp(g), int(max_streams), int(max_step_frames))
+        if own_dim:
+            self._h = lib().pk_mi355_features_stream_create_stats(am.handle, _fp(g), g.shape[0], int(max_streams), int(max_step_frames))
+        else:
+            self._h = lib().pk_mi355_features_stream_create(am.handle, None if g is None else _fp(g), int(max_streams), int(max_step_frames))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
 
@@ -1054,6 +1089,75 @@ def _check_code(rc):
     if rc < 0:
         raise PkCodeError(rc, lib().pk_mi355_last_error().decode() or "pk_mi355 error %d" % rc)
     return rc
+
+
+def _ark_view(handle):
+    m = pk_matrix_t()
+    _check_code(lib().pk_mi355_ark_matrix(handle, C.byref(m)))
+    if m.ncol == 0 or m.nrow == 0:
+        return np.zeros((m.ncol, m.nrow), np.float32)
+    return np.ctypeslib.as_array(m.data, shape=(m.ncol, m.nrow)).copy()
+
+
+class ArkReader:
+    """A Kaldi archive or script file of float matrices (pk_mi355_ark_*): iterable over (key, float32 [T][D]), read entry
+    by entry.  spec: "ark:<path>", "scp:<path>" or a bare path (a ".scp" suffix means a script file)."""
+
+    def __init__(self, spec):
+        self._h = lib().pk_mi355_ark_open(os.fspath(spec).encode())
+        if not self._h:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode(errors="replace"))
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if not self._h:
+            raise StopIteration
+        rc = lib().pk_mi355_ark_next(self._h)
+        if rc < 0:
+            raise PkCodeError(rc, lib().pk_mi355_last_error().decode(errors="replace"))
+        if rc == 0:
+            self.close()
+            raise StopIteration
+        return lib().pk_mi355_ark_key(self._h).decode(errors="surrogateescape"), _ark_view(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pk_mi355_ark_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_kaldi_matrix(rx):
+    """One keyless Kaldi matrix object from "path" or "path:offset" -> float32 [rows][cols]."""
+    h = lib().pk_mi355_ark_read_object(os.fspath(rx).encode())
+    if not h:
+        raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode(errors="replace"))
+    try:
+        return _ark_view(h)
+    finally:
+        lib().pk_mi355_ark_close(h)
+
+
+def kaldi_global_stats(rx):
+    """A global CMVN statistics file (a 2 x (D + 1) matrix: sums and count, then the sums of squares) -> its row 0 as
+    float32 [D + 1], what FeatureScorer / OnlineFeatureScorer take as global_stats."""
+    m = read_kaldi_matrix(rx)
+    if m.shape[0] != 2 or m.shape[1] < 2:
+        raise PkCodeError(-1, "%s holds a %d x %d matrix; global CMVN statistics are 2 x (D + 1)" % (rx, m.shape[0], m.shape[1]))
+    return np.ascontiguousarray(m[0])
 
 
 class Fst:

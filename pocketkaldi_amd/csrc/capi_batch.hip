@@ -307,9 +307,16 @@ int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
 // What both feature entries check before the device is touched (kind, and RAW's needs).
 int CheckFeatureKind(const pk_mi355_batch *b, int kind) {
   if (kind != PK_MI355_FEATS_NORMALIZED && kind != PK_MI355_FEATS_RAW) return Fail(PK_MI355_E_INVALID, "unknown feature kind %d", kind);
-  if (kind == PK_MI355_FEATS_RAW && (!b->have_stats || b->core.am->feat_dim != kNumBins))
-    return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics and a %d-dim model (this batch: %s, %d-dim)", kNumBins,
-                b->have_stats ? "statistics" : "no statistics", b->core.am->feat_dim);
+  // (statistics are only ever held at the model's own dimension: 41 floats through the 40-dim entries, feat_dim + 1
+  // through pk_mi355_features_batch_create_stats)
+  if (kind == PK_MI355_FEATS_RAW && !b->have_stats) {
+    if (b->core.am->feat_dim == kNumBins)
+      return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics and a %d-dim model (this batch: no statistics, %d-dim)", kNumBins,
+                  kNumBins);
+    return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics: this %d-dim batch was made without them "
+                "(pk_mi355_features_batch_create_stats takes the %d of a %d-dim model)", b->core.am->feat_dim, b->core.am->feat_dim + 1,
+                b->core.am->feat_dim);
+  }
   return 0;
 }
 int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts) {
@@ -317,6 +324,13 @@ int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts)
   for (int u = 0; u < num_utts; ++u)
     if (frames[u] < 0) return Fail(PK_MI355_E_INVALID, "utterance %d has a negative frame count (%d)", u, frames[u]);
   return FramesFit(b, frames, num_utts);
+}
+// RAW at a dimension other than 40 is normalised by CmvnChainKernel into the d_feats staging (the one host NORMALIZED
+// features use): made at the first call that needs it.  b->feats is not touched: a caller's NORMALIZED device pointer stays.
+int EnsureFeatsStaging(pk_mi355_batch *b) {
+  if (b->d_feats) return 0;
+  HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * b->core.am->feat_dim));
+  return 0;
 }
 int WaveEntryAllowed(const pk_mi355_batch *b) {
   if (b->features_only) return Fail(PK_MI355_E_STATE, "this batch was made by pk_mi355_features_batch_create: it takes features, not audio");
@@ -352,7 +366,7 @@ namespace pkhost {
 bool BatchScored(const pk_mi355_batch *b) { return b->scored; }
 const pk_mi355_am *BatchModel(const pk_mi355_batch *b) { return b->core.am; }
 
-void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats41, int units, int64_t max_frames,
+void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats, int stats_dim, int units, int64_t max_frames,
                       int64_t max_rows, int64_t chunk_cap, CreateCheck &chk) {
   const int pad = am->left + am->right;
   c->am = am; c->device = am->device; c->max_frames = max_frames;
@@ -365,13 +379,15 @@ void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats4
     if (chk.ok) chk(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
   };
   chk(hipStreamCreate(&c->stream));
-  if (global_stats41) {
-    FrontendTables host;
-    if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+  if (global_stats) {
+    if (stats_dim == kNumBins) {
+      FrontendTables host;
+      if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+      table(&c->d_tables, &host, sizeof(FrontendTables));
+    }
     CmvnTables ctab;
-    BuildCmvnTables(global_stats41[kNumBins], &ctab);
-    table(&c->d_tables, &host, sizeof(FrontendTables));
-    table(&c->d_global, global_stats41, sizeof(float) * (kNumBins + 1));
+    BuildCmvnTables(global_stats[stats_dim], &ctab);
+    table(&c->d_global, global_stats, sizeof(float) * (stats_dim + 1));
     table(&c->d_cmvn_tab, &ctab, sizeof(CmvnTables));
   }
   chk(hipMalloc(&c->d_yt, sizeof(float) * c->ldy * am->feat_dim));
@@ -420,17 +436,18 @@ int64_t PublicChunkCap() {
 
 // Every way to a batch, arguments checked: max_utts utterances and max_frames frames; max_total_samples PCM samples
 // (0: features only); passes of at most chunk_cap frames.  global_stats41 may be null for a features-only batch.
-pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples, int64_t max_frames,
+// global_stats: am->feat_dim sums and the count.
+pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int max_utts, int64_t max_total_samples, int64_t max_frames,
                             int64_t chunk_cap) {
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
   b->max_utts = max_utts; b->max_samples = max_total_samples;
   b->features_only = max_total_samples == 0;
-  b->have_stats = global_stats41 != nullptr;
+  b->have_stats = global_stats != nullptr;
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
-  CreateScorerCore(&c, am, global_stats41, max_utts, max_frames, max_frames, chunk_cap, chk);
+  CreateScorerCore(&c, am, global_stats, am->feat_dim, max_utts, max_frames, max_frames, chunk_cap, chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
   // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
@@ -443,7 +460,10 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats41, int 
   chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
   chk(hipMalloc(&b->d_lay, lay_bytes));
   chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
-  if (b->have_stats) {
+  if (b->have_stats && am->feat_dim != kNumBins) {     // CmvnChainKernel reads an utterance's own rows only: no lead, no slack
+    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
+    b->d_raw = b->d_raw_alloc;
+  } else if (b->have_stats) {
     const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
     chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
     if (chk.ok) chk(hipMemset(b->d_raw_alloc, 0, sizeof(float) * raw_floats));
@@ -503,6 +523,24 @@ pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float 
     return nullptr;
   }
   return CreateBatch(am, global_stats41, max_utts, 0, max_total_frames, PublicChunkCap());
+}
+
+pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_utts,
+                                                       int64_t max_total_frames) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (!global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (stats_len != am->feat_dim + 1) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
+         am->feat_dim + 1);
+    return nullptr;
+  }
+  if (am->feat_dim == kNumBins) return pk_mi355_features_batch_create(am, global_stats, max_utts, max_total_frames);
+  if (max_utts <= 0 || max_total_frames <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
+    return nullptr;
+  }
+  return CreateBatch(am, global_stats, max_utts, 0, max_total_frames, PublicChunkCap());
 }
 
 int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
@@ -638,10 +676,9 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
   if (int rc = UseDevice(b->core.device)) return rc;
   // RAW: where FbankKernel would have written them; NORMALIZED: the staging FeatureLayoutKernel reads
   float *dst = b->d_raw;
-  if (kind == PK_MI355_FEATS_NORMALIZED) {
-    if (!b->d_feats) HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * D));
-    dst = b->d_feats;
-  }
+  if (kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins)
+    if (int rc = EnsureFeatsStaging(b)) return rc;
+  if (kind == PK_MI355_FEATS_NORMALIZED) dst = b->d_feats;
   // The layout first: its upload travels while the host stages the features below (a copy out of pageable memory
   // holds the host until it is done), and the first kernel of the score call is then queued straight behind them.
   if (int rc = SetLayoutFrames(b, frames.data(), nullptr, num_utts)) return rc;
@@ -652,7 +689,7 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
       HIP_TRY(hipMemcpyAsync(dst + row * D, feats[u].data, sizeof(float) * (size_t)frames[u] * D, hipMemcpyHostToDevice, b->core.stream));
     row += frames[u];
   }
-  b->feats = b->d_feats;
+  if (kind == PK_MI355_FEATS_NORMALIZED) b->feats = b->d_feats;
   b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
   return 0;
 }
@@ -663,13 +700,16 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
   if (int rc = CheckFeatureCounts(b, num_frames, num_utts)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   if (kind == PK_MI355_FEATS_RAW) {                     // CMVN reads around every utterance: into d_raw with its lead and slack
+    const int D = b->core.am->feat_dim;                 // (any other dimension than 40: as a host call's rows, fetch_fbank's source)
+    if (D != kNumBins)
+      if (int rc = EnsureFeatsStaging(b)) return rc;
     int64_t total = 0;
     for (int u = 0; u < num_utts; ++u) total += num_frames[u];
     if (total > 0)
-      HIP_TRY(hipMemcpyAsync(b->d_raw, d_feats, sizeof(float) * (size_t)total * kNumBins, hipMemcpyDeviceToDevice, b->core.stream));
+      HIP_TRY(hipMemcpyAsync(b->d_raw, d_feats, sizeof(float) * (size_t)total * D, hipMemcpyDeviceToDevice, b->core.stream));
   }
   if (int rc = SetLayoutFrames(b, num_frames, nullptr, num_utts)) return rc;
-  b->feats = d_feats;                                   // NORMALIZED: read where they lie
+  if (kind == PK_MI355_FEATS_NORMALIZED) b->feats = d_feats;   // read where they lie
   b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
   return 0;
 }
@@ -700,7 +740,10 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);
     if (b->source == pk_mi355_batch::kNormalized)
       LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else
+    else if (D != kNumBins) {                  // raw rows at the model's own dimension: the chain, then the layout of its result
+      LaunchCmvnChain(b->d_raw, lay, b->num_utts, D, c.d_global, c.d_cmvn_tab, b->d_feats, c.stream);
+      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    } else
       LaunchCmvn(b->d_raw, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream);
   }
   // Rows of the layer stack: compact (row out_base[u] + t is frame t of utterance u; the first layer finds its
@@ -853,8 +896,8 @@ int pk_mi355_batch_fetch_fbank(pk_mi355_batch_t *b, int utt, float *out) {
   if (b->source == pk_mi355_batch::kNormalized) return Fail(PK_MI355_E_STATE, "the batch was fed normalised features: there is no fbank");
   const int T = b->h_T[utt];
   if (T == 0) return 0;
-  HIP_TRY(hipMemcpyAsync(out, b->d_raw + b->h_raw_base[utt] * kNumBins, sizeof(float) * (size_t)T * kNumBins,
-                         hipMemcpyDeviceToHost, b->core.stream));
+  const int D = b->core.am->feat_dim;          // (40 whenever there is a front-end)
+  HIP_TRY(hipMemcpyAsync(out, b->d_raw + b->h_raw_base[utt] * D, sizeof(float) * (size_t)T * D, hipMemcpyDeviceToHost, b->core.stream));
   HIP_TRY(hipStreamSynchronize(b->core.stream));
   return 0;
 }

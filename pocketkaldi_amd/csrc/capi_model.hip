@@ -280,6 +280,7 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
 
 int pk_mi355_am_num_pdfs(const pk_mi355_am_t *am) { return am ? am->num_pdfs : 0; }
 int pk_mi355_am_input_dim(const pk_mi355_am_t *am) { return am ? am->input_dim : 0; }
+int pk_mi355_am_feat_dim(const pk_mi355_am_t *am) { return am && am->finalized ? am->feat_dim : 0; }
 int pk_mi355_am_transition_to_pdf(const pk_mi355_am_t *am, int trans_id) {
   if (am->tid2pdf.empty()) return trans_id;
   return am->tid2pdf[trans_id];

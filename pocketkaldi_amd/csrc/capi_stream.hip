@@ -60,10 +60,10 @@ struct pk_mi355_stream {
   int64_t wave_cap = 0;
   // per-slot state in HBM
   float *d_tails = nullptr;           // [slots][2][kTailCap]
-  float *d_sums = nullptr;            // [slots][40]
-  float *d_raw_hist = nullptr;        // [slots][600][40]
-  float *d_hist = nullptr;            // [slots][hist_len][40]
-  float *d_feat_hist = nullptr;       // [slots][2][hist_len][feat_dim]: NORMALIZED slots (made at the first such open)
+  float *d_sums = nullptr;            // [slots][feat_dim] (40 wherever there is a front-end)
+  float *d_raw_hist = nullptr;        // [slots][600][feat_dim]
+  float *d_hist = nullptr;            // [slots][hist_len][40] (StreamCmvnKernel's; not made at another dimension)
+  float *d_feat_hist = nullptr;       // [slots][2][hist_len][feat_dim]: slots laid out by StreamFeatureLayoutKernel (made at the first such open)
   // per-step staging
   float *h_upload = nullptr, *d_upload = nullptr;    // pushed samples, page-locked -> HBM
   float *d_wave = nullptr;            // segments
@@ -104,7 +104,10 @@ void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
   s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
                   sizeof(int32_t) * Shift4Cap(c.max_cols);
   chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
-  if (s->have_stats) {
+  if (s->have_stats && c.am->feat_dim != kNumBins) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
+    chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * c.am->feat_dim));
+    chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * c.am->feat_dim));
+  } else if (s->have_stats) {
     chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
     chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * kNumBins));
     chk(hipMalloc(&s->d_hist, sizeof(float) * max_streams * s->hist_len * kNumBins));
@@ -154,7 +157,7 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
   s->wave_cap = max_step_samples + (int64_t)max_streams * kTailCap;
   const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
   CreateCheck chk{"stream_create"};
-  CreateScorerCore(&c, am, global_stats41, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  CreateScorerCore(&c, am, global_stats41, kNumBins, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
   CreateStepBuffers(s, chk);
   chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
   chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
@@ -162,12 +165,9 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
   return s;
 }
 
-pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames) {
-  if (!ModelAllowed(am)) return nullptr;
-  if (global_stats41 && am->feat_dim != kNumBins) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
-    return nullptr;
-  }
+namespace {
+// global_stats: null, or am->feat_dim sums and the count
+pk_mi355_stream *CreateFeaturesStream(pk_mi355_am_t *am, const float *global_stats, int max_streams, int64_t max_step_frames) {
   if (max_streams <= 0 || max_step_frames <= 0 || max_step_frames > ((int64_t)1 << 30) / am->feat_dim) {
     Fail(PK_MI355_E_INVALID, "bad stream capacity");
     return nullptr;
@@ -175,16 +175,38 @@ pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const floa
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_stream *s = new pk_mi355_stream();
   s->max_streams = max_streams; s->max_step_samples = max_step_frames;
-  s->features_only = true; s->have_stats = global_stats41 != nullptr;
+  s->features_only = true; s->have_stats = global_stats != nullptr;
   s->frame_cost = 1; s->upload_cap = max_step_frames * am->feat_dim;
   s->slots.resize(max_streams);
   s->hist_len = std::max(am->left + am->right, 1);
   // a slot's rows are its new frames and the (at most R) frames held back for look-ahead, padded to four
   CreateCheck chk{"features_stream_create"};
-  CreateScorerCore(&s->core, am, global_stats41, max_streams, max_step_frames, max_step_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  CreateScorerCore(&s->core, am, global_stats, am->feat_dim, max_streams, max_step_frames, max_step_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
   CreateStepBuffers(s, chk);
   if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
   return s;
+}
+}  // namespace
+
+pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames) {
+  if (!ModelAllowed(am)) return nullptr;
+  if (global_stats41 && am->feat_dim != kNumBins) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
+    return nullptr;
+  }
+  return CreateFeaturesStream(am, global_stats41, max_streams, max_step_frames);
+}
+
+pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_streams,
+                                                         int64_t max_step_frames) {
+  if (!ModelAllowed(am)) return nullptr;
+  if (!global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (stats_len != am->feat_dim + 1) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
+         am->feat_dim + 1);
+    return nullptr;
+  }
+  return CreateFeaturesStream(am, global_stats, max_streams, max_step_frames);
 }
 
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s) {
@@ -245,7 +267,7 @@ int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind) {
     return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics the stream object was made without");
   Slot &z = s->slots[slot];
   if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
-  if (kind == PK_MI355_FEATS_NORMALIZED)
+  if (kind == PK_MI355_FEATS_NORMALIZED || s->core.am->feat_dim != kNumBins)   // (RAW at another dimension than 40 is laid out as NORMALIZED is)
     if (int rc = EnsureFeatureHistory(s)) return rc;
   z.state = kOpen;
   z.n = z.a = z.tail_len = 0;
@@ -345,7 +367,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   // NORMALIZED slots (StreamFeatureLayoutKernel) from its back; rows and columns in slot order whichever the type.
   std::vector<int> who, at, flushed;                  // slots taking part, their records; closed slots with nothing left
   int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
-  int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, max_feat_cols = 0;
+  int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, chain_pushed = 0, max_feat_cols = 0;
   const int D = am->feat_dim;
   std::vector<ShiftSpan> spans;                       // (end row, column shift) per slot with rows
   for (int slot = 0; slot < s->max_streams; ++slot) {
@@ -354,7 +376,9 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     const bool closed = z.state == kClosed;
     // a native-rate slot's new samples are the outputs that became final (all of them once it is closed)
     // (a feature slot: no samples, an empty segment; its frames are what was pushed)
-    const bool feats = z.kind >= 0, layout = z.kind == PK_MI355_FEATS_NORMALIZED;
+    // (RAW at a dimension other than 40: StreamCmvnChainKernel normalises the pushed rows where they lie, and the
+    // record then goes with the NORMALIZED ones)
+    const bool feats = z.kind >= 0, layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && D != kNumBins);
     const int new_len = feats    ? 0
                         : !z.tab ? (int)z.pending.size()
                                  : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
@@ -389,7 +413,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     if (!layout) raw += m;
     if (z.tab && new_len) native_total += (int64_t)z.native.size();
     if (!feats) { max_m = std::max(max_m, m); ++n_audio; }
-    if (z.kind == PK_MI355_FEATS_RAW) raw_pushed += m;
+    if (z.kind == PK_MI355_FEATS_RAW) (layout ? chain_pushed : raw_pushed) += m;
     who.push_back(slot);
     at.push_back(rec_at);
   }
@@ -409,7 +433,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     Slot &z = s->slots[r.slot];
     if (z.kind >= 0) {                   // pushed frames, frame-major
       if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * D);
-      if (r.m && z.kind == PK_MI355_FEATS_NORMALIZED) z.hist_par ^= 1;    // the step writes the other history buffer
+      if (r.m && (z.kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins)) z.hist_par ^= 1;    // the step writes the other history buffer
     } else if (z.tab && r.new_len) {
       // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
       const ResampleTable &t = z.tab->host;
@@ -482,6 +506,9 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   if (n_front > 0)
     LaunchStreamCmvn(d_recs, n_front, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
                      c.d_yt, c.ldy, c.stream);
+  if (chain_pushed > 0)                // before the layout: it reads the rows the chain leaves behind
+    LaunchStreamCmvnChain(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist,
+                          c.stream);
   if (n_back > 0)
     LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
                               c.d_yt, c.ldy, c.stream);

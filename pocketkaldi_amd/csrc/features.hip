@@ -1,6 +1,7 @@
 // features.hip -- FeatureLayoutKernel: features the caller already has, frame-major [sum T][D], become the padded
 // feature-major operand Yt[D][ldy] of the spliced first layer, for every utterance of a call in one launch
-// (pk_score.h; the host side is capi_batch.hip).
+// (pk_score.h; the host side is capi_batch.hip).  Further down: CmvnChainKernel, the
+// sliding-window CMVN on raw rows of any feature dimension, which runs in front of it.
 //
 // A pure copy: frame t of utterance u goes to column pad_base[u] + L + t, frame 0 into the L columns in front of it
 // and frame T - 1 into the R columns behind (the clamp of am.cc:73-75 done once at write time, as CmvnKernel does it).
@@ -67,7 +68,79 @@ __global__ __launch_bounds__(kFlThreads) void FeatureLayoutKernel(const uint32_t
   }
 }
 
+// ------------------------------------------------------------------ CMVN at any dimension
+//
+// CmvnChainKernel: raw rows [sum T][D] -> normalised rows [sum T][D], both frame-major; FeatureLayoutKernel then lays the
+// result out.  cmvn.cc is elementwise in the feature index, so this is StreamCmvnKernel's chain (stream.hip) with any
+// number of lanes: one wavefront per (utterance, block of 64 features), lane = feature, serial over t.  Per frame the
+// wave reads and writes ONE contiguous run of up to 64 floats; the frame that leaves the window (t - 600) is read raw
+// from the input, which is why the kernel cannot run in place.  Frames are taken kChainAhead at a time and the loads of
+// the next group are issued before the chain of the current one -- the rows and the two table entries of each of its
+// frames (wave-uniform: scalar loads) -- so the chain waits on its own f64 adds, not on memory.
+// Every address is formed from t clamped into [0, T) and d clamped into [d0, D): a load past the utterance's rows
+// or past feature D - 1 is never issued; a lane past D shadows the block's first feature and stores nothing.
+constexpr int kChainAhead = 8;
+
+__global__ __launch_bounds__(64) void CmvnChainKernel(const float *__restrict__ raw, UttLayout utts, int num_utts, int D,
+                                                      const float *__restrict__ g, const CmvnTables *__restrict__ tab,
+                                                      float *__restrict__ out) {
+  const int d0 = blockIdx.x * 64;
+  const bool live = d0 + (int)threadIdx.x < D;
+  const int d = live ? d0 + threadIdx.x : d0;
+  const float gd = g[d];
+  for (int u = blockIdx.y; u < num_utts; u += gridDim.y) {          // (uniform over the wave)
+    const int T = utts.num_frames[u];
+    if (T <= 0) continue;
+    const float *x = raw + utts.raw_base[u] * D + d;
+    float *y = out + utts.raw_base[u] * D + d;
+    auto row = [&](int t) { return (int64_t)(t < 0 ? 0 : t < T ? t : T - 1) * D; };
+    float cur[kChainAhead], old[kChainAhead], nxt[kChainAhead], nold[kChainAhead];
+    float al[kChainAhead], ns[kChainAhead], nal[kChainAhead], nns[kChainAhead];     // alpha, neg_scale of the group's frames
+#pragma unroll
+    for (int k = 0; k < kChainAhead; ++k) {                         // (T >= 1; no frame has left yet; k < 600)
+      cur[k] = x[row(k)]; old[k] = 0.0f;
+      al[k] = tab->alpha[k]; ns[k] = tab->neg_scale[k];
+    }
+    float s = 0.0f;
+    for (int t0 = 0; t0 < T; t0 += kChainAhead) {
+#pragma unroll
+      for (int k = 0; k < kChainAhead; ++k) {                       // the next group's loads, ahead of this group's chain
+        const int t = t0 + kChainAhead + k;
+        const int tt = t < kCmvnWindow ? t : kCmvnWindow - 1;
+        nxt[k] = x[row(t)];
+        nold[k] = x[row(t - kCmvnWindow)];
+        nal[k] = tab->alpha[tt]; nns[k] = tab->neg_scale[tt];
+      }
+#pragma unroll
+      for (int k = 0; k < kChainAhead; ++k) {
+        const int t = t0 + k;
+        if (t < T) {
+          const float xv = cur[k];
+          double acc = s;                              // cmvn.cc:44-52
+          acc += xv;
+          if (t >= kCmvnWindow) acc += -1.0 * static_cast<double>(old[k]);              // cmvn.cc:58-64
+          s = static_cast<float>(acc);                 // cmvn.cc:66-70
+          float st = s;
+          if (t + 1 < kCmvnWindow) st += al[k] * gd;                                    // cmvn.cc:73-92
+          float v = xv;
+          v += ns[k] * st;                                                              // cmvn.cc:94-101
+          if (live) y[(int64_t)t * D] = v;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kChainAhead; ++k) { cur[k] = nxt[k]; old[k] = nold[k]; al[k] = nal[k]; ns[k] = nns[k]; }
+    }
+  }
+}
+
 }  // namespace
+
+void LaunchCmvnChain(const float *raw, const UttLayout &utts, int num_utts, int dim, const float *d_global, const CmvnTables *d_cmvn_tab,
+                     float *out, hipStream_t stream) {
+  if (num_utts <= 0 || dim <= 0) return;
+  const dim3 grid((dim + 63) / 64, num_utts < 65535 ? num_utts : 65535);
+  hipLaunchKernelGGL(CmvnChainKernel, grid, dim3(64), 0, stream, raw, utts, num_utts, dim, d_global, d_cmvn_tab, out);
+}
 
 void LaunchFeatureLayout(const float *feats, const UttLayout &utts, int num_utts, int max_frames, int dim, int left, int right,
                          float *yt, int64_t ldy, hipStream_t stream) {

@@ -54,6 +54,18 @@ void LaunchStreamFeatureLayout(const StreamRec *recs, int n, int max_cols, const
 void LaunchFeatureLayout(const float *feats, const UttLayout &utts, int num_utts, int max_frames, int dim, int left, int right,
                          float *yt, int64_t ldy, hipStream_t stream);
 
+// launchers, CMVN at any feature dimension: the chain of cmvn.cc:44-101 with lane = feature, one
+// wavefront per (utterance or record, block of 64 features); g: dim sums (the count lives in tab).
+// LaunchCmvnChain (features.hip): raw rows [sum T][dim] -> normalised rows `out` of the same shape (never in place:
+// frame t - 600 is read raw), utterance u's rows from raw_base[u] on; LaunchFeatureLayout then lays `out` out.
+// LaunchStreamCmvnChain (stream.hip): the RAW records among the n given have their m pushed rows, [m][dim] at new_off of
+// the upload staging, normalised in place; sums[slot][dim] and raw_hist[slot][600][dim] carry the slot from step to step.
+// The caller has checked every base and count against the buffers.
+void LaunchCmvnChain(const float *raw, const UttLayout &utts, int num_utts, int dim, const float *d_global, const CmvnTables *d_cmvn_tab,
+                     float *out, hipStream_t stream);
+void LaunchStreamCmvnChain(const StreamRec *recs, int n, int dim, float *upload, const float *g, const CmvnTables *tab, float *sums,
+                           float *raw_hist, hipStream_t stream);
+
 }  // namespace pkmi
 
 namespace pkhost {
@@ -81,10 +93,11 @@ struct CreateCheck {
   void operator()(hipError_t e) { if (e != hipSuccess && ok) { ok = false; Fail(PK_MI355_E_DEVICE, "%s: %s", name, hipGetErrorString(e)); } }
 };
 // On the selected device (am's): `units` utterances or slots of at most max_frames frames and max_rows rows of the
-// layer stack together, passes of at most chunk_cap rows.  Yt has am->feat_dim rows.  global_stats41 may be null (a
-// scorer that is only ever fed normalised features): the front-end tables are then not made.
+// layer stack together, passes of at most chunk_cap rows.  Yt has am->feat_dim rows.  global_stats (stats_dim sums,
+// then the count) may be null (a scorer that is only ever fed normalised features): no table is then made.  The fbank
+// tables are made for stats_dim == 40 only; at any other dimension there is no front-end, only the CMVN tables.
 // On failure (chk.ok false) the caller still calls FreeScorerCore.
-void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats41, int units, int64_t max_frames,
+void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats, int stats_dim, int units, int64_t max_frames,
                       int64_t max_rows, int64_t chunk_cap, CreateCheck &chk);
 void FreeScorerCore(ScorerCore *c);             // (the owner has waited for the stream)
 

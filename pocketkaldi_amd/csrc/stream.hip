@@ -184,6 +184,75 @@ __global__ __launch_bounds__(kSflThreads) void StreamFeatureLayoutKernel(const S
   }
 }
 
+// RAW slots at a feature dimension other than 40: StreamCmvnKernel's chain with any number of
+// lanes.  One wavefront per (record, block of 64 features), lane = feature; records that are not RAW or brought no
+// frames return at once.  The slot's m pushed rows are normalised IN PLACE where they lie in the upload staging
+// ([m][D] at new_off): the raw values the window needs later are kept in the slot's ring raw_hist[slot][600][D], the
+// running sums in sums[slot][D], exactly as StreamCmvnKernel keeps them at 40.  StreamFeatureLayoutKernel then lays the
+// record out as it does a NORMALIZED one.  A lane owns its feature's column of the rows, the ring and the sums, so
+// no two lanes (and no two waves) touch one address.  Frames are taken kSChainAhead at a time, the next group's loads
+// (rows, ring entries, and the two table entries of each frame) issued before the current group's chain and stores: the
+// ring positions and rows of the two groups differ (600 is far more than 2 kSChainAhead).  Addresses are formed from i clamped into [0, m) and d clamped into [d0, D).
+constexpr int kSChainAhead = 8;
+
+__global__ __launch_bounds__(kWave) void StreamCmvnChainKernel(const StreamRec *__restrict__ recs, int D, float *upload,
+                                                               const float *__restrict__ g, const CmvnTables *__restrict__ tab,
+                                                               float *__restrict__ sums, float *raw_hist) {
+  const StreamRec r = recs[blockIdx.x];
+  if (r.kind != PK_MI355_FEATS_RAW || r.m <= 0) return;
+  const int d0 = blockIdx.y * kWave;
+  const bool live = d0 + (int)threadIdx.x < D;
+  const int d = live ? d0 + threadIdx.x : d0;
+  float *x = upload + r.new_off + d;
+  float *rh = raw_hist + (int64_t)r.slot * kCmvnWindow * D + d;
+  const int m = r.m;
+  auto row = [&](int i) { return (int64_t)(i < m ? i : m - 1) * D; };
+  auto ring = [&](int i) { return (int64_t)((r.n_old + (i < m ? i : m - 1)) % kCmvnWindow) * D; };
+  float s = r.n_old > 0 ? sums[(int64_t)r.slot * D + d] : 0.0f;
+  const float gd = g[d];
+  float cur[kSChainAhead], old[kSChainAhead], nxt[kSChainAhead], nold[kSChainAhead];
+  float al[kSChainAhead], ns[kSChainAhead], nal[kSChainAhead], nns[kSChainAhead];   // alpha, neg_scale of the group's frames
+  auto entry = [&](int i) { return r.n_old + i < kCmvnWindow ? r.n_old + i : kCmvnWindow - 1; };
+#pragma unroll
+  for (int k = 0; k < kSChainAhead; ++k) {
+    cur[k] = x[row(k)];
+    old[k] = r.n_old + k >= kCmvnWindow ? rh[ring(k)] : 0.0f;      // (the ring is read only once the window slides)
+    al[k] = tab->alpha[entry(k)]; ns[k] = tab->neg_scale[entry(k)];
+  }
+  for (int i0 = 0; i0 < m; i0 += kSChainAhead) {
+#pragma unroll
+    for (int k = 0; k < kSChainAhead; ++k) {                        // the next group's loads, ahead of this group's chain
+      const int i = i0 + kSChainAhead + k;
+      nxt[k] = x[row(i)];
+      nold[k] = r.n_old + i >= kCmvnWindow ? rh[ring(i)] : 0.0f;
+      nal[k] = tab->alpha[entry(i)]; nns[k] = tab->neg_scale[entry(i)];
+    }
+#pragma unroll
+    for (int k = 0; k < kSChainAhead; ++k) {
+      const int i = i0 + k;
+      if (i < m) {
+        const int t = r.n_old + i;
+        const float xv = cur[k];
+        double acc = s;                                // cmvn.cc:44-52
+        acc += xv;
+        if (t >= kCmvnWindow) acc += -1.0 * static_cast<double>(old[k]);                // cmvn.cc:58-64
+        s = static_cast<float>(acc);                   // cmvn.cc:66-70
+        float st = s;
+        if (t + 1 < kCmvnWindow) st += al[k] * gd;                                      // cmvn.cc:73-92
+        float v = xv;
+        v += ns[k] * st;                                                                // cmvn.cc:94-101
+        if (live) {
+          rh[ring(i)] = xv;
+          x[row(i)] = v;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kSChainAhead; ++k) { cur[k] = nxt[k]; old[k] = nold[k]; al[k] = nal[k]; ns[k] = nns[k]; }
+  }
+  if (live) sums[(int64_t)r.slot * D + d] = s;
+}
+
 }  // namespace
 
 // ================================================================== launchers (pk_score.h)
@@ -204,6 +273,13 @@ void LaunchStreamRawRows(const StreamRec *recs, int n, const float *upload, floa
   if (n <= 0) return;
   hipLaunchKernelGGL(StreamRawRowsKernel, dim3(n), dim3(256), 0, stream, recs, reinterpret_cast<const uint32_t *>(upload),
                      reinterpret_cast<uint32_t *>(rows));
+}
+
+void LaunchStreamCmvnChain(const StreamRec *recs, int n, int dim, float *upload, const float *g, const CmvnTables *tab, float *sums,
+                           float *raw_hist, hipStream_t stream) {
+  if (n <= 0 || dim <= 0) return;
+  hipLaunchKernelGGL(StreamCmvnChainKernel, dim3(n, (dim + kWave - 1) / kWave), dim3(kWave), 0, stream, recs, dim, upload, g, tab, sums,
+                     raw_hist);
 }
 
 void LaunchStreamFeatureLayout(const StreamRec *recs, int n, int max_cols, const float *upload, float *hist, int hist_len, int dim,

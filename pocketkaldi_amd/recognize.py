@@ -3,7 +3,8 @@
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
                                         [--online [--chunk-ms N] [--partials] [--commit]
                                          [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
-    python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz> --features raw|normalized [--ctm] [--reference-softmax]
+    python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...>
+                                        --features raw|normalized [--ctm] [--reference-softmax] [--online ...]
 
 One line per wave, main.cc:28's "%s\\t%s\\t%f\\n": the file, the sentence, the log-likelihood per frame.  An input
 that does not end in .wav is a list of wave files, one per line (main.cc:34-46); its waves are decoded together, as
@@ -17,8 +18,13 @@ the 10 ms frame grid of the converted audio.
 
 --features KIND takes features instead of audio (Recognizer.process_features): a .npy file holds one [T][D] matrix and is
 printed under the file's name, a .npz file holds one utterance per array and each is printed under its array's name, in
-the file's order.  KIND raw: 40-dim log-mel fbank, the CMVN is applied; normalized: ready for the splice.  --ctm works as
-it does for audio.  Not with --online (the online scorer takes audio only).
+the file's order.  A Kaldi archive or script file of matrices (x.ark, x.scp, ark:<path>, scp:<path>; pk.ArkReader) holds
+one utterance per entry, printed under its key; its entries are read and decoded in groups of at most MAX_UTTS utterances
+and MAX_SAMPLES / 160 frames, not all read first.  KIND raw: 40-dim log-mel fbank, the CMVN is applied; normalized: ready
+for the splice.  --ctm works as it does for audio.  With --online every utterance goes through
+OnlineRecognizer.open_features / push_features, max(1, chunk-ms // 10) frames per step, and --partials, --commit,
+--endpoint-silence and --endpoint-rule work as they do for audio, at 10 ms per frame; stdout is what it is without
+--online, and what --online prints for the audio the features came from.
 
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
@@ -46,11 +52,13 @@ RESERVE = 32
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
-    print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz> --features raw|normalized [--ctm] [--reference-softmax]")
+    print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
+          "--features raw|normalized [--ctm] [--reference-softmax] [--online ...]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
     print("    *.npy / *.npz (with --features): decode this feature matrix / every array of the file.")
+    print("    *.ark / *.scp / ark:<path> / scp:<path> (with --features): decode every matrix of this Kaldi archive / script file.")
     return 1
 
 
@@ -74,8 +82,10 @@ def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, part
         rec.destroy()
 
 
-def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, pieces=None):
-    rates = rates or [16000] * len(waves)
+def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, pieces=None, feature_kind=None):
+    """feature_kind ("raw" / "normalized"): `waves` are [T][D] feature matrices, fed max(1, chunk_ms // 10) frames a step
+    through open_features / push_features; a frame is 10 ms."""
+    rates = [100] * len(waves) if feature_kind else rates or [16000] * len(waves)       # (units per second: frames, or samples)
     if reference_softmax:
         rec.am.set_softmax("reference")
     results = [None] * len(waves)
@@ -83,13 +93,13 @@ def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commi
         group = list(range(first, min(first + MAX_UTTS, len(waves))))
         pos, shown = {u: 0 for u in group}, {u: ("", "") if commit else "" for u in group}
         for u in group:
-            rec.open(u - first, rates[u])
+            rec.open_features(u - first, feature_kind) if feature_kind else rec.open(u - first, rates[u])
         live = set(group)
         while live:
             closing = []
             for u in sorted(live):
                 chunk = max(rates[u] * chunk_ms // 1000, 1)
-                rec.push(u - first, waves[u][pos[u]:pos[u] + chunk])
+                (rec.push_features if feature_kind else rec.push)(u - first, waves[u][pos[u]:pos[u] + chunk])
                 pos[u] += chunk
                 if pos[u] >= len(waves[u]):          # the last chunk and the close in the same step
                     rec.close(u - first)
@@ -138,7 +148,7 @@ def main(argv):
     features = None
     if "--features" in argv:
         at = argv.index("--features")
-        if at + 1 >= len(argv) or argv[at + 1] not in pk.FEATURE_KINDS or "--online" in argv:
+        if at + 1 >= len(argv) or argv[at + 1] not in pk.FEATURE_KINDS:
             return usage()
         features = argv[at + 1]
         del argv[at:at + 2]
@@ -164,36 +174,22 @@ def main(argv):
     if ("--partials" in flags or "--commit" in flags) and "--online" not in flags:
         return usage()
     model_file, input_file = args
-    rec, pieces = None, {}
+    if features and not is_feature_input(input_file):
+        return usage()
     try:
         if features:
-            import numpy as np
-            if not input_file.endswith((".npy", ".npz")):
-                return usage()
-            if input_file.endswith(".npy"):
-                files, feats = [input_file], [np.load(input_file, allow_pickle=False)]
-            else:
-                with np.load(input_file, allow_pickle=False) as z:
-                    files, feats = list(z.files), [z[k] for k in z.files]
-            frames = [int(f.shape[0]) if getattr(f, "ndim", 0) == 2 else 1 for f in feats]     # (process_features names a bad shape)
-            rec = pk.Recognizer(model_file, max_utts=min(max(len(feats), 1), MAX_UTTS),
-                                max_total_samples=160 * max(max(frames + [1]), min(sum(frames), MAX_SAMPLES // 160)))
-            if "--reference-softmax" in flags:
-                rec.am.set_softmax("reference")
-            results, names = rec.process_features(feats, features), rec.symbols
-        elif input_file.endswith(".wav"):
+            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint)
+        if input_file.endswith(".wav"):
             files = [input_file]
         else:
             with open(input_file) as f:
                 files = [line.strip() for line in f if line.strip()]
-        waves, rates = [], []
-        for name in [] if features else files:
+        waves, rates, rec, pieces = [], [], None, {}
+        for name in files:
             wave, rate = pk.read_wave(name, channel)
             waves.append(wave)
             rates.append(rate)
-        if features:
-            pass
-        elif "--online" in flags:
+        if "--online" in flags:
             results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
                                               "--partials" in flags, "--commit" in flags, rates, endpoint,
                                               pieces if endpoint else None)
@@ -208,9 +204,17 @@ def main(argv):
     except (pk.PkError, OSError, ValueError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
-    for u, name in enumerate(files if endpoint else []):       # one line per utterance; word times from the wave's start
+    emit(files, results, names, "--ctm" in flags, pieces if endpoint else None)
+    if rec is not None:
+        rec.close()
+    return 0
+
+
+def emit(files, results, names, ctm, pieces=None):
+    """The output lines.  pieces (endpointing): one line per utterance, word times from the wave's start."""
+    for u, name in enumerate(files if pieces is not None else []):
         for p in pieces[u]:
-            if "--ctm" in flags:
+            if ctm:
                 for s in p.result.segments:
                     if s.word != 0:
                         print("%s 1 %.2f %.2f %s" % (name, (p.first_frame + s.start_frame) * FRAME_SHIFT,
@@ -219,15 +223,78 @@ def main(argv):
                 sys.stdout.write("%s[%.2f-%.2f]\t%s\t%f\n" % (name, p.first_frame * FRAME_SHIFT,
                                                                (p.first_frame + p.num_frames) * FRAME_SHIFT, p.result.text,
                                                                p.result.loglikelihood_per_frame))
-    for name, r in zip([] if endpoint else files, results):
-        if "--ctm" in flags:
+    for name, r in zip([] if pieces is not None else files, results):
+        if ctm:
             for s in r.segments:
                 if s.word != 0:
                     print("%s 1 %.2f %.2f %s" % (name, s.start_frame * FRAME_SHIFT, s.num_frames * FRAME_SHIFT, names[s.word]))
         else:
             sys.stdout.write("%s\t%s\t%f\n" % (name, r.text, r.loglikelihood_per_frame))
-    if rec is not None:
-        rec.close()
+
+
+def is_feature_input(name):
+    return name.endswith((".npy", ".npz", ".ark", ".scp")) or name.startswith(("ark:", "scp:", "ark,", "scp,"))
+
+
+def feature_groups(input_file):
+    """The utterances of a feature input as lists of (name, [T][D] matrix): a .npy / .npz file whole; a Kaldi archive or
+    script file entry by entry, in groups of at most MAX_UTTS utterances and MAX_SAMPLES / 160 frames (an entry
+    longer than that alone) -- they are not all read first."""
+    import numpy as np
+    if input_file.endswith(".npy"):
+        yield [(input_file, np.load(input_file, allow_pickle=False))]
+    elif input_file.endswith(".npz"):
+        with np.load(input_file, allow_pickle=False) as z:
+            yield [(k, z[k]) for k in z.files]
+    else:
+        group, frames = [], 0
+        for key, m in pk.ArkReader(input_file):
+            if group and (len(group) == MAX_UTTS or frames + m.shape[0] > MAX_SAMPLES // 160):
+                yield group
+                group, frames = [], 0
+            group.append((key, m))
+            frames += m.shape[0]
+        if group:
+            yield group
+
+
+def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint):
+    """--features: every group of utterances through a Recognizer (process_features) or, with --online, through the
+    slots of an OnlineRecognizer; the object is kept from group to group while the group fits it.  Raises what main
+    reports; -> the exit code."""
+    online = "--online" in flags
+    rec, held = None, (0, 0)                             # the object, and (utterances, frames) it was made for
+    step = max(chunk_ms // 10, 1)                        # frames per push
+    try:
+        for group in feature_groups(input_file):
+            files, feats = [k for k, _ in group], [m for _, m in group]
+            frames = [int(f.shape[0]) if getattr(f, "ndim", 0) == 2 else 1 for f in feats]     # (process_features names a bad shape)
+            need = (min(max(len(feats), 1), MAX_UTTS), max(max(frames + [1]), min(sum(frames), MAX_SAMPLES // 160)))
+            # (an online object's capacity is its streams and the step size: the frames of a group do not count)
+            if rec is None or need[0] > held[0] or (not online and need[1] > held[1]):
+                if rec is not None:
+                    rec.destroy() if online else rec.close()
+                if online:                               # (a pushed frame counts 160 samples against the step capacity)
+                    rec = pk.OnlineRecognizer(model_file, max_streams=need[0], max_step_samples=160 * step * need[0])
+                    if "--commit" in flags:
+                        rec.decoder.set_commit(True)
+                    if endpoint:
+                        rec.set_endpointing(*endpoint)
+                else:
+                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1])
+                    if "--reference-softmax" in flags:
+                        rec.am.set_softmax("reference")
+                held = need
+            pieces = {} if endpoint else None
+            if online:
+                results, names = stream_waves(rec, files, feats, chunk_ms, "--reference-softmax" in flags, "--partials" in flags,
+                                              "--commit" in flags, None, pieces, feature_kind=kind)
+            else:
+                results, names = rec.process_features(feats, kind), rec.symbols
+            emit(files, results, names, "--ctm" in flags, pieces)
+    finally:
+        if rec is not None:
+            rec.destroy() if online else rec.close()
     return 0
 
 

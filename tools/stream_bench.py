@@ -37,6 +37,10 @@ the frames of one chunk per step (10 frames for 100 ms) into a features-only sco
 statistics for raw).  The features are the batch scorer's on the same waves -- its fbank for raw, its CMVN'd features for
 normalized -- so the check against BatchScorer stays bit for bit.  profiles/stream_features_bench.json holds the audio
 leg and both feature legs of one session.
+
+--feat-dim D (with --features) replaces the waves by synthetic [T][D] features and model S by the tiny model at that
+dimension: raw features then take StreamCmvnChainKernel in front of the layout launch, and the
+normalized leg of the same dimension is the step without it.  profiles/cmvn_any_bench.json holds both legs at D = 80.
 """
 import argparse
 import json
@@ -65,7 +69,12 @@ def main():
     ap.add_argument("--endpoint", action="store_true")
     ap.add_argument("--trace-capacity", type=int, default=0)
     ap.add_argument("--features", choices=["normalized", "raw"], default=None)
+    ap.add_argument("--feat-dim", type=int, default=40,
+                    help="with --features: synthetic features of this dimension (5 N(0, 1) + 3; raw: statistics of count 2500, "
+                         "StreamCmvnChainKernel's path, DESIGN.md section 15) through a small model; checked against FeatureScorer")
     a = ap.parse_args()
+    if a.feat_dim != 40 and (a.features is None or a.decode or a.commit or a.endpoint):
+        ap.error("--feat-dim takes --features and no decoder")
     a.decode = a.decode or a.commit or a.endpoint
 
     pk.set_device(0)
@@ -76,7 +85,20 @@ def main():
     chunk = int(round(a.chunk_ms * synth.SAMPLE_RATE / 1000.0))
     nsteps = (len(waves[0]) + chunk - 1) // chunk
     feats = None
-    if a.features:
+    model_name = "S (440 -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax"
+    if a.feat_dim != 40:
+        D = a.feat_dim
+        layers, prior, L, R = synth.model("tiny", feat_dim=D)
+        am = pk.AcousticModel(layers, prior, L, R)
+        model_name = "tiny at feat_dim %d (L = R = 5), f32, stable softmax" % D
+        g = np.concatenate([np.full(D, 3.0 * 2500.0), [2500.0]]).astype(np.float32)
+        T = pk.num_frames(len(waves[0]))
+        base = [(5.0 * np.random.default_rng(u).standard_normal((T, D)) + 3.0).astype(np.float32) for u in range(4)]
+        feats = [base[u % 4] for u in range(a.streams)]
+        chunk = int(round(a.chunk_ms / 10.0))                  # frames per step
+        nsteps = (T + chunk - 1) // chunk
+        sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None)
+    elif a.features:
         bs = pk.BatchScorer(am, g, a.streams, sum(len(w) for w in waves))
         bs.set_waves(waves)
         bs.score(0.1)
@@ -154,14 +176,18 @@ def main():
     run(False, min(nsteps, 100))             # warm-up: a pass of at most 100 steps
     walls, frames, rows0 = run(True)
     walls_ms = np.array(walls) * 1e3
-    bs = pk.BatchScorer(am, g, 1, len(waves[0]))
-    bs.set_waves(waves[:1])
+    if a.feat_dim != 40:
+        bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g)
+        bs.set_features(feats[:1], a.features)
+    else:
+        bs = pk.BatchScorer(am, g, 1, len(waves[0]))
+        bs.set_waves(waves[:1])
     bs.score(0.1)
     ok = np.concatenate(rows0).tobytes() == bs.fetch(0).log_prob().tobytes()
     rec = {
         "streams": a.streams, "seconds": a.seconds, "chunk_ms": a.chunk_ms, "steps": len(walls),
         "input": "features, %s, %d frames a push" % (a.features, chunk) if feats else "audio",
-        "model": "S (440 -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax",
+        "model": model_name,
         "device": torch.cuda.get_device_name(0),
         "step_ms": {"median": float(np.median(walls_ms)), "p90": float(np.percentile(walls_ms, 90)),
                     "max": float(walls_ms.max())},
