@@ -361,6 +361,64 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
                                        int num_utts, int kind);
 int pk_mi355_features_dim(const pk_mi355_batch_t *b);
 
+/* ---- The front-end at a specification: log-mel fbank with any number of bins over any band,
+ * and MFCC on top of it, on the GPU, for models whose features are not the reference's 40-bin fbank.              */
+#define PK_MI355_FRONTEND_FBANK 0
+#define PK_MI355_FRONTEND_MFCC  1
+#define PK_MI355_WINDOW_HAMMING 0   /* the reference's (fbank.cc:249-256) */
+#define PK_MI355_WINDOW_POVEY   1   /* Kaldi's default: pow(0.5 - 0.5 cos(a i), 0.85) */
+typedef struct pk_mi355_frontend_spec {
+  int32_t kind;            /* PK_MI355_FRONTEND_FBANK 0, PK_MI355_FRONTEND_MFCC 1 */
+  int32_t num_mel_bins;    /* 3 .. 128 */
+  int32_t num_ceps;        /* MFCC: 1 .. num_mel_bins;  FBANK: must be 0 */
+  int32_t window;          /* PK_MI355_WINDOW_HAMMING 0 (the reference's), PK_MI355_WINDOW_POVEY 1 (Kaldi's default) */
+  float   low_freq;        /* Hz, >= 0 */
+  float   high_freq;       /* Hz; <= 0: that much below 8000 (Kaldi's convention) */
+  float   cepstral_lifter; /* MFCC: >= 0, 0 = none (Kaldi: 22);  FBANK: ignored */
+} pk_mi355_frontend_spec_t;
+/* The output dimension is num_mel_bins (fbank) or num_ceps (MFCC).  Everything else is the reference's and fixed:
+ * 16 kHz, 400-sample frames every 160 samples (pk_mi355_num_frames), DC removal, pre-emphasis 0.97 in double, the
+ * 512-point split-radix FFT, power spectrum, floor FLT_EPSILON, logf; no dither, energy, deltas or VTLN.
+ *
+ * The rule.  Up to the power spectrum P[0..256]: the arithmetic of pk_mi355_fbank_compute bit for bit, with the spec's
+ * window (both formed in double and rounded to float once; Povey's cosine is the double cosine of the reference's
+ * float angle step times i).  Mel triangles: fbank.cc:103-163 in the reference's float expressions with num_mel_bins
+ * bins between low_freq and the resolved high_freq; a bin needs at least one tap (Kaldi's condition).  Mel energy of
+ * bin b: e = +0.0f; for j ascending: e += w[j] * P[off + j] -- a rounded product, a rounded add, no fma -- then
+ * max(e, FLT_EPSILON) and logf.  No spectrum value outside a bin's own taps influences it.  MFCC: c[k] = +0.0f; for b
+ * ascending: c[k] += dct[k][b] * logmel[b], the same roundings; then c[k] *= lifter[k].  dct[0][b] = sqrt(1 / B),
+ * dct[k][b] = sqrt(2 / B) cos(pi / B (b + 0.5) k), lifter[k] = 1 + 0.5 Q sin(pi k / Q) (Q = 0: 1), formed in double
+ * and rounded to float once: Kaldi's definitions.  Kaldi leaves the order of the dot to BLAS, so agreement with Kaldi
+ * is within rounding, not bitwise.
+ *
+ * Refused with PK_MI355_E_INVALID and a text that names the field, before any device call: an unknown kind or window;
+ * num_mel_bins outside 3 .. 128; num_ceps outside 1 .. num_mel_bins (MFCC) or nonzero (fbank); a negative or
+ * non-finite low_freq, a non-finite high_freq, a negative or non-finite cepstral_lifter; a resolved high_freq above
+ * 8000 or not above low_freq; a triangle without a tap (the text names the bin).
+ *
+ * Host only, no device: the check, the dimension (negative code on failure), the reference's configuration, and the
+ * tables -- window[400], mel_off[B] (first FFT bin), mel_len[B], mel_weights (the bins' taps back to back, sum of
+ * mel_len <= 512 floats), dct[num_ceps][B] and lifter[num_ceps] (MFCC only; untouched for fbank); any pointer may be
+ * NULL.                                                                                                             */
+int pk_mi355_frontend_check(const pk_mi355_frontend_spec_t *spec);
+int pk_mi355_frontend_dim(const pk_mi355_frontend_spec_t *spec);
+int pk_mi355_frontend_default(pk_mi355_frontend_spec_t *spec);
+int pk_mi355_frontend_tables(const pk_mi355_frontend_spec_t *spec, float *window, int32_t *mel_off, int32_t *mel_len,
+                             float *mel_weights, float *dct, float *lifter);
+/* One wave (host, 16 kHz, unscaled sample values) -> out {ncol = T, nrow = dim} host, as pk_mi355_fbank_compute.   */
+int pk_mi355_frontend_compute(const pk_mi355_frontend_spec_t *spec, const pk_vector_t *wave, pk_matrix_t *out);
+/* A batch scorer with this front-end: pk_mi355_batch_create for a model of pk_mi355_frontend_dim(spec) features.
+ * global_stats: dim sums, then the frame count.  PK_MI355_E_INVALID, naming both numbers: a spec dimension that is not
+ * pk_mi355_am_feat_dim(am), a stats_len that is not that + 1; F16X3 / F16 need a dimension that is a multiple of 8.
+ * Every set_waves* entry (pk_mi355_resample_set_waves too; capacity counts 16 kHz samples) and everything behind
+ * them works as on pk_mi355_batch_create's object, with the isolation contract above: score runs FbankAnyKernel in the
+ * PK_MI355_K_FBANK slot -- always, at the default spec too -- and then the CMVN of the dimension; fetch_fbank returns
+ * the front-end's rows [T][dim].  pk_mi355_features_set* work on it, and a later set_waves* switches back.  (Named
+ * with the front-end's entries, as the feature entries are: pk_mi355_batch_create with another front-end.)         */
+pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec,
+                                                 const float *global_stats, int stats_len, int max_utts,
+                                                 int64_t max_total_samples);
+
 /* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
  * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
  * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is

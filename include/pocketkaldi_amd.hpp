@@ -422,6 +422,80 @@ class OnlineScorer {
   Status status_;
 };
 
+// A front-end specification (pk_mi355_frontend_spec_t): log-mel fbank with any number of bins
+// over any band, or MFCC on top of it.  The defaults are the reference's front-end; Kaldi's usual MFCC is
+// FrontendSpec::Mfcc(23, 13).  Nothing is checked here: the library refuses a bad spec wherever one is used.
+struct FrontendSpec : pk_mi355_frontend_spec_t {
+  FrontendSpec() { pk_mi355_frontend_default(this); }
+  static FrontendSpec Fbank(int num_mel_bins, int window = PK_MI355_WINDOW_POVEY, float low_freq = 20.0f, float high_freq = 0.0f) {
+    FrontendSpec s;
+    s.num_mel_bins = num_mel_bins; s.window = window; s.low_freq = low_freq; s.high_freq = high_freq;
+    return s;
+  }
+  static FrontendSpec Mfcc(int num_mel_bins, int num_ceps, int window = PK_MI355_WINDOW_POVEY, float low_freq = 20.0f,
+                           float high_freq = 0.0f, float cepstral_lifter = 22.0f) {
+    FrontendSpec s = Fbank(num_mel_bins, window, low_freq, high_freq);
+    s.kind = PK_MI355_FRONTEND_MFCC; s.num_ceps = num_ceps; s.cepstral_lifter = cepstral_lifter;
+    return s;
+  }
+  Status Check() const { return Status::FromLast(pk_mi355_frontend_check(this)); }
+  int dim() const { return pk_mi355_frontend_dim(this); }      // negative: the spec is refused
+};
+
+// Fbank at a spec: wave (16 kHz sample values) -> features {nrow = spec.dim(), ncol = T}, resized like Fbank::Compute's.
+class Frontend {
+ public:
+  explicit Frontend(const FrontendSpec &spec) : spec_(spec) {}
+  void Compute(const pk_vector_t *wave, pk_matrix_t *features) {
+    status_ = Status::FromLast(pk_mi355_frontend_compute(&spec_, wave, features));
+  }
+  const FrontendSpec &spec() const { return spec_; }
+  const Status &last_status() const { return status_; }
+
+ private:
+  FrontendSpec spec_;
+  Status status_;
+};
+
+// The batched, device-resident scorer (pk_mi355_batch_*): PCM of many utterances -> log-likelihood rows.
+class BatchScorer {
+ public:
+  // the reference's front-end: a 40-dim model and its 41 statistics
+  BatchScorer(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples)
+      : b_(pk_mi355_batch_create(am, global_stats41, max_utts, max_total_samples)) {
+    if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // a front-end at a spec of the model's feature dimension (pk_mi355_frontend_batch_create): stats_len = that + 1
+  BatchScorer(pk_mi355_am_t *am, const FrontendSpec &spec, const float *global_stats, int stats_len, int max_utts,
+              int64_t max_total_samples)
+      : b_(pk_mi355_frontend_batch_create(am, &spec, global_stats, stats_len, max_utts, max_total_samples)) {
+    if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  ~BatchScorer() { pk_mi355_batch_destroy(b_); }
+  BatchScorer(const BatchScorer &) = delete;
+  BatchScorer &operator=(const BatchScorer &) = delete;
+
+  Status SetWaves(const pk_vector_t *waves, int num_utts) { return Status::FromLast(pk_mi355_batch_set_waves(b_, waves, num_utts)); }
+  // utterance u sampled at rates[u] Hz, converted on the GPU on the way in
+  Status SetWaves(const pk_vector_t *waves, const int *rates, int num_utts) {
+    return Status::FromLast(pk_mi355_resample_set_waves(b_, waves, rates, num_utts));
+  }
+  Status Score(float prob_scale) { return Status::FromLast(pk_mi355_batch_score(b_, prob_scale, 1)); }
+  int NumFrames(int utt) const { return pk_mi355_batch_num_frames(b_, utt); }
+  int FeatDim() const { return pk_mi355_features_dim(b_); }
+  // utterance utt's rows as a host decodable ({ncol = T, nrow = num_pdfs}; release with pk_decodable_destroy)
+  Status Fetch(int utt, pk_decodable_t *out) { return Status::FromLast(pk_mi355_batch_fetch(b_, utt, out)); }
+  // the front-end's rows, [T][FeatDim()] floats
+  Status FetchFeatures(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_fbank(b_, utt, out)); }
+
+  const Status &last_status() const { return status_; }
+  pk_mi355_batch_t *handle() const { return b_; }
+
+ private:
+  pk_mi355_batch_t *b_;
+  Status status_;
+};
+
 // Kaldi archives and script files of float matrices (pk_mi355_ark_*), entry by entry:
 //   ArkReader r("scp:feats.scp");  while (r.Next()) use(r.Key(), r.Matrix());  if (!r.last_status().ok()) ...
 class ArkReader {

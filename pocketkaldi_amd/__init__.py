@@ -77,6 +77,11 @@ class pk_mi355_endpoint_t(C.Structure):          # a slot's endpoint record (inc
 _lib = None
 
 # every symbol include/pk_mi355.h declares (tests check the library exports all of them)
+class pk_mi355_frontend_spec_t(C.Structure):     # a front-end specification (include/pk_mi355.h)
+    _fields_ = [("kind", C.c_int32), ("num_mel_bins", C.c_int32), ("num_ceps", C.c_int32), ("window", C.c_int32),
+                ("low_freq", C.c_float), ("high_freq", C.c_float), ("cepstral_lifter", C.c_float)]
+
+
 EXPORTS = [
     "pk_mi355_last_error", "pk_mi355_set_device", "pk_decodable_init", "pk_decodable_destroy",
     "pk_decodable_loglikelihood", "pk_decodable_islastframe", "pk_mi355_am_create",
@@ -137,6 +142,8 @@ EXPORTS = [
     "pk_mi355_features_stream_create", "pk_mi355_stream_open_features", "pk_mi355_stream_push_features",
     "pk_mi355_stream_feat_dim", "pk_mi355_stream_slot_kind",
     "pk_mi355_online_recognizer_open_features", "pk_mi355_online_recognizer_push_features",
+    "pk_mi355_frontend_check", "pk_mi355_frontend_dim", "pk_mi355_frontend_default", "pk_mi355_frontend_tables",
+    "pk_mi355_frontend_compute", "pk_mi355_frontend_batch_create",
 ]
 
 
@@ -400,6 +407,14 @@ def lib():
     L.pk_mi355_stream_slot_kind.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_online_recognizer_open_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pk_mi355_online_recognizer_push_features.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int]
+    specp = C.POINTER(pk_mi355_frontend_spec_t)
+    L.pk_mi355_frontend_check.argtypes = [specp]
+    L.pk_mi355_frontend_dim.argtypes = [specp]
+    L.pk_mi355_frontend_default.argtypes = [specp]
+    L.pk_mi355_frontend_tables.argtypes = [specp, f32p, i32p, i32p, f32p, f32p, f32p]
+    L.pk_mi355_frontend_compute.argtypes = [specp, C.POINTER(pk_vector_t), C.POINTER(pk_matrix_t)]
+    L.pk_mi355_frontend_batch_create.restype = C.c_void_p
+    L.pk_mi355_frontend_batch_create.argtypes = [C.c_void_p, specp, f32p, C.c_int, C.c_int, C.c_int64]
     _lib = L
     return L
 
@@ -527,6 +542,83 @@ class Fbank:
         v = pk_vector_t(wave.shape[0], _fp(wave))
         m = pk_matrix_t(0, 0, None)
         _check(lib().pk_mi355_fbank_compute(C.byref(v), C.byref(m)))
+        return _take_matrix(m)
+
+
+FRONTEND_KINDS = {"fbank": 0, "mfcc": 1}             # PK_MI355_FRONTEND_*
+FRONTEND_WINDOWS = {"hamming": 0, "povey": 1}        # PK_MI355_WINDOW_*
+
+
+class FrontendSpec:
+    """A front-end specification (pk_mi355_frontend_spec_t): log-mel fbank with num_mel_bins bins between low_freq and
+    high_freq (<= 0: that much below 8000 Hz), or MFCC -- its first num_ceps cepstra, liftered (0: not) -- on top of it.
+    The defaults are the reference's front-end.  kind and window also take the header's integers; nothing is checked
+    here: the library refuses a bad spec (PkCodeError, the field named) wherever one is used."""
+
+    def __init__(self, kind="fbank", num_mel_bins=40, num_ceps=None, window="hamming", low_freq=20.0, high_freq=0.0,
+                 cepstral_lifter=22.0):
+        self.kind = FRONTEND_KINDS.get(kind, kind)
+        self.window = FRONTEND_WINDOWS.get(window, window)
+        self.num_mel_bins, self.low_freq, self.high_freq = num_mel_bins, low_freq, high_freq
+        self.num_ceps = num_ceps if num_ceps is not None else (13 if self.kind == 1 else 0)
+        self.cepstral_lifter = cepstral_lifter
+
+    def struct(self):
+        try:
+            return pk_mi355_frontend_spec_t(int(self.kind), int(self.num_mel_bins), int(self.num_ceps), int(self.window),
+                                            float(self.low_freq), float(self.high_freq), float(self.cepstral_lifter))
+        except (TypeError, ValueError) as e:
+            raise PkCodeError(-1, "front-end spec: %s" % e)
+
+    def check(self):
+        _check_code(lib().pk_mi355_frontend_check(C.byref(self.struct())))
+
+    @property
+    def dim(self):
+        """num_mel_bins for fbank, num_ceps for MFCC."""
+        return _check_code(lib().pk_mi355_frontend_dim(C.byref(self.struct())))
+
+    def __repr__(self):
+        return "FrontendSpec(kind=%r, num_mel_bins=%r, num_ceps=%r, window=%r, low_freq=%r, high_freq=%r, cepstral_lifter=%r)" % (
+            self.kind, self.num_mel_bins, self.num_ceps, self.window, self.low_freq, self.high_freq, self.cepstral_lifter)
+
+
+def frontend_default():
+    """The reference's configuration (pk_mi355_frontend_default)."""
+    st = pk_mi355_frontend_spec_t()
+    _check_code(lib().pk_mi355_frontend_default(C.byref(st)))
+    return FrontendSpec(st.kind, st.num_mel_bins, st.num_ceps, st.window, st.low_freq, st.high_freq, st.cepstral_lifter)
+
+
+FrontendTables = collections.namedtuple("FrontendTables", "window mel_off mel_len mel_weights dct lifter")
+
+
+def frontend_tables(spec):
+    """The tables of a spec (pk_mi355_frontend_tables; host only): window[400], mel_off[B], mel_len[B], mel_weights (a list
+    of B arrays: bin b's taps, for FFT bins mel_off[b] ...), dct[num_ceps][B] and lifter[num_ceps] (MFCC; fbank: empty)."""
+    st = spec.struct()
+    _check_code(lib().pk_mi355_frontend_check(C.byref(st)))
+    B, K = st.num_mel_bins, st.num_ceps
+    i32p = C.POINTER(C.c_int32)
+    window, off, length = np.zeros(400, np.float32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    packed, dct, lifter = np.zeros(512, np.float32), np.zeros((K, B), np.float32), np.zeros(K, np.float32)
+    _check_code(lib().pk_mi355_frontend_tables(C.byref(st), _fp(window), off.ctypes.data_as(i32p), length.ctypes.data_as(i32p), _fp(packed),
+                                               _fp(dct) if K else None, _fp(lifter) if K else None))
+    base = np.concatenate([[0], np.cumsum(length)])
+    return FrontendTables(window, off, length, [packed[base[b]:base[b + 1]].copy() for b in range(B)], dct, lifter)
+
+
+class Frontend:
+    """The front-end at a spec for one wave: compute(wave) -> [T][spec.dim] (pk_mi355_frontend_compute)."""
+
+    def __init__(self, spec):
+        self.spec = spec
+
+    def compute(self, wave):
+        wave = _f32(wave).ravel()
+        v = pk_vector_t(wave.shape[0], _fp(wave) if wave.size else None)
+        m = pk_matrix_t(0, 0, None)
+        _check_code(lib().pk_mi355_frontend_compute(C.byref(self.spec.struct()), C.byref(v), C.byref(m)))
         return _take_matrix(m)
 
 
@@ -802,15 +894,23 @@ class Decodable:
 class BatchScorer:
     """Many utterances in flight: PCM -> fbank -> CMVN -> nnet -> log-likelihoods, all in HBM."""
 
-    def __init__(self, am, global_stats, max_utts, max_total_samples):
+    def __init__(self, am, global_stats, max_utts, max_total_samples, frontend=None):
+        """frontend: a FrontendSpec of the model's feature dimension (pk_mi355_frontend_batch_create; global_stats: that
+        many sums, then the count).  Without it: the reference's 40-bin front-end and 41 statistics."""
         g = _f32(global_stats)
+        self._am = am
+        self._keep = None
+        if frontend is not None:
+            self._h = lib().pk_mi355_frontend_batch_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
+                                                           int(max_utts), int(max_total_samples))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
         if g.shape != (41,):
             raise PkError("global_stats must have 41 entries")
-        self._am = am
         self._h = lib().pk_mi355_batch_create(am.handle, _fp(g), int(max_utts), int(max_total_samples))
         if not self._h:
             raise PkError(lib().pk_mi355_last_error().decode())
-        self._keep = None
 
     def close(self):
         if getattr(self, "_h", None):

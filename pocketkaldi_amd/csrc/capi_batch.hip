@@ -9,6 +9,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "pk_frontend.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -154,6 +155,8 @@ struct pk_mi355_batch {
   Source source = kNone;
   bool features_only = false;       // made by pk_mi355_features_batch_create: no PCM capacity, the wave entries are refused
   bool have_stats = false;          // the CMVN tables and d_raw exist (always, for a wave batch)
+  // made by pk_mi355_frontend_batch_create: the spec's tables; score then runs FbankAnyKernel instead of FbankKernel
+  FrontendAnyTables *d_any = nullptr;
   float *d_feats = nullptr;         // owned [max_frames][feat_dim] staging of set_features(NORMALIZED), made on first use
   const float *feats = nullptr;     // normalised features, frame-major (d_feats or the caller's device pointer)
   // pk_mi355_resample_set_waves: the utterances that are not at 16 kHz wait here at their own rate, page-locked and
@@ -437,8 +440,9 @@ int64_t PublicChunkCap() {
 // Every way to a batch, arguments checked: max_utts utterances and max_frames frames; max_total_samples PCM samples
 // (0: features only); passes of at most chunk_cap frames.  global_stats41 may be null for a features-only batch.
 // global_stats: am->feat_dim sums and the count.
+// any: the tables of a front-end spec of am->feat_dim features (pk_mi355_frontend_batch_create), or null.
 pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int max_utts, int64_t max_total_samples, int64_t max_frames,
-                            int64_t chunk_cap) {
+                            int64_t chunk_cap, const FrontendAnyTables *any = nullptr) {
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
@@ -468,6 +472,18 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int ma
     chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
     if (chk.ok) chk(hipMemset(b->d_raw_alloc, 0, sizeof(float) * raw_floats));
     if (chk.ok) b->d_raw = b->d_raw_alloc + kCmvnRawLead;
+  }
+  if (any) {
+    if (!c.d_tables && chk.ok) {                     // (the scorer core makes FbankKernel's tables for 40-dim statistics only)
+      FrontendTables host;
+      if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+      chk(hipMalloc(&c.d_tables, sizeof(FrontendTables)));
+      if (chk.ok) chk(hipMemcpy(c.d_tables, &host, sizeof(FrontendTables), hipMemcpyHostToDevice));
+    }
+    chk(hipMalloc(&b->d_any, sizeof(FrontendAnyTables)));
+    if (chk.ok) chk(hipMemcpy(b->d_any, any, sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
+    if (am->feat_dim != kNumBins)                    // CmvnChainKernel's output, which FeatureLayoutKernel reads
+      chk(hipMalloc(&b->d_feats, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
   }
   if (IsF16(am->precision)) chk(hipMalloc(&b->d_y2, sizeof(_Float16) * 2 * c.ldy * am->feat_dim));
   if (const char *e = getenv("PK_MI355_LANES")) b->lanes = atoi(e) >= 2 ? 2 : 1;
@@ -543,6 +559,29 @@ pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const 
   return CreateBatch(am, global_stats, max_utts, 0, max_total_frames, PublicChunkCap());
 }
 
+pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
+                                                 int stats_len, int max_utts, int64_t max_total_samples) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (!spec || !global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  std::vector<FrontendAnyTables> any(1);
+  if (BuildFrontendAnyTables(spec, any.data())) return nullptr;      // (names the field)
+  if (any[0].dim != am->feat_dim) {
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model expects %d", any[0].dim, am->feat_dim);
+    return nullptr;
+  }
+  if (stats_len != am->feat_dim + 1) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
+         am->feat_dim + 1);
+    return nullptr;
+  }
+  if (max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
+    return nullptr;
+  }
+  return CreateBatch(am, global_stats, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts, PublicChunkCap(), any.data());
+}
+
 int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
 
 void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
@@ -553,7 +592,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   FreeExec(&b->exec2);
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched, b->ev_layout}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
-  hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats);
+  hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats); hipFree(b->d_any);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
   hipFree(b->d_native);
@@ -734,7 +773,8 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   const int D = am->feat_dim;
   if (b->source == pk_mi355_batch::kWaves) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
-    LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_raw, c.stream);
+    if (b->d_any) LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, D, b->d_raw, c.stream);
+    else LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_raw, c.stream);
   }
   {                                            // raw rows (fbank's, or the caller's) or normalised features -> Yt
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);

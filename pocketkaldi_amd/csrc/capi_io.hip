@@ -4,6 +4,7 @@
 
 #include <vector>
 
+#include "pk_frontend.h"
 #include "pk_host.h"
 
 using namespace pkmi;
@@ -138,6 +139,51 @@ int pk_mi355_fbank_compute(const pk_vector_t *wave, pk_matrix_t *out) {
   }
   if (e != hipSuccess) ret = Fail(PK_MI355_E_DEVICE, "fbank_compute: %s", hipGetErrorString(e));
   hipFree(d_tab); hipFree(d_wave); hipFree(d_raw); hipFree(d_i64); hipFree(d_T);
+  return ret;
+}
+
+int pk_mi355_frontend_compute(const pk_mi355_frontend_spec_t *spec, const pk_vector_t *wave, pk_matrix_t *out) {
+  if (!spec || !wave || !out) return Fail(PK_MI355_E_INVALID, "null argument");
+  std::vector<FrontendAnyTables> any(1);
+  if (int rc = BuildFrontendAnyTables(spec, any.data())) return rc;      // before any device call
+  int rc = UseDevice(CurrentDevice());
+  if (rc) return rc;
+  const int T = pk_mi355_num_frames(wave->dim), D = any[0].dim;
+  if (T == 0) return ResizeHostMatrix(out, 0, 0);
+  if ((rc = ResizeHostMatrix(out, D, T))) return rc;
+  FrontendTables host;
+  if (BuildFrontendTables(&host)) return Fail(PK_MI355_E_INVALID, "front-end table construction failed");
+  FrontendTables *d_tab = nullptr;
+  FrontendAnyTables *d_any = nullptr;
+  float *d_wave = nullptr, *d_raw = nullptr;
+  int64_t *d_i64 = nullptr;
+  int32_t *d_T = nullptr;
+  int64_t zeros[2] = {0, 0};
+  int32_t hT = T;
+  int ret = 0;
+  hipError_t e = hipSuccess;
+  auto step = [&](hipError_t x) { if (e == hipSuccess) e = x; };
+  step(hipMalloc(&d_tab, sizeof(FrontendTables)));
+  step(hipMalloc(&d_any, sizeof(FrontendAnyTables)));
+  step(hipMalloc(&d_wave, sizeof(float) * wave->dim));
+  step(hipMalloc(&d_raw, sizeof(float) * (size_t)T * D));
+  step(hipMalloc(&d_i64, sizeof(int64_t) * 2));
+  step(hipMalloc(&d_T, sizeof(int32_t)));
+  if (e == hipSuccess) {
+    step(hipMemcpy(d_tab, &host, sizeof(FrontendTables), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_any, any.data(), sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_wave, wave->data, sizeof(float) * wave->dim, hipMemcpyHostToDevice));
+    step(hipMemcpy(d_i64, zeros, sizeof(zeros), hipMemcpyHostToDevice));
+    step(hipMemcpy(d_T, &hT, sizeof(hT), hipMemcpyHostToDevice));
+  }
+  if (e == hipSuccess) {
+    UttLayout lay{d_i64, d_T, d_i64 + 1, d_i64 + 1};
+    LaunchFbankAny(d_wave, nullptr, lay, 1, T, d_tab, d_any, D, d_raw, nullptr);
+    step(hipGetLastError());
+    step(hipMemcpy(out->data, d_raw, sizeof(float) * (size_t)T * D, hipMemcpyDeviceToHost));
+  }
+  if (e != hipSuccess) ret = Fail(PK_MI355_E_DEVICE, "frontend_compute: %s", hipGetErrorString(e));
+  hipFree(d_tab); hipFree(d_any); hipFree(d_wave); hipFree(d_raw); hipFree(d_i64); hipFree(d_T);
   return ret;
 }
 

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "pk_dma.h"
+#include "pk_frontend.h"
 #include "pk_kernels.h"
 #include "pk_logf.h"
 #include "pk_wave.h"
@@ -481,6 +482,202 @@ __global__ __launch_bounds__(kWave * kFbankWaves, 4) void FbankKernel(
   }
 }
 
+// The front-end at a specification (pk_frontend.h): FbankKernel's frame walk with the spec's
+// window, then a mel stage for up to 128 bins and, for MFCC, the DCT and the lifter.  Everything up to the power
+// spectrum is FbankKernel's code -- MakeFftLane, ComplexFft256, RealPostPass called as they stand, the staging and the
+// pre-emphasis restated line for line -- so the bits are its bits.  The mel stage forms every tap's product once, tap
+// i = lane + 64 r by whichever lane that is (a product is one rounding wherever it is formed; there are no padding
+// taps, so nothing outside a triangle is ever read for it), then lane b and lane b + 64 add their bin's products in
+// ascending order.  MFCC: the log-mel values go through LDS, and lane k (and k + 64) runs the sequential dot with row
+// k of the DCT, read from global memory at [b][k] (consecutive lanes, consecutive addresses; 64 KiB at 128 x 128, which
+// LDS has no room for beside four frames), and multiplies by its lifter coefficient.
+template <typename SampleT>
+__global__ __launch_bounds__(kWave * kFbankWaves, 4) void FbankAnyKernel(
+    const SampleT *__restrict__ wave_pcm, UttLayout utts, const FrontendTables *__restrict__ gtab,
+    const FrontendAnyTables *__restrict__ gany, float *__restrict__ raw) {
+  __shared__ LdsTables tab;
+  __shared__ FrontendAnyLds any;
+  __shared__ FrameLds frames[kFbankWaves];
+
+  CopyTablesToLds(tab, gtab);
+  {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int kPieces = (int)(sizeof(FrontendAnyLds) / 16);
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(&gany->lds);
+    u32x4 *dst = reinterpret_cast<u32x4 *>(&any);
+    for (int i = threadIdx.x; i < kPieces; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  FrameLds &fr = frames[wv];
+  FftLane fc;
+  MakeFftLane(fc, lane, tab, fr.z);
+  float *s_x = fr.x, *s_pow = fr.pw;
+  f32x2 *s_z = fr.z;
+  static_assert(sizeof(float) * kAnyMaxTaps <= sizeof(float) * kFrameLength + sizeof(f32x2) * kFftCplx, "mel products fit in x + z");
+  static_assert(kAnyMaxBins <= kFftCplx && kAnyMaxBins == 2 * kWave && kAnyMaxTaps == 8 * kWave, "lane roles");
+  float *s_prod = fr.x;               // x and z are dead once the power spectrum is written
+  float *s_logmel = fr.pw;            // and the power spectrum once the products are formed
+  const int num_bins = gany->num_bins, num_ceps = gany->num_ceps, num_taps = gany->num_taps, D = gany->dim;
+  const int utt = blockIdx.y;
+  const int T = utts.num_frames[utt];
+  const SampleT *w0 = wave_pcm + utts.wave_off[utt];
+  float *out0 = raw + utts.raw_base[utt] * D;
+
+  // ---- FbankKernel's fetch (fbank.cc:74-100): pair p = lane + 64 r is point p of the half-size complex FFT
+  const int t_step = gridDim.x * kFbankWaves;
+  auto fetch = [&](int t, SampleT (&de)[4], SampleT (&dod)[4]) {
+    const SampleT *w = w0 + (int64_t)t * kFrameShift;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int pidx = lane + kWave * r;
+      const bool in = t < T && 2 * pidx + 1 < kFrameLength;
+      struct __attribute__((packed, aligned(sizeof(SampleT)))) Pair { SampleT e, o; };
+      Pair pr = {static_cast<SampleT>(0), static_cast<SampleT>(0)};
+      if (in) pr = *reinterpret_cast<const Pair *>(w + 2 * pidx);
+      de[r] = pr.e;
+      dod[r] = pr.o;
+    }
+  };
+  SampleT cur_e[4], cur_o[4], next_e[4], next_o[4];
+  fetch(blockIdx.x * kFbankWaves + wv, cur_e, cur_o);
+  for (int t = blockIdx.x * kFbankWaves + wv; t < T; t += t_step) {
+    fetch(t + t_step, next_e, next_o);
+    float xe[4], xo[4];
+    bool exact = true;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      xe[r] = static_cast<float>(cur_e[r]);
+      xo[r] = static_cast<float>(cur_o[r]);
+      if (!std::is_same<SampleT, int16_t>::value)
+        exact = exact && (fabsf(xe[r]) <= 32768.0f) && (xe[r] == truncf(xe[r]))
+                      && (fabsf(xo[r]) <= 32768.0f) && (xo[r] == truncf(xo[r]));
+    }
+
+    // ---- fbank.cc:48-52: DC offset = sequential float sum / 400 (integers of 16 bits: any order is exact)
+    float sum;
+    if (__all(exact)) {
+      const float p = ((xe[0] + xo[0]) + (xe[1] + xo[1])) + ((xe[2] + xo[2]) + (xe[3] + xo[3]));
+      sum = TwWaveSum(p);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int pidx = lane + kWave * r;
+        if (2 * pidx + 1 < kFrameLength) { s_x[2 * pidx] = xe[r]; s_x[2 * pidx + 1] = xo[r]; }
+      }
+      WaveSync();
+      float s = 0;
+      if (lane == 0) {
+#pragma unroll 8
+        for (int i = 0; i < kFrameLength; ++i) s += s_x[i];
+      }
+      sum = __shfl(s, 0);
+      WaveSync();
+    }
+    const float mean = sum / kFrameLength;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                     // fbank.cc:53-55
+      xe[r] -= mean;
+      xo[r] -= mean;
+    }
+
+    // ---- fbank.cc:58-68: pre-emphasis in double, one rounding to float, then the spec's window; zero padding 400..511
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int pidx = lane + kWave * r;
+      float prev_e = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, xo[r]), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+      if (lane == 0) prev_e = r == 0 ? xe[0] : __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xo[r > 0 ? r - 1 : 0]), 63));
+      const f32x2 win = *reinterpret_cast<const f32x2 *>(any.window + 2 * (pidx < kFrameLength / 2 ? pidx : 0));
+      float ye = 0.0f, yo = 0.0f;
+      if (2 * pidx + 1 < kFrameLength) {
+        ye = static_cast<float>(static_cast<double>(xe[r]) - 0.97 * static_cast<double>(prev_e));
+        ye *= win[0];
+        yo = static_cast<float>(static_cast<double>(xo[r]) - 0.97 * static_cast<double>(xe[r]));
+        yo *= win[1];
+      }
+      *((r & 1) ? PointHi(fc.stage[r >> 1]) : PointLo(fc.stage[r >> 1])) = f32x2{ye, yo};
+    }
+    WaveSync();
+
+    ComplexFft256(lane, fc);
+
+    // ---- bit-reversed read, real post-pass and power spectrum (srfft.cc:239-265, :389-436, fbank.cc:193-211)
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int k = 1 + lane + kWave * r;            // 1..128
+      const int kd = kFftCplx - k;
+      const RealBins rb = RealPostPass(fc, r);
+      s_pow[k] = rb.a_re * rb.a_re + rb.a_im * rb.a_im;
+      if (kd != k) s_pow[kd] = rb.o_re * rb.o_re + rb.o_im * rb.o_im;
+    }
+    if (lane == 0) {                                 // srfft.cc:444-447, fbank.cc:201-210
+      const f32x2 z00 = s_z[0];
+      const float zeroth = z00[0] + z00[1], n2th = z00[0] - z00[1];
+      s_pow[0] = zeroth * zeroth;
+      s_pow[kFftCplx] = n2th * n2th;
+    }
+    WaveSync();
+
+    // ---- mel energies (vector.cc:252-262): the products, tap i = lane + 64 r ...
+#pragma unroll 1
+    for (int r = 0; r < kAnyMaxTaps / kWave; ++r) {
+      const int i = lane + kWave * r;
+      if (i < num_taps) s_prod[i] = any.mel_w[i] * s_pow[any.mel_tap[i]];
+    }
+    WaveSync();
+    // ... then each bin's additions in ascending order, the floor and the log (fbank.cc:244-245)
+    float logmel[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      if (lane + kWave * r < num_bins) {
+        // (where the bin's run starts and its length: read per frame, as the window is -- held across the FFT they
+        // would cost the registers that keep the kernel at four waves per SIMD without scratch)
+        const float *q = s_prod + any.mel_base[lane + kWave * r];
+        const int len = any.mel_len[lane + kWave * r];
+        float e = 0.0f;
+        int j = 0;
+        for (; j + 4 <= len; j += 4) {
+          const float q0 = q[j], q1 = q[j + 1], q2 = q[j + 2], q3 = q[j + 3];
+          e += q0;
+          e += q1;
+          e += q2;
+          e += q3;
+        }
+        for (; j < len; ++j) e += q[j];
+        if (e < 1.1920928955078125e-07f) e = 1.1920928955078125e-07f;
+        logmel[r] = LogfRestated(e, tab.logf_tab);
+      }
+    }
+    if (num_ceps == 0) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        if (lane + kWave * r < num_bins) out0[(int64_t)t * D + lane + kWave * r] = logmel[r];
+    } else {
+      // ---- MFCC: c[k] = sum over b ascending of dct[k][b] * logmel[b], then the lifter
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        if (lane + kWave * r < num_bins) s_logmel[lane + kWave * r] = logmel[r];
+      WaveSync();
+#pragma unroll 1
+      for (int r = 0; r < 2; ++r) {
+        const int k = lane + kWave * r;
+        if (k < num_ceps) {
+          const float *dct = gany->dct_t + k;
+          float c = 0.0f;
+          for (int b = 0; b < num_bins; ++b) c += dct[b * kAnyMaxBins] * s_logmel[b];
+          c *= gany->lifter[k];
+          out0[(int64_t)t * D + k] = c;
+        }
+      }
+    }
+    WaveSync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { cur_e[r] = next_e[r]; cur_o[r] = next_o[r]; }
+  }
+}
+
 // One workgroup of four wavefronts per utterance.  The running window sum is rounded to float
 // every frame (cmvn.cc:66-70), so ONE wavefront walks the frames in order, one lane per
 // feature, and does nothing but that chain -- one f32 add while the window fills (for floats,
@@ -755,6 +952,20 @@ void LaunchFbank(const float *wave_f32, const int16_t *wave_i16, const UttLayout
     hipLaunchKernelGGL(FbankKernel<int16_t>, grid, block, 0, stream, wave_i16, utts, d_tables, raw);
   else
     hipLaunchKernelGGL(FbankKernel<float>, grid, block, 0, stream, wave_f32, utts, d_tables, raw);
+}
+
+void LaunchFbankAny(const float *wave_f32, const int16_t *wave_i16, const UttLayout &utts, int num_utts, int max_frames,
+                    const FrontendTables *d_tables, const FrontendAnyTables *d_any, int dim, float *raw, hipStream_t stream) {
+  if (num_utts <= 0 || max_frames <= 0 || dim <= 0) return;
+  int gx = 3072 / num_utts;     // LaunchFbank's grid: the frame walk is the same
+  if (gx < 1) gx = 1;
+  const int need = (max_frames + kFbankWaves - 1) / kFbankWaves;
+  if (gx > need) gx = need;
+  dim3 grid(gx, num_utts), block(kWave * kFbankWaves);
+  if (wave_i16)
+    hipLaunchKernelGGL(FbankAnyKernel<int16_t>, grid, block, 0, stream, wave_i16, utts, d_tables, d_any, raw);
+  else
+    hipLaunchKernelGGL(FbankAnyKernel<float>, grid, block, 0, stream, wave_f32, utts, d_tables, d_any, raw);
 }
 
 void LaunchCmvn(const float *raw, const UttLayout &utts, int num_utts, const float *d_global41,

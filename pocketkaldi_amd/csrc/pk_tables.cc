@@ -3,10 +3,12 @@
 // exactly where the reference's do.  See pk_tables.h / pk_resample.h for what each table is.
 #include "pk_tables.h"
 #include "pk_files.h"
+#include "pk_frontend.h"
 #include "pk_logf.h"
 #include "pk_resample.h"
 
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 #include <algorithm>
@@ -201,6 +203,104 @@ void BuildCmvnTables(float global_count_f, CmvnTables *t) {
   }
 }
 
+// ------------------------------------------------------------------ the front-end at a specification (pk_frontend.h)
+
+int BuildFrontendAnyTables(const pk_mi355_frontend_spec_t *spec, FrontendAnyTables *t) {
+  using pkhost::Fail;
+  if (!spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  const pk_mi355_frontend_spec_t &s = *spec;
+  if (s.kind != PK_MI355_FRONTEND_FBANK && s.kind != PK_MI355_FRONTEND_MFCC)
+    return Fail(PK_MI355_E_INVALID, "front-end spec: unknown kind %d (0 fbank, 1 MFCC)", s.kind);
+  if (s.window != PK_MI355_WINDOW_HAMMING && s.window != PK_MI355_WINDOW_POVEY)
+    return Fail(PK_MI355_E_INVALID, "front-end spec: unknown window %d (0 Hamming, 1 Povey)", s.window);
+  const int B = s.num_mel_bins;
+  if (B < kAnyMinBins || B > kAnyMaxBins)
+    return Fail(PK_MI355_E_INVALID, "front-end spec: num_mel_bins %d is outside %d .. %d", B, kAnyMinBins, kAnyMaxBins);
+  const bool mfcc = s.kind == PK_MI355_FRONTEND_MFCC;
+  if (mfcc && (s.num_ceps < 1 || s.num_ceps > B))
+    return Fail(PK_MI355_E_INVALID, "front-end spec: num_ceps %d is outside 1 .. num_mel_bins = %d", s.num_ceps, B);
+  if (!mfcc && s.num_ceps != 0) return Fail(PK_MI355_E_INVALID, "front-end spec: num_ceps must be 0 for fbank (got %d)", s.num_ceps);
+  if (!std::isfinite(s.low_freq) || s.low_freq < 0) return Fail(PK_MI355_E_INVALID, "front-end spec: low_freq %g is negative or not finite", (double)s.low_freq);
+  if (!std::isfinite(s.high_freq)) return Fail(PK_MI355_E_INVALID, "front-end spec: high_freq %g is not finite", (double)s.high_freq);
+  if (mfcc && (!std::isfinite(s.cepstral_lifter) || s.cepstral_lifter < 0))
+    return Fail(PK_MI355_E_INVALID, "front-end spec: cepstral_lifter %g is negative or not finite", (double)s.cepstral_lifter);
+  const float high = s.high_freq > 0.0f ? s.high_freq : kAnyNyquist + s.high_freq;      // Kaldi: <= 0 is an offset from Nyquist
+  if (high > kAnyNyquist || !(high > s.low_freq))
+    return Fail(PK_MI355_E_INVALID, "front-end spec: high_freq resolves to %g Hz: it must be above low_freq = %g and at most %g",
+                (double)high, (double)s.low_freq, (double)kAnyNyquist);
+
+  std::vector<FrontendAnyTables> own;      // (t == null: the check alone; 70 KiB, so not on the stack)
+  if (!t) { own.resize(1); t = own.data(); }
+  memset(t, 0, sizeof(*t));
+  t->kind = s.kind; t->num_bins = B; t->num_ceps = mfcc ? s.num_ceps : 0; t->dim = mfcc ? s.num_ceps : B;
+
+  // ---- window: the reference's float angle step (fbank.cc:249-256).  Hamming as BuildFrontendTables forms it (float
+  // cosine, the expression in double); Povey in double throughout.  One rounding to float.
+  const float a = kTwoPiTrunc / (kFrameLength - 1);
+  for (int i = 0; i < kFrameLength; ++i) {
+    const float i_fl = static_cast<float>(i);
+    if (s.window == PK_MI355_WINDOW_HAMMING) t->lds.window[i] = 0.54 - 0.46 * cosf(a * i_fl);
+    else t->lds.window[i] = pow(0.5 - 0.5 * cos(static_cast<double>(a) * i), 0.85);
+  }
+
+  // ---- mel triangles, fbank.cc:103-163 with B bins over the spec's band; a bin needs one tap (Kaldi's condition)
+  const float sample_freq = kSampleRate;
+  const int num_fft_bins = kFftSize / 2;
+  const float fft_bin_width = sample_freq / kFftSize;
+  // The band's edges: the reference writes MelScale(20) and MelScale(8000) with constants, which its compiler folds with
+  // a correctly rounded logarithm -- one ulp above the C library's logf at 20 Hz.  So the edges take the logarithm in
+  // double, rounded to float once (what the fold gives, at every band); the FFT bins' mel values below are computed at
+  // run time in the reference too, with the C library's logf.
+  auto edge_mel = [](float freq) { return 1127.0f * static_cast<float>(log(static_cast<double>(1.0f + freq / 700.0f))); };
+  const float mel_low = edge_mel(s.low_freq);
+  const float mel_high = edge_mel(high);
+  const float mel_delta = (mel_high - mel_low) / (B + 1);
+  int taps = 0;
+  for (int bin = 0; bin < B; ++bin) {
+    const float left = mel_low + bin * mel_delta;
+    const float center = mel_low + (bin + 1) * mel_delta;
+    const float right = mel_low + (bin + 2) * mel_delta;
+    int first = -1, last = -1;
+    float w[kFftSize / 2];
+    for (int i = 0; i < num_fft_bins; ++i) {
+      const float freq = fft_bin_width * i;
+      const float mel = MelScale(freq);
+      w[i] = 0.0f;
+      if (mel > left && mel < right) {
+        w[i] = (mel <= center) ? (mel - left) / (center - left) : (right - mel) / (right - center);
+        if (first < 0) first = i;
+        last = i;
+      }
+    }
+    if (first < 0)
+      return Fail(PK_MI355_E_INVALID, "front-end spec: mel bin %d of %d over %g .. %g Hz has an empty triangle (no FFT bin inside it): "
+                  "fewer bins or a wider band", bin, B, (double)s.low_freq, (double)high);
+    const int len = last + 1 - first;
+    if (taps + len > kAnyMaxTaps) return Fail(PK_MI355_E_INVALID, "internal: front-end spec with more than %d mel taps", kAnyMaxTaps);
+    t->mel_off[bin] = first;
+    t->lds.mel_base[bin] = (short)taps;
+    t->lds.mel_len[bin] = (short)len;
+    for (int j = 0; j < len; ++j) {
+      t->lds.mel_w[taps + j] = w[first + j];
+      t->lds.mel_tap[taps + j] = (short)(first + j);
+    }
+    taps += len;
+  }
+  t->num_taps = taps;
+
+  // ---- DCT and lifter (Kaldi's definitions), in double, one rounding
+  for (int k = 0; k < kAnyMaxBins; ++k) t->lifter[k] = 1.0f;
+  if (mfcc) {
+    for (int k = 0; k < s.num_ceps; ++k) {
+      for (int b = 0; b < B; ++b)
+        t->dct_t[b * kAnyMaxBins + k] = k == 0 ? sqrt(1.0 / B) : sqrt(2.0 / B) * cos(M_PI / B * (b + 0.5) * k);
+      const double Q = s.cepstral_lifter;
+      if (Q != 0) t->lifter[k] = 1.0 + 0.5 * Q * sin(M_PI * k / Q);
+    }
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ resampler (pk_resample.h)
 
 int BuildResampleTable(int rate, ResampleTable *t) {
@@ -307,6 +407,39 @@ int64_t pk_mi355_resample_num_output(int rate, int64_t n) {
   if (int rc = BuildOrFail(rate, &t)) return rc;
   if (n < 0) return pkhost::Fail(PK_MI355_E_INVALID, "negative sample count");
   return pkmi::ResampleNumOutput(t, n);
+}
+
+// ------------------------------------------------------------------ the front-end spec's host entries (no device)
+
+int pk_mi355_frontend_check(const pk_mi355_frontend_spec_t *spec) { return pkmi::BuildFrontendAnyTables(spec, nullptr); }
+
+int pk_mi355_frontend_dim(const pk_mi355_frontend_spec_t *spec) {
+  if (int rc = pkmi::BuildFrontendAnyTables(spec, nullptr)) return rc;
+  return spec->kind == PK_MI355_FRONTEND_MFCC ? spec->num_ceps : spec->num_mel_bins;
+}
+
+int pk_mi355_frontend_default(pk_mi355_frontend_spec_t *spec) {      // fbank.h:10, fbank.cc:116-117, :249-256
+  if (!spec) return pkhost::Fail(PK_MI355_E_INVALID, "null argument");
+  *spec = pk_mi355_frontend_spec_t{PK_MI355_FRONTEND_FBANK, pkmi::kNumBins, 0, PK_MI355_WINDOW_HAMMING, 20.0f, 0.0f, 0.0f};
+  return 0;
+}
+
+int pk_mi355_frontend_tables(const pk_mi355_frontend_spec_t *spec, float *window, int32_t *mel_off, int32_t *mel_len, float *mel_weights,
+                             float *dct, float *lifter) {
+  std::vector<pkmi::FrontendAnyTables> tv(1);
+  pkmi::FrontendAnyTables &t = tv[0];
+  if (int rc = pkmi::BuildFrontendAnyTables(spec, &t)) return rc;
+  if (window) memcpy(window, t.lds.window, sizeof(t.lds.window));
+  for (int b = 0; b < t.num_bins; ++b) {
+    if (mel_off) mel_off[b] = t.mel_off[b];
+    if (mel_len) mel_len[b] = t.lds.mel_len[b];
+  }
+  if (mel_weights) memcpy(mel_weights, t.lds.mel_w, sizeof(float) * t.num_taps);
+  for (int k = 0; k < t.num_ceps; ++k) {
+    if (dct) for (int b = 0; b < t.num_bins; ++b) dct[k * t.num_bins + b] = t.dct_t[b * pkmi::kAnyMaxBins + k];
+    if (lifter) lifter[k] = t.lifter[k];
+  }
+  return 0;
 }
 
 }  // extern "C"
