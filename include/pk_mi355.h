@@ -211,6 +211,12 @@ int pk_mi355_am_read(pk_mi355_am_t *am, const char *nnet_path, const char *prior
  * right_context, num_pdfs, tid2pdf (am.cc:22-62).  The decoder's keys (fst, symbol_table) are
  * not touched.  precision: PK_MI355_PRECISION_*.  On success *am_out is a finalized model.     */
 int pk_mi355_load(const char *config_path, int precision, pk_mi355_am_t **am_out, float *cmvn_stats41);
+/* The same for a model of any feature dimension: the cmvn_stats vector may have any length up
+ * to stats_cap and is copied to stats, its length to *stats_len.  PK_MI355_E_IO, both numbers and the file named, when
+ * it is longer than stats_cap or not pk_mi355_am_feat_dim + 1 long (the sums, then the count).  Every other check
+ * and message is pk_mi355_load's, which keeps its own "41 expected".                                             */
+int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **am_out, float *stats, int stats_cap,
+                        int *stats_len);
 
 int pk_mi355_am_num_pdfs(const pk_mi355_am_t *am);      /* am.h:38 */
 int pk_mi355_am_input_dim(const pk_mi355_am_t *am);     /* spliced width */
@@ -731,6 +737,19 @@ pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const floa
  * 8 x max(L + R, 1) x feat_dim bytes of every feature slot.                                                        */
 pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len,
                                                          int max_streams, int64_t max_step_frames);
+/* An online scorer with this front-end: pk_mi355_stream_create for a model of
+ * pk_mi355_frontend_dim(spec) features, F32 only.  Every frame's row is, bit for bit, the row of
+ * pk_mi355_frontend_batch_create's object on the whole wave, at every chunking and in both softmax modes; at the
+ * default spec also pk_mi355_stream_create's.  What is final is unchanged: an open slot scores [a, n - R), the step
+ * after close the rest.  open, open_rate (8 - 96 kHz), push, push_i16 and open_features / push_features (RAW and
+ * NORMALIZED, [n][dim]; a frame counts 160 samples) work in the same step.  Device memory per slot at dim != 40:
+ * 4 x dim + 2400 x dim + 8 x max(L + R, 1) x dim bytes of CMVN state and history beside the 3 192 bytes of tails.
+ * Before any device call: PK_MI355_E_INVALID for a bad spec (in pk_mi355_frontend_check's words), a spec whose
+ * dimension is not the model's (both numbers named), stats_len != feat_dim + 1 (both named), an f16 model, a
+ * capacity <= 0; PK_MI355_E_STATE for a model that is not finalized.  NULL on failure.                            */
+pk_mi355_stream_t *pk_mi355_frontend_stream_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec,
+                                                   const float *global_stats, int stats_len, int max_streams,
+                                                   int64_t max_step_samples);
 /* Open slot for features of `kind`.  Also valid on an object made by pk_mi355_stream_create (40-dim, both kinds): there
  * a pushed frame counts as 160 samples against max_step_samples.  The NORMALIZED slots' device state is made at the
  * first such open.  PK_MI355_E_INVALID: an unknown kind, RAW on an object without statistics; PK_MI355_E_STATE: the
@@ -959,6 +978,12 @@ const char *pk_mi355_symtab_get(const pk_mi355_symtab_t *st, int id);
 typedef struct pk_mi355_recognizer pk_mi355_recognizer_t;
 pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int precision, int max_utts,
                                                 int64_t max_total_samples, int64_t trace_capacity);
+/* The same for a model of pk_mi355_frontend_dim(spec) features: pk_mi355_load_stats and
+ * pk_mi355_frontend_batch_create in place of pk_mi355_load and pk_mi355_batch_create, whose refusals are this
+ * entry's; a bad spec is refused first.  Every other entry works unchanged; process_features takes [T][dim].    */
+pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec,
+                                                         int precision, int max_utts, int64_t max_total_samples,
+                                                         int64_t trace_capacity);
 void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r);
 /* The owned objects: beam, trace gc, softmax mode, f16 calibration and every result getter (words, weight, ok,
  * alignment, word segments) are their existing entries.                                                          */
@@ -993,6 +1018,12 @@ float pk_mi355_recognizer_loglikelihood_per_frame(const pk_mi355_recognizer_t *r
 typedef struct pk_mi355_online_recognizer pk_mi355_online_recognizer_t;
 pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config_path, int max_streams,
                                                               int64_t max_step_samples, int64_t trace_capacity);
+/* The same for a model of pk_mi355_frontend_dim(spec) features: pk_mi355_load_stats and
+ * pk_mi355_frontend_stream_create in place of pk_mi355_load and pk_mi355_stream_create, whose refusals are this
+ * entry's; a bad spec is refused first.  Every other entry works unchanged; push_features takes [n][dim].       */
+pk_mi355_online_recognizer_t *pk_mi355_frontend_online_recognizer_load(const char *config_path,
+                                                                       const pk_mi355_frontend_spec_t *spec, int max_streams,
+                                                                       int64_t max_step_samples, int64_t trace_capacity);
 void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r);
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r);
 pk_mi355_stream_t *pk_mi355_online_recognizer_stream(pk_mi355_online_recognizer_t *r);

@@ -325,6 +325,13 @@ class Recognizer {
     r_ = pk_mi355_recognizer_load(model_file.c_str(), precision, max_utts, max_total_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // A model of the spec's feature dimension (a FrontendSpec; pk_mi355_frontend_recognizer_load)
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, int precision = PK_MI355_PRECISION_F32,
+              int max_utts = 1, int64_t max_total_samples = 16000 * 60, int64_t trace_capacity = 0) {
+    pk_mi355_recognizer_destroy(r_);
+    r_ = pk_mi355_frontend_recognizer_load(model_file.c_str(), &spec, precision, max_utts, max_total_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   // pk_process for n waves at once; out (may be null) receives one Utterance per wave.  rates (may be null: 16000
   // throughout): the sample rate of every wave; the others are converted on the GPU (pk_mi355_recognizer_process_rates)
   Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out, const int *rates = nullptr) {
@@ -367,6 +374,13 @@ class OnlineScorer {
   enum FeaturesOnlyTag { kFeaturesOnly };
   OnlineScorer(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples)
       : s_(pk_mi355_stream_create(am, global_stats41, max_streams, max_step_samples)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // The front-end at a spec of the model's feature dimension (a FrontendSpec; pk_mi355_frontend_stream_create, DESIGN.md
+  // section 18): stats_len = that + 1.  Audio slots at any rate and feature slots of both kinds, as on the object above.
+  OnlineScorer(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t &spec, const float *global_stats, int stats_len, int max_streams,
+               int64_t max_step_samples)
+      : s_(pk_mi355_frontend_stream_create(am, &spec, global_stats, stats_len, max_streams, max_step_samples)) {
     if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   // Without a front-end (pk_mi355_features_stream_create): a model of any feature dimension, feature slots only,
@@ -645,6 +659,13 @@ class OnlineRecognizer {
               int64_t trace_capacity = 0) {
     pk_mi355_online_recognizer_destroy(r_);
     r_ = pk_mi355_online_recognizer_load(model_file.c_str(), max_streams, max_step_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // A model of the spec's feature dimension (a FrontendSpec; pk_mi355_frontend_online_recognizer_load)
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, int max_streams = 1,
+              int64_t max_step_samples = 16000 * 8, int64_t trace_capacity = 0) {
+    pk_mi355_online_recognizer_destroy(r_);
+    r_ = pk_mi355_frontend_online_recognizer_load(model_file.c_str(), &spec, max_streams, max_step_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   Status Open(int slot) { return Status::FromLast(pk_mi355_online_recognizer_open(r_, slot)); }

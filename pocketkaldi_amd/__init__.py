@@ -144,6 +144,7 @@ EXPORTS = [
     "pk_mi355_online_recognizer_open_features", "pk_mi355_online_recognizer_push_features",
     "pk_mi355_frontend_check", "pk_mi355_frontend_dim", "pk_mi355_frontend_default", "pk_mi355_frontend_tables",
     "pk_mi355_frontend_compute", "pk_mi355_frontend_batch_create",
+    "pk_mi355_frontend_stream_create", "pk_mi355_load_stats", "pk_mi355_frontend_recognizer_load", "pk_mi355_frontend_online_recognizer_load",
 ]
 
 
@@ -415,6 +416,13 @@ def lib():
     L.pk_mi355_frontend_compute.argtypes = [specp, C.POINTER(pk_vector_t), C.POINTER(pk_matrix_t)]
     L.pk_mi355_frontend_batch_create.restype = C.c_void_p
     L.pk_mi355_frontend_batch_create.argtypes = [C.c_void_p, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_frontend_stream_create.restype = C.c_void_p
+    L.pk_mi355_frontend_stream_create.argtypes = [C.c_void_p, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_load_stats.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), f32p, C.c_int, C.POINTER(C.c_int)]
+    L.pk_mi355_frontend_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_frontend_recognizer_load.argtypes = [C.c_char_p, specp, C.c_int, C.c_int, C.c_int64, C.c_int64]
+    L.pk_mi355_frontend_online_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_frontend_online_recognizer_load.argtypes = [C.c_char_p, specp, C.c_int, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -583,6 +591,33 @@ class FrontendSpec:
             self.kind, self.num_mel_bins, self.num_ceps, self.window, self.low_freq, self.high_freq, self.cepstral_lifter)
 
 
+def parse_frontend(text):
+    """A FrontendSpec from "key=value,key=value,...": the keys are FrontendSpec's field names (kind: fbank | mfcc, window:
+    hamming | povey, the others numbers), omitted keys take its defaults.  ValueError, the key named, for an unknown key
+    or a value that does not parse.  Nothing else is checked here: the library refuses a bad spec where it is used."""
+    fields = {"kind": FRONTEND_KINDS, "window": FRONTEND_WINDOWS, "num_mel_bins": int, "num_ceps": int, "low_freq": float,
+              "high_freq": float, "cepstral_lifter": float}
+    given = {}
+    for item in [t.strip() for t in text.split(",") if t.strip()]:
+        key, eq, value = item.partition("=")
+        key, value = key.strip(), value.strip()
+        if key not in fields:
+            raise ValueError("front-end spec: unknown key '%s' (the keys are %s)" % (key, ", ".join(sorted(fields))))
+        if key in given:
+            raise ValueError("front-end spec: key '%s' given twice" % key)
+        how = fields[key]
+        try:
+            if not eq:
+                raise ValueError
+            given[key] = how[value] if isinstance(how, dict) else how(value)
+            if given[key] != given[key]:                     # (nan parses as a float)
+                raise ValueError
+        except (KeyError, ValueError):
+            raise ValueError("front-end spec: bad value '%s' for key '%s'%s" % (
+                value, key, " (one of %s)" % ", ".join(sorted(how)) if isinstance(how, dict) else ""))
+    return FrontendSpec(**given)
+
+
 def frontend_default():
     """The reference's configuration (pk_mi355_frontend_default)."""
     st = pk_mi355_frontend_spec_t()
@@ -688,6 +723,18 @@ class AcousticModel:
         _check(lib().pk_mi355_load(config_path.encode(), cls.PRECISIONS[precision], C.byref(h), _fp(stats)))
         self._h = h.value
         return self, stats
+
+    @classmethod
+    def load_stats(cls, config_path, precision="f32", stats_cap=129):
+        """load for a model of any feature dimension (pk_mi355_load_stats): (model, cmvn_global_stats[feat_dim + 1])."""
+        self = cls.__new__(cls)
+        h, n = C.c_void_p(), C.c_int()
+        stats = np.zeros(max(int(stats_cap), 1), dtype=np.float32)
+        self._h = None
+        _check_code(lib().pk_mi355_load_stats(os.fspath(config_path).encode(), cls.PRECISIONS[precision], C.byref(h), _fp(stats), int(stats_cap),
+                                              C.byref(n)))
+        self._h = h.value
+        return self, stats[:n.value].copy()
 
     def set_softmax(self, mode):
         """"stable" (default): overflow-safe log-softmax; "reference": the reference's operations one by one."""
@@ -1073,12 +1120,20 @@ class OnlineScorer:
     [a, n - R) of an open slot, the rest after close()), bit for bit what BatchScorer gives on the whole wave.  A slot
     opened with open_features takes [n][40] frames through push_features instead (OnlineFeatureScorer: any dimension)."""
 
-    def __init__(self, am, global_stats, max_streams, max_step_samples):
+    def __init__(self, am, global_stats, max_streams, max_step_samples, frontend=None):
+        """frontend: a FrontendSpec of the model's feature dimension (pk_mi355_frontend_stream_create; global_stats: that
+        many sums, then the count).  Feature slots then take [n][dim] frames."""
         g = _f32(global_stats)
-        if g.shape != (41,):
-            raise PkError("global_stats must have 41 entries")
         self._am = am
         self._max_streams = int(max_streams)
+        if frontend is not None:
+            self._h = lib().pk_mi355_frontend_stream_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
+                                                            int(max_streams), int(max_step_samples))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
+        if g.shape != (41,):
+            raise PkError("global_stats must have 41 entries")
         self._h = lib().pk_mi355_stream_create(am.handle, _fp(g), int(max_streams), int(max_step_samples))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
@@ -1647,9 +1702,15 @@ class Recognizer:
     scorer and a decoder with alignment on.  .am / .batch / .decoder / .symbols are the owned objects (beam, trace gc,
     softmax mode and calibration are set through them); process(waves) -> [Result]."""
 
-    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0):
-        self._h = lib().pk_mi355_recognizer_load(os.fspath(config).encode(), AcousticModel.PRECISIONS[precision], int(max_utts),
-                                                 int(max_total_samples), int(trace_capacity))
+    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0, frontend=None):
+        """frontend: a FrontendSpec; the model file is then one of that feature dimension (pk_mi355_frontend_recognizer_load)."""
+        if frontend is not None:
+            self._h = lib().pk_mi355_frontend_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()),
+                                                              AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
+                                                              int(trace_capacity))
+        else:
+            self._h = lib().pk_mi355_recognizer_load(os.fspath(config).encode(), AcousticModel.PRECISIONS[precision], int(max_utts),
+                                                     int(max_total_samples), int(trace_capacity))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self.max_utts, self.max_total_samples = int(max_utts), int(max_total_samples)
@@ -1749,9 +1810,15 @@ class OnlineRecognizer:
     close and step through the recognizer, not through .scorer / .decoder: a slot closed behind its back is never
     reported finished."""
 
-    def __init__(self, config, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0):
-        self._h = lib().pk_mi355_online_recognizer_load(os.fspath(config).encode(), int(max_streams), int(max_step_samples),
-                                                        int(trace_capacity))
+    def __init__(self, config, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0, frontend=None):
+        """frontend: a FrontendSpec; the model file is then one of that feature dimension
+        (pk_mi355_frontend_online_recognizer_load)."""
+        if frontend is not None:
+            self._h = lib().pk_mi355_frontend_online_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()), int(max_streams),
+                                                                     int(max_step_samples), int(trace_capacity))
+        else:
+            self._h = lib().pk_mi355_online_recognizer_load(os.fspath(config).encode(), int(max_streams), int(max_step_samples),
+                                                            int(trace_capacity))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self.max_streams, self.max_step_samples = int(max_streams), int(max_step_samples)

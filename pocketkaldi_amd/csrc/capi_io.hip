@@ -10,11 +10,12 @@
 using namespace pkmi;
 using namespace pkhost;
 
-extern "C" {
-
-int pk_mi355_am_read(pk_mi355_am_t *am, const char *nnet_path, const char *prior_path,
-                     const char *tid2pdf_path, int left_context, int right_context,
-                     int num_pdfs) {
+namespace {
+// pk_mi355_am_read.  files_fit: called with the first linear layer's input width once every file is read
+// and before the model -- and with it the device -- is touched; its code, if not 0, is the entry's.
+template <class FilesFit>
+int AmRead(pk_mi355_am_t *am, const char *nnet_path, const char *prior_path, const char *tid2pdf_path, int left_context, int right_context,
+           int num_pdfs, FilesFit files_fit) {
   if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model already finalized");
   std::vector<HostLayer> layers;
   std::vector<float> prior;
@@ -26,11 +27,25 @@ int pk_mi355_am_read(pk_mi355_am_t *am, const char *nnet_path, const char *prior
   if ((int)prior.size() != num_pdfs)
     return Fail(PK_MI355_E_INVALID, "prior has %d entries, num_pdfs = %d", (int)prior.size(), num_pdfs);
   for (const HostLayer &L : layers)
+    if (L.type == PK_NNET_LINEAR_LAYER) {
+      if ((rc = files_fit(L.in_dim))) return rc;
+      break;
+    }
+  for (const HostLayer &L : layers)
     if ((rc = L.type == PK_NNET_LINEAR_LAYER ? pk_mi355_am_add_linear(am, L.in_dim, L.out_dim, L.W.data(), L.b.data())
                                              : pk_mi355_am_add_layer(am, L.type)))
       return rc;
   return pk_mi355_am_finalize(am, prior.data(), num_pdfs, left_context, right_context,
                               tid.empty() ? nullptr : tid.data(), (int)tid.size());
+}
+}  // namespace
+
+extern "C" {
+
+int pk_mi355_am_read(pk_mi355_am_t *am, const char *nnet_path, const char *prior_path,
+                     const char *tid2pdf_path, int left_context, int right_context,
+                     int num_pdfs) {
+  return AmRead(am, nnet_path, prior_path, tid2pdf_path, left_context, right_context, num_pdfs, [](int) { return 0; });
 }
 
 // pk_load's share of this path (pocketkaldi.cc:72-144)
@@ -50,6 +65,35 @@ int pk_mi355_load(const char *config_path, int precision, pk_mi355_am_t **am_out
     return rc;
   }
   memcpy(cmvn_stats41, conf.cmvn_stats, sizeof(conf.cmvn_stats));
+  *am_out = am;
+  return 0;
+}
+
+// pk_mi355_load for a model of any feature dimension: the statistics vector at the model's length
+int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **am_out, float *stats, int stats_cap, int *stats_len) {
+  if (!config_path || !am_out || !stats || !stats_len) return Fail(PK_MI355_E_INVALID, "null argument");
+  *am_out = nullptr; *stats_len = 0;
+  if (stats_cap <= 0) return Fail(PK_MI355_E_INVALID, "bad statistics capacity %d", stats_cap);
+  ModelConfig conf;
+  int rc = ReadModelConfigStats(config_path, stats_cap, &conf);
+  if (rc) return rc;
+  pk_mi355_am_t *am = pk_mi355_am_create();
+  if (!am) return PK_MI355_E_DEVICE;
+  // the statistics against the model's feature dimension -- the first layer's width over the spliced frames -- as soon as
+  // the files are read (a width that is no multiple of the frames is the model's own refusal, at finalize)
+  auto stats_fit = [&](int in_dim) {
+    const int frames = conf.left + conf.right + 1, dim = in_dim / frames;
+    if (in_dim % frames != 0 || (int)conf.stats.size() == dim + 1) return 0;
+    return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, the %d-dim model of %s needs %d (the sums, then the count)", conf.cmvn_path.c_str(),
+                (int)conf.stats.size(), dim, config_path, dim + 1);
+  };
+  if ((rc = pk_mi355_am_set_precision(am, precision)) ||
+      (rc = AmRead(am, conf.nnet.c_str(), conf.prior.c_str(), conf.tid2pdf.c_str(), conf.left, conf.right, conf.num_pdfs, stats_fit))) {
+    pk_mi355_am_destroy(am);
+    return rc;
+  }
+  memcpy(stats, conf.stats.data(), sizeof(float) * conf.stats.size());
+  *stats_len = (int)conf.stats.size();
   *am_out = am;
   return 0;
 }

@@ -179,16 +179,24 @@ void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r) {
   delete r;
 }
 
-pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config_path, int max_streams, int64_t max_step_samples,
-                                                              int64_t trace_capacity) {
-  if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
-  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
+}  // extern "C"
+
+namespace {
+// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
+pk_mi355_online_recognizer_t *LoadOnlineRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int max_streams,
+                                                   int64_t max_step_samples, int64_t trace_capacity) {
   pk_mi355_online_recognizer *r = new pk_mi355_online_recognizer();
   auto failed = [&]() { pk_mi355_online_recognizer_destroy(r); return nullptr; };
-  if (LoadRecognizerFiles(config_path, r)) return failed();
-  float stats[kCmvnStats];
-  if (pk_mi355_load(config_path, PK_MI355_PRECISION_F32, &r->am, stats)) return failed();
-  if (!(r->stream = pk_mi355_stream_create(r->am, stats, max_streams, max_step_samples))) return failed();
+  if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
+  float stats[kMaxCmvnStats];
+  if (spec) {
+    int stats_len = 0;
+    if (pk_mi355_load_stats(config_path, PK_MI355_PRECISION_F32, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->stream = pk_mi355_frontend_stream_create(r->am, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
+  } else {
+    if (pk_mi355_load(config_path, PK_MI355_PRECISION_F32, &r->am, stats)) return failed();
+    if (!(r->stream = pk_mi355_stream_create(r->am, stats, max_streams, max_step_samples))) return failed();
+  }
   if (!(r->decoder = pk_mi355_online_decoder_create(r->fst, r->am, max_streams, trace_capacity))) return failed();
   if (pk_mi355_online_decoder_set_alignment(r->decoder, 1)) return failed();
   r->max_streams = max_streams;
@@ -200,6 +208,24 @@ pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config
   r->pieces.assign(max_streams, std::vector<pk_mi355_online_recognizer::Piece>());
   r->piece_first.assign(max_streams, 0);
   return r;
+}
+}  // namespace
+
+extern "C" {
+
+pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config_path, int max_streams, int64_t max_step_samples,
+                                                              int64_t trace_capacity) {
+  if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
+  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
+  return LoadOnlineRecognizer(config_path, nullptr, max_streams, max_step_samples, trace_capacity);
+}
+
+pk_mi355_online_recognizer_t *pk_mi355_frontend_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec,
+                                                                       int max_streams, int64_t max_step_samples, int64_t trace_capacity) {
+  if (!config_path || !spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
+  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
+  return LoadOnlineRecognizer(config_path, spec, max_streams, max_step_samples, trace_capacity);
 }
 
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r) {

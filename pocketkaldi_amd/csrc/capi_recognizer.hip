@@ -11,13 +11,13 @@ using namespace pkhost;
 
 namespace pkhost {
 
-int LoadRecognizerFiles(const char *config_path, RecognizerFiles *r) {
+int LoadRecognizerFiles(const char *config_path, RecognizerFiles *r, bool any_stats) {
   // pk_load's order (pocketkaldi.cc:81-131): fst, cmvn_stats, the AcousticModel keys, symbol_table.  Keys and host-side
   // files first, so that a model file that cannot work is refused before the device is touched.
   std::string path;
   ModelConfig conf;
   if (ConfigPath(config_path, "fst", &path) || !(r->fst = pk_mi355_fst_read(path.c_str()))) return pk_mi355_last_error_code();
-  int rc = ReadModelConfig(config_path, &conf);
+  int rc = any_stats ? ReadModelConfigStats(config_path, kMaxCmvnStats, &conf) : ReadModelConfig(config_path, &conf);
   if (rc) return rc;
   if (ConfigPath(config_path, "symbol_table", &path) || !(r->symtab = pk_mi355_symtab_read(path.c_str())))
     return pk_mi355_last_error_code();
@@ -68,19 +68,45 @@ void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
   delete r;
 }
 
+}  // extern "C"
+
+namespace {
+// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
+pk_mi355_recognizer_t *LoadRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision, int max_utts,
+                                      int64_t max_total_samples, int64_t trace_capacity) {
+  pk_mi355_recognizer *r = new pk_mi355_recognizer();
+  auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
+  if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
+  float stats[kMaxCmvnStats];
+  if (spec) {
+    int stats_len = 0;
+    if (pk_mi355_load_stats(config_path, precision, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->batch = pk_mi355_frontend_batch_create(r->am, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
+  } else {
+    if (pk_mi355_load(config_path, precision, &r->am, stats)) return failed();
+    if (!(r->batch = pk_mi355_batch_create(r->am, stats, max_utts, max_total_samples))) return failed();
+  }
+  if (!(r->decoder = pk_mi355_decoder_create(r->fst, r->am, max_utts, trace_capacity))) return failed();
+  if (pk_mi355_decoder_set_alignment(r->decoder, 1)) return failed();
+  return r;
+}
+}  // namespace
+
+extern "C" {
+
 pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int precision, int max_utts, int64_t max_total_samples,
                                                 int64_t trace_capacity) {
   if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
   if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
-  pk_mi355_recognizer *r = new pk_mi355_recognizer();
-  auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
-  if (LoadRecognizerFiles(config_path, r)) return failed();
-  float stats[kCmvnStats];
-  if (pk_mi355_load(config_path, precision, &r->am, stats)) return failed();
-  if (!(r->batch = pk_mi355_batch_create(r->am, stats, max_utts, max_total_samples))) return failed();
-  if (!(r->decoder = pk_mi355_decoder_create(r->fst, r->am, max_utts, trace_capacity))) return failed();
-  if (pk_mi355_decoder_set_alignment(r->decoder, 1)) return failed();
-  return r;
+  return LoadRecognizer(config_path, nullptr, precision, max_utts, max_total_samples, trace_capacity);
+}
+
+pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision,
+                                                         int max_utts, int64_t max_total_samples, int64_t trace_capacity) {
+  if (!config_path || !spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
+  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
+  return LoadRecognizer(config_path, spec, precision, max_utts, max_total_samples, trace_capacity);
 }
 
 pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r) {

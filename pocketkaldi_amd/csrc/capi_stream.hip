@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "pk_frontend.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -77,6 +78,11 @@ struct pk_mi355_stream {
   float *h_native = nullptr, *d_native = nullptr;
   int64_t native_cap = 0;
   bool staged = false;
+  // made by pk_mi355_frontend_stream_create: the spec's tables; a step then runs FbankAnyKernel
+  // instead of FbankKernel.  At a dimension other than 40 the audio slots' fresh rows lie in the upload staging from
+  // float rows_area on (behind the max_step_samples samples), where the chain and the layout kernel find them.
+  FrontendAnyTables *d_any = nullptr;
+  int64_t rows_area = 0;
 };
 
 namespace {
@@ -107,13 +113,15 @@ void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
   if (s->have_stats && c.am->feat_dim != kNumBins) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
     chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * c.am->feat_dim));
     chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * c.am->feat_dim));
+    if (s->rows_area)                  // audio slots are laid out by StreamFeatureLayoutKernel: their history, at create
+      chk(hipMalloc(&s->d_feat_hist, sizeof(float) * max_streams * 2 * s->hist_len * c.am->feat_dim));
   } else if (s->have_stats) {
     chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
     chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * kNumBins));
     chk(hipMalloc(&s->d_hist, sizeof(float) * max_streams * s->hist_len * kNumBins));
     chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
   }
-  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * s->upload_cap, hipHostMallocDefault));
+  chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * (s->rows_area ? s->rows_area : s->upload_cap), hipHostMallocDefault));
   chk(hipMalloc(&s->d_upload, sizeof(float) * s->upload_cap));
   chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
   chk(hipMalloc(&s->d_meta, s->meta_bytes));
@@ -158,6 +166,56 @@ pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global
   const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
   CreateCheck chk{"stream_create"};
   CreateScorerCore(&c, am, global_stats41, kNumBins, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  CreateStepBuffers(s, chk);
+  chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
+  chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
+  if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
+  return s;
+}
+
+pk_mi355_stream_t *pk_mi355_frontend_stream_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
+                                                   int stats_len, int max_streams, int64_t max_step_samples) {
+  if (!am || !spec || !global_stats) { Fail(PK_MI355_E_INVALID, am ? "null argument" : "null model"); return nullptr; }
+  std::vector<FrontendAnyTables> any(1);
+  if (BuildFrontendAnyTables(spec, any.data())) return nullptr;      // (names the field)
+  if (!ModelAllowed(am)) return nullptr;
+  const int D = am->feat_dim;
+  if (any[0].dim != D) {
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model expects %d", any[0].dim, D);
+    return nullptr;
+  }
+  if (stats_len != D + 1) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, D, D + 1);
+    return nullptr;
+  }
+  if (max_streams <= 0 || max_step_samples <= 0 || max_step_samples > (int64_t)1 << 30) {
+    Fail(PK_MI355_E_INVALID, "bad stream capacity");
+    return nullptr;
+  }
+  if (UseDevice(am->device)) return nullptr;
+  pk_mi355_stream *s = new pk_mi355_stream();
+  ScorerCore &c = s->core;
+  s->max_streams = max_streams; s->max_step_samples = max_step_samples;
+  s->have_stats = true;
+  s->slots.resize(max_streams);
+  s->hist_len = std::max(am->left + am->right, 1);
+  // segments, frames and rows as pk_mi355_stream_create counts them
+  s->wave_cap = max_step_samples + (int64_t)max_streams * kTailCap;
+  const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
+  // D == 40: FbankAnyKernel writes d_rows, where StreamCmvnKernel reads.  Otherwise the staging holds the step's samples
+  // (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
+  s->rows_area = D == kNumBins ? 0 : RoundUp(max_step_samples, 64);
+  s->upload_cap = D == kNumBins ? max_step_samples : s->rows_area + max_frames * D;
+  CreateCheck chk{"frontend_stream_create"};
+  CreateScorerCore(&c, am, global_stats, D, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  if (!c.d_tables && chk.ok) {                       // (the scorer core makes FbankKernel's tables for 40-dim statistics only)
+    FrontendTables host;
+    if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+    chk(hipMalloc(&c.d_tables, sizeof(FrontendTables)));
+    if (chk.ok) chk(hipMemcpy(c.d_tables, &host, sizeof(FrontendTables), hipMemcpyHostToDevice));
+  }
+  chk(hipMalloc(&s->d_any, sizeof(FrontendAnyTables)));
+  if (chk.ok) chk(hipMemcpy(s->d_any, any.data(), sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
   CreateStepBuffers(s, chk);
   chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
   chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
@@ -219,7 +277,7 @@ void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   hipSetDevice(s->core.device);
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
   hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist); hipFree(s->d_feat_hist);
-  hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta);
+  hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta); hipFree(s->d_any);
   s->resampler.Free();
   if (s->h_native) hipHostFree(s->h_native);
   hipFree(s->d_native);
@@ -363,8 +421,13 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   StreamRec *recs = reinterpret_cast<StreamRec *>(s->h_meta);
   char *lay_base = s->h_meta + RoundUp(sizeof(StreamRec) * s->max_streams, 256);
   const size_t shift4_at = s->meta_bytes - sizeof(int32_t) * Shift4Cap(c.max_cols);
-  // Records: audio and RAW slots (StreamAssembleKernel, FbankKernel, StreamCmvnKernel) from the front of the array,
-  // NORMALIZED slots (StreamFeatureLayoutKernel) from its back; rows and columns in slot order whichever the type.
+  // Records.  A 40-dim object: audio and RAW slots (StreamAssembleKernel, FbankKernel or FbankAnyKernel,
+  // StreamCmvnKernel) from the front of the array, NORMALIZED slots (StreamFeatureLayoutKernel) from its back.  Another
+  // dimension: audio slots from the front, feature slots of both kinds from the back; on an object with a front-end spec
+  // (rows_area != 0) the back block is then moved up behind the front one, in slot order (below, once the plan is known
+  // to fit), so that records [0, n_front) are exactly the audio slots -- what the assembly and the fbank see -- and records
+  // [0, n_front + n_back) exactly the slots taking part -- what StreamCmvnChainKernel and StreamFeatureLayoutKernel see.
+  // Rows and columns are in slot order whichever the type and wherever the record lies.
   std::vector<int> who, at, flushed;                  // slots taking part, their records; closed slots with nothing left
   int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
   int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, chain_pushed = 0, max_feat_cols = 0;
@@ -378,7 +441,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     // (a feature slot: no samples, an empty segment; its frames are what was pushed)
     // (RAW at a dimension other than 40: StreamCmvnChainKernel normalises the pushed rows where they lie, and the
     // record then goes with the NORMALIZED ones)
-    const bool feats = z.kind >= 0, layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && D != kNumBins);
+    // (a front-end spec at a dimension other than 40, DESIGN.md section 18: audio records go the same way, their rows
+    // written into the staging's row area by FbankAnyKernel; they stay in front, where the assembly and the fbank look)
+    const bool feats = z.kind >= 0, spec_rows = !feats && s->rows_area > 0;
+    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && D != kNumBins);
     const int new_len = feats    ? 0
                         : !z.tab ? (int)z.pending.size()
                                  : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
@@ -396,6 +462,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
     r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
     r.woff = woff; r.new_off = upl; r.raw_base = layout ? 0 : raw;
+    r.row_off = spec_rows ? s->rows_area + raw * D : upl;
     r.col_base = 0; r.cols = 0;
     if (b > z.a) {
       // Rows slot after slot, each padded to four; the slot's columns a - L .. b + R - 1 in a region of RoundUp(b - a, 4)
@@ -407,7 +474,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       out += RoundUp(b - z.a, 4);
       col += r.cols;
       spans.push_back({out, shift});
-      if (layout) max_feat_cols = std::max(max_feat_cols, r.cols);
+      if (layout || spec_rows) max_feat_cols = std::max(max_feat_cols, r.cols);
     }
     woff += seg; upl += feats ? (int64_t)m * D : new_len;
     if (!layout) raw += m;
@@ -417,9 +484,19 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     who.push_back(slot);
     at.push_back(rec_at);
   }
-  if (woff > s->wave_cap || upl > s->upload_cap || (n_back > 0 && !s->d_feat_hist) || native_total > s->native_cap || raw > c.max_frames ||
-      RoundUp(out, kTileF16) > c.max_cols || col > c.max_cols)
+  const int64_t upl_cap = s->rows_area ? s->rows_area : s->upload_cap;      // (a row area: the pushes end where it begins)
+  const bool staging_fits = woff <= s->wave_cap && upl <= upl_cap && native_total <= s->native_cap &&
+                            (!s->rows_area || s->rows_area + raw * D <= s->upload_cap);
+  const bool rows_fit = raw <= c.max_frames && RoundUp(out, kTileF16) <= c.max_cols && col <= c.max_cols;
+  if (!staging_fits || !rows_fit || (n_back > 0 && !s->d_feat_hist))
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
+  // A front-end spec at D != 40: the back block (taken last first) moves up behind the front one, as told above.
+  if (s->rows_area) {
+    const std::vector<StreamRec> back(recs + (s->max_streams - n_back), recs + s->max_streams);
+    for (int j = 0; j < n_back; ++j) recs[n_front + j] = back[n_back - 1 - j];
+    for (int &k : at)
+      if (k >= n_front) k = n_front + (s->max_streams - 1 - k);
+  }
   // the column shift of every group of four rows (the groups past the last row keep the last shift)
   const int64_t total_rows = out;
   int32_t bad = 0;
@@ -454,6 +531,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     if (z.kind < 0) {
       z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
       z.tail_par ^= 1;
+      if (s->rows_area && r.m) z.hist_par ^= 1;     // laid out by StreamFeatureLayoutKernel: the step writes the other history buffer
     }
     z.n = r.n_old + r.m;
     z.a = r.b;
@@ -495,23 +573,42 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   const int64_t *d_woff = reinterpret_cast<const int64_t *>(d_lay);
   const int64_t *d_rawb = d_woff + s->max_streams;
   const int32_t *d_T = reinterpret_cast<const int32_t *>(d_rawb + s->max_streams);
-  // A step of audio slots alone: the three launches below, over all K records, as ever.  RAW slots ride along with an
-  // empty segment and T = 0; their pushed rows reach d_rows by one launch more per step.
-  if (n_audio > 0) {
-    LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
-    UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
-    LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
+  UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
+  if (s->rows_area) {
+    // A front-end spec at D != 40: assembly and fbank over the n_front audio records, the rows
+    // [raw_base][D] going to the staging's row area; then every record through the chain (audio and RAW ones are
+    // normalised where they lie, NORMALIZED ones return) and through the layout, which reads what the chain leaves.
+    const int n_recs = n_front + n_back;
+    if (n_audio > 0) {
+      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
+      LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_upload + s->rows_area, c.stream);
+    }
+    if (max_m > 0 || chain_pushed > 0)
+      LaunchStreamCmvnChain(d_recs, n_recs, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
+    LaunchStreamFeatureLayout(d_recs, n_recs, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
+  } else {
+    // Every other object, as ever.  A step of audio slots alone: assembly, fbank (the spec's kernel on a spec'd 40-dim
+    // object, into the same rows) and StreamCmvnKernel over the n_front front records.  RAW slots at 40 ride along with an
+    // empty segment and T = 0; their pushed rows reach d_rows by one launch more per step.  The back records -- NORMALIZED
+    // slots, and RAW ones at another dimension, which the chain normalises first -- go through the layout.
+    if (n_audio > 0) {
+      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
+      if (s->d_any)
+        LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_rows, c.stream);
+      else
+        LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
+    }
+    if (raw_pushed > 0) LaunchStreamRawRows(d_recs, n_front, s->d_upload, s->d_rows, c.stream);
+    if (n_front > 0)
+      LaunchStreamCmvn(d_recs, n_front, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
+                       c.d_yt, c.ldy, c.stream);
+    if (chain_pushed > 0)                // before the layout: it reads the rows the chain leaves behind
+      LaunchStreamCmvnChain(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist,
+                            c.stream);
+    if (n_back > 0)
+      LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
+                                c.d_yt, c.ldy, c.stream);
   }
-  if (raw_pushed > 0) LaunchStreamRawRows(d_recs, n_front, s->d_upload, s->d_rows, c.stream);
-  if (n_front > 0)
-    LaunchStreamCmvn(d_recs, n_front, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
-                     c.d_yt, c.ldy, c.stream);
-  if (chain_pushed > 0)                // before the layout: it reads the rows the chain leaves behind
-    LaunchStreamCmvnChain(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist,
-                          c.stream);
-  if (n_back > 0)
-    LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
-                              c.d_yt, c.ldy, c.stream);
   const Operand op{c.d_yt, nullptr, c.ldy, ZeroSource(c), reinterpret_cast<const int32_t *>(s->d_meta + shift4_at)};
   const Lane lane{c.stream, &c.exec};
   if ((rc = WalkChunks(am, op, total_rows, c.chunk, &lane, 1, true, prob_scale, c.d_ll, nullptr))) return rc;

@@ -144,7 +144,19 @@ struct ConfigFile {
 
 }  // namespace
 
-int ReadModelConfig(const char *config_path, ModelConfig *out) {
+namespace {
+int ReadModelConfigAt(const char *config_path, int stats_cap, ModelConfig *out);   // stats_cap 0: the reference's 41
+}
+
+int ReadModelConfig(const char *config_path, ModelConfig *out) { return ReadModelConfigAt(config_path, 0, out); }
+
+int ReadModelConfigStats(const char *config_path, int stats_cap, ModelConfig *out) {
+  if (stats_cap <= 0) return Fail(PK_MI355_E_INVALID, "bad statistics capacity %d", stats_cap);
+  return ReadModelConfigAt(config_path, stats_cap, out);
+}
+
+namespace {
+int ReadModelConfigAt(const char *config_path, int stats_cap, ModelConfig *out) {
   ConfigFile conf;
   int rc = conf.Read(config_path);
   if (rc) return rc;
@@ -152,9 +164,16 @@ int ReadModelConfig(const char *config_path, ModelConfig *out) {
   std::string cmvn_path;
   std::vector<float> stats;
   if ((rc = conf.Path("cmvn_stats", &cmvn_path)) || (rc = ReadVec(cmvn_path.c_str(), &stats))) return rc;
-  if ((int)stats.size() != kCmvnStats)
-    return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, %d expected", cmvn_path.c_str(), (int)stats.size(), kCmvnStats);
-  memcpy(out->cmvn_stats, stats.data(), sizeof(out->cmvn_stats));
+  if (stats_cap == 0) {
+    if ((int)stats.size() != kCmvnStats)
+      return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, %d expected", cmvn_path.c_str(), (int)stats.size(), kCmvnStats);
+    memcpy(out->cmvn_stats, stats.data(), sizeof(out->cmvn_stats));
+  } else {
+    if (stats.empty() || (int)stats.size() > stats_cap)
+      return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, 1 to %d expected", cmvn_path.c_str(), (int)stats.size(), stats_cap);
+    out->stats = stats;
+    out->cmvn_path = cmvn_path;
+  }
   // AcousticModel::Read, am.cc:22-62 (a missing left_context is not an error there either)
   if ((rc = conf.Path("nnet", &out->nnet)) || (rc = conf.Path("prior", &out->prior))) return rc;
   if (conf.Find("left_context") && (rc = conf.Integer("left_context", &out->left))) return rc;
@@ -164,6 +183,7 @@ int ReadModelConfig(const char *config_path, ModelConfig *out) {
   if (out->left < 0 || out->right < 0) return Fail(PK_MI355_E_INVALID, "negative context in %s", config_path);
   return 0;
 }
+}  // namespace
 
 // ------------------------------------------------------------------ WAV
 

@@ -98,10 +98,15 @@ constexpr int kCmvnStats = 41;   // 40 sums + the frame count
 // what pk_load takes from the model file (pocketkaldi.cc:72-144, am.cc:22-62)
 struct ModelConfig {
   float cmvn_stats[kCmvnStats];
+  std::vector<float> stats;        // ReadModelConfigStats: the cmvn_stats vector at its own length (cmvn_stats is then not set)
+  std::string cmvn_path;           // the file it came from
   std::string nnet, prior, tid2pdf;
   int left = 0, right = 0, num_pdfs = 0;
 };
 int ReadModelConfig(const char *config_path, ModelConfig *out);
+// The same file for a model of any feature dimension: a cmvn_stats vector of 1 .. stats_cap floats (PK_MI355_E_IO
+// otherwise, both numbers and the file named).  Whether it fits the model is the caller's check.
+int ReadModelConfigStats(const char *config_path, int stats_cap, ModelConfig *out);
 
 // ------------------------------------------------------------------ WAV
 // pcm_reader.cc:45-220: strict 44-byte-header RIFF/WAVE PCM, mono, 16 kHz, 8/16/32-bit,

@@ -249,7 +249,9 @@ struct RecognizerFiles {
   pk_mi355_fst_t *fst = nullptr;
   pk_mi355_symtab_t *symtab = nullptr;
 };
-int LoadRecognizerFiles(const char *config_path, RecognizerFiles *out);   // on failure the caller still frees *out
+// on failure the caller still frees *out.  any_stats: a cmvn_stats vector of any length up to kMaxCmvnStats (the spec'd loads)
+int LoadRecognizerFiles(const char *config_path, RecognizerFiles *out, bool any_stats = false);
+constexpr int kMaxCmvnStats = 129;   // the widest front-end spec (128 features) and the count
 void FreeRecognizerFiles(RecognizerFiles *f);
 // The words' strings joined by one space (pocketkaldi.cc:232-238); PK_MI355_E_INVALID for a word without a name.
 int JoinWords(const pk_mi355_symtab_t *symtab, const int *words, int count, std::string *text);

@@ -30,6 +30,9 @@ struct StreamRec {
   int64_t new_off;     // first pushed sample in the upload staging
   int64_t raw_base;    // first row of the slot's new frames in the step's raw rows
   int64_t col_base;    // first column of the slot's region of Yt
+  int64_t row_off;     // StreamCmvnChainKernel, StreamFeatureLayoutKernel: the first float of the slot's fresh rows [m][D] in the
+                       // upload staging -- new_off for a feature slot; for an audio slot of a front-end spec at D != 40
+                       //  the rows FbankAnyKernel wrote into the staging's row area, behind the samples
 };
 
 // launchers (stream.hip): one workgroup (StreamAssembleKernel) / one wavefront (StreamCmvnKernel) for each of n records
@@ -40,7 +43,7 @@ void LaunchStreamCmvn(const StreamRec *recs, int n, float *rows, const float *g,
 // launchers (stream.hip), feature slots.  LaunchStreamRawRows: one workgroup for each of n records; those of kind
 // PK_MI355_FEATS_RAW have their m pushed rows copied from the upload staging to rows + 40 raw_base, where FbankKernel
 // would have written them.  LaunchStreamFeatureLayout: (tiles of 64 columns) x (n records, all NORMALIZED): the slot's
-// region of Yt[dim][ldy] as StreamCmvnKernel defines it, frame f from the new frames (f >= n_old) or from the slot's
+// region of Yt[dim][ldy] as StreamCmvnKernel defines it, frame f from the new frames (f >= n_old, at row_off) or from the slot's
 // history hist[slot][hist_par][f % hist_len][dim]; the other history buffer receives frames [max(n - hist_len, 0), n).
 // max_cols: the widest region.  The caller has checked every base and count against the buffers.
 void LaunchStreamRawRows(const StreamRec *recs, int n, const float *upload, float *rows, hipStream_t stream);
@@ -58,8 +61,8 @@ void LaunchFeatureLayout(const float *feats, const UttLayout &utts, int num_utts
 // wavefront per (utterance or record, block of 64 features); g: dim sums (the count lives in tab).
 // LaunchCmvnChain (features.hip): raw rows [sum T][dim] -> normalised rows `out` of the same shape (never in place:
 // frame t - 600 is read raw), utterance u's rows from raw_base[u] on; LaunchFeatureLayout then lays `out` out.
-// LaunchStreamCmvnChain (stream.hip): the RAW records among the n given have their m pushed rows, [m][dim] at new_off of
-// the upload staging, normalised in place; sums[slot][dim] and raw_hist[slot][600][dim] carry the slot from step to step.
+// LaunchStreamCmvnChain (stream.hip): the RAW and the audio records among the n given have their m fresh rows, [m][dim] at
+// row_off of the upload staging, normalised in place; sums[slot][dim] and raw_hist[slot][600][dim] carry the slot from step to step.
 // The caller has checked every base and count against the buffers.
 void LaunchCmvnChain(const float *raw, const UttLayout &utts, int num_utts, int dim, const float *d_global, const CmvnTables *d_cmvn_tab,
                      float *out, hipStream_t stream);

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kSflThreads) void StreamFeatureLayoutKernel(const S
   for (int k = blockIdx.y; k < num_recs; k += gridDim.y) {
     const StreamRec r = recs[k];
     const int n = r.n_old + r.m;
-    const uint32_t *fresh = upload + r.new_off;                                            // frames n_old .. n - 1, [m][D]
+    const uint32_t *fresh = upload + r.row_off;                                            // frames n_old .. n - 1, [m][D]
     const uint32_t *old = hist + ((int64_t)r.slot * 2 + r.hist_par) * hist_len * D;        // frames below n_old
     if (blockIdx.x == 0 && r.m > 0) {
       uint32_t *next = hist + ((int64_t)r.slot * 2 + (r.hist_par ^ 1)) * hist_len * D;
@@ -185,9 +185,10 @@ __global__ __launch_bounds__(kSflThreads) void StreamFeatureLayoutKernel(const S
 }
 
 // RAW slots at a feature dimension other than 40: StreamCmvnKernel's chain with any number of
-// lanes.  One wavefront per (record, block of 64 features), lane = feature; records that are not RAW or brought no
-// frames return at once.  The slot's m pushed rows are normalised IN PLACE where they lie in the upload staging
-// ([m][D] at new_off): the raw values the window needs later are kept in the slot's ring raw_hist[slot][600][D], the
+// lanes.  One wavefront per (record, block of 64 features), lane = feature; NORMALIZED records and records that brought no
+// frames return at once.  RAW records bring pushed rows, audio records of a front-end spec the
+// rows FbankAnyKernel has just written.  The slot's m fresh rows are normalised IN PLACE where they lie in the upload
+// staging ([m][D] at row_off): the raw values the window needs later are kept in the slot's ring raw_hist[slot][600][D], the
 // running sums in sums[slot][D], exactly as StreamCmvnKernel keeps them at 40.  StreamFeatureLayoutKernel then lays the
 // record out as it does a NORMALIZED one.  A lane owns its feature's column of the rows, the ring and the sums, so
 // no two lanes (and no two waves) touch one address.  Frames are taken kSChainAhead at a time, the next group's loads
@@ -199,11 +200,11 @@ __global__ __launch_bounds__(kWave) void StreamCmvnChainKernel(const StreamRec *
                                                                const float *__restrict__ g, const CmvnTables *__restrict__ tab,
                                                                float *__restrict__ sums, float *raw_hist) {
   const StreamRec r = recs[blockIdx.x];
-  if (r.kind != PK_MI355_FEATS_RAW || r.m <= 0) return;
+  if (r.kind == PK_MI355_FEATS_NORMALIZED || r.m <= 0) return;
   const int d0 = blockIdx.y * kWave;
   const bool live = d0 + (int)threadIdx.x < D;
   const int d = live ? d0 + threadIdx.x : d0;
-  float *x = upload + r.new_off + d;
+  float *x = upload + r.row_off + d;
   float *rh = raw_hist + (int64_t)r.slot * kCmvnWindow * D + d;
   const int m = r.m;
   auto row = [&](int i) { return (int64_t)(i < m ? i : m - 1) * D; };

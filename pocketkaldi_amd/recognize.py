@@ -1,6 +1,7 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
+                                        [--frontend key=value,...]
                                         [--online [--chunk-ms N] [--partials] [--commit]
                                          [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
     python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...>
@@ -25,6 +26,12 @@ for the splice.  --ctm works as it does for audio.  With --online every utteranc
 OnlineRecognizer.open_features / push_features, max(1, chunk-ms // 10) frames per step, and --partials, --commit,
 --endpoint-silence and --endpoint-rule work as they do for audio, at 10 ms per frame; stdout is what it is without
 --online, and what --online prints for the audio the features came from.
+
+--frontend key=value,... takes a model of another front-end than the reference's (pk.FrontendSpec),
+for example kind=mfcc,num_mel_bins=23,num_ceps=13,window=povey,low_freq=20,high_freq=-400,cepstral_lifter=22.  The keys
+are FrontendSpec's field names, omitted keys take its defaults; an unknown key or a value that does not parse is refused
+with the key named and the usage text.  The model file's cmvn_stats then has the spec's dimension + 1 entries, and
+--features matrices are [T][dimension].  It combines with every other flag; without it nothing changes.
 
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
@@ -51,6 +58,7 @@ RESERVE = 32
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
+          "[--frontend key=value,...] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
           "--features raw|normalized [--ctm] [--reference-softmax] [--online ...]")
@@ -63,7 +71,7 @@ def usage():
 
 
 def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, endpoint=None,
-                     pieces=None):
+                     pieces=None, frontend=None):
     """Every wave through a slot of an OnlineRecognizer, `chunk_ms` milliseconds per step, MAX_UTTS waves at a time.
     endpoint: (silence pdfs, rules or None) turns endpointing on; pieces[u] is then wave u's list of Utterance.
     -> (the results in order, the symbol names by word id)"""
@@ -71,7 +79,7 @@ def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, part
     # a step's capacity counts 16 kHz samples; a converted slot also counts the few a close would add (RESERVE)
     reserve = RESERVE if any(r != 16000 for r in rates) else 0
     rec = pk.OnlineRecognizer(model_file, max_streams=min(max(len(waves), 1), MAX_UTTS),
-                              max_step_samples=(16 * chunk_ms + reserve) * min(max(len(waves), 1), MAX_UTTS))
+                              max_step_samples=(16 * chunk_ms + reserve) * min(max(len(waves), 1), MAX_UTTS), frontend=frontend)
     try:
         if commit:
             rec.decoder.set_commit(True)
@@ -152,6 +160,17 @@ def main(argv):
             return usage()
         features = argv[at + 1]
         del argv[at:at + 2]
+    frontend = None
+    if "--frontend" in argv:
+        at = argv.index("--frontend")
+        try:
+            frontend = pk.parse_frontend(argv[at + 1])
+        except IndexError:
+            return usage()
+        except ValueError as e:
+            print("pocketkaldi: --frontend: %s" % e)
+            return usage()
+        del argv[at:at + 2]
     endpoint, rules = None, []
     try:
         while "--endpoint-rule" in argv:
@@ -178,7 +197,7 @@ def main(argv):
         return usage()
     try:
         if features:
-            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint)
+            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend)
         if input_file.endswith(".wav"):
             files = [input_file]
         else:
@@ -192,11 +211,11 @@ def main(argv):
         if "--online" in flags:
             results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
                                               "--partials" in flags, "--commit" in flags, rates, endpoint,
-                                              pieces if endpoint else None)
+                                              pieces if endpoint else None, frontend)
         else:
             sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
-                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)))
+                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend)
             if "--reference-softmax" in flags:
                 rec.am.set_softmax("reference")
             native = any(r != 16000 for r in rates)
@@ -258,7 +277,7 @@ def feature_groups(input_file):
             yield group
 
 
-def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint):
+def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None):
     """--features: every group of utterances through a Recognizer (process_features) or, with --online, through the
     slots of an OnlineRecognizer; the object is kept from group to group while the group fits it.  Raises what main
     reports; -> the exit code."""
@@ -275,13 +294,13 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint):
                 if rec is not None:
                     rec.destroy() if online else rec.close()
                 if online:                               # (a pushed frame counts 160 samples against the step capacity)
-                    rec = pk.OnlineRecognizer(model_file, max_streams=need[0], max_step_samples=160 * step * need[0])
+                    rec = pk.OnlineRecognizer(model_file, max_streams=need[0], max_step_samples=160 * step * need[0], frontend=frontend)
                     if "--commit" in flags:
                         rec.decoder.set_commit(True)
                     if endpoint:
                         rec.set_endpointing(*endpoint)
                 else:
-                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1])
+                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend)
                     if "--reference-softmax" in flags:
                         rec.am.set_softmax("reference")
                 held = need

@@ -41,6 +41,11 @@ leg and both feature legs of one session.
 --feat-dim D (with --features) replaces the waves by synthetic [T][D] features and model S by the tiny model at that
 dimension: raw features then take StreamCmvnChainKernel in front of the layout launch, and the
 normalized leg of the same dimension is the step without it.  profiles/cmvn_any_bench.json holds both legs at D = 80.
+
+--frontend key=value,... (pk.parse_frontend, the syntax of recognize.py's flag) feeds the same audio to an online scorer
+with that front-end and model S at the spec's dimension; the statistics are the means of the first
+stream's features at the spec, count 2500, and the check is against BatchScorer(frontend=spec).
+profiles/frontend_stream_bench.json holds those legs beside the plain audio leg.
 """
 import argparse
 import json
@@ -72,7 +77,16 @@ def main():
     ap.add_argument("--feat-dim", type=int, default=40,
                     help="with --features: synthetic features of this dimension (5 N(0, 1) + 3; raw: statistics of count 2500, "
                          "StreamCmvnChainKernel's path, DESIGN.md section 15) through a small model; checked against FeatureScorer")
+    ap.add_argument("--frontend", default=None, help="a front-end spec, key=value,... (audio streams; model S at its dimension)")
     a = ap.parse_args()
+    spec = None
+    if a.frontend is not None:
+        if a.features or a.feat_dim != 40:
+            ap.error("--frontend takes audio streams")
+        try:
+            spec = pk.parse_frontend(a.frontend)
+        except ValueError as e:
+            ap.error(str(e))
     if a.feat_dim != 40 and (a.features is None or a.decode or a.commit or a.endpoint):
         ap.error("--feat-dim takes --features and no decoder")
     a.decode = a.decode or a.commit or a.endpoint
@@ -86,7 +100,15 @@ def main():
     nsteps = (len(waves[0]) + chunk - 1) // chunk
     feats = None
     model_name = "S (440 -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax"
-    if a.feat_dim != 40:
+    if spec is not None:
+        D = spec.dim
+        layers, prior, L, R = synth.model("S", feat_dim=D)
+        am = pk.AcousticModel(layers, prior, L, R)
+        model_name = "S at feat_dim %d (%d -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax; front-end %r" % (D, 11 * D, spec)
+        fb = pk.Frontend(spec).compute(waves[0])
+        g = np.concatenate([fb.astype(np.float64).mean(axis=0) * 2500.0, [2500.0]]).astype(np.float32)
+        sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk, frontend=spec)
+    elif a.feat_dim != 40:
         D = a.feat_dim
         layers, prior, L, R = synth.model("tiny", feat_dim=D)
         am = pk.AcousticModel(layers, prior, L, R)
@@ -180,7 +202,7 @@ def main():
         bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g)
         bs.set_features(feats[:1], a.features)
     else:
-        bs = pk.BatchScorer(am, g, 1, len(waves[0]))
+        bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec)
         bs.set_waves(waves[:1])
     bs.score(0.1)
     ok = np.concatenate(rows0).tobytes() == bs.fetch(0).log_prob().tobytes()
