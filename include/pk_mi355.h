@@ -358,8 +358,8 @@ pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const 
  * both kinds, capacity: the frames its sample capacity can produce, max_total_samples / 160 + max_utts); a later
  * set_waves* switches such a batch back to audio.  PK_MI355_E_INVALID, before anything is copied or launched: a null
  * argument, nrow != feat_dim, a negative ncol, an unknown kind, RAW on a batch without statistics (with feat_dim != 40
- * only pk_mi355_features_batch_create_stats gives it some), more utterances, frames or columns than the capacity; the
- * batch keeps what it held.                                                                                       */
+ * only pk_mi355_features_batch_create_stats gives it some) whose normalisation spec is the sliding rule
+ * (pk_mi355_norm_set), more utterances, frames or columns than the capacity; the batch keeps what it held.           */
 int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num_utts, int kind);
 /* Same, features already in HBM, utterance after utterance, [sum T][feat_dim] (4-byte aligned).  NORMALIZED: not
  * copied, must stay valid until scored.  RAW: one device-to-device copy on the batch's stream.                   */
@@ -425,6 +425,55 @@ pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi3
                                                  const float *global_stats, int stats_len, int max_utts,
                                                  int64_t max_total_samples);
 
+/* ---- Normalisation at a specification: what Kaldi's apply-cmvn does per utterance or per
+ * speaker, with or without variance, or nothing -- instead of cmvn.cc's sliding rule -- between the front-end (or the
+ * caller's raw features) and the first layer of a batch scorer.                                                    */
+#define PK_MI355_NORM_SLIDING   0   /* cmvn.cc's rule (the default; what every scorer did before): means only */
+#define PK_MI355_NORM_NONE      1   /* the raw rows go to the first layer as they are; both switches are ignored */
+#define PK_MI355_NORM_UTTERANCE 2   /* statistics of the utterance's own frames */
+#define PK_MI355_NORM_SPEAKER   3   /* statistics the caller hands over (pk_mi355_norm_set_speaker_stats) */
+typedef struct pk_mi355_norm_spec {
+  int32_t mode;         /* PK_MI355_NORM_* */
+  int32_t norm_means;   /* 0 or 1 (SLIDING: must be 1) */
+  int32_t norm_vars;    /* 0 or 1 (SLIDING: must be 0) */
+} pk_mi355_norm_spec_t;
+/* Statistics of one utterance or speaker at dimension D are 2 x (D + 1) doubles, the matrix compute-cmvn-stats writes:
+ * row 0 the D sums and then the frame count, row 1 the D sums of squares and then 0.
+ *
+ * The rule, every column d on its own.  UTTERANCE, T frames: S0 = S1 = 0.0; for t ascending: S0 += (double)x[t][d],
+ * S1 += (double)x[t][d] * (double)x[t][d]; N = T.  SPEAKER: S0, S1, N are the caller's.  Then, in double:
+ * mean = norm_means ? S0 / N : 0; without norm_vars scale = 1, offset = -mean; with it var = S1 / N - mean * mean,
+ * raised to 1e-20 where it is below (a NaN stays), scale = 1 / sqrt(var), offset = -(mean * scale).  Both are rounded
+ * to float once, and y = norm_vars ? (x * scale) + offset : x + offset in float, a rounded product and a rounded add
+ * (Kaldi's AccCmvnStats and ApplyCmvn).  An utterance without frames does nothing; one frame with norm_vars meets the
+ * floor; a NaN makes its own column of its own utterance NaN and touches nothing else.  The statistics an UTTERANCE
+ * call computes are compute-cmvn-stats' bits, and the sum of several utterances' records is a valid speaker record.
+ *
+ * pk_mi355_norm_check: PK_MI355_E_INVALID with a text that names the field -- a null spec, an unknown mode, a switch
+ * that is neither 0 nor 1 (any mode but NONE), SLIDING with norm_means = 0 or norm_vars = 1, UTTERANCE or SPEAKER with
+ * both switches 0 ("use mode none").  Host only.                                                                  */
+int pk_mi355_norm_check(const pk_mi355_norm_spec_t *spec);
+/* The rule on the host, for one matrix x [T][D] -> y [T][D] (not in place): the restatement the GPU path is held to.
+ * stats: the 2 x (D + 1) record of SPEAKER mode (required there, ignored otherwise).  stats_out (may be NULL): the
+ * record an UTTERANCE call accumulated.  SLIDING is refused: pk_mi355_cmvn_apply is that rule.  A count that is not
+ * positive and finite: PK_MI355_E_INVALID.                                                                        */
+int pk_mi355_norm_apply(const pk_mi355_norm_spec_t *spec, const float *x, int num_frames, int dim, const double *stats,
+                        float *y, double *stats_out);
+/* The spec of a batch scorer of any kind (pk_mi355_batch_create, pk_mi355_features_batch_create*,
+ * pk_mi355_frontend_batch_create); it holds until it is set again and takes effect at the next score call.  With a
+ * mode other than SLIDING a features-only batch made without statistics takes PK_MI355_FEATS_RAW.  With SLIDING the
+ * batch launches what it always launched.  NormKernel and FeatureLayoutKernel share the PK_MI355_K_CMVN timing slot.
+ * (Named with a prefix of their own, as the feature entries are: batch entries with another normalisation.)        */
+int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec);
+/* SPEAKER mode: [num_utts][2][feat_dim + 1] doubles, utterance u's speaker record at stats + u * 2 * (feat_dim + 1).
+ * They belong to the NEXT score call and are consumed by it.  PK_MI355_E_INVALID, naming the utterance, for a count
+ * that is not positive and finite -- here, before any launch.  pk_mi355_batch_score in SPEAKER mode without records,
+ * or with records for another number of utterances than the call's: PK_MI355_E_STATE.                            */
+int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, int num_utts);
+/* The 2 x (feat_dim + 1) record the last score call computed for utterance utt in UTTERANCE mode;
+ * PK_MI355_E_STATE when the last score was not one in that mode.                                                   */
+int pk_mi355_norm_fetch_stats(pk_mi355_batch_t *b, int utt, double *out);
+
 /* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
  * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
  * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is
@@ -444,6 +493,10 @@ int pk_mi355_ark_next(pk_mi355_ark_t *h);
  * frames, memory [frames][dim] -- the image pk_mi355_features_set takes.  Both are valid until the next call on h.  */
 const char *pk_mi355_ark_key(const pk_mi355_ark_t *h);
 int pk_mi355_ark_matrix(const pk_mi355_ark_t *h, pk_matrix_t *view);
+/* The current entry's values as doubles, before the narrowing, [rows][cols] into out (capacity: doubles it holds) -> the
+ * number written.  Kept for matrices of at most two rows: CMVN statistics records (compute-cmvn-stats writes doubles,
+ * and a variance is the difference of two of its quotients).  PK_MI355_E_INVALID: more rows, or a buffer too small.  */
+int pk_mi355_ark_matrix_f64(const pk_mi355_ark_t *h, double *out, int capacity);
 void pk_mi355_ark_close(pk_mi355_ark_t *h);
 /* One keyless object from "path" or "path:offset" (a global CMVN statistics file, say): a handle whose current entry
  * is that object (pk_mi355_ark_matrix; pk_mi355_ark_next gives 0), to be closed as any other.  NULL on failure.     */

@@ -471,6 +471,24 @@ class Frontend {
   Status status_;
 };
 
+// A normalisation specification (pk_mi355_norm_spec_t): the sliding rule (the default), none, or
+// Kaldi's apply-cmvn per utterance or per speaker, with or without variance.  Nothing is checked here: the library
+// refuses a bad spec wherever one is used.
+struct NormSpec : pk_mi355_norm_spec_t {
+  NormSpec() { mode = PK_MI355_NORM_SLIDING; norm_means = 1; norm_vars = 0; }
+  static NormSpec None() { NormSpec s; s.mode = PK_MI355_NORM_NONE; return s; }
+  static NormSpec Utterance(bool means = true, bool vars = false) { return Make(PK_MI355_NORM_UTTERANCE, means, vars); }
+  static NormSpec Speaker(bool means = true, bool vars = false) { return Make(PK_MI355_NORM_SPEAKER, means, vars); }
+  Status Check() const { return Status::FromLast(pk_mi355_norm_check(this)); }
+
+ private:
+  static NormSpec Make(int mode, bool means, bool vars) {
+    NormSpec s;
+    s.mode = mode; s.norm_means = means ? 1 : 0; s.norm_vars = vars ? 1 : 0;
+    return s;
+  }
+};
+
 // The batched, device-resident scorer (pk_mi355_batch_*): PCM of many utterances -> log-likelihood rows.
 class BatchScorer {
  public:
@@ -501,6 +519,17 @@ class BatchScorer {
   Status Fetch(int utt, pk_decodable_t *out) { return Status::FromLast(pk_mi355_batch_fetch(b_, utt, out)); }
   // the front-end's rows, [T][FeatDim()] floats
   Status FetchFeatures(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_fbank(b_, utt, out)); }
+  // what the first layer reads, [T][FeatDim()] floats
+  Status FetchNormalized(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_cmvn(b_, utt, out)); }
+  // The normalisation between the front-end and the first layer; it holds until it is set again.
+  Status SetNorm(const NormSpec &spec) { return Status::FromLast(pk_mi355_norm_set(b_, &spec)); }
+  // mode speaker: [num_utts][2][FeatDim() + 1] doubles, consumed by the next Score
+  Status SetSpeakerStats(const double *stats, int num_utts) { return Status::FromLast(pk_mi355_norm_set_speaker_stats(b_, stats, num_utts)); }
+  // the 2 x (FeatDim() + 1) record the last Score computed for utterance utt in mode utterance
+  Status NormStats(int utt, std::vector<double> *out) {
+    out->assign(2 * (static_cast<size_t>(FeatDim()) + 1), 0.0);
+    return Status::FromLast(pk_mi355_norm_fetch_stats(b_, utt, out->data()));
+  }
 
   const Status &last_status() const { return status_; }
   pk_mi355_batch_t *handle() const { return b_; }

@@ -30,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "parse_norm", "cmvn_normalize", "kaldi_cmvn_stats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -80,6 +80,10 @@ _lib = None
 class pk_mi355_frontend_spec_t(C.Structure):     # a front-end specification (include/pk_mi355.h)
     _fields_ = [("kind", C.c_int32), ("num_mel_bins", C.c_int32), ("num_ceps", C.c_int32), ("window", C.c_int32),
                 ("low_freq", C.c_float), ("high_freq", C.c_float), ("cepstral_lifter", C.c_float)]
+
+
+class pk_mi355_norm_spec_t(C.Structure):         # a normalisation specification (include/pk_mi355.h)
+    _fields_ = [("mode", C.c_int32), ("norm_means", C.c_int32), ("norm_vars", C.c_int32)]
 
 
 EXPORTS = [
@@ -145,6 +149,8 @@ EXPORTS = [
     "pk_mi355_frontend_check", "pk_mi355_frontend_dim", "pk_mi355_frontend_default", "pk_mi355_frontend_tables",
     "pk_mi355_frontend_compute", "pk_mi355_frontend_batch_create",
     "pk_mi355_frontend_stream_create", "pk_mi355_load_stats", "pk_mi355_frontend_recognizer_load", "pk_mi355_frontend_online_recognizer_load",
+    "pk_mi355_norm_check", "pk_mi355_norm_apply", "pk_mi355_norm_set", "pk_mi355_norm_set_speaker_stats", "pk_mi355_norm_fetch_stats",
+    "pk_mi355_ark_matrix_f64",
 ]
 
 
@@ -423,6 +429,13 @@ def lib():
     L.pk_mi355_frontend_recognizer_load.argtypes = [C.c_char_p, specp, C.c_int, C.c_int, C.c_int64, C.c_int64]
     L.pk_mi355_frontend_online_recognizer_load.restype = C.c_void_p
     L.pk_mi355_frontend_online_recognizer_load.argtypes = [C.c_char_p, specp, C.c_int, C.c_int64, C.c_int64]
+    normp, f64p = C.POINTER(pk_mi355_norm_spec_t), C.POINTER(C.c_double)
+    L.pk_mi355_norm_check.argtypes = [normp]
+    L.pk_mi355_norm_apply.argtypes = [normp, f32p, C.c_int, C.c_int, f64p, f32p, f64p]
+    L.pk_mi355_norm_set.argtypes = [C.c_void_p, normp]
+    L.pk_mi355_norm_set_speaker_stats.argtypes = [C.c_void_p, f64p, C.c_int]
+    L.pk_mi355_norm_fetch_stats.argtypes = [C.c_void_p, C.c_int, f64p]
+    L.pk_mi355_ark_matrix_f64.argtypes = [C.c_void_p, f64p, C.c_int]
     _lib = L
     return L
 
@@ -655,6 +668,82 @@ class Frontend:
         m = pk_matrix_t(0, 0, None)
         _check_code(lib().pk_mi355_frontend_compute(C.byref(self.spec.struct()), C.byref(v), C.byref(m)))
         return _take_matrix(m)
+
+
+NORM_MODES = {"sliding": 0, "none": 1, "utterance": 2, "speaker": 3}      # PK_MI355_NORM_*
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+class NormSpec:
+    """A normalisation specification (pk_mi355_norm_spec_t): mode "sliding" (cmvn.cc's rule, the default), "none",
+    "utterance" or "speaker" (Kaldi's apply-cmvn on the utterance's own or on the caller's statistics), and the two
+    switches.  mode also takes the header's integer; nothing is checked here: the library refuses a bad spec
+    (PkCodeError, the field named) wherever one is used."""
+
+    def __init__(self, mode="sliding", norm_means=True, norm_vars=False):
+        self.mode = NORM_MODES.get(mode, mode)
+        self.norm_means, self.norm_vars = norm_means, norm_vars
+
+    def struct(self):
+        try:
+            return pk_mi355_norm_spec_t(int(self.mode), int(self.norm_means), int(self.norm_vars))
+        except (TypeError, ValueError) as e:
+            raise PkCodeError(-1, "norm spec: %s" % e)
+
+    def check(self):
+        _check_code(lib().pk_mi355_norm_check(C.byref(self.struct())))
+
+    def __repr__(self):
+        return "NormSpec(mode=%r, norm_means=%r, norm_vars=%r)" % (self.mode, self.norm_means, self.norm_vars)
+
+
+def parse_norm(text):
+    """A NormSpec from "key=value,key=value,...": mode (sliding | none | utterance | speaker), norm_means and norm_vars
+    (true | false | 1 | 0); omitted keys take NormSpec's defaults.  ValueError, the key named, for an unknown key or a
+    value that does not parse.  Nothing else is checked here: the library refuses a bad spec where it is used."""
+    switch = {"true": True, "false": False, "1": True, "0": False}
+    fields = {"mode": NORM_MODES, "norm_means": switch, "norm_vars": switch}
+    given = {}
+    for item in [t.strip() for t in text.split(",") if t.strip()]:
+        key, eq, value = item.partition("=")
+        key, value = key.strip(), value.strip()
+        if key not in fields:
+            raise ValueError("norm spec: unknown key '%s' (the keys are %s)" % (key, ", ".join(sorted(fields))))
+        if key in given:
+            raise ValueError("norm spec: key '%s' given twice" % key)
+        if not eq or value not in fields[key]:
+            raise ValueError("norm spec: bad value '%s' for key '%s' (one of %s)" % (value, key, ", ".join(sorted(fields[key]))))
+        given[key] = fields[key][value]
+    return NormSpec(**given)
+
+
+def _stats_records(stats, n, dim):
+    """n records of 2 x (dim + 1) doubles -> one float64 array [n][2][dim + 1]; another shape is refused here."""
+    try:
+        a = np.ascontiguousarray(stats, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise PkCodeError(-1, "speaker statistics are not numbers: %s" % e)
+    if a.shape != (n, 2, dim + 1):
+        raise PkCodeError(-1, "speaker statistics have shape %s, expected [%d][2][%d]" % (a.shape, n, dim + 1))
+    return a
+
+
+def cmvn_normalize(feats, spec, stats=None):
+    """The rule of a NormSpec on the host for one [T][D] matrix (pk_mi355_norm_apply: the restatement the GPU path is
+    held to) -> (normalised float32 [T][D], the 2 x (D + 1) float64 record an "utterance" call accumulated, else None).
+    stats: the 2 x (D + 1) record of mode "speaker".  Mode "sliding" is CMVN's rule and refused here."""
+    x = _f32(feats)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise PkCodeError(-1, "features have shape %s, expected [T][D]" % (x.shape,))
+    T, D = x.shape
+    st = spec.struct()
+    rec = None if stats is None else _stats_records([stats], 1, D)
+    y, acc = np.zeros((T, D), np.float32), np.zeros((2, D + 1), np.float64)
+    _check_code(lib().pk_mi355_norm_apply(C.byref(st), _fp(x), T, D, None if rec is None else _dp(rec), _fp(y), _dp(acc)))
+    return y, (acc if st.mode == NORM_MODES["utterance"] else None)
 
 
 class CMVN:
@@ -1006,8 +1095,9 @@ class BatchScorer:
 
     def set_features(self, feats, kind="normalized"):
         """Features instead of audio: one [T][feat_dim] matrix per utterance.  kind "normalized": ready for the splice
-        (what Decodable takes); "raw": features the sliding-window CMVN is applied to first (40-dim log-mel fbank, or
-        the model's own dimension on a FeatureScorer made with feat_dim + 1 statistics)."""
+        (what Decodable takes); "raw": features the scorer's normalisation is applied to first -- the sliding-window CMVN
+        (40-dim log-mel fbank, or the model's own dimension on a FeatureScorer made with feat_dim + 1 statistics) or
+        what set_norm selected (any scorer, statistics or not)."""
         arr, keep = _feature_matrices(feats, self.feat_dim())
         _check_code(lib().pk_mi355_features_set(self._h, arr, len(keep), _feature_kind(kind)))
 
@@ -1066,6 +1156,23 @@ class BatchScorer:
         """What the first layer reads, [T][feat_dim]."""
         out = np.zeros((self.num_frames(utt), self.feat_dim()), dtype=np.float32)
         _check_code(lib().pk_mi355_batch_fetch_cmvn(self._h, utt, _fp(out)))
+        return out
+
+    def set_norm(self, spec):
+        """The normalisation between the front-end (or raw features) and the first layer: a NormSpec.  It holds until it
+        is set again.  Anything but "sliding" also lets a FeatureScorer made without statistics take kind "raw"."""
+        _check_code(lib().pk_mi355_norm_set(self._h, C.byref(spec.struct())))
+
+    def set_speaker_stats(self, stats):
+        """Mode "speaker": one 2 x (feat_dim + 1) record per utterance of the next score call, which consumes them."""
+        n = len(stats)
+        a = _stats_records(stats, n, self.feat_dim())
+        _check_code(lib().pk_mi355_norm_set_speaker_stats(self._h, _dp(a) if n else None, n))
+
+    def norm_stats(self, utt):
+        """The 2 x (feat_dim + 1) float64 record the last score call computed for utterance utt in mode "utterance"."""
+        out = np.zeros((2, self.feat_dim() + 1), np.float64)
+        _check_code(lib().pk_mi355_norm_fetch_stats(self._h, utt, _dp(out)))
         return out
 
     def gather_loglik(self, utt, d_frames, d_trans_ids, n, d_out):
@@ -1313,6 +1420,43 @@ def kaldi_global_stats(rx):
     if m.shape[0] != 2 or m.shape[1] < 2:
         raise PkCodeError(-1, "%s holds a %d x %d matrix; global CMVN statistics are 2 x (D + 1)" % (rx, m.shape[0], m.shape[1]))
     return np.ascontiguousarray(m[0])
+
+
+def _ark_stats(handle, what):
+    """The current entry of a reader as a 2 x (D + 1) float64 statistics record (pk_mi355_ark_matrix_f64)."""
+    m = pk_matrix_t()
+    _check_code(lib().pk_mi355_ark_matrix(handle, C.byref(m)))
+    if m.ncol != 2 or m.nrow < 2:
+        raise PkCodeError(-1, "%s holds a %d x %d matrix; CMVN statistics are 2 x (D + 1)" % (what, m.ncol, m.nrow))
+    out = np.zeros((2, m.nrow), np.float64)
+    _check_code(lib().pk_mi355_ark_matrix_f64(handle, _dp(out), out.size))
+    return out
+
+
+def kaldi_cmvn_stats(rx):
+    """A CMVN statistics file (compute-cmvn-stats' 2 x (D + 1) matrix) from "path" or "path:offset" -> float64
+    [2][D + 1], the doubles as the file holds them: what set_speaker_stats and cmvn_normalize take."""
+    h = lib().pk_mi355_ark_read_object(os.fspath(rx).encode())
+    if not h:
+        raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode(errors="replace"))
+    try:
+        return _ark_stats(h, rx)
+    finally:
+        lib().pk_mi355_ark_close(h)
+
+
+def read_cmvn_stats_archive(spec):
+    """An archive or script file of CMVN statistics ("ark:", "scp:" or a path, as ArkReader) -> {key: float64 [2][D + 1]}."""
+    out = {}
+    with ArkReader(spec) as r:
+        while True:
+            rc = lib().pk_mi355_ark_next(r._h)
+            if rc < 0:
+                raise PkCodeError(rc, lib().pk_mi355_last_error().decode(errors="replace"))
+            if rc == 0:
+                return out
+            key = lib().pk_mi355_ark_key(r._h).decode(errors="surrogateescape")
+            out[key] = _ark_stats(r._h, "%s key '%s'" % (spec, key))
 
 
 class Fst:
@@ -1751,12 +1895,17 @@ class Recognizer:
                               lib().pk_mi355_recognizer_loglikelihood_per_frame(self._h, u), self.decoder.word_segments(u)))
         return out
 
-    def process_features(self, feats, kind="raw"):
+    def _speaker_stats(self, speaker_stats, n):
+        return None if speaker_stats is None else _stats_records(speaker_stats, n, self.batch.feat_dim())
+
+    def process_features(self, feats, kind="raw", speaker_stats=None):
         """pk_process from features: one [T][feat_dim] matrix per utterance (kind: as BatchScorer.set_features).  A list
         that does not fit max_utts or the frames the recognizer holds is split into as many calls as it needs; a
-        single matrix that cannot fit is refused."""
+        single matrix that cannot fit is refused.  speaker_stats: one record per utterance for a batch whose norm
+        (self.batch.set_norm) is in mode "speaker"; they are split with the list."""
         code = _feature_kind(kind)
         arr, keep = _feature_matrices(feats, self.batch.feat_dim())
+        spk = self._speaker_stats(speaker_stats, len(keep))
         cap = self.max_total_samples // 160 + self.max_utts       # the frames pk_mi355_batch_create makes room for
         for i, f in enumerate(keep):
             if f.shape[0] > cap:
@@ -1766,6 +1915,8 @@ class Recognizer:
             if i == len(keep) or i - first == self.max_utts or frames + keep[i].shape[0] > cap:
                 if i > first:
                     sub = (pk_matrix_t * (i - first))(*[arr[j] for j in range(first, i)])
+                    if spk is not None:
+                        self.batch.set_speaker_stats(spk[first:i])
                     _check_code(lib().pk_mi355_recognizer_process_features(self._h, sub, i - first, code))
                     out += self._results(i - first)
                 first, frames = i, 0
@@ -1773,11 +1924,13 @@ class Recognizer:
                 frames += keep[i].shape[0]
         return out
 
-    def process(self, waves, rates=None):
+    def process(self, waves, rates=None, speaker_stats=None):
         """pk_process for every wave (float sample values as read_wav gives them; rates: the sample rate of every wave,
         None for 16000 -- the others are converted on the GPU).  A list that does not fit max_utts / max_total_samples
-        (counted at 16 kHz) is split into as many calls as it needs; a single wave that cannot fit is refused."""
+        (counted at 16 kHz) is split into as many calls as it needs; a single wave that cannot fit is refused.
+        speaker_stats: as process_features."""
         waves = [_f32(w).ravel() for w in waves]
+        spk = self._speaker_stats(speaker_stats, len(waves))
         if rates is None:
             sizes = [w.shape[0] for w in waves]
         else:
@@ -1790,6 +1943,8 @@ class Recognizer:
 
         def flush():
             first = len(out)
+            if spk is not None:
+                self.batch.set_speaker_stats(spk[first:first + len(call)])
             return self._process_call(call, None if rates is None else rates[first:first + len(call)])
         for w, n in zip(waves, sizes):
             if call and (len(call) == self.max_utts or samples + n > self.max_total_samples):

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pk_frontend.h"
+#include "pk_norm_kernel.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -188,6 +189,13 @@ struct pk_mi355_batch {
   // stages
   float *d_raw_alloc = nullptr;
   float *d_raw = nullptr;   // [max_frames][40], kCmvnRawLead floats into d_raw_alloc
+  // The normalisation spec (pk_mi355_norm_set).  Anything but SLIDING: NormKernel (or, for NONE,
+  // nothing) stands in front of FeatureLayoutKernel, from d_raw into d_feats; the buffers below are made by norm_set.
+  pk_mi355_norm_spec_t norm{PK_MI355_NORM_SLIDING, 1, 0};
+  double *d_norm_stats = nullptr;   // [max_utts][2][feat_dim + 1]: the records an UTTERANCE-mode score writes
+  float *d_spk_table = nullptr;     // [max_utts][2][feat_dim]: offsets and scales of the speaker records handed over
+  int spk_utts = -1;                // the utterances the pending speaker records are for (-1: none pending)
+  bool norm_stats_valid = false;    // the last score call was one in UTTERANCE mode on raw rows or audio
   _Float16 *d_y2 = nullptr;   // f16x3: interleaved (hi, lo) rows [ldy][2 feat_dim]
   float *h_ll = nullptr;    // page-locked mirror of d_ll (pk_mi355_batch_fetch_all), made on first use
   ArenaRec *arena = nullptr;  // its shared-ownership record
@@ -312,7 +320,7 @@ int CheckFeatureKind(const pk_mi355_batch *b, int kind) {
   if (kind != PK_MI355_FEATS_NORMALIZED && kind != PK_MI355_FEATS_RAW) return Fail(PK_MI355_E_INVALID, "unknown feature kind %d", kind);
   // (statistics are only ever held at the model's own dimension: 41 floats through the 40-dim entries, feat_dim + 1
   // through pk_mi355_features_batch_create_stats)
-  if (kind == PK_MI355_FEATS_RAW && !b->have_stats) {
+  if (kind == PK_MI355_FEATS_RAW && !b->have_stats && b->norm.mode == PK_MI355_NORM_SLIDING) {
     if (b->core.am->feat_dim == kNumBins)
       return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics and a %d-dim model (this batch: no statistics, %d-dim)", kNumBins,
                   kNumBins);
@@ -333,6 +341,14 @@ int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts)
 int EnsureFeatsStaging(pk_mi355_batch *b) {
   if (b->d_feats) return 0;
   HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * b->core.am->feat_dim));
+  return 0;
+}
+// A features-only batch made without statistics has no raw rows until a normalisation spec other than SLIDING lets it
+// take RAW features: [max_frames][feat_dim], read by NormKernel and FeatureLayoutKernel within an utterance's own rows.
+int EnsureRawRows(pk_mi355_batch *b) {
+  if (b->d_raw) return 0;
+  HIP_TRY(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)b->core.max_frames * b->core.am->feat_dim));
+  b->d_raw = b->d_raw_alloc;
   return 0;
 }
 int WaveEntryAllowed(const pk_mi355_batch *b) {
@@ -593,6 +609,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched, b->ev_layout}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats); hipFree(b->d_any);
+  hipFree(b->d_norm_stats); hipFree(b->d_spk_table);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
   hipFree(b->d_native);
@@ -714,9 +731,11 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
   if (int rc = CheckFeatureCounts(b, frames.data(), num_utts)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   // RAW: where FbankKernel would have written them; NORMALIZED: the staging FeatureLayoutKernel reads
-  float *dst = b->d_raw;
   if (kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins)
     if (int rc = EnsureFeatsStaging(b)) return rc;
+  if (kind == PK_MI355_FEATS_RAW)
+    if (int rc = EnsureRawRows(b)) return rc;
+  float *dst = b->d_raw;
   if (kind == PK_MI355_FEATS_NORMALIZED) dst = b->d_feats;
   // The layout first: its upload travels while the host stages the features below (a copy out of pageable memory
   // holds the host until it is done), and the first kernel of the score call is then queued straight behind them.
@@ -742,6 +761,7 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
     const int D = b->core.am->feat_dim;                 // (any other dimension than 40: as a host call's rows, fetch_fbank's source)
     if (D != kNumBins)
       if (int rc = EnsureFeatsStaging(b)) return rc;
+    if (int rc = EnsureRawRows(b)) return rc;
     int64_t total = 0;
     for (int u = 0; u < num_utts; ++u) total += num_frames[u];
     if (total > 0)
@@ -750,6 +770,46 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
   if (int rc = SetLayoutFrames(b, num_frames, nullptr, num_utts)) return rc;
   if (kind == PK_MI355_FEATS_NORMALIZED) b->feats = d_feats;   // read where they lie
   b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
+  return 0;
+}
+
+int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec) {
+  if (!b || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = pknorm::CheckSpec(spec)) return rc;      // (names the field)
+  if (spec->mode != PK_MI355_NORM_SLIDING) {            // what NormKernel writes and reads, made at the first spec that needs it
+    if (int rc = UseDevice(b->core.device)) return rc;
+    const size_t D = (size_t)b->core.am->feat_dim;
+    if (int rc = EnsureFeatsStaging(b)) return rc;
+    if (!b->d_norm_stats) HIP_TRY(hipMalloc(&b->d_norm_stats, sizeof(double) * 2 * (D + 1) * (size_t)b->max_utts));
+    if (!b->d_spk_table) HIP_TRY(hipMalloc(&b->d_spk_table, sizeof(float) * 2 * D * (size_t)b->max_utts));
+  }
+  b->norm = *spec;
+  b->spk_utts = -1;                                     // records finalised under another spec are not this spec's
+  return 0;
+}
+
+int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, int num_utts) {
+  if (!b || (num_utts > 0 && !stats)) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (b->norm.mode != PK_MI355_NORM_SPEAKER) return Fail(PK_MI355_E_STATE, "speaker statistics need mode speaker (pk_mi355_norm_set)");
+  if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+  const int D = b->core.am->feat_dim;
+  std::vector<float> table((size_t)std::max(num_utts, 1) * 2 * D);
+  if (int rc = pknorm::FinalizeSpeakerStats(stats, num_utts, D, b->norm.norm_means != 0, b->norm.norm_vars != 0, table.data())) return rc;
+  if (int rc = UseDevice(b->core.device)) return rc;
+  if (num_utts > 0) {                                   // (pageable memory: the copy has read the table when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_spk_table, table.data(), sizeof(float) * 2 * D * (size_t)num_utts, hipMemcpyHostToDevice, b->core.stream));
+    HIP_TRY(hipStreamSynchronize(b->core.stream));
+  }
+  b->spk_utts = num_utts;
+  return 0;
+}
+
+int pk_mi355_norm_fetch_stats(pk_mi355_batch_t *b, int utt, double *out) {
+  if (!b || !out || utt < 0 || utt >= b->num_utts) return Fail(PK_MI355_E_INVALID, "bad utterance index");
+  if (!b->scored || !b->norm_stats_valid) return Fail(PK_MI355_E_STATE, "the last score call computed no statistics (mode utterance on raw rows or audio does)");
+  const size_t rec = 2 * ((size_t)b->core.am->feat_dim + 1);
+  HIP_TRY(hipMemcpyAsync(out, b->d_norm_stats + utt * rec, sizeof(double) * rec, hipMemcpyDeviceToHost, b->core.stream));
+  HIP_TRY(hipStreamSynchronize(b->core.stream));
   return 0;
 }
 
@@ -768,9 +828,30 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   b->range_status = 0;
   b->range_msg[0] = 0;
   b->scored = false;
-  if (b->num_utts == 0 || b->total_frames == 0) { b->scored = true; return 0; }
-  const UttLayout &lay = b->lay;
+  // The normalisation of this call (raw rows or audio; normalised features pass it by).  Speaker records belong to one
+  // score call: this one consumes them, whatever becomes of it.
+  const int spk_utts = b->spk_utts;
+  b->spk_utts = -1;
+  b->norm_stats_valid = false;
   const int D = am->feat_dim;
+  const int mode = b->source == pk_mi355_batch::kNormalized ? PK_MI355_NORM_NONE : b->norm.mode;
+  if (b->source != pk_mi355_batch::kNormalized) {
+    if (mode == PK_MI355_NORM_SLIDING && !b->have_stats)
+      return Fail(PK_MI355_E_STATE, "raw features in mode sliding need the CMVN statistics: this batch was made without them");
+    if (mode == PK_MI355_NORM_SPEAKER && spk_utts < 0)
+      return Fail(PK_MI355_E_STATE, "mode speaker: no speaker statistics set for this score call (pk_mi355_norm_set_speaker_stats)");
+    if (mode == PK_MI355_NORM_SPEAKER && spk_utts != b->num_utts)
+      return Fail(PK_MI355_E_STATE, "mode speaker: statistics for %d utterances, the call has %d", spk_utts, b->num_utts);
+  }
+  if (b->num_utts == 0 || b->total_frames == 0) {
+    if (mode == PK_MI355_NORM_UTTERANCE && b->num_utts > 0) {      // records of no frames: zeros
+      HIP_TRY(hipMemsetAsync(b->d_norm_stats, 0, sizeof(double) * 2 * (D + 1) * (size_t)b->num_utts, c.stream));
+      b->norm_stats_valid = true;
+    }
+    b->scored = true;
+    return 0;
+  }
+  const UttLayout &lay = b->lay;
   if (b->source == pk_mi355_batch::kWaves) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
     if (b->d_any) LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, D, b->d_raw, c.stream);
@@ -780,7 +861,14 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);
     if (b->source == pk_mi355_batch::kNormalized)
       LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else if (D != kNumBins) {                  // raw rows at the model's own dimension: the chain, then the layout of its result
+    else if (mode == PK_MI355_NORM_NONE)      // the raw rows as they are (at D = 40: d_raw, behind CmvnKernel's lead)
+      LaunchFeatureLayout(b->d_raw, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    else if (mode != PK_MI355_NORM_SLIDING) { // NormKernel, then the layout of its result
+      LaunchNorm(b->d_raw, lay, b->num_utts, D, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats,
+                 b->d_feats, c.stream);
+      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+      b->norm_stats_valid = mode == PK_MI355_NORM_UTTERANCE;
+    } else if (D != kNumBins) {                  // raw rows at the model's own dimension: the chain, then the layout of its result
       LaunchCmvnChain(b->d_raw, lay, b->num_utts, D, c.d_global, c.d_cmvn_tab, b->d_feats, c.stream);
       LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
     } else
@@ -846,8 +934,11 @@ int pkhost::BatchCalibrateLocked(pk_mi355_batch *b) {
   pk_mi355_am *am = b->core.am;
   if (am->exps_stale) if (int rc = RefreshExps(am)) return rc;
   const ExecBufs &e = b->core.exec;
+  const int spk_utts = b->spk_utts;              // calibration passes do not consume the speaker records: the score behind them does
   return CalibrateLoop(am, e, [&]() -> int {
+    b->spk_utts = spk_utts;
     const int rc = pk_mi355_batch_score(b, 1.0f, 0);
+    b->spk_utts = spk_utts;
     b->scored = false;                           // calibration passes are not results
     b->range_pending = false;
     if (rc) return rc;

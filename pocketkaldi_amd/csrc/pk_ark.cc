@@ -11,7 +11,8 @@
 //   scp             lines "<key> <path>" or "<key> <path>:<offset>", the offset being the byte position of the object
 //                   (just past the key's space); paths are opened as given.
 // A matrix is rows = frames: its bytes are a pk_matrix_t with nrow = cols and ncol = rows as they lie; doubles are
-// narrowed with one (float) cast.  An archive is read entry by entry; every size a file states is checked in 64 bits
+// narrowed with one (float) cast; a matrix of at most kWideRows rows -- a CMVN statistics record, whose sums need their
+// doubles -- is kept as doubles too (pk_mi355_ark_matrix_f64).  An archive is read entry by entry; every size a file states is checked in 64 bits
 // against the bytes that remain in the file before anything is allocated from it.
 // PK_MI355_E_IO: what cannot be opened, is truncated or is malformed.  PK_MI355_E_INVALID: well-formed input this reader
 // does not take -- compressed matrices, vectors, scp ranges, pipes -- named in the text (an scp line by its number).
@@ -33,6 +34,7 @@ struct pk_mi355_ark {
   int failed = 0;               // the code of the failure that ended the reading
   std::string key;
   std::vector<float> data;      // the current entry, [rows][cols]
+  std::vector<double> wide;     // the same values before the narrowing, when rows <= kWideRows (otherwise empty)
   int rows = 0, cols = 0;
   bool have = false;
 };
@@ -40,6 +42,7 @@ struct pk_mi355_ark {
 namespace {
 
 constexpr size_t kMaxKey = 4096;        // a "key" longer than this is garbage, not a key
+constexpr int kWideRows = 2;            // matrices of at most this many rows are also kept as doubles
 
 int64_t Remaining(FILE *f) {            // bytes from the position to the end of the file; -1: not a seekable file
   const off_t at = ftello(f);
@@ -50,7 +53,7 @@ int64_t Remaining(FILE *f) {            // bytes from the position to the end of
 }
 
 // The binary object behind "\0B" at the position of f.  `where` names the object in the error text.
-int ReadBinaryMatrix(FILE *f, const char *where, std::vector<float> *data, int *rows, int *cols) {
+int ReadBinaryMatrix(FILE *f, const char *where, std::vector<float> *data, std::vector<double> *wide, int *rows, int *cols) {
   char tok[8];
   size_t n = 0;
   for (;;) {                                            // the token, up to and with its space
@@ -83,14 +86,19 @@ int ReadBinaryMatrix(FILE *f, const char *where, std::vector<float> *data, int *
   if (count > (uint64_t)remain / (uint64_t)width)
     return Fail(PK_MI355_E_IO, "%s: truncated: %d x %d values of %d bytes, %lld bytes remain", where, dim[0], dim[1], width, (long long)remain);
   data->resize((size_t)count);
+  const bool keep = dim[0] <= kWideRows;
+  wide->clear();
+  if (keep) wide->reserve((size_t)count);
   if (width == 4) {
     if (count && fread(data->data(), 4, (size_t)count, f) != count) return Fail(PK_MI355_E_IO, "%s: short read", where);
+    if (keep) wide->assign(data->begin(), data->end());
   } else {
     double buf[1024];
     for (uint64_t done = 0; done < count;) {
       const size_t take = (size_t)std::min<uint64_t>(1024, count - done);
       if (fread(buf, 8, take, f) != take) return Fail(PK_MI355_E_IO, "%s: short read", where);
       for (size_t i = 0; i < take; ++i) (*data)[(size_t)done + i] = (float)buf[i];
+      if (keep) wide->insert(wide->end(), buf, buf + take);
       done += take;
     }
   }
@@ -100,12 +108,13 @@ int ReadBinaryMatrix(FILE *f, const char *where, std::vector<float> *data, int *
 }
 
 // The text object at the position of f (which is past any "\0B" test): " [", rows, "]".
-int ReadTextMatrix(FILE *f, const char *where, std::vector<float> *data, int *rows, int *cols) {
+int ReadTextMatrix(FILE *f, const char *where, std::vector<float> *data, std::vector<double> *wide, int *rows, int *cols) {
   int c;
   do c = fgetc(f); while (c == ' ' || c == '\t' || c == '\n' || c == '\r');
   if (c == EOF) return Fail(PK_MI355_E_IO, "%s: truncated where an object begins", where);
   if (c != '[') return Fail(PK_MI355_E_IO, "%s: garbage where '\\0B' or '[' belongs", where);
   data->clear();
+  wide->clear();
   int nrows = 0, ncols = -1, in_row = 0;
   auto end_row = [&]() -> int {
     if (in_row == 0) return 0;
@@ -141,6 +150,8 @@ int ReadTextMatrix(FILE *f, const char *where, std::vector<float> *data, int *ro
     const double v = strtod(word.c_str(), &end);
     if (end == word.c_str() || *end != 0) return Fail(PK_MI355_E_IO, "%s: '%s' where a number belongs", where, word.c_str());
     data->push_back((float)v);
+    if (nrows < kWideRows) wide->push_back(v);
+    else if (!wide->empty()) std::vector<double>().swap(*wide);      // a third row: not a statistics record
     ++in_row;
   }
   *rows = nrows;
@@ -149,19 +160,19 @@ int ReadTextMatrix(FILE *f, const char *where, std::vector<float> *data, int *ro
 }
 
 // One object at the position of f: binary when it begins with "\0B", text otherwise.
-int ReadObject(FILE *f, const char *where, std::vector<float> *data, int *rows, int *cols) {
+int ReadObject(FILE *f, const char *where, std::vector<float> *data, std::vector<double> *wide, int *rows, int *cols) {
   const int c = fgetc(f);
   if (c == EOF) return Fail(PK_MI355_E_IO, "%s: truncated where an object begins", where);
   if (c != 0) {
     ungetc(c, f);
-    return ReadTextMatrix(f, where, data, rows, cols);
+    return ReadTextMatrix(f, where, data, wide, rows, cols);
   }
   if (fgetc(f) != 'B') return Fail(PK_MI355_E_IO, "%s: garbage where '\\0B' belongs", where);
-  return ReadBinaryMatrix(f, where, data, rows, cols);
+  return ReadBinaryMatrix(f, where, data, wide, rows, cols);
 }
 
 // "path" or "path:offset" -> the object there.  Ranges, pipes and "-" are named and refused.
-int ReadRx(const std::string &rx, const char *where, std::vector<float> *data, int *rows, int *cols) {
+int ReadRx(const std::string &rx, const char *where, std::vector<float> *data, std::vector<double> *wide, int *rows, int *cols) {
   if (rx.empty()) return Fail(PK_MI355_E_IO, "%s: no file name", where);
   if (rx == "-" || rx.back() == '|' || rx.front() == '|')
     return Fail(PK_MI355_E_INVALID, "%s: '%s' is a pipe or the standard input; this reader opens files", where, rx.c_str());
@@ -181,7 +192,7 @@ int ReadRx(const std::string &rx, const char *where, std::vector<float> *data, i
   if (size < 0) rc = Fail(PK_MI355_E_IO, "%s: %s cannot be measured", where, path.c_str());
   else if (offset > size) rc = Fail(PK_MI355_E_IO, "%s: offset %lld is past the end of %s (%lld bytes)", where, (long long)offset, path.c_str(), (long long)size);
   else if (fseeko(f, (off_t)offset, SEEK_SET) != 0) rc = Fail(PK_MI355_E_IO, "%s: cannot seek in %s", where, path.c_str());
-  else rc = ReadObject(f, where, data, rows, cols);
+  else rc = ReadObject(f, where, data, wide, rows, cols);
   fclose(f);
   return rc;
 }
@@ -222,7 +233,7 @@ int NextScp(pk_mi355_ark *h) {
   h->key = text.substr(0, sp);
   char where[256];
   snprintf(where, sizeof(where), "%.150s line %d", h->path.c_str(), h->line);
-  return ReadRx(text.substr(at), where, &h->data, &h->rows, &h->cols) ? pk_mi355_last_error_code() : 1;
+  return ReadRx(text.substr(at), where, &h->data, &h->wide, &h->rows, &h->cols) ? pk_mi355_last_error_code() : 1;
 }
 
 }  // namespace
@@ -258,7 +269,7 @@ pk_mi355_ark_t *pk_mi355_ark_read_object(const char *rxfilename) {
   h->single = true; h->path = rxfilename;
   int rc;
   try {
-    rc = ReadRx(h->path, rxfilename, &h->data, &h->rows, &h->cols);
+    rc = ReadRx(h->path, rxfilename, &h->data, &h->wide, &h->rows, &h->cols);
   } catch (const std::exception &) {                     // (no exception crosses the C boundary)
     rc = Fail(PK_MI355_E_IO, "%s: out of host memory", rxfilename);
   }
@@ -281,7 +292,7 @@ int pk_mi355_ark_next(pk_mi355_ark_t *h) {
       if (rc == 1) {
         char where[256];
         snprintf(where, sizeof(where), "%.120s key '%.100s'", h->path.c_str(), h->key.c_str());
-        if (ReadObject(h->f, where, &h->data, &h->rows, &h->cols)) rc = pk_mi355_last_error_code();
+        if (ReadObject(h->f, where, &h->data, &h->wide, &h->rows, &h->cols)) rc = pk_mi355_last_error_code();
       }
     }
   } catch (const std::exception &) {                     // an entry the host cannot hold; no exception crosses the C boundary
@@ -301,6 +312,17 @@ int pk_mi355_ark_matrix(const pk_mi355_ark_t *h, pk_matrix_t *view) {
   view->nrow = h->cols;                                  // the feature dimension
   view->data = h->data.empty() ? nullptr : const_cast<float *>(h->data.data());
   return 0;
+}
+
+int pk_mi355_ark_matrix_f64(const pk_mi355_ark_t *h, double *out, int capacity) {
+  if (!h || !out) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (!h->have) return Fail(PK_MI355_E_STATE, "no current entry");
+  if (h->rows > kWideRows) return Fail(PK_MI355_E_INVALID, "the entry has %d rows: doubles are kept for matrices of at most %d rows", h->rows, kWideRows);
+  const size_t count = (size_t)h->rows * (size_t)h->cols;
+  if (h->wide.size() != count) return Fail(PK_MI355_E_STATE, "internal: the entry's doubles were not kept");
+  if (capacity < 0 || (size_t)capacity < count) return Fail(PK_MI355_E_INVALID, "the entry has %d x %d values, the buffer holds %d", h->rows, h->cols, capacity);
+  for (size_t i = 0; i < count; ++i) out[i] = h->wide[i];
+  return (int)count;
 }
 
 void pk_mi355_ark_close(pk_mi355_ark_t *h) {

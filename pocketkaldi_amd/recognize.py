@@ -2,6 +2,7 @@
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
                                         [--frontend key=value,...]
+                                        [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]]
                                         [--online [--chunk-ms N] [--partials] [--commit]
                                          [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
     python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...>
@@ -33,6 +34,16 @@ are FrontendSpec's field names, omitted keys take its defaults; an unknown key o
 with the key named and the usage text.  The model file's cmvn_stats then has the spec's dimension + 1 entries, and
 --features matrices are [T][dimension].  It combines with every other flag; without it nothing changes.
 
+--cmvn mode=sliding|none|utterance|speaker,norm_means=true|false,norm_vars=true|false takes a model that was trained with
+Kaldi's apply-cmvn instead of the sliding rule (pk.NormSpec): per utterance, per speaker, with or
+without variance, or not at all.  It works with every batch form -- wave files and lists, --features raw matrices and
+archives, --frontend.  Mode speaker needs --cmvn-stats RX, an archive or script file of 2 x (D + 1) statistics matrices
+(compute-cmvn-stats' output; ark:<path>, scp:<path> or a path), keyed by what this program prints in front of an
+utterance's line -- or by speaker, with --utt2spk FILE ("<utterance> <speaker>" per line).  An utterance or a speaker
+without an entry is refused with its name and the usage text, as are --cmvn-stats without mode=speaker and mode=speaker
+without --cmvn-stats.  With --features normalized the matrices are ready for the splice and no norm applies.  The
+online objects do not take a norm spec yet: --cmvn with --online is refused with the usage text.
+
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
 up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
@@ -58,16 +69,92 @@ RESERVE = 32
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
-          "[--frontend key=value,...] "
+          "[--frontend key=value,...] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
-          "--features raw|normalized [--ctm] [--reference-softmax] [--online ...]")
+          "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--online ...]")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
     print("    *.npy / *.npz (with --features): decode this feature matrix / every array of the file.")
     print("    *.ark / *.scp / ark:<path> / scp:<path> (with --features): decode every matrix of this Kaldi archive / script file.")
     return 1
+
+
+class Norm:
+    """--cmvn and what goes with it: the spec, and for mode speaker the statistics by key and the utterance-to-speaker map."""
+
+    def __init__(self, spec, stats=None, utt2spk=None):
+        self.spec, self.stats, self.utt2spk = spec, stats, utt2spk
+
+    def apply(self, rec):
+        rec.batch.set_norm(self.spec)
+
+    def speaker_stats(self, names):
+        """The records of these utterances, or None when the mode takes none.  UsageError names a missing key."""
+        if self.stats is None:
+            return None
+        out = []
+        for name in names:
+            key = name
+            if self.utt2spk is not None:
+                if name not in self.utt2spk:
+                    raise UsageError("--utt2spk: no speaker for utterance '%s'" % name)
+                key = self.utt2spk[name]
+            if key not in self.stats:
+                raise UsageError("--cmvn-stats: no statistics for %s '%s'" % ("speaker" if self.utt2spk is not None else "utterance", key))
+            out.append(self.stats[key])
+        return out
+
+
+class UsageError(Exception):
+    pass
+
+
+def take_value(argv, flag):
+    """Remove `flag VALUE` from argv -> VALUE, or None when the flag is absent.  UsageError when the value is missing."""
+    if flag not in argv:
+        return None
+    at = argv.index(flag)
+    if at + 1 >= len(argv):
+        raise UsageError("%s needs a value" % flag)
+    value = argv[at + 1]
+    del argv[at:at + 2]
+    return value
+
+
+def parse_norm_flags(argv):
+    """--cmvn, --cmvn-stats and --utt2spk out of argv -> a Norm, or None without --cmvn.  UsageError says what is wrong."""
+    text, stats_rx, utt2spk_file = take_value(argv, "--cmvn"), take_value(argv, "--cmvn-stats"), take_value(argv, "--utt2spk")
+    if text is None:
+        if stats_rx is not None or utt2spk_file is not None:
+            raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker")
+        return None
+    if "--online" in argv:
+        raise UsageError("--cmvn: the online objects do not take a norm spec yet; use it without --online")
+    try:
+        spec = pk.parse_norm(text)
+        spec.check()
+    except (ValueError, pk.PkError) as e:
+        raise UsageError("--cmvn: %s" % e)
+    speaker = spec.mode == pk.NORM_MODES["speaker"]
+    if speaker and stats_rx is None:
+        raise UsageError("--cmvn mode=speaker needs --cmvn-stats")
+    if not speaker and (stats_rx is not None or utt2spk_file is not None):
+        raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker")
+    stats = utt2spk = None
+    if speaker:
+        stats = pk.read_cmvn_stats_archive(stats_rx)
+        if utt2spk_file is not None:
+            utt2spk = {}
+            with open(utt2spk_file) as f:
+                for n, line in enumerate(f):
+                    if line.strip():
+                        parts = line.split()
+                        if len(parts) != 2:
+                            raise UsageError("--utt2spk: line %d of %s is not '<utterance> <speaker>'" % (n + 1, utt2spk_file))
+                        utt2spk[parts[0]] = parts[1]
+    return Norm(spec, stats, utt2spk)
 
 
 def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, endpoint=None,
@@ -171,6 +258,14 @@ def main(argv):
             print("pocketkaldi: --frontend: %s" % e)
             return usage()
         del argv[at:at + 2]
+    try:
+        norm = parse_norm_flags(argv)
+    except UsageError as e:
+        print("pocketkaldi: %s" % e)
+        return usage()
+    except (pk.PkError, OSError) as e:
+        print("pocketkaldi: %s" % e)
+        return 1
     endpoint, rules = None, []
     try:
         while "--endpoint-rule" in argv:
@@ -197,7 +292,7 @@ def main(argv):
         return usage()
     try:
         if features:
-            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend)
+            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend, norm)
         if input_file.endswith(".wav"):
             files = [input_file]
         else:
@@ -218,8 +313,13 @@ def main(argv):
                                 max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend)
             if "--reference-softmax" in flags:
                 rec.am.set_softmax("reference")
+            if norm:
+                norm.apply(rec)
             native = any(r != 16000 for r in rates)
-            results, names = rec.process(waves, rates if native else None), rec.symbols
+            results, names = rec.process(waves, rates if native else None, norm.speaker_stats(files) if norm else None), rec.symbols
+    except UsageError as e:
+        print("pocketkaldi: %s" % e)
+        return usage()
     except (pk.PkError, OSError, ValueError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
         return 1
@@ -277,7 +377,7 @@ def feature_groups(input_file):
             yield group
 
 
-def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None):
+def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None, norm=None):
     """--features: every group of utterances through a Recognizer (process_features) or, with --online, through the
     slots of an OnlineRecognizer; the object is kept from group to group while the group fits it.  Raises what main
     reports; -> the exit code."""
@@ -303,13 +403,16 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
                     rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend)
                     if "--reference-softmax" in flags:
                         rec.am.set_softmax("reference")
+                    if norm:
+                        norm.apply(rec)
                 held = need
             pieces = {} if endpoint else None
             if online:
                 results, names = stream_waves(rec, files, feats, chunk_ms, "--reference-softmax" in flags, "--partials" in flags,
                                               "--commit" in flags, None, pieces, feature_kind=kind)
             else:
-                results, names = rec.process_features(feats, kind), rec.symbols
+                spk = norm.speaker_stats(files) if norm and kind == "raw" else None
+                results, names = rec.process_features(feats, kind, spk), rec.symbols
             emit(files, results, names, "--ctm" in flags, pieces)
     finally:
         if rec is not None:
