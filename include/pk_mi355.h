@@ -474,6 +474,52 @@ int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, in
  * PK_MI355_E_STATE when the last score was not one in that mode.                                                   */
 int pk_mi355_norm_fetch_stats(pk_mi355_batch_t *b, int utt, double *out);
 
+/* ---- Online CMVN: Kaldi's OnlineCmvn -- the rule of apply-cmvn-online and of a live recogniser
+ * -- restated: a sliding window of cmn_window frames carried in double, with or without variance, smoothed first by the
+ * speaker's statistics and then by global ones while the window is not yet full.  Means are always normalised.  (Not
+ * compared with a Kaldi binary; no Freeze, no skip_dims.)                                                          */
+typedef struct pk_mi355_online_cmvn_spec {
+  int32_t cmn_window;       /* W, in [1, 6000]; Kaldi's default 600 */
+  int32_t speaker_frames;   /* >= 0; at most this many frames of the speaker's statistics smooth a window (600) */
+  int32_t global_frames;    /* >= 0; at most this many frames of the global statistics (200); > 0 needs them */
+  int32_t norm_vars;        /* 0 or 1 */
+} pk_mi355_online_cmvn_spec_t;
+/* Global and speaker statistics are 2 x (D + 1) doubles, as above.  The rule, every column d on its own, the state in
+ * double: S0 = S1 = 0.0; for t ascending:
+ *   1. S0 += (double)x[t], then S1 += (double)x[t] * (double)x[t];
+ *   2. if t >= W: S0 -= (double)x[t - W], then S1 -= (double)x[t - W] * (double)x[t - W] (after the additions);
+ *   3. N = min(t + 1, W);
+ *   4. on copies s0, s1, N, every a + f * b a rounded product and a rounded add: nothing if N >= W; with a speaker
+ *      record of count C > 0: c = min(W - N, speaker_frames, C), and if c > 0: f = c / C, s0 += f * spk[0][d],
+ *      s1 += f * spk[1][d], N += f * C; if still N < W and global_frames > 0: c = min(W - N, global_frames), f = c / G
+ *      (G the global count), s0 += f * glob[0][d], s1 += f * glob[1][d], N += f * G;
+ *   5. mean, scale, offset and y[t] from s0, s1, N as above (norm_means = 1; the floor 1e-20; one rounding to float each).
+ * The smoothed copies never feed back into S0, S1.  No frames: nothing happens.  A NaN makes its own column of its own
+ * utterance NaN from its frame on (x - x of a NaN or an inf is NaN: it does not leave with the window).
+ *
+ * pk_mi355_online_cmvn_check: PK_MI355_E_INVALID with a text that names the field -- a null spec, cmn_window outside
+ * [1, 6000], a negative speaker_frames or global_frames, a norm_vars that is neither 0 nor 1, global_frames > 0 with
+ * global_stats NULL or with a global count (global_stats[dim]) that is not positive and finite.  global_stats may be
+ * NULL when global_frames is 0.  Host only.                                                                        */
+int pk_mi355_online_cmvn_check(const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats, int dim);
+/* The rule on the host, for one matrix x [T][D] -> y [T][D] (not in place): the restatement the GPU path is held to.
+ * speaker_stats (may be NULL: no speaker prior; a count of 0 means the same): PK_MI355_E_INVALID for a count that is
+ * negative or not finite.  state_out (may be NULL): 2 x (D + 1) doubles, the window state behind the last frame -- row
+ * 0 the D sums S0 and then the frames seen, row 1 the D sums S1 and then 0.                                        */
+int pk_mi355_online_cmvn_apply(const pk_mi355_online_cmvn_spec_t *spec, const float *x, int num_frames, int dim,
+                               const double *global_stats, const double *speaker_stats, float *y, double *state_out);
+/* Online CMVN as the normalisation of a batch scorer of any kind, in NormKernel's place: OnlineCmvnKernel, then
+ * FeatureLayoutKernel, in the PK_MI355_K_CMVN timing slot.  global_stats: 2 x (feat_dim + 1) doubles, copied (NULL
+ * with global_frames = 0).  The refusals are pk_mi355_online_cmvn_check's, before any launch; the batch then keeps the
+ * norm it had.  It holds until a pk_mi355_norm_set leaves it.  As with every spec but SLIDING, a features-only batch
+ * made without statistics then takes PK_MI355_FEATS_RAW.  pk_mi355_norm_set_speaker_stats is legal in this mode: the
+ * records are optional, belong to the next score call and are consumed by it; a count that is negative or not finite
+ * is PK_MI355_E_INVALID (the utterance named), records for another number of utterances than the call's make
+ * pk_mi355_batch_score fail with PK_MI355_E_STATE.  pk_mi355_norm_fetch_stats has nothing to return in this mode
+ * (PK_MI355_E_STATE).  Device memory, made at the first call: the [max_frames][feat_dim] float staging (shared with
+ * the other modes) and 16 * (feat_dim + 1) * (max_utts + 1) bytes of statistics.                                    */
+int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats);
+
 /* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
  * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
  * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is
@@ -814,6 +860,33 @@ int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind);
 int pk_mi355_stream_push_features(pk_mi355_stream_t *s, int slot, const float *frames, int num_frames);
 /* The model's feature dimension: the length of a pushed frame.  Negative on a null object.                          */
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s);
+
+/* ---- The normalisation of an online scorer of any kind (pk_mi355_stream_create, pk_mi355_features_stream_create*,
+ * pk_mi355_frontend_stream_create): every row a slot's life produces is the row the batch scorer produces under the
+ * same spec on the whole input, bit for bit, whatever the chunks.  Both set entries: only while no slot is in use (open,
+ * or closed and not yet flushed), else PK_MI355_E_STATE, and the object keeps the norm it had.  With anything but
+ * SLIDING the audio and RAW slots' fresh rows go through StreamNormKernel (NONE: nothing) and
+ * StreamFeatureLayoutKernel at every dimension, 40 included, and an object made without statistics takes
+ * PK_MI355_FEATS_RAW slots; with SLIDING (never set, or set again) it launches what it always launched.
+ * pk_mi355_stream_norm_set: SLIDING, NONE or SPEAKER; UTTERANCE is PK_MI355_E_INVALID (an utterance's statistics do
+ * not exist while it is live); the other refusals are pk_mi355_norm_check's.
+ * pk_mi355_stream_norm_set_online_cmvn: as pk_mi355_norm_set_online_cmvn.
+ * Device memory, made by the first call that needs it, S slots at dimension D: 16 D S bytes of whole-slot sums;
+ * SPEAKER 8 D S bytes of tables; online CMVN 16 D S bytes of window sums, 16 (D + 1) (S + 1) bytes of records and
+ * 4 cmn_window D S bytes of raw rows; and the layout history 8 max(L + R, 1) D S bytes where it does not exist yet. */
+int pk_mi355_stream_norm_set(pk_mi355_stream_t *s, const pk_mi355_norm_spec_t *spec);
+int pk_mi355_stream_norm_set_online_cmvn(pk_mi355_stream_t *s, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats);
+/* The speaker's 2 x (feat_dim + 1) record of an open slot, handed over before the slot's first frame is computed (else,
+ * or for a slot of NORMALIZED features, or under SLIDING or NONE: PK_MI355_E_STATE); it lasts until the slot is opened
+ * again.  SPEAKER: required -- pk_mi355_stream_step with an audio or RAW slot in use that has none fails with
+ * PK_MI355_E_STATE, names the slot and consumes nothing; a count that is not positive and finite is PK_MI355_E_INVALID.
+ * Online CMVN: optional; a count of 0 is no prior, one that is negative or not finite PK_MI355_E_INVALID.           */
+int pk_mi355_stream_norm_set_speaker_stats(pk_mi355_stream_t *s, int slot, const double *stats);
+/* SPEAKER and online CMVN: the 2 x (feat_dim + 1) record of all frames of the slot computed since it was opened (it
+ * stays readable after the slot's flush, until the slot is opened again), accumulated in the UTTERANCE rule's order:
+ * the bits pk_mi355_norm_fetch_stats gives for the whole input, so a caller can add it to the speaker's record for the
+ * next utterance.  PK_MI355_E_STATE under SLIDING or NONE and for a slot of NORMALIZED features.  Synchronises.      */
+int pk_mi355_stream_norm_fetch_stats(pk_mi355_stream_t *s, int slot, double *out);
 /* What the slot was last opened as: -1 for audio (also before its first opening), else its PK_MI355_FEATS_* kind.  A
  * null object or a slot out of range gives PK_MI355_E_INVALID, which is -1 as well, and sets pk_mi355_last_error.     */
 int pk_mi355_stream_slot_kind(const pk_mi355_stream_t *s, int slot);

@@ -419,6 +419,19 @@ class OnlineScorer {
   int FeatDim() const { return pk_mi355_stream_feat_dim(s_); }
   // -1: audio, else the PK_MI355_FEATS_* kind the slot was last opened with
   int SlotKind(int slot) const { return pk_mi355_stream_slot_kind(s_, slot); }
+  // The normalisation of the audio and RAW slots, while no slot is in use: a NormSpec of mode sliding,
+  // none or speaker, or an OnlineCmvnSpec with its global statistics (2 x (FeatDim() + 1) doubles; null with global_frames = 0).
+  Status SetNorm(const pk_mi355_norm_spec_t &spec) { return Status::FromLast(pk_mi355_stream_norm_set(s_, &spec)); }
+  Status SetNorm(const pk_mi355_online_cmvn_spec_t &spec, const double *global_stats) {
+    return Status::FromLast(pk_mi355_stream_norm_set_online_cmvn(s_, &spec, global_stats));
+  }
+  // the speaker's 2 x (FeatDim() + 1) record of an open slot, before its first frame is computed
+  Status SetSpeakerStats(int slot, const double *stats) { return Status::FromLast(pk_mi355_stream_norm_set_speaker_stats(s_, slot, stats)); }
+  // the 2 x (FeatDim() + 1) record of all frames of the slot since it was opened
+  Status NormStats(int slot, std::vector<double> *out) {
+    out->assign(2 * (static_cast<size_t>(pk_mi355_stream_feat_dim(s_)) + 1), 0.0);
+    return Status::FromLast(pk_mi355_stream_norm_fetch_stats(s_, slot, out->data()));
+  }
   Status Close(int slot) { return Status::FromLast(pk_mi355_stream_close(s_, slot)); }
   // Synchronous: the rows are ready on return.
   Status Step(float prob_scale) { return Status::FromLast(pk_mi355_stream_step(s_, prob_scale, 1)); }
@@ -489,6 +502,16 @@ struct NormSpec : pk_mi355_norm_spec_t {
   }
 };
 
+// Online CMVN (pk_mi355_online_cmvn_spec_t): Kaldi's OnlineCmvn at its defaults.  Nothing is
+// checked here: the library refuses a bad spec wherever one is used.
+struct OnlineCmvnSpec : pk_mi355_online_cmvn_spec_t {
+  explicit OnlineCmvnSpec(int window = 600, int spk_frames = 600, int glob_frames = 200, bool vars = false) {
+    cmn_window = window; speaker_frames = spk_frames; global_frames = glob_frames; norm_vars = vars ? 1 : 0;
+  }
+  // global_stats: 2 x (dim + 1) doubles, or null when global_frames is 0
+  Status Check(const double *global_stats, int dim) const { return Status::FromLast(pk_mi355_online_cmvn_check(this, global_stats, dim)); }
+};
+
 // The batched, device-resident scorer (pk_mi355_batch_*): PCM of many utterances -> log-likelihood rows.
 class BatchScorer {
  public:
@@ -523,7 +546,11 @@ class BatchScorer {
   Status FetchNormalized(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_cmvn(b_, utt, out)); }
   // The normalisation between the front-end and the first layer; it holds until it is set again.
   Status SetNorm(const NormSpec &spec) { return Status::FromLast(pk_mi355_norm_set(b_, &spec)); }
-  // mode speaker: [num_utts][2][FeatDim() + 1] doubles, consumed by the next Score
+  // Online CMVN instead; global_stats: 2 x (FeatDim() + 1) doubles, or null with global_frames = 0.
+  Status SetNorm(const OnlineCmvnSpec &spec, const double *global_stats) {
+    return Status::FromLast(pk_mi355_norm_set_online_cmvn(b_, &spec, global_stats));
+  }
+  // mode speaker (required) and online CMVN (optional): [num_utts][2][FeatDim() + 1] doubles, consumed by the next Score
   Status SetSpeakerStats(const double *stats, int num_utts) { return Status::FromLast(pk_mi355_norm_set_speaker_stats(b_, stats, num_utts)); }
   // the 2 x (FeatDim() + 1) record the last Score computed for utterance utt in mode utterance
   Status NormStats(int utt, std::vector<double> *out) {

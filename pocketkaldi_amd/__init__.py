@@ -30,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "parse_norm", "cmvn_normalize", "kaldi_cmvn_stats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -84,6 +84,10 @@ class pk_mi355_frontend_spec_t(C.Structure):     # a front-end specification (in
 
 class pk_mi355_norm_spec_t(C.Structure):         # a normalisation specification (include/pk_mi355.h)
     _fields_ = [("mode", C.c_int32), ("norm_means", C.c_int32), ("norm_vars", C.c_int32)]
+
+
+class pk_mi355_online_cmvn_spec_t(C.Structure):  # an online CMVN specification (include/pk_mi355.h)
+    _fields_ = [("cmn_window", C.c_int32), ("speaker_frames", C.c_int32), ("global_frames", C.c_int32), ("norm_vars", C.c_int32)]
 
 
 EXPORTS = [
@@ -151,6 +155,9 @@ EXPORTS = [
     "pk_mi355_frontend_stream_create", "pk_mi355_load_stats", "pk_mi355_frontend_recognizer_load", "pk_mi355_frontend_online_recognizer_load",
     "pk_mi355_norm_check", "pk_mi355_norm_apply", "pk_mi355_norm_set", "pk_mi355_norm_set_speaker_stats", "pk_mi355_norm_fetch_stats",
     "pk_mi355_ark_matrix_f64",
+    "pk_mi355_online_cmvn_check", "pk_mi355_online_cmvn_apply", "pk_mi355_norm_set_online_cmvn",
+    "pk_mi355_stream_norm_set", "pk_mi355_stream_norm_set_online_cmvn", "pk_mi355_stream_norm_set_speaker_stats",
+    "pk_mi355_stream_norm_fetch_stats",
 ]
 
 
@@ -435,6 +442,14 @@ def lib():
     L.pk_mi355_norm_set.argtypes = [C.c_void_p, normp]
     L.pk_mi355_norm_set_speaker_stats.argtypes = [C.c_void_p, f64p, C.c_int]
     L.pk_mi355_norm_fetch_stats.argtypes = [C.c_void_p, C.c_int, f64p]
+    onlinep = C.POINTER(pk_mi355_online_cmvn_spec_t)
+    L.pk_mi355_online_cmvn_check.argtypes = [onlinep, f64p, C.c_int]
+    L.pk_mi355_online_cmvn_apply.argtypes = [onlinep, f32p, C.c_int, C.c_int, f64p, f64p, f32p, f64p]
+    L.pk_mi355_norm_set_online_cmvn.argtypes = [C.c_void_p, onlinep, f64p]
+    L.pk_mi355_stream_norm_set.argtypes = [C.c_void_p, normp]
+    L.pk_mi355_stream_norm_set_online_cmvn.argtypes = [C.c_void_p, onlinep, f64p]
+    L.pk_mi355_stream_norm_set_speaker_stats.argtypes = [C.c_void_p, C.c_int, f64p]
+    L.pk_mi355_stream_norm_fetch_stats.argtypes = [C.c_void_p, C.c_int, f64p]
     L.pk_mi355_ark_matrix_f64.argtypes = [C.c_void_p, f64p, C.c_int]
     _lib = L
     return L
@@ -700,23 +715,83 @@ class NormSpec:
         return "NormSpec(mode=%r, norm_means=%r, norm_vars=%r)" % (self.mode, self.norm_means, self.norm_vars)
 
 
+class OnlineCmvnSpec:
+    """An online CMVN specification (pk_mi355_online_cmvn_spec_t): Kaldi's OnlineCmvn -- a window
+    of cmn_window frames, smoothed by at most speaker_frames of the speaker's statistics and then at most global_frames
+    of the global ones while it is not full; means always, variance with norm_vars.  Nothing is checked here: the
+    library refuses a bad spec (PkCodeError, the field named) wherever one is used."""
+
+    def __init__(self, cmn_window=600, speaker_frames=600, global_frames=200, norm_vars=False):
+        self.cmn_window, self.speaker_frames, self.global_frames, self.norm_vars = cmn_window, speaker_frames, global_frames, norm_vars
+
+    def struct(self):
+        try:
+            return pk_mi355_online_cmvn_spec_t(int(self.cmn_window), int(self.speaker_frames), int(self.global_frames), int(self.norm_vars))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise PkCodeError(-1, "online cmvn spec: %s" % e)
+
+    def check(self, global_stats=None, dim=None):
+        """global_stats: the 2 x (D + 1) record, or None; dim: D when there is no record to take it from."""
+        g = None if global_stats is None else _global_record(global_stats, dim)
+        D = dim if g is None else g.shape[1] - 1
+        _check_code(lib().pk_mi355_online_cmvn_check(C.byref(self.struct()), None if g is None else _dp(g), int(D or 0)))
+
+    def __repr__(self):
+        return "OnlineCmvnSpec(cmn_window=%r, speaker_frames=%r, global_frames=%r, norm_vars=%r)" % (
+            self.cmn_window, self.speaker_frames, self.global_frames, self.norm_vars)
+
+
+def _global_record(stats, dim=None):
+    """One 2 x (D + 1) record of doubles; another shape is refused here."""
+    try:
+        a = np.ascontiguousarray(stats, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise PkCodeError(-1, "global statistics are not numbers: %s" % e)
+    if a.ndim != 2 or a.shape[0] != 2 or a.shape[1] < 2 or (dim is not None and a.shape[1] != dim + 1):
+        raise PkCodeError(-1, "global statistics have shape %s, expected [2][%s]" % (a.shape, "D + 1" if dim is None else dim + 1))
+    return a
+
+
+ONLINE_CMVN_KEYS = ("cmn_window", "speaker_frames", "global_frames")
+
+
 def parse_norm(text):
     """A NormSpec from "key=value,key=value,...": mode (sliding | none | utterance | speaker), norm_means and norm_vars
-    (true | false | 1 | 0); omitted keys take NormSpec's defaults.  ValueError, the key named, for an unknown key or a
-    value that does not parse.  Nothing else is checked here: the library refuses a bad spec where it is used."""
+    (true | false | 1 | 0); omitted keys take NormSpec's defaults.  mode=online gives an OnlineCmvnSpec instead, with the
+    keys cmn_window, speaker_frames, global_frames (integers) and norm_vars.  ValueError, the key named, for an unknown
+    key, a value that does not parse, or a key that does not go with the mode.  Nothing else is checked here: the
+    library refuses a bad spec where it is used."""
     switch = {"true": True, "false": False, "1": True, "0": False}
-    fields = {"mode": NORM_MODES, "norm_means": switch, "norm_vars": switch}
+    modes = dict(NORM_MODES, online="online")
+    fields = {"mode": modes, "norm_means": switch, "norm_vars": switch}
+    keys = sorted(list(fields) + list(ONLINE_CMVN_KEYS))
     given = {}
     for item in [t.strip() for t in text.split(",") if t.strip()]:
         key, eq, value = item.partition("=")
         key, value = key.strip(), value.strip()
-        if key not in fields:
-            raise ValueError("norm spec: unknown key '%s' (the keys are %s)" % (key, ", ".join(sorted(fields))))
+        if key not in keys:
+            raise ValueError("norm spec: unknown key '%s' (the keys are %s)" % (key, ", ".join(keys)))
         if key in given:
             raise ValueError("norm spec: key '%s' given twice" % key)
+        if key in ONLINE_CMVN_KEYS:
+            try:
+                given[key] = int(value) if eq else None
+            except ValueError:
+                given[key] = None
+            if given[key] is None:
+                raise ValueError("norm spec: bad value '%s' for key '%s' (an integer)" % (value, key))
+            continue
         if not eq or value not in fields[key]:
             raise ValueError("norm spec: bad value '%s' for key '%s' (one of %s)" % (value, key, ", ".join(sorted(fields[key]))))
         given[key] = fields[key][value]
+    if given.get("mode") == "online":
+        if "norm_means" in given:
+            raise ValueError("norm spec: key 'norm_means' does not go with mode=online (online CMVN always normalises the means)")
+        del given["mode"]
+        return OnlineCmvnSpec(**given)
+    for key in ONLINE_CMVN_KEYS:
+        if key in given:
+            raise ValueError("norm spec: key '%s' needs mode=online" % key)
     return NormSpec(**given)
 
 
@@ -744,6 +819,24 @@ def cmvn_normalize(feats, spec, stats=None):
     y, acc = np.zeros((T, D), np.float32), np.zeros((2, D + 1), np.float64)
     _check_code(lib().pk_mi355_norm_apply(C.byref(st), _fp(x), T, D, None if rec is None else _dp(rec), _fp(y), _dp(acc)))
     return y, (acc if st.mode == NORM_MODES["utterance"] else None)
+
+
+def cmvn_online(feats, spec, global_stats=None, speaker_stats=None, return_state=False):
+    """The rule of an OnlineCmvnSpec on the host for one [T][D] matrix (pk_mi355_online_cmvn_apply: the restatement the
+    GPU path is held to) -> normalised float32 [T][D].  global_stats, speaker_stats: 2 x (D + 1) records or None.
+    return_state: also the 2 x (D + 1) float64 window state behind the last frame (sums and frames seen, sums of
+    squares and 0)."""
+    x = _f32(feats)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise PkCodeError(-1, "features have shape %s, expected [T][D]" % (x.shape,))
+    T, D = x.shape
+    st = spec.struct()
+    g = None if global_stats is None else _global_record(global_stats, D)
+    spk = None if speaker_stats is None else _stats_records([speaker_stats], 1, D)
+    y, state = np.zeros((T, D), np.float32), np.zeros((2, D + 1), np.float64)
+    _check_code(lib().pk_mi355_online_cmvn_apply(C.byref(st), _fp(x), T, D, None if g is None else _dp(g), None if spk is None else _dp(spk),
+                                                 _fp(y), _dp(state)))
+    return (y, state) if return_state else y
 
 
 class CMVN:
@@ -1158,13 +1251,22 @@ class BatchScorer:
         _check_code(lib().pk_mi355_batch_fetch_cmvn(self._h, utt, _fp(out)))
         return out
 
-    def set_norm(self, spec):
-        """The normalisation between the front-end (or raw features) and the first layer: a NormSpec.  It holds until it
-        is set again.  Anything but "sliding" also lets a FeatureScorer made without statistics take kind "raw"."""
+    def set_norm(self, spec, global_stats=None):
+        """The normalisation between the front-end (or raw features) and the first layer: a NormSpec, or an
+        OnlineCmvnSpec with the 2 x (feat_dim + 1) global record it smooths with (None with global_frames = 0).  It
+        holds until it is set again.  Anything but "sliding" also lets a FeatureScorer made without statistics take
+        kind "raw"."""
+        if isinstance(spec, OnlineCmvnSpec):
+            g = None if global_stats is None else _global_record(global_stats, self.feat_dim())
+            _check_code(lib().pk_mi355_norm_set_online_cmvn(self._h, C.byref(spec.struct()), None if g is None else _dp(g)))
+            return
+        if global_stats is not None:
+            raise PkCodeError(-1, "global statistics go with an OnlineCmvnSpec, not with a NormSpec")
         _check_code(lib().pk_mi355_norm_set(self._h, C.byref(spec.struct())))
 
     def set_speaker_stats(self, stats):
-        """Mode "speaker": one 2 x (feat_dim + 1) record per utterance of the next score call, which consumes them."""
+        """Mode "speaker" (required) and online CMVN (optional; a count of 0: no prior for that utterance): one
+        2 x (feat_dim + 1) record per utterance of the next score call, which consumes them."""
         n = len(stats)
         a = _stats_records(stats, n, self.feat_dim())
         _check_code(lib().pk_mi355_norm_set_speaker_stats(self._h, _dp(a) if n else None, n))
@@ -1256,20 +1358,51 @@ class OnlineScorer:
         except Exception:
             pass
 
-    def open(self, slot, rate=16000):
-        """rate: the sample rate of what will be pushed to the slot; converted to 16 kHz on the GPU step by step."""
+    def set_norm(self, spec, global_stats=None):
+        """The normalisation of the audio and "raw" slots, while no slot is in use: a NormSpec of mode
+        "sliding" (the default), "none" or "speaker", or an OnlineCmvnSpec with the 2 x (feat_dim + 1) global record it
+        smooths with (None with global_frames = 0).  Every row is then the BatchScorer's under the same spec."""
+        if isinstance(spec, OnlineCmvnSpec):
+            g = None if global_stats is None else _global_record(global_stats, self.feat_dim())
+            _check_code(lib().pk_mi355_stream_norm_set_online_cmvn(self._h, C.byref(spec.struct()), None if g is None else _dp(g)))
+            return
+        if global_stats is not None:
+            raise PkCodeError(-1, "global statistics go with an OnlineCmvnSpec, not with a NormSpec")
+        _check_code(lib().pk_mi355_stream_norm_set(self._h, C.byref(spec.struct())))
+
+    def set_speaker_stats(self, slot, stats):
+        """The speaker's 2 x (feat_dim + 1) record of an open slot, before its first frame is computed: required in mode
+        "speaker", optional under online CMVN."""
+        a = _stats_records([stats], 1, self.feat_dim())
+        _check_code(lib().pk_mi355_stream_norm_set_speaker_stats(self._h, int(slot), _dp(a)))
+
+    def norm_stats(self, slot):
+        """Mode "speaker" and online CMVN: the 2 x (feat_dim + 1) float64 record of all frames of the slot since it was
+        opened -- BatchScorer.norm_stats' bits on the whole input."""
+        out = np.zeros((2, self.feat_dim() + 1), np.float64)
+        _check_code(lib().pk_mi355_stream_norm_fetch_stats(self._h, int(slot), _dp(out)))
+        return out
+
+    def open(self, slot, rate=16000, speaker_stats=None):
+        """rate: the sample rate of what will be pushed to the slot; converted to 16 kHz on the GPU step by step.
+        speaker_stats: set_speaker_stats on the opened slot."""
         if rate == 16000:
             _check_code(lib().pk_mi355_stream_open(self._h, int(slot)))
         else:
             _check_code(lib().pk_mi355_stream_open_rate(self._h, int(slot), int(rate)))
+        if speaker_stats is not None:
+            self.set_speaker_stats(slot, speaker_stats)
 
     def rate(self, slot):
         return _check_code(lib().pk_mi355_stream_rate(self._h, int(slot)))
 
-    def open_features(self, slot, kind="normalized"):
+    def open_features(self, slot, kind="normalized", speaker_stats=None):
         """The slot takes features instead of audio: kind "normalized" (ready for the splice) or "raw" (40-dim log-mel
-        fbank; the sliding-window CMVN is applied first, carried from step to step)."""
+        fbank; the scorer's normalisation -- the sliding-window CMVN unless set_norm chose another -- is applied first,
+        carried from step to step).  speaker_stats: set_speaker_stats on the opened slot."""
         _check_code(lib().pk_mi355_stream_open_features(self._h, int(slot), _feature_kind(kind)))
+        if speaker_stats is not None:
+            self.set_speaker_stats(slot, speaker_stats)
 
     def push_features(self, slot, frames):
         """[n][feat_dim] frames, n >= 0."""
@@ -1998,12 +2131,15 @@ class OnlineRecognizer:
         except Exception:
             pass
 
-    def open(self, slot, rate=16000):
-        """rate: the sample rate of what will be pushed to the slot."""
+    def open(self, slot, rate=16000, speaker_stats=None):
+        """rate: the sample rate of what will be pushed to the slot.  speaker_stats: the slot's record under the norm set
+        on self.scorer (OnlineScorer.set_norm, set_speaker_stats)."""
         if rate == 16000:
             _check_code(lib().pk_mi355_online_recognizer_open(self._h, int(slot)))
         else:
             _check_code(lib().pk_mi355_online_recognizer_open_rate(self._h, int(slot), int(rate)))
+        if speaker_stats is not None:
+            self.scorer.set_speaker_stats(slot, speaker_stats)
 
     def push(self, slot, samples):
         """float sample values (as read_wav gives them); an int16 array goes through push_i16."""
@@ -2018,10 +2154,12 @@ class OnlineRecognizer:
                                                               x.ctypes.data_as(C.POINTER(C.c_int16)) if x.size else None,
                                                               x.shape[0]))
 
-    def open_features(self, slot, kind="raw"):
+    def open_features(self, slot, kind="raw", speaker_stats=None):
         """The slot takes 40-dim features instead of audio: "raw" log-mel fbank (what a front-end of the caller's makes)
-        or "normalized" (CMVN already applied)."""
+        or "normalized" (CMVN already applied).  speaker_stats: as open."""
         _check_code(lib().pk_mi355_online_recognizer_open_features(self._h, int(slot), _feature_kind(kind)))
+        if speaker_stats is not None:
+            self.scorer.set_speaker_stats(slot, speaker_stats)
 
     def push_features(self, slot, frames):
         """[n][40] frames, n >= 0."""

@@ -196,6 +196,11 @@ struct pk_mi355_batch {
   float *d_spk_table = nullptr;     // [max_utts][2][feat_dim]: offsets and scales of the speaker records handed over
   int spk_utts = -1;                // the utterances the pending speaker records are for (-1: none pending)
   bool norm_stats_valid = false;    // the last score call was one in UTTERANCE mode on raw rows or audio
+  // Online CMVN (pk_mi355_norm_set_online_cmvn): norm.mode is pknorm::kNormOnlineCmvn and
+  // OnlineCmvnKernel stands where NormKernel would; the buffers are made by the first such call.
+  pk_mi355_online_cmvn_spec_t online_cmvn{600, 600, 200, 0};
+  double *d_online_glob = nullptr;  // [2][feat_dim + 1]: the global record
+  double *d_online_spk = nullptr;   // [max_utts][2][feat_dim + 1]: the speaker records handed over for the next score
   _Float16 *d_y2 = nullptr;   // f16x3: interleaved (hi, lo) rows [ldy][2 feat_dim]
   float *h_ll = nullptr;    // page-locked mirror of d_ll (pk_mi355_batch_fetch_all), made on first use
   ArenaRec *arena = nullptr;  // its shared-ownership record
@@ -609,7 +614,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched, b->ev_layout}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats); hipFree(b->d_any);
-  hipFree(b->d_norm_stats); hipFree(b->d_spk_table);
+  hipFree(b->d_norm_stats); hipFree(b->d_spk_table); hipFree(b->d_online_glob); hipFree(b->d_online_spk);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
   hipFree(b->d_native);
@@ -788,11 +793,41 @@ int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec) {
   return 0;
 }
 
+int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats) {
+  if (!b || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  const size_t D = (size_t)b->core.am->feat_dim;
+  if (int rc = pknorm::CheckOnlineSpec(spec, global_stats, (int)D)) return rc;      // (names the field)
+  if (int rc = UseDevice(b->core.device)) return rc;
+  if (int rc = EnsureFeatsStaging(b)) return rc;
+  const size_t rec = 2 * (D + 1);
+  if (!b->d_online_glob) HIP_TRY(hipMalloc(&b->d_online_glob, sizeof(double) * rec));
+  if (!b->d_online_spk) HIP_TRY(hipMalloc(&b->d_online_spk, sizeof(double) * rec * (size_t)b->max_utts));
+  if (spec->global_frames > 0) {                        // (pageable memory: the copy has read the record when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_online_glob, global_stats, sizeof(double) * rec, hipMemcpyHostToDevice, b->core.stream));
+    HIP_TRY(hipStreamSynchronize(b->core.stream));
+  }
+  b->online_cmvn = *spec;
+  b->norm = pk_mi355_norm_spec_t{pknorm::kNormOnlineCmvn, 1, spec->norm_vars};
+  b->spk_utts = -1;                                     // records handed over under another spec are not this spec's
+  return 0;
+}
+
 int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, int num_utts) {
   if (!b || (num_utts > 0 && !stats)) return Fail(PK_MI355_E_INVALID, "null argument");
-  if (b->norm.mode != PK_MI355_NORM_SPEAKER) return Fail(PK_MI355_E_STATE, "speaker statistics need mode speaker (pk_mi355_norm_set)");
+  if (b->norm.mode != PK_MI355_NORM_SPEAKER && b->norm.mode != pknorm::kNormOnlineCmvn)
+    return Fail(PK_MI355_E_STATE, "speaker statistics need mode speaker (pk_mi355_norm_set) or online CMVN (pk_mi355_norm_set_online_cmvn)");
   if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
   const int D = b->core.am->feat_dim;
+  if (b->norm.mode == pknorm::kNormOnlineCmvn) {        // the records as they are: the kernel smooths with them
+    if (int rc = pknorm::CheckOnlineSpeakerCounts(stats, num_utts, D)) return rc;
+    if (int rc = UseDevice(b->core.device)) return rc;
+    if (num_utts > 0) {
+      HIP_TRY(hipMemcpyAsync(b->d_online_spk, stats, sizeof(double) * 2 * ((size_t)D + 1) * (size_t)num_utts, hipMemcpyHostToDevice, b->core.stream));
+      HIP_TRY(hipStreamSynchronize(b->core.stream));
+    }
+    b->spk_utts = num_utts;
+    return 0;
+  }
   std::vector<float> table((size_t)std::max(num_utts, 1) * 2 * D);
   if (int rc = pknorm::FinalizeSpeakerStats(stats, num_utts, D, b->norm.norm_means != 0, b->norm.norm_vars != 0, table.data())) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
@@ -842,6 +877,8 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
       return Fail(PK_MI355_E_STATE, "mode speaker: no speaker statistics set for this score call (pk_mi355_norm_set_speaker_stats)");
     if (mode == PK_MI355_NORM_SPEAKER && spk_utts != b->num_utts)
       return Fail(PK_MI355_E_STATE, "mode speaker: statistics for %d utterances, the call has %d", spk_utts, b->num_utts);
+    if (mode == pknorm::kNormOnlineCmvn && spk_utts >= 0 && spk_utts != b->num_utts)
+      return Fail(PK_MI355_E_STATE, "online CMVN: speaker statistics for %d utterances, the call has %d", spk_utts, b->num_utts);
   }
   if (b->num_utts == 0 || b->total_frames == 0) {
     if (mode == PK_MI355_NORM_UTTERANCE && b->num_utts > 0) {      // records of no frames: zeros
@@ -863,7 +900,11 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
       LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
     else if (mode == PK_MI355_NORM_NONE)      // the raw rows as they are (at D = 40: d_raw, behind CmvnKernel's lead)
       LaunchFeatureLayout(b->d_raw, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else if (mode != PK_MI355_NORM_SLIDING) { // NormKernel, then the layout of its result
+    else if (mode == pknorm::kNormOnlineCmvn) {   // OnlineCmvnKernel, then the layout of its result
+      LaunchOnlineCmvn(b->d_raw, lay, b->num_utts, D, b->online_cmvn, b->d_online_glob, spk_utts >= 0 ? b->d_online_spk : nullptr, b->d_feats,
+                       c.stream);
+      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    } else if (mode != PK_MI355_NORM_SLIDING) { // NormKernel, then the layout of its result
       LaunchNorm(b->d_raw, lay, b->num_utts, D, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats,
                  b->d_feats, c.stream);
       LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);

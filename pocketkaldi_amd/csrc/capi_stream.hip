@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pk_frontend.h"
+#include "pk_norm_kernel.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -41,6 +42,7 @@ struct Slot {
   // the frames handed to a step.  hist_par: the NORMALIZED history buffer that holds the frames below n.
   int kind = -1;
   int hist_par = 0;
+  bool spk_set = false;    // pk_mi355_stream_norm_set_speaker_stats has handed over this opening's record
 };
 
 // the most input samples a native-rate slot carries from one step to the next (Q + max_taps <= 8190 + 74)
@@ -83,9 +85,24 @@ struct pk_mi355_stream {
   // float rows_area on (behind the max_step_samples samples), where the chain and the layout kernel find them.
   FrontendAnyTables *d_any = nullptr;
   int64_t rows_area = 0;
+  // The normalisation spec (pk_mi355_stream_norm_set*).  Anything but SLIDING: the audio and RAW
+  // slots' fresh rows go through StreamNormKernel (NONE: through nothing) and StreamFeatureLayoutKernel at every
+  // dimension; norm.mode is pknorm::kNormOnlineCmvn under online CMVN.  The state below is made by the set calls.
+  pk_mi355_norm_spec_t norm{PK_MI355_NORM_SLIDING, 1, 0};
+  pk_mi355_online_cmvn_spec_t online_cmvn{600, 600, 200, 0};
+  double *d_norm_glob = nullptr, *d_norm_spk = nullptr;      // [2][feat_dim + 1], [slots][2][feat_dim + 1]
+  double *d_norm_win = nullptr, *d_norm_total = nullptr;     // [slots][2][feat_dim] each
+  float *d_norm_table = nullptr, *d_norm_ring = nullptr;     // [slots][2][feat_dim], [slots][ring_window][feat_dim]
+  int ring_window = 0;
 };
 
 namespace {
+StreamNormState NormState(const pk_mi355_stream *s) {
+  const pk_mi355_online_cmvn_spec_t &o = s->online_cmvn;
+  return StreamNormState{s->norm.mode, s->norm.norm_vars, o.cmn_window, o.speaker_frames, o.global_frames, s->d_norm_glob, s->d_norm_spk,
+                         s->d_norm_table, s->d_norm_win, s->d_norm_total, s->d_norm_ring};
+}
+
 int SlotIndex(const pk_mi355_stream *s, int slot) {
   if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
   if (slot < 0 || slot >= s->max_streams) return Fail(PK_MI355_E_INVALID, "slot %d out of range [0, %d)", slot, s->max_streams);
@@ -131,6 +148,25 @@ int EnsureFeatureHistory(pk_mi355_stream *s) {
   if (s->d_feat_hist) return 0;
   if (int rc = UseDevice(s->core.device)) return rc;
   HIP_TRY(hipMalloc(&s->d_feat_hist, sizeof(float) * s->max_streams * 2 * s->hist_len * s->core.am->feat_dim));
+  return 0;
+}
+
+// A slot that is being opened starts without a speaker record; under online CMVN its record on the device says "count 0".
+int ResetSlotNorm(pk_mi355_stream *s, int slot) {
+  s->slots[slot].spk_set = false;
+  if (s->norm.mode != pknorm::kNormOnlineCmvn) return 0;
+  if (int rc = UseDevice(s->core.device)) return rc;
+  const size_t rec = 2 * ((size_t)s->core.am->feat_dim + 1);
+  HIP_TRY(hipMemsetAsync(s->d_norm_spk + slot * rec, 0, sizeof(double) * rec, s->core.stream));
+  return 0;
+}
+
+// The norm entries change what a slot's life looks like: only while every slot is free.
+int NoSlotInUse(const pk_mi355_stream *s) {
+  for (size_t k = 0; k < s->slots.size(); ++k)
+    if (s->slots[k].state != kFree)
+      return Fail(PK_MI355_E_STATE, "slot %d is %s: the normalisation spec is set while no slot is open", (int)k,
+                  s->slots[k].state == kOpen ? "open" : "closed and not yet flushed by a step");
   return 0;
 }
 }  // namespace
@@ -278,6 +314,7 @@ void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
   hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist); hipFree(s->d_feat_hist);
   hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta); hipFree(s->d_any);
+  hipFree(s->d_norm_glob); hipFree(s->d_norm_spk); hipFree(s->d_norm_win); hipFree(s->d_norm_total); hipFree(s->d_norm_table); hipFree(s->d_norm_ring);
   s->resampler.Free();
   if (s->h_native) hipHostFree(s->h_native);
   hipFree(s->d_native);
@@ -306,6 +343,7 @@ int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
       s->native_cap = cap;
     }
   }
+  if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
   z.n = z.a = z.tail_len = 0;
   z.pending.clear();
@@ -321,12 +359,14 @@ int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
 int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind) {
   if (int rc = SlotIndex(s, slot)) return rc;
   if (kind != PK_MI355_FEATS_NORMALIZED && kind != PK_MI355_FEATS_RAW) return Fail(PK_MI355_E_INVALID, "unknown feature kind %d", kind);
-  if (kind == PK_MI355_FEATS_RAW && !s->have_stats)
+  if (kind == PK_MI355_FEATS_RAW && !s->have_stats && s->norm.mode == PK_MI355_NORM_SLIDING)
     return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics the stream object was made without");
   Slot &z = s->slots[slot];
   if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
-  if (kind == PK_MI355_FEATS_NORMALIZED || s->core.am->feat_dim != kNumBins)   // (RAW at another dimension than 40 is laid out as NORMALIZED is)
+  // (RAW at another dimension than 40, or under another normalisation spec than SLIDING, is laid out as NORMALIZED is)
+  if (kind == PK_MI355_FEATS_NORMALIZED || s->core.am->feat_dim != kNumBins || s->norm.mode != PK_MI355_NORM_SLIDING)
     if (int rc = EnsureFeatureHistory(s)) return rc;
+  if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
   z.n = z.a = z.tail_len = 0;
   z.pending.clear();
@@ -404,6 +444,97 @@ int pk_mi355_stream_close(pk_mi355_stream_t *s, int slot) {
   return 0;
 }
 
+int pk_mi355_stream_norm_set(pk_mi355_stream_t *s, const pk_mi355_norm_spec_t *spec) {
+  if (!s || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (int rc = pknorm::CheckSpec(spec)) return rc;      // (names the field)
+  if (spec->mode == PK_MI355_NORM_UTTERANCE)
+    return Fail(PK_MI355_E_INVALID, "norm spec: mode utterance cannot run on a live stream: an utterance's statistics do not exist while it is "
+                "live (mode speaker, or online CMVN, pk_mi355_stream_norm_set_online_cmvn)");
+  if (int rc = NoSlotInUse(s)) return rc;
+  if (spec->mode != PK_MI355_NORM_SLIDING) {
+    if (int rc = EnsureFeatureHistory(s)) return rc;
+    if (int rc = UseDevice(s->core.device)) return rc;
+    const size_t D = (size_t)s->core.am->feat_dim, n = (size_t)s->max_streams;
+    if (!s->d_norm_total) HIP_TRY(hipMalloc(&s->d_norm_total, sizeof(double) * 2 * D * n));
+    if (!s->d_norm_table) HIP_TRY(hipMalloc(&s->d_norm_table, sizeof(float) * 2 * D * n));
+  }
+  s->norm = *spec;
+  return 0;
+}
+
+int pk_mi355_stream_norm_set_online_cmvn(pk_mi355_stream_t *s, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats) {
+  if (!s || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  const size_t D = (size_t)s->core.am->feat_dim, n = (size_t)s->max_streams, rec = 2 * (D + 1);
+  if (int rc = pknorm::CheckOnlineSpec(spec, global_stats, (int)D)) return rc;      // (names the field)
+  if (int rc = NoSlotInUse(s)) return rc;
+  if (int rc = EnsureFeatureHistory(s)) return rc;
+  if (int rc = UseDevice(s->core.device)) return rc;
+  if (!s->d_norm_total) HIP_TRY(hipMalloc(&s->d_norm_total, sizeof(double) * 2 * D * n));
+  if (!s->d_norm_win) HIP_TRY(hipMalloc(&s->d_norm_win, sizeof(double) * 2 * D * n));
+  if (!s->d_norm_glob) HIP_TRY(hipMalloc(&s->d_norm_glob, sizeof(double) * rec));
+  if (!s->d_norm_spk) HIP_TRY(hipMalloc(&s->d_norm_spk, sizeof(double) * rec * n));
+  if (s->ring_window < spec->cmn_window) {              // (no slot is in use: nothing is carried in the ring)
+    HIP_TRY(hipStreamSynchronize(s->core.stream));
+    hipFree(s->d_norm_ring);
+    s->d_norm_ring = nullptr; s->ring_window = 0;
+    HIP_TRY(hipMalloc(&s->d_norm_ring, sizeof(float) * n * (size_t)spec->cmn_window * D));
+    s->ring_window = spec->cmn_window;
+  }
+  if (spec->global_frames > 0) {                        // (pageable memory: the copy has read the record when the call returns)
+    HIP_TRY(hipMemcpyAsync(s->d_norm_glob, global_stats, sizeof(double) * rec, hipMemcpyHostToDevice, s->core.stream));
+    HIP_TRY(hipStreamSynchronize(s->core.stream));
+  }
+  s->online_cmvn = *spec;
+  s->norm = pk_mi355_norm_spec_t{pknorm::kNormOnlineCmvn, 1, spec->norm_vars};
+  return 0;
+}
+
+int pk_mi355_stream_norm_set_speaker_stats(pk_mi355_stream_t *s, int slot, const double *stats) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  if (!stats) return Fail(PK_MI355_E_INVALID, "null argument");
+  const int mode = s->norm.mode;
+  if (mode != PK_MI355_NORM_SPEAKER && mode != pknorm::kNormOnlineCmvn)
+    return Fail(PK_MI355_E_STATE, "speaker statistics need mode speaker (pk_mi355_stream_norm_set) or online CMVN (pk_mi355_stream_norm_set_online_cmvn)");
+  Slot &z = s->slots[slot];
+  if (z.state != kOpen || z.n != 0)
+    return Fail(PK_MI355_E_STATE, "slot %d: speaker statistics belong to an open slot before its first frame is computed", slot);
+  if (z.kind == PK_MI355_FEATS_NORMALIZED) return Fail(PK_MI355_E_STATE, "slot %d takes normalised features: no normalisation applies", slot);
+  const int D = s->core.am->feat_dim;
+  if (mode == PK_MI355_NORM_SPEAKER) {
+    std::vector<float> table((size_t)2 * D);
+    if (int rc = pknorm::FinalizeSpeakerStats(stats, 1, D, s->norm.norm_means != 0, s->norm.norm_vars != 0, table.data())) return rc;
+    if (int rc = UseDevice(s->core.device)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_norm_table + (size_t)slot * 2 * D, table.data(), sizeof(float) * 2 * D, hipMemcpyHostToDevice, s->core.stream));
+  } else {
+    if (int rc = pknorm::CheckOnlineSpeakerCounts(stats, 1, D)) return rc;
+    if (int rc = UseDevice(s->core.device)) return rc;
+    const size_t rec = 2 * ((size_t)D + 1);
+    HIP_TRY(hipMemcpyAsync(s->d_norm_spk + slot * rec, stats, sizeof(double) * rec, hipMemcpyHostToDevice, s->core.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(s->core.stream));        // (pageable memory: the copy has read its source)
+  z.spk_set = true;
+  return 0;
+}
+
+int pk_mi355_stream_norm_fetch_stats(pk_mi355_stream_t *s, int slot, double *out) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  if (!out) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (s->norm.mode != PK_MI355_NORM_SPEAKER && s->norm.mode != pknorm::kNormOnlineCmvn)
+    return Fail(PK_MI355_E_STATE, "statistics are accumulated in mode speaker and under online CMVN only");
+  const Slot &z = s->slots[slot];
+  if (z.kind == PK_MI355_FEATS_NORMALIZED) return Fail(PK_MI355_E_STATE, "slot %d takes normalised features: no statistics", slot);
+  const size_t D = (size_t)s->core.am->feat_dim;
+  for (size_t i = 0; i < 2 * (D + 1); ++i) out[i] = 0.0;
+  if (z.n == 0) return 0;                               // (no frame computed since the slot was opened: the record of no frames)
+  if (int rc = UseDevice(s->core.device)) return rc;
+  std::vector<double> sums(2 * D);
+  HIP_TRY(hipMemcpyAsync(sums.data(), s->d_norm_total + (size_t)slot * 2 * D, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s->core.stream));
+  HIP_TRY(hipStreamSynchronize(s->core.stream));
+  for (size_t d = 0; d < D; ++d) { out[d] = sums[d]; out[D + 1 + d] = sums[D + d]; }
+  out[D] = (double)z.n;
+  return 0;
+}
+
 int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
   ScorerCore &c = s->core;
@@ -432,6 +563,17 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
   int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, chain_pushed = 0, max_feat_cols = 0;
   const int D = am->feat_dim;
+  // Another normalisation spec than SLIDING: nothing goes through StreamCmvnKernel's fused path.  RAW
+  // slots at 40 become back records as at every other dimension (normalised where they lie in the upload staging); audio
+  // slots at 40 stay in front, their rows in d_rows (row_off counts from there), and are laid out from there.
+  const int nmode = s->norm.mode;
+  const bool sliding = nmode == PK_MI355_NORM_SLIDING;
+  if (nmode == PK_MI355_NORM_SPEAKER)
+    for (int slot = 0; slot < s->max_streams; ++slot) {
+      const Slot &z = s->slots[slot];
+      if (z.state != kFree && z.kind != PK_MI355_FEATS_NORMALIZED && !z.spk_set)
+        return Fail(PK_MI355_E_STATE, "mode speaker: slot %d has no speaker statistics (pk_mi355_stream_norm_set_speaker_stats)", slot);
+    }
   std::vector<ShiftSpan> spans;                       // (end row, column shift) per slot with rows
   for (int slot = 0; slot < s->max_streams; ++slot) {
     const Slot &z = s->slots[slot];
@@ -444,7 +586,8 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     // (a front-end spec at a dimension other than 40, DESIGN.md section 18: audio records go the same way, their rows
     // written into the staging's row area by FbankAnyKernel; they stay in front, where the assembly and the fbank look)
     const bool feats = z.kind >= 0, spec_rows = !feats && s->rows_area > 0;
-    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && D != kNumBins);
+    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && (D != kNumBins || !sliding));
+    const bool front_rows = !feats && !sliding && !spec_rows;       // an audio slot at 40 under a norm spec: laid out from d_rows
     const int new_len = feats    ? 0
                         : !z.tab ? (int)z.pending.size()
                                  : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
@@ -462,7 +605,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
     r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
     r.woff = woff; r.new_off = upl; r.raw_base = layout ? 0 : raw;
-    r.row_off = spec_rows ? s->rows_area + raw * D : upl;
+    r.row_off = spec_rows ? s->rows_area + raw * D : front_rows ? raw * D : upl;
     r.col_base = 0; r.cols = 0;
     if (b > z.a) {
       // Rows slot after slot, each padded to four; the slot's columns a - L .. b + R - 1 in a region of RoundUp(b - a, 4)
@@ -474,7 +617,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       out += RoundUp(b - z.a, 4);
       col += r.cols;
       spans.push_back({out, shift});
-      if (layout || spec_rows) max_feat_cols = std::max(max_feat_cols, r.cols);
+      if (layout || spec_rows || front_rows) max_feat_cols = std::max(max_feat_cols, r.cols);
     }
     woff += seg; upl += feats ? (int64_t)m * D : new_len;
     if (!layout) raw += m;
@@ -488,7 +631,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   const bool staging_fits = woff <= s->wave_cap && upl <= upl_cap && native_total <= s->native_cap &&
                             (!s->rows_area || s->rows_area + raw * D <= s->upload_cap);
   const bool rows_fit = raw <= c.max_frames && RoundUp(out, kTileF16) <= c.max_cols && col <= c.max_cols;
-  if (!staging_fits || !rows_fit || (n_back > 0 && !s->d_feat_hist))
+  if (!staging_fits || !rows_fit || ((n_back > 0 || (!sliding && n_front > 0)) && !s->d_feat_hist))
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
   // A front-end spec at D != 40: the back block (taken last first) moves up behind the front one, as told above.
   if (s->rows_area) {
@@ -510,7 +653,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     Slot &z = s->slots[r.slot];
     if (z.kind >= 0) {                   // pushed frames, frame-major
       if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * D);
-      if (r.m && (z.kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins)) z.hist_par ^= 1;    // the step writes the other history buffer
+      if (r.m && (z.kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins || !sliding)) z.hist_par ^= 1;    // the step writes the other history buffer
     } else if (z.tab && r.new_len) {
       // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
       const ResampleTable &t = z.tab->host;
@@ -531,7 +674,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     if (z.kind < 0) {
       z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
       z.tail_par ^= 1;
-      if (s->rows_area && r.m) z.hist_par ^= 1;     // laid out by StreamFeatureLayoutKernel: the step writes the other history buffer
+      if ((s->rows_area || !sliding) && r.m) z.hist_par ^= 1;     // laid out by StreamFeatureLayoutKernel: the step writes the other history buffer
     }
     z.n = r.n_old + r.m;
     z.a = r.b;
@@ -583,9 +726,32 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
       LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_upload + s->rows_area, c.stream);
     }
-    if (max_m > 0 || chain_pushed > 0)
+    if ((max_m > 0 || chain_pushed > 0) && sliding)
       LaunchStreamCmvnChain(d_recs, n_recs, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
+    else if ((max_m > 0 || chain_pushed > 0) && nmode != PK_MI355_NORM_NONE)
+      LaunchStreamNorm(d_recs, n_recs, D, s->d_upload, NormState(s), c.stream);
     LaunchStreamFeatureLayout(d_recs, n_recs, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
+  } else if (!sliding) {
+    // A norm spec on every other object: the audio records' rows (40-dim: FbankKernel's or the spec's kernel's, in d_rows)
+    // and the back records' (RAW ones normalised where they were pushed) each through StreamNormKernel -- mode none:
+    // through nothing -- and the layout.
+    if (n_audio > 0) {
+      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
+      if (s->d_any)
+        LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_rows, c.stream);
+      else
+        LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
+    }
+    if (n_front > 0) {
+      if (max_m > 0 && nmode != PK_MI355_NORM_NONE) LaunchStreamNorm(d_recs, n_front, D, s->d_rows, NormState(s), c.stream);
+      LaunchStreamFeatureLayout(d_recs, n_front, max_feat_cols, s->d_rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
+    }
+    if (n_back > 0) {
+      if (chain_pushed > 0 && nmode != PK_MI355_NORM_NONE)
+        LaunchStreamNorm(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, NormState(s), c.stream);
+      LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
+                                c.d_yt, c.ldy, c.stream);
+    }
   } else {
     // Every other object, as ever.  A step of audio slots alone: assembly, fbank (the spec's kernel on a spec'd 40-dim
     // object, into the same rows) and StreamCmvnKernel over the n_front front records.  RAW slots at 40 ride along with an

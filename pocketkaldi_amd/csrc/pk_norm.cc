@@ -1,5 +1,6 @@
 // pk_norm.cc -- the normalisation spec on the host (pk_norm.h): the check, the speaker records'
-// finalisation and the whole rule for one matrix.  No HIP: g++ builds it, into the library and into tests/cpp/norm_test.cc.
+// finalisation and the whole rule for one matrix; and online CMVN: its check and the whole rule for
+// one matrix.  No HIP: g++ builds it, into the library and into tests/cpp/norm_test.cc and online_cmvn_test.cc.
 #include "pk_norm.h"
 
 #include <cmath>
@@ -47,9 +48,88 @@ int FinalizeSpeakerStats(const double *stats, int num_utts, int dim, bool norm_m
   return 0;
 }
 
+int CheckOnlineSpec(const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats, int dim) {
+  if (!spec) return Fail(PK_MI355_E_INVALID, "null argument");
+  const pk_mi355_online_cmvn_spec_t &s = *spec;
+  if (s.cmn_window < 1 || s.cmn_window > kMaxCmnWindow)
+    return Fail(PK_MI355_E_INVALID, "online cmvn spec: cmn_window %d is outside [1, %d]", s.cmn_window, kMaxCmnWindow);
+  if (s.speaker_frames < 0) return Fail(PK_MI355_E_INVALID, "online cmvn spec: speaker_frames %d is negative", s.speaker_frames);
+  if (s.global_frames < 0) return Fail(PK_MI355_E_INVALID, "online cmvn spec: global_frames %d is negative", s.global_frames);
+  if (s.norm_vars != 0 && s.norm_vars != 1) return Fail(PK_MI355_E_INVALID, "online cmvn spec: norm_vars %d is neither 0 nor 1", s.norm_vars);
+  if (s.global_frames > 0) {
+    if (!global_stats) return Fail(PK_MI355_E_INVALID, "online cmvn spec: global_frames %d needs the global statistics", s.global_frames);
+    if (dim <= 0) return Fail(PK_MI355_E_INVALID, "online cmvn: dimension %d", dim);
+    const double n = global_stats[dim];
+    if (!std::isfinite(n) || !(n > 0.0))
+      return Fail(PK_MI355_E_INVALID, "online cmvn spec: global_frames %d with global statistics whose count %g is not positive and finite", s.global_frames, n);
+  }
+  return 0;
+}
+
+int CheckOnlineSpeakerCounts(const double *stats, int num_utts, int dim) {
+  if (num_utts > 0 && !stats) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (dim <= 0) return Fail(PK_MI355_E_INVALID, "speaker statistics: dimension %d", dim);
+  const size_t rec = 2 * ((size_t)dim + 1);
+  for (int u = 0; u < num_utts; ++u) {
+    const double n = stats[u * rec + dim];
+    if (!std::isfinite(n) || n < 0.0)
+      return Fail(PK_MI355_E_INVALID, "speaker statistics of utterance %d: the count %g is negative or not finite", u, n);
+  }
+  return 0;
+}
+
 }  // namespace pknorm
 
 extern "C" {
+
+int pk_mi355_online_cmvn_check(const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats, int dim) {
+  return pknorm::CheckOnlineSpec(spec, global_stats, dim);
+}
+
+int pk_mi355_online_cmvn_apply(const pk_mi355_online_cmvn_spec_t *spec, const float *x, int num_frames, int dim, const double *global_stats,
+                               const double *speaker_stats, float *y, double *state_out) {
+  using namespace pknorm;
+  if (int rc = CheckOnlineSpec(spec, global_stats, dim)) return rc;
+  if (num_frames < 0 || dim <= 0) return Fail(PK_MI355_E_INVALID, "bad shape (%d frames of %d features)", num_frames, dim);
+  if (num_frames > 0 && (!x || !y)) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (speaker_stats)
+    if (int rc = CheckOnlineSpeakerCounts(speaker_stats, 1, dim)) return rc;
+  const size_t T = (size_t)num_frames, D = (size_t)dim, W = (size_t)spec->cmn_window;
+  const bool vars = spec->norm_vars != 0;
+  const bool glob = spec->global_frames > 0;
+  std::vector<double> state(2 * (D + 1), 0.0);
+  for (size_t d = 0; d < D; ++d) {
+    OnlinePrior p;
+    p.window = (double)spec->cmn_window;
+    p.speaker_frames = (double)spec->speaker_frames;
+    p.speaker_count = speaker_stats ? speaker_stats[D] : 0.0;
+    p.spk0 = speaker_stats ? speaker_stats[d] : 0.0;
+    p.spk1 = speaker_stats ? speaker_stats[D + 1 + d] : 0.0;
+    p.global_frames = (double)spec->global_frames;
+    p.global_count = glob ? global_stats[D] : 0.0;
+    p.glob0 = glob ? global_stats[d] : 0.0;
+    p.glob1 = glob ? global_stats[D + 1 + d] : 0.0;
+    double S0 = 0.0, S1 = 0.0;
+    for (size_t t = 0; t < T; ++t) {
+      const double v = (double)x[t * D + d];
+      S0 = S0 + v;
+      S1 = S1 + v * v;
+      if (t >= W) {
+        const double o = (double)x[(t - W) * D + d];
+        S0 = S0 - o;
+        S1 = S1 - o * o;
+      }
+      float offs, scale;
+      OnlineCmvnFinalize(S0, S1, (double)(t + 1), p, vars, &offs, &scale);
+      y[t * D + d] = NormApply(x[t * D + d], offs, scale, vars);
+    }
+    state[d] = S0;
+    state[D + 1 + d] = S1;
+  }
+  state[D] = (double)num_frames;
+  if (state_out) for (size_t i = 0; i < state.size(); ++i) state_out[i] = state[i];
+  return 0;
+}
 
 int pk_mi355_norm_check(const pk_mi355_norm_spec_t *spec) { return pknorm::CheckSpec(spec); }
 

@@ -10,8 +10,11 @@
 // Feature slots enter behind the front-end: RAW rows are copied to where FbankKernel would have
 // written them (StreamRawRowsKernel) and StreamCmvnKernel runs on them unchanged; NORMALIZED frames of any dimension
 // are laid out by StreamFeatureLayoutKernel, which carries the left context in two history buffers used in turn.
+// Under a normalisation spec other than the sliding rule audio and RAW rows go through
+// StreamNormKernel and StreamFeatureLayoutKernel instead of StreamCmvnKernel / StreamCmvnChainKernel.
 #include <hip/hip_runtime.h>
 
+#include "pk_norm_kernel.h"
 #include "pk_score.h"
 
 using namespace pkhost;
@@ -254,11 +257,126 @@ __global__ __launch_bounds__(kWave) void StreamCmvnChainKernel(const StreamRec *
   if (live) sums[(int64_t)r.slot * D + d] = s;
 }
 
+// Audio and RAW slots of a scorer whose normalisation spec is `speaker` or online CMVN, in
+// StreamCmvnChainKernel's place and shape: one wavefront per (record, block of 64 features), lane = feature, the slot's m
+// fresh rows normalised IN PLACE at rows + row_off; StreamFeatureLayoutKernel then lays the record out.  A lane owns
+// its feature's column of the rows, of the ring and of the two pairs of sums.
+//   Both modes: total[slot] gains every frame's value and square in double, t ascending -- the utterance rule's order,
+//     so the record of a whole slot is the batch scorer's norm_stats of the whole input.
+//   speaker: y = NormApply(x, the slot's finalised offset and scale).
+//   online CMVN: the batch kernel's lines (norm.hip) with the state carried from step to step -- the window sums in
+//     win[slot], the raw rows still inside the window in ring[slot][t % W] (frame t - W leaves from the position frame
+//     t takes).  Frames are taken kSNormAhead at a time, the next group's rows and ring entries loaded into registers
+//     ahead of the current group's chain and handed to it through LDS (lane-private columns: no barrier).  A ring entry
+//     that this very launch writes (t - W >= n_old: a window shorter than the step) is not loaded ahead: the chain reads
+//     it where it needs it, behind the lane's own store.  The ring positions a group writes and the positions loaded
+//     ahead for the next group differ: they could meet only for W <= 2 kSNormAhead - 1, where the entry is this launch's.
+// Addresses are formed from i clamped into [0, m) and d clamped into [d0, D).
+constexpr int kSNormAhead = 8;
+
+__global__ __launch_bounds__(kWave) void StreamNormKernel(const StreamRec *__restrict__ recs, int D, float *rows, pkmi::StreamNormState st) {
+  __shared__ float s_cur[kSNormAhead][kWave], s_old[kSNormAhead][kWave];
+  const StreamRec r = recs[blockIdx.x];
+  if (r.kind == PK_MI355_FEATS_NORMALIZED || r.m <= 0) return;
+  const int lane = threadIdx.x;
+  const int d0 = blockIdx.y * kWave;
+  const bool live = d0 + lane < D;
+  const int d = live ? d0 + lane : d0;
+  const bool vars = st.norm_vars != 0;
+  const int m = r.m, W = st.window;
+  float *x = rows + r.row_off + d;
+  double *tot = st.total + (int64_t)r.slot * 2 * D + d;
+  double t0s = r.n_old > 0 ? tot[0] : 0.0, t1s = r.n_old > 0 ? tot[D] : 0.0;
+  auto row = [&](int i) { return (int64_t)(i < m ? i : m - 1) * D; };
+  if (st.mode == PK_MI355_NORM_SPEAKER) {
+    const float *tab = st.table + (int64_t)r.slot * 2 * D;
+    const float offs = tab[d], scale = tab[D + d];
+    float cur[kSNormAhead];
+#pragma unroll
+    for (int k = 0; k < kSNormAhead; ++k) cur[k] = x[row(k)];
+    for (int i0 = 0; i0 < m; i0 += kSNormAhead) {
+      float nxt[kSNormAhead];
+#pragma unroll
+      for (int k = 0; k < kSNormAhead; ++k) nxt[k] = x[row(i0 + kSNormAhead + k)];
+#pragma unroll
+      for (int k = 0; k < kSNormAhead; ++k)
+        if (i0 + k < m) {
+          const double v = static_cast<double>(cur[k]);
+          t0s = t0s + v;
+          t1s = t1s + v * v;
+          if (live) x[row(i0 + k)] = pknorm::NormApply(cur[k], offs, scale, vars);
+        }
+#pragma unroll
+      for (int k = 0; k < kSNormAhead; ++k) cur[k] = nxt[k];
+    }
+    if (live) { tot[0] = t0s; tot[D] = t1s; }
+    return;
+  }
+  pknorm::OnlinePrior p;
+  p.window = static_cast<double>(W);
+  p.speaker_frames = static_cast<double>(st.speaker_frames);
+  p.global_frames = st.global_frames > 0 ? static_cast<double>(st.global_frames) : 0.0;
+  p.global_count = st.global_frames > 0 ? st.glob[D] : 0.0;
+  p.glob0 = st.global_frames > 0 ? st.glob[d] : 0.0;
+  p.glob1 = st.global_frames > 0 ? st.glob[D + 1 + d] : 0.0;
+  const double *rec = st.spk + (int64_t)r.slot * 2 * (D + 1);
+  p.speaker_count = rec[D];
+  p.spk0 = rec[d];
+  p.spk1 = rec[D + 1 + d];
+  double *win = st.win + (int64_t)r.slot * 2 * D + d;
+  float *rh = st.ring + (int64_t)r.slot * W * D + d;
+  double S0 = r.n_old > 0 ? win[0] : 0.0, S1 = r.n_old > 0 ? win[D] : 0.0;
+  auto ring = [&](int i) { return (int64_t)((r.n_old + (i < m ? i : m - 1)) % W) * D; };
+  // frame t - W of fresh frame i was stored by an earlier launch: its ring entry may be loaded ahead
+  auto settled = [&](int i) { return i < m && r.n_old + i >= W && i < W; };
+  float cur[kSNormAhead], old[kSNormAhead];
+#pragma unroll
+  for (int k = 0; k < kSNormAhead; ++k) { cur[k] = x[row(k)]; old[k] = settled(k) ? rh[ring(k)] : 0.0f; }
+  for (int i0 = 0; i0 < m; i0 += kSNormAhead) {
+#pragma unroll
+    for (int k = 0; k < kSNormAhead; ++k) { s_cur[k][lane] = cur[k]; s_old[k][lane] = old[k]; }
+#pragma unroll
+    for (int k = 0; k < kSNormAhead; ++k) {                          // the next group's loads, ahead of this group's chain
+      const int i = i0 + kSNormAhead + k;
+      cur[k] = x[row(i)];
+      old[k] = settled(i) ? rh[ring(i)] : 0.0f;
+    }
+    const int n = m - i0 < kSNormAhead ? m - i0 : kSNormAhead;
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+      const int i = i0 + k, t = r.n_old + i;
+      const float xt = s_cur[k][lane];
+      const double v = static_cast<double>(xt);
+      t0s = t0s + v;
+      t1s = t1s + v * v;
+      S0 = S0 + v;
+      S1 = S1 + v * v;
+      if (t >= W) {
+        const double o = static_cast<double>(i < W ? s_old[k][lane] : rh[ring(i)]);     // (i >= W: this launch's own store)
+        S0 = S0 - o;
+        S1 = S1 - o * o;
+      }
+      float offs, scale;
+      pknorm::OnlineCmvnFinalize(S0, S1, static_cast<double>(t + 1), p, vars, &offs, &scale);
+      if (live) {
+        rh[ring(i)] = xt;
+        x[row(i)] = pknorm::NormApply(xt, offs, scale, vars);
+      }
+    }
+  }
+  if (live) { win[0] = S0; win[D] = S1; tot[0] = t0s; tot[D] = t1s; }
+}
+
 }  // namespace
 
 // ================================================================== launchers (pk_score.h)
 
 namespace pkmi {
+
+void LaunchStreamNorm(const StreamRec *recs, int n, int dim, float *rows, const StreamNormState &st, hipStream_t stream) {
+  if (n <= 0 || dim <= 0) return;
+  hipLaunchKernelGGL(StreamNormKernel, dim3(n, (dim + kWave - 1) / kWave), dim3(kWave), 0, stream, recs, dim, rows, st);
+}
 
 void LaunchStreamAssemble(const StreamRec *recs, int n, const float *upload, float *tails, float *wave, hipStream_t stream) {
   hipLaunchKernelGGL(StreamAssembleKernel, dim3(n), dim3(256), 0, stream, recs, upload, tails, wave);

@@ -3,6 +3,8 @@
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
                                         [--frontend key=value,...]
                                         [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]]
+                                        [--cmvn mode=online,cmn_window=...,speaker_frames=...,global_frames=...,norm_vars=...
+                                         [--cmvn-global RX] [--cmvn-stats RX [--utt2spk FILE]]]
                                         [--online [--chunk-ms N] [--partials] [--commit]
                                          [--endpoint-silence 0,1,2 [--endpoint-rule must,trail_s,relcost,len_s ...]]]
     python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...>
@@ -41,8 +43,15 @@ archives, --frontend.  Mode speaker needs --cmvn-stats RX, an archive or script 
 (compute-cmvn-stats' output; ark:<path>, scp:<path> or a path), keyed by what this program prints in front of an
 utterance's line -- or by speaker, with --utt2spk FILE ("<utterance> <speaker>" per line).  An utterance or a speaker
 without an entry is refused with its name and the usage text, as are --cmvn-stats without mode=speaker and mode=speaker
-without --cmvn-stats.  With --features normalized the matrices are ready for the splice and no norm applies.  The
-online objects do not take a norm spec yet: --cmvn with --online is refused with the usage text.
+without --cmvn-stats.  With --features normalized the matrices are ready for the splice and no norm applies.  With
+--online the modes none, speaker and online (below) run on the online objects and print what the batch form prints;
+mode=utterance with --online is refused with the usage text: an utterance's statistics do not exist while it is live.
+
+--cmvn mode=online,cmn_window=600,speaker_frames=600,global_frames=200,norm_vars=true|false takes a model that was trained
+on apply-cmvn-online's features (pk.OnlineCmvnSpec): Kaldi's online CMVN over every whole
+utterance, on the batch scorer or, with --online, live.  --cmvn-global RX names the 2 x (D + 1) global statistics (pk.kaldi_cmvn_stats) the window
+is smoothed with; global_frames > 0 without it is refused with the usage text.  --cmvn-stats and --utt2spk give the
+speakers' statistics as for mode=speaker; here they are optional.
 
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
@@ -70,6 +79,7 @@ RESERVE = 32
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
           "[--frontend key=value,...] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
+          "[--cmvn mode=online,cmn_window=...,speaker_frames=...,global_frames=...,norm_vars=... [--cmvn-global RX] [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
           "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--online ...]")
@@ -84,11 +94,21 @@ def usage():
 class Norm:
     """--cmvn and what goes with it: the spec, and for mode speaker the statistics by key and the utterance-to-speaker map."""
 
-    def __init__(self, spec, stats=None, utt2spk=None):
-        self.spec, self.stats, self.utt2spk = spec, stats, utt2spk
+    def __init__(self, spec, stats=None, utt2spk=None, global_stats=None):
+        self.spec, self.stats, self.utt2spk, self.global_stats = spec, stats, utt2spk, global_stats
 
     def apply(self, rec):
-        rec.batch.set_norm(self.spec)
+        if isinstance(self.spec, pk.OnlineCmvnSpec):
+            rec.batch.set_norm(self.spec, self.global_stats)
+        else:
+            rec.batch.set_norm(self.spec)
+
+    def apply_online(self, rec):
+        """The same spec on an OnlineRecognizer's scorer."""
+        if isinstance(self.spec, pk.OnlineCmvnSpec):
+            rec.scorer.set_norm(self.spec, self.global_stats)
+        else:
+            rec.scorer.set_norm(self.spec)
 
     def speaker_stats(self, names):
         """The records of these utterances, or None when the mode takes none.  UsageError names a missing key."""
@@ -124,26 +144,43 @@ def take_value(argv, flag):
 
 
 def parse_norm_flags(argv):
-    """--cmvn, --cmvn-stats and --utt2spk out of argv -> a Norm, or None without --cmvn.  UsageError says what is wrong."""
+    """--cmvn, --cmvn-global, --cmvn-stats and --utt2spk out of argv -> a Norm, or None without --cmvn.  UsageError says
+    what is wrong."""
     text, stats_rx, utt2spk_file = take_value(argv, "--cmvn"), take_value(argv, "--cmvn-stats"), take_value(argv, "--utt2spk")
+    global_rx = take_value(argv, "--cmvn-global")
     if text is None:
         if stats_rx is not None or utt2spk_file is not None:
-            raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker")
+            raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker or mode=online")
+        if global_rx is not None:
+            raise UsageError("--cmvn-global goes with --cmvn mode=online")
         return None
-    if "--online" in argv:
-        raise UsageError("--cmvn: the online objects do not take a norm spec yet; use it without --online")
     try:
         spec = pk.parse_norm(text)
-        spec.check()
+        online_cmvn = isinstance(spec, pk.OnlineCmvnSpec)
+        if "--online" in argv and not online_cmvn and spec.mode == pk.NORM_MODES["utterance"]:
+            raise UsageError("--cmvn mode=utterance: the online objects do not take a norm spec yet that needs an utterance's statistics: "
+                             "they do not exist while the utterance is live; use mode=speaker or mode=online, or leave out --online")
+        if not online_cmvn:
+            spec.check()
+        elif spec.global_frames <= 0 or global_rx is not None:      # (global_frames > 0 without --cmvn-global: said below)
+            spec.check(None, 1) if spec.global_frames <= 0 else pk.OnlineCmvnSpec(spec.cmn_window, spec.speaker_frames, 0, spec.norm_vars).check(None, 1)
     except (ValueError, pk.PkError) as e:
         raise UsageError("--cmvn: %s" % e)
-    speaker = spec.mode == pk.NORM_MODES["speaker"]
+    if not online_cmvn and global_rx is not None:
+        raise UsageError("--cmvn-global goes with --cmvn mode=online")
+    if online_cmvn and spec.global_frames > 0 and global_rx is None:
+        raise UsageError("--cmvn mode=online with global_frames > 0 needs --cmvn-global (the global statistics), or global_frames=0")
+    speaker = not online_cmvn and spec.mode == pk.NORM_MODES["speaker"]
     if speaker and stats_rx is None:
         raise UsageError("--cmvn mode=speaker needs --cmvn-stats")
-    if not speaker and (stats_rx is not None or utt2spk_file is not None):
-        raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker")
-    stats = utt2spk = None
-    if speaker:
+    if not speaker and not online_cmvn and (stats_rx is not None or utt2spk_file is not None):
+        raise UsageError("--cmvn-stats and --utt2spk go with --cmvn mode=speaker or mode=online")
+    if online_cmvn and utt2spk_file is not None and stats_rx is None:
+        raise UsageError("--utt2spk goes with --cmvn-stats")
+    stats = utt2spk = global_stats = None
+    if online_cmvn and global_rx is not None:
+        global_stats = pk.kaldi_cmvn_stats(global_rx)
+    if speaker or stats_rx is not None:
         stats = pk.read_cmvn_stats_archive(stats_rx)
         if utt2spk_file is not None:
             utt2spk = {}
@@ -154,11 +191,11 @@ def parse_norm_flags(argv):
                         if len(parts) != 2:
                             raise UsageError("--utt2spk: line %d of %s is not '<utterance> <speaker>'" % (n + 1, utt2spk_file))
                         utt2spk[parts[0]] = parts[1]
-    return Norm(spec, stats, utt2spk)
+    return Norm(spec, stats, utt2spk, global_stats)
 
 
 def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, endpoint=None,
-                     pieces=None, frontend=None):
+                     pieces=None, frontend=None, norm=None):
     """Every wave through a slot of an OnlineRecognizer, `chunk_ms` milliseconds per step, MAX_UTTS waves at a time.
     endpoint: (silence pdfs, rules or None) turns endpointing on; pieces[u] is then wave u's list of Utterance.
     -> (the results in order, the symbol names by word id)"""
@@ -172,14 +209,18 @@ def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, part
             rec.decoder.set_commit(True)
         if endpoint:
             rec.set_endpointing(*endpoint)
-        return stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit, rates, pieces)
+        if norm:
+            norm.apply_online(rec)
+        return stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit, rates, pieces, norm=norm)
     finally:
         rec.destroy()
 
 
-def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, pieces=None, feature_kind=None):
+def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, pieces=None, feature_kind=None,
+                 norm=None):
     """feature_kind ("raw" / "normalized"): `waves` are [T][D] feature matrices, fed max(1, chunk_ms // 10) frames a step
-    through open_features / push_features; a frame is 10 ms."""
+    through open_features / push_features; a frame is 10 ms.  norm: the Norm whose speaker statistics the slots are opened with."""
+    spk = norm.speaker_stats(files) if norm and feature_kind != "normalized" else None
     rates = [100] * len(waves) if feature_kind else rates or [16000] * len(waves)       # (units per second: frames, or samples)
     if reference_softmax:
         rec.am.set_softmax("reference")
@@ -188,7 +229,8 @@ def stream_waves(rec, files, waves, chunk_ms, reference_softmax, partials, commi
         group = list(range(first, min(first + MAX_UTTS, len(waves))))
         pos, shown = {u: 0 for u in group}, {u: ("", "") if commit else "" for u in group}
         for u in group:
-            rec.open_features(u - first, feature_kind) if feature_kind else rec.open(u - first, rates[u])
+            record = spk[u] if spk else None
+            rec.open_features(u - first, feature_kind, record) if feature_kind else rec.open(u - first, rates[u], record)
         live = set(group)
         while live:
             closing = []
@@ -306,7 +348,7 @@ def main(argv):
         if "--online" in flags:
             results, names = recognize_online(model_file, files, waves, chunk_ms, "--reference-softmax" in flags,
                                               "--partials" in flags, "--commit" in flags, rates, endpoint,
-                                              pieces if endpoint else None, frontend)
+                                              pieces if endpoint else None, frontend, norm)
         else:
             sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
@@ -399,6 +441,8 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
                         rec.decoder.set_commit(True)
                     if endpoint:
                         rec.set_endpointing(*endpoint)
+                    if norm:
+                        norm.apply_online(rec)
                 else:
                     rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend)
                     if "--reference-softmax" in flags:
@@ -409,7 +453,7 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
             pieces = {} if endpoint else None
             if online:
                 results, names = stream_waves(rec, files, feats, chunk_ms, "--reference-softmax" in flags, "--partials" in flags,
-                                              "--commit" in flags, None, pieces, feature_kind=kind)
+                                              "--commit" in flags, None, pieces, feature_kind=kind, norm=norm)
             else:
                 spk = norm.speaker_stats(files) if norm and kind == "raw" else None
                 results, names = rec.process_features(feats, kind, spk), rec.symbols

@@ -2,7 +2,8 @@
 Prints ONE JSON line and writes it to profiles/norm_bench.json.
 
 256 utterances x 998 frames at D = 80 through the tiny model, fed as RAW features to one scorer: the PK_MI355_K_CMVN
-slot of score() (per-stage timing on) for utterance mode with variance, speaker mode, `none`, the sliding rule, and the
+slot of score() (per-stage timing on) for utterance mode with variance, speaker mode, online CMVN at its defaults with
+and without variance, `none`, the sliding rule, and the
 same utterances fed as NORMALIZED features -- alternating, medians of five.  Every slot holds FeatureLayoutKernel; the
 NORMALIZED leg holds nothing else, so a leg's kernel is its slot minus that one.  The yardstick is the sliding leg's
 CmvnChainKernel in the same session: serial in t like NormKernel, which reads the rows twice.
@@ -56,15 +57,18 @@ def batch_leg(utts, frames, D, steps):
     rec = [rec4[u % 4] for u in range(utts)]
     fs = pk.FeatureScorer(am, utts, utts * frames, global_stats=g)
 
+    glob = sum(rec4)                                       # online CMVN's global record
+
     def feed(spec, kind="raw", stats=None):
         def run():
-            fs.set_norm(spec)
+            fs.set_norm(spec, glob) if isinstance(spec, pk.OnlineCmvnSpec) else fs.set_norm(spec)
             if stats is not None:
                 fs.set_speaker_stats(stats)
             fs.set_features(raw, kind)
         return run
 
     feeds = {"utterance_vars": feed(pk.NormSpec("utterance", True, True)), "speaker_vars": feed(pk.NormSpec("speaker", True, True), stats=rec),
+             "online_cmvn": feed(pk.OnlineCmvnSpec(), stats=rec), "online_cmvn_vars": feed(pk.OnlineCmvnSpec(norm_vars=True), stats=rec),
              "none": feed(pk.NormSpec("none")), "sliding": feed(pk.NormSpec()), "normalized": feed(pk.NormSpec(), "normalized")}
     med, every, launches = slots(fs, feeds, steps)
     total = int(fs.total_frames())
@@ -76,6 +80,9 @@ def batch_leg(utts, frames, D, steps):
     feeds["speaker_vars"]()
     fs.score(0.1)
     same = same and got.tobytes() == fs.fetch_cmvn(utts - 1).tobytes()
+    feeds["online_cmvn_vars"]()                            # online CMVN is its host rule
+    fs.score(0.1)
+    same = same and fs.fetch_cmvn(utts - 1).tobytes() == pk.cmvn_online(raw[utts - 1], pk.OnlineCmvnSpec(norm_vars=True), glob, rec[utts - 1]).tobytes()
     fs.close()
     am.close()
     layout = med["normalized"]
@@ -84,6 +91,7 @@ def batch_leg(utts, frames, D, steps):
                 cmvn_slot_ms=med, cmvn_slot_ms_all=every, cmvn_slot_launches=launches, kernel_ms=kernel,
                 waves=utts * ((D + 63) // 64), norm_over_chain=round(kernel["utterance_vars"] / max(kernel["sliding"], 1e-6), 3),
                 speaker_over_chain=round(kernel["speaker_vars"] / max(kernel["sliding"], 1e-6), 3),
+                online_cmvn_over_chain=round(kernel["online_cmvn_vars"] / max(kernel["sliding"], 1e-6), 3),
                 norm_ns_per_frame_of_a_wave=round(kernel["utterance_vars"] * 1e6 / frames, 2), same_rows=bool(same))
 
 

@@ -46,6 +46,11 @@ normalized leg of the same dimension is the step without it.  profiles/cmvn_any_
 with that front-end and model S at the spec's dimension; the statistics are the means of the first
 stream's features at the spec, count 2500, and the check is against BatchScorer(frontend=spec).
 profiles/frontend_stream_bench.json holds those legs beside the plain audio leg.
+
+--cmvn SPEC (pk.parse_norm's text: mode=none, mode=speaker,norm_vars=true, mode=online,norm_vars=true, ...) sets that
+normalisation on the scorer, with stream 0's own statistics as the global record and as every
+slot's speaker record; the check is against the batch scorer under the same spec.  profiles/stream_bench_cmvn_*.json
+hold the default leg and one leg per mode.
 """
 import argparse
 import json
@@ -63,6 +68,12 @@ import pocketkaldi_amd as pk  # noqa: E402
 from pocketkaldi_amd import synth  # noqa: E402
 
 
+def bs_rows(bs):
+    """The front-end's rows of the check's one utterance (a score in the scorer's current mode computes them)."""
+    bs.score(0.1)
+    return bs.fetch_fbank(0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -78,7 +89,11 @@ def main():
                     help="with --features: synthetic features of this dimension (5 N(0, 1) + 3; raw: statistics of count 2500, "
                          "StreamCmvnChainKernel's path, DESIGN.md section 15) through a small model; checked against FeatureScorer")
     ap.add_argument("--frontend", default=None, help="a front-end spec, key=value,... (audio streams; model S at its dimension)")
+    ap.add_argument("--cmvn", default=None, help="a normalisation spec for the scorer, pk.parse_norm's text (mode=none | speaker | online,...; "
+                    "DESIGN.md section 20); the global and the speakers' records are stream 0's own statistics")
     a = ap.parse_args()
+    if a.cmvn is not None and a.features == "normalized":
+        ap.error("--cmvn takes audio or raw features")
     spec = None
     if a.frontend is not None:
         if a.features or a.feat_dim != 40:
@@ -131,6 +146,22 @@ def main():
         sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None)
     else:
         sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk)
+    norm = record0 = None
+    if a.cmvn is not None:
+        norm = pk.parse_norm(a.cmvn)
+        if feats:
+            rows0 = feats[0]
+        else:
+            bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec)
+            bs.set_waves(waves[:1])
+            bs.score(0.1)
+            rows0 = bs.fetch_fbank(0)
+            bs.close()
+        record0 = pk.cmvn_normalize(rows0, pk.NormSpec("utterance", True, True))[1]
+        online_cmvn = isinstance(norm, pk.OnlineCmvnSpec)
+        sc.set_norm(norm, record0) if online_cmvn else sc.set_norm(norm)
+        if not online_cmvn and norm.mode != pk.NORM_MODES["speaker"]:
+            record0 = None                                     # (no records in mode none)
     dec = None
     if a.decode:
         import tempfile
@@ -151,7 +182,7 @@ def main():
 
     def run(record, nsteps=nsteps):
         for s in range(a.streams):
-            sc.open_features(s, a.features) if feats else sc.open(s)
+            sc.open_features(s, a.features, speaker_stats=record0) if feats else sc.open(s, speaker_stats=record0)
             if dec:
                 dec.open(s)
         walls, frames, rows0 = [], 0, []
@@ -204,12 +235,17 @@ def main():
     else:
         bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec)
         bs.set_waves(waves[:1])
+    if norm is not None:
+        bs.set_norm(norm, pk.cmvn_normalize(feats[0] if feats else bs_rows(bs), pk.NormSpec("utterance", True, True))[1]) \
+            if isinstance(norm, pk.OnlineCmvnSpec) else bs.set_norm(norm)
+        if record0 is not None:
+            bs.set_speaker_stats([record0])
     bs.score(0.1)
     ok = np.concatenate(rows0).tobytes() == bs.fetch(0).log_prob().tobytes()
     rec = {
         "streams": a.streams, "seconds": a.seconds, "chunk_ms": a.chunk_ms, "steps": len(walls),
         "input": "features, %s, %d frames a push" % (a.features, chunk) if feats else "audio",
-        "model": model_name,
+        "model": model_name, "cmvn": a.cmvn,
         "device": torch.cuda.get_device_name(0),
         "step_ms": {"median": float(np.median(walls_ms)), "p90": float(np.percentile(walls_ms, 90)),
                     "max": float(walls_ms.max())},
