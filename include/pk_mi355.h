@@ -520,6 +520,57 @@ int pk_mi355_online_cmvn_apply(const pk_mi355_online_cmvn_spec_t *spec, const fl
  * the other modes) and 16 * (feat_dim + 1) * (max_utts + 1) bytes of statistics.                                    */
 int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats);
 
+/* ---- Delta features: Kaldi's add-deltas between the normalisation and the splice of a batch
+ * scorer, for models whose first layer expects (order + 1) x the dimension the front-end, the statistics and the
+ * normalisation work at (13 MFCC -> 39, 40 fbank -> 120).  Restated from Kaldi's DeltaFeatures; not compared with a
+ * Kaldi binary (Kaldi leaves the axpy to BLAS, so agreement with it is within rounding).  No energy; the online
+ * objects do not have deltas yet.                                                                                  */
+typedef struct pk_mi355_deltas_spec {
+  int32_t order;    /* 1 .. 3 (Kaldi's default 2) */
+  int32_t window;   /* 1 .. 8 (Kaldi's default 2) */
+} pk_mi355_deltas_spec_t;
+/* Base dimension Db -> output dimension (order + 1) * Db: block 0 the features, block i their i-th differences.
+ *
+ * Scales, in float: s[0] = [1.0f].  For i = 1 .. order: s[i] has len(s[i-1]) + 2 * window entries, all +0.0f at first;
+ * with po = (len(s[i-1]) - 1) / 2, for j = -window .. window ascending and inside that for k = -po .. po ascending:
+ * s[i][j + k + po + window] += (float)j * s[i-1][k + po], a rounded product and a rounded add; then every entry is
+ * multiplied by (float)(1.0 / (double)normalizer), normalizer the sum of j * j accumulated in float.
+ *
+ * Apply, every column on its own, T frames: block i of output frame t is acc = +0.0f; for j = -M_i .. M_i ascending
+ * (M_i = i * window): if s[i][j + M_i] != 0.0f then acc = acc + (s[i][j + M_i] * x[clamp(t + j, 0, T - 1)]), a rounded
+ * product and a rounded add, no fma.  Taps whose scale is zero are skipped, as Kaldi skips them (an inf at the centre
+ * of a first-order delta does not become NaN).  Block 0 is therefore +0.0f + 1.0f * x: -0.0 comes out as +0.0, NaN and
+ * inf pass through.  No frames: nothing happens.  A NaN spoils its own column only, within M_i frames of it, in its own
+ * utterance.
+ *
+ * pk_mi355_deltas_check: PK_MI355_E_INVALID with a text that names the field -- a null spec, order outside [1, 3],
+ * window outside [1, 8].  pk_mi355_deltas_dim: (order + 1) * base_dim, or the negative code.  pk_mi355_deltas_scales:
+ * the table, [order + 1][2 * order * window + 1] floats, row i centred (entry j of s[i] at column order * window + j)
+ * and zero around it.  pk_mi355_deltas_apply: the rule on the host for one matrix x [T][base_dim] ->
+ * y [T][(order + 1) * base_dim] (not in place): the restatement the GPU path is held to.  Host only, all four.      */
+int pk_mi355_deltas_check(const pk_mi355_deltas_spec_t *spec);
+int pk_mi355_deltas_dim(const pk_mi355_deltas_spec_t *spec, int base_dim);
+int pk_mi355_deltas_scales(const pk_mi355_deltas_spec_t *spec, float *table);
+int pk_mi355_deltas_apply(const pk_mi355_deltas_spec_t *spec, const float *x, int num_frames, int base_dim, float *y);
+/* A batch scorer with deltas in front of the splice.  Db = pk_mi355_am_feat_dim(am) / (order + 1), which must divide
+ * exactly.  frontend: a spec of Db features (then capacity counts 16 kHz samples, and global_stats is required), or
+ * NULL: features only (capacity counts frames; global_stats may be NULL, as on pk_mi355_features_batch_create).
+ * global_stats: Db sums and the count; stats_len must be Db + 1.  PK_MI355_E_INVALID, naming both numbers, for a
+ * feat_dim that (order + 1) does not divide, a front-end of another dimension than Db, another stats_len; the deltas
+ * and front-end specs are refused in their checks' words; F16X3 / F16 need feat_dim to be a multiple of 8.
+ * Stage order: front-end or the caller's PK_MI355_FEATS_RAW rows [T][Db] -> the normalisation at Db (any spec of
+ * pk_mi355_norm_set or pk_mi355_norm_set_online_cmvn; SLIDING at any Db, 40 too, runs the chain kernel, whose columns
+ * are the 40-dim path's bit for bit) -> DeltaKernel into a [max_frames][feat_dim] staging of its own, inside the
+ * PK_MI355_K_CMVN timing slot -> the layout at feat_dim -> the layers.  On such a batch everything in front of the
+ * deltas is at Db: the RAW rows of pk_mi355_features_set*, fetch_fbank, speaker and global records, fetch_stats.
+ * PK_MI355_FEATS_NORMALIZED features stay "ready for the splice": [T][feat_dim], past the norm and the deltas.
+ * pk_mi355_batch_fetch_cmvn returns what the first layer reads, [T][feat_dim].                                      */
+pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas,
+                                               const pk_mi355_frontend_spec_t *frontend, const float *global_stats,
+                                               int stats_len, int max_utts, int64_t capacity);
+/* Db of a batch made by the entry above; feat_dim on every other batch; 0 for NULL.                                 */
+int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b);
+
 /* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
  * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
  * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is
@@ -1110,6 +1161,13 @@ pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int pre
 pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec,
                                                          int precision, int max_utts, int64_t max_total_samples,
                                                          int64_t trace_capacity);
+/* The same with deltas for a model of (order + 1) * pk_mi355_frontend_dim(frontend_spec)
+ * features: the model file's cmvn_stats holds pk_mi355_frontend_dim + 1 entries, and the batch is
+ * pk_mi355_deltas_batch_create's, whose refusals are this entry's; bad specs are refused first.  process_features with
+ * PK_MI355_FEATS_RAW takes [T][pk_mi355_frontend_dim], with PK_MI355_FEATS_NORMALIZED [T][feat_dim].               */
+pk_mi355_recognizer_t *pk_mi355_deltas_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                       const pk_mi355_deltas_spec_t *deltas_spec, int precision, int max_utts,
+                                                       int64_t max_total_samples, int64_t trace_capacity);
 void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r);
 /* The owned objects: beam, trace gc, softmax mode, f16 calibration and every result getter (words, weight, ok,
  * alignment, word segments) are their existing entries.                                                          */

@@ -332,6 +332,14 @@ class Recognizer {
     r_ = pk_mi355_frontend_recognizer_load(model_file.c_str(), &spec, precision, max_utts, max_total_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // A model of (order + 1) x the spec's feature dimension, deltas behind the normalisation (a FrontendSpec and a
+  // DeltaSpec; pk_mi355_deltas_recognizer_load)
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t &deltas,
+              int precision = PK_MI355_PRECISION_F32, int max_utts = 1, int64_t max_total_samples = 16000 * 60, int64_t trace_capacity = 0) {
+    pk_mi355_recognizer_destroy(r_);
+    r_ = pk_mi355_deltas_recognizer_load(model_file.c_str(), &spec, &deltas, precision, max_utts, max_total_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   // pk_process for n waves at once; out (may be null) receives one Utterance per wave.  rates (may be null: 16000
   // throughout): the sample rate of every wave; the others are converted on the GPU (pk_mi355_recognizer_process_rates)
   Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out, const int *rates = nullptr) {
@@ -512,6 +520,21 @@ struct OnlineCmvnSpec : pk_mi355_online_cmvn_spec_t {
   Status Check(const double *global_stats, int dim) const { return Status::FromLast(pk_mi355_online_cmvn_check(this, global_stats, dim)); }
 };
 
+// Delta features (pk_mi355_deltas_spec_t): Kaldi's add-deltas at its defaults.  Nothing is checked
+// here: the library refuses a bad spec wherever one is used.
+struct DeltaSpec : pk_mi355_deltas_spec_t {
+  explicit DeltaSpec(int order_ = 2, int window_ = 2) { order = order_; window = window_; }
+  Status Check() const { return Status::FromLast(pk_mi355_deltas_check(this)); }
+  int dim(int base_dim) const { return pk_mi355_deltas_dim(this, base_dim); }      // negative: the spec or the dimension is refused
+  // the rule on the host: x [T][base_dim] -> out [T][dim(base_dim)]
+  Status Apply(const float *x, int num_frames, int base_dim, std::vector<float> *out) const {
+    const int d = dim(base_dim);
+    if (d < 0) return Status::FromLast(d);
+    out->assign(static_cast<size_t>(num_frames > 0 ? num_frames : 0) * d, 0.0f);
+    return Status::FromLast(pk_mi355_deltas_apply(this, x, num_frames, base_dim, out->data()));
+  }
+};
+
 // The batched, device-resident scorer (pk_mi355_batch_*): PCM of many utterances -> log-likelihood rows.
 class BatchScorer {
  public:
@@ -526,6 +549,13 @@ class BatchScorer {
       : b_(pk_mi355_frontend_batch_create(am, &spec, global_stats, stats_len, max_utts, max_total_samples)) {
     if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // deltas behind the normalisation (pk_mi355_deltas_batch_create): a model of deltas.dim(spec.dim()) features, the
+  // front-end, the statistics (stats_len = spec.dim() + 1) and the normalisation at BaseDim() = spec.dim()
+  BatchScorer(pk_mi355_am_t *am, const FrontendSpec &spec, const DeltaSpec &deltas, const float *global_stats, int stats_len, int max_utts,
+              int64_t max_total_samples)
+      : b_(pk_mi355_deltas_batch_create(am, &deltas, &spec, global_stats, stats_len, max_utts, max_total_samples)) {
+    if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   ~BatchScorer() { pk_mi355_batch_destroy(b_); }
   BatchScorer(const BatchScorer &) = delete;
   BatchScorer &operator=(const BatchScorer &) = delete;
@@ -538,23 +568,25 @@ class BatchScorer {
   Status Score(float prob_scale) { return Status::FromLast(pk_mi355_batch_score(b_, prob_scale, 1)); }
   int NumFrames(int utt) const { return pk_mi355_batch_num_frames(b_, utt); }
   int FeatDim() const { return pk_mi355_features_dim(b_); }
+  // the dimension in front of the deltas (the front-end's, the statistics'); FeatDim() on a scorer without deltas
+  int BaseDim() const { return pk_mi355_deltas_base_dim(b_); }
   // utterance utt's rows as a host decodable ({ncol = T, nrow = num_pdfs}; release with pk_decodable_destroy)
   Status Fetch(int utt, pk_decodable_t *out) { return Status::FromLast(pk_mi355_batch_fetch(b_, utt, out)); }
-  // the front-end's rows, [T][FeatDim()] floats
+  // the front-end's rows, [T][BaseDim()] floats
   Status FetchFeatures(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_fbank(b_, utt, out)); }
   // what the first layer reads, [T][FeatDim()] floats
   Status FetchNormalized(int utt, float *out) { return Status::FromLast(pk_mi355_batch_fetch_cmvn(b_, utt, out)); }
   // The normalisation between the front-end and the first layer; it holds until it is set again.
   Status SetNorm(const NormSpec &spec) { return Status::FromLast(pk_mi355_norm_set(b_, &spec)); }
-  // Online CMVN instead; global_stats: 2 x (FeatDim() + 1) doubles, or null with global_frames = 0.
+  // Online CMVN instead; global_stats: 2 x (BaseDim() + 1) doubles, or null with global_frames = 0.
   Status SetNorm(const OnlineCmvnSpec &spec, const double *global_stats) {
     return Status::FromLast(pk_mi355_norm_set_online_cmvn(b_, &spec, global_stats));
   }
-  // mode speaker (required) and online CMVN (optional): [num_utts][2][FeatDim() + 1] doubles, consumed by the next Score
+  // mode speaker (required) and online CMVN (optional): [num_utts][2][BaseDim() + 1] doubles, consumed by the next Score
   Status SetSpeakerStats(const double *stats, int num_utts) { return Status::FromLast(pk_mi355_norm_set_speaker_stats(b_, stats, num_utts)); }
-  // the 2 x (FeatDim() + 1) record the last Score computed for utterance utt in mode utterance
+  // the 2 x (BaseDim() + 1) record the last Score computed for utterance utt in mode utterance
   Status NormStats(int utt, std::vector<double> *out) {
-    out->assign(2 * (static_cast<size_t>(FeatDim()) + 1), 0.0);
+    out->assign(2 * (static_cast<size_t>(BaseDim()) + 1), 0.0);
     return Status::FromLast(pk_mi355_norm_fetch_stats(b_, utt, out->data()));
   }
 

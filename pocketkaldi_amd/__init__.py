@@ -30,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -88,6 +88,10 @@ class pk_mi355_norm_spec_t(C.Structure):         # a normalisation specification
 
 class pk_mi355_online_cmvn_spec_t(C.Structure):  # an online CMVN specification (include/pk_mi355.h)
     _fields_ = [("cmn_window", C.c_int32), ("speaker_frames", C.c_int32), ("global_frames", C.c_int32), ("norm_vars", C.c_int32)]
+
+
+class pk_mi355_deltas_spec_t(C.Structure):       # a delta-features specification (include/pk_mi355.h)
+    _fields_ = [("order", C.c_int32), ("window", C.c_int32)]
 
 
 EXPORTS = [
@@ -158,6 +162,8 @@ EXPORTS = [
     "pk_mi355_online_cmvn_check", "pk_mi355_online_cmvn_apply", "pk_mi355_norm_set_online_cmvn",
     "pk_mi355_stream_norm_set", "pk_mi355_stream_norm_set_online_cmvn", "pk_mi355_stream_norm_set_speaker_stats",
     "pk_mi355_stream_norm_fetch_stats",
+    "pk_mi355_deltas_check", "pk_mi355_deltas_dim", "pk_mi355_deltas_scales", "pk_mi355_deltas_apply",
+    "pk_mi355_deltas_batch_create", "pk_mi355_deltas_base_dim", "pk_mi355_deltas_recognizer_load",
 ]
 
 
@@ -451,6 +457,16 @@ def lib():
     L.pk_mi355_stream_norm_set_speaker_stats.argtypes = [C.c_void_p, C.c_int, f64p]
     L.pk_mi355_stream_norm_fetch_stats.argtypes = [C.c_void_p, C.c_int, f64p]
     L.pk_mi355_ark_matrix_f64.argtypes = [C.c_void_p, f64p, C.c_int]
+    deltasp = C.POINTER(pk_mi355_deltas_spec_t)
+    L.pk_mi355_deltas_check.argtypes = [deltasp]
+    L.pk_mi355_deltas_dim.argtypes = [deltasp, C.c_int]
+    L.pk_mi355_deltas_scales.argtypes = [deltasp, f32p]
+    L.pk_mi355_deltas_apply.argtypes = [deltasp, f32p, C.c_int, C.c_int, f32p]
+    L.pk_mi355_deltas_batch_create.restype = C.c_void_p
+    L.pk_mi355_deltas_batch_create.argtypes = [C.c_void_p, deltasp, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_deltas_base_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_deltas_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_deltas_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, C.c_int, C.c_int, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -839,6 +855,77 @@ def cmvn_online(feats, spec, global_stats=None, speaker_stats=None, return_state
     return (y, state) if return_state else y
 
 
+class DeltaSpec:
+    """A delta-features specification (pk_mi355_deltas_spec_t): Kaldi's add-deltas, order 1 to 3
+    and window 1 to 8 (Kaldi's defaults 2 and 2).  Nothing is checked here: the library refuses a bad spec (PkCodeError,
+    the field named) wherever one is used."""
+
+    def __init__(self, order=2, window=2):
+        self.order, self.window = order, window
+
+    def struct(self):
+        try:
+            return pk_mi355_deltas_spec_t(int(self.order), int(self.window))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise PkCodeError(-1, "deltas spec: %s" % e)
+
+    def check(self):
+        _check_code(lib().pk_mi355_deltas_check(C.byref(self.struct())))
+
+    def dim(self, base):
+        """The output dimension for `base` input features: (order + 1) * base."""
+        n = lib().pk_mi355_deltas_dim(C.byref(self.struct()), int(base))
+        _check_code(min(n, 0))
+        return n
+
+    def __repr__(self):
+        return "DeltaSpec(order=%r, window=%r)" % (self.order, self.window)
+
+
+def parse_deltas(text):
+    """A DeltaSpec from "order=2,window=2"; omitted keys take DeltaSpec's defaults.  ValueError, the key named, for an
+    unknown key, a key given twice or a value that is not an integer.  The ranges are the library's to refuse."""
+    given = {}
+    for item in [t.strip() for t in text.split(",") if t.strip()]:
+        key, eq, value = item.partition("=")
+        key, value = key.strip(), value.strip()
+        if key not in ("order", "window"):
+            raise ValueError("deltas spec: unknown key '%s' (the keys are order, window)" % key)
+        if key in given:
+            raise ValueError("deltas spec: key '%s' given twice" % key)
+        try:
+            given[key] = int(value) if eq else None
+        except ValueError:
+            given[key] = None
+        if given[key] is None:
+            raise ValueError("deltas spec: bad value '%s' for key '%s' (an integer)" % (value, key))
+    return DeltaSpec(**given)
+
+
+def delta_scales(spec):
+    """The scale table of a DeltaSpec, float32 [order + 1][2 * order * window + 1]: row i holds block i's scales centred
+    (entry j at column order * window + j), zeros around them."""
+    st = spec.struct()
+    _check_code(lib().pk_mi355_deltas_check(C.byref(st)))
+    out = np.zeros((st.order + 1, 2 * st.order * st.window + 1), np.float32)
+    _check_code(lib().pk_mi355_deltas_scales(C.byref(st), _fp(out)))
+    return out
+
+
+def add_deltas(feats, spec):
+    """The rule of a DeltaSpec on the host for one [T][Db] matrix (pk_mi355_deltas_apply: the restatement the GPU path is
+    held to) -> float32 [T][(order + 1) * Db]."""
+    x = _f32(feats)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise PkCodeError(-1, "features have shape %s, expected [T][D]" % (x.shape,))
+    st = spec.struct()
+    _check_code(lib().pk_mi355_deltas_check(C.byref(st)))
+    T, D = x.shape
+    y = np.zeros((T, (st.order + 1) * D), np.float32)
+    _check_code(lib().pk_mi355_deltas_apply(C.byref(st), _fp(x), T, D, _fp(y)))
+    return y
+
+
 class CMVN:
     """cmvn.h:17-26.  Sliding-window mean normalisation with a global prior."""
 
@@ -1123,12 +1210,21 @@ class Decodable:
 class BatchScorer:
     """Many utterances in flight: PCM -> fbank -> CMVN -> nnet -> log-likelihoods, all in HBM."""
 
-    def __init__(self, am, global_stats, max_utts, max_total_samples, frontend=None):
+    def __init__(self, am, global_stats, max_utts, max_total_samples, frontend=None, deltas=None):
         """frontend: a FrontendSpec of the model's feature dimension (pk_mi355_frontend_batch_create; global_stats: that
-        many sums, then the count).  Without it: the reference's 40-bin front-end and 41 statistics."""
+        many sums, then the count).  Without it: the reference's 40-bin front-end and 41 statistics.
+        deltas: a DeltaSpec (pk_mi355_deltas_batch_create): the front-end (the default FrontendSpec when none is given),
+        the statistics and the normalisation are then at base_dim() = feat_dim / (order + 1)."""
         g = _f32(global_stats)
         self._am = am
         self._keep = None
+        if deltas is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
+                                                         int(max_utts), int(max_total_samples))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
         if frontend is not None:
             self._h = lib().pk_mi355_frontend_batch_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
                                                            int(max_utts), int(max_total_samples))
@@ -1186,13 +1282,19 @@ class BatchScorer:
     def feat_dim(self):
         return lib().pk_mi355_features_dim(self._h)
 
+    def base_dim(self):
+        """The dimension in front of the deltas -- the front-end's, raw rows', statistics' -- on a scorer made with
+        deltas=; feat_dim() on every other."""
+        return lib().pk_mi355_deltas_base_dim(self._h)
+
     def set_features(self, feats, kind="normalized"):
         """Features instead of audio: one [T][feat_dim] matrix per utterance.  kind "normalized": ready for the splice
         (what Decodable takes); "raw": features the scorer's normalisation is applied to first -- the sliding-window CMVN
         (40-dim log-mel fbank, or the model's own dimension on a FeatureScorer made with feat_dim + 1 statistics) or
         what set_norm selected (any scorer, statistics or not)."""
-        arr, keep = _feature_matrices(feats, self.feat_dim())
-        _check_code(lib().pk_mi355_features_set(self._h, arr, len(keep), _feature_kind(kind)))
+        k = _feature_kind(kind)
+        arr, keep = _feature_matrices(feats, self.base_dim() if k == FEATURE_KINDS["raw"] else self.feat_dim())
+        _check_code(lib().pk_mi355_features_set(self._h, arr, len(keep), k))
 
     def set_features_device(self, device_ptr, num_frames, kind="normalized", keep_alive=None):
         """Features already in HBM: device_ptr -> the utterances' rows one after the other, [sum T][feat_dim] floats."""
@@ -1241,7 +1343,7 @@ class BatchScorer:
         return out
 
     def fetch_fbank(self, utt):
-        out = np.zeros((self.num_frames(utt), self.feat_dim()), dtype=np.float32)     # (40 wherever there is a front-end)
+        out = np.zeros((self.num_frames(utt), self.base_dim()), dtype=np.float32)     # (the front-end's dimension)
         _check_code(lib().pk_mi355_batch_fetch_fbank(self._h, utt, _fp(out)))
         return out
 
@@ -1257,7 +1359,7 @@ class BatchScorer:
         holds until it is set again.  Anything but "sliding" also lets a FeatureScorer made without statistics take
         kind "raw"."""
         if isinstance(spec, OnlineCmvnSpec):
-            g = None if global_stats is None else _global_record(global_stats, self.feat_dim())
+            g = None if global_stats is None else _global_record(global_stats, self.base_dim())
             _check_code(lib().pk_mi355_norm_set_online_cmvn(self._h, C.byref(spec.struct()), None if g is None else _dp(g)))
             return
         if global_stats is not None:
@@ -1268,12 +1370,12 @@ class BatchScorer:
         """Mode "speaker" (required) and online CMVN (optional; a count of 0: no prior for that utterance): one
         2 x (feat_dim + 1) record per utterance of the next score call, which consumes them."""
         n = len(stats)
-        a = _stats_records(stats, n, self.feat_dim())
+        a = _stats_records(stats, n, self.base_dim())
         _check_code(lib().pk_mi355_norm_set_speaker_stats(self._h, _dp(a) if n else None, n))
 
     def norm_stats(self, utt):
         """The 2 x (feat_dim + 1) float64 record the last score call computed for utterance utt in mode "utterance"."""
-        out = np.zeros((2, self.feat_dim() + 1), np.float64)
+        out = np.zeros((2, self.base_dim() + 1), np.float64)
         _check_code(lib().pk_mi355_norm_fetch_stats(self._h, utt, _dp(out)))
         return out
 
@@ -1312,9 +1414,19 @@ class FeatureScorer(BatchScorer):
     dimension), capacity in frames.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim model)
     enables kind "raw"."""
 
-    def __init__(self, am, max_utts, max_total_frames, global_stats=None):
-        g, own_dim = _stats_route(am, global_stats)
+    def __init__(self, am, max_utts, max_total_frames, global_stats=None, deltas=None):
+        """deltas: a DeltaSpec (pk_mi355_deltas_batch_create without a front-end): kind "raw" then takes [T][base_dim()]
+        rows, and global_stats, when given, holds base_dim() sums and the count."""
         self._am = am
+        self._keep = None
+        if deltas is not None:
+            g = None if global_stats is None else _f32(global_stats)
+            self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
+                                                         0 if g is None else g.size, int(max_utts), int(max_total_frames))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
+        g, own_dim = _stats_route(am, global_stats)
         if own_dim:
             self._h = lib().pk_mi355_features_batch_create_stats(am.handle, _fp(g), g.shape[0], int(max_utts), int(max_total_frames))
         else:
@@ -1979,9 +2091,16 @@ class Recognizer:
     scorer and a decoder with alignment on.  .am / .batch / .decoder / .symbols are the owned objects (beam, trace gc,
     softmax mode and calibration are set through them); process(waves) -> [Result]."""
 
-    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0, frontend=None):
-        """frontend: a FrontendSpec; the model file is then one of that feature dimension (pk_mi355_frontend_recognizer_load)."""
-        if frontend is not None:
+    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0, frontend=None, deltas=None):
+        """frontend: a FrontendSpec; the model file is then one of that feature dimension (pk_mi355_frontend_recognizer_load).
+        deltas: a DeltaSpec; the model file is then one of (order + 1) x the front-end's dimension whose cmvn_stats are at
+        the front-end's (pk_mi355_deltas_recognizer_load; the default FrontendSpec when only deltas is given)."""
+        if deltas is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_deltas_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()), C.byref(deltas.struct()),
+                                                            AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
+                                                            int(trace_capacity))
+        elif frontend is not None:
             self._h = lib().pk_mi355_frontend_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()),
                                                               AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
                                                               int(trace_capacity))
@@ -2029,7 +2148,7 @@ class Recognizer:
         return out
 
     def _speaker_stats(self, speaker_stats, n):
-        return None if speaker_stats is None else _stats_records(speaker_stats, n, self.batch.feat_dim())
+        return None if speaker_stats is None else _stats_records(speaker_stats, n, self.batch.base_dim())
 
     def process_features(self, feats, kind="raw", speaker_stats=None):
         """pk_process from features: one [T][feat_dim] matrix per utterance (kind: as BatchScorer.set_features).  A list
@@ -2037,7 +2156,7 @@ class Recognizer:
         single matrix that cannot fit is refused.  speaker_stats: one record per utterance for a batch whose norm
         (self.batch.set_norm) is in mode "speaker"; they are split with the list."""
         code = _feature_kind(kind)
-        arr, keep = _feature_matrices(feats, self.batch.feat_dim())
+        arr, keep = _feature_matrices(feats, self.batch.base_dim() if code == FEATURE_KINDS["raw"] else self.batch.feat_dim())
         spk = self._speaker_stats(speaker_stats, len(keep))
         cap = self.max_total_samples // 160 + self.max_utts       # the frames pk_mi355_batch_create makes room for
         for i, f in enumerate(keep):

@@ -9,6 +9,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "pk_delta_kernel.h"
 #include "pk_frontend.h"
 #include "pk_norm_kernel.h"
 #include "pk_resample.h"
@@ -201,6 +202,14 @@ struct pk_mi355_batch {
   pk_mi355_online_cmvn_spec_t online_cmvn{600, 600, 200, 0};
   double *d_online_glob = nullptr;  // [2][feat_dim + 1]: the global record
   double *d_online_spk = nullptr;   // [max_utts][2][feat_dim + 1]: the speaker records handed over for the next score
+  // Deltas (pk_mi355_deltas_batch_create): everything in front of DeltaKernel -- the front-end,
+  // the raw rows, the normalisation, its records -- works at base_dim = feat_dim / (order + 1); on every other batch
+  // base_dim is feat_dim and nothing below is made.
+  int base_dim = 0;
+  bool has_deltas = false;
+  pk_mi355_deltas_spec_t deltas{0, 0};
+  float *d_delta_scales = nullptr;  // the spec's scale table (pkdelta::BuildScales)
+  float *d_delta = nullptr;         // [max_frames][feat_dim]: DeltaKernel's result, which FeatureLayoutKernel reads
   _Float16 *d_y2 = nullptr;   // f16x3: interleaved (hi, lo) rows [ldy][2 feat_dim]
   float *h_ll = nullptr;    // page-locked mirror of d_ll (pk_mi355_batch_fetch_all), made on first use
   ArenaRec *arena = nullptr;  // its shared-ownership record
@@ -326,6 +335,9 @@ int CheckFeatureKind(const pk_mi355_batch *b, int kind) {
   // (statistics are only ever held at the model's own dimension: 41 floats through the 40-dim entries, feat_dim + 1
   // through pk_mi355_features_batch_create_stats)
   if (kind == PK_MI355_FEATS_RAW && !b->have_stats && b->norm.mode == PK_MI355_NORM_SLIDING) {
+    if (b->has_deltas)
+      return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics: this batch of %d-dim base features was made without them "
+                  "(pk_mi355_deltas_batch_create takes %d)", b->base_dim, b->base_dim + 1);
     if (b->core.am->feat_dim == kNumBins)
       return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics and a %d-dim model (this batch: no statistics, %d-dim)", kNumBins,
                   kNumBins);
@@ -352,7 +364,7 @@ int EnsureFeatsStaging(pk_mi355_batch *b) {
 // take RAW features: [max_frames][feat_dim], read by NormKernel and FeatureLayoutKernel within an utterance's own rows.
 int EnsureRawRows(pk_mi355_batch *b) {
   if (b->d_raw) return 0;
-  HIP_TRY(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)b->core.max_frames * b->core.am->feat_dim));
+  HIP_TRY(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)b->core.max_frames * b->base_dim));
   b->d_raw = b->d_raw_alloc;
   return 0;
 }
@@ -463,16 +475,19 @@ int64_t PublicChunkCap() {
 // global_stats: am->feat_dim sums and the count.
 // any: the tables of a front-end spec of am->feat_dim features (pk_mi355_frontend_batch_create), or null.
 pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int max_utts, int64_t max_total_samples, int64_t max_frames,
-                            int64_t chunk_cap, const FrontendAnyTables *any = nullptr) {
+                            int64_t chunk_cap, const FrontendAnyTables *any = nullptr, const pk_mi355_deltas_spec_t *deltas = nullptr) {
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
   b->max_utts = max_utts; b->max_samples = max_total_samples;
   b->features_only = max_total_samples == 0;
   b->have_stats = global_stats != nullptr;
+  b->has_deltas = deltas != nullptr;
+  if (deltas) b->deltas = *deltas;
+  b->base_dim = deltas ? am->feat_dim / (deltas->order + 1) : am->feat_dim;
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
-  CreateScorerCore(&c, am, global_stats, am->feat_dim, max_utts, max_frames, max_frames, chunk_cap, chk);
+  CreateScorerCore(&c, am, global_stats, b->base_dim, max_utts, max_frames, max_frames, chunk_cap, chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
   // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
@@ -485,8 +500,8 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int ma
   chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
   chk(hipMalloc(&b->d_lay, lay_bytes));
   chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
-  if (b->have_stats && am->feat_dim != kNumBins) {     // CmvnChainKernel reads an utterance's own rows only: no lead, no slack
-    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
+  if (b->have_stats && (am->feat_dim != kNumBins || deltas)) {     // CmvnChainKernel reads an utterance's own rows only: no lead, no slack
+    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)c.max_frames * b->base_dim));
     b->d_raw = b->d_raw_alloc;
   } else if (b->have_stats) {
     const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
@@ -503,8 +518,17 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int ma
     }
     chk(hipMalloc(&b->d_any, sizeof(FrontendAnyTables)));
     if (chk.ok) chk(hipMemcpy(b->d_any, any, sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
-    if (am->feat_dim != kNumBins)                    // CmvnChainKernel's output, which FeatureLayoutKernel reads
+    if (am->feat_dim != kNumBins && !deltas)         // CmvnChainKernel's output, which FeatureLayoutKernel reads
       chk(hipMalloc(&b->d_feats, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
+  }
+  if (deltas) {     // the norm kernels' output at base_dim (and NORMALIZED host features at feat_dim), DeltaKernel's table and output
+    float table[pkdelta::kMaxTable];
+    pkdelta::BuildScales(*deltas, table);
+    const size_t bytes = sizeof(float) * (size_t)(deltas->order + 1) * pkdelta::RowLen(*deltas);
+    chk(hipMalloc(&b->d_feats, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
+    chk(hipMalloc(&b->d_delta, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
+    chk(hipMalloc(&b->d_delta_scales, bytes));
+    if (chk.ok) chk(hipMemcpy(b->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
   }
   if (IsF16(am->precision)) chk(hipMalloc(&b->d_y2, sizeof(_Float16) * 2 * c.ldy * am->feat_dim));
   if (const char *e = getenv("PK_MI355_LANES")) b->lanes = atoi(e) >= 2 ? 2 : 1;
@@ -603,6 +627,41 @@ pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi3
   return CreateBatch(am, global_stats, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts, PublicChunkCap(), any.data());
 }
 
+pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
+                                               const float *global_stats, int stats_len, int max_utts, int64_t capacity) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (!deltas || (frontend && !global_stats)) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pkdelta::CheckSpec(deltas)) return nullptr;                    // (names the field)
+  const int blocks = deltas->order + 1;
+  if (am->feat_dim % blocks != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", deltas->order, blocks, am->feat_dim);
+    return nullptr;
+  }
+  const int Db = am->feat_dim / blocks;
+  std::vector<FrontendAnyTables> any(frontend ? 1 : 0);
+  if (frontend) {
+    if (BuildFrontendAnyTables(frontend, any.data())) return nullptr;      // (names the field)
+    if (any[0].dim != Db) {
+      Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model's %d with deltas of order %d need %d", any[0].dim, am->feat_dim,
+           deltas->order, Db);
+      return nullptr;
+    }
+  }
+  if (global_stats && stats_len != Db + 1) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, %d-dim base features need %d (the sums, then the count)", stats_len, Db, Db + 1);
+    return nullptr;
+  }
+  if (max_utts <= 0 || capacity <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
+    return nullptr;
+  }
+  if (frontend) return CreateBatch(am, global_stats, max_utts, capacity, capacity / kFrameShift + max_utts, PublicChunkCap(), any.data(), deltas);
+  return CreateBatch(am, global_stats, max_utts, 0, capacity, PublicChunkCap(), nullptr, deltas);
+}
+
+int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b) { return b ? b->base_dim : 0; }
+
 int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
 
 void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
@@ -614,6 +673,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   for (hipEvent_t e : {b->ev_front, b->ev_lane2, b->ev_scored, b->ev_fetched, b->ev_layout}) if (e) hipEventDestroy(e);
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats); hipFree(b->d_any);
+  hipFree(b->d_delta); hipFree(b->d_delta_scales);
   hipFree(b->d_norm_stats); hipFree(b->d_spk_table); hipFree(b->d_online_glob); hipFree(b->d_online_spk);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
@@ -726,9 +786,12 @@ int pk_mi355_batch_set_waves_device(pk_mi355_batch_t *b, const float *d_samples,
 int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num_utts, int kind) {
   if (!b || (num_utts > 0 && !feats)) return Fail(PK_MI355_E_INVALID, "null argument");
   if (int rc = CheckFeatureKind(b, kind)) return rc;
-  const int D = b->core.am->feat_dim;
+  const int D = kind == PK_MI355_FEATS_RAW ? b->base_dim : b->core.am->feat_dim;      // (a deltas batch: RAW rows are in front of the deltas)
   std::vector<int> frames(std::max(num_utts, 0));
   for (int u = 0; u < num_utts; ++u) {
+    if (feats[u].nrow != D && b->has_deltas)
+      return Fail(PK_MI355_E_INVALID, "features of utterance %d have %d rows, this batch expects %d (%s)", u, feats[u].nrow, D,
+                  kind == PK_MI355_FEATS_RAW ? "raw rows in front of the deltas" : "normalised rows at the model's dimension");
     if (feats[u].nrow != D) return Fail(PK_MI355_E_INVALID, "features of utterance %d have %d rows, the model expects %d", u, feats[u].nrow, D);
     if (feats[u].ncol > 0 && !feats[u].data) return Fail(PK_MI355_E_INVALID, "features of utterance %d: null data", u);
     frames[u] = feats[u].ncol;                          // (a negative one is named by CheckFeatureCounts)
@@ -763,7 +826,7 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
   if (int rc = CheckFeatureCounts(b, num_frames, num_utts)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   if (kind == PK_MI355_FEATS_RAW) {                     // CMVN reads around every utterance: into d_raw with its lead and slack
-    const int D = b->core.am->feat_dim;                 // (any other dimension than 40: as a host call's rows, fetch_fbank's source)
+    const int D = b->base_dim;                          // (any other dimension than 40: as a host call's rows, fetch_fbank's source)
     if (D != kNumBins)
       if (int rc = EnsureFeatsStaging(b)) return rc;
     if (int rc = EnsureRawRows(b)) return rc;
@@ -783,7 +846,7 @@ int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec) {
   if (int rc = pknorm::CheckSpec(spec)) return rc;      // (names the field)
   if (spec->mode != PK_MI355_NORM_SLIDING) {            // what NormKernel writes and reads, made at the first spec that needs it
     if (int rc = UseDevice(b->core.device)) return rc;
-    const size_t D = (size_t)b->core.am->feat_dim;
+    const size_t D = (size_t)b->base_dim;
     if (int rc = EnsureFeatsStaging(b)) return rc;
     if (!b->d_norm_stats) HIP_TRY(hipMalloc(&b->d_norm_stats, sizeof(double) * 2 * (D + 1) * (size_t)b->max_utts));
     if (!b->d_spk_table) HIP_TRY(hipMalloc(&b->d_spk_table, sizeof(float) * 2 * D * (size_t)b->max_utts));
@@ -795,7 +858,7 @@ int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec) {
 
 int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats) {
   if (!b || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
-  const size_t D = (size_t)b->core.am->feat_dim;
+  const size_t D = (size_t)b->base_dim;
   if (int rc = pknorm::CheckOnlineSpec(spec, global_stats, (int)D)) return rc;      // (names the field)
   if (int rc = UseDevice(b->core.device)) return rc;
   if (int rc = EnsureFeatsStaging(b)) return rc;
@@ -817,7 +880,7 @@ int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, in
   if (b->norm.mode != PK_MI355_NORM_SPEAKER && b->norm.mode != pknorm::kNormOnlineCmvn)
     return Fail(PK_MI355_E_STATE, "speaker statistics need mode speaker (pk_mi355_norm_set) or online CMVN (pk_mi355_norm_set_online_cmvn)");
   if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
-  const int D = b->core.am->feat_dim;
+  const int D = b->base_dim;
   if (b->norm.mode == pknorm::kNormOnlineCmvn) {        // the records as they are: the kernel smooths with them
     if (int rc = pknorm::CheckOnlineSpeakerCounts(stats, num_utts, D)) return rc;
     if (int rc = UseDevice(b->core.device)) return rc;
@@ -842,7 +905,7 @@ int pk_mi355_norm_set_speaker_stats(pk_mi355_batch_t *b, const double *stats, in
 int pk_mi355_norm_fetch_stats(pk_mi355_batch_t *b, int utt, double *out) {
   if (!b || !out || utt < 0 || utt >= b->num_utts) return Fail(PK_MI355_E_INVALID, "bad utterance index");
   if (!b->scored || !b->norm_stats_valid) return Fail(PK_MI355_E_STATE, "the last score call computed no statistics (mode utterance on raw rows or audio does)");
-  const size_t rec = 2 * ((size_t)b->core.am->feat_dim + 1);
+  const size_t rec = 2 * ((size_t)b->base_dim + 1);
   HIP_TRY(hipMemcpyAsync(out, b->d_norm_stats + utt * rec, sizeof(double) * rec, hipMemcpyDeviceToHost, b->core.stream));
   HIP_TRY(hipStreamSynchronize(b->core.stream));
   return 0;
@@ -869,6 +932,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   b->spk_utts = -1;
   b->norm_stats_valid = false;
   const int D = am->feat_dim;
+  const int Db = b->base_dim;                    // the dimension in front of the deltas (D without them)
   const int mode = b->source == pk_mi355_batch::kNormalized ? PK_MI355_NORM_NONE : b->norm.mode;
   if (b->source != pk_mi355_batch::kNormalized) {
     if (mode == PK_MI355_NORM_SLIDING && !b->have_stats)
@@ -882,7 +946,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   }
   if (b->num_utts == 0 || b->total_frames == 0) {
     if (mode == PK_MI355_NORM_UTTERANCE && b->num_utts > 0) {      // records of no frames: zeros
-      HIP_TRY(hipMemsetAsync(b->d_norm_stats, 0, sizeof(double) * 2 * (D + 1) * (size_t)b->num_utts, c.stream));
+      HIP_TRY(hipMemsetAsync(b->d_norm_stats, 0, sizeof(double) * 2 * (Db + 1) * (size_t)b->num_utts, c.stream));
       b->norm_stats_valid = true;
     }
     b->scored = true;
@@ -891,14 +955,29 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   const UttLayout &lay = b->lay;
   if (b->source == pk_mi355_batch::kWaves) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
-    if (b->d_any) LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, D, b->d_raw, c.stream);
+    if (b->d_any) LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, Db, b->d_raw, c.stream);
     else LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_raw, c.stream);
   }
   {                                            // raw rows (fbank's, or the caller's) or normalised features -> Yt
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);
     if (b->source == pk_mi355_batch::kNormalized)
       LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else if (mode == PK_MI355_NORM_NONE)      // the raw rows as they are (at D = 40: d_raw, behind CmvnKernel's lead)
+    else if (b->has_deltas) {                   // the normalisation at Db (none: the raw rows), DeltaKernel, the layout of its result
+      const float *rows = b->d_feats;
+      if (mode == PK_MI355_NORM_NONE)
+        rows = b->d_raw;
+      else if (mode == pknorm::kNormOnlineCmvn)
+        LaunchOnlineCmvn(b->d_raw, lay, b->num_utts, Db, b->online_cmvn, b->d_online_glob, spk_utts >= 0 ? b->d_online_spk : nullptr, b->d_feats,
+                         c.stream);
+      else if (mode != PK_MI355_NORM_SLIDING) {
+        LaunchNorm(b->d_raw, lay, b->num_utts, Db, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats,
+                   b->d_feats, c.stream);
+        b->norm_stats_valid = mode == PK_MI355_NORM_UTTERANCE;
+      } else                                    // (at Db = 40 too: CmvnKernel would write the layout itself)
+        LaunchCmvnChain(b->d_raw, lay, b->num_utts, Db, c.d_global, c.d_cmvn_tab, b->d_feats, c.stream);
+      LaunchDelta(rows, lay, b->num_utts, b->max_T, Db, b->deltas, b->d_delta_scales, b->d_delta, c.stream);
+      LaunchFeatureLayout(b->d_delta, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    } else if (mode == PK_MI355_NORM_NONE)      // the raw rows as they are (at D = 40: d_raw, behind CmvnKernel's lead)
       LaunchFeatureLayout(b->d_raw, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
     else if (mode == pknorm::kNormOnlineCmvn) {   // OnlineCmvnKernel, then the layout of its result
       LaunchOnlineCmvn(b->d_raw, lay, b->num_utts, D, b->online_cmvn, b->d_online_glob, spk_utts >= 0 ? b->d_online_spk : nullptr, b->d_feats,
@@ -1068,7 +1147,7 @@ int pk_mi355_batch_fetch_fbank(pk_mi355_batch_t *b, int utt, float *out) {
   if (b->source == pk_mi355_batch::kNormalized) return Fail(PK_MI355_E_STATE, "the batch was fed normalised features: there is no fbank");
   const int T = b->h_T[utt];
   if (T == 0) return 0;
-  const int D = b->core.am->feat_dim;          // (40 whenever there is a front-end)
+  const int D = b->base_dim;                   // (the front-end's dimension)
   HIP_TRY(hipMemcpyAsync(out, b->d_raw + b->h_raw_base[utt] * D, sizeof(float) * (size_t)T * D, hipMemcpyDeviceToHost, b->core.stream));
   HIP_TRY(hipStreamSynchronize(b->core.stream));
   return 0;

@@ -71,6 +71,14 @@ int pk_mi355_load(const char *config_path, int precision, pk_mi355_am_t **am_out
 
 // pk_mi355_load for a model of any feature dimension: the statistics vector at the model's length
 int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **am_out, float *stats, int stats_cap, int *stats_len) {
+  return LoadStatsBlocks(config_path, precision, 1, am_out, stats, stats_cap, stats_len);
+}
+
+}  // extern "C"
+
+// blocks: 1, or the order + 1 blocks of a deltas spec -- the statistics are then at feat_dim / blocks
+int pkhost::LoadStatsBlocks(const char *config_path, int precision, int blocks, pk_mi355_am_t **am_out, float *stats, int stats_cap,
+                            int *stats_len) {
   if (!config_path || !am_out || !stats || !stats_len) return Fail(PK_MI355_E_INVALID, "null argument");
   *am_out = nullptr; *stats_len = 0;
   if (stats_cap <= 0) return Fail(PK_MI355_E_INVALID, "bad statistics capacity %d", stats_cap);
@@ -82,8 +90,12 @@ int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **
   // the statistics against the model's feature dimension -- the first layer's width over the spliced frames -- as soon as
   // the files are read (a width that is no multiple of the frames is the model's own refusal, at finalize)
   auto stats_fit = [&](int in_dim) {
-    const int frames = conf.left + conf.right + 1, dim = in_dim / frames;
+    const int frames = conf.left + conf.right + 1, feat_dim = in_dim / frames, dim = feat_dim / blocks;
     if (in_dim % frames != 0 || (int)conf.stats.size() == dim + 1) return 0;
+    if (blocks > 1 && feat_dim % blocks != 0) return 0;      // (pk_mi355_deltas_batch_create's refusal, which names both numbers)
+    if (blocks > 1)
+      return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, the %d-dim model of %s with %d delta blocks needs %d (the sums, then the count)",
+                  conf.cmvn_path.c_str(), (int)conf.stats.size(), feat_dim, config_path, blocks, dim + 1);
     return Fail(PK_MI355_E_IO, "cmvn_stats in %s has %d entries, the %d-dim model of %s needs %d (the sums, then the count)", conf.cmvn_path.c_str(),
                 (int)conf.stats.size(), dim, config_path, dim + 1);
   };
@@ -97,6 +109,8 @@ int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **
   *am_out = am;
   return 0;
 }
+
+extern "C" {
 
 int pk_mi355_test_logf(const float *x, int n, float *out) {
   if (!x || !out || n < 0) return Fail(PK_MI355_E_INVALID, "bad argument");

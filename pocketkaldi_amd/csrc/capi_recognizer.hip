@@ -72,13 +72,18 @@ void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
 
 namespace {
 // spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
+// deltas (with a spec only): the model's features are (order + 1) x the spec's, the statistics at the spec's dimension
 pk_mi355_recognizer_t *LoadRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision, int max_utts,
-                                      int64_t max_total_samples, int64_t trace_capacity) {
+                                      int64_t max_total_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr) {
   pk_mi355_recognizer *r = new pk_mi355_recognizer();
   auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (spec) {
+  if (deltas) {
+    int stats_len = 0;
+    if (LoadStatsBlocks(config_path, precision, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->batch = pk_mi355_deltas_batch_create(r->am, deltas, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
+  } else if (spec) {
     int stats_len = 0;
     if (pk_mi355_load_stats(config_path, precision, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
     if (!(r->batch = pk_mi355_frontend_batch_create(r->am, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
@@ -107,6 +112,15 @@ pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path
   if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
   if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
   return LoadRecognizer(config_path, spec, precision, max_utts, max_total_samples, trace_capacity);
+}
+
+pk_mi355_recognizer_t *pk_mi355_deltas_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                       const pk_mi355_deltas_spec_t *deltas_spec, int precision, int max_utts,
+                                                       int64_t max_total_samples, int64_t trace_capacity) {
+  if (!config_path || !frontend_spec || !deltas_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
+  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
+  return LoadRecognizer(config_path, frontend_spec, precision, max_utts, max_total_samples, trace_capacity, deltas_spec);
 }
 
 pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r) {

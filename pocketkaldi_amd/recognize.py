@@ -1,7 +1,7 @@
 """The reference's command-line program (main.cc:17-80) over the Recognizer.
 
     python -m pocketkaldi_amd.recognize <model-file> <x.wav | x.scp> [--ctm] [--reference-softmax] [--channel N]
-                                        [--frontend key=value,...]
+                                        [--frontend key=value,...] [--deltas order=N,window=N]
                                         [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]]
                                         [--cmvn mode=online,cmn_window=...,speaker_frames=...,global_frames=...,norm_vars=...
                                          [--cmvn-global RX] [--cmvn-stats RX [--utt2spk FILE]]]
@@ -53,6 +53,14 @@ utterance, on the batch scorer or, with --online, live.  --cmvn-global RX names 
 is smoothed with; global_frames > 0 without it is refused with the usage text.  --cmvn-stats and --utt2spk give the
 speakers' statistics as for mode=speaker; here they are optional.
 
+--deltas order=2,window=2 takes a model that was trained on add-deltas' features (pk.DeltaSpec): its
+first layer expects (order + 1) x the dimension of the front-end -- the reference's, or --frontend's -- and the model
+file's cmvn_stats, --cmvn-stats and --cmvn-global are at the front-end's dimension: the deltas are taken behind the
+normalisation.  It works with every batch form -- wave files and lists, --features raw matrices and archives ([T][front-end's
+dimension]), --frontend, --cmvn.  --features normalized --deltas takes matrices that are ready for the splice,
+[T][(order + 1) x the front-end's dimension], and no deltas are added.  With --online it is refused with the usage text:
+the live objects do not have deltas yet.
+
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
 up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
@@ -78,11 +86,13 @@ RESERVE = 32
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
-          "[--frontend key=value,...] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
+          "[--frontend key=value,...] [--deltas order=N,window=N] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--cmvn mode=online,cmn_window=...,speaker_frames=...,global_frames=...,norm_vars=... [--cmvn-global RX] [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
-          "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--online ...]")
+          "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--deltas ...] [--online ...]")
+    print("  --deltas order=N,window=N: add-deltas behind the normalisation (not with --online); --features raw matrices are [T][front-end's "
+          "dimension], --features normalized matrices [T][the model's dimension] and take no deltas.")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
@@ -300,6 +310,17 @@ def main(argv):
             print("pocketkaldi: --frontend: %s" % e)
             return usage()
         del argv[at:at + 2]
+    deltas = None
+    try:
+        text = take_value(argv, "--deltas")
+        if text is not None:
+            deltas = pk.parse_deltas(text)
+            deltas.check()
+            if "--online" in argv:
+                raise UsageError("the live objects do not have deltas yet: leave out --online")
+    except (UsageError, ValueError, pk.PkError) as e:
+        print("pocketkaldi: --deltas: %s" % e)
+        return usage()
     try:
         norm = parse_norm_flags(argv)
     except UsageError as e:
@@ -334,7 +355,7 @@ def main(argv):
         return usage()
     try:
         if features:
-            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend, norm)
+            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend, norm, deltas)
         if input_file.endswith(".wav"):
             files = [input_file]
         else:
@@ -352,7 +373,7 @@ def main(argv):
         else:
             sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
-                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend)
+                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend, deltas=deltas)
             if "--reference-softmax" in flags:
                 rec.am.set_softmax("reference")
             if norm:
@@ -419,7 +440,7 @@ def feature_groups(input_file):
             yield group
 
 
-def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None, norm=None):
+def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None, norm=None, deltas=None):
     """--features: every group of utterances through a Recognizer (process_features) or, with --online, through the
     slots of an OnlineRecognizer; the object is kept from group to group while the group fits it.  Raises what main
     reports; -> the exit code."""
@@ -444,7 +465,7 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
                     if norm:
                         norm.apply_online(rec)
                 else:
-                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend)
+                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend, deltas=deltas)
                     if "--reference-softmax" in flags:
                         rec.am.set_softmax("reference")
                     if norm:
