@@ -12,6 +12,7 @@
 #include "pk_delta_kernel.h"
 #include "pk_frontend.h"
 #include "pk_norm_kernel.h"
+#include "pk_plan.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -151,15 +152,16 @@ struct pk_mi355_batch {
   int16_t *d_wave_i16 = nullptr;    // owned int16 buffer
   const float *wave_f32 = nullptr;  // what the kernels read (owned or external)
   const int16_t *wave_i16 = nullptr;
-  // What the last set_* call handed over, and so what score starts from: audio (fbank, CMVN, layers), raw fbank
-  // features in d_raw (CMVN, layers) or normalised features at `feats` (FeatureLayoutKernel, layers).
-  enum Source { kNone, kWaves, kRaw, kNormalized };
-  Source source = kNone;
+  // What the last set_* call handed over, and so what score's plan (pk_plan.h) starts from: audio, raw features in
+  // d_raw or normalised features at `feats`.
+  pkplan::Source source = pkplan::kNoSource;
   bool features_only = false;       // made by pk_mi355_features_batch_create: no PCM capacity, the wave entries are refused
   bool have_stats = false;          // the CMVN tables and d_raw exist (always, for a wave batch)
   // made by pk_mi355_frontend_batch_create: the spec's tables; score then runs FbankAnyKernel instead of FbankKernel
   FrontendAnyTables *d_any = nullptr;
-  float *d_feats = nullptr;         // owned [max_frames][feat_dim] staging of set_features(NORMALIZED), made on first use
+  // owned [max_frames][feat_dim], made by EnsureBuffers: what every normalising kernel writes, and the staging of host
+  // features handed over as NORMALIZED
+  float *d_feats = nullptr;
   const float *feats = nullptr;     // normalised features, frame-major (d_feats or the caller's device pointer)
   // pk_mi355_resample_set_waves: the utterances that are not at 16 kHz wait here at their own rate, page-locked and
   // on the device (both made and grown on demand), and are converted straight into d_wave
@@ -189,7 +191,7 @@ struct pk_mi355_batch {
   const int32_t *d_shift4 = nullptr;   // in d_lay; null when every shift of the layout is zero (one utterance at column 0) or rows = columns
   // stages
   float *d_raw_alloc = nullptr;
-  float *d_raw = nullptr;   // [max_frames][40], kCmvnRawLead floats into d_raw_alloc
+  float *d_raw = nullptr;   // [max_frames][base_dim]; kCmvnRawLead floats into d_raw_alloc where CmvnKernel runs (EnsureBuffers)
   // The normalisation spec (pk_mi355_norm_set).  Anything but SLIDING: NormKernel (or, for NONE,
   // nothing) stands in front of FeatureLayoutKernel, from d_raw into d_feats; the buffers below are made by norm_set.
   pk_mi355_norm_spec_t norm{PK_MI355_NORM_SLIDING, 1, 0};
@@ -325,7 +327,7 @@ int SetLayout(pk_mi355_batch *b, const int *num_samples, int num_utts) {
   }
   if (total > b->max_samples) return Fail(PK_MI355_E_INVALID, "too many samples (%lld > %lld)", (long long)total, (long long)b->max_samples);
   if (int rc = SetLayoutFrames(b, frames.data(), num_samples, num_utts)) return rc;
-  b->source = pk_mi355_batch::kWaves;
+  b->source = pkplan::kWaves;
   return 0;
 }
 
@@ -353,21 +355,28 @@ int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts)
     if (frames[u] < 0) return Fail(PK_MI355_E_INVALID, "utterance %d has a negative frame count (%d)", u, frames[u]);
   return FramesFit(b, frames, num_utts);
 }
-// RAW at a dimension other than 40 is normalised by CmvnChainKernel into the d_feats staging (the one host NORMALIZED
-// features use): made at the first call that needs it.  b->feats is not touched: a caller's NORMALIZED device pointer stays.
-int EnsureFeatsStaging(pk_mi355_batch *b) {
-  if (b->d_feats) return 0;
-  HIP_TRY(hipMalloc(&b->d_feats, sizeof(float) * (size_t)b->core.max_frames * b->core.am->feat_dim));
-  return 0;
+pkplan::BatchShape ShapeOf(const pk_mi355_batch *b) {
+  return pkplan::BatchShape{b->base_dim, b->core.am->feat_dim, b->d_any != nullptr, b->has_deltas, b->have_stats};
 }
-// A features-only batch made without statistics has no raw rows until a normalisation spec other than SLIDING lets it
-// take RAW features: [max_frames][feat_dim], read by NormKernel and FeatureLayoutKernel within an utterance's own rows.
-int EnsureRawRows(pk_mi355_batch *b) {
-  if (b->d_raw) return 0;
-  HIP_TRY(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)b->core.max_frames * b->base_dim));
-  b->d_raw = b->d_raw_alloc;
-  return 0;
+// The own rows a plan reads or writes (pkplan::BatchPlan::buffers), made by the first call that needs them: create, for
+// what a set call could not make in time, then features_set* and norm_set*.  d_raw [max_frames][base_dim] has its lead
+// and its zeroed slack exactly where CmvnKernel runs, which reads around every utterance; every other kernel stays
+// within an utterance's own rows.  b->feats is not touched: a caller's NORMALIZED device pointer stays.
+hipError_t EnsureBuffers(pk_mi355_batch *b, unsigned need) {
+  const size_t frames = (size_t)b->core.max_frames, D = (size_t)b->core.am->feat_dim;
+  hipError_t e = hipSuccess;
+  if ((need & pkplan::kRawRows) && !b->d_raw) {
+    const size_t lead = pkplan::FusedCmvn(ShapeOf(b)) ? kCmvnRawLead : 0, floats = frames * b->base_dim + (lead ? lead + kCmvnRawSlack : 0);
+    e = hipMalloc(&b->d_raw_alloc, sizeof(float) * floats);
+    if (e == hipSuccess && lead) e = hipMemset(b->d_raw_alloc, 0, sizeof(float) * floats);
+    if (e == hipSuccess) b->d_raw = b->d_raw_alloc + lead;
+  }
+  if (e == hipSuccess && (need & pkplan::kFeatRows) && !b->d_feats) e = hipMalloc(&b->d_feats, sizeof(float) * frames * D);
+  if (e == hipSuccess && (need & pkplan::kDeltaRows) && !b->d_delta) e = hipMalloc(&b->d_delta, sizeof(float) * frames * D);
+  return e;
 }
+// what scoring `source` under `mode` needs of them
+unsigned BuffersFor(const pk_mi355_batch *b, pkplan::Source source, int mode) { return pkplan::PlanBatch(ShapeOf(b), source, mode, false).buffers; }
 int WaveEntryAllowed(const pk_mi355_batch *b) {
   if (b->features_only) return Fail(PK_MI355_E_STATE, "this batch was made by pk_mi355_features_batch_create: it takes features, not audio");
   return 0;
@@ -470,24 +479,29 @@ int64_t PublicChunkCap() {
   return e && atol(e) >= kTile ? RoundUp(atol(e), kTileF16) : 262144;
 }
 
-// Every way to a batch, arguments checked: max_utts utterances and max_frames frames; max_total_samples PCM samples
-// (0: features only); passes of at most chunk_cap frames.  global_stats41 may be null for a features-only batch.
-// global_stats: am->feat_dim sums and the count.
-// any: the tables of a front-end spec of am->feat_dim features (pk_mi355_frontend_batch_create), or null.
-pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int max_utts, int64_t max_total_samples, int64_t max_frames,
-                            int64_t chunk_cap, const FrontendAnyTables *any = nullptr, const pk_mi355_deltas_spec_t *deltas = nullptr) {
+// A batch as CreateBatch makes it, arguments checked.  stats: null (a features-only batch), or the base dimension's sums
+// and the count -- the base dimension is the model's divided by deltas->order + 1, the model's own without deltas.
+// max_samples PCM samples (0: features only), max_frames frames, passes of at most chunk_cap frames.
+struct BatchSpec {
+  const float *stats; int max_utts; int64_t max_samples, max_frames, chunk_cap;
+  const FrontendAnyTables *any;             // the tables of a front-end spec of the base dimension, or null
+  const pk_mi355_deltas_spec_t *deltas;     // or null
+};
+// Every way to a batch.
+pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   if (UseDevice(am->device)) return nullptr;
+  const pk_mi355_deltas_spec_t *deltas = spec.deltas;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
-  b->max_utts = max_utts; b->max_samples = max_total_samples;
-  b->features_only = max_total_samples == 0;
-  b->have_stats = global_stats != nullptr;
+  b->max_utts = spec.max_utts; b->max_samples = spec.max_samples;
+  b->features_only = spec.max_samples == 0;
+  b->have_stats = spec.stats != nullptr;
   b->has_deltas = deltas != nullptr;
   if (deltas) b->deltas = *deltas;
   b->base_dim = deltas ? am->feat_dim / (deltas->order + 1) : am->feat_dim;
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
-  CreateScorerCore(&c, am, global_stats, b->base_dim, max_utts, max_frames, max_frames, chunk_cap, chk);
+  CreateScorerCore(&c, am, spec.stats, b->base_dim, spec.max_utts, spec.max_frames, spec.max_frames, spec.chunk_cap, chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
   // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
@@ -496,37 +510,18 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int ma
   // save anyway: such models keep row = column of Yt.
   b->compact = pad >= 3;
   if (const char *e = getenv("PK_MI355_COMPACT_ROWS")) b->compact = b->compact && atoi(e) != 0;    // (A/B switch: 0 = row = column of Yt)
-  const size_t lay_bytes = RoundUp(kLayoutEntry * max_utts, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
+  const size_t lay_bytes = RoundUp(kLayoutEntry * spec.max_utts, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
   chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
   chk(hipMalloc(&b->d_lay, lay_bytes));
   chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
-  if (b->have_stats && (am->feat_dim != kNumBins || deltas)) {     // CmvnChainKernel reads an utterance's own rows only: no lead, no slack
-    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * (size_t)c.max_frames * b->base_dim));
-    b->d_raw = b->d_raw_alloc;
-  } else if (b->have_stats) {
-    const size_t raw_floats = (size_t)c.max_frames * kNumBins + kCmvnRawLead + kCmvnRawSlack;
-    chk(hipMalloc(&b->d_raw_alloc, sizeof(float) * raw_floats));
-    if (chk.ok) chk(hipMemset(b->d_raw_alloc, 0, sizeof(float) * raw_floats));
-    if (chk.ok) b->d_raw = b->d_raw_alloc + kCmvnRawLead;
-  }
-  if (any) {
-    if (!c.d_tables && chk.ok) {                     // (the scorer core makes FbankKernel's tables for 40-dim statistics only)
-      FrontendTables host;
-      if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
-      chk(hipMalloc(&c.d_tables, sizeof(FrontendTables)));
-      if (chk.ok) chk(hipMemcpy(c.d_tables, &host, sizeof(FrontendTables), hipMemcpyHostToDevice));
-    }
-    chk(hipMalloc(&b->d_any, sizeof(FrontendAnyTables)));
-    if (chk.ok) chk(hipMemcpy(b->d_any, any, sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
-    if (am->feat_dim != kNumBins && !deltas)         // CmvnChainKernel's output, which FeatureLayoutKernel reads
-      chk(hipMalloc(&b->d_feats, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
-  }
-  if (deltas) {     // the norm kernels' output at base_dim (and NORMALIZED host features at feat_dim), DeltaKernel's table and output
+  if (spec.any) UploadSpecTables(&c, spec.any, &b->d_any, chk);
+  // The rows of the SLIDING plan of an object with statistics; every other plan's are made by the set call that brings it
+  // about.  A wave batch has no such call for its audio (everything now); a features-only one gets its raw rows.
+  if (b->have_stats) chk(EnsureBuffers(b, b->features_only ? pkplan::kRawRows : BuffersFor(b, pkplan::kWaves, PK_MI355_NORM_SLIDING)));
+  if (deltas) {     // DeltaKernel's table
     float table[pkdelta::kMaxTable];
     pkdelta::BuildScales(*deltas, table);
     const size_t bytes = sizeof(float) * (size_t)(deltas->order + 1) * pkdelta::RowLen(*deltas);
-    chk(hipMalloc(&b->d_feats, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
-    chk(hipMalloc(&b->d_delta, sizeof(float) * (size_t)c.max_frames * am->feat_dim));
     chk(hipMalloc(&b->d_delta_scales, bytes));
     if (chk.ok) chk(hipMemcpy(b->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
   }
@@ -541,6 +536,43 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const float *global_stats, int ma
   }
   if (!chk.ok) { pk_mi355_batch_destroy(b); return nullptr; }
   return b;
+}
+
+// What a public create entry was handed.  stats41: 41 statistics by the entry's contract (a 40-dim model's; no
+// stats_len).  audio: the capacity is in samples and there is a front-end -- the spec's, or without one the reference's
+// 40 bins; else it is in frames.  null_arg: the entry found one of the pointers it needs null.
+struct BatchRequest {
+  const float *stats; int stats_len; bool stats41; int max_utts; int64_t capacity; bool audio, null_arg;
+  const pk_mi355_frontend_spec_t *frontend; const pk_mi355_deltas_spec_t *deltas;
+};
+// The argument checks of every public create entry, in the one order that names the fault each of them has always named,
+// also when several arguments are bad at once; an entry runs those its request gives rise to.
+pk_mi355_batch *CheckedBatch(pk_mi355_am_t *am, const BatchRequest &r) {
+  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (r.null_arg) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  const int D = am->feat_dim, order = r.deltas ? r.deltas->order : 0;
+  if (r.deltas && pkdelta::CheckSpec(r.deltas)) return nullptr;         // (names the field)
+  if (D % (order + 1) != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
+    return nullptr;
+  }
+  const int Db = D / (order + 1);
+  std::vector<FrontendAnyTables> any(r.frontend ? 1 : 0);
+  if (r.frontend && BuildFrontendAnyTables(r.frontend, any.data())) return nullptr;      // (names the field)
+  if (r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return nullptr;
+  if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr)) return nullptr;
+  // (pk_mi355_batch_create, the one audio entry without a spec, has always named its missing statistics here)
+  if (r.max_utts <= 0 || r.capacity <= 0 || (r.audio && !r.frontend && !r.stats)) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
+  if (r.stats && r.stats41 && D != kNumBins) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, D);
+    return nullptr;
+  }
+  if (IsF16(am->precision) && D % 8 != 0) {      // as pk_decodable_init: the spliced view of the split copy needs whole 8-k chunks
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", D);
+    return nullptr;
+  }
+  return CreateBatch(am, BatchSpec{r.stats, r.max_utts, r.audio ? r.capacity : 0, r.audio ? r.capacity / kFrameShift + r.max_utts : r.capacity,
+                                   PublicChunkCap(), r.frontend ? any.data() : nullptr, r.deltas});
 }
 
 // am->mu held.  One of the model's own one-utterance scorers for a call of `need` samples or frames: kept while the call
@@ -559,105 +591,34 @@ pk_mi355_batch *EnsureOwned(OwnedBatch *o, int64_t need, bool keep, Make make) {
 namespace pkhost {
 pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames) {      // (at least one whole pass: every pass is kSingleChunk rows)
   return EnsureOwned(&am->single, std::max(frames, kSingleChunk), true,
-                     [&](int64_t cap) { return CreateBatch(am, nullptr, 1, 0, cap, kSingleChunk); });
+                     [&](int64_t cap) { return CreateBatch(am, BatchSpec{nullptr, 1, 0, cap, kSingleChunk, nullptr, nullptr}); });
 }
 }  // namespace pkhost
 
 extern "C" {
 
 pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
-  if (!global_stats41 || max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  return CreateBatch(am, global_stats41, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts, PublicChunkCap());
+  return CheckedBatch(am, BatchRequest{global_stats41, 0, true, max_utts, max_total_samples, true, false, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_frames) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (max_utts <= 0 || max_total_frames <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  if (global_stats41 && am->feat_dim != kNumBins) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
-    return nullptr;
-  }
-  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_decodable_init: the spliced view of the split copy needs whole 8-k chunks
-    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
-    return nullptr;
-  }
-  return CreateBatch(am, global_stats41, max_utts, 0, max_total_frames, PublicChunkCap());
+  return CheckedBatch(am, BatchRequest{global_stats41, 0, true, max_utts, max_total_frames, false, false, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_utts,
                                                        int64_t max_total_frames) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (!global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (stats_len != am->feat_dim + 1) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
-         am->feat_dim + 1);
-    return nullptr;
-  }
-  if (am->feat_dim == kNumBins) return pk_mi355_features_batch_create(am, global_stats, max_utts, max_total_frames);
-  if (max_utts <= 0 || max_total_frames <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
-    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
-    return nullptr;
-  }
-  return CreateBatch(am, global_stats, max_utts, 0, max_total_frames, PublicChunkCap());
+  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, max_total_frames, false, !global_stats, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
                                                  int stats_len, int max_utts, int64_t max_total_samples) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (!spec || !global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  std::vector<FrontendAnyTables> any(1);
-  if (BuildFrontendAnyTables(spec, any.data())) return nullptr;      // (names the field)
-  if (any[0].dim != am->feat_dim) {
-    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model expects %d", any[0].dim, am->feat_dim);
-    return nullptr;
-  }
-  if (stats_len != am->feat_dim + 1) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
-         am->feat_dim + 1);
-    return nullptr;
-  }
-  if (max_utts <= 0 || max_total_samples <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
-    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
-    return nullptr;
-  }
-  return CreateBatch(am, global_stats, max_utts, max_total_samples, max_total_samples / kFrameShift + max_utts, PublicChunkCap(), any.data());
+  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, max_total_samples, true, !spec || !global_stats, spec, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
                                                const float *global_stats, int stats_len, int max_utts, int64_t capacity) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (!deltas || (frontend && !global_stats)) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pkdelta::CheckSpec(deltas)) return nullptr;                    // (names the field)
-  const int blocks = deltas->order + 1;
-  if (am->feat_dim % blocks != 0) {
-    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", deltas->order, blocks, am->feat_dim);
-    return nullptr;
-  }
-  const int Db = am->feat_dim / blocks;
-  std::vector<FrontendAnyTables> any(frontend ? 1 : 0);
-  if (frontend) {
-    if (BuildFrontendAnyTables(frontend, any.data())) return nullptr;      // (names the field)
-    if (any[0].dim != Db) {
-      Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model's %d with deltas of order %d need %d", any[0].dim, am->feat_dim,
-           deltas->order, Db);
-      return nullptr;
-    }
-  }
-  if (global_stats && stats_len != Db + 1) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, %d-dim base features need %d (the sums, then the count)", stats_len, Db, Db + 1);
-    return nullptr;
-  }
-  if (max_utts <= 0 || capacity <= 0) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  if (IsF16(am->precision) && am->feat_dim % 8 != 0) {      // as pk_mi355_features_batch_create
-    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", am->feat_dim);
-    return nullptr;
-  }
-  if (frontend) return CreateBatch(am, global_stats, max_utts, capacity, capacity / kFrameShift + max_utts, PublicChunkCap(), any.data(), deltas);
-  return CreateBatch(am, global_stats, max_utts, 0, capacity, PublicChunkCap(), nullptr, deltas);
+  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !deltas || (frontend && !global_stats),
+                                       frontend, deltas});
 }
 
 int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b) { return b ? b->base_dim : 0; }
@@ -799,16 +760,13 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
   if (int rc = CheckFeatureCounts(b, frames.data(), num_utts)) return rc;
   if (int rc = UseDevice(b->core.device)) return rc;
   // RAW: where FbankKernel would have written them; NORMALIZED: the staging FeatureLayoutKernel reads
-  if (kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins)
-    if (int rc = EnsureFeatsStaging(b)) return rc;
-  if (kind == PK_MI355_FEATS_RAW)
-    if (int rc = EnsureRawRows(b)) return rc;
+  HIP_TRY(EnsureBuffers(b, kind == PK_MI355_FEATS_RAW ? BuffersFor(b, pkplan::kRaw, b->norm.mode) : pkplan::kFeatRows));
   float *dst = b->d_raw;
   if (kind == PK_MI355_FEATS_NORMALIZED) dst = b->d_feats;
   // The layout first: its upload travels while the host stages the features below (a copy out of pageable memory
   // holds the host until it is done), and the first kernel of the score call is then queued straight behind them.
   if (int rc = SetLayoutFrames(b, frames.data(), nullptr, num_utts)) return rc;
-  b->source = pk_mi355_batch::kNone;             // (until the features are there too)
+  b->source = pkplan::kNoSource;             // (until the features are there too)
   int64_t row = 0;
   for (int u = 0; u < num_utts; ++u) {
     if (frames[u] > 0)
@@ -816,7 +774,7 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
     row += frames[u];
   }
   if (kind == PK_MI355_FEATS_NORMALIZED) b->feats = b->d_feats;
-  b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
+  b->source = kind == PK_MI355_FEATS_RAW ? pkplan::kRaw : pkplan::kNormalized;
   return 0;
 }
 
@@ -827,9 +785,7 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
   if (int rc = UseDevice(b->core.device)) return rc;
   if (kind == PK_MI355_FEATS_RAW) {                     // CMVN reads around every utterance: into d_raw with its lead and slack
     const int D = b->base_dim;                          // (any other dimension than 40: as a host call's rows, fetch_fbank's source)
-    if (D != kNumBins)
-      if (int rc = EnsureFeatsStaging(b)) return rc;
-    if (int rc = EnsureRawRows(b)) return rc;
+    HIP_TRY(EnsureBuffers(b, BuffersFor(b, pkplan::kRaw, b->norm.mode)));
     int64_t total = 0;
     for (int u = 0; u < num_utts; ++u) total += num_frames[u];
     if (total > 0)
@@ -837,17 +793,17 @@ int pk_mi355_features_set_device(pk_mi355_batch_t *b, const float *d_feats, cons
   }
   if (int rc = SetLayoutFrames(b, num_frames, nullptr, num_utts)) return rc;
   if (kind == PK_MI355_FEATS_NORMALIZED) b->feats = d_feats;   // read where they lie
-  b->source = kind == PK_MI355_FEATS_RAW ? pk_mi355_batch::kRaw : pk_mi355_batch::kNormalized;
+  b->source = kind == PK_MI355_FEATS_RAW ? pkplan::kRaw : pkplan::kNormalized;
   return 0;
 }
 
 int pk_mi355_norm_set(pk_mi355_batch_t *b, const pk_mi355_norm_spec_t *spec) {
   if (!b || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
   if (int rc = pknorm::CheckSpec(spec)) return rc;      // (names the field)
+  if (int rc = UseDevice(b->core.device)) return rc;
+  HIP_TRY(EnsureBuffers(b, BuffersFor(b, pkplan::kRaw, spec->mode)));      // (audio needs the same rows)
   if (spec->mode != PK_MI355_NORM_SLIDING) {            // what NormKernel writes and reads, made at the first spec that needs it
-    if (int rc = UseDevice(b->core.device)) return rc;
     const size_t D = (size_t)b->base_dim;
-    if (int rc = EnsureFeatsStaging(b)) return rc;
     if (!b->d_norm_stats) HIP_TRY(hipMalloc(&b->d_norm_stats, sizeof(double) * 2 * (D + 1) * (size_t)b->max_utts));
     if (!b->d_spk_table) HIP_TRY(hipMalloc(&b->d_spk_table, sizeof(float) * 2 * D * (size_t)b->max_utts));
   }
@@ -861,7 +817,7 @@ int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmv
   const size_t D = (size_t)b->base_dim;
   if (int rc = pknorm::CheckOnlineSpec(spec, global_stats, (int)D)) return rc;      // (names the field)
   if (int rc = UseDevice(b->core.device)) return rc;
-  if (int rc = EnsureFeatsStaging(b)) return rc;
+  HIP_TRY(EnsureBuffers(b, BuffersFor(b, pkplan::kRaw, pknorm::kNormOnlineCmvn)));
   const size_t rec = 2 * (D + 1);
   if (!b->d_online_glob) HIP_TRY(hipMalloc(&b->d_online_glob, sizeof(double) * rec));
   if (!b->d_online_spk) HIP_TRY(hipMalloc(&b->d_online_spk, sizeof(double) * rec * (size_t)b->max_utts));
@@ -913,7 +869,7 @@ int pk_mi355_norm_fetch_stats(pk_mi355_batch_t *b, int utt, double *out) {
 
 int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   if (!b) return Fail(PK_MI355_E_INVALID, "null batch");
-  if (b->source == pk_mi355_batch::kNone) return Fail(PK_MI355_E_STATE, "no waves or features set");
+  if (b->source == pkplan::kNoSource) return Fail(PK_MI355_E_STATE, "no waves or features set");
   ScorerCore &c = b->core;
   int rc = UseDevice(c.device);
   if (rc) return rc;
@@ -933,8 +889,8 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   b->norm_stats_valid = false;
   const int D = am->feat_dim;
   const int Db = b->base_dim;                    // the dimension in front of the deltas (D without them)
-  const int mode = b->source == pk_mi355_batch::kNormalized ? PK_MI355_NORM_NONE : b->norm.mode;
-  if (b->source != pk_mi355_batch::kNormalized) {
+  const int mode = b->source == pkplan::kNormalized ? PK_MI355_NORM_NONE : b->norm.mode;
+  if (b->source != pkplan::kNormalized) {
     if (mode == PK_MI355_NORM_SLIDING && !b->have_stats)
       return Fail(PK_MI355_E_STATE, "raw features in mode sliding need the CMVN statistics: this batch was made without them");
     if (mode == PK_MI355_NORM_SPEAKER && spk_utts < 0)
@@ -953,47 +909,40 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     return 0;
   }
   const UttLayout &lay = b->lay;
-  if (b->source == pk_mi355_batch::kWaves) {
+  // The plan (pk_plan.h; DESIGN.md, "The two plans"): the front-end, then raw rows (fbank's, or the caller's) or
+  // normalised features -> Yt.  What it reads and writes was made by create and the set calls (EnsureBuffers).
+  const pkplan::BatchPlan plan = pkplan::PlanBatch(ShapeOf(b), b->source, b->norm.mode, spk_utts >= 0);
+  auto own = [b](pkplan::Rows r) { return r == pkplan::kRawRows ? b->d_raw : r == pkplan::kFeatRows ? b->d_feats : b->d_delta; };
+  auto run = [&](int first, int last) {
+    for (int k = first; k < last; ++k) {
+      const pkplan::Step &st = plan.step[k];
+      const float *in = st.in == pkplan::kCallerRows ? b->feats : own(st.in);
+      float *out = own(st.out);                  // (the stages that write Yt do not look at it)
+      switch (st.stage) {
+        case pkplan::kFbank: LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, out, c.stream); break;
+        case pkplan::kFbankAny: LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, st.dim, out, c.stream); break;
+        case pkplan::kCmvn: LaunchCmvn(in, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream); break;
+        case pkplan::kCmvnChain: LaunchCmvnChain(in, lay, b->num_utts, st.dim, c.d_global, c.d_cmvn_tab, out, c.stream); break;
+        case pkplan::kNorm:
+          LaunchNorm(in, lay, b->num_utts, st.dim, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats, out, c.stream);
+          break;
+        case pkplan::kOnlineCmvn:
+          LaunchOnlineCmvn(in, lay, b->num_utts, st.dim, b->online_cmvn, b->d_online_glob, plan.speaker ? b->d_online_spk : nullptr, out, c.stream);
+          break;
+        case pkplan::kDelta: LaunchDelta(in, lay, b->num_utts, b->max_T, st.dim, b->deltas, b->d_delta_scales, out, c.stream); break;
+        case pkplan::kFeatureLayout: LaunchFeatureLayout(in, lay, b->num_utts, b->max_T, st.dim, am->left, am->right, c.d_yt, c.ldy, c.stream); break;
+      }
+    }
+  };
+  if (plan.front) {
     Scoped t(tm, PK_MI355_K_FBANK, c.stream);
-    if (b->d_any) LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, Db, b->d_raw, c.stream);
-    else LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_raw, c.stream);
+    run(0, plan.front);
   }
-  {                                            // raw rows (fbank's, or the caller's) or normalised features -> Yt
+  {
     Scoped t(tm, PK_MI355_K_CMVN, c.stream);
-    if (b->source == pk_mi355_batch::kNormalized)
-      LaunchFeatureLayout(b->feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else if (b->has_deltas) {                   // the normalisation at Db (none: the raw rows), DeltaKernel, the layout of its result
-      const float *rows = b->d_feats;
-      if (mode == PK_MI355_NORM_NONE)
-        rows = b->d_raw;
-      else if (mode == pknorm::kNormOnlineCmvn)
-        LaunchOnlineCmvn(b->d_raw, lay, b->num_utts, Db, b->online_cmvn, b->d_online_glob, spk_utts >= 0 ? b->d_online_spk : nullptr, b->d_feats,
-                         c.stream);
-      else if (mode != PK_MI355_NORM_SLIDING) {
-        LaunchNorm(b->d_raw, lay, b->num_utts, Db, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats,
-                   b->d_feats, c.stream);
-        b->norm_stats_valid = mode == PK_MI355_NORM_UTTERANCE;
-      } else                                    // (at Db = 40 too: CmvnKernel would write the layout itself)
-        LaunchCmvnChain(b->d_raw, lay, b->num_utts, Db, c.d_global, c.d_cmvn_tab, b->d_feats, c.stream);
-      LaunchDelta(rows, lay, b->num_utts, b->max_T, Db, b->deltas, b->d_delta_scales, b->d_delta, c.stream);
-      LaunchFeatureLayout(b->d_delta, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    } else if (mode == PK_MI355_NORM_NONE)      // the raw rows as they are (at D = 40: d_raw, behind CmvnKernel's lead)
-      LaunchFeatureLayout(b->d_raw, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    else if (mode == pknorm::kNormOnlineCmvn) {   // OnlineCmvnKernel, then the layout of its result
-      LaunchOnlineCmvn(b->d_raw, lay, b->num_utts, D, b->online_cmvn, b->d_online_glob, spk_utts >= 0 ? b->d_online_spk : nullptr, b->d_feats,
-                       c.stream);
-      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    } else if (mode != PK_MI355_NORM_SLIDING) { // NormKernel, then the layout of its result
-      LaunchNorm(b->d_raw, lay, b->num_utts, D, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats,
-                 b->d_feats, c.stream);
-      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-      b->norm_stats_valid = mode == PK_MI355_NORM_UTTERANCE;
-    } else if (D != kNumBins) {                  // raw rows at the model's own dimension: the chain, then the layout of its result
-      LaunchCmvnChain(b->d_raw, lay, b->num_utts, D, c.d_global, c.d_cmvn_tab, b->d_feats, c.stream);
-      LaunchFeatureLayout(b->d_feats, lay, b->num_utts, b->max_T, D, am->left, am->right, c.d_yt, c.ldy, c.stream);
-    } else
-      LaunchCmvn(b->d_raw, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream);
+    run(plan.front, plan.n);
   }
+  b->norm_stats_valid = plan.writes_stats;
   // Rows of the layer stack: compact (row out_base[u] + t is frame t of utterance u; the first layer finds its
   // features shift4[row / 4] columns -- f16 modes: rows of the split copy -- further on; no shift4 when all are zero).
   const bool f16 = IsF16(am->precision);
@@ -1041,7 +990,7 @@ int pk_mi355_batch_calibrate(pk_mi355_batch_t *b) {
   if (!b) return Fail(PK_MI355_E_INVALID, "null batch");
   pk_mi355_am *am = b->core.am;
   if (!IsF16(am->precision)) return 0;
-  if (b->source == pk_mi355_batch::kNone) return Fail(PK_MI355_E_STATE, "no waves or features set");
+  if (b->source == pkplan::kNoSource) return Fail(PK_MI355_E_STATE, "no waves or features set");
   if (b->total_frames == 0) return Fail(PK_MI355_E_INVALID, "calibration needs at least one frame");
   if (int rc = UseDevice(b->core.device)) return rc;
   std::lock_guard<std::mutex> lock(am->mu);
@@ -1144,7 +1093,7 @@ int pk_mi355_batch_fetch_all(pk_mi355_batch_t *b, pk_decodable_t *out, int num_o
 int pk_mi355_batch_fetch_fbank(pk_mi355_batch_t *b, int utt, float *out) {
   if (!b || !out || utt < 0 || utt >= b->num_utts) return Fail(PK_MI355_E_INVALID, "bad utterance index");
   if (!b->scored) return Fail(PK_MI355_E_STATE, "batch not scored");
-  if (b->source == pk_mi355_batch::kNormalized) return Fail(PK_MI355_E_STATE, "the batch was fed normalised features: there is no fbank");
+  if (b->source == pkplan::kNormalized) return Fail(PK_MI355_E_STATE, "the batch was fed normalised features: there is no fbank");
   const int T = b->h_T[utt];
   if (T == 0) return 0;
   const int D = b->base_dim;                   // (the front-end's dimension)

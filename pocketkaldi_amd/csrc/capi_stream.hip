@@ -9,6 +9,7 @@
 
 #include "pk_frontend.h"
 #include "pk_norm_kernel.h"
+#include "pk_plan.h"
 #include "pk_resample.h"
 #include "pk_score.h"
 
@@ -179,34 +180,53 @@ const float *StreamLoglikBase(const pk_mi355_stream *s) { return s->core.d_ll; }
 bool StreamSlotFlushed(const pk_mi355_stream *s, int slot) { return slot >= 0 && slot < s->max_streams && s->slots[slot].last_flushed; }
 }  // namespace pkhost
 
-extern "C" {
+namespace {
+// What the create entries differ in.  entry: the name in a device failure's text.  audio: live PCM through a front-end
+// (any: the tables of a front-end spec, or null for the reference's 40 bins), step_cap in samples; else features
+// only, step_cap in frames.  stats: null (features only), or am->feat_dim sums and the count.
+struct StreamShape { const char *entry; bool audio; const float *stats; const FrontendAnyTables *any; int max_streams; int64_t step_cap; };
 
-pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples) {
-  if (!ModelAllowed(am)) return nullptr;
-  if (am->feat_dim != kNumBins) { Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", kNumBins, am->feat_dim); return nullptr; }
-  if (!global_stats41 || max_streams <= 0 || max_step_samples <= 0 || max_step_samples > (int64_t)1 << 30) {
+// Every way to a stream object; the entries have checked their other arguments.
+pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
+  const int D = am->feat_dim, max_streams = sh.max_streams;
+  // (pk_mi355_stream_create, the one audio entry whose statistics can still be missing here, has always named that so)
+  if (max_streams <= 0 || sh.step_cap <= 0 || sh.step_cap > ((int64_t)1 << 30) / (sh.audio ? 1 : D) || (sh.audio && !sh.stats)) {
     Fail(PK_MI355_E_INVALID, "bad stream capacity");
     return nullptr;
   }
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_stream *s = new pk_mi355_stream();
-  ScorerCore &c = s->core;
-  s->max_streams = max_streams; s->max_step_samples = max_step_samples;
-  s->have_stats = true; s->upload_cap = max_step_samples;
+  s->max_streams = max_streams; s->max_step_samples = sh.step_cap;
+  s->features_only = !sh.audio; s->have_stats = sh.stats != nullptr;
+  s->frame_cost = sh.audio ? kFrameShift : 1;
   s->slots.resize(max_streams);
-  const int pad = am->left + am->right;
-  s->hist_len = std::max(pad, 1);
-  // a slot's segment holds at most 399 carried samples and its pushes; its rows are its new frames and the (at most R)
-  // frames held back for look-ahead, padded to four
-  s->wave_cap = max_step_samples + (int64_t)max_streams * kTailCap;
-  const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
-  CreateCheck chk{"stream_create"};
-  CreateScorerCore(&c, am, global_stats41, kNumBins, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  s->hist_len = std::max(am->left + am->right, 1);
+  // Audio: a slot's segment holds at most 399 carried samples and its pushes.  A slot's rows are its new frames and the
+  // (at most R) frames held back for look-ahead, padded to four.
+  s->wave_cap = sh.audio ? sh.step_cap + (int64_t)max_streams * kTailCap : 0;
+  const int64_t max_frames = sh.audio ? s->wave_cap / kFrameShift + max_streams : sh.step_cap;
+  // Audio at D == 40: the fbank writes d_rows, where StreamCmvnKernel reads.  At another dimension the staging holds the
+  // step's samples (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
+  s->rows_area = sh.audio && D != kNumBins ? RoundUp(sh.step_cap, 64) : 0;
+  s->upload_cap = !sh.audio ? sh.step_cap * D : s->rows_area ? s->rows_area + max_frames * D : sh.step_cap;
+  CreateCheck chk{sh.entry};
+  CreateScorerCore(&s->core, am, sh.stats, D, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  if (sh.any) UploadSpecTables(&s->core, sh.any, &s->d_any, chk);
   CreateStepBuffers(s, chk);
-  chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
-  chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
+  if (sh.audio) {
+    chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
+    chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
+  }
   if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
   return s;
+}
+}  // namespace
+
+extern "C" {
+
+pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples) {
+  if (!ModelAllowed(am) || !FrontendFits(kNumBins, false, am, am->feat_dim, 0)) return nullptr;
+  return CreateStream(am, StreamShape{"stream_create", true, global_stats41, nullptr, max_streams, max_step_samples});
 }
 
 pk_mi355_stream_t *pk_mi355_frontend_stream_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
@@ -214,73 +234,9 @@ pk_mi355_stream_t *pk_mi355_frontend_stream_create(pk_mi355_am_t *am, const pk_m
   if (!am || !spec || !global_stats) { Fail(PK_MI355_E_INVALID, am ? "null argument" : "null model"); return nullptr; }
   std::vector<FrontendAnyTables> any(1);
   if (BuildFrontendAnyTables(spec, any.data())) return nullptr;      // (names the field)
-  if (!ModelAllowed(am)) return nullptr;
-  const int D = am->feat_dim;
-  if (any[0].dim != D) {
-    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model expects %d", any[0].dim, D);
-    return nullptr;
-  }
-  if (stats_len != D + 1) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, D, D + 1);
-    return nullptr;
-  }
-  if (max_streams <= 0 || max_step_samples <= 0 || max_step_samples > (int64_t)1 << 30) {
-    Fail(PK_MI355_E_INVALID, "bad stream capacity");
-    return nullptr;
-  }
-  if (UseDevice(am->device)) return nullptr;
-  pk_mi355_stream *s = new pk_mi355_stream();
-  ScorerCore &c = s->core;
-  s->max_streams = max_streams; s->max_step_samples = max_step_samples;
-  s->have_stats = true;
-  s->slots.resize(max_streams);
-  s->hist_len = std::max(am->left + am->right, 1);
-  // segments, frames and rows as pk_mi355_stream_create counts them
-  s->wave_cap = max_step_samples + (int64_t)max_streams * kTailCap;
-  const int64_t max_frames = s->wave_cap / kFrameShift + max_streams;
-  // D == 40: FbankAnyKernel writes d_rows, where StreamCmvnKernel reads.  Otherwise the staging holds the step's samples
-  // (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
-  s->rows_area = D == kNumBins ? 0 : RoundUp(max_step_samples, 64);
-  s->upload_cap = D == kNumBins ? max_step_samples : s->rows_area + max_frames * D;
-  CreateCheck chk{"frontend_stream_create"};
-  CreateScorerCore(&c, am, global_stats, D, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
-  if (!c.d_tables && chk.ok) {                       // (the scorer core makes FbankKernel's tables for 40-dim statistics only)
-    FrontendTables host;
-    if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
-    chk(hipMalloc(&c.d_tables, sizeof(FrontendTables)));
-    if (chk.ok) chk(hipMemcpy(c.d_tables, &host, sizeof(FrontendTables), hipMemcpyHostToDevice));
-  }
-  chk(hipMalloc(&s->d_any, sizeof(FrontendAnyTables)));
-  if (chk.ok) chk(hipMemcpy(s->d_any, any.data(), sizeof(FrontendAnyTables), hipMemcpyHostToDevice));
-  CreateStepBuffers(s, chk);
-  chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
-  chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
-  if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
-  return s;
+  if (!ModelAllowed(am) || !FrontendFits(any[0].dim, true, am, am->feat_dim, 0) || !StatsLenFits(stats_len, am->feat_dim, false)) return nullptr;
+  return CreateStream(am, StreamShape{"frontend_stream_create", true, global_stats, any.data(), max_streams, max_step_samples});
 }
-
-namespace {
-// global_stats: null, or am->feat_dim sums and the count
-pk_mi355_stream *CreateFeaturesStream(pk_mi355_am_t *am, const float *global_stats, int max_streams, int64_t max_step_frames) {
-  if (max_streams <= 0 || max_step_frames <= 0 || max_step_frames > ((int64_t)1 << 30) / am->feat_dim) {
-    Fail(PK_MI355_E_INVALID, "bad stream capacity");
-    return nullptr;
-  }
-  if (UseDevice(am->device)) return nullptr;
-  pk_mi355_stream *s = new pk_mi355_stream();
-  s->max_streams = max_streams; s->max_step_samples = max_step_frames;
-  s->features_only = true; s->have_stats = global_stats != nullptr;
-  s->frame_cost = 1; s->upload_cap = max_step_frames * am->feat_dim;
-  s->slots.resize(max_streams);
-  s->hist_len = std::max(am->left + am->right, 1);
-  // a slot's rows are its new frames and the (at most R) frames held back for look-ahead, padded to four
-  CreateCheck chk{"features_stream_create"};
-  CreateScorerCore(&s->core, am, global_stats, am->feat_dim, max_streams, max_step_frames, max_step_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
-  CreateStepBuffers(s, chk);
-  if (!chk.ok) { pk_mi355_stream_destroy(s); return nullptr; }
-  return s;
-}
-}  // namespace
 
 pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames) {
   if (!ModelAllowed(am)) return nullptr;
@@ -288,19 +244,15 @@ pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const floa
     Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
     return nullptr;
   }
-  return CreateFeaturesStream(am, global_stats41, max_streams, max_step_frames);
+  return CreateStream(am, StreamShape{"features_stream_create", false, global_stats41, nullptr, max_streams, max_step_frames});
 }
 
 pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_streams,
                                                          int64_t max_step_frames) {
   if (!ModelAllowed(am)) return nullptr;
   if (!global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (stats_len != am->feat_dim + 1) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, am->feat_dim,
-         am->feat_dim + 1);
-    return nullptr;
-  }
-  return CreateFeaturesStream(am, global_stats, max_streams, max_step_frames);
+  if (!StatsLenFits(stats_len, am->feat_dim, false)) return nullptr;
+  return CreateStream(am, StreamShape{"features_stream_create", false, global_stats, nullptr, max_streams, max_step_frames});
 }
 
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s) {
@@ -717,63 +669,26 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   const int64_t *d_rawb = d_woff + s->max_streams;
   const int32_t *d_T = reinterpret_cast<const int32_t *>(d_rawb + s->max_streams);
   UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
-  if (s->rows_area) {
-    // A front-end spec at D != 40: assembly and fbank over the n_front audio records, the rows
-    // [raw_base][D] going to the staging's row area; then every record through the chain (audio and RAW ones are
-    // normalised where they lie, NORMALIZED ones return) and through the layout, which reads what the chain leaves.
-    const int n_recs = n_front + n_back;
-    if (n_audio > 0) {
-      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
-      LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_upload + s->rows_area, c.stream);
-    }
-    if ((max_m > 0 || chain_pushed > 0) && sliding)
-      LaunchStreamCmvnChain(d_recs, n_recs, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
-    else if ((max_m > 0 || chain_pushed > 0) && nmode != PK_MI355_NORM_NONE)
-      LaunchStreamNorm(d_recs, n_recs, D, s->d_upload, NormState(s), c.stream);
-    LaunchStreamFeatureLayout(d_recs, n_recs, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
-  } else if (!sliding) {
-    // A norm spec on every other object: the audio records' rows (40-dim: FbankKernel's or the spec's kernel's, in d_rows)
-    // and the back records' (RAW ones normalised where they were pushed) each through StreamNormKernel -- mode none:
-    // through nothing -- and the layout.
-    if (n_audio > 0) {
-      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
-      if (s->d_any)
-        LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_rows, c.stream);
-      else
-        LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
-    }
-    if (n_front > 0) {
-      if (max_m > 0 && nmode != PK_MI355_NORM_NONE) LaunchStreamNorm(d_recs, n_front, D, s->d_rows, NormState(s), c.stream);
-      LaunchStreamFeatureLayout(d_recs, n_front, max_feat_cols, s->d_rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
-    }
-    if (n_back > 0) {
-      if (chain_pushed > 0 && nmode != PK_MI355_NORM_NONE)
-        LaunchStreamNorm(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, NormState(s), c.stream);
-      LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
-                                c.d_yt, c.ldy, c.stream);
-    }
-  } else {
-    // Every other object, as ever.  A step of audio slots alone: assembly, fbank (the spec's kernel on a spec'd 40-dim
-    // object, into the same rows) and StreamCmvnKernel over the n_front front records.  RAW slots at 40 ride along with an
-    // empty segment and T = 0; their pushed rows reach d_rows by one launch more per step.  The back records -- NORMALIZED
-    // slots, and RAW ones at another dimension, which the chain normalises first -- go through the layout.
-    if (n_audio > 0) {
-      LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
-      if (s->d_any)
-        LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, s->d_rows, c.stream);
-      else
-        LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_rows, c.stream);
-    }
-    if (raw_pushed > 0) LaunchStreamRawRows(d_recs, n_front, s->d_upload, s->d_rows, c.stream);
-    if (n_front > 0)
-      LaunchStreamCmvn(d_recs, n_front, s->d_rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R,
-                       c.d_yt, c.ldy, c.stream);
-    if (chain_pushed > 0)                // before the layout: it reads the rows the chain leaves behind
-      LaunchStreamCmvnChain(d_recs + (s->max_streams - n_back), n_back, D, s->d_upload, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist,
-                            c.stream);
-    if (n_back > 0)
-      LaunchStreamFeatureLayout(d_recs + (s->max_streams - n_back), n_back, max_feat_cols, s->d_upload, s->d_feat_hist, s->hist_len, D, L, R,
-                                c.d_yt, c.ldy, c.stream);
+  // The plan (pk_plan.h; DESIGN.md, "The two plans").  The front stage: assembly and fbank over the n_front front records,
+  // the rows [raw_base][D] going to d_rows, or on an object with a row area to the staging behind the samples.
+  const pkplan::StreamPlan plan = pkplan::PlanStream(s->rows_area != 0, nmode, pkplan::StepCounts{n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed});
+  if (plan.front) {
+    float *dst = s->rows_area ? s->d_upload + s->rows_area : s->d_rows;
+    LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
+    if (s->d_any) LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, dst, c.stream);
+    else LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, dst, c.stream);
+  }
+  // Then every block of records through its normaliser (the back block's before its layout, which reads the rows the
+  // normaliser leaves behind) and its layout.
+  for (int k = 0; k < plan.n; ++k) {
+    const pkplan::Block &bl = plan.block[k];
+    const StreamRec *r = d_recs + (bl.back ? s->max_streams - n_back : 0);
+    float *rows = bl.step_rows ? s->d_rows : s->d_upload;
+    if (bl.raw_rows) LaunchStreamRawRows(r, bl.count, s->d_upload, s->d_rows, c.stream);
+    if (bl.norm == pkplan::kStreamNorm) LaunchStreamNorm(r, bl.count, D, rows, NormState(s), c.stream);
+    else if (bl.norm == pkplan::kStreamCmvnChain) LaunchStreamCmvnChain(r, bl.count, D, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
+    if (bl.fused) LaunchStreamCmvn(r, bl.count, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R, c.d_yt, c.ldy, c.stream);
+    else LaunchStreamFeatureLayout(r, bl.count, max_feat_cols, rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
   }
   const Operand op{c.d_yt, nullptr, c.ldy, ZeroSource(c), reinterpret_cast<const int32_t *>(s->d_meta + shift4_at)};
   const Lane lane{c.stream, &c.exec};

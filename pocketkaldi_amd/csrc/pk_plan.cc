@@ -1,0 +1,67 @@
+// pk_plan.cc -- the stage plans of the batch and the online scorer (pk_plan.h; DESIGN.md, "The two plans").
+#include "pk_plan.h"
+
+namespace pkplan {
+
+BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given) {
+  BatchPlan p;
+  auto add = [&p](Stage stage, Rows in, Rows out, int dim) {
+    p.step[p.n++] = Step{stage, in, out, dim};
+    p.buffers |= (in | out) & kOwnRows;
+  };
+  if (source == kNormalized) {                        // the mode is ignored
+    add(kFeatureLayout, kCallerRows, kYt, o.D);
+    return p;
+  }
+  if (source == kNoSource || (mode == PK_MI355_NORM_SLIDING && !o.stats)) return p;
+  if (source == kWaves) {
+    add(o.spec ? kFbankAny : kFbank, kNoRows, kRawRows, o.Db);
+    p.front = 1;
+  }
+  Rows rows = kFeatRows;                              // the normalisation at Db, from d_raw
+  switch (mode) {
+    case PK_MI355_NORM_NONE: rows = kRawRows; break;
+    case pknorm::kNormOnlineCmvn:
+      add(kOnlineCmvn, kRawRows, kFeatRows, o.Db);
+      p.speaker = speaker_given;
+      break;
+    case PK_MI355_NORM_UTTERANCE:
+    case PK_MI355_NORM_SPEAKER:
+      add(kNorm, kRawRows, kFeatRows, o.Db);
+      p.writes_stats = mode == PK_MI355_NORM_UTTERANCE;
+      break;
+    default:                                          // SLIDING
+      if (FusedCmvn(o)) {
+        add(kCmvn, kRawRows, kYt, o.Db);
+        return p;
+      }
+      add(kCmvnChain, kRawRows, kFeatRows, o.Db);
+  }
+  if (o.deltas) {
+    add(kDelta, rows, kDeltaRows, o.Db);
+    rows = kDeltaRows;
+  }
+  add(kFeatureLayout, rows, kYt, o.D);
+  return p;
+}
+
+StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k) {
+  StreamPlan p;
+  p.front = k.n_audio > 0;
+  const bool sliding = mode == PK_MI355_NORM_SLIDING;
+  // what normalises fresh rows outside StreamCmvnKernel's fused path (mode none: nothing)
+  const StreamNormaliser norm = sliding ? kStreamCmvnChain : mode == PK_MI355_NORM_NONE ? kNoNormaliser : kStreamNorm;
+  if (row_area) {       // audio, RAW and NORMALIZED records in one block, all rows in the staging (NORMALIZED ones return from the normaliser)
+    p.block[p.n++] = Block{false, k.n_front + k.n_back, false, false, k.max_m > 0 || k.chain_pushed > 0 ? norm : kNoNormaliser, false};
+    return p;
+  }
+  if (k.n_front > 0 && sliding)                       // audio and RAW records at 40 dimensions
+    p.block[p.n++] = Block{false, k.n_front, true, k.raw_pushed > 0, kNoNormaliser, true};
+  else if (k.n_front > 0)                             // a norm spec: audio records alone, laid out from d_rows
+    p.block[p.n++] = Block{false, k.n_front, true, false, k.max_m > 0 ? norm : kNoNormaliser, false};
+  if (k.n_back > 0)                                   // NORMALIZED records, and the RAW ones normalised where they were pushed
+    p.block[p.n++] = Block{true, k.n_back, false, false, k.chain_pushed > 0 ? norm : kNoNormaliser, false};
+  return p;
+}
+
+}  // namespace pkplan

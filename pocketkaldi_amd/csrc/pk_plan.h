@@ -1,0 +1,54 @@
+// pk_plan.h -- which launches a scorer makes between the audio (or the features handed over) and the splice, as pure
+// functions of what the object is and what the call brings ("The two plans").  pk_mi355_batch_score and
+// pk_mi355_stream_step execute what these return and decide nothing themselves.  Plain C++: no HIP header; pk_plan.cc is
+// compiled by g++ like pk_norm.cc and builds into a stand-alone program (tests/cpp/plan_test.cc).  Internal.
+#ifndef PK_PLAN_H_
+#define PK_PLAN_H_
+
+#include "pk_norm.h"
+
+namespace pkplan {
+
+// ------------------------------------------------------------------ the batch scorer
+enum Source { kNoSource, kWaves, kRaw, kNormalized };      // what the last set call handed over
+enum Stage { kFbank, kFbankAny, kCmvn, kCmvnChain, kNorm, kOnlineCmvn, kDelta, kFeatureLayout };
+// Where a stage reads and writes.  The first three are the batch's own buffers (d_raw, d_feats, d_delta) and double as
+// the bits of BatchPlan::buffers; kCallerRows: the normalised features handed over, where they lie.
+enum Rows { kNoRows = 0, kRawRows = 1, kFeatRows = 2, kDeltaRows = 4, kCallerRows = 8, kYt = 16 };
+constexpr unsigned kOwnRows = kRawRows | kFeatRows | kDeltaRows;
+
+struct BatchShape { int Db, D; bool spec, deltas, stats; };   // base and model dimension; front-end spec, deltas, CMVN statistics
+struct Step { Stage stage; Rows in, out; int dim; };
+struct BatchPlan {
+  int n = 0, front = 0;          // steps, and how many of them (0 or 1, the first) are the front-end
+  Step step[4];
+  bool speaker = false;          // kOnlineCmvn smooths with the speaker records handed over for this call
+  bool writes_stats = false;     // kNorm in mode UTTERANCE leaves every utterance's record behind
+  unsigned buffers = 0;          // the own rows the steps read or write
+};
+// SLIDING at 40 dimensions without deltas: CmvnKernel normalises and writes Yt itself, and reads around every utterance --
+// the one plan whose d_raw needs the lead and the slack.
+inline bool FusedCmvn(const BatchShape &o) { return o.stats && !o.deltas && o.Db == 40; }
+// mode: PK_MI355_NORM_* or pknorm::kNormOnlineCmvn.  Empty for what score refuses in front of the plan (nothing set;
+// SLIDING on raw rows or audio without statistics).
+BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given);
+
+// ------------------------------------------------------------------ the online scorer
+enum StreamNormaliser { kNoNormaliser, kStreamNorm, kStreamCmvnChain };
+// A run of records that goes through one normaliser and one layout.  back: the records at the array's end (the last
+// n_back), else those from record 0.  step_rows: the rows lie in d_rows (the fbank's), else in the upload staging.
+// raw_rows: StreamRawRowsKernel first copies the RAW records' pushed rows to d_rows.  fused: StreamCmvnKernel normalises
+// and lays out in one launch; else the normaliser (if any), then StreamFeatureLayoutKernel.
+struct Block { bool back; int count; bool step_rows, raw_rows; StreamNormaliser norm; bool fused; };
+struct StepCounts { int n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed; };
+struct StreamPlan {
+  bool front = false;            // StreamAssembleKernel and the fbank run over the n_front front records
+  int n = 0;
+  Block block[2];
+};
+// row_area: an object with a front-end spec at another dimension than 40, whose fresh rows all lie in the upload staging.
+StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k);
+
+}  // namespace pkplan
+
+#endif  // PK_PLAN_H_

@@ -6,6 +6,7 @@
 
 #include <functional>
 
+#include "pk_frontend.h"
 #include "pk_host.h"
 
 namespace pkmi {
@@ -103,6 +104,42 @@ struct CreateCheck {
 void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats, int stats_dim, int units, int64_t max_frames,
                       int64_t max_rows, int64_t chunk_cap, CreateCheck &chk);
 void FreeScorerCore(ScorerCore *c);             // (the owner has waited for the stream)
+
+// What the create entries of both scorers share.  UploadSpecTables: a front-end spec's tables to *d_any (the owner frees
+// it), and FbankKernel's own tables, which FbankAnyKernel reads too, where the core made none.  FrontendFits: false and
+// the fail text when a front-end of `dim` features (spec: one made from a front-end spec) does not feed base_dim -- the
+// model's own dimension, or with deltas of `order` in between the one in front of them.  StatsLenFits: the same for
+// statistics of stats_len entries at `dim` (base: a dimension in front of deltas).
+inline void UploadSpecTables(ScorerCore *c, const pkmi::FrontendAnyTables *any, pkmi::FrontendAnyTables **d_any, CreateCheck &chk) {
+  if (!c->d_tables && chk.ok) {                      // (the scorer core makes FbankKernel's tables for 40-dim statistics only)
+    pkmi::FrontendTables host;
+    if (BuildFrontendTables(&host)) { chk.ok = false; Fail(PK_MI355_E_INVALID, "front-end table construction failed"); }
+    chk(hipMalloc(&c->d_tables, sizeof(pkmi::FrontendTables)));
+    if (chk.ok) chk(hipMemcpy(c->d_tables, &host, sizeof(pkmi::FrontendTables), hipMemcpyHostToDevice));
+  }
+  chk(hipMalloc(d_any, sizeof(pkmi::FrontendAnyTables)));
+  if (chk.ok) chk(hipMemcpy(*d_any, any, sizeof(pkmi::FrontendAnyTables), hipMemcpyHostToDevice));
+}
+
+inline bool FrontendFits(int dim, bool spec, const pk_mi355_am *am, int base_dim, int order) {
+  if (dim == base_dim) return true;
+  if (order > 0)
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model's %d with deltas of order %d need %d", dim, am->feat_dim, order, base_dim);
+  else if (spec)
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the model expects %d", dim, am->feat_dim);
+  else
+    Fail(PK_MI355_E_INVALID, "the front-end produces %d-dim features, the model expects %d", dim, am->feat_dim);
+  return false;
+}
+
+inline bool StatsLenFits(int stats_len, int dim, bool base) {
+  if (stats_len == dim + 1) return true;
+  if (base)
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, %d-dim base features need %d (the sums, then the count)", stats_len, dim, dim + 1);
+  else
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, dim, dim + 1);
+  return false;
+}
 
 // ------------------------------------------------------------------ column shifts (capi_batch.hip)
 // Spans of rows (a multiple of four each) with one column shift -> one entry per group of four rows, for every row a
