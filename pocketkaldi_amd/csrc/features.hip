@@ -15,6 +15,7 @@
 // utterance's first row is 4-byte aligned and no better.  Workgroups never wait on each other.
 #include <hip/hip_runtime.h>
 
+#include "pk_norm.h"
 #include "pk_score.h"
 
 namespace pkmi {
@@ -71,8 +72,8 @@ __global__ __launch_bounds__(kFlThreads) void FeatureLayoutKernel(const uint32_t
 // ------------------------------------------------------------------ CMVN at any dimension
 //
 // CmvnChainKernel: raw rows [sum T][D] -> normalised rows [sum T][D], both frame-major; FeatureLayoutKernel then lays the
-// result out.  cmvn.cc is elementwise in the feature index, so this is StreamCmvnKernel's chain (stream.hip) with any
-// number of lanes: one wavefront per (utterance, block of 64 features), lane = feature, serial over t.  Per frame the
+// result out.  cmvn.cc is elementwise in the feature index, so this is CmvnKernel's chain (pk_norm.h's sliding steps) with
+// any number of lanes: one wavefront per (utterance, block of 64 features), lane = feature, serial over t.  Per frame the
 // wave reads and writes ONE contiguous run of up to 64 floats; the frame that leaves the window (t - 600) is read raw
 // from the input, which is why the kernel cannot run in place.  Frames are taken kChainAhead at a time and the loads of
 // the next group are issued before the chain of the current one -- the rows and the two table entries of each of its
@@ -115,15 +116,8 @@ __global__ __launch_bounds__(64) void CmvnChainKernel(const float *__restrict__ 
       for (int k = 0; k < kChainAhead; ++k) {
         const int t = t0 + k;
         if (t < T) {
-          const float xv = cur[k];
-          double acc = s;                              // cmvn.cc:44-52
-          acc += xv;
-          if (t >= kCmvnWindow) acc += -1.0 * static_cast<double>(old[k]);              // cmvn.cc:58-64
-          s = static_cast<float>(acc);                 // cmvn.cc:66-70
-          float st = s;
-          if (t + 1 < kCmvnWindow) st += al[k] * gd;                                    // cmvn.cc:73-92
-          float v = xv;
-          v += ns[k] * st;                                                              // cmvn.cc:94-101
+          s = pknorm::SlidingSum(s, cur[k], old[k], t >= kCmvnWindow);
+          const float v = pknorm::SlidingApply(cur[k], s, al[k], ns[k], gd, t + 1 < kCmvnWindow);
           if (live) y[(int64_t)t * D] = v;
         }
       }

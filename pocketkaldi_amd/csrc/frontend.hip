@@ -21,6 +21,7 @@
 #include "pk_frontend.h"
 #include "pk_kernels.h"
 #include "pk_logf.h"
+#include "pk_norm.h"
 #include "pk_wave.h"
 
 #pragma clang fp contract(off)
@@ -680,15 +681,15 @@ __global__ __launch_bounds__(kWave * kFbankWaves, 4) void FbankAnyKernel(
 
 // One workgroup of four wavefronts per utterance.  The running window sum is rounded to float
 // every frame (cmvn.cc:66-70), so ONE wavefront walks the frames in order, one lane per
-// feature, and does nothing but that chain -- one f32 add while the window fills (for floats,
-// float(double(s) + double(x)) IS s + x: the double sum is exact or differs from it by less than
-// a quarter of a float ulp), widen / two fp64 adds / narrow once it slides -- leaving S_t in LDS.
+// feature, and does nothing but that chain, pknorm::SlidingSum (pk_norm.h) -- in effect one f32
+// add while the window fills (for floats, float(double(s) + double(x)) IS s + x: the double sum is
+// exact or differs from it by less than a quarter of a float ulp) -- leaving S_t in LDS.
 // Everything else is parallel over frames and belongs to the other waves: one moves frames
 // HBM -> LDS by LDS-DMA, kCmvnAhead tiles (64 frames, 10 KiB each) ahead of the chain with a
 // counted wait, so that the chain never waits for memory (with one tile of lead the kernel ran at
 // one DMA round trip per tile: 2.9 us per 64 frames); two turn (x_t, S_t) of the previous tile
-// into y_t (lane = frame, 16-byte LDS reads of four features) and store rows of 64 consecutive
-// frames (256 bytes) into the feature-major operand of the first affine layer.
+// into y_t by pknorm::SlidingApply (lane = frame, 16-byte LDS reads of four features) and store
+// rows of 64 consecutive frames (256 bytes) into the feature-major operand of the first layer.
 // The window count is min(t + 1, 600), so the smoothing weight and the 1/count scale come
 // from the host-built CmvnTables.  One raw s_barrier per tile.
 constexpr int kCmvnTile = 64;                                   // frames per tile
@@ -820,11 +821,8 @@ __global__ __launch_bounds__(kWave * kCmvnWaves) void CmvnKernel(
           }
 #pragma unroll
           for (int v = 0; v < kCmvnTile; ++v) {
-            double acc = s;                                 // cmvn.cc:44-52
-            acc += xs[v];
-            if (MODE == 2 || (MODE == 1 && t0 + v >= kCmvnWindow))
-              acc += -1.0 * static_cast<double>(xo[MODE != 0 ? v : 0]);     // cmvn.cc:58-64
-            s = static_cast<float>(acc);                    // cmvn.cc:66-70
+            if constexpr (MODE == 0) s = pknorm::SlidingSum(s, xs[v], 0.0f, false);
+            else s = pknorm::SlidingSum(s, xs[v], xo[v], MODE == 2 || t0 + v >= kCmvnWindow);
             sum[v * kNumBins + d] = s;
           }
         };
@@ -849,10 +847,7 @@ __global__ __launch_bounds__(kWave * kCmvnWaves) void CmvnKernel(
         float *dst = col + (int64_t)(4 * q) * ldy;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float st = s4[e];
-          if (smooth) st += al * g4[qi][e];                     // cmvn.cc:73-92 (count < window)
-          float y = x4[e];
-          y += ns * st;                                         // cmvn.cc:94-101
+          const float y = pknorm::SlidingApply(x4[e], s4[e], al, ns, g4[qi][e], smooth);
           if (t < T) dst[(int64_t)e * ldy] = y;
         }
       }
@@ -866,10 +861,8 @@ __global__ __launch_bounds__(kWave * kCmvnWaves) void CmvnKernel(
             const int te = side == 0 ? 0 : T - 1;                         // the frame to replicate
             const int lt = te - j * kCmvnTile;
             const int te_c = te < kCmvnWindow ? te : kCmvnWindow - 1;
-            float st = sum[lt * kNumBins + dd];
-            if (te + 1 < kCmvnWindow) st += s_alpha[te_c] * s_g[dd];
-            float y = xin[lt * kNumBins + dd];
-            y += s_nscale[te_c] * st;
+            const float y = pknorm::SlidingApply(xin[lt * kNumBins + dd], sum[lt * kNumBins + dd], s_alpha[te_c], s_nscale[te_c], s_g[dd],
+                                                 te + 1 < kCmvnWindow);
             float *row = y0 + (int64_t)dd * ldy;
             if (side == 0) for (int p = 0; p < left; ++p) row[p] = y;
             else for (int p = 0; p < right; ++p) row[left + T + p] = y;

@@ -60,11 +60,7 @@ __global__ __launch_bounds__(64) void NormKernel(const float *__restrict__ raw, 
         for (int k = 0; k < kNormAhead; ++k) nxt[k] = x[row(t0 + kNormAhead + k)];     // ahead of this group's adds
 #pragma unroll
         for (int k = 0; k < kNormAhead; ++k)
-          if (t0 + k < T) {
-            const double v = static_cast<double>(cur[k]);
-            s0 = s0 + v;
-            s1 = s1 + v * v;
-          }
+          if (t0 + k < T) pknorm::StatsAdd(s0, s1, cur[k]);
 #pragma unroll
         for (int k = 0; k < kNormAhead; ++k) cur[k] = nxt[k];
       }
@@ -99,6 +95,7 @@ __global__ __launch_bounds__(64) void NormKernel(const float *__restrict__ raw, 
 // [kNormAhead][64] arrays only, so the wave needs no barrier, and the chain's loop stays rolled (the finalisation
 // holds several f64 divisions and a square root; kNormAhead unrolled copies of it would not fit the instruction cache).
 // Never in place: frame t - W is read raw.  Addresses are clamped as in NormKernel; the records are read at d < D.
+// The prior fill and the window step restate pknorm::MakeOnlinePrior and WindowStep (pk_norm.h).
 __global__ __launch_bounds__(64) void OnlineCmvnKernel(const float *__restrict__ raw, UttLayout utts, int num_utts, int D, int W,
                                                        int speaker_frames, int global_frames, int norm_vars,
                                                        const double *__restrict__ glob, const double *__restrict__ spk,

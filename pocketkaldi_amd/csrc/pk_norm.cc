@@ -96,29 +96,13 @@ int pk_mi355_online_cmvn_apply(const pk_mi355_online_cmvn_spec_t *spec, const fl
     if (int rc = CheckOnlineSpeakerCounts(speaker_stats, 1, dim)) return rc;
   const size_t T = (size_t)num_frames, D = (size_t)dim, W = (size_t)spec->cmn_window;
   const bool vars = spec->norm_vars != 0;
-  const bool glob = spec->global_frames > 0;
+  const double *glob = spec->global_frames > 0 ? global_stats : nullptr;       // (checked above: not null when asked for)
   std::vector<double> state(2 * (D + 1), 0.0);
   for (size_t d = 0; d < D; ++d) {
-    OnlinePrior p;
-    p.window = (double)spec->cmn_window;
-    p.speaker_frames = (double)spec->speaker_frames;
-    p.speaker_count = speaker_stats ? speaker_stats[D] : 0.0;
-    p.spk0 = speaker_stats ? speaker_stats[d] : 0.0;
-    p.spk1 = speaker_stats ? speaker_stats[D + 1 + d] : 0.0;
-    p.global_frames = (double)spec->global_frames;
-    p.global_count = glob ? global_stats[D] : 0.0;
-    p.glob0 = glob ? global_stats[d] : 0.0;
-    p.glob1 = glob ? global_stats[D + 1 + d] : 0.0;
+    const OnlinePrior p = MakeOnlinePrior(spec->cmn_window, spec->speaker_frames, spec->global_frames, glob, speaker_stats, dim, (int)d);
     double S0 = 0.0, S1 = 0.0;
     for (size_t t = 0; t < T; ++t) {
-      const double v = (double)x[t * D + d];
-      S0 = S0 + v;
-      S1 = S1 + v * v;
-      if (t >= W) {
-        const double o = (double)x[(t - W) * D + d];
-        S0 = S0 - o;
-        S1 = S1 - o * o;
-      }
+      WindowStep(S0, S1, x[t * D + d], t >= W ? x[(t - W) * D + d] : 0.0f, t >= W);
       float offs, scale;
       OnlineCmvnFinalize(S0, S1, (double)(t + 1), p, vars, &offs, &scale);
       y[t * D + d] = NormApply(x[t * D + d], offs, scale, vars);
@@ -153,11 +137,7 @@ int pk_mi355_norm_apply(const pk_mi355_norm_spec_t *spec, const float *x, int nu
   } else {
     std::vector<double> rec(2 * (D + 1), 0.0);
     for (size_t t = 0; t < T; ++t)
-      for (size_t d = 0; d < D; ++d) {
-        const double v = (double)x[t * D + d];
-        rec[d] += v;
-        rec[D + 1 + d] += v * v;
-      }
+      for (size_t d = 0; d < D; ++d) StatsAdd(rec[d], rec[D + 1 + d], x[t * D + d]);
     rec[D] = (double)num_frames;
     if (stats_out) for (size_t i = 0; i < rec.size(); ++i) stats_out[i] = rec[i];
     if (T == 0) return 0;

@@ -43,6 +43,7 @@ __global__ __launch_bounds__(256) void StreamAssembleKernel(const StreamRec *__r
 // f32 add while the window fills, widen / two fp64 adds / narrow once it slides (cmvn.cc:44-70), then the smoothing
 // with the global sums and the 1/count scale of the global frame index (cmvn.cc:73-101, CmvnTables).  The step's raw
 // rows are turned into CMVN'd rows in place.  Then lane = column: the slot's region of the spliced operand.
+// The chain restates pknorm::SlidingSum and SlidingApply (pk_norm.h); DESIGN.md section 23 says why.
 __global__ __launch_bounds__(kWave) void StreamCmvnKernel(const StreamRec *__restrict__ recs, float *__restrict__ rows,
                                                           const float *__restrict__ g, const CmvnTables *__restrict__ tab,
                                                           float *__restrict__ sums, float *__restrict__ raw_hist,
@@ -188,7 +189,8 @@ __global__ __launch_bounds__(kSflThreads) void StreamFeatureLayoutKernel(const S
 }
 
 // RAW slots at a feature dimension other than 40: StreamCmvnKernel's chain with any number of
-// lanes.  One wavefront per (record, block of 64 features), lane = feature; NORMALIZED records and records that brought no
+// lanes, through pknorm::SlidingSum and SlidingApply (pk_norm.h).
+// One wavefront per (record, block of 64 features), lane = feature; NORMALIZED records and records that brought no
 // frames return at once.  RAW records bring pushed rows, audio records of a front-end spec the
 // rows FbankAnyKernel has just written.  The slot's m fresh rows are normalised IN PLACE where they lie in the upload
 // staging ([m][D] at row_off): the raw values the window needs later are kept in the slot's ring raw_hist[slot][600][D], the
@@ -237,14 +239,8 @@ __global__ __launch_bounds__(kWave) void StreamCmvnChainKernel(const StreamRec *
       if (i < m) {
         const int t = r.n_old + i;
         const float xv = cur[k];
-        double acc = s;                                // cmvn.cc:44-52
-        acc += xv;
-        if (t >= kCmvnWindow) acc += -1.0 * static_cast<double>(old[k]);                // cmvn.cc:58-64
-        s = static_cast<float>(acc);                   // cmvn.cc:66-70
-        float st = s;
-        if (t + 1 < kCmvnWindow) st += al[k] * gd;                                      // cmvn.cc:73-92
-        float v = xv;
-        v += ns[k] * st;                                                                // cmvn.cc:94-101
+        s = pknorm::SlidingSum(s, xv, old[k], t >= kCmvnWindow);
+        const float v = pknorm::SlidingApply(xv, s, al[k], ns[k], gd, t + 1 < kCmvnWindow);
         if (live) {
           rh[ring(i)] = xv;
           x[row(i)] = v;
@@ -261,10 +257,11 @@ __global__ __launch_bounds__(kWave) void StreamCmvnChainKernel(const StreamRec *
 // StreamCmvnChainKernel's place and shape: one wavefront per (record, block of 64 features), lane = feature, the slot's m
 // fresh rows normalised IN PLACE at rows + row_off; StreamFeatureLayoutKernel then lays the record out.  A lane owns
 // its feature's column of the rows, of the ring and of the two pairs of sums.
-//   Both modes: total[slot] gains every frame's value and square in double, t ascending -- the utterance rule's order,
-//     so the record of a whole slot is the batch scorer's norm_stats of the whole input.
+//   Both modes: total[slot] gains every frame's value and square (pknorm::StatsAdd), t ascending -- the utterance
+//     rule's order, so the record of a whole slot is the batch scorer's norm_stats of the whole input.
 //   speaker: y = NormApply(x, the slot's finalised offset and scale).
-//   online CMVN: the batch kernel's lines (norm.hip) with the state carried from step to step -- the window sums in
+//   online CMVN: the batch kernel's steps (norm.hip; here through pknorm::MakeOnlinePrior and WindowStep) with the
+//     state carried from step to step -- the window sums in
 //     win[slot], the raw rows still inside the window in ring[slot][t % W] (frame t - W leaves from the position frame
 //     t takes).  Frames are taken kSNormAhead at a time, the next group's rows and ring entries loaded into registers
 //     ahead of the current group's chain and handed to it through LDS (lane-private columns: no barrier).  A ring entry
@@ -301,9 +298,7 @@ __global__ __launch_bounds__(kWave) void StreamNormKernel(const StreamRec *__res
 #pragma unroll
       for (int k = 0; k < kSNormAhead; ++k)
         if (i0 + k < m) {
-          const double v = static_cast<double>(cur[k]);
-          t0s = t0s + v;
-          t1s = t1s + v * v;
+          pknorm::StatsAdd(t0s, t1s, cur[k]);
           if (live) x[row(i0 + k)] = pknorm::NormApply(cur[k], offs, scale, vars);
         }
 #pragma unroll
@@ -312,17 +307,10 @@ __global__ __launch_bounds__(kWave) void StreamNormKernel(const StreamRec *__res
     if (live) { tot[0] = t0s; tot[D] = t1s; }
     return;
   }
-  pknorm::OnlinePrior p;
-  p.window = static_cast<double>(W);
-  p.speaker_frames = static_cast<double>(st.speaker_frames);
-  p.global_frames = st.global_frames > 0 ? static_cast<double>(st.global_frames) : 0.0;
-  p.global_count = st.global_frames > 0 ? st.glob[D] : 0.0;
-  p.glob0 = st.global_frames > 0 ? st.glob[d] : 0.0;
-  p.glob1 = st.global_frames > 0 ? st.glob[D + 1 + d] : 0.0;
   const double *rec = st.spk + (int64_t)r.slot * 2 * (D + 1);
-  p.speaker_count = rec[D];
-  p.spk0 = rec[d];
-  p.spk1 = rec[D + 1 + d];
+  __builtin_assume(rec != nullptr);     // pk_mi355_stream_norm_set_online_cmvn allocates st.spk before any slot runs
+  const pknorm::OnlinePrior p =
+      pknorm::MakeOnlinePrior(W, st.speaker_frames, st.global_frames, st.global_frames > 0 ? st.glob : nullptr, rec, D, d);
   double *win = st.win + (int64_t)r.slot * 2 * D + d;
   float *rh = st.ring + (int64_t)r.slot * W * D + d;
   double S0 = r.n_old > 0 ? win[0] : 0.0, S1 = r.n_old > 0 ? win[D] : 0.0;
@@ -346,16 +334,9 @@ __global__ __launch_bounds__(kWave) void StreamNormKernel(const StreamRec *__res
     for (int k = 0; k < n; ++k) {
       const int i = i0 + k, t = r.n_old + i;
       const float xt = s_cur[k][lane];
-      const double v = static_cast<double>(xt);
-      t0s = t0s + v;
-      t1s = t1s + v * v;
-      S0 = S0 + v;
-      S1 = S1 + v * v;
-      if (t >= W) {
-        const double o = static_cast<double>(i < W ? s_old[k][lane] : rh[ring(i)]);     // (i >= W: this launch's own store)
-        S0 = S0 - o;
-        S1 = S1 - o * o;
-      }
+      pknorm::StatsAdd(t0s, t1s, xt);
+      if (t >= W) pknorm::WindowStep(S0, S1, xt, i < W ? s_old[k][lane] : rh[ring(i)], true);
+      else pknorm::WindowStep(S0, S1, xt, 0.0f, false);                  // (i >= W above: this launch's own store)
       float offs, scale;
       pknorm::OnlineCmvnFinalize(S0, S1, static_cast<double>(t + 1), p, vars, &offs, &scale);
       if (live) {

@@ -6,7 +6,11 @@
 //
 // Cases: every refusal of the spec; speaker records with counts of 0, -1, NaN and inf (refused, the utterance named,
 // nothing written); the variance floor; records for 1 and 200 utterances at D = 97 in the three switch pairs; and
-// pk_mi355_norm_apply on a small matrix in every mode, no frames included.
+// pk_mi355_norm_apply on a small matrix in every mode, no frames included; and the sliding rule's two steps
+// (pknorm::SlidingSum, SlidingApply over BuildCmvnTables' scalars), walked frame by frame as the chain kernels walk them,
+// on 700 frames at D = 40 and 41, whose hash the driver holds to the oracle.
+// Sliding input: x[t][d] = float((h(t D + d + 31337) >> 8) / 2^24 * 30 - 12 (+ 1e4 in column D / 2)), the statistics
+// float(2500 (3 (+ 1e4))) per column and the count 2500.
 // Record (u, d): k = 1000 u + d, N = 50 + 100 (u % 7), m = (h(k) >> 8) / 65536 - 128, v = 0.01 + (h(k + 7777) >> 16) / 4096,
 // S0 = m N, S1 = (m m + v) N, with h(k) = k * 2654435761 mod 2^32.
 #include <math.h>
@@ -20,6 +24,7 @@
 
 #include "../../pocketkaldi_amd/csrc/pk_files.h"
 #include "../../pocketkaldi_amd/csrc/pk_norm.h"
+#include "../../pocketkaldi_amd/csrc/pk_tables.h"
 
 using pkhost::LastError;
 
@@ -130,6 +135,29 @@ int main() {
     CHECK(pk_mi355_norm_apply(&utt, nullptr, 0, dim, nullptr, nullptr, rec.data()) == 0 && rec[dim] == 0.0 && rec[0] == 0.0, "no frames");
     CHECK(pk_mi355_norm_apply(&utt, x.data(), 1, dim, nullptr, y2.data(), rec.data()) == 0 && rec[dim] == 1.0, "one frame");
     for (int d = 0; d < dim; ++d) CHECK(y2[d] == x[d] * 1e10f + (float)-((double)x[d] * 1e10), "one frame, column %d: %g", d, y2[d]);
+  }
+
+  // ---- the sliding rule, frame by frame
+  for (int dim : {40, 41}) {
+    const int T = 700, W = pkmi::kCmvnWindow;
+    pkmi::CmvnTables tab;
+    pkmi::BuildCmvnTables(2500.0f, &tab);
+    std::vector<float> x((size_t)T * dim), y(x.size()), g(dim);
+    for (int d = 0; d < dim; ++d) {
+      const double big = d == dim / 2 ? 1e4 : 0.0;
+      g[d] = (float)(2500.0 * (3.0 + big));
+      for (int t = 0; t < T; ++t) x[(size_t)t * dim + d] = (float)((double)(H((uint32_t)(t * dim + d) + 31337u) >> 8) / 16777216.0 * 30.0 - 12.0 + big);
+    }
+    for (int d = 0; d < dim; ++d) {
+      float s = 0.0f;
+      for (int t = 0; t < T; ++t) {
+        const int tt = t < W ? t : W - 1;
+        const float xt = x[(size_t)t * dim + d];
+        s = pknorm::SlidingSum(s, xt, t >= W ? x[(size_t)(t - W) * dim + d] : 0.0f, t >= W);
+        y[(size_t)t * dim + d] = pknorm::SlidingApply(xt, s, tab.alpha[tt], tab.neg_scale[tt], g[d], t + 1 < W);
+      }
+    }
+    printf("sliding %d %016llx %016llx\n", dim, Fnv(x.data(), sizeof(float) * x.size()), Fnv(y.data(), sizeof(float) * y.size()));
   }
 
   if (g_failures) { printf("norm_test FAILED (%d)\n", g_failures); return 1; }

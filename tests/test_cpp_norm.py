@@ -1,7 +1,8 @@
 """The normalisation spec in C++.
   * tests/cpp/norm_test.cc: csrc/pk_norm.cc in a process of its own, plain and under ASan + UBSan -- the spec's
     refusals, counts of 0, -1, NaN and inf, the variance floor, records for 1 and 200 utterances; the tables it
-    finalises hash to the numpy restatement's (tests/norm_cases.py).
+    finalises hash to the numpy restatement's (tests/norm_cases.py); and the sliding rule's two steps of pk_norm.h,
+    which the CMVN kernels compile, walked over 700 frames at D = 40 and 41: the rows hash to the oracle's.
   * tests/cpp/norm_example.cc: an 80-bin front-end, pocketkaldi::BatchScorer::SetNorm(NormSpec::Utterance(true, true));
     its normalised rows, statistics and log-likelihood rows hash to Python's."""
 import os
@@ -12,8 +13,10 @@ import pytest
 
 import pocketkaldi_amd as pk
 
+import cmvn_any_cases as CA
 import norm_cases as NC
 from test_cpp_ark_features import fnv, weight
+from oracle import oracle as O
 from test_cpp_stream import build
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,6 +43,30 @@ def records(U):
     return rec
 
 
+def sliding_input(dim, T=700):
+    """norm_test.cc's sliding input, restated: values around 3, column dim // 2 around 1e4 (the two kinds of
+    cmvn_any_cases.features), and cmvn_any_cases.stats_for's statistics."""
+    t, d = np.meshgrid(np.arange(T), np.arange(dim), indexing="ij")
+    x = (h(t * dim + d + 31337) >> np.uint64(8)).astype(np.float64) / 16777216.0 * 30.0 - 12.0
+    x[:, dim // 2] += CA.BIG_COLUMN_MEAN
+    return CA.stats_for(dim), x.astype(np.float32)
+
+
+@pytest.mark.parametrize("dim", [40, 41])
+def test_sliding_input_tells_a_float_only_sum_from_the_double_step(dim):
+    """As test_cmvn_any_host.py shows for its input: the restated chain with the widen / narrow step IS the oracle on the
+    program's input, and without it both kinds of column differ once the window slides."""
+    g, x = sliding_input(dim)
+    want = CA.cmvn_any(g, x)
+    assert want.tobytes() == CA.restated_chain(g, x, True).tobytes()
+    differs = CA.restated_chain(g, x, False).view(np.uint32) != want.view(np.uint32)
+    assert not differs[:CA.WINDOW].any()
+    per_column = differs.sum(axis=0)
+    print("frames on which the float-only chain differs: big column %d, the others %d..%d"
+          % (per_column[dim // 2], np.delete(per_column, dim // 2).min(), np.delete(per_column, dim // 2).max()))
+    assert per_column[dim // 2] >= 10 and np.delete(per_column, dim // 2).min() >= 10
+
+
 @pytest.mark.parametrize("flavour", [
     "plain",
     pytest.param("sanitized", marks=pytest.mark.skipif(pk.lib().pk_mi355_device_count() > 0,
@@ -49,7 +76,7 @@ def test_host_side_stand_alone(flavour):
     binary_path = os.path.join(REPO, "tests", "cpp", "norm_test_%s.bin" % flavour)
     subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off"] + (SANITIZE if flavour == "sanitized" else []) +
                           [os.path.join(REPO, "tests", "cpp", "norm_test.cc"), os.path.join(CSRC, "pk_norm.cc"), os.path.join(CSRC, "pk_files.cc"),
-                           "-o", binary_path])
+                           os.path.join(CSRC, "pk_tables.cc"), "-o", binary_path])
     run = subprocess.run([binary_path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-4000:]
     assert run.stderr == ""                                  # a sanitizer reports there
@@ -66,6 +93,12 @@ def test_host_side_stand_alone(flavour):
     x = ((h(np.arange(37 * 5) + 99) >> np.uint64(12)).astype(np.float64) / 1024.0 - 300.0).astype(np.float32).reshape(37, 5)
     y, rec = NC.normalize(x, "utterance", True, True)
     want += ["matrix %s" % fnv(x.tobytes()), "utterance %s %s" % (fnv(y.tobytes()), fnv(rec.tobytes()))]
+    for dim in (40, 41):                                     # the sliding steps against the oracle
+        g, x = sliding_input(dim)
+        y = CA.cmvn_any(g, x)
+        if dim == 40:
+            assert y.tobytes() == O.cmvn(g, x).tobytes()
+        want.append("sliding %d %s %s" % (dim, fnv(x.tobytes()), fnv(y.tobytes())))
     assert out[:len(want)] == want
 
 
