@@ -523,8 +523,8 @@ int pk_mi355_norm_set_online_cmvn(pk_mi355_batch_t *b, const pk_mi355_online_cmv
 /* ---- Delta features: Kaldi's add-deltas between the normalisation and the splice of a batch
  * scorer, for models whose first layer expects (order + 1) x the dimension the front-end, the statistics and the
  * normalisation work at (13 MFCC -> 39, 40 fbank -> 120).  Restated from Kaldi's DeltaFeatures; not compared with a
- * Kaldi binary (Kaldi leaves the axpy to BLAS, so agreement with it is within rounding).  No energy; the online
- * objects do not have deltas yet.                                                                                  */
+ * Kaldi binary (Kaldi leaves the axpy to BLAS, so agreement with it is within rounding).  No energy.  The online
+ * objects: pk_mi355_deltas_stream_create below.                                                                    */
 typedef struct pk_mi355_deltas_spec {
   int32_t order;    /* 1 .. 3 (Kaldi's default 2) */
   int32_t window;   /* 1 .. 8 (Kaldi's default 2) */
@@ -911,6 +911,32 @@ int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind);
 int pk_mi355_stream_push_features(pk_mi355_stream_t *s, int slot, const float *frames, int num_frames);
 /* The model's feature dimension: the length of a pushed frame.  Negative on a null object.                          */
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s);
+/* An online scorer with deltas in front of the splice: pk_mi355_deltas_batch_create's arguments,
+ * checks (in its order, with its texts) and meaning of Db, frontend (NULL: features only, capacity in frames pushed
+ * between two steps; else capacity in 16 kHz samples and global_stats required), global_stats and stats_len; an f16
+ * model is refused as on every stream entry.  Everything in front of the deltas works at Db, as on a deltas batch: the
+ * front-end, the statistics, every normalisation the online scorer accepts (pk_mi355_stream_norm_set*: sliding -- the
+ * chain kernel at every Db, 40 too --, none, speaker, online CMVN), their speaker and global records,
+ * pk_mi355_stream_norm_fetch_stats, and PK_MI355_FEATS_RAW slots, whose pushes are [n][Db].  PK_MI355_FEATS_NORMALIZED
+ * slots stay [n][feat_dim] and take no deltas.
+ *
+ * The rule for a live slot.  M = order * window, R the model's right context; per slot n normalised base frames so far,
+ * nd delta frames final so far, a rows scored so far.  One step: delta frames [nd, nd') become final, nd' = closed ? n :
+ * max(nd, n - M); delta frame t, block i, is the apply rule above over the normalised base frames clamp(t + j, 0, n - 1)
+ * (while the slot is open t + M <= n - 1, so the upper clamp binds only after close; the lower clamp is frame 0 of this
+ * opening); rows [a, b) are scored, b = closed ? nd' : max(a, nd' - R), spliced over delta frames as on every stream.
+ * The look-ahead of a live slot is therefore M + R frames; a slot closed with n = 0 gives nothing, one closed with
+ * n <= M + R gives all its rows at the flush, one closed a step after its last push flushes M + R frames from its
+ * history.  Over a slot's life the rows are those of a batch made by pk_mi355_deltas_batch_create on the whole input
+ * under the same normalisation, bit for bit, at every chunking and in both softmax modes.
+ * Memory beyond a stream without deltas: 16 * M * Db bytes of ring per slot, a staging of
+ * (max_frames + max_streams * M) * feat_dim floats, and M more rows per slot in the layer buffers.  A step that cannot
+ * fit fails with PK_MI355_E_INVALID and consumes nothing.                                                            */
+pk_mi355_stream_t *pk_mi355_deltas_stream_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas,
+                                                 const pk_mi355_frontend_spec_t *frontend, const float *global_stats,
+                                                 int stats_len, int max_streams, int64_t capacity);
+/* Db of a stream made by the entry above; feat_dim on every other stream; PK_MI355_E_INVALID for NULL.              */
+int pk_mi355_stream_base_dim(const pk_mi355_stream_t *s);
 
 /* ---- The normalisation of an online scorer of any kind (pk_mi355_stream_create, pk_mi355_features_stream_create*,
  * pk_mi355_frontend_stream_create): every row a slot's life produces is the row the batch scorer produces under the
@@ -1208,6 +1234,14 @@ pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config
 pk_mi355_online_recognizer_t *pk_mi355_frontend_online_recognizer_load(const char *config_path,
                                                                        const pk_mi355_frontend_spec_t *spec, int max_streams,
                                                                        int64_t max_step_samples, int64_t trace_capacity);
+/* The same with deltas for a model of (order + 1) * pk_mi355_frontend_dim(frontend_spec)
+ * features whose cmvn_stats hold the front-end's dimension + 1 entries: pk_mi355_deltas_stream_create in place of
+ * pk_mi355_frontend_stream_create, whose refusals are this entry's; bad specs are refused first.  push_features of a
+ * RAW slot takes [n][Db].                                                                                           */
+pk_mi355_online_recognizer_t *pk_mi355_deltas_online_recognizer_load(const char *config_path,
+                                                                     const pk_mi355_frontend_spec_t *frontend_spec,
+                                                                     const pk_mi355_deltas_spec_t *deltas_spec, int max_streams,
+                                                                     int64_t max_step_samples, int64_t trace_capacity);
 void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r);
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r);
 pk_mi355_stream_t *pk_mi355_online_recognizer_stream(pk_mi355_online_recognizer_t *r);

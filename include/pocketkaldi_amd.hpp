@@ -403,6 +403,21 @@ class OnlineScorer {
       : s_(pk_mi355_features_stream_create_stats(am, global_stats, stats_len, max_streams, max_step_frames)) {
     if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // Deltas behind the normalisation (a DeltaSpec; pk_mi355_deltas_stream_create): a model of
+  // (order + 1) x the front-end's dimension; the front-end, the statistics (stats_len = BaseDim() + 1), the normalisation
+  // and RAW slots are at BaseDim().  A live slot looks order * window + R frames ahead.
+  OnlineScorer(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t &deltas, const float *global_stats,
+               int stats_len, int max_streams, int64_t max_step_samples)
+      : s_(pk_mi355_deltas_stream_create(am, &deltas, &spec, global_stats, stats_len, max_streams, max_step_samples)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // The same without a front-end: feature slots only, capacity in frames; global_stats (BaseDim() sums, then the count) may
+  // be null.
+  OnlineScorer(FeaturesOnlyTag, pk_mi355_am_t *am, const pk_mi355_deltas_spec_t &deltas, const float *global_stats, int stats_len,
+               int max_streams, int64_t max_step_frames)
+      : s_(pk_mi355_deltas_stream_create(am, &deltas, nullptr, global_stats, stats_len, max_streams, max_step_frames)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   ~OnlineScorer() { pk_mi355_stream_destroy(s_); }
   OnlineScorer(const OnlineScorer &) = delete;
   OnlineScorer &operator=(const OnlineScorer &) = delete;
@@ -425,19 +440,21 @@ class OnlineScorer {
     return Status::FromLast(pk_mi355_stream_push_features(s_, slot, frames, num_frames));
   }
   int FeatDim() const { return pk_mi355_stream_feat_dim(s_); }
+  // the dimension in front of the deltas (the front-end's, the statistics', a RAW slot's frames); FeatDim() on a scorer without deltas
+  int BaseDim() const { return pk_mi355_stream_base_dim(s_); }
   // -1: audio, else the PK_MI355_FEATS_* kind the slot was last opened with
   int SlotKind(int slot) const { return pk_mi355_stream_slot_kind(s_, slot); }
   // The normalisation of the audio and RAW slots, while no slot is in use: a NormSpec of mode sliding,
-  // none or speaker, or an OnlineCmvnSpec with its global statistics (2 x (FeatDim() + 1) doubles; null with global_frames = 0).
+  // none or speaker, or an OnlineCmvnSpec with its global statistics (2 x (BaseDim() + 1) doubles; null with global_frames = 0).
   Status SetNorm(const pk_mi355_norm_spec_t &spec) { return Status::FromLast(pk_mi355_stream_norm_set(s_, &spec)); }
   Status SetNorm(const pk_mi355_online_cmvn_spec_t &spec, const double *global_stats) {
     return Status::FromLast(pk_mi355_stream_norm_set_online_cmvn(s_, &spec, global_stats));
   }
-  // the speaker's 2 x (FeatDim() + 1) record of an open slot, before its first frame is computed
+  // the speaker's 2 x (BaseDim() + 1) record of an open slot, before its first frame is computed
   Status SetSpeakerStats(int slot, const double *stats) { return Status::FromLast(pk_mi355_stream_norm_set_speaker_stats(s_, slot, stats)); }
-  // the 2 x (FeatDim() + 1) record of all frames of the slot since it was opened
+  // the 2 x (BaseDim() + 1) record of all frames of the slot since it was opened
   Status NormStats(int slot, std::vector<double> *out) {
-    out->assign(2 * (static_cast<size_t>(pk_mi355_stream_feat_dim(s_)) + 1), 0.0);
+    out->assign(2 * (static_cast<size_t>(pk_mi355_stream_base_dim(s_)) + 1), 0.0);
     return Status::FromLast(pk_mi355_stream_norm_fetch_stats(s_, slot, out->data()));
   }
   Status Close(int slot) { return Status::FromLast(pk_mi355_stream_close(s_, slot)); }
@@ -754,6 +771,14 @@ class OnlineRecognizer {
               int64_t max_step_samples = 16000 * 8, int64_t trace_capacity = 0) {
     pk_mi355_online_recognizer_destroy(r_);
     r_ = pk_mi355_frontend_online_recognizer_load(model_file.c_str(), &spec, max_streams, max_step_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // A model of (order + 1) x the spec's feature dimension, deltas behind the normalisation (a FrontendSpec and a
+  // DeltaSpec; pk_mi355_deltas_online_recognizer_load)
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t &deltas, int max_streams = 1,
+              int64_t max_step_samples = 16000 * 8, int64_t trace_capacity = 0) {
+    pk_mi355_online_recognizer_destroy(r_);
+    r_ = pk_mi355_deltas_online_recognizer_load(model_file.c_str(), &spec, &deltas, max_streams, max_step_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   Status Open(int slot) { return Status::FromLast(pk_mi355_online_recognizer_open(r_, slot)); }

@@ -164,6 +164,7 @@ EXPORTS = [
     "pk_mi355_stream_norm_fetch_stats",
     "pk_mi355_deltas_check", "pk_mi355_deltas_dim", "pk_mi355_deltas_scales", "pk_mi355_deltas_apply",
     "pk_mi355_deltas_batch_create", "pk_mi355_deltas_base_dim", "pk_mi355_deltas_recognizer_load",
+    "pk_mi355_deltas_stream_create", "pk_mi355_stream_base_dim", "pk_mi355_deltas_online_recognizer_load",
 ]
 
 
@@ -467,6 +468,11 @@ def lib():
     L.pk_mi355_deltas_base_dim.argtypes = [C.c_void_p]
     L.pk_mi355_deltas_recognizer_load.restype = C.c_void_p
     L.pk_mi355_deltas_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, C.c_int, C.c_int, C.c_int64, C.c_int64]
+    L.pk_mi355_deltas_stream_create.restype = C.c_void_p
+    L.pk_mi355_deltas_stream_create.argtypes = [C.c_void_p, deltasp, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_stream_base_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_deltas_online_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_deltas_online_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, C.c_int, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -1441,12 +1447,25 @@ class OnlineScorer:
     [a, n - R) of an open slot, the rest after close()), bit for bit what BatchScorer gives on the whole wave.  A slot
     opened with open_features takes [n][40] frames through push_features instead (OnlineFeatureScorer: any dimension)."""
 
-    def __init__(self, am, global_stats, max_streams, max_step_samples, frontend=None):
+    _has_deltas = False                     # made with deltas=: "raw" slots are then base_dim() wide
+
+    def __init__(self, am, global_stats, max_streams, max_step_samples, frontend=None, deltas=None):
         """frontend: a FrontendSpec of the model's feature dimension (pk_mi355_frontend_stream_create; global_stats: that
-        many sums, then the count).  Feature slots then take [n][dim] frames."""
+        many sums, then the count).  Feature slots then take [n][dim] frames.
+        deltas: a DeltaSpec (pk_mi355_deltas_stream_create): the front-end (the default FrontendSpec when none is given),
+        the statistics, the normalisation and "raw" slots are then at base_dim() = feat_dim / (order + 1), and a live
+        slot looks order * window + R frames ahead."""
         g = _f32(global_stats)
         self._am = am
         self._max_streams = int(max_streams)
+        self._has_deltas = deltas is not None
+        if deltas is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_deltas_stream_create(am.handle, C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
+                                                          int(max_streams), int(max_step_samples))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
         if frontend is not None:
             self._h = lib().pk_mi355_frontend_stream_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
                                                             int(max_streams), int(max_step_samples))
@@ -1475,7 +1494,7 @@ class OnlineScorer:
         "sliding" (the default), "none" or "speaker", or an OnlineCmvnSpec with the 2 x (feat_dim + 1) global record it
         smooths with (None with global_frames = 0).  Every row is then the BatchScorer's under the same spec."""
         if isinstance(spec, OnlineCmvnSpec):
-            g = None if global_stats is None else _global_record(global_stats, self.feat_dim())
+            g = None if global_stats is None else _global_record(global_stats, self.base_dim())
             _check_code(lib().pk_mi355_stream_norm_set_online_cmvn(self._h, C.byref(spec.struct()), None if g is None else _dp(g)))
             return
         if global_stats is not None:
@@ -1485,13 +1504,13 @@ class OnlineScorer:
     def set_speaker_stats(self, slot, stats):
         """The speaker's 2 x (feat_dim + 1) record of an open slot, before its first frame is computed: required in mode
         "speaker", optional under online CMVN."""
-        a = _stats_records([stats], 1, self.feat_dim())
+        a = _stats_records([stats], 1, self.base_dim())
         _check_code(lib().pk_mi355_stream_norm_set_speaker_stats(self._h, int(slot), _dp(a)))
 
     def norm_stats(self, slot):
         """Mode "speaker" and online CMVN: the 2 x (feat_dim + 1) float64 record of all frames of the slot since it was
         opened -- BatchScorer.norm_stats' bits on the whole input."""
-        out = np.zeros((2, self.feat_dim() + 1), np.float64)
+        out = np.zeros((2, self.base_dim() + 1), np.float64)
         _check_code(lib().pk_mi355_stream_norm_fetch_stats(self._h, int(slot), _dp(out)))
         return out
 
@@ -1517,12 +1536,24 @@ class OnlineScorer:
             self.set_speaker_stats(slot, speaker_stats)
 
     def push_features(self, slot, frames):
-        """[n][feat_dim] frames, n >= 0."""
-        f = _feature_frames(frames, self.feat_dim())
+        """[n][feat_dim] frames, n >= 0 ([n][base_dim] for a "raw" slot of a scorer made with deltas=)."""
+        f = _feature_frames(frames, self._push_dim(slot) if self._has_deltas else self.feat_dim())
         _check_code(lib().pk_mi355_stream_push_features(self._h, int(slot), _fp(f) if f.size else None, f.shape[0]))
 
     def feat_dim(self):
         return _check_code(lib().pk_mi355_stream_feat_dim(self._h))
+
+    def base_dim(self):
+        """The dimension in front of the deltas -- the front-end's, raw slots', statistics' -- on a scorer made with
+        deltas=; feat_dim() on every other."""
+        return _check_code(lib().pk_mi355_stream_base_dim(self._h))
+
+    def _push_dim(self, slot):
+        """The width of the frames push_features takes for slot: feat_dim(), or base_dim() for a "raw" slot of a scorer
+        made with deltas=."""
+        if self._has_deltas and lib().pk_mi355_stream_slot_kind(self._h, int(slot)) == FEATURE_KINDS["raw"]:
+            return self.base_dim()
+        return self.feat_dim()
 
     def slot_kind(self, slot):
         """None for an audio slot, else "normalized" / "raw": what the slot was last opened as."""
@@ -1572,10 +1603,20 @@ class OnlineFeatureScorer(OnlineScorer):
     capacity in frames pushed between two steps.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim
     model) enables kind "raw".  The audio entries (open, push, push_i16) fail on it."""
 
-    def __init__(self, am, max_streams, max_step_frames, global_stats=None):
-        g, own_dim = _stats_route(am, global_stats)
+    def __init__(self, am, max_streams, max_step_frames, global_stats=None, deltas=None):
+        """deltas: a DeltaSpec (pk_mi355_deltas_stream_create without a front-end): "raw" slots then take [n][base_dim()]
+        frames, and global_stats, when given, holds base_dim() sums and the count."""
         self._am = am
         self._max_streams = int(max_streams)
+        self._has_deltas = deltas is not None
+        if deltas is not None:
+            g = None if global_stats is None else _f32(global_stats)
+            self._h = lib().pk_mi355_deltas_stream_create(am.handle, C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
+                                                          0 if g is None else g.size, int(max_streams), int(max_step_frames))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
+        g, own_dim = _stats_route(am, global_stats)
         if own_dim:
             self._h = lib().pk_mi355_features_stream_create_stats(am.handle, _fp(g), g.shape[0], int(max_streams), int(max_step_frames))
         else:
@@ -2217,10 +2258,16 @@ class OnlineRecognizer:
     close and step through the recognizer, not through .scorer / .decoder: a slot closed behind its back is never
     reported finished."""
 
-    def __init__(self, config, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0, frontend=None):
+    def __init__(self, config, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0, frontend=None, deltas=None):
         """frontend: a FrontendSpec; the model file is then one of that feature dimension
-        (pk_mi355_frontend_online_recognizer_load)."""
-        if frontend is not None:
+        (pk_mi355_frontend_online_recognizer_load).
+        deltas: a DeltaSpec; the model file is then one of (order + 1) x the front-end's dimension whose cmvn_stats are at
+        the front-end's (pk_mi355_deltas_online_recognizer_load; the default FrontendSpec when only deltas is given)."""
+        if deltas is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_deltas_online_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()), C.byref(deltas.struct()),
+                                                                   int(max_streams), int(max_step_samples), int(trace_capacity))
+        elif frontend is not None:
             self._h = lib().pk_mi355_frontend_online_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()), int(max_streams),
                                                                      int(max_step_samples), int(trace_capacity))
         else:
@@ -2232,7 +2279,7 @@ class OnlineRecognizer:
         L = lib()
         self.am = _Borrowed.of(AcousticModel, L.pk_mi355_online_recognizer_am(self._h), self)
         self.scorer = _Borrowed.of(OnlineScorer, L.pk_mi355_online_recognizer_stream(self._h), self, free="destroy", _am=self.am,
-                                   _max_streams=int(max_streams))
+                                   _max_streams=int(max_streams), _has_deltas=deltas is not None)
         self.decoder = _Borrowed.of(OnlineDecoder, L.pk_mi355_online_recognizer_decoder(self._h), self, free="destroy",
                                     _am=self.am, _fst=None)
         self.symbols = SymbolTable._borrowed(L.pk_mi355_online_recognizer_symtab(self._h), self)
@@ -2281,8 +2328,8 @@ class OnlineRecognizer:
             self.scorer.set_speaker_stats(slot, speaker_stats)
 
     def push_features(self, slot, frames):
-        """[n][40] frames, n >= 0."""
-        f = _feature_frames(frames, self.scorer.feat_dim())
+        """[n][dim] frames, n >= 0 (dim: OnlineScorer.push_features')."""
+        f = _feature_frames(frames, self.scorer._push_dim(slot))
         _check_code(lib().pk_mi355_online_recognizer_push_features(self._h, int(slot), _fp(f) if f.size else None, f.shape[0]))
 
     def close(self, slot):

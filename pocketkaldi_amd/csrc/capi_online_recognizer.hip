@@ -184,12 +184,16 @@ void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r) {
 namespace {
 // spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
 pk_mi355_online_recognizer_t *LoadOnlineRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int max_streams,
-                                                   int64_t max_step_samples, int64_t trace_capacity) {
+                                                   int64_t max_step_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr) {
   pk_mi355_online_recognizer *r = new pk_mi355_online_recognizer();
   auto failed = [&]() { pk_mi355_online_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (spec) {
+  if (deltas) {
+    int stats_len = 0;
+    if (LoadStatsBlocks(config_path, PK_MI355_PRECISION_F32, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->stream = pk_mi355_deltas_stream_create(r->am, deltas, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
+  } else if (spec) {
     int stats_len = 0;
     if (pk_mi355_load_stats(config_path, PK_MI355_PRECISION_F32, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
     if (!(r->stream = pk_mi355_frontend_stream_create(r->am, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
@@ -226,6 +230,15 @@ pk_mi355_online_recognizer_t *pk_mi355_frontend_online_recognizer_load(const cha
   if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
   if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
   return LoadOnlineRecognizer(config_path, spec, max_streams, max_step_samples, trace_capacity);
+}
+
+pk_mi355_online_recognizer_t *pk_mi355_deltas_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                                     const pk_mi355_deltas_spec_t *deltas_spec, int max_streams,
+                                                                     int64_t max_step_samples, int64_t trace_capacity) {
+  if (!config_path || !frontend_spec || !deltas_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
+  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
+  return LoadOnlineRecognizer(config_path, frontend_spec, max_streams, max_step_samples, trace_capacity, deltas_spec);
 }
 
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r) {

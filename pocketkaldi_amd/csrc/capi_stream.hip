@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "pk_delta_kernel.h"
 #include "pk_frontend.h"
 #include "pk_norm_kernel.h"
 #include "pk_plan.h"
@@ -22,6 +23,8 @@ enum SlotState { kFree = 0, kOpen = 1, kClosed = 2 };
 struct Slot {
   int state = kFree;
   int n = 0;               // CMVN frames computed
+  int nd = 0;              // a deltas object: delta frames final, n - M at most while open
+  int ring_par = 0;        //   the delta ring buffer that holds the base frames below n
   int a = 0;               // frames scored (the next row to score)
   int tail_len = 0;
   int tail_par = 0;
@@ -95,6 +98,18 @@ struct pk_mi355_stream {
   double *d_norm_win = nullptr, *d_norm_total = nullptr;     // [slots][2][feat_dim] each
   float *d_norm_table = nullptr, *d_norm_ring = nullptr;     // [slots][2][feat_dim], [slots][ring_window][feat_dim]
   int ring_window = 0;
+  // Made by pk_mi355_deltas_stream_create: StreamDeltaKernel between the normaliser and the layout.
+  // Everything in front of it -- the front-end, the statistics, every normaliser's state above, RAW slots -- is at base_dim
+  // = feat_dim / (order + 1); on every other object base_dim = feat_dim.  An audio object has a row area at every
+  // dimension.  The delta staging, (max_frames + max_streams M) rows of feat_dim floats, lies in d_upload from float
+  // delta_area on, where the layout launch finds it through the step's second record array.
+  int base_dim = 0;
+  bool has_deltas = false;
+  pk_mi355_deltas_spec_t deltas{0, 0};
+  int reach = 0;                      // M = order * window
+  float *d_delta_scales = nullptr;    // the spec's scale table (pkdelta::BuildScales)
+  float *d_delta_ring = nullptr;      // [slots][2][2 M][base_dim]
+  int64_t delta_area = 0, delta_rows = 0;
 };
 
 namespace {
@@ -125,13 +140,17 @@ bool ModelAllowed(const pk_mi355_am *am) {
 void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
   const ScorerCore &c = s->core;
   const int max_streams = s->max_streams;
+  // (a deltas object: the layout's records lie behind the UttLayout arrays, a second StreamRec array)
   s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
-                  sizeof(int32_t) * Shift4Cap(c.max_cols);
+                  (s->has_deltas ? RoundUp(sizeof(StreamRec) * max_streams, 256) : 0) + sizeof(int32_t) * Shift4Cap(c.max_cols);
   chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
-  if (s->have_stats && c.am->feat_dim != kNumBins) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
-    chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * c.am->feat_dim));
-    chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * c.am->feat_dim));
-    if (s->rows_area)                  // audio slots are laid out by StreamFeatureLayoutKernel: their history, at create
+  const int Db = s->base_dim;
+  if (s->has_deltas)                   // every slot is laid out by StreamFeatureLayoutKernel: the history, at create
+    chk(hipMalloc(&s->d_feat_hist, sizeof(float) * max_streams * 2 * s->hist_len * c.am->feat_dim));
+  if (s->have_stats && (Db != kNumBins || s->has_deltas)) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
+    chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * Db));
+    chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * Db));
+    if (s->rows_area && !s->d_feat_hist)   // audio slots are laid out by StreamFeatureLayoutKernel: their history, at create
       chk(hipMalloc(&s->d_feat_hist, sizeof(float) * max_streams * 2 * s->hist_len * c.am->feat_dim));
   } else if (s->have_stats) {
     chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * kNumBins));
@@ -140,7 +159,7 @@ void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
     chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
   }
   chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * (s->rows_area ? s->rows_area : s->upload_cap), hipHostMallocDefault));
-  chk(hipMalloc(&s->d_upload, sizeof(float) * s->upload_cap));
+  chk(hipMalloc(&s->d_upload, sizeof(float) * (s->has_deltas ? s->delta_area + s->delta_rows * c.am->feat_dim : s->upload_cap)));
   chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
   chk(hipMalloc(&s->d_meta, s->meta_bytes));
 }
@@ -157,7 +176,7 @@ int ResetSlotNorm(pk_mi355_stream *s, int slot) {
   s->slots[slot].spk_set = false;
   if (s->norm.mode != pknorm::kNormOnlineCmvn) return 0;
   if (int rc = UseDevice(s->core.device)) return rc;
-  const size_t rec = 2 * ((size_t)s->core.am->feat_dim + 1);
+  const size_t rec = 2 * ((size_t)s->base_dim + 1);
   HIP_TRY(hipMemsetAsync(s->d_norm_spk + slot * rec, 0, sizeof(double) * rec, s->core.stream));
   return 0;
 }
@@ -184,7 +203,11 @@ namespace {
 // What the create entries differ in.  entry: the name in a device failure's text.  audio: live PCM through a front-end
 // (any: the tables of a front-end spec, or null for the reference's 40 bins), step_cap in samples; else features
 // only, step_cap in frames.  stats: null (features only), or am->feat_dim sums and the count.
-struct StreamShape { const char *entry; bool audio; const float *stats; const FrontendAnyTables *any; int max_streams; int64_t step_cap; };
+// deltas: null, or the checked spec of a deltas object, whose front-end and statistics are at am->feat_dim / (order + 1).
+struct StreamShape {
+  const char *entry; bool audio; const float *stats; const FrontendAnyTables *any; int max_streams; int64_t step_cap;
+  const pk_mi355_deltas_spec_t *deltas = nullptr;
+};
 
 // Every way to a stream object; the entries have checked their other arguments.
 pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
@@ -198,7 +221,11 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   pk_mi355_stream *s = new pk_mi355_stream();
   s->max_streams = max_streams; s->max_step_samples = sh.step_cap;
   s->features_only = !sh.audio; s->have_stats = sh.stats != nullptr;
-  s->frame_cost = sh.audio ? kFrameShift : 1;
+  s->has_deltas = sh.deltas != nullptr;
+  if (sh.deltas) { s->deltas = *sh.deltas; s->reach = pkdelta::Reach(*sh.deltas); }
+  const int Db = s->base_dim = sh.deltas ? D / (sh.deltas->order + 1) : D, M = s->reach;
+  // (a NORMALIZED frame of a deltas object can be wider than 160 floats: it counts as what it takes in the staging)
+  s->frame_cost = sh.audio ? std::max(kFrameShift, D) : 1;
   s->slots.resize(max_streams);
   s->hist_len = std::max(am->left + am->right, 1);
   // Audio: a slot's segment holds at most 399 carried samples and its pushes.  A slot's rows are its new frames and the
@@ -207,12 +234,23 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   const int64_t max_frames = sh.audio ? s->wave_cap / kFrameShift + max_streams : sh.step_cap;
   // Audio at D == 40: the fbank writes d_rows, where StreamCmvnKernel reads.  At another dimension the staging holds the
   // step's samples (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
-  s->rows_area = sh.audio && D != kNumBins ? RoundUp(sh.step_cap, 64) : 0;
-  s->upload_cap = !sh.audio ? sh.step_cap * D : s->rows_area ? s->rows_area + max_frames * D : sh.step_cap;
+  // With deltas the row area is there at every base dimension, its rows Db floats wide; a closing
+  // slot emits up to M + R rows more than it was pushed, and the delta staging lies behind everything else.
+  s->rows_area = sh.audio && (D != kNumBins || sh.deltas) ? RoundUp(sh.step_cap, 64) : 0;
+  s->upload_cap = !sh.audio ? sh.step_cap * D : s->rows_area ? s->rows_area + max_frames * Db : sh.step_cap;
+  if (sh.deltas) { s->delta_area = RoundUp(s->upload_cap, 64); s->delta_rows = max_frames + (int64_t)max_streams * M; }
   CreateCheck chk{sh.entry};
-  CreateScorerCore(&s->core, am, sh.stats, D, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + 3), 262144, chk);
+  CreateScorerCore(&s->core, am, sh.stats, Db, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + M + 3), 262144, chk);
   if (sh.any) UploadSpecTables(&s->core, sh.any, &s->d_any, chk);
   CreateStepBuffers(s, chk);
+  if (sh.deltas) {     // StreamDeltaKernel's table and the slots' rings
+    float table[pkdelta::kMaxTable];
+    pkdelta::BuildScales(*sh.deltas, table);
+    const size_t bytes = sizeof(float) * (size_t)(sh.deltas->order + 1) * pkdelta::RowLen(*sh.deltas);
+    chk(hipMalloc(&s->d_delta_scales, bytes));
+    if (chk.ok) chk(hipMemcpy(s->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
+    chk(hipMalloc(&s->d_delta_ring, sizeof(float) * max_streams * 2 * 2 * M * Db));
+  }
   if (sh.audio) {
     chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
     chk(hipMalloc(&s->d_wave, sizeof(float) * s->wave_cap));
@@ -255,15 +293,45 @@ pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, cons
   return CreateStream(am, StreamShape{"features_stream_create", false, global_stats, nullptr, max_streams, max_step_frames});
 }
 
+// pk_mi355_deltas_batch_create's checks with its texts (capi_batch.hip, CheckedBatch), and for every model that entry
+// accepts in its order; an online scorer refuses an f16 model besides, as every stream entry does.  What needs no
+// finalized model -- the null arguments and the deltas spec -- is said first, so that it is said without a device too.
+pk_mi355_stream_t *pk_mi355_deltas_stream_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
+                                                 const float *global_stats, int stats_len, int max_streams, int64_t capacity) {
+  if (!am) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
+  if (!deltas || (frontend && !global_stats)) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pkdelta::CheckSpec(deltas)) return nullptr;                      // (names the field)
+  if (!ModelAllowed(am)) return nullptr;                               // f16; not finalized
+  const int D = am->feat_dim, order = deltas->order;
+  if (D % (order + 1) != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
+    return nullptr;
+  }
+  const int Db = D / (order + 1);
+  std::vector<FrontendAnyTables> any(frontend ? 1 : 0);
+  if (frontend && BuildFrontendAnyTables(frontend, any.data())) return nullptr;      // (names the field)
+  if (frontend && !FrontendFits(any[0].dim, true, am, Db, order)) return nullptr;
+  if (global_stats && !StatsLenFits(stats_len, Db, true)) return nullptr;
+  StreamShape sh{"deltas_stream_create", frontend != nullptr, global_stats, frontend ? any.data() : nullptr, max_streams, capacity};
+  sh.deltas = deltas;
+  return CreateStream(am, sh);
+}
+
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s) {
   if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
   return s->core.am->feat_dim;
+}
+
+int pk_mi355_stream_base_dim(const pk_mi355_stream_t *s) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  return s->base_dim;
 }
 
 void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   if (!s) return;
   hipSetDevice(s->core.device);
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
+  hipFree(s->d_delta_scales); hipFree(s->d_delta_ring);
   hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist); hipFree(s->d_feat_hist);
   hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta); hipFree(s->d_any);
   hipFree(s->d_norm_glob); hipFree(s->d_norm_spk); hipFree(s->d_norm_win); hipFree(s->d_norm_total); hipFree(s->d_norm_table); hipFree(s->d_norm_ring);
@@ -297,7 +365,7 @@ int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
   }
   if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
-  z.n = z.a = z.tail_len = 0;
+  z.n = z.a = z.nd = z.tail_len = 0;
   z.pending.clear();
   z.rate = rate; z.tab = tab;
   z.kind = -1;
@@ -316,11 +384,11 @@ int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind) {
   Slot &z = s->slots[slot];
   if (z.state != kFree) return Fail(PK_MI355_E_STATE, "slot %d is %s", slot, z.state == kOpen ? "open" : "closed and not yet flushed by a step");
   // (RAW at another dimension than 40, or under another normalisation spec than SLIDING, is laid out as NORMALIZED is)
-  if (kind == PK_MI355_FEATS_NORMALIZED || s->core.am->feat_dim != kNumBins || s->norm.mode != PK_MI355_NORM_SLIDING)
+  if (kind == PK_MI355_FEATS_NORMALIZED || s->base_dim != kNumBins || s->norm.mode != PK_MI355_NORM_SLIDING)
     if (int rc = EnsureFeatureHistory(s)) return rc;
   if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
-  z.n = z.a = z.tail_len = 0;
+  z.n = z.a = z.nd = z.tail_len = 0;
   z.pending.clear();
   z.rate = kSampleRate; z.tab = nullptr;
   z.kind = kind;
@@ -345,7 +413,8 @@ int pk_mi355_stream_push_features(pk_mi355_stream_t *s, int slot, const float *f
   if (s->pending_total + (int64_t)num_frames * s->frame_cost > s->max_step_samples)
     return Fail(PK_MI355_E_INVALID, "push of %d frames exceeds the step capacity (%lld pending of %lld, a frame counts %d)", num_frames,
                 (long long)s->pending_total, (long long)s->max_step_samples, s->frame_cost);
-  z.pending.insert(z.pending.end(), frames, frames + (size_t)num_frames * s->core.am->feat_dim);
+  // (a deltas object: RAW frames are in front of the deltas, base_dim wide; NORMALIZED ones are past them)
+  z.pending.insert(z.pending.end(), frames, frames + (size_t)num_frames * (z.kind == PK_MI355_FEATS_RAW ? s->base_dim : s->core.am->feat_dim));
   s->pending_total += (int64_t)num_frames * s->frame_cost;
   return 0;
 }
@@ -406,7 +475,7 @@ int pk_mi355_stream_norm_set(pk_mi355_stream_t *s, const pk_mi355_norm_spec_t *s
   if (spec->mode != PK_MI355_NORM_SLIDING) {
     if (int rc = EnsureFeatureHistory(s)) return rc;
     if (int rc = UseDevice(s->core.device)) return rc;
-    const size_t D = (size_t)s->core.am->feat_dim, n = (size_t)s->max_streams;
+    const size_t D = (size_t)s->base_dim, n = (size_t)s->max_streams;
     if (!s->d_norm_total) HIP_TRY(hipMalloc(&s->d_norm_total, sizeof(double) * 2 * D * n));
     if (!s->d_norm_table) HIP_TRY(hipMalloc(&s->d_norm_table, sizeof(float) * 2 * D * n));
   }
@@ -416,7 +485,7 @@ int pk_mi355_stream_norm_set(pk_mi355_stream_t *s, const pk_mi355_norm_spec_t *s
 
 int pk_mi355_stream_norm_set_online_cmvn(pk_mi355_stream_t *s, const pk_mi355_online_cmvn_spec_t *spec, const double *global_stats) {
   if (!s || !spec) return Fail(PK_MI355_E_INVALID, "null argument");
-  const size_t D = (size_t)s->core.am->feat_dim, n = (size_t)s->max_streams, rec = 2 * (D + 1);
+  const size_t D = (size_t)s->base_dim, n = (size_t)s->max_streams, rec = 2 * (D + 1);
   if (int rc = pknorm::CheckOnlineSpec(spec, global_stats, (int)D)) return rc;      // (names the field)
   if (int rc = NoSlotInUse(s)) return rc;
   if (int rc = EnsureFeatureHistory(s)) return rc;
@@ -451,7 +520,7 @@ int pk_mi355_stream_norm_set_speaker_stats(pk_mi355_stream_t *s, int slot, const
   if (z.state != kOpen || z.n != 0)
     return Fail(PK_MI355_E_STATE, "slot %d: speaker statistics belong to an open slot before its first frame is computed", slot);
   if (z.kind == PK_MI355_FEATS_NORMALIZED) return Fail(PK_MI355_E_STATE, "slot %d takes normalised features: no normalisation applies", slot);
-  const int D = s->core.am->feat_dim;
+  const int D = s->base_dim;
   if (mode == PK_MI355_NORM_SPEAKER) {
     std::vector<float> table((size_t)2 * D);
     if (int rc = pknorm::FinalizeSpeakerStats(stats, 1, D, s->norm.norm_means != 0, s->norm.norm_vars != 0, table.data())) return rc;
@@ -475,7 +544,7 @@ int pk_mi355_stream_norm_fetch_stats(pk_mi355_stream_t *s, int slot, double *out
     return Fail(PK_MI355_E_STATE, "statistics are accumulated in mode speaker and under online CMVN only");
   const Slot &z = s->slots[slot];
   if (z.kind == PK_MI355_FEATS_NORMALIZED) return Fail(PK_MI355_E_STATE, "slot %d takes normalised features: no statistics", slot);
-  const size_t D = (size_t)s->core.am->feat_dim;
+  const size_t D = (size_t)s->base_dim;
   for (size_t i = 0; i < 2 * (D + 1); ++i) out[i] = 0.0;
   if (z.n == 0) return 0;                               // (no frame computed since the slot was opened: the record of no frames)
   if (int rc = UseDevice(s->core.device)) return rc;
@@ -504,6 +573,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   StreamRec *recs = reinterpret_cast<StreamRec *>(s->h_meta);
   char *lay_base = s->h_meta + RoundUp(sizeof(StreamRec) * s->max_streams, 256);
   const size_t shift4_at = s->meta_bytes - sizeof(int32_t) * Shift4Cap(c.max_cols);
+  // A deltas object: lrecs[k] is what the layout launch sees for the slot of recs[k] -- for an audio
+  // or RAW slot the delta frames [nd, nd1) that StreamDeltaKernel makes final, as rows of the delta staging; for a
+  // NORMALIZED slot recs[k] itself.  On every other object the layout reads recs.
+  const bool dl = s->has_deltas;
+  StreamRec *lrecs = dl ? reinterpret_cast<StreamRec *>(lay_base + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * s->max_streams, 256)) : recs;
   // Records.  A 40-dim object: audio and RAW slots (StreamAssembleKernel, FbankKernel or FbankAnyKernel,
   // StreamCmvnKernel) from the front of the array, NORMALIZED slots (StreamFeatureLayoutKernel) from its back.  Another
   // dimension: audio slots from the front, feature slots of both kinds from the back; on an object with a front-end spec
@@ -514,7 +588,9 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   std::vector<int> who, at, flushed;                  // slots taking part, their records; closed slots with nothing left
   int64_t woff = 0, upl = 0, raw = 0, out = 0, col = 0, native_total = 0;
   int max_m = 0, n_front = 0, n_back = 0, n_audio = 0, raw_pushed = 0, chain_pushed = 0, max_feat_cols = 0;
-  const int D = am->feat_dim;
+  int64_t dout = 0;                                   // rows of the delta staging taken
+  int max_new = 0, n_delta = 0;                       // the most delta frames a record makes final; records StreamDeltaKernel serves
+  const int D = am->feat_dim, Db = s->base_dim, M = s->reach;
   // Another normalisation spec than SLIDING: nothing goes through StreamCmvnKernel's fused path.  RAW
   // slots at 40 become back records as at every other dimension (normalised where they lie in the upload staging); audio
   // slots at 40 stay in front, their rows in d_rows (row_off counts from there), and are laid out from there.
@@ -538,26 +614,30 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     // (a front-end spec at a dimension other than 40, DESIGN.md section 18: audio records go the same way, their rows
     // written into the staging's row area by FbankAnyKernel; they stay in front, where the assembly and the fbank look)
     const bool feats = z.kind >= 0, spec_rows = !feats && s->rows_area > 0;
-    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && (D != kNumBins || !sliding));
+    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && (Db != kNumBins || !sliding || dl));
+    const bool delta_rec = dl && z.kind != PK_MI355_FEATS_NORMALIZED;
+    const int width = z.kind == PK_MI355_FEATS_NORMALIZED ? D : Db;       // floats of a pushed frame
     const bool front_rows = !feats && !sliding && !spec_rows;       // an audio slot at 40 under a norm spec: laid out from d_rows
     const int new_len = feats    ? 0
                         : !z.tab ? (int)z.pending.size()
                                  : (int)((closed ? ResampleNumOutput(z.tab->host, z.n_in) : ResampleNumFinal(z.tab->host, z.n_in)) - z.n_prod);
     const int seg = z.tail_len + new_len;
-    const int m = feats ? (int)(z.pending.size() / D) : pk_mi355_num_frames(seg);
+    const int m = feats ? (int)(z.pending.size() / width) : pk_mi355_num_frames(seg);
     const int n = z.n + m;
-    const int b = closed ? n : std::max(z.a, n - R);    // open: R frames of look-ahead held back
+    // open: R frames of look-ahead held back -- and in front of deltas M base frames more (pkdelta::StreamDeltaAdvance)
+    const pkdelta::StreamDeltaCounts dc = delta_rec ? pkdelta::StreamDeltaAdvance(n, z.nd, z.a, M, R, closed) : pkdelta::StreamDeltaCounts{n, 0};
+    const int b = delta_rec ? dc.b : closed ? n : std::max(z.a, n - R);
     if (new_len == 0 && m == 0 && b == z.a) {
       if (closed) flushed.push_back(slot);
       continue;
     }
     const int rec_at = layout ? s->max_streams - 1 - n_back++ : n_front++;
     StreamRec &r = recs[rec_at];
-    r.kind = z.kind; r.hist_par = z.hist_par;
+    r.kind = z.kind; r.hist_par = z.hist_par; r.ring_par = z.ring_par;
     r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
     r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
     r.woff = woff; r.new_off = upl; r.raw_base = layout ? 0 : raw;
-    r.row_off = spec_rows ? s->rows_area + raw * D : front_rows ? raw * D : upl;
+    r.row_off = spec_rows ? s->rows_area + raw * Db : front_rows ? raw * Db : upl;
     r.col_base = 0; r.cols = 0;
     if (b > z.a) {
       // Rows slot after slot, each padded to four; the slot's columns a - L .. b + R - 1 in a region of RoundUp(b - a, 4)
@@ -571,7 +651,18 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       spans.push_back({out, shift});
       if (layout || spec_rows || front_rows) max_feat_cols = std::max(max_feat_cols, r.cols);
     }
-    woff += seg; upl += feats ? (int64_t)m * D : new_len;
+    if (dl) {
+      StreamRec &lr = lrecs[rec_at];
+      lr = r;
+      if (delta_rec) {
+        lr.n_old = z.nd; lr.m = dc.nd1 - z.nd;
+        lr.row_off = s->delta_area + dout * D;
+        dout += lr.m;
+        max_new = std::max(max_new, lr.m);
+        ++n_delta;
+      }
+    }
+    woff += seg; upl += feats ? (int64_t)m * width : new_len;
     if (!layout) raw += m;
     if (z.tab && new_len) native_total += (int64_t)z.native.size();
     if (!feats) { max_m = std::max(max_m, m); ++n_audio; }
@@ -581,14 +672,20 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   }
   const int64_t upl_cap = s->rows_area ? s->rows_area : s->upload_cap;      // (a row area: the pushes end where it begins)
   const bool staging_fits = woff <= s->wave_cap && upl <= upl_cap && native_total <= s->native_cap &&
-                            (!s->rows_area || s->rows_area + raw * D <= s->upload_cap);
+                            (!s->rows_area || s->rows_area + raw * Db <= s->upload_cap) && dout <= s->delta_rows;
   const bool rows_fit = raw <= c.max_frames && RoundUp(out, kTileF16) <= c.max_cols && col <= c.max_cols;
+  if (dl && n_front > 0 && !s->rows_area)             // (pk_plan.cc: no plan serves front records of a deltas object without a row area)
+    return Fail(PK_MI355_E_INVALID, "internal: a deltas stream with audio records and no row area");
   if (!staging_fits || !rows_fit || ((n_back > 0 || (!sliding && n_front > 0)) && !s->d_feat_hist))
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
   // A front-end spec at D != 40: the back block (taken last first) moves up behind the front one, as told above.
   if (s->rows_area) {
     const std::vector<StreamRec> back(recs + (s->max_streams - n_back), recs + s->max_streams);
     for (int j = 0; j < n_back; ++j) recs[n_front + j] = back[n_back - 1 - j];
+    if (dl) {
+      const std::vector<StreamRec> lback(lrecs + (s->max_streams - n_back), lrecs + s->max_streams);
+      for (int j = 0; j < n_back; ++j) lrecs[n_front + j] = lback[n_back - 1 - j];
+    }
     for (int &k : at)
       if (k >= n_front) k = n_front + (s->max_streams - 1 - k);
   }
@@ -603,9 +700,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   for (size_t k = 0; k < who.size(); ++k) {
     const StreamRec &r = recs[at[k]];
     Slot &z = s->slots[r.slot];
+    const bool delta_rec = dl && z.kind != PK_MI355_FEATS_NORMALIZED;
+    const int lay_m = lrecs[at[k]].m;    // the fresh rows the layout sees (behind deltas: the delta frames that became final)
     if (z.kind >= 0) {                   // pushed frames, frame-major
-      if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * D);
-      if (r.m && (z.kind == PK_MI355_FEATS_NORMALIZED || D != kNumBins || !sliding)) z.hist_par ^= 1;    // the step writes the other history buffer
+      if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * (z.kind == PK_MI355_FEATS_NORMALIZED ? D : Db));
+      if (lay_m && (z.kind == PK_MI355_FEATS_NORMALIZED || Db != kNumBins || !sliding || dl)) z.hist_par ^= 1;    // the step writes the other history buffer
     } else if (z.tab && r.new_len) {
       // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
       const ResampleTable &t = z.tab->host;
@@ -626,7 +725,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     if (z.kind < 0) {
       z.tail_len = r.tail_len + r.new_len - kFrameShift * r.m;
       z.tail_par ^= 1;
-      if ((s->rows_area || !sliding) && r.m) z.hist_par ^= 1;     // laid out by StreamFeatureLayoutKernel: the step writes the other history buffer
+      if ((s->rows_area || !sliding) && lay_m) z.hist_par ^= 1;     // laid out by StreamFeatureLayoutKernel: the step writes the other history buffer
+    }
+    if (delta_rec) {
+      if (r.m) z.ring_par ^= 1;          // StreamDeltaKernel writes the other ring buffer
+      z.nd = lrecs[at[k]].n_old + lay_m;
     }
     z.n = r.n_old + r.m;
     z.a = r.b;
@@ -664,6 +767,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   HIP_TRY(hipEventRecord(s->ev_staged, c.stream));
   s->staged = true;
   const StreamRec *d_recs = reinterpret_cast<const StreamRec *>(s->d_meta);
+  const StreamRec *d_lrecs = reinterpret_cast<const StreamRec *>(s->d_meta + (reinterpret_cast<char *>(lrecs) - s->h_meta));
   const char *d_lay = s->d_meta + (lay_base - s->h_meta);
   const int64_t *d_woff = reinterpret_cast<const int64_t *>(d_lay);
   const int64_t *d_rawb = d_woff + s->max_streams;
@@ -671,11 +775,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
   // The plan (pk_plan.h; DESIGN.md, "The two plans").  The front stage: assembly and fbank over the n_front front records,
   // the rows [raw_base][D] going to d_rows, or on an object with a row area to the staging behind the samples.
-  const pkplan::StreamPlan plan = pkplan::PlanStream(s->rows_area != 0, nmode, pkplan::StepCounts{n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed});
+  const pkplan::StreamPlan plan = pkplan::PlanStream(s->rows_area != 0, nmode, pkplan::StepCounts{n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed}, dl);
   if (plan.front) {
     float *dst = s->rows_area ? s->d_upload + s->rows_area : s->d_rows;
     LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
-    if (s->d_any) LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, D, dst, c.stream);
+    if (s->d_any) LaunchFbankAny(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, s->d_any, Db, dst, c.stream);
     else LaunchFbank(s->d_wave, nullptr, lay, n_front, max_m, c.d_tables, dst, c.stream);
   }
   // Then every block of records through its normaliser (the back block's before its layout, which reads the rows the
@@ -683,12 +787,14 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   for (int k = 0; k < plan.n; ++k) {
     const pkplan::Block &bl = plan.block[k];
     const StreamRec *r = d_recs + (bl.back ? s->max_streams - n_back : 0);
+    const StreamRec *lr = d_lrecs + (bl.back ? s->max_streams - n_back : 0);     // (r itself without deltas)
     float *rows = bl.step_rows ? s->d_rows : s->d_upload;
     if (bl.raw_rows) LaunchStreamRawRows(r, bl.count, s->d_upload, s->d_rows, c.stream);
-    if (bl.norm == pkplan::kStreamNorm) LaunchStreamNorm(r, bl.count, D, rows, NormState(s), c.stream);
-    else if (bl.norm == pkplan::kStreamCmvnChain) LaunchStreamCmvnChain(r, bl.count, D, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
+    if (bl.norm == pkplan::kStreamNorm) LaunchStreamNorm(r, bl.count, Db, rows, NormState(s), c.stream);
+    else if (bl.norm == pkplan::kStreamCmvnChain) LaunchStreamCmvnChain(r, bl.count, Db, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
+    if (bl.delta && n_delta > 0) LaunchStreamDelta(r, lr, bl.count, max_new, Db, s->deltas, s->d_delta_scales, rows, s->d_delta_ring, c.stream);
     if (bl.fused) LaunchStreamCmvn(r, bl.count, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R, c.d_yt, c.ldy, c.stream);
-    else LaunchStreamFeatureLayout(r, bl.count, max_feat_cols, rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
+    else LaunchStreamFeatureLayout(lr, bl.count, max_feat_cols, rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
   }
   const Operand op{c.d_yt, nullptr, c.ldy, ZeroSource(c), reinterpret_cast<const int32_t *>(s->d_meta + shift4_at)};
   const Lane lane{c.stream, &c.exec};

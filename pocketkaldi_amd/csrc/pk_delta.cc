@@ -1,5 +1,6 @@
 // pk_delta.cc -- delta features on the host (pk_delta.h): the check, the scale table and the whole
-// rule for one matrix.  No HIP: g++ builds it, into the library and into tests/cpp/delta_test.cc.
+// rule for one matrix; the streaming apply of a live slot (section 24).  No HIP: g++ builds it, into the library and into
+// tests/cpp/delta_test.cc and tests/cpp/stream_delta_test.cc.
 #include "pk_delta.h"
 
 #include <vector>
@@ -38,6 +39,44 @@ void BuildScales(const pk_mi355_deltas_spec_t &spec, float *table) {
     const float inv = (float)(1.0 / (double)normalizer);
     for (int j = -(po + W); j <= po + W; ++j) cur[j] = cur[j] * inv;
   }
+}
+
+StreamDeltaHost::StreamDeltaHost(const pk_mi355_deltas_spec_t &spec, int base_dim) : spec_(spec), Db_(base_dim), M_(Reach(spec)) {
+  BuildScales(spec_, table_);
+  for (int p = 0; p < 2; ++p) ring_[p] = new float[(size_t)2 * M_ * Db_];
+}
+
+StreamDeltaHost::~StreamDeltaHost() {
+  for (int p = 0; p < 2; ++p) delete[] ring_[p];
+}
+
+int StreamDeltaHost::Push(const float *x, int m, bool closed, float *out) {
+  const int n_old = n_, n = n_ + m, L = RowLen(spec_), Db = Db_, M = M_;
+  const StreamDeltaCounts c = StreamDeltaAdvance(n, nd_, 0, M, 0, closed);
+  const float *old = ring_[par_];
+  auto frame = [&](int f) {               // f in [max(n_old - 2 M, 0), n)
+    const StreamDeltaSource s = StreamDeltaPick(f, n_old, M);
+    return s.fresh ? x + (size_t)s.row * Db : old + (size_t)s.row * Db;
+  };
+  const size_t F = (size_t)(spec_.order + 1) * Db;
+  for (int t = nd_; t < c.nd1; ++t)
+    for (int i = 0; i <= spec_.order; ++i)
+      for (int d = 0; d < Db; ++d)
+        out[(size_t)(t - nd_) * F + (size_t)i * Db + d] = DeltaApply<float>(table_ + i * L + M, i * spec_.window, [&](int j) {
+          const int tt = t + j;
+          return frame(tt < 0 ? 0 : tt > n - 1 ? n - 1 : tt)[d];
+        });
+  if (m > 0) {                            // frames [max(n - 2 M, 0), n) to the other buffer, which nothing above reads
+    float *next = ring_[par_ ^ 1];
+    for (int f = n - 2 * M > 0 ? n - 2 * M : 0; f < n; ++f) {
+      const float *src = frame(f);
+      for (int d = 0; d < Db; ++d) next[(size_t)(f % (2 * M)) * Db + d] = src[d];
+    }
+    par_ ^= 1;
+  }
+  const int made = c.nd1 - nd_;
+  n_ = n; nd_ = c.nd1;
+  return made;
 }
 
 }  // namespace pkdelta

@@ -2,7 +2,9 @@
 // spec's check, the scale table and the per-element apply step.  Plain C++: no HIP header; pk_delta.cc is compiled by g++
 // like pk_norm.cc, so it also builds into a stand-alone program that runs under the host sanitizers
 // (tests/cpp/delta_test.cc).  delta.hip includes this header for DeltaApply: the kernel and the host run the same
-// lines.  Internal, like pk_norm.h.
+// lines.  Below them what a live slot adds: the frame accounting of one step, the choice between
+// a step's fresh rows and the slot's ring -- which StreamDeltaKernel compiles too -- and a host streaming apply for the
+// stand-alone test (tests/cpp/stream_delta_test.cc).  Internal, like pk_norm.h.
 #ifndef PK_DELTA_H_
 #define PK_DELTA_H_
 
@@ -44,6 +46,46 @@ PK_NORM_HD inline V DeltaApply(const float *centre, int M, Load x) {
   }
   return acc;
 }
+
+// ------------------------------------------------------------------ a live slot
+// One step of a slot's frame accounting.  n: normalised base frames after the step's pushes; nd: delta frames final
+// before it; a: rows scored before it; M = order * window; R: the model's right context.  Delta frames [nd, nd1) become
+// final (an open slot holds M base frames back, a closed one none); rows [a, b) are scored (an open slot holds R delta
+// frames back).
+struct StreamDeltaCounts { int nd1, b; };
+inline StreamDeltaCounts StreamDeltaAdvance(int n, int nd, int a, int M, int R, bool closed) {
+  const int nd1 = closed ? n : (n - M > nd ? n - M : nd);
+  const int b = closed ? nd1 : (nd1 - R > a ? nd1 - R : a);
+  return StreamDeltaCounts{nd1, b};
+}
+
+// Where normalised base frame f of a slot lies during a step that found n_old frames computed: among the step's fresh
+// rows (row f - n_old), or in the slot's ring of the last 2 M frames (entry f mod 2 M; only f >= n_old - 2 M is there).
+struct StreamDeltaSource { bool fresh; int row; };
+PK_NORM_HD inline StreamDeltaSource StreamDeltaPick(int f, int n_old, int M) {
+  return f >= n_old ? StreamDeltaSource{true, f - n_old} : StreamDeltaSource{false, f % (2 * M)};
+}
+
+// The live rule on the host (test-only, internal; tests/cpp/stream_delta_test.cc holds it to pk_mi355_deltas_apply on
+// the whole matrix): what StreamDeltaKernel does for one slot, with the same accounting, the same pick and a ring of
+// exactly 2 M frames.  Push(x, m, closed, out): m normalised base rows [m][Db]; appends the rows [.][(order + 1) Db]
+// that became final to *out and returns how many.  Nothing may be pushed after closed.
+class StreamDeltaHost {
+ public:
+  StreamDeltaHost(const pk_mi355_deltas_spec_t &spec, int base_dim);
+  ~StreamDeltaHost();
+  StreamDeltaHost(const StreamDeltaHost &) = delete;
+  StreamDeltaHost &operator=(const StreamDeltaHost &) = delete;
+  int Push(const float *x, int m, bool closed, float *out);      // out: room for m + M rows
+  int frames() const { return n_; }
+  int final_frames() const { return nd_; }
+
+ private:
+  pk_mi355_deltas_spec_t spec_;
+  int Db_, M_, n_ = 0, nd_ = 0, par_ = 0;
+  float table_[kMaxTable];
+  float *ring_[2];                // two buffers of exactly 2 M * Db floats each, used in turn
+};
 
 }  // namespace pkdelta
 

@@ -45,22 +45,25 @@ BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_g
   return p;
 }
 
-StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k) {
+StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k, bool deltas) {
   StreamPlan p;
   p.front = k.n_audio > 0;
   const bool sliding = mode == PK_MI355_NORM_SLIDING;
   // what normalises fresh rows outside StreamCmvnKernel's fused path (mode none: nothing)
   const StreamNormaliser norm = sliding ? kStreamCmvnChain : mode == PK_MI355_NORM_NONE ? kNoNormaliser : kStreamNorm;
   if (row_area) {       // audio, RAW and NORMALIZED records in one block, all rows in the staging (NORMALIZED ones return from the normaliser)
-    p.block[p.n++] = Block{false, k.n_front + k.n_back, false, false, k.max_m > 0 || k.chain_pushed > 0 ? norm : kNoNormaliser, false};
+    p.block[p.n++] = Block{false, k.n_front + k.n_back, false, false, k.max_m > 0 || k.chain_pushed > 0 ? norm : kNoNormaliser, false, deltas};
     return p;
   }
-  if (k.n_front > 0 && sliding)                       // audio and RAW records at 40 dimensions
+  // (A deltas object has front records only with a row area, above: one with a front-end has a row area at every base
+  // dimension, a features-only one has no front records.  pk_mi355_stream_step refuses the cell below with deltas set --
+  // its delta staging lies in the upload staging, which a block of d_rows could not address.)
+  if (k.n_front > 0 && sliding && !deltas)            // audio and RAW records at 40 dimensions
     p.block[p.n++] = Block{false, k.n_front, true, k.raw_pushed > 0, kNoNormaliser, true};
   else if (k.n_front > 0)                             // a norm spec: audio records alone, laid out from d_rows
-    p.block[p.n++] = Block{false, k.n_front, true, false, k.max_m > 0 ? norm : kNoNormaliser, false};
+    p.block[p.n++] = Block{false, k.n_front, true, false, k.max_m > 0 ? norm : kNoNormaliser, false, deltas};
   if (k.n_back > 0)                                   // NORMALIZED records, and the RAW ones normalised where they were pushed
-    p.block[p.n++] = Block{true, k.n_back, false, false, k.chain_pushed > 0 ? norm : kNoNormaliser, false};
+    p.block[p.n++] = Block{true, k.n_back, false, false, k.chain_pushed > 0 ? norm : kNoNormaliser, false, deltas};
   return p;
 }
 

@@ -38,16 +38,20 @@ enum StreamNormaliser { kNoNormaliser, kStreamNorm, kStreamCmvnChain };
 // A run of records that goes through one normaliser and one layout.  back: the records at the array's end (the last
 // n_back), else those from record 0.  step_rows: the rows lie in d_rows (the fbank's), else in the upload staging.
 // raw_rows: StreamRawRowsKernel first copies the RAW records' pushed rows to d_rows.  fused: StreamCmvnKernel normalises
-// and lays out in one launch; else the normaliser (if any), then StreamFeatureLayoutKernel.
-struct Block { bool back; int count; bool step_rows, raw_rows; StreamNormaliser norm; bool fused; };
+// and lays out in one launch; else the normaliser (if any), then StreamFeatureLayoutKernel.  delta (a deltas object,
+// DESIGN.md section 24): StreamDeltaKernel between the two, and the layout reads the step's second record array.
+struct Block { bool back; int count; bool step_rows, raw_rows; StreamNormaliser norm; bool fused; bool delta = false; };
 struct StepCounts { int n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed; };
 struct StreamPlan {
   bool front = false;            // StreamAssembleKernel and the fbank run over the n_front front records
   int n = 0;
   Block block[2];
 };
-// row_area: an object with a front-end spec at another dimension than 40, whose fresh rows all lie in the upload staging.
-StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k);
+// row_area: an object with a front-end spec at another dimension than 40, or a deltas object with a front-end, whose
+// fresh rows all lie in the upload staging.  deltas: an object made by pk_mi355_deltas_stream_create -- nothing takes the
+// fused path (StreamCmvnKernel writes the layout itself, as FusedCmvn on the batch side), SLIDING runs the chain at the
+// base dimension, at 40 too, and every block goes normaliser, StreamDeltaKernel, layout.
+StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k, bool deltas = false);
 
 }  // namespace pkplan
 

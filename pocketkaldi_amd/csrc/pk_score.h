@@ -27,6 +27,7 @@ struct StreamRec {
   int32_t kind;        // -1: audio; PK_MI355_FEATS_RAW / _NORMALIZED: a feature slot (tail_len = new_len = 0, an empty
                        // segment; m = frames pushed since the last step, [m][D] floats at new_off of the upload staging)
   int32_t hist_par;    // NORMALIZED: the slot's history buffer that holds the frames below n_old (the step writes the other one)
+  int32_t ring_par;    // a deltas object: the slot's delta ring buffer that holds the base frames below n_old
   int64_t woff;        // first sample of the segment in the wave staging
   int64_t new_off;     // first pushed sample in the upload staging
   int64_t raw_base;    // first row of the slot's new frames in the step's raw rows

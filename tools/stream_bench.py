@@ -51,6 +51,12 @@ profiles/frontend_stream_bench.json holds those legs beside the plain audio leg.
 normalisation on the scorer, with stream 0's own statistics as the global record and as every
 slot's speaker record; the check is against the batch scorer under the same spec.  profiles/stream_bench_cmvn_*.json
 hold the default leg and one leg per mode.
+
+--deltas order,window puts delta features in front of the splice (pk.DeltaSpec), with
+--features raw --feat-dim Db (synthetic [T][Db] rows through the tiny model at (order + 1) Db, Db = 40 too) or with audio
+and --frontend (model S at (order + 1) x the spec's dimension); the check is against the batch deltas scorer.  The leg to
+hold it against is --features normalized --feat-dim (order + 1) Db on the same tree: the difference is StreamDeltaKernel
+and the normaliser.  profiles/stream_deltas_bench.json holds those legs.
 """
 import argparse
 import json
@@ -91,7 +97,19 @@ def main():
     ap.add_argument("--frontend", default=None, help="a front-end spec, key=value,... (audio streams; model S at its dimension)")
     ap.add_argument("--cmvn", default=None, help="a normalisation spec for the scorer, pk.parse_norm's text (mode=none | speaker | online,...; "
                     "DESIGN.md section 20); the global and the speakers' records are stream 0's own statistics")
+    ap.add_argument("--deltas", default=None, help="order,window: delta features in front of the splice (DESIGN.md section 24), with "
+                    "--features raw --feat-dim Db or with audio and --frontend")
     a = ap.parse_args()
+    dspec = None
+    if a.deltas is not None:
+        try:
+            dspec = pk.DeltaSpec(*[int(v) for v in a.deltas.split(",")])
+            dspec.check()
+        except (ValueError, TypeError, pk.PkError) as e:
+            ap.error("--deltas order,window: %s" % e)
+        if a.decode or a.commit or a.endpoint or not ((a.features == "raw") != (a.frontend is not None)):
+            ap.error("--deltas takes --features raw --feat-dim Db, or audio with --frontend, and no decoder")
+    synthetic = a.feat_dim != 40 or (dspec is not None and a.features is not None)
     if a.cmvn is not None and a.features == "normalized":
         ap.error("--cmvn takes audio or raw features")
     spec = None
@@ -102,7 +120,7 @@ def main():
             spec = pk.parse_frontend(a.frontend)
         except ValueError as e:
             ap.error(str(e))
-    if a.feat_dim != 40 and (a.features is None or a.decode or a.commit or a.endpoint):
+    if a.feat_dim != 40 and dspec is None and (a.features is None or a.decode or a.commit or a.endpoint):
         ap.error("--feat-dim takes --features and no decoder")
     a.decode = a.decode or a.commit or a.endpoint
 
@@ -117,24 +135,27 @@ def main():
     model_name = "S (440 -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax"
     if spec is not None:
         D = spec.dim
-        layers, prior, L, R = synth.model("S", feat_dim=D)
+        Dm = D if dspec is None else dspec.dim(D)
+        layers, prior, L, R = synth.model("S", feat_dim=Dm)
         am = pk.AcousticModel(layers, prior, L, R)
-        model_name = "S at feat_dim %d (%d -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax; front-end %r" % (D, 11 * D, spec)
+        model_name = "S at feat_dim %d (%d -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax; front-end %r%s" % (
+            Dm, 11 * Dm, spec, "" if dspec is None else "; %r" % dspec)
         fb = pk.Frontend(spec).compute(waves[0])
         g = np.concatenate([fb.astype(np.float64).mean(axis=0) * 2500.0, [2500.0]]).astype(np.float32)
-        sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk, frontend=spec)
-    elif a.feat_dim != 40:
+        sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk, frontend=spec, deltas=dspec)
+    elif synthetic:
         D = a.feat_dim
-        layers, prior, L, R = synth.model("tiny", feat_dim=D)
+        Dm = D if dspec is None else dspec.dim(D)
+        layers, prior, L, R = synth.model("tiny", feat_dim=Dm)
         am = pk.AcousticModel(layers, prior, L, R)
-        model_name = "tiny at feat_dim %d (L = R = 5), f32, stable softmax" % D
+        model_name = "tiny at feat_dim %d (L = R = 5), f32, stable softmax%s" % (Dm, "" if dspec is None else "; %r in front, base %d" % (dspec, D))
         g = np.concatenate([np.full(D, 3.0 * 2500.0), [2500.0]]).astype(np.float32)
         T = pk.num_frames(len(waves[0]))
         base = [(5.0 * np.random.default_rng(u).standard_normal((T, D)) + 3.0).astype(np.float32) for u in range(4)]
         feats = [base[u % 4] for u in range(a.streams)]
         chunk = int(round(a.chunk_ms / 10.0))                  # frames per step
         nsteps = (T + chunk - 1) // chunk
-        sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None)
+        sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None, deltas=dspec)
     elif a.features:
         bs = pk.BatchScorer(am, g, a.streams, sum(len(w) for w in waves))
         bs.set_waves(waves)
@@ -152,7 +173,7 @@ def main():
         if feats:
             rows0 = feats[0]
         else:
-            bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec)
+            bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec, deltas=dspec)
             bs.set_waves(waves[:1])
             bs.score(0.1)
             rows0 = bs.fetch_fbank(0)
@@ -229,11 +250,11 @@ def main():
     run(False, min(nsteps, 100))             # warm-up: a pass of at most 100 steps
     walls, frames, rows0 = run(True)
     walls_ms = np.array(walls) * 1e3
-    if a.feat_dim != 40:
-        bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g)
+    if synthetic:
+        bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g, deltas=dspec)
         bs.set_features(feats[:1], a.features)
     else:
-        bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec)
+        bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec, deltas=dspec)
         bs.set_waves(waves[:1])
     if norm is not None:
         bs.set_norm(norm, pk.cmvn_normalize(feats[0] if feats else bs_rows(bs), pk.NormSpec("utterance", True, True))[1]) \
@@ -245,14 +266,15 @@ def main():
     rec = {
         "streams": a.streams, "seconds": a.seconds, "chunk_ms": a.chunk_ms, "steps": len(walls),
         "input": "features, %s, %d frames a push" % (a.features, chunk) if feats else "audio",
-        "model": model_name, "cmvn": a.cmvn,
+        "model": model_name, "cmvn": a.cmvn, "deltas": a.deltas,
         "device": torch.cuda.get_device_name(0),
         "step_ms": {"median": float(np.median(walls_ms)), "p90": float(np.percentile(walls_ms, 90)),
                     "max": float(walls_ms.max())},
         "frames": int(frames),
         "frames_per_s": float(frames / (walls_ms.sum() / 1e3)),
         "rtf": float(np.median(walls_ms) / a.chunk_ms),
-        "algorithmic_delay_ms": {"window_and_lookahead": 15.0 + 10.0 * R, "plus_chunk_at_most": a.chunk_ms},
+        "algorithmic_delay_ms": {"window_and_lookahead": 15.0 + 10.0 * (R + (dspec.order * dspec.window if dspec else 0)),
+                                 "plus_chunk_at_most": a.chunk_ms},
         "check_stream0_equals_batch": bool(ok),
     }
     if dec:
