@@ -571,6 +571,68 @@ pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355
 /* Db of a batch made by the entry above; feat_dim on every other batch; 0 for NULL.                                 */
 int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b);
 
+/* ---- Feature transforms: Kaldi's splice-feats | transform-feats (LDA+MLLT: 13 x 7 = 91 -> 40)
+ * and per-utterance transform-feats (fMLLR: 40 -> 40, a matrix per speaker) as the last stage in front of the first
+ * layer of a batch scorer, behind the normalisation and the deltas.  Restated from the tools' description (splice-feats
+ * repeats the first and last frame; transform-feats does AddMatMat, then adds the offset column with AddVecToRows --
+ * hence "offset last"); it has not been compared with a Kaldi binary, and Kaldi leaves the product's order to BLAS, so
+ * agreement with Kaldi is within rounding.  The online objects take no transform yet.                               */
+typedef struct pk_mi355_transform_spec {
+  int32_t left_context, right_context;   /* frames spliced to the left and right: each 0 .. 16, together at most 16 */
+  int32_t in_dim;                        /* Dp, the width of the rows the stage reads: 1 .. 512 */
+  int32_t rows, cols;                    /* the matrix: rows 1 .. 2048 outputs; cols K = (left + right + 1) * Dp (linear)
+                                            or K + 1 (affine: the last column is the offset) */
+  const float *matrix;                   /* row-major [rows][cols], Kaldi's layout; every entry finite */
+} pk_mi355_transform_spec_t;
+/* in_dim is explicit because at left = right = 0 a 41-column matrix may be 41 -> linear or 40 -> affine.
+ * matrix == NULL with rows == cols == 0 and left == right == 0: no global stage -- the object then exists for
+ * per-utterance matrices only, and its output dimension is in_dim.
+ *
+ * One output o of frame t of an utterance of T frames, in float, with L = left_context, R = right_context:
+ *   acc = +0.0f
+ *   for j = -L .. R ascending, for d = 0 .. Dp - 1 ascending:
+ *     acc = acc + (m[o][(j + L) * Dp + d] * x[clamp(t + j, 0, T - 1)][d])      a rounded product, a rounded add, no fma
+ *   if affine: acc = acc + m[o][K]
+ * No tap is skipped: a zero matrix entry times an inf is NaN, as BLAS would give.  T == 0: nothing happens.  A NaN at
+ * x[t][d] makes every output of frames [t - R, t + L] of its own utterance NaN and touches nothing else.  -0.0 cannot
+ * survive the +0.0f start.  The per-utterance stage is the same rule with L = R = 0, in_dim = the global stage's output
+ * dimension (the model's feat_dim) and utterance u's own [feat_dim][feat_dim] or [feat_dim][feat_dim + 1] matrix; it
+ * runs after the global stage, in the call for which matrices were handed over.
+ *
+ * pk_mi355_transform_check: PK_MI355_E_INVALID with a text that names the field -- a null spec, a context outside
+ * [0, 16] or a sum above 16, in_dim outside [1, 512], rows outside [1, 2048], cols that is neither K nor K + 1 (both
+ * numbers named), a null matrix in any but the all-zero form, an entry that is not finite (the first such row and
+ * column named).  pk_mi355_transform_out_dim: rows (in_dim without a matrix), or the negative code.
+ * pk_mi355_transform_apply: the rule on the host for one matrix x [T][in_dim] -> y [T][out_dim] (not in place; without
+ * a matrix a copy): the restatement the GPU path is held to.  Host only, all three.                                  */
+int pk_mi355_transform_check(const pk_mi355_transform_spec_t *spec);
+int pk_mi355_transform_out_dim(const pk_mi355_transform_spec_t *spec);
+int pk_mi355_transform_apply(const pk_mi355_transform_spec_t *spec, const float *x, int num_frames, float *y);
+/* A batch scorer with the transform in front of the splice.  deltas may be NULL; frontend NULL: features only (capacity
+ * counts frames; global_stats may be NULL), else capacity counts 16 kHz samples and global_stats is required.
+ * Db = in_dim / (order + 1) with deltas (must divide), in_dim without; a front-end must produce Db; stats_len must be
+ * Db + 1; pk_mi355_transform_out_dim must be pk_mi355_am_feat_dim(am).  PK_MI355_E_INVALID naming both numbers
+ * otherwise.  Checked in this order: model state, null arguments, deltas spec, transform spec, divisibility, front-end
+ * spec, front-end dimension, stats_len, output dimension, capacity, the f16 multiple-of-8 rule on feat_dim.
+ * Stage order: front-end or the caller's PK_MI355_FEATS_RAW rows [T][Db] -> the normalisation at Db (any spec; SLIDING
+ * runs the chain kernel at every Db) -> DeltaKernel (with deltas) -> TransformKernel with the global matrix (if there is
+ * one) -> TransformKernel with the matrices of pk_mi355_transform_set_utt (if any were handed over for the call) -> the
+ * layout at feat_dim -> the layers; the transform launches lie inside the PK_MI355_K_CMVN timing slot.  Everything in
+ * front of the transform is at Db, as on a deltas batch: the RAW rows of pk_mi355_features_set*, fetch_fbank, speaker
+ * and global records, fetch_stats.  PK_MI355_FEATS_NORMALIZED features stay [T][feat_dim], past every stage.
+ * pk_mi355_batch_fetch_cmvn returns what the first layer reads.  The matrix is copied: it need not outlive the call.  */
+pk_mi355_batch_t *pk_mi355_transform_batch_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform,
+                                                  const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
+                                                  const float *global_stats, int stats_len, int max_utts, int64_t capacity);
+/* in_dim of a batch made by the entry above; feat_dim on every other batch; 0 for NULL.                             */
+int pk_mi355_transform_in_dim(const pk_mi355_batch_t *b);
+/* Per-utterance matrices for the NEXT score call, which consumes them (as speaker records): mats [num_utts][rows][cols],
+ * rows = feat_dim, cols = feat_dim (linear) or feat_dim + 1 (affine), else PK_MI355_E_INVALID; an entry that is not
+ * finite is PK_MI355_E_INVALID and names the utterance.  Matrices for another number of utterances than the call's make
+ * pk_mi355_batch_score fail with PK_MI355_E_STATE; so does this call on a batch not made by
+ * pk_mi355_transform_batch_create.  No matrices handed over: the stage does not run.                                */
+int pk_mi355_transform_set_utt(pk_mi355_batch_t *b, const float *mats, int rows, int cols, int num_utts);
+
 /* ---- Kaldi archives and script files of float matrices: where features usually are on disk.
  * Read on the host, HIP-free.  Binary ("\0B", "FM " / "DM ", 4 + int32 rows, 4 + int32 cols, values) and text (" [", one
  * row per line, " ]") matrices, any mixture in one archive; doubles are narrowed with one (float) cast.  An archive is
@@ -1194,6 +1256,15 @@ pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path
 pk_mi355_recognizer_t *pk_mi355_deltas_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
                                                        const pk_mi355_deltas_spec_t *deltas_spec, int precision, int max_utts,
                                                        int64_t max_total_samples, int64_t trace_capacity);
+/* The same with a transform, behind deltas when deltas_spec is not NULL, for a model whose
+ * features are the transform's output: the model file's cmvn_stats holds pk_mi355_frontend_dim + 1 entries, and the
+ * batch is pk_mi355_transform_batch_create's, whose refusals are this entry's; bad specs are refused first.
+ * Per-utterance matrices for a process call: pk_mi355_transform_set_utt on pk_mi355_recognizer_batch before it, as
+ * speaker records are handed over.  process_features with PK_MI355_FEATS_RAW takes [T][pk_mi355_frontend_dim].      */
+pk_mi355_recognizer_t *pk_mi355_transform_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                          const pk_mi355_deltas_spec_t *deltas_spec,
+                                                          const pk_mi355_transform_spec_t *transform_spec, int precision, int max_utts,
+                                                          int64_t max_total_samples, int64_t trace_capacity);
 void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r);
 /* The owned objects: beam, trace gc, softmax mode, f16 calibration and every result getter (words, weight, ok,
  * alignment, word segments) are their existing entries.                                                          */

@@ -340,6 +340,15 @@ class Recognizer {
     r_ = pk_mi355_deltas_recognizer_load(model_file.c_str(), &spec, &deltas, precision, max_utts, max_total_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // A model of the transform's output dimension, the transform behind the normalisation and (deltas not null) the deltas
+  // (pk_mi355_transform_recognizer_load)
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t *deltas,
+              const pk_mi355_transform_spec_t &transform, int precision = PK_MI355_PRECISION_F32, int max_utts = 1,
+              int64_t max_total_samples = 16000 * 60, int64_t trace_capacity = 0) {
+    pk_mi355_recognizer_destroy(r_);
+    r_ = pk_mi355_transform_recognizer_load(model_file.c_str(), &spec, deltas, &transform, precision, max_utts, max_total_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   // pk_process for n waves at once; out (may be null) receives one Utterance per wave.  rates (may be null: 16000
   // throughout): the sample rate of every wave; the others are converted on the GPU (pk_mi355_recognizer_process_rates)
   Status Process(const pk_vector_t *waves, int n, std::vector<Utterance> *out, const int *rates = nullptr) {
@@ -552,6 +561,30 @@ struct DeltaSpec : pk_mi355_deltas_spec_t {
   }
 };
 
+// A feature transform (pk_mi355_transform_spec_t): Kaldi's splice-feats | transform-feats.  The
+// matrix [rows][cols], row-major, is copied; pass none (in_dim alone) for a scorer that takes per-utterance matrices
+// only.  Nothing is checked here: the library refuses a bad spec wherever one is used.
+struct TransformSpec : pk_mi355_transform_spec_t {
+  TransformSpec(const float *m, int rows_, int cols_, int in_dim_, int left = 0, int right = 0) : keep_(m, m + static_cast<size_t>(rows_) * cols_) {
+    left_context = left; right_context = right; in_dim = in_dim_; rows = rows_; cols = cols_; matrix = keep_.data();
+  }
+  explicit TransformSpec(int in_dim_) { left_context = right_context = 0; in_dim = in_dim_; rows = cols = 0; matrix = nullptr; }
+  TransformSpec(const TransformSpec &o) : pk_mi355_transform_spec_t(o), keep_(o.keep_) { matrix = o.matrix ? keep_.data() : nullptr; }
+  TransformSpec &operator=(const TransformSpec &) = delete;
+  Status Check() const { return Status::FromLast(pk_mi355_transform_check(this)); }
+  int out_dim() const { return pk_mi355_transform_out_dim(this); }      // negative: the spec is refused
+  // the rule on the host: x [T][in_dim] -> out [T][out_dim()]
+  Status Apply(const float *x, int num_frames, std::vector<float> *out) const {
+    const int d = out_dim();
+    if (d < 0) return Status::FromLast(d);
+    out->assign(static_cast<size_t>(num_frames > 0 ? num_frames : 0) * d, 0.0f);
+    return Status::FromLast(pk_mi355_transform_apply(this, x, num_frames, out->data()));
+  }
+
+ private:
+  std::vector<float> keep_;
+};
+
 // The batched, device-resident scorer (pk_mi355_batch_*): PCM of many utterances -> log-likelihood rows.
 class BatchScorer {
  public:
@@ -573,6 +606,14 @@ class BatchScorer {
       : b_(pk_mi355_deltas_batch_create(am, &deltas, &spec, global_stats, stats_len, max_utts, max_total_samples)) {
     if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // a transform in front of the splice, behind the deltas when `deltas` is not null (pk_mi355_transform_batch_create): a
+  // model of transform.out_dim() features; the front-end, the statistics (stats_len = spec.dim() + 1) and the
+  // normalisation at BaseDim() = spec.dim()
+  BatchScorer(pk_mi355_am_t *am, const FrontendSpec &spec, const DeltaSpec *deltas, const TransformSpec &transform, const float *global_stats,
+              int stats_len, int max_utts, int64_t max_total_samples)
+      : b_(pk_mi355_transform_batch_create(am, &transform, deltas, &spec, global_stats, stats_len, max_utts, max_total_samples)) {
+    if (!b_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   ~BatchScorer() { pk_mi355_batch_destroy(b_); }
   BatchScorer(const BatchScorer &) = delete;
   BatchScorer &operator=(const BatchScorer &) = delete;
@@ -587,6 +628,13 @@ class BatchScorer {
   int FeatDim() const { return pk_mi355_features_dim(b_); }
   // the dimension in front of the deltas (the front-end's, the statistics'); FeatDim() on a scorer without deltas
   int BaseDim() const { return pk_mi355_deltas_base_dim(b_); }
+  // the width of the rows the transform reads; FeatDim() on a scorer without one
+  int InDim() const { return pk_mi355_transform_in_dim(b_); }
+  // a scorer with a transform: [num_utts][FeatDim()][cols] floats, cols = FeatDim() or FeatDim() + 1 (the offset last),
+  // applied behind the global matrix and consumed by the next Score
+  Status SetUttTransforms(const float *mats, int cols, int num_utts) {
+    return Status::FromLast(pk_mi355_transform_set_utt(b_, mats, FeatDim(), cols, num_utts));
+  }
   // utterance utt's rows as a host decodable ({ncol = T, nrow = num_pdfs}; release with pk_decodable_destroy)
   Status Fetch(int utt, pk_decodable_t *out) { return Status::FromLast(pk_mi355_batch_fetch(b_, utt, out)); }
   // the front-end's rows, [T][BaseDim()] floats

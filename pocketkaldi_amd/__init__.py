@@ -30,7 +30,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "TransformSpec", "parse_transform", "transform_feats", "splice_feats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
@@ -92,6 +92,11 @@ class pk_mi355_online_cmvn_spec_t(C.Structure):  # an online CMVN specification 
 
 class pk_mi355_deltas_spec_t(C.Structure):       # a delta-features specification (include/pk_mi355.h)
     _fields_ = [("order", C.c_int32), ("window", C.c_int32)]
+
+
+class pk_mi355_transform_spec_t(C.Structure):    # a feature-transform specification (include/pk_mi355.h)
+    _fields_ = [("left_context", C.c_int32), ("right_context", C.c_int32), ("in_dim", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("matrix", C.POINTER(C.c_float))]
 
 
 EXPORTS = [
@@ -165,6 +170,8 @@ EXPORTS = [
     "pk_mi355_deltas_check", "pk_mi355_deltas_dim", "pk_mi355_deltas_scales", "pk_mi355_deltas_apply",
     "pk_mi355_deltas_batch_create", "pk_mi355_deltas_base_dim", "pk_mi355_deltas_recognizer_load",
     "pk_mi355_deltas_stream_create", "pk_mi355_stream_base_dim", "pk_mi355_deltas_online_recognizer_load",
+    "pk_mi355_transform_check", "pk_mi355_transform_out_dim", "pk_mi355_transform_apply", "pk_mi355_transform_batch_create",
+    "pk_mi355_transform_in_dim", "pk_mi355_transform_set_utt", "pk_mi355_transform_recognizer_load",
 ]
 
 
@@ -473,6 +480,16 @@ def lib():
     L.pk_mi355_stream_base_dim.argtypes = [C.c_void_p]
     L.pk_mi355_deltas_online_recognizer_load.restype = C.c_void_p
     L.pk_mi355_deltas_online_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, C.c_int, C.c_int64, C.c_int64]
+    xformp = C.POINTER(pk_mi355_transform_spec_t)
+    L.pk_mi355_transform_check.argtypes = [xformp]
+    L.pk_mi355_transform_out_dim.argtypes = [xformp]
+    L.pk_mi355_transform_apply.argtypes = [xformp, f32p, C.c_int, f32p]
+    L.pk_mi355_transform_batch_create.restype = C.c_void_p
+    L.pk_mi355_transform_batch_create.argtypes = [C.c_void_p, xformp, deltasp, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_transform_in_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_transform_set_utt.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int]
+    L.pk_mi355_transform_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_transform_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, xformp, C.c_int, C.c_int, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -932,6 +949,113 @@ def add_deltas(feats, spec):
     return y
 
 
+class TransformSpec:
+    """A feature-transform specification (pk_mi355_transform_spec_t): Kaldi's splice-feats with
+    left_context / right_context frames, then transform-feats with `matrix` [rows][cols] -- cols = (left + right + 1) *
+    in_dim (linear) or one more (affine: the last column is the offset).  in_dim is required when left_context =
+    right_context = 0 (a 41-column matrix may be 41 -> linear or 40 -> affine) and when matrix is None (no global stage:
+    the scorer then takes per-utterance matrices only); otherwise it is derived from cols.  The ranges and the matrix
+    entries are the library's to refuse (PkCodeError, the field named) wherever the spec is used."""
+
+    def __init__(self, matrix=None, left_context=0, right_context=0, in_dim=None):
+        self.matrix = None if matrix is None else _f32(matrix)
+        self.left_context, self.right_context = left_context, right_context
+        if self.matrix is not None and self.matrix.ndim != 2:
+            raise PkCodeError(-1, "transform spec: the matrix has shape %s, expected [rows][cols]" % (self.matrix.shape,))
+        if in_dim is None:
+            try:
+                w = int(left_context) + int(right_context) + 1
+            except (TypeError, ValueError) as e:
+                raise PkCodeError(-1, "transform spec: %s" % e)
+            if self.matrix is None:
+                raise PkCodeError(-1, "transform spec: in_dim is required without a matrix")
+            cols = self.matrix.shape[1]
+            if w <= 1:
+                raise PkCodeError(-1, "transform spec: in_dim is required when left_context = right_context = 0 (a %d-column matrix "
+                                  "may be %d -> linear or %d -> affine)" % (cols, cols, cols - 1))
+            # w > 1: at most one of cols and cols - 1 is a multiple of w; neither: the library names both numbers
+            in_dim = (cols - 1) // w if cols % w else cols // w
+        self.in_dim = in_dim
+
+    def struct(self):
+        try:
+            m = self.matrix
+            return pk_mi355_transform_spec_t(int(self.left_context), int(self.right_context), int(self.in_dim), 0 if m is None else m.shape[0],
+                                             0 if m is None else m.shape[1], None if m is None else _fp(m))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise PkCodeError(-1, "transform spec: %s" % e)
+
+    def check(self):
+        _check_code(lib().pk_mi355_transform_check(C.byref(self.struct())))
+
+    @property
+    def out_dim(self):
+        """The output dimension: the matrix's rows, or in_dim without a matrix."""
+        return _check_code(lib().pk_mi355_transform_out_dim(C.byref(self.struct())))
+
+    def __repr__(self):
+        return "TransformSpec(matrix=%s, left_context=%r, right_context=%r, in_dim=%r)" % (
+            None if self.matrix is None else "<%d x %d>" % self.matrix.shape, self.left_context, self.right_context, self.in_dim)
+
+
+def parse_transform(text):
+    """A TransformSpec from "matrix=final.mat,left_context=3,right_context=3[,in_dim=13]"; the matrix is read with
+    read_kaldi_matrix.  ValueError, the key named, for an unknown key, a key given twice, a context or in_dim that is not
+    an integer, or no matrix."""
+    given = {}
+    for item in [t.strip() for t in text.split(",") if t.strip()]:
+        key, eq, value = item.partition("=")
+        key, value = key.strip(), value.strip()
+        if key not in ("matrix", "left_context", "right_context", "in_dim"):
+            raise ValueError("transform spec: unknown key '%s' (the keys are matrix, left_context, right_context, in_dim)" % key)
+        if key in given:
+            raise ValueError("transform spec: key '%s' given twice" % key)
+        if key == "matrix":
+            if not eq or not value:
+                raise ValueError("transform spec: bad value '%s' for key 'matrix' (a file)" % value)
+            given[key] = value
+            continue
+        try:
+            given[key] = int(value) if eq else None
+        except ValueError:
+            given[key] = None
+        if given[key] is None:
+            raise ValueError("transform spec: bad value '%s' for key '%s' (an integer)" % (value, key))
+    if "matrix" not in given:
+        raise ValueError("transform spec: no matrix (matrix=FILE)")
+    given["matrix"] = read_kaldi_matrix(given["matrix"])
+    return TransformSpec(**given)
+
+
+def transform_feats(feats, spec):
+    """The rule of a TransformSpec on the host for one [T][in_dim] matrix (pk_mi355_transform_apply: the restatement the
+    GPU path is held to) -> float32 [T][out_dim]."""
+    x = _f32(feats)
+    st = spec.struct()
+    _check_code(lib().pk_mi355_transform_check(C.byref(st)))
+    if x.ndim != 2 or x.shape[1] != st.in_dim:
+        raise PkCodeError(-1, "features have shape %s, the transform reads [T][%d]" % (x.shape, st.in_dim))
+    T = x.shape[0]
+    y = np.zeros((T, spec.out_dim), np.float32)
+    _check_code(lib().pk_mi355_transform_apply(C.byref(st), _fp(x), T, _fp(y)))
+    return y
+
+
+def splice_feats(feats, left, right):
+    """Kaldi's splice-feats on the host: [T][D] -> [T][(left + right + 1) * D], frame t the frames t - left .. t + right with
+    the first and last frame repeated at the edges.  A copy; no arithmetic."""
+    x = _f32(feats)
+    if x.ndim != 2:
+        raise PkCodeError(-1, "features have shape %s, expected [T][D]" % (x.shape,))
+    if left < 0 or right < 0:
+        raise PkCodeError(-1, "splice: negative context (%d, %d)" % (left, right))
+    T = x.shape[0]
+    if T == 0:
+        return np.zeros((0, (left + right + 1) * x.shape[1]), np.float32)
+    idx = np.clip(np.arange(T)[:, None] + np.arange(-left, right + 1)[None, :], 0, T - 1)
+    return np.ascontiguousarray(x[idx].reshape(T, -1))
+
+
 class CMVN:
     """cmvn.h:17-26.  Sliding-window mean normalisation with a global prior."""
 
@@ -1216,14 +1340,23 @@ class Decodable:
 class BatchScorer:
     """Many utterances in flight: PCM -> fbank -> CMVN -> nnet -> log-likelihoods, all in HBM."""
 
-    def __init__(self, am, global_stats, max_utts, max_total_samples, frontend=None, deltas=None):
+    def __init__(self, am, global_stats, max_utts, max_total_samples, frontend=None, deltas=None, transform=None):
         """frontend: a FrontendSpec of the model's feature dimension (pk_mi355_frontend_batch_create; global_stats: that
         many sums, then the count).  Without it: the reference's 40-bin front-end and 41 statistics.
         deltas: a DeltaSpec (pk_mi355_deltas_batch_create): the front-end (the default FrontendSpec when none is given),
-        the statistics and the normalisation are then at base_dim() = feat_dim / (order + 1)."""
+        the statistics and the normalisation are then at base_dim() = feat_dim / (order + 1).
+        transform: a TransformSpec (pk_mi355_transform_batch_create) whose out_dim is the model's feat_dim: the front-end,
+        the statistics and the normalisation are then at base_dim() = in_dim() / (order + 1), in_dim() without deltas."""
         g = _f32(global_stats)
         self._am = am
         self._keep = None
+        if transform is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_transform_batch_create(am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()),
+                                                            C.byref(fe.struct()), _fp(g.ravel()), g.size, int(max_utts), int(max_total_samples))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
         if deltas is not None:
             fe = FrontendSpec() if frontend is None else frontend
             self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
@@ -1292,6 +1425,19 @@ class BatchScorer:
         """The dimension in front of the deltas -- the front-end's, raw rows', statistics' -- on a scorer made with
         deltas=; feat_dim() on every other."""
         return lib().pk_mi355_deltas_base_dim(self._h)
+
+    def in_dim(self):
+        """The width of the rows the transform reads on a scorer made with transform=; feat_dim() on every other."""
+        return lib().pk_mi355_transform_in_dim(self._h)
+
+    def set_utt_transforms(self, matrices):
+        """A scorer made with transform=: one [feat_dim][feat_dim] (linear) or [feat_dim][feat_dim + 1] (affine) matrix per
+        utterance of the next score call, which consumes them; applied behind the global matrix."""
+        n = len(matrices)
+        a = np.ascontiguousarray(np.stack([_f32(m) for m in matrices])) if n else np.zeros((0, self.feat_dim(), self.feat_dim()), np.float32)
+        if a.ndim != 3:
+            raise PkCodeError(-1, "per-utterance transforms have shape %s, expected [utterances][rows][cols]" % (a.shape,))
+        _check_code(lib().pk_mi355_transform_set_utt(self._h, _fp(a) if n else None, a.shape[1], a.shape[2], n))
 
     def set_features(self, feats, kind="normalized"):
         """Features instead of audio: one [T][feat_dim] matrix per utterance.  kind "normalized": ready for the splice
@@ -1420,11 +1566,20 @@ class FeatureScorer(BatchScorer):
     dimension), capacity in frames.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim model)
     enables kind "raw"."""
 
-    def __init__(self, am, max_utts, max_total_frames, global_stats=None, deltas=None):
+    def __init__(self, am, max_utts, max_total_frames, global_stats=None, deltas=None, transform=None):
         """deltas: a DeltaSpec (pk_mi355_deltas_batch_create without a front-end): kind "raw" then takes [T][base_dim()]
-        rows, and global_stats, when given, holds base_dim() sums and the count."""
+        rows, and global_stats, when given, holds base_dim() sums and the count.
+        transform: a TransformSpec (pk_mi355_transform_batch_create without a front-end), alone or behind deltas."""
         self._am = am
         self._keep = None
+        if transform is not None:
+            g = None if global_stats is None else _f32(global_stats)
+            self._h = lib().pk_mi355_transform_batch_create(am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()),
+                                                            None, None if g is None else _fp(g.ravel()), 0 if g is None else g.size, int(max_utts),
+                                                            int(max_total_frames))
+            if not self._h:
+                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            return
         if deltas is not None:
             g = None if global_stats is None else _f32(global_stats)
             self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
@@ -2132,11 +2287,20 @@ class Recognizer:
     scorer and a decoder with alignment on.  .am / .batch / .decoder / .symbols are the owned objects (beam, trace gc,
     softmax mode and calibration are set through them); process(waves) -> [Result]."""
 
-    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0, frontend=None, deltas=None):
+    def __init__(self, config, precision="f32", max_utts=8, max_total_samples=16000 * 60, trace_capacity=0, frontend=None, deltas=None,
+                 transform=None):
         """frontend: a FrontendSpec; the model file is then one of that feature dimension (pk_mi355_frontend_recognizer_load).
         deltas: a DeltaSpec; the model file is then one of (order + 1) x the front-end's dimension whose cmvn_stats are at
-        the front-end's (pk_mi355_deltas_recognizer_load; the default FrontendSpec when only deltas is given)."""
-        if deltas is not None:
+        the front-end's (pk_mi355_deltas_recognizer_load; the default FrontendSpec when only deltas is given).
+        transform: a TransformSpec, alone or behind deltas; the model file is then one of the transform's out_dim whose
+        cmvn_stats are at the front-end's dimension (pk_mi355_transform_recognizer_load)."""
+        if transform is not None:
+            fe = FrontendSpec() if frontend is None else frontend
+            self._h = lib().pk_mi355_transform_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()),
+                                                               None if deltas is None else C.byref(deltas.struct()), C.byref(transform.struct()),
+                                                               AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
+                                                               int(trace_capacity))
+        elif deltas is not None:
             fe = FrontendSpec() if frontend is None else frontend
             self._h = lib().pk_mi355_deltas_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()), C.byref(deltas.struct()),
                                                             AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
@@ -2191,14 +2355,23 @@ class Recognizer:
     def _speaker_stats(self, speaker_stats, n):
         return None if speaker_stats is None else _stats_records(speaker_stats, n, self.batch.base_dim())
 
-    def process_features(self, feats, kind="raw", speaker_stats=None):
+    def _utt_transforms(self, utt_transforms, n):
+        if utt_transforms is None:
+            return None
+        if len(utt_transforms) != n:
+            raise PkCodeError(-1, "%d per-utterance transforms for %d utterances" % (len(utt_transforms), n))
+        return list(utt_transforms)
+
+    def process_features(self, feats, kind="raw", speaker_stats=None, utt_transforms=None):
         """pk_process from features: one [T][feat_dim] matrix per utterance (kind: as BatchScorer.set_features).  A list
         that does not fit max_utts or the frames the recognizer holds is split into as many calls as it needs; a
         single matrix that cannot fit is refused.  speaker_stats: one record per utterance for a batch whose norm
-        (self.batch.set_norm) is in mode "speaker"; they are split with the list."""
+        (self.batch.set_norm) is in mode "speaker"; they are split with the list.  utt_transforms: one matrix per
+        utterance (BatchScorer.set_utt_transforms) on a recognizer made with transform=; split with the list too."""
         code = _feature_kind(kind)
         arr, keep = _feature_matrices(feats, self.batch.base_dim() if code == FEATURE_KINDS["raw"] else self.batch.feat_dim())
         spk = self._speaker_stats(speaker_stats, len(keep))
+        mats = self._utt_transforms(utt_transforms, len(keep))
         cap = self.max_total_samples // 160 + self.max_utts       # the frames pk_mi355_batch_create makes room for
         for i, f in enumerate(keep):
             if f.shape[0] > cap:
@@ -2210,6 +2383,8 @@ class Recognizer:
                     sub = (pk_matrix_t * (i - first))(*[arr[j] for j in range(first, i)])
                     if spk is not None:
                         self.batch.set_speaker_stats(spk[first:i])
+                    if mats is not None:
+                        self.batch.set_utt_transforms(mats[first:i])
                     _check_code(lib().pk_mi355_recognizer_process_features(self._h, sub, i - first, code))
                     out += self._results(i - first)
                 first, frames = i, 0
@@ -2217,13 +2392,14 @@ class Recognizer:
                 frames += keep[i].shape[0]
         return out
 
-    def process(self, waves, rates=None, speaker_stats=None):
+    def process(self, waves, rates=None, speaker_stats=None, utt_transforms=None):
         """pk_process for every wave (float sample values as read_wav gives them; rates: the sample rate of every wave,
         None for 16000 -- the others are converted on the GPU).  A list that does not fit max_utts / max_total_samples
         (counted at 16 kHz) is split into as many calls as it needs; a single wave that cannot fit is refused.
-        speaker_stats: as process_features."""
+        speaker_stats, utt_transforms: as process_features."""
         waves = [_f32(w).ravel() for w in waves]
         spk = self._speaker_stats(speaker_stats, len(waves))
+        mats = self._utt_transforms(utt_transforms, len(waves))
         if rates is None:
             sizes = [w.shape[0] for w in waves]
         else:
@@ -2238,6 +2414,8 @@ class Recognizer:
             first = len(out)
             if spk is not None:
                 self.batch.set_speaker_stats(spk[first:first + len(call)])
+            if mats is not None:
+                self.batch.set_utt_transforms(mats[first:first + len(call)])
             return self._process_call(call, None if rates is None else rates[first:first + len(call)])
         for w, n in zip(waves, sizes):
             if call and (len(call) == self.max_utts or samples + n > self.max_total_samples):

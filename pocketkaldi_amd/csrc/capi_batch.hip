@@ -15,6 +15,7 @@
 #include "pk_plan.h"
 #include "pk_resample.h"
 #include "pk_score.h"
+#include "pk_transform_kernel.h"
 
 using namespace pkmi;
 using namespace pkhost;
@@ -211,7 +212,17 @@ struct pk_mi355_batch {
   bool has_deltas = false;
   pk_mi355_deltas_spec_t deltas{0, 0};
   float *d_delta_scales = nullptr;  // the spec's scale table (pkdelta::BuildScales)
-  float *d_delta = nullptr;         // [max_frames][feat_dim]: DeltaKernel's result, which FeatureLayoutKernel reads
+  float *d_delta = nullptr;         // [max_frames][in_dim]: DeltaKernel's result, which the next stage reads
+  // The transform (pk_mi355_transform_batch_create): the last stages in front of the layout.
+  // in_dim is the width of the rows the global matrix reads (feat_dim on every other batch, and without a global matrix).
+  int in_dim = 0;
+  bool is_xform = false;            // made by pk_mi355_transform_batch_create
+  pkmi::TransformStage xform{};     // the global stage (mt null: none); mt is owned
+  float *d_xform = nullptr;         // [max_frames][feat_dim]: the global stage's result
+  float *d_umats = nullptr;         // [max_utts][feat_dim + 1][Ldo(feat_dim)]: the matrices handed over for the next score
+  float *d_uxform = nullptr;        // [max_frames][feat_dim]: the per-utterance stage's result
+  int umat_utts = -1;               // the utterances the pending matrices are for (-1: none pending)
+  bool umat_affine = false;
   _Float16 *d_y2 = nullptr;   // f16x3: interleaved (hi, lo) rows [ldy][2 feat_dim]
   float *h_ll = nullptr;    // page-locked mirror of d_ll (pk_mi355_batch_fetch_all), made on first use
   ArenaRec *arena = nullptr;  // its shared-ownership record
@@ -337,6 +348,9 @@ int CheckFeatureKind(const pk_mi355_batch *b, int kind) {
   // (statistics are only ever held at the model's own dimension: 41 floats through the 40-dim entries, feat_dim + 1
   // through pk_mi355_features_batch_create_stats)
   if (kind == PK_MI355_FEATS_RAW && !b->have_stats && b->norm.mode == PK_MI355_NORM_SLIDING) {
+    if (b->is_xform)
+      return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics: this batch of %d-dim base features was made without them "
+                  "(pk_mi355_transform_batch_create takes %d)", b->base_dim, b->base_dim + 1);
     if (b->has_deltas)
       return Fail(PK_MI355_E_INVALID, "raw features need the CMVN statistics: this batch of %d-dim base features was made without them "
                   "(pk_mi355_deltas_batch_create takes %d)", b->base_dim, b->base_dim + 1);
@@ -356,7 +370,8 @@ int CheckFeatureCounts(const pk_mi355_batch *b, const int *frames, int num_utts)
   return FramesFit(b, frames, num_utts);
 }
 pkplan::BatchShape ShapeOf(const pk_mi355_batch *b) {
-  return pkplan::BatchShape{b->base_dim, b->core.am->feat_dim, b->d_any != nullptr, b->has_deltas, b->have_stats};
+  return pkplan::BatchShape{b->base_dim, b->core.am->feat_dim, b->d_any != nullptr, b->has_deltas, b->have_stats, b->is_xform,
+                            b->xform.mt ? b->in_dim : 0};
 }
 // The own rows a plan reads or writes (pkplan::BatchPlan::buffers), made by the first call that needs them: create, for
 // what a set call could not make in time, then features_set* and norm_set*.  d_raw [max_frames][base_dim] has its lead
@@ -371,8 +386,13 @@ hipError_t EnsureBuffers(pk_mi355_batch *b, unsigned need) {
     if (e == hipSuccess && lead) e = hipMemset(b->d_raw_alloc, 0, sizeof(float) * floats);
     if (e == hipSuccess) b->d_raw = b->d_raw_alloc + lead;
   }
-  if (e == hipSuccess && (need & pkplan::kFeatRows) && !b->d_feats) e = hipMalloc(&b->d_feats, sizeof(float) * frames * D);
-  if (e == hipSuccess && (need & pkplan::kDeltaRows) && !b->d_delta) e = hipMalloc(&b->d_delta, sizeof(float) * frames * D);
+  // (d_feats holds the normalisation's rows at base_dim or the NORMALIZED staging at D; a transform object's base_dim
+  // may be the larger.  in_dim is D on every batch without a global matrix.)
+  if (e == hipSuccess && (need & pkplan::kFeatRows) && !b->d_feats)
+    e = hipMalloc(&b->d_feats, sizeof(float) * frames * std::max(D, (size_t)b->base_dim));
+  if (e == hipSuccess && (need & pkplan::kDeltaRows) && !b->d_delta) e = hipMalloc(&b->d_delta, sizeof(float) * frames * (size_t)b->in_dim);
+  if (e == hipSuccess && (need & pkplan::kXformRows) && !b->d_xform) e = hipMalloc(&b->d_xform, sizeof(float) * frames * D);
+  if (e == hipSuccess && (need & pkplan::kUttXformRows) && !b->d_uxform) e = hipMalloc(&b->d_uxform, sizeof(float) * frames * D);
   return e;
 }
 // what scoring `source` under `mode` needs of them
@@ -486,6 +506,7 @@ struct BatchSpec {
   const float *stats; int max_utts; int64_t max_samples, max_frames, chunk_cap;
   const FrontendAnyTables *any;             // the tables of a front-end spec of the base dimension, or null
   const pk_mi355_deltas_spec_t *deltas;     // or null
+  const pk_mi355_transform_spec_t *xform = nullptr;      // a checked transform spec: the base dimension is then in_dim / (order + 1)
 };
 // Every way to a batch.
 pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
@@ -498,7 +519,9 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   b->have_stats = spec.stats != nullptr;
   b->has_deltas = deltas != nullptr;
   if (deltas) b->deltas = *deltas;
-  b->base_dim = deltas ? am->feat_dim / (deltas->order + 1) : am->feat_dim;
+  b->is_xform = spec.xform != nullptr;
+  b->in_dim = spec.xform ? spec.xform->in_dim : am->feat_dim;
+  b->base_dim = deltas ? b->in_dim / (deltas->order + 1) : b->in_dim;
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
   CreateScorerCore(&c, am, spec.stats, b->base_dim, spec.max_utts, spec.max_frames, spec.max_frames, spec.chunk_cap, chk);
@@ -515,6 +538,15 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   chk(hipMalloc(&b->d_lay, lay_bytes));
   chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
   if (spec.any) UploadSpecTables(&c, spec.any, &b->d_any, chk);
+  if (spec.xform && pkxf::HasMatrix(*spec.xform)) {     // TransformKernel's global matrix, transposed and padded (before the plan below is asked for its rows)
+    const pk_mi355_transform_spec_t &x = *spec.xform;
+    std::vector<float> packed((size_t)x.cols * pkxf::Ldo(x.rows));
+    pkxf::PackTransposed(x.matrix, x.rows, x.cols, packed.data());
+    float *d_mt = nullptr;
+    chk(hipMalloc(&d_mt, sizeof(float) * packed.size()));
+    if (chk.ok) chk(hipMemcpy(d_mt, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    b->xform = pkmi::TransformStage{x.in_dim, x.left_context, x.right_context, x.rows, pkxf::Affine(x), d_mt, 0};
+  }
   // The rows of the SLIDING plan of an object with statistics; every other plan's are made by the set call that brings it
   // about.  A wave batch has no such call for its audio (everything now); a features-only one gets its raw rows.
   if (b->have_stats) chk(EnsureBuffers(b, b->features_only ? pkplan::kRawRows : BuffersFor(b, pkplan::kWaves, PK_MI355_NORM_SLIDING)));
@@ -544,6 +576,7 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
 struct BatchRequest {
   const float *stats; int stats_len; bool stats41; int max_utts; int64_t capacity; bool audio, null_arg;
   const pk_mi355_frontend_spec_t *frontend; const pk_mi355_deltas_spec_t *deltas;
+  const pk_mi355_transform_spec_t *xform = nullptr;      // pk_mi355_transform_batch_create's
 };
 // The argument checks of every public create entry, in the one order that names the fault each of them has always named,
 // also when several arguments are bad at once; an entry runs those its request gives rise to.
@@ -552,15 +585,31 @@ pk_mi355_batch *CheckedBatch(pk_mi355_am_t *am, const BatchRequest &r) {
   if (r.null_arg) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
   const int D = am->feat_dim, order = r.deltas ? r.deltas->order : 0;
   if (r.deltas && pkdelta::CheckSpec(r.deltas)) return nullptr;         // (names the field)
-  if (D % (order + 1) != 0) {
+  if (r.xform && pkxf::CheckSpec(r.xform)) return nullptr;              // (names the field)
+  // what the stages in front of the first layer start from: the model's features, or the rows a transform reads
+  const int Din = r.xform ? r.xform->in_dim : D;
+  if (r.xform && Din % (order + 1) != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the transform's in_dim %d", order, order + 1, Din);
+    return nullptr;
+  }
+  if (Din % (order + 1) != 0) {
     Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
     return nullptr;
   }
-  const int Db = D / (order + 1);
+  const int Db = Din / (order + 1);
   std::vector<FrontendAnyTables> any(r.frontend ? 1 : 0);
   if (r.frontend && BuildFrontendAnyTables(r.frontend, any.data())) return nullptr;      // (names the field)
-  if (r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return nullptr;
-  if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr)) return nullptr;
+  if (r.xform && r.audio && any[0].dim != Db) {
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the transform's in_dim %d with %d delta blocks needs %d", any[0].dim, Din,
+         order + 1, Db);
+    return nullptr;
+  }
+  if (!r.xform && r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return nullptr;
+  if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr || r.xform != nullptr)) return nullptr;
+  if (r.xform && pkxf::OutDim(*r.xform) != D) {
+    Fail(PK_MI355_E_INVALID, "the transform produces %d-dim features, the model expects %d", pkxf::OutDim(*r.xform), D);
+    return nullptr;
+  }
   // (pk_mi355_batch_create, the one audio entry without a spec, has always named its missing statistics here)
   if (r.max_utts <= 0 || r.capacity <= 0 || (r.audio && !r.frontend && !r.stats)) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
   if (r.stats && r.stats41 && D != kNumBins) {
@@ -572,7 +621,7 @@ pk_mi355_batch *CheckedBatch(pk_mi355_am_t *am, const BatchRequest &r) {
     return nullptr;
   }
   return CreateBatch(am, BatchSpec{r.stats, r.max_utts, r.audio ? r.capacity : 0, r.audio ? r.capacity / kFrameShift + r.max_utts : r.capacity,
-                                   PublicChunkCap(), r.frontend ? any.data() : nullptr, r.deltas});
+                                   PublicChunkCap(), r.frontend ? any.data() : nullptr, r.deltas, r.xform});
 }
 
 // am->mu held.  One of the model's own one-utterance scorers for a call of `need` samples or frames: kept while the call
@@ -623,6 +672,43 @@ pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355
 
 int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b) { return b ? b->base_dim : 0; }
 
+pk_mi355_batch_t *pk_mi355_transform_batch_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform, const pk_mi355_deltas_spec_t *deltas,
+                                                  const pk_mi355_frontend_spec_t *frontend, const float *global_stats, int stats_len, int max_utts,
+                                                  int64_t capacity) {
+  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !transform || (frontend && !global_stats),
+                                       frontend, deltas, transform});
+}
+
+int pk_mi355_transform_in_dim(const pk_mi355_batch_t *b) { return b ? b->in_dim : 0; }
+
+int pk_mi355_transform_set_utt(pk_mi355_batch_t *b, const float *mats, int rows, int cols, int num_utts) {
+  if (!b || (num_utts > 0 && !mats)) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (!b->is_xform) return Fail(PK_MI355_E_STATE, "per-utterance transforms need a batch made by pk_mi355_transform_batch_create");
+  if (num_utts < 0 || num_utts > b->max_utts) return Fail(PK_MI355_E_INVALID, "too many utterances (%d > %d)", num_utts, b->max_utts);
+  const int D = b->core.am->feat_dim;
+  if (rows != D) return Fail(PK_MI355_E_INVALID, "per-utterance transforms have %d rows, the model's features need %d", rows, D);
+  if (cols != D && cols != D + 1)
+    return Fail(PK_MI355_E_INVALID, "per-utterance transforms have %d columns, the model's %d-dim features need %d (linear) or %d (affine)", cols, D, D,
+                D + 1);
+  const size_t each = (size_t)rows * cols, packed_each = (size_t)cols * pkxf::Ldo(rows);
+  const int64_t bad = pkxf::FirstNonFinite(mats, (int64_t)(each * (size_t)num_utts));
+  if (bad >= 0)
+    return Fail(PK_MI355_E_INVALID, "the transform of utterance %d has an entry that is not finite (row %d, column %d)", (int)(bad / (int64_t)each),
+                (int)(bad % (int64_t)each / cols), (int)(bad % cols));
+  if (int rc = UseDevice(b->core.device)) return rc;
+  HIP_TRY(EnsureBuffers(b, pkplan::kUttXformRows));
+  if (!b->d_umats) HIP_TRY(hipMalloc(&b->d_umats, sizeof(float) * (size_t)(D + 1) * pkxf::Ldo(D) * (size_t)b->max_utts));
+  if (num_utts > 0) {                                   // (pageable memory: the copy has read the matrices when the call returns)
+    std::vector<float> packed(packed_each * (size_t)num_utts);
+    for (int u = 0; u < num_utts; ++u) pkxf::PackTransposed(mats + each * u, rows, cols, packed.data() + packed_each * u);
+    HIP_TRY(hipMemcpyAsync(b->d_umats, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice, b->core.stream));
+    HIP_TRY(hipStreamSynchronize(b->core.stream));
+  }
+  b->umat_utts = num_utts;
+  b->umat_affine = cols == D + 1;
+  return 0;
+}
+
 int pk_mi355_features_dim(const pk_mi355_batch_t *b) { return b ? b->core.am->feat_dim : 0; }
 
 void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
@@ -635,6 +721,7 @@ void pk_mi355_batch_destroy(pk_mi355_batch_t *b) {
   if (b->stream2) hipStreamDestroy(b->stream2);
   hipFree(b->d_wave); hipFree(b->d_wave_i16); hipFree(b->d_raw_alloc); hipFree(b->d_y2); hipFree(b->d_feats); hipFree(b->d_any);
   hipFree(b->d_delta); hipFree(b->d_delta_scales);
+  hipFree(const_cast<float *>(b->xform.mt)); hipFree(b->d_xform); hipFree(b->d_umats); hipFree(b->d_uxform);
   hipFree(b->d_norm_stats); hipFree(b->d_spk_table); hipFree(b->d_online_glob); hipFree(b->d_online_spk);
   b->resampler.Free();
   if (b->h_native) hipHostFree(b->h_native);
@@ -750,6 +837,9 @@ int pk_mi355_features_set(pk_mi355_batch_t *b, const pk_matrix_t *feats, int num
   const int D = kind == PK_MI355_FEATS_RAW ? b->base_dim : b->core.am->feat_dim;      // (a deltas batch: RAW rows are in front of the deltas)
   std::vector<int> frames(std::max(num_utts, 0));
   for (int u = 0; u < num_utts; ++u) {
+    if (feats[u].nrow != D && b->is_xform)
+      return Fail(PK_MI355_E_INVALID, "features of utterance %d have %d rows, this batch expects %d (%s)", u, feats[u].nrow, D,
+                  kind == PK_MI355_FEATS_RAW ? "raw rows in front of the transform" : "normalised rows at the model's dimension");
     if (feats[u].nrow != D && b->has_deltas)
       return Fail(PK_MI355_E_INVALID, "features of utterance %d have %d rows, this batch expects %d (%s)", u, feats[u].nrow, D,
                   kind == PK_MI355_FEATS_RAW ? "raw rows in front of the deltas" : "normalised rows at the model's dimension");
@@ -887,6 +977,8 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   const int spk_utts = b->spk_utts;
   b->spk_utts = -1;
   b->norm_stats_valid = false;
+  const int umat_utts = b->umat_utts;            // (the per-utterance transforms likewise)
+  b->umat_utts = -1;
   const int D = am->feat_dim;
   const int Db = b->base_dim;                    // the dimension in front of the deltas (D without them)
   const int mode = b->source == pkplan::kNormalized ? PK_MI355_NORM_NONE : b->norm.mode;
@@ -899,6 +991,8 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
       return Fail(PK_MI355_E_STATE, "mode speaker: statistics for %d utterances, the call has %d", spk_utts, b->num_utts);
     if (mode == pknorm::kNormOnlineCmvn && spk_utts >= 0 && spk_utts != b->num_utts)
       return Fail(PK_MI355_E_STATE, "online CMVN: speaker statistics for %d utterances, the call has %d", spk_utts, b->num_utts);
+    if (umat_utts >= 0 && umat_utts != b->num_utts)
+      return Fail(PK_MI355_E_STATE, "per-utterance transforms for %d utterances, the call has %d", umat_utts, b->num_utts);
   }
   if (b->num_utts == 0 || b->total_frames == 0) {
     if (mode == PK_MI355_NORM_UTTERANCE && b->num_utts > 0) {      // records of no frames: zeros
@@ -911,8 +1005,12 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
   const UttLayout &lay = b->lay;
   // The plan (pk_plan.h; DESIGN.md, "The two plans"): the front-end, then raw rows (fbank's, or the caller's) or
   // normalised features -> Yt.  What it reads and writes was made by create and the set calls (EnsureBuffers).
-  const pkplan::BatchPlan plan = pkplan::PlanBatch(ShapeOf(b), b->source, b->norm.mode, spk_utts >= 0);
-  auto own = [b](pkplan::Rows r) { return r == pkplan::kRawRows ? b->d_raw : r == pkplan::kFeatRows ? b->d_feats : b->d_delta; };
+  const pkplan::BatchPlan plan = pkplan::PlanBatch(ShapeOf(b), b->source, b->norm.mode, spk_utts >= 0, umat_utts >= 0);
+  HIP_TRY(EnsureBuffers(b, plan.buffers));        // (made by create and the set calls already: nothing happens here)
+  auto own = [b](pkplan::Rows r) {
+    return r == pkplan::kRawRows ? b->d_raw : r == pkplan::kFeatRows ? b->d_feats : r == pkplan::kDeltaRows ? b->d_delta
+         : r == pkplan::kXformRows ? b->d_xform : b->d_uxform;
+  };
   auto run = [&](int first, int last) {
     for (int k = first; k < last; ++k) {
       const pkplan::Step &st = plan.step[k];
@@ -930,6 +1028,11 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
           LaunchOnlineCmvn(in, lay, b->num_utts, st.dim, b->online_cmvn, b->d_online_glob, plan.speaker ? b->d_online_spk : nullptr, out, c.stream);
           break;
         case pkplan::kDelta: LaunchDelta(in, lay, b->num_utts, b->max_T, st.dim, b->deltas, b->d_delta_scales, out, c.stream); break;
+        case pkplan::kTransform: LaunchTransform(in, lay, b->num_utts, b->max_T, b->xform, out, c.stream); break;
+        case pkplan::kUttTransform:
+          LaunchTransform(in, lay, b->num_utts, b->max_T,
+                          TransformStage{D, 0, 0, D, b->umat_affine, b->d_umats, (int64_t)(D + (b->umat_affine ? 1 : 0)) * pkxf::Ldo(D)}, out, c.stream);
+          break;
         case pkplan::kFeatureLayout: LaunchFeatureLayout(in, lay, b->num_utts, b->max_T, st.dim, am->left, am->right, c.d_yt, c.ldy, c.stream); break;
       }
     }
@@ -1004,10 +1107,13 @@ int pkhost::BatchCalibrateLocked(pk_mi355_batch *b) {
   if (am->exps_stale) if (int rc = RefreshExps(am)) return rc;
   const ExecBufs &e = b->core.exec;
   const int spk_utts = b->spk_utts;              // calibration passes do not consume the speaker records: the score behind them does
+  const int umat_utts = b->umat_utts;            // (nor the per-utterance transforms)
   return CalibrateLoop(am, e, [&]() -> int {
     b->spk_utts = spk_utts;
+    b->umat_utts = umat_utts;
     const int rc = pk_mi355_batch_score(b, 1.0f, 0);
     b->spk_utts = spk_utts;
+    b->umat_utts = umat_utts;
     b->scored = false;                           // calibration passes are not results
     b->range_pending = false;
     if (rc) return rc;

@@ -76,7 +76,9 @@ int pk_mi355_load_stats(const char *config_path, int precision, pk_mi355_am_t **
 
 }  // extern "C"
 
-// blocks: 1, or the order + 1 blocks of a deltas spec -- the statistics are then at feat_dim / blocks
+// blocks: 1, or the order + 1 blocks of a deltas spec -- the statistics are then at feat_dim / blocks; 0: a transform
+// stands in front of the model, the statistics are at the transform's base dimension and
+// pk_mi355_transform_batch_create holds them to it
 int pkhost::LoadStatsBlocks(const char *config_path, int precision, int blocks, pk_mi355_am_t **am_out, float *stats, int stats_cap,
                             int *stats_len) {
   if (!config_path || !am_out || !stats || !stats_len) return Fail(PK_MI355_E_INVALID, "null argument");
@@ -90,6 +92,7 @@ int pkhost::LoadStatsBlocks(const char *config_path, int precision, int blocks, 
   // the statistics against the model's feature dimension -- the first layer's width over the spliced frames -- as soon as
   // the files are read (a width that is no multiple of the frames is the model's own refusal, at finalize)
   auto stats_fit = [&](int in_dim) {
+    if (blocks == 0) return 0;
     const int frames = conf.left + conf.right + 1, feat_dim = in_dim / frames, dim = feat_dim / blocks;
     if (in_dim % frames != 0 || (int)conf.stats.size() == dim + 1) return 0;
     if (blocks > 1 && feat_dim % blocks != 0) return 0;      // (pk_mi355_deltas_batch_create's refusal, which names both numbers)

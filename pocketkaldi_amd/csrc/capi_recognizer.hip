@@ -73,13 +73,19 @@ void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
 namespace {
 // spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
 // deltas (with a spec only): the model's features are (order + 1) x the spec's, the statistics at the spec's dimension
+// xform (with a spec only): the model's features are the transform's output, the statistics at the spec's dimension
 pk_mi355_recognizer_t *LoadRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision, int max_utts,
-                                      int64_t max_total_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr) {
+                                      int64_t max_total_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr,
+                                      const pk_mi355_transform_spec_t *xform = nullptr) {
   pk_mi355_recognizer *r = new pk_mi355_recognizer();
   auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (deltas) {
+  if (xform) {
+    int stats_len = 0;
+    if (LoadStatsBlocks(config_path, precision, 0, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->batch = pk_mi355_transform_batch_create(r->am, xform, deltas, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
+  } else if (deltas) {
     int stats_len = 0;
     if (LoadStatsBlocks(config_path, precision, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
     if (!(r->batch = pk_mi355_deltas_batch_create(r->am, deltas, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
@@ -121,6 +127,16 @@ pk_mi355_recognizer_t *pk_mi355_deltas_recognizer_load(const char *config_path, 
   if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
   if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
   return LoadRecognizer(config_path, frontend_spec, precision, max_utts, max_total_samples, trace_capacity, deltas_spec);
+}
+
+pk_mi355_recognizer_t *pk_mi355_transform_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                          const pk_mi355_deltas_spec_t *deltas_spec, const pk_mi355_transform_spec_t *transform_spec,
+                                                          int precision, int max_utts, int64_t max_total_samples, int64_t trace_capacity) {
+  if (!config_path || !frontend_spec || !transform_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(frontend_spec) || (deltas_spec && pk_mi355_deltas_check(deltas_spec)) || pk_mi355_transform_check(transform_spec))
+    return nullptr;                                       // (name the field)
+  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
+  return LoadRecognizer(config_path, frontend_spec, precision, max_utts, max_total_samples, trace_capacity, deltas_spec, transform_spec);
 }
 
 pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r) {

@@ -252,7 +252,8 @@ struct RecognizerFiles {
 // on failure the caller still frees *out.  any_stats: a cmvn_stats vector of any length up to kMaxCmvnStats (the spec'd loads)
 int LoadRecognizerFiles(const char *config_path, RecognizerFiles *out, bool any_stats = false);
 constexpr int kMaxCmvnStats = 129;   // the widest front-end spec (128 features) and the count
-// pk_mi355_load_stats with the statistics at feat_dim / blocks (capi_io.hip; blocks = 1: that entry)
+// pk_mi355_load_stats with the statistics at feat_dim / blocks (capi_io.hip; blocks = 1: that entry; blocks = 0: at any
+// length -- a transform stands in front of the model and pk_mi355_transform_batch_create holds them to its base dimension)
 int LoadStatsBlocks(const char *config_path, int precision, int blocks, pk_mi355_am_t **am_out, float *stats, int stats_cap, int *stats_len);
 void FreeRecognizerFiles(RecognizerFiles *f);
 // The words' strings joined by one space (pocketkaldi.cc:232-238); PK_MI355_E_INVALID for a word without a name.

@@ -3,7 +3,7 @@
 
 namespace pkplan {
 
-BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given) {
+BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given, bool utt_transforms) {
   BatchPlan p;
   auto add = [&p](Stage stage, Rows in, Rows out, int dim) {
     p.step[p.n++] = Step{stage, in, out, dim};
@@ -40,6 +40,14 @@ BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_g
   if (o.deltas) {
     add(kDelta, rows, kDeltaRows, o.Db);
     rows = kDeltaRows;
+  }
+  if (o.transform && o.Dp > 0) {                      // the global matrix: rows of Dp features -> rows of D
+    add(kTransform, rows, kXformRows, o.Dp);
+    rows = kXformRows;
+  }
+  if (o.transform && utt_transforms) {                // this call's own matrices, D -> D
+    add(kUttTransform, rows, kUttXformRows, o.D);
+    rows = kUttXformRows;
   }
   add(kFeatureLayout, rows, kYt, o.D);
   return p;

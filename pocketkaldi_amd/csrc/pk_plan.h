@@ -11,27 +11,32 @@ namespace pkplan {
 
 // ------------------------------------------------------------------ the batch scorer
 enum Source { kNoSource, kWaves, kRaw, kNormalized };      // what the last set call handed over
-enum Stage { kFbank, kFbankAny, kCmvn, kCmvnChain, kNorm, kOnlineCmvn, kDelta, kFeatureLayout };
-// Where a stage reads and writes.  The first three are the batch's own buffers (d_raw, d_feats, d_delta) and double as
-// the bits of BatchPlan::buffers; kCallerRows: the normalised features handed over, where they lie.
-enum Rows { kNoRows = 0, kRawRows = 1, kFeatRows = 2, kDeltaRows = 4, kCallerRows = 8, kYt = 16 };
-constexpr unsigned kOwnRows = kRawRows | kFeatRows | kDeltaRows;
+// (kTransform, kUttTransform: the two stages of a transform object)
+enum Stage { kFbank, kFbankAny, kCmvn, kCmvnChain, kNorm, kOnlineCmvn, kDelta, kFeatureLayout, kTransform, kUttTransform };
+// Where a stage reads and writes.  kRawRows, kFeatRows, kDeltaRows, kXformRows and kUttXformRows are the batch's own
+// buffers (d_raw, d_feats, d_delta, d_xform, d_uxform) and double as the bits of BatchPlan::buffers; kCallerRows: the
+// normalised features handed over, where they lie.
+enum Rows { kNoRows = 0, kRawRows = 1, kFeatRows = 2, kDeltaRows = 4, kCallerRows = 8, kYt = 16, kXformRows = 32, kUttXformRows = 64 };
+constexpr unsigned kOwnRows = kRawRows | kFeatRows | kDeltaRows | kXformRows | kUttXformRows;
 
-struct BatchShape { int Db, D; bool spec, deltas, stats; };   // base and model dimension; front-end spec, deltas, CMVN statistics
+// base and model dimension; front-end spec, deltas, CMVN statistics.  transform: an object made by
+// pk_mi355_transform_batch_create; Dp: the width of the rows its global matrix reads, 0 when it has none.
+struct BatchShape { int Db, D; bool spec, deltas, stats; bool transform = false; int Dp = 0; };
 struct Step { Stage stage; Rows in, out; int dim; };
 struct BatchPlan {
   int n = 0, front = 0;          // steps, and how many of them (0 or 1, the first) are the front-end
-  Step step[4];
+  Step step[6];
   bool speaker = false;          // kOnlineCmvn smooths with the speaker records handed over for this call
   bool writes_stats = false;     // kNorm in mode UTTERANCE leaves every utterance's record behind
   unsigned buffers = 0;          // the own rows the steps read or write
 };
 // SLIDING at 40 dimensions without deltas: CmvnKernel normalises and writes Yt itself, and reads around every utterance --
 // the one plan whose d_raw needs the lead and the slack.
-inline bool FusedCmvn(const BatchShape &o) { return o.stats && !o.deltas && o.Db == 40; }
+inline bool FusedCmvn(const BatchShape &o) { return o.stats && !o.deltas && !o.transform && o.Db == 40; }
 // mode: PK_MI355_NORM_* or pknorm::kNormOnlineCmvn.  Empty for what score refuses in front of the plan (nothing set;
-// SLIDING on raw rows or audio without statistics).
-BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given);
+// SLIDING on raw rows or audio without statistics).  utt_transforms: per-utterance matrices were handed over for this
+// call (a transform object only).
+BatchPlan PlanBatch(const BatchShape &o, Source source, int mode, bool speaker_given, bool utt_transforms = false);
 
 // ------------------------------------------------------------------ the online scorer
 enum StreamNormaliser { kNoNormaliser, kStreamNorm, kStreamCmvnChain };

@@ -61,6 +61,15 @@ dimension]), --frontend, --cmvn.  --features normalized --deltas takes matrices 
 [T][(order + 1) x the front-end's dimension], and no deltas are added.  With --online it is refused with the usage text:
 the live objects do not have deltas yet.
 
+--transform matrix=final.mat,left_context=3,right_context=3 takes a model that was trained on splice-feats |
+transform-feats features (LDA+MLLT; pk.TransformSpec): the matrix (a Kaldi matrix file) is applied
+behind the normalisation and the deltas, and the model file's cmvn_stats, --cmvn-stats and --cmvn-global are at the
+front-end's dimension.  --utt-transforms ark:trans.ark names a Kaldi archive of per-utterance matrices (fMLLR), applied
+behind the global one (or alone), keyed by utterance or, with --utt2spk FILE, by speaker; a missing key is refused with
+the usage text and named.  Both work with every batch form and with --frontend, --cmvn and --deltas; --features
+normalized matrices are past every stage and take neither.  With --online either is refused with the usage text: the
+live objects do not have transforms yet.
+
 --online feeds the waves as live audio through the OnlineRecognizer, --chunk-ms N (default 100) milliseconds per step
 (measured at the file's own rate),
 up to MAX_UTTS waves at a time, a slot each; what it prints on stdout is what it prints without the flag.  --partials
@@ -86,13 +95,17 @@ RESERVE = 32
 
 def usage():
     print("Usage: python -m pocketkaldi_amd.recognize <model-file> <input-file> [--ctm] [--reference-softmax] [--channel N] "
-          "[--frontend key=value,...] [--deltas order=N,window=N] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
+          "[--frontend key=value,...] [--deltas order=N,window=N] [--transform matrix=FILE,left_context=N,right_context=N] "
+          "[--utt-transforms RX [--utt2spk FILE]] [--cmvn mode=...,norm_means=...,norm_vars=... [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--cmvn mode=online,cmn_window=...,speaker_frames=...,global_frames=...,norm_vars=... [--cmvn-global RX] [--cmvn-stats RX [--utt2spk FILE]]] "
           "[--online [--chunk-ms N] [--partials] [--commit] [--endpoint-silence P,Q,... [--endpoint-rule M,T,C,L ...]]]")
     print("       python -m pocketkaldi_amd.recognize <model-file> <feats.npy | feats.npz | x.ark | x.scp | ark:... | scp:...> "
-          "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--deltas ...] [--online ...]")
+          "--features raw|normalized [--ctm] [--reference-softmax] [--cmvn ...] [--deltas ...] [--transform ...] [--utt-transforms ...] [--online ...]")
     print("  --deltas order=N,window=N: add-deltas behind the normalisation (not with --online); --features raw matrices are [T][front-end's "
           "dimension], --features normalized matrices [T][the model's dimension] and take no deltas.")
+    print("  --transform matrix=FILE,left_context=N,right_context=N[,in_dim=N]: splice-feats | transform-feats behind the normalisation and "
+          "the deltas (not with --online); --utt-transforms RX: a Kaldi archive of per-utterance matrices applied behind it, keyed by utterance, "
+          "or by speaker with --utt2spk.")
     print("  Input-file:")
     print("    *.wav: decode this file.")
     print("    *.scp: decode audios listed in it.")
@@ -193,15 +206,77 @@ def parse_norm_flags(argv):
     if speaker or stats_rx is not None:
         stats = pk.read_cmvn_stats_archive(stats_rx)
         if utt2spk_file is not None:
-            utt2spk = {}
-            with open(utt2spk_file) as f:
-                for n, line in enumerate(f):
-                    if line.strip():
-                        parts = line.split()
-                        if len(parts) != 2:
-                            raise UsageError("--utt2spk: line %d of %s is not '<utterance> <speaker>'" % (n + 1, utt2spk_file))
-                        utt2spk[parts[0]] = parts[1]
+            utt2spk = read_utt2spk(utt2spk_file)
     return Norm(spec, stats, utt2spk, global_stats)
+
+
+def read_utt2spk(utt2spk_file):
+    utt2spk = {}
+    with open(utt2spk_file) as f:
+        for n, line in enumerate(f):
+            if line.strip():
+                parts = line.split()
+                if len(parts) != 2:
+                    raise UsageError("--utt2spk: line %d of %s is not '<utterance> <speaker>'" % (n + 1, utt2spk_file))
+                utt2spk[parts[0]] = parts[1]
+    return utt2spk
+
+
+class Transforms:
+    """--transform and --utt-transforms: the spec, and the per-utterance matrices by key with the utterance-to-speaker map."""
+
+    def __init__(self, spec, mats=None, utt2spk=None):
+        self.spec, self.mats, self.utt2spk = spec, mats, utt2spk
+
+    def utt_transforms(self, names):
+        """The matrices of these utterances, or None without --utt-transforms.  UsageError names a missing key."""
+        if self.mats is None:
+            return None
+        out = []
+        for name in names:
+            key = name
+            if self.utt2spk is not None:
+                if name not in self.utt2spk:
+                    raise UsageError("--utt2spk: no speaker for utterance '%s'" % name)
+                key = self.utt2spk[name]
+            if key not in self.mats:
+                raise UsageError("--utt-transforms: no transform for %s '%s'" % ("speaker" if self.utt2spk is not None else "utterance", key))
+            out.append(self.mats[key])
+        return out
+
+
+def parse_transform_flags(argv):
+    """--transform and --utt-transforms out of argv (and --utt2spk, unless --cmvn-stats shares it) -> a Transforms, or None
+    without either.  UsageError says what is wrong."""
+    text, rx = take_value(argv, "--transform"), take_value(argv, "--utt-transforms")
+    if text is None and rx is None:
+        return None
+    if "--online" in argv:
+        raise UsageError("the live objects do not have transforms yet: leave out --online")
+    spec = mats = utt2spk = None
+    if text is not None:
+        try:
+            spec = pk.parse_transform(text)
+            spec.check()
+        except (ValueError, pk.PkError, OSError) as e:
+            raise UsageError("--transform: %s" % e)
+    if rx is not None:
+        try:
+            mats = dict(pk.ArkReader(rx))
+        except (pk.PkError, OSError) as e:
+            raise UsageError("--utt-transforms: %s" % e)
+        if not mats:
+            raise UsageError("--utt-transforms: %s holds no matrix" % rx)
+        if "--utt2spk" in argv:
+            at = argv.index("--utt2spk")
+            if at + 1 >= len(argv):
+                raise UsageError("--utt2spk needs a value")
+            utt2spk = read_utt2spk(argv[at + 1])
+            if "--cmvn-stats" not in argv:               # (else the statistics are keyed by speaker too: --cmvn's parser takes the flag)
+                del argv[at:at + 2]
+        if spec is None:                                 # per-utterance matrices alone: no global stage, at the matrices' own dimension
+            spec = pk.TransformSpec(None, in_dim=int(next(iter(mats.values())).shape[0]))
+    return Transforms(spec, mats, utt2spk)
 
 
 def recognize_online(model_file, files, waves, chunk_ms, reference_softmax, partials, commit=False, rates=None, endpoint=None,
@@ -322,6 +397,11 @@ def main(argv):
         print("pocketkaldi: --deltas: %s" % e)
         return usage()
     try:
+        xform = parse_transform_flags(argv)
+    except UsageError as e:
+        print("pocketkaldi: %s" % e)
+        return usage()
+    try:
         norm = parse_norm_flags(argv)
     except UsageError as e:
         print("pocketkaldi: %s" % e)
@@ -355,7 +435,7 @@ def main(argv):
         return usage()
     try:
         if features:
-            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend, norm, deltas)
+            return recognize_features(model_file, input_file, features, flags, chunk_ms, endpoint, frontend, norm, deltas, xform)
         if input_file.endswith(".wav"):
             files = [input_file]
         else:
@@ -373,13 +453,15 @@ def main(argv):
         else:
             sizes = [pk.resample_num_output(r, len(w)) for w, r in zip(waves, rates)]       # capacity counts 16 kHz samples
             rec = pk.Recognizer(model_file, max_utts=min(max(len(waves), 1), MAX_UTTS),
-                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend, deltas=deltas)
+                                max_total_samples=max(max(sizes + [1]), min(sum(sizes), MAX_SAMPLES)), frontend=frontend, deltas=deltas,
+                                transform=xform.spec if xform else None)
             if "--reference-softmax" in flags:
                 rec.am.set_softmax("reference")
             if norm:
                 norm.apply(rec)
             native = any(r != 16000 for r in rates)
-            results, names = rec.process(waves, rates if native else None, norm.speaker_stats(files) if norm else None), rec.symbols
+            results, names = rec.process(waves, rates if native else None, norm.speaker_stats(files) if norm else None,
+                                         xform.utt_transforms(files) if xform else None), rec.symbols
     except UsageError as e:
         print("pocketkaldi: %s" % e)
         return usage()
@@ -440,7 +522,7 @@ def feature_groups(input_file):
             yield group
 
 
-def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None, norm=None, deltas=None):
+def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, frontend=None, norm=None, deltas=None, xform=None):
     """--features: every group of utterances through a Recognizer (process_features) or, with --online, through the
     slots of an OnlineRecognizer; the object is kept from group to group while the group fits it.  Raises what main
     reports; -> the exit code."""
@@ -465,7 +547,8 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
                     if norm:
                         norm.apply_online(rec)
                 else:
-                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend, deltas=deltas)
+                    rec = pk.Recognizer(model_file, max_utts=need[0], max_total_samples=160 * need[1], frontend=frontend, deltas=deltas,
+                                        transform=xform.spec if xform else None)
                     if "--reference-softmax" in flags:
                         rec.am.set_softmax("reference")
                     if norm:
@@ -477,7 +560,8 @@ def recognize_features(model_file, input_file, kind, flags, chunk_ms, endpoint, 
                                               "--commit" in flags, None, pieces, feature_kind=kind, norm=norm)
             else:
                 spk = norm.speaker_stats(files) if norm and kind == "raw" else None
-                results, names = rec.process_features(feats, kind, spk), rec.symbols
+                mats = xform.utt_transforms(files) if xform and kind == "raw" else None
+                results, names = rec.process_features(feats, kind, spk, mats), rec.symbols
             emit(files, results, names, "--ctm" in flags, pieces)
     finally:
         if rec is not None:
