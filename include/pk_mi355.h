@@ -576,7 +576,7 @@ int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b);
  * layer of a batch scorer, behind the normalisation and the deltas.  Restated from the tools' description (splice-feats
  * repeats the first and last frame; transform-feats does AddMatMat, then adds the offset column with AddVecToRows --
  * hence "offset last"); it has not been compared with a Kaldi binary, and Kaldi leaves the product's order to BLAS, so
- * agreement with Kaldi is within rounding.  The online objects take no transform yet.                               */
+ * agreement with Kaldi is within rounding.  The online objects: pk_mi355_transform_stream_create below.              */
 typedef struct pk_mi355_transform_spec {
   int32_t left_context, right_context;   /* frames spliced to the left and right: each 0 .. 16, together at most 16 */
   int32_t in_dim;                        /* Dp, the width of the rows the stage reads: 1 .. 512 */
@@ -999,6 +999,47 @@ pk_mi355_stream_t *pk_mi355_deltas_stream_create(pk_mi355_am_t *am, const pk_mi3
                                                  int stats_len, int max_streams, int64_t capacity);
 /* Db of a stream made by the entry above; feat_dim on every other stream; PK_MI355_E_INVALID for NULL.              */
 int pk_mi355_stream_base_dim(const pk_mi355_stream_t *s);
+/* An online scorer with the transform in front of the splice: pk_mi355_transform_batch_create's
+ * arguments, checks (in its order, with its texts, through the same code) and meaning of Db, deltas (may be NULL),
+ * frontend (NULL: features only, capacity in frames pushed between two steps; else capacity in 16 kHz samples and
+ * global_stats required), global_stats and stats_len.  An f16 model is refused besides, as on every stream entry; the
+ * null arguments and the two specs are checked before the model is looked at.  Everything in front of the transform
+ * works at Db, as on a transform batch: the front-end, the statistics, every normalisation the online scorer accepts,
+ * their records, pk_mi355_stream_norm_fetch_stats and PK_MI355_FEATS_RAW slots, whose pushes are [n][Db].
+ * PK_MI355_FEATS_NORMALIZED slots stay [n][feat_dim] and pass no stage.  The matrix is copied.
+ *
+ * The rule for a live slot.  Lt, Rt the spec's contexts, C = Lt + Rt; R the model's right context; M = order * window
+ * with deltas, 0 without.  Per slot: nin, the transform's input frames final so far (the normalised base frames n
+ * without deltas, the nd' of the deltas rule above with them); nx, transform frames final so far; a, rows scored so far.
+ * One step:
+ *   - transform frames [nx, nx') become final, nx' = closed ? nin : max(nx, nin - Rt);
+ *   - transform frame t is the apply rule of pk_mi355_transform_spec_t over the input frames clamp(t + j, 0, nin - 1),
+ *     j = -Lt .. Rt (while the slot is open t + Rt <= nin - 1, so the upper clamp binds only after close; the lower
+ *     clamp is frame 0 of this opening);
+ *   - the slot's own matrix (pk_mi355_stream_transform_set_slot), if it has one, is applied to the newly final frames
+ *     [nx, nx') with L = R = 0; a slot without one passes its rows on as bits (a copy, not an identity product: -0.0,
+ *     NaN payloads and inf survive, as on a batch call without matrices);
+ *   - rows [a, b) are scored, b = closed ? nx' : max(a, nx' - R), spliced over transform frames as on every stream.
+ * The look-ahead of a live slot is therefore M + Rt + R frames; a slot closed with n = 0 gives nothing, one closed with
+ * n <= M + Rt + R gives all its rows at the flush, one closed a step after its last push flushes from its history alone.
+ * Over a slot's life the rows are those of a batch made by pk_mi355_transform_batch_create on the whole input under the
+ * same normalisation, deltas and matrices, bit for bit, at every chunking and in both softmax modes.
+ * Memory beyond a stream without a transform: 8 * max(C, 1) * in_dim bytes of ring per slot, a staging of
+ * (max_frames + max_streams * (M + Rt)) * feat_dim floats (a second one, as large, from the first
+ * pk_mi355_stream_transform_set_slot on, with (feat_dim + 1) * RoundUp(feat_dim, 64) floats of matrix per slot), the
+ * matrix, Rt more rows per slot in the layer buffers, and two more record arrays of 96 * max_streams bytes.  A step that
+ * cannot fit fails with PK_MI355_E_INVALID and consumes nothing.                                                     */
+pk_mi355_stream_t *pk_mi355_transform_stream_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform,
+                                                    const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
+                                                    const float *global_stats, int stats_len, int max_streams, int64_t capacity);
+/* in_dim of a stream made by the entry above; feat_dim on every other stream; PK_MI355_E_INVALID for NULL.          */
+int pk_mi355_stream_in_dim(const pk_mi355_stream_t *s);
+/* The slot's own matrix (fMLLR for the speaker on that slot): row-major [rows][cols], rows = feat_dim, cols = feat_dim
+ * (linear) or feat_dim + 1 (affine), every entry finite, else PK_MI355_E_INVALID (naming row and column); feat_dim
+ * above 1024 is PK_MI355_E_INVALID too.  For an open audio or RAW slot before its first transform frame is computed;
+ * otherwise, on a NORMALIZED slot, or on a stream of another entry: PK_MI355_E_STATE.  The matrix is copied and lasts
+ * until the slot is opened again.  Optional: a slot without one skips the stage.                                     */
+int pk_mi355_stream_transform_set_slot(pk_mi355_stream_t *s, int slot, const float *matrix, int rows, int cols);
 
 /* ---- The normalisation of an online scorer of any kind (pk_mi355_stream_create, pk_mi355_features_stream_create*,
  * pk_mi355_frontend_stream_create): every row a slot's life produces is the row the batch scorer produces under the
@@ -1313,6 +1354,18 @@ pk_mi355_online_recognizer_t *pk_mi355_deltas_online_recognizer_load(const char 
                                                                      const pk_mi355_frontend_spec_t *frontend_spec,
                                                                      const pk_mi355_deltas_spec_t *deltas_spec, int max_streams,
                                                                      int64_t max_step_samples, int64_t trace_capacity);
+/* The same with a transform, behind deltas when deltas_spec is not NULL, for a model whose
+ * features are the transform's output and whose cmvn_stats hold the front-end's dimension + 1 entries:
+ * pk_mi355_transform_stream_create in place of pk_mi355_frontend_stream_create, whose refusals are this entry's; bad
+ * specs are refused first.  A slot's own matrix: pk_mi355_stream_transform_set_slot on
+ * pk_mi355_online_recognizer_stream once the slot is open.  With endpointing a matrix belongs to the opening: every
+ * utterance cut from that opening uses it.  push_features of a RAW slot takes [n][Db].                             */
+pk_mi355_online_recognizer_t *pk_mi355_transform_online_recognizer_load(const char *config_path,
+                                                                        const pk_mi355_frontend_spec_t *frontend_spec,
+                                                                        const pk_mi355_deltas_spec_t *deltas_spec,
+                                                                        const pk_mi355_transform_spec_t *transform_spec,
+                                                                        int max_streams, int64_t max_step_samples,
+                                                                        int64_t trace_capacity);
 void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r);
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r);
 pk_mi355_stream_t *pk_mi355_online_recognizer_stream(pk_mi355_online_recognizer_t *r);

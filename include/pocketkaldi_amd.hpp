@@ -427,6 +427,22 @@ class OnlineScorer {
       : s_(pk_mi355_deltas_stream_create(am, &deltas, nullptr, global_stats, stats_len, max_streams, max_step_frames)) {
     if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
+  // A transform in front of the splice, behind the deltas when `deltas` is not null (a pk_mi355_transform_spec_t;
+  // pk_mi355_transform_stream_create): a model of the transform's output dimension; the front-end, the
+  // statistics (stats_len = BaseDim() + 1), the normalisation and RAW slots are at BaseDim() = InDim() / (order + 1).  A live
+  // slot looks order * window + right_context + R frames ahead.
+  OnlineScorer(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t *deltas,
+               const pk_mi355_transform_spec_t &transform, const float *global_stats, int stats_len, int max_streams, int64_t max_step_samples)
+      : s_(pk_mi355_transform_stream_create(am, &transform, deltas, &spec, global_stats, stats_len, max_streams, max_step_samples)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // The same without a front-end: feature slots only, capacity in frames; global_stats (BaseDim() sums, then the count) may
+  // be null.
+  OnlineScorer(FeaturesOnlyTag, pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_transform_spec_t &transform,
+               const float *global_stats, int stats_len, int max_streams, int64_t max_step_frames)
+      : s_(pk_mi355_transform_stream_create(am, &transform, deltas, nullptr, global_stats, stats_len, max_streams, max_step_frames)) {
+    if (!s_) status_ = Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
   ~OnlineScorer() { pk_mi355_stream_destroy(s_); }
   OnlineScorer(const OnlineScorer &) = delete;
   OnlineScorer &operator=(const OnlineScorer &) = delete;
@@ -451,6 +467,13 @@ class OnlineScorer {
   int FeatDim() const { return pk_mi355_stream_feat_dim(s_); }
   // the dimension in front of the deltas (the front-end's, the statistics', a RAW slot's frames); FeatDim() on a scorer without deltas
   int BaseDim() const { return pk_mi355_stream_base_dim(s_); }
+  // the width of the rows the transform reads; FeatDim() on a scorer without a transform
+  int InDim() const { return pk_mi355_stream_in_dim(s_); }
+  // A scorer with a transform: the open slot's own [FeatDim()][cols] matrix, cols = FeatDim() (linear) or FeatDim() + 1
+  // (affine), before its first transform frame is computed; it lasts until the slot is opened again.
+  Status SetSlotTransform(int slot, const float *matrix, int cols) {
+    return Status::FromLast(pk_mi355_stream_transform_set_slot(s_, slot, matrix, pk_mi355_stream_feat_dim(s_), cols));
+  }
   // -1: audio, else the PK_MI355_FEATS_* kind the slot was last opened with
   int SlotKind(int slot) const { return pk_mi355_stream_slot_kind(s_, slot); }
   // The normalisation of the audio and RAW slots, while no slot is in use: a NormSpec of mode sliding,
@@ -827,6 +850,15 @@ class OnlineRecognizer {
               int64_t max_step_samples = 16000 * 8, int64_t trace_capacity = 0) {
     pk_mi355_online_recognizer_destroy(r_);
     r_ = pk_mi355_deltas_online_recognizer_load(model_file.c_str(), &spec, &deltas, max_streams, max_step_samples, trace_capacity);
+    return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
+  }
+  // A model of the transform's output dimension, the transform behind the normalisation and (deltas not null) the deltas
+  // (pk_mi355_transform_online_recognizer_load).  A slot's own matrix:
+  // pk_mi355_stream_transform_set_slot on stream() once the slot is open.
+  Status Load(const std::string &model_file, const pk_mi355_frontend_spec_t &spec, const pk_mi355_deltas_spec_t *deltas,
+              const pk_mi355_transform_spec_t &transform, int max_streams = 1, int64_t max_step_samples = 16000 * 8, int64_t trace_capacity = 0) {
+    pk_mi355_online_recognizer_destroy(r_);
+    r_ = pk_mi355_transform_online_recognizer_load(model_file.c_str(), &spec, deltas, &transform, max_streams, max_step_samples, trace_capacity);
     return r_ ? Status() : Status(pk_mi355_last_error_code(), pk_mi355_last_error());
   }
   Status Open(int slot) { return Status::FromLast(pk_mi355_online_recognizer_open(r_, slot)); }

@@ -172,6 +172,8 @@ EXPORTS = [
     "pk_mi355_deltas_stream_create", "pk_mi355_stream_base_dim", "pk_mi355_deltas_online_recognizer_load",
     "pk_mi355_transform_check", "pk_mi355_transform_out_dim", "pk_mi355_transform_apply", "pk_mi355_transform_batch_create",
     "pk_mi355_transform_in_dim", "pk_mi355_transform_set_utt", "pk_mi355_transform_recognizer_load",
+    "pk_mi355_transform_stream_create", "pk_mi355_stream_in_dim", "pk_mi355_stream_transform_set_slot",
+    "pk_mi355_transform_online_recognizer_load",
 ]
 
 
@@ -490,6 +492,12 @@ def lib():
     L.pk_mi355_transform_set_utt.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int]
     L.pk_mi355_transform_recognizer_load.restype = C.c_void_p
     L.pk_mi355_transform_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, xformp, C.c_int, C.c_int, C.c_int64, C.c_int64]
+    L.pk_mi355_transform_stream_create.restype = C.c_void_p
+    L.pk_mi355_transform_stream_create.argtypes = [C.c_void_p, xformp, deltasp, specp, f32p, C.c_int, C.c_int, C.c_int64]
+    L.pk_mi355_stream_in_dim.argtypes = [C.c_void_p]
+    L.pk_mi355_stream_transform_set_slot.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int]
+    L.pk_mi355_transform_online_recognizer_load.restype = C.c_void_p
+    L.pk_mi355_transform_online_recognizer_load.argtypes = [C.c_char_p, specp, deltasp, xformp, C.c_int, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -1633,6 +1641,48 @@ class OnlineScorer:
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
 
+    @classmethod
+    def with_transform(cls, am, global_stats, max_streams, max_step_samples, transform, frontend=None, deltas=None):
+        """A scorer with a TransformSpec in front of the splice (pk_mi355_transform_stream_create), behind deltas when a
+        DeltaSpec is given: the front-end (the default FrontendSpec when none is given), the statistics, the normalisation
+        and "raw" slots are then at base_dim() = in_dim() / (order + 1), and a live slot looks order * window +
+        right_context + R frames ahead.  set_slot_transform hands an open slot its own matrix."""
+        if not isinstance(transform, TransformSpec):
+            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
+        if deltas is not None and not isinstance(deltas, DeltaSpec):
+            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
+        if frontend is not None and not isinstance(frontend, FrontendSpec):
+            raise TypeError("frontend must be a FrontendSpec, not %s" % type(frontend).__name__)
+        g = _f32(global_stats)
+        fe = FrontendSpec() if frontend is None else frontend
+        return cls._made_with_transform(am, max_streams, lib().pk_mi355_transform_stream_create(
+            am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
+            int(max_streams), int(max_step_samples)))
+
+    @classmethod
+    def _made_with_transform(cls, am, max_streams, handle):
+        if not handle:
+            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self = cls.__new__(cls)
+        self._am = am
+        self._max_streams = int(max_streams)
+        self._has_deltas = True             # "raw" slots are base_dim() wide, as behind deltas
+        self._h = handle
+        return self
+
+    def in_dim(self):
+        """The width of the rows the transform reads on a scorer made by with_transform; feat_dim() on every other."""
+        return _check_code(lib().pk_mi355_stream_in_dim(self._h))
+
+    def set_slot_transform(self, slot, matrix):
+        """A scorer made by with_transform: the open slot's own [feat_dim][feat_dim] (linear) or [feat_dim][feat_dim + 1]
+        (affine) matrix, before its first transform frame is computed; applied behind the global matrix until the slot is
+        opened again.  A slot without one passes its rows on as they are."""
+        m = _f32(matrix)
+        if m.ndim != 2:
+            raise PkCodeError(-1, "a slot's transform has shape %s, expected [rows][cols]" % (m.shape,))
+        _check_code(lib().pk_mi355_stream_transform_set_slot(self._h, int(slot), _fp(m), m.shape[0], m.shape[1]))
+
     def destroy(self):
         if getattr(self, "_h", None):
             lib().pk_mi355_stream_destroy(self._h)
@@ -1778,6 +1828,19 @@ class OnlineFeatureScorer(OnlineScorer):
             self._h = lib().pk_mi355_features_stream_create(am.handle, None if g is None else _fp(g), int(max_streams), int(max_step_frames))
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+
+    @classmethod
+    def with_transform(cls, am, max_streams, max_step_frames, transform, global_stats=None, deltas=None):
+        """OnlineScorer.with_transform without a front-end: "raw" slots take [n][base_dim()] frames, and global_stats, when
+        given, holds base_dim() sums and the count."""
+        if not isinstance(transform, TransformSpec):
+            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
+        if deltas is not None and not isinstance(deltas, DeltaSpec):
+            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
+        g = None if global_stats is None else _f32(global_stats)
+        return cls._made_with_transform(am, max_streams, lib().pk_mi355_transform_stream_create(
+            am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
+            0 if g is None else g.size, int(max_streams), int(max_step_frames)))
 
 
 class PkCodeError(PkError):
@@ -2451,13 +2514,37 @@ class OnlineRecognizer:
         else:
             self._h = lib().pk_mi355_online_recognizer_load(os.fspath(config).encode(), int(max_streams), int(max_step_samples),
                                                             int(trace_capacity))
+        self._adopt(max_streams, max_step_samples, deltas is not None)
+
+    @classmethod
+    def with_transform(cls, config, transform, max_streams=8, max_step_samples=16000 * 8, trace_capacity=0, frontend=None, deltas=None):
+        """A recognizer whose scorer is OnlineScorer.with_transform's (pk_mi355_transform_online_recognizer_load): the model
+        file is one of the transform's output dimension whose cmvn_stats are at the front-end's (the default FrontendSpec
+        when none is given).  A slot's own matrix: self.scorer.set_slot_transform(slot, matrix) once the slot is open; with
+        endpointing every utterance cut from that opening uses it."""
+        if not isinstance(transform, TransformSpec):
+            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
+        if deltas is not None and not isinstance(deltas, DeltaSpec):
+            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
+        if frontend is not None and not isinstance(frontend, FrontendSpec):
+            raise TypeError("frontend must be a FrontendSpec, not %s" % type(frontend).__name__)
+        fe = FrontendSpec() if frontend is None else frontend
+        self = cls.__new__(cls)
+        self._h = lib().pk_mi355_transform_online_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()),
+                                                                  None if deltas is None else C.byref(deltas.struct()), C.byref(transform.struct()),
+                                                                  int(max_streams), int(max_step_samples), int(trace_capacity))
+        self._adopt(max_streams, max_step_samples, True)
+        return self
+
+    def _adopt(self, max_streams, max_step_samples, base_dim_slots):
+        """The owned objects of a loaded recognizer.  base_dim_slots: "raw" slots are the scorer's base_dim() wide."""
         if not self._h:
             raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self.max_streams, self.max_step_samples = int(max_streams), int(max_step_samples)
         L = lib()
         self.am = _Borrowed.of(AcousticModel, L.pk_mi355_online_recognizer_am(self._h), self)
         self.scorer = _Borrowed.of(OnlineScorer, L.pk_mi355_online_recognizer_stream(self._h), self, free="destroy", _am=self.am,
-                                   _max_streams=int(max_streams), _has_deltas=deltas is not None)
+                                   _max_streams=int(max_streams), _has_deltas=bool(base_dim_slots))
         self.decoder = _Borrowed.of(OnlineDecoder, L.pk_mi355_online_recognizer_decoder(self._h), self, free="destroy",
                                     _am=self.am, _fst=None)
         self.symbols = SymbolTable._borrowed(L.pk_mi355_online_recognizer_symtab(self._h), self)

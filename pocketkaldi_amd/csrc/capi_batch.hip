@@ -570,56 +570,11 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   return b;
 }
 
-// What a public create entry was handed.  stats41: 41 statistics by the entry's contract (a 40-dim model's; no
-// stats_len).  audio: the capacity is in samples and there is a front-end -- the spec's, or without one the reference's
-// 40 bins; else it is in frames.  null_arg: the entry found one of the pointers it needs null.
-struct BatchRequest {
-  const float *stats; int stats_len; bool stats41; int max_utts; int64_t capacity; bool audio, null_arg;
-  const pk_mi355_frontend_spec_t *frontend; const pk_mi355_deltas_spec_t *deltas;
-  const pk_mi355_transform_spec_t *xform = nullptr;      // pk_mi355_transform_batch_create's
-};
-// The argument checks of every public create entry, in the one order that names the fault each of them has always named,
-// also when several arguments are bad at once; an entry runs those its request gives rise to.
+// Every public create entry: the shared checks (pkhost::CheckCreate, below), then the batch.
 pk_mi355_batch *CheckedBatch(pk_mi355_am_t *am, const BatchRequest &r) {
-  if (!am || !am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (r.null_arg) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  const int D = am->feat_dim, order = r.deltas ? r.deltas->order : 0;
-  if (r.deltas && pkdelta::CheckSpec(r.deltas)) return nullptr;         // (names the field)
-  if (r.xform && pkxf::CheckSpec(r.xform)) return nullptr;              // (names the field)
-  // what the stages in front of the first layer start from: the model's features, or the rows a transform reads
-  const int Din = r.xform ? r.xform->in_dim : D;
-  if (r.xform && Din % (order + 1) != 0) {
-    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the transform's in_dim %d", order, order + 1, Din);
-    return nullptr;
-  }
-  if (Din % (order + 1) != 0) {
-    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
-    return nullptr;
-  }
-  const int Db = Din / (order + 1);
-  std::vector<FrontendAnyTables> any(r.frontend ? 1 : 0);
-  if (r.frontend && BuildFrontendAnyTables(r.frontend, any.data())) return nullptr;      // (names the field)
-  if (r.xform && r.audio && any[0].dim != Db) {
-    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the transform's in_dim %d with %d delta blocks needs %d", any[0].dim, Din,
-         order + 1, Db);
-    return nullptr;
-  }
-  if (!r.xform && r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return nullptr;
-  if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr || r.xform != nullptr)) return nullptr;
-  if (r.xform && pkxf::OutDim(*r.xform) != D) {
-    Fail(PK_MI355_E_INVALID, "the transform produces %d-dim features, the model expects %d", pkxf::OutDim(*r.xform), D);
-    return nullptr;
-  }
-  // (pk_mi355_batch_create, the one audio entry without a spec, has always named its missing statistics here)
-  if (r.max_utts <= 0 || r.capacity <= 0 || (r.audio && !r.frontend && !r.stats)) { Fail(PK_MI355_E_INVALID, "bad batch capacity"); return nullptr; }
-  if (r.stats && r.stats41 && D != kNumBins) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, D);
-    return nullptr;
-  }
-  if (IsF16(am->precision) && D % 8 != 0) {      // as pk_decodable_init: the spliced view of the split copy needs whole 8-k chunks
-    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", D);
-    return nullptr;
-  }
+  std::vector<FrontendAnyTables> any;
+  int Db = 0;
+  if (!CheckCreate(am, r, &any, &Db)) return nullptr;
   return CreateBatch(am, BatchSpec{r.stats, r.max_utts, r.audio ? r.capacity : 0, r.audio ? r.capacity / kFrameShift + r.max_utts : r.capacity,
                                    PublicChunkCap(), r.frontend ? any.data() : nullptr, r.deltas, r.xform});
 }
@@ -638,6 +593,63 @@ pk_mi355_batch *EnsureOwned(OwnedBatch *o, int64_t need, bool keep, Make make) {
 }  // namespace
 
 namespace pkhost {
+// The argument checks of every public create entry (pk_score.h), in the one order that names the fault each of them has
+// always named, also when several arguments are bad at once; an entry runs those its request gives rise to.
+bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi::FrontendAnyTables> *any_out, int *base_dim) {
+  std::vector<pkmi::FrontendAnyTables> &any = *any_out;
+  if (!am || (!r.live && !am->finalized)) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
+  if (r.null_arg) { Fail(PK_MI355_E_INVALID, "null argument"); return false; }
+  if (r.deltas && pkdelta::CheckSpec(r.deltas)) return false;         // (names the field)
+  if (r.xform && pkxf::CheckSpec(r.xform)) return false;              // (names the field)
+  if (r.live) {                      // an online scorer: the model is looked at from here on, so the above is said without a device
+    if (am->precision != PK_MI355_PRECISION_F32) {
+      Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
+      return false;
+    }
+    if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
+  }
+  const int D = am->feat_dim, order = r.deltas ? r.deltas->order : 0;
+  // what the stages in front of the first layer start from: the model's features, or the rows a transform reads
+  const int Din = r.xform ? r.xform->in_dim : D;
+  if (r.xform && Din % (order + 1) != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the transform's in_dim %d", order, order + 1, Din);
+    return false;
+  }
+  if (Din % (order + 1) != 0) {
+    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
+    return false;
+  }
+  const int Db = Din / (order + 1);
+  any.assign(r.frontend ? 1 : 0, pkmi::FrontendAnyTables());
+  if (r.frontend && BuildFrontendAnyTables(r.frontend, any.data())) return false;      // (names the field)
+  if (r.xform && r.audio && any[0].dim != Db) {
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the transform's in_dim %d with %d delta blocks needs %d", any[0].dim, Din,
+         order + 1, Db);
+    return false;
+  }
+  if (!r.xform && r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return false;
+  if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr || r.xform != nullptr)) return false;
+  if (r.xform && pkxf::OutDim(*r.xform) != D) {
+    Fail(PK_MI355_E_INVALID, "the transform produces %d-dim features, the model expects %d", pkxf::OutDim(*r.xform), D);
+    return false;
+  }
+  // (pk_mi355_batch_create, the one audio entry without a spec, has always named its missing statistics here)
+  if (r.max_utts <= 0 || r.capacity <= 0 || (r.audio && !r.frontend && !r.stats)) {
+    Fail(PK_MI355_E_INVALID, r.live ? "bad stream capacity" : "bad batch capacity");
+    return false;
+  }
+  if (r.stats && r.stats41 && D != kNumBins) {
+    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, D);
+    return false;
+  }
+  if (IsF16(am->precision) && D % 8 != 0) {      // as pk_decodable_init: the spliced view of the split copy needs whole 8-k chunks
+    Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", D);
+    return false;
+  }
+  *base_dim = Db;
+  return true;
+}
+
 pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames) {      // (at least one whole pass: every pass is kSingleChunk rows)
   return EnsureOwned(&am->single, std::max(frames, kSingleChunk), true,
                      [&](int64_t cap) { return CreateBatch(am, BatchSpec{nullptr, 1, 0, cap, kSingleChunk, nullptr, nullptr}); });

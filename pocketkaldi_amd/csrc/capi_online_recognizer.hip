@@ -184,12 +184,17 @@ void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r) {
 namespace {
 // spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
 pk_mi355_online_recognizer_t *LoadOnlineRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int max_streams,
-                                                   int64_t max_step_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr) {
+                                                   int64_t max_step_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr,
+                                                   const pk_mi355_transform_spec_t *xform = nullptr) {
   pk_mi355_online_recognizer *r = new pk_mi355_online_recognizer();
   auto failed = [&]() { pk_mi355_online_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (deltas) {
+  if (xform) {         // (the statistics at the transform's base dimension: pk_mi355_transform_stream_create holds them to it)
+    int stats_len = 0;
+    if (LoadStatsBlocks(config_path, PK_MI355_PRECISION_F32, 0, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
+    if (!(r->stream = pk_mi355_transform_stream_create(r->am, xform, deltas, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
+  } else if (deltas) {
     int stats_len = 0;
     if (LoadStatsBlocks(config_path, PK_MI355_PRECISION_F32, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
     if (!(r->stream = pk_mi355_deltas_stream_create(r->am, deltas, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
@@ -239,6 +244,17 @@ pk_mi355_online_recognizer_t *pk_mi355_deltas_online_recognizer_load(const char 
   if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
   if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
   return LoadOnlineRecognizer(config_path, frontend_spec, max_streams, max_step_samples, trace_capacity, deltas_spec);
+}
+
+pk_mi355_online_recognizer_t *pk_mi355_transform_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
+                                                                        const pk_mi355_deltas_spec_t *deltas_spec,
+                                                                        const pk_mi355_transform_spec_t *transform_spec, int max_streams,
+                                                                        int64_t max_step_samples, int64_t trace_capacity) {
+  if (!config_path || !frontend_spec || !transform_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
+  if (pk_mi355_frontend_check(frontend_spec) || (deltas_spec && pk_mi355_deltas_check(deltas_spec)) || pk_mi355_transform_check(transform_spec))
+    return nullptr;                                       // (name the field)
+  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
+  return LoadOnlineRecognizer(config_path, frontend_spec, max_streams, max_step_samples, trace_capacity, deltas_spec, transform_spec);
 }
 
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r) {

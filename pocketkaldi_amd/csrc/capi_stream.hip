@@ -13,6 +13,7 @@
 #include "pk_plan.h"
 #include "pk_resample.h"
 #include "pk_score.h"
+#include "pk_transform_kernel.h"
 
 using namespace pkmi;
 using namespace pkhost;
@@ -25,6 +26,9 @@ struct Slot {
   int n = 0;               // CMVN frames computed
   int nd = 0;              // a deltas object: delta frames final, n - M at most while open
   int ring_par = 0;        //   the delta ring buffer that holds the base frames below n
+  int nx = 0;              // a transform object: transform frames final, nin - Rt at most while open
+  int xf_par = 0;          //   the transform ring buffer that holds the input frames below nin (= nd with deltas, else n)
+  int mat = kSlotMatNone;  //   this opening's own matrix (pk_mi355_stream_transform_set_slot): none, linear or affine
   int a = 0;               // frames scored (the next row to score)
   int tail_len = 0;
   int tail_par = 0;
@@ -110,6 +114,19 @@ struct pk_mi355_stream {
   float *d_delta_scales = nullptr;    // the spec's scale table (pkdelta::BuildScales)
   float *d_delta_ring = nullptr;      // [slots][2][2 M][base_dim]
   int64_t delta_area = 0, delta_rows = 0;
+  // Made by pk_mi355_transform_stream_create: StreamTransformKernel behind the normaliser or the
+  // deltas, with the spec's matrix (xf.mt, owned; null: the spec has none) and then with the slots' own (d_slot_mats,
+  // [slots][feat_dim + 1][Ldo(feat_dim)], made at the first pk_mi355_stream_transform_set_slot).  in_dim: the width of
+  // the rows the transform reads, (order + 1) base_dim; feat_dim on every other object.  Its staging, xf_rows =
+  // max_frames + max_streams (M + Rt) rows of feat_dim floats, lies in d_upload from float xf_area on, behind the delta
+  // staging; the per-slot stage's, as large, from uxf_area on (0: not made yet), behind that.  upload_floats: d_upload's size.
+  bool has_xform = false;
+  int in_dim = 0;
+  TransformStage xf{};
+  float *d_xf_ring = nullptr;         // [slots][2][max(Lt + Rt, 1)][in_dim]
+  float *d_slot_mats = nullptr;
+  int64_t xf_area = 0, xf_rows = 0, uxf_area = 0, upload_floats = 0;
+  int extra_recs = 0;                 // StreamRec arrays behind the UttLayout arrays: deltas 1, a transform 2 more
 };
 
 namespace {
@@ -140,14 +157,14 @@ bool ModelAllowed(const pk_mi355_am *am) {
 void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
   const ScorerCore &c = s->core;
   const int max_streams = s->max_streams;
-  // (a deltas object: the layout's records lie behind the UttLayout arrays, a second StreamRec array)
+  // (a deltas or transform object: the later stages' records lie behind the UttLayout arrays, a StreamRec array each)
   s->meta_bytes = RoundUp(sizeof(StreamRec) * max_streams, 256) + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * max_streams, 256) +
-                  (s->has_deltas ? RoundUp(sizeof(StreamRec) * max_streams, 256) : 0) + sizeof(int32_t) * Shift4Cap(c.max_cols);
+                  s->extra_recs * RoundUp(sizeof(StreamRec) * max_streams, 256) + sizeof(int32_t) * Shift4Cap(c.max_cols);
   chk(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
   const int Db = s->base_dim;
-  if (s->has_deltas)                   // every slot is laid out by StreamFeatureLayoutKernel: the history, at create
+  if (s->has_deltas || s->has_xform)   // every slot is laid out by StreamFeatureLayoutKernel: the history, at create
     chk(hipMalloc(&s->d_feat_hist, sizeof(float) * max_streams * 2 * s->hist_len * c.am->feat_dim));
-  if (s->have_stats && (Db != kNumBins || s->has_deltas)) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
+  if (s->have_stats && (Db != kNumBins || s->has_deltas || s->has_xform)) {   // StreamCmvnChainKernel's state; its rows stay in the upload staging
     chk(hipMalloc(&s->d_sums, sizeof(float) * max_streams * Db));
     chk(hipMalloc(&s->d_raw_hist, sizeof(float) * max_streams * kCmvnWindow * Db));
     if (s->rows_area && !s->d_feat_hist)   // audio slots are laid out by StreamFeatureLayoutKernel: their history, at create
@@ -159,7 +176,8 @@ void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
     chk(hipMalloc(&s->d_rows, sizeof(float) * c.max_frames * kNumBins));
   }
   chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_upload), sizeof(float) * (s->rows_area ? s->rows_area : s->upload_cap), hipHostMallocDefault));
-  chk(hipMalloc(&s->d_upload, sizeof(float) * (s->has_deltas ? s->delta_area + s->delta_rows * c.am->feat_dim : s->upload_cap)));
+  s->upload_floats = s->has_xform ? s->xf_area + s->xf_rows * c.am->feat_dim : s->has_deltas ? s->delta_area + s->delta_rows * c.am->feat_dim : s->upload_cap;
+  chk(hipMalloc(&s->d_upload, sizeof(float) * s->upload_floats));
   chk(hipHostMalloc(reinterpret_cast<void **>(&s->h_meta), s->meta_bytes, hipHostMallocDefault));
   chk(hipMalloc(&s->d_meta, s->meta_bytes));
 }
@@ -207,13 +225,17 @@ namespace {
 struct StreamShape {
   const char *entry; bool audio; const float *stats; const FrontendAnyTables *any; int max_streams; int64_t step_cap;
   const pk_mi355_deltas_spec_t *deltas = nullptr;
+  const pk_mi355_transform_spec_t *xform = nullptr;      // the checked spec of a transform object: base dimension in_dim / (order + 1)
 };
 
 // Every way to a stream object; the entries have checked their other arguments.
 pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   const int D = am->feat_dim, max_streams = sh.max_streams;
+  const int Din = sh.xform ? sh.xform->in_dim : D;      // what the deltas make, or the normaliser without them
+  const int Db = sh.deltas ? Din / (sh.deltas->order + 1) : Din;
+  const int Dw = std::max(D, Db);                       // the widest pushed frame: NORMALIZED at D, RAW at Db
   // (pk_mi355_stream_create, the one audio entry whose statistics can still be missing here, has always named that so)
-  if (max_streams <= 0 || sh.step_cap <= 0 || sh.step_cap > ((int64_t)1 << 30) / (sh.audio ? 1 : D) || (sh.audio && !sh.stats)) {
+  if (max_streams <= 0 || sh.step_cap <= 0 || sh.step_cap > ((int64_t)1 << 30) / (sh.audio ? 1 : Dw) || (sh.audio && !sh.stats)) {
     Fail(PK_MI355_E_INVALID, "bad stream capacity");
     return nullptr;
   }
@@ -223,9 +245,12 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   s->features_only = !sh.audio; s->have_stats = sh.stats != nullptr;
   s->has_deltas = sh.deltas != nullptr;
   if (sh.deltas) { s->deltas = *sh.deltas; s->reach = pkdelta::Reach(*sh.deltas); }
-  const int Db = s->base_dim = sh.deltas ? D / (sh.deltas->order + 1) : D, M = s->reach;
+  s->has_xform = sh.xform != nullptr;
+  s->in_dim = Din; s->base_dim = Db;
+  s->extra_recs = (sh.deltas ? 1 : 0) + (sh.xform ? 2 : 0);
+  const int M = s->reach, Rt = sh.xform ? sh.xform->right_context : 0, Ct = sh.xform ? sh.xform->left_context + Rt : 0;
   // (a NORMALIZED frame of a deltas object can be wider than 160 floats: it counts as what it takes in the staging)
-  s->frame_cost = sh.audio ? std::max(kFrameShift, D) : 1;
+  s->frame_cost = sh.audio ? std::max(kFrameShift, Dw) : 1;
   s->slots.resize(max_streams);
   s->hist_len = std::max(am->left + am->right, 1);
   // Audio: a slot's segment holds at most 399 carried samples and its pushes.  A slot's rows are its new frames and the
@@ -236,11 +261,17 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   // step's samples (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
   // With deltas the row area is there at every base dimension, its rows Db floats wide; a closing
   // slot emits up to M + R rows more than it was pushed, and the delta staging lies behind everything else.
-  s->rows_area = sh.audio && (D != kNumBins || sh.deltas) ? RoundUp(sh.step_cap, 64) : 0;
-  s->upload_cap = !sh.audio ? sh.step_cap * D : s->rows_area ? s->rows_area + max_frames * Db : sh.step_cap;
+  // A transform object likewise has a row area wherever it has a front-end; a closing slot emits up
+  // to M + Rt + R rows more than it was pushed, and the transform's staging lies behind the delta staging.
+  s->rows_area = sh.audio && (D != kNumBins || sh.deltas || sh.xform) ? RoundUp(sh.step_cap, 64) : 0;
+  s->upload_cap = !sh.audio ? sh.step_cap * Dw : s->rows_area ? s->rows_area + max_frames * Db : sh.step_cap;
   if (sh.deltas) { s->delta_area = RoundUp(s->upload_cap, 64); s->delta_rows = max_frames + (int64_t)max_streams * M; }
+  if (sh.xform) {
+    s->xf_area = sh.deltas ? RoundUp(s->delta_area + s->delta_rows * Din, 64) : RoundUp(s->upload_cap, 64);
+    s->xf_rows = max_frames + (int64_t)max_streams * (M + Rt);
+  }
   CreateCheck chk{sh.entry};
-  CreateScorerCore(&s->core, am, sh.stats, Db, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + M + 3), 262144, chk);
+  CreateScorerCore(&s->core, am, sh.stats, Db, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + M + Rt + 3), 262144, chk);
   if (sh.any) UploadSpecTables(&s->core, sh.any, &s->d_any, chk);
   CreateStepBuffers(s, chk);
   if (sh.deltas) {     // StreamDeltaKernel's table and the slots' rings
@@ -249,7 +280,20 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
     const size_t bytes = sizeof(float) * (size_t)(sh.deltas->order + 1) * pkdelta::RowLen(*sh.deltas);
     chk(hipMalloc(&s->d_delta_scales, bytes));
     if (chk.ok) chk(hipMemcpy(s->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
-    chk(hipMalloc(&s->d_delta_ring, sizeof(float) * max_streams * 2 * 2 * M * Db));
+    chk(hipMalloc(&s->d_delta_ring, sizeof(float) * max_streams * 2 * 2 * M * Db));      // (delta rows are Din = (order + 1) Db floats wide)
+  }
+  if (sh.xform) {      // StreamTransformKernel's global matrix, transposed and padded, and the slots' rings
+    const pk_mi355_transform_spec_t &x = *sh.xform;
+    s->xf = TransformStage{x.in_dim, x.left_context, x.right_context, D, false, nullptr, 0};
+    if (pkxf::HasMatrix(x)) {
+      std::vector<float> packed((size_t)x.cols * pkxf::Ldo(x.rows));
+      pkxf::PackTransposed(x.matrix, x.rows, x.cols, packed.data());
+      float *d_mt = nullptr;
+      chk(hipMalloc(&d_mt, sizeof(float) * packed.size()));
+      if (chk.ok) chk(hipMemcpy(d_mt, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+      s->xf.affine = pkxf::Affine(x); s->xf.mt = d_mt;
+    }
+    chk(hipMalloc(&s->d_xf_ring, sizeof(float) * max_streams * 2 * std::max(Ct, 1) * Din));
   }
   if (sh.audio) {
     chk(hipMalloc(&s->d_tails, sizeof(float) * max_streams * 2 * kTailCap));
@@ -317,6 +361,66 @@ pk_mi355_stream_t *pk_mi355_deltas_stream_create(pk_mi355_am_t *am, const pk_mi3
   return CreateStream(am, sh);
 }
 
+// pk_mi355_transform_batch_create's checks through the path it takes itself (pkhost::CheckCreate, `live`: the null
+// arguments and the specs before the model is looked at, an f16 model refused).
+pk_mi355_stream_t *pk_mi355_transform_stream_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform,
+                                                    const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
+                                                    const float *global_stats, int stats_len, int max_streams, int64_t capacity) {
+  BatchRequest r{global_stats, stats_len, false, max_streams, capacity, frontend != nullptr, !transform || (frontend && !global_stats), frontend, deltas,
+                 transform};
+  r.live = true;
+  std::vector<FrontendAnyTables> any;
+  int Db = 0;
+  if (!CheckCreate(am, r, &any, &Db)) return nullptr;
+  StreamShape sh{"transform_stream_create", frontend != nullptr, global_stats, frontend ? any.data() : nullptr, max_streams, capacity};
+  sh.deltas = deltas; sh.xform = transform;
+  return CreateStream(am, sh);
+}
+
+int pk_mi355_stream_in_dim(const pk_mi355_stream_t *s) {
+  if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
+  return s->in_dim;
+}
+
+int pk_mi355_stream_transform_set_slot(pk_mi355_stream_t *s, int slot, const float *matrix, int rows, int cols) {
+  if (int rc = SlotIndex(s, slot)) return rc;
+  if (!matrix) return Fail(PK_MI355_E_INVALID, "null argument");
+  if (!s->has_xform) return Fail(PK_MI355_E_STATE, "a slot's own transform needs a stream made by pk_mi355_transform_stream_create");
+  const int D = s->core.am->feat_dim;
+  if (rows != D) return Fail(PK_MI355_E_INVALID, "the slot's transform has %d rows, the model's features need %d", rows, D);
+  if (cols != D && cols != D + 1)
+    return Fail(PK_MI355_E_INVALID, "the slot's transform has %d columns, the model's %d-dim features need %d (linear) or %d (affine)", cols, D, D, D + 1);
+  if (D > kMaxSlotTransformDim)         // (the stage keeps kTransformFrames rows of D floats in LDS)
+    return Fail(PK_MI355_E_INVALID, "a slot's own transform needs a feature dimension of at most %d (got %d)", kMaxSlotTransformDim, D);
+  const int64_t bad = pkxf::FirstNonFinite(matrix, (int64_t)rows * cols);
+  if (bad >= 0)
+    return Fail(PK_MI355_E_INVALID, "the slot's transform has an entry that is not finite (row %d, column %d)", (int)(bad / cols), (int)(bad % cols));
+  Slot &z = s->slots[slot];
+  if (z.state == kOpen && z.kind == PK_MI355_FEATS_NORMALIZED)
+    return Fail(PK_MI355_E_STATE, "slot %d takes normalised features: no transform applies", slot);
+  if (z.state != kOpen || z.nx != 0)
+    return Fail(PK_MI355_E_STATE, "slot %d: a transform belongs to an open slot before its first transform frame is computed", slot);
+  if (int rc = UseDevice(s->core.device)) return rc;
+  const size_t each = (size_t)(D + 1) * pkxf::Ldo(D);
+  if (!s->d_slot_mats) HIP_TRY(hipMalloc(&s->d_slot_mats, sizeof(float) * each * (size_t)s->max_streams));
+  if (!s->uxf_area) {
+    // The per-slot stage's staging, behind the global stage's in the allocation of the upload staging.  Nothing in that
+    // allocation outlives a step: once the stream is idle it is made anew, larger.
+    const int64_t at = RoundUp(s->upload_floats, 64), floats = at + s->xf_rows * D;
+    float *grown = nullptr;
+    HIP_TRY(hipStreamSynchronize(s->core.stream));
+    HIP_TRY(hipMalloc(&grown, sizeof(float) * floats));
+    hipFree(s->d_upload);
+    s->d_upload = grown; s->upload_floats = floats; s->uxf_area = at;
+  }
+  std::vector<float> packed((size_t)cols * pkxf::Ldo(D));
+  pkxf::PackTransposed(matrix, rows, cols, packed.data());
+  HIP_TRY(hipMemcpyAsync(s->d_slot_mats + each * (size_t)slot, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice, s->core.stream));
+  HIP_TRY(hipStreamSynchronize(s->core.stream));        // (pageable memory: the copy has read its source)
+  z.mat = cols == D + 1 ? kSlotMatAffine : kSlotMatLinear;
+  return 0;
+}
+
 int pk_mi355_stream_feat_dim(const pk_mi355_stream_t *s) {
   if (!s) return Fail(PK_MI355_E_INVALID, "null stream");
   return s->core.am->feat_dim;
@@ -332,6 +436,7 @@ void pk_mi355_stream_destroy(pk_mi355_stream_t *s) {
   hipSetDevice(s->core.device);
   if (s->core.stream) hipStreamSynchronize(s->core.stream);
   hipFree(s->d_delta_scales); hipFree(s->d_delta_ring);
+  hipFree(const_cast<float *>(s->xf.mt)); hipFree(s->d_xf_ring); hipFree(s->d_slot_mats);
   hipFree(s->d_tails); hipFree(s->d_sums); hipFree(s->d_raw_hist); hipFree(s->d_hist); hipFree(s->d_feat_hist);
   hipFree(s->d_upload); hipFree(s->d_wave); hipFree(s->d_rows); hipFree(s->d_meta); hipFree(s->d_any);
   hipFree(s->d_norm_glob); hipFree(s->d_norm_spk); hipFree(s->d_norm_win); hipFree(s->d_norm_total); hipFree(s->d_norm_table); hipFree(s->d_norm_ring);
@@ -365,7 +470,8 @@ int pk_mi355_stream_open_rate(pk_mi355_stream_t *s, int slot, int rate) {
   }
   if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
-  z.n = z.a = z.nd = z.tail_len = 0;
+  z.n = z.a = z.nd = z.nx = z.tail_len = 0;
+  z.mat = kSlotMatNone;
   z.pending.clear();
   z.rate = rate; z.tab = tab;
   z.kind = -1;
@@ -388,7 +494,8 @@ int pk_mi355_stream_open_features(pk_mi355_stream_t *s, int slot, int kind) {
     if (int rc = EnsureFeatureHistory(s)) return rc;
   if (int rc = ResetSlotNorm(s, slot)) return rc;
   z.state = kOpen;
-  z.n = z.a = z.nd = z.tail_len = 0;
+  z.n = z.a = z.nd = z.nx = z.tail_len = 0;
+  z.mat = kSlotMatNone;
   z.pending.clear();
   z.rate = kSampleRate; z.tab = nullptr;
   z.kind = kind;
@@ -576,8 +683,21 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   // A deltas object: lrecs[k] is what the layout launch sees for the slot of recs[k] -- for an audio
   // or RAW slot the delta frames [nd, nd1) that StreamDeltaKernel makes final, as rows of the delta staging; for a
   // NORMALIZED slot recs[k] itself.  On every other object the layout reads recs.
-  const bool dl = s->has_deltas;
-  StreamRec *lrecs = dl ? reinterpret_cast<StreamRec *>(lay_base + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * s->max_streams, 256)) : recs;
+  // A transform object has two arrays more, behind the deltas' where there is one: xrecs[k], the
+  // transform frames [nx, nx1) that become final -- rows of the transform's staging when the spec has a matrix, else the
+  // rows the stage in front left -- and urecs[k], the same frames as rows of the per-slot stage's staging.  The layout reads
+  // the last stage that runs in this step (lrecs, chosen once the records are made).
+  const bool dl = s->has_deltas, xf = s->has_xform, chained = dl || xf;
+  auto extra = [&](int i) {
+    return reinterpret_cast<StreamRec *>(lay_base + RoundUp((sizeof(int64_t) * 2 + sizeof(int32_t)) * s->max_streams, 256) +
+                                         i * RoundUp(sizeof(StreamRec) * s->max_streams, 256));
+  };
+  StreamRec *drecs = dl ? extra(0) : recs, *xrecs = xf ? extra(dl ? 1 : 0) : drecs, *urecs = xf ? extra(dl ? 2 : 1) : xrecs;
+  const bool xf_global = xf && s->xf.mt != nullptr;
+  const int Din = s->in_dim, Rt = s->xf.right;          // (Rt: 0 on every other object)
+  int64_t xout = 0;                                   // rows of the transform stagings taken
+  int max_xnew = 0, n_xf = 0;                         // the most transform frames a record makes final; records StreamTransformKernel serves
+  bool slot_mats = false;                             // a record's slot holds a matrix of its own: the per-slot stage runs
   // Records.  A 40-dim object: audio and RAW slots (StreamAssembleKernel, FbankKernel or FbankAnyKernel,
   // StreamCmvnKernel) from the front of the array, NORMALIZED slots (StreamFeatureLayoutKernel) from its back.  Another
   // dimension: audio slots from the front, feature slots of both kinds from the back; on an object with a front-end spec
@@ -614,8 +734,8 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     // (a front-end spec at a dimension other than 40, DESIGN.md section 18: audio records go the same way, their rows
     // written into the staging's row area by FbankAnyKernel; they stay in front, where the assembly and the fbank look)
     const bool feats = z.kind >= 0, spec_rows = !feats && s->rows_area > 0;
-    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && (Db != kNumBins || !sliding || dl));
-    const bool delta_rec = dl && z.kind != PK_MI355_FEATS_NORMALIZED;
+    const bool layout = z.kind == PK_MI355_FEATS_NORMALIZED || (feats && (Db != kNumBins || !sliding || chained));
+    const bool delta_rec = dl && z.kind != PK_MI355_FEATS_NORMALIZED, xf_rec = xf && z.kind != PK_MI355_FEATS_NORMALIZED;
     const int width = z.kind == PK_MI355_FEATS_NORMALIZED ? D : Db;       // floats of a pushed frame
     const bool front_rows = !feats && !sliding && !spec_rows;       // an audio slot at 40 under a norm spec: laid out from d_rows
     const int new_len = feats    ? 0
@@ -626,14 +746,16 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     const int n = z.n + m;
     // open: R frames of look-ahead held back -- and in front of deltas M base frames more (pkdelta::StreamDeltaAdvance)
     const pkdelta::StreamDeltaCounts dc = delta_rec ? pkdelta::StreamDeltaAdvance(n, z.nd, z.a, M, R, closed) : pkdelta::StreamDeltaCounts{n, 0};
-    const int b = delta_rec ? dc.b : closed ? n : std::max(z.a, n - R);
+    // (behind a transform Rt input frames more: pkxf::StreamTransformAdvance, over the delta frames where there are deltas)
+    const pkxf::StreamTransformCounts tc = xf_rec ? pkxf::StreamTransformAdvance(dc.nd1, z.nx, z.a, Rt, R, closed) : pkxf::StreamTransformCounts{0, 0};
+    const int b = xf_rec ? tc.b : delta_rec ? dc.b : closed ? n : std::max(z.a, n - R);
     if (new_len == 0 && m == 0 && b == z.a) {
       if (closed) flushed.push_back(slot);
       continue;
     }
     const int rec_at = layout ? s->max_streams - 1 - n_back++ : n_front++;
     StreamRec &r = recs[rec_at];
-    r.kind = z.kind; r.hist_par = z.hist_par; r.ring_par = z.ring_par;
+    r.kind = z.kind; r.hist_par = z.hist_par; r.ring_par = z.ring_par; r.xf_bits = z.xf_par | (z.mat << 1);
     r.slot = slot; r.tail_len = z.tail_len; r.new_len = new_len; r.tail_par = z.tail_par;
     r.n_old = z.n; r.m = m; r.a = z.a; r.b = b; r.closed = closed ? 1 : 0;
     r.woff = woff; r.new_off = upl; r.raw_base = layout ? 0 : raw;
@@ -652,14 +774,30 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
       if (layout || spec_rows || front_rows) max_feat_cols = std::max(max_feat_cols, r.cols);
     }
     if (dl) {
-      StreamRec &lr = lrecs[rec_at];
+      StreamRec &lr = drecs[rec_at];
       lr = r;
       if (delta_rec) {
         lr.n_old = z.nd; lr.m = dc.nd1 - z.nd;
-        lr.row_off = s->delta_area + dout * D;
+        lr.row_off = s->delta_area + dout * Din;
         dout += lr.m;
         max_new = std::max(max_new, lr.m);
         ++n_delta;
+      }
+    }
+    if (xf) {
+      StreamRec &xr = xrecs[rec_at], &ur = urecs[rec_at];
+      xr = drecs[rec_at];                // (without a matrix in the spec nx = nin: the rows the stage in front left, as they lie)
+      if (xf_rec) {
+        xr.n_old = z.nx; xr.m = tc.nx1 - z.nx;
+        if (xf_global) xr.row_off = s->xf_area + xout * D;
+      }
+      ur = xr;
+      if (xf_rec) {
+        ur.row_off = s->uxf_area + xout * D;
+        xout += xr.m;
+        max_xnew = std::max(max_xnew, xr.m);
+        ++n_xf;
+        slot_mats = slot_mats || z.mat != kSlotMatNone;
       }
     }
     woff += seg; upl += feats ? (int64_t)m * width : new_len;
@@ -672,9 +810,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   }
   const int64_t upl_cap = s->rows_area ? s->rows_area : s->upload_cap;      // (a row area: the pushes end where it begins)
   const bool staging_fits = woff <= s->wave_cap && upl <= upl_cap && native_total <= s->native_cap &&
-                            (!s->rows_area || s->rows_area + raw * Db <= s->upload_cap) && dout <= s->delta_rows;
+                            (!s->rows_area || s->rows_area + raw * Db <= s->upload_cap) && dout <= s->delta_rows && xout <= s->xf_rows &&
+                            (!slot_mats || s->uxf_area > 0);
   const bool rows_fit = raw <= c.max_frames && RoundUp(out, kTileF16) <= c.max_cols && col <= c.max_cols;
-  if (dl && n_front > 0 && !s->rows_area)             // (pk_plan.cc: no plan serves front records of a deltas object without a row area)
+  if (chained && n_front > 0 && !s->rows_area)        // (pk_plan.cc: no plan serves front records of a deltas or transform object without a row area)
     return Fail(PK_MI355_E_INVALID, "internal: a deltas stream with audio records and no row area");
   if (!staging_fits || !rows_fit || ((n_back > 0 || (!sliding && n_front > 0)) && !s->d_feat_hist))
     return Fail(PK_MI355_E_INVALID, "internal: step exceeds the stream's capacity");
@@ -682,9 +821,10 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   if (s->rows_area) {
     const std::vector<StreamRec> back(recs + (s->max_streams - n_back), recs + s->max_streams);
     for (int j = 0; j < n_back; ++j) recs[n_front + j] = back[n_back - 1 - j];
-    if (dl) {
-      const std::vector<StreamRec> lback(lrecs + (s->max_streams - n_back), lrecs + s->max_streams);
-      for (int j = 0; j < n_back; ++j) lrecs[n_front + j] = lback[n_back - 1 - j];
+    for (int i = 0; i < s->extra_recs; ++i) {
+      StreamRec *e = extra(i);
+      const std::vector<StreamRec> eback(e + (s->max_streams - n_back), e + s->max_streams);
+      for (int j = 0; j < n_back; ++j) e[n_front + j] = eback[n_back - 1 - j];
     }
     for (int &k : at)
       if (k >= n_front) k = n_front + (s->max_streams - 1 - k);
@@ -694,6 +834,7 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   int32_t bad = 0;
   if (total_rows > 0 && !ExpandShift4(spans, total_rows, c.zero_span, reinterpret_cast<int32_t *>(s->h_meta + shift4_at), &bad))
     return Fail(PK_MI355_E_INVALID, "internal: column shift %d outside [0, %lld]", bad, (long long)(c.zero_span - kTile));
+  StreamRec *lrecs = slot_mats ? urecs : xrecs;       // (xrecs is drecs without a transform, drecs is recs without deltas)
   // the plan holds: consume every pushed sample, advance the slots
   std::vector<ResampleItem> items;
   int64_t native_at = 0;
@@ -701,10 +842,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     const StreamRec &r = recs[at[k]];
     Slot &z = s->slots[r.slot];
     const bool delta_rec = dl && z.kind != PK_MI355_FEATS_NORMALIZED;
-    const int lay_m = lrecs[at[k]].m;    // the fresh rows the layout sees (behind deltas: the delta frames that became final)
+    const bool xf_rec = xf && z.kind != PK_MI355_FEATS_NORMALIZED;
+    const int lay_m = lrecs[at[k]].m;    // the fresh rows the layout sees (behind deltas or a transform: the frames that became final)
     if (z.kind >= 0) {                   // pushed frames, frame-major
       if (r.m) memcpy(s->h_upload + r.new_off, z.pending.data(), sizeof(float) * (size_t)r.m * (z.kind == PK_MI355_FEATS_NORMALIZED ? D : Db));
-      if (lay_m && (z.kind == PK_MI355_FEATS_NORMALIZED || Db != kNumBins || !sliding || dl)) z.hist_par ^= 1;    // the step writes the other history buffer
+      if (lay_m && (z.kind == PK_MI355_FEATS_NORMALIZED || Db != kNumBins || !sliding || chained)) z.hist_par ^= 1;    // the step writes the other history buffer
     } else if (z.tab && r.new_len) {
       // outputs [n_prod, n_prod + new_len) from the samples held, straight to where pushed 16 kHz samples would lie
       const ResampleTable &t = z.tab->host;
@@ -729,7 +871,11 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
     }
     if (delta_rec) {
       if (r.m) z.ring_par ^= 1;          // StreamDeltaKernel writes the other ring buffer
-      z.nd = lrecs[at[k]].n_old + lay_m;
+      z.nd = drecs[at[k]].n_old + drecs[at[k]].m;
+    }
+    if (xf_rec) {
+      if (drecs[at[k]].m && s->xf.left + s->xf.right > 0) z.xf_par ^= 1;    // StreamTransformKernel writes the other ring buffer
+      z.nx = xrecs[at[k]].n_old + xrecs[at[k]].m;
     }
     z.n = r.n_old + r.m;
     z.a = r.b;
@@ -767,7 +913,8 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   HIP_TRY(hipEventRecord(s->ev_staged, c.stream));
   s->staged = true;
   const StreamRec *d_recs = reinterpret_cast<const StreamRec *>(s->d_meta);
-  const StreamRec *d_lrecs = reinterpret_cast<const StreamRec *>(s->d_meta + (reinterpret_cast<char *>(lrecs) - s->h_meta));
+  auto on_device = [&](const StreamRec *h) { return reinterpret_cast<const StreamRec *>(s->d_meta + (reinterpret_cast<const char *>(h) - s->h_meta)); };
+  const StreamRec *d_lrecs = on_device(lrecs), *d_drecs = on_device(drecs), *d_xrecs = on_device(xrecs), *d_urecs = on_device(urecs);
   const char *d_lay = s->d_meta + (lay_base - s->h_meta);
   const int64_t *d_woff = reinterpret_cast<const int64_t *>(d_lay);
   const int64_t *d_rawb = d_woff + s->max_streams;
@@ -775,7 +922,8 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   UttLayout lay{d_woff, d_T, d_rawb, d_rawb};
   // The plan (pk_plan.h; DESIGN.md, "The two plans").  The front stage: assembly and fbank over the n_front front records,
   // the rows [raw_base][D] going to d_rows, or on an object with a row area to the staging behind the samples.
-  const pkplan::StreamPlan plan = pkplan::PlanStream(s->rows_area != 0, nmode, pkplan::StepCounts{n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed}, dl);
+  const pkplan::StreamPlan plan = pkplan::PlanStream(s->rows_area != 0, nmode, pkplan::StepCounts{n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed}, dl,
+                                                     xf, xf_global, slot_mats);
   if (plan.front) {
     float *dst = s->rows_area ? s->d_upload + s->rows_area : s->d_rows;
     LaunchStreamAssemble(d_recs, n_front, s->d_upload, s->d_tails, s->d_wave, c.stream);
@@ -787,12 +935,18 @@ int pk_mi355_stream_step(pk_mi355_stream_t *s, float prob_scale, int sync) {
   for (int k = 0; k < plan.n; ++k) {
     const pkplan::Block &bl = plan.block[k];
     const StreamRec *r = d_recs + (bl.back ? s->max_streams - n_back : 0);
-    const StreamRec *lr = d_lrecs + (bl.back ? s->max_streams - n_back : 0);     // (r itself without deltas)
+    const int first = bl.back ? s->max_streams - n_back : 0;
+    const StreamRec *lr = d_lrecs + first;     // (r itself without deltas and transform)
+    const StreamRec *dr = d_drecs + first, *xr = d_xrecs + first, *ur = d_urecs + first;
     float *rows = bl.step_rows ? s->d_rows : s->d_upload;
     if (bl.raw_rows) LaunchStreamRawRows(r, bl.count, s->d_upload, s->d_rows, c.stream);
     if (bl.norm == pkplan::kStreamNorm) LaunchStreamNorm(r, bl.count, Db, rows, NormState(s), c.stream);
     else if (bl.norm == pkplan::kStreamCmvnChain) LaunchStreamCmvnChain(r, bl.count, Db, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, c.stream);
-    if (bl.delta && n_delta > 0) LaunchStreamDelta(r, lr, bl.count, max_new, Db, s->deltas, s->d_delta_scales, rows, s->d_delta_ring, c.stream);
+    if (bl.delta && n_delta > 0) LaunchStreamDelta(r, dr, bl.count, max_new, Db, s->deltas, s->d_delta_scales, rows, s->d_delta_ring, c.stream);
+    if (bl.transform && n_xf > 0) LaunchStreamTransform(dr, xr, bl.count, max_xnew, s->xf, false, rows, s->d_xf_ring, c.stream);
+    if (bl.slot_transform && n_xf > 0)
+      LaunchStreamTransform(xr, ur, bl.count, max_xnew, TransformStage{D, 0, 0, D, false, s->d_slot_mats, (int64_t)(D + 1) * pkxf::Ldo(D)}, true, rows,
+                            s->d_xf_ring, c.stream);
     if (bl.fused) LaunchStreamCmvn(r, bl.count, rows, c.d_global, c.d_cmvn_tab, s->d_sums, s->d_raw_hist, s->d_hist, s->hist_len, L, R, c.d_yt, c.ldy, c.stream);
     else LaunchStreamFeatureLayout(lr, bl.count, max_feat_cols, rows, s->d_feat_hist, s->hist_len, D, L, R, c.d_yt, c.ldy, c.stream);
   }

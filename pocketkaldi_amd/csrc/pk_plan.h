@@ -45,7 +45,12 @@ enum StreamNormaliser { kNoNormaliser, kStreamNorm, kStreamCmvnChain };
 // raw_rows: StreamRawRowsKernel first copies the RAW records' pushed rows to d_rows.  fused: StreamCmvnKernel normalises
 // and lays out in one launch; else the normaliser (if any), then StreamFeatureLayoutKernel.  delta (a deltas object,
 // DESIGN.md section 24): StreamDeltaKernel between the two, and the layout reads the step's second record array.
-struct Block { bool back; int count; bool step_rows, raw_rows; StreamNormaliser norm; bool fused; bool delta = false; };
+// transform, slot_transform (a transform object): StreamTransformKernel with the global matrix,
+// and once more with the slots' own matrices, behind the deltas; the layout reads the last stage's record array.
+struct Block {
+  bool back; int count; bool step_rows, raw_rows; StreamNormaliser norm; bool fused; bool delta = false;
+  bool transform = false, slot_transform = false;
+};
 struct StepCounts { int n_front, n_back, n_audio, max_m, raw_pushed, chain_pushed; };
 struct StreamPlan {
   bool front = false;            // StreamAssembleKernel and the fbank run over the n_front front records
@@ -56,7 +61,11 @@ struct StreamPlan {
 // fresh rows all lie in the upload staging.  deltas: an object made by pk_mi355_deltas_stream_create -- nothing takes the
 // fused path (StreamCmvnKernel writes the layout itself, as FusedCmvn on the batch side), SLIDING runs the chain at the
 // base dimension, at 40 too, and every block goes normaliser, StreamDeltaKernel, layout.
-StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k, bool deltas = false);
+// transform: an object made by pk_mi355_transform_stream_create -- as deltas: nothing fused, the chain at the base
+// dimension, and every block goes normaliser, [StreamDeltaKernel], StreamTransformKernel (global_matrix: the spec has a
+// matrix), the per-slot stage (slot_matrices: in this step a record's slot holds a matrix of its own), layout.
+StreamPlan PlanStream(bool row_area, int mode, const StepCounts &k, bool deltas = false, bool transform = false, bool global_matrix = false,
+                      bool slot_matrices = false);
 
 }  // namespace pkplan
 

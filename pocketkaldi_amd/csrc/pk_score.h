@@ -28,6 +28,9 @@ struct StreamRec {
                        // segment; m = frames pushed since the last step, [m][D] floats at new_off of the upload staging)
   int32_t hist_par;    // NORMALIZED: the slot's history buffer that holds the frames below n_old (the step writes the other one)
   int32_t ring_par;    // a deltas object: the slot's delta ring buffer that holds the base frames below n_old
+  int32_t xf_bits;     // a transform object.  Bit 0: the slot's transform ring buffer that holds the input
+                       // frames below the step's first fresh one; bits 1-2: the slot's own matrix (kSlotMat*: none, linear,
+                       // affine).  (It lies where the struct had padding: a record is the 96 bytes it was.)
   int64_t woff;        // first sample of the segment in the wave staging
   int64_t new_off;     // first pushed sample in the upload staging
   int64_t raw_base;    // first row of the slot's new frames in the step's raw rows
@@ -36,6 +39,8 @@ struct StreamRec {
                        // upload staging -- new_off for a feature slot; for an audio slot of a front-end spec at D != 40
                        //  the rows FbankAnyKernel wrote into the staging's row area, behind the samples
 };
+static_assert(sizeof(StreamRec) == 96, "StreamRec: xf_bits fills the padding behind ring_par");
+enum { kSlotMatNone = 0, kSlotMatLinear = 1, kSlotMatAffine = 2 };      // StreamRec::xf_bits >> 1
 
 // launchers (stream.hip): one workgroup (StreamAssembleKernel) / one wavefront (StreamCmvnKernel) for each of n records
 void LaunchStreamAssemble(const StreamRec *recs, int n, const float *upload, float *tails, float *wave, hipStream_t stream);
@@ -141,6 +146,21 @@ inline bool StatsLenFits(int stats_len, int dim, bool base) {
     Fail(PK_MI355_E_INVALID, "the CMVN statistics have %d entries, a %d-dim model needs %d (the sums, then the count)", stats_len, dim, dim + 1);
   return false;
 }
+
+// What a public create entry was handed.  stats41: 41 statistics by the entry's contract (a 40-dim model's; no
+// stats_len).  audio: the capacity is in samples and there is a front-end -- the spec's, or without one the reference's
+// 40 bins; else it is in frames.  null_arg: the entry found one of the pointers it needs null.  live: an online scorer's
+// entry (pk_mi355_transform_stream_create): an f16 model is refused besides, and the model is looked at only behind the
+// null arguments and the specs.
+struct BatchRequest {
+  const float *stats; int stats_len; bool stats41; int max_utts; int64_t capacity; bool audio, null_arg;
+  const pk_mi355_frontend_spec_t *frontend; const pk_mi355_deltas_spec_t *deltas;
+  const pk_mi355_transform_spec_t *xform = nullptr;      // pk_mi355_transform_batch_create's and _stream_create's
+  bool live = false;
+};
+// The argument checks of the create entries (capi_batch.hip).  False: refused, the text is pk_mi355_last_error's.  True:
+// *any holds the front-end spec's tables (empty without one), *base_dim the dimension in front of deltas and transform.
+bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi::FrontendAnyTables> *any, int *base_dim);
 
 // ------------------------------------------------------------------ column shifts (capi_batch.hip)
 // Spans of rows (a multiple of four each) with one column shift -> one entry per group of four rows, for every row a

@@ -1,6 +1,6 @@
 // pk_transform.cc -- feature transforms on the host (pk_transform.h): the check, the matrix layout
-// the kernel reads and the whole rule for one matrix.  No HIP: g++ builds it, into the library and into
-// tests/cpp/transform_test.cc.
+// the kernel reads and the whole rule for one matrix; the streaming apply of a live slot (section 26).  No HIP: g++ builds
+// it, into the library and into tests/cpp/transform_test.cc and tests/cpp/stream_transform_test.cc.
 #include "pk_transform.h"
 
 #include <math.h>
@@ -51,6 +51,46 @@ void PackTransposed(const float *m, int rows, int cols, float *out) {
     for (int o = 0; o < rows; ++o) out[(size_t)k * ldo + o] = m[(size_t)o * cols + k];
     for (int o = rows; o < ldo; ++o) out[(size_t)k * ldo + o] = 0.0f;
   }
+}
+
+StreamTransformHost::StreamTransformHost(const pk_mi355_transform_spec_t &spec) : spec_(spec), C_(spec.left_context + spec.right_context) {
+  for (int p = 0; p < 2; ++p) ring_[p] = new float[(size_t)C_ * spec_.in_dim];
+}
+
+StreamTransformHost::~StreamTransformHost() {
+  for (int p = 0; p < 2; ++p) delete[] ring_[p];
+}
+
+int StreamTransformHost::Push(const float *x, int m, bool closed, float *out) {
+  const int nin_old = nin_, nin = nin_ + m, Dp = spec_.in_dim, C = C_, L = spec_.left_context;
+  const StreamTransformCounts c = StreamTransformAdvance(nin, nx_, 0, spec_.right_context, 0, closed);
+  const float *old = ring_[par_];
+  auto frame = [&](int f) {               // f in [max(nin_old - C, 0), nin)
+    const StreamTransformSource s = StreamTransformPick(f, nin_old, C);
+    return s.fresh ? x + (size_t)s.row * Dp : old + (size_t)s.row * Dp;
+  };
+  auto clamped = [&](int t) { return frame(t < 0 ? 0 : t > nin - 1 ? nin - 1 : t); };
+  if (!HasMatrix(spec_)) {                // rows pass as bits
+    for (int t = nx_; t < c.nx1; ++t) memcpy(out + (size_t)(t - nx_) * Dp, frame(t), sizeof(float) * Dp);
+  } else {
+    const int W = Window(spec_);
+    const bool affine = Affine(spec_);
+    const size_t rows = (size_t)spec_.rows, cols = (size_t)spec_.cols;
+    for (int t = nx_; t < c.nx1; ++t)
+      for (size_t o = 0; o < rows; ++o) {
+        const float *mrow = spec_.matrix + o * cols;
+        out[(size_t)(t - nx_) * rows + o] =
+            TransformApply<float>(W, Dp, affine, [&](int k) { return mrow[k]; }, [&](int j, int d) { return clamped(t + j - L)[d]; });
+      }
+  }
+  if (m > 0 && C > 0) {                   // frames [max(nin - C, 0), nin) to the other buffer, which nothing above reads
+    float *next = ring_[par_ ^ 1];
+    for (int f = nin - C > 0 ? nin - C : 0; f < nin; ++f) memcpy(next + (size_t)(f % C) * Dp, frame(f), sizeof(float) * Dp);
+    par_ ^= 1;
+  }
+  const int made = c.nx1 - nx_;
+  nin_ = nin; nx_ = c.nx1;
+  return made;
 }
 
 }  // namespace pkxf

@@ -57,6 +57,13 @@ hold the default leg and one leg per mode.
 and --frontend (model S at (order + 1) x the spec's dimension); the check is against the batch deltas scorer.  The leg to
 hold it against is --features normalized --feat-dim (order + 1) Db on the same tree: the difference is StreamDeltaKernel
 and the normaliser.  profiles/stream_deltas_bench.json holds those legs.
+
+--transform left,right,out_dim puts a feature transform in front of the splice (pk.TransformSpec): a
+seeded affine matrix from (left + right + 1) x the width in front of it -- Db, or (order + 1) Db behind --deltas -- to
+out_dim, with --features raw --feat-dim Db (the tiny model at out_dim) or with audio and --frontend (model S at out_dim).
+--slot-transforms hands every slot a matrix of its own (out_dim x (out_dim + 1)) when it is opened.  The check is against
+the batch transform scorer under the same matrices; the leg to hold it against is --features normalized --feat-dim
+out_dim on the same tree.  profiles/stream_transform_bench.json holds those legs.
 """
 import argparse
 import json
@@ -99,7 +106,23 @@ def main():
                     "DESIGN.md section 20); the global and the speakers' records are stream 0's own statistics")
     ap.add_argument("--deltas", default=None, help="order,window: delta features in front of the splice (DESIGN.md section 24), with "
                     "--features raw --feat-dim Db or with audio and --frontend")
+    ap.add_argument("--transform", default=None, help="left,right,out_dim: a feature transform in front of the splice (DESIGN.md section 26), "
+                    "with --features raw --feat-dim Db or with audio and --frontend; behind --deltas when both are given")
+    ap.add_argument("--tiny", action="store_true", help="with --features at 40 dimensions: synthetic features through the tiny model, as at "
+                    "every other --feat-dim (the leg to hold a transform to 40 dimensions against)")
+    ap.add_argument("--slot-transforms", action="store_true", help="with --transform: every slot gets a matrix of its own at its open")
     a = ap.parse_args()
+    xf = None
+    if a.transform is not None:
+        try:
+            xf = tuple(int(v) for v in a.transform.split(","))
+            assert len(xf) == 3 and min(xf[:2]) >= 0 and xf[2] >= 1
+        except (ValueError, AssertionError):
+            ap.error("--transform left,right,out_dim")
+        if a.decode or a.commit or a.endpoint or not ((a.features == "raw") != (a.frontend is not None)):
+            ap.error("--transform takes --features raw --feat-dim Db, or audio with --frontend, and no decoder")
+    if a.slot_transforms and xf is None:
+        ap.error("--slot-transforms goes with --transform")
     dspec = None
     if a.deltas is not None:
         try:
@@ -109,7 +132,19 @@ def main():
             ap.error("--deltas order,window: %s" % e)
         if a.decode or a.commit or a.endpoint or not ((a.features == "raw") != (a.frontend is not None)):
             ap.error("--deltas takes --features raw --feat-dim Db, or audio with --frontend, and no decoder")
-    synthetic = a.feat_dim != 40 or (dspec is not None and a.features is not None)
+    if a.tiny and a.features is None:
+        ap.error("--tiny goes with --features")
+    synthetic = a.feat_dim != 40 or a.tiny or ((dspec is not None or xf is not None) and a.features is not None)
+
+    def transform_of(width):
+        """(the spec, the slots' four matrices or None) for rows `width` wide in front of the transform."""
+        Lt, Rt, out = xf
+        K = (Lt + Rt + 1) * width
+        m = (np.random.default_rng(5).standard_normal((out, K + 1)) / np.sqrt(K)).astype(np.float32)
+        own = [(np.eye(out, out + 1) + 0.1 * np.random.default_rng(60 + u).standard_normal((out, out + 1))).astype(np.float32) for u in range(4)]
+        return pk.TransformSpec(m, Lt, Rt, in_dim=width), own if a.slot_transforms else None
+
+    xspec = slot_mats = None
     if a.cmvn is not None and a.features == "normalized":
         ap.error("--cmvn takes audio or raw features")
     spec = None
@@ -120,7 +155,7 @@ def main():
             spec = pk.parse_frontend(a.frontend)
         except ValueError as e:
             ap.error(str(e))
-    if a.feat_dim != 40 and dspec is None and (a.features is None or a.decode or a.commit or a.endpoint):
+    if a.feat_dim != 40 and dspec is None and xf is None and (a.features is None or a.decode or a.commit or a.endpoint):
         ap.error("--feat-dim takes --features and no decoder")
     a.decode = a.decode or a.commit or a.endpoint
 
@@ -136,26 +171,39 @@ def main():
     if spec is not None:
         D = spec.dim
         Dm = D if dspec is None else dspec.dim(D)
+        if xf is not None:
+            xspec, slot_mats = transform_of(Dm)
+            Dm = xf[2]
         layers, prior, L, R = synth.model("S", feat_dim=Dm)
         am = pk.AcousticModel(layers, prior, L, R)
         model_name = "S at feat_dim %d (%d -> 4 x 1024 -> 3000, L = R = 5), f32, stable softmax; front-end %r%s" % (
-            Dm, 11 * Dm, spec, "" if dspec is None else "; %r" % dspec)
+            Dm, 11 * Dm, spec, ("" if dspec is None else "; %r" % dspec) + ("" if xspec is None else "; %r" % xspec))
         fb = pk.Frontend(spec).compute(waves[0])
         g = np.concatenate([fb.astype(np.float64).mean(axis=0) * 2500.0, [2500.0]]).astype(np.float32)
-        sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk, frontend=spec, deltas=dspec)
+        if xspec is not None:
+            sc = pk.OnlineScorer.with_transform(am, g, a.streams, a.streams * chunk, xspec, frontend=spec, deltas=dspec)
+        else:
+            sc = pk.OnlineScorer(am, g, a.streams, a.streams * chunk, frontend=spec, deltas=dspec)
     elif synthetic:
         D = a.feat_dim
         Dm = D if dspec is None else dspec.dim(D)
+        if xf is not None:
+            xspec, slot_mats = transform_of(Dm)
+            Dm = xf[2]
         layers, prior, L, R = synth.model("tiny", feat_dim=Dm)
         am = pk.AcousticModel(layers, prior, L, R)
-        model_name = "tiny at feat_dim %d (L = R = 5), f32, stable softmax%s" % (Dm, "" if dspec is None else "; %r in front, base %d" % (dspec, D))
+        model_name = "tiny at feat_dim %d (L = R = 5), f32, stable softmax%s" % (
+            Dm, ("" if dspec is None else "; %r in front, base %d" % (dspec, D)) + ("" if xspec is None else "; %r in front" % xspec))
         g = np.concatenate([np.full(D, 3.0 * 2500.0), [2500.0]]).astype(np.float32)
         T = pk.num_frames(len(waves[0]))
         base = [(5.0 * np.random.default_rng(u).standard_normal((T, D)) + 3.0).astype(np.float32) for u in range(4)]
         feats = [base[u % 4] for u in range(a.streams)]
         chunk = int(round(a.chunk_ms / 10.0))                  # frames per step
         nsteps = (T + chunk - 1) // chunk
-        sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None, deltas=dspec)
+        if xspec is not None:
+            sc = pk.OnlineFeatureScorer.with_transform(am, a.streams, a.streams * chunk, xspec, global_stats=g, deltas=dspec)
+        else:
+            sc = pk.OnlineFeatureScorer(am, a.streams, a.streams * chunk, global_stats=g if a.features == "raw" else None, deltas=dspec)
     elif a.features:
         bs = pk.BatchScorer(am, g, a.streams, sum(len(w) for w in waves))
         bs.set_waves(waves)
@@ -204,6 +252,8 @@ def main():
     def run(record, nsteps=nsteps):
         for s in range(a.streams):
             sc.open_features(s, a.features, speaker_stats=record0) if feats else sc.open(s, speaker_stats=record0)
+            if slot_mats:
+                sc.set_slot_transform(s, slot_mats[s % 4])
             if dec:
                 dec.open(s)
         walls, frames, rows0 = [], 0, []
@@ -251,29 +301,31 @@ def main():
     walls, frames, rows0 = run(True)
     walls_ms = np.array(walls) * 1e3
     if synthetic:
-        bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g, deltas=dspec)
+        bs = pk.FeatureScorer(am, 1, feats[0].shape[0], global_stats=g, deltas=dspec, transform=xspec)
         bs.set_features(feats[:1], a.features)
     else:
-        bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec, deltas=dspec)
+        bs = pk.BatchScorer(am, g, 1, len(waves[0]), frontend=spec, deltas=dspec, transform=xspec)
         bs.set_waves(waves[:1])
     if norm is not None:
         bs.set_norm(norm, pk.cmvn_normalize(feats[0] if feats else bs_rows(bs), pk.NormSpec("utterance", True, True))[1]) \
             if isinstance(norm, pk.OnlineCmvnSpec) else bs.set_norm(norm)
         if record0 is not None:
             bs.set_speaker_stats([record0])
+    if slot_mats:                            # (consumed by the score call that follows)
+        bs.set_utt_transforms(slot_mats[:1])
     bs.score(0.1)
     ok = np.concatenate(rows0).tobytes() == bs.fetch(0).log_prob().tobytes()
     rec = {
         "streams": a.streams, "seconds": a.seconds, "chunk_ms": a.chunk_ms, "steps": len(walls),
         "input": "features, %s, %d frames a push" % (a.features, chunk) if feats else "audio",
-        "model": model_name, "cmvn": a.cmvn, "deltas": a.deltas,
+        "model": model_name, "cmvn": a.cmvn, "deltas": a.deltas, "transform": a.transform, "slot_transforms": bool(a.slot_transforms),
         "device": torch.cuda.get_device_name(0),
         "step_ms": {"median": float(np.median(walls_ms)), "p90": float(np.percentile(walls_ms, 90)),
                     "max": float(walls_ms.max())},
         "frames": int(frames),
         "frames_per_s": float(frames / (walls_ms.sum() / 1e3)),
         "rtf": float(np.median(walls_ms) / a.chunk_ms),
-        "algorithmic_delay_ms": {"window_and_lookahead": 15.0 + 10.0 * (R + (dspec.order * dspec.window if dspec else 0)),
+        "algorithmic_delay_ms": {"window_and_lookahead": 15.0 + 10.0 * (R + (dspec.order * dspec.window if dspec else 0) + (xf[1] if xf else 0)),
                                  "plus_chunk_at_most": a.chunk_ms},
         "check_stream0_equals_batch": bool(ok),
     }
