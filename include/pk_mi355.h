@@ -76,6 +76,19 @@ enum {
   PK_NNET_SOFTMAX_LAYER = 3
 };
 #endif
+/* Kinds 4 and 5 carry the reference's numbers (nnet.h:18-19; its reader loads neither); 6 to 8 are this library's.
+ * The rules: pk_mi355_layer_apply_host below.                                     */
+#ifndef PK_NNET_ADD_LAYER
+enum {
+  PK_NNET_ADD_LAYER = 4,              /* y[d] = x[d] + v[d]                          */
+  PK_NNET_MUL_LAYER = 5               /* y[d] = x[d] * v[d]                          */
+};
+#endif
+enum {
+  PK_MI355_NNET_SIGMOID_LAYER = 6,
+  PK_MI355_NNET_TANH_LAYER = 7,
+  PK_MI355_NNET_PNORM_LAYER = 8       /* the 2-norm of groups of in_dim / out_dim consecutive features */
+};
 
 /* Error codes */
 enum {
@@ -137,6 +150,27 @@ int pk_mi355_am_add_linear(pk_mi355_am_t *am, int in_dim, int out_dim, const flo
                            const float *b);
 /* ReLULayer / NormalizeLayer / SoftmaxLayer, nnet.cc:38-75                       */
 int pk_mi355_am_add_layer(pk_mi355_am_t *am, int layer_type);
+/* The kinds without a parameter also include PK_MI355_NNET_SIGMOID_LAYER and PK_MI355_NNET_TANH_LAYER.  A bare kind
+ * 4, 5 or 8 is refused there ("unexpected layer type"): those take their parameter through the two entries below.
+ * The kinds 4 to 8 exist in F32 precision only (F16X3 / F16 refuse the network at finalize).
+ *
+ * PK_NNET_ADD_LAYER / PK_NNET_MUL_LAYER: v[dim] is copied; dim > 0 and every entry finite (PK_MI355_E_INVALID names
+ * the first index that is not).  finalize holds dim to the width the layers in front leave.                        */
+int pk_mi355_am_add_vector_layer(pk_mi355_am_t *am, int kind, int dim, const float *v);
+/* PK_MI355_NNET_PNORM_LAYER, in_dim -> out_dim: out_dim > 0 and in_dim a multiple of it (PK_MI355_E_INVALID names
+ * both numbers); the group size is in_dim / out_dim, p is 2.                                                       */
+int pk_mi355_am_add_pnorm(pk_mi355_am_t *am, int in_dim, int out_dim);
+/* The rule of one layer of kind 4 to 8 on the host, for rows x[rows][in_dim] -> out[rows][out_dim] (never in place
+ * for kind 8); needs no GPU.  The GPU layers are held to it bit for bit.  With E = float expf, every operation IEEE,
+ * none fused:
+ *   add, mul : param = v[in_dim]; out_dim = in_dim; in float
+ *   sigmoid  : x > 0: 1.0 / (1.0 + (double)E(-x)); otherwise e = (double)E(x), e / (e + 1.0); rounded to float once
+ *   tanh     : x > 0: t = E(-x), q = t * t (float), -1.0 + 2.0 / (1.0 + (double)q); otherwise t = E(x), q = t * t,
+ *              1.0 - 2.0 / (1.0 + (double)q); rounded to float once (a NaN takes the second branch and stays NaN)
+ *   p-norm   : param = NULL; s = 0.0f, s = s + x[o G + g] * x[o G + g] for g = 0 .. G - 1 (float), out[o] = sqrtf(s)
+ *              correctly rounded; an overflowed sum gives inf (Kaldi's rescaling fallback is not restated)
+ * param = NULL and out_dim = in_dim for sigmoid and tanh.                                                          */
+int pk_mi355_layer_apply_host(int kind, const float *x, int rows, int in_dim, const float *param, int out_dim, float *out);
 
 /* Arithmetic of the affine layers (set before finalize / read; default F32).
  *   F32   : fp32 MFMA, accumulation order of the reference's SGEMM -- bit-identical layers.

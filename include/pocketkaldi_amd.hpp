@@ -129,6 +129,11 @@ class AcousticModel {
     return Status::FromLast(pk_mi355_am_add_linear(am_, in_dim, out_dim, W, b));
   }
   Status AddLayer(int layer_type) { return Status::FromLast(pk_mi355_am_add_layer(am_, layer_type)); }
+  // PK_NNET_ADD_LAYER / PK_NNET_MUL_LAYER with their vector; the 2-norm of groups of in_dim / out_dim features
+  Status AddVectorLayer(int kind, const std::vector<float> &v) {
+    return Status::FromLast(pk_mi355_am_add_vector_layer(am_, kind, static_cast<int>(v.size()), v.data()));
+  }
+  Status AddPnorm(int in_dim, int out_dim) { return Status::FromLast(pk_mi355_am_add_pnorm(am_, in_dim, out_dim)); }
   Status Finalize(const std::vector<float> &prior, int left_context, int right_context,
                   const std::vector<int32_t> &tid2pdf) {
     return Status::FromLast(pk_mi355_am_finalize(am_, prior.data(), static_cast<int>(prior.size()),

@@ -30,9 +30,10 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "TransformSpec", "parse_transform", "transform_feats", "splice_feats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "TransformSpec", "parse_transform", "transform_feats", "splice_feats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "ADD", "MUL", "SIGMOID", "TANH", "PNORM", "apply_layer", "write_nnet", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
+ADD, MUL, SIGMOID, TANH, PNORM = 4, 5, 6, 7, 8      # 4 and 5: the reference's numbers (nnet.h:18-19); 6 to 8: ours
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -174,6 +175,7 @@ EXPORTS = [
     "pk_mi355_transform_in_dim", "pk_mi355_transform_set_utt", "pk_mi355_transform_recognizer_load",
     "pk_mi355_transform_stream_create", "pk_mi355_stream_in_dim", "pk_mi355_stream_transform_set_slot",
     "pk_mi355_transform_online_recognizer_load",
+    "pk_mi355_am_add_vector_layer", "pk_mi355_am_add_pnorm", "pk_mi355_layer_apply_host",
 ]
 
 
@@ -217,6 +219,9 @@ def lib():
     L.pk_mi355_am_destroy.argtypes = [C.c_void_p]
     L.pk_mi355_am_add_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, f32p]
     L.pk_mi355_am_add_layer.argtypes = [C.c_void_p, C.c_int]
+    L.pk_mi355_am_add_vector_layer.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p]
+    L.pk_mi355_am_add_pnorm.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pk_mi355_layer_apply_host.argtypes = [C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int, f32p]
     L.pk_mi355_am_set_precision.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_am_precision.argtypes = [C.c_void_p]
     L.pk_mi355_am_finalize.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
@@ -1083,9 +1088,10 @@ class AcousticModel:
     """am.h:23-52 + nnet.h:88-104.
 
     layers: list of ("linear", W[out][in], b[out]) | ("relu",) | ("normalize",) | ("softmax",)
+            | ("sigmoid",) | ("tanh",) | ("pnorm", out_dim) | ("add", v[dim]) | ("mul", v[dim])   (f32 precision only)
     prior:  pdf prior probabilities (the log is taken at load, am.cc:43)
     """
-    _KIND = {"relu": RELU, "normalize": NORMALIZE, "softmax": SOFTMAX}
+    _KIND = {"relu": RELU, "normalize": NORMALIZE, "softmax": SOFTMAX, "sigmoid": SIGMOID, "tanh": TANH}
 
     PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2}
 
@@ -1095,10 +1101,21 @@ class AcousticModel:
         self._h = L.pk_mi355_am_create()
         _check(L.pk_mi355_am_set_precision(self._h, self.PRECISIONS[precision]))
         if layers is not None:
+            width = 0                        # what the layers so far leave (a p-norm's input width)
             for l in layers:
                 if l[0] == "linear":
                     W, b = _f32(l[1]), _f32(l[2])
                     _check(L.pk_mi355_am_add_linear(self._h, W.shape[1], W.shape[0], _fp(W), _fp(b)))
+                    width = W.shape[0]
+                elif l[0] in ("add", "mul"):
+                    v = _f32(l[1]).ravel()
+                    _check(L.pk_mi355_am_add_vector_layer(self._h, _LAYER_KIND[l[0]], v.shape[0], _fp(v)))
+                    width = v.shape[0]
+                elif l[0] == "pnorm":
+                    if width <= 0:
+                        raise PkError("a p-norm layer needs a layer in front of it that states the width")
+                    _check(L.pk_mi355_am_add_pnorm(self._h, width, int(l[1])))
+                    width = int(l[1])
                 else:
                     _check(L.pk_mi355_am_add_layer(self._h, self._KIND[l[0]]))
             pr = None if prior is None else _f32(prior)
@@ -1217,6 +1234,61 @@ class AcousticModel:
         m_out = pk_matrix_t(0, 0, None)
         _check(lib().pk_mi355_nnet_propagate(self._h, C.byref(m_in), C.byref(m_out)))
         return _take_matrix(m_out)
+
+
+_LAYER_KIND = {"linear": LINEAR, "relu": RELU, "normalize": NORMALIZE, "softmax": SOFTMAX, "add": ADD, "mul": MUL, "sigmoid": SIGMOID,
+               "tanh": TANH, "pnorm": PNORM}
+
+
+def apply_layer(kind, x, param=None):
+    """The rule of one layer of kind "add" / "mul" (param: the vector), "sigmoid" / "tanh" or "pnorm" (param: out_dim) on the
+    host for rows x [T][dim] (pk_mi355_layer_apply_host: the restatement the GPU layers are held to) -> float32 rows."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise PkCodeError(-1, "rows have shape %s, expected [T][dim]" % (x.shape,))
+    k = _LAYER_KIND[kind] if isinstance(kind, str) else int(kind)
+    T, D = x.shape
+    v, O = None, D
+    if k == PNORM:
+        O = int(param)
+    elif k in (ADD, MUL):
+        v = _f32(param).ravel()
+        if v.shape[0] != D:
+            raise PkCodeError(-1, "the vector has %d entries, the rows %d" % (v.shape[0], D))
+    y = np.zeros((T, max(O, 0)), np.float32)
+    _check_code(lib().pk_mi355_layer_apply_host(k, _fp(x), T, D, None if v is None else _fp(v), O, _fp(y)))
+    return y
+
+
+def write_nnet(path, layers):
+    """The NNT0 model file of `layers` (AcousticModel's list; all nine kinds), as tool/convert_am.py of the reference
+    writes kinds 0 to 3 and 5: LAY0 sections, a Linear's W as MAT0 of VEC0 rows and its bias, an add / mul layer's
+    vector as one VEC0, a p-norm's in_dim and out_dim as two int32 (in_dim: the width the layers in front leave)."""
+    import struct
+
+    def vec(v):
+        v = _f32(v).ravel()
+        return b"VEC0" + struct.pack("<ii", 4 * v.shape[0] + 4, v.shape[0]) + v.tobytes()
+
+    out = [b"NNT0" + struct.pack("<ii", 4, len(layers))]
+    width = 0
+    for l in layers:
+        kind = _LAYER_KIND[l[0]]
+        out.append(b"LAY0" + struct.pack("<ii", 4, kind))
+        if kind == LINEAR:
+            W, b = _f32(l[1]), _f32(l[2])
+            out.append(b"MAT0" + struct.pack("<iii", 8, W.shape[0], W.shape[1]) + b"".join(vec(r) for r in W) + vec(b))
+            width = W.shape[0]
+        elif kind in (ADD, MUL):
+            out.append(vec(l[1]))
+            width = _f32(l[1]).size
+        elif kind == PNORM:
+            if width <= 0:
+                raise PkError("a p-norm layer needs a layer in front of it that states the width")
+            out.append(struct.pack("<ii", width, int(l[1])))
+            width = int(l[1])
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
 
 
 def device_logf(x):

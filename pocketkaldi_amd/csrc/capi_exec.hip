@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "pk_layers.h"
 #include "pk_score.h"
 
 using namespace pkmi;
@@ -242,6 +243,44 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
         Scoped t(timer, PK_MI355_K_OTHER, stream);
         if (cur_rows) LaunchNormalize(const_cast<float *>(cur), rows_pad, cur_dim, cur_ld, 1, stream);
         else LaunchNormalize(const_cast<float *>(cur), rows_pad, cur_dim, 1, cur_ld, stream);
+        break;
+      }
+      case PK_NNET_ADD_LAYER:
+      case PK_NNET_MUL_LAYER:
+      case PK_MI355_NNET_SIGMOID_LAYER:
+      case PK_MI355_NNET_TANH_LAYER: {
+        // in place on the dim real features.  A panel's padding rows [dim, RoundUp(dim, kBK)) are
+        // not touched: they stay what the GEMM in front wrote (zeros for finite frames), and the next GEMM meets them
+        // with zero weights.
+        if (cur_splice) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
+        if (cur == e.in) {                 // never modify inputs in place: copy first
+          float *dst = bufs[next_buf];
+          HIP_TRY(hipMemcpyAsync(dst, cur, sizeof(float) * (size_t)RoundUp(cur_dim, kBK) * e.rows_cap,
+                                 hipMemcpyDeviceToDevice, stream));
+          cur = dst; next_buf ^= 1;
+        }
+        Scoped t(timer, PK_MI355_K_OTHER, stream);
+        const float *v = pklayers::IsVectorKind(L.type) ? blob + am->vec_off[i] : nullptr;
+        if (cur_rows) LaunchLayerElementwise(L.type, const_cast<float *>(cur), rows_pad, cur_dim, cur_ld, 1, v, stream);
+        else LaunchLayerElementwise(L.type, const_cast<float *>(cur), rows_pad, cur_dim, 1, cur_ld, v, stream);
+        break;
+      }
+      case PK_MI355_NNET_PNORM_LAYER: {
+        // into the other work buffer, which holds whatever an earlier layer or call left: in the panel layout the rows
+        // [out_dim, RoundUp(out_dim, kBK)) are written as zeros, because the next GEMM reads them (against zero weights:
+        // 0 * NaN is NaN)
+        if (cur_splice) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
+        float *dst = bufs[next_buf];
+        Scoped t(timer, PK_MI355_K_OTHER, stream);
+        if (cur_rows) {
+          const int64_t ld = RoundUp(L.out_dim, kTile);
+          LaunchPnorm(cur, rows_pad, cur_dim, L.out_dim, cur_ld, 1, dst, ld, L.out_dim, stream);
+          cur_ld = ld;
+        } else {
+          LaunchPnorm(cur, rows_pad, cur_dim, L.out_dim, 1, cur_ld, dst, e.rows_cap, (int)RoundUp(L.out_dim, kBK), stream);
+          cur_ld = e.rows_cap;
+        }
+        cur = dst; cur_dim = L.out_dim; next_buf ^= 1;
         break;
       }
       case PK_NNET_SOFTMAX_LAYER: {

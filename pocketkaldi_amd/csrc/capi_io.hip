@@ -31,10 +31,13 @@ int AmRead(pk_mi355_am_t *am, const char *nnet_path, const char *prior_path, con
       if ((rc = files_fit(L.in_dim))) return rc;
       break;
     }
-  for (const HostLayer &L : layers)
-    if ((rc = L.type == PK_NNET_LINEAR_LAYER ? pk_mi355_am_add_linear(am, L.in_dim, L.out_dim, L.W.data(), L.b.data())
-                                             : pk_mi355_am_add_layer(am, L.type)))
-      return rc;
+  for (const HostLayer &L : layers) {
+    if (L.type == PK_NNET_LINEAR_LAYER) rc = pk_mi355_am_add_linear(am, L.in_dim, L.out_dim, L.W.data(), L.b.data());
+    else if (L.type == PK_NNET_ADD_LAYER || L.type == PK_NNET_MUL_LAYER) rc = pk_mi355_am_add_vector_layer(am, L.type, L.in_dim, L.b.data());
+    else if (L.type == PK_MI355_NNET_PNORM_LAYER) rc = pk_mi355_am_add_pnorm(am, L.in_dim, L.out_dim);
+    else rc = pk_mi355_am_add_layer(am, L.type);
+    if (rc) return rc;
+  }
   return pk_mi355_am_finalize(am, prior.data(), num_pdfs, left_context, right_context,
                               tid.empty() ? nullptr : tid.data(), (int)tid.size());
 }

@@ -11,6 +11,7 @@
 
 #include "pk_f16_layout.h"
 #include "pk_host.h"
+#include "pk_layers.h"
 
 using namespace pkmi;
 using namespace pkhost;
@@ -111,10 +112,32 @@ int pk_mi355_am_add_linear(pk_mi355_am_t *am, int in_dim, int out_dim, const flo
 int pk_mi355_am_add_layer(pk_mi355_am_t *am, int layer_type) {
   if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model is finalized");
   if (layer_type != PK_NNET_RELU_LAYER && layer_type != PK_NNET_NORMALIZE_LAYER &&
-      layer_type != PK_NNET_SOFTMAX_LAYER)   // nnet.cc:106-127 accepts only kinds 0..3
+      layer_type != PK_NNET_SOFTMAX_LAYER && !pklayers::IsPlainKind(layer_type))   // (kinds 4, 5 and 8 need their parameter)
     return Fail(PK_MI355_E_INVALID, "unexpected layer type: %d", layer_type);
   HostLayer L;
   L.type = layer_type;
+  am->layers.push_back(L);
+  return 0;
+}
+
+int pk_mi355_am_add_vector_layer(pk_mi355_am_t *am, int kind, int dim, const float *v) {
+  if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model is finalized");
+  if (int rc = pklayers::CheckVectorLayer(kind, dim, v)) return rc;
+  HostLayer L;
+  L.type = kind;
+  L.in_dim = L.out_dim = dim;
+  L.b.assign(v, v + dim);
+  am->layers.push_back(std::move(L));
+  return 0;
+}
+
+int pk_mi355_am_add_pnorm(pk_mi355_am_t *am, int in_dim, int out_dim) {
+  if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model is finalized");
+  if (int rc = pklayers::CheckPnorm(in_dim, out_dim)) return rc;
+  HostLayer L;
+  L.type = PK_MI355_NNET_PNORM_LAYER;
+  L.in_dim = in_dim;
+  L.out_dim = out_dim;
   am->layers.push_back(L);
   return 0;
 }
@@ -145,8 +168,7 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
                          int right_context, const int32_t *tid2pdf, int num_tids) {
   if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model already finalized");
   if (left_context < 0 || right_context < 0) return Fail(PK_MI355_E_INVALID, "negative context");
-  int rc = UseDevice(am->device);
-  if (rc) return rc;
+  int rc = 0;        // (the device is selected once the network has passed its checks: those need none)
 
   // dimension chain
   const bool f16 = IsF16(am->precision);
@@ -167,16 +189,28 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
     }
     if (!ok) return Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision supports (Linear [ReLU] [Normalize])+ [Softmax] networks only");
   }
+  // dim: the running width, 0 until a layer states one (a Linear, a vector layer or a p-norm; the other kinds keep
+  // whatever width reaches them)
   int first_in = 0, dim = 0;
   am->lin.clear();
   am->flops_per_frame = 0;
   size_t off = 0;
   int max_pad = 0;
-  for (auto &L : am->layers) {
+  for (int i = 0; i < (int)am->layers.size(); ++i) {
+    HostLayer &L = am->layers[i];
+    if (pklayers::IsVectorKind(L.type) || L.type == PK_MI355_NNET_PNORM_LAYER) {
+      if (dim == 0) first_in = L.in_dim;
+      else if (L.in_dim != dim)
+        return Fail(PK_MI355_E_INVALID, "layer dimension mismatch: layer %d (%s) is %d wide, the layers in front of it leave %d", i,
+                    L.type == PK_MI355_NNET_PNORM_LAYER ? "p-norm" : "vector layer", L.in_dim, dim);
+      dim = L.out_dim;
+      max_pad = std::max(max_pad, (int)RoundUp(L.in_dim, kTile));
+      continue;
+    }
     if (L.type != PK_NNET_LINEAR_LAYER) continue;
-    if (first_in == 0) { first_in = L.in_dim; }
+    if (dim == 0) { first_in = L.in_dim; }
     else if (L.in_dim != dim)
-      return Fail(PK_MI355_E_INVALID, "layer dimension mismatch: %d after %d", L.in_dim, dim);
+      return Fail(PK_MI355_E_INVALID, "layer dimension mismatch: %d after %d (layer %d)", L.in_dim, dim, i);
     dim = L.out_dim;
     DevLinear D;
     D.K = L.in_dim; D.N = L.out_dim;
@@ -195,7 +229,7 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
     max_pad = std::max(max_pad, D.Npad);
     max_pad = std::max(max_pad, (int)RoundUp(D.K, f16 ? kTileF16 : kTile));
   }
-  if (am->lin.empty()) {
+  if (dim == 0) {
     // layer-only networks (the nnet_test.cc micro-tests): the width is the pdf count
     if (num_pdfs <= 0) return Fail(PK_MI355_E_INVALID, "cannot infer the width of a network without linear layers");
     first_in = dim = num_pdfs;
@@ -219,6 +253,11 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   const int nlin = (int)am->lin.size();
   am->h_exps.assign(2 * nlin + 1, 0);
   if (f16) off += RoundUp(2 * nlin + 1, 4);
+  // the vectors of the add / mul layers, each padded to 4 floats, behind everything a model without them has (its
+  // offsets and blob_floats are what they were); inside the blob, so the one broadcast carries them
+  am->vec_off.assign(am->layers.size(), 0);
+  for (size_t i = 0; i < am->layers.size(); ++i)
+    if (pklayers::IsVectorKind(am->layers[i].type)) { am->vec_off[i] = off; off += RoundUp(am->layers[i].in_dim, 4); }
   am->blob_floats = off;
 
   // pack: W^T zero-padded to [Kpad][Npad] (nnet.cc:16-17 keeps the transpose),
@@ -265,6 +304,10 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   for (int i = 0; i < dim; ++i)
     blob[am->logprior_off + i] = prior ? logf(prior[i]) : 0.0f;
   if (f16) memcpy(blob.data() + am->exp_off, am->h_exps.data(), sizeof(int32_t) * am->h_exps.size());
+  for (size_t i = 0; i < am->layers.size(); ++i)
+    if (pklayers::IsVectorKind(am->layers[i].type))
+      memcpy(blob.data() + am->vec_off[i], am->layers[i].b.data(), sizeof(float) * am->layers[i].b.size());
+  if ((rc = UseDevice(am->device))) return rc;
   HIP_TRY(hipMalloc(&am->d_blob, sizeof(float) * off));
   HIP_TRY(hipMemcpy(am->d_blob, blob.data(), sizeof(float) * off, hipMemcpyHostToDevice));
 

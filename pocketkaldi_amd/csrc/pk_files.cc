@@ -63,8 +63,20 @@ int ReadNnet(const char *path, std::vector<HostLayer> *layers) {
       if ((int)L.b.size() != rows) return Fail(PK_MI355_E_IO, "bias dimension mismatch in %s", path);
       L.in_dim = cols;
       L.out_dim = rows;
-    } else if (L.type != PK_NNET_RELU_LAYER && L.type != PK_NNET_NORMALIZE_LAYER && L.type != PK_NNET_SOFTMAX_LAYER) {
-      return Fail(PK_MI355_E_IO, "read_layer: unexpected layer type: %d (%s)", L.type, path);   // nnet.cc:106-127
+    } else if (L.type == PK_NNET_ADD_LAYER || L.type == PK_NNET_MUL_LAYER) {
+      // one VEC0, what convert_am.py's write_layer emits for kind 5 (a FixedScaleComponent).  Its kind-4 branch
+      // contradicts itself and its parser never produces that kind: 4 is defined here like 5.
+      if ((rc = f.Vec(&L.b))) return rc;
+      if (L.b.empty()) return Fail(PK_MI355_E_IO, "read_layer: empty vector in a layer of type %d (%s)", L.type, path);
+      L.in_dim = L.out_dim = (int)L.b.size();
+    } else if (L.type == PK_MI355_NNET_PNORM_LAYER) {
+      if (!f.I32(&L.in_dim) || !f.I32(&L.out_dim))
+        return Fail(PK_MI355_E_IO, "read_layer: p-norm dimensions expected in %s", path);
+      if (L.in_dim <= 0 || L.out_dim <= 0 || L.in_dim % L.out_dim != 0)
+        return Fail(PK_MI355_E_IO, "read_layer: p-norm input width %d is not a multiple of the output width %d (%s)", L.in_dim, L.out_dim, path);
+    } else if (L.type != PK_NNET_RELU_LAYER && L.type != PK_NNET_NORMALIZE_LAYER && L.type != PK_NNET_SOFTMAX_LAYER &&
+               L.type != PK_MI355_NNET_SIGMOID_LAYER && L.type != PK_MI355_NNET_TANH_LAYER) {
+      return Fail(PK_MI355_E_IO, "read_layer: unexpected layer type: %d (%s)", L.type, path);   // nnet.cc:106-127 knows 0..3
     }
     layers->push_back(std::move(L));
   }

@@ -25,7 +25,8 @@ const char *LastError();
 // ------------------------------------------------------------------ section files
 // "VEC0" i32 bytes(=4n+4) i32 n, n x 4 bytes (vector.cc:393-425);
 // "MAT0" i32 8, i32 rows, i32 cols, rows x VEC0 (matrix.cc:288-319);
-// "NNT0" i32 4, i32 layers; "LAY0" i32 4, i32 type [+ MAT0 W, VEC0 b] (nnet.cc:80-147)
+// "NNT0" i32 4, i32 layers; "LAY0" i32 4, i32 type [+ MAT0 W, VEC0 b] (nnet.cc:80-147);
+// beyond the reference's reader: type 4 / 5 + VEC0 v, type 8 + i32 in_dim, i32 out_dim, types 6 / 7 bare
 
 struct FileBuf {
   std::vector<unsigned char> d;
@@ -86,7 +87,7 @@ struct HostLayer {
   int type = 0;
   int in_dim = 0, out_dim = 0;
   std::vector<float> W;   // [out][in]
-  std::vector<float> b;
+  std::vector<float> b;   // the bias; kinds 4 and 5: the vector (in_dim = out_dim = its length).  Kind 8: the two dims only
 };
 
 int ReadNnet(const char *path, std::vector<HostLayer> *layers);

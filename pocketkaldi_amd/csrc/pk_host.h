@@ -139,6 +139,7 @@ struct pk_mi355_am {
   float *d_blob = nullptr;
   size_t blob_floats = 0;
   size_t logprior_off = 0;
+  std::vector<size_t> vec_off;     // by layer index: where an add / mul layer's vector lies in the blob (float offset; others 0)
   // f16x3 / f16: the operand exponents, int32 words INSIDE the blob (so the one broadcast carries them):
   // [w_exp of linear layer 0 .. n-1 | x_exp of the operand of linear layer 0 .. n-1 | 0].  The kernels read the
   // device words; h_exps mirrors them on the host (refreshed from the device after a broadcast).
