@@ -1417,6 +1417,73 @@ class Decodable:
             pass
 
 
+def _raise_last():
+    """The library's last error as a PkCodeError."""
+    raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+
+
+def _byref(spec):
+    return None if spec is None else C.byref(spec.struct())
+
+
+def _check_spec_types(transform, deltas, frontend=None):
+    """with_transform's arguments: a TransformSpec, and a DeltaSpec / FrontendSpec where one is given."""
+    for name, spec, kind in (("transform", transform, TransformSpec), ("deltas", deltas, DeltaSpec), ("frontend", frontend, FrontendSpec)):
+        if (spec is not None or kind is TransformSpec) and not isinstance(spec, kind):
+            raise TypeError("%s must be a %s, not %s" % (name, kind.__name__, type(spec).__name__))
+
+
+def _stats_route(am, global_stats):
+    """(statistics or None, True when they go to the _create_stats entries).  41 entries: the 40-dim entries, with every
+    refusal of theirs; feat_dim + 1: the entries that take the model's own dimension; anything else is refused here."""
+    if global_stats is None:
+        return None, False
+    g = _f32(global_stats)
+    if g.shape == (41,):
+        return g, False
+    dim = lib().pk_mi355_am_feat_dim(am.handle)
+    if dim > 0 and g.shape == (dim + 1,):
+        return g, True
+    raise PkError("global_stats must have 41 entries, or feat_dim + 1 = %d for this model (got %s)"
+                  % (dim + 1, "x".join(str(n) for n in g.shape)))
+
+
+def _create_scorer(live, audio, am, global_stats, count, capacity, frontend=None, deltas=None, transform=None):
+    """The handle of a scorer: the one choice among the library's create entries.  live: an online scorer of `count` slots,
+    else a batch of `count` utterances; audio: `capacity` in samples and a front-end (the default FrontendSpec when deltas
+    or a transform come without one), else in frames and global_stats may be None."""
+    L = lib()
+    count, capacity = int(count), int(capacity)
+    if transform is not None or deltas is not None or frontend is not None:
+        g = _f32(global_stats) if audio or global_stats is not None else None
+        if audio and frontend is None:
+            frontend = FrontendSpec()
+        if transform is not None:
+            make, specs = (L.pk_mi355_transform_stream_create if live else L.pk_mi355_transform_batch_create), (transform, deltas, frontend)
+        elif deltas is not None:
+            make, specs = (L.pk_mi355_deltas_stream_create if live else L.pk_mi355_deltas_batch_create), (deltas, frontend)
+        else:
+            make, specs = (L.pk_mi355_frontend_stream_create if live else L.pk_mi355_frontend_batch_create), (frontend,)
+        stats = (None, 0) if g is None else (_fp(g.ravel()), g.size)
+        h = make(am.handle, *[_byref(spec) for spec in specs], *stats, count, capacity)
+    elif audio:                             # the reference's 40-bin front-end and 41 statistics
+        g = _f32(global_stats)
+        if g.shape != (41,):
+            raise PkError("global_stats must have 41 entries")
+        h = (L.pk_mi355_stream_create if live else L.pk_mi355_batch_create)(am.handle, _fp(g), count, capacity)
+        if not h and not live:              # (a BatchScorer's oldest failures carry no code)
+            raise PkError(L.pk_mi355_last_error().decode())
+    else:
+        g, own_dim = _stats_route(am, global_stats)
+        if own_dim:
+            h = (L.pk_mi355_features_stream_create_stats if live else L.pk_mi355_features_batch_create_stats)(am.handle, _fp(g), g.shape[0], count, capacity)
+        else:
+            h = (L.pk_mi355_features_stream_create if live else L.pk_mi355_features_batch_create)(am.handle, None if g is None else _fp(g), count, capacity)
+    if not h:
+        _raise_last()
+    return h
+
+
 class BatchScorer:
     """Many utterances in flight: PCM -> fbank -> CMVN -> nnet -> log-likelihoods, all in HBM."""
 
@@ -1427,34 +1494,9 @@ class BatchScorer:
         the statistics and the normalisation are then at base_dim() = feat_dim / (order + 1).
         transform: a TransformSpec (pk_mi355_transform_batch_create) whose out_dim is the model's feat_dim: the front-end,
         the statistics and the normalisation are then at base_dim() = in_dim() / (order + 1), in_dim() without deltas."""
-        g = _f32(global_stats)
         self._am = am
         self._keep = None
-        if transform is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_transform_batch_create(am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()),
-                                                            C.byref(fe.struct()), _fp(g.ravel()), g.size, int(max_utts), int(max_total_samples))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if deltas is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
-                                                         int(max_utts), int(max_total_samples))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if frontend is not None:
-            self._h = lib().pk_mi355_frontend_batch_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
-                                                           int(max_utts), int(max_total_samples))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if g.shape != (41,):
-            raise PkError("global_stats must have 41 entries")
-        self._h = lib().pk_mi355_batch_create(am.handle, _fp(g), int(max_utts), int(max_total_samples))
-        if not self._h:
-            raise PkError(lib().pk_mi355_last_error().decode())
+        self._h = _create_scorer(False, True, am, global_stats, max_utts, max_total_samples, frontend, deltas, transform)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1626,21 +1668,6 @@ class BatchScorer:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KINDS)}
 
 
-def _stats_route(am, global_stats):
-    """(statistics or None, True when they go to the _create_stats entries).  41 entries: the 40-dim entries, with every
-    refusal of theirs; feat_dim + 1: the entries that take the model's own dimension; anything else is refused here."""
-    if global_stats is None:
-        return None, False
-    g = _f32(global_stats)
-    if g.shape == (41,):
-        return g, False
-    dim = lib().pk_mi355_am_feat_dim(am.handle)
-    if dim > 0 and g.shape == (dim + 1,):
-        return g, True
-    raise PkError("global_stats must have 41 entries, or feat_dim + 1 = %d for this model (got %s)"
-                  % (dim + 1, "x".join(str(n) for n in g.shape)))
-
-
 class FeatureScorer(BatchScorer):
     """A BatchScorer without a front-end, fed by set_features / set_features_device: any model (any feature
     dimension), capacity in frames.  global_stats (feat_dim sums, then the count: 41 floats for a 40-dim model)
@@ -1652,29 +1679,7 @@ class FeatureScorer(BatchScorer):
         transform: a TransformSpec (pk_mi355_transform_batch_create without a front-end), alone or behind deltas."""
         self._am = am
         self._keep = None
-        if transform is not None:
-            g = None if global_stats is None else _f32(global_stats)
-            self._h = lib().pk_mi355_transform_batch_create(am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()),
-                                                            None, None if g is None else _fp(g.ravel()), 0 if g is None else g.size, int(max_utts),
-                                                            int(max_total_frames))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if deltas is not None:
-            g = None if global_stats is None else _f32(global_stats)
-            self._h = lib().pk_mi355_deltas_batch_create(am.handle, C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
-                                                         0 if g is None else g.size, int(max_utts), int(max_total_frames))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        g, own_dim = _stats_route(am, global_stats)
-        if own_dim:
-            self._h = lib().pk_mi355_features_batch_create_stats(am.handle, _fp(g), g.shape[0], int(max_utts), int(max_total_frames))
-        else:
-            self._h = lib().pk_mi355_features_batch_create(am.handle, None if g is None else _fp(g), int(max_utts), int(max_total_frames))
-        if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-        self._keep = None
+        self._h = _create_scorer(False, False, am, global_stats, max_utts, max_total_frames, None, deltas, transform)
 
 
 class OnlineScorer:
@@ -1690,28 +1695,10 @@ class OnlineScorer:
         deltas: a DeltaSpec (pk_mi355_deltas_stream_create): the front-end (the default FrontendSpec when none is given),
         the statistics, the normalisation and "raw" slots are then at base_dim() = feat_dim / (order + 1), and a live
         slot looks order * window + R frames ahead."""
-        g = _f32(global_stats)
         self._am = am
         self._max_streams = int(max_streams)
         self._has_deltas = deltas is not None
-        if deltas is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_deltas_stream_create(am.handle, C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
-                                                          int(max_streams), int(max_step_samples))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if frontend is not None:
-            self._h = lib().pk_mi355_frontend_stream_create(am.handle, C.byref(frontend.struct()), _fp(g.ravel()), g.size,
-                                                            int(max_streams), int(max_step_samples))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        if g.shape != (41,):
-            raise PkError("global_stats must have 41 entries")
-        self._h = lib().pk_mi355_stream_create(am.handle, _fp(g), int(max_streams), int(max_step_samples))
-        if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self._h = _create_scorer(True, True, am, global_stats, max_streams, max_step_samples, frontend, deltas)
 
     @classmethod
     def with_transform(cls, am, global_stats, max_streams, max_step_samples, transform, frontend=None, deltas=None):
@@ -1719,22 +1706,11 @@ class OnlineScorer:
         DeltaSpec is given: the front-end (the default FrontendSpec when none is given), the statistics, the normalisation
         and "raw" slots are then at base_dim() = in_dim() / (order + 1), and a live slot looks order * window +
         right_context + R frames ahead.  set_slot_transform hands an open slot its own matrix."""
-        if not isinstance(transform, TransformSpec):
-            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
-        if deltas is not None and not isinstance(deltas, DeltaSpec):
-            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
-        if frontend is not None and not isinstance(frontend, FrontendSpec):
-            raise TypeError("frontend must be a FrontendSpec, not %s" % type(frontend).__name__)
-        g = _f32(global_stats)
-        fe = FrontendSpec() if frontend is None else frontend
-        return cls._made_with_transform(am, max_streams, lib().pk_mi355_transform_stream_create(
-            am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()), C.byref(fe.struct()), _fp(g.ravel()), g.size,
-            int(max_streams), int(max_step_samples)))
+        _check_spec_types(transform, deltas, frontend)
+        return cls._made_with_transform(am, max_streams, _create_scorer(True, True, am, global_stats, max_streams, max_step_samples, frontend, deltas, transform))
 
     @classmethod
     def _made_with_transform(cls, am, max_streams, handle):
-        if not handle:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self = cls.__new__(cls)
         self._am = am
         self._max_streams = int(max_streams)
@@ -1886,33 +1862,14 @@ class OnlineFeatureScorer(OnlineScorer):
         self._am = am
         self._max_streams = int(max_streams)
         self._has_deltas = deltas is not None
-        if deltas is not None:
-            g = None if global_stats is None else _f32(global_stats)
-            self._h = lib().pk_mi355_deltas_stream_create(am.handle, C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
-                                                          0 if g is None else g.size, int(max_streams), int(max_step_frames))
-            if not self._h:
-                raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
-            return
-        g, own_dim = _stats_route(am, global_stats)
-        if own_dim:
-            self._h = lib().pk_mi355_features_stream_create_stats(am.handle, _fp(g), g.shape[0], int(max_streams), int(max_step_frames))
-        else:
-            self._h = lib().pk_mi355_features_stream_create(am.handle, None if g is None else _fp(g), int(max_streams), int(max_step_frames))
-        if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self._h = _create_scorer(True, False, am, global_stats, max_streams, max_step_frames, None, deltas)
 
     @classmethod
     def with_transform(cls, am, max_streams, max_step_frames, transform, global_stats=None, deltas=None):
         """OnlineScorer.with_transform without a front-end: "raw" slots take [n][base_dim()] frames, and global_stats, when
         given, holds base_dim() sums and the count."""
-        if not isinstance(transform, TransformSpec):
-            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
-        if deltas is not None and not isinstance(deltas, DeltaSpec):
-            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
-        g = None if global_stats is None else _f32(global_stats)
-        return cls._made_with_transform(am, max_streams, lib().pk_mi355_transform_stream_create(
-            am.handle, C.byref(transform.struct()), None if deltas is None else C.byref(deltas.struct()), None, None if g is None else _fp(g.ravel()),
-            0 if g is None else g.size, int(max_streams), int(max_step_frames)))
+        _check_spec_types(transform, deltas)
+        return cls._made_with_transform(am, max_streams, _create_scorer(True, False, am, global_stats, max_streams, max_step_frames, None, deltas, transform))
 
 
 class PkCodeError(PkError):
@@ -2230,7 +2187,7 @@ class OnlineDecoder:
         self._fst, self._am = fst, am
         self._h = lib().pk_mi355_online_decoder_create(fst.handle, am.handle, int(max_streams), int(trace_capacity))
         if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            _raise_last()
         self._keep = None
 
     def destroy(self):
@@ -2374,7 +2331,7 @@ class SymbolTable:
         self._owner = None
         self._h = lib().pk_mi355_symtab_read(os.fspath(path).encode())
         if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            _raise_last()
 
     @classmethod
     def _borrowed(cls, handle, owner):
@@ -2417,6 +2374,27 @@ class _Borrowed:
         return self
 
 
+def _load_recognizer(live, config, precision, count, capacity, trace_capacity, frontend=None, deltas=None, transform=None):
+    """The handle of a Recognizer (live: of an OnlineRecognizer, which takes no precision): the one choice among the
+    library's load entries; the default FrontendSpec when deltas or a transform come without a front-end."""
+    L = lib()
+    if frontend is None and (deltas is not None or transform is not None):
+        frontend = FrontendSpec()
+    if transform is not None:
+        load, specs = (L.pk_mi355_transform_online_recognizer_load if live else L.pk_mi355_transform_recognizer_load), (frontend, deltas, transform)
+    elif deltas is not None:
+        load, specs = (L.pk_mi355_deltas_online_recognizer_load if live else L.pk_mi355_deltas_recognizer_load), (frontend, deltas)
+    elif frontend is not None:
+        load, specs = (L.pk_mi355_frontend_online_recognizer_load if live else L.pk_mi355_frontend_recognizer_load), (frontend,)
+    else:
+        load, specs = (L.pk_mi355_online_recognizer_load if live else L.pk_mi355_recognizer_load), ()
+    h = load(os.fspath(config).encode(), *[_byref(spec) for spec in specs], *([] if live else [AcousticModel.PRECISIONS[precision]]),
+             int(count), int(capacity), int(trace_capacity))
+    if not h:
+        _raise_last()
+    return h
+
+
 class Recognizer:
     """pk_load + pk_process (pocketkaldi.cc:72-248): the model file's graph, symbol table and acoustic model, a batch
     scorer and a decoder with alignment on.  .am / .batch / .decoder / .symbols are the owned objects (beam, trace gc,
@@ -2429,26 +2407,7 @@ class Recognizer:
         the front-end's (pk_mi355_deltas_recognizer_load; the default FrontendSpec when only deltas is given).
         transform: a TransformSpec, alone or behind deltas; the model file is then one of the transform's out_dim whose
         cmvn_stats are at the front-end's dimension (pk_mi355_transform_recognizer_load)."""
-        if transform is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_transform_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()),
-                                                               None if deltas is None else C.byref(deltas.struct()), C.byref(transform.struct()),
-                                                               AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
-                                                               int(trace_capacity))
-        elif deltas is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_deltas_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()), C.byref(deltas.struct()),
-                                                            AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
-                                                            int(trace_capacity))
-        elif frontend is not None:
-            self._h = lib().pk_mi355_frontend_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()),
-                                                              AcousticModel.PRECISIONS[precision], int(max_utts), int(max_total_samples),
-                                                              int(trace_capacity))
-        else:
-            self._h = lib().pk_mi355_recognizer_load(os.fspath(config).encode(), AcousticModel.PRECISIONS[precision], int(max_utts),
-                                                     int(max_total_samples), int(trace_capacity))
-        if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+        self._h = _load_recognizer(False, config, precision, max_utts, max_total_samples, trace_capacity, frontend, deltas, transform)
         self.max_utts, self.max_total_samples = int(max_utts), int(max_total_samples)
         L = lib()
         self.am = _Borrowed.of(AcousticModel, L.pk_mi355_recognizer_am(self._h), self)
@@ -2576,16 +2535,7 @@ class OnlineRecognizer:
         (pk_mi355_frontend_online_recognizer_load).
         deltas: a DeltaSpec; the model file is then one of (order + 1) x the front-end's dimension whose cmvn_stats are at
         the front-end's (pk_mi355_deltas_online_recognizer_load; the default FrontendSpec when only deltas is given)."""
-        if deltas is not None:
-            fe = FrontendSpec() if frontend is None else frontend
-            self._h = lib().pk_mi355_deltas_online_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()), C.byref(deltas.struct()),
-                                                                   int(max_streams), int(max_step_samples), int(trace_capacity))
-        elif frontend is not None:
-            self._h = lib().pk_mi355_frontend_online_recognizer_load(os.fspath(config).encode(), C.byref(frontend.struct()), int(max_streams),
-                                                                     int(max_step_samples), int(trace_capacity))
-        else:
-            self._h = lib().pk_mi355_online_recognizer_load(os.fspath(config).encode(), int(max_streams), int(max_step_samples),
-                                                            int(trace_capacity))
+        self._h = _load_recognizer(True, config, None, max_streams, max_step_samples, trace_capacity, frontend, deltas)
         self._adopt(max_streams, max_step_samples, deltas is not None)
 
     @classmethod
@@ -2594,24 +2544,14 @@ class OnlineRecognizer:
         file is one of the transform's output dimension whose cmvn_stats are at the front-end's (the default FrontendSpec
         when none is given).  A slot's own matrix: self.scorer.set_slot_transform(slot, matrix) once the slot is open; with
         endpointing every utterance cut from that opening uses it."""
-        if not isinstance(transform, TransformSpec):
-            raise TypeError("transform must be a TransformSpec, not %s" % type(transform).__name__)
-        if deltas is not None and not isinstance(deltas, DeltaSpec):
-            raise TypeError("deltas must be a DeltaSpec, not %s" % type(deltas).__name__)
-        if frontend is not None and not isinstance(frontend, FrontendSpec):
-            raise TypeError("frontend must be a FrontendSpec, not %s" % type(frontend).__name__)
-        fe = FrontendSpec() if frontend is None else frontend
+        _check_spec_types(transform, deltas, frontend)
         self = cls.__new__(cls)
-        self._h = lib().pk_mi355_transform_online_recognizer_load(os.fspath(config).encode(), C.byref(fe.struct()),
-                                                                  None if deltas is None else C.byref(deltas.struct()), C.byref(transform.struct()),
-                                                                  int(max_streams), int(max_step_samples), int(trace_capacity))
+        self._h = _load_recognizer(True, config, None, max_streams, max_step_samples, trace_capacity, frontend, deltas, transform)
         self._adopt(max_streams, max_step_samples, True)
         return self
 
     def _adopt(self, max_streams, max_step_samples, base_dim_slots):
         """The owned objects of a loaded recognizer.  base_dim_slots: "raw" slots are the scorer's base_dim() wide."""
-        if not self._h:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
         self.max_streams, self.max_step_samples = int(max_streams), int(max_step_samples)
         L = lib()
         self.am = _Borrowed.of(AcousticModel, L.pk_mi355_online_recognizer_am(self._h), self)
@@ -2680,14 +2620,14 @@ class OnlineRecognizer:
         """The slot's current hypothesis as text (valid until the next step)."""
         s = lib().pk_mi355_online_recognizer_partial(self._h, int(slot))
         if s is None:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            _raise_last()
         return s.decode()
 
     def stable(self, slot):
         """The words of partial(slot) that are final now, as text; "" unless decoder.set_commit(True) was called."""
         s = lib().pk_mi355_online_recognizer_stable(self._h, int(slot))
         if s is None:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            _raise_last()
         return s.decode()
 
     def finished(self, slot):
@@ -2697,7 +2637,7 @@ class OnlineRecognizer:
         """The Result of a finished slot: what Recognizer.process gives on the whole wave."""
         text = lib().pk_mi355_online_recognizer_hyp(self._h, int(slot))
         if text is None:
-            raise PkCodeError(lib().pk_mi355_last_error_code(), lib().pk_mi355_last_error().decode())
+            _raise_last()
         words, weight, ok = self.decoder.result(slot)
         return Result(text.decode(), words, weight, ok,
                       lib().pk_mi355_online_recognizer_loglikelihood_per_frame(self._h, int(slot)),

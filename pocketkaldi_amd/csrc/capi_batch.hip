@@ -499,32 +499,24 @@ int64_t PublicChunkCap() {
   return e && atol(e) >= kTile ? RoundUp(atol(e), kTileF16) : 262144;
 }
 
-// A batch as CreateBatch makes it, arguments checked.  stats: null (a features-only batch), or the base dimension's sums
-// and the count -- the base dimension is the model's divided by deltas->order + 1, the model's own without deltas.
-// max_samples PCM samples (0: features only), max_frames frames, passes of at most chunk_cap frames.
-struct BatchSpec {
-  const float *stats; int max_utts; int64_t max_samples, max_frames, chunk_cap;
-  const FrontendAnyTables *any;             // the tables of a front-end spec of the base dimension, or null
-  const pk_mi355_deltas_spec_t *deltas;     // or null
-  const pk_mi355_transform_spec_t *xform = nullptr;      // a checked transform spec: the base dimension is then in_dim / (order + 1)
-};
-// Every way to a batch.
-pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
+// Every way to a batch: the request and what its checks worked out (SingleBatch: through no check).  max_samples PCM
+// samples (0: features only), max_frames frames, passes of at most chunk_cap frames.
+pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const CreateRequest &r, const CreateDims &dims) {
   if (UseDevice(am->device)) return nullptr;
-  const pk_mi355_deltas_spec_t *deltas = spec.deltas;
+  const pk_mi355_deltas_spec_t *deltas = r.deltas;
+  const int64_t max_frames = r.audio ? r.capacity / kFrameShift + r.units : r.capacity;
   pk_mi355_batch *b = new pk_mi355_batch();
   ScorerCore &c = b->core;
-  b->max_utts = spec.max_utts; b->max_samples = spec.max_samples;
-  b->features_only = spec.max_samples == 0;
-  b->have_stats = spec.stats != nullptr;
+  b->max_utts = r.units; b->max_samples = r.audio ? r.capacity : 0;
+  b->features_only = !r.audio;
+  b->have_stats = r.stats != nullptr;
   b->has_deltas = deltas != nullptr;
   if (deltas) b->deltas = *deltas;
-  b->is_xform = spec.xform != nullptr;
-  b->in_dim = spec.xform ? spec.xform->in_dim : am->feat_dim;
-  b->base_dim = deltas ? b->in_dim / (deltas->order + 1) : b->in_dim;
+  b->is_xform = r.xform != nullptr;
+  b->in_dim = dims.in_dim; b->base_dim = dims.base_dim;
   const int pad = am->left + am->right;
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
-  CreateScorerCore(&c, am, spec.stats, b->base_dim, spec.max_utts, spec.max_frames, spec.max_frames, spec.chunk_cap, chk);
+  CreateScorerCore(&c, am, r.stats, b->base_dim, r.units, max_frames, max_frames, r.chunk_cap ? r.chunk_cap : PublicChunkCap(), chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
   // the utterances before it of T + pad - RoundUp(T, 4), which goes negative once pad < 3 (pad = 0: after any length that
   // is not a multiple of four), and the rows can then outnumber the columns every buffer is sized for.  The kernels add
@@ -533,30 +525,17 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   // save anyway: such models keep row = column of Yt.
   b->compact = pad >= 3;
   if (const char *e = getenv("PK_MI355_COMPACT_ROWS")) b->compact = b->compact && atoi(e) != 0;    // (A/B switch: 0 = row = column of Yt)
-  const size_t lay_bytes = RoundUp(kLayoutEntry * spec.max_utts, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
+  const size_t lay_bytes = RoundUp(kLayoutEntry * r.units, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
   chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
   chk(hipMalloc(&b->d_lay, lay_bytes));
   chk(hipEventCreateWithFlags(&b->ev_layout, hipEventDisableTiming));
-  if (spec.any) UploadSpecTables(&c, spec.any, &b->d_any, chk);
-  if (spec.xform && pkxf::HasMatrix(*spec.xform)) {     // TransformKernel's global matrix, transposed and padded (before the plan below is asked for its rows)
-    const pk_mi355_transform_spec_t &x = *spec.xform;
-    std::vector<float> packed((size_t)x.cols * pkxf::Ldo(x.rows));
-    pkxf::PackTransposed(x.matrix, x.rows, x.cols, packed.data());
-    float *d_mt = nullptr;
-    chk(hipMalloc(&d_mt, sizeof(float) * packed.size()));
-    if (chk.ok) chk(hipMemcpy(d_mt, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-    b->xform = pkmi::TransformStage{x.in_dim, x.left_context, x.right_context, x.rows, pkxf::Affine(x), d_mt, 0};
-  }
+  if (dims.any()) UploadSpecTables(&c, dims.any(), &b->d_any, chk);
+  // TransformKernel's global matrix (before the plan below is asked for its rows)
+  if (r.xform && pkxf::HasMatrix(*r.xform)) b->xform = UploadTransform(*r.xform, chk);
   // The rows of the SLIDING plan of an object with statistics; every other plan's are made by the set call that brings it
   // about.  A wave batch has no such call for its audio (everything now); a features-only one gets its raw rows.
   if (b->have_stats) chk(EnsureBuffers(b, b->features_only ? pkplan::kRawRows : BuffersFor(b, pkplan::kWaves, PK_MI355_NORM_SLIDING)));
-  if (deltas) {     // DeltaKernel's table
-    float table[pkdelta::kMaxTable];
-    pkdelta::BuildScales(*deltas, table);
-    const size_t bytes = sizeof(float) * (size_t)(deltas->order + 1) * pkdelta::RowLen(*deltas);
-    chk(hipMalloc(&b->d_delta_scales, bytes));
-    if (chk.ok) chk(hipMemcpy(b->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
-  }
+  if (deltas) b->d_delta_scales = UploadDeltaScales(*deltas, chk);     // DeltaKernel's table
   if (IsF16(am->precision)) chk(hipMalloc(&b->d_y2, sizeof(_Float16) * 2 * c.ldy * am->feat_dim));
   if (const char *e = getenv("PK_MI355_LANES")) b->lanes = atoi(e) >= 2 ? 2 : 1;
   if (c.max_cols <= c.chunk) b->lanes = 1;           // a single chunk has nothing to overlap with
@@ -568,15 +547,6 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const BatchSpec &spec) {
   }
   if (!chk.ok) { pk_mi355_batch_destroy(b); return nullptr; }
   return b;
-}
-
-// Every public create entry: the shared checks (pkhost::CheckCreate, below), then the batch.
-pk_mi355_batch *CheckedBatch(pk_mi355_am_t *am, const BatchRequest &r) {
-  std::vector<FrontendAnyTables> any;
-  int Db = 0;
-  if (!CheckCreate(am, r, &any, &Db)) return nullptr;
-  return CreateBatch(am, BatchSpec{r.stats, r.max_utts, r.audio ? r.capacity : 0, r.audio ? r.capacity / kFrameShift + r.max_utts : r.capacity,
-                                   PublicChunkCap(), r.frontend ? any.data() : nullptr, r.deltas, r.xform});
 }
 
 // am->mu held.  One of the model's own one-utterance scorers for a call of `need` samples or frames: kept while the call
@@ -593,14 +563,10 @@ pk_mi355_batch *EnsureOwned(OwnedBatch *o, int64_t need, bool keep, Make make) {
 }  // namespace
 
 namespace pkhost {
-// The argument checks of every public create entry (pk_score.h), in the one order that names the fault each of them has
-// always named, also when several arguments are bad at once; an entry runs those its request gives rise to.
-bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi::FrontendAnyTables> *any_out, int *base_dim) {
-  std::vector<pkmi::FrontendAnyTables> &any = *any_out;
-  if (!am || (!r.live && !am->finalized)) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
-  if (r.null_arg) { Fail(PK_MI355_E_INVALID, "null argument"); return false; }
-  if (r.deltas && pkdelta::CheckSpec(r.deltas)) return false;         // (names the field)
-  if (r.xform && pkxf::CheckSpec(r.xform)) return false;              // (names the field)
+// The argument checks of every public create entry of both scorers (pk_score.h), in the one order of DESIGN.md section
+// 28, also when several arguments are bad at once; an entry runs those its request gives rise to.
+bool CheckCreate(const pk_mi355_am *am, const CreateRequest &r, CreateDims *dims) {
+  if (!CheckRequestArgs(am && (r.live || am->finalized), r, dims)) return false;      // the model, null arguments, the specs
   if (r.live) {                      // an online scorer: the model is looked at from here on, so the above is said without a device
     if (am->precision != PK_MI355_PRECISION_F32) {
       Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
@@ -620,21 +586,23 @@ bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi:
     return false;
   }
   const int Db = Din / (order + 1);
-  any.assign(r.frontend ? 1 : 0, pkmi::FrontendAnyTables());
-  if (r.frontend && BuildFrontendAnyTables(r.frontend, any.data())) return false;      // (names the field)
-  if (r.xform && r.audio && any[0].dim != Db) {
-    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the transform's in_dim %d with %d delta blocks needs %d", any[0].dim, Din,
+  if (!r.live && !BuildRequestTables(r, dims)) return false;      // (a batch entry names a bad front-end spec here)
+  const int front_dim = r.frontend ? dims->any()->dim : kNumBins;
+  if (r.xform && r.audio && front_dim != Db) {
+    Fail(PK_MI355_E_INVALID, "the front-end spec produces %d-dim features, the transform's in_dim %d with %d delta blocks needs %d", front_dim, Din,
          order + 1, Db);
     return false;
   }
-  if (!r.xform && r.audio && !FrontendFits(r.frontend ? any[0].dim : kNumBins, r.frontend != nullptr, am, Db, order)) return false;
+  if (!r.xform && r.audio && !FrontendFits(front_dim, r.frontend != nullptr, am, Db, order)) return false;
   if (r.stats && !r.stats41 && !StatsLenFits(r.stats_len, Db, r.deltas != nullptr || r.xform != nullptr)) return false;
   if (r.xform && pkxf::OutDim(*r.xform) != D) {
     Fail(PK_MI355_E_INVALID, "the transform produces %d-dim features, the model expects %d", pkxf::OutDim(*r.xform), D);
     return false;
   }
-  // (pk_mi355_batch_create, the one audio entry without a spec, has always named its missing statistics here)
-  if (r.max_utts <= 0 || r.capacity <= 0 || (r.audio && !r.frontend && !r.stats)) {
+  // The one place where capacity is refused.  An audio object without statistics has always been named so (only
+  // pk_mi355_batch_create and pk_mi355_stream_create can ask for one); a live step's staging is indexed in 32 bits.
+  const bool no_stats = r.audio && !r.stats && (r.live || !r.frontend);
+  if (r.units <= 0 || r.capacity <= 0 || no_stats || (r.live && r.capacity > ((int64_t)1 << 30) / (r.audio ? 1 : std::max(D, Db)))) {
     Fail(PK_MI355_E_INVALID, r.live ? "bad stream capacity" : "bad batch capacity");
     return false;
   }
@@ -646,39 +614,70 @@ bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi:
     Fail(PK_MI355_E_INVALID, "f16x3 / f16 precision needs a feature dimension that is a multiple of 8 (got %d)", D);
     return false;
   }
-  *base_dim = Db;
+  dims->in_dim = Din; dims->base_dim = Db;
   return true;
 }
 
+pk_mi355_batch *CheckedBatch(pk_mi355_am *am, const CreateRequest &r) {
+  CreateDims dims;
+  return CheckCreate(am, r, &dims) ? CreateBatch(am, r, dims) : nullptr;
+}
+
+float *UploadDeltaScales(const pk_mi355_deltas_spec_t &deltas, CreateCheck &chk) {
+  float table[pkdelta::kMaxTable], *d_scales = nullptr;
+  pkdelta::BuildScales(deltas, table);
+  const size_t bytes = sizeof(float) * (size_t)(deltas.order + 1) * pkdelta::RowLen(deltas);
+  chk(hipMalloc(&d_scales, bytes));
+  if (chk.ok) chk(hipMemcpy(d_scales, table, bytes, hipMemcpyHostToDevice));
+  return d_scales;
+}
+
+pkmi::TransformStage UploadTransform(const pk_mi355_transform_spec_t &x, CreateCheck &chk) {
+  pkmi::TransformStage stage{x.in_dim, x.left_context, x.right_context, pkxf::OutDim(x), false, nullptr, 0};
+  if (!pkxf::HasMatrix(x)) return stage;
+  std::vector<float> packed((size_t)x.cols * pkxf::Ldo(x.rows));
+  pkxf::PackTransposed(x.matrix, x.rows, x.cols, packed.data());
+  float *d_mt = nullptr;
+  chk(hipMalloc(&d_mt, sizeof(float) * packed.size()));
+  if (chk.ok) chk(hipMemcpy(d_mt, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+  stage.affine = pkxf::Affine(x); stage.mt = d_mt;
+  return stage;
+}
+
 pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames) {      // (at least one whole pass: every pass is kSingleChunk rows)
-  return EnsureOwned(&am->single, std::max(frames, kSingleChunk), true,
-                     [&](int64_t cap) { return CreateBatch(am, BatchSpec{nullptr, 1, 0, cap, kSingleChunk, nullptr, nullptr}); });
+  return EnsureOwned(&am->single, std::max(frames, kSingleChunk), true, [&](int64_t cap) {
+    CreateRequest r{nullptr, 0, false, 1, cap, false, false, nullptr, nullptr};
+    r.chunk_cap = kSingleChunk;
+    CreateDims dims;
+    dims.in_dim = dims.base_dim = am->feat_dim;
+    return CreateBatch(am, r, dims);
+  });
 }
 }  // namespace pkhost
 
 extern "C" {
 
 pk_mi355_batch_t *pk_mi355_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_samples) {
-  return CheckedBatch(am, BatchRequest{global_stats41, 0, true, max_utts, max_total_samples, true, false, nullptr, nullptr});
+  return CheckedBatch(am, CreateRequest{global_stats41, 0, true, max_utts, max_total_samples, true, false, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_features_batch_create(pk_mi355_am_t *am, const float *global_stats41, int max_utts, int64_t max_total_frames) {
-  return CheckedBatch(am, BatchRequest{global_stats41, 0, true, max_utts, max_total_frames, false, false, nullptr, nullptr});
+  return CheckedBatch(am, CreateRequest{global_stats41, 0, true, max_utts, max_total_frames, false, false, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_features_batch_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_utts,
                                                        int64_t max_total_frames) {
-  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, max_total_frames, false, !global_stats, nullptr, nullptr});
+  return CheckedBatch(am, CreateRequest{global_stats, stats_len, false, max_utts, max_total_frames, false, !global_stats, nullptr, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_frontend_batch_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
                                                  int stats_len, int max_utts, int64_t max_total_samples) {
-  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, max_total_samples, true, !spec || !global_stats, spec, nullptr});
+  return CheckedBatch(am, CreateRequest{global_stats, stats_len, false, max_utts, max_total_samples, true, !spec || !global_stats, spec, nullptr});
 }
 
 pk_mi355_batch_t *pk_mi355_deltas_batch_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
                                                const float *global_stats, int stats_len, int max_utts, int64_t capacity) {
-  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !deltas || (frontend && !global_stats),
+  return CheckedBatch(am, CreateRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !deltas || (frontend && !global_stats),
                                        frontend, deltas});
 }
 
@@ -687,7 +686,7 @@ int pk_mi355_deltas_base_dim(const pk_mi355_batch_t *b) { return b ? b->base_dim
 pk_mi355_batch_t *pk_mi355_transform_batch_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform, const pk_mi355_deltas_spec_t *deltas,
                                                   const pk_mi355_frontend_spec_t *frontend, const float *global_stats, int stats_len, int max_utts,
                                                   int64_t capacity) {
-  return CheckedBatch(am, BatchRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !transform || (frontend && !global_stats),
+  return CheckedBatch(am, CreateRequest{global_stats, stats_len, false, max_utts, capacity, frontend != nullptr, !transform || (frontend && !global_stats),
                                        frontend, deltas, transform});
 }
 
@@ -1283,7 +1282,7 @@ int pk_mi355_process_acoustic(pk_mi355_am_t *am, const pk_vector_t *cmvn_global_
   std::lock_guard<std::mutex> lock(am->mu);
   const float *stats = cmvn_global_stats->data;
   pk_mi355_batch *b = EnsureOwned(&am->proc, std::max<int64_t>(raw_wave->dim, 16000), memcmp(am->proc_stats, stats, sizeof(am->proc_stats)) == 0,
-                                  [&](int64_t cap) { return pk_mi355_batch_create(am, stats, 1, cap); });
+                                  [&](int64_t cap) { return CheckedBatch(am, CreateRequest{stats, 0, true, 1, cap, true, false, nullptr, nullptr}); });
   if (!b) return PK_MI355_E_DEVICE;
   memcpy(am->proc_stats, stats, sizeof(am->proc_stats));
   int rc = pk_mi355_batch_set_waves(b, raw_wave, 1);

@@ -7,7 +7,7 @@
 #include <utility>
 #include <vector>
 
-#include "pk_host.h"
+#include "pk_score.h"
 
 using namespace pkhost;
 
@@ -182,30 +182,21 @@ void pk_mi355_online_recognizer_destroy(pk_mi355_online_recognizer_t *r) {
 }  // extern "C"
 
 namespace {
-// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
-pk_mi355_online_recognizer_t *LoadOnlineRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int max_streams,
-                                                   int64_t max_step_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr,
-                                                   const pk_mi355_transform_spec_t *xform = nullptr) {
+// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (deltas, xform: as
+// capi_recognizer.hip's LoadRecognizer).  The online scorer runs f32 models only.
+pk_mi355_online_recognizer_t *LoadOnlineRecognizer(int required, const char *config_path, const pk_mi355_frontend_spec_t *spec,
+                                                   const pk_mi355_deltas_spec_t *deltas, const pk_mi355_transform_spec_t *xform, int max_streams,
+                                                   int64_t max_step_samples, int64_t trace_capacity) {
+  if (!CheckLoadArgs(config_path, required, spec, deltas, xform, max_streams, max_step_samples, trace_capacity, "bad online recognizer capacity"))
+    return nullptr;
   pk_mi355_online_recognizer *r = new pk_mi355_online_recognizer();
   auto failed = [&]() { pk_mi355_online_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (xform) {         // (the statistics at the transform's base dimension: pk_mi355_transform_stream_create holds them to it)
-    int stats_len = 0;
-    if (LoadStatsBlocks(config_path, PK_MI355_PRECISION_F32, 0, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->stream = pk_mi355_transform_stream_create(r->am, xform, deltas, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
-  } else if (deltas) {
-    int stats_len = 0;
-    if (LoadStatsBlocks(config_path, PK_MI355_PRECISION_F32, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->stream = pk_mi355_deltas_stream_create(r->am, deltas, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
-  } else if (spec) {
-    int stats_len = 0;
-    if (pk_mi355_load_stats(config_path, PK_MI355_PRECISION_F32, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->stream = pk_mi355_frontend_stream_create(r->am, spec, stats, stats_len, max_streams, max_step_samples))) return failed();
-  } else {
-    if (pk_mi355_load(config_path, PK_MI355_PRECISION_F32, &r->am, stats)) return failed();
-    if (!(r->stream = pk_mi355_stream_create(r->am, stats, max_streams, max_step_samples))) return failed();
-  }
+  CreateRequest req;
+  if (LoadModelAndStats(config_path, PK_MI355_PRECISION_F32, spec, deltas, xform, max_streams, max_step_samples, &r->am, stats, &req)) return failed();
+  req.live = true;
+  if (!(r->stream = CheckedStream(r->am, req))) return failed();
   if (!(r->decoder = pk_mi355_online_decoder_create(r->fst, r->am, max_streams, trace_capacity))) return failed();
   if (pk_mi355_online_decoder_set_alignment(r->decoder, 1)) return failed();
   r->max_streams = max_streams;
@@ -224,37 +215,27 @@ extern "C" {
 
 pk_mi355_online_recognizer_t *pk_mi355_online_recognizer_load(const char *config_path, int max_streams, int64_t max_step_samples,
                                                               int64_t trace_capacity) {
-  if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
-  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
-  return LoadOnlineRecognizer(config_path, nullptr, max_streams, max_step_samples, trace_capacity);
+  return LoadOnlineRecognizer(0, config_path, nullptr, nullptr, nullptr, max_streams, max_step_samples, trace_capacity);
 }
 
 pk_mi355_online_recognizer_t *pk_mi355_frontend_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec,
                                                                        int max_streams, int64_t max_step_samples, int64_t trace_capacity) {
-  if (!config_path || !spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
-  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
-  return LoadOnlineRecognizer(config_path, spec, max_streams, max_step_samples, trace_capacity);
+  return LoadOnlineRecognizer(kNeedFrontend, config_path, spec, nullptr, nullptr, max_streams, max_step_samples, trace_capacity);
 }
 
 pk_mi355_online_recognizer_t *pk_mi355_deltas_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
                                                                      const pk_mi355_deltas_spec_t *deltas_spec, int max_streams,
                                                                      int64_t max_step_samples, int64_t trace_capacity) {
-  if (!config_path || !frontend_spec || !deltas_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
-  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
-  return LoadOnlineRecognizer(config_path, frontend_spec, max_streams, max_step_samples, trace_capacity, deltas_spec);
+  return LoadOnlineRecognizer(kNeedFrontend | kNeedDeltas, config_path, frontend_spec, deltas_spec, nullptr, max_streams, max_step_samples,
+                              trace_capacity);
 }
 
 pk_mi355_online_recognizer_t *pk_mi355_transform_online_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
                                                                         const pk_mi355_deltas_spec_t *deltas_spec,
                                                                         const pk_mi355_transform_spec_t *transform_spec, int max_streams,
                                                                         int64_t max_step_samples, int64_t trace_capacity) {
-  if (!config_path || !frontend_spec || !transform_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(frontend_spec) || (deltas_spec && pk_mi355_deltas_check(deltas_spec)) || pk_mi355_transform_check(transform_spec))
-    return nullptr;                                       // (name the field)
-  if (max_streams <= 0 || max_step_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad online recognizer capacity"); return nullptr; }
-  return LoadOnlineRecognizer(config_path, frontend_spec, max_streams, max_step_samples, trace_capacity, deltas_spec, transform_spec);
+  return LoadOnlineRecognizer(kNeedFrontend | kNeedTransform, config_path, frontend_spec, deltas_spec, transform_spec, max_streams, max_step_samples,
+                              trace_capacity);
 }
 
 pk_mi355_am_t *pk_mi355_online_recognizer_am(pk_mi355_online_recognizer_t *r) {

@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "pk_host.h"
+#include "pk_score.h"
 
 using namespace pkhost;
 
@@ -33,6 +33,19 @@ void FreeRecognizerFiles(RecognizerFiles *f) {
   pk_mi355_symtab_destroy(f->symtab);
   pk_mi355_fst_destroy(f->fst);
   f->symtab = nullptr; f->fst = nullptr;
+}
+
+int LoadModelAndStats(const char *config_path, int precision, const pk_mi355_frontend_spec_t *frontend, const pk_mi355_deltas_spec_t *deltas,
+                      const pk_mi355_transform_spec_t *xform, int units, int64_t capacity, pk_mi355_am_t **am, float *stats, CreateRequest *r) {
+  int stats_len = 0;
+  *r = CreateRequest{stats, 0, !frontend, units, capacity, true, false, frontend, deltas, xform};
+  if (!frontend) return pk_mi355_load(config_path, precision, am, stats);      // (41 statistics by that entry's contract)
+  // a transform's scorer holds the statistics to its base dimension; deltas put them at feat_dim / (order + 1)
+  const int rc = xform    ? LoadStatsBlocks(config_path, precision, 0, am, stats, kMaxCmvnStats, &stats_len)
+                 : deltas ? LoadStatsBlocks(config_path, precision, deltas->order + 1, am, stats, kMaxCmvnStats, &stats_len)
+                          : pk_mi355_load_stats(config_path, precision, am, stats, kMaxCmvnStats, &stats_len);
+  r->stats_len = stats_len;
+  return rc;
 }
 
 int JoinWords(const pk_mi355_symtab_t *symtab, const int *words, int count, std::string *text) {
@@ -71,32 +84,20 @@ void pk_mi355_recognizer_destroy(pk_mi355_recognizer_t *r) {
 }  // extern "C"
 
 namespace {
-// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension (arguments checked)
+// spec null: the reference's model file and front-end; otherwise a model of the spec's dimension
 // deltas (with a spec only): the model's features are (order + 1) x the spec's, the statistics at the spec's dimension
 // xform (with a spec only): the model's features are the transform's output, the statistics at the spec's dimension
-pk_mi355_recognizer_t *LoadRecognizer(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision, int max_utts,
-                                      int64_t max_total_samples, int64_t trace_capacity, const pk_mi355_deltas_spec_t *deltas = nullptr,
-                                      const pk_mi355_transform_spec_t *xform = nullptr) {
+pk_mi355_recognizer_t *LoadRecognizer(int required, const char *config_path, const pk_mi355_frontend_spec_t *spec, const pk_mi355_deltas_spec_t *deltas,
+                                      const pk_mi355_transform_spec_t *xform, int precision, int max_utts, int64_t max_total_samples,
+                                      int64_t trace_capacity) {
+  if (!CheckLoadArgs(config_path, required, spec, deltas, xform, max_utts, max_total_samples, trace_capacity, "bad recognizer capacity")) return nullptr;
   pk_mi355_recognizer *r = new pk_mi355_recognizer();
   auto failed = [&]() { pk_mi355_recognizer_destroy(r); return nullptr; };
   if (LoadRecognizerFiles(config_path, r, spec != nullptr)) return failed();
   float stats[kMaxCmvnStats];
-  if (xform) {
-    int stats_len = 0;
-    if (LoadStatsBlocks(config_path, precision, 0, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->batch = pk_mi355_transform_batch_create(r->am, xform, deltas, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
-  } else if (deltas) {
-    int stats_len = 0;
-    if (LoadStatsBlocks(config_path, precision, deltas->order + 1, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->batch = pk_mi355_deltas_batch_create(r->am, deltas, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
-  } else if (spec) {
-    int stats_len = 0;
-    if (pk_mi355_load_stats(config_path, precision, &r->am, stats, kMaxCmvnStats, &stats_len)) return failed();
-    if (!(r->batch = pk_mi355_frontend_batch_create(r->am, spec, stats, stats_len, max_utts, max_total_samples))) return failed();
-  } else {
-    if (pk_mi355_load(config_path, precision, &r->am, stats)) return failed();
-    if (!(r->batch = pk_mi355_batch_create(r->am, stats, max_utts, max_total_samples))) return failed();
-  }
+  CreateRequest req;
+  if (LoadModelAndStats(config_path, precision, spec, deltas, xform, max_utts, max_total_samples, &r->am, stats, &req)) return failed();
+  if (!(r->batch = CheckedBatch(r->am, req))) return failed();
   if (!(r->decoder = pk_mi355_decoder_create(r->fst, r->am, max_utts, trace_capacity))) return failed();
   if (pk_mi355_decoder_set_alignment(r->decoder, 1)) return failed();
   return r;
@@ -107,36 +108,26 @@ extern "C" {
 
 pk_mi355_recognizer_t *pk_mi355_recognizer_load(const char *config_path, int precision, int max_utts, int64_t max_total_samples,
                                                 int64_t trace_capacity) {
-  if (!config_path) { Fail(PK_MI355_E_INVALID, "null path"); return nullptr; }
-  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
-  return LoadRecognizer(config_path, nullptr, precision, max_utts, max_total_samples, trace_capacity);
+  return LoadRecognizer(0, config_path, nullptr, nullptr, nullptr, precision, max_utts, max_total_samples, trace_capacity);
 }
 
 pk_mi355_recognizer_t *pk_mi355_frontend_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *spec, int precision,
                                                          int max_utts, int64_t max_total_samples, int64_t trace_capacity) {
-  if (!config_path || !spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(spec)) return nullptr;      // (names the field)
-  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
-  return LoadRecognizer(config_path, spec, precision, max_utts, max_total_samples, trace_capacity);
+  return LoadRecognizer(kNeedFrontend, config_path, spec, nullptr, nullptr, precision, max_utts, max_total_samples, trace_capacity);
 }
 
 pk_mi355_recognizer_t *pk_mi355_deltas_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
                                                        const pk_mi355_deltas_spec_t *deltas_spec, int precision, int max_utts,
                                                        int64_t max_total_samples, int64_t trace_capacity) {
-  if (!config_path || !frontend_spec || !deltas_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(frontend_spec) || pk_mi355_deltas_check(deltas_spec)) return nullptr;      // (name the field)
-  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
-  return LoadRecognizer(config_path, frontend_spec, precision, max_utts, max_total_samples, trace_capacity, deltas_spec);
+  return LoadRecognizer(kNeedFrontend | kNeedDeltas, config_path, frontend_spec, deltas_spec, nullptr, precision, max_utts, max_total_samples,
+                        trace_capacity);
 }
 
 pk_mi355_recognizer_t *pk_mi355_transform_recognizer_load(const char *config_path, const pk_mi355_frontend_spec_t *frontend_spec,
                                                           const pk_mi355_deltas_spec_t *deltas_spec, const pk_mi355_transform_spec_t *transform_spec,
                                                           int precision, int max_utts, int64_t max_total_samples, int64_t trace_capacity) {
-  if (!config_path || !frontend_spec || !transform_spec) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pk_mi355_frontend_check(frontend_spec) || (deltas_spec && pk_mi355_deltas_check(deltas_spec)) || pk_mi355_transform_check(transform_spec))
-    return nullptr;                                       // (name the field)
-  if (max_utts <= 0 || max_total_samples <= 0 || trace_capacity < 0) { Fail(PK_MI355_E_INVALID, "bad recognizer capacity"); return nullptr; }
-  return LoadRecognizer(config_path, frontend_spec, precision, max_utts, max_total_samples, trace_capacity, deltas_spec, transform_spec);
+  return LoadRecognizer(kNeedFrontend | kNeedTransform, config_path, frontend_spec, deltas_spec, transform_spec, precision, max_utts, max_total_samples,
+                        trace_capacity);
 }
 
 pk_mi355_am_t *pk_mi355_recognizer_am(pk_mi355_recognizer_t *r) {

@@ -142,17 +142,6 @@ int SlotIndex(const pk_mi355_stream *s, int slot) {
   return 0;
 }
 
-// What every create entry checks of its model before the device is touched.
-bool ModelAllowed(const pk_mi355_am *am) {
-  if (!am) { Fail(PK_MI355_E_INVALID, "null model"); return false; }
-  if (am->precision != PK_MI355_PRECISION_F32) {
-    Fail(PK_MI355_E_INVALID, "the online scorer runs f32 models only (the f16 modes' calibration and range verdict are per batch)");
-    return false;
-  }
-  if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
-  return true;
-}
-
 // The per-slot CMVN state and the step's raw rows (audio and RAW slots), the upload staging and the step's plan.
 void CreateStepBuffers(pk_mi355_stream *s, CreateCheck &chk) {
   const ScorerCore &c = s->core;
@@ -218,30 +207,16 @@ bool StreamSlotFlushed(const pk_mi355_stream *s, int slot) { return slot >= 0 &&
 }  // namespace pkhost
 
 namespace {
-// What the create entries differ in.  entry: the name in a device failure's text.  audio: live PCM through a front-end
-// (any: the tables of a front-end spec, or null for the reference's 40 bins), step_cap in samples; else features
-// only, step_cap in frames.  stats: null (features only), or am->feat_dim sums and the count.
-// deltas: null, or the checked spec of a deltas object, whose front-end and statistics are at am->feat_dim / (order + 1).
-struct StreamShape {
-  const char *entry; bool audio; const float *stats; const FrontendAnyTables *any; int max_streams; int64_t step_cap;
-  const pk_mi355_deltas_spec_t *deltas = nullptr;
-  const pk_mi355_transform_spec_t *xform = nullptr;      // the checked spec of a transform object: base dimension in_dim / (order + 1)
-};
-
-// Every way to a stream object; the entries have checked their other arguments.
-pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
-  const int D = am->feat_dim, max_streams = sh.max_streams;
-  const int Din = sh.xform ? sh.xform->in_dim : D;      // what the deltas make, or the normaliser without them
-  const int Db = sh.deltas ? Din / (sh.deltas->order + 1) : Din;
+// Every way to a stream object: the request and what its checks worked out.  Audio: live PCM through a front-end (the
+// spec's tables, or without one the reference's 40 bins), the step capacity in samples; else features only, in frames.
+// The statistics, like a front-end, are at the base dimension.
+pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const CreateRequest &sh, const CreateDims &dims) {
+  const int D = am->feat_dim, max_streams = sh.units, Din = dims.in_dim, Db = dims.base_dim;
   const int Dw = std::max(D, Db);                       // the widest pushed frame: NORMALIZED at D, RAW at Db
-  // (pk_mi355_stream_create, the one audio entry whose statistics can still be missing here, has always named that so)
-  if (max_streams <= 0 || sh.step_cap <= 0 || sh.step_cap > ((int64_t)1 << 30) / (sh.audio ? 1 : Dw) || (sh.audio && !sh.stats)) {
-    Fail(PK_MI355_E_INVALID, "bad stream capacity");
-    return nullptr;
-  }
+  const int64_t step_cap = sh.capacity;
   if (UseDevice(am->device)) return nullptr;
   pk_mi355_stream *s = new pk_mi355_stream();
-  s->max_streams = max_streams; s->max_step_samples = sh.step_cap;
+  s->max_streams = max_streams; s->max_step_samples = step_cap;
   s->features_only = !sh.audio; s->have_stats = sh.stats != nullptr;
   s->has_deltas = sh.deltas != nullptr;
   if (sh.deltas) { s->deltas = *sh.deltas; s->reach = pkdelta::Reach(*sh.deltas); }
@@ -255,44 +230,33 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
   s->hist_len = std::max(am->left + am->right, 1);
   // Audio: a slot's segment holds at most 399 carried samples and its pushes.  A slot's rows are its new frames and the
   // (at most R) frames held back for look-ahead, padded to four.
-  s->wave_cap = sh.audio ? sh.step_cap + (int64_t)max_streams * kTailCap : 0;
-  const int64_t max_frames = sh.audio ? s->wave_cap / kFrameShift + max_streams : sh.step_cap;
+  s->wave_cap = sh.audio ? step_cap + (int64_t)max_streams * kTailCap : 0;
+  const int64_t max_frames = sh.audio ? s->wave_cap / kFrameShift + max_streams : step_cap;
   // Audio at D == 40: the fbank writes d_rows, where StreamCmvnKernel reads.  At another dimension the staging holds the
   // step's samples (a pushed frame is D <= 128 < 160 floats and counts as 160 samples), then max_frames rows of D floats.
   // With deltas the row area is there at every base dimension, its rows Db floats wide; a closing
   // slot emits up to M + R rows more than it was pushed, and the delta staging lies behind everything else.
   // A transform object likewise has a row area wherever it has a front-end; a closing slot emits up
   // to M + Rt + R rows more than it was pushed, and the transform's staging lies behind the delta staging.
-  s->rows_area = sh.audio && (D != kNumBins || sh.deltas || sh.xform) ? RoundUp(sh.step_cap, 64) : 0;
-  s->upload_cap = !sh.audio ? sh.step_cap * Dw : s->rows_area ? s->rows_area + max_frames * Db : sh.step_cap;
+  s->rows_area = sh.audio && (D != kNumBins || sh.deltas || sh.xform) ? RoundUp(step_cap, 64) : 0;
+  s->upload_cap = !sh.audio ? step_cap * Dw : s->rows_area ? s->rows_area + max_frames * Db : step_cap;
   if (sh.deltas) { s->delta_area = RoundUp(s->upload_cap, 64); s->delta_rows = max_frames + (int64_t)max_streams * M; }
   if (sh.xform) {
     s->xf_area = sh.deltas ? RoundUp(s->delta_area + s->delta_rows * Din, 64) : RoundUp(s->upload_cap, 64);
     s->xf_rows = max_frames + (int64_t)max_streams * (M + Rt);
   }
-  CreateCheck chk{sh.entry};
+  // the name a device failure is told under: the public entry such a request comes from
+  CreateCheck chk{sh.xform ? "transform_stream_create" : sh.deltas ? "deltas_stream_create" : sh.frontend ? "frontend_stream_create"
+                  : sh.audio ? "stream_create" : "features_stream_create"};
   CreateScorerCore(&s->core, am, sh.stats, Db, max_streams, max_frames, max_frames + (int64_t)max_streams * (am->right + M + Rt + 3), 262144, chk);
-  if (sh.any) UploadSpecTables(&s->core, sh.any, &s->d_any, chk);
+  if (dims.any()) UploadSpecTables(&s->core, dims.any(), &s->d_any, chk);
   CreateStepBuffers(s, chk);
   if (sh.deltas) {     // StreamDeltaKernel's table and the slots' rings
-    float table[pkdelta::kMaxTable];
-    pkdelta::BuildScales(*sh.deltas, table);
-    const size_t bytes = sizeof(float) * (size_t)(sh.deltas->order + 1) * pkdelta::RowLen(*sh.deltas);
-    chk(hipMalloc(&s->d_delta_scales, bytes));
-    if (chk.ok) chk(hipMemcpy(s->d_delta_scales, table, bytes, hipMemcpyHostToDevice));
+    s->d_delta_scales = UploadDeltaScales(*sh.deltas, chk);
     chk(hipMalloc(&s->d_delta_ring, sizeof(float) * max_streams * 2 * 2 * M * Db));      // (delta rows are Din = (order + 1) Db floats wide)
   }
-  if (sh.xform) {      // StreamTransformKernel's global matrix, transposed and padded, and the slots' rings
-    const pk_mi355_transform_spec_t &x = *sh.xform;
-    s->xf = TransformStage{x.in_dim, x.left_context, x.right_context, D, false, nullptr, 0};
-    if (pkxf::HasMatrix(x)) {
-      std::vector<float> packed((size_t)x.cols * pkxf::Ldo(x.rows));
-      pkxf::PackTransposed(x.matrix, x.rows, x.cols, packed.data());
-      float *d_mt = nullptr;
-      chk(hipMalloc(&d_mt, sizeof(float) * packed.size()));
-      if (chk.ok) chk(hipMemcpy(d_mt, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-      s->xf.affine = pkxf::Affine(x); s->xf.mt = d_mt;
-    }
+  if (sh.xform) {      // StreamTransformKernel's global matrix and the slots' rings
+    s->xf = UploadTransform(*sh.xform, chk);
     chk(hipMalloc(&s->d_xf_ring, sizeof(float) * max_streams * 2 * std::max(Ct, 1) * Din));
   }
   if (sh.audio) {
@@ -304,77 +268,44 @@ pk_mi355_stream *CreateStream(pk_mi355_am_t *am, const StreamShape &sh) {
 }
 }  // namespace
 
+pk_mi355_stream *pkhost::CheckedStream(pk_mi355_am *am, const CreateRequest &r) {
+  CreateDims dims;
+  return CheckCreate(am, r, &dims) ? CreateStream(am, r, dims) : nullptr;
+}
+
+// The entries fill a CreateRequest (pk_create.h) in its fields' order; the last two say `live`, and whether a null model
+// is "null model" (the four entries older than the deltas) or "model not finalized".
 extern "C" {
 
 pk_mi355_stream_t *pk_mi355_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_samples) {
-  if (!ModelAllowed(am) || !FrontendFits(kNumBins, false, am, am->feat_dim, 0)) return nullptr;
-  return CreateStream(am, StreamShape{"stream_create", true, global_stats41, nullptr, max_streams, max_step_samples});
+  return CheckedStream(am, CreateRequest{global_stats41, 0, true, max_streams, max_step_samples, true, false, nullptr, nullptr, nullptr, true, true});
 }
 
 pk_mi355_stream_t *pk_mi355_frontend_stream_create(pk_mi355_am_t *am, const pk_mi355_frontend_spec_t *spec, const float *global_stats,
                                                    int stats_len, int max_streams, int64_t max_step_samples) {
-  if (!am || !spec || !global_stats) { Fail(PK_MI355_E_INVALID, am ? "null argument" : "null model"); return nullptr; }
-  std::vector<FrontendAnyTables> any(1);
-  if (BuildFrontendAnyTables(spec, any.data())) return nullptr;      // (names the field)
-  if (!ModelAllowed(am) || !FrontendFits(any[0].dim, true, am, am->feat_dim, 0) || !StatsLenFits(stats_len, am->feat_dim, false)) return nullptr;
-  return CreateStream(am, StreamShape{"frontend_stream_create", true, global_stats, any.data(), max_streams, max_step_samples});
+  return CheckedStream(am, CreateRequest{global_stats, stats_len, false, max_streams, max_step_samples, true, !spec || !global_stats, spec, nullptr, nullptr, true, true});
 }
 
 pk_mi355_stream_t *pk_mi355_features_stream_create(pk_mi355_am_t *am, const float *global_stats41, int max_streams, int64_t max_step_frames) {
-  if (!ModelAllowed(am)) return nullptr;
-  if (global_stats41 && am->feat_dim != kNumBins) {
-    Fail(PK_MI355_E_INVALID, "the CMVN statistics are for %d-dim features, the model expects %d", kNumBins, am->feat_dim);
-    return nullptr;
-  }
-  return CreateStream(am, StreamShape{"features_stream_create", false, global_stats41, nullptr, max_streams, max_step_frames});
+  return CheckedStream(am, CreateRequest{global_stats41, 0, true, max_streams, max_step_frames, false, false, nullptr, nullptr, nullptr, true, true});
 }
 
 pk_mi355_stream_t *pk_mi355_features_stream_create_stats(pk_mi355_am_t *am, const float *global_stats, int stats_len, int max_streams,
                                                          int64_t max_step_frames) {
-  if (!ModelAllowed(am)) return nullptr;
-  if (!global_stats) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (!StatsLenFits(stats_len, am->feat_dim, false)) return nullptr;
-  return CreateStream(am, StreamShape{"features_stream_create", false, global_stats, nullptr, max_streams, max_step_frames});
+  return CheckedStream(am, CreateRequest{global_stats, stats_len, false, max_streams, max_step_frames, false, !global_stats, nullptr, nullptr, nullptr, true, true});
 }
 
-// pk_mi355_deltas_batch_create's checks with its texts (capi_batch.hip, CheckedBatch), and for every model that entry
-// accepts in its order; an online scorer refuses an f16 model besides, as every stream entry does.  What needs no
-// finalized model -- the null arguments and the deltas spec -- is said first, so that it is said without a device too.
 pk_mi355_stream_t *pk_mi355_deltas_stream_create(pk_mi355_am_t *am, const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
                                                  const float *global_stats, int stats_len, int max_streams, int64_t capacity) {
-  if (!am) { Fail(PK_MI355_E_STATE, "model not finalized"); return nullptr; }
-  if (!deltas || (frontend && !global_stats)) { Fail(PK_MI355_E_INVALID, "null argument"); return nullptr; }
-  if (pkdelta::CheckSpec(deltas)) return nullptr;                      // (names the field)
-  if (!ModelAllowed(am)) return nullptr;                               // f16; not finalized
-  const int D = am->feat_dim, order = deltas->order;
-  if (D % (order + 1) != 0) {
-    Fail(PK_MI355_E_INVALID, "deltas of order %d make %d blocks, which does not divide the model's %d-dim features", order, order + 1, D);
-    return nullptr;
-  }
-  const int Db = D / (order + 1);
-  std::vector<FrontendAnyTables> any(frontend ? 1 : 0);
-  if (frontend && BuildFrontendAnyTables(frontend, any.data())) return nullptr;      // (names the field)
-  if (frontend && !FrontendFits(any[0].dim, true, am, Db, order)) return nullptr;
-  if (global_stats && !StatsLenFits(stats_len, Db, true)) return nullptr;
-  StreamShape sh{"deltas_stream_create", frontend != nullptr, global_stats, frontend ? any.data() : nullptr, max_streams, capacity};
-  sh.deltas = deltas;
-  return CreateStream(am, sh);
+  return CheckedStream(am, CreateRequest{global_stats, stats_len, false, max_streams, capacity, frontend != nullptr, !deltas || (frontend && !global_stats),
+                                frontend, deltas, nullptr, true, false});
 }
 
-// pk_mi355_transform_batch_create's checks through the path it takes itself (pkhost::CheckCreate, `live`: the null
-// arguments and the specs before the model is looked at, an f16 model refused).
 pk_mi355_stream_t *pk_mi355_transform_stream_create(pk_mi355_am_t *am, const pk_mi355_transform_spec_t *transform,
                                                     const pk_mi355_deltas_spec_t *deltas, const pk_mi355_frontend_spec_t *frontend,
                                                     const float *global_stats, int stats_len, int max_streams, int64_t capacity) {
-  BatchRequest r{global_stats, stats_len, false, max_streams, capacity, frontend != nullptr, !transform || (frontend && !global_stats), frontend, deltas,
-                 transform};
-  r.live = true;
-  std::vector<FrontendAnyTables> any;
-  int Db = 0;
-  if (!CheckCreate(am, r, &any, &Db)) return nullptr;
-  StreamShape sh{"transform_stream_create", frontend != nullptr, global_stats, frontend ? any.data() : nullptr, max_streams, capacity};
-  sh.deltas = deltas; sh.xform = transform;
-  return CreateStream(am, sh);
+  return CheckedStream(am, CreateRequest{global_stats, stats_len, false, max_streams, capacity, frontend != nullptr, !transform || (frontend && !global_stats),
+                                frontend, deltas, transform, true, false});
 }
 
 int pk_mi355_stream_in_dim(const pk_mi355_stream_t *s) {

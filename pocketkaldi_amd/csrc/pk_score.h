@@ -6,11 +6,13 @@
 
 #include <functional>
 
+#include "pk_create.h"
 #include "pk_frontend.h"
 #include "pk_host.h"
 
 namespace pkmi {
 
+struct TransformStage;                      // pk_transform_kernel.h
 constexpr int kTailCap = kFrameLength;     // a carried tail holds at most 399 samples (fewer than one frame's 400)
 
 // One slot's share of a step (device array, one entry per slot taking part).
@@ -147,20 +149,25 @@ inline bool StatsLenFits(int stats_len, int dim, bool base) {
   return false;
 }
 
-// What a public create entry was handed.  stats41: 41 statistics by the entry's contract (a 40-dim model's; no
-// stats_len).  audio: the capacity is in samples and there is a front-end -- the spec's, or without one the reference's
-// 40 bins; else it is in frames.  null_arg: the entry found one of the pointers it needs null.  live: an online scorer's
-// entry (pk_mi355_transform_stream_create): an f16 model is refused besides, and the model is looked at only behind the
-// null arguments and the specs.
-struct BatchRequest {
-  const float *stats; int stats_len; bool stats41; int max_utts; int64_t capacity; bool audio, null_arg;
-  const pk_mi355_frontend_spec_t *frontend; const pk_mi355_deltas_spec_t *deltas;
-  const pk_mi355_transform_spec_t *xform = nullptr;      // pk_mi355_transform_batch_create's and _stream_create's
-  bool live = false;
-};
-// The argument checks of the create entries (capi_batch.hip).  False: refused, the text is pk_mi355_last_error's.  True:
-// *any holds the front-end spec's tables (empty without one), *base_dim the dimension in front of deltas and transform.
-bool CheckCreate(const pk_mi355_am *am, const BatchRequest &r, std::vector<pkmi::FrontendAnyTables> *any, int *base_dim);
+// The request (pk_create.h) through its checks, in the one order of DESIGN.md section 28 (capi_batch.hip); an entry
+// runs those its request gives rise to.  False: refused, the text is pk_mi355_last_error's.  True: *dims is filled.
+bool CheckCreate(const pk_mi355_am *am, const CreateRequest &r, CreateDims *dims);
+// Every way to a scorer behind the public entries' one-line request fillers: CheckCreate, then the object (capi_batch.hip,
+// capi_stream.hip).  Null: refused or failed, the text is pk_mi355_last_error's.
+pk_mi355_batch *CheckedBatch(pk_mi355_am *am, const CreateRequest &r);
+pk_mi355_stream *CheckedStream(pk_mi355_am *am, const CreateRequest &r);
+
+// What both recognizers load behind their files (capi_recognizer.hip): the model at `precision` and its statistics into
+// stats[kMaxCmvnStats] -- the reference's 41 without a front-end spec, else at the base dimension of (frontend, deltas,
+// xform) -- and in *r the audio request that hands them to a scorer of `units` and `capacity` samples (the caller says live).
+int LoadModelAndStats(const char *config_path, int precision, const pk_mi355_frontend_spec_t *frontend, const pk_mi355_deltas_spec_t *deltas,
+                      const pk_mi355_transform_spec_t *xform, int units, int64_t capacity, pk_mi355_am_t **am, float *stats, CreateRequest *r);
+
+// What both creates upload for the stages of a checked request (capi_batch.hip).  UploadDeltaScales: the spec's scale
+// table (pkdelta::BuildScales); the owner frees it.  UploadTransform: the spec's stage record (pk_transform_kernel.h), its
+// matrix (if it has one) transposed and padded (pkxf::PackTransposed) on the device; the owner frees mt.
+float *UploadDeltaScales(const pk_mi355_deltas_spec_t &deltas, CreateCheck &chk);
+pkmi::TransformStage UploadTransform(const pk_mi355_transform_spec_t &x, CreateCheck &chk);
 
 // ------------------------------------------------------------------ column shifts (capi_batch.hip)
 // Spans of rows (a multiple of four each) with one column shift -> one entry per group of four rows, for every row a
@@ -190,8 +197,8 @@ int CalibrateLoop(pk_mi355_am *am, const ExecBufs &e, const std::function<int()>
 
 // ------------------------------------------------------------------ the single-utterance entries' scorer (capi_batch.hip)
 constexpr int64_t kSingleChunk = 4096;   // frames per pass of pk_decodable_init, pk_mi355_am_calibrate and nnet_propagate
-// am->mu held: the model's one-utterance features batch (pk_mi355_features_batch_create's, without statistics, passes
-// of kSingleChunk rows), remade when `frames` do not fit.  Null: the create failed (its text is in pk_mi355_last_error).
+// am->mu held: the model's one-utterance features batch (a features request without statistics, passes of kSingleChunk
+// rows, through no check), remade when `frames` do not fit.  Null: the create failed (its text is in pk_mi355_last_error).
 pk_mi355_batch *SingleBatch(pk_mi355_am *am, int64_t frames);
 // pk_mi355_batch_calibrate behind its argument checks, for a caller that holds am->mu
 int BatchCalibrateLocked(pk_mi355_batch *b);
