@@ -87,7 +87,8 @@ enum {
 enum {
   PK_MI355_NNET_SIGMOID_LAYER = 6,
   PK_MI355_NNET_TANH_LAYER = 7,
-  PK_MI355_NNET_PNORM_LAYER = 8       /* the 2-norm of groups of in_dim / out_dim consecutive features */
+  PK_MI355_NNET_PNORM_LAYER = 8,      /* the 2-norm of groups of in_dim / out_dim consecutive features */
+  PK_MI355_NNET_TIME_SPLICE_LAYER = 9 /* y[t][c in_dim + d] = x[t + o_c][d]: a splice between hidden layers (TDNN) */
 };
 
 /* Error codes */
@@ -171,6 +172,22 @@ int pk_mi355_am_add_pnorm(pk_mi355_am_t *am, int in_dim, int out_dim);
  *              correctly rounded; an overflowed sum gives inf (Kaldi's rescaling fallback is not restated)
  * param = NULL and out_dim = in_dim for sigmoid and tanh.                                                          */
 int pk_mi355_layer_apply_host(int kind, const float *x, int rows, int in_dim, const float *param, int out_dim, float *out);
+/* PK_MI355_NNET_TIME_SPLICE_LAYER (F32 precision only): n strictly ascending frame offsets o_0 < ... < o_{n-1},
+ * 1 <= n <= 16, |o_c| <= 32, in_dim > 0 (PK_MI355_E_INVALID names the offending numbers).  in_dim -> n in_dim:
+ *   y[t][c in_dim + d] = x[t + o_c][d]      (a copy: every bit is kept)
+ * With lo = max(0, -o_0) and hi = max(0, o_{n-1}) per layer and Lh, Rh their sums over the network (Lh + Rh <= 128 at
+ * finalize), an utterance of T frames is scored as if its normalised features were extended by left_context + Lh copies
+ * of the first frame in front and right_context + Rh copies of the last behind; the hidden activations at the virtual
+ * frames outside [0, T) are computed from that extended input, every time-splice consumes lo frames on the left and hi
+ * on the right, and exactly the frames [0, T) reach the output.  The layer needs a Linear in front of it and one
+ * somewhere behind it.  Models with such layers run on the whole-utterance scorers (pk_decodable_init, the batch
+ * scorers, the recognizer); pk_mi355_nnet_propagate and the online scorers refuse them.                              */
+int pk_mi355_am_add_time_splice(pk_mi355_am_t *am, int in_dim, const int32_t *offsets, int n);
+/* Lh and Rh as finalize's walk of the network recorded them ((0, 0) before it, and for a model without time-splice layers). */
+int pk_mi355_am_time_context(const pk_mi355_am_t *am, int *left, int *right);
+/* The layer's rule on the host in its shrinking form, x[rows][in_dim] -> out[rows - lo - hi][n in_dim]: output row r is
+ * input frame r + lo.  PK_MI355_E_INVALID when rows <= lo + hi or the offsets break the limits above.  Needs no GPU. */
+int pk_mi355_time_splice_host(const float *x, int rows, int in_dim, const int32_t *offsets, int n, float *out);
 
 /* Arithmetic of the affine layers (set before finalize / read; default F32).
  *   F32   : fp32 MFMA, accumulation order of the reference's SGEMM -- bit-identical layers.

@@ -134,6 +134,12 @@ class AcousticModel {
     return Status::FromLast(pk_mi355_am_add_vector_layer(am_, kind, static_cast<int>(v.size()), v.data()));
   }
   Status AddPnorm(int in_dim, int out_dim) { return Status::FromLast(pk_mi355_am_add_pnorm(am_, in_dim, out_dim)); }
+  // PK_MI355_NNET_TIME_SPLICE_LAYER: in_dim -> offsets.size() * in_dim, y[t][c in_dim + d] = x[t + offsets[c]][d]
+  Status AddTimeSplice(int in_dim, const std::vector<int32_t> &offsets) {
+    return Status::FromLast(pk_mi355_am_add_time_splice(am_, in_dim, offsets.data(), static_cast<int>(offsets.size())));
+  }
+  // what the time-splice layers consume together on the left and on the right ((0, 0) without any; after Finalize)
+  Status TimeContext(int *left, int *right) const { return Status::FromLast(pk_mi355_am_time_context(am_, left, right)); }
   Status Finalize(const std::vector<float> &prior, int left_context, int right_context,
                   const std::vector<int32_t> &tid2pdf) {
     return Status::FromLast(pk_mi355_am_finalize(am_, prior.data(), static_cast<int>(prior.size()),

@@ -30,9 +30,13 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["PkError", "lib", "lib_path", "read_wav", "read_wave", "resample", "resample_table", "resample_num_output", "ResampleTable", "process_acoustic", "Fbank", "CMVN", "AcousticModel", "Decodable",
-           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "TransformSpec", "parse_transform", "transform_feats", "splice_feats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "ADD", "MUL", "SIGMOID", "TANH", "PNORM", "apply_layer", "write_nnet", "KINDS"]
+           "BatchScorer", "OnlineScorer", "Fst", "Decoder", "OnlineDecoder", "SymbolTable", "Recognizer", "OnlineRecognizer", "Result", "Segment", "NormSpec", "OnlineCmvnSpec", "parse_norm", "cmvn_normalize", "cmvn_online", "kaldi_cmvn_stats", "DeltaSpec", "parse_deltas", "delta_scales", "add_deltas", "TransformSpec", "parse_transform", "transform_feats", "splice_feats", "num_frames", "LINEAR", "RELU", "NORMALIZE", "SOFTMAX", "ADD", "MUL", "SIGMOID", "TANH", "PNORM", "TIME_SPLICE", "ONLINE_TIME_SPLICE_REFUSAL", "apply_layer", "time_splice", "write_nnet", "KINDS"]
 
 LINEAR, RELU, NORMALIZE, SOFTMAX = 0, 1, 2, 3
+TIME_SPLICE = 9                                      # a splice between hidden layers
+# what every online create says of a model with time-splice layers (csrc/capi_batch.hip: CheckCreate; recognize.py turns it
+# into a usage error; tests/test_gpu_time_splice.py holds the two texts together)
+ONLINE_TIME_SPLICE_REFUSAL = "time-splice layers are not supported by the online scorers yet"
 ADD, MUL, SIGMOID, TANH, PNORM = 4, 5, 6, 7, 8      # 4 and 5: the reference's numbers (nnet.h:18-19); 6 to 8: ours
 KINDS = ("fbank", "cmvn", "gemm", "tail", "other")
 
@@ -176,6 +180,7 @@ EXPORTS = [
     "pk_mi355_transform_stream_create", "pk_mi355_stream_in_dim", "pk_mi355_stream_transform_set_slot",
     "pk_mi355_transform_online_recognizer_load",
     "pk_mi355_am_add_vector_layer", "pk_mi355_am_add_pnorm", "pk_mi355_layer_apply_host",
+    "pk_mi355_am_add_time_splice", "pk_mi355_am_time_context", "pk_mi355_time_splice_host",
 ]
 
 
@@ -222,6 +227,9 @@ def lib():
     L.pk_mi355_am_add_vector_layer.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p]
     L.pk_mi355_am_add_pnorm.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pk_mi355_layer_apply_host.argtypes = [C.c_int, f32p, C.c_int, C.c_int, f32p, C.c_int, f32p]
+    L.pk_mi355_am_add_time_splice.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int]
+    L.pk_mi355_am_time_context.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pk_mi355_time_splice_host.argtypes = [f32p, C.c_int, C.c_int, i32p, C.c_int, f32p]
     L.pk_mi355_am_set_precision.argtypes = [C.c_void_p, C.c_int]
     L.pk_mi355_am_precision.argtypes = [C.c_void_p]
     L.pk_mi355_am_finalize.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
@@ -1089,6 +1097,7 @@ class AcousticModel:
 
     layers: list of ("linear", W[out][in], b[out]) | ("relu",) | ("normalize",) | ("softmax",)
             | ("sigmoid",) | ("tanh",) | ("pnorm", out_dim) | ("add", v[dim]) | ("mul", v[dim])   (f32 precision only)
+            | ("splice", [offsets])   a time-splice between hidden layers (f32 only; the whole-utterance scorers)
     prior:  pdf prior probabilities (the log is taken at load, am.cc:43)
     """
     _KIND = {"relu": RELU, "normalize": NORMALIZE, "softmax": SOFTMAX, "sigmoid": SIGMOID, "tanh": TANH}
@@ -1116,6 +1125,12 @@ class AcousticModel:
                         raise PkError("a p-norm layer needs a layer in front of it that states the width")
                     _check(L.pk_mi355_am_add_pnorm(self._h, width, int(l[1])))
                     width = int(l[1])
+                elif l[0] == "splice":
+                    if width <= 0:
+                        raise PkError("network must start with a linear layer when splicing")
+                    o = np.ascontiguousarray(l[1], dtype=np.int32).ravel()
+                    _check(L.pk_mi355_am_add_time_splice(self._h, width, o.ctypes.data_as(C.POINTER(C.c_int32)), o.shape[0]))
+                    width *= o.shape[0]
                 else:
                     _check(L.pk_mi355_am_add_layer(self._h, self._KIND[l[0]]))
             pr = None if prior is None else _f32(prior)
@@ -1190,6 +1205,12 @@ class AcousticModel:
     def input_dim(self):
         return lib().pk_mi355_am_input_dim(self._h)
 
+    def time_context(self):
+        """(Lh, Rh): the frames the time-splice layers consume together on the left and on the right; (0, 0) without any."""
+        l, r = C.c_int(), C.c_int()
+        _check(lib().pk_mi355_am_time_context(self._h, C.byref(l), C.byref(r)))
+        return l.value, r.value
+
     def transition_id_to_pdf_id(self, tid):
         return lib().pk_mi355_am_transition_to_pdf(self._h, int(tid))
 
@@ -1237,7 +1258,7 @@ class AcousticModel:
 
 
 _LAYER_KIND = {"linear": LINEAR, "relu": RELU, "normalize": NORMALIZE, "softmax": SOFTMAX, "add": ADD, "mul": MUL, "sigmoid": SIGMOID,
-               "tanh": TANH, "pnorm": PNORM}
+               "tanh": TANH, "pnorm": PNORM, "splice": TIME_SPLICE}
 
 
 def apply_layer(kind, x, param=None):
@@ -1260,10 +1281,25 @@ def apply_layer(kind, x, param=None):
     return y
 
 
+def time_splice(x, offsets):
+    """The time-splice layer's rule on the host in its shrinking form (pk_mi355_time_splice_host): rows x [T][dim] ->
+    [T - lo - hi][n dim], row r = the input frames r + lo + o_c side by side, every bit kept."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise PkCodeError(-1, "rows have shape %s, expected [T][dim]" % (x.shape,))
+    o = np.ascontiguousarray(offsets, dtype=np.int32).ravel()
+    T, D = x.shape
+    lo, hi = (max(0, -int(o[0])), max(0, int(o[-1]))) if o.size else (0, 0)
+    y = np.zeros((max(T - lo - hi, 0), max(o.size * D, 1)), np.float32)
+    _check_code(lib().pk_mi355_time_splice_host(_fp(x), T, D, o.ctypes.data_as(C.POINTER(C.c_int32)), o.shape[0], _fp(y)))
+    return y[:, :o.size * D]
+
+
 def write_nnet(path, layers):
     """The NNT0 model file of `layers` (AcousticModel's list; all nine kinds), as tool/convert_am.py of the reference
     writes kinds 0 to 3 and 5: LAY0 sections, a Linear's W as MAT0 of VEC0 rows and its bias, an add / mul layer's
-    vector as one VEC0, a p-norm's in_dim and out_dim as two int32 (in_dim: the width the layers in front leave)."""
+    vector as one VEC0, a p-norm's in_dim and out_dim as two int32 (in_dim: the width the layers in front leave), a
+    time-splice's in_dim, n and its n offsets as int32."""
     import struct
 
     def vec(v):
@@ -1287,6 +1323,12 @@ def write_nnet(path, layers):
                 raise PkError("a p-norm layer needs a layer in front of it that states the width")
             out.append(struct.pack("<ii", width, int(l[1])))
             width = int(l[1])
+        elif kind == TIME_SPLICE:
+            if width <= 0:
+                raise PkError("network must start with a linear layer when splicing")
+            o = [int(v) for v in l[1]]
+            out.append(struct.pack("<ii%di" % len(o), width, len(o), *o))
+            width *= len(o)
     with open(path, "wb") as f:
         f.write(b"".join(out))
 

@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libpk_mi355.so")
 STAMP = os.path.join(HERE, "libpk_mi355.buildhash")
 HIP_SOURCES = ["frontend.hip", "gemm.hip", "gemm_f16.hip", "tail.hip", "capi_model.hip", "capi_exec.hip", "capi_batch.hip",
                "capi_io.hip", "capi_collective.hip", "capi_recognizer.hip", "capi_online_recognizer.hip", "capi_decoder.hip", "capi_online_decoder.hip", "decode.hip",
-               "stream.hip", "capi_stream.hip", "resample.hip", "capi_resample.hip", "features.hip", "norm.hip", "delta.hip", "transform.hip", "layers.hip"]
+               "stream.hip", "capi_stream.hip", "resample.hip", "capi_resample.hip", "features.hip", "norm.hip", "delta.hip", "transform.hip", "layers.hip", "time_splice.hip"]
 HOST_SOURCES = ["pk_tables.cc", "pk_files.cc", "pk_ark.cc", "pk_norm.cc", "pk_delta.cc", "pk_plan.cc", "pk_transform.cc", "pk_layers.cc"]
 HEADERS = ["pk_kernels.h", "pk_tables.h", "pk_logf.h", "pk_expf.h", "pk_dma.h", "pk_tail_wave.h", "pk_wave.h", "pk_host.h", "pk_create.h", "pk_files.h", "pk_decode.h", "pk_score.h", "pk_f16_layout.h", "pk_resample.h", "pk_frontend.h", "pk_norm.h", "pk_norm_kernel.h", "pk_delta.h", "pk_delta_kernel.h", "pk_plan.h", "pk_transform.h", "pk_transform_kernel.h", "pk_layers.h", "libpk_mi355.map",
            os.path.join("..", "..", "include", "pk_mi355.h")]

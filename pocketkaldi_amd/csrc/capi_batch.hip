@@ -250,7 +250,7 @@ constexpr size_t kLayoutEntry = 3 * sizeof(int64_t) + sizeof(int32_t);   // byte
 
 // Frames and columns (every utterance with its context pads) against the batch's capacity.
 int FramesFit(const pk_mi355_batch *b, const int *frames, int num_utts) {
-  const int pad = b->core.am->left + b->core.am->right;
+  const int pad = ContextPad(b->core.am);
   int64_t raw = 0, col = 0;
   for (int u = 0; u < num_utts; ++u) {
     raw += frames[u];
@@ -270,7 +270,7 @@ int FramesFit(const pk_mi355_batch *b, const int *frames, int num_utts) {
 int SetLayoutFrames(pk_mi355_batch *b, const int *frames, const int *num_samples, int num_utts) {
   if (int rc = FramesFit(b, frames, num_utts)) return rc;
   ScorerCore &c = b->core;
-  const int pad = c.am->left + c.am->right;
+  const int pad = ContextPad(c.am);
   HIP_TRY(hipEventSynchronize(b->ev_layout));      // the last layout's upload has left the page-locked block
   const size_t n = (size_t)num_utts;
   size_t bytes = kLayoutEntry * n;                 // wave_off | raw_base | pad_base | T, then shift4 at the next multiple of 256
@@ -305,11 +305,11 @@ int SetLayoutFrames(pk_mi355_batch *b, const int *frames, const int *num_samples
   bool shifted = false;
   for (int u = 0; u < num_utts; ++u) {
     const int T = b->h_T[u];
-    b->h_out_base[u] = b->compact ? row : b->h_pad_base[u];
+    b->h_out_base[u] = b->compact ? row : b->h_pad_base[u] + c.am->time_left;      // (row pad_base + i is virtual frame i - Lh)
     if (T == 0) continue;
     b->total_rows = b->h_out_base[u] + T;
     row += RoundUp(T, 4);
-    spans.push_back({row, (int32_t)(b->h_pad_base[u] - b->h_out_base[u])});
+    spans.push_back({row, b->compact ? (int32_t)(b->h_pad_base[u] - b->h_out_base[u]) : 0});
     shifted = shifted || spans.back().shift != 0;
   }
   b->d_shift4 = nullptr;
@@ -433,12 +433,15 @@ const pk_mi355_am *BatchModel(const pk_mi355_batch *b) { return b->core.am; }
 
 void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats, int stats_dim, int units, int64_t max_frames,
                       int64_t max_rows, int64_t chunk_cap, CreateCheck &chk) {
-  const int pad = am->left + am->right;
+  const int pad = ContextPad(am);
   c->am = am; c->device = am->device; c->max_frames = max_frames;
   c->max_cols = RoundUp(max_rows + (int64_t)units * pad, kTileF16);
   c->chunk = std::min<int64_t>(chunk_cap, c->max_cols);
   c->zero_span = ZeroSpan(units, pad);
   c->ldy = RoundUp(c->max_cols, c->chunk) + 256 + c->zero_span;
+  // a time-splice model's last pass starts up to HaloLeft rows off a tile boundary and runs the virtual frames behind the
+  // last utterance: its last tile's padding rows read that much further
+  if (HasTimeSplice(am)) c->ldy += RoundUp(HaloLeft(am) + HaloRight(am) + kTile, 256);
   auto table = [&](auto **d, const void *h, size_t bytes) {
     chk(hipMalloc(d, bytes));
     if (chk.ok) chk(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
@@ -458,7 +461,7 @@ void CreateScorerCore(ScorerCore *c, pk_mi355_am *am, const float *global_stats,
   chk(hipMalloc(&c->d_yt, sizeof(float) * c->ldy * am->feat_dim));
   if (chk.ok) chk(hipMemset(c->d_yt, 0, sizeof(float) * c->ldy * am->feat_dim));   // the zero span at the end of feature row 0
   chk(hipMalloc(&c->d_ll, sizeof(float) * c->max_cols * am->num_pdfs));
-  if (chk.ok && AllocExec(am, c->chunk, &c->exec)) chk.ok = false;
+  if (chk.ok && AllocExec(am, ExecRows(am, c->chunk), &c->exec)) chk.ok = false;
 }
 
 void FreeScorerCore(ScorerCore *c) {
@@ -514,7 +517,7 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const CreateRequest &r, const Cre
   if (deltas) b->deltas = *deltas;
   b->is_xform = r.xform != nullptr;
   b->in_dim = dims.in_dim; b->base_dim = dims.base_dim;
-  const int pad = am->left + am->right;
+  const int pad = ContextPad(am);
   CreateCheck chk{b->features_only ? "batch_create_features" : "batch_create"};
   CreateScorerCore(&c, am, r.stats, b->base_dim, r.units, max_frames, max_frames, r.chunk_cap ? r.chunk_cap : PublicChunkCap(), chk);
   // Compact rows pad every utterance's rows to four but not its columns: the column shift of utterance u is the sum over
@@ -523,7 +526,8 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const CreateRequest &r, const Cre
   // the shift to UNSIGNED 32-bit lane offsets of scalar-base LDS-DMA (gemm.hip issue_splice, gemm_f16.hip xoff), where a
   // negative value addresses 4 GiB further on.  With fewer than three context frames there are next to no pad rows to
   // save anyway: such models keep row = column of Yt.
-  b->compact = pad >= 3;
+  // A time-splice model's rows include the virtual frames in front of and behind every utterance: row = column of Yt too.
+  b->compact = pad >= 3 && !HasTimeSplice(am);
   if (const char *e = getenv("PK_MI355_COMPACT_ROWS")) b->compact = b->compact && atoi(e) != 0;    // (A/B switch: 0 = row = column of Yt)
   const size_t lay_bytes = RoundUp(kLayoutEntry * r.units, 256) + (b->compact ? sizeof(int32_t) * Shift4Cap(c.max_cols) : 0);
   chk(hipHostMalloc(reinterpret_cast<void **>(&b->h_lay), lay_bytes, hipHostMallocDefault));
@@ -543,7 +547,7 @@ pk_mi355_batch *CreateBatch(pk_mi355_am_t *am, const CreateRequest &r, const Cre
     chk(hipStreamCreate(&b->stream2));
     chk(hipEventCreateWithFlags(&b->ev_front, hipEventDisableTiming));
     chk(hipEventCreateWithFlags(&b->ev_lane2, hipEventDisableTiming));
-    if (chk.ok && AllocExec(am, c.chunk, &b->exec2)) chk.ok = false;
+    if (chk.ok && AllocExec(am, ExecRows(am, c.chunk), &b->exec2)) chk.ok = false;
   }
   if (!chk.ok) { pk_mi355_batch_destroy(b); return nullptr; }
   return b;
@@ -573,6 +577,7 @@ bool CheckCreate(const pk_mi355_am *am, const CreateRequest &r, CreateDims *dims
       return false;
     }
     if (!am->finalized) { Fail(PK_MI355_E_STATE, "model not finalized"); return false; }
+    if (HasTimeSplice(am)) { Fail(PK_MI355_E_INVALID, "time-splice layers are not supported by the online scorers yet"); return false; }
   }
   const int D = am->feat_dim, order = r.deltas ? r.deltas->order : 0;
   // what the stages in front of the first layer start from: the model's features, or the rows a transform reads
@@ -1022,6 +1027,9 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
     return r == pkplan::kRawRows ? b->d_raw : r == pkplan::kFeatRows ? b->d_feats : r == pkplan::kDeltaRows ? b->d_delta
          : r == pkplan::kXformRows ? b->d_xform : b->d_uxform;
   };
+  // what the writers of Yt replicate in front of and behind an utterance: the first layer's context and the virtual
+  // frames of the time-splice layers
+  const int yl = am->left + am->time_left, yr = am->right + am->time_right;
   auto run = [&](int first, int last) {
     for (int k = first; k < last; ++k) {
       const pkplan::Step &st = plan.step[k];
@@ -1030,7 +1038,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
       switch (st.stage) {
         case pkplan::kFbank: LaunchFbank(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, out, c.stream); break;
         case pkplan::kFbankAny: LaunchFbankAny(b->wave_f32, b->wave_i16, lay, b->num_utts, b->max_T, c.d_tables, b->d_any, st.dim, out, c.stream); break;
-        case pkplan::kCmvn: LaunchCmvn(in, lay, b->num_utts, c.d_global, c.d_cmvn_tab, am->left, am->right, c.d_yt, c.ldy, c.stream); break;
+        case pkplan::kCmvn: LaunchCmvn(in, lay, b->num_utts, c.d_global, c.d_cmvn_tab, yl, yr, c.d_yt, c.ldy, c.stream); break;
         case pkplan::kCmvnChain: LaunchCmvnChain(in, lay, b->num_utts, st.dim, c.d_global, c.d_cmvn_tab, out, c.stream); break;
         case pkplan::kNorm:
           LaunchNorm(in, lay, b->num_utts, st.dim, mode, b->norm.norm_means != 0, b->norm.norm_vars != 0, b->d_spk_table, b->d_norm_stats, out, c.stream);
@@ -1044,7 +1052,7 @@ int pk_mi355_batch_score(pk_mi355_batch_t *b, float prob_scale, int sync) {
           LaunchTransform(in, lay, b->num_utts, b->max_T,
                           TransformStage{D, 0, 0, D, b->umat_affine, b->d_umats, (int64_t)(D + (b->umat_affine ? 1 : 0)) * pkxf::Ldo(D)}, out, c.stream);
           break;
-        case pkplan::kFeatureLayout: LaunchFeatureLayout(in, lay, b->num_utts, b->max_T, st.dim, am->left, am->right, c.d_yt, c.ldy, c.stream); break;
+        case pkplan::kFeatureLayout: LaunchFeatureLayout(in, lay, b->num_utts, b->max_T, st.dim, yl, yr, c.d_yt, c.ldy, c.stream); break;
       }
     }
   };
@@ -1226,7 +1234,7 @@ int pk_mi355_batch_fetch_cmvn(pk_mi355_batch_t *b, int utt, float *out) {
   if (T == 0) return 0;
   const int D = b->core.am->feat_dim;
   std::vector<float> tmp((size_t)D * T);
-  HIP_TRY(hipMemcpy2DAsync(tmp.data(), sizeof(float) * T, b->core.d_yt + b->h_pad_base[utt] + b->core.am->left,
+  HIP_TRY(hipMemcpy2DAsync(tmp.data(), sizeof(float) * T, b->core.d_yt + b->h_pad_base[utt] + b->core.am->left + b->core.am->time_left,
                            sizeof(float) * b->core.ldy, sizeof(float) * T, D, hipMemcpyDeviceToHost, b->core.stream));
   HIP_TRY(hipStreamSynchronize(b->core.stream));
   for (int t = 0; t < T; ++t)

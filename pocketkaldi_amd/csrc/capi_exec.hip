@@ -18,6 +18,10 @@ using namespace pkhost;
 namespace pkhost {
 
 struct ExecResult { const float *data = nullptr; int64_t ld = 0; int dim = 0; };   // where RunLayers left its result: frame-major rows
+// A pass of a time-splice model runs more rows than it owns: the log-likelihood tail covers rows
+// [skip, skip + rows) of the pass and writes them to tail_out[0 ..].  fuse: the tail may be fused into the last GEMM
+// (skip == 0; a walk of one pass).
+struct OwnedRows { int skip = 0, rows = 0; bool fuse = false; };
 
 int AllocExec(const pk_mi355_am *am, int64_t rows_cap, ExecBufs *e) {
   e->rows_cap = rows_cap;
@@ -114,7 +118,9 @@ int EvalRange(const pk_mi355_am *am, const ExecBufs *const *bufs, int nbufs) {
 int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t ldq,
               int splice_dim, int rows, bool want_tail, float scale, float *tail_out,
               int64_t tail_ld, hipStream_t stream, Timer *timer, ExecResult *res, const float *splice_zero = nullptr,
-              const int32_t *splice_shift = nullptr) {
+              const int32_t *splice_shift = nullptr, const OwnedRows *own = nullptr) {
+  // the rows the tail covers: all of the pass's, or the owned ones
+  const int tail_skip = own ? own->skip : 0, tail_rows = own ? own->rows : rows;
   const int rows_pad = (int)RoundUp(rows, kTile);
   if (splice_dim > 0 && !splice_zero) return Fail(PK_MI355_E_INVALID, "spliced input without a zero source");
   if (rows_pad > e.rows_cap) return Fail(PK_MI355_E_INVALID, "chunk larger than workspace");
@@ -181,10 +187,10 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
         }
         bool fused_tail = false;
         if (rows_out && want_tail && !fuse_relu && !am->softmax_reference && i + 2 == nl &&
-            am->layers[i + 1].type == PK_NNET_SOFTMAX_LAYER && am->knobs.wave_tail32) {
+            am->layers[i + 1].type == PK_NNET_SOFTMAX_LAYER && am->knobs.wave_tail32 && (!own || (own->fuse && own->skip == 0))) {
           g.tail_out = tail_out; g.tail_ld = tail_ld;
           g.tail_log_prior = blob + am->logprior_off; g.tail_scale = scale;
-          g.tail_n = D.N; g.tail_rows = rows; g.row_done = e.row_done;
+          g.tail_n = D.N; g.tail_rows = tail_rows; g.row_done = e.row_done;
           g.tail_walk = am->knobs.tail_walk;
           fused_tail = GemmFusesTail(g, am->knobs.fused_tail_min_tiles);
           if (!fused_tail) g.tail_out = nullptr;
@@ -283,6 +289,19 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
         cur = dst; cur_dim = L.out_dim; next_buf ^= 1;
         break;
       }
+      case PK_MI355_NNET_TIME_SPLICE_LAYER: {
+        // panels only (finalize: a Linear in front and one behind), into the other work buffer; the padding rows
+        // [n in_dim, RoundUp(n in_dim, kBK)) are written as zeros, as behind a p-norm.  Column j of the pass reads columns
+        // j + o_c of the same pass: the rows a pass owns find theirs inside it (WalkChunks runs the halo).
+        if (cur_splice) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
+        if (cur_rows) return Fail(PK_MI355_E_INVALID, "layer %d (time splice) has no linear layer behind it", i);
+        float *dst = bufs[next_buf];
+        Scoped t(timer, PK_MI355_K_OTHER, stream);
+        LaunchTimeSplice(cur, cur_ld, rows_pad, cur_dim, reinterpret_cast<const int32_t *>(blob + am->vec_off[i]), (int)L.offsets.size(), dst,
+                         e.rows_cap, (int)RoundUp(L.out_dim, kBK), stream);
+        cur = dst; cur_ld = e.rows_cap; cur_dim = L.out_dim; next_buf ^= 1;
+        break;
+      }
       case PK_NNET_SOFTMAX_LAYER: {
         if (cur_splice) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
         if (!cur_rows) to_rows();
@@ -290,8 +309,8 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
         Scoped t(timer, PK_MI355_K_TAIL, stream);
         if (final_layer && want_tail) {
           if (!(am->knobs.wave_tail32 && !am->softmax_reference &&
-                LaunchTailWave(cur, cur_ld, rows, cur_dim, blob + am->logprior_off, scale, tail_out, tail_ld, stream)))
-            LaunchTail(kTailSoftmaxLoglik, am->softmax_reference, cur, cur_ld, rows, cur_dim,
+                LaunchTailWave(cur + tail_skip * cur_ld, cur_ld, tail_rows, cur_dim, blob + am->logprior_off, scale, tail_out, tail_ld, stream)))
+            LaunchTail(kTailSoftmaxLoglik, am->softmax_reference, cur + tail_skip * cur_ld, cur_ld, tail_rows, cur_dim,
                        blob + am->logprior_off, scale, tail_out, tail_ld, stream);
           tail_done = true;
         } else {
@@ -312,7 +331,7 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
   }
   if (want_tail && !tail_done) {
     Scoped t(timer, PK_MI355_K_TAIL, stream);
-    LaunchTail(kTailLoglik, am->softmax_reference, cur, cur_ld, rows, cur_dim, blob + am->logprior_off,
+    LaunchTail(kTailLoglik, am->softmax_reference, cur + tail_skip * cur_ld, cur_ld, tail_rows, cur_dim, blob + am->logprior_off,
                scale, tail_out, tail_ld, stream);
   }
   if (res) { res->data = cur; res->ld = cur_ld; res->dim = cur_dim; }
@@ -396,9 +415,23 @@ int WalkChunks(const pk_mi355_am *am, const Operand &op, int64_t total_rows, int
                bool want_tail, float scale, float *out, Timer *timer) {
   const int D = am->feat_dim, N = am->num_pdfs;
   const bool f16 = IsF16(am->precision);
+  // A time-splice model: a pass owns rows [r0, r0 + rows) and runs HaloLeft rows in front of them
+  // and HaloRight behind, cut to [0, total_rows + Rh) -- the last utterance's virtual frames lie behind its last output
+  // row.  It writes the rows it owns and no others (neighbouring passes may run on two streams).
+  const bool halo = HasTimeSplice(am);
+  if (halo && (f16 || op.shift4)) return Fail(PK_MI355_E_INVALID, "internal: a time-splice model runs f32, row = column of Yt");
   for (int64_t r0 = 0; r0 < total_rows; r0 += chunk) {
     const int rows = (int)std::min<int64_t>(chunk, total_rows - r0);
     const Lane &l = lanes[r0 / chunk % nlanes];
+    if (halo) {
+      const int64_t first = std::max<int64_t>(0, r0 - HaloLeft(am));
+      const int64_t end = std::min<int64_t>(r0 + rows + HaloRight(am), total_rows + am->time_right);
+      const OwnedRows own{(int)(r0 - first), rows, total_rows <= chunk};
+      if (int rc = RunLayers(am, *l.exec, op.yt + first, op.ld, D, (int)(end - first), want_tail, scale, out + r0 * N, N, l.stream, timer, nullptr, op.zero,
+                             nullptr, &own))
+        return rc;
+      continue;
+    }
     const int32_t *shift4 = op.shift4 ? op.shift4 + r0 / 4 : nullptr;
     float *dst = out + r0 * N;
     const int rc = f16 ? RunLayersF16(am, *l.exec, op.y2 + r0 * 2 * D, 2 * D, rows, want_tail, scale, dst, N, l.stream, timer, nullptr, shift4)
@@ -502,6 +535,8 @@ extern "C" {
 
 int pk_mi355_nnet_propagate(pk_mi355_am_t *am, const pk_matrix_t *in, pk_matrix_t *out) {
   if (!am || !am->finalized) return Fail(PK_MI355_E_STATE, "model not finalized");
+  if (HasTimeSplice(am))      // (a spliced row's neighbours are not the splice of the neighbours)
+    return Fail(PK_MI355_E_INVALID, "propagate takes spliced rows without utterance edges; a model with time-splice layers needs a scorer");
   if (!in || !out || in->nrow != am->input_dim)
     return Fail(PK_MI355_E_INVALID, "input has %d rows, the network expects %d", in ? in->nrow : -1, am->input_dim);
   int rc = UseDevice(am->device);

@@ -35,6 +35,7 @@ int AmRead(pk_mi355_am_t *am, const char *nnet_path, const char *prior_path, con
     if (L.type == PK_NNET_LINEAR_LAYER) rc = pk_mi355_am_add_linear(am, L.in_dim, L.out_dim, L.W.data(), L.b.data());
     else if (L.type == PK_NNET_ADD_LAYER || L.type == PK_NNET_MUL_LAYER) rc = pk_mi355_am_add_vector_layer(am, L.type, L.in_dim, L.b.data());
     else if (L.type == PK_MI355_NNET_PNORM_LAYER) rc = pk_mi355_am_add_pnorm(am, L.in_dim, L.out_dim);
+    else if (L.type == PK_MI355_NNET_TIME_SPLICE_LAYER) rc = pk_mi355_am_add_time_splice(am, L.in_dim, L.offsets.data(), (int)L.offsets.size());
     else rc = pk_mi355_am_add_layer(am, L.type);
     if (rc) return rc;
   }

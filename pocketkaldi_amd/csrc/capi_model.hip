@@ -142,6 +142,25 @@ int pk_mi355_am_add_pnorm(pk_mi355_am_t *am, int in_dim, int out_dim) {
   return 0;
 }
 
+int pk_mi355_am_add_time_splice(pk_mi355_am_t *am, int in_dim, const int32_t *offsets, int n) {
+  if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "model is finalized");
+  if (int rc = pklayers::CheckTimeSplice(in_dim, offsets, n)) return rc;
+  HostLayer L;
+  L.type = PK_MI355_NNET_TIME_SPLICE_LAYER;
+  L.in_dim = in_dim;
+  L.out_dim = n * in_dim;
+  L.offsets.assign(offsets, offsets + n);
+  am->layers.push_back(std::move(L));
+  return 0;
+}
+
+int pk_mi355_am_time_context(const pk_mi355_am_t *am, int *left, int *right) {
+  if (!am) return Fail(PK_MI355_E_INVALID, "null model");      // ((0, 0) until finalize has walked the network)
+  if (left) *left = am->time_left;
+  if (right) *right = am->time_right;
+  return 0;
+}
+
 int pk_mi355_am_set_precision(pk_mi355_am_t *am, int precision) {
   if (!am || am->finalized) return Fail(PK_MI355_E_STATE, "set the precision before finalizing the model");
   if (precision != PK_MI355_PRECISION_F32 && precision != PK_MI355_PRECISION_F16X3 && precision != PK_MI355_PRECISION_F16)
@@ -196,8 +215,24 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   am->flops_per_frame = 0;
   size_t off = 0;
   int max_pad = 0;
+  int time_left = 0, time_right = 0, first_linear = -1, last_linear = -1;
+  for (int i = 0; i < (int)am->layers.size(); ++i)
+    if (am->layers[i].type == PK_NNET_LINEAR_LAYER) { last_linear = i; if (first_linear < 0) first_linear = i; }
   for (int i = 0; i < (int)am->layers.size(); ++i) {
     HostLayer &L = am->layers[i];
+    if (L.type == PK_MI355_NNET_TIME_SPLICE_LAYER) {
+      //  the layer exists in the panel layout between two affine layers only
+      if (first_linear < 0 || i < first_linear) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
+      if (L.in_dim != dim)
+        return Fail(PK_MI355_E_INVALID, "layer dimension mismatch: layer %d (time splice) is %d wide, the layers in front of it leave %d", i, L.in_dim, dim);
+      if (i > last_linear) return Fail(PK_MI355_E_INVALID, "layer %d (time splice) has no linear layer behind it", i);
+      const int n = (int)L.offsets.size();
+      time_left += pklayers::TimeLo(L.offsets.data(), n);
+      time_right += pklayers::TimeHi(L.offsets.data(), n);
+      dim = L.out_dim;
+      max_pad = std::max(max_pad, (int)RoundUp(L.out_dim, kTile));
+      continue;
+    }
     if (pklayers::IsVectorKind(L.type) || L.type == PK_MI355_NNET_PNORM_LAYER) {
       if (dim == 0) first_in = L.in_dim;
       else if (L.in_dim != dim)
@@ -246,6 +281,11 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   if (first_in % ctx != 0)
     return Fail(PK_MI355_E_INVALID, "input width %d is not a multiple of the context %d", first_in, ctx);
   am->feat_dim = first_in / ctx;
+  if (time_left + time_right > pklayers::kMaxTimeContext)
+    return Fail(PK_MI355_E_INVALID, "the time-splice layers consume %d frames on the left and %d on the right, at most %d together are supported",
+                time_left, time_right, pklayers::kMaxTimeContext);
+  am->time_left = time_left;
+  am->time_right = time_right;
   am->max_dim_pad = max_pad;
   am->logprior_off = off;
   off += RoundUp(dim, 4);
@@ -258,6 +298,9 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   am->vec_off.assign(am->layers.size(), 0);
   for (size_t i = 0; i < am->layers.size(); ++i)
     if (pklayers::IsVectorKind(am->layers[i].type)) { am->vec_off[i] = off; off += RoundUp(am->layers[i].in_dim, 4); }
+  // behind them the offsets of the time-splice layers, int32 words, each list padded to 4
+  for (size_t i = 0; i < am->layers.size(); ++i)
+    if (am->layers[i].type == PK_MI355_NNET_TIME_SPLICE_LAYER) { am->vec_off[i] = off; off += RoundUp(am->layers[i].offsets.size(), 4); }
   am->blob_floats = off;
 
   // pack: W^T zero-padded to [Kpad][Npad] (nnet.cc:16-17 keeps the transpose),
@@ -307,6 +350,9 @@ int pk_mi355_am_finalize(pk_mi355_am_t *am, const float *prior, int num_pdfs, in
   for (size_t i = 0; i < am->layers.size(); ++i)
     if (pklayers::IsVectorKind(am->layers[i].type))
       memcpy(blob.data() + am->vec_off[i], am->layers[i].b.data(), sizeof(float) * am->layers[i].b.size());
+  for (size_t i = 0; i < am->layers.size(); ++i)
+    if (am->layers[i].type == PK_MI355_NNET_TIME_SPLICE_LAYER)
+      memcpy(blob.data() + am->vec_off[i], am->layers[i].offsets.data(), sizeof(int32_t) * am->layers[i].offsets.size());
   if ((rc = UseDevice(am->device))) return rc;
   HIP_TRY(hipMalloc(&am->d_blob, sizeof(float) * off));
   HIP_TRY(hipMemcpy(am->d_blob, blob.data(), sizeof(float) * off, hipMemcpyHostToDevice));

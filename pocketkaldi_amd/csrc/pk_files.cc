@@ -74,6 +74,20 @@ int ReadNnet(const char *path, std::vector<HostLayer> *layers) {
         return Fail(PK_MI355_E_IO, "read_layer: p-norm dimensions expected in %s", path);
       if (L.in_dim <= 0 || L.out_dim <= 0 || L.in_dim % L.out_dim != 0)
         return Fail(PK_MI355_E_IO, "read_layer: p-norm input width %d is not a multiple of the output width %d (%s)", L.in_dim, L.out_dim, path);
+    } else if (L.type == PK_MI355_NNET_TIME_SPLICE_LAYER) {
+      int32_t n;
+      // (a kind 9 with nothing behind it keeps the words a file of an unknown kind is refused with)
+      if (!f.I32(&L.in_dim) || !f.I32(&n))
+        return Fail(PK_MI355_E_IO, "read_layer: unexpected layer type: %d without a time-splice layer's in_dim and offset count (%s)", L.type, path);
+      if (L.in_dim <= 0 || n < 1 || n > 16)
+        return Fail(PK_MI355_E_IO, "read_layer: time-splice layer of width %d with %d offsets (%s)", L.in_dim, n, path);
+      L.offsets.resize(n);
+      for (int c = 0; c < n; ++c) {
+        if (!f.I32(&L.offsets[c])) return Fail(PK_MI355_E_IO, "read_layer: %d time-splice offsets expected in %s", n, path);
+        if (L.offsets[c] < -32 || L.offsets[c] > 32 || (c > 0 && L.offsets[c] <= L.offsets[c - 1]))
+          return Fail(PK_MI355_E_IO, "read_layer: time-splice offset %d (index %d) is out of range or out of order (%s)", L.offsets[c], c, path);
+      }
+      L.out_dim = n * L.in_dim;
     } else if (L.type != PK_NNET_RELU_LAYER && L.type != PK_NNET_NORMALIZE_LAYER && L.type != PK_NNET_SOFTMAX_LAYER &&
                L.type != PK_MI355_NNET_SIGMOID_LAYER && L.type != PK_MI355_NNET_TANH_LAYER) {
       return Fail(PK_MI355_E_IO, "read_layer: unexpected layer type: %d (%s)", L.type, path);   // nnet.cc:106-127 knows 0..3

@@ -26,7 +26,8 @@ const char *LastError();
 // "VEC0" i32 bytes(=4n+4) i32 n, n x 4 bytes (vector.cc:393-425);
 // "MAT0" i32 8, i32 rows, i32 cols, rows x VEC0 (matrix.cc:288-319);
 // "NNT0" i32 4, i32 layers; "LAY0" i32 4, i32 type [+ MAT0 W, VEC0 b] (nnet.cc:80-147);
-// beyond the reference's reader: type 4 / 5 + VEC0 v, type 8 + i32 in_dim, i32 out_dim, types 6 / 7 bare
+// beyond the reference's reader: type 4 / 5 + VEC0 v, type 8 + i32 in_dim, i32 out_dim, types 6 / 7 bare;
+// (section 29) type 9 + i32 in_dim, i32 n, n x i32 offset
 
 struct FileBuf {
   std::vector<unsigned char> d;
@@ -88,6 +89,7 @@ struct HostLayer {
   int in_dim = 0, out_dim = 0;
   std::vector<float> W;   // [out][in]
   std::vector<float> b;   // the bias; kinds 4 and 5: the vector (in_dim = out_dim = its length).  Kind 8: the two dims only
+  std::vector<int32_t> offsets;   // kind 9: the frame offsets (out_dim = their count times in_dim)
 };
 
 int ReadNnet(const char *path, std::vector<HostLayer> *layers);

@@ -133,13 +133,15 @@ struct pk_mi355_am {
   int left = 0, right = 0, num_pdfs = 0;
   int input_dim = 0, output_dim = 0, feat_dim = 0;
   int max_dim_pad = 0;             // widest activation, rounded to the tile
+  int time_left = 0, time_right = 0;   // Lh, Rh: what the time-splice layers (kind 9) consume together (0, 0: none)
   std::vector<int32_t> tid2pdf;
   int32_t *d_tid2pdf = nullptr;    // device copy for the on-GPU gather
   std::vector<pkhost::DevLinear> lin;      // one per linear layer, in order
   float *d_blob = nullptr;
   size_t blob_floats = 0;
   size_t logprior_off = 0;
-  std::vector<size_t> vec_off;     // by layer index: where an add / mul layer's vector lies in the blob (float offset; others 0)
+  std::vector<size_t> vec_off;     // by layer index: where an add / mul layer's vector lies in the blob (float offset; others 0);
+                                   // a time-splice layer's offsets lie there likewise, as int32 words
   // f16x3 / f16: the operand exponents, int32 words INSIDE the blob (so the one broadcast carries them):
   // [w_exp of linear layer 0 .. n-1 | x_exp of the operand of linear layer 0 .. n-1 | 0].  The kernels read the
   // device words; h_exps mirrors them on the host (refreshed from the device after a broadcast).
@@ -159,6 +161,18 @@ struct pk_mi355_am {
 };
 
 namespace pkhost {
+
+// Time-splice models.  ContextPad: the columns of Yt an utterance takes beyond its frames (the
+// first layer's context and the virtual frames the time-splice layers consume).  HaloLeft / HaloRight: the rows a pass of
+// the layer stack runs in front of and behind the rows it owns, Lh and Rh rounded up to the four rows the first layer's
+// operand and its column shifts are grouped by.  ExecRows: the rows one pass's layer buffers hold for passes of `chunk`.
+inline bool HasTimeSplice(const pk_mi355_am *am) { return am->time_left + am->time_right > 0; }
+inline int ContextPad(const pk_mi355_am *am) { return am->left + am->right + am->time_left + am->time_right; }
+inline int HaloLeft(const pk_mi355_am *am) { return (int)RoundUp(am->time_left, 4); }
+inline int HaloRight(const pk_mi355_am *am) { return (int)RoundUp(am->time_right, 4); }
+inline int64_t ExecRows(const pk_mi355_am *am, int64_t chunk) {
+  return HasTimeSplice(am) ? RoundUp(chunk + HaloLeft(am) + HaloRight(am), kTile) : chunk;
+}
 
 // host mirror of the exponent words <- device (after a broadcast, or a write through the blob's device pointer); and back
 int RefreshExps(pk_mi355_am *am);

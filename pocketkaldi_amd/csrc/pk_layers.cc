@@ -1,7 +1,10 @@
 // pk_layers.cc -- the layer kinds 4 to 8 on the host (pk_layers.h): the checks of the two entries
 // that take a parameter, and the whole rule for a matrix of rows.  No HIP: g++ builds it, into the library and into
 // tests/cpp/layers_test.cc.
+// Also the time-splice layer's checks and host rule (kind 9; tests/cpp/time_splice_test.cc).
 #include "pk_layers.h"
+
+#include <string.h>
 
 #include <cmath>
 
@@ -57,9 +60,42 @@ void ApplyHost(int kind, const float *x, int rows, int in_dim, const float *para
     }
 }
 
+int CheckTimeSplice(int in_dim, const int32_t *offsets, int n) {
+  if (in_dim <= 0) return Fail(PK_MI355_E_INVALID, "bad time-splice layer (in_dim %d)", in_dim);
+  if (n < 1 || n > kMaxTimeOffsets || !offsets)
+    return Fail(PK_MI355_E_INVALID, "time-splice layer: %d offsets, between 1 and %d are allowed", n, kMaxTimeOffsets);
+  for (int c = 0; c < n; ++c) {
+    if (offsets[c] < -kMaxTimeOffset || offsets[c] > kMaxTimeOffset)
+      return Fail(PK_MI355_E_INVALID, "time-splice layer: offset %d (index %d) is outside [-%d, %d]", offsets[c], c, kMaxTimeOffset, kMaxTimeOffset);
+    if (c > 0 && offsets[c] <= offsets[c - 1])
+      return Fail(PK_MI355_E_INVALID, "time-splice layer: the offsets must ascend strictly, offset %d (index %d) follows %d", offsets[c], c,
+                  offsets[c - 1]);
+  }
+  return 0;
+}
+
+void TimeSpliceHost(const float *x, int rows, int in_dim, const int32_t *offsets, int n, float *out) {
+  const size_t D = (size_t)in_dim;
+  const int lo = TimeLo(offsets, n), hi = TimeHi(offsets, n);
+  for (int r = 0; r < rows - lo - hi; ++r)
+    for (int c = 0; c < n; ++c)
+      memcpy(out + ((size_t)r * n + c) * D, x + (size_t)(r + lo + offsets[c]) * D, sizeof(float) * D);   // (bits, not values)
+}
+
 }  // namespace pklayers
 
 extern "C" {
+
+int pk_mi355_time_splice_host(const float *x, int rows, int in_dim, const int32_t *offsets, int n, float *out) {
+  using namespace pklayers;
+  if (int rc = CheckTimeSplice(in_dim, offsets, n)) return rc;
+  const int lo = TimeLo(offsets, n), hi = TimeHi(offsets, n);
+  if (rows <= lo + hi)
+    return pkhost::Fail(PK_MI355_E_INVALID, "time splice: %d rows, the offsets consume %d on the left and %d on the right", rows, lo, hi);
+  if (!x || !out) return pkhost::Fail(PK_MI355_E_INVALID, "null argument");
+  TimeSpliceHost(x, rows, in_dim, offsets, n, out);
+  return 0;
+}
 
 int pk_mi355_layer_apply_host(int kind, const float *x, int rows, int in_dim, const float *param, int out_dim, float *out) {
   using namespace pklayers;

@@ -3,6 +3,7 @@
 // pk_mi355_layer_apply_host, and tests/cpp/layers_test.cc) and by layers.hip (the kernels).  Plain C++ unless hipcc
 // compiles it; the launchers at the end exist for hipcc only.  Kept out of pk_kernels.h: that header is part of the hash
 // that ties the GEMM profiles to the GEMM's sources.  Internal, like pk_host.h.
+// Below them the time-splice layer, kind 9: its limits, its host rule and its launcher (time_splice.hip).
 //
 // The definitions are the project's.  They follow Kaldi's CPU code as recalled (MatrixBase::Sigmoid, MatrixBase::Tanh,
 // VectorBase::Norm(2.0)), whose double literals promote the arithmetic; they have not been compared with a Kaldi binary.
@@ -69,6 +70,19 @@ int CheckPnorm(int in_dim, int out_dim);
 // the rule for rows [rows][in_dim] -> [rows][out_dim] (arguments checked by the caller)
 void ApplyHost(int kind, const float *x, int rows, int in_dim, const float *param, int out_dim, float *out);
 
+// ------------------------------------------------------------------ the time-splice layer, kind 9
+// y[t][c in_dim + d] = x[t + o_c][d] for strictly ascending offsets o_0 < ... < o_{n-1}: a copy, every bit kept.
+constexpr int kMaxTimeOffsets = 16;      // n
+constexpr int kMaxTimeOffset = 32;       // |o_c|
+constexpr int kMaxTimeContext = 128;     // Lh + Rh of a network
+// what one layer consumes on the left and on the right
+inline int TimeLo(const int32_t *offsets, int n) { return n > 0 && offsets[0] < 0 ? -offsets[0] : 0; }
+inline int TimeHi(const int32_t *offsets, int n) { return n > 0 && offsets[n - 1] > 0 ? offsets[n - 1] : 0; }
+// what pk_mi355_am_add_time_splice refuses, in its words
+int CheckTimeSplice(int in_dim, const int32_t *offsets, int n);
+// the shrinking rule for rows [rows][in_dim] -> [rows - lo - hi][n in_dim] (arguments checked by the caller)
+void TimeSpliceHost(const float *x, int rows, int in_dim, const int32_t *offsets, int n, float *out);
+
 }  // namespace pklayers
 
 #if defined(__HIPCC__)
@@ -89,6 +103,13 @@ void LaunchLayerElementwise(int kind, float *x, int frames, int dim, int64_t str
 // rows against zero weights, and 0 * NaN is NaN: what an earlier call left there must not survive).
 void LaunchPnorm(const float *x, int frames, int in_dim, int out_dim, int64_t stride_f, int64_t stride_d, float *out,
                  int64_t out_ld, int out_pad, hipStream_t stream);
+
+// The time-splice layer on feature-major panels (time_splice.hip), never in place: panel row c in_dim + d, column j of
+// `out` is x[d][clamp(j + o_c, 0, rows - 1)] for j < rows (the clamp only keeps the read inside the pass's buffer: no
+// clamped column reaches a valid output row).  offsets_dev: the n offsets on the device.  Rows [n in_dim, out_pad) of
+// `out` are written as zeros, for PnormPanelKernel's reason.
+void LaunchTimeSplice(const float *x, int64_t ld, int rows, int in_dim, const int32_t *offsets_dev, int n, float *out,
+                      int64_t out_ld, int out_pad, hipStream_t stream);
 
 }  // namespace pkmi
 #endif

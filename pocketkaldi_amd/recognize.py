@@ -467,6 +467,8 @@ def main(argv):
         return usage()
     except (pk.PkError, OSError, ValueError) as e:
         print("pocketkaldi: %s" % e)                     # main.cc:10-15
+        if "--online" in flags and pk.ONLINE_TIME_SPLICE_REFUSAL in str(e):
+            return usage()                               # (the model file says so only once it is loaded: leave out --online)
         return 1
     emit(files, results, names, "--ctm" in flags, pieces if endpoint else None)
     if rec is not None:
