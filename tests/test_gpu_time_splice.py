@@ -25,10 +25,6 @@ F32 = np.float32
 ONLINE_REFUSAL = "time-splice layers are not supported by the online scorers yet"
 
 
-def identity(D):
-    return ("linear", np.eye(D, dtype=F32), np.zeros(D, F32))
-
-
 def assert_rows(got, want, what):
     assert len(got) == len(want)
     for u, (a, b) in enumerate(zip(got, want)):
@@ -54,10 +50,7 @@ def score(am, feats, fs=None, scale=TC.SCALE):
 
 # ---------------------------------------------------------------- a. the kind alone
 
-def alone_layers(D, offsets, seed):
-    rng = np.random.default_rng([0xA10E, D, seed])
-    n = len(offsets) * D
-    return [identity(D), ("splice", offsets), ("linear", (rng.standard_normal((5, n)) / np.sqrt(n)).astype(F32), (rng.standard_normal(5) * 0.1).astype(F32))]
+alone_layers = TC.alone_layers
 
 
 @pytest.mark.parametrize("offsets", [[0], [-1, 0, 1], [-3, 3], [0, 2], [-2, 1]], ids=lambda o: "o" + "_".join(str(v) for v in o))

@@ -1,6 +1,7 @@
 """The time-splice layer, kind 9, without a GPU: the host rule against the numpy restatement of
 tests/time_splice_cases.py bit for bit, every refusal that needs no device with its text, the right edge rule against the
-wrong one on the GPU tests' inputs, and the model file through the reader."""
+wrong one on the GPU tests' inputs (every batch of tests/test_gpu_time_splice_limits.py included, with the places its sweep
+of the pass boundary visits), and the model file through the reader."""
 import ctypes as C
 import struct
 
@@ -224,6 +225,84 @@ def test_right_and_wrong_edge_rule_differ():
             assert differ[:TC.LH].all() and differ[T - TC.RH:].all() and not differ[TC.LH:T - TC.RH].any(), T
             told += 1
     assert told >= 3
+
+
+def test_python_refusals_at_the_limits():
+    """What tests/test_gpu_time_splice_limits.py runs at the limits, one step beyond them, through pk.AcousticModel."""
+    lin = ("linear", np.zeros((8, 8), np.float32), np.zeros(8, np.float32))
+    wide = ("linear", np.zeros((8, 16), np.float32), np.zeros(8, np.float32))
+    with pytest.raises(pk.PkError, match="17 offsets, between 1 and 16"):
+        pk.AcousticModel([lin, ("splice", list(range(17))), lin], prior=np.ones(8, np.float32))
+    for bad, text in (([0, 33], r"offset 33 \(index 1\) is outside \[-32, 32\]"), ([-33, 0], r"offset -33 \(index 0\) is outside \[-32, 32\]")):
+        with pytest.raises(pk.PkError, match=text):
+            pk.AcousticModel([lin, ("splice", bad), wide], prior=np.ones(8, np.float32))
+    deep = [lin] + [("splice", [-32, 32]), wide] * 2 + [("splice", [0, 1]), wide]
+    with pytest.raises(pk.PkError, match="consume 64 frames on the left and 65 on the right, at most 128 together"):
+        pk.AcousticModel(deep, prior=np.ones(8, np.float32))
+    for precision in ("f16x3", "f16"):                 # any f16 precision, at the largest context too
+        with pytest.raises(pk.PkError, match=r"f16x3 / f16 precision supports \(Linear \[ReLU\] \[Normalize\]\)\+ \[Softmax\] networks only"):
+            pk.AcousticModel(deep[:5], prior=np.ones(8, np.float32), precision=precision)
+
+
+# ---------------------------------------------------------------- 1c'. the cases of the limits, the pass edges and the audio path
+
+@pytest.fixture(scope="module")
+def limit_batches():
+    return list(TC.limit_batches())
+
+
+def test_limit_cases_tell_the_edge_rules_apart(limit_batches):
+    """Every batch of tests/test_gpu_time_splice_limits.py: the right and the wrong rule differ in at least one of the
+    first Lh and one of the last Rh rows of every utterance longer than the context; the finite cases are finite, and in
+    the designed ones only the rows a non-finite frame reaches are NaN.  The "alone" form is the exception it has to be:
+    an identity in front of one splice, no first-layer context -- there the two rules are the same function, and the
+    case is about the copy."""
+    told = {}
+    for name, layers, prior, left, right, feats, designed in limit_batches:
+        Lh, Rh = TC.time_context(layers)
+        for f in feats:
+            T = f.shape[0]
+            want = TC.loglik_time(layers, f, prior, left, right, TC.SCALE)
+            assert want.shape == (T, len(prior)), name
+            if designed:
+                allowed = TC.nan_rows_allowed(layers, f, left, right)
+                nan = np.isnan(want).any(axis=1)
+                assert not (nan & ~allowed).any() and np.isfinite(want[~nan]).all(), (name, T)
+                assert T < max(TC.LIMIT_T) or (nan.any() and (~nan).any()), (name, T)      # the longest has rows of both kinds
+            else:
+                assert np.isfinite(want).all(), (name, T)
+            if T == 0:
+                continue
+            same = TC.same_rows(want, TC.loglik_wrong(layers, f, prior, left, right, TC.SCALE))
+            if name.startswith("alone"):
+                assert same.all(), (name, T)
+            elif T > Lh + Rh:
+                assert not same[:Lh].all() and not same[T - Rh:].all(), (name, T)
+                told[name] = told.get(name, 0) + 1
+    assert all(name.startswith("alone") or told.get(name, 0) >= 1 for name, *_ in limit_batches), told
+
+
+def test_the_sweep_visits_every_place_at_the_edge():
+    """Position 256, the first of the second pass, lies in turn on every kind of row and of column between utterance 0's
+    last frames and utterance 1's first, derived from the layout section 29 documents."""
+    ctx = (TC.MS_LEFT, TC.MS_RIGHT, TC.MS_LH, TC.MS_RH)
+    assert TC.time_context(TC.multisplice()[0]) == (TC.MS_LH, TC.MS_RH) == (11, 8)
+    seen = [TC.place([T0] + TC.SWEEP_REST, *ctx, TC.PASS_ROWS) for T0 in TC.sweep_lengths(*ctx)]
+    assert len(seen) == 33 and all(T0 + sum(TC.SWEEP_REST) < 600 for T0 in TC.sweep_lengths(*ctx))
+    rows = [(u, r) for u, r, _ in seen]
+    cols = [(u, c) for u, _, c in seen]
+    assert rows.count((0, "frame")) == 4 and rows.count((0, "right virtual")) == 8 and rows.count((0, "no frame")) == 4      # (3 before the last, and it)
+    assert rows.count((1, "left virtual")) == 11 and rows.count((1, "frame")) == 6
+    assert cols.count((0, "frame")) == 6 and cols.count((0, "right copy")) == 10 and cols.count((1, "left copy")) == 13 and cols.count((1, "frame")) == 4
+    # the ends of the batch: the last frame's row on the last / first row of a tile, from row 0 and from the last pass's first row
+    pad = sum(ctx)
+    origin = TC.PASS_ROWS - 12                         # HaloLeft = RoundUp(11, 4)
+    for name, lengths in TC.end_batches(*ctx).items():
+        last = lengths[0] + pad + TC.MS_LH + lengths[1] - 1
+        assert last >= TC.PASS_ROWS, name
+        assert TC.place(lengths, *ctx, last)[:2] == (1, "frame") and TC.place(lengths, *ctx, last + 1)[:2] == (1, "right virtual")
+        at = (last - (origin if name.endswith("pass") else 0)) % TC.TILE
+        assert at == (TC.TILE - 1 if name.startswith("last") else 0), (name, last)
 
 
 # ---------------------------------------------------------------- 1d. the model file
