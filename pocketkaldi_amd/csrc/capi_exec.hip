@@ -219,6 +219,12 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
           }
           LaunchGemm(g, stream);
         }
+        // A panel's padding rows [N, RoundUp(N, kBK)) are what the zero rows of the padded weights made of the frame: 0 for
+        // a finite frame, 0 * inf = NaN for one that holds an infinite value -- and the next GEMM's k-padding reads them
+        // (against zero weights: 0 * NaN is NaN, in every output of that frame, where the reference has the real
+        // features' +-inf).  They are written as zeros, as behind a p-norm.  No width of the BASELINE models has such rows.
+        if (!rows_out && D.N % kBK != 0)
+          HIP_TRY(hipMemsetAsync(dst + (int64_t)D.N * e.rows_cap, 0, sizeof(float) * (size_t)(RoundUp(D.N, kBK) - D.N) * e.rows_cap, stream));
         cur = dst; cur_ld = g.ldo; cur_rows = rows_out; cur_splice = false; cur_dim = D.N;
         next_buf ^= 1;
         if (fuse_relu) ++i;
@@ -256,8 +262,8 @@ int RunLayers(const pk_mi355_am *am, const ExecBufs &e, const float *q0, int64_t
       case PK_MI355_NNET_SIGMOID_LAYER:
       case PK_MI355_NNET_TANH_LAYER: {
         // in place on the dim real features.  A panel's padding rows [dim, RoundUp(dim, kBK)) are
-        // not touched: they stay what the GEMM in front wrote (zeros for finite frames), and the next GEMM meets them
-        // with zero weights.
+        // not touched: they stay the zeros written behind the GEMM in front, and the next GEMM meets them with zero
+        // weights.
         if (cur_splice) return Fail(PK_MI355_E_INVALID, "network must start with a linear layer when splicing");
         if (cur == e.in) {                 // never modify inputs in place: copy first
           float *dst = bufs[next_buf];

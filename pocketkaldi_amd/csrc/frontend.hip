@@ -15,6 +15,7 @@
 // between passes.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "pk_dma.h"
@@ -930,6 +931,15 @@ void LaunchLogfTest(const float *x, int n, const FrontendTables *d_tables, float
   hipLaunchKernelGGL(LogfTestKernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, d_tables, out);
 }
 
+// The fbank kernels take utterance blockIdx.y: a batch goes out in slices of at most 65 535 utterances, the limit of
+// grid.y.  The per-utterance arrays are offset by the slice's first utterance; their entries (wave_off, raw_base) are
+// absolute, so the kernels see no difference.
+constexpr int kMaxFbankGridY = 65535;
+
+static UttLayout UttSlice(const UttLayout &u, int at) {
+  return UttLayout{u.wave_off + at, u.num_frames + at, u.raw_base + at, u.pad_base + at};
+}
+
 void LaunchFbank(const float *wave_f32, const int16_t *wave_i16, const UttLayout &utts,
                  int num_utts, int max_frames, const FrontendTables *d_tables, float *raw,
                  hipStream_t stream) {
@@ -940,11 +950,15 @@ void LaunchFbank(const float *wave_f32, const int16_t *wave_i16, const UttLayout
   if (gx < 1) gx = 1;
   const int need = (max_frames + kFbankWaves - 1) / kFbankWaves;
   if (gx > need) gx = need;
-  dim3 grid(gx, num_utts), block(kWave * kFbankWaves);
-  if (wave_i16)
-    hipLaunchKernelGGL(FbankKernel<int16_t>, grid, block, 0, stream, wave_i16, utts, d_tables, raw);
-  else
-    hipLaunchKernelGGL(FbankKernel<float>, grid, block, 0, stream, wave_f32, utts, d_tables, raw);
+  const dim3 block(kWave * kFbankWaves);
+  for (int at = 0; at < num_utts; at += kMaxFbankGridY) {     // (one launch, today's grid, up to 65 535 utterances)
+    const dim3 grid(gx, std::min(kMaxFbankGridY, num_utts - at));
+    const UttLayout lay = UttSlice(utts, at);
+    if (wave_i16)
+      hipLaunchKernelGGL(FbankKernel<int16_t>, grid, block, 0, stream, wave_i16, lay, d_tables, raw);
+    else
+      hipLaunchKernelGGL(FbankKernel<float>, grid, block, 0, stream, wave_f32, lay, d_tables, raw);
+  }
 }
 
 void LaunchFbankAny(const float *wave_f32, const int16_t *wave_i16, const UttLayout &utts, int num_utts, int max_frames,
@@ -954,11 +968,15 @@ void LaunchFbankAny(const float *wave_f32, const int16_t *wave_i16, const UttLay
   if (gx < 1) gx = 1;
   const int need = (max_frames + kFbankWaves - 1) / kFbankWaves;
   if (gx > need) gx = need;
-  dim3 grid(gx, num_utts), block(kWave * kFbankWaves);
-  if (wave_i16)
-    hipLaunchKernelGGL(FbankAnyKernel<int16_t>, grid, block, 0, stream, wave_i16, utts, d_tables, d_any, raw);
-  else
-    hipLaunchKernelGGL(FbankAnyKernel<float>, grid, block, 0, stream, wave_f32, utts, d_tables, d_any, raw);
+  const dim3 block(kWave * kFbankWaves);
+  for (int at = 0; at < num_utts; at += kMaxFbankGridY) {
+    const dim3 grid(gx, std::min(kMaxFbankGridY, num_utts - at));
+    const UttLayout lay = UttSlice(utts, at);
+    if (wave_i16)
+      hipLaunchKernelGGL(FbankAnyKernel<int16_t>, grid, block, 0, stream, wave_i16, lay, d_tables, d_any, raw);
+    else
+      hipLaunchKernelGGL(FbankAnyKernel<float>, grid, block, 0, stream, wave_f32, lay, d_tables, d_any, raw);
+  }
 }
 
 void LaunchCmvn(const float *raw, const UttLayout &utts, int num_utts, const float *d_global41,

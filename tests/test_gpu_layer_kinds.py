@@ -66,6 +66,26 @@ def test_each_kind_alone(case):
         am.close()
 
 
+def test_infinite_features_in_front_of_narrow_hidden_layers():
+    """Hidden widths 4 and 6, no multiples of 16: the panels have padding rows, which the zero rows of the padded weights
+    make 0 * inf = NaN for a frame that holds an infinite feature.  The next affine layer's k-padding must not meet them:
+    the frame's real features are +-inf and 0, and the reference's logits are +-inf, not NaN in every output."""
+    import grid_walk_cases as GW
+    layers, prior = GW.row_layers()
+    x = LC.designed(67, 2, 11)
+    assert np.isinf(x).sum() == 2
+    want = LC.loglik(layers, x, prior, 0, 0, 0.1)
+    assert (np.isinf(x).any(axis=1) & np.isfinite(want).all(axis=1)).any()      # tanh saturates: such a row is finite, not NaN
+    am = pk.AcousticModel(layers, prior).set_softmax("reference")
+    try:
+        d = pk.Decodable(am, 0.1, x)
+        got = d.log_prob()
+        d.destroy()
+        assert LC.same(got, want)
+    finally:
+        am.close()
+
+
 # ---------------------------------------------------------------- the stack
 
 @pytest.fixture(scope="module")
